@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: MB/s of raw bytes encoded by the Unigram encode hot path.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 One "step" = one pass of Tokenizer::encode_ordinary_batch (reference
 src/tokenizer.rs:114-123 over src/model.rs:59-129) over one resident batch of
@@ -54,7 +54,12 @@ def main() -> None:
     ap.add_argument("--estep-steps", type=int, default=3)
     ap.add_argument("--no-distinct", action="store_true", help="skip the encode passes with every token its own score")
     ap.add_argument("--master-port", type=int, default=29533)
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write rank 0's result of the last one (token ids, per-sample offsets) "
+                         "as DIR/<name>.npy; see dump_outputs()")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # Launched bare (`python bench.py --gpus N`): start the N ranks ourselves, one fresh process per
@@ -133,26 +138,32 @@ def main() -> None:
             dist.barrier()
         torch.cuda.synchronize(dev)
 
-    def step():
+    def step(keep: bool = False):
         res = model.encode_corpus(corpus)  # synchronous: returns when ids are complete in HBM
         n_tok = res.num_tokens
+        if keep:  # --dump-outputs: the result outlives the timed region
+            return n_tok, res
         res.free()
-        return n_tok
+        return n_tok, None
 
     n_tokens = 0
     for _ in range(args.warmup):
-        n_tokens = step()
+        n_tokens, _ = step()
     kernel_ms: dict[str, float] = {}
+    dump = args.dump_outputs is not None and rank == 0
     sync_all()
     t_start = time.perf_counter()
-    for _ in range(args.steps):
-        n_tokens = step()
+    for i in range(args.steps):
+        n_tokens, last = step(keep=dump and i == args.steps - 1)
         for k, v in model.last_kernel_times().items():  # hipEvents on the model's stream
             kernel_ms[k] = kernel_ms.get(k, 0.0) + v
     sync_all()
     elapsed = time.perf_counter() - t_start
     alg_bytes = model.last_algorithmic_bytes()
     corun_cus = model.last_encode_corun_cus()  # (of the timed passes: the host-to-host leg below encodes 256 MiB chunks)
+    if last is not None:
+        dump_outputs(args.dump_outputs, last.ids(), last.offsets())
+        last.free()
 
     from tokengeex_amd import dist as tdist
     max_elapsed, tot_bytes, tot_tokens = tdist.aggregate_timing(elapsed, n_bytes, n_tokens, dist, coll_dev)
@@ -344,6 +355,23 @@ def main() -> None:
 
     if dist is not None:
         dist.destroy_process_group()
+
+
+def dump_outputs(out_dir: str, ids, offs) -> None:
+    """--dump-outputs: what encode_corpus returned to its caller in the last timed step — token ids (uint32[T]) and
+    per-sample offsets into them (uint64[S + 1]) — as out_dir/ids.npy (float32: ids < 2**24 are exact) and
+    out_dir/offsets.npy (float64).  An array longer than its cap is replaced by a fixed seeded sample of its entries
+    in ascending position order, the positions in out_dir/<name>_index.npy (float64): at most 52 MiB in all.  The
+    inputs are seeded, so two builds that compute the same result write the same files."""
+    import numpy as np
+    assert ids.size == 0 or int(ids.max()) < 1 << 24, "ids beyond float32's exact integers"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a, dtype, cap in (("ids", ids, np.float32, 3 << 20), ("offsets", offs, np.float64, 1 << 20)):
+        if a.size > cap:
+            idx = np.unique(np.random.default_rng(0).integers(0, a.size, cap))
+            np.save(os.path.join(out_dir, f"{name}_index.npy"), idx.astype(np.float64))
+            a = a[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a.astype(dtype))
 
 
 def cpu_baseline(toks, scores, flat, offs, model, target_seconds: float) -> dict:

@@ -4,7 +4,7 @@
  * This is the drop-in boundary: a Rust `extern "C"` block, a
  * C++ host or Python/ctypes bind exactly these symbols.  Plain pointers and
  * sizes only; no exceptions or unwinding cross it; every function returns a
- * tgx_status.  All reference citations are relative to /root/reference.
+ * tgx_status.  All reference citations are relative to the TokenGeeX source tree.
  *
  * Batch format (replaces Vec<&str> / &[&str] of the reference's batch loops):
  *   text  : uint8_t[N]      all samples' bytes back to back (already processed

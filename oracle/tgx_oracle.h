@@ -5,7 +5,7 @@
  * baseline ("port").  Nothing under tokengeex_amd/ may include, link or call
  * it; only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg do.
  *
- * Every function names the reference file:line (relative to /root/reference)
+ * Every function names the reference file:line (relative to the TokenGeeX source tree)
  * whose behaviour it restates.  The reference is Rust and cannot be compiled
  * in this image (no cargo/rustc), so parity of this restatement is pinned by
  * the reference's own known-answer tests (tests/test_oracle_kat.py):

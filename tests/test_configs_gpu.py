@@ -85,6 +85,26 @@ def test_bench_starts_its_own_ranks():
     assert out["roofline"]["achieved"] > 0 and out["cpu_baseline"]["cores"] >= 1 and out["cpu_baseline"]["value_1thread"] > 0
 
 
+def test_bench_dump_outputs_are_the_timed_result(tmp_path):
+    """`bench.py --dump-outputs DIR` writes the last timed step's ids and offsets: here whole (8 MiB corpus), and equal
+    to the CPU oracle's encoding of the corpus bench.py builds (the committed 32 000-entry vocabulary, seed 1000)."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--size-mb", "8", "--steps", "2",
+                        "--warmup", "1", "--no-cpu-baseline", "--no-e2e", "--no-estep", "--no-distinct",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-2000:]
+    out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+    assert out["steps"] == 2 and out["ms_per_step"] > 0
+    assert sorted(os.listdir(tmp_path)) == ["ids.npy", "offsets.npy"]
+    ids, oo = np.load(tmp_path / "ids.npy"), np.load(tmp_path / "offsets.npy")
+    assert ids.dtype == np.float32 and oo.dtype == np.float64 and ids.size == out["config"]["tokens_per_gpu"]
+    toks, scores, _ = synth.load_spec_vocab(32000)
+    flat, offs = synth.make_corpus(8 << 20, "mixed", max_len=65536, seed_offset=1000)
+    want_ids, want_oo = orc.OracleModel(toks, scores).encode_batch_flat(flat, offs, threads=8)
+    np.testing.assert_array_equal(oo, want_oo.astype(np.float64))
+    np.testing.assert_array_equal(ids, want_ids.astype(np.float32))
+
+
 def test_two_models_share_one_resident_corpus_from_two_threads():
     """prune and merge keep the corpus in HBM while models come and go (src/prune.rs:48); two models encoding
     and scanning the SAME corpus handle from two host threads must not see each other's scratch."""

@@ -3,7 +3,7 @@
 # register counts, spill instructions (v_readlane / v_writelane of spilled scalars, scratch) and instruction totals
 set -e
 SRC=$1; PAT=${2:-.}
-CS=/root/repo/tokengeex_amd/csrc
+CS=$(cd "$(dirname "$0")/../../tokengeex_amd/csrc" && pwd)
 mkdir -p /tmp/isa && cd /tmp/isa
 hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -munsafe-fp-atomics -Wall -Wno-unused-result -Wno-pass-failed -x hip -S $CS/$SRC -o /tmp/isa/$SRC.s --cuda-device-only 2>&1 | grep -v "^$" | grep -v "hip-link" | head -20
 python3 - "$SRC" "$PAT" <<'PY'

@@ -2,7 +2,7 @@
 # The round's records: rocprofv3 stats + PMC traffic of the default bench command, the bench variants, the
 # prune / merge passes at 1 GiB / 32 K and 256 MiB / 500 K, one prune and one merge run, the shape sweeps.
 # usage: tools/final_profile.sh <outdir-under-gpurun_out> [commit-label]
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 O=$R/gpurun_out/$1
 mkdir -p $O
 cd $R

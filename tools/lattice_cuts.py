@@ -1,7 +1,7 @@
 """How often the lattice of the bench corpus has a position no token match crosses (the cut points of csrc/cuts.hip):
 segment lengths between consecutive cuts, on the CPU.  usage: python tools/lattice_cuts.py <spec32k | 500k | 2mib | distinct>"""
 import os, sys
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tools")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import numpy as np
 from tokengeex_amd import synth, _lib
 import hot_coverage as hc

@@ -2,7 +2,7 @@
 # Collect PMC counters for the encode pass (one bench step per counter group).
 # usage: tools/pmc_encode.sh <outdir-under-gpurun_out> [extra bench args]
 export TMPDIR=/tmp
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$R/gpurun_out/$1; shift
 mkdir -p $OUT
 cd /tmp

@@ -2,7 +2,7 @@
 # SQ / TA counter groups for the encode pass of bench.py (one bench step per group; --pmc with --kernel-trace only).
 # usage: tools/pmc_quick.sh <outdir-under-gpurun_out> [extra bench args]
 export TMPDIR=/tmp
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$R/gpurun_out/$1; shift
 mkdir -p $OUT
 cd /tmp

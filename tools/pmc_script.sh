@@ -2,7 +2,7 @@
 # SQ / TCC counter groups of any script's kernels, per kernel launch in launch order (not averaged).
 # usage: tools/pmc_script.sh <outdir-under-gpurun_out> <script.py> [args]
 export TMPDIR=/tmp
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$R/gpurun_out/$1; shift
 mkdir -p $OUT
 cd /tmp

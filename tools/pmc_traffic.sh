@@ -2,7 +2,7 @@
 # HBM traffic of the bench kernels: FETCH_SIZE and WRITE_SIZE in separate passes (MI355X_MICROARCH.md),
 # --pmc with --kernel-trace only.  usage: tools/pmc_traffic.sh <outdir-under-gpurun_out> [commit-label]
 export TMPDIR=/tmp
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$R/gpurun_out/$1
 mkdir -p $OUT
 cd /tmp

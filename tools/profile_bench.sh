@@ -2,7 +2,7 @@
 # rocprofv3 --kernel-trace --stats of the default bench command, then the PMC traffic passes (FETCH_SIZE and
 # WRITE_SIZE in separate runs).  usage: tools/profile_bench.sh <outdir-under-gpurun_out> [commit-label]
 export TMPDIR=/tmp
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$R/gpurun_out/$1
 mkdir -p $OUT
 cd /tmp

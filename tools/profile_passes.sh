@@ -2,7 +2,7 @@
 # rocprofv3 kernel stats + PMC groups of the prune / merge corpus passes (tests/measure/passes_bench.py).
 # usage: tools/profile_passes.sh <outdir-under-gpurun_out> <MiB> <vocab>
 export TMPDIR=/tmp
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$R/gpurun_out/$1; MIB=${2:-1024}; V=${3:-32000}
 mkdir -p $OUT
 cd /tmp

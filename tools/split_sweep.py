@@ -1,6 +1,6 @@
 import os, sys
 os.environ["TGX_KNOBS"] = "1"
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tools")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import numpy as np
 import tokengeex_amd as tgx
 from tokengeex_amd import synth

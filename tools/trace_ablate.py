@@ -1,5 +1,5 @@
 import os, sys
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 os.environ["TGX_DEBUG"] = "1"
 import tokengeex_amd as tgx
 from tokengeex_amd import synth

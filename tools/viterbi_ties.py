@@ -2,7 +2,7 @@
 or within rounding of each other (they depend on the running sum from the sample start, src/model.rs:96-108), counted
 on the CPU.  usage: python tools/viterbi_ties.py <spec32k | distinct | 2mib> [MiB]"""
 import os, sys
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tools")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import numpy as np
 from tokengeex_amd import synth, _lib
 import hot_coverage as hc
