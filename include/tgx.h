@@ -249,6 +249,28 @@ uint64_t tgx_corpus_num_bytes(const tgx_corpus *c);
 tgx_status tgx_encode_corpus(tgx_model *m, tgx_corpus *c, double dropout, uint64_t seed,
                              tgx_result **out);
 
+/* ---- subword regularisation: a segmentation drawn from the lattice ---------
+ * Kudo 2018 (SentencePiece's enable_sampling, nbest_size = -1): every sample gets one segmentation x drawn with
+ * probability P(x | text) ∝ exp(alpha · Σ_{t ∈ x} score(t)) instead of the Viterbi path.  alpha = 0 is uniform over
+ * the segmentations; a large alpha approaches encode.  The draw is forward filtering, backward sampling: with
+ * A[0] = 0 and A[p] = logsumexp over the matches (q, len), q + len = p, of A[q] + alpha · score, the token ending at
+ * p is the match with the largest key A[q] + alpha · score − log(−log u), u = tgx_sample_u01(seed, sample, q, len),
+ * exact ties going to the longer token; the path is the back-trace from n.  `sample` is the sample's index in the
+ * batch (the corpus form: as uploaded), `q` the match's first byte in the sample, `len` its length in bytes.
+ *   alpha must be finite and >= 0 (else TGX_ERR_INVALID); a model with a non-finite score gives
+ *   TGX_ERR_UNSUPPORTED; an unreachable end gives TGX_ERR_NO_PATH exactly as tgx_encode_batch on the same batch.
+ *   logz (NULL or f64[n_samples], input order) receives every sample's log Z = A[n] under alpha.
+ *   Ids and offsets come back in the usual tgx_result. */
+/* the uniform of the race: x = seed ^ 0xD6E8FEB86659FD93 ^ sample·0x9E3779B97F4A7C15 ^ pos·0xC2B2AE3D27D4EB4F ^
+ * len·0x165667B19E3779F9, the three xor-shift / multiply rounds of tgx_dropout_u01, u = ((x >> 11) + 0.5) · 2^-53 in
+ * f64, except that the one value this rounds to 1.0 (x >> 11 = 2^53 − 1) gives the largest double below 1: never 0 or 1 */
+double tgx_sample_u01(uint64_t seed, uint64_t sample, uint64_t pos, uint32_t len);
+tgx_status tgx_encode_batch_sample(tgx_model *m, const uint8_t *text, const uint64_t *offs,
+                                   uint64_t n_samples, double alpha, uint64_t seed,
+                                   double *logz, tgx_result **out);
+tgx_status tgx_encode_corpus_sample(tgx_model *m, tgx_corpus *c, double alpha, uint64_t seed,
+                                    double *logz, tgx_result **out);
+
 /* Frequency pass of prune_vocab — src/prune.rs:205-244: freq[id] += 1 for every
  * Viterbi token (dropout 0.0).  freq[vocab_size] is ACCUMULATED into (host). */
 tgx_status tgx_count_tokens(tgx_model *m, tgx_corpus *c, uint64_t *freq);

@@ -98,6 +98,9 @@ SYMBOLS = {
     "tgx_last_estep_redo": (_u64, [_vp]),
     "tgx_last_encode_corun_cus": (_u32, [_vp]),
     "tgx_encode_corun_timeouts": (_u32, [_vp]),
+    "tgx_sample_u01": (_d, [_u64, _u64, _u64, _u32]),
+    "tgx_encode_batch_sample": (_i, [_vp, _vp, _vp, _u64, _d, _u64, _vp, _pvp]),
+    "tgx_encode_corpus_sample": (_i, [_vp, _vp, _d, _u64, _vp, _pvp]),
 }
 
 
@@ -540,6 +543,28 @@ class NativeModel:
         check(lib.tgx_encode_corpus(self._h, corpus._h, float(dropout), seed & (2**64 - 1), C.byref(h)))
         return NativeResult(h)
 
+    def encode_batch_sample_flat(self, flat: np.ndarray, offs: np.ndarray, alpha: float, seed: int,
+                                 return_logz: bool = False):
+        """One segmentation per sample drawn from the lattice under temperature alpha (tgx_encode_batch_sample)
+        -> NativeResult, or (NativeResult, logz f64[S]) with return_logz."""
+        flat = np.ascontiguousarray(flat, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        n = offs.shape[0] - 1
+        logz = np.zeros(max(n, 1), np.float64) if return_logz else None
+        h = C.c_void_p()
+        check(lib.tgx_encode_batch_sample(self._h, ptr(flat) if flat.size else None, ptr(offs), n, float(alpha),
+                                          seed & (2**64 - 1), ptr(logz) if return_logz else None, C.byref(h)))
+        return (NativeResult(h), logz[:n]) if return_logz else NativeResult(h)
+
+    def encode_corpus_sample(self, corpus: NativeCorpus, alpha: float, seed: int, return_logz: bool = False):
+        """encode_batch_sample_flat over a resident corpus (tgx_encode_corpus_sample)."""
+        n = corpus.num_samples
+        logz = np.zeros(max(n, 1), np.float64) if return_logz else None
+        h = C.c_void_p()
+        check(lib.tgx_encode_corpus_sample(self._h, corpus._h, float(alpha), seed & (2**64 - 1),
+                                           ptr(logz) if return_logz else None, C.byref(h)))
+        return (NativeResult(h), logz[:n]) if return_logz else NativeResult(h)
+
     def count_tokens(self, corpus: NativeCorpus, freq: np.ndarray | None = None) -> np.ndarray:
         if freq is None:
             freq = np.zeros(self.vocab_size, np.uint64)
@@ -738,3 +763,7 @@ def prune_select(freq, keep, always_keep, alt_offs, alt_ids, scores, n_samples: 
 
 def dropout_u01(seed: int, sample: int, pos: int, length: int) -> float:
     return lib.tgx_dropout_u01_host(seed, sample, pos, length)
+
+
+def sample_u01(seed: int, sample: int, pos: int, length: int) -> float:
+    return lib.tgx_sample_u01(seed, sample, pos, length)

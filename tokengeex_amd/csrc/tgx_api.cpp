@@ -23,6 +23,7 @@
 
 #include "../../include/tgx.h"
 #include "kernels.h"
+#include "sample.h"
 #include "trie_build.h"
 
 namespace {
@@ -3399,6 +3400,199 @@ tgx_status tgx_estep(tgx_model* m, tgx_corpus* c, uint64_t snippet_len, double d
                             bad, (unsigned long long)g_err_len));
     }
     return cleanup(TGX_OK);
+}
+
+// ---- sampling (sample.hip) ---------------------------------------------------------
+
+double tgx_sample_u01(uint64_t seed, uint64_t sample, uint64_t pos, uint32_t len) {
+    uint64_t x = seed ^ 0xD6E8FEB86659FD93ULL ^ (sample * 0x9E3779B97F4A7C15ULL) ^ (pos * 0xC2B2AE3D27D4EB4FULL) ^
+                 ((uint64_t)len * 0x165667B19E3779F9ULL);
+    x ^= x >> 30;
+    x *= 0xBF58476D1CE4E5B9ULL;
+    x ^= x >> 27;
+    x *= 0x94D049BB133111EBULL;
+    x ^= x >> 31;
+    const double u = ((double)(x >> 11) + 0.5) * (1.0 / 9007199254740992.0);
+    return u < 1.0 ? u : 0x1.fffffffffffffp-1;  // (2^53 - 1 + 0.5 rounds to 2^53)
+}
+
+// alpha finite and >= 0, scores finite, alpha · score finite; caller holds m->mu
+static tgx_status sample_check(const tgx_model* m, double alpha) {
+    if (!(alpha >= 0.0) || !std::isfinite(alpha)) return fail(TGX_ERR_INVALID, "alpha must be finite and >= 0 (got %g)", alpha);
+    if (!m->scores_finite) return fail(TGX_ERR_UNSUPPORTED, "sampling needs every score to be finite");
+    for (double sc : m->vocab_scores)
+        if (!std::isfinite(alpha * sc)) return fail(TGX_ERR_INVALID, "alpha * score overflows (alpha %g)", alpha);
+    return TGX_OK;
+}
+
+// caller holds m->mu and c->mu
+static tgx_status sample_corpus_locked(tgx_model* m, tgx_corpus* c, double alpha, uint64_t seed, double* logz, tgx_result** out) {
+    HIP_TRY(hipSetDevice(m->device));
+    {
+        const tgx_status est = ensure_encode_tables(m);
+        if (est != TGX_OK) return est;
+    }
+    m->n_timed = 0;
+    const uint64_t S = c->n_samples;
+    const uint32_t n_slots = (uint32_t)m->flat.table.size();
+
+    // the rows kernel: tokens <= 32 bytes, the token hash table of the trace, every w = exp(alpha · score) in [2^-300, 2^300]
+    bool rows = m->lm <= 32 && m->d_tokhash != nullptr;
+    for (double sc : m->vocab_scores)
+        if (!(std::fabs(alpha * sc) <= 207.0)) rows = false;
+    if (const char* e = knob("TGX_SAMPLE_PATH")) {
+        if (strcmp(e, "generic") == 0) rows = false;
+    }
+
+    tgx_result* r = new tgx_result();
+    r->device = m->device;
+    r->n_samples = S;
+    double* d_logz = nullptr;     // f64[S], then the range flag
+    double* d_wslot = nullptr;    // f64[n_slots]
+    const size_t lb = (size_t)S * 8 + 16, wb = (size_t)n_slots * 8 + 16;
+    auto cleanup = [&](tgx_status st) {
+        if (d_logz) pool_free(m->device, d_logz, lb);
+        if (d_wslot) pool_free(m->device, d_wslot, wb);
+        if (st != TGX_OK) tgx_result_free(r);
+        return st;
+    };
+    if (pool_alloc(m->device, (size_t)(S + 1) * 8, (void**)&r->d_offs) != hipSuccess ||
+        pool_alloc(m->device, lb, (void**)&d_logz) != hipSuccess || (rows && pool_alloc(m->device, wb, (void**)&d_wslot) != hipSuccess))
+        return cleanup(fail(TGX_ERR_DEVICE, "out of device memory (sampling)"));
+    tgx_status st = ensure_scratch(c, false);
+    if (st != TGX_OK) return cleanup(st);
+    unsigned long long* d_range = reinterpret_cast<unsigned long long*>(d_logz + S);
+    if (hipMemsetAsync(m->d_ctrl, 0x00, 8, m->stream) != hipSuccess || hipMemsetAsync(m->d_ctrl + 1, 0xFF, 8, m->stream) != hipSuccess ||
+        hipMemsetAsync(d_range, 0x00, 8, m->stream) != hipSuccess)
+        return cleanup(fail(TGX_ERR_DEVICE, "memset failed"));
+
+    tgx::EncodeParams p{};
+    p.text = c->d_text;
+    p.offs = c->d_offs;
+    p.order = c->d_order;
+    p.n_samples = S;
+    p.trie = m->d_trie;
+    p.tokid = m->d_tokid;
+    p.root_base = m->flat.table[0].base & ~tgx::kTerminalBit;
+    p.lm = m->lm;
+    p.n_slots = n_slots;
+    p.bp = c->d_bp;
+    p.tmp = c->d_tmp;
+    p.counts = c->d_counts;
+    p.status = c->d_status;
+    p.bp8 = reinterpret_cast<uint8_t*>(c->d_bp);
+    p.tokhash = m->d_tokhash;
+    p.tokhash_mask = m->tokhash.mask;
+    p.tokhash_seed = m->tokhash.seed;
+    p.err_sample = m->d_ctrl + 1;
+    p.queue = m->d_ctrl;
+    p.seed = seed;
+    p.trace_carry = (S && c->n_bytes / S < 2048) ? 1u : 0u;
+    tgx::SampleParams q{};
+    q.alpha = alpha;
+    q.logz = d_logz;
+    q.wslot = d_wslot;
+    q.range_flag = d_range;
+    if (rows) {
+        time_begin(m, "sample_wslot_kernel");
+        if (tgx::launch_sample_wslot(m->d_trie, n_slots, alpha, d_wslot, m->stream) != hipSuccess)
+            return cleanup(fail(TGX_ERR_DEVICE, "sample_wslot_kernel launch failed"));
+        time_end(m);
+        time_begin(m, "sample_rows_kernel");
+        if (tgx::launch_sample_rows(p, q, (uint32_t)m->num_cus, m->stream) != hipSuccess)
+            return cleanup(fail(TGX_ERR_DEVICE, "sample_rows_kernel launch failed"));
+        time_end(m);
+        unsigned long long range = 0;
+        if (hipMemcpyAsync(&range, d_range, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess || hipStreamSynchronize(m->stream) != hipSuccess)
+            return cleanup(fail(TGX_ERR_DEVICE, "sampling pass failed: %s", hipGetErrorString(hipGetLastError())));
+        if (range) {  // a value the linear domain cannot hold exactly: the whole call on the log-domain kernel
+            rows = false;
+            if (hipMemsetAsync(m->d_ctrl + 1, 0xFF, 8, m->stream) != hipSuccess) return cleanup(fail(TGX_ERR_DEVICE, "memset failed"));
+        } else {
+            const uint32_t blocks_t = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((S + 3) / 4, (uint64_t)m->num_cus * 8));
+            time_begin(m, "trace32_kernel");
+            if (tgx::launch_trace32(p, blocks_t, false, m->stream) != hipSuccess)
+                return cleanup(fail(TGX_ERR_DEVICE, "trace32_kernel launch failed"));
+            time_end(m);
+        }
+    }
+    if (!rows) {
+        time_begin(m, "sample_kernel");
+        if (tgx::launch_sample(p, q, (uint32_t)m->num_cus, m->stream) != hipSuccess)
+            return cleanup(fail(TGX_ERR_DEVICE, "sample_kernel launch failed"));
+        time_end(m);
+    }
+
+    // token counts -> offsets -> ids, as encode_corpus_locked does
+    if (!c->d_scan_tmp) {
+        if (tgx::scan_temp_bytes(S, &c->scan_tmp_bytes) != hipSuccess)
+            return cleanup(fail(TGX_ERR_DEVICE, "scan temp-size query failed"));
+        if (c->scan_tmp_bytes && pool_alloc(m->device, c->scan_tmp_bytes, &c->d_scan_tmp) != hipSuccess)
+            return cleanup(fail(TGX_ERR_DEVICE, "out of device memory (scan)"));
+    }
+    time_begin(m, "scan_counts_kernel");
+    if (tgx::launch_scan(c->d_counts, r->d_offs, S, c->d_scan_tmp, c->scan_tmp_bytes, m->stream) != hipSuccess)
+        return cleanup(fail(TGX_ERR_DEVICE, "scan launch failed"));
+    time_end(m);
+    if (hipMemcpyAsync(&m->h_ctrl[0], m->d_ctrl + 1, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
+        hipMemcpyAsync(&m->h_ctrl[1], r->d_offs + S, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
+        hipStreamSynchronize(m->stream) != hipSuccess)
+        return cleanup(fail(TGX_ERR_DEVICE, "sampling pass failed: %s", hipGetErrorString(hipGetLastError())));
+    st = check_no_path(m, c);
+    if (st != TGX_OK) return cleanup(st);
+    r->n_tokens = m->h_ctrl[1];
+    if (pool_alloc(m->device, (size_t)r->n_tokens * 4 + 256, (void**)&r->d_ids) != hipSuccess)
+        return cleanup(fail(TGX_ERR_DEVICE, "out of device memory (result ids)"));
+    tgx::CompactParams cp{};
+    cp.offs = c->d_offs;
+    cp.order = c->d_order;
+    cp.n_samples = S;
+    cp.tmp = c->d_tmp;
+    cp.out_offs = r->d_offs;
+    cp.ids = r->d_ids;
+    const bool crows = S && r->n_tokens / S < 128;
+    const uint64_t units = crows ? 16 : 4;
+    const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((S + units - 1) / units, (uint64_t)m->num_cus * 8));
+    time_begin(m, "compact_kernel");
+    if (tgx::launch_compact(cp, blocks, crows, m->stream) != hipSuccess)
+        return cleanup(fail(TGX_ERR_DEVICE, "compact launch failed"));
+    time_end(m);
+    if ((logz && S && hipMemcpyAsync(logz, d_logz, (size_t)S * 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess) ||
+        hipStreamSynchronize(m->stream) != hipSuccess)
+        return cleanup(fail(TGX_ERR_DEVICE, "compact failed: %s", hipGetErrorString(hipGetLastError())));
+    m->last_alg_bytes = c->n_bytes + 4 * r->n_tokens + 16 * (S + 1);
+    *out = r;
+    return cleanup(TGX_OK);
+}
+
+tgx_status tgx_encode_corpus_sample(tgx_model* m, tgx_corpus* c, double alpha, uint64_t seed, double* logz, tgx_result** out) {
+    if (usable_device_count() <= 0) return fail(TGX_ERR_DEVICE, "no usable HIP device (gfx950 required)");
+    if (!m || !c || !out) return fail(TGX_ERR_INVALID, "tgx_encode_corpus_sample: NULL argument");
+    *out = nullptr;
+    if (m->device != c->device) return fail(TGX_ERR_INVALID, "model and corpus on different devices");
+    std::lock_guard<std::mutex> lk(m->mu);
+    const tgx_status st = sample_check(m, alpha);
+    if (st != TGX_OK) return st;
+    std::lock_guard<std::mutex> lkc(c->mu);
+    return sample_corpus_locked(m, c, alpha, seed, logz, out);
+}
+
+tgx_status tgx_encode_batch_sample(tgx_model* m, const uint8_t* text, const uint64_t* offs, uint64_t n_samples, double alpha,
+                                   uint64_t seed, double* logz, tgx_result** out) {
+    if (usable_device_count() <= 0) return fail(TGX_ERR_DEVICE, "no usable HIP device (gfx950 required)");
+    if (!m || !out) return fail(TGX_ERR_INVALID, "tgx_encode_batch_sample: NULL argument");
+    *out = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(m->mu);
+        const tgx_status st = sample_check(m, alpha);
+        if (st != TGX_OK) return st;
+    }
+    tgx_corpus* c = nullptr;
+    tgx_status st = tgx_corpus_upload(m->device, text, offs, n_samples, &c);
+    if (st != TGX_OK) return st;
+    st = tgx_encode_corpus_sample(m, c, alpha, seed, logz, out);
+    tgx_corpus_free(c);
+    return st;
 }
 
 // ---- measurement ---------------------------------------------------------------

@@ -247,6 +247,64 @@ class Tokenizer:
         finally:
             res.free()
 
+    # -- subword regularisation: a segmentation drawn from the lattice (csrc/sample.hip) --
+    def _sample_seed(self, seed: int | None) -> int:
+        if seed is not None:
+            return int(seed)
+        return self.seed if self.seed is not None else random.getrandbits(64)
+
+    def encode_sample(self, text: str, alpha: float, seed: int | None = None) -> list[int]:
+        return self.encode_batch_sample([text], alpha, seed)[0]
+
+    def encode_batch_sample(self, texts: list[str], alpha: float, seed: int | None = None) -> list[list[int]]:
+        """encode_batch with every sample's segmentation drawn from P(x | text) ∝ exp(alpha · Σ score) (Kudo 2018)."""
+        text_b, offs_b = _fast.pack_strs(texts)
+        ids, o = self.encode_batch_sample_flat(np.frombuffer(text_b, dtype=np.uint8), np.frombuffer(offs_b, dtype=np.uint64),
+                                               alpha, seed)
+        return _split_rows(ids, o)
+
+    def encode_batch_sample_flat(self, flat: np.ndarray, offs: np.ndarray, alpha: float, seed: int | None = None,
+                                 ordinary: bool = False, return_logz: bool = False):
+        """encode_batch_flat with sampled segmentations -> (ids uint32[T], offsets uint64[S+1]) [, logz f64[S]].  Specials
+        keep their ids; a sample's log Z is the sum over its non-special segments.  The draw of a match hashes the index of
+        its segment in the packed batch of non-special segments (tgx_sample_u01)."""
+        if not self._native_front():
+            raise TokenGeeXError("encode_batch_sample_flat: a processor without a packed-buffer form", _lib.ERR_UNSUPPORTED)
+        seed = self._sample_seed(seed)
+        flat = np.ascontiguousarray(flat, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        only_crlf = all(isinstance(p, CrlfProcessor) for p in self._processors)
+        crlf = only_crlf and len(self._processors) > 0
+        n = offs.shape[0] - 1
+
+        def run(pflat, poffs):
+            if poffs.shape[0] <= 1:
+                return np.zeros(0, np.uint32), np.zeros(1, np.uint64), np.zeros(0, np.float64)
+            res, logz = self._model().encode_batch_sample_flat(pflat, poffs, alpha, seed, return_logz=True)
+            try:
+                return res.ids(), res.offsets(), logz
+            finally:
+                res.free()
+
+        if ordinary or not self._special_tokens:
+            if n and self._processors:
+                flat, offs = self._preprocess_flat(flat, offs)
+            ids, id_offs, logz = run(flat, offs)
+            if not n:
+                logz = np.zeros(0, np.float64)
+            return (ids, id_offs, logz) if return_logz else (ids, id_offs)
+        seg_offs, sb, se, ss = _lib.split_specials_flat(flat, offs, [t.encode("utf-8") for t in self._special_tokens])
+        pflat, poffs = _lib.pack_segments(flat, sb, se, ss, crlf)
+        if not only_crlf and poffs.shape[0] > 1:
+            pflat, poffs = self._preprocess_flat(pflat, poffs)
+        ids, id_offs, seg_logz = run(pflat, poffs)
+        out = _lib.assemble_ids(seg_offs, ss, ids, id_offs, self.base_vocab_size())
+        if not return_logz:
+            return out
+        seg_sample = np.repeat(np.arange(n), np.diff(seg_offs.astype(np.int64)))
+        logz = np.bincount(seg_sample[ss < 0], weights=seg_logz, minlength=n).astype(np.float64) if n else np.zeros(0)
+        return out[0], out[1], logz
+
     # -- decode: src/tokenizer.rs:126-187, src/model.rs:146-160 --
     def _model_decode(self, ids) -> str:
         buf = bytearray()
