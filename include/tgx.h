@@ -271,6 +271,32 @@ tgx_status tgx_encode_batch_sample(tgx_model *m, const uint8_t *text, const uint
 tgx_status tgx_encode_corpus_sample(tgx_model *m, tgx_corpus *c, double alpha, uint64_t seed,
                                     double *logz, tgx_result **out);
 
+/* ---- n-best segmentation: the k highest-scoring segmentations per sample ---
+ * SentencePiece's NBestEncode (and the list that SampleEncode with nbest_size > 1 draws from).  For a sample of n
+ * bytes the matches are what encode sees with dropout 0: a match is (q, len, id, s), s = score[id].  Every position p
+ * gets a list L[p] of at most k entries (score, q, r):
+ *   L[0] = [(0.0, -, -)];
+ *   L[p] = the top k, in the order below, of all candidates (L[q][r].score + s, q, r) over every match (q, len) with
+ *          q + len = p and every r < |L[q]|; the addition is the f64 add encode forms, left to right;
+ *   order: score descending, then q ascending (the longer last token first), then r ascending — a strict total
+ *          order, so the lists do not depend on how they are merged.
+ * Row r of a sample is the back-trace from L[n][r].  Row 0 is tgx_encode_batch's path (encode keeps the first,
+ * longest match on a tie); rows are pairwise distinct segmentations with non-increasing scores; and the rows for k
+ * are the first k rows for any k' > k (fl(a + s) is monotone in a, and r breaks the ties rounding creates).
+ *   *out has n_samples · nbest rows: row s · nbest + r is the r-th best segmentation of sample s, samples in input
+ *     order; tgx_result_num_samples returns that row count and the result accessors work unchanged.  Rows at or
+ *     beyond n_found are empty.  An empty sample has one empty row of score 0.0.
+ *   scores (NULL or f64[n_samples · nbest]): each row's path score, -inf for rows at or beyond n_found.
+ *   n_found (NULL or u32[n_samples]): min(nbest, the number of segmentations of the sample).
+ *   nbest = 0 or > TGX_MAX_NBEST gives TGX_ERR_INVALID; a model with a non-finite score, or with 2^22 tokens or
+ *   more, gives TGX_ERR_UNSUPPORTED; an unreachable end gives TGX_ERR_NO_PATH exactly as tgx_encode_batch on the
+ *   same batch.  Any token length up to TGX_MAX_TOKEN_LEN; dropout does not apply. */
+#define TGX_MAX_NBEST 16
+tgx_status tgx_encode_batch_nbest(tgx_model *m, const uint8_t *text, const uint64_t *offs, uint64_t n_samples,
+                                  uint32_t nbest, double *scores, uint32_t *n_found, tgx_result **out);
+tgx_status tgx_encode_corpus_nbest(tgx_model *m, tgx_corpus *c, uint32_t nbest,
+                                   double *scores, uint32_t *n_found, tgx_result **out);
+
 /* Frequency pass of prune_vocab — src/prune.rs:205-244: freq[id] += 1 for every
  * Viterbi token (dropout 0.0).  freq[vocab_size] is ACCUMULATED into (host). */
 tgx_status tgx_count_tokens(tgx_model *m, tgx_corpus *c, uint64_t *freq);

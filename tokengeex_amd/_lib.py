@@ -18,6 +18,7 @@ LIB_PATH = os.path.join(_HERE, "libtgx.so")
 OK, ERR_IO, ERR_JSON, ERR_TOKEN_ID_OOB, ERR_NO_PATH, ERR_DEVICE, ERR_Z_NOT_NORMAL, ERR_INVALID, \
     ERR_UNSUPPORTED = range(9)
 MAX_TOKEN_LEN = 64
+MAX_NBEST = 16  # TGX_MAX_NBEST
 ESTEP_SNIPPET_LEN = 81920
 
 # every exported symbol of include/tgx.h: name -> (restype, argtypes)
@@ -101,6 +102,8 @@ SYMBOLS = {
     "tgx_sample_u01": (_d, [_u64, _u64, _u64, _u32]),
     "tgx_encode_batch_sample": (_i, [_vp, _vp, _vp, _u64, _d, _u64, _vp, _pvp]),
     "tgx_encode_corpus_sample": (_i, [_vp, _vp, _d, _u64, _vp, _pvp]),
+    "tgx_encode_batch_nbest": (_i, [_vp, _vp, _vp, _u64, _u32, _vp, _vp, _pvp]),
+    "tgx_encode_corpus_nbest": (_i, [_vp, _vp, _u32, _vp, _vp, _pvp]),
 }
 
 
@@ -565,6 +568,28 @@ class NativeModel:
                                            ptr(logz) if return_logz else None, C.byref(h)))
         return (NativeResult(h), logz[:n]) if return_logz else NativeResult(h)
 
+    def encode_batch_nbest_flat(self, flat: np.ndarray, offs: np.ndarray, nbest: int):
+        """The nbest highest-scoring segmentations of every sample (tgx_encode_batch_nbest) -> (NativeResult of S·nbest
+        rows, row s·nbest + r the r-th best of sample s; scores f64[S·nbest], -inf past n_found; n_found u32[S])."""
+        flat = np.ascontiguousarray(flat, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        n = offs.shape[0] - 1
+        scores = np.empty(max(n * int(nbest), 1), np.float64)
+        n_found = np.empty(max(n, 1), np.uint32)
+        h = C.c_void_p()
+        check(lib.tgx_encode_batch_nbest(self._h, ptr(flat) if flat.size else None, ptr(offs), n, int(nbest), ptr(scores),
+                                         ptr(n_found), C.byref(h)))
+        return NativeResult(h), scores[:n * int(nbest)], n_found[:n]
+
+    def encode_corpus_nbest(self, corpus: NativeCorpus, nbest: int):
+        """encode_batch_nbest_flat over a resident corpus (tgx_encode_corpus_nbest)."""
+        n = corpus.num_samples
+        scores = np.empty(max(n * int(nbest), 1), np.float64)
+        n_found = np.empty(max(n, 1), np.uint32)
+        h = C.c_void_p()
+        check(lib.tgx_encode_corpus_nbest(self._h, corpus._h, int(nbest), ptr(scores), ptr(n_found), C.byref(h)))
+        return NativeResult(h), scores[:n * int(nbest)], n_found[:n]
+
     def count_tokens(self, corpus: NativeCorpus, freq: np.ndarray | None = None) -> np.ndarray:
         if freq is None:
             freq = np.zeros(self.vocab_size, np.uint64)
@@ -767,3 +792,19 @@ def dropout_u01(seed: int, sample: int, pos: int, length: int) -> float:
 
 def sample_u01(seed: int, sample: int, pos: int, length: int) -> float:
     return lib.tgx_sample_u01(seed, sample, pos, length)
+
+
+def sample_u01_array(seed: int, sample: np.ndarray, pos: np.ndarray, length: np.ndarray) -> np.ndarray:
+    """tgx_sample_u01 over arrays (numpy u64 arithmetic wraps as the C code does)."""
+    with np.errstate(over="ignore"):
+        x = (np.uint64(seed & (2**64 - 1)) ^ np.uint64(0xD6E8FEB86659FD93)
+             ^ (np.asarray(sample, np.uint64) * np.uint64(0x9E3779B97F4A7C15))
+             ^ (np.asarray(pos, np.uint64) * np.uint64(0xC2B2AE3D27D4EB4F))
+             ^ (np.asarray(length, np.uint64) * np.uint64(0x165667B19E3779F9)))
+        x ^= x >> np.uint64(30)
+        x *= np.uint64(0xBF58476D1CE4E5B9)
+        x ^= x >> np.uint64(27)
+        x *= np.uint64(0x94D049BB133111EB)
+        x ^= x >> np.uint64(31)
+    u = ((x >> np.uint64(11)).astype(np.float64) + 0.5) * (1.0 / 9007199254740992.0)
+    return np.minimum(u, np.nextafter(1.0, 0.0))

@@ -23,6 +23,7 @@
 
 #include "../../include/tgx.h"
 #include "kernels.h"
+#include "nbest.h"
 #include "sample.h"
 #include "trie_build.h"
 
@@ -3591,6 +3592,211 @@ tgx_status tgx_encode_batch_sample(tgx_model* m, const uint8_t* text, const uint
     tgx_status st = tgx_corpus_upload(m->device, text, offs, n_samples, &c);
     if (st != TGX_OK) return st;
     st = tgx_encode_corpus_sample(m, c, alpha, seed, logz, out);
+    tgx_corpus_free(c);
+    return st;
+}
+
+// ---- n-best segmentation (nbest.hip) ------------------------------------------------
+
+// caller holds m->mu
+static tgx_status nbest_check(const tgx_model* m, uint32_t nbest) {
+    if (nbest == 0 || nbest > TGX_MAX_NBEST) return fail(TGX_ERR_INVALID, "nbest must be in 1..%d (got %u)", TGX_MAX_NBEST, nbest);
+    if (!m->scores_finite) return fail(TGX_ERR_UNSUPPORTED, "n-best needs every score to be finite");
+    if (m->vocab_size >= tgx::kNbestMaxVocab)
+        return fail(TGX_ERR_UNSUPPORTED, "n-best supports vocabularies of fewer than %u tokens", tgx::kNbestMaxVocab);
+    return TGX_OK;
+}
+
+// Scratch of a chunk: K back-pointers per position (N + S positions) and nbest ids per byte.  A call whose scratch would
+// exceed the budget is cut at sample boundaries (input order); a sample larger than the budget is a chunk of its own.
+static uint64_t nbest_chunk_budget() {
+    uint64_t mb = 8192;
+    if (const char* e = knob("TGX_NBEST_CHUNK_MB")) {
+        const long long v = atoll(e);
+        if (v > 0) mb = (uint64_t)v;
+    }
+    return mb << 20;
+}
+
+// caller holds m->mu and c->mu
+static tgx_status nbest_corpus_locked(tgx_model* m, tgx_corpus* c, uint32_t k, double* scores, uint32_t* n_found, tgx_result** out) {
+    HIP_TRY(hipSetDevice(m->device));
+    m->n_timed = 0;
+    const uint64_t S = c->n_samples;
+    const uint32_t K = k <= 1 ? 1u : k <= 2 ? 2u : k <= 4 ? 4u : k <= 8 ? 8u : 16u;
+    const uint64_t rows_all = S * k;
+    const uint64_t* ho = c->h_offs.data();
+
+    // chunks [cs[i], cs[i + 1]) of samples in input order
+    const uint64_t budget = nbest_chunk_budget();
+    std::vector<uint64_t> cs{0};
+    uint64_t max_bytes = 0, max_samples = 0;
+    {
+        uint64_t s0 = 0;
+        for (uint64_t s = 0; s < S; s++) {
+            const uint64_t bytes = ho[s + 1] - ho[s0], samples = s + 1 - s0;
+            const uint64_t need = (bytes + samples) * K * 4 + bytes * k * 4;
+            if (s > s0 && need > budget) {
+                cs.push_back(s);
+                s0 = s;
+            }
+        }
+        cs.push_back(S);
+        if (S == 0) cs.assign({0, 0});
+        for (size_t i = 0; i + 1 < cs.size(); i++) {
+            max_bytes = std::max(max_bytes, ho[cs[i + 1]] - ho[cs[i]]);
+            max_samples = std::max(max_samples, cs[i + 1] - cs[i]);
+        }
+    }
+    // every chunk's samples longest first (the order the kernel hands them to its waves)
+    std::vector<uint32_t> order(S);
+    for (size_t i = 0; i + 1 < cs.size(); i++) {
+        std::iota(order.begin() + (long)cs[i], order.begin() + (long)cs[i + 1], (uint32_t)cs[i]);
+        std::stable_sort(order.begin() + (long)cs[i], order.begin() + (long)cs[i + 1],
+                         [ho](uint32_t a, uint32_t b) { return ho[a + 1] - ho[a] > ho[b + 1] - ho[b]; });
+    }
+
+    tgx_result* r = new tgx_result();
+    r->device = m->device;
+    r->n_samples = rows_all;
+    uint32_t *d_bp = nullptr, *d_tmp = nullptr, *d_counts = nullptr, *d_nfound = nullptr, *d_order = nullptr;
+    double* d_scores = nullptr;
+    void* d_scan = nullptr;
+    size_t scan_bytes = 0;
+    std::vector<std::pair<uint32_t*, uint64_t>> parts;  // every chunk's ids
+    const size_t bpb = (size_t)(max_bytes + max_samples) * K * 4 + 256, tb = (size_t)max_bytes * k * 4 + 256;
+    const size_t cb = (size_t)rows_all * 4 + 256, sb = (size_t)rows_all * 8 + 256, nb = (size_t)S * 4 + 256;
+    auto cleanup = [&](tgx_status st) {
+        pool_free(m->device, d_bp, bpb);
+        pool_free(m->device, d_tmp, tb);
+        pool_free(m->device, d_counts, cb);
+        pool_free(m->device, d_scores, sb);
+        pool_free(m->device, d_nfound, nb);
+        pool_free(m->device, d_order, nb);
+        pool_free(m->device, d_scan, scan_bytes);
+        for (auto& pt : parts) pool_free(m->device, pt.first, (size_t)pt.second * 4 + 256);
+        if (st != TGX_OK) tgx_result_free(r);
+        return st;
+    };
+    if (tgx::scan_temp_bytes(max_samples * k, &scan_bytes) != hipSuccess) return cleanup(fail(TGX_ERR_DEVICE, "scan temp-size query failed"));
+    if (pool_alloc(m->device, (size_t)(rows_all + 1) * 8, (void**)&r->d_offs) != hipSuccess ||
+        pool_alloc(m->device, bpb, (void**)&d_bp) != hipSuccess || pool_alloc(m->device, tb, (void**)&d_tmp) != hipSuccess ||
+        pool_alloc(m->device, cb, (void**)&d_counts) != hipSuccess || pool_alloc(m->device, sb, (void**)&d_scores) != hipSuccess ||
+        pool_alloc(m->device, nb, (void**)&d_nfound) != hipSuccess || pool_alloc(m->device, nb, (void**)&d_order) != hipSuccess ||
+        (scan_bytes && pool_alloc(m->device, scan_bytes, &d_scan) != hipSuccess))
+        return cleanup(fail(TGX_ERR_DEVICE, "out of device memory (n-best)"));
+    if ((S && hipMemcpyAsync(d_order, order.data(), (size_t)S * 4, hipMemcpyHostToDevice, m->stream) != hipSuccess) ||
+        hipMemsetAsync(r->d_offs, 0, 8, m->stream) != hipSuccess || hipMemsetAsync(m->d_ctrl + 1, 0xFF, 8, m->stream) != hipSuccess)
+        return cleanup(fail(TGX_ERR_DEVICE, "n-best upload failed"));
+
+    tgx::NbestParams p{};
+    p.text = c->d_text;
+    p.offs = c->d_offs;
+    p.trie = m->d_trie;
+    p.tokid = m->d_tokid;
+    p.root_base = m->flat.table[0].base & ~tgx::kTerminalBit;
+    p.n_slots = (uint32_t)m->flat.table.size();
+    p.lm = m->lm;
+    p.k = k;
+    p.bp = d_bp;
+    p.tmp = d_tmp;
+    p.scores = d_scores;
+    p.n_found = d_nfound;
+    p.err_sample = m->d_ctrl + 1;
+    uint64_t total = 0;
+    for (size_t ci = 0; ci + 1 < cs.size() && cs[ci] < cs[ci + 1]; ci++) {
+        const uint64_t s0 = cs[ci], ns = cs[ci + 1] - s0, R0 = s0 * k;
+        p.order = d_order + s0;
+        p.n_samples = ns;
+        p.s0 = s0;
+        p.byte0 = ho[s0];
+        p.chunk_bytes = ho[s0 + ns] - ho[s0];
+        p.counts = d_counts + R0;
+        time_begin(m, "nbest_kernel");
+        if (tgx::launch_nbest(p, K, (uint32_t)m->num_cus, m->stream) != hipSuccess) return cleanup(fail(TGX_ERR_DEVICE, "nbest_kernel launch failed"));
+        time_end(m);
+        time_begin(m, "nbest_trace_kernel");
+        if (tgx::launch_nbest_trace(p, K, (uint32_t)m->num_cus, m->stream) != hipSuccess)
+            return cleanup(fail(TGX_ERR_DEVICE, "nbest_trace_kernel launch failed"));
+        time_end(m);
+        time_begin(m, "scan_counts_kernel");
+        if (tgx::launch_scan(d_counts + R0, r->d_offs + R0, ns * k, d_scan, scan_bytes, m->stream) != hipSuccess)
+            return cleanup(fail(TGX_ERR_DEVICE, "scan launch failed"));
+        time_end(m);
+        uint64_t tc = 0;
+        if (hipMemcpyAsync(&m->h_ctrl[0], m->d_ctrl + 1, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
+            hipMemcpyAsync(&m->h_ctrl[1], r->d_offs + R0 + ns * k, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
+            hipStreamSynchronize(m->stream) != hipSuccess)
+            return cleanup(fail(TGX_ERR_DEVICE, "n-best pass failed: %s", hipGetErrorString(hipGetLastError())));
+        const tgx_status st = check_no_path(m, c);  // chunks go in input order: the first failing one holds the lowest sample
+        if (st != TGX_OK) return cleanup(st);
+        tc = m->h_ctrl[1];
+        uint32_t* ids = nullptr;
+        if (pool_alloc(m->device, (size_t)tc * 4 + 256, (void**)&ids) != hipSuccess)
+            return cleanup(fail(TGX_ERR_DEVICE, "out of device memory (n-best ids)"));
+        parts.push_back({ids, tc});
+        time_begin(m, "nbest_compact_kernel");
+        if (tgx::launch_nbest_compact(p, r->d_offs + R0, ids, (uint32_t)m->num_cus, m->stream) != hipSuccess)
+            return cleanup(fail(TGX_ERR_DEVICE, "nbest_compact_kernel launch failed"));
+        time_end(m);
+        if (total && tgx::launch_offs_add(r->d_offs + R0, ns * k, total, m->stream) != hipSuccess)
+            return cleanup(fail(TGX_ERR_DEVICE, "offset launch failed"));
+        total += tc;
+    }
+    r->n_tokens = total;
+    if (parts.size() == 1) {
+        r->d_ids = parts[0].first;
+        parts.clear();
+    } else {
+        if (pool_alloc(m->device, (size_t)total * 4 + 256, (void**)&r->d_ids) != hipSuccess)
+            return cleanup(fail(TGX_ERR_DEVICE, "out of device memory (result ids)"));
+        uint64_t at = 0;
+        for (auto& pt : parts) {
+            if (pt.second && hipMemcpyAsync(r->d_ids + at, pt.first, (size_t)pt.second * 4, hipMemcpyDeviceToDevice, m->stream) != hipSuccess)
+                return cleanup(fail(TGX_ERR_DEVICE, "n-best gather failed"));
+            at += pt.second;
+        }
+    }
+    if ((scores && rows_all && hipMemcpyAsync(scores, d_scores, (size_t)rows_all * 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess) ||
+        (n_found && S && hipMemcpyAsync(n_found, d_nfound, (size_t)S * 4, hipMemcpyDeviceToHost, m->stream) != hipSuccess) ||
+        hipStreamSynchronize(m->stream) != hipSuccess)
+        return cleanup(fail(TGX_ERR_DEVICE, "n-best pass failed: %s", hipGetErrorString(hipGetLastError())));
+    m->h_ctrl[0] = ~0ULL;
+    if (hipMemcpy(&m->h_ctrl[0], m->d_ctrl + 1, 8, hipMemcpyDeviceToHost) != hipSuccess)
+        return cleanup(fail(TGX_ERR_DEVICE, "n-best pass failed"));
+    const tgx_status st = check_no_path(m, c);  // (a corrupt back-pointer found by the trace: never a fault)
+    if (st != TGX_OK) return cleanup(st);
+    m->last_alg_bytes = c->n_bytes + 4 * r->n_tokens + 8 * (rows_all + 1) + 12 * rows_all;
+    *out = r;
+    return cleanup(TGX_OK);
+}
+
+tgx_status tgx_encode_corpus_nbest(tgx_model* m, tgx_corpus* c, uint32_t nbest, double* scores, uint32_t* n_found, tgx_result** out) {
+    if (usable_device_count() <= 0) return fail(TGX_ERR_DEVICE, "no usable HIP device (gfx950 required)");
+    if (!m || !c || !out) return fail(TGX_ERR_INVALID, "tgx_encode_corpus_nbest: NULL argument");
+    *out = nullptr;
+    if (m->device != c->device) return fail(TGX_ERR_INVALID, "model and corpus on different devices");
+    std::lock_guard<std::mutex> lk(m->mu);
+    const tgx_status st = nbest_check(m, nbest);
+    if (st != TGX_OK) return st;
+    std::lock_guard<std::mutex> lkc(c->mu);
+    return nbest_corpus_locked(m, c, nbest, scores, n_found, out);
+}
+
+tgx_status tgx_encode_batch_nbest(tgx_model* m, const uint8_t* text, const uint64_t* offs, uint64_t n_samples, uint32_t nbest,
+                                  double* scores, uint32_t* n_found, tgx_result** out) {
+    if (usable_device_count() <= 0) return fail(TGX_ERR_DEVICE, "no usable HIP device (gfx950 required)");
+    if (!m || !out) return fail(TGX_ERR_INVALID, "tgx_encode_batch_nbest: NULL argument");
+    *out = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(m->mu);
+        const tgx_status st = nbest_check(m, nbest);
+        if (st != TGX_OK) return st;
+    }
+    tgx_corpus* c = nullptr;
+    tgx_status st = tgx_corpus_upload(m->device, text, offs, n_samples, &c);
+    if (st != TGX_OK) return st;
+    st = tgx_encode_corpus_nbest(m, c, nbest, scores, n_found, out);
     tgx_corpus_free(c);
     return st;
 }

@@ -98,6 +98,86 @@ def _split_rows(ids: np.ndarray, offs: np.ndarray) -> list[list[int]]:
     return [flat[o[i]:o[i + 1]] for i in range(len(o) - 1)]
 
 
+def combine_nbest(seg_offs: np.ndarray, seg_special: np.ndarray, base_vocab: int, ids: np.ndarray, id_offs: np.ndarray,
+                  scores: np.ndarray, n_found: np.ndarray, nbest: int):
+    """Per-segment n-best lists -> per-sample lists (Tokenizer.encode_batch_nbest_flat).  `ids` / `id_offs` / `scores` /
+    `n_found` are the device's output over the non-special segments (nbest rows each).  A sample's list is the k-best
+    product of its segments' lists, taken left to right: the candidates (C[i].score + Lseg[j].score, i, j), ordered by
+    score descending, then i, then j; the top nbest are kept.  Special tokens add nothing to the score; a sample without
+    non-special segments has one row of score 0.0.  Samples made of one non-special segment are mapped directly.
+    -> (ids u32, offsets u64[S·nbest+1], scores f64[S·nbest], n_found u32[S])."""
+    k = int(nbest)
+    seg_offs = seg_offs.astype(np.int64)
+    n = seg_offs.shape[0] - 1
+    ss = np.asarray(seg_special, np.int64)
+    id_offs = id_offs.astype(np.int64)
+    nseg = np.diff(seg_offs)
+    text_idx = np.cumsum(ss < 0) - 1  # segment -> its index among the non-special segments
+    first = np.minimum(seg_offs[:-1], max(ss.size - 1, 0))
+    simple = (nseg == 1) & (ss[first] < 0) if ss.size else np.zeros(n, bool)
+    out_scores = np.full(n * k, -np.inf)
+    out_nf = np.zeros(n, np.uint32)
+    sp_base = int(ids.shape[0])  # special token t sits at sp_base + t of the pool
+    n_sp = int(ss.max()) + 1 if ss.size and ss.max() >= 0 else 0
+    pool = np.concatenate([ids.astype(np.uint32), (base_vocab + np.arange(n_sp)).astype(np.uint32)])
+    # one non-special segment: its rows are the sample's
+    s1 = np.nonzero(simple)[0]
+    j1 = text_idx[seg_offs[s1]]
+    rows = (s1[:, None] * k + np.arange(k)[None, :]).ravel()
+    src = (j1[:, None] * k + np.arange(k)[None, :]).ravel()
+    out_scores[rows] = scores[src]
+    out_nf[s1] = n_found[j1]
+    p_row, p_start, p_len = [rows], [id_offs[src]], [id_offs[src + 1] - id_offs[src]]
+    # no segment (an empty sample): one empty row
+    s0 = np.nonzero(nseg == 0)[0]
+    out_scores[s0 * k] = 0.0
+    out_nf[s0] = 1
+    # the rest (specials, several segments): the product, sample by sample
+    rr, rs, rl = [], [], []
+    for s in np.nonzero(~simple & (nseg > 0))[0].tolist():
+        cur = [(0.0, [])]
+        for g in range(int(seg_offs[s]), int(seg_offs[s + 1])):
+            if ss[g] >= 0:
+                cur = [(sc, pcs + [(sp_base + int(ss[g]), 1)]) for sc, pcs in cur]
+                continue
+            j = int(text_idx[g])
+            cands = [(cur[i][0] + float(scores[j * k + jj]), i, jj) for i in range(len(cur)) for jj in range(int(n_found[j]))]
+            cands.sort(key=lambda t: (-t[0], t[1], t[2]))
+            cur = [(sc, cur[i][1] + [(int(id_offs[j * k + jj]), int(id_offs[j * k + jj + 1] - id_offs[j * k + jj]))])
+                   for sc, i, jj in cands[:k]]
+        out_nf[s] = len(cur)
+        for r, (sc, pcs) in enumerate(cur):
+            out_scores[s * k + r] = sc
+            for st, ln in pcs:
+                rr.append(s * k + r)
+                rs.append(st)
+                rl.append(ln)
+    p_row.append(np.asarray(rr, np.int64))
+    p_start.append(np.asarray(rs, np.int64))
+    p_len.append(np.asarray(rl, np.int64))
+    p_row, p_start, p_len = np.concatenate(p_row), np.concatenate(p_start), np.concatenate(p_len)
+    o = np.argsort(p_row, kind="stable")
+    p_row, p_start, p_len = p_row[o], p_start[o], p_len[o]
+    out_offs = np.zeros(n * k + 1, np.uint64)
+    out_offs[1:] = np.cumsum(np.bincount(p_row, weights=p_len, minlength=n * k).astype(np.int64))
+    total = int(out_offs[-1])
+    at = np.cumsum(p_len) - p_len
+    idx = np.repeat(p_start - at, p_len) + np.arange(total)
+    return pool[idx], out_offs, out_scores, out_nf
+
+
+def nbest_draw(scores: np.ndarray, n_found: np.ndarray, alpha: float, seed: int) -> np.ndarray:
+    """The row each sample draws from its n-best list (scores f64[S, k]): the largest alpha · score_r − log(−log u_r),
+    u_r = tgx_sample_u01(seed, i, r, 0), over r < n_found[i]; ties to the lower r."""
+    S, k = scores.shape
+    i = np.repeat(np.arange(S, dtype=np.uint64), k)
+    r = np.tile(np.arange(k, dtype=np.uint64), S)
+    u = _lib.sample_u01_array(seed, i, r, np.zeros(S * k, np.uint64)).reshape(S, k)
+    valid = np.arange(k)[None, :] < np.asarray(n_found, np.int64)[:, None]
+    key = np.where(valid, float(alpha) * np.where(valid, scores, 0.0) - np.log(-np.log(u)), -np.inf)
+    return np.argmax(key, axis=1) if S else np.zeros(0, np.int64)
+
+
 # ---- Tokenizer ---------------------------------------------------------------------
 
 class Tokenizer:
@@ -304,6 +384,72 @@ class Tokenizer:
         seg_sample = np.repeat(np.arange(n), np.diff(seg_offs.astype(np.int64)))
         logz = np.bincount(seg_sample[ss < 0], weights=seg_logz, minlength=n).astype(np.float64) if n else np.zeros(0)
         return out[0], out[1], logz
+
+    # -- n-best segmentation: the k highest-scoring segmentations per sample (csrc/nbest.hip) --
+    def encode_nbest(self, text: str, nbest: int) -> list[list[int]]:
+        return self.encode_batch_nbest([text], nbest)[0]
+
+    def encode_batch_nbest(self, texts: list[str], nbest: int) -> list[list[list[int]]]:
+        """Per sample, up to nbest segmentations (id lists), best first (SentencePiece's NBestEncode)."""
+        text_b, offs_b = _fast.pack_strs(texts)
+        ids, o, _, nf = self.encode_batch_nbest_flat(np.frombuffer(text_b, dtype=np.uint8), np.frombuffer(offs_b, dtype=np.uint64),
+                                                     nbest)
+        rows = _split_rows(ids, o)
+        k = int(nbest)
+        return [rows[i * k:i * k + int(nf[i])] for i in range(len(texts))]
+
+    def encode_batch_nbest_flat(self, flat: np.ndarray, offs: np.ndarray, nbest: int, ordinary: bool = False):
+        """encode_batch_flat with the nbest best segmentations of every sample -> (ids uint32[T], offsets u64[S·nbest+1],
+        scores f64[S·nbest], n_found u32[S]); row s·nbest + r is the r-th best of sample s, rows at or beyond n_found are
+        empty with score -inf.  Specials keep their ids and add nothing to the score; a sample split by specials gets the
+        k-best product of its segments' lists (combine_nbest)."""
+        if not self._native_front():
+            raise TokenGeeXError("encode_batch_nbest_flat: a processor without a packed-buffer form", _lib.ERR_UNSUPPORTED)
+        k = int(nbest)
+        if not 1 <= k <= _lib.MAX_NBEST:
+            raise TokenGeeXError(f"nbest must be in 1..{_lib.MAX_NBEST} (got {nbest})", _lib.ERR_INVALID)
+        flat = np.ascontiguousarray(flat, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        only_crlf = all(isinstance(p, CrlfProcessor) for p in self._processors)
+        crlf = only_crlf and len(self._processors) > 0
+        n = offs.shape[0] - 1
+
+        def run(pflat, poffs):
+            if poffs.shape[0] <= 1:
+                return np.zeros(0, np.uint32), np.zeros(1, np.uint64), np.zeros(0, np.float64), np.zeros(0, np.uint32)
+            res, sc, nf = self._model().encode_batch_nbest_flat(pflat, poffs, k)
+            try:
+                return res.ids(), res.offsets(), sc, nf
+            finally:
+                res.free()
+
+        if ordinary or not self._special_tokens:
+            if n and self._processors:
+                flat, offs = self._preprocess_flat(flat, offs)
+            return run(flat, offs)
+        seg_offs, sb, se, ss = _lib.split_specials_flat(flat, offs, [t.encode("utf-8") for t in self._special_tokens])
+        pflat, poffs = _lib.pack_segments(flat, sb, se, ss, crlf)
+        if not only_crlf and poffs.shape[0] > 1:
+            pflat, poffs = self._preprocess_flat(pflat, poffs)
+        ids, id_offs, sc, nf = run(pflat, poffs)
+        return combine_nbest(seg_offs, ss, self.base_vocab_size(), ids, id_offs, sc, nf, k)
+
+    def encode_nbest_sample(self, text: str, nbest: int, alpha: float, seed: int | None = None) -> list[int]:
+        return self.encode_batch_nbest_sample([text], nbest, alpha, seed)[0]
+
+    def encode_batch_nbest_sample(self, texts: list[str], nbest: int, alpha: float, seed: int | None = None) -> list[list[int]]:
+        """One segmentation per sample drawn from its n-best list with P ∝ exp(alpha · score) (SentencePiece's
+        SampleEncode with nbest_size > 1): the row with the largest alpha · score_r − log(−log u_r) wins, u_r =
+        tgx_sample_u01(seed, i, r, 0) for sample i of the batch, ties to the lower r."""
+        if not (alpha >= 0.0 and np.isfinite(alpha)):
+            raise TokenGeeXError(f"alpha must be finite and >= 0 (got {alpha})", _lib.ERR_INVALID)
+        seed = self._sample_seed(seed)
+        text_b, offs_b = _fast.pack_strs(texts)
+        ids, o, sc, nf = self.encode_batch_nbest_flat(np.frombuffer(text_b, dtype=np.uint8), np.frombuffer(offs_b, dtype=np.uint64),
+                                                      nbest)
+        pick = nbest_draw(sc.reshape(len(texts), int(nbest)), nf, alpha, seed)
+        rows = np.arange(len(texts)) * int(nbest) + pick
+        return [ids[int(o[r]):int(o[r + 1])].tolist() for r in rows.tolist()]
 
     # -- decode: src/tokenizer.rs:126-187, src/model.rs:146-160 --
     def _model_decode(self, ids) -> str:
