@@ -316,13 +316,9 @@ def test_long_token_vocabularies(monkeypatch, max_len, path):
 
 
 @pytest.mark.parametrize("max_len", [16, 24])
-def test_token_end_mask_pipeline(monkeypatch, max_len):
-    """TGX_TRACE=mask (trace2.hip): the back-trace only marks token ends in a per-sample bit mask, a popcount scan
-    numbers the tokens, emit_kernel looks the ids up and writes them in place — no `tmp`, no compaction.  Kept as the
-    measured alternative (1.3 ms per GiB slower than trace + compact); ids, offsets and errors as the
-    default's: bit-exact against the oracle, with empty samples, dropout, samples of 1 .. 200 bytes (a word of the mask
-    and less) and an unreachable end."""
-    monkeypatch.setenv("TGX_TRACE", "mask")
+def test_trace_and_compact_edge_cases(max_len):
+    """The back-trace and compact_kernel at the edges: ids, offsets and errors bit-exact against the oracle, with empty
+    samples, dropout, samples of 1 .. 200 bytes and an unreachable end."""
     rng = np.random.default_rng(77 + max_len)
     flat, offs = synth.make_corpus(512 << 10, "mixed", seed_offset=31 + max_len, max_len=20000)
     if max_len == 16:
@@ -332,7 +328,7 @@ def test_token_end_mask_pipeline(monkeypatch, max_len):
     nat, ora = tgx.NativeModel(toks, scores), orc.OracleModel(toks, scores)
     assert_same_encoding(nat, ora, flat, offs)
     kt = nat.last_kernel_times()
-    assert "mark_kernel" in kt and "emit_kernel" in kt and "compact_kernel" not in kt
+    assert "compact_kernel" in kt
     assert_same_encoding(nat, ora, flat, offs, dropout=0.3, seed=9)
     texts = [b"", b"a", b"", b"ab" * 16, b"ab" * 32, b"ab" * 32 + b"a", b"q" * 63, b"q" * 64, b"q" * 65, b"", b"hello world " * 40, b""]
     texts += [bytes(flat[i * 211: i * 211 + n]) for i, n in enumerate(range(1, 200))]

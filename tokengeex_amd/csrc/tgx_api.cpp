@@ -164,6 +164,50 @@ void pool_free(int device, void* ptr, size_t bytes) {
     if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
 }
 
+// A pooled device buffer with one owner: (device, ptr, bytes), bytes being the rounded size it was asked with (what the
+// pool files it under).  It goes back to the pool exactly once: on reset(), on the next alloc() or with its owner.
+template <class T>
+class PoolBuf {
+public:
+    PoolBuf() = default;
+    PoolBuf(const PoolBuf&) = delete;
+    PoolBuf& operator=(const PoolBuf&) = delete;
+    PoolBuf(PoolBuf&& o) noexcept : device_(o.device_), ptr_(o.ptr_), bytes_(o.bytes_) { o.ptr_ = nullptr; }
+    PoolBuf& operator=(PoolBuf&& o) noexcept {
+        if (this != &o) {
+            reset();
+            device_ = o.device_;
+            ptr_ = o.ptr_;
+            bytes_ = o.bytes_;
+            o.ptr_ = nullptr;
+        }
+        return *this;
+    }
+    ~PoolBuf() { reset(); }
+
+    hipError_t alloc(int device, size_t bytes) {
+        reset();
+        void* p = nullptr;
+        const hipError_t e = pool_alloc(device, bytes, &p);
+        if (e != hipSuccess) return e;
+        device_ = device;
+        ptr_ = static_cast<T*>(p);
+        bytes_ = rounded(bytes);
+        return hipSuccess;
+    }
+    void reset() {
+        if (ptr_) pool_free(device_, ptr_, bytes_);
+        ptr_ = nullptr;
+    }
+    T* get() const { return ptr_; }
+    operator T*() const { return ptr_; }
+
+private:
+    int device_ = 0;
+    T* ptr_ = nullptr;
+    size_t bytes_ = 0;
+};
+
 struct KernelTime {
     const char* name;
     hipEvent_t start, stop;
@@ -205,7 +249,6 @@ struct tgx_model {
     bool values_ranked = false;        // the score values were re-ranked by how often a sample of some corpus reads them (ensure_value_ranks)
     uint32_t corun_wait_timeouts = 0;  // co-run passes whose host wait for encode5_kernel's blocks ran into its 2 ms limit (then: no more co-runs)
     uint64_t last_redo_samples = 0;    // samples the last encode4l pass left to encode2_kernel
-    bool mask_path = false;            // the last encode pass wrote the token-end mask (TGX_TRACE=mask: mark / scan / emit, trace2.hip)
     int last_encode_waves_per_cu = 0;  // resident waves per CU of the last rows4 encode launch (self-check)
     bool estep_linear_ok = false;   // tables for the linear-domain E-step kernels exist
     tgx::TokHashTable tokhash;      // token bytes -> id (rows4 trace); ok == false: not usable
@@ -243,23 +286,13 @@ struct tgx_corpus {
     std::vector<uint64_t> h_offs;
     std::vector<uint32_t> h_sorted_len;  // sample lengths in the order of d_order (longest first) ...
     std::vector<uint64_t> h_sorted_cum;  // ... and their running sum
+    PoolBuf<uint8_t> d_text_alloc;
     uint8_t* d_text = nullptr;        // = d_text_alloc + 256 (the backward E-step sweep reads before a position)
-    uint8_t* d_text_alloc = nullptr;
-    uint64_t* d_offs = nullptr;
-    uint32_t* d_order = nullptr;
-    uint32_t* d_bp = nullptr;      // scratch, allocated on first pass
-    uint32_t* d_tmp = nullptr;
-    uint32_t* d_counts = nullptr;
-    uint32_t* d_status = nullptr;
-    void* d_scan_tmp = nullptr;
+    PoolBuf<uint64_t> d_offs;
+    PoolBuf<uint32_t> d_order;
+    PoolBuf<uint32_t> d_bp, d_tmp, d_counts, d_status;  // scratch, allocated on first pass (ensure_scratch)
+    PoolBuf<void> d_scan_tmp;
     size_t scan_tmp_bytes = 0;
-    // round 4 (trace2.hip): one bit per text byte ("a token ends here") and its popcount prefix, allocated on first pass
-    unsigned long long* d_endmask = nullptr;
-    uint64_t* d_prefix = nullptr;
-    uint64_t* d_mword = nullptr;       // u64[S + 1]: the samples' first mask words
-    void* d_mscan_tmp = nullptr;
-    size_t mscan_tmp_bytes = 0;
-    uint64_t mask_words = 0;
     // E-step work list of the corpus (every sample cut at multiples of snippet_len, longest snippet first) and its
     // device copies: built on the first pass with a given snippet length, reused by the following ones (prune
     // runs two E-steps per iteration over the same corpus; building and sorting the list took 5 of 65 ms at 1 GiB)
@@ -267,14 +300,12 @@ struct tgx_corpus {
         uint64_t snippet_len = 0;
         std::vector<uint64_t> soffs, sbase;
         std::vector<uint32_t> ssample, order;
-        uint64_t *d_soffs = nullptr, *d_sbase = nullptr;
-        uint32_t *d_order = nullptr, *d_ssample = nullptr;
-        size_t obytes = 0, ordbytes = 0;
+        PoolBuf<uint64_t> d_soffs, d_sbase;
+        PoolBuf<uint32_t> d_order, d_ssample;
         // windows of the snippets (cuts.hip: one boundary is sought per window): built with the work list
         uint32_t window = 0;
         uint64_t n_windows = 0;
-        uint32_t *d_win_snip = nullptr, *d_win_k = nullptr;
-        size_t winbytes = 0;
+        PoolBuf<uint32_t> d_win_snip, d_win_k;
     } es;
     // the scratch above belongs to the corpus, so a pass holds this lock too (always after its model's):
     // two models may work on one resident corpus from two host threads (prune and merge do, src/prune.rs:48)
@@ -284,14 +315,58 @@ struct tgx_corpus {
 struct tgx_result {
     int device = 0;
     uint64_t n_samples = 0, n_tokens = 0;
-    uint32_t* d_ids = nullptr;
-    uint64_t* d_offs = nullptr;
+    PoolBuf<uint32_t> d_ids;
+    PoolBuf<uint64_t> d_offs;
     std::unique_ptr<uint32_t[]> h_ids;  // uninitialised: a vector would zero a GB first
     std::vector<uint64_t> h_offs;
     bool have_ids = false, have_offs = false;
 };
 
 namespace {
+
+// One pass over a corpus (encode, sampling, n-best, a frequency, pair or E-step pass, a re-rank of a model's tables): it
+// owns the pass's scratch and the result it builds.  A pass that fails may have queued kernels that still read or write
+// those buffers, the corpus's scratch or the result, so the model's streams are synchronised before anything goes back to
+// the pool, where another caller could take it.  A pass that succeeds says so with done(): every success path has
+// synchronised its stream already (or ended in a synchronous copy), and gains no synchronisation here.
+class Pass {
+public:
+    explicit Pass(tgx_model* m) : m_(m) {}
+    Pass(const Pass&) = delete;
+    Pass& operator=(const Pass&) = delete;
+    ~Pass() {
+        if (ok_) return;
+        (void)hipStreamSynchronize(m_->stream);
+        if (m_->stream2) (void)hipStreamSynchronize(m_->stream2);
+    }  // (then the members go: the scratch and an unclaimed result)
+
+    template <class T>
+    hipError_t alloc(size_t bytes, T** out) {
+        PoolBuf<void> b;
+        const hipError_t e = b.alloc(m_->device, bytes);
+        *out = static_cast<T*>(b.get());
+        if (e == hipSuccess) scratch_.push_back(std::move(b));
+        return e;
+    }
+    tgx_result* new_result(uint64_t n_samples) {
+        result_.reset(new tgx_result());
+        result_->device = m_->device;
+        result_->n_samples = n_samples;
+        return result_.get();
+    }
+    tgx_result* release_result() { return result_.release(); }
+    void adopt_result(tgx_result* r) { result_.reset(r); }
+    tgx_status done() {
+        ok_ = true;
+        return TGX_OK;
+    }
+
+private:
+    tgx_model* m_;
+    bool ok_ = false;
+    std::vector<PoolBuf<void>> scratch_;
+    std::unique_ptr<tgx_result> result_;
+};
 
 int usable_device_count() {
     int n = 0;
@@ -347,30 +422,14 @@ void time_end(tgx_model* m) {
     m->n_timed++;
 }
 
-// mask: the ids go through the token-end mask (TGX_TRACE=mask: mark / scan / emit, trace2.hip — the measured
-// alternative, 1.3 ms per GiB slower); else right-aligned in `tmp` and compacted (the default)
-tgx_status ensure_scratch(tgx_corpus* c, bool mask) {
-    const bool rows = mask;
+// the encode and sampling passes' scratch: back-pointers, ids right-aligned in `tmp` (then compacted), counts, status
+tgx_status ensure_scratch(tgx_corpus* c) {
     HIP_TRY(hipSetDevice(c->device));
-    if (!c->d_bp) {
-        // u32[N] for the one-sample-per-wave kernel; the rows4 kernels use it as bytes, N + 128 per sample
-        HIP_TRY(pool_alloc(c->device, std::max((size_t)c->n_bytes * 4 + 256, (size_t)c->n_bytes + 128 * (size_t)c->n_samples + 512), (void**)&c->d_bp));
-        HIP_TRY(pool_alloc(c->device, (size_t)c->n_samples * 4 + 256, (void**)&c->d_counts));
-        HIP_TRY(pool_alloc(c->device, (size_t)c->n_samples * 4 + 256, (void**)&c->d_status));
-    }
-    if (!rows && !c->d_tmp) HIP_TRY(pool_alloc(c->device, (size_t)c->n_bytes * 4 + 256, (void**)&c->d_tmp));
-    if (rows && !c->d_endmask) {
-        std::vector<uint64_t> mword(c->n_samples + 1, 0);  // sample s owns ceil(n / 64) words of the mask
-        for (uint64_t i = 0; i < c->n_samples; i++) mword[i + 1] = mword[i] + (c->h_offs[i + 1] - c->h_offs[i] + 63) / 64;
-        c->mask_words = mword[c->n_samples];
-        HIP_TRY(pool_alloc(c->device, (size_t)(c->n_samples + 1) * 8 + 256, (void**)&c->d_mword));
-        HIP_TRY(hipMemcpy(c->d_mword, mword.data(), (size_t)(c->n_samples + 1) * 8, hipMemcpyHostToDevice));
-        HIP_TRY(pool_alloc(c->device, (size_t)(c->mask_words + 1) * 8 + 256, (void**)&c->d_endmask));
-        HIP_TRY(hipMemset(c->d_endmask + c->mask_words, 0, 8));  // the word of padding (the scan's last element)
-        HIP_TRY(pool_alloc(c->device, (size_t)(c->mask_words + 1) * 8 + 256, (void**)&c->d_prefix));
-        HIP_TRY(tgx::mask_scan_temp_bytes(c->mask_words, &c->mscan_tmp_bytes));
-        if (c->mscan_tmp_bytes) HIP_TRY(pool_alloc(c->device, c->mscan_tmp_bytes, &c->d_mscan_tmp));
-    }
+    // u32[N] for the one-sample-per-wave kernel; the rows4 kernels use it as bytes, N + 128 per sample
+    if (!c->d_bp) HIP_TRY(c->d_bp.alloc(c->device, std::max((size_t)c->n_bytes * 4 + 256, (size_t)c->n_bytes + 128 * (size_t)c->n_samples + 512)));
+    if (!c->d_counts) HIP_TRY(c->d_counts.alloc(c->device, (size_t)c->n_samples * 4 + 256));
+    if (!c->d_status) HIP_TRY(c->d_status.alloc(c->device, (size_t)c->n_samples * 4 + 256));
+    if (!c->d_tmp) HIP_TRY(c->d_tmp.alloc(c->device, (size_t)c->n_bytes * 4 + 256));
     return TGX_OK;
 }
 
@@ -398,16 +457,11 @@ tgx_status ensure_value_ranks(tgx_model* m, const tgx_corpus* c) {
     const uint32_t nv = m->n_values, chunk = 65536u;
     const uint64_t stride = std::max<uint64_t>(chunk, (c->n_bytes + 63) / 64);
     const size_t cb = ((size_t)nv + 1) * 4 + 256;
+    Pass pass(m);
     unsigned int* d_cnt = nullptr;
     uint32_t* d_perm = nullptr;
-    auto drop = [&]() {
-        pool_free(m->device, d_cnt, cb);
-        pool_free(m->device, d_perm, cb);
-    };
-    if (pool_alloc(m->device, cb, (void**)&d_cnt) != hipSuccess || pool_alloc(m->device, cb, (void**)&d_perm) != hipSuccess) {
-        drop();
+    if (pass.alloc(cb, &d_cnt) != hipSuccess || pass.alloc(cb, &d_perm) != hipSuccess)
         return fail(TGX_ERR_DEVICE, "out of device memory (value counts)");
-    }
     std::vector<unsigned int> cnt((size_t)nv + 1, 0u);
     std::vector<double> values((size_t)nv + 1), wvalues;
     bool ok = hipMemsetAsync(d_cnt, 0, cb, m->stream) == hipSuccess &&
@@ -419,10 +473,8 @@ tgx_status ensure_value_ranks(tgx_model* m, const tgx_corpus* c) {
         wvalues.resize((size_t)nv + 1);
         ok = hipMemcpyAsync(wvalues.data(), m->d_wvalues, ((size_t)nv + 1) * 8, hipMemcpyDeviceToHost, m->stream) == hipSuccess;
     }
-    if (!ok || hipStreamSynchronize(m->stream) != hipSuccess) {
-        drop();
+    if (!ok || hipStreamSynchronize(m->stream) != hipSuccess)
         return fail(TGX_ERR_DEVICE, "value count pass failed: %s", hipGetErrorString(hipGetLastError()));
-    }
     hp.mark("value counts");
     std::vector<uint32_t> order(nv);
     for (uint32_t r = 0; r < nv; r++) order[r] = r + 1u;
@@ -447,22 +499,16 @@ tgx_status ensure_value_ranks(tgx_model* m, const tgx_corpus* c) {
          hipMemcpyAsync(m->d_values, v2.data(), ((size_t)nv + 1) * 8, hipMemcpyHostToDevice, m->stream) == hipSuccess &&
          (w2.empty() || hipMemcpyAsync(m->d_wvalues, w2.data(), ((size_t)nv + 1) * 8, hipMemcpyHostToDevice, m->stream) == hipSuccess) &&
          hipStreamSynchronize(m->stream) == hipSuccess;
-    drop();
     if (!ok) return fail(TGX_ERR_DEVICE, "value re-rank failed: %s", hipGetErrorString(hipGetLastError()));
     m->value_coverage = std::move(cov);
     hp.mark("re-rank");
-    return TGX_OK;
+    return pass.done();
 }
 
-// Runs the wave-per-sample kernel over the corpus; on return (stream synced)
-// h_ctrl[0] = min failing sample (~0 if none).
-tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64_t seed) {
-    {
-        const char* force0 = knob("TGX_PATH");
-        const char* tr = knob("TGX_TRACE");
-        m->mask_path = tr && strcmp(tr, "mask") == 0 && m->lm <= 32 && m->scores_finite && m->d_tokhash && !(force0 && strcmp(force0, "fused") == 0);
-    }
-    tgx_status st = ensure_scratch(c, m->mask_path);
+// Queues the encode kernels and the back-trace over the corpus: every sample's token count in c->d_counts, its ids
+// right-aligned in c->d_tmp, the lowest failing sample in d_ctrl[1].  Diagnostic scratch belongs to `pass`.
+tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64_t seed, Pass& pass) {
+    tgx_status st = ensure_scratch(c);
     if (st != TGX_OK) return st;
     HIP_TRY(hipMemsetAsync(m->d_ctrl, 0x00, 8, m->stream));
     HIP_TRY(hipMemsetAsync(m->d_ctrl + 1, 0xFF, 8, m->stream));
@@ -480,7 +526,7 @@ tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64
     p.tmp = c->d_tmp;
     p.counts = c->d_counts;
     p.status = c->d_status;
-    p.bp8 = reinterpret_cast<uint8_t*>(c->d_bp);  // the rows4 path uses the scratch row as bytes
+    p.bp8 = reinterpret_cast<uint8_t*>(c->d_bp.get());  // the rows4 path uses the scratch row as bytes
     p.tokhash = m->d_tokhash;
     p.tokhash_mask = m->tokhash.mask;
     p.tokhash_seed = m->tokhash.seed;
@@ -492,10 +538,6 @@ tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64
     // 5.5 -> 4.6 ms per GiB, 9 KiB samples 2.93 -> 3.04)
     p.trace_carry = (c->n_samples && c->n_bytes / c->n_samples < 2048) ? 1u : 0u;
     if (const char* e = knob("TGX_TRACE_CARRY")) p.trace_carry = atoi(e) ? 1u : 0u;
-    p.endmask = c->d_endmask;
-    p.mword = c->d_mword;
-    p.mask_words = c->mask_words;
-    p.prefix = c->d_prefix;
     {
         // timing experiments (tools/ablate.py) — results are WRONG when set; honoured only with TGX_DEBUG=1
         const char* f = debug_on() ? getenv("TGX_FLAGS") : nullptr;
@@ -785,11 +827,8 @@ tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64
         const size_t n_stamp_waves5 = (size_t)blocks5 * (size_t)waves;
         if (const char* e = debug_on() ? getenv("TGX_STAMPS") : nullptr) {
             if (*e == '1') {
-                if (pool_alloc(m->device, n_stamp_waves5 * 64, (void**)&d_stamps5) != hipSuccess) return fail(TGX_ERR_DEVICE, "out of device memory (stamps)");
-                if (hipMemsetAsync(d_stamps5, 0, n_stamp_waves5 * 64, m->stream) != hipSuccess) {
-                    pool_free(m->device, d_stamps5, n_stamp_waves5 * 64);
-                    return fail(TGX_ERR_DEVICE, "stamps reset failed");
-                }
+                if (pass.alloc(n_stamp_waves5 * 64, &d_stamps5) != hipSuccess) return fail(TGX_ERR_DEVICE, "out of device memory (stamps)");
+                if (hipMemsetAsync(d_stamps5, 0, n_stamp_waves5 * 64, m->stream) != hipSuccess) return fail(TGX_ERR_DEVICE, "stamps reset failed");
                 p.stamps = d_stamps5;
             }
         }
@@ -802,13 +841,7 @@ tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64
             }
             // (co-run: more than half of the CU's LDS, so that no block of the long-sample kernel shares the CU)
             const hipError_t le = tgx::launch_encode5(p, q, cold, ppl, long_tokens, waves, blocks5, corun_cus && n_long ? 84u * 1024u : 0u, m->stream);
-            if (le != hipSuccess) {
-                if (d_stamps5) {
-                    (void)hipStreamSynchronize(m->stream);
-                    pool_free(m->device, d_stamps5, n_stamp_waves5 * 64);
-                }
-                return fail(TGX_ERR_DEVICE, "encode5 launch failed: %s", hipGetErrorString(le));
-            }
+            if (le != hipSuccess) return fail(TGX_ERR_DEVICE, "encode5 launch failed: %s", hipGetErrorString(le));
         }
         bool joined = false, joined_slot = false;
         if (n_long && corun_cus) {  // the long-sample kernel beside it, on the second stream, with a timing slot of its own
@@ -831,11 +864,7 @@ tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64
             const hipError_t l6 = tgx::launch_encode6(p6, q6, cold6, blocks6, m->stream2);
             if (slot) (void)hipEventRecord(m->timed[m->n_timed + 1].stop, m->stream2);
             (void)hipEventRecord(m->ev_join, m->stream2);
-            if (l6 != hipSuccess) {
-                (void)hipStreamSynchronize(m->stream);
-                (void)hipStreamSynchronize(m->stream2);
-                return fail(TGX_ERR_DEVICE, "encode6 launch failed: %s", hipGetErrorString(l6));
-            }
+            if (l6 != hipSuccess) return fail(TGX_ERR_DEVICE, "encode6 launch failed: %s", hipGetErrorString(l6));
             joined = true;
             joined_slot = slot;
         }
@@ -848,7 +877,6 @@ tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64
             std::vector<unsigned long long> h(n_stamp_waves5 * 8);
             const bool ok = hipStreamSynchronize(m->stream) == hipSuccess &&
                             hipMemcpy(h.data(), d_stamps5, n_stamp_waves5 * 64, hipMemcpyDeviceToHost) == hipSuccess;
-            pool_free(m->device, d_stamps5, n_stamp_waves5 * 64);
             p.stamps = nullptr;
             if (!ok) return fail(TGX_ERR_DEVICE, "stamps copy failed");
             double sum[5] = {0, 0, 0, 0, 0}, iters = 0;
@@ -879,9 +907,8 @@ tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64
         p.n_samples = c->n_samples;
         const uint32_t blocks_t =
             (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((c->n_samples + 3) / 4, (uint64_t)m->num_cus * 8));
-        time_begin(m, m->mask_path ? "mark_kernel" : long_tokens ? "trace32_kernel" : "trace_kernel");
-        if (m->mask_path) HIP_TRY(tgx::launch_mark(p, blocks_t, long_tokens ? 32u : 16u, true, m->stream));
-        else if (long_tokens) HIP_TRY(tgx::launch_trace32(p, blocks_t, true, m->stream));
+        time_begin(m, long_tokens ? "trace32_kernel" : "trace_kernel");
+        if (long_tokens) HIP_TRY(tgx::launch_trace32(p, blocks_t, true, m->stream));
         else HIP_TRY(tgx::launch_trace(p, blocks_t, m->stream));
         time_end(m);
     } else if (use4) {
@@ -981,9 +1008,8 @@ tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64
         p.n_samples = c->n_samples;
         const uint32_t blocks_t =
             (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((c->n_samples + 3) / 4, (uint64_t)m->num_cus * 8));
-        time_begin(m, m->mask_path ? "mark_kernel" : "trace_kernel");
-        if (m->mask_path) HIP_TRY(tgx::launch_mark(p, blocks_t, 16u, true, m->stream));
-        else HIP_TRY(tgx::launch_trace(p, blocks_t, m->stream));
+        time_begin(m, "trace_kernel");
+        HIP_TRY(tgx::launch_trace(p, blocks_t, m->stream));
         time_end(m);
     } else if (use2) {
         // Tokens of 17..32 bytes: the 16-lane rows with an overflow list for the long matches (encode4l.hip);
@@ -1019,9 +1045,8 @@ tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64
             HIP_TRY(tgx::launch_encode2(p, (uint32_t)m->num_cus, false, m->stream));
             time_end(m);
         }
-        time_begin(m, m->mask_path ? "mark_kernel" : "trace32_kernel");
-        if (m->mask_path) HIP_TRY(tgx::launch_mark(p, blocks_t, 32u, !rows2, m->stream));
-        else HIP_TRY(tgx::launch_trace32(p, blocks_t, !rows2, m->stream));
+        time_begin(m, "trace32_kernel");
+        HIP_TRY(tgx::launch_trace32(p, blocks_t, !rows2, m->stream));
         time_end(m);
     } else {
         time_begin(m, "encode_kernel");
@@ -1044,6 +1069,57 @@ tgx_status check_no_path(tgx_model* m, const tgx_corpus* c) {
     // Display of Error::NoPath, reference src/lib.rs:243-245
     return fail(TGX_ERR_NO_PATH, "no path to position %llu/%llu", (unsigned long long)n,
                 (unsigned long long)n);
+}
+
+// The ids of an encode or sampling pass whose kernels left every sample's token count in c->d_counts and its ids
+// right-aligned in c->d_tmp: the counts scanned into r's offsets, the lowest failing sample and the total read back,
+// the ids buffer, the compaction.  The compaction is queued, not waited for.  `what` names the pass in messages.
+tgx_status compact_ids(tgx_model* m, tgx_corpus* c, tgx_result* r, const char* what) {
+    const uint64_t S = c->n_samples;
+    if (!c->d_scan_tmp) {  // scratch of the device-wide scan (large sample counts only), kept on the corpus
+        if (tgx::scan_temp_bytes(S, &c->scan_tmp_bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan temp-size query failed");
+        if (c->scan_tmp_bytes && c->d_scan_tmp.alloc(m->device, c->scan_tmp_bytes) != hipSuccess)
+            return fail(TGX_ERR_DEVICE, "out of device memory (scan)");
+    }
+    time_begin(m, "scan_counts_kernel");
+    if (tgx::launch_scan(c->d_counts, r->d_offs, S, c->d_scan_tmp, c->scan_tmp_bytes, m->stream) != hipSuccess)
+        return fail(TGX_ERR_DEVICE, "scan launch failed");
+    time_end(m);
+    if (hipMemcpyAsync(&m->h_ctrl[0], m->d_ctrl + 1, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
+        hipMemcpyAsync(&m->h_ctrl[1], r->d_offs + S, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
+        hipStreamSynchronize(m->stream) != hipSuccess)
+        return fail(TGX_ERR_DEVICE, "%s pass failed: %s", what, hipGetErrorString(hipGetLastError()));
+    const tgx_status st = check_no_path(m, c);
+    if (st != TGX_OK) return st;
+    r->n_tokens = m->h_ctrl[1];
+    if (r->d_ids.alloc(m->device, (size_t)r->n_tokens * 4 + 256) != hipSuccess)
+        return fail(TGX_ERR_DEVICE, "out of device memory (result ids)");
+    tgx::CompactParams cp{};
+    cp.offs = c->d_offs;
+    cp.order = c->d_order;
+    cp.n_samples = S;
+    cp.tmp = c->d_tmp;
+    cp.out_offs = r->d_offs;
+    cp.ids = r->d_ids;
+    // short samples (fewer than 128 ids on average): a 16-lane row per sample instead of a wave
+    const bool rows = S && r->n_tokens / S < 128;
+    const uint64_t units = rows ? 16 : 4;  // samples per block and round
+    const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((S + units - 1) / units, (uint64_t)m->num_cus * 8));
+    time_begin(m, "compact_kernel");
+    if (tgx::launch_compact(cp, blocks, rows, m->stream) != hipSuccess) return fail(TGX_ERR_DEVICE, "compact launch failed");
+    time_end(m);
+    return TGX_OK;
+}
+
+// the tgx_encode_batch* entry points: the batch uploaded, `run` over the corpus, the corpus freed
+template <class Run>
+tgx_status on_uploaded_batch(const tgx_model* m, const uint8_t* text, const uint64_t* offs, uint64_t n_samples, Run run) {
+    tgx_corpus* c = nullptr;
+    tgx_status st = tgx_corpus_upload(m->device, text, offs, n_samples, &c);
+    if (st != TGX_OK) return st;
+    st = run(c);
+    tgx_corpus_free(c);
+    return st;
 }
 
 }  // namespace
@@ -1202,16 +1278,11 @@ tgx_status tgx_model_create_ex(const uint8_t* bytes, const uint64_t* offs, const
 // the part of model creation after the host tables exist: checks, device tables, uploads
 static tgx_status finish_model_create(tgx_model* m, const uint8_t* bytes, const uint64_t* offs, const double* scores,
                                       uint32_t vocab_size, int device, uint32_t flags, tgx_model** out) {
-    if (m->flat.max_token_len > TGX_MAX_TOKEN_LEN) {
-        uint32_t l = m->flat.max_token_len;
-        delete m;
-        return fail(TGX_ERR_UNSUPPORTED, "token of %u bytes exceeds TGX_MAX_TOKEN_LEN (%d)", l,
+    std::unique_ptr<tgx_model, void (*)(tgx_model*)> owner(m, tgx_model_destroy);  // released on success only
+    if (m->flat.max_token_len > TGX_MAX_TOKEN_LEN)
+        return fail(TGX_ERR_UNSUPPORTED, "token of %u bytes exceeds TGX_MAX_TOKEN_LEN (%d)", m->flat.max_token_len,
                     TGX_MAX_TOKEN_LEN);
-    }
-    if (m->flat.table.size() >= (1u << 26)) {
-        delete m;
-        return fail(TGX_ERR_UNSUPPORTED, "trie needs more than 2^26 slots");
-    }
+    if (m->flat.table.size() >= (1u << 26)) return fail(TGX_ERR_UNSUPPORTED, "trie needs more than 2^26 slots");
     m->lm = std::max<uint32_t>(4, (m->flat.max_token_len + 3) & ~3u);
     if (vocab_size) {
         m->vocab_bytes.assign(bytes + offs[0], bytes + offs[vocab_size]);
@@ -1224,50 +1295,37 @@ static tgx_status finish_model_create(tgx_model* m, const uint8_t* bytes, const 
         m->vocab_offs.assign(1, 0);
     }
 
-    auto cleanup = [&](tgx_status st) {
-        tgx_model_destroy(m);
-        return st;
-    };
-#define HIP_TRY_M(expr)                                                                     \
-    do {                                                                                    \
-        hipError_t _e = (expr);                                                             \
-        if (_e != hipSuccess)                                                               \
-            return cleanup(fail(TGX_ERR_DEVICE, "HIP error %d (%s) at %s:%d: %s", (int)_e,  \
-                                hipGetErrorString(_e), __FILE__, __LINE__, #expr));         \
-    } while (0)
-    HIP_TRY_M(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(device));
     hipDeviceProp_t prop;
-    HIP_TRY_M(hipGetDeviceProperties(&prop, device));
+    HIP_TRY(hipGetDeviceProperties(&prop, device));
     m->num_cus = prop.multiProcessorCount;
-    HIP_TRY_M(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
+    HIP_TRY(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
     size_t tbytes = m->flat.table.size() * sizeof(tgx::TrieRec);
-    HIP_TRY_M(hipMalloc(&m->d_trie, tbytes));
-    HIP_TRY_M(hipMalloc((void**)&m->d_tokid, m->flat.tokid.size() * 4));
-    HIP_TRY_M(hipMalloc((void**)&m->d_ctrl, 64));
+    HIP_TRY(hipMalloc(&m->d_trie, tbytes));
+    HIP_TRY(hipMalloc((void**)&m->d_tokid, m->flat.tokid.size() * 4));
+    HIP_TRY(hipMalloc((void**)&m->d_ctrl, 64));
     // the tables only encode needs (bytes -> id table of the trace, 8-byte records and score table of
     // encode5_kernel): now, unless the model is created for E-step passes — then at its first encode
     if (!(flags & TGX_MODEL_FOR_ESTEP)) {
         const tgx_status est = ensure_encode_tables(m);
-        if (est != TGX_OK) return cleanup(est);
+        if (est != TGX_OK) return est;
     }
-    HIP_TRY_M(hipHostMalloc((void**)&m->h_ctrl, 64, hipHostMallocDefault));
-    HIP_TRY_M(hipMemcpyAsync(m->d_trie, m->flat.table.data(), tbytes, hipMemcpyHostToDevice, m->stream));
-    HIP_TRY_M(hipMemcpyAsync(m->d_tokid, m->flat.tokid.data(), m->flat.tokid.size() * 4,
-                             hipMemcpyHostToDevice, m->stream));
+    HIP_TRY(hipHostMalloc((void**)&m->h_ctrl, 64, hipHostMallocDefault));
+    HIP_TRY(hipMemcpyAsync(m->d_trie, m->flat.table.data(), tbytes, hipMemcpyHostToDevice, m->stream));
+    HIP_TRY(hipMemcpyAsync(m->d_tokid, m->flat.tokid.data(), m->flat.tokid.size() * 4, hipMemcpyHostToDevice, m->stream));
     for (int i = 0; i < kMaxTimed; i++) {
         m->timed[i].used = false;
         m->timed[i].name = "";
-        HIP_TRY_M(hipEventCreate(&m->timed[i].start));
-        HIP_TRY_M(hipEventCreate(&m->timed[i].stop));
+        HIP_TRY(hipEventCreate(&m->timed[i].start));
+        HIP_TRY(hipEventCreate(&m->timed[i].stop));
     }
     {
         int occ = 0;
-        HIP_TRY_M(tgx::encode_max_blocks_per_cu(m->lm, &occ));
+        HIP_TRY(tgx::encode_max_blocks_per_cu(m->lm, &occ));
         m->blocks_per_cu = std::max(1, std::min(occ, 16));
     }
-    HIP_TRY_M(hipStreamSynchronize(m->stream));
-#undef HIP_TRY_M
-    *out = m;
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    *out = owner.release();
     return TGX_OK;
 }
 
@@ -1550,16 +1608,13 @@ tgx_status tgx_corpus_upload(int device, const uint8_t* text, const uint64_t* of
         if (offs[i + 1] - offs[i] >= 0xFFFFFF00ull)
             return fail(TGX_ERR_UNSUPPORTED, "sample %llu is 4 GiB or longer", (unsigned long long)i);
     }
-    tgx_corpus* c = new tgx_corpus();
+    std::unique_ptr<tgx_corpus> c(new tgx_corpus());
     c->device = device;
     c->n_samples = n_samples;
     c->n_bytes = n_samples ? offs[n_samples] - base : 0;
     c->h_offs.resize(n_samples + 1);
     for (uint64_t i = 0; i <= n_samples; i++) c->h_offs[i] = n_samples ? offs[i] - base : 0;
-    if (n_samples && c->n_bytes && !text) {
-        delete c;
-        return fail(TGX_ERR_INVALID, "tgx_corpus_upload: text is NULL");
-    }
+    if (n_samples && c->n_bytes && !text) return fail(TGX_ERR_INVALID, "tgx_corpus_upload: text is NULL");
     // longest first: the tail of a pass is then made of short samples
     std::vector<uint32_t> order(n_samples);
     std::iota(order.begin(), order.end(), 0u);
@@ -1576,54 +1631,22 @@ tgx_status tgx_corpus_upload(int device, const uint8_t* text, const uint64_t* of
         run += c->h_sorted_len[i];
         c->h_sorted_cum[i] = run;
     }
-    auto cleanup = [&](tgx_status st) {
-        tgx_corpus_free(c);
-        return st;
-    };
-#define HIP_TRY_C(expr)                                                                     \
-    do {                                                                                    \
-        hipError_t _e = (expr);                                                             \
-        if (_e != hipSuccess)                                                               \
-            return cleanup(fail(TGX_ERR_DEVICE, "HIP error %d (%s) at %s:%d: %s", (int)_e,  \
-                                hipGetErrorString(_e), __FILE__, __LINE__, #expr));         \
-    } while (0)
-    HIP_TRY_C(hipSetDevice(device));
-    HIP_TRY_C(pool_alloc(device, (size_t)c->n_bytes + 512, (void**)&c->d_text_alloc));
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(c->d_text_alloc.alloc(device, (size_t)c->n_bytes + 512));
     c->d_text = c->d_text_alloc + 256;
-    HIP_TRY_C(hipMemset(c->d_text_alloc, 0, 256));
-    HIP_TRY_C(pool_alloc(device, (size_t)(n_samples + 1) * 8, (void**)&c->d_offs));
-    HIP_TRY_C(pool_alloc(device, (size_t)n_samples * 4 + 4, (void**)&c->d_order));
-    if (c->n_bytes) HIP_TRY_C(copy_sync(c->d_text, text + base, c->n_bytes, hipMemcpyHostToDevice, device));
-    HIP_TRY_C(hipMemset(c->d_text + c->n_bytes, 0, 256));
-    HIP_TRY_C(hipMemcpy(c->d_offs, c->h_offs.data(), (n_samples + 1) * 8, hipMemcpyHostToDevice));
-    if (n_samples) HIP_TRY_C(hipMemcpy(c->d_order, order.data(), n_samples * 4, hipMemcpyHostToDevice));
-#undef HIP_TRY_C
-    *out = c;
+    HIP_TRY(hipMemset(c->d_text_alloc, 0, 256));
+    HIP_TRY(c->d_offs.alloc(device, (size_t)(n_samples + 1) * 8));
+    HIP_TRY(c->d_order.alloc(device, (size_t)n_samples * 4 + 4));
+    if (c->n_bytes) HIP_TRY(copy_sync(c->d_text, text + base, c->n_bytes, hipMemcpyHostToDevice, device));
+    HIP_TRY(hipMemset(c->d_text + c->n_bytes, 0, 256));
+    HIP_TRY(hipMemcpy(c->d_offs, c->h_offs.data(), (n_samples + 1) * 8, hipMemcpyHostToDevice));
+    if (n_samples) HIP_TRY(hipMemcpy(c->d_order, order.data(), n_samples * 4, hipMemcpyHostToDevice));
+    *out = c.release();
     return TGX_OK;
 }
 
-void tgx_corpus_free(tgx_corpus* c) {
-    if (!c) return;
-    pool_free(c->device, c->d_text_alloc, (size_t)c->n_bytes + 512);
-    pool_free(c->device, c->d_offs, (size_t)(c->n_samples + 1) * 8);
-    pool_free(c->device, c->d_order, (size_t)c->n_samples * 4 + 4);
-    pool_free(c->device, c->d_bp, std::max((size_t)c->n_bytes * 4 + 256, (size_t)c->n_bytes + 128 * (size_t)c->n_samples + 512));
-    if (c->d_tmp) pool_free(c->device, c->d_tmp, (size_t)c->n_bytes * 4 + 256);
-    pool_free(c->device, c->d_counts, (size_t)c->n_samples * 4 + 256);
-    pool_free(c->device, c->d_status, (size_t)c->n_samples * 4 + 256);
-    pool_free(c->device, c->d_scan_tmp, c->scan_tmp_bytes);
-    pool_free(c->device, c->d_endmask, (size_t)(c->mask_words + 1) * 8 + 256);
-    pool_free(c->device, c->d_prefix, (size_t)(c->mask_words + 1) * 8 + 256);
-    pool_free(c->device, c->d_mscan_tmp, c->mscan_tmp_bytes);
-    pool_free(c->device, c->d_mword, (size_t)(c->n_samples + 1) * 8 + 256);
-    pool_free(c->device, c->es.d_soffs, c->es.obytes);
-    pool_free(c->device, c->es.d_sbase, c->es.obytes);
-    pool_free(c->device, c->es.d_order, c->es.ordbytes);
-    pool_free(c->device, c->es.d_ssample, c->es.ordbytes);
-    pool_free(c->device, c->es.d_win_snip, c->es.winbytes);
-    pool_free(c->device, c->es.d_win_k, c->es.winbytes);
-    delete c;
-}
+// (every pass has finished with the corpus's buffers when it returns: they go straight back to the pool)
+void tgx_corpus_free(tgx_corpus* c) { delete c; }
 
 uint64_t tgx_corpus_num_samples(const tgx_corpus* c) { return c ? c->n_samples : 0; }
 uint64_t tgx_corpus_num_bytes(const tgx_corpus* c) { return c ? c->n_bytes : 0; }
@@ -1641,102 +1664,20 @@ static tgx_status encode_corpus_locked(tgx_model* m, tgx_corpus* c, double dropo
     m->n_timed = 0;
     const uint64_t S = c->n_samples;
 
-    tgx_result* r = new tgx_result();
-    r->device = m->device;
-    r->n_samples = S;
-    auto cleanup = [&](tgx_status st) {
-        tgx_result_free(r);
-        return st;
-    };
-    if (pool_alloc(m->device, (size_t)(S + 1) * 8, (void**)&r->d_offs) != hipSuccess)
-        return cleanup(fail(TGX_ERR_DEVICE, "out of device memory (result offsets)"));
-
-    tgx_status st = run_encode_kernel(m, c, dropout, seed);
-    if (st != TGX_OK) return cleanup(st);
-    if (m->mask_path) {
-        // TGX_TRACE=mask: ids in their final place (trace2.hip): the mask's popcount prefix gives every token its index, the batch its
-        // token count and every sample its offset; emit_kernel turns set bits into ids, fully parallel
-        time_begin(m, "mask_scan");
-        if (tgx::launch_mask_scan(c->d_endmask, c->d_prefix, c->mask_words, c->d_mscan_tmp, c->mscan_tmp_bytes, m->stream) != hipSuccess ||
-            tgx::launch_sample_offs(c->d_mword, S, c->d_prefix, r->d_offs, m->stream) != hipSuccess)
-            return cleanup(fail(TGX_ERR_DEVICE, "mask scan launch failed"));
-        time_end(m);
-        if (hipMemcpyAsync(&m->h_ctrl[0], m->d_ctrl + 1, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
-            hipMemcpyAsync(&m->h_ctrl[1], c->d_prefix + c->mask_words, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
-            hipStreamSynchronize(m->stream) != hipSuccess)
-            return cleanup(fail(TGX_ERR_DEVICE, "encode pass failed: %s", hipGetErrorString(hipGetLastError())));
-        st = check_no_path(m, c);
-        if (st != TGX_OK) return cleanup(st);
-        r->n_tokens = m->h_ctrl[1];
-        if (pool_alloc(m->device, (size_t)r->n_tokens * 4 + 256, (void**)&r->d_ids) != hipSuccess)
-            return cleanup(fail(TGX_ERR_DEVICE, "out of device memory (result ids)"));
-        tgx::EncodeParams pe{};
-        pe.text = c->d_text;
-        pe.tokhash = m->d_tokhash;
-        pe.tokhash_mask = m->tokhash.mask;
-        pe.tokhash_seed = m->tokhash.seed;
-        pe.err_sample = m->d_ctrl + 1;
-        pe.offs = c->d_offs;
-        pe.n_samples = S;
-        pe.endmask = c->d_endmask;
-        pe.mword = c->d_mword;
-        pe.mask_words = c->mask_words;
-        pe.prefix = c->d_prefix;
-        pe.ids_out = r->d_ids;
-        time_begin(m, "emit_kernel");
-        if (tgx::launch_emit(pe, m->lm <= 16 ? 16u : 32u, (uint32_t)m->num_cus, m->stream) != hipSuccess)
-            return cleanup(fail(TGX_ERR_DEVICE, "emit launch failed"));
-        time_end(m);
-        if (hipMemcpyAsync(&m->h_ctrl[0], m->d_ctrl + 1, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
-            hipStreamSynchronize(m->stream) != hipSuccess)
-            return cleanup(fail(TGX_ERR_DEVICE, "emit failed: %s", hipGetErrorString(hipGetLastError())));
-        st = check_no_path(m, c);  // (a lookup that missed: "corrupt back-pointer", never a fault)
-        if (st != TGX_OK) return cleanup(st);
-    } else {
-    if (!c->d_scan_tmp) {  // scratch of the device-wide scan (large sample counts only), kept on the corpus
-        if (tgx::scan_temp_bytes(S, &c->scan_tmp_bytes) != hipSuccess)
-            return cleanup(fail(TGX_ERR_DEVICE, "scan temp-size query failed"));
-        if (c->scan_tmp_bytes && pool_alloc(m->device, c->scan_tmp_bytes, &c->d_scan_tmp) != hipSuccess)
-            return cleanup(fail(TGX_ERR_DEVICE, "out of device memory (scan)"));
-    }
-    time_begin(m, "scan_counts_kernel");
-    if (tgx::launch_scan(c->d_counts, r->d_offs, S, c->d_scan_tmp, c->scan_tmp_bytes, m->stream) != hipSuccess)
-        return cleanup(fail(TGX_ERR_DEVICE, "scan launch failed"));
-    time_end(m);
-    if (hipMemcpyAsync(&m->h_ctrl[0], m->d_ctrl + 1, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
-        hipMemcpyAsync(&m->h_ctrl[1], r->d_offs + S, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
-        hipStreamSynchronize(m->stream) != hipSuccess)
-        return cleanup(fail(TGX_ERR_DEVICE, "encode pass failed: %s", hipGetErrorString(hipGetLastError())));
-    st = check_no_path(m, c);
-    if (st != TGX_OK) return cleanup(st);
-
-    r->n_tokens = m->h_ctrl[1];
-    if (pool_alloc(m->device, (size_t)r->n_tokens * 4 + 256, (void**)&r->d_ids) != hipSuccess)
-        return cleanup(fail(TGX_ERR_DEVICE, "out of device memory (result ids)"));
-    if (hipMemsetAsync(m->d_ctrl, 0x00, 8, m->stream) != hipSuccess)
-        return cleanup(fail(TGX_ERR_DEVICE, "memset failed"));
-    tgx::CompactParams cp{};
-    cp.offs = c->d_offs;
-    cp.order = c->d_order;
-    cp.n_samples = S;
-    cp.tmp = c->d_tmp;
-    cp.out_offs = r->d_offs;
-    cp.ids = r->d_ids;
-    time_begin(m, "compact_kernel");
-    // short samples (fewer than 128 ids on average): a 16-lane row per sample instead of a wave
-    const bool rows = S && r->n_tokens / S < 128;
-    const uint64_t units = rows ? 16 : 4;  // samples per block and round
-    uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((S + units - 1) / units, (uint64_t)m->num_cus * 8));
-    if (tgx::launch_compact(cp, blocks, rows, m->stream) != hipSuccess)
-        return cleanup(fail(TGX_ERR_DEVICE, "compact launch failed"));
-    time_end(m);
+    Pass pass(m);
+    tgx_result* r = pass.new_result(S);
+    if (r->d_offs.alloc(m->device, (size_t)(S + 1) * 8) != hipSuccess)
+        return fail(TGX_ERR_DEVICE, "out of device memory (result offsets)");
+    tgx_status st = run_encode_kernel(m, c, dropout, seed, pass);
+    if (st != TGX_OK) return st;
+    st = compact_ids(m, c, r, "encode");
+    if (st != TGX_OK) return st;
     if (hipStreamSynchronize(m->stream) != hipSuccess)
-        return cleanup(fail(TGX_ERR_DEVICE, "compact failed: %s", hipGetErrorString(hipGetLastError())));
-    }
+        return fail(TGX_ERR_DEVICE, "compact failed: %s", hipGetErrorString(hipGetLastError()));
     // N + 4T + 16(S+1)
     m->last_alg_bytes = c->n_bytes + 4 * r->n_tokens + 16 * (S + 1);
-    *out = r;
-    return TGX_OK;
+    *out = pass.release_result();
+    return pass.done();
 }
 
 tgx_status tgx_encode_corpus(tgx_model* m, tgx_corpus* c, double dropout, uint64_t seed,
@@ -1753,12 +1694,7 @@ tgx_status tgx_encode_batch(tgx_model* m, const uint8_t* text, const uint64_t* o
                             uint64_t n_samples, double dropout, uint64_t seed, tgx_result** out) {
     if (!m || !out) return fail(TGX_ERR_INVALID, "tgx_encode_batch: NULL argument");
     *out = nullptr;
-    tgx_corpus* c = nullptr;
-    tgx_status st = tgx_corpus_upload(m->device, text, offs, n_samples, &c);
-    if (st != TGX_OK) return st;
-    st = tgx_encode_corpus(m, c, dropout, seed, out);
-    tgx_corpus_free(c);
-    return st;
+    return on_uploaded_batch(m, text, offs, n_samples, [&](tgx_corpus* c) { return tgx_encode_corpus(m, c, dropout, seed, out); });
 }
 
 // Host buffers in, host buffers out (what a Rust caller of Tokenizer::encode_batch has: bindings/python/src/lib.rs:51-59
@@ -2073,15 +2009,10 @@ tgx_status tgx_result_copy_offsets(const tgx_result* r, uint64_t* dst, uint64_t 
     return TGX_OK;
 }
 
-const void* tgx_result_ids_device(const tgx_result* r) { return r ? r->d_ids : nullptr; }
-const void* tgx_result_offsets_device(const tgx_result* r) { return r ? r->d_offs : nullptr; }
+const void* tgx_result_ids_device(const tgx_result* r) { return r ? r->d_ids.get() : nullptr; }
+const void* tgx_result_offsets_device(const tgx_result* r) { return r ? r->d_offs.get() : nullptr; }
 
-void tgx_result_free(tgx_result* r) {
-    if (!r) return;
-    pool_free(r->device, r->d_ids, (size_t)r->n_tokens * 4 + 256);
-    pool_free(r->device, r->d_offs, (size_t)(r->n_samples + 1) * 8);
-    delete r;
-}
+void tgx_result_free(tgx_result* r) { delete r; }
 
 // ---- frequency pass ------------------------------------------------------------
 
@@ -2095,80 +2026,59 @@ tgx_status tgx_count_tokens(tgx_model* m, tgx_corpus* c, uint64_t* freq) {
     tgx_result* r = nullptr;
     tgx_status st = encode_corpus_locked(m, c, 0.0, 0, &r);
     if (st != TGX_OK) return st;
+    Pass pass(m);
+    pass.adopt_result(r);
     const uint64_t T = r->n_tokens;
-    if (T >= 0xFFFFFFFFull) {
-        tgx_result_free(r);
-        return fail(TGX_ERR_UNSUPPORTED, "frequency pass over more than 2^32-1 tokens per call");
-    }
+    if (T >= 0xFFFFFFFFull) return fail(TGX_ERR_UNSUPPORTED, "frequency pass over more than 2^32-1 tokens per call");
     if (T && m->vocab_size <= tgx::kHistMaxVocab && !knob("TGX_FREQ_SORT")) {
         // the vocabulary's counters fit a block's LDS: one private histogram per block (pairs.hip)
         unsigned long long* d_hist = nullptr;
         const size_t hb = (size_t)m->vocab_size * 8 + 256;
-        auto done = [&](tgx_status s2) {
-            if (s2 != TGX_OK) (void)hipStreamSynchronize(m->stream);
-            pool_free(m->device, d_hist, hb);
-            tgx_result_free(r);
-            return s2;
-        };
-        if (pool_alloc(m->device, hb, (void**)&d_hist) != hipSuccess) return done(fail(TGX_ERR_DEVICE, "out of device memory (frequency pass)"));
-        if (hipMemsetAsync(d_hist, 0, hb, m->stream) != hipSuccess) return done(fail(TGX_ERR_DEVICE, "memset failed"));
+        if (pass.alloc(hb, &d_hist) != hipSuccess) return fail(TGX_ERR_DEVICE, "out of device memory (frequency pass)");
+        if (hipMemsetAsync(d_hist, 0, hb, m->stream) != hipSuccess) return fail(TGX_ERR_DEVICE, "memset failed");
         time_begin(m, "ids_histogram_kernel");
         if (tgx::launch_ids_histogram(r->d_ids, T, m->vocab_size, d_hist, (uint32_t)m->num_cus, m->stream) != hipSuccess)
-            return done(fail(TGX_ERR_DEVICE, "histogram launch failed"));
+            return fail(TGX_ERR_DEVICE, "histogram launch failed");
         time_end(m);
         std::vector<unsigned long long> hh(m->vocab_size);
         if (hipMemcpyAsync(hh.data(), d_hist, (size_t)m->vocab_size * 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
             hipStreamSynchronize(m->stream) != hipSuccess)
-            return done(fail(TGX_ERR_DEVICE, "frequency pass failed: %s", hipGetErrorString(hipGetLastError())));
+            return fail(TGX_ERR_DEVICE, "frequency pass failed: %s", hipGetErrorString(hipGetLastError()));
         for (uint32_t i = 0; i < m->vocab_size; i++) freq[i] += hh[i];
         m->last_alg_bytes = c->n_bytes + 8 * (c->n_samples + 1) + 8ull * m->vocab_size;
-        return done(TGX_OK);
+        return pass.done();
     }
     uint32_t *d_sorted = nullptr, *d_unique = nullptr;
     unsigned int *d_cnt = nullptr, *d_runs = nullptr;
     void* d_temp = nullptr;
     size_t tb1 = 0, tb2 = 0;
     const size_t kb = (size_t)T * 4 + 256;
-    auto cleanup = [&](tgx_status s2) {
-        // kernels already queued may still write these buffers: no other handle may take them from the pool yet
-        if (s2 != TGX_OK) (void)hipStreamSynchronize(m->stream);
-        pool_free(m->device, d_sorted, kb);
-        pool_free(m->device, d_unique, kb);
-        pool_free(m->device, d_cnt, kb);
-        pool_free(m->device, d_runs, 256);
-        pool_free(m->device, d_temp, std::max(tb1, tb2) + 256);
-        tgx_result_free(r);
-        return s2;
-    };
-    if (T == 0) return cleanup(TGX_OK);
+    if (T == 0) return pass.done();
     if (tgx::ids_sort_temp_bytes(T, &tb1) != hipSuccess || tgx::ids_rle_temp_bytes(T, &tb2) != hipSuccess)
-        return cleanup(fail(TGX_ERR_DEVICE, "rocPRIM temp-size query failed"));
-    if (pool_alloc(m->device, kb, (void**)&d_sorted) != hipSuccess ||
-        pool_alloc(m->device, kb, (void**)&d_unique) != hipSuccess ||
-        pool_alloc(m->device, kb, (void**)&d_cnt) != hipSuccess ||
-        pool_alloc(m->device, 256, (void**)&d_runs) != hipSuccess ||
-        pool_alloc(m->device, std::max(tb1, tb2) + 256, &d_temp) != hipSuccess)
-        return cleanup(fail(TGX_ERR_DEVICE, "out of device memory (frequency pass)"));
+        return fail(TGX_ERR_DEVICE, "rocPRIM temp-size query failed");
+    if (pass.alloc(kb, &d_sorted) != hipSuccess || pass.alloc(kb, &d_unique) != hipSuccess || pass.alloc(kb, &d_cnt) != hipSuccess ||
+        pass.alloc(256, &d_runs) != hipSuccess || pass.alloc(std::max(tb1, tb2) + 256, &d_temp) != hipSuccess)
+        return fail(TGX_ERR_DEVICE, "out of device memory (frequency pass)");
     unsigned int end_bit = 1;
     while (end_bit < 32 && (1ull << end_bit) < (uint64_t)m->vocab_size) end_bit++;
     time_begin(m, "ids_sort+rle");
     if (tgx::ids_sort(d_temp, tb1, r->d_ids, d_sorted, T, end_bit, m->stream) != hipSuccess ||
         tgx::ids_rle(d_temp, tb2, d_sorted, T, d_unique, d_cnt, d_runs, m->stream) != hipSuccess)
-        return cleanup(fail(TGX_ERR_DEVICE, "id sort / run-length encode failed"));
+        return fail(TGX_ERR_DEVICE, "id sort / run-length encode failed");
     time_end(m);
     unsigned int runs = 0;
     if (hipMemcpyAsync(&runs, d_runs, 4, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
         hipStreamSynchronize(m->stream) != hipSuccess)
-        return cleanup(fail(TGX_ERR_DEVICE, "frequency pass failed: %s", hipGetErrorString(hipGetLastError())));
+        return fail(TGX_ERR_DEVICE, "frequency pass failed: %s", hipGetErrorString(hipGetLastError()));
     std::vector<uint32_t> hu(runs ? runs : 1);
     std::vector<unsigned int> hc(runs ? runs : 1);
     if (runs && (hipMemcpy(hu.data(), d_unique, (size_t)runs * 4, hipMemcpyDeviceToHost) != hipSuccess ||
                  hipMemcpy(hc.data(), d_cnt, (size_t)runs * 4, hipMemcpyDeviceToHost) != hipSuccess))
-        return cleanup(fail(TGX_ERR_DEVICE, "D2H copy of the histogram failed"));
+        return fail(TGX_ERR_DEVICE, "D2H copy of the histogram failed");
     for (unsigned int i = 0; i < runs; i++)
         if (hu[i] < m->vocab_size) freq[hu[i]] += hc[i];
     m->last_alg_bytes = c->n_bytes + 8 * (c->n_samples + 1) + 8ull * m->vocab_size;
-    return cleanup(TGX_OK);
+    return pass.done();
 }
 
 // max_pairs == 0: the whole table in ascending key order (tgx_count_pairs); otherwise the max_pairs most
@@ -2185,38 +2095,21 @@ static tgx_status count_pairs_impl(tgx_model* m, tgx_corpus* c, uint64_t max_pai
     tgx_result* r = nullptr;
     tgx_status st = encode_corpus_locked(m, c, 0.0, 0, &r);  // model.encode(sample, 0.0), merge.rs:58
     if (st != TGX_OK) return st;
+    Pass pass(m);
+    pass.adopt_result(r);
     const uint64_t T = r->n_tokens, S = r->n_samples;
-    if (T >= 0xFFFFFFFFull) {
-        tgx_result_free(r);
-        return fail(TGX_ERR_UNSUPPORTED, "pair scan over more than 2^32-1 tokens per pass");
-    }
+    if (T >= 0xFFFFFFFFull) return fail(TGX_ERR_UNSUPPORTED, "pair scan over more than 2^32-1 tokens per pass");
     unsigned long long *d_keys = nullptr, *d_sorted = nullptr, *d_unique = nullptr;
     unsigned int *d_cnt = nullptr, *d_runs = nullptr;
     void* d_temp = nullptr;
     size_t tb1 = 0, tb2 = 0;
     const size_t kb = (size_t)T * 8 + 256, cb = (size_t)T * 4 + 256;
-    auto cleanup = [&](tgx_status s2) {
-        // kernels already queued may still write these buffers: no other handle may take them from the pool yet
-        if (s2 != TGX_OK) (void)hipStreamSynchronize(m->stream);
-        pool_free(m->device, d_keys, kb);
-        pool_free(m->device, d_sorted, kb);
-        pool_free(m->device, d_unique, kb);
-        pool_free(m->device, d_cnt, cb);
-        pool_free(m->device, d_runs, 256);
-        pool_free(m->device, d_temp, std::max(tb1, tb2) + 256);
-        tgx_result_free(r);
-        return s2;
-    };
-    if (T == 0) return cleanup(TGX_OK);
+    if (T == 0) return pass.done();
     if (tgx::pair_sort_temp_bytes(T, &tb1) != hipSuccess || tgx::pair_rle_temp_bytes(T, &tb2) != hipSuccess)
-        return cleanup(fail(TGX_ERR_DEVICE, "rocPRIM temp-size query failed"));
-    if (pool_alloc(m->device, kb, (void**)&d_keys) != hipSuccess ||
-        pool_alloc(m->device, kb, (void**)&d_sorted) != hipSuccess ||
-        pool_alloc(m->device, kb, (void**)&d_unique) != hipSuccess ||
-        pool_alloc(m->device, cb, (void**)&d_cnt) != hipSuccess ||
-        pool_alloc(m->device, 256, (void**)&d_runs) != hipSuccess ||
-        pool_alloc(m->device, std::max(tb1, tb2) + 256, &d_temp) != hipSuccess)
-        return cleanup(fail(TGX_ERR_DEVICE, "out of device memory (pair scan)"));
+        return fail(TGX_ERR_DEVICE, "rocPRIM temp-size query failed");
+    if (pass.alloc(kb, &d_keys) != hipSuccess || pass.alloc(kb, &d_sorted) != hipSuccess || pass.alloc(kb, &d_unique) != hipSuccess ||
+        pass.alloc(cb, &d_cnt) != hipSuccess || pass.alloc(256, &d_runs) != hipSuccess || pass.alloc(std::max(tb1, tb2) + 256, &d_temp) != hipSuccess)
+        return fail(TGX_ERR_DEVICE, "out of device memory (pair scan)");
     const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((S + 3) / 4, (uint64_t)m->num_cus * 8));
     // pair keys of 2 shift (+ 1 for the sentinel) bits, shift = bits of the largest id; widened to the API's
     // (a << 32) | b on the host
@@ -2226,21 +2119,21 @@ static tgx_status count_pairs_impl(tgx_model* m, tgx_corpus* c, uint64_t max_pai
     const unsigned int end_bit = shift < 32 ? 2 * shift + 1 : 64;
     time_begin(m, "pair_keys_kernel");
     if (tgx::launch_pair_keys(r->d_ids, r->d_offs, S, shift, sentinel, d_keys, blocks, m->stream) != hipSuccess)
-        return cleanup(fail(TGX_ERR_DEVICE, "pair key launch failed"));
+        return fail(TGX_ERR_DEVICE, "pair key launch failed");
     time_end(m);
     time_begin(m, "pair_sort+rle");
     if (tgx::pair_sort(d_temp, tb1, d_keys, d_sorted, T, end_bit, m->stream) != hipSuccess ||
         tgx::pair_rle(d_temp, tb2, d_sorted, T, d_unique, d_cnt, d_runs, m->stream) != hipSuccess)
-        return cleanup(fail(TGX_ERR_DEVICE, "pair sort / run-length encode failed"));
+        return fail(TGX_ERR_DEVICE, "pair sort / run-length encode failed");
     time_end(m);
     unsigned int runs = 0;
     if (hipMemcpyAsync(&runs, d_runs, 4, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
         hipStreamSynchronize(m->stream) != hipSuccess)
-        return cleanup(fail(TGX_ERR_DEVICE, "pair scan failed: %s", hipGetErrorString(hipGetLastError())));
+        return fail(TGX_ERR_DEVICE, "pair scan failed: %s", hipGetErrorString(hipGetLastError()));
     // the sentinel run (one per non-empty sample) has the largest key: it is the last run
     unsigned long long last_key = 0;
     if (runs && hipMemcpy(&last_key, d_unique + (runs - 1), 8, hipMemcpyDeviceToHost) != hipSuccess)
-        return cleanup(fail(TGX_ERR_DEVICE, "D2H copy failed"));
+        return fail(TGX_ERR_DEVICE, "D2H copy failed");
     if (runs && last_key == sentinel) runs--;
     const unsigned long long* src_keys = d_unique;
     const unsigned int* src_cnt = d_cnt;
@@ -2250,17 +2143,15 @@ static tgx_status count_pairs_impl(tgx_model* m, tgx_corpus* c, uint64_t max_pai
         // candidates of a table of millions (src/merge.rs:84-126)
         size_t tb3 = 0;
         if (tgx::pair_count_sort_temp_bytes(runs, &tb3) != hipSuccess)
-            return cleanup(fail(TGX_ERR_DEVICE, "rocPRIM temp-size query failed"));
+            return fail(TGX_ERR_DEVICE, "rocPRIM temp-size query failed");
         void* d_temp3 = nullptr;
-        if (pool_alloc(m->device, tb3 + 256, &d_temp3) != hipSuccess)
-            return cleanup(fail(TGX_ERR_DEVICE, "out of device memory (pair scan)"));
+        if (pass.alloc(tb3 + 256, &d_temp3) != hipSuccess) return fail(TGX_ERR_DEVICE, "out of device memory (pair scan)");
         unsigned int* cnt_out = reinterpret_cast<unsigned int*>(d_sorted);  // the sorted keys are no longer needed
         time_begin(m, "pair_count_sort");
         hipError_t e3 = tgx::pair_count_sort(d_temp3, tb3, d_cnt, cnt_out, d_unique, d_keys, runs, m->stream);
         time_end(m);
         if (e3 == hipSuccess) e3 = hipStreamSynchronize(m->stream);
-        pool_free(m->device, d_temp3, tb3 + 256);
-        if (e3 != hipSuccess) return cleanup(fail(TGX_ERR_DEVICE, "pair count sort failed"));
+        if (e3 != hipSuccess) return fail(TGX_ERR_DEVICE, "pair count sort failed");
         src_keys = d_keys;
         src_cnt = cnt_out;
         runs = (unsigned int)std::min<uint64_t>(runs, max_pairs);
@@ -2270,7 +2161,7 @@ static tgx_status count_pairs_impl(tgx_model* m, tgx_corpus* c, uint64_t max_pai
     if (!ok || !oc) {
         free(ok);
         free(oc);
-        return cleanup(fail(TGX_ERR_DEVICE, "out of host memory (pair table of %llu entries)", (unsigned long long)runs));
+        return fail(TGX_ERR_DEVICE, "out of host memory (pair table of %llu entries)", (unsigned long long)runs);
     }
     if (!max_pairs && runs) {
         // the whole table (millions of pairs: the multi-GPU merge exchanges it): brought into the ABI's form on the
@@ -2284,7 +2175,7 @@ static tgx_status count_pairs_impl(tgx_model* m, tgx_corpus* c, uint64_t max_pai
             copy_sync(oc, ec, (size_t)runs * 8, hipMemcpyDeviceToHost, m->device) != hipSuccess) {
             free(ok);
             free(oc);
-            return cleanup(fail(TGX_ERR_DEVICE, "D2H copy of pair table failed"));
+            return fail(TGX_ERR_DEVICE, "D2H copy of pair table failed");
         }
     } else {
         std::vector<unsigned long long> hk(runs ? runs : 1);
@@ -2293,7 +2184,7 @@ static tgx_status count_pairs_impl(tgx_model* m, tgx_corpus* c, uint64_t max_pai
                      hipMemcpy(hc.data(), src_cnt, (size_t)runs * 4, hipMemcpyDeviceToHost) != hipSuccess)) {
             free(ok);
             free(oc);
-            return cleanup(fail(TGX_ERR_DEVICE, "D2H copy of pair table failed"));
+            return fail(TGX_ERR_DEVICE, "D2H copy of pair table failed");
         }
         const unsigned long long low = shift < 32 ? (1ull << shift) - 1 : 0xFFFFFFFFull;
         for (unsigned int i = 0; i < runs; i++) {
@@ -2306,7 +2197,7 @@ static tgx_status count_pairs_impl(tgx_model* m, tgx_corpus* c, uint64_t max_pai
     *n_pairs = runs;
     // N + 8(S+1) + 16P
     m->last_alg_bytes = c->n_bytes + 8 * (S + 1) + 16ull * runs;
-    return cleanup(TGX_OK);
+    return pass.done();
 }
 
 tgx_status tgx_count_pairs(tgx_model* m, tgx_corpus* c, uint64_t** keys, uint64_t** counts, uint64_t* n_pairs) {
@@ -2418,21 +2309,7 @@ static tgx_status ensure_estep_work(tgx_model* m, tgx_corpus* c, uint64_t snippe
     if (es.snippet_len == snippet_len) return TGX_OK;
     const uint64_t S = c->n_samples, N = c->n_bytes;
     {
-        pool_free(c->device, es.d_soffs, es.obytes);
-        pool_free(c->device, es.d_sbase, es.obytes);
-        pool_free(c->device, es.d_order, es.ordbytes);
-        pool_free(c->device, es.d_ssample, es.ordbytes);
-        pool_free(c->device, es.d_win_snip, es.winbytes);
-        pool_free(c->device, es.d_win_k, es.winbytes);
-        es.d_soffs = es.d_sbase = nullptr;
-        es.d_order = es.d_ssample = nullptr;
-        es.d_win_snip = es.d_win_k = nullptr;
-        es.window = 0;
-        es.n_windows = 0;
-        es.snippet_len = 0;
-        es.soffs.clear();
-        es.ssample.clear();
-        es.sbase.clear();
+        es = tgx_corpus::EstepWork{};  // (the old list's buffers go back to the pool)
         es.soffs.reserve(S + N / snippet_len + 2);
         for (uint64_t i = 0; i < S; i++) {
             const uint64_t b = c->h_offs[i], e = c->h_offs[i + 1];
@@ -2452,12 +2329,9 @@ static tgx_status ensure_estep_work(tgx_model* m, tgx_corpus* c, uint64_t snippe
         std::stable_sort(es.order.begin(), es.order.end(), [&so](uint32_t a, uint32_t b) {
             return so[a + 1] - so[a] > so[b + 1] - so[b];
         });
-        es.obytes = (size_t)(K0 + 1) * 8 + 256;
-        es.ordbytes = (size_t)K0 * 4 + 256;
-        if (pool_alloc(c->device, es.obytes, (void**)&es.d_soffs) != hipSuccess ||
-            pool_alloc(c->device, es.obytes, (void**)&es.d_sbase) != hipSuccess ||
-            pool_alloc(c->device, es.ordbytes, (void**)&es.d_order) != hipSuccess ||
-            pool_alloc(c->device, es.ordbytes, (void**)&es.d_ssample) != hipSuccess)
+        const size_t obytes = (size_t)(K0 + 1) * 8 + 256, ordbytes = (size_t)K0 * 4 + 256;
+        if (es.d_soffs.alloc(c->device, obytes) != hipSuccess || es.d_sbase.alloc(c->device, obytes) != hipSuccess ||
+            es.d_order.alloc(c->device, ordbytes) != hipSuccess || es.d_ssample.alloc(c->device, ordbytes) != hipSuccess)
             return fail(TGX_ERR_DEVICE, "out of device memory (E-step work list)");
         if (hipMemcpyAsync(es.d_soffs, es.soffs.data(), (K0 + 1) * 8, hipMemcpyHostToDevice, m->stream) != hipSuccess ||
             (K0 && hipMemcpyAsync(es.d_sbase, es.sbase.data(), K0 * 8, hipMemcpyHostToDevice, m->stream) != hipSuccess) ||
@@ -2470,40 +2344,23 @@ static tgx_status ensure_estep_work(tgx_model* m, tgx_corpus* c, uint64_t snippe
     return TGX_OK;
 }
 
-// ---- pieces (cuts.hip): long snippets cut where no token match crosses — the lattice factorises there
+// ---- pieces (cuts.hip): long snippets cut where no token match crosses — the lattice factorises there.  The buffers
+// belong to the pass that built the list.
 struct EstepPieces {
-    uint64_t n = 0, longest = 0, cap = 0;
+    uint64_t n = 0, longest = 0;
     uint64_t *d_bound = nullptr, *d_pos = nullptr, *d_offs = nullptr, *d_base = nullptr;
     uint32_t *d_flag = nullptr, *d_sample = nullptr, *d_snip = nullptr, *d_len = nullptr, *d_idx = nullptr, *d_len2 = nullptr, *d_order = nullptr;
     void *d_scan = nullptr, *d_sort = nullptr;
     double* d_zsnip = nullptr;
     size_t scan_bytes = 0, sort_bytes = 0, zsnip_bytes = 0;
 };
-static void estep_pieces_free(tgx_model* m, EstepPieces& pc) {
-    pool_free(m->device, pc.d_bound, pc.cap * 8 + 256);
-    pool_free(m->device, pc.d_pos, (pc.cap + 1) * 8 + 256);
-    pool_free(m->device, pc.d_offs, (pc.cap + 1) * 8 + 256);
-    pool_free(m->device, pc.d_base, pc.cap * 8 + 256);
-    pool_free(m->device, pc.d_flag, (pc.cap + 1) * 4 + 256);
-    pool_free(m->device, pc.d_sample, pc.cap * 4 + 256);
-    pool_free(m->device, pc.d_snip, pc.cap * 4 + 256);
-    pool_free(m->device, pc.d_len, pc.cap * 4 + 256);
-    pool_free(m->device, pc.d_idx, pc.cap * 4 + 256);
-    pool_free(m->device, pc.d_len2, pc.cap * 4 + 256);
-    pool_free(m->device, pc.d_order, pc.cap * 4 + 256);
-    pool_free(m->device, pc.d_scan, pc.scan_bytes);
-    pool_free(m->device, pc.d_sort, pc.sort_bytes);
-    pool_free(m->device, pc.d_zsnip, pc.zsnip_bytes);
-    pc = EstepPieces{};
-}
 // the windows of the corpus's snippets (one boundary is sought per window), kept with the work list
 static tgx_status ensure_estep_windows(tgx_model* m, tgx_corpus* c, uint32_t window) {
     tgx_corpus::EstepWork& es = c->es;
     if (es.window == window && es.d_win_snip) return TGX_OK;
     const uint64_t K = es.soffs.size() - 1, N = c->n_bytes;
-    pool_free(c->device, es.d_win_snip, es.winbytes);
-    pool_free(c->device, es.d_win_k, es.winbytes);
-    es.d_win_snip = es.d_win_k = nullptr;
+    es.d_win_snip.reset();
+    es.d_win_k.reset();
     es.window = 0;
     std::vector<uint32_t> ws, wk;
     ws.reserve(K + N / window + 2);
@@ -2516,9 +2373,8 @@ static tgx_status ensure_estep_windows(tgx_model* m, tgx_corpus* c, uint32_t win
         }
     }
     es.n_windows = ws.size();
-    es.winbytes = es.n_windows * 4 + 256;
-    if (pool_alloc(c->device, es.winbytes, (void**)&es.d_win_snip) != hipSuccess ||
-        pool_alloc(c->device, es.winbytes, (void**)&es.d_win_k) != hipSuccess)
+    const size_t winbytes = es.n_windows * 4 + 256;
+    if (es.d_win_snip.alloc(c->device, winbytes) != hipSuccess || es.d_win_k.alloc(c->device, winbytes) != hipSuccess)
         return fail(TGX_ERR_DEVICE, "out of device memory (E-step windows)");
     if (hipMemcpyAsync(es.d_win_snip, ws.data(), es.n_windows * 4, hipMemcpyHostToDevice, m->stream) != hipSuccess ||
         hipMemcpyAsync(es.d_win_k, wk.data(), es.n_windows * 4, hipMemcpyHostToDevice, m->stream) != hipSuccess ||
@@ -2529,34 +2385,25 @@ static tgx_status ensure_estep_windows(tgx_model* m, tgx_corpus* c, uint32_t win
 }
 // cut_windows_kernel, scan, scatter, lengths, longest-first order: the piece list of this pass (dropout decides the
 // matches, so the list is per pass).  trie16: a 16-byte-record table of the forward tokens (scores or weights alike).
-static tgx_status estep_pieces_build(tgx_model* m, tgx_corpus* c, const void* trie16, double dropout, uint64_t seed, EstepPieces* out) {
+static tgx_status estep_pieces_build(tgx_model* m, tgx_corpus* c, const void* trie16, double dropout, uint64_t seed, Pass& pass,
+                                     EstepPieces* out) {
     tgx_corpus::EstepWork& es = c->es;
     EstepPieces& pc = *out;
     const uint64_t K = es.soffs.size() - 1, N = c->n_bytes;
     const uint64_t W = es.n_windows;
-    pc.cap = W;
     pc.zsnip_bytes = (size_t)K * 8 + 256;
-    auto bad = [&](const char* what) {
-        (void)hipStreamSynchronize(m->stream);
-        estep_pieces_free(m, pc);
-        return fail(TGX_ERR_DEVICE, "E-step pieces: %s", what);
-    };
+    auto bad = [&](const char* what) { return fail(TGX_ERR_DEVICE, "E-step pieces: %s", what); };
     if (tgx::scan_temp_bytes(W, &pc.scan_bytes) != hipSuccess || tgx::piece_sort_temp_bytes(W, &pc.sort_bytes) != hipSuccess)
         return bad("scratch sizes");
-    if (pool_alloc(m->device, W * 8 + 256, (void**)&pc.d_bound) != hipSuccess ||
-        pool_alloc(m->device, (W + 1) * 8 + 256, (void**)&pc.d_pos) != hipSuccess ||
-        pool_alloc(m->device, (W + 1) * 8 + 256, (void**)&pc.d_offs) != hipSuccess ||
-        pool_alloc(m->device, W * 8 + 256, (void**)&pc.d_base) != hipSuccess ||
-        pool_alloc(m->device, (W + 1) * 4 + 256, (void**)&pc.d_flag) != hipSuccess ||
-        pool_alloc(m->device, W * 4 + 256, (void**)&pc.d_sample) != hipSuccess ||
-        pool_alloc(m->device, W * 4 + 256, (void**)&pc.d_snip) != hipSuccess ||
-        pool_alloc(m->device, W * 4 + 256, (void**)&pc.d_len) != hipSuccess ||
-        pool_alloc(m->device, W * 4 + 256, (void**)&pc.d_idx) != hipSuccess ||
-        pool_alloc(m->device, W * 4 + 256, (void**)&pc.d_len2) != hipSuccess ||
-        pool_alloc(m->device, W * 4 + 256, (void**)&pc.d_order) != hipSuccess ||
-        (pc.scan_bytes && pool_alloc(m->device, pc.scan_bytes, &pc.d_scan) != hipSuccess) ||
-        (pc.sort_bytes && pool_alloc(m->device, pc.sort_bytes, &pc.d_sort) != hipSuccess) ||
-        pool_alloc(m->device, pc.zsnip_bytes, (void**)&pc.d_zsnip) != hipSuccess)
+    if (pass.alloc(W * 8 + 256, &pc.d_bound) != hipSuccess || pass.alloc((W + 1) * 8 + 256, &pc.d_pos) != hipSuccess ||
+        pass.alloc((W + 1) * 8 + 256, &pc.d_offs) != hipSuccess || pass.alloc(W * 8 + 256, &pc.d_base) != hipSuccess ||
+        pass.alloc((W + 1) * 4 + 256, &pc.d_flag) != hipSuccess || pass.alloc(W * 4 + 256, &pc.d_sample) != hipSuccess ||
+        pass.alloc(W * 4 + 256, &pc.d_snip) != hipSuccess || pass.alloc(W * 4 + 256, &pc.d_len) != hipSuccess ||
+        pass.alloc(W * 4 + 256, &pc.d_idx) != hipSuccess || pass.alloc(W * 4 + 256, &pc.d_len2) != hipSuccess ||
+        pass.alloc(W * 4 + 256, &pc.d_order) != hipSuccess ||
+        (pc.scan_bytes && pass.alloc(pc.scan_bytes, &pc.d_scan) != hipSuccess) ||
+        (pc.sort_bytes && pass.alloc(pc.sort_bytes, &pc.d_sort) != hipSuccess) ||
+        pass.alloc(pc.zsnip_bytes, &pc.d_zsnip) != hipSuccess)
         return bad("out of device memory");
     tgx::CutParams q{};
     q.text = c->d_text;
@@ -2628,24 +2475,17 @@ static tgx_status ensure_estep_trie8t(tgx_model* m, const tgx_corpus* c) {
         // up to 64 chunks of 64 KiB spread over the corpus (4 MiB: ~13 M matches)
         const uint32_t chunk = 65536u;
         const uint64_t stride = std::max<uint64_t>(chunk, (c->n_bytes + 63) / 64);
+        const size_t cb = nw * 4 + 256;
+        Pass pass(m);
         unsigned int* d_cnt = nullptr;
         uint32_t* d_perm = nullptr;
-        const size_t cb = nw * 4 + 256;
-        auto drop = [&]() {
-            pool_free(m->device, d_cnt, cb);
-            pool_free(m->device, d_perm, cb);
-        };
-        if (pool_alloc(m->device, cb, (void**)&d_cnt) != hipSuccess || pool_alloc(m->device, cb, (void**)&d_perm) != hipSuccess) {
-            drop();
+        if (pass.alloc(cb, &d_cnt) != hipSuccess || pass.alloc(cb, &d_perm) != hipSuccess)
             return fail(TGX_ERR_DEVICE, "out of device memory (match counts)");
-        }
         std::vector<unsigned int> cnt(nw, 0u);
         if (hipMemsetAsync(d_cnt, 0, cb, m->stream) != hipSuccess ||
             tgx::launch_match_count(c->d_text, c->n_bytes, chunk, stride, m->d_trie8t, (uint32_t)ns, t8.root_base, t8.n_tok, d_cnt, (uint32_t)m->num_cus, m->stream) != hipSuccess ||
-            hipMemcpyAsync(cnt.data(), d_cnt, nw * 4, hipMemcpyDeviceToHost, m->stream) != hipSuccess || hipStreamSynchronize(m->stream) != hipSuccess) {
-            drop();
+            hipMemcpyAsync(cnt.data(), d_cnt, nw * 4, hipMemcpyDeviceToHost, m->stream) != hipSuccess || hipStreamSynchronize(m->stream) != hipSuccess)
             return fail(TGX_ERR_DEVICE, "match count pass failed: %s", hipGetErrorString(hipGetLastError()));
-        }
         hp.mark("match counts");
         // new order: the kTrie8TSortedRanks most matched tokens by descending count (ties: the old rank), the others as they were
         const uint32_t n_tok = t8.n_tok;
@@ -2678,11 +2518,9 @@ static tgx_status ensure_estep_trie8t(tgx_model* m, const tgx_corpus* c) {
         t8.w.swap(w2);
         t8.id_of_rank.swap(id2);
         if (hipMemcpyAsync(d_perm, perm.data(), nw * 4, hipMemcpyHostToDevice, m->stream) != hipSuccess ||
-            tgx::launch_rank_remap(m->d_trie8t, (uint32_t)ns, d_perm, m->stream) != hipSuccess || hipStreamSynchronize(m->stream) != hipSuccess) {
-            drop();
+            tgx::launch_rank_remap(m->d_trie8t, (uint32_t)ns, d_perm, m->stream) != hipSuccess || hipStreamSynchronize(m->stream) != hipSuccess)
             return fail(TGX_ERR_DEVICE, "rank remap failed: %s", hipGetErrorString(hipGetLastError()));
-        }
-        drop();
+        pass.done();
         hp.mark("re-rank");
     }
     HIP_TRY(hipMemcpy(m->d_wtab, t8.w.data(), nw * 8, hipMemcpyHostToDevice));
@@ -2700,12 +2538,13 @@ static tgx_status estep_fused(tgx_model* m, tgx_corpus* c, uint64_t snippet_len,
                               double* logz_sum, bool* fallback) {
     *fallback = false;
     tgx::HostPhases hp("estep_fused");
+    Pass pass(m);
     {
         const tgx_status tst = ensure_estep_trie8t(m, c);
         if (tst != TGX_OK) return tst;
         if (!m->have_trie8t) {
             *fallback = true;
-            return TGX_OK;
+            return pass.done();
         }
         hp.mark("trie8t");
         const tgx_status wst = ensure_estep_work(m, c, snippet_len);
@@ -2719,7 +2558,7 @@ static tgx_status estep_fused(tgx_model* m, tgx_corpus* c, uint64_t snippet_len,
     if (K == 0) {
         if (logz_sum) *logz_sum = 0.0;
         m->last_alg_bytes = N + 8 * (S + 1) + 8ull * m->vocab_size;
-        return TGX_OK;
+        return pass.done();
     }
     // A piece is a chain of trips (~0.12 us per byte: a 64 KiB snippet takes ~8 ms) while a pass runs at ~33 GB/s: long
     // snippets are cut where no match crosses (cuts.hip) when the longest chain is a sizeable part of the pass — 256 MiB:
@@ -2736,7 +2575,7 @@ static tgx_status estep_fused(tgx_model* m, tgx_corpus* c, uint64_t snippet_len,
         if (pieces) {
             tgx_status pst = ensure_estep_windows(m, c, window);
             if (pst != TGX_OK) return pst;
-            pst = estep_pieces_build(m, c, m->d_trie, dropout, seed, &pc);
+            pst = estep_pieces_build(m, c, m->d_trie, dropout, seed, pass, &pc);
             if (pst != TGX_OK) return pst;
             m->last_estep_pieces = pc.n;
         }
@@ -2790,29 +2629,15 @@ static tgx_status estep_fused(tgx_model* m, tgx_corpus* c, uint64_t snippet_len,
     void* d_work = nullptr;  // Estep7Work in device memory (kernels.h)
     uint64_t *d_roffs = nullptr, *d_rbase = nullptr;
     uint32_t *d_rsample = nullptr, *d_rsnip = nullptr;
-    auto cleanup = [&](tgx_status s2) {
-        if (s2 != TGX_OK) (void)hipStreamSynchronize(m->stream);
-        estep_pieces_free(m, pc);
-        pool_free(m->device, d_exp, ebytes);
-        pool_free(m->device, d_z, 256);
-        pool_free(m->device, d_work, 512);
-        pool_free(m->device, d_zsnip, zbytes);
-        pool_free(m->device, d_roffs, r8);
-        pool_free(m->device, d_rbase, r8);
-        pool_free(m->device, d_rsample, r4);
-        pool_free(m->device, d_rsnip, r4);
-        return s2;
-    };
     static_assert(sizeof(tgx::Estep7Work) <= 512, "Estep7Work scratch");
-    if (pool_alloc(m->device, ebytes, (void**)&d_exp) != hipSuccess || pool_alloc(m->device, 256, (void**)&d_z) != hipSuccess ||
-        pool_alloc(m->device, 512, &d_work) != hipSuccess || pool_alloc(m->device, zbytes, (void**)&d_zsnip) != hipSuccess || pool_alloc(m->device, r8, (void**)&d_roffs) != hipSuccess ||
-        pool_alloc(m->device, r8, (void**)&d_rbase) != hipSuccess || pool_alloc(m->device, r4, (void**)&d_rsample) != hipSuccess ||
-        pool_alloc(m->device, r4, (void**)&d_rsnip) != hipSuccess)
-        return cleanup(fail(TGX_ERR_DEVICE, "out of device memory (E-step scratch)"));
+    if (pass.alloc(ebytes, &d_exp) != hipSuccess || pass.alloc(256, &d_z) != hipSuccess || pass.alloc(512, &d_work) != hipSuccess ||
+        pass.alloc(zbytes, &d_zsnip) != hipSuccess || pass.alloc(r8, &d_roffs) != hipSuccess || pass.alloc(r8, &d_rbase) != hipSuccess ||
+        pass.alloc(r4, &d_rsample) != hipSuccess || pass.alloc(r4, &d_rsnip) != hipSuccess)
+        return fail(TGX_ERR_DEVICE, "out of device memory (E-step scratch)");
     if (hipMemsetAsync(d_exp, 0, ebytes, m->stream) != hipSuccess || hipMemsetAsync(d_z, 0, 256, m->stream) != hipSuccess ||
         hipMemsetAsync(d_zsnip, 0, zbytes, m->stream) != hipSuccess || hipMemsetAsync(m->d_ctrl + 3, 0x00, 24, m->stream) != hipSuccess ||
         hipMemsetAsync(m->d_ctrl + 1, 0xFF, 8, m->stream) != hipSuccess)
-        return cleanup(fail(TGX_ERR_DEVICE, "E-step setup failed"));
+        return fail(TGX_ERR_DEVICE, "E-step setup failed");
     tgx::Estep7Params p{};
     tgx::Estep7Work& wk = p.host_work;
     p.text = c->d_text;
@@ -2852,7 +2677,7 @@ static tgx_status estep_fused(tgx_model* m, tgx_corpus* c, uint64_t snippet_len,
     unsigned long long* d_stamps = nullptr;
     const size_t n_stamp_waves = (size_t)blocks * (size_t)waves;
     if (const char* e = debug_on() ? getenv("TGX_STAMPS") : nullptr) {
-        if (*e == '7' && pool_alloc(m->device, n_stamp_waves * 64, (void**)&d_stamps) == hipSuccess) {
+        if (*e == '7' && pass.alloc(n_stamp_waves * 64, &d_stamps) == hipSuccess) {
             (void)hipMemsetAsync(d_stamps, 0, n_stamp_waves * 64, m->stream);
             p.stamps = d_stamps;
         }
@@ -2863,15 +2688,11 @@ static tgx_status estep_fused(tgx_model* m, tgx_corpus* c, uint64_t snippet_len,
     }
     hp.mark("pieces + buffers");
     time_begin(m, "estep7_kernel");
-    if (tgx::launch_estep7(p, wide, ppl, waves, blocks, m->stream) != hipSuccess) {
-        pool_free(m->device, d_stamps, n_stamp_waves * 64);
-        return cleanup(fail(TGX_ERR_DEVICE, "estep7 launch failed"));
-    }
+    if (tgx::launch_estep7(p, wide, ppl, waves, blocks, m->stream) != hipSuccess) return fail(TGX_ERR_DEVICE, "estep7 launch failed");
     time_end(m);
     if (d_stamps) {  // diagnostic: mean ticks per trip and phase over all waves
         std::vector<unsigned long long> hs(n_stamp_waves * 8);
         const bool ok = hipStreamSynchronize(m->stream) == hipSuccess && hipMemcpy(hs.data(), d_stamps, n_stamp_waves * 64, hipMemcpyDeviceToHost) == hipSuccess;
-        pool_free(m->device, d_stamps, n_stamp_waves * 64);
         if (ok) {
             double sum[6] = {0, 0, 0, 0, 0, 0}, trips = 0;
             for (size_t w = 0; w < n_stamp_waves; w++) {
@@ -2886,19 +2707,19 @@ static tgx_status estep_fused(tgx_model* m, tgx_corpus* c, uint64_t snippet_len,
     if (hipMemcpyAsync(&flag, m->d_ctrl + 5, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
         hipMemcpyAsync(&n_redo, m->d_ctrl + 4, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
         hipStreamSynchronize(m->stream) != hipSuccess)
-        return cleanup(fail(TGX_ERR_DEVICE, "E-step pass failed: %s", hipGetErrorString(hipGetLastError())));
+        return fail(TGX_ERR_DEVICE, "E-step pass failed: %s", hipGetErrorString(hipGetLastError()));
     m->last_estep_redo = n_redo;
     if (flag != 0) {  // a position nothing reaches, a value out of range: the pass belongs to the log-domain kernels
         *fallback = true;
-        return cleanup(TGX_OK);
+        return pass.done();
     }
     if (n_redo != 0) {
         // the stretches the kernel could not close within a trip: estep7_redo_kernel, trips spilled to scratch
-        if (n_redo > redo_cap) return cleanup(fail(TGX_ERR_DEVICE, "E-step redo list longer than its buffers"));
+        if (n_redo > redo_cap) return fail(TGX_ERR_DEVICE, "E-step redo list longer than its buffers");
         std::vector<uint64_t> ro(2 * n_redo), tbase(n_redo + 1, 0);
-        if (hipMemcpy(ro.data(), d_roffs, 2 * n_redo * 8, hipMemcpyDeviceToHost) != hipSuccess) return cleanup(fail(TGX_ERR_DEVICE, "redo list read-back failed"));
+        if (hipMemcpy(ro.data(), d_roffs, 2 * n_redo * 8, hipMemcpyDeviceToHost) != hipSuccess) return fail(TGX_ERR_DEVICE, "redo list read-back failed");
         for (uint64_t i = 0; i < n_redo; i++) {
-            if (ro[2 * i + 1] < ro[2 * i] || ro[2 * i + 1] > N) return cleanup(fail(TGX_ERR_DEVICE, "corrupt E-step redo list"));
+            if (ro[2 * i + 1] < ro[2 * i] || ro[2 * i + 1] > N) return fail(TGX_ERR_DEVICE, "corrupt E-step redo list");
             tbase[i + 1] = tbase[i] + (ro[2 * i + 1] - ro[2 * i]) / 16 + 1;
         }
         const uint64_t TT = tbase[n_redo];
@@ -2908,20 +2729,12 @@ static tgx_status estep_fused(tgx_model* m, tgx_corpus* c, uint64_t snippet_len,
         int32_t* d_aexp = nullptr;
         unsigned char* d_ms = nullptr;
         uint64_t* d_tbase = nullptr;
-        auto cleanup2 = [&](tgx_status s2) {
-            (void)hipStreamSynchronize(m->stream);
-            pool_free(m->device, d_alpha, ab);
-            pool_free(m->device, d_aexp, xb);
-            pool_free(m->device, d_ms, mb);
-            pool_free(m->device, d_tbase, tbb);
-            return s2;
-        };
-        if (pool_alloc(m->device, ab, (void**)&d_alpha) != hipSuccess || pool_alloc(m->device, xb, (void**)&d_aexp) != hipSuccess ||
-            pool_alloc(m->device, mb, (void**)&d_ms) != hipSuccess || pool_alloc(m->device, tbb, (void**)&d_tbase) != hipSuccess)
-            return cleanup(cleanup2(fail(TGX_ERR_DEVICE, "out of device memory (E-step redo scratch)")));
+        if (pass.alloc(ab, &d_alpha) != hipSuccess || pass.alloc(xb, &d_aexp) != hipSuccess || pass.alloc(mb, &d_ms) != hipSuccess ||
+            pass.alloc(tbb, &d_tbase) != hipSuccess)
+            return fail(TGX_ERR_DEVICE, "out of device memory (E-step redo scratch)");
         if (hipMemcpyAsync(d_tbase, tbase.data(), (n_redo + 1) * 8, hipMemcpyHostToDevice, m->stream) != hipSuccess ||
             hipMemsetAsync(m->d_ctrl + 3, 0x00, 8, m->stream) != hipSuccess)
-            return cleanup(cleanup2(fail(TGX_ERR_DEVICE, "E-step redo setup failed")));
+            return fail(TGX_ERR_DEVICE, "E-step redo setup failed");
         tgx::Estep7RedoParams q{};
         q.text = c->d_text;
         q.redo_offs = d_roffs;
@@ -2949,40 +2762,39 @@ static tgx_status estep_fused(tgx_model* m, tgx_corpus* c, uint64_t snippet_len,
         time_begin(m, "estep7_redo_kernel");
         const hipError_t le = tgx::launch_estep7_redo(q, wide_redo, (uint32_t)m->num_cus, m->stream);
         time_end(m);
-        if (le != hipSuccess) return cleanup(cleanup2(fail(TGX_ERR_DEVICE, "estep7 redo launch failed: %s", hipGetErrorString(le))));
+        if (le != hipSuccess) return fail(TGX_ERR_DEVICE, "estep7 redo launch failed: %s", hipGetErrorString(le));
         if (hipMemcpyAsync(&flag, m->d_ctrl + 5, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess)
-            return cleanup(cleanup2(fail(TGX_ERR_DEVICE, "E-step redo pass failed")));
-        const tgx_status rst = cleanup2(TGX_OK);  // (synchronises the stream)
-        if (rst != TGX_OK) return cleanup(rst);
-        if (hipGetLastError() != hipSuccess) return cleanup(fail(TGX_ERR_DEVICE, "E-step redo pass failed"));
+            return fail(TGX_ERR_DEVICE, "E-step redo pass failed");
+        (void)hipStreamSynchronize(m->stream);
+        if (hipGetLastError() != hipSuccess) return fail(TGX_ERR_DEVICE, "E-step redo pass failed");
         if (flag != 0) {
             *fallback = true;
-            return cleanup(TGX_OK);
+            return pass.done();
         }
     }
     hp.mark("kernel + redo");
-    if (tgx::launch_snip_z_check(d_zsnip, K, m->d_ctrl + 1, m->stream) != hipSuccess) return cleanup(fail(TGX_ERR_DEVICE, "z check launch failed"));
+    if (tgx::launch_snip_z_check(d_zsnip, K, m->d_ctrl + 1, m->stream) != hipSuccess) return fail(TGX_ERR_DEVICE, "z check launch failed");
     std::vector<double> h((size_t)m->n_tok7 + 1);
     double hz = 0.0;
     if (hipMemcpyAsync(&m->h_ctrl[0], m->d_ctrl + 1, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
         hipMemcpyAsync(h.data(), d_exp, h.size() * 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
         hipMemcpyAsync(&hz, d_z, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess || hipStreamSynchronize(m->stream) != hipSuccess)
-        return cleanup(fail(TGX_ERR_DEVICE, "E-step pass failed: %s", hipGetErrorString(hipGetLastError())));
+        return fail(TGX_ERR_DEVICE, "E-step pass failed: %s", hipGetErrorString(hipGetLastError()));
     m->last_alg_bytes = N + 8 * (S + 1) + 8ull * m->vocab_size;
     const unsigned long long bad = m->h_ctrl[0];
     if (bad != ~0ULL) {  // nothing of a failed pass reaches the caller's `expected`
         const uint64_t smp = es.ssample[bad];
         g_err_sample = smp;
         g_err_pos = g_err_len = c->h_offs[smp + 1] - c->h_offs[smp];
-        return cleanup(fail(TGX_ERR_Z_NOT_NORMAL, "normalization constant is not a normal number (sample %llu, len=%llu)",
-                            (unsigned long long)smp, (unsigned long long)g_err_len));  // src/prune.rs:90-96
+        return fail(TGX_ERR_Z_NOT_NORMAL, "normalization constant is not a normal number (sample %llu, len=%llu)",
+                    (unsigned long long)smp, (unsigned long long)g_err_len);  // src/prune.rs:90-96
     }
     hp.mark("download");
     for (uint32_t r = 1; r <= m->n_tok7; r++) expected[m->id_of_rank[r]] += h[r];
     hp.mark("rank -> id");
     if (logz_sum) *logz_sum = hz;
     m->estep_calls++;
-    return cleanup(TGX_OK);
+    return pass.done();
 }
 
 // E-step on the four-snippets-per-wave kernels (estep4.hip).  Caller holds m->mu and has
@@ -2995,6 +2807,7 @@ static tgx_status estep_rows4(tgx_model* m, tgx_corpus* c, uint64_t snippet_len,
     const bool long_tokens = m->lm > 16;
     if (fallback) *fallback = false;
     const uint64_t S = c->n_samples, N = c->n_bytes;
+    Pass pass(m);
     {
         const tgx_status wst = ensure_estep_work(m, c, snippet_len);
         if (wst != TGX_OK) return wst;
@@ -3018,7 +2831,6 @@ static tgx_status estep_rows4(tgx_model* m, tgx_corpus* c, uint64_t snippet_len,
     // Estimates as below (1 position per lane: forward 52 GB/s and 14.5 ms per 64 KiB of chain, backward 21 GB/s and
     // 29 ms); TGX_ESTEP_PIECES=0 / 1 forces, TGX_ESTEP_WINDOW sets the window.
     EstepPieces pc;
-    auto free_pieces = [&]() { estep_pieces_free(m, pc); };
     bool pieces = false;
     if (linear && K && m->lm <= 32) {
         uint32_t window = 2048;
@@ -3036,7 +2848,7 @@ static tgx_status estep_rows4(tgx_model* m, tgx_corpus* c, uint64_t snippet_len,
         }
     }
     if (pieces) {
-        const tgx_status pst = estep_pieces_build(m, c, m->d_trie_w, dropout, seed, &pc);
+        const tgx_status pst = estep_pieces_build(m, c, m->d_trie_w, dropout, seed, pass, &pc);
         if (pst != TGX_OK) return pst;
         m->last_estep_pieces = pc.n;
     } else {
@@ -3054,27 +2866,13 @@ static tgx_status estep_rows4(tgx_model* m, tgx_corpus* c, uint64_t snippet_len,
     double *d_alpha = nullptr, *d_exp = nullptr, *d_z = nullptr, *d_zarr = nullptr;
     int32_t* d_aexp = nullptr;  // block exponents of alpha (linear-domain kernels)
     const size_t xbytes = (size_t)((N >> 4) + Kmax + 128) * 4;
-    auto cleanup = [&](tgx_status s2) {
-        // kernels already queued may still write these buffers: no other handle may take them from the pool yet
-        if (s2 != TGX_OK) (void)hipStreamSynchronize(m->stream);
-        free_pieces();
-        pool_free(m->device, d_alpha, abytes);
-        pool_free(m->device, d_aexp, xbytes);
-        pool_free(m->device, d_exp, ebytes);
-        pool_free(m->device, d_z, 256);
-        pool_free(m->device, d_zarr, zbytes);
-        return s2;
-    };
-    if (pool_alloc(m->device, abytes, (void**)&d_alpha) != hipSuccess ||
-        (linear && pool_alloc(m->device, xbytes, (void**)&d_aexp) != hipSuccess) ||
-        pool_alloc(m->device, ebytes, (void**)&d_exp) != hipSuccess ||
-        pool_alloc(m->device, 256, (void**)&d_z) != hipSuccess ||
-        pool_alloc(m->device, zbytes, (void**)&d_zarr) != hipSuccess)
-        return cleanup(fail(TGX_ERR_DEVICE, "out of device memory (E-step scratch)"));
+    if (pass.alloc(abytes, &d_alpha) != hipSuccess || (linear && pass.alloc(xbytes, &d_aexp) != hipSuccess) ||
+        pass.alloc(ebytes, &d_exp) != hipSuccess || pass.alloc(256, &d_z) != hipSuccess || pass.alloc(zbytes, &d_zarr) != hipSuccess)
+        return fail(TGX_ERR_DEVICE, "out of device memory (E-step scratch)");
     if (hipMemsetAsync(d_exp, 0, ebytes, m->stream) != hipSuccess ||
         hipMemsetAsync(d_z, 0, 256, m->stream) != hipSuccess ||
         hipMemsetAsync(m->d_ctrl + 1, 0xFF, 8, m->stream) != hipSuccess)
-        return cleanup(fail(TGX_ERR_DEVICE, "E-step setup copies failed"));
+        return fail(TGX_ERR_DEVICE, "E-step setup copies failed");
     tgx::Estep4Params p{};
     p.text = c->d_text;
     p.soffs = d_soffs;
@@ -3145,7 +2943,7 @@ static tgx_status estep_rows4(tgx_model* m, tgx_corpus* c, uint64_t snippet_len,
             // is better off without them; a model's second pass, or a pass over enough text, builds them.
             if (!m->estep_trie8_tried && (m->estep_calls >= 1 || ff != nullptr || (double)N * 4.7e-12 >= (double)m->vocab_size * 80e-9)) {
                 const tgx_status est = ensure_estep_trie8(m);
-                if (est != TGX_OK) return cleanup(est);
+                if (est != TGX_OK) return est;
             }
             use5f = m->have_wvalues;
         }
@@ -3178,7 +2976,7 @@ static tgx_status estep_rows4(tgx_model* m, tgx_corpus* c, uint64_t snippet_len,
         }
         cold5f = n_hot < m->n_values;
         int per_simd = 0;
-        if (tgx::estep5_waves_per_simd(dropout > 0.0, cold5f, ppl5f, &per_simd) != hipSuccess) return cleanup(fail(TGX_ERR_DEVICE, "estep5 attribute query failed"));
+        if (tgx::estep5_waves_per_simd(dropout > 0.0, cold5f, ppl5f, &per_simd) != hipSuccess) return fail(TGX_ERR_DEVICE, "estep5 attribute query failed");
         waves5f = std::max(1, std::min(waves5f, per_simd * 4));
         const uint64_t n_units = pieces ? pc.n : K;
         {
@@ -3216,23 +3014,23 @@ static tgx_status estep_rows4(tgx_model* m, tgx_corpus* c, uint64_t snippet_len,
         if (hipMemsetAsync(m->d_ctrl + 3, 0x00, 24, m->stream) != hipSuccess ||
             hipMemsetAsync(d_z, 0, 256, m->stream) != hipSuccess ||
             hipMemsetAsync(m->d_ctrl + 1, 0xFF, 8, m->stream) != hipSuccess)
-            return cleanup(fail(TGX_ERR_DEVICE, "E-step queue reset failed"));
+            return fail(TGX_ERR_DEVICE, "E-step queue reset failed");
         const bool fwd5 = use_linear && use5f;
         time_begin(m, fwd5 ? "estep5_fwd_kernel" : (use_linear ? "estep4l_fwd_kernel" : "estep4_fwd_kernel"));
         if ((fwd5 ? tgx::launch_estep5_fwd(p, q5f, cold5f, ppl5f, waves5f, blocks5f, m->stream)
                   : (use_linear ? tgx::launch_estep4l_fwd(p, eppl_fwd, long_tokens, (uint32_t)m->num_cus, m->stream)
                                 : tgx::launch_estep4_fwd(p, (uint32_t)m->num_cus, m->stream))) != hipSuccess)
-            return cleanup(fail(TGX_ERR_DEVICE, "E-step forward launch failed"));
+            return fail(TGX_ERR_DEVICE, "E-step forward launch failed");
         time_end(m);
         if (use_linear) {
             unsigned long long flag = 0;
             if (hipMemcpyAsync(&flag, m->d_ctrl + 5, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
                 hipStreamSynchronize(m->stream) != hipSuccess)
-                return cleanup(fail(TGX_ERR_DEVICE, "E-step forward pass failed: %s", hipGetErrorString(hipGetLastError())));
+                return fail(TGX_ERR_DEVICE, "E-step forward pass failed: %s", hipGetErrorString(hipGetLastError()));
             if (flag != 0) {
                 if (long_tokens) {
                     if (fallback) *fallback = true;
-                    return cleanup(TGX_OK);
+                    return pass.done();
                 }
                 use_linear = false;
                 continue;
@@ -3243,16 +3041,16 @@ static tgx_status estep_rows4(tgx_model* m, tgx_corpus* c, uint64_t snippet_len,
         if (const char* e = knob("TGX_BWD_GROUPS")) bwd_groups = (uint32_t)std::max(0, atoi(e));
         if ((use_linear ? tgx::launch_estep4l_bwd(p, eppl_bwd, long_tokens, (uint32_t)m->num_cus, bwd_groups, m->stream)
                         : tgx::launch_estep4_bwd(p, (uint32_t)m->num_cus, m->stream)) != hipSuccess)
-            return cleanup(fail(TGX_ERR_DEVICE, "estep4 backward launch failed"));
+            return fail(TGX_ERR_DEVICE, "estep4 backward launch failed");
         time_end(m);
         if (on_pieces && tgx::launch_piece_z_check(d_zarr, pc.d_snip, pc.n, pc.d_zsnip, K, m->d_ctrl + 1, m->stream) != hipSuccess)
-            return cleanup(fail(TGX_ERR_DEVICE, "E-step z check launch failed"));
+            return fail(TGX_ERR_DEVICE, "E-step z check launch failed");
         break;
     }
     double* d_sum = d_exp + (size_t)n_rep * n_rev;  // replica sums
     time_begin(m, "estep4_reduce_kernel");
     if (tgx::launch_estep4_reduce(d_exp, d_sum, (uint32_t)n_rev, n_rep, m->stream) != hipSuccess)
-        return cleanup(fail(TGX_ERR_DEVICE, "estep4 reduce launch failed"));
+        return fail(TGX_ERR_DEVICE, "estep4 reduce launch failed");
     time_end(m);
     std::vector<double> h(n_rev);
     double hz = 0.0;
@@ -3265,13 +3063,13 @@ static tgx_status estep_rows4(tgx_model* m, tgx_corpus* c, uint64_t snippet_len,
         hipMemcpyAsync(h.data(), d_sum, n_rev * 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
         hipMemcpyAsync(&hz, d_z, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
         hipStreamSynchronize(m->stream) != hipSuccess)
-        return cleanup(fail(TGX_ERR_DEVICE, "E-step pass failed: %s", hipGetErrorString(hipGetLastError())));
+        return fail(TGX_ERR_DEVICE, "E-step pass failed: %s", hipGetErrorString(hipGetLastError()));
     if (use_linear && flag_bwd != 0) {  // nothing of this pass reaches `expected`
         if (long_tokens && fallback) {
             *fallback = true;  // the generic kernel redoes it (tgx_estep)
-            return cleanup(TGX_OK);
+            return pass.done();
         }
-        return cleanup(fail(TGX_ERR_DEVICE, "E-step backward kernel raised range_flag %llu after a clean forward pass", flag_bwd));
+        return fail(TGX_ERR_DEVICE, "E-step backward kernel raised range_flag %llu after a clean forward pass", flag_bwd);
     }
     m->last_alg_bytes = N + 8 * (S + 1) + 8ull * m->vocab_size;
     const unsigned long long bad = m->h_ctrl[0];
@@ -3279,8 +3077,8 @@ static tgx_status estep_rows4(tgx_model* m, tgx_corpus* c, uint64_t snippet_len,
         const uint64_t smp = ssample[bad];
         g_err_sample = smp;
         g_err_pos = g_err_len = c->h_offs[smp + 1] - c->h_offs[smp];
-        return cleanup(fail(TGX_ERR_Z_NOT_NORMAL, "normalization constant is not a normal number (sample %llu, len=%llu)",
-                            (unsigned long long)smp, (unsigned long long)g_err_len));  // src/prune.rs:90-96
+        return fail(TGX_ERR_Z_NOT_NORMAL, "normalization constant is not a normal number (sample %llu, len=%llu)",
+                    (unsigned long long)smp, (unsigned long long)g_err_len);  // src/prune.rs:90-96
     }
     for (size_t t = 0; t < n_rev; t++) {
         const uint32_t id = m->flat_rev.tokid[t];
@@ -3288,7 +3086,7 @@ static tgx_status estep_rows4(tgx_model* m, tgx_corpus* c, uint64_t snippet_len,
     }
     if (logz_sum) *logz_sum = hz;
     m->estep_calls++;
-    return cleanup(TGX_OK);
+    return pass.done();
 }
 
 tgx_status tgx_estep(tgx_model* m, tgx_corpus* c, uint64_t snippet_len, double dropout,
@@ -3332,23 +3130,14 @@ tgx_status tgx_estep(tgx_model* m, tgx_corpus* c, uint64_t snippet_len, double d
     uint32_t n_rep = 256;
     while (n_rep > 1 && (size_t)n_rep * n_rev * 8 > (512ull << 20)) n_rep >>= 1;
     const size_t abytes = (size_t)(N + S + 128) * 8, ebytes = (size_t)(n_rep + 1) * n_rev * 8 + 256;
+    Pass pass(m);
     double *d_alpha = nullptr, *d_exp = nullptr, *d_z = nullptr;
-    auto cleanup = [&](tgx_status s2) {
-        // kernels already queued may still write these buffers: no other handle may take them from the pool yet
-        if (s2 != TGX_OK) (void)hipStreamSynchronize(m->stream);
-        pool_free(m->device, d_alpha, abytes);
-        pool_free(m->device, d_exp, ebytes);
-        pool_free(m->device, d_z, 256);
-        return s2;
-    };
-    if (pool_alloc(m->device, abytes, (void**)&d_alpha) != hipSuccess ||
-        pool_alloc(m->device, ebytes, (void**)&d_exp) != hipSuccess ||
-        pool_alloc(m->device, 256, (void**)&d_z) != hipSuccess)
-        return cleanup(fail(TGX_ERR_DEVICE, "out of device memory (E-step scratch)"));
+    if (pass.alloc(abytes, &d_alpha) != hipSuccess || pass.alloc(ebytes, &d_exp) != hipSuccess || pass.alloc(256, &d_z) != hipSuccess)
+        return fail(TGX_ERR_DEVICE, "out of device memory (E-step scratch)");
     if (hipMemsetAsync(d_exp, 0, ebytes, m->stream) != hipSuccess ||
         hipMemsetAsync(d_z, 0, 256, m->stream) != hipSuccess ||
         hipMemsetAsync(m->d_ctrl + 1, 0xFF, 8, m->stream) != hipSuccess)
-        return cleanup(fail(TGX_ERR_DEVICE, "memset failed"));
+        return fail(TGX_ERR_DEVICE, "memset failed");
     tgx::EstepParams p{};
     p.text = c->d_text;
     p.offs = c->d_offs;
@@ -3373,18 +3162,18 @@ tgx_status tgx_estep(tgx_model* m, tgx_corpus* c, uint64_t snippet_len, double d
         1, std::min<uint64_t>((S + wpb - 1) / wpb, (uint64_t)m->num_cus * (uint64_t)m->estep_blocks_per_cu));
     time_begin(m, "estep_kernel");
     if (tgx::launch_estep(p, blocks, m->stream) != hipSuccess)
-        return cleanup(fail(TGX_ERR_DEVICE, "estep launch failed"));
+        return fail(TGX_ERR_DEVICE, "estep launch failed");
     time_end(m);
     double* d_sum = d_exp + (size_t)n_rep * n_rev;
     if (tgx::launch_estep4_reduce(d_exp, d_sum, (uint32_t)n_rev, n_rep, m->stream) != hipSuccess)
-        return cleanup(fail(TGX_ERR_DEVICE, "estep reduce launch failed"));
+        return fail(TGX_ERR_DEVICE, "estep reduce launch failed");
     std::vector<double> h(n_rev);
     double hz = 0.0;
     if (hipMemcpyAsync(&m->h_ctrl[0], m->d_ctrl + 1, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
         hipMemcpyAsync(h.data(), d_sum, n_rev * 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
         hipMemcpyAsync(&hz, d_z, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
         hipStreamSynchronize(m->stream) != hipSuccess)
-        return cleanup(fail(TGX_ERR_DEVICE, "E-step pass failed: %s", hipGetErrorString(hipGetLastError())));
+        return fail(TGX_ERR_DEVICE, "E-step pass failed: %s", hipGetErrorString(hipGetLastError()));
     for (size_t t = 0; t < n_rev; t++) {
         const uint32_t id = m->flat_rev.tokid[t];
         if (id != tgx::kNoToken) expected[id] += h[t];
@@ -3397,10 +3186,10 @@ tgx_status tgx_estep(tgx_model* m, tgx_corpus* c, uint64_t snippet_len, double d
         g_err_sample = bad;
         g_err_pos = g_err_len = c->h_offs[bad + 1] - c->h_offs[bad];
         // the reference panics here: src/prune.rs:90-96
-        return cleanup(fail(TGX_ERR_Z_NOT_NORMAL, "normalization constant is not a normal number (sample %llu, len=%llu)",
-                            bad, (unsigned long long)g_err_len));
+        return fail(TGX_ERR_Z_NOT_NORMAL, "normalization constant is not a normal number (sample %llu, len=%llu)",
+                    bad, (unsigned long long)g_err_len);
     }
-    return cleanup(TGX_OK);
+    return pass.done();
 }
 
 // ---- sampling (sample.hip) ---------------------------------------------------------
@@ -3445,27 +3234,20 @@ static tgx_status sample_corpus_locked(tgx_model* m, tgx_corpus* c, double alpha
         if (strcmp(e, "generic") == 0) rows = false;
     }
 
-    tgx_result* r = new tgx_result();
-    r->device = m->device;
-    r->n_samples = S;
+    Pass pass(m);
+    tgx_result* r = pass.new_result(S);
     double* d_logz = nullptr;     // f64[S], then the range flag
     double* d_wslot = nullptr;    // f64[n_slots]
     const size_t lb = (size_t)S * 8 + 16, wb = (size_t)n_slots * 8 + 16;
-    auto cleanup = [&](tgx_status st) {
-        if (d_logz) pool_free(m->device, d_logz, lb);
-        if (d_wslot) pool_free(m->device, d_wslot, wb);
-        if (st != TGX_OK) tgx_result_free(r);
-        return st;
-    };
-    if (pool_alloc(m->device, (size_t)(S + 1) * 8, (void**)&r->d_offs) != hipSuccess ||
-        pool_alloc(m->device, lb, (void**)&d_logz) != hipSuccess || (rows && pool_alloc(m->device, wb, (void**)&d_wslot) != hipSuccess))
-        return cleanup(fail(TGX_ERR_DEVICE, "out of device memory (sampling)"));
-    tgx_status st = ensure_scratch(c, false);
-    if (st != TGX_OK) return cleanup(st);
+    if (r->d_offs.alloc(m->device, (size_t)(S + 1) * 8) != hipSuccess || pass.alloc(lb, &d_logz) != hipSuccess ||
+        (rows && pass.alloc(wb, &d_wslot) != hipSuccess))
+        return fail(TGX_ERR_DEVICE, "out of device memory (sampling)");
+    tgx_status st = ensure_scratch(c);
+    if (st != TGX_OK) return st;
     unsigned long long* d_range = reinterpret_cast<unsigned long long*>(d_logz + S);
     if (hipMemsetAsync(m->d_ctrl, 0x00, 8, m->stream) != hipSuccess || hipMemsetAsync(m->d_ctrl + 1, 0xFF, 8, m->stream) != hipSuccess ||
         hipMemsetAsync(d_range, 0x00, 8, m->stream) != hipSuccess)
-        return cleanup(fail(TGX_ERR_DEVICE, "memset failed"));
+        return fail(TGX_ERR_DEVICE, "memset failed");
 
     tgx::EncodeParams p{};
     p.text = c->d_text;
@@ -3481,7 +3263,7 @@ static tgx_status sample_corpus_locked(tgx_model* m, tgx_corpus* c, double alpha
     p.tmp = c->d_tmp;
     p.counts = c->d_counts;
     p.status = c->d_status;
-    p.bp8 = reinterpret_cast<uint8_t*>(c->d_bp);
+    p.bp8 = reinterpret_cast<uint8_t*>(c->d_bp.get());
     p.tokhash = m->d_tokhash;
     p.tokhash_mask = m->tokhash.mask;
     p.tokhash_seed = m->tokhash.seed;
@@ -3497,73 +3279,41 @@ static tgx_status sample_corpus_locked(tgx_model* m, tgx_corpus* c, double alpha
     if (rows) {
         time_begin(m, "sample_wslot_kernel");
         if (tgx::launch_sample_wslot(m->d_trie, n_slots, alpha, d_wslot, m->stream) != hipSuccess)
-            return cleanup(fail(TGX_ERR_DEVICE, "sample_wslot_kernel launch failed"));
+            return fail(TGX_ERR_DEVICE, "sample_wslot_kernel launch failed");
         time_end(m);
         time_begin(m, "sample_rows_kernel");
         if (tgx::launch_sample_rows(p, q, (uint32_t)m->num_cus, m->stream) != hipSuccess)
-            return cleanup(fail(TGX_ERR_DEVICE, "sample_rows_kernel launch failed"));
+            return fail(TGX_ERR_DEVICE, "sample_rows_kernel launch failed");
         time_end(m);
         unsigned long long range = 0;
         if (hipMemcpyAsync(&range, d_range, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess || hipStreamSynchronize(m->stream) != hipSuccess)
-            return cleanup(fail(TGX_ERR_DEVICE, "sampling pass failed: %s", hipGetErrorString(hipGetLastError())));
+            return fail(TGX_ERR_DEVICE, "sampling pass failed: %s", hipGetErrorString(hipGetLastError()));
         if (range) {  // a value the linear domain cannot hold exactly: the whole call on the log-domain kernel
             rows = false;
-            if (hipMemsetAsync(m->d_ctrl + 1, 0xFF, 8, m->stream) != hipSuccess) return cleanup(fail(TGX_ERR_DEVICE, "memset failed"));
+            if (hipMemsetAsync(m->d_ctrl + 1, 0xFF, 8, m->stream) != hipSuccess) return fail(TGX_ERR_DEVICE, "memset failed");
         } else {
             const uint32_t blocks_t = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((S + 3) / 4, (uint64_t)m->num_cus * 8));
             time_begin(m, "trace32_kernel");
             if (tgx::launch_trace32(p, blocks_t, false, m->stream) != hipSuccess)
-                return cleanup(fail(TGX_ERR_DEVICE, "trace32_kernel launch failed"));
+                return fail(TGX_ERR_DEVICE, "trace32_kernel launch failed");
             time_end(m);
         }
     }
     if (!rows) {
         time_begin(m, "sample_kernel");
         if (tgx::launch_sample(p, q, (uint32_t)m->num_cus, m->stream) != hipSuccess)
-            return cleanup(fail(TGX_ERR_DEVICE, "sample_kernel launch failed"));
+            return fail(TGX_ERR_DEVICE, "sample_kernel launch failed");
         time_end(m);
     }
 
-    // token counts -> offsets -> ids, as encode_corpus_locked does
-    if (!c->d_scan_tmp) {
-        if (tgx::scan_temp_bytes(S, &c->scan_tmp_bytes) != hipSuccess)
-            return cleanup(fail(TGX_ERR_DEVICE, "scan temp-size query failed"));
-        if (c->scan_tmp_bytes && pool_alloc(m->device, c->scan_tmp_bytes, &c->d_scan_tmp) != hipSuccess)
-            return cleanup(fail(TGX_ERR_DEVICE, "out of device memory (scan)"));
-    }
-    time_begin(m, "scan_counts_kernel");
-    if (tgx::launch_scan(c->d_counts, r->d_offs, S, c->d_scan_tmp, c->scan_tmp_bytes, m->stream) != hipSuccess)
-        return cleanup(fail(TGX_ERR_DEVICE, "scan launch failed"));
-    time_end(m);
-    if (hipMemcpyAsync(&m->h_ctrl[0], m->d_ctrl + 1, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
-        hipMemcpyAsync(&m->h_ctrl[1], r->d_offs + S, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
-        hipStreamSynchronize(m->stream) != hipSuccess)
-        return cleanup(fail(TGX_ERR_DEVICE, "sampling pass failed: %s", hipGetErrorString(hipGetLastError())));
-    st = check_no_path(m, c);
-    if (st != TGX_OK) return cleanup(st);
-    r->n_tokens = m->h_ctrl[1];
-    if (pool_alloc(m->device, (size_t)r->n_tokens * 4 + 256, (void**)&r->d_ids) != hipSuccess)
-        return cleanup(fail(TGX_ERR_DEVICE, "out of device memory (result ids)"));
-    tgx::CompactParams cp{};
-    cp.offs = c->d_offs;
-    cp.order = c->d_order;
-    cp.n_samples = S;
-    cp.tmp = c->d_tmp;
-    cp.out_offs = r->d_offs;
-    cp.ids = r->d_ids;
-    const bool crows = S && r->n_tokens / S < 128;
-    const uint64_t units = crows ? 16 : 4;
-    const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((S + units - 1) / units, (uint64_t)m->num_cus * 8));
-    time_begin(m, "compact_kernel");
-    if (tgx::launch_compact(cp, blocks, crows, m->stream) != hipSuccess)
-        return cleanup(fail(TGX_ERR_DEVICE, "compact launch failed"));
-    time_end(m);
+    st = compact_ids(m, c, r, "sampling");
+    if (st != TGX_OK) return st;
     if ((logz && S && hipMemcpyAsync(logz, d_logz, (size_t)S * 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess) ||
         hipStreamSynchronize(m->stream) != hipSuccess)
-        return cleanup(fail(TGX_ERR_DEVICE, "compact failed: %s", hipGetErrorString(hipGetLastError())));
+        return fail(TGX_ERR_DEVICE, "compact failed: %s", hipGetErrorString(hipGetLastError()));
     m->last_alg_bytes = c->n_bytes + 4 * r->n_tokens + 16 * (S + 1);
-    *out = r;
-    return cleanup(TGX_OK);
+    *out = pass.release_result();
+    return pass.done();
 }
 
 tgx_status tgx_encode_corpus_sample(tgx_model* m, tgx_corpus* c, double alpha, uint64_t seed, double* logz, tgx_result** out) {
@@ -3588,12 +3338,7 @@ tgx_status tgx_encode_batch_sample(tgx_model* m, const uint8_t* text, const uint
         const tgx_status st = sample_check(m, alpha);
         if (st != TGX_OK) return st;
     }
-    tgx_corpus* c = nullptr;
-    tgx_status st = tgx_corpus_upload(m->device, text, offs, n_samples, &c);
-    if (st != TGX_OK) return st;
-    st = tgx_encode_corpus_sample(m, c, alpha, seed, logz, out);
-    tgx_corpus_free(c);
-    return st;
+    return on_uploaded_batch(m, text, offs, n_samples, [&](tgx_corpus* c) { return tgx_encode_corpus_sample(m, c, alpha, seed, logz, out); });
 }
 
 // ---- n-best segmentation (nbest.hip) ------------------------------------------------
@@ -3656,38 +3401,25 @@ static tgx_status nbest_corpus_locked(tgx_model* m, tgx_corpus* c, uint32_t k, d
                          [ho](uint32_t a, uint32_t b) { return ho[a + 1] - ho[a] > ho[b + 1] - ho[b]; });
     }
 
-    tgx_result* r = new tgx_result();
-    r->device = m->device;
-    r->n_samples = rows_all;
+    Pass pass(m);
+    tgx_result* r = pass.new_result(rows_all);
     uint32_t *d_bp = nullptr, *d_tmp = nullptr, *d_counts = nullptr, *d_nfound = nullptr, *d_order = nullptr;
     double* d_scores = nullptr;
     void* d_scan = nullptr;
     size_t scan_bytes = 0;
-    std::vector<std::pair<uint32_t*, uint64_t>> parts;  // every chunk's ids
+    const bool one_chunk = cs.size() == 2;  // its ids are the result's; else every chunk's ids, gathered at the end
+    std::vector<std::pair<uint32_t*, uint64_t>> parts;
     const size_t bpb = (size_t)(max_bytes + max_samples) * K * 4 + 256, tb = (size_t)max_bytes * k * 4 + 256;
     const size_t cb = (size_t)rows_all * 4 + 256, sb = (size_t)rows_all * 8 + 256, nb = (size_t)S * 4 + 256;
-    auto cleanup = [&](tgx_status st) {
-        pool_free(m->device, d_bp, bpb);
-        pool_free(m->device, d_tmp, tb);
-        pool_free(m->device, d_counts, cb);
-        pool_free(m->device, d_scores, sb);
-        pool_free(m->device, d_nfound, nb);
-        pool_free(m->device, d_order, nb);
-        pool_free(m->device, d_scan, scan_bytes);
-        for (auto& pt : parts) pool_free(m->device, pt.first, (size_t)pt.second * 4 + 256);
-        if (st != TGX_OK) tgx_result_free(r);
-        return st;
-    };
-    if (tgx::scan_temp_bytes(max_samples * k, &scan_bytes) != hipSuccess) return cleanup(fail(TGX_ERR_DEVICE, "scan temp-size query failed"));
-    if (pool_alloc(m->device, (size_t)(rows_all + 1) * 8, (void**)&r->d_offs) != hipSuccess ||
-        pool_alloc(m->device, bpb, (void**)&d_bp) != hipSuccess || pool_alloc(m->device, tb, (void**)&d_tmp) != hipSuccess ||
-        pool_alloc(m->device, cb, (void**)&d_counts) != hipSuccess || pool_alloc(m->device, sb, (void**)&d_scores) != hipSuccess ||
-        pool_alloc(m->device, nb, (void**)&d_nfound) != hipSuccess || pool_alloc(m->device, nb, (void**)&d_order) != hipSuccess ||
-        (scan_bytes && pool_alloc(m->device, scan_bytes, &d_scan) != hipSuccess))
-        return cleanup(fail(TGX_ERR_DEVICE, "out of device memory (n-best)"));
+    if (tgx::scan_temp_bytes(max_samples * k, &scan_bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan temp-size query failed");
+    if (r->d_offs.alloc(m->device, (size_t)(rows_all + 1) * 8) != hipSuccess || pass.alloc(bpb, &d_bp) != hipSuccess ||
+        pass.alloc(tb, &d_tmp) != hipSuccess || pass.alloc(cb, &d_counts) != hipSuccess || pass.alloc(sb, &d_scores) != hipSuccess ||
+        pass.alloc(nb, &d_nfound) != hipSuccess || pass.alloc(nb, &d_order) != hipSuccess ||
+        (scan_bytes && pass.alloc(scan_bytes, &d_scan) != hipSuccess))
+        return fail(TGX_ERR_DEVICE, "out of device memory (n-best)");
     if ((S && hipMemcpyAsync(d_order, order.data(), (size_t)S * 4, hipMemcpyHostToDevice, m->stream) != hipSuccess) ||
         hipMemsetAsync(r->d_offs, 0, 8, m->stream) != hipSuccess || hipMemsetAsync(m->d_ctrl + 1, 0xFF, 8, m->stream) != hipSuccess)
-        return cleanup(fail(TGX_ERR_DEVICE, "n-best upload failed"));
+        return fail(TGX_ERR_DEVICE, "n-best upload failed");
 
     tgx::NbestParams p{};
     p.text = c->d_text;
@@ -3713,62 +3445,61 @@ static tgx_status nbest_corpus_locked(tgx_model* m, tgx_corpus* c, uint32_t k, d
         p.chunk_bytes = ho[s0 + ns] - ho[s0];
         p.counts = d_counts + R0;
         time_begin(m, "nbest_kernel");
-        if (tgx::launch_nbest(p, K, (uint32_t)m->num_cus, m->stream) != hipSuccess) return cleanup(fail(TGX_ERR_DEVICE, "nbest_kernel launch failed"));
+        if (tgx::launch_nbest(p, K, (uint32_t)m->num_cus, m->stream) != hipSuccess) return fail(TGX_ERR_DEVICE, "nbest_kernel launch failed");
         time_end(m);
         time_begin(m, "nbest_trace_kernel");
         if (tgx::launch_nbest_trace(p, K, (uint32_t)m->num_cus, m->stream) != hipSuccess)
-            return cleanup(fail(TGX_ERR_DEVICE, "nbest_trace_kernel launch failed"));
+            return fail(TGX_ERR_DEVICE, "nbest_trace_kernel launch failed");
         time_end(m);
         time_begin(m, "scan_counts_kernel");
         if (tgx::launch_scan(d_counts + R0, r->d_offs + R0, ns * k, d_scan, scan_bytes, m->stream) != hipSuccess)
-            return cleanup(fail(TGX_ERR_DEVICE, "scan launch failed"));
+            return fail(TGX_ERR_DEVICE, "scan launch failed");
         time_end(m);
         uint64_t tc = 0;
         if (hipMemcpyAsync(&m->h_ctrl[0], m->d_ctrl + 1, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
             hipMemcpyAsync(&m->h_ctrl[1], r->d_offs + R0 + ns * k, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
             hipStreamSynchronize(m->stream) != hipSuccess)
-            return cleanup(fail(TGX_ERR_DEVICE, "n-best pass failed: %s", hipGetErrorString(hipGetLastError())));
+            return fail(TGX_ERR_DEVICE, "n-best pass failed: %s", hipGetErrorString(hipGetLastError()));
         const tgx_status st = check_no_path(m, c);  // chunks go in input order: the first failing one holds the lowest sample
-        if (st != TGX_OK) return cleanup(st);
+        if (st != TGX_OK) return st;
         tc = m->h_ctrl[1];
         uint32_t* ids = nullptr;
-        if (pool_alloc(m->device, (size_t)tc * 4 + 256, (void**)&ids) != hipSuccess)
-            return cleanup(fail(TGX_ERR_DEVICE, "out of device memory (n-best ids)"));
+        const size_t ib = (size_t)tc * 4 + 256;
+        if ((one_chunk ? r->d_ids.alloc(m->device, ib) : pass.alloc(ib, &ids)) != hipSuccess)
+            return fail(TGX_ERR_DEVICE, "out of device memory (n-best ids)");
+        if (one_chunk) ids = r->d_ids;
         parts.push_back({ids, tc});
         time_begin(m, "nbest_compact_kernel");
         if (tgx::launch_nbest_compact(p, r->d_offs + R0, ids, (uint32_t)m->num_cus, m->stream) != hipSuccess)
-            return cleanup(fail(TGX_ERR_DEVICE, "nbest_compact_kernel launch failed"));
+            return fail(TGX_ERR_DEVICE, "nbest_compact_kernel launch failed");
         time_end(m);
         if (total && tgx::launch_offs_add(r->d_offs + R0, ns * k, total, m->stream) != hipSuccess)
-            return cleanup(fail(TGX_ERR_DEVICE, "offset launch failed"));
+            return fail(TGX_ERR_DEVICE, "offset launch failed");
         total += tc;
     }
     r->n_tokens = total;
-    if (parts.size() == 1) {
-        r->d_ids = parts[0].first;
-        parts.clear();
-    } else {
-        if (pool_alloc(m->device, (size_t)total * 4 + 256, (void**)&r->d_ids) != hipSuccess)
-            return cleanup(fail(TGX_ERR_DEVICE, "out of device memory (result ids)"));
+    if (!r->d_ids) {
+        if (r->d_ids.alloc(m->device, (size_t)total * 4 + 256) != hipSuccess)
+            return fail(TGX_ERR_DEVICE, "out of device memory (result ids)");
         uint64_t at = 0;
         for (auto& pt : parts) {
             if (pt.second && hipMemcpyAsync(r->d_ids + at, pt.first, (size_t)pt.second * 4, hipMemcpyDeviceToDevice, m->stream) != hipSuccess)
-                return cleanup(fail(TGX_ERR_DEVICE, "n-best gather failed"));
+                return fail(TGX_ERR_DEVICE, "n-best gather failed");
             at += pt.second;
         }
     }
     if ((scores && rows_all && hipMemcpyAsync(scores, d_scores, (size_t)rows_all * 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess) ||
         (n_found && S && hipMemcpyAsync(n_found, d_nfound, (size_t)S * 4, hipMemcpyDeviceToHost, m->stream) != hipSuccess) ||
         hipStreamSynchronize(m->stream) != hipSuccess)
-        return cleanup(fail(TGX_ERR_DEVICE, "n-best pass failed: %s", hipGetErrorString(hipGetLastError())));
+        return fail(TGX_ERR_DEVICE, "n-best pass failed: %s", hipGetErrorString(hipGetLastError()));
     m->h_ctrl[0] = ~0ULL;
     if (hipMemcpy(&m->h_ctrl[0], m->d_ctrl + 1, 8, hipMemcpyDeviceToHost) != hipSuccess)
-        return cleanup(fail(TGX_ERR_DEVICE, "n-best pass failed"));
+        return fail(TGX_ERR_DEVICE, "n-best pass failed");
     const tgx_status st = check_no_path(m, c);  // (a corrupt back-pointer found by the trace: never a fault)
-    if (st != TGX_OK) return cleanup(st);
+    if (st != TGX_OK) return st;
     m->last_alg_bytes = c->n_bytes + 4 * r->n_tokens + 8 * (rows_all + 1) + 12 * rows_all;
-    *out = r;
-    return cleanup(TGX_OK);
+    *out = pass.release_result();
+    return pass.done();
 }
 
 tgx_status tgx_encode_corpus_nbest(tgx_model* m, tgx_corpus* c, uint32_t nbest, double* scores, uint32_t* n_found, tgx_result** out) {
@@ -3793,12 +3524,7 @@ tgx_status tgx_encode_batch_nbest(tgx_model* m, const uint8_t* text, const uint6
         const tgx_status st = nbest_check(m, nbest);
         if (st != TGX_OK) return st;
     }
-    tgx_corpus* c = nullptr;
-    tgx_status st = tgx_corpus_upload(m->device, text, offs, n_samples, &c);
-    if (st != TGX_OK) return st;
-    st = tgx_encode_corpus_nbest(m, c, nbest, scores, n_found, out);
-    tgx_corpus_free(c);
-    return st;
+    return on_uploaded_batch(m, text, offs, n_samples, [&](tgx_corpus* c) { return tgx_encode_corpus_nbest(m, c, nbest, scores, n_found, out); });
 }
 
 // ---- measurement ---------------------------------------------------------------
