@@ -96,14 +96,31 @@ struct Res5 {
 // conditional load costs the stagger at those depths (see above), so the build with every value in LDS, whose vector and
 // texture units are in balance, loses (12.63 -> 13.07 ms per GiB); the COLD build, whose cold values go through the texture
 // path as well, gains (14.30 -> 13.70).  From depth 7 or 9 on it loses in both.
-template <bool DROPOUT, bool LONG, bool RES, int PPL, int D, bool SKIP = false>
+// COMPACTION (round 5, CK > 0: the hot and COLD builds of encode5_kernel at two to four positions per lane): a trip
+// issues PPL gathers per depth until its deepest walk ends, every lane every gather, and the texture path charges a
+// gather by its live lanes with a floor of ~20 cycles (profiles/r03/d_gather3_dead_lanes.txt) — while 3.46 levels are
+// what an average walk needs.  Every walk still alive at depth CK is at exactly depth CK, so the level that computes
+// the offsets of depth CK does not gather them: the wave counts its live walks (ballot per group), and if they fit in
+// 64 (128) lanes, moves each one's state — next record offset, match-entry base | maxd, the text words of depths CK ..
+// 15 — to lane rank % 64, slot rank / 64 with ds_permute_b32 and goes on with one (two) walks per lane: the same
+// unrolled levels, same match-entry addresses, same matches.  A walk's rank is its group's base plus its rank among
+// the group's live lanes; the DEAD lanes of a group are sent to the lanes its live walks leave free, so every
+// ds_permute is a permutation of the 64 lanes (no lane is written twice, none reads what a lane that receives nothing
+// would read), and a lane knows without a validity word whether, and into which slot, it received a walk.  More live
+// walks than that: the gathers are issued where they are and the trip goes on uncompacted.  PK (packed walks): wlane
+// holds the walk's own column bits (l * 32) as well, the entry of depth d is at bfi(0x1E0, wlane + 32 d, wlane).
+// DESIGN.md section R5.
+template <bool DROPOUT, bool LONG, bool RES, int PPL, int D, bool SKIP = false, int CK = 0, bool PK = false>
 struct Walk5 {
+    static_assert(CK == 0 || (!DROPOUT && !LONG && !RES && PPL >= 2 && D < CK && CK < 16), "compaction: hot and COLD builds of two to four walks per lane");
     // rec[g], c[g]: record and text byte of depth D of walk g (the load may still be in flight)
     static __device__ __forceinline__ void run(const WalkCtx<PPL>& W, Res5& R, const uint32_t (&bytes)[PPL][4], const uint32_t (&maxd)[PPL],
                                                const uint32_t (&pg)[PPL], const uint32_t (&wlane)[PPL], bool (&alive)[PPL],
                                                uint2 (&rec)[PPL], uint32_t (&c)[PPL]) {
         static_assert(!RES || PPL == 1, "resolving walks keep one pending value per lane");
         constexpr int d = D;
+        constexpr bool CUT = CK != 0 && D + 1 == CK;  // this level computes the offsets of depth CK: compact before gathering them
+        uint32_t off_cut[PPL];
         bool any = false;
 #pragma unroll
         for (int g = 0; g < PPL; ++g) {
@@ -127,6 +144,8 @@ struct Walk5 {
                     R.pend_val = buf_ld_f64(R.cold, (idx - R.hot_max - 1u) << 3);
                     R.pend_addr = addr;
                 }
+            } else if (PK) {
+                if (term) lds_st<uint16_t>(((wlane[g] + 32u * (uint32_t)d) & 0x1E0u) | (wlane[g] & ~0x1E0u), (uint16_t)rank);
             } else {
                 if (term) lds_st<uint16_t>(wlane[g] | ((W.l32 + 32u * (uint32_t)d) & 0x1E0u), (uint16_t)rank);
             }
@@ -136,7 +155,9 @@ struct Walk5 {
                 c[g] = (bytes[g][e >> 2] >> ((e & 3) * 8)) & 0xFFu;
                 alive[g] = alive[g] && ((uint32_t)e < maxd[g]);
                 const uint32_t off = (rec[g].x ^ (c[g] << 3)) & 0xFFFFFFu;
-                if (SKIP && D >= 11) {
+                if (CUT) {
+                    off_cut[g] = off;
+                } else if (SKIP && D >= 11) {
                     if (__builtin_amdgcn_ballot_w64(alive[g]) != 0) rec[g] = buf_ld8(W.trie, alive[g] ? off : 0u);
                 } else {
                     rec[g] = buf_ld8(W.trie, alive[g] ? off : 0u);
@@ -150,11 +171,87 @@ struct Walk5 {
             if (RES) R.complete();
             return;
         }
-        Walk5<DROPOUT, LONG, RES, PPL, D + 1, SKIP>::run(W, R, bytes, maxd, pg, wlane, alive, rec, c);
+        if constexpr (CUT) {
+            uint64_t bm[PPL];
+            uint32_t base[PPL], n_alive = 0;
+#pragma unroll
+            for (int g = 0; g < PPL; ++g) {
+                bm[g] = __builtin_amdgcn_ballot_w64(alive[g]);
+                base[g] = n_alive;
+                n_alive += (uint32_t)__builtin_popcountll(bm[g]);
+            }
+            if (n_alive <= 64u) {
+                pack<1>(W, R, bytes, maxd, wlane, alive, off_cut, bm, base, n_alive);
+                return;
+            }
+            if (PPL >= 3 && n_alive <= 128u) {
+                pack<(PPL >= 3 ? 2 : 1)>(W, R, bytes, maxd, wlane, alive, off_cut, bm, base, n_alive);
+                return;
+            }
+#pragma unroll
+            for (int g = 0; g < PPL; ++g) rec[g] = buf_ld8(W.trie, alive[g] ? off_cut[g] : 0u);
+            Walk5<DROPOUT, LONG, RES, PPL, D + 1, SKIP, 0, PK>::run(W, R, bytes, maxd, pg, wlane, alive, rec, c);
+        } else {
+            Walk5<DROPOUT, LONG, RES, PPL, D + 1, SKIP, CK, PK>::run(W, R, bytes, maxd, pg, wlane, alive, rec, c);
+        }
+    }
+
+    // the live walks (bm[g]: group g's, base[g]: the live walks of the groups before) to P2 walks per lane, then the
+    // levels from depth CK on
+    template <int P2>
+    static __device__ __forceinline__ void pack(const WalkCtx<PPL>& W, Res5& R, const uint32_t (&bytes)[PPL][4], const uint32_t (&maxd)[PPL],
+                                                const uint32_t (&wlane)[PPL], const bool (&alive)[PPL], const uint32_t (&off)[PPL],
+                                                const uint64_t (&bm)[PPL], const uint32_t (&base)[PPL], uint32_t n_alive) {
+        constexpr int Q0 = CK >> 2;      // the first text word the levels from CK on read
+        constexpr int NW = 2 + 4 - Q0;   // dwords per walk: offset, entry base | maxd << 24, text words Q0 .. 3
+        const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+        uint32_t v2[P2][NW];
+#pragma unroll
+        for (int t = 0; t < P2; ++t)
+#pragma unroll
+            for (int i = 0; i < NW; ++i) v2[t][i] = 0u;
+#pragma unroll
+        for (int g = 0; g < PPL; ++g) {
+            const uint32_t cnt = (uint32_t)__builtin_popcountll(bm[g]);
+            const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(bm[g] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bm[g], 0u));
+            // live walks to lanes base .. base + cnt - 1, dead ones to the rest (mod 64): a permutation
+            const uint32_t dst = (base[g] + (alive[g] ? below : cnt + lane - below)) & 63u;
+            uint32_t v[NW];
+            v[0] = off[g];
+            v[1] = (PK ? wlane[g] : (wlane[g] | W.l32)) | (maxd[g] << 24);  // (LDS offsets < 2^18, maxd <= 16)
+#pragma unroll
+            for (int q = Q0; q < 4; ++q) v[2 + q - Q0] = bytes[g][q];
+            const uint32_t t = (lane - base[g]) & 63u;  // the walk this lane receives has rank base[g] + t: live iff t < cnt
+            const bool got = t < cnt;
+            const bool hi = base[g] + t >= 64u;
+#pragma unroll
+            for (int i = 0; i < NW; ++i) {
+                const uint32_t x = (uint32_t)__builtin_amdgcn_ds_permute((int)(dst << 2), (int)v[i]);
+#pragma unroll
+                for (int s2 = 0; s2 < P2; ++s2)
+                    if (got && (P2 == 1 || (s2 == 1) == hi)) v2[s2][i] = x;
+            }
+        }
+        WalkCtx<P2> W2{W.trie, W.s, W.l32, W.dropout, W.seed, W.estep_rule};
+        uint32_t bytes2[P2][4], maxd2[P2], pg2[P2], wl2[P2], c2[P2];
+        bool alive2[P2];
+        uint2 rec2[P2];
+#pragma unroll
+        for (int s2 = 0; s2 < P2; ++s2) {
+            alive2[s2] = 64u * (uint32_t)s2 + lane < n_alive;
+            wl2[s2] = v2[s2][1] & 0xFFFFFFu;
+            maxd2[s2] = v2[s2][1] >> 24;
+            pg2[s2] = 0u;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) bytes2[s2][q] = q < Q0 ? 0u : v2[s2][2 + (q < Q0 ? 0 : q - Q0)];
+            c2[s2] = (bytes2[s2][Q0] >> ((CK & 3) * 8)) & 0xFFu;
+            rec2[s2] = buf_ld8(W.trie, alive2[s2] ? v2[s2][0] : 0u);
+        }
+        Walk5<DROPOUT, LONG, RES, P2, CK, SKIP, 0, true>::run(W2, R, bytes2, maxd2, pg2, wl2, alive2, rec2, c2);
     }
 };
-template <bool DROPOUT, bool LONG, bool RES, int PPL, bool SKIP>
-struct Walk5<DROPOUT, LONG, RES, PPL, 16, SKIP> {
+template <bool DROPOUT, bool LONG, bool RES, int PPL, bool SKIP, int CK, bool PK>
+struct Walk5<DROPOUT, LONG, RES, PPL, 16, SKIP, CK, PK> {
     static __device__ __forceinline__ void run(const WalkCtx<PPL>&, Res5& R, const uint32_t (&)[PPL][4], const uint32_t (&)[PPL],
                                                const uint32_t (&)[PPL], const uint32_t (&)[PPL], bool (&)[PPL], uint2 (&)[PPL],
                                                uint32_t (&)[PPL]) {
@@ -300,7 +397,8 @@ __device__ __forceinline__ void e5_long_tail(__amdgpu_buffer_rsrc_t trie, const 
         t_last = _now;                                                 \
     }
 
-template <bool DROPOUT, bool COLD, int PPL, bool LONG>
+// CK: the depth at which the walks are compacted (Walk5; 0: never)
+template <bool DROPOUT, bool COLD, int PPL, bool LONG, int CK = 0>
 __global__ __launch_bounds__(1024, (PPL == 1 ? 8 : (PPL == 2 ? 6 : (PPL == 3 ? 4 : 1)))) void encode5_kernel(EncodeParams P, Encode5Params Q) {
     static_assert(!LONG || PPL == 4, "the long-token build runs four positions per lane");
     extern __shared__ __align__(16) unsigned char smem[];
@@ -440,7 +538,7 @@ __global__ __launch_bounds__(1024, (PPL == 1 ? 8 : (PPL == 2 ? 6 : (PPL == 3 ? 4
             asm volatile("" : "+v"(l32));
             WalkCtx<PPL> W{trie_b, s, l32, P.dropout, P.seed};
             Res5 no_res{};
-            Walk5<DROPOUT, LONG, false, PPL, 0, COLD && PPL < 4>::run(W, no_res, bytes, maxd, pg, wlane, alive, rec, c);  // (four positions per lane: the geometry of batches bound by their chains, where the stagger is worth more — 512 MiB 9.67 -> 10.11 ms with SKIP)
+            Walk5<DROPOUT, LONG, false, PPL, 0, COLD && PPL < 4, CK>::run(W, no_res, bytes, maxd, pg, wlane, alive, rec, c);  // (four positions per lane: the geometry of batches bound by their chains, where the stagger is worth more — 512 MiB 9.67 -> 10.11 ms with SKIP)
         }
         if (LONG) {
 #pragma unroll
@@ -1188,21 +1286,39 @@ hipError_t launch_estep5_fwd(const Estep4Params& p, Encode5Params q, bool cold, 
 }
 
 typedef void (*encode5_fn)(EncodeParams, Encode5Params);
-static encode5_fn pick_encode5(bool dropout, bool cold, int ppl, bool long_tokens) {
+// compact: the depth of Walk5's compaction (0, 4 .. 8); the DROPOUT, LONG and one-position-per-lane builds never compact
+static encode5_fn pick_encode5(bool dropout, bool cold, int ppl, bool long_tokens, int compact) {
     if (long_tokens) {  // tokens of 17..32 bytes: four positions per lane only
         if (cold) return dropout ? encode5_kernel<true, true, 4, true> : encode5_kernel<false, true, 4, true>;
         return dropout ? encode5_kernel<true, false, 4, true> : encode5_kernel<false, false, 4, true>;
     }
-    if (cold) {
-        if (ppl == 1) return dropout ? encode5_kernel<true, true, 1, false> : encode5_kernel<false, true, 1, false>;
-        if (ppl == 2) return dropout ? encode5_kernel<true, true, 2, false> : encode5_kernel<false, true, 2, false>;
-        if (ppl == 3) return dropout ? encode5_kernel<true, true, 3, false> : encode5_kernel<false, true, 3, false>;
-        return dropout ? encode5_kernel<true, true, 4, false> : encode5_kernel<false, true, 4, false>;
+    if (dropout) {
+        if (cold) {
+            if (ppl == 1) return encode5_kernel<true, true, 1, false>;
+            if (ppl == 2) return encode5_kernel<true, true, 2, false>;
+            if (ppl == 3) return encode5_kernel<true, true, 3, false>;
+            return encode5_kernel<true, true, 4, false>;
+        }
+        if (ppl == 1) return encode5_kernel<true, false, 1, false>;
+        if (ppl == 2) return encode5_kernel<true, false, 2, false>;
+        if (ppl == 3) return encode5_kernel<true, false, 3, false>;
+        return encode5_kernel<true, false, 4, false>;
     }
-    if (ppl == 1) return dropout ? encode5_kernel<true, false, 1, false> : encode5_kernel<false, false, 1, false>;
-    if (ppl == 2) return dropout ? encode5_kernel<true, false, 2, false> : encode5_kernel<false, false, 2, false>;
-    if (ppl == 3) return dropout ? encode5_kernel<true, false, 3, false> : encode5_kernel<false, false, 3, false>;
-    return dropout ? encode5_kernel<true, false, 4, false> : encode5_kernel<false, false, 4, false>;
+#define TGX_E5K(C, PL) \
+    (compact == 4 ? encode5_kernel<false, C, PL, false, 4> : compact == 5 ? encode5_kernel<false, C, PL, false, 5> \
+     : compact == 6 ? encode5_kernel<false, C, PL, false, 6> : compact == 7 ? encode5_kernel<false, C, PL, false, 7> \
+     : compact == 8 ? encode5_kernel<false, C, PL, false, 8> : encode5_kernel<false, C, PL, false, 0>)
+    if (cold) {
+        if (ppl == 1) return encode5_kernel<false, true, 1, false>;
+        if (ppl == 2) return TGX_E5K(true, 2);
+        if (ppl == 3) return TGX_E5K(true, 3);
+        return TGX_E5K(true, 4);
+    }
+    if (ppl == 1) return encode5_kernel<false, false, 1, false>;
+    if (ppl == 2) return TGX_E5K(false, 2);
+    if (ppl == 3) return TGX_E5K(false, 3);
+    return TGX_E5K(false, 4);
+#undef TGX_E5K
 }
 
 // LDS of one block of `waves` waves: score table (-inf and n_hot values), the waves' lists of long matches (LONG
@@ -1223,9 +1339,9 @@ uint32_t encode5_max_hot(bool long_tokens, int waves, int ppl, uint32_t budget) 
     return budget > fixed + 64u ? (budget - fixed) / 8u : 0u;
 }
 
-hipError_t encode5_waves_per_simd(bool dropout, bool cold, int ppl, bool long_tokens, int* out) {
+hipError_t encode5_waves_per_simd(bool dropout, bool cold, int ppl, bool long_tokens, int compact, int* out) {
     hipFuncAttributes attr;
-    hipError_t e = hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(pick_encode5(dropout, cold, ppl, long_tokens)));
+    hipError_t e = hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(pick_encode5(dropout, cold, ppl, long_tokens, compact)));
     if (e != hipSuccess) return e;
     const int regs = (attr.numRegs + 7) & ~7;
     *out = regs > 0 ? (512 / regs > 8 ? 8 : 512 / regs) : 8;
@@ -1264,10 +1380,13 @@ hipError_t launch_encode6(const EncodeParams& p, Encode5Params q, bool cold, uin
     return hipGetLastError();
 }
 
-hipError_t launch_encode5(const EncodeParams& p, Encode5Params q, bool cold, int ppl, bool long_tokens, int waves, uint32_t blocks, uint32_t min_lds, hipStream_t stream) {
+hipError_t launch_encode5(const EncodeParams& p, Encode5Params q, bool cold, int ppl, bool long_tokens, int compact, int waves, uint32_t blocks,
+                          uint32_t min_lds, hipStream_t stream) {
     uint32_t lds = encode5_lds_layout(q.n_hot, long_tokens, waves, ppl, &q.list_off, &q.root_off, &q.idx_off);
-    if (lds > 160u * 1024u || q.n_hot > q.n_values || (!cold && q.n_hot != q.n_values) || (long_tokens && ppl != 4)) return hipErrorInvalidValue;
-    encode5_fn fn = pick_encode5(p.dropout > 0.0, cold, ppl, long_tokens);
+    if (lds > 160u * 1024u || q.n_hot > q.n_values || (!cold && q.n_hot != q.n_values) || (long_tokens && ppl != 4) ||
+        (compact != 0 && (compact < 4 || compact > 8)))
+        return hipErrorInvalidValue;
+    encode5_fn fn = pick_encode5(p.dropout > 0.0, cold, ppl, long_tokens, compact);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return e;
     if (lds < min_lds && min_lds <= 160u * 1024u) lds = min_lds;  // (a launch that wants its CUs to itself)

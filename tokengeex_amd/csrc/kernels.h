@@ -271,7 +271,7 @@ uint32_t encode4_lds_bytes(int waves, int ppl, bool root);
 hipError_t launch_trace(const EncodeParams& p, uint32_t blocks, hipStream_t stream);
 uint32_t encode5_lds_layout(uint32_t n_hot, bool long_tokens, int waves, int ppl, uint32_t* list_off, uint32_t* root_off, uint32_t* idx_off);
 uint32_t encode5_max_hot(bool long_tokens, int waves, int ppl, uint32_t budget);
-hipError_t encode5_waves_per_simd(bool dropout, bool cold, int ppl, bool long_tokens, int* out);
+hipError_t encode5_waves_per_simd(bool dropout, bool cold, int ppl, bool long_tokens, int compact, int* out);
 uint32_t encode6_lds_layout(uint32_t n_hot, uint32_t pool, uint32_t* root_off, uint32_t* ctrl_off, uint32_t* ring_off);
 uint32_t encode6_max_hot(uint32_t budget, uint32_t pool);
 uint32_t encode6_pool_total(uint32_t pool);  // pool entries of a block (index space they take)
@@ -279,7 +279,8 @@ uint32_t encode6_pool_total(uint32_t pool);  // pool entries of a block (index s
 hipError_t estep5_waves_per_simd(bool dropout, bool cold, int ppl, int* out);
 hipError_t launch_estep5_fwd(const struct Estep4Params& p, Encode5Params q, bool cold, int ppl, int waves, uint32_t blocks, hipStream_t stream);
 hipError_t launch_encode6(const EncodeParams& p, Encode5Params q, bool cold, uint32_t blocks, hipStream_t stream);
-hipError_t launch_encode5(const EncodeParams& p, Encode5Params q, bool cold, int ppl, bool long_tokens, int waves, uint32_t blocks,
+// compact: the depth at which the walks of a trip are compacted (0: never; 4 .. 8; encode5.hip: Walk5)
+hipError_t launch_encode5(const EncodeParams& p, Encode5Params q, bool cold, int ppl, bool long_tokens, int compact, int waves, uint32_t blocks,
                           uint32_t min_lds, hipStream_t stream);
 hipError_t launch_encode2(const EncodeParams& p, uint32_t num_cus, bool permuted, hipStream_t stream);   // encode2.hip
 hipError_t launch_trace32(const EncodeParams& p, uint32_t blocks, bool permuted, hipStream_t stream);

@@ -214,6 +214,8 @@ struct KernelTime {
     bool used;
 };
 constexpr int kMaxTimed = 8;
+// encode5_kernel: the depth at which a trip's live walks are compacted (0: never; TGX_E5_COMPACT=off|4..8 overrides)
+constexpr int kE5CompactDepth = 5;
 
 }  // namespace
 
@@ -694,9 +696,12 @@ tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64
         const uint64_t rest_bytes = c->n_bytes - (n_long ? c->h_sorted_cum[n_long - 1] : 0);
         const uint64_t rest_max = rest_n ? c->h_sorted_len[n_long] : 0;
         int ppl = 4, bpc = 1, hot_waves = 16;  // hot_waves: the most waves beside which every value fits
+        // the depth at which a trip's live walks are packed into fewer lanes (encode5.hip: Walk5)
+        int compact = kE5CompactDepth;
+        if (const char* e = knob("TGX_E5_COMPACT")) compact = (strcmp(e, "off") == 0 || atoi(e) == 0) ? 0 : std::min(8, std::max(4, atoi(e)));
         {
             int ps4 = 0;
-            HIP_TRY(tgx::encode5_waves_per_simd(dropout > 0.0, false, 4, long_tokens, &ps4));
+            HIP_TRY(tgx::encode5_waves_per_simd(dropout > 0.0, false, 4, long_tokens, compact, &ps4));
             hot_waves = std::min(16, ps4 * 4);
             const int least = long_tokens ? 12 : 13;  // (the long-token build has four positions per lane only)
             while (hot_waves >= least && m->n_values > tgx::encode5_max_hot(long_tokens, hot_waves, 4, 160u * 1024u)) hot_waves--;
@@ -747,12 +752,12 @@ tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64
         const uint32_t budget = 160u * 1024u / (uint32_t)bpc;
         bool cold = false;
         int per_simd = 0;
-        HIP_TRY(tgx::encode5_waves_per_simd(dropout > 0.0, false, ppl, long_tokens, &per_simd));
+        HIP_TRY(tgx::encode5_waves_per_simd(dropout > 0.0, false, ppl, long_tokens, compact, &per_simd));
         int waves = std::min(16, (per_simd / bpc) * 4);
         if ((ppl == 4 || ppl == 3) && bpc == 1 && hot_waves > 0) waves = std::min(waves, hot_waves);
         if (m->n_values > tgx::encode5_max_hot(long_tokens, waves, ppl, budget)) {
             cold = true;
-            HIP_TRY(tgx::encode5_waves_per_simd(dropout > 0.0, true, ppl, long_tokens, &per_simd));
+            HIP_TRY(tgx::encode5_waves_per_simd(dropout > 0.0, true, ppl, long_tokens, compact, &per_simd));
             waves = std::min(16, (per_simd / bpc) * 4);
         }
         if (balance_waves > 0 && ppl == 4 && bpc == 1) waves = std::min(waves, balance_waves);
@@ -840,7 +845,7 @@ tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64
                 HIP_TRY(hipMemsetAsync(m->d_ctrl + 6, 0x00, 8, m->stream));
             }
             // (co-run: more than half of the CU's LDS, so that no block of the long-sample kernel shares the CU)
-            const hipError_t le = tgx::launch_encode5(p, q, cold, ppl, long_tokens, waves, blocks5, corun_cus && n_long ? 84u * 1024u : 0u, m->stream);
+            const hipError_t le = tgx::launch_encode5(p, q, cold, ppl, long_tokens, compact, waves, blocks5, corun_cus && n_long ? 84u * 1024u : 0u, m->stream);
             if (le != hipSuccess) return fail(TGX_ERR_DEVICE, "encode5 launch failed: %s", hipGetErrorString(le));
         }
         bool joined = false, joined_slot = false;
