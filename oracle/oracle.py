@@ -65,6 +65,10 @@ def lib() -> C.CDLL:
     L.orc_estep.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_double,
                             C.c_uint64, C.c_int, C.c_void_p, C.POINTER(C.c_double),
                             C.POINTER(C.c_uint64)]
+    L.orc_marginal_ext.restype = C.c_double
+    L.orc_marginal_ext.argtypes = L.orc_marginal.argtypes
+    L.orc_estep_ext.restype = C.c_int
+    L.orc_estep_ext.argtypes = L.orc_estep.argtypes
     L.orc_count_tokens.restype = C.c_int
     L.orc_count_tokens.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int,
                                    C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -190,6 +194,27 @@ class OracleModel:
         es = C.c_uint64()
         st = lib().orc_estep(self._h, _ptr(flat), _ptr(offs), S, snippet_len, dropout, seed, threads,
                              _ptr(expected), C.byref(z), C.byref(es))
+        return st, expected, z.value, es.value
+
+    def marginal_ext(self, snippet: bytes, dropout: float = 0.0, seed: int = 0, sample_index: int = 0,
+                     snippet_base: int = 0):
+        """marginal() in 80-bit extended precision (orc_marginal_ext): the truth f64 results are measured
+        against.  -> (expected float64[V], log z)"""
+        buf = np.frombuffer(snippet, dtype=np.uint8) if len(snippet) else np.zeros(0, np.uint8)
+        expected = np.zeros(self.vocab_size, np.float64)
+        z = lib().orc_marginal_ext(self._h, _ptr(buf), len(snippet), dropout, seed, sample_index,
+                                   snippet_base, _ptr(expected))
+        return expected, z
+
+    def estep_ext_flat(self, flat, offs, snippet_len: int = 81920, dropout: float = 0.0, seed: int = 0,
+                       threads: int = 8):
+        """estep_flat() in 80-bit extended precision (orc_estep_ext). -> (status, expected, logz_sum, err_sample)"""
+        S = offs.shape[0] - 1
+        expected = np.zeros(self.vocab_size, np.float64)
+        z = C.c_double()
+        es = C.c_uint64()
+        st = lib().orc_estep_ext(self._h, _ptr(flat), _ptr(offs), S, snippet_len, dropout, seed, threads,
+                                 _ptr(expected), C.byref(z), C.byref(es))
         return st, expected, z.value, es.value
 
     def count_tokens_flat(self, flat, offs, threads: int = 1):

@@ -14,6 +14,8 @@
  */
 #include "tgx_oracle.h"
 
+#include <float.h>
+#include <limits.h>
 #include <math.h>
 #include <pthread.h>
 #include <stdatomic.h>
@@ -638,6 +640,200 @@ int orc_estep(const orc_model *m, const uint8_t *text, const uint64_t *offs, uin
     free(c.local_expected);
     free(c.local_z);
     free(c.lat);
+    pthread_mutex_destroy(&c.err.mu);
+    return c.err.status;
+}
+
+/* ---- the E-step in 80-bit extended precision (truth for the f64 oracle and the kernels) ---- */
+#if LDBL_MANT_DIG != 64
+#error "orc_marginal_ext / orc_estep_ext need the x87 80-bit long double (64-bit mantissa)"
+#endif
+
+/* Per-thread scratch of the extended-precision sweeps: per position a mantissa in [0.5, 1) and its own
+ * binary exponent for F (forward) and G (backward), per node its weight expl(score). */
+typedef struct {
+    long double *fm, *gm, *w;
+    int *fe, *ge;
+    size_t pos_cap, node_cap;
+} ext_scratch;
+
+static void ext_scratch_destroy(ext_scratch *x) {
+    free(x->fm);
+    free(x->gm);
+    free(x->w);
+    free(x->fe);
+    free(x->ge);
+}
+
+static inline void ext_norm(long double v, long double *m, int *e, int e0) {
+    int k;
+    *m = frexpl(v, &k);
+    *e = e0 + k;
+}
+
+/* populate_marginal's per-node semantics (src/lattice.rs:245-312) in the linear domain.  F[0] = 1;
+ * F[p] = sum of F[q] w over the nodes (q, len = p - q) ending at p, or exactly 1 where none does
+ * (alpha keeps its 0.0, :255-256).  G[len] = 1 (EOS); G[p] = sum of w G[p + len] over the nodes
+ * beginning at p, or exactly 1 where none does.  Z = F[len]; node (p, id, len) adds
+ * F[p] w G[p + len] / Z to expected[id].  Returns log Z. */
+static long double marginal_ext(const lattice *l, ext_scratch *x, long double *expected) {
+    size_t len = l->len, num_nodes = l->n_nodes;
+    if (len + 1 > x->pos_cap) {
+        x->pos_cap = 2 * (len + 1);
+        x->fm = (long double *)realloc(x->fm, sizeof(long double) * x->pos_cap);
+        x->gm = (long double *)realloc(x->gm, sizeof(long double) * x->pos_cap);
+        x->fe = (int *)realloc(x->fe, sizeof(int) * x->pos_cap);
+        x->ge = (int *)realloc(x->ge, sizeof(int) * x->pos_cap);
+    }
+    if (num_nodes > x->node_cap) {
+        x->node_cap = 2 * num_nodes;
+        x->w = (long double *)realloc(x->w, sizeof(long double) * x->node_cap);
+    }
+    long double *fm = x->fm, *gm = x->gm, *w = x->w;
+    int *fe = x->fe, *ge = x->ge;
+    for (size_t i = 0; i < num_nodes; i++) w[i] = expl((long double)l->nodes[i].score);
+
+    ext_norm(1.0L, &fm[0], &fe[0], 0); /* BOS: the only node ending at 0 */
+    for (size_t pos = 1; pos <= len; pos++) {
+        const ivec *en = &l->end_nodes[pos];
+        if (en->n == 0) {
+            ext_norm(1.0L, &fm[pos], &fe[pos], 0);
+            continue;
+        }
+        int emax = INT_MIN;
+        for (uint32_t q = 0; q < en->n; q++) {
+            int e = fe[l->nodes[en->d[q]].pos];
+            if (e > emax) emax = e;
+        }
+        long double s = 0.0L;
+        for (uint32_t q = 0; q < en->n; q++) {
+            size_t lid = en->d[q], from = l->nodes[lid].pos;
+            s += ldexpl(fm[from] * w[lid], fe[from] - emax);
+        }
+        ext_norm(s, &fm[pos], &fe[pos], emax);
+    }
+    ext_norm(1.0L, &gm[len], &ge[len], 0); /* EOS: the only node beginning at len */
+    for (size_t pos = len; pos-- > 0;) {
+        const ivec *bn = &l->begin_nodes[pos];
+        if (bn->n == 0) {
+            ext_norm(1.0L, &gm[pos], &ge[pos], 0);
+            continue;
+        }
+        int emax = INT_MIN;
+        for (uint32_t r = 0; r < bn->n; r++) {
+            int e = ge[pos + l->nodes[bn->d[r]].token_len];
+            if (e > emax) emax = e;
+        }
+        long double s = 0.0L;
+        for (uint32_t r = 0; r < bn->n; r++) {
+            size_t rid = bn->d[r], to = pos + l->nodes[rid].token_len;
+            s += ldexpl(w[rid] * gm[to], ge[to] - emax);
+        }
+        ext_norm(s, &gm[pos], &ge[pos], emax);
+    }
+    long double zm = fm[len];
+    int ze = fe[len];
+    for (size_t pos = 0; pos < len; pos++) {
+        const ivec *bn = &l->begin_nodes[pos];
+        for (uint32_t r = 0; r < bn->n; r++) {
+            size_t idx = bn->d[r], to = pos + l->nodes[idx].token_len;
+            expected[l->nodes[idx].token_id] +=
+                ldexpl(fm[pos] * w[idx] * gm[to] / zm, fe[pos] + ge[to] - ze);
+        }
+    }
+    /* mantissa in [1, 2): Z == 1 gives log Z == 0.0 exactly, as the f64 oracle's z */
+    return logl(2.0L * zm) + (long double)(ze - 1) * 0.693147180559945309417232121458176568L;
+}
+
+double orc_marginal_ext(const orc_model *m, const uint8_t *snippet, size_t n, double dropout,
+                        uint64_t seed, uint64_t sample_index, uint64_t snippet_base,
+                        double *expected) {
+    uint32_t V = m->vocab_size;
+    lattice l;
+    memset(&l, 0, sizeof(l));
+    ext_scratch x;
+    memset(&x, 0, sizeof(x));
+    long double *ex = (long double *)calloc(V ? V : 1, sizeof(long double));
+    lattice_from(&l, snippet, n);
+    populate_nodes(m, &l, dropout, seed, sample_index, snippet_base);
+    long double z = marginal_ext(&l, &x, ex);
+    for (uint32_t i = 0; i < V; i++) expected[i] += (double)ex[i];
+    free(ex);
+    ext_scratch_destroy(&x);
+    lattice_destroy(&l);
+    return (double)z;
+}
+
+typedef struct {
+    const orc_model *m;
+    const uint8_t *text;
+    const uint64_t *offs;
+    uint64_t snippet_len;
+    double dropout;
+    uint64_t seed;
+    long double **local_expected; /* per thread */
+    long double *local_z;
+    lattice *lat;
+    ext_scratch *scr;
+    err_slot err;
+} estep_ext_ctx;
+
+static void estep_ext_chunk(void *p, uint64_t lo, uint64_t hi, int tid) {
+    estep_ext_ctx *c = (estep_ext_ctx *)p;
+    lattice *l = &c->lat[tid];
+    for (uint64_t s = lo; s < hi; s++) {
+        const uint8_t *sample = c->text + c->offs[s];
+        uint64_t n = c->offs[s + 1] - c->offs[s];
+        for (uint64_t base = 0; base < n; base += c->snippet_len) { /* src/prune.rs:83 */
+            uint64_t sn = n - base < c->snippet_len ? n - base : c->snippet_len;
+            lattice_from(l, sample + base, (size_t)sn);
+            populate_nodes(c->m, l, c->dropout, c->seed, s, base);
+            long double z = marginal_ext(l, &c->scr[tid], c->local_expected[tid]);
+            if (fpclassify((double)z) != FP_NORMAL) err_record(&c->err, ORC_ERR_Z_NOT_NORMAL, s, base);
+            c->local_z[tid] += z;
+        }
+    }
+}
+
+int orc_estep_ext(const orc_model *m, const uint8_t *text, const uint64_t *offs, uint64_t n_samples,
+                  uint64_t snippet_len, double dropout, uint64_t seed, int n_threads,
+                  double *expected, double *logz_sum, uint64_t *err_sample) {
+    if (n_threads < 1) n_threads = 1;
+    uint32_t V = m->vocab_size;
+    estep_ext_ctx c;
+    memset(&c, 0, sizeof(c));
+    c.m = m;
+    c.text = text;
+    c.offs = offs;
+    c.snippet_len = snippet_len ? snippet_len : 81920;
+    c.dropout = dropout;
+    c.seed = seed;
+    c.local_expected = (long double **)calloc((size_t)n_threads, sizeof(long double *));
+    c.local_z = (long double *)calloc((size_t)n_threads, sizeof(long double));
+    c.lat = (lattice *)calloc((size_t)n_threads, sizeof(lattice));
+    c.scr = (ext_scratch *)calloc((size_t)n_threads, sizeof(ext_scratch));
+    for (int t = 0; t < n_threads; t++)
+        c.local_expected[t] = (long double *)calloc(V ? V : 1, sizeof(long double));
+    pthread_mutex_init(&c.err.mu, NULL);
+    c.err.status = ORC_OK;
+    par_chunks(n_samples, n_threads, 8, estep_ext_chunk, &c);
+    /* merged in long double, in thread order; rounded to double once */
+    long double zsum = 0.0L;
+    for (int t = 1; t < n_threads; t++)
+        for (uint32_t i = 0; i < V; i++) c.local_expected[0][i] += c.local_expected[t][i];
+    for (uint32_t i = 0; i < V; i++) expected[i] += (double)c.local_expected[0][i];
+    for (int t = 0; t < n_threads; t++) {
+        zsum += c.local_z[t];
+        free(c.local_expected[t]);
+        lattice_destroy(&c.lat[t]);
+        ext_scratch_destroy(&c.scr[t]);
+    }
+    if (logz_sum) *logz_sum = (double)zsum;
+    if (c.err.status != ORC_OK && err_sample) *err_sample = c.err.sample;
+    free(c.local_expected);
+    free(c.local_z);
+    free(c.lat);
+    free(c.scr);
     pthread_mutex_destroy(&c.err.mu);
     return c.err.status;
 }

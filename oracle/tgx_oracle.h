@@ -79,6 +79,25 @@ int orc_estep(const orc_model *m, const uint8_t *text, const uint64_t *offs,
               uint64_t n_samples, uint64_t snippet_len, double dropout, uint64_t seed,
               int n_threads, double *expected, double *logz_sum, uint64_t *err_sample);
 
+/* The same two E-step entry points in 80-bit extended precision: the TRUTH that the f64 oracle above
+ * and the GPU kernels are measured against (tests only).  Same arguments, snippet cutting, threading and
+ * status as orc_marginal / orc_estep; the nodes (matches, dropout decisions) are theirs, only the
+ * arithmetic differs: linear domain in long double with a normalised mantissa and its own binary
+ * exponent per position, w = expl(score), expected counts accumulated and merged in long double and
+ * rounded to double once, log Z = logl(m) + e ln 2.  The reference's per-node semantics are kept,
+ * quirks included (src/lattice.rs:245-312): a position no node ends at has forward value exactly 1
+ * (alpha keeps its 0.0, :255-256), one no node begins at has backward value exactly 1; if nothing ends
+ * at the snippet's end, z is exactly 0.0 and orc_estep_ext reports ORC_ERR_Z_NOT_NORMAL for the sample
+ * orc_estep reports.  The reference's log_sum_exp drops a term more than 50 below the running sum
+ * (:321-333); that cut-off is deliberately absent here: each such term is below e^-50 < 2e-22 of the
+ * sum it would have joined.  Build fails where long double is not the 64-bit-mantissa x87 type. */
+double orc_marginal_ext(const orc_model *m, const uint8_t *snippet, size_t n, double dropout,
+                        uint64_t seed, uint64_t sample_index, uint64_t snippet_base,
+                        double *expected);
+int orc_estep_ext(const orc_model *m, const uint8_t *text, const uint64_t *offs,
+                  uint64_t n_samples, uint64_t snippet_len, double dropout, uint64_t seed,
+                  int n_threads, double *expected, double *logz_sum, uint64_t *err_sample);
+
 /* frequency pass — src/prune.rs:205-244: freq[id] += 1 over Viterbi ids. */
 int orc_count_tokens(const orc_model *m, const uint8_t *text, const uint64_t *offs,
                      uint64_t n_samples, int n_threads, uint64_t *freq,

@@ -22,7 +22,7 @@ import tokengeex_amd as tgx
 from oracle import oracle as orc
 from tokengeex_amd import synth
 
-from util import assert_same_encoding, load_vocab_500k
+from util import assert_estep_truth, assert_same_encoding, load_vocab_500k
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -64,6 +64,7 @@ def test_config3_prune_passes_at_500k_vocab():
     np.testing.assert_allclose(got, want, rtol=1.2e-8 * max(1.0, longest / 4096.0), atol=1e-12)
     assert np.array_equal(got != 0, want != 0)
     assert abs(gz - wz) <= 1e-12 * abs(wz) + 1e-9
+    assert assert_estep_truth(got, gz, nat.last_kernel_times(), ora, sf, so, want=want, wz=wz) == "linear"
     mass = float(np.dot(got, np.array([len(t) for t in toks], np.float64)))
     assert abs(mass - sf.size) < 1e-6 * sf.size       # every byte covered with total mass 1
     assert "estep7_kernel" in nat.last_kernel_times()   # round 4: 32-bit match entries for more than 65 535 tokens

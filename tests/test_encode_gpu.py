@@ -12,7 +12,7 @@ import tokengeex_amd as tgx
 from oracle import oracle as orc
 from tokengeex_amd import synth
 
-from util import assert_same_encoding, corpus_and_vocab
+from util import assert_estep_truth, assert_same_encoding, corpus_and_vocab
 
 
 def _pair(tokens, scores):
@@ -213,11 +213,13 @@ def test_committed_spec_vocabularies_against_the_oracle(size):
     np.testing.assert_array_equal(keys, wk)
     np.testing.assert_array_equal(counts, wc)
     got, gz = nat.estep(corpus)
+    kernels = nat.last_kernel_times()
     st, want, wz, _ = ora.estep_flat(flat, offs, threads=8)
     assert st == orc.OK
     longest = int(np.diff(offs.astype(np.int64)).max())
     np.testing.assert_allclose(got, want, rtol=1.2e-8 * max(1.0, longest / 4096.0), atol=1e-12)
     assert np.array_equal(got != 0, want != 0) and abs(gz - wz) <= 1e-12 * abs(wz) + 1e-9
+    assert_estep_truth(got, gz, kernels, ora, flat, offs, want=want, wz=wz)
 
 
 def test_both_kernel_paths_agree(monkeypatch):

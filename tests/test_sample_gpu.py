@@ -66,6 +66,36 @@ def _checked(name, alpha, viterbi=False):
             for i, (inc, t) in enumerate(zip(_incoming(name), _corpus()))]
 
 
+@functools.lru_cache(maxsize=None)
+def _logz_truth(name, alpha):
+    """Per-sample log Z in 80-bit extended precision: orc_marginal_ext on the model with scores alpha * scores (the
+    corpus vocabularies cover every byte, so the lattice quirks do not apply)."""
+    toks, scores = _vocab(name)
+    om = orc.OracleModel(toks, alpha * scores)
+    return np.array([om.marginal_ext(t)[1] for t in _corpus()])
+
+
+def _assert_logz_truth(name, alpha, logz, kernels):
+    """sample_rows_kernel (linear domain, exact power-of-two rescales): |logz - truth| <= 1e-13 max(1, |truth|) (measured:
+    5e-15 relative at most).
+    sample_kernel (log domain): each of the n positions adds a log-sum-exp whose rounding is ~ulp(|z_p|) at the running
+    |z_p| <= |z|, and those roundings random-walk: the error is ~sqrt(n) ulp(|z|) = sqrt(n) 2^-52 |z|, the model of the
+    E-step's log-domain kernels (tests/test_estep_pairs_gpu.py, rtol_for).  Several roundings per step (exp, log1p, the
+    adds, a sum over the incoming tokens) make the factor in front larger than 1: measured 14 at the longest sample (2.5e-8 at the
+    70 000-byte sample with alpha 0, |z| = 3.2e4; 1.2e-8 at |z| = 1.7e5), so the bound is 64 sqrt(n) 2^-52 |z| + 1e-13:
+    1e-7 .. 6e-7 absolute at that sample, against today's 1e-9 |z| = 3e-5 .. 1.7e-4."""
+    truth = _logz_truth(name, alpha)
+    lens = np.array([len(t) for t in _corpus()], np.float64)
+    if "sample_rows_kernel" in kernels:
+        bound = 1e-13 * np.maximum(1.0, np.abs(truth))
+    else:
+        assert "sample_kernel" in kernels, kernels
+        bound = 64.0 * np.sqrt(np.maximum(lens, 1.0)) * 2.0 ** -52 * np.abs(truth) + 1e-13
+    err = np.abs(np.asarray(logz) - truth)
+    i = int(np.argmax(err / bound))
+    assert np.all(err <= bound), (i, len(_corpus()[i]), logz[i], truth[i], err[i], bound[i])
+
+
 def _rows(res):
     ids, oo = res.ids(), res.offsets()
     res.free()
@@ -101,6 +131,7 @@ def test_ids_match_the_checker(vocab, sample_path, alpha):
     else:
         assert "sample_kernel" in names and "sample_rows_kernel" not in names, names
     want = _checked(vocab, alpha)
+    _assert_logz_truth(vocab, alpha, logz, names)
     close = 0
     for i, w in enumerate(want):
         assert abs(logz[i] - w["logz"]) <= 1e-9 * max(1.0, abs(w["logz"])), (i, logz[i], w["logz"])
@@ -148,6 +179,7 @@ def test_logz_matches_the_marginal_and_the_estep(sample_path, alpha):
     texts = _corpus()
     _, logz = _sample(native, texts, alpha, logz=True)
     om = orc.OracleModel(toks, alpha * scores)
+    _assert_logz_truth("vocab_32000", alpha, logz, native.last_kernel_times())
     for i, t in enumerate(texts):
         if len(t) <= 81920:
             _, z = om.marginal(t)

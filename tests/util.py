@@ -83,6 +83,85 @@ def estep_longdouble(oracle_model, text: bytes):
     return expected.astype(np.float64), logz
 
 
+def rtol_for(snippet_bytes):
+    """Tolerance between the f64 oracle (or a log-domain kernel) and the truth: the reference's log-domain sums are
+    only defined to ~sqrt(n) ulp(|z|) (tests/test_estep_pairs_gpu.py)."""
+    return 1.2e-8 * max(1.0, snippet_bytes / 4096.0)
+
+
+# kernels whose arithmetic is the linear domain (exact power-of-two rescales) and the log-domain ones
+LINEAR_ESTEP = ("estep7_kernel", "estep7_redo_kernel", "estep4l_fwd_kernel", "estep4l_bwd_kernel", "estep5_fwd_kernel")
+LOG_ESTEP = ("estep4_fwd_kernel", "estep4_bwd_kernel", "estep_kernel")
+_TRUTH: dict = {}
+
+
+def _digest(*arrays) -> str:
+    import hashlib
+    h = hashlib.sha1()
+    for a in arrays:
+        a = np.ascontiguousarray(a)
+        h.update(str((a.dtype, a.shape)).encode())
+        h.update(a.tobytes())
+    return h.hexdigest()
+
+
+def estep_truth(oracle_model, flat, offs, snippet_len=81920, dropout=0.0, seed=0):
+    """orc_estep_ext (80-bit extended precision) of one pass, cached per (model, corpus, snippet length, dropout, seed).
+    -> (status, expected, logz_sum, err_sample)"""
+    key = (_digest(oracle_model._flat, oracle_model._offs, oracle_model.scores), _digest(flat, offs),
+           int(snippet_len), float(dropout), int(seed))
+    if key not in _TRUTH:
+        if len(_TRUTH) >= 24:
+            _TRUTH.pop(next(iter(_TRUTH)))
+        _TRUTH[key] = oracle_model.estep_ext_flat(flat, offs, snippet_len, dropout, seed, threads=8)
+    return _TRUTH[key]
+
+
+def estep_family(kernels) -> str:
+    """'log' when any log-domain E-step kernel ran (a fallback included), else 'linear' (some linear kernel must have)."""
+    if any(k in kernels for k in LOG_ESTEP):
+        return "log"
+    assert any(k in kernels for k in LINEAR_ESTEP), kernels
+    return "linear"
+
+
+def estep_gate(got, gz, kernels, truth, tz, longest):
+    """The two-sided gate of tests/measure/fuzz_gpu.py: a pass of the kernels against the truth, with the bounds of
+    assert_estep_truth.  -> (family, ok, largest relative distance on counts above 1e-9)"""
+    fam = estep_family(kernels)
+    big = truth > 1e-9
+    dist = float((np.abs(got - truth)[big] / truth[big]).max()) if big.any() else 0.0
+    if fam == "linear":
+        ok = bool(np.allclose(got, truth, rtol=1e-10, atol=1e-13)) and abs(gz - tz) <= 1e-13 * abs(tz)
+    else:
+        ok = bool(np.allclose(got, truth, rtol=rtol_for(longest), atol=1e-12)) and abs(gz - tz) <= 1e-12 * abs(tz) + 1e-9
+    return fam, ok, dist
+
+
+def assert_estep_truth(got, gz, kernels, oracle_model, flat, offs, snippet_len=81920, dropout=0.0, seed=0,
+                       want=None, wz=None):
+    """The truth gate of every E-step comparison.  Linear-domain kernels: every count within rtol 1e-10, atol 1e-13 of
+    the truth and log Z within 1e-13 relative.  Log-domain kernels: within rtol_for(longest snippet) — their error is
+    the f64 oracle's kind.  The oracle's own result (want, wz), when given, must be within rtol_for of the truth: if that
+    fails it is the f64 formula's rounding, not a kernel's."""
+    st, truth, tz, _ = estep_truth(oracle_model, flat, offs, snippet_len, dropout, seed)
+    assert st == orc.OK
+    longest = int(np.diff(offs.astype(np.int64)).max()) if offs.size > 1 else 0
+    rtol = rtol_for(min(snippet_len, longest))
+    if want is not None:
+        bad = ~np.isclose(want, truth, rtol=rtol, atol=1e-12)
+        assert not bad.any(), ("the f64 ORACLE (not a kernel) misses the truth", np.nonzero(bad)[0][:5])
+        assert abs(wz - tz) <= 1e-12 * abs(tz) + 1e-9, ("the f64 ORACLE's log Z (not a kernel's)", wz, tz)
+    fam = estep_family(kernels)
+    if fam == "linear":
+        np.testing.assert_allclose(got, truth, rtol=1e-10, atol=1e-13, err_msg=f"linear-domain kernels {sorted(kernels)}")
+        assert abs(gz - tz) <= 1e-13 * abs(tz), (gz, tz, sorted(kernels))
+    else:
+        np.testing.assert_allclose(got, truth, rtol=rtol, atol=1e-12, err_msg=f"log-domain kernels {sorted(kernels)}")
+        assert abs(gz - tz) <= 1e-12 * abs(tz) + 1e-9, (gz, tz, sorted(kernels))
+    return fam
+
+
 def load_vocab_500k():
     """The 500 000-entry synthetic vocabulary of BASELINE.json configs[3] (prune's start): built once by
     tools/make_vocab_cache.py 500000 (synth.build_vocab over 64 MiB of the mixed corpus, minutes of numpy) and
