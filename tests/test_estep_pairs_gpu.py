@@ -121,6 +121,25 @@ def test_estep_z_not_normal_is_reported():
     assert st == orc.ERR_Z_NOT_NORMAL and es == 1
 
 
+@pytest.mark.parametrize("path", [None, "rows4", "fused"])
+def test_estep_z_not_normal_leaves_expected_untouched(monkeypatch, path):
+    """include/tgx.h: on TGX_ERR_Z_NOT_NORMAL nothing of the failed pass is added to expected[] — on the default
+    path (estep7.hip), the rows4 kernels and the generic kernel (TGX_PATH=fused) alike."""
+    if path is None:
+        monkeypatch.delenv("TGX_PATH", raising=False)
+    else:
+        monkeypatch.setenv("TGX_PATH", path)
+    nat, _ = _pair([b"a", b"b"], [0.0, -1.0])
+    flat, offs = tgx.pack([b"bb", b"aa", b"ab"])
+    corpus = tgx.NativeCorpus(flat, offs)
+    sentinel = np.float64(-12345.678)
+    expected = np.full(nat.vocab_size, sentinel, np.float64)
+    with pytest.raises(tgx.TokenGeeXError) as e:
+        nat.estep(corpus, expected=expected)
+    assert e.value.status == 6 and e.value.sample == 1
+    assert expected.tobytes() == np.full(nat.vocab_size, sentinel, np.float64).tobytes()
+
+
 def test_count_pairs_parity():
     flat, offs, toks, scores = corpus_and_vocab(2 << 20, "mixed", 6000, 16)
     nat, ora = _pair(toks, scores)

@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <unordered_set>
 #include <cstdarg>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cmath>
@@ -217,6 +218,32 @@ constexpr int kMaxTimed = 8;
 // encode5_kernel: the depth at which a trip's live walks are compacted (0: never; TGX_E5_COMPACT=off|4..8 overrides)
 constexpr int kE5CompactDepth = 5;
 
+// The model's control words in device memory: the counters and flags its kernels share with the host, one member per
+// role (this is the only place that says which kernel uses which).  Kernels take `unsigned long long*` to a member.  A
+// pass holds m->mu, so one pass uses them at a time; each pass resets the ones it reads.
+struct DeviceCtrl {
+    unsigned long long queue;        // work queue of encode4 / encode4l / encode2 / encode5_kernel and the sampling kernels
+    unsigned long long err;          // lowest failing sample (encode, sampling, n-best) or snippet (E-step); ~0: none
+    unsigned long long queue6;       // encode6_kernel's own work queue when it runs beside encode5_kernel (co-run)
+    struct Estep {                   // contiguous: an E-step pass clears these with ONE hipMemsetAsync over `estep`
+        unsigned long long queue;       // estep7_kernel, estep7_redo_kernel, the forward kernels of estep4 / estep4l / estep5
+        unsigned long long redo_count;  // estep7_kernel: stretches left to estep7_redo_kernel
+        unsigned long long queue_bwd;   // the backward kernels of estep4 / estep4l
+        unsigned long long range_flag;  // every linear-domain E-step kernel: the pass belongs to the log-domain kernels
+    } estep;
+    unsigned long long encode_redo;  // encode4l_kernel, the LONG build of encode5_kernel: samples left to encode2_kernel
+    unsigned long long longest;      // estep_pieces_build: the longest piece (piece_len_kernel)
+    unsigned long long err_piece;    // err_snip of the chained E-step kernels on pieces (z is checked per snippet afterwards)
+};
+static_assert(offsetof(DeviceCtrl::Estep, redo_count) == 8 && offsetof(DeviceCtrl::Estep, queue_bwd) == 16 &&
+                  offsetof(DeviceCtrl::Estep, range_flag) == 24 && sizeof(DeviceCtrl::Estep) == 32,
+              "the E-step words are cleared by one memset");
+// what a pass reads back into page-locked host memory
+struct HostCtrl {
+    unsigned long long err;           // DeviceCtrl::err
+    unsigned long long total_tokens;  // the last entry of the scanned token counts
+};
+
 }  // namespace
 
 struct tgx_model {
@@ -227,8 +254,8 @@ struct tgx_model {
     tgx::FlatTrie flat;
     void* d_trie = nullptr;
     uint32_t* d_tokid = nullptr;
-    unsigned long long* d_ctrl = nullptr;  // [0] work counter, [1] min failing sample
-    unsigned long long* h_ctrl = nullptr;  // pinned: [0] err sample, [1] total tokens
+    DeviceCtrl* d_ctrl = nullptr;
+    HostCtrl* h_ctrl = nullptr;  // page-locked
     hipStream_t stream = nullptr;
     hipStream_t stream2 = nullptr;          // encode6_kernel beside encode5_kernel (run_encode_kernel: co-run)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -442,6 +469,80 @@ uint32_t grid_blocks(const tgx_model* m, uint64_t n_samples) {
     return (uint32_t)std::max<uint64_t>(1, std::min(want, cap));
 }
 
+// An integer knob that holds only inside [lo, hi]: any other value is ignored.
+void knob_int(const char* name, int lo, int hi, int* x) {
+    if (const char* e = knob(name)) {
+        const int v = atoi(e);
+        if (v >= lo && v <= hi) *x = v;
+    }
+}
+// TGX_E5_HOT / TGX_E7_HOT: a smaller LDS copy than fits (tests of the COLD builds, table-size sweeps)
+uint32_t knob_cap_hot(const char* name, uint32_t n_hot) {
+    if (const char* e = knob(name)) {
+        const int v = atoi(e);
+        if (v >= 0) n_hot = std::min(n_hot, (uint32_t)v);
+    }
+    return n_hot;
+}
+// TGX_FLAGS: timing experiments (tools/ablate.py) — results are WRONG when set; honoured only with TGX_DEBUG=1
+uint32_t debug_flags() {
+    const char* f = debug_on() ? getenv("TGX_FLAGS") : nullptr;
+    return f ? (uint32_t)atoi(f) : 0u;
+}
+
+// blocks of the trace kernels: four samples per block and round, eight blocks per CU
+uint32_t trace_blocks(const tgx_model* m, uint64_t n_samples) {
+    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n_samples + 3) / 4, (uint64_t)m->num_cus * 8));
+}
+// fewer waves (of four rows) per block when the pass has fewer units than the chip has rows, so that they spread over
+// the `n_blocks` resident blocks
+int waves_for_units(int waves, uint64_t units, uint64_t n_blocks) {
+    const uint64_t rows_wanted = (units + n_blocks - 1) / n_blocks;
+    return (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)waves, (rows_wanted + 3) / 4));
+}
+// rows claim several consecutive units of the order per atomic when units are short: one global atomic round trip
+// (~1-2 us) per unit is what a corpus of 130-byte samples otherwise waits for
+uint32_t claim_chunk_for(uint64_t n_bytes, uint64_t units) {
+    const uint64_t avg = units ? n_bytes / units : 0;
+    return (uint32_t)std::min<uint64_t>(16, std::max<uint64_t>(1, 4096 / std::max<uint64_t>(1, avg)));
+}
+
+// Phase stamps of a kernel's waves (diagnosis; TGX_STAMPS=<which> with TGX_DEBUG=1): 64 bytes per wave, cleared, owned by
+// the pass.  d == nullptr: not asked for, or not to be had.
+struct Stamps {
+    unsigned long long* d = nullptr;
+    size_t n_waves = 0;
+};
+Stamps stamps_begin(tgx_model* m, Pass& pass, char which, size_t n_waves) {
+    const char* e = debug_on() ? getenv("TGX_STAMPS") : nullptr;
+    Stamps st;
+    st.n_waves = n_waves;
+    if (!e || *e != which || pass.alloc(n_waves * 64, &st.d) != hipSuccess || hipMemsetAsync(st.d, 0, n_waves * 64, m->stream) != hipSuccess)
+        st.d = nullptr;
+    return st;
+}
+// ... and after the launch: mean ticks per `unit` and phase over all waves (a wave counts its units in the word after its
+// phases).  ppl: positions per lane, named in the line unless 0.
+void stamps_report(tgx_model* m, const Stamps& st, int ppl, const char* what, const char* unit, std::initializer_list<const char*> phases) {
+    std::vector<unsigned long long> h(st.n_waves * 8);
+    if (hipStreamSynchronize(m->stream) != hipSuccess || hipMemcpy(h.data(), st.d, st.n_waves * 64, hipMemcpyDeviceToHost) != hipSuccess) return;
+    const size_t np = phases.size();  // (at most 7)
+    double sum[7] = {0, 0, 0, 0, 0, 0, 0}, count = 0;
+    for (size_t w = 0; w < st.n_waves; w++) {
+        for (size_t i = 0; i < np; i++) sum[i] += (double)h[w * 8 + i];
+        count += (double)h[w * 8 + np];
+    }
+    fprintf(stderr, "[tgx] %s (s_memtime ticks per wave-%s, %zu waves", what, unit, st.n_waves);
+    if (ppl) fprintf(stderr, " x ppl %d", ppl);
+    fprintf(stderr, ", %.0f %ss):", count, unit);
+    size_t i = 0;
+    for (const char* name : phases) {
+        fprintf(stderr, "%s %s %.0f", i ? " " : "", name, sum[i] / count);
+        i++;
+    }
+    fprintf(stderr, "\n");
+}
+
 // encode5_kernel keeps the first ranks of the score values in LDS.  build_trie8 ranks a value by the probability mass of
 // its tokens — how often they are CHOSEN — but a value is read whenever one of its tokens MATCHES: a vocabulary after an
 // M-step has a value per token, and its kept single-byte tokens have tiny scores and match at every position.  So, as
@@ -507,13 +608,9 @@ tgx_status ensure_value_ranks(tgx_model* m, const tgx_corpus* c) {
     return pass.done();
 }
 
-// Queues the encode kernels and the back-trace over the corpus: every sample's token count in c->d_counts, its ids
-// right-aligned in c->d_tmp, the lowest failing sample in d_ctrl[1].  Diagnostic scratch belongs to `pass`.
-tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64_t seed, Pass& pass) {
-    tgx_status st = ensure_scratch(c);
-    if (st != TGX_OK) return st;
-    HIP_TRY(hipMemsetAsync(m->d_ctrl, 0x00, 8, m->stream));
-    HIP_TRY(hipMemsetAsync(m->d_ctrl + 1, 0xFF, 8, m->stream));
+// What every encode and sampling kernel is told about the model, the corpus and its scratch (ensure_scratch); dropout,
+// flags and the kernel's own fields are the caller's.
+tgx::EncodeParams base_encode_params(const tgx_model* m, const tgx_corpus* c, uint64_t seed) {
     tgx::EncodeParams p{};
     p.text = c->d_text;
     p.offs = c->d_offs;
@@ -532,19 +629,46 @@ tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64
     p.tokhash = m->d_tokhash;
     p.tokhash_mask = m->tokhash.mask;
     p.tokhash_seed = m->tokhash.seed;
-    p.err_sample = m->d_ctrl + 1;
-    p.queue = m->d_ctrl;
-    p.dropout = dropout;
+    p.err_sample = &m->d_ctrl->err;
+    p.queue = &m->d_ctrl->queue;
     p.seed = seed;
     // samples of less than 2 KiB on average: the trace keeps its waiting tokens across samples (trace_body.h; 140-byte samples
     // 5.5 -> 4.6 ms per GiB, 9 KiB samples 2.93 -> 3.04)
     p.trace_carry = (c->n_samples && c->n_bytes / c->n_samples < 2048) ? 1u : 0u;
-    if (const char* e = knob("TGX_TRACE_CARRY")) p.trace_carry = atoi(e) ? 1u : 0u;
-    {
-        // timing experiments (tools/ablate.py) — results are WRONG when set; honoured only with TGX_DEBUG=1
-        const char* f = debug_on() ? getenv("TGX_FLAGS") : nullptr;
-        p.flags = f ? (uint32_t)atoi(f) : 0u;
+    return p;
+}
+
+// The samples whose wave ran out of list entries for long matches (encode4l_kernel, the LONG build of encode5_kernel:
+// p.redo_count, the list in c->d_counts) go to encode2_kernel.  Waits for the kernel that filled the list.
+tgx_status redo_long_matches(tgx_model* m, tgx_corpus* c, const tgx::EncodeParams& p) {
+    unsigned long long n_redo = 0;
+    HIP_TRY(hipMemcpyAsync(&n_redo, &m->d_ctrl->encode_redo, 8, hipMemcpyDeviceToHost, m->stream));
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    if (n_redo > c->n_samples) return fail(TGX_ERR_DEVICE, "redo list longer than the batch");
+    m->last_redo_samples = n_redo;
+    if (n_redo) {
+        tgx::EncodeParams q = p;
+        q.order = c->d_counts;
+        q.n_samples = n_redo;
+        HIP_TRY(hipMemsetAsync(&m->d_ctrl->queue, 0x00, 8, m->stream));  // the work queue
+        time_begin(m, "encode2_kernel");
+        HIP_TRY(tgx::launch_encode2(q, (uint32_t)m->num_cus, true, m->stream));
+        time_end(m);
     }
+    return TGX_OK;
+}
+
+// Queues the encode kernels and the back-trace over the corpus: every sample's token count in c->d_counts, its ids
+// right-aligned in c->d_tmp, the lowest failing sample in d_ctrl->err.  Diagnostic scratch belongs to `pass`.
+tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64_t seed, Pass& pass) {
+    tgx_status st = ensure_scratch(c);
+    if (st != TGX_OK) return st;
+    HIP_TRY(hipMemsetAsync(&m->d_ctrl->queue, 0x00, 8, m->stream));
+    HIP_TRY(hipMemsetAsync(&m->d_ctrl->err, 0xFF, 8, m->stream));
+    tgx::EncodeParams p = base_encode_params(m, c, seed);
+    p.dropout = dropout;
+    if (const char* e = knob("TGX_TRACE_CARRY")) p.trace_carry = atoi(e) ? 1u : 0u;
+    p.flags = debug_flags();
     // TGX_PATH=fused forces the one-sample-per-wave kernel (A/B timing, tests of both paths)
     const char* force = knob("TGX_PATH");
     const bool use4 = m->lm <= 16 && m->scores_finite && m->d_tokhash && !(force && strcmp(force, "fused") == 0);
@@ -611,10 +735,7 @@ tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64
             }
             n_hot6 = std::min(m->n_values, tgx::encode6_max_hot(160u * 1024u / (uint32_t)e6_bpc, pool6));
         }
-        if (const char* e = knob("TGX_E5_HOT")) {
-            const int v = atoi(e);
-            if (v >= 0) n_hot6 = std::min(n_hot6, (uint32_t)v);
-        }
+        n_hot6 = knob_cap_hot("TGX_E5_HOT", n_hot6);
         const bool cold6 = n_hot6 < m->n_values;
         uint64_t n_long = 0;
         uint32_t corun_cus = 0;  // CUs of encode6_kernel when both kernels run at once (0: one after the other)
@@ -745,10 +866,7 @@ tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64
                 bpc = ppl >= 3 ? 1 : 2;
             }
         }
-        if (const char* e = knob("TGX_BPC")) {
-            const int v = atoi(e);
-            if (v >= 1 && v <= 8) bpc = v;
-        }
+        knob_int("TGX_BPC", 1, 8, &bpc);
         const uint32_t budget = 160u * 1024u / (uint32_t)bpc;
         bool cold = false;
         int per_simd = 0;
@@ -761,20 +879,11 @@ tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64
             waves = std::min(16, (per_simd / bpc) * 4);
         }
         if (balance_waves > 0 && ppl == 4 && bpc == 1) waves = std::min(waves, balance_waves);
-        {
-            const uint64_t rows_wanted = (rest_n + (uint64_t)cus5 * bpc - 1) / ((uint64_t)cus5 * bpc);
-            waves = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)waves, (rows_wanted + 3) / 4));
-        }
-        if (const char* e = knob("TGX_WAVES")) {
-            const int v = atoi(e);
-            if (v >= 1 && v <= 16) waves = v;
-        }
+        waves = waves_for_units(waves, rest_n, (uint64_t)cus5 * bpc);
+        knob_int("TGX_WAVES", 1, 16, &waves);
         while (waves > 1 && tgx::encode5_max_hot(long_tokens, waves, ppl, budget) < 16u) waves--;
         uint32_t n_hot = std::min(m->n_values, tgx::encode5_max_hot(long_tokens, waves, ppl, budget));
-        if (const char* e = knob("TGX_E5_HOT")) {  // tests of the COLD builds (a small LDS copy), table-size sweeps
-            const int v = atoi(e);
-            if (v >= 0) n_hot = std::min(n_hot, (uint32_t)v);
-        }
+        n_hot = knob_cap_hot("TGX_E5_HOT", n_hot);
         cold = n_hot < m->n_values;
         m->last_n_hot = n_hot;
         // whole blocks only: a block's waves are dealt round-robin to the SIMDs, ceil(waves / 4) on the fullest
@@ -789,12 +898,8 @@ tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64
         q.root_base = m->root_base8;
         q.n_values = m->n_values;
         q.n_hot = n_hot;
-        {   // rows claim several consecutive samples of the order per atomic when samples are short: one global
-            // atomic round trip (~1-2 us) per sample is what a corpus of 130-byte samples otherwise waits for
-            const uint64_t avg = c->n_samples ? c->n_bytes / c->n_samples : 0;
-            q.claim_chunk = (uint32_t)std::min<uint64_t>(16, std::max<uint64_t>(1, 4096 / std::max<uint64_t>(1, avg)));
-            if (const char* e = knob("TGX_CLAIM_CHUNK")) q.claim_chunk = (uint32_t)std::min(64, std::max(1, atoi(e)));
-        }
+        q.claim_chunk = claim_chunk_for(c->n_bytes, c->n_samples);
+        if (const char* e = knob("TGX_CLAIM_CHUNK")) q.claim_chunk = (uint32_t)std::min(64, std::max(1, atoi(e)));
         m->last_long_samples = n_long;
         m->last_corun_cus = n_long ? corun_cus : 0u;
         tgx::EncodeParams p6 = p;
@@ -810,7 +915,7 @@ tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64
                 time_begin(m, "encode6_kernel");
                 HIP_TRY(tgx::launch_encode6(p6, q6, cold6, blocks6, m->stream));
                 time_end(m);
-                HIP_TRY(hipMemsetAsync(m->d_ctrl, 0x00, 8, m->stream));  // the work queue, for encode5_kernel
+                HIP_TRY(hipMemsetAsync(&m->d_ctrl->queue, 0x00, 8, m->stream));  // the work queue, for encode5_kernel
             } else {
                 if (!m->stream2) {
                     HIP_TRY(hipStreamCreateWithFlags(&m->stream2, hipStreamNonBlocking));
@@ -820,29 +925,22 @@ tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64
                 }
                 *reinterpret_cast<volatile unsigned int*>(m->h_started) = 0u;
                 q.started = m->h_started;
-                p6.queue = m->d_ctrl + 2;  // a work queue of its own
-                HIP_TRY(hipMemsetAsync(m->d_ctrl + 2, 0x00, 8, m->stream));
+                p6.queue = &m->d_ctrl->queue6;  // a work queue of its own
+                HIP_TRY(hipMemsetAsync(&m->d_ctrl->queue6, 0x00, 8, m->stream));
                 HIP_TRY(hipEventRecord(m->ev_fork, m->stream));
                 HIP_TRY(hipStreamWaitEvent(m->stream2, m->ev_fork, 0));
             }
             p.order = c->d_order + n_long;
             p.n_samples = c->n_samples - n_long;
         }
-        unsigned long long* d_stamps5 = nullptr;
-        const size_t n_stamp_waves5 = (size_t)blocks5 * (size_t)waves;
-        if (const char* e = debug_on() ? getenv("TGX_STAMPS") : nullptr) {
-            if (*e == '1') {
-                if (pass.alloc(n_stamp_waves5 * 64, &d_stamps5) != hipSuccess) return fail(TGX_ERR_DEVICE, "out of device memory (stamps)");
-                if (hipMemsetAsync(d_stamps5, 0, n_stamp_waves5 * 64, m->stream) != hipSuccess) return fail(TGX_ERR_DEVICE, "stamps reset failed");
-                p.stamps = d_stamps5;
-            }
-        }
+        const Stamps stamps5 = stamps_begin(m, pass, '1', (size_t)blocks5 * (size_t)waves);
+        p.stamps = stamps5.d;
         time_begin(m, "encode5_kernel");
         {
             if (long_tokens) {  // samples whose wave ran out of list entries for long matches go to encode2_kernel
-                p.redo_count = m->d_ctrl + 6;
+                p.redo_count = &m->d_ctrl->encode_redo;
                 p.redo_list = c->d_counts;  // free until the trace writes the token counts
-                HIP_TRY(hipMemsetAsync(m->d_ctrl + 6, 0x00, 8, m->stream));
+                HIP_TRY(hipMemsetAsync(&m->d_ctrl->encode_redo, 0x00, 8, m->stream));
             }
             // (co-run: more than half of the CU's LDS, so that no block of the long-sample kernel shares the CU)
             const hipError_t le = tgx::launch_encode5(p, q, cold, ppl, long_tokens, compact, waves, blocks5, corun_cus && n_long ? 84u * 1024u : 0u, m->stream);
@@ -878,40 +976,15 @@ tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64
             if (joined_slot) m->n_timed++;
             HIP_TRY(hipStreamWaitEvent(m->stream, m->ev_join, 0));  // the trace needs both kernels' back-pointers
         }
-        if (d_stamps5) {  // diagnostic: mean ticks per iteration and phase over all waves
-            std::vector<unsigned long long> h(n_stamp_waves5 * 8);
-            const bool ok = hipStreamSynchronize(m->stream) == hipSuccess &&
-                            hipMemcpy(h.data(), d_stamps5, n_stamp_waves5 * 64, hipMemcpyDeviceToHost) == hipSuccess;
-            p.stamps = nullptr;
-            if (!ok) return fail(TGX_ERR_DEVICE, "stamps copy failed");
-            double sum[5] = {0, 0, 0, 0, 0}, iters = 0;
-            for (size_t w = 0; w < n_stamp_waves5; w++) {
-                for (int i = 0; i < 5; i++) sum[i] += (double)h[w * 8 + i];
-                iters += (double)h[w * 8 + 5];
-            }
-            fprintf(stderr, "[tgx] encode5 stamps (s_memtime ticks per wave-iteration, %zu waves x ppl %d, %.0f iterations): switch %.0f  text+reset %.0f  walk %.0f  relax %.0f  store %.0f\n",
-                    n_stamp_waves5, ppl, iters, sum[0] / iters, sum[1] / iters, sum[2] / iters, sum[3] / iters, sum[4] / iters);
-        }
+        if (stamps5.d) stamps_report(m, stamps5, ppl, "encode5 stamps", "iteration", {"switch", "text+reset", "walk", "relax", "store"});
+        p.stamps = nullptr;
         if (long_tokens) {
-            unsigned long long n_redo = 0;
-            HIP_TRY(hipMemcpyAsync(&n_redo, m->d_ctrl + 6, 8, hipMemcpyDeviceToHost, m->stream));
-            HIP_TRY(hipStreamSynchronize(m->stream));
-            if (n_redo > c->n_samples) return fail(TGX_ERR_DEVICE, "redo list longer than the batch");
-            m->last_redo_samples = n_redo;
-            if (n_redo) {
-                tgx::EncodeParams q2 = p;
-                q2.order = c->d_counts;
-                q2.n_samples = n_redo;
-                HIP_TRY(hipMemsetAsync(m->d_ctrl, 0x00, 8, m->stream));  // the work queue
-                time_begin(m, "encode2_kernel");
-                HIP_TRY(tgx::launch_encode2(q2, (uint32_t)m->num_cus, true, m->stream));
-                time_end(m);
-            }
+            const tgx_status rst = redo_long_matches(m, c, p);
+            if (rst != TGX_OK) return rst;
         }
         p.order = c->d_order;
         p.n_samples = c->n_samples;
-        const uint32_t blocks_t =
-            (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((c->n_samples + 3) / 4, (uint64_t)m->num_cus * 8));
+        const uint32_t blocks_t = trace_blocks(m, c->n_samples);
         time_begin(m, long_tokens ? "trace32_kernel" : "trace_kernel");
         if (long_tokens) HIP_TRY(tgx::launch_trace32(p, blocks_t, true, m->stream));
         else HIP_TRY(tgx::launch_trace(p, blocks_t, m->stream));
@@ -951,14 +1024,8 @@ tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64
         }
         if (ppl == 2) { waves = 5; bpc = 2; }
         if (ppl == 4) { waves = 5; bpc = 1; }
-        if (const char* e = knob("TGX_WAVES")) {
-            const int v = atoi(e);
-            if (v >= 1 && v <= 16) waves = v;
-        }
-        if (const char* e = knob("TGX_BPC")) {
-            const int v = atoi(e);
-            if (v >= 1 && v <= 8) bpc = v;
-        }
+        knob_int("TGX_WAVES", 1, 16, &waves);
+        knob_int("TGX_BPC", 1, 8, &bpc);
         bool root = ppl == 1;  // first trie level in LDS (4 KiB per block)
         if (const char* e = knob("TGX_ROOT")) root = root && atoi(e) != 0;
         while (waves > 1 && tgx::encode4_lds_bytes(waves, ppl, root) > (160u * 1024u) / (uint32_t)bpc) waves--;
@@ -981,77 +1048,41 @@ tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64
         const uint64_t rows_per_block = 4 * (uint64_t)waves;
         const uint32_t blocks4 = (uint32_t)std::max<uint64_t>(
             1, std::min<uint64_t>((p.n_samples + rows_per_block - 1) / rows_per_block, (uint64_t)m->num_cus * bpc));
-        unsigned long long* d_stamps = nullptr;
-        const size_t n_stamp_waves = (size_t)blocks4 * (size_t)waves;
-        // (stamp buffers of the diagnostic runs: a failing call between allocation and release ends the process's
-        // usefulness for diagnosis anyway; they are only ever allocated with TGX_DEBUG=1)
-        if (const char* e = debug_on() ? getenv("TGX_STAMPS") : nullptr) {
-            if (*e == '1' && dropout <= 0.0 && ppl == 1) {
-                HIP_TRY(hipMalloc((void**)&d_stamps, n_stamp_waves * 64));
-                HIP_TRY(hipMemsetAsync(d_stamps, 0, n_stamp_waves * 64, m->stream));
-                p.stamps = d_stamps;
-            }
-        }
+        Stamps stamps4;  // (the kernel has them without dropout, one position per lane)
+        if (dropout <= 0.0 && ppl == 1) stamps4 = stamps_begin(m, pass, '1', (size_t)blocks4 * (size_t)waves);
+        p.stamps = stamps4.d;
         time_begin(m, "encode4_kernel");
         HIP_TRY(tgx::launch_encode4(p, ppl, waves, blocks4, root, m->stream));
         time_end(m);
-        if (d_stamps) {  // diagnostic: mean cycles per iteration and phase over all waves
-            std::vector<unsigned long long> h(n_stamp_waves * 8);
-            HIP_TRY(hipStreamSynchronize(m->stream));
-            HIP_TRY(hipMemcpy(h.data(), d_stamps, n_stamp_waves * 64, hipMemcpyDeviceToHost));
-            double sum[5] = {0, 0, 0, 0, 0}, iters = 0;
-            for (size_t w = 0; w < n_stamp_waves; w++) {
-                for (int i = 0; i < 5; i++) sum[i] += (double)h[w * 8 + i];
-                iters += (double)h[w * 8 + 5];
-            }
-            fprintf(stderr, "[tgx] stamps (s_memtime ticks per wave-iteration, %zu waves, %.0f iterations): switch %.0f  text %.0f  walk %.0f  relax %.0f  store %.0f\n",
-                    n_stamp_waves, iters, sum[0] / iters, sum[1] / iters, sum[2] / iters, sum[3] / iters, sum[4] / iters);
-            (void)hipFree(d_stamps);
-            p.stamps = nullptr;
-        }
+        if (stamps4.d) stamps_report(m, stamps4, 0, "stamps", "iteration", {"switch", "text", "walk", "relax", "store"});
+        p.stamps = nullptr;
         p.order = c->d_order;
         p.n_samples = c->n_samples;
-        const uint32_t blocks_t =
-            (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((c->n_samples + 3) / 4, (uint64_t)m->num_cus * 8));
         time_begin(m, "trace_kernel");
-        HIP_TRY(tgx::launch_trace(p, blocks_t, m->stream));
+        HIP_TRY(tgx::launch_trace(p, trace_blocks(m, c->n_samples), m->stream));
         time_end(m);
     } else if (use2) {
         // Tokens of 17..32 bytes: the 16-lane rows with an overflow list for the long matches (encode4l.hip);
         // samples whose wave ran out of overflow entries are redone two per wave on 32-lane rows (encode2.hip),
         // as is the whole batch with TGX_PATH=rows2.
-        const uint32_t blocks_t =
-            (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((c->n_samples + 3) / 4, (uint64_t)m->num_cus * 8));
         const bool rows2 = force && strcmp(force, "rows2") == 0;
         m->last_redo_samples = 0;
         if (!rows2) {
-            p.redo_count = m->d_ctrl + 6;
+            p.redo_count = &m->d_ctrl->encode_redo;
             p.redo_list = c->d_counts;  // free until the trace writes the token counts
-            HIP_TRY(hipMemsetAsync(m->d_ctrl + 6, 0x00, 8, m->stream));
+            HIP_TRY(hipMemsetAsync(&m->d_ctrl->encode_redo, 0x00, 8, m->stream));
             time_begin(m, "encode4l_kernel");
             HIP_TRY(tgx::launch_encode4l(p, (uint32_t)m->num_cus, m->stream));
             time_end(m);
-            unsigned long long n_redo = 0;
-            HIP_TRY(hipMemcpyAsync(&n_redo, m->d_ctrl + 6, 8, hipMemcpyDeviceToHost, m->stream));
-            HIP_TRY(hipStreamSynchronize(m->stream));
-            if (n_redo > c->n_samples) return fail(TGX_ERR_DEVICE, "redo list longer than the batch");
-            m->last_redo_samples = n_redo;
-            if (n_redo) {
-                tgx::EncodeParams q = p;
-                q.order = c->d_counts;
-                q.n_samples = n_redo;
-                HIP_TRY(hipMemsetAsync(m->d_ctrl, 0x00, 8, m->stream));  // the work queue
-                time_begin(m, "encode2_kernel");
-                HIP_TRY(tgx::launch_encode2(q, (uint32_t)m->num_cus, true, m->stream));
-                time_end(m);
-            }
+            const tgx_status rst = redo_long_matches(m, c, p);
+            if (rst != TGX_OK) return rst;
         } else {
             time_begin(m, "encode2_kernel");
             HIP_TRY(tgx::launch_encode2(p, (uint32_t)m->num_cus, false, m->stream));
             time_end(m);
         }
         time_begin(m, "trace32_kernel");
-        HIP_TRY(tgx::launch_trace32(p, blocks_t, !rows2, m->stream));
+        HIP_TRY(tgx::launch_trace32(p, trace_blocks(m, c->n_samples), !rows2, m->stream));
         time_end(m);
     } else {
         time_begin(m, "encode_kernel");
@@ -1062,7 +1093,7 @@ tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64
 }
 
 tgx_status check_no_path(tgx_model* m, const tgx_corpus* c) {
-    unsigned long long bad = m->h_ctrl[0];
+    unsigned long long bad = m->h_ctrl->err;
     if (bad == ~0ULL) return TGX_OK;
     if (bad & (1ULL << 62))
         return fail(TGX_ERR_DEVICE, "internal error: corrupt back-pointer (sample or text byte %llu)",
@@ -1090,13 +1121,13 @@ tgx_status compact_ids(tgx_model* m, tgx_corpus* c, tgx_result* r, const char* w
     if (tgx::launch_scan(c->d_counts, r->d_offs, S, c->d_scan_tmp, c->scan_tmp_bytes, m->stream) != hipSuccess)
         return fail(TGX_ERR_DEVICE, "scan launch failed");
     time_end(m);
-    if (hipMemcpyAsync(&m->h_ctrl[0], m->d_ctrl + 1, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
-        hipMemcpyAsync(&m->h_ctrl[1], r->d_offs + S, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
+    if (hipMemcpyAsync(&m->h_ctrl->err, &m->d_ctrl->err, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
+        hipMemcpyAsync(&m->h_ctrl->total_tokens, r->d_offs + S, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
         hipStreamSynchronize(m->stream) != hipSuccess)
         return fail(TGX_ERR_DEVICE, "%s pass failed: %s", what, hipGetErrorString(hipGetLastError()));
     const tgx_status st = check_no_path(m, c);
     if (st != TGX_OK) return st;
-    r->n_tokens = m->h_ctrl[1];
+    r->n_tokens = m->h_ctrl->total_tokens;
     if (r->d_ids.alloc(m->device, (size_t)r->n_tokens * 4 + 256) != hipSuccess)
         return fail(TGX_ERR_DEVICE, "out of device memory (result ids)");
     tgx::CompactParams cp{};
@@ -1308,14 +1339,14 @@ static tgx_status finish_model_create(tgx_model* m, const uint8_t* bytes, const 
     size_t tbytes = m->flat.table.size() * sizeof(tgx::TrieRec);
     HIP_TRY(hipMalloc(&m->d_trie, tbytes));
     HIP_TRY(hipMalloc((void**)&m->d_tokid, m->flat.tokid.size() * 4));
-    HIP_TRY(hipMalloc((void**)&m->d_ctrl, 64));
+    HIP_TRY(hipMalloc((void**)&m->d_ctrl, sizeof(DeviceCtrl)));
     // the tables only encode needs (bytes -> id table of the trace, 8-byte records and score table of
     // encode5_kernel): now, unless the model is created for E-step passes — then at its first encode
     if (!(flags & TGX_MODEL_FOR_ESTEP)) {
         const tgx_status est = ensure_encode_tables(m);
         if (est != TGX_OK) return est;
     }
-    HIP_TRY(hipHostMalloc((void**)&m->h_ctrl, 64, hipHostMallocDefault));
+    HIP_TRY(hipHostMalloc((void**)&m->h_ctrl, sizeof(HostCtrl), hipHostMallocDefault));
     HIP_TRY(hipMemcpyAsync(m->d_trie, m->flat.table.data(), tbytes, hipMemcpyHostToDevice, m->stream));
     HIP_TRY(hipMemcpyAsync(m->d_tokid, m->flat.tokid.data(), m->flat.tokid.size() * 4, hipMemcpyHostToDevice, m->stream));
     for (int i = 0; i < kMaxTimed; i++) {
@@ -2426,7 +2457,7 @@ static tgx_status estep_pieces_build(tgx_model* m, tgx_corpus* c, const void* tr
     q.seed = seed;
     q.bound = pc.d_bound;
     q.flag = pc.d_flag;
-    unsigned long long* const d_longest = m->d_ctrl + 6;
+    unsigned long long* const d_longest = &m->d_ctrl->longest;
     time_begin(m, "cut_windows_kernel");
     if (tgx::launch_cut_windows(q, m->stream) != hipSuccess) return bad("cut kernel launch failed");
     time_end(m);
@@ -2536,6 +2567,58 @@ static tgx_status ensure_estep_trie8t(tgx_model* m, const tgx_corpus* c) {
     return TGX_OK;
 }
 
+// Whether this pass cuts its snippets into pieces, and then their list (pc->n != 0: cut; m->last_estep_pieces says the
+// same).  A pass cuts when its longest snippet spans more than four windows and `worth` says that its serial chain is a
+// sizeable part of the pass; TGX_ESTEP_PIECES=0 / 1 forces, TGX_ESTEP_WINDOW sets the window.
+static tgx_status estep_pieces_if_worth(tgx_model* m, tgx_corpus* c, uint32_t window, const void* trie16, bool (*worth)(double longest0, double n_bytes),
+                                        double dropout, uint64_t seed, Pass& pass, EstepPieces* pc) {
+    const tgx_corpus::EstepWork& es = c->es;
+    if (const char* e = knob("TGX_ESTEP_WINDOW")) window = (uint32_t)std::min(1 << 20, std::max(256, atoi(e)));
+    const double longest0 = (double)(es.soffs[es.order[0] + 1] - es.soffs[es.order[0]]);
+    bool pieces = longest0 > 4.0 * window && worth(longest0, (double)c->n_bytes);
+    if (const char* e = knob("TGX_ESTEP_PIECES")) pieces = atoi(e) != 0 && longest0 > (double)window;
+    if (pieces) {
+        tgx_status st = ensure_estep_windows(m, c, window);
+        if (st != TGX_OK) return st;
+        st = estep_pieces_build(m, c, trie16, dropout, seed, pass, pc);
+        if (st != TGX_OK) return st;
+    }
+    m->last_estep_pieces = pc->n;
+    return TGX_OK;
+}
+
+// The end of an E-step pass, the same on every path: the lowest failing snippet (into m->h_ctrl->err), the h->size() counts
+// at d_counts and log Z come back with one synchronisation — with them the linear-domain kernels' range flag where
+// `range_flag` is given.  The caller looks at the range flag, then at estep_z_failure, and only then adds to `expected`.
+static tgx_status estep_read_back(tgx_model* m, const tgx_corpus* c, const double* d_counts, std::vector<double>* h, const double* d_z, double* hz,
+                                  unsigned long long* range_flag) {
+    if (hipMemcpyAsync(&m->h_ctrl->err, &m->d_ctrl->err, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
+        (range_flag && hipMemcpyAsync(range_flag, &m->d_ctrl->estep.range_flag, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess) ||
+        hipMemcpyAsync(h->data(), d_counts, h->size() * 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
+        hipMemcpyAsync(hz, d_z, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess || hipStreamSynchronize(m->stream) != hipSuccess)
+        return fail(TGX_ERR_DEVICE, "E-step pass failed: %s", hipGetErrorString(hipGetLastError()));
+    m->last_alg_bytes = c->n_bytes + 8 * (c->n_samples + 1) + 8ull * m->vocab_size;  // N + 8 (S + 1) + 8 V
+    return TGX_OK;
+}
+// TGX_ERR_Z_NOT_NORMAL if the pass read back found a snippet (snip_sample: its sample; nullptr: the units are samples)
+// whose normalisation constant is not a normal number: nothing of such a pass may reach the caller's `expected` or log Z.
+static tgx_status estep_z_failure(const tgx_model* m, const tgx_corpus* c, const uint32_t* snip_sample) {
+    const unsigned long long bad = m->h_ctrl->err;
+    if (bad == ~0ULL) return TGX_OK;
+    const uint64_t smp = snip_sample ? snip_sample[bad] : bad;
+    g_err_sample = smp;
+    g_err_pos = g_err_len = c->h_offs[smp + 1] - c->h_offs[smp];
+    return fail(TGX_ERR_Z_NOT_NORMAL, "normalization constant is not a normal number (sample %llu, len=%llu)",
+                (unsigned long long)smp, (unsigned long long)g_err_len);  // the reference panics here: src/prune.rs:90-96
+}
+// counts by slot of the reversed trie -> expected[id]
+static void add_slot_counts(const tgx_model* m, const std::vector<double>& h, double* expected) {
+    for (size_t t = 0; t < h.size(); t++) {
+        const uint32_t id = m->flat_rev.tokid[t];
+        if (id != tgx::kNoToken) expected[id] += h[t];
+    }
+}
+
 // E-step on estep7_kernel (estep7.hip): one walk per position, every trip of a row a lattice of its own.  Caller holds
 // both locks.  `fallback`: the chained kernels must do the pass (no records for this vocabulary, a position nothing
 // reaches, a value out of range); `expected` is untouched then.
@@ -2570,21 +2653,12 @@ static tgx_status estep_fused(tgx_model* m, tgx_corpus* c, uint64_t snippet_len,
     // 21.2 -> 8.6 ms; 1 GiB: 33.6 ms uncut, 34.3 cut (the cut search and the piece list cost 0.5 - 0.8 ms).  Windows of
     // 4 KiB: 8.64 ms at 256 MiB against 8.91 with 2 KiB and 9.23 with 1 KiB (profiles/r04)
     EstepPieces pc;
-    bool pieces = false;
     {
-        uint32_t window = 4096;
-        if (const char* e = knob("TGX_ESTEP_WINDOW")) window = (uint32_t)std::min(1 << 20, std::max(256, atoi(e)));
-        const double longest0 = (double)(es.soffs[es.order[0] + 1] - es.soffs[es.order[0]]);
-        pieces = longest0 > 4.0 * window && longest0 * 0.12e-6 > 0.4 * ((double)N / 33e9);
-        if (const char* e = knob("TGX_ESTEP_PIECES")) pieces = atoi(e) != 0 && longest0 > (double)window;
-        if (pieces) {
-            tgx_status pst = ensure_estep_windows(m, c, window);
-            if (pst != TGX_OK) return pst;
-            pst = estep_pieces_build(m, c, m->d_trie, dropout, seed, pass, &pc);
-            if (pst != TGX_OK) return pst;
-            m->last_estep_pieces = pc.n;
-        }
+        const auto worth = [](double longest0, double n_bytes) { return longest0 * 0.12e-6 > 0.4 * (n_bytes / 33e9); };
+        const tgx_status pst = estep_pieces_if_worth(m, c, 4096, m->d_trie, worth, dropout, seed, pass, &pc);
+        if (pst != TGX_OK) return pst;
     }
+    const bool pieces = pc.n != 0;
     const uint64_t units = pieces ? pc.n : K;
     // 16-bit match entries hold 65 535 ranks.  A vocabulary of a few more tokens (the usual "64 K": 65 536) keeps them — 34
     // against 24 GB/s with 32-bit entries — and leaves the trips in which one of its least matched tokens (the ranks beyond
@@ -2605,26 +2679,14 @@ static tgx_status estep_fused(tgx_model* m, tgx_corpus* c, uint64_t snippet_len,
     // 34.2 / 38.5 / 44.3 and forty times the stretches without a cut in a trip — profiles/r04)
     int ppl = wide ? 2 : 4, waves = 12;
     const bool ppl_forced = ovf;  // (the overflow build exists for four positions per lane)
-    if (const char* e = knob("TGX_EPPL")) {
-        const int v = atoi(e);
-        if (v >= 1 && v <= 4) ppl = v;
-    }
+    knob_int("TGX_EPPL", 1, 4, &ppl);
     if (ppl_forced) ppl = 4;
-    if (const char* e = knob("TGX_E7_WAVES")) {
-        const int v = atoi(e);
-        if (v >= 1 && v <= 12) waves = v;
-    }
-    {   // fewer waves when the pass has fewer units than the chip has rows, so that they spread over the CUs
-        const uint64_t rows_wanted = (units + (uint64_t)m->num_cus - 1) / (uint64_t)m->num_cus;
-        waves = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)waves, (rows_wanted + 3) / 4));
-    }
+    knob_int("TGX_E7_WAVES", 1, 12, &waves);
+    waves = waves_for_units(waves, units, (uint64_t)m->num_cus);
     // (32-bit entries take twice the LDS: the geometry must leave room for a table worth having)
     while (waves > 1 && tgx::estep7_max_hot(wide, waves, ppl, 160u * 1024u) < 1024u) waves--;
     uint32_t n_hot = std::min(m->n_tok7, tgx::estep7_max_hot(wide, waves, ppl, 160u * 1024u));
-    if (const char* e = knob("TGX_E7_HOT")) {
-        const int v = atoi(e);
-        if (v >= 0) n_hot = std::min(n_hot, (uint32_t)v);
-    }
+    n_hot = knob_cap_hot("TGX_E7_HOT", n_hot);
     if (ovf && n_hot >= m->n_tok7) n_hot = m->n_tok7 - 1u;  // (the overflow build is a COLD build)
     const size_t ebytes = ((size_t)m->n_tok7 + 1) * 8 + 256, zbytes = (size_t)K * 8 + 256;
     // (the redo list: a piece can leave several stretches, each longer than a trip's reach)
@@ -2640,8 +2702,8 @@ static tgx_status estep_fused(tgx_model* m, tgx_corpus* c, uint64_t snippet_len,
         pass.alloc(r4, &d_rsample) != hipSuccess || pass.alloc(r4, &d_rsnip) != hipSuccess)
         return fail(TGX_ERR_DEVICE, "out of device memory (E-step scratch)");
     if (hipMemsetAsync(d_exp, 0, ebytes, m->stream) != hipSuccess || hipMemsetAsync(d_z, 0, 256, m->stream) != hipSuccess ||
-        hipMemsetAsync(d_zsnip, 0, zbytes, m->stream) != hipSuccess || hipMemsetAsync(m->d_ctrl + 3, 0x00, 24, m->stream) != hipSuccess ||
-        hipMemsetAsync(m->d_ctrl + 1, 0xFF, 8, m->stream) != hipSuccess)
+        hipMemsetAsync(d_zsnip, 0, zbytes, m->stream) != hipSuccess || hipMemsetAsync(&m->d_ctrl->estep, 0x00, sizeof(DeviceCtrl::Estep), m->stream) != hipSuccess ||
+        hipMemsetAsync(&m->d_ctrl->err, 0xFF, 8, m->stream) != hipSuccess)
         return fail(TGX_ERR_DEVICE, "E-step setup failed");
     tgx::Estep7Params p{};
     tgx::Estep7Work& wk = p.host_work;
@@ -2663,9 +2725,9 @@ static tgx_status estep_fused(tgx_model* m, tgx_corpus* c, uint64_t snippet_len,
     p.expected = d_exp;
     wk.zsnip = d_zsnip;
     wk.logz_sum = d_z;
-    wk.queue = m->d_ctrl + 3;
-    wk.redo_count = m->d_ctrl + 4;
-    wk.range_flag = m->d_ctrl + 5;
+    wk.queue = &m->d_ctrl->estep.queue;
+    wk.redo_count = &m->d_ctrl->estep.redo_count;
+    wk.range_flag = &m->d_ctrl->estep.range_flag;
     wk.redo_offs = d_roffs;
     wk.redo_sample = d_rsample;
     wk.redo_base = d_rbase;
@@ -2673,44 +2735,20 @@ static tgx_status estep_fused(tgx_model* m, tgx_corpus* c, uint64_t snippet_len,
     wk.redo_cap = redo_cap;
     p.dropout = dropout;
     p.seed = seed;
-    {
-        const uint64_t avg = units ? N / units : 0;
-        p.claim_chunk = (uint32_t)std::min<uint64_t>(16, std::max<uint64_t>(1, 4096 / std::max<uint64_t>(1, avg)));
-    }
+    p.claim_chunk = claim_chunk_for(N, units);
     const uint64_t rows_per_block = 4ull * (uint64_t)waves;
     const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((units + rows_per_block - 1) / rows_per_block, (uint64_t)m->num_cus));
-    unsigned long long* d_stamps = nullptr;
-    const size_t n_stamp_waves = (size_t)blocks * (size_t)waves;
-    if (const char* e = debug_on() ? getenv("TGX_STAMPS") : nullptr) {
-        if (*e == '7' && pass.alloc(n_stamp_waves * 64, &d_stamps) == hipSuccess) {
-            (void)hipMemsetAsync(d_stamps, 0, n_stamp_waves * 64, m->stream);
-            p.stamps = d_stamps;
-        }
-    }
-    {
-        const char* f = debug_on() ? getenv("TGX_FLAGS") : nullptr;
-        p.flags = f ? (uint32_t)atoi(f) : 0u;
-    }
+    const Stamps stamps = stamps_begin(m, pass, '7', (size_t)blocks * (size_t)waves);
+    p.stamps = stamps.d;
+    p.flags = debug_flags();
     hp.mark("pieces + buffers");
     time_begin(m, "estep7_kernel");
     if (tgx::launch_estep7(p, wide, ppl, waves, blocks, m->stream) != hipSuccess) return fail(TGX_ERR_DEVICE, "estep7 launch failed");
     time_end(m);
-    if (d_stamps) {  // diagnostic: mean ticks per trip and phase over all waves
-        std::vector<unsigned long long> hs(n_stamp_waves * 8);
-        const bool ok = hipStreamSynchronize(m->stream) == hipSuccess && hipMemcpy(hs.data(), d_stamps, n_stamp_waves * 64, hipMemcpyDeviceToHost) == hipSuccess;
-        if (ok) {
-            double sum[6] = {0, 0, 0, 0, 0, 0}, trips = 0;
-            for (size_t w = 0; w < n_stamp_waves; w++) {
-                for (int i = 0; i < 6; i++) sum[i] += (double)hs[w * 8 + i];
-                trips += (double)hs[w * 8 + 6];
-            }
-            fprintf(stderr, "[tgx] estep7 stamps (s_memtime ticks per wave-trip, %zu waves x ppl %d, %.0f trips): claim %.0f  walk %.0f  cut %.0f  forward %.0f  z %.0f  backward %.0f\n",
-                    n_stamp_waves, ppl, trips, sum[0] / trips, sum[1] / trips, sum[2] / trips, sum[3] / trips, sum[4] / trips, sum[5] / trips);
-        }
-    }
+    if (stamps.d) stamps_report(m, stamps, ppl, "estep7 stamps", "trip", {"claim", "walk", "cut", "forward", "z", "backward"});
     unsigned long long flag = 0, n_redo = 0;
-    if (hipMemcpyAsync(&flag, m->d_ctrl + 5, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
-        hipMemcpyAsync(&n_redo, m->d_ctrl + 4, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
+    if (hipMemcpyAsync(&flag, &m->d_ctrl->estep.range_flag, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
+        hipMemcpyAsync(&n_redo, &m->d_ctrl->estep.redo_count, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
         hipStreamSynchronize(m->stream) != hipSuccess)
         return fail(TGX_ERR_DEVICE, "E-step pass failed: %s", hipGetErrorString(hipGetLastError()));
     m->last_estep_redo = n_redo;
@@ -2738,7 +2776,7 @@ static tgx_status estep_fused(tgx_model* m, tgx_corpus* c, uint64_t snippet_len,
             pass.alloc(tbb, &d_tbase) != hipSuccess)
             return fail(TGX_ERR_DEVICE, "out of device memory (E-step redo scratch)");
         if (hipMemcpyAsync(d_tbase, tbase.data(), (n_redo + 1) * 8, hipMemcpyHostToDevice, m->stream) != hipSuccess ||
-            hipMemsetAsync(m->d_ctrl + 3, 0x00, 8, m->stream) != hipSuccess)
+            hipMemsetAsync(&m->d_ctrl->estep.queue, 0x00, 8, m->stream) != hipSuccess)
             return fail(TGX_ERR_DEVICE, "E-step redo setup failed");
         tgx::Estep7RedoParams q{};
         q.text = c->d_text;
@@ -2757,8 +2795,8 @@ static tgx_status estep_fused(tgx_model* m, tgx_corpus* c, uint64_t snippet_len,
         q.expected = d_exp;
         q.zsnip = d_zsnip;
         q.logz_sum = d_z;
-        q.range_flag = m->d_ctrl + 5;
-        q.queue = m->d_ctrl + 3;
+        q.range_flag = &m->d_ctrl->estep.range_flag;
+        q.queue = &m->d_ctrl->estep.queue;
         q.alpha = d_alpha;
         q.aexp = d_aexp;
         q.mscratch = d_ms;
@@ -2768,7 +2806,7 @@ static tgx_status estep_fused(tgx_model* m, tgx_corpus* c, uint64_t snippet_len,
         const hipError_t le = tgx::launch_estep7_redo(q, wide_redo, (uint32_t)m->num_cus, m->stream);
         time_end(m);
         if (le != hipSuccess) return fail(TGX_ERR_DEVICE, "estep7 redo launch failed: %s", hipGetErrorString(le));
-        if (hipMemcpyAsync(&flag, m->d_ctrl + 5, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess)
+        if (hipMemcpyAsync(&flag, &m->d_ctrl->estep.range_flag, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess)
             return fail(TGX_ERR_DEVICE, "E-step redo pass failed");
         (void)hipStreamSynchronize(m->stream);
         if (hipGetLastError() != hipSuccess) return fail(TGX_ERR_DEVICE, "E-step redo pass failed");
@@ -2778,22 +2816,12 @@ static tgx_status estep_fused(tgx_model* m, tgx_corpus* c, uint64_t snippet_len,
         }
     }
     hp.mark("kernel + redo");
-    if (tgx::launch_snip_z_check(d_zsnip, K, m->d_ctrl + 1, m->stream) != hipSuccess) return fail(TGX_ERR_DEVICE, "z check launch failed");
+    if (tgx::launch_snip_z_check(d_zsnip, K, &m->d_ctrl->err, m->stream) != hipSuccess) return fail(TGX_ERR_DEVICE, "z check launch failed");
     std::vector<double> h((size_t)m->n_tok7 + 1);
     double hz = 0.0;
-    if (hipMemcpyAsync(&m->h_ctrl[0], m->d_ctrl + 1, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
-        hipMemcpyAsync(h.data(), d_exp, h.size() * 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
-        hipMemcpyAsync(&hz, d_z, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess || hipStreamSynchronize(m->stream) != hipSuccess)
-        return fail(TGX_ERR_DEVICE, "E-step pass failed: %s", hipGetErrorString(hipGetLastError()));
-    m->last_alg_bytes = N + 8 * (S + 1) + 8ull * m->vocab_size;
-    const unsigned long long bad = m->h_ctrl[0];
-    if (bad != ~0ULL) {  // nothing of a failed pass reaches the caller's `expected`
-        const uint64_t smp = es.ssample[bad];
-        g_err_sample = smp;
-        g_err_pos = g_err_len = c->h_offs[smp + 1] - c->h_offs[smp];
-        return fail(TGX_ERR_Z_NOT_NORMAL, "normalization constant is not a normal number (sample %llu, len=%llu)",
-                    (unsigned long long)smp, (unsigned long long)g_err_len);  // src/prune.rs:90-96
-    }
+    tgx_status st = estep_read_back(m, c, d_exp, &h, d_z, &hz, nullptr);
+    if (st == TGX_OK) st = estep_z_failure(m, c, es.ssample.data());
+    if (st != TGX_OK) return st;
     hp.mark("download");
     for (uint32_t r = 1; r <= m->n_tok7; r++) expected[m->id_of_rank[r]] += h[r];
     hp.mark("rank -> id");
@@ -2811,7 +2839,7 @@ static tgx_status estep_rows4(tgx_model* m, tgx_corpus* c, uint64_t snippet_len,
                               uint64_t seed, double* expected, double* logz_sum, bool* fallback) {
     const bool long_tokens = m->lm > 16;
     if (fallback) *fallback = false;
-    const uint64_t S = c->n_samples, N = c->n_bytes;
+    const uint64_t N = c->n_bytes;
     Pass pass(m);
     {
         const tgx_status wst = ensure_estep_work(m, c, snippet_len);
@@ -2836,29 +2864,19 @@ static tgx_status estep_rows4(tgx_model* m, tgx_corpus* c, uint64_t snippet_len,
     // Estimates as below (1 position per lane: forward 52 GB/s and 14.5 ms per 64 KiB of chain, backward 21 GB/s and
     // 29 ms); TGX_ESTEP_PIECES=0 / 1 forces, TGX_ESTEP_WINDOW sets the window.
     EstepPieces pc;
-    bool pieces = false;
+    m->last_estep_pieces = 0;
     if (linear && K && m->lm <= 32) {
-        uint32_t window = 2048;
-        if (const char* e = knob("TGX_ESTEP_WINDOW")) window = (uint32_t)std::min(1 << 20, std::max(256, atoi(e)));
-        const double longest0 = (double)(soffs[order[0] + 1] - soffs[order[0]]);
-        const double t_chain = longest0 / 65536.0 * (9.0 + 20.9) * 1e-3;     // the best chains of either kernel
-        const double t_thru = (double)N / 52e9 + (double)N / 21e9;
         // (measured, 32 000 entries, samples <= 64 KiB: 64 MiB 31.3 -> 4.1 ms, 256 MiB 33.0 -> 14.4, 512 MiB 44.8 -> 28.3,
         // 1 GiB 57.1 -> 57.2: the longest chains delay a pass well before they bound it — profiles/r03)
-        pieces = longest0 > 4.0 * window && t_chain > 0.5 * t_thru;
-        if (const char* e = knob("TGX_ESTEP_PIECES")) pieces = atoi(e) != 0 && longest0 > (double)window;
-        if (pieces) {
-            const tgx_status wst = ensure_estep_windows(m, c, window);
-            if (wst != TGX_OK) return wst;
-        }
-    }
-    if (pieces) {
-        const tgx_status pst = estep_pieces_build(m, c, m->d_trie_w, dropout, seed, pass, &pc);
+        const auto worth = [](double longest0, double n_bytes) {
+            const double t_chain = longest0 / 65536.0 * (9.0 + 20.9) * 1e-3;  // the best chains of either kernel
+            const double t_thru = n_bytes / 52e9 + n_bytes / 21e9;
+            return t_chain > 0.5 * t_thru;
+        };
+        const tgx_status pst = estep_pieces_if_worth(m, c, 2048, m->d_trie_w, worth, dropout, seed, pass, &pc);
         if (pst != TGX_OK) return pst;
-        m->last_estep_pieces = pc.n;
-    } else {
-        m->last_estep_pieces = 0;
     }
+    const bool pieces = pc.n != 0;
     const uint64_t Kmax = pieces ? std::max<uint64_t>(K, pc.n) : K;
     // replicas of the expected-count array (see estep4_bwd_kernel): up to 256, within 512 MiB
     // (round 3: 2.  The 256 of round 1 kept a handful of very frequent tokens from serialising every wave's atomics; those
@@ -2876,7 +2894,7 @@ static tgx_status estep_rows4(tgx_model* m, tgx_corpus* c, uint64_t snippet_len,
         return fail(TGX_ERR_DEVICE, "out of device memory (E-step scratch)");
     if (hipMemsetAsync(d_exp, 0, ebytes, m->stream) != hipSuccess ||
         hipMemsetAsync(d_z, 0, 256, m->stream) != hipSuccess ||
-        hipMemsetAsync(m->d_ctrl + 1, 0xFF, 8, m->stream) != hipSuccess)
+        hipMemsetAsync(&m->d_ctrl->err, 0xFF, 8, m->stream) != hipSuccess)
         return fail(TGX_ERR_DEVICE, "E-step setup copies failed");
     tgx::Estep4Params p{};
     p.text = c->d_text;
@@ -2896,14 +2914,11 @@ static tgx_status estep_rows4(tgx_model* m, tgx_corpus* c, uint64_t snippet_len,
     p.n_slots_rev = (uint32_t)n_rev;
     p.n_replicas = n_rep;
     p.logz_sum = d_z;
-    p.err_snip = m->d_ctrl + 1;
-    p.queue_fwd = m->d_ctrl + 3;
-    p.queue_bwd = m->d_ctrl + 4;
-    p.range_flag = m->d_ctrl + 5;
-    {
-        const char* f = debug_on() ? getenv("TGX_FLAGS") : nullptr;
-        p.flags = f ? (uint32_t)atoi(f) : 0u;
-    }
+    p.err_snip = &m->d_ctrl->err;
+    p.queue_fwd = &m->d_ctrl->estep.queue;
+    p.queue_bwd = &m->d_ctrl->estep.queue_bwd;
+    p.range_flag = &m->d_ctrl->estep.range_flag;
+    p.flags = debug_flags();
     p.dropout = dropout;
     p.seed = seed;
     // The linear-domain kernels are tried first; if some position of some snippet has no incoming token
@@ -2970,29 +2985,15 @@ static tgx_status estep_rows4(tgx_model* m, tgx_corpus* c, uint64_t snippet_len,
             ppl5f = 3;
             waves5f = 16;
         }
-        if (const char* e = knob("TGX_EPPL")) {
-            const int v = atoi(e);
-            if (v >= 1 && v <= 4) ppl5f = v;
-        }
-        uint32_t n_hot = std::min(m->n_values, tgx::encode5_max_hot(false, waves5f, ppl5f, budget));
-        if (const char* e = knob("TGX_E5_HOT")) {
-            const int v = atoi(e);
-            if (v >= 0) n_hot = std::min(n_hot, (uint32_t)v);
-        }
+        knob_int("TGX_EPPL", 1, 4, &ppl5f);
+        uint32_t n_hot = knob_cap_hot("TGX_E5_HOT", std::min(m->n_values, tgx::encode5_max_hot(false, waves5f, ppl5f, budget)));
         cold5f = n_hot < m->n_values;
         int per_simd = 0;
         if (tgx::estep5_waves_per_simd(dropout > 0.0, cold5f, ppl5f, &per_simd) != hipSuccess) return fail(TGX_ERR_DEVICE, "estep5 attribute query failed");
         waves5f = std::max(1, std::min(waves5f, per_simd * 4));
         const uint64_t n_units = pieces ? pc.n : K;
-        {
-            const uint64_t rows_wanted = (n_units + (uint64_t)m->num_cus - 1) / (uint64_t)m->num_cus;
-            waves5f = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)waves5f, (rows_wanted + 3) / 4));
-        }
-        n_hot = std::min(m->n_values, tgx::encode5_max_hot(false, waves5f, ppl5f, budget));  // (fewer waves: more room)
-        if (const char* e = knob("TGX_E5_HOT")) {
-            const int v = atoi(e);
-            if (v >= 0) n_hot = std::min(n_hot, (uint32_t)v);
-        }
+        waves5f = waves_for_units(waves5f, n_units, (uint64_t)m->num_cus);
+        n_hot = knob_cap_hot("TGX_E5_HOT", std::min(m->n_values, tgx::encode5_max_hot(false, waves5f, ppl5f, budget)));  // (fewer waves: more room)
         cold5f = n_hot < m->n_values;
         q5f.trie8 = m->d_trie8;
         q5f.trie_bytes = (uint32_t)(m->flat.table.size() * sizeof(tgx::Trie8Rec));
@@ -3000,8 +3001,7 @@ static tgx_status estep_rows4(tgx_model* m, tgx_corpus* c, uint64_t snippet_len,
         q5f.root_base = m->root_base8;
         q5f.n_values = m->n_values;
         q5f.n_hot = n_hot;
-        const uint64_t avg = n_units ? N / n_units : 0;
-        q5f.claim_chunk = (uint32_t)std::min<uint64_t>(16, std::max<uint64_t>(1, 4096 / std::max<uint64_t>(1, avg)));
+        q5f.claim_chunk = claim_chunk_for(N, n_units);
         const uint64_t rows_per_block = 4ull * (uint64_t)waves5f;
         blocks5f = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n_units + rows_per_block - 1) / rows_per_block, (uint64_t)m->num_cus));
     }
@@ -3015,10 +3015,10 @@ static tgx_status estep_rows4(tgx_model* m, tgx_corpus* c, uint64_t snippet_len,
         p.n_snips = on_pieces ? pc.n : K;
         p.snip_sample = on_pieces ? pc.d_sample : d_ssample;
         p.snip_base = on_pieces ? pc.d_base : d_sbase;
-        p.err_snip = on_pieces ? m->d_ctrl + 7 : m->d_ctrl + 1;  // pieces: z is checked per snippet (launch_piece_z_check)
-        if (hipMemsetAsync(m->d_ctrl + 3, 0x00, 24, m->stream) != hipSuccess ||
+        p.err_snip = on_pieces ? &m->d_ctrl->err_piece : &m->d_ctrl->err;  // pieces: z is checked per snippet (launch_piece_z_check)
+        if (hipMemsetAsync(&m->d_ctrl->estep, 0x00, sizeof(DeviceCtrl::Estep), m->stream) != hipSuccess ||
             hipMemsetAsync(d_z, 0, 256, m->stream) != hipSuccess ||
-            hipMemsetAsync(m->d_ctrl + 1, 0xFF, 8, m->stream) != hipSuccess)
+            hipMemsetAsync(&m->d_ctrl->err, 0xFF, 8, m->stream) != hipSuccess)
             return fail(TGX_ERR_DEVICE, "E-step queue reset failed");
         const bool fwd5 = use_linear && use5f;
         time_begin(m, fwd5 ? "estep5_fwd_kernel" : (use_linear ? "estep4l_fwd_kernel" : "estep4_fwd_kernel"));
@@ -3029,7 +3029,7 @@ static tgx_status estep_rows4(tgx_model* m, tgx_corpus* c, uint64_t snippet_len,
         time_end(m);
         if (use_linear) {
             unsigned long long flag = 0;
-            if (hipMemcpyAsync(&flag, m->d_ctrl + 5, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
+            if (hipMemcpyAsync(&flag, &m->d_ctrl->estep.range_flag, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
                 hipStreamSynchronize(m->stream) != hipSuccess)
                 return fail(TGX_ERR_DEVICE, "E-step forward pass failed: %s", hipGetErrorString(hipGetLastError()));
             if (flag != 0) {
@@ -3048,7 +3048,7 @@ static tgx_status estep_rows4(tgx_model* m, tgx_corpus* c, uint64_t snippet_len,
                         : tgx::launch_estep4_bwd(p, (uint32_t)m->num_cus, m->stream)) != hipSuccess)
             return fail(TGX_ERR_DEVICE, "estep4 backward launch failed");
         time_end(m);
-        if (on_pieces && tgx::launch_piece_z_check(d_zarr, pc.d_snip, pc.n, pc.d_zsnip, K, m->d_ctrl + 1, m->stream) != hipSuccess)
+        if (on_pieces && tgx::launch_piece_z_check(d_zarr, pc.d_snip, pc.n, pc.d_zsnip, K, &m->d_ctrl->err, m->stream) != hipSuccess)
             return fail(TGX_ERR_DEVICE, "E-step z check launch failed");
         break;
     }
@@ -3063,12 +3063,8 @@ static tgx_status estep_rows4(tgx_model* m, tgx_corpus* c, uint64_t snippet_len,
     // position and window; the forward kernel counts them by START position), so it can run out where the forward
     // kernel did not: the flag is read again with the results, and a pass that raised it is discarded.
     unsigned long long flag_bwd = 0;
-    if (hipMemcpyAsync(&m->h_ctrl[0], m->d_ctrl + 1, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
-        hipMemcpyAsync(&flag_bwd, m->d_ctrl + 5, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
-        hipMemcpyAsync(h.data(), d_sum, n_rev * 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
-        hipMemcpyAsync(&hz, d_z, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
-        hipStreamSynchronize(m->stream) != hipSuccess)
-        return fail(TGX_ERR_DEVICE, "E-step pass failed: %s", hipGetErrorString(hipGetLastError()));
+    tgx_status st = estep_read_back(m, c, d_sum, &h, d_z, &hz, &flag_bwd);
+    if (st != TGX_OK) return st;
     if (use_linear && flag_bwd != 0) {  // nothing of this pass reaches `expected`
         if (long_tokens && fallback) {
             *fallback = true;  // the generic kernel redoes it (tgx_estep)
@@ -3076,19 +3072,9 @@ static tgx_status estep_rows4(tgx_model* m, tgx_corpus* c, uint64_t snippet_len,
         }
         return fail(TGX_ERR_DEVICE, "E-step backward kernel raised range_flag %llu after a clean forward pass", flag_bwd);
     }
-    m->last_alg_bytes = N + 8 * (S + 1) + 8ull * m->vocab_size;
-    const unsigned long long bad = m->h_ctrl[0];
-    if (bad != ~0ULL) {  // nothing of a failed pass reaches the caller's `expected`
-        const uint64_t smp = ssample[bad];
-        g_err_sample = smp;
-        g_err_pos = g_err_len = c->h_offs[smp + 1] - c->h_offs[smp];
-        return fail(TGX_ERR_Z_NOT_NORMAL, "normalization constant is not a normal number (sample %llu, len=%llu)",
-                    (unsigned long long)smp, (unsigned long long)g_err_len);  // src/prune.rs:90-96
-    }
-    for (size_t t = 0; t < n_rev; t++) {
-        const uint32_t id = m->flat_rev.tokid[t];
-        if (id != tgx::kNoToken) expected[id] += h[t];
-    }
+    st = estep_z_failure(m, c, ssample.data());
+    if (st != TGX_OK) return st;
+    add_slot_counts(m, h, expected);
     if (logz_sum) *logz_sum = hz;
     m->estep_calls++;
     return pass.done();
@@ -3141,7 +3127,7 @@ tgx_status tgx_estep(tgx_model* m, tgx_corpus* c, uint64_t snippet_len, double d
         return fail(TGX_ERR_DEVICE, "out of device memory (E-step scratch)");
     if (hipMemsetAsync(d_exp, 0, ebytes, m->stream) != hipSuccess ||
         hipMemsetAsync(d_z, 0, 256, m->stream) != hipSuccess ||
-        hipMemsetAsync(m->d_ctrl + 1, 0xFF, 8, m->stream) != hipSuccess)
+        hipMemsetAsync(&m->d_ctrl->err, 0xFF, 8, m->stream) != hipSuccess)
         return fail(TGX_ERR_DEVICE, "memset failed");
     tgx::EstepParams p{};
     p.text = c->d_text;
@@ -3159,7 +3145,7 @@ tgx_status tgx_estep(tgx_model* m, tgx_corpus* c, uint64_t snippet_len, double d
     p.n_slots_rev = (uint32_t)n_rev;
     p.n_replicas = n_rep;
     p.logz_sum = d_z;
-    p.err_sample = m->d_ctrl + 1;
+    p.err_sample = &m->d_ctrl->err;
     p.dropout = dropout;
     p.seed = seed;
     const uint64_t wpb = tgx::estep_waves_per_block(m->lm);
@@ -3174,26 +3160,11 @@ tgx_status tgx_estep(tgx_model* m, tgx_corpus* c, uint64_t snippet_len, double d
         return fail(TGX_ERR_DEVICE, "estep reduce launch failed");
     std::vector<double> h(n_rev);
     double hz = 0.0;
-    if (hipMemcpyAsync(&m->h_ctrl[0], m->d_ctrl + 1, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
-        hipMemcpyAsync(h.data(), d_sum, n_rev * 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
-        hipMemcpyAsync(&hz, d_z, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
-        hipStreamSynchronize(m->stream) != hipSuccess)
-        return fail(TGX_ERR_DEVICE, "E-step pass failed: %s", hipGetErrorString(hipGetLastError()));
-    for (size_t t = 0; t < n_rev; t++) {
-        const uint32_t id = m->flat_rev.tokid[t];
-        if (id != tgx::kNoToken) expected[id] += h[t];
-    }
+    st = estep_read_back(m, c, d_sum, &h, d_z, &hz, nullptr);
+    if (st == TGX_OK) st = estep_z_failure(m, c, nullptr);  // (this kernel's units are the samples)
+    if (st != TGX_OK) return st;
+    add_slot_counts(m, h, expected);
     if (logz_sum) *logz_sum = hz;
-    // N + 8(S+1) + 8V
-    m->last_alg_bytes = N + 8 * (S + 1) + 8ull * m->vocab_size;
-    const unsigned long long bad = m->h_ctrl[0];
-    if (bad != ~0ULL) {
-        g_err_sample = bad;
-        g_err_pos = g_err_len = c->h_offs[bad + 1] - c->h_offs[bad];
-        // the reference panics here: src/prune.rs:90-96
-        return fail(TGX_ERR_Z_NOT_NORMAL, "normalization constant is not a normal number (sample %llu, len=%llu)",
-                    bad, (unsigned long long)g_err_len);
-    }
     return pass.done();
 }
 
@@ -3250,32 +3221,11 @@ static tgx_status sample_corpus_locked(tgx_model* m, tgx_corpus* c, double alpha
     tgx_status st = ensure_scratch(c);
     if (st != TGX_OK) return st;
     unsigned long long* d_range = reinterpret_cast<unsigned long long*>(d_logz + S);
-    if (hipMemsetAsync(m->d_ctrl, 0x00, 8, m->stream) != hipSuccess || hipMemsetAsync(m->d_ctrl + 1, 0xFF, 8, m->stream) != hipSuccess ||
+    if (hipMemsetAsync(&m->d_ctrl->queue, 0x00, 8, m->stream) != hipSuccess || hipMemsetAsync(&m->d_ctrl->err, 0xFF, 8, m->stream) != hipSuccess ||
         hipMemsetAsync(d_range, 0x00, 8, m->stream) != hipSuccess)
         return fail(TGX_ERR_DEVICE, "memset failed");
 
-    tgx::EncodeParams p{};
-    p.text = c->d_text;
-    p.offs = c->d_offs;
-    p.order = c->d_order;
-    p.n_samples = S;
-    p.trie = m->d_trie;
-    p.tokid = m->d_tokid;
-    p.root_base = m->flat.table[0].base & ~tgx::kTerminalBit;
-    p.lm = m->lm;
-    p.n_slots = n_slots;
-    p.bp = c->d_bp;
-    p.tmp = c->d_tmp;
-    p.counts = c->d_counts;
-    p.status = c->d_status;
-    p.bp8 = reinterpret_cast<uint8_t*>(c->d_bp.get());
-    p.tokhash = m->d_tokhash;
-    p.tokhash_mask = m->tokhash.mask;
-    p.tokhash_seed = m->tokhash.seed;
-    p.err_sample = m->d_ctrl + 1;
-    p.queue = m->d_ctrl;
-    p.seed = seed;
-    p.trace_carry = (S && c->n_bytes / S < 2048) ? 1u : 0u;
+    const tgx::EncodeParams p = base_encode_params(m, c, seed);
     tgx::SampleParams q{};
     q.alpha = alpha;
     q.logz = d_logz;
@@ -3295,11 +3245,10 @@ static tgx_status sample_corpus_locked(tgx_model* m, tgx_corpus* c, double alpha
             return fail(TGX_ERR_DEVICE, "sampling pass failed: %s", hipGetErrorString(hipGetLastError()));
         if (range) {  // a value the linear domain cannot hold exactly: the whole call on the log-domain kernel
             rows = false;
-            if (hipMemsetAsync(m->d_ctrl + 1, 0xFF, 8, m->stream) != hipSuccess) return fail(TGX_ERR_DEVICE, "memset failed");
+            if (hipMemsetAsync(&m->d_ctrl->err, 0xFF, 8, m->stream) != hipSuccess) return fail(TGX_ERR_DEVICE, "memset failed");
         } else {
-            const uint32_t blocks_t = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((S + 3) / 4, (uint64_t)m->num_cus * 8));
             time_begin(m, "trace32_kernel");
-            if (tgx::launch_trace32(p, blocks_t, false, m->stream) != hipSuccess)
+            if (tgx::launch_trace32(p, trace_blocks(m, S), false, m->stream) != hipSuccess)
                 return fail(TGX_ERR_DEVICE, "trace32_kernel launch failed");
             time_end(m);
         }
@@ -3423,7 +3372,7 @@ static tgx_status nbest_corpus_locked(tgx_model* m, tgx_corpus* c, uint32_t k, d
         (scan_bytes && pass.alloc(scan_bytes, &d_scan) != hipSuccess))
         return fail(TGX_ERR_DEVICE, "out of device memory (n-best)");
     if ((S && hipMemcpyAsync(d_order, order.data(), (size_t)S * 4, hipMemcpyHostToDevice, m->stream) != hipSuccess) ||
-        hipMemsetAsync(r->d_offs, 0, 8, m->stream) != hipSuccess || hipMemsetAsync(m->d_ctrl + 1, 0xFF, 8, m->stream) != hipSuccess)
+        hipMemsetAsync(r->d_offs, 0, 8, m->stream) != hipSuccess || hipMemsetAsync(&m->d_ctrl->err, 0xFF, 8, m->stream) != hipSuccess)
         return fail(TGX_ERR_DEVICE, "n-best upload failed");
 
     tgx::NbestParams p{};
@@ -3439,7 +3388,7 @@ static tgx_status nbest_corpus_locked(tgx_model* m, tgx_corpus* c, uint32_t k, d
     p.tmp = d_tmp;
     p.scores = d_scores;
     p.n_found = d_nfound;
-    p.err_sample = m->d_ctrl + 1;
+    p.err_sample = &m->d_ctrl->err;
     uint64_t total = 0;
     for (size_t ci = 0; ci + 1 < cs.size() && cs[ci] < cs[ci + 1]; ci++) {
         const uint64_t s0 = cs[ci], ns = cs[ci + 1] - s0, R0 = s0 * k;
@@ -3461,13 +3410,13 @@ static tgx_status nbest_corpus_locked(tgx_model* m, tgx_corpus* c, uint32_t k, d
             return fail(TGX_ERR_DEVICE, "scan launch failed");
         time_end(m);
         uint64_t tc = 0;
-        if (hipMemcpyAsync(&m->h_ctrl[0], m->d_ctrl + 1, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
-            hipMemcpyAsync(&m->h_ctrl[1], r->d_offs + R0 + ns * k, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
+        if (hipMemcpyAsync(&m->h_ctrl->err, &m->d_ctrl->err, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
+            hipMemcpyAsync(&m->h_ctrl->total_tokens, r->d_offs + R0 + ns * k, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
             hipStreamSynchronize(m->stream) != hipSuccess)
             return fail(TGX_ERR_DEVICE, "n-best pass failed: %s", hipGetErrorString(hipGetLastError()));
         const tgx_status st = check_no_path(m, c);  // chunks go in input order: the first failing one holds the lowest sample
         if (st != TGX_OK) return st;
-        tc = m->h_ctrl[1];
+        tc = m->h_ctrl->total_tokens;
         uint32_t* ids = nullptr;
         const size_t ib = (size_t)tc * 4 + 256;
         if ((one_chunk ? r->d_ids.alloc(m->device, ib) : pass.alloc(ib, &ids)) != hipSuccess)
@@ -3497,8 +3446,8 @@ static tgx_status nbest_corpus_locked(tgx_model* m, tgx_corpus* c, uint32_t k, d
         (n_found && S && hipMemcpyAsync(n_found, d_nfound, (size_t)S * 4, hipMemcpyDeviceToHost, m->stream) != hipSuccess) ||
         hipStreamSynchronize(m->stream) != hipSuccess)
         return fail(TGX_ERR_DEVICE, "n-best pass failed: %s", hipGetErrorString(hipGetLastError()));
-    m->h_ctrl[0] = ~0ULL;
-    if (hipMemcpy(&m->h_ctrl[0], m->d_ctrl + 1, 8, hipMemcpyDeviceToHost) != hipSuccess)
+    m->h_ctrl->err = ~0ULL;
+    if (hipMemcpy(&m->h_ctrl->err, &m->d_ctrl->err, 8, hipMemcpyDeviceToHost) != hipSuccess)
         return fail(TGX_ERR_DEVICE, "n-best pass failed");
     const tgx_status st = check_no_path(m, c);  // (a corrupt back-pointer found by the trace: never a fault)
     if (st != TGX_OK) return st;
