@@ -233,6 +233,63 @@ tgx_status tgx_result_copy_offsets(const tgx_result *r, uint64_t *dst, uint64_t 
 const void *tgx_result_ids_device(const tgx_result *r);
 const void *tgx_result_offsets_device(const tgx_result *r);
 void tgx_result_free(tgx_result *r);
+/* The device the result's arrays live on. */
+int tgx_result_device(const tgx_result *r);
+
+/* ---- layouts for a model: the ids of a result as padded rows or packed blocks, written on the device ----------
+ * A result of encode, sampling or n-best (n-best rows are just rows) laid out in caller-owned DEVICE memory, e.g. a
+ * torch tensor's data_ptr(), by the kernels of csrc/layout.hip: the ids never visit the host.  Row i has the tokens
+ * t_i[0..n_i), n_i = ooffs[i+1] - ooffs[i].  bos_id / eos_id: TGX_NO_ID = none; A = how many of the two are present.
+ * Every id written, pad_id included, must be below 2^31 (TGX_ERR_INVALID otherwise).  Elements are int32_t, or
+ * int64_t with TGX_LAYOUT_I64.  All element indices are 64-bit.
+ *
+ * Padded, row_len = L (L >= 1 and L >= A, else TGX_ERR_INVALID): keep_i = min(n_i, L - A) tokens are kept, the first
+ *   keep_i, or the last keep_i with TGX_LAYOUT_TRUNC_LEFT; seq_i = [bos] + kept + [eos], len_i = keep_i + A;
+ *   out[i, 0:len_i] = seq_i and the rest of the row is pad_id, or out[i, L-len_i:L] = seq_i with TGX_LAYOUT_PAD_LEFT.
+ *   d_mask (NULL or u8[S·L]): 1 on seq_i, 0 on padding.  d_lengths (NULL or i32[S]): len_i.  *n_truncated (NULL or
+ *   host): rows with n_i > L - A.  S = 0 writes nothing.
+ * Packed, block_len = L >= 1: the rows' sequences [bos] + t_i + [eos] back to back; row i starts at stream position
+ *   P_i = ooffs[i] + i·A, n_stream = T + S·A, *n_blocks = ceil(n_stream / L) (0 for an empty stream) and n_blocks·L
+ *   elements are written: position j < n_stream belongs to the row i with P_i <= j < P_{i+1} (rows with n_i = 0 and
+ *   A = 0 own no position), d_doc[j] = i and d_pos[j] = j - P_i (each NULL or i32[n_blocks·L]); in the tail of the
+ *   last block ids = pad_id, doc = -1, pos = 0.  2^31 rows or more: TGX_ERR_UNSUPPORTED.
+ * tgx_result_layout_info sizes the destinations: *max_row_len = max_i n_i + A (A when S = 0; a device reduction, one
+ *   word is read back), *n_stream as above.  Either out pointer may be NULL.  The reduction runs on the library's
+ *   stream (see below), so it also waits for work queued earlier on the device's null stream although it reads the
+ *   result's offsets only: a cost in time, not a dependency.  It is skipped when max_row_len is NULL.
+ *
+ * stream is a hipStream_t: pass the stream the destination's allocator orders its memory on (torch's current
+ * stream); NULL selects a stream of the library.  That one is a blocking stream (hipStreamDefault): its work starts
+ * after everything queued earlier on the device's null stream, so NULL is also right for a caller whose stream IS the
+ * null stream, whose handle is 0 (torch's default stream).  The work is queued on the chosen stream and the call
+ * returns only after the stream has reached its end.  Two rules rest on this: a caching allocator may hand out a
+ * block that work still queued on its stream reads, so writing it from an unordered stream would race; and the result
+ * may be freed, and its pooled buffers reused, as soon as the call returns.  The destinations must be device memory on
+ * the result's device (checked with hipPointerGetAttributes: TGX_ERR_INVALID otherwise).  Only where a destination
+ * lies can be checked, not how large it is: room for every element written (S·row_len ids and mask bytes, S lengths;
+ * n_blocks·block_len ids, docs and positions) is the caller's responsibility.  NULL arguments are refused before any
+ * device call.  The calling thread's current device is the same after the call as before. */
+#define TGX_NO_ID 0xFFFFFFFFu
+#define TGX_LAYOUT_PAD_LEFT 1u
+#define TGX_LAYOUT_TRUNC_LEFT 2u
+#define TGX_LAYOUT_I64 4u
+tgx_status tgx_result_layout_info(const tgx_result *r, uint32_t bos_id, uint32_t eos_id,
+                                  uint64_t *max_row_len, uint64_t *n_stream);
+tgx_status tgx_result_pad_device(const tgx_result *r, uint32_t row_len, uint32_t pad_id, uint32_t bos_id, uint32_t eos_id,
+                                 uint32_t flags, void *stream, void *d_ids, uint8_t *d_mask, int32_t *d_lengths,
+                                 uint64_t *n_truncated);
+tgx_status tgx_result_pack_device(const tgx_result *r, uint32_t block_len, uint32_t pad_id, uint32_t bos_id, uint32_t eos_id,
+                                  uint32_t flags, void *stream, void *d_ids, int32_t *d_doc, int32_t *d_pos, uint64_t *n_blocks);
+/* Host twins over host arrays (ids u32[T], may be NULL when T = 0; offs u64[n_rows + 1], offs[0] = 0, ascending):
+ * the same semantics through the same row mapping (csrc/layout.h), no device — for callers of tgx_encode_batch_host
+ * and for validation on machines without a GPU.  Here every id of `ids` that is written is checked against 2^31.
+ * The packed form writes ceil((T + n_rows·A) / block_len) · block_len elements. */
+tgx_status tgx_layout_pad_host(const uint32_t *ids, const uint64_t *offs, uint64_t n_rows, uint32_t row_len, uint32_t pad_id,
+                               uint32_t bos_id, uint32_t eos_id, uint32_t flags, void *out_ids, uint8_t *out_mask,
+                               int32_t *out_lengths, uint64_t *n_truncated);
+tgx_status tgx_layout_pack_host(const uint32_t *ids, const uint64_t *offs, uint64_t n_rows, uint32_t block_len, uint32_t pad_id,
+                                uint32_t bos_id, uint32_t eos_id, uint32_t flags, void *out_ids, int32_t *out_doc,
+                                int32_t *out_pos, uint64_t *n_blocks);
 
 /* ---- resident corpus: the prune / merge training loops -------------------- */
 /* The reference holds `samples: &[&str]` in RAM across all EM / merge passes

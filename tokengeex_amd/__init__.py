@@ -7,8 +7,10 @@ and DESIGN.md for the path and its boundary.
 """
 from ._lib import (ESTEP_SNIPPET_LEN, MAX_TOKEN_LEN, NativeCorpus, NativeModel, NativeResult,
                    TokenGeeXError, device_count, pack)
+from . import tensors  # torch is imported inside its functions
+from .tensors import to_packed, to_padded
 from .tokenizer import CrlfProcessor, Tokenizer, UnicodeProcessor, split_special_tokens
 
 __all__ = ["Tokenizer", "TokenGeeXError", "NativeModel", "NativeCorpus", "NativeResult",
            "CrlfProcessor", "UnicodeProcessor", "split_special_tokens", "device_count", "pack",
-           "MAX_TOKEN_LEN", "ESTEP_SNIPPET_LEN"]
+           "MAX_TOKEN_LEN", "ESTEP_SNIPPET_LEN", "tensors", "to_padded", "to_packed"]

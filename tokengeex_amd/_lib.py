@@ -20,6 +20,8 @@ OK, ERR_IO, ERR_JSON, ERR_TOKEN_ID_OOB, ERR_NO_PATH, ERR_DEVICE, ERR_Z_NOT_NORMA
 MAX_TOKEN_LEN = 64
 MAX_NBEST = 16  # TGX_MAX_NBEST
 ESTEP_SNIPPET_LEN = 81920
+NO_ID = 0xFFFFFFFF  # TGX_NO_ID: no bos / eos
+LAYOUT_PAD_LEFT, LAYOUT_TRUNC_LEFT, LAYOUT_I64 = 1, 2, 4  # TGX_LAYOUT_*
 
 # every exported symbol of include/tgx.h: name -> (restype, argtypes)
 _vp, _u64, _u32, _i, _d = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_double
@@ -104,6 +106,12 @@ SYMBOLS = {
     "tgx_encode_corpus_sample": (_i, [_vp, _vp, _d, _u64, _vp, _pvp]),
     "tgx_encode_batch_nbest": (_i, [_vp, _vp, _vp, _u64, _u32, _vp, _vp, _pvp]),
     "tgx_encode_corpus_nbest": (_i, [_vp, _vp, _u32, _vp, _vp, _pvp]),
+    "tgx_result_device": (_i, [_vp]),
+    "tgx_result_layout_info": (_i, [_vp, _u32, _u32, _pu64, _pu64]),
+    "tgx_result_pad_device": (_i, [_vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _pu64]),
+    "tgx_result_pack_device": (_i, [_vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _pu64]),
+    "tgx_layout_pad_host": (_i, [_vp, _vp, _u64, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _pu64]),
+    "tgx_layout_pack_host": (_i, [_vp, _vp, _u64, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _pu64]),
 }
 
 
@@ -117,11 +125,39 @@ class TokenGeeXError(Exception):
         self.status, self.sample, self.pos, self.length = status, sample, pos, length
 
 
+def _share_torch_hip_runtime() -> None:
+    """One HIP runtime per process.  A PyTorch-ROCm wheel carries its own libamdhip64.so (soname libamdhip64.so.7, the
+    name libtgx.so asks for) and libhsa-runtime64.so.  When torch is imported first, libtgx.so binds to that copy and the
+    two share devices, streams and pointers (bench.py, dist.py).  Imported the other way round, libtgx.so would bring
+    in the system's copy, torch its own beside it, and the runtime that initialises second finds no GPU — and
+    tokengeex_amd.tensors hands torch's streams and data_ptr()s to libtgx.so, which only works inside one runtime.  So
+    torch's copy, if there is one, is loaded here ahead of libtgx.so, WITHOUT importing torch (find_spec only looks the
+    package up).  TGX_HIP_RUNTIME=system keeps the system's runtime (then import torch first, or do not use
+    tokengeex_amd.tensors)."""
+    import sys
+    if os.environ.get("TGX_HIP_RUNTIME", "") == "system" or "torch" in sys.modules:
+        return
+    import importlib.util
+    try:
+        spec = importlib.util.find_spec("torch")
+    except (ImportError, ValueError):
+        return
+    for root in (spec.submodule_search_locations or []) if spec else []:
+        path = os.path.join(root, "lib", "libamdhip64.so")
+        if os.path.exists(path):
+            try:
+                C.CDLL(path, mode=C.RTLD_GLOBAL)
+            except OSError:
+                pass  # libtgx.so then loads the system's runtime, as without torch
+            return
+
+
 def _load() -> C.CDLL:
     if not os.path.exists(LIB_PATH):
         raise ImportError(
             f"{LIB_PATH} is missing: the HIP extension is mandatory (no CPU fallback). "
             "Build it with `python tokengeex_amd/build.py`.")
+    _share_torch_hip_runtime()
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in SYMBOLS.items():
         fn = getattr(lib, name)  # AttributeError if the .so does not export it
@@ -362,6 +398,68 @@ def utf8_lossy(data: bytes) -> bytes:
     return out[:n].tobytes()
 
 
+def _u32_arg(v, name: str) -> int:
+    v = int(v)
+    if not 0 <= v <= 0xFFFFFFFF:
+        raise TokenGeeXError(f"{name} {v} is not a u32", ERR_INVALID)
+    return v
+
+
+def _id_or_none(v) -> int:
+    return NO_ID if v is None else _u32_arg(v, "token id")
+
+
+def layout_flags(padding_side: str = "right", truncation_side: str = "right", dtype=np.int32) -> int:
+    """TGX_LAYOUT_* flags of a padded / packed layout; dtype: int32 or int64 (numpy)."""
+    for side in (padding_side, truncation_side):
+        if side not in ("left", "right"):
+            raise ValueError(f"side must be 'left' or 'right' (got {side!r})")
+    dt = np.dtype(dtype)
+    if dt not in (np.dtype(np.int32), np.dtype(np.int64)):
+        raise ValueError(f"dtype must be int32 or int64 (got {dt})")
+    return ((LAYOUT_PAD_LEFT if padding_side == "left" else 0) | (LAYOUT_TRUNC_LEFT if truncation_side == "left" else 0)
+            | (LAYOUT_I64 if dt == np.dtype(np.int64) else 0))
+
+
+def layout_pad_host(ids: np.ndarray, offs: np.ndarray, row_len: int, pad_id: int, *, bos_id: int | None = None,
+                    eos_id: int | None = None, padding_side: str = "right", truncation_side: str = "right", dtype=np.int32) -> dict:
+    """Host twin of NativeResult.pad_device (tgx_layout_pad_host: the same row mapping, no device) over ids u32[T] and
+    offsets u64[S+1] -> {"input_ids": [S, row_len] of dtype, "attention_mask": u8 [S, row_len], "lengths": i32[S],
+    "n_truncated": int}."""
+    ids = np.ascontiguousarray(ids, dtype=np.uint32)
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    n, L = offs.shape[0] - 1, _u32_arg(row_len, "row_len")
+    out = np.empty((n, L), np.dtype(dtype))
+    mask = np.empty((n, L), np.uint8)
+    lengths = np.empty(n, np.int32)
+    nt = C.c_uint64()
+    check(lib.tgx_layout_pad_host(ptr(ids) if ids.size else None, ptr(offs), n, L, _u32_arg(pad_id, "pad_id"), _id_or_none(bos_id), _id_or_none(eos_id),
+                                  layout_flags(padding_side, truncation_side, dtype), ptr(out) if out.size else None,
+                                  ptr(mask) if mask.size else None, ptr(lengths) if n else None, C.byref(nt)))
+    return {"input_ids": out, "attention_mask": mask, "lengths": lengths, "n_truncated": nt.value}
+
+
+def layout_pack_host(ids: np.ndarray, offs: np.ndarray, block_len: int, pad_id: int, *, bos_id: int | None = None,
+                     eos_id: int | None = None, dtype=np.int32) -> dict:
+    """Host twin of NativeResult.pack_device (tgx_layout_pack_host) -> {"input_ids": [B, block_len] of dtype, "doc_ids" and
+    "positions": i32 [B, block_len]}."""
+    ids = np.ascontiguousarray(ids, dtype=np.uint32)
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    n, L = offs.shape[0] - 1, _u32_arg(block_len, "block_len")
+    a = (_id_or_none(bos_id) != NO_ID) + (_id_or_none(eos_id) != NO_ID)
+    n_stream = int(offs[-1]) + n * a
+    nb = -(-n_stream // L) if L else 0
+    out = np.empty((nb, L), np.dtype(dtype))
+    doc = np.empty((nb, L), np.int32)
+    pos = np.empty((nb, L), np.int32)
+    got = C.c_uint64()
+    check(lib.tgx_layout_pack_host(ptr(ids) if ids.size else None, ptr(offs), n, L, _u32_arg(pad_id, "pad_id"), _id_or_none(bos_id), _id_or_none(eos_id),
+                                   layout_flags(dtype=dtype), ptr(out) if out.size else None, ptr(doc) if doc.size else None,
+                                   ptr(pos) if pos.size else None, C.byref(got)))
+    assert got.value == nb, (got.value, nb)
+    return {"input_ids": out, "doc_ids": doc, "positions": pos}
+
+
 class NativeResult:
     """Owns a tgx_result (ids + offsets of one encode pass)."""
 
@@ -407,6 +505,47 @@ class NativeResult:
 
     def ids_device_ptr(self) -> int:
         return lib.tgx_result_ids_device(self._h) or 0
+
+    @property
+    def device(self) -> int:
+        return lib.tgx_result_device(self._h)
+
+    # -- layouts for a model (include/tgx.h: tgx_result_pad_device / tgx_result_pack_device; csrc/layout.hip) --
+    def layout_info(self, bos_id: int | None = None, eos_id: int | None = None) -> tuple[int, int]:
+        """-> (max_row_len = longest row + A, n_stream = T + S·A), A = how many of bos / eos are given: what sizes the
+        destinations of pad_device / pack_device.  The longest row is reduced on the device (one word comes back)."""
+        mx, ns = C.c_uint64(), C.c_uint64()
+        check(lib.tgx_result_layout_info(self._h, _id_or_none(bos_id), _id_or_none(eos_id), C.byref(mx), C.byref(ns)))
+        return mx.value, ns.value
+
+    def pad_device(self, row_len: int, pad_id: int, ids_ptr: int, *, mask_ptr: int = 0, lengths_ptr: int = 0,
+                   bos_id: int | None = None, eos_id: int | None = None, flags: int = 0, stream: int = 0) -> int:
+        """The rows padded / truncated to row_len, written by the device into caller-owned device memory given as raw
+        integer pointers (ids: i32 or, with LAYOUT_I64, i64 [S·row_len]; mask u8[S·row_len]; lengths i32[S]; 0 = not
+        wanted), queued on `stream` (a hipStream_t as an integer; 0: a stream of the library, which is ordered after everything
+        queued earlier on the device's null stream — 0 is that stream's own handle, torch's default stream).  Returns when
+        the stream has reached its end -> number of truncated rows."""
+        nt = C.c_uint64()
+        check(lib.tgx_result_pad_device(self._h, _u32_arg(row_len, "row_len"), _u32_arg(pad_id, "pad_id"), _id_or_none(bos_id), _id_or_none(eos_id),
+                                        int(flags), stream or None, ids_ptr or None, mask_ptr or None, lengths_ptr or None, C.byref(nt)))
+        return nt.value
+
+    def pack_device(self, block_len: int, pad_id: int, ids_ptr: int, *, doc_ptr: int = 0, pos_ptr: int = 0,
+                    bos_id: int | None = None, eos_id: int | None = None, flags: int = 0, stream: int = 0) -> int:
+        """The rows' sequences back to back, cut into blocks of block_len (ids i32 / i64, doc and pos i32, each
+        [n_blocks·block_len] with n_blocks = ceil(layout_info()[1] / block_len)); as pad_device -> n_blocks."""
+        nb = C.c_uint64()
+        check(lib.tgx_result_pack_device(self._h, _u32_arg(block_len, "block_len"), _u32_arg(pad_id, "pad_id"), _id_or_none(bos_id), _id_or_none(eos_id),
+                                         int(flags), stream or None, ids_ptr or None, doc_ptr or None, pos_ptr or None, C.byref(nb)))
+        return nb.value
+
+    def pad_host(self, row_len: int, pad_id: int, **kw) -> dict:
+        """layout_pad_host over the ids and offsets copied to the host."""
+        return layout_pad_host(self.ids(), self.offsets(), row_len, pad_id, **kw)
+
+    def pack_host(self, block_len: int, pad_id: int, **kw) -> dict:
+        """layout_pack_host over the ids and offsets copied to the host."""
+        return layout_pack_host(self.ids(), self.offsets(), block_len, pad_id, **kw)
 
 
 class NativeCorpus:

@@ -289,4 +289,25 @@ hipError_t scan_temp_bytes(uint64_t n, size_t* bytes);
 hipError_t launch_scan(uint32_t* counts, uint64_t* offsets, uint64_t n, void* temp, size_t temp_bytes, hipStream_t stream);
 hipError_t launch_compact(const CompactParams& p, uint32_t blocks, bool rows, hipStream_t stream);
 
+// layout.hip: a result's ids laid out as [S, L] padded rows or as a packed stream of [B, L] blocks (layout.h has the
+// row mapping).  Outputs are caller-owned device memory; any of mask / lengths / doc / pos / counter may be null.
+struct LayoutParams {
+    const uint32_t* ids;            // u32[T]
+    const uint64_t* offs;           // u64[S+1]
+    uint64_t n_rows;                // S
+    uint32_t len;                   // row_len (padded) or block_len (packed)
+    uint32_t pad, bos, eos;         // bos / eos: 0xFFFFFFFF = none
+    uint32_t flags;                 // TGX_LAYOUT_*
+    void* out;                      // i32 or i64 (TGX_LAYOUT_I64)
+    uint8_t* mask;                  // padded: u8[S·L]
+    int32_t* lengths;               // padded: i32[S]
+    int32_t* doc;                   // packed: i32[n_out]
+    int32_t* pos;                   // packed: i32[n_out]
+    unsigned long long* counter;    // padded: rows with n_i > L - A are added to it (zeroed by the caller)
+};
+hipError_t launch_layout_max_row(const uint64_t* offs, uint64_t n_rows, unsigned long long* max_out, hipStream_t stream);
+hipError_t launch_layout_pad(const LayoutParams& p, hipStream_t stream);
+// n_stream = T + S·A positions hold ids, n_out = n_blocks · block_len elements are written
+hipError_t launch_layout_pack(const LayoutParams& p, uint64_t n_stream, uint64_t n_out, hipStream_t stream);
+
 }  // namespace tgx

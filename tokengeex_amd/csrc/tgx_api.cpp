@@ -24,6 +24,7 @@
 
 #include "../../include/tgx.h"
 #include "kernels.h"
+#include "layout.h"
 #include "nbest.h"
 #include "sample.h"
 #include "trie_build.h"
@@ -343,6 +344,7 @@ struct tgx_corpus {
 
 struct tgx_result {
     int device = 0;
+    uint32_t vocab_size = 0;  // of the model that wrote it: every id is below it
     uint64_t n_samples = 0, n_tokens = 0;
     PoolBuf<uint32_t> d_ids;
     PoolBuf<uint64_t> d_offs;
@@ -380,6 +382,7 @@ public:
     tgx_result* new_result(uint64_t n_samples) {
         result_.reset(new tgx_result());
         result_->device = m_->device;
+        result_->vocab_size = m_->vocab_size;
         result_->n_samples = n_samples;
         return result_.get();
     }
@@ -2049,6 +2052,282 @@ const void* tgx_result_ids_device(const tgx_result* r) { return r ? r->d_ids.get
 const void* tgx_result_offsets_device(const tgx_result* r) { return r ? r->d_offs.get() : nullptr; }
 
 void tgx_result_free(tgx_result* r) { delete r; }
+int tgx_result_device(const tgx_result* r) { return r ? r->device : -1; }
+
+// ---- layouts: padded rows / packed blocks of a result, in caller-owned device memory (layout.hip) ----------------
+
+namespace {
+
+// the calling thread's current device is put back when a layout entry point that had to change it returns
+class DeviceScope {
+public:
+    DeviceScope() { (void)hipGetDevice(&prev_); }
+    ~DeviceScope() {
+        if (prev_ >= 0) (void)hipSetDevice(prev_);
+    }
+    DeviceScope(const DeviceScope&) = delete;
+    DeviceScope& operator=(const DeviceScope&) = delete;
+
+private:
+    int prev_ = -1;
+};
+
+// What a caller gets when it passes no stream of its own: one per device.  It is a BLOCKING stream (hipStreamDefault),
+// so what is queued on it starts after everything queued earlier on the device's null stream, which is where a
+// caller that "has no stream" has its work (torch's default stream is the null stream, handle 0).
+hipStream_t layout_stream(int device) {
+    static std::mutex mu;
+    static hipStream_t streams[64] = {};
+    if (device < 0 || device >= 64) return nullptr;
+    std::lock_guard<std::mutex> lk(mu);
+    if (!streams[device]) {
+        hipStream_t st = nullptr;
+        if (hipStreamCreateWithFlags(&st, hipStreamDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            return nullptr;  // the null stream itself: ordered the same way
+        }
+        streams[device] = st;
+    }
+    return streams[device];
+}
+
+// TGX_OK when every id a layout writes besides the tokens' is below 2^31 (pad always, bos / eos when present)
+tgx_status layout_check_ids(const char* who, uint32_t pad_id, uint32_t bos_id, uint32_t eos_id) {
+    if (pad_id >= 0x80000000u) return fail(TGX_ERR_INVALID, "%s: pad_id %u is not below 2^31", who, pad_id);
+    if (bos_id != TGX_NO_ID && bos_id >= 0x80000000u) return fail(TGX_ERR_INVALID, "%s: bos_id %u is not below 2^31", who, bos_id);
+    if (eos_id != TGX_NO_ID && eos_id >= 0x80000000u) return fail(TGX_ERR_INVALID, "%s: eos_id %u is not below 2^31", who, eos_id);
+    return TGX_OK;
+}
+
+tgx_status layout_check_flags(const char* who, uint32_t flags, uint32_t allowed) {
+    if (flags & ~allowed) return fail(TGX_ERR_INVALID, "%s: unknown flags 0x%x", who, flags & ~allowed);
+    return TGX_OK;
+}
+
+// p (may be NULL when optional) must be device memory of `device`; the current device is `device`
+tgx_status layout_check_dest(const char* who, const char* what, const void* p, int device) {
+    if (!p) return TGX_OK;
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(TGX_ERR_INVALID, "%s: %s is not device memory", who, what);
+    }
+    if (attr.type != hipMemoryTypeDevice) return fail(TGX_ERR_INVALID, "%s: %s is not device memory", who, what);
+    if (attr.device != device) return fail(TGX_ERR_INVALID, "%s: %s is on device %d, the result on device %d", who, what, attr.device, device);
+    return TGX_OK;
+}
+
+tgx_status layout_check_host(const char* who, const uint32_t* ids, const uint64_t* offs, uint64_t n_rows) {
+    if (!offs) return fail(TGX_ERR_INVALID, "%s: offs is NULL", who);
+    if (offs[0] != 0) return fail(TGX_ERR_INVALID, "%s: offs[0] must be 0", who);
+    for (uint64_t i = 0; i < n_rows; i++)
+        if (offs[i + 1] < offs[i]) return fail(TGX_ERR_INVALID, "%s: offsets not monotone at %llu", who, (unsigned long long)i);
+    if (offs[n_rows] && !ids) return fail(TGX_ERR_INVALID, "%s: ids is NULL", who);
+    return TGX_OK;
+}
+
+extern "C++" {  // (this part of the file is inside extern "C")
+template <class T>
+tgx_status layout_pad_host(const tgx::LayoutSeq& seq, const uint32_t* ids, const uint64_t* offs, uint64_t n_rows, uint32_t L, uint32_t flags,
+                           T* out, uint8_t* mask, int32_t* lengths, uint64_t* n_truncated) {
+    // as the kernel: the flat [S, L] output in groups of kLayoutGroup consecutive elements, each walked by pad_group
+    const uint64_t total = n_rows * (uint64_t)L;
+    unsigned long long truncated = 0;
+    for (uint64_t e0 = 0; e0 < total; e0 += tgx::kLayoutGroup) {
+        const uint32_t n_in = total - e0 < tgx::kLayoutGroup ? (uint32_t)(total - e0) : tgx::kLayoutGroup;
+        uint32_t v[tgx::kLayoutGroup] = {0, 0, 0, 0};
+        const uint32_t m = tgx::pad_group(seq, ids, offs, L, flags, e0, n_in, lengths, v, &truncated);
+        for (uint32_t k = 0; k < n_in; k++) {
+            if (v[k] >= 0x80000000u)
+                return fail(TGX_ERR_INVALID, "tgx_layout_pad_host: id %u of row %llu is not below 2^31", v[k], (unsigned long long)((e0 + k) / L));
+            out[e0 + k] = (T)v[k];
+            if (mask) mask[e0 + k] = (uint8_t)(m >> (8 * k));
+        }
+    }
+    if (n_truncated) *n_truncated = truncated;
+    return TGX_OK;
+}
+
+template <class T>
+tgx_status layout_pack_host(const tgx::LayoutSeq& seq, const uint32_t* ids, const uint64_t* offs, uint64_t n_rows, uint64_t n_stream,
+                            uint64_t n_out, T* out, int32_t* doc, int32_t* pos) {
+    // as the kernel: tiles of kPackTile positions, the owners of a tile's ends bound the search inside it, and a
+    // group of four consecutive positions walks on from row to row
+    uint64_t lo = 0, hi = 0;
+    tgx::PackCursor cur;
+    for (uint64_t j = 0; j < n_out; j++) {
+        uint32_t id = seq.pad;
+        int32_t d = -1, q = 0;
+        if (j % tgx::kPackTile == 0 && j < n_stream) {
+            const uint64_t last = j + tgx::kPackTile - 1 < n_stream ? j + tgx::kPackTile - 1 : n_stream - 1;
+            lo = tgx::pack_find_row(offs, seq.extra, 0, n_rows - 1, j);
+            hi = tgx::pack_find_row(offs, seq.extra, 0, n_rows - 1, last);
+        }
+        if (j % 4 == 0) cur = tgx::PackCursor();
+        if (j < n_stream) {
+            const uint64_t i = tgx::pack_advance(cur, offs, seq.extra, lo, hi, j);
+            id = tgx::pack_at(seq, ids, offs, i, j, &q);
+            d = (int32_t)i;
+            if (id >= 0x80000000u) return fail(TGX_ERR_INVALID, "tgx_layout_pack_host: id %u of row %llu is not below 2^31", id, (unsigned long long)i);
+        }
+        out[j] = (T)id;
+        if (doc) doc[j] = d;
+        if (pos) pos[j] = q;
+    }
+    return TGX_OK;
+}
+}  // extern "C++"
+
+}  // namespace
+
+tgx_status tgx_layout_pad_host(const uint32_t* ids, const uint64_t* offs, uint64_t n_rows, uint32_t row_len, uint32_t pad_id,
+                               uint32_t bos_id, uint32_t eos_id, uint32_t flags, void* out_ids, uint8_t* out_mask,
+                               int32_t* out_lengths, uint64_t* n_truncated) {
+    const char* who = "tgx_layout_pad_host";
+    if (!out_ids && n_rows) return fail(TGX_ERR_INVALID, "%s: out_ids is NULL", who);
+    tgx_status st = layout_check_host(who, ids, offs, n_rows);
+    if (st == TGX_OK) st = layout_check_flags(who, flags, TGX_LAYOUT_PAD_LEFT | TGX_LAYOUT_TRUNC_LEFT | TGX_LAYOUT_I64);
+    if (st == TGX_OK) st = layout_check_ids(who, pad_id, bos_id, eos_id);
+    if (st != TGX_OK) return st;
+    const tgx::LayoutSeq seq = tgx::layout_seq(bos_id, eos_id, pad_id);
+    if (row_len < 1 || row_len < seq.extra) return fail(TGX_ERR_INVALID, "%s: row_len %u (needs >= 1 and >= %u for bos / eos)", who, row_len, seq.extra);
+    if (flags & TGX_LAYOUT_I64)
+        return layout_pad_host(seq, ids, offs, n_rows, row_len, flags, static_cast<int64_t*>(out_ids), out_mask, out_lengths, n_truncated);
+    return layout_pad_host(seq, ids, offs, n_rows, row_len, flags, static_cast<int32_t*>(out_ids), out_mask, out_lengths, n_truncated);
+}
+
+tgx_status tgx_layout_pack_host(const uint32_t* ids, const uint64_t* offs, uint64_t n_rows, uint32_t block_len, uint32_t pad_id,
+                                uint32_t bos_id, uint32_t eos_id, uint32_t flags, void* out_ids, int32_t* out_doc,
+                                int32_t* out_pos, uint64_t* n_blocks) {
+    const char* who = "tgx_layout_pack_host";
+    if (!n_blocks) return fail(TGX_ERR_INVALID, "%s: n_blocks is NULL", who);
+    tgx_status st = layout_check_host(who, ids, offs, n_rows);
+    if (st == TGX_OK) st = layout_check_flags(who, flags, TGX_LAYOUT_I64);
+    if (st == TGX_OK) st = layout_check_ids(who, pad_id, bos_id, eos_id);
+    if (st != TGX_OK) return st;
+    if (block_len < 1) return fail(TGX_ERR_INVALID, "%s: block_len is 0", who);
+    if (n_rows >= 0x80000000ull) return fail(TGX_ERR_UNSUPPORTED, "%s: 2^31 rows or more", who);
+    const tgx::LayoutSeq seq = tgx::layout_seq(bos_id, eos_id, pad_id);
+    const uint64_t n_stream = offs[n_rows] + n_rows * seq.extra;
+    const uint64_t nb = (n_stream + block_len - 1) / block_len;
+    *n_blocks = nb;
+    if (nb == 0) return TGX_OK;
+    if (!out_ids) return fail(TGX_ERR_INVALID, "%s: out_ids is NULL", who);
+    if (flags & TGX_LAYOUT_I64)
+        return layout_pack_host(seq, ids, offs, n_rows, n_stream, nb * block_len, static_cast<int64_t*>(out_ids), out_doc, out_pos);
+    return layout_pack_host(seq, ids, offs, n_rows, n_stream, nb * block_len, static_cast<int32_t*>(out_ids), out_doc, out_pos);
+}
+
+tgx_status tgx_result_layout_info(const tgx_result* r, uint32_t bos_id, uint32_t eos_id, uint64_t* max_row_len, uint64_t* n_stream) {
+    if (!r) return fail(TGX_ERR_INVALID, "tgx_result_layout_info: result is NULL");
+    const uint64_t A = (bos_id != TGX_NO_ID ? 1 : 0) + (eos_id != TGX_NO_ID ? 1 : 0);
+    if (n_stream) *n_stream = r->n_tokens + r->n_samples * A;
+    if (!max_row_len) return TGX_OK;
+    *max_row_len = A;
+    if (r->n_samples == 0 || r->n_tokens == 0) return TGX_OK;
+    DeviceScope scope;
+    HIP_TRY(hipSetDevice(r->device));
+    PoolBuf<unsigned long long> d_max;
+    HIP_TRY(d_max.alloc(r->device, sizeof(unsigned long long)));
+    hipStream_t st = layout_stream(r->device);
+    unsigned long long h_max = 0;
+    hipError_t e = hipMemsetAsync(d_max, 0, sizeof(unsigned long long), st);
+    if (e == hipSuccess) e = tgx::launch_layout_max_row(r->d_offs, r->n_samples, d_max, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(&h_max, d_max, sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
+    const hipError_t es = hipStreamSynchronize(st);  // also after a failure: d_max goes back to the pool
+    HIP_TRY(e);
+    HIP_TRY(es);
+    *max_row_len = h_max + A;
+    return TGX_OK;
+}
+
+tgx_status tgx_result_pad_device(const tgx_result* r, uint32_t row_len, uint32_t pad_id, uint32_t bos_id, uint32_t eos_id,
+                                 uint32_t flags, void* stream, void* d_ids, uint8_t* d_mask, int32_t* d_lengths,
+                                 uint64_t* n_truncated) {
+    const char* who = "tgx_result_pad_device";
+    if (!r) return fail(TGX_ERR_INVALID, "%s: result is NULL", who);
+    if (!d_ids && r->n_samples) return fail(TGX_ERR_INVALID, "%s: d_ids is NULL", who);
+    tgx_status st = layout_check_flags(who, flags, TGX_LAYOUT_PAD_LEFT | TGX_LAYOUT_TRUNC_LEFT | TGX_LAYOUT_I64);
+    if (st == TGX_OK) st = layout_check_ids(who, pad_id, bos_id, eos_id);
+    if (st != TGX_OK) return st;
+    if (r->vocab_size > 0x80000000u) return fail(TGX_ERR_INVALID, "%s: the model's ids are not all below 2^31", who);
+    const tgx::LayoutSeq seq = tgx::layout_seq(bos_id, eos_id, pad_id);
+    if (row_len < 1 || row_len < seq.extra) return fail(TGX_ERR_INVALID, "%s: row_len %u (needs >= 1 and >= %u for bos / eos)", who, row_len, seq.extra);
+    if (n_truncated) *n_truncated = 0;
+    if (r->n_samples == 0) return TGX_OK;
+    DeviceScope scope;
+    HIP_TRY(hipSetDevice(r->device));
+    if ((st = layout_check_dest(who, "d_ids", d_ids, r->device)) != TGX_OK) return st;
+    if ((st = layout_check_dest(who, "d_mask", d_mask, r->device)) != TGX_OK) return st;
+    if ((st = layout_check_dest(who, "d_lengths", d_lengths, r->device)) != TGX_OK) return st;
+    hipStream_t hs = stream ? static_cast<hipStream_t>(stream) : layout_stream(r->device);
+    PoolBuf<unsigned long long> d_count;
+    if (n_truncated) HIP_TRY(d_count.alloc(r->device, sizeof(unsigned long long)));
+    tgx::LayoutParams p = {};
+    p.ids = r->d_ids;
+    p.offs = r->d_offs;
+    p.n_rows = r->n_samples;
+    p.len = row_len;
+    p.pad = pad_id;
+    p.bos = bos_id;
+    p.eos = eos_id;
+    p.flags = flags;
+    p.out = d_ids;
+    p.mask = d_mask;
+    p.lengths = d_lengths;
+    p.counter = d_count.get();
+    unsigned long long h_count = 0;
+    hipError_t e = n_truncated ? hipMemsetAsync(d_count, 0, sizeof(unsigned long long), hs) : hipSuccess;
+    if (e == hipSuccess) e = tgx::launch_layout_pad(p, hs);
+    if (e == hipSuccess && n_truncated) e = hipMemcpyAsync(&h_count, d_count, sizeof(unsigned long long), hipMemcpyDeviceToHost, hs);
+    // the stream has reached its end before the result or the destination can change hands (also after a failure)
+    const hipError_t es = hipStreamSynchronize(hs);
+    HIP_TRY(e);
+    HIP_TRY(es);
+    if (n_truncated) *n_truncated = h_count;
+    return TGX_OK;
+}
+
+tgx_status tgx_result_pack_device(const tgx_result* r, uint32_t block_len, uint32_t pad_id, uint32_t bos_id, uint32_t eos_id,
+                                  uint32_t flags, void* stream, void* d_ids, int32_t* d_doc, int32_t* d_pos, uint64_t* n_blocks) {
+    const char* who = "tgx_result_pack_device";
+    if (!r || !n_blocks) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
+    tgx_status st = layout_check_flags(who, flags, TGX_LAYOUT_I64);
+    if (st == TGX_OK) st = layout_check_ids(who, pad_id, bos_id, eos_id);
+    if (st != TGX_OK) return st;
+    if (r->vocab_size > 0x80000000u) return fail(TGX_ERR_INVALID, "%s: the model's ids are not all below 2^31", who);
+    if (block_len < 1) return fail(TGX_ERR_INVALID, "%s: block_len is 0", who);
+    if (r->n_samples >= 0x80000000ull) return fail(TGX_ERR_UNSUPPORTED, "%s: 2^31 rows or more", who);
+    const tgx::LayoutSeq seq = tgx::layout_seq(bos_id, eos_id, pad_id);
+    const uint64_t n_stream = r->n_tokens + r->n_samples * seq.extra;
+    const uint64_t nb = (n_stream + block_len - 1) / block_len;
+    *n_blocks = nb;
+    if (nb == 0) return TGX_OK;
+    if (!d_ids) return fail(TGX_ERR_INVALID, "%s: d_ids is NULL", who);
+    DeviceScope scope;
+    HIP_TRY(hipSetDevice(r->device));
+    if ((st = layout_check_dest(who, "d_ids", d_ids, r->device)) != TGX_OK) return st;
+    if ((st = layout_check_dest(who, "d_doc", d_doc, r->device)) != TGX_OK) return st;
+    if ((st = layout_check_dest(who, "d_pos", d_pos, r->device)) != TGX_OK) return st;
+    hipStream_t hs = stream ? static_cast<hipStream_t>(stream) : layout_stream(r->device);
+    tgx::LayoutParams p = {};
+    p.ids = r->d_ids;
+    p.offs = r->d_offs;
+    p.n_rows = r->n_samples;
+    p.len = block_len;
+    p.pad = pad_id;
+    p.bos = bos_id;
+    p.eos = eos_id;
+    p.flags = flags;
+    p.out = d_ids;
+    p.doc = d_doc;
+    p.pos = d_pos;
+    const hipError_t e = tgx::launch_layout_pack(p, n_stream, nb * block_len, hs);
+    const hipError_t es = hipStreamSynchronize(hs);
+    HIP_TRY(e);
+    HIP_TRY(es);
+    return TGX_OK;
+}
 
 // ---- frequency pass ------------------------------------------------------------
 

@@ -1,0 +1,145 @@
+"""Encoded ids as PyTorch tensors on the device that produced them.
+
+A NativeResult (of encode, sampling or n-best: n-best rows are just rows) holds flat u32 ids and u64 offsets in HBM.
+`to_padded` and `to_packed` lay them out for a model — [S, L] `input_ids` with `attention_mask`, or the documents
+concatenated and cut into [B, L] blocks — with the kernels of csrc/layout.hip, straight into tensors allocated with
+`torch.empty`: the ids never visit the host.
+
+The kernels are queued on `torch.cuda.current_stream(device)`, the stream torch's caching allocator orders the
+tensors' memory on, and the call returns once that stream has reached its end: the tensors can be used by any torch op
+right away, and the result may be freed right away.  The current device is not changed.
+
+torch is imported inside the functions: `import tokengeex_amd` stays torch-free.
+"""
+from __future__ import annotations
+
+from . import _lib
+
+
+def _np_dtype(torch, dtype):
+    import numpy as np
+    if dtype == torch.int64:
+        return np.int64
+    if dtype == torch.int32:
+        return np.int32
+    raise ValueError(f"dtype must be torch.int32 or torch.int64 (got {dtype})")
+
+
+def _check_dest(torch, name: str, t, device, dtype, numel: int) -> int:
+    """A destination must be a contiguous tensor of `dtype` on `device` with room for numel elements -> its data_ptr()."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    if t.device != device:
+        raise ValueError(f"{name} is on {t.device}, the result on {device}")
+    if t.dtype != dtype:
+        raise ValueError(f"{name} has dtype {t.dtype}, expected {dtype}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+    if t.numel() < numel:
+        raise ValueError(f"{name} has room for {t.numel()} elements, {numel} are written")
+    return t.data_ptr() if numel else 0
+
+
+def _device_of(torch, result):
+    if not torch.cuda.is_available():
+        # libtgx.so produced the result, so a GPU is there: torch is looking through a HIP runtime of its own
+        raise _lib.TokenGeeXError("torch sees no GPU although libtgx.so does: two HIP runtimes in one process "
+                                  "(TGX_HIP_RUNTIME=system set? then import torch before tokengeex_amd)", _lib.ERR_DEVICE)
+    return torch.device("cuda", result.device)
+
+
+def pad_into(result: "_lib.NativeResult", input_ids, attention_mask=None, lengths=None, *, row_len: int, pad_id: int,
+             bos_id: int | None = None, eos_id: int | None = None, padding_side: str = "right",
+             truncation_side: str = "right") -> int:
+    """The padded layout written into tensors the caller owns (input_ids: int32 or int64, at least S·row_len elements;
+    attention_mask: uint8, the same count; lengths: int32, S): each must be contiguous and on the result's device, which
+    is checked before anything is launched.  -> number of truncated rows."""
+    import torch
+    dev = _device_of(torch, result)
+    S, L = result.num_samples, int(row_len)
+    if not isinstance(input_ids, torch.Tensor):
+        raise TypeError("input_ids must be a torch.Tensor")
+    flags = _lib.layout_flags(padding_side, truncation_side, _np_dtype(torch, input_ids.dtype))
+    p_ids = _check_dest(torch, "input_ids", input_ids, dev, input_ids.dtype, S * L)
+    p_mask = 0 if attention_mask is None else _check_dest(torch, "attention_mask", attention_mask, dev, torch.uint8, S * L)
+    p_len = 0 if lengths is None else _check_dest(torch, "lengths", lengths, dev, torch.int32, S)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    return result.pad_device(L, pad_id, p_ids, mask_ptr=p_mask, lengths_ptr=p_len, bos_id=bos_id, eos_id=eos_id, flags=flags,
+                             stream=stream)
+
+
+def pack_into(result: "_lib.NativeResult", input_ids, doc_ids=None, positions=None, *, block_len: int, pad_id: int,
+              bos_id: int | None = None, eos_id: int | None = None) -> int:
+    """The packed layout written into tensors the caller owns (input_ids: int32 or int64; doc_ids, positions: int32; each
+    at least n_blocks·block_len elements, n_blocks = ceil(result.layout_info(bos_id, eos_id)[1] / block_len)); checked
+    as in pad_into.  -> n_blocks."""
+    import torch
+    dev = _device_of(torch, result)
+    L = int(block_len)
+    if L < 1:
+        raise _lib.TokenGeeXError("block_len must be at least 1", _lib.ERR_INVALID)
+    if not isinstance(input_ids, torch.Tensor):
+        raise TypeError("input_ids must be a torch.Tensor")
+    flags = _lib.layout_flags(dtype=_np_dtype(torch, input_ids.dtype))
+    n_out = -(-result.layout_info(bos_id, eos_id)[1] // L) * L
+    p_ids = _check_dest(torch, "input_ids", input_ids, dev, input_ids.dtype, n_out)
+    p_doc = 0 if doc_ids is None else _check_dest(torch, "doc_ids", doc_ids, dev, torch.int32, n_out)
+    p_pos = 0 if positions is None else _check_dest(torch, "positions", positions, dev, torch.int32, n_out)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    return result.pack_device(L, pad_id, p_ids, doc_ptr=p_doc, pos_ptr=p_pos, bos_id=bos_id, eos_id=eos_id, flags=flags,
+                              stream=stream)
+
+
+def to_padded(result: "_lib.NativeResult", *, max_length: int | None = None, pad_id: int, bos_id: int | None = None,
+              eos_id: int | None = None, padding_side: str = "right", truncation_side: str = "right", dtype=None,
+              return_lengths: bool = False) -> dict:
+    """-> {"input_ids": [S, L] of dtype (torch.int64 by default, or torch.int32), "attention_mask": [S, L] torch.uint8
+    [, "lengths": [S] torch.int32]} on torch.device("cuda", result.device).
+
+    Every row is [bos] + its tokens + [eos], cut to L (truncation_side: which end of the TOKENS goes; bos and eos
+    stay) and filled up with pad_id on padding_side.  max_length=None: L = the longest row with its bos / eos (at
+    least 1), so nothing is truncated."""
+    import torch
+    dtype = torch.int64 if dtype is None else dtype
+    _np_dtype(torch, dtype)
+    dev = _device_of(torch, result)
+    if max_length is None:
+        L = max(1, result.layout_info(bos_id, eos_id)[0])
+    else:
+        L = int(max_length)
+        if L < 1:
+            raise _lib.TokenGeeXError("max_length must be at least 1", _lib.ERR_INVALID)
+    S = result.num_samples
+    out = {"input_ids": torch.empty((S, L), dtype=dtype, device=dev),
+           "attention_mask": torch.empty((S, L), dtype=torch.uint8, device=dev)}
+    if return_lengths:
+        out["lengths"] = torch.empty((S,), dtype=torch.int32, device=dev)
+    pad_into(result, out["input_ids"], out["attention_mask"], out.get("lengths"), row_len=L, pad_id=pad_id, bos_id=bos_id,
+             eos_id=eos_id, padding_side=padding_side, truncation_side=truncation_side)
+    return out
+
+
+def to_packed(result: "_lib.NativeResult", block_len: int, *, pad_id: int, bos_id: int | None = None, eos_id: int | None = None,
+              dtype=None, return_doc: bool = False, drop_last: bool = False) -> dict:
+    """The LM-pretraining layout -> {"input_ids": [B, block_len] of dtype [, "doc_ids", "positions": [B, block_len]
+    torch.int32]}: the rows' sequences [bos] + tokens + [eos] concatenated and cut into blocks; doc_ids names the row
+    an element came from, positions its index in that row's sequence; the tail of the last block holds pad_id, doc -1,
+    position 0.  drop_last leaves a partly filled last block out (a view of the same memory)."""
+    import torch
+    dtype = torch.int64 if dtype is None else dtype
+    _np_dtype(torch, dtype)
+    dev = _device_of(torch, result)
+    L = int(block_len)
+    if L < 1:
+        raise _lib.TokenGeeXError("block_len must be at least 1", _lib.ERR_INVALID)
+    n_stream = result.layout_info(bos_id, eos_id)[1]
+    B = -(-n_stream // L)
+    out = {"input_ids": torch.empty((B, L), dtype=dtype, device=dev)}
+    if return_doc:
+        out["doc_ids"] = torch.empty((B, L), dtype=torch.int32, device=dev)
+        out["positions"] = torch.empty((B, L), dtype=torch.int32, device=dev)
+    pack_into(result, out["input_ids"], out.get("doc_ids"), out.get("positions"), block_len=L, pad_id=pad_id, bos_id=bos_id,
+              eos_id=eos_id)
+    if drop_last and n_stream % L:
+        out = {k: v[:B - 1] for k, v in out.items()}
+    return out

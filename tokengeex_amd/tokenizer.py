@@ -327,6 +327,104 @@ class Tokenizer:
         finally:
             res.free()
 
+    # -- encoded ids as device tensors for a model (tokengeex_amd/tensors.py over csrc/layout.hip) --
+    def _layout_ids(self, layout: dict) -> dict:
+        """pad / bos / eos of a layout request, given as ids or as special-token strings -> pad_id / bos_id / eos_id."""
+        out = dict(layout)
+        for short in ("pad", "bos", "eos"):
+            if short in out:
+                if short + "_id" in out:
+                    raise TypeError(f"both {short} and {short}_id given")
+                out[short + "_id"] = out.pop(short)
+            v = out.get(short + "_id")
+            if isinstance(v, str):
+                k = self.special_token_to_id(v)
+                if k is None:
+                    raise TokenGeeXError(f"{v!r} is not a special token of this tokenizer", _lib.ERR_INVALID)
+                out[short + "_id"] = k
+        if out.get("pad_id") is None:
+            raise TypeError("pad (or pad_id) is required")
+        return out
+
+    def _ordinary_result(self, flat: np.ndarray, offs: np.ndarray, dropout: float):
+        """The ordinary path of encode_batch_flat up to the device result (processors run, text is not split at special
+        tokens) -> NativeResult, or None for an empty batch."""
+        if not self._native_front():
+            raise TokenGeeXError("a processor without a packed-buffer form", _lib.ERR_UNSUPPORTED)
+        flat = np.ascontiguousarray(flat, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        if offs.shape[0] <= 1:
+            return None
+        if self._processors:
+            flat, offs = self._preprocess_flat(flat, offs)
+        return self._model().encode_batch_flat(flat, offs, dropout, self._seed(dropout))
+
+    def encode_ordinary_batch_padded_flat(self, flat: np.ndarray, offs: np.ndarray, dropout: float = 0.0, **layout) -> dict:
+        """encode_ordinary_batch over a packed batch (uint8 flat, uint64 offsets[S+1]) with the ids laid out on the device
+        as torch tensors -> {"input_ids": [S, L], "attention_mask": [S, L] uint8 [, "lengths"]} on the tokenizer's device
+        (tensors.to_padded: max_length, padding_side, truncation_side, dtype, return_lengths).  pad (required), bos and eos
+        are ids or special-token strings (also spelt pad_id / bos_id / eos_id).  The ids go from the encode kernels to the
+        tensors without visiting the host.
+
+        This is the ORDINARY path: the processors run as in encode_ordinary_batch and the text is not split at special
+        tokens — a special token's string inside a text is encoded as ordinary text.  The special-aware encode_batch
+        assembles its ids on the host (tgx_assemble_ids); a device layout for it is out of scope."""
+        from . import tensors
+        layout = self._layout_ids(layout)
+        res = self._ordinary_result(flat, offs, dropout)
+        if res is None:
+            return self._empty_layout(True, None, layout)
+        try:
+            return tensors.to_padded(res, **layout)
+        finally:
+            res.free()
+
+    def encode_ordinary_batch_packed_flat(self, flat: np.ndarray, offs: np.ndarray, block_len: int, dropout: float = 0.0,
+                                          **layout) -> dict:
+        """As encode_ordinary_batch_padded_flat with the LM-pretraining layout: the samples' sequences [bos] + ids + [eos]
+        concatenated and cut into blocks -> {"input_ids": [B, block_len] [, "doc_ids", "positions"]} (tensors.to_packed:
+        dtype, return_doc, drop_last)."""
+        from . import tensors
+        layout = self._layout_ids(layout)
+        res = self._ordinary_result(flat, offs, dropout)
+        if res is None:
+            return self._empty_layout(False, block_len, layout)
+        try:
+            return tensors.to_packed(res, block_len, **layout)
+        finally:
+            res.free()
+
+    def _empty_layout(self, padded: bool, block_len, layout: dict) -> dict:
+        """What the layouts give for a batch without samples: [0, L] tensors (nothing runs on the device)."""
+        import torch
+        dev = torch.device("cuda", self._device)
+        dtype = layout.get("dtype") or torch.int64
+        if padded:
+            a = (layout.get("bos_id") is not None) + (layout.get("eos_id") is not None)
+            L = max(1, a) if layout.get("max_length") is None else int(layout["max_length"])
+            out = {"input_ids": torch.empty((0, L), dtype=dtype, device=dev),
+                   "attention_mask": torch.empty((0, L), dtype=torch.uint8, device=dev)}
+            if layout.get("return_lengths"):
+                out["lengths"] = torch.empty((0,), dtype=torch.int32, device=dev)
+            return out
+        out = {"input_ids": torch.empty((0, int(block_len)), dtype=dtype, device=dev)}
+        if layout.get("return_doc"):
+            out["doc_ids"] = torch.empty((0, int(block_len)), dtype=torch.int32, device=dev)
+            out["positions"] = torch.empty((0, int(block_len)), dtype=torch.int32, device=dev)
+        return out
+
+    def encode_ordinary_batch_padded(self, texts: list[str], dropout: float = 0.0, **layout) -> dict:
+        """encode_ordinary_batch_padded_flat over a list of strings."""
+        text_b, offs_b = _fast.pack_strs(texts)
+        return self.encode_ordinary_batch_padded_flat(np.frombuffer(text_b, dtype=np.uint8), np.frombuffer(offs_b, dtype=np.uint64),
+                                                      dropout, **layout)
+
+    def encode_ordinary_batch_packed(self, texts: list[str], block_len: int, dropout: float = 0.0, **layout) -> dict:
+        """encode_ordinary_batch_packed_flat over a list of strings."""
+        text_b, offs_b = _fast.pack_strs(texts)
+        return self.encode_ordinary_batch_packed_flat(np.frombuffer(text_b, dtype=np.uint8), np.frombuffer(offs_b, dtype=np.uint64),
+                                                      block_len, dropout, **layout)
+
     # -- subword regularisation: a segmentation drawn from the lattice (csrc/sample.hip) --
     def _sample_seed(self, seed: int | None) -> int:
         if seed is not None:
