@@ -235,6 +235,9 @@ const void *tgx_result_offsets_device(const tgx_result *r);
 void tgx_result_free(tgx_result *r);
 /* The device the result's arrays live on. */
 int tgx_result_device(const tgx_result *r);
+/* Every id of the result is below it: the vocabulary size of the model that wrote it (plus the number of special
+ * tokens for the result of tgx_assemble_result). */
+uint32_t tgx_result_vocab_size(const tgx_result *r);
 
 /* ---- layouts for a model: the ids of a result as padded rows or packed blocks, written on the device ----------
  * A result of encode, sampling or n-best (n-best rows are just rows) laid out in caller-owned DEVICE memory, e.g. a
@@ -290,6 +293,43 @@ tgx_status tgx_layout_pad_host(const uint32_t *ids, const uint64_t *offs, uint64
 tgx_status tgx_layout_pack_host(const uint32_t *ids, const uint64_t *offs, uint64_t n_rows, uint32_t block_len, uint32_t pad_id,
                                 uint32_t bos_id, uint32_t eos_id, uint32_t flags, void *out_ids, int32_t *out_doc,
                                 int32_t *out_pos, uint64_t *n_blocks);
+
+/* ---- assembly: a sample-level result with the special tokens' ids, put together on the device ----------------
+ * The special-aware encode (Tokenizer::encode_batch, src/tokenizer.rs:65-90) splits every sample at its special tokens,
+ * encodes the segments between them and concatenates, per sample, the special tokens' ids and the segments' ids.
+ * tgx_assemble_ids does the last step on host arrays; tgx_assemble_result does it in HBM (csrc/assemble.hip), so that
+ * the ids of a batch with special tokens reach the layouts above without visiting the host.
+ *   A model with base vocabulary size V.
+ *   segs: a result over E rows with T ids and offsets o[0..E] — the encode or sampling result over the non-special
+ *     segments, in order.
+ *   seg_offs u64[S+1]: sample i owns segments [seg_offs[i], seg_offs[i+1]); K = seg_offs[S].
+ *   seg_special i32[K]: a value >= 0 is an index into the special tokens, any negative value means "the next encoded
+ *     segment" (what tgx_split_specials returns).  n_specials: the number of special tokens.
+ * Let enc(k) = seg_special[k] < 0 and r_k = the number of k' < k with enc(k'); r_K must equal E.  Segment k starts at
+ * output position D_k = o[r_k] + (k - r_k); D_K = T + (K - E) = T'.  Then
+ *   out_offs[i] = D_{seg_offs[i]} for i = 0..S, and
+ *   for D_k <= j < D_{k+1}: out_ids[j] = enc(k) ? ids[o[r_k] + (j - D_k)] : V + seg_special[k].
+ * An encoded segment with no ids, and a sample with no segments, own no position.  This is what tgx_assemble_ids
+ * computes.  All element and segment indices are 64-bit.
+ *
+ * tgx_assemble_result runs on the model's stream, uploads the two host arrays, and returns after the stream has
+ * reached its end: *out has n_samples = S rows, T' ids, vocabulary size V + n_specials (what the layouts check ids
+ * against) and lives on the model's device; every entry point that takes a result takes it.  segs is only read and
+ * stays valid; the caller frees both results.  tgx_last_kernel_times reports the stage's kernels.  TGX_ERR_INVALID,
+ * before anything is launched: seg_offs[0] != 0 or seg_offs not non-decreasing; a special index >= n_specials; the
+ * number of encoded segments differs from segs' row count (so an n-best result, which has n_samples · nbest rows, is
+ * refused: combining n-best rows across segments stays with the caller); segs is NULL although E > 0 (segs is NULL
+ * iff E == 0; a result without rows is accepted too); segs is on another device or was written by a model with a
+ * different vocabulary size; V + n_specials > 0xFFFFFFFE.  S = 0 gives TGX_OK and an empty result with offsets [0].
+ * tgx_assemble_host is the host twin over host arrays (ids may be NULL when T = 0, id_offs when n_encoded = 0): the
+ * same checks, plus id_offs[0] = 0 and ascending, and ids_cap >= T'; no device — it walks the kernel's tiles through
+ * the same index arithmetic (csrc/assemble.h).  out_offs u64[S+1]. */
+tgx_status tgx_assemble_result(tgx_model *m, const tgx_result *segs, const uint64_t *seg_offs, const int32_t *seg_special,
+                               uint64_t n_samples, uint32_t n_specials, tgx_result **out);
+tgx_status tgx_assemble_host(const uint32_t *ids, const uint64_t *id_offs, uint64_t n_encoded,
+                             const uint64_t *seg_offs, const int32_t *seg_special, uint64_t n_samples,
+                             uint32_t vocab_size, uint32_t n_specials,
+                             uint32_t *out_ids, uint64_t ids_cap, uint64_t *out_offs);
 
 /* ---- resident corpus: the prune / merge training loops -------------------- */
 /* The reference holds `samples: &[&str]` in RAM across all EM / merge passes

@@ -112,6 +112,9 @@ SYMBOLS = {
     "tgx_result_pack_device": (_i, [_vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _pu64]),
     "tgx_layout_pad_host": (_i, [_vp, _vp, _u64, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _pu64]),
     "tgx_layout_pack_host": (_i, [_vp, _vp, _u64, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _pu64]),
+    "tgx_assemble_result": (_i, [_vp, _vp, _vp, _vp, _u64, _u32, _pvp]),
+    "tgx_result_vocab_size": (_u32, [_vp]),
+    "tgx_assemble_host": (_i, [_vp, _vp, _u64, _vp, _vp, _u64, _u32, _u32, _vp, _u64, _vp]),
 }
 
 
@@ -333,6 +336,26 @@ def assemble_ids(seg_offs: np.ndarray, seg_special: np.ndarray, ids: np.ndarray,
     return out[: int(out_offs[-1])], out_offs
 
 
+def assemble_host(seg_offs: np.ndarray, seg_special: np.ndarray, ids: np.ndarray, id_offs: np.ndarray | None, vocab_size: int,
+                  n_specials: int, ids_cap: int | None = None):
+    """Host twin of NativeModel.assemble (tgx_assemble_host: the kernels' index arithmetic, no device) over the encode
+    result of the non-special segments (ids u32[T], id_offs u64[E+1] or None when no segment is encoded) and the split
+    plan -> (ids u32[T'], offsets u64[S+1]) with special k as vocab_size + k.  ids_cap: room at the destination (default:
+    what is needed)."""
+    seg_offs = np.ascontiguousarray(seg_offs, dtype=np.uint64)
+    seg_special = np.ascontiguousarray(seg_special, dtype=np.int32)
+    ids = np.ascontiguousarray(ids, dtype=np.uint32)
+    id_offs = None if id_offs is None else np.ascontiguousarray(id_offs, dtype=np.uint64)
+    n = seg_offs.shape[0] - 1
+    n_enc = 0 if id_offs is None else id_offs.shape[0] - 1
+    cap = ids.shape[0] + int((seg_special >= 0).sum()) if ids_cap is None else int(ids_cap)
+    out = np.empty(max(1, cap), np.uint32)
+    out_offs = np.zeros(n + 1, np.uint64)
+    check(lib.tgx_assemble_host(ptr(ids) if ids.size else None, ptr(id_offs), n_enc, ptr(seg_offs), ptr(seg_special) if seg_special.size else None,
+                                n, _u32_arg(vocab_size, "vocab_size"), _u32_arg(n_specials, "n_specials"), ptr(out), cap, ptr(out_offs)))
+    return out[: int(out_offs[-1])], out_offs
+
+
 def decode_batch_flat(vocab_flat, vocab_offs, vocab_size: int, special_flat, special_offs, n_specials: int,
                       ids: np.ndarray, id_offs: np.ndarray, include_special: bool):
     """decode_batch over packed ids -> (utf-8 bytes, offsets u64[S+1])."""
@@ -481,6 +504,11 @@ class NativeResult:
     @property
     def num_samples(self) -> int:
         return lib.tgx_result_num_samples(self._h)
+
+    @property
+    def vocab_size(self) -> int:
+        """Every id of the result is below it: the model's vocabulary, plus the special tokens for an assembled result."""
+        return lib.tgx_result_vocab_size(self._h)
 
     def offsets(self) -> np.ndarray:
         out = np.empty(self.num_samples + 1, np.uint64)
@@ -697,6 +725,18 @@ class NativeModel:
         check(lib.tgx_encode_batch_sample(self._h, ptr(flat) if flat.size else None, ptr(offs), n, float(alpha),
                                           seed & (2**64 - 1), ptr(logz) if return_logz else None, C.byref(h)))
         return (NativeResult(h), logz[:n]) if return_logz else NativeResult(h)
+
+    def assemble(self, segs: "NativeResult | None", seg_offs: np.ndarray, seg_special: np.ndarray, n_specials: int) -> NativeResult:
+        """The sample-level result of a batch split at special tokens, put together on the device (tgx_assemble_result,
+        csrc/assemble.hip): segs is the encode or sampling result over the non-special segments (None when every segment
+        is special), seg_offs u64[S+1] / seg_special i32[K] the split plan of split_specials_flat.  Special k gets the id
+        vocab_size + k.  segs stays valid and is the caller's to free."""
+        seg_offs = np.ascontiguousarray(seg_offs, dtype=np.uint64)
+        seg_special = np.ascontiguousarray(seg_special, dtype=np.int32)
+        h = C.c_void_p()
+        check(lib.tgx_assemble_result(self._h, None if segs is None else segs._h, ptr(seg_offs), ptr(seg_special) if seg_special.size else None,
+                                      seg_offs.shape[0] - 1, _u32_arg(n_specials, "n_specials"), C.byref(h)))
+        return NativeResult(h)
 
     def encode_corpus_sample(self, corpus: NativeCorpus, alpha: float, seed: int, return_logz: bool = False):
         """encode_batch_sample_flat over a resident corpus (tgx_encode_corpus_sample)."""

@@ -310,4 +310,24 @@ hipError_t launch_layout_pad(const LayoutParams& p, hipStream_t stream);
 // n_stream = T + S·A positions hold ids, n_out = n_blocks · block_len elements are written
 hipError_t launch_layout_pack(const LayoutParams& p, uint64_t n_stream, uint64_t n_out, hipStream_t stream);
 
+// assemble.hip: a sample-level result from the result over the non-special segments and the split plan (assemble.h has
+// the index arithmetic).  All pointers are device memory.
+struct AssembleParams {
+    const uint32_t* ids;            // u32[T]: the segment-level result (not read when no segment is encoded)
+    const uint64_t* offs;           // u64[E+1]: its offsets (one zero when no segment is encoded)
+    const uint64_t* seg_offs;       // u64[S+1]
+    const int32_t* seg_special;     // i32[K+1] (the last entry belongs to the scan)
+    uint64_t* rank;                 // u64[K+1]: r_k, written by launch_assemble_ranks
+    uint64_t* starts;               // u64[K+1]: D_k, written by assemble_starts_kernel
+    uint64_t n_segs, n_samples;     // K, S
+    uint64_t n_out;                 // T' = T + (K - E)
+    uint32_t vocab_size;            // V: special k gets the id V + k
+    uint32_t* out_ids;              // u32[T'], 16-byte aligned
+    uint64_t* out_offs;             // u64[S+1]
+};
+hipError_t assemble_scan_temp_bytes(uint64_t n_segs, size_t* bytes);
+hipError_t launch_assemble_ranks(int32_t* seg_special, uint64_t* rank, uint64_t n_segs, void* temp, size_t temp_bytes, hipStream_t stream);
+hipError_t launch_assemble_starts(const AssembleParams& p, hipStream_t stream);
+hipError_t launch_assemble_fill(const AssembleParams& p, hipStream_t stream);
+
 }  // namespace tgx

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/tgx.h"
+#include "assemble.h"
 #include "kernels.h"
 #include "layout.h"
 #include "nbest.h"
@@ -2053,6 +2054,7 @@ const void* tgx_result_offsets_device(const tgx_result* r) { return r ? r->d_off
 
 void tgx_result_free(tgx_result* r) { delete r; }
 int tgx_result_device(const tgx_result* r) { return r ? r->device : -1; }
+uint32_t tgx_result_vocab_size(const tgx_result* r) { return r ? r->vocab_size : 0; }
 
 // ---- layouts: padded rows / packed blocks of a result, in caller-owned device memory (layout.hip) ----------------
 
@@ -2327,6 +2329,140 @@ tgx_status tgx_result_pack_device(const tgx_result* r, uint32_t block_len, uint3
     HIP_TRY(e);
     HIP_TRY(es);
     return TGX_OK;
+}
+
+// ---- assembly: a sample-level result with the special tokens' ids, from the segment-level result (assemble.hip) ----
+
+namespace {
+
+// What tgx_assemble_result and tgx_assemble_host check of a split plan before anything runs.  n_rows: the rows of the
+// segment-level result (0 without one).  *n_segs = K.
+tgx_status assemble_check(const char* who, const uint64_t* seg_offs, const int32_t* seg_special, uint64_t n_samples, uint32_t vocab_size,
+                          uint32_t n_specials, bool have_segs, uint64_t n_rows, uint64_t* n_segs) {
+    if (!seg_offs) return fail(TGX_ERR_INVALID, "%s: seg_offs is NULL", who);
+    if (seg_offs[0] != 0) return fail(TGX_ERR_INVALID, "%s: seg_offs[0] must be 0", who);
+    for (uint64_t i = 0; i < n_samples; i++)
+        if (seg_offs[i + 1] < seg_offs[i]) return fail(TGX_ERR_INVALID, "%s: seg_offs not monotone at %llu", who, (unsigned long long)i);
+    const uint64_t K = seg_offs[n_samples];
+    if (K && !seg_special) return fail(TGX_ERR_INVALID, "%s: seg_special is NULL", who);
+    if ((uint64_t)vocab_size + n_specials > 0xFFFFFFFEull)
+        return fail(TGX_ERR_INVALID, "%s: %u tokens and %u special tokens leave no room for their ids", who, vocab_size, n_specials);
+    uint64_t E = 0;
+    for (uint64_t k = 0; k < K; k++) {
+        if (seg_special[k] < 0)
+            E++;
+        else if ((uint32_t)seg_special[k] >= n_specials)
+            return fail(TGX_ERR_INVALID, "%s: segment %llu is special token %d of %u", who, (unsigned long long)k, seg_special[k], n_specials);
+    }
+    if (E && !have_segs) return fail(TGX_ERR_INVALID, "%s: %llu encoded segments and no result over them", who, (unsigned long long)E);
+    if (E != n_rows)
+        return fail(TGX_ERR_INVALID, "%s: %llu encoded segments, the result over them has %llu rows", who, (unsigned long long)E,
+                    (unsigned long long)n_rows);
+    *n_segs = K;
+    return TGX_OK;
+}
+
+}  // namespace
+
+tgx_status tgx_assemble_host(const uint32_t* ids, const uint64_t* id_offs, uint64_t n_encoded, const uint64_t* seg_offs,
+                             const int32_t* seg_special, uint64_t n_samples, uint32_t vocab_size, uint32_t n_specials, uint32_t* out_ids,
+                             uint64_t ids_cap, uint64_t* out_offs) {
+    const char* who = "tgx_assemble_host";
+    if (!out_offs) return fail(TGX_ERR_INVALID, "%s: out_offs is NULL", who);
+    uint64_t K = 0;
+    tgx_status st = assemble_check(who, seg_offs, seg_special, n_samples, vocab_size, n_specials, id_offs != nullptr, n_encoded, &K);
+    if (st != TGX_OK) return st;
+    static const uint64_t kNoOffs[1] = {0};
+    if (!id_offs) id_offs = kNoOffs;
+    if ((st = layout_check_host(who, ids, id_offs, n_encoded)) != TGX_OK) return st;
+    const uint64_t n_out = id_offs[n_encoded] + (K - n_encoded);
+    if (ids_cap < n_out) return fail(TGX_ERR_INVALID, "%s: %llu ids, room for %llu", who, (unsigned long long)n_out, (unsigned long long)ids_cap);
+    if (n_out && !out_ids) return fail(TGX_ERR_INVALID, "%s: out_ids is NULL", who);
+    // as the device: the ranks, the starts with the samples' offsets, then the kernel's tiles and thread slots
+    std::vector<uint64_t> rank(K + 1), starts(K + 1);
+    for (uint64_t k = 0, r = 0; k <= K; k++) {
+        rank[k] = r;
+        if (k < K && seg_special[k] < 0) r++;
+    }
+    for (uint64_t k = 0; k <= K; k++) starts[k] = tgx::assemble_seg_start(id_offs, rank.data(), k);
+    for (uint64_t i = 0; i <= n_samples; i++) out_offs[i] = tgx::assemble_seg_start(id_offs, rank.data(), seg_offs[i]);
+    for (uint64_t t0 = 0; t0 < n_out; t0 += tgx::kAssembleTile) {
+        const uint64_t last = tgx::assemble_tile_last(t0, n_out);
+        const uint64_t lo = tgx::assemble_find_seg(starts.data(), 0, K - 1, t0), hi = tgx::assemble_find_seg(starts.data(), 0, K - 1, last);
+        for (uint64_t e0 = t0; e0 <= last; e0 += tgx::kAssembleGroup) {
+            const uint32_t n_in = last + 1 - e0 < tgx::kAssembleGroup ? (uint32_t)(last + 1 - e0) : tgx::kAssembleGroup;
+            uint32_t v[tgx::kAssembleGroup] = {0, 0, 0, 0};
+            tgx::assemble_group(ids, starts.data(), rank.data(), seg_special, vocab_size, lo, hi, e0, n_in, v);
+            for (uint32_t q = 0; q < n_in; q++) out_ids[e0 + q] = v[q];
+        }
+    }
+    return TGX_OK;
+}
+
+tgx_status tgx_assemble_result(tgx_model* m, const tgx_result* segs, const uint64_t* seg_offs, const int32_t* seg_special,
+                               uint64_t n_samples, uint32_t n_specials, tgx_result** out) {
+    const char* who = "tgx_assemble_result";
+    if (usable_device_count() <= 0) return fail(TGX_ERR_DEVICE, "no usable HIP device (gfx950 required)");
+    if (!m || !out) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
+    *out = nullptr;
+    uint64_t K = 0;
+    const tgx_status cst = assemble_check(who, seg_offs, seg_special, n_samples, m->vocab_size, n_specials, segs != nullptr, segs ? segs->n_samples : 0, &K);
+    if (cst != TGX_OK) return cst;
+    if (segs && segs->device != m->device)
+        return fail(TGX_ERR_INVALID, "%s: the result is on device %d, the model on device %d", who, segs->device, m->device);
+    if (segs && segs->vocab_size != m->vocab_size)
+        return fail(TGX_ERR_INVALID, "%s: the result was written for %u tokens, the model has %u", who, segs->vocab_size, m->vocab_size);
+    const uint64_t S = n_samples, E = segs ? segs->n_samples : 0;
+    const uint64_t n_out = (segs ? segs->n_tokens : 0) + (K - E);
+
+    std::lock_guard<std::mutex> lk(m->mu);
+    HIP_TRY(hipSetDevice(m->device));
+    m->n_timed = 0;
+    Pass pass(m);
+    tgx_result* r = pass.new_result(S);
+    r->vocab_size = m->vocab_size + n_specials;
+    r->n_tokens = n_out;
+    uint64_t *d_seg_offs = nullptr, *d_rank = nullptr, *d_starts = nullptr, *d_zero = nullptr;
+    int32_t* d_special = nullptr;
+    void* d_scan = nullptr;
+    size_t scan_bytes = 0;
+    if (tgx::assemble_scan_temp_bytes(K, &scan_bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan temp-size query failed");
+    if (r->d_offs.alloc(m->device, (size_t)(S + 1) * 8) != hipSuccess || r->d_ids.alloc(m->device, (size_t)n_out * 4 + 256) != hipSuccess ||
+        pass.alloc((size_t)(S + 1) * 8, &d_seg_offs) != hipSuccess || pass.alloc((size_t)(K + 1) * 4, &d_special) != hipSuccess ||
+        pass.alloc((size_t)(K + 1) * 8, &d_rank) != hipSuccess || pass.alloc((size_t)(K + 1) * 8, &d_starts) != hipSuccess ||
+        (E == 0 && pass.alloc(8, &d_zero) != hipSuccess) || pass.alloc(scan_bytes, &d_scan) != hipSuccess)  // (never NULL: that asks the scan for its size)
+        return fail(TGX_ERR_DEVICE, "out of device memory (assembly)");
+    if (hipMemcpyAsync(d_seg_offs, seg_offs, (size_t)(S + 1) * 8, hipMemcpyHostToDevice, m->stream) != hipSuccess ||
+        (K && hipMemcpyAsync(d_special, seg_special, (size_t)K * 4, hipMemcpyHostToDevice, m->stream) != hipSuccess) ||
+        (d_zero && hipMemsetAsync(d_zero, 0, 8, m->stream) != hipSuccess))
+        return fail(TGX_ERR_DEVICE, "upload of the split plan failed: %s", hipGetErrorString(hipGetLastError()));
+
+    tgx::AssembleParams p = {};
+    p.ids = E ? segs->d_ids.get() : nullptr;
+    p.offs = E ? segs->d_offs.get() : d_zero;
+    p.seg_offs = d_seg_offs;
+    p.seg_special = d_special;
+    p.rank = d_rank;
+    p.starts = d_starts;
+    p.n_segs = K;
+    p.n_samples = S;
+    p.n_out = n_out;
+    p.vocab_size = m->vocab_size;
+    p.out_ids = r->d_ids;
+    p.out_offs = r->d_offs;
+    time_begin(m, "assemble_ranks_scan");
+    if (tgx::launch_assemble_ranks(d_special, d_rank, K, d_scan, scan_bytes, m->stream) != hipSuccess)
+        return fail(TGX_ERR_DEVICE, "scan launch failed");
+    time_end(m);
+    time_begin(m, "assemble_starts_kernel");
+    if (tgx::launch_assemble_starts(p, m->stream) != hipSuccess) return fail(TGX_ERR_DEVICE, "assemble_starts_kernel launch failed");
+    time_end(m);
+    time_begin(m, "assemble_fill_kernel");
+    if (tgx::launch_assemble_fill(p, m->stream) != hipSuccess) return fail(TGX_ERR_DEVICE, "assemble_fill_kernel launch failed");
+    time_end(m);
+    if (hipStreamSynchronize(m->stream) != hipSuccess) return fail(TGX_ERR_DEVICE, "assembly failed: %s", hipGetErrorString(hipGetLastError()));
+    *out = pass.release_result();
+    return pass.done();
 }
 
 // ---- frequency pass ------------------------------------------------------------

@@ -367,8 +367,8 @@ class Tokenizer:
         tensors without visiting the host.
 
         This is the ORDINARY path: the processors run as in encode_ordinary_batch and the text is not split at special
-        tokens — a special token's string inside a text is encoded as ordinary text.  The special-aware encode_batch
-        assembles its ids on the host (tgx_assemble_ids); a device layout for it is out of scope."""
+        tokens — a special token's string inside a text is encoded as ordinary text.  encode_batch_padded_flat is the
+        special-aware form: the same layout over encode_batch's ids, put together on the device (encode_batch_result_flat)."""
         from . import tensors
         layout = self._layout_ids(layout)
         res = self._ordinary_result(flat, offs, dropout)
@@ -383,7 +383,7 @@ class Tokenizer:
                                           **layout) -> dict:
         """As encode_ordinary_batch_padded_flat with the LM-pretraining layout: the samples' sequences [bos] + ids + [eos]
         concatenated and cut into blocks -> {"input_ids": [B, block_len] [, "doc_ids", "positions"]} (tensors.to_packed:
-        dtype, return_doc, drop_last)."""
+        dtype, return_doc, drop_last).  The ORDINARY path as well; encode_batch_packed_flat is the special-aware form."""
         from . import tensors
         layout = self._layout_ids(layout)
         res = self._ordinary_result(flat, offs, dropout)
@@ -424,6 +424,108 @@ class Tokenizer:
         text_b, offs_b = _fast.pack_strs(texts)
         return self.encode_ordinary_batch_packed_flat(np.frombuffer(text_b, dtype=np.uint8), np.frombuffer(offs_b, dtype=np.uint64),
                                                       block_len, dropout, **layout)
+
+    # -- the special-aware encode_batch with its ids kept on the device (csrc/assemble.hip) --
+    def _split_segments(self, flat: np.ndarray, offs: np.ndarray):
+        """The front of encode_batch_flat: the batch split at special tokens, the non-special segments packed and
+        processed -> (seg_offs u64[S+1], seg_special i32[K], segments' flat, segments' offsets u64[E+1])."""
+        only_crlf = all(isinstance(p, CrlfProcessor) for p in self._processors)  # then the packing pass does it on the way
+        crlf = only_crlf and len(self._processors) > 0
+        seg_offs, sb, se, ss = _lib.split_specials_flat(flat, offs, [t.encode("utf-8") for t in self._special_tokens])
+        pflat, poffs = _lib.pack_segments(flat, sb, se, ss, crlf)
+        if not only_crlf and poffs.shape[0] > 1:
+            pflat, poffs = self._preprocess_flat(pflat, poffs)
+        return seg_offs, ss, pflat, poffs
+
+    def encode_batch_result_flat(self, flat: np.ndarray, offs: np.ndarray, dropout: float = 0.0):
+        """encode_batch_flat up to a device result: special-token split, processors and encode as there, then the
+        samples' ids — special tokens' included — put together in HBM (NativeModel.assemble) instead of on the host
+        -> NativeResult (ids() / offsets() are encode_batch_flat's; tensors.to_padded / to_packed lay it out), or None
+        for a batch without samples.  The caller frees it."""
+        if not self._native_front():
+            raise TokenGeeXError("encode_batch_result_flat: a processor without a packed-buffer form", _lib.ERR_UNSUPPORTED)
+        if not self._special_tokens:
+            return self._ordinary_result(flat, offs, dropout)
+        flat = np.ascontiguousarray(flat, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        if offs.shape[0] <= 1:
+            return None
+        seg_offs, ss, pflat, poffs = self._split_segments(flat, offs)
+        model = self._model()
+        segs = model.encode_batch_flat(pflat, poffs, dropout, self._seed(dropout)) if poffs.shape[0] > 1 else None
+        try:
+            return model.assemble(segs, seg_offs, ss, len(self._special_tokens))
+        finally:
+            if segs is not None:
+                segs.free()
+
+    def encode_batch_sample_result_flat(self, flat: np.ndarray, offs: np.ndarray, alpha: float, seed: int | None = None,
+                                        return_logz: bool = False):
+        """encode_batch_sample_flat up to a device result, as encode_batch_result_flat -> NativeResult or None
+        [, logz f64[S]: a sample's log Z is the sum over its non-special segments, added up on the host]."""
+        if not self._native_front():
+            raise TokenGeeXError("encode_batch_sample_result_flat: a processor without a packed-buffer form", _lib.ERR_UNSUPPORTED)
+        seed = self._sample_seed(seed)
+        flat = np.ascontiguousarray(flat, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        n = offs.shape[0] - 1
+        if n <= 0:
+            return (None, np.zeros(0, np.float64)) if return_logz else None
+        model = self._model()
+        if not self._special_tokens:
+            if self._processors:
+                flat, offs = self._preprocess_flat(flat, offs)
+            res, logz = model.encode_batch_sample_flat(flat, offs, alpha, seed, return_logz=True)
+            return (res, logz) if return_logz else res
+        seg_offs, ss, pflat, poffs = self._split_segments(flat, offs)
+        segs, seg_logz = None, np.zeros(0, np.float64)
+        if poffs.shape[0] > 1:
+            segs, seg_logz = model.encode_batch_sample_flat(pflat, poffs, alpha, seed, return_logz=True)
+        try:
+            res = model.assemble(segs, seg_offs, ss, len(self._special_tokens))
+        finally:
+            if segs is not None:
+                segs.free()
+        if not return_logz:
+            return res
+        seg_sample = np.repeat(np.arange(n), np.diff(seg_offs.astype(np.int64)))
+        return res, np.bincount(seg_sample[ss < 0], weights=seg_logz, minlength=n).astype(np.float64)
+
+    def encode_batch_padded_flat(self, flat: np.ndarray, offs: np.ndarray, dropout: float = 0.0, **layout) -> dict:
+        """encode_ordinary_batch_padded_flat for the special-aware encode_batch: the text is split at special tokens, which
+        get their own ids, and the ids are put together and laid out on the device (encode_batch_result_flat)."""
+        from . import tensors
+        layout = self._layout_ids(layout)
+        res = self.encode_batch_result_flat(flat, offs, dropout)
+        if res is None:
+            return self._empty_layout(True, None, layout)
+        try:
+            return tensors.to_padded(res, **layout)
+        finally:
+            res.free()
+
+    def encode_batch_packed_flat(self, flat: np.ndarray, offs: np.ndarray, block_len: int, dropout: float = 0.0, **layout) -> dict:
+        """encode_ordinary_batch_packed_flat for the special-aware encode_batch (encode_batch_result_flat)."""
+        from . import tensors
+        layout = self._layout_ids(layout)
+        res = self.encode_batch_result_flat(flat, offs, dropout)
+        if res is None:
+            return self._empty_layout(False, block_len, layout)
+        try:
+            return tensors.to_packed(res, block_len, **layout)
+        finally:
+            res.free()
+
+    def encode_batch_padded(self, texts: list[str], dropout: float = 0.0, **layout) -> dict:
+        """encode_batch_padded_flat over a list of strings."""
+        text_b, offs_b = _fast.pack_strs(texts)
+        return self.encode_batch_padded_flat(np.frombuffer(text_b, dtype=np.uint8), np.frombuffer(offs_b, dtype=np.uint64), dropout, **layout)
+
+    def encode_batch_packed(self, texts: list[str], block_len: int, dropout: float = 0.0, **layout) -> dict:
+        """encode_batch_packed_flat over a list of strings."""
+        text_b, offs_b = _fast.pack_strs(texts)
+        return self.encode_batch_packed_flat(np.frombuffer(text_b, dtype=np.uint8), np.frombuffer(offs_b, dtype=np.uint64), block_len,
+                                             dropout, **layout)
 
     # -- subword regularisation: a segmentation drawn from the lattice (csrc/sample.hip) --
     def _sample_seed(self, seed: int | None) -> int:
