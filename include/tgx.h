@@ -331,6 +331,72 @@ tgx_status tgx_assemble_host(const uint32_t *ids, const uint64_t *id_offs, uint6
                              uint32_t vocab_size, uint32_t n_specials,
                              uint32_t *out_ids, uint64_t ids_cap, uint64_t *out_offs);
 
+/* ---- decode on the device: a result's ids or a padded id tensor to UTF-8 text (csrc/decode.hip) -------------------
+ * What tgx_decode_batch computes, with ids, text and row offsets all in HBM.
+ *
+ * Input: a stream of N elements in S rows.
+ *   Offsets form (tgx_decode_result): a result; u32 ids, row i = elements [ooffs[i], ooffs[i+1]); every element is live.
+ *   Padded form (tgx_decode_padded): caller-owned device memory, S = n_rows rows of L = row_len elements, contiguous and
+ *     row-major, int32_t or (flags: TGX_LAYOUT_I64) int64_t; row i = elements [i·L, (i+1)·L).  Element (i, c) is live iff
+ *     (d_mask == NULL || d_mask[i·L + c] != 0) && (d_lengths == NULL || c < d_lengths[i]) && (skip_id == TGX_NO_ID ||
+ *     element != skip_id); d_mask is u8[S·L], d_lengths i32[S] with a negative length counting as 0.  An element that
+ *     is not live is absent: it is not checked, owns no byte and does not end a run.
+ * Classes: with V the model's vocabulary size, a live element x with 0 <= x < V is a base id, V <= x < V + n_specials
+ *   special token x - V (special_bytes / special_offs: host arrays as in tgx_decode_batch), anything else — negative
+ *   values and values >= 2^32 of int64 rows included — is out of bounds.
+ * Out of bounds: TGX_ERR_TOKEN_ID_OOB and no text.  *bad_sample = the lowest row that holds such an element, *bad_id =
+ *   the first such element of that row (a negative value as its two's complement), tgx_last_error() = "token id {x} is
+ *   out of bounds" with a negative x printed signed.
+ * Row i's text: walk its live elements in order.  A maximal stretch of consecutive base ids is a run; its tokens' bytes
+ *   are concatenated and passed through String::from_utf8_lossy.  A special token ends the run before it and starts a new
+ *   one after it; with include_special its bytes are emitted verbatim, without it nothing is emitted and it still
+ *   separates the two runs.  Tokens of length 0 own no byte and do not end a run; row ends end runs.
+ * from_utf8_lossy replaces every maximal invalid subpart by EF BF BD.  It is applied as a rule local to a byte: inside a
+ *   run, byte p contributes 0, 1 or 3 output bytes, decided from at most 3 bytes before and after p inside the run.  For
+ *   a byte c = s[p] that is no continuation byte (80..BF), sub(p) = (consumed, valid): c < 80: (1, valid); C0, C1,
+ *   F5..FF: (1, invalid); a lead byte needs 2 (C2..DF), 3 (E0..EF) or 4 (F0..F4) bytes, its second byte in 80..BF except
+ *   E0: A0..BF, ED: 80..9F, F0: 90..BF, F4: 80..8F, all later ones in 80..BF; k = the bytes that exist inside the run
+ *   and fit; k == needed: (needed, valid), else (k, invalid).  A non-continuation byte contributes 1 if sub(p) is valid,
+ *   else 3.  A continuation byte at p: q = the nearest non-continuation byte with p - q <= 3 inside the run; if q
+ *   exists and q + consumed(q) > p, p contributes 1 when sub(q) is valid and 0 when not; otherwise p is a stray: 3.
+ *   tgx_text_num_replaced = the replacement characters written.
+ * Stream rule: that of the layouts above.  `stream` is a hipStream_t, NULL the library's blocking stream; the work is
+ *   queued there and the call returns after the stream has reached its end.  d_ids, d_mask and d_lengths are checked with
+ *   hipPointerGetAttributes before anything is queued (device memory on the model's device, else TGX_ERR_INVALID); NULL
+ *   arguments are refused before any device call; the caller's current device is restored.
+ * tgx_decode_result: r on the model's device and tgx_result_vocab_size(r) <= V + n_specials, else TGX_ERR_INVALID; r is
+ *   only read.  S = 0 or N = 0: TGX_OK and a text with offsets all 0.  The model's token bytes go to its device on the
+ *   first decode.  tgx_last_kernel_times is not touched: the kernels run on the caller's stream.
+ * A tgx_text holds the bytes and u64 offsets[S+1] in HBM (pooled buffers) until tgx_text_free.  tgx_corpus_from_text:
+ *   a resident corpus over its rows, by a device-to-device copy (only the S + 1 offsets visit the host).
+ * tgx_decode_rows_host is the host twin over host arrays: the same semantics through the kernels' index arithmetic
+ *   (csrc/decode.h), no device.  id_kind: 0 = u32, 1 = i32, 2 = i64 elements; id_offs != NULL selects the offsets form
+ *   (mask, lengths, skip_id and row_len are then ignored).  *out_text is malloc'd (tgx_free), out_offs u64[n_rows + 1]. */
+typedef struct tgx_text tgx_text;
+tgx_status tgx_decode_result(tgx_model *m, const tgx_result *r, const uint8_t *special_bytes, const uint64_t *special_offs,
+                             uint32_t n_specials, int include_special, void *stream, tgx_text **out,
+                             uint64_t *bad_sample, uint64_t *bad_id);
+tgx_status tgx_decode_padded(tgx_model *m, const void *d_ids, uint64_t n_rows, uint64_t row_len, uint32_t flags,
+                             const uint8_t *d_mask, const int32_t *d_lengths, uint32_t skip_id,
+                             const uint8_t *special_bytes, const uint64_t *special_offs, uint32_t n_specials,
+                             int include_special, void *stream, tgx_text **out, uint64_t *bad_sample, uint64_t *bad_id);
+uint64_t tgx_text_num_rows(const tgx_text *t);
+uint64_t tgx_text_num_bytes(const tgx_text *t);
+uint64_t tgx_text_num_replaced(const tgx_text *t);
+int tgx_text_device(const tgx_text *t);
+tgx_status tgx_text_copy_bytes(const tgx_text *t, uint8_t *dst, uint64_t cap);
+tgx_status tgx_text_copy_offsets(const tgx_text *t, uint64_t *dst, uint64_t cap);
+const void *tgx_text_bytes_device(const tgx_text *t);
+const void *tgx_text_offsets_device(const tgx_text *t);
+void tgx_text_free(tgx_text *t);
+tgx_status tgx_corpus_from_text(const tgx_text *t, tgx_corpus **out);
+tgx_status tgx_decode_rows_host(const uint8_t *vocab_bytes, const uint64_t *vocab_offs, uint32_t vocab_size,
+                                const uint8_t *special_bytes, const uint64_t *special_offs, uint32_t n_specials,
+                                const void *ids, uint32_t id_kind, const uint64_t *id_offs, uint64_t n_rows,
+                                uint64_t row_len, const uint8_t *mask, const int32_t *lengths, uint32_t skip_id,
+                                int include_special, uint8_t **out_text, uint64_t *out_offs, uint64_t *n_replaced,
+                                uint64_t *bad_sample, uint64_t *bad_id);
+
 /* ---- resident corpus: the prune / merge training loops -------------------- */
 /* The reference holds `samples: &[&str]` in RAM across all EM / merge passes
  * (src/prune.rs:23, src/merge.rs:33); here the batch is uploaded once and stays

@@ -115,6 +115,20 @@ SYMBOLS = {
     "tgx_assemble_result": (_i, [_vp, _vp, _vp, _vp, _u64, _u32, _pvp]),
     "tgx_result_vocab_size": (_u32, [_vp]),
     "tgx_assemble_host": (_i, [_vp, _vp, _u64, _vp, _vp, _u64, _u32, _u32, _vp, _u64, _vp]),
+    "tgx_decode_result": (_i, [_vp, _vp, _vp, _vp, _u32, _i, _vp, _pvp, _pu64, _pu64]),
+    "tgx_decode_padded": (_i, [_vp, _vp, _u64, _u64, _u32, _vp, _vp, _u32, _vp, _vp, _u32, _i, _vp, _pvp, _pu64, _pu64]),
+    "tgx_text_num_rows": (_u64, [_vp]),
+    "tgx_text_num_bytes": (_u64, [_vp]),
+    "tgx_text_num_replaced": (_u64, [_vp]),
+    "tgx_text_device": (_i, [_vp]),
+    "tgx_text_copy_bytes": (_i, [_vp, _vp, _u64]),
+    "tgx_text_copy_offsets": (_i, [_vp, _vp, _u64]),
+    "tgx_text_bytes_device": (_vp, [_vp]),
+    "tgx_text_offsets_device": (_vp, [_vp]),
+    "tgx_text_free": (None, [_vp]),
+    "tgx_corpus_from_text": (_i, [_vp, _pvp]),
+    "tgx_decode_rows_host": (_i, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _u32, _vp, _u64, _u64, _vp, _vp, _u32, _i, _pvp, _vp, _pu64,
+                                  _pu64, _pu64]),
 }
 
 
@@ -372,6 +386,56 @@ def decode_batch_flat(vocab_flat, vocab_offs, vocab_size: int, special_flat, spe
     return _take(txt, int(out_offs[-1]), C.c_uint8, np.uint8), out_offs
 
 
+def _raise_decode(st: int, bad_sample: int, bad_id: int):
+    msg = (lib.tgx_last_error() or b"").decode("utf-8", "replace")
+    if st == ERR_TOKEN_ID_OOB:
+        raise TokenGeeXError(msg, st, bad_sample, bad_id, None)
+    raise TokenGeeXError(msg, st)
+
+
+_DECODE_KINDS = {np.dtype(np.uint32): 0, np.dtype(np.int32): 1, np.dtype(np.int64): 2}  # id_kind of tgx_decode_rows_host
+
+
+def decode_rows_host(vocab_flat, vocab_offs, vocab_size: int, special_flat, special_offs, n_specials: int, ids: np.ndarray,
+                     id_offs: np.ndarray | None = None, *, mask: np.ndarray | None = None, lengths: np.ndarray | None = None,
+                     skip_id: int | None = None, include_special: bool = True):
+    """Host twin of NativeModel.decode_result / decode_padded (tgx_decode_rows_host: the kernels' index arithmetic, no
+    device).  Offsets form: ids u32[N] with id_offs u64[S+1].  Padded form (id_offs None): ids [S, L] int32 or int64 with
+    mask u8/bool [S, L], lengths i32[S] and skip_id, each optional -> (utf-8 bytes, offsets u64[S+1], n_replaced)."""
+    vocab_flat = np.ascontiguousarray(vocab_flat, dtype=np.uint8)
+    vocab_offs = np.ascontiguousarray(vocab_offs, dtype=np.uint64)
+    special_flat = np.ascontiguousarray(special_flat, dtype=np.uint8)
+    special_offs = np.ascontiguousarray(special_offs, dtype=np.uint64)
+    if id_offs is not None:
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        id_offs = np.ascontiguousarray(id_offs, dtype=np.uint64)
+        n, L = id_offs.shape[0] - 1, 0
+    else:
+        ids = np.ascontiguousarray(ids)
+        if ids.ndim != 2 or ids.dtype not in (np.dtype(np.int32), np.dtype(np.int64)):
+            raise ValueError("the padded form takes a 2-d int32 or int64 array")
+        n, L = ids.shape
+        if mask is not None:
+            mask = np.ascontiguousarray(mask).astype(np.uint8, copy=False)
+            if mask.shape != ids.shape:
+                raise ValueError("mask and ids differ in shape")
+        if lengths is not None:
+            lengths = np.ascontiguousarray(lengths, dtype=np.int32)
+            if lengths.shape != (n,):
+                raise ValueError("lengths must have one entry per row")
+    out_offs = np.zeros(n + 1, np.uint64)
+    txt, nr, bs, bi = C.c_void_p(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+    st = lib.tgx_decode_rows_host(ptr(vocab_flat) if vocab_flat.size else None, ptr(vocab_offs), _u32_arg(vocab_size, "vocab_size"),
+                                  ptr(special_flat) if special_flat.size else None, ptr(special_offs), _u32_arg(n_specials, "n_specials"),
+                                  ptr(ids) if ids.size else None, _DECODE_KINDS[ids.dtype], None if id_offs is None else ptr(id_offs), n, L,
+                                  None if mask is None or not mask.size else ptr(mask), None if lengths is None or not n else ptr(lengths),
+                                  _id_or_none(skip_id), 1 if include_special else 0, C.byref(txt), ptr(out_offs), C.byref(nr), C.byref(bs),
+                                  C.byref(bi))
+    if st != OK:
+        _raise_decode(st, bs.value, bi.value)
+    return _take(txt, int(out_offs[-1]), C.c_uint8, np.uint8), out_offs, nr.value
+
+
 def substring_df(flat: np.ndarray, part_begin: np.ndarray, part_end: np.ndarray, part_sample: np.ndarray,
                  max_token_length: int, insert_probability: float = 1.0, seed: int = 0, device: int = 0, with_collisions: bool = False,
                  part_origin=None):
@@ -576,6 +640,67 @@ class NativeResult:
         return layout_pack_host(self.ids(), self.offsets(), block_len, pad_id, **kw)
 
 
+class NativeText:
+    """Owns a tgx_text: the UTF-8 bytes and u64 offsets[S+1] of S decoded rows, resident in HBM (csrc/decode.hip)."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    def __del__(self):
+        self.free()
+
+    def free(self):
+        if getattr(self, "_h", None):
+            lib.tgx_text_free(self._h)
+            self._h = None
+
+    @property
+    def num_rows(self) -> int:
+        return lib.tgx_text_num_rows(self._h)
+
+    @property
+    def num_bytes(self) -> int:
+        return lib.tgx_text_num_bytes(self._h)
+
+    @property
+    def num_replaced(self) -> int:
+        """Replacement characters String::from_utf8_lossy wrote."""
+        return lib.tgx_text_num_replaced(self._h)
+
+    @property
+    def device(self) -> int:
+        return lib.tgx_text_device(self._h)
+
+    def bytes(self) -> np.ndarray:
+        n = self.num_bytes
+        out = np.empty(n, np.uint8)
+        if n:
+            check(lib.tgx_text_copy_bytes(self._h, ptr(out), n))
+        return out
+
+    def offsets(self) -> np.ndarray:
+        out = np.empty(self.num_rows + 1, np.uint64)
+        check(lib.tgx_text_copy_offsets(self._h, ptr(out), out.size))
+        return out
+
+    @property
+    def bytes_ptr(self) -> int:
+        return lib.tgx_text_bytes_device(self._h) or 0
+
+    @property
+    def offsets_ptr(self) -> int:
+        return lib.tgx_text_offsets_device(self._h) or 0
+
+    def to_corpus(self) -> "NativeCorpus":
+        """A resident corpus over the rows (tgx_corpus_from_text: a device-to-device copy; the text stays valid)."""
+        h = C.c_void_p()
+        check(lib.tgx_corpus_from_text(self._h, C.byref(h)))
+        c = NativeCorpus.__new__(NativeCorpus)
+        c._h = h
+        c.device = self.device
+        return c
+
+
 class NativeCorpus:
     """Owns a tgx_corpus: a packed batch resident in HBM across passes."""
 
@@ -737,6 +862,41 @@ class NativeModel:
         check(lib.tgx_assemble_result(self._h, None if segs is None else segs._h, ptr(seg_offs), ptr(seg_special) if seg_special.size else None,
                                       seg_offs.shape[0] - 1, _u32_arg(n_specials, "n_specials"), C.byref(h)))
         return NativeResult(h)
+
+    # -- decode on the device (include/tgx.h: tgx_decode_result / tgx_decode_padded; csrc/decode.hip) --
+    @staticmethod
+    def _specials(special_flat, special_offs):
+        sf = np.ascontiguousarray(special_flat, dtype=np.uint8)
+        so = np.ascontiguousarray(special_offs, dtype=np.uint64)
+        return sf, so, so.shape[0] - 1
+
+    def decode_result(self, result: NativeResult, special_flat, special_offs, include_special: bool, stream: int = 0) -> "NativeText":
+        """The rows of a result on this model's device decoded to UTF-8 text in HBM: ids >= vocab_size are the special tokens
+        (special_flat / special_offs: their bytes in the batch format), every run of base ids between them goes through
+        String::from_utf8_lossy on its own.  Queued on `stream` (a hipStream_t as an integer; 0: the library's blocking
+        stream); returns when the stream has reached its end.  The result is only read."""
+        sf, so, n = self._specials(special_flat, special_offs)
+        h, bs, bi = C.c_void_p(), C.c_uint64(), C.c_uint64()
+        st = lib.tgx_decode_result(self._h, result._h, ptr(sf) if sf.size else None, ptr(so), n, 1 if include_special else 0,
+                                   stream or None, C.byref(h), C.byref(bs), C.byref(bi))
+        if st != OK:
+            _raise_decode(st, bs.value, bi.value)
+        return NativeText(h)
+
+    def decode_padded(self, ids_ptr: int, n_rows: int, row_len: int, i64: bool, *, mask_ptr: int = 0, lengths_ptr: int = 0,
+                      skip_id: int | None = None, special_flat=(), special_offs=(0,), include_special: bool = True,
+                      stream: int = 0) -> "NativeText":
+        """[n_rows, row_len] ids in device memory (int32, or int64 with i64; raw integer pointers) decoded as decode_result
+        does.  An element is live iff its mask byte (u8 [n_rows, row_len]) is non-zero, its column is below its row's
+        length (i32[n_rows]) and it differs from skip_id — each test only when given; other elements are absent."""
+        sf, so, n = self._specials(special_flat, special_offs)
+        h, bs, bi = C.c_void_p(), C.c_uint64(), C.c_uint64()
+        st = lib.tgx_decode_padded(self._h, ids_ptr or None, int(n_rows), int(row_len), LAYOUT_I64 if i64 else 0, mask_ptr or None,
+                                   lengths_ptr or None, _id_or_none(skip_id), ptr(sf) if sf.size else None, ptr(so), n,
+                                   1 if include_special else 0, stream or None, C.byref(h), C.byref(bs), C.byref(bi))
+        if st != OK:
+            _raise_decode(st, bs.value, bi.value)
+        return NativeText(h)
 
     def encode_corpus_sample(self, corpus: NativeCorpus, alpha: float, seed: int, return_logz: bool = False):
         """encode_batch_sample_flat over a resident corpus (tgx_encode_corpus_sample)."""

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "decode.h"
+
 namespace tgx {
 
 struct EncodeParams {
@@ -329,5 +331,33 @@ hipError_t assemble_scan_temp_bytes(uint64_t n_segs, size_t* bytes);
 hipError_t launch_assemble_ranks(int32_t* seg_special, uint64_t* rank, uint64_t n_segs, void* temp, size_t temp_bytes, hipStream_t stream);
 hipError_t launch_assemble_starts(const AssembleParams& p, hipStream_t stream);
 hipError_t launch_assemble_fill(const AssembleParams& p, hipStream_t stream);
+
+// decode.hip: ids decoded to UTF-8 text (decode.h has the index arithmetic).  All pointers are device memory.
+struct DecodeParams {
+    DecodeTables tab;
+    DecodeSrc src;
+    uint32_t* meta;                 // u32[N+1]: raw length and class per element (the last entry belongs to the scan)
+    uint64_t* starts;               // u64[N+1]: B, the elements' raw byte starts
+    uint64_t* specials;             // u64[N+1]: X, live specials before an element; NULL when the stream has none
+    unsigned long long* bad_pos;    // lowest stream position of an out-of-bounds element (~0 set by the caller: none)
+    unsigned long long* n_replaced; // replacement characters (zeroed by the caller)
+    unsigned long long* n_specials_live;  // live special tokens (zeroed by the caller)
+    uint64_t n_raw;                 // B[N]
+    uint8_t* raw;                   // u8[n_raw rounded up to whole slots, + 16], 16-byte aligned
+    uint32_t* flags;                // u32[G]: run starts and verbatim bytes per slot of 16 raw bytes, G = ceil(n_raw / 16)
+    uint32_t* codes;                // u32[G+1]: output bytes per raw byte (the last entry belongs to the scan)
+    uint64_t* row_offs;             // u64[S+1]: the rows' raw starts, then their final offsets
+    uint64_t* gpos;                 // u64[G+1]: the slots' output positions (only after a replacement)
+    uint8_t* out;                   // the final bytes (only after a replacement)
+};
+hipError_t decode_scan_temp_bytes(uint64_t n, size_t* bytes);
+hipError_t launch_decode_meta(const DecodeParams& p, void* temp, size_t temp_bytes, hipStream_t stream);      // meta and B
+hipError_t launch_decode_specials(const DecodeParams& p, void* temp, size_t temp_bytes, hipStream_t stream);  // X
+hipError_t launch_decode_fill(const DecodeParams& p, hipStream_t stream);
+hipError_t launch_decode_rows(const DecodeParams& p, hipStream_t stream);   // after the fill
+hipError_t launch_decode_utf8(const DecodeParams& p, hipStream_t stream);   // after the rows
+hipError_t decode_expand_temp_bytes(uint64_t n_groups, size_t* bytes);
+hipError_t launch_decode_positions(const DecodeParams& p, void* temp, size_t temp_bytes, hipStream_t stream);
+hipError_t launch_decode_expand(const DecodeParams& p, hipStream_t stream);  // the bytes and the rows' final offsets
 
 }  // namespace tgx

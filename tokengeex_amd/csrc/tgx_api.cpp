@@ -24,6 +24,7 @@
 
 #include "../../include/tgx.h"
 #include "assemble.h"
+#include "decode.h"
 #include "kernels.h"
 #include "layout.h"
 #include "nbest.h"
@@ -304,6 +305,12 @@ struct tgx_model {
     uint32_t n_tok7 = 0, root_base7 = 0;
     bool trie8t_tried = false, have_trie8t = false;
     uint64_t last_estep_redo = 0;      // stretches the last fused E-step left to the chained kernels
+    // decode (decode.hip): the tokens' lengths, 16-byte slots and packed bytes, uploaded at the first decode (ensure_decode_tables)
+    uint8_t* d_dec_len = nullptr;
+    void* d_dec_slots = nullptr;
+    uint8_t* d_dec_bytes = nullptr;
+    uint64_t* d_dec_offs = nullptr;
+    bool decode_tables_ready = false;
     int estep_blocks_per_cu = 0;
     KernelTime timed[kMaxTimed] = {};
     int n_timed = 0;
@@ -1490,6 +1497,10 @@ void tgx_model_destroy(tgx_model* m) {
     if (m->d_wvalues) (void)hipFree(m->d_wvalues);
     if (m->d_trie8t) (void)hipFree(m->d_trie8t);
     if (m->d_wtab) (void)hipFree(m->d_wtab);
+    if (m->d_dec_len) (void)hipFree(m->d_dec_len);
+    if (m->d_dec_slots) (void)hipFree(m->d_dec_slots);
+    if (m->d_dec_bytes) (void)hipFree(m->d_dec_bytes);
+    if (m->d_dec_offs) (void)hipFree(m->d_dec_offs);
     if (m->stream2) (void)hipStreamDestroy(m->stream2);
     if (m->ev_fork) (void)hipEventDestroy(m->ev_fork);
     if (m->ev_join) (void)hipEventDestroy(m->ev_join);
@@ -1631,11 +1642,13 @@ static hipError_t copy_sync(void* dst, const void* src, size_t bytes, hipMemcpyK
     return hipStreamSynchronize(st);
 }
 
-tgx_status tgx_corpus_upload(int device, const uint8_t* text, const uint64_t* offs,
-                             uint64_t n_samples, tgx_corpus** out) {
-    if (!out) return fail(TGX_ERR_INVALID, "tgx_corpus_upload: out is NULL");
+// A resident corpus over `text` (host memory, or memory of `device` when text_on_device) and host offsets: what
+// tgx_corpus_upload and tgx_corpus_from_text share, so the two build the same corpus.
+static tgx_status corpus_create(const char* who, int device, const uint8_t* text, bool text_on_device, const uint64_t* offs,
+                                uint64_t n_samples, tgx_corpus** out) {
+    if (!out) return fail(TGX_ERR_INVALID, "%s: out is NULL", who);
     *out = nullptr;
-    if (n_samples && !offs) return fail(TGX_ERR_INVALID, "tgx_corpus_upload: offs is NULL");
+    if (n_samples && !offs) return fail(TGX_ERR_INVALID, "%s: offs is NULL", who);
     int ndev = usable_device_count();
     if (ndev <= 0) return fail(TGX_ERR_DEVICE, "no usable HIP device (gfx950 required)");
     if (device < 0 || device >= ndev)
@@ -1654,7 +1667,7 @@ tgx_status tgx_corpus_upload(int device, const uint8_t* text, const uint64_t* of
     c->n_bytes = n_samples ? offs[n_samples] - base : 0;
     c->h_offs.resize(n_samples + 1);
     for (uint64_t i = 0; i <= n_samples; i++) c->h_offs[i] = n_samples ? offs[i] - base : 0;
-    if (n_samples && c->n_bytes && !text) return fail(TGX_ERR_INVALID, "tgx_corpus_upload: text is NULL");
+    if (n_samples && c->n_bytes && !text) return fail(TGX_ERR_INVALID, "%s: text is NULL", who);
     // longest first: the tail of a pass is then made of short samples
     std::vector<uint32_t> order(n_samples);
     std::iota(order.begin(), order.end(), 0u);
@@ -1677,12 +1690,17 @@ tgx_status tgx_corpus_upload(int device, const uint8_t* text, const uint64_t* of
     HIP_TRY(hipMemset(c->d_text_alloc, 0, 256));
     HIP_TRY(c->d_offs.alloc(device, (size_t)(n_samples + 1) * 8));
     HIP_TRY(c->d_order.alloc(device, (size_t)n_samples * 4 + 4));
-    if (c->n_bytes) HIP_TRY(copy_sync(c->d_text, text + base, c->n_bytes, hipMemcpyHostToDevice, device));
+    if (c->n_bytes) HIP_TRY(copy_sync(c->d_text, text + base, c->n_bytes, text_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, device));
     HIP_TRY(hipMemset(c->d_text + c->n_bytes, 0, 256));
     HIP_TRY(hipMemcpy(c->d_offs, c->h_offs.data(), (n_samples + 1) * 8, hipMemcpyHostToDevice));
     if (n_samples) HIP_TRY(hipMemcpy(c->d_order, order.data(), n_samples * 4, hipMemcpyHostToDevice));
     *out = c.release();
     return TGX_OK;
+}
+
+tgx_status tgx_corpus_upload(int device, const uint8_t* text, const uint64_t* offs,
+                             uint64_t n_samples, tgx_corpus** out) {
+    return corpus_create("tgx_corpus_upload", device, text, false, offs, n_samples, out);
 }
 
 // (every pass has finished with the corpus's buffers when it returns: they go straight back to the pool)
@@ -2463,6 +2481,460 @@ tgx_status tgx_assemble_result(tgx_model* m, const tgx_result* segs, const uint6
     if (hipStreamSynchronize(m->stream) != hipSuccess) return fail(TGX_ERR_DEVICE, "assembly failed: %s", hipGetErrorString(hipGetLastError()));
     *out = pass.release_result();
     return pass.done();
+}
+
+// ---- decode: ids in HBM to UTF-8 text in HBM (decode.hip; decode.h has the index arithmetic) ----------------------
+
+struct tgx_text {
+    int device = 0;
+    uint64_t n_rows = 0, n_bytes = 0, n_replaced = 0;
+    PoolBuf<uint8_t> d_bytes;
+    PoolBuf<uint64_t> d_offs;
+};
+
+namespace {
+
+// lengths and 16-byte slots of a vocabulary's tokens: what the kernels (device copies) and the host twin read
+tgx_status decode_build_tables(const char* who, const uint8_t* bytes, const uint64_t* offs, uint32_t V, std::vector<uint8_t>* len,
+                               std::vector<tgx::DecodeSlot>* slots) {
+    len->assign(V, 0);
+    slots->assign(V, tgx::DecodeSlot{0, 0});
+    for (uint32_t i = 0; i < V; i++) {
+        if (offs[i + 1] < offs[i]) return fail(TGX_ERR_INVALID, "%s: vocabulary offsets not monotone at %u", who, i);
+        const uint64_t n = offs[i + 1] - offs[i];
+        if (n > TGX_MAX_TOKEN_LEN) return fail(TGX_ERR_UNSUPPORTED, "%s: token of %llu bytes exceeds TGX_MAX_TOKEN_LEN (%d)", who, (unsigned long long)n, TGX_MAX_TOKEN_LEN);
+        (*len)[i] = (uint8_t)n;
+        if (n > tgx::kDecodeSlotLen) continue;
+        tgx::DecodeSlot& sl = (*slots)[i];
+        for (uint64_t k = 0; k < n; k++) (k < 8 ? sl.lo : sl.hi) |= (uint64_t)bytes[offs[i] + k] << (8 * (k & 7));
+    }
+    return TGX_OK;
+}
+
+tgx_status decode_check_specials(const char* who, uint32_t vocab_size, const uint8_t* special_bytes, const uint64_t* special_offs, uint32_t n_specials) {
+    if (n_specials && !special_offs) return fail(TGX_ERR_INVALID, "%s: special_offs is NULL", who);
+    if ((uint64_t)vocab_size + n_specials > 0xFFFFFFFEull)
+        return fail(TGX_ERR_INVALID, "%s: %u tokens and %u special tokens leave no room for their ids", who, vocab_size, n_specials);
+    for (uint32_t k = 0; k < n_specials; k++) {
+        if (special_offs[k + 1] < special_offs[k]) return fail(TGX_ERR_INVALID, "%s: special_offs not monotone at %u", who, k);
+        if (special_offs[k + 1] - special_offs[k] >= 0x80000000ull) return fail(TGX_ERR_UNSUPPORTED, "%s: special token %u is 2 GiB or longer", who, k);
+    }
+    if (n_specials && special_offs[n_specials] > special_offs[0] && !special_bytes) return fail(TGX_ERR_INVALID, "%s: special_bytes is NULL", who);
+    return TGX_OK;
+}
+
+tgx_status decode_oob(uint32_t kind, int64_t x, uint64_t row, uint64_t* bad_sample, uint64_t* bad_id) {
+    if (bad_sample) *bad_sample = row;
+    if (bad_id) *bad_id = (uint64_t)x;
+    g_err_sample = row;
+    g_err_pos = (uint64_t)x;
+    if (kind == tgx::kDecodeU32) return fail(TGX_ERR_TOKEN_ID_OOB, "token id %llu is out of bounds", (unsigned long long)x);
+    return fail(TGX_ERR_TOKEN_ID_OOB, "token id %lld is out of bounds", (long long)x);
+}
+
+uint64_t decode_elem_bytes(uint32_t kind) { return kind == tgx::kDecodeI64 ? 8 : 4; }
+
+// the model's token tables on its device, once (under m->mu)
+tgx_status ensure_decode_tables(tgx_model* m) {
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (m->decode_tables_ready) return TGX_OK;
+    const uint32_t V = m->vocab_size;
+    std::vector<uint8_t> len;
+    std::vector<tgx::DecodeSlot> slots;
+    const tgx_status st = decode_build_tables("decode", m->vocab_bytes.data(), m->vocab_offs.data(), V, &len, &slots);
+    if (st != TGX_OK) return st;
+    const size_t nb = m->vocab_bytes.size();
+    if (!m->d_dec_len) HIP_TRY(hipMalloc((void**)&m->d_dec_len, (size_t)V + 16));
+    if (!m->d_dec_slots) HIP_TRY(hipMalloc(&m->d_dec_slots, ((size_t)V + 1) * sizeof(tgx::DecodeSlot)));
+    if (!m->d_dec_bytes) HIP_TRY(hipMalloc((void**)&m->d_dec_bytes, nb + 16));
+    if (!m->d_dec_offs) HIP_TRY(hipMalloc((void**)&m->d_dec_offs, ((size_t)V + 1) * 8));
+    if (V) HIP_TRY(hipMemcpy(m->d_dec_len, len.data(), V, hipMemcpyHostToDevice));
+    if (V) HIP_TRY(hipMemcpy(m->d_dec_slots, slots.data(), (size_t)V * sizeof(tgx::DecodeSlot), hipMemcpyHostToDevice));
+    if (nb) HIP_TRY(hipMemcpy(m->d_dec_bytes, m->vocab_bytes.data(), nb, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(m->d_dec_offs, m->vocab_offs.data(), ((size_t)V + 1) * 8, hipMemcpyHostToDevice));
+    m->decode_tables_ready = true;
+    return TGX_OK;
+}
+
+// p (may be NULL when optional) must be device memory of `device`; the current device is `device`
+tgx_status decode_check_src(const char* who, const char* what, const void* p, int device) {
+    if (!p) return TGX_OK;
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(TGX_ERR_INVALID, "%s: %s is not device memory", who, what);
+    }
+    if (attr.type != hipMemoryTypeDevice) return fail(TGX_ERR_INVALID, "%s: %s is not device memory", who, what);
+    if (attr.device != device) return fail(TGX_ERR_INVALID, "%s: %s is on device %d, the model on device %d", who, what, attr.device, device);
+    return TGX_OK;
+}
+
+// the buffers of one decode; they go back to the pool after the stream has reached its end (StreamEnd below them)
+struct DecodeWork {
+    PoolBuf<uint32_t> meta, flags, codes;
+    PoolBuf<uint64_t> starts, specials, gpos, sp_offs;
+    PoolBuf<uint8_t> sp_bytes, raw;
+    PoolBuf<void> scan, scan2;
+    PoolBuf<unsigned long long> ctrl;  // [0]: lowest out-of-bounds position, [1]: replacement characters, [2]: live specials
+    std::unique_ptr<tgx_text> text;
+};
+class StreamEnd {
+public:
+    explicit StreamEnd(hipStream_t s) : s_(s) {}
+    ~StreamEnd() {
+        if (!ok_) (void)hipStreamSynchronize(s_);
+    }
+    void done() { ok_ = true; }
+
+private:
+    hipStream_t s_;
+    bool ok_ = false;
+};
+
+// The decode of src (device pointers) on stream hs of the model's device, which is current.  row_offs_dev: the offsets
+// form's offsets, read back only to name the row of an out-of-bounds id.
+tgx_status decode_device(tgx_model* m, tgx::DecodeSrc src, const uint8_t* special_bytes, const uint64_t* special_offs, uint32_t n_specials,
+                         int include_special, hipStream_t hs, tgx_text** out, uint64_t* bad_sample, uint64_t* bad_id) {
+    const int dev = m->device;
+    const uint64_t S = src.n_rows, N = src.n;
+    DecodeWork w;
+    StreamEnd end(hs);  // destroyed before w: a failed call's queued work is over before its buffers change hands
+    w.text.reset(new tgx_text());
+    tgx_text* t = w.text.get();
+    t->device = dev;
+    t->n_rows = S;
+    HIP_TRY(t->d_offs.alloc(dev, (size_t)(S + 1) * 8));
+    if (S == 0 || N == 0) {
+        HIP_TRY(t->d_bytes.alloc(dev, 0));
+        HIP_TRY(hipMemsetAsync(t->d_offs, 0, (size_t)(S + 1) * 8, hs));
+        HIP_TRY(hipStreamSynchronize(hs));
+        end.done();
+        *out = w.text.release();
+        return TGX_OK;
+    }
+    tgx_status st = ensure_decode_tables(m);
+    if (st != TGX_OK) return st;
+
+    const uint64_t sp_total = n_specials ? special_offs[n_specials] - special_offs[0] : 0;
+    size_t scan_bytes = 0;
+    if (tgx::decode_scan_temp_bytes(N, &scan_bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan temp-size query failed");
+    HIP_TRY(w.meta.alloc(dev, (size_t)(N + 1) * 4));
+    HIP_TRY(w.starts.alloc(dev, (size_t)(N + 1) * 8));
+    HIP_TRY(w.scan.alloc(dev, scan_bytes));  // (never NULL: that asks the scan for its size)
+    HIP_TRY(w.ctrl.alloc(dev, 24));
+    HIP_TRY(w.sp_offs.alloc(dev, ((size_t)n_specials + 1) * 8));
+    HIP_TRY(w.sp_bytes.alloc(dev, (size_t)sp_total + 16));
+    std::vector<uint64_t> sp_offs0((size_t)n_specials + 1, 0);  // from 0; alive until the stream has taken them
+    for (uint32_t k = 0; k <= n_specials && n_specials; k++) sp_offs0[k] = special_offs[k] - special_offs[0];
+    HIP_TRY(hipMemcpyAsync(w.sp_offs, sp_offs0.data(), sp_offs0.size() * 8, hipMemcpyHostToDevice, hs));
+    if (sp_total) HIP_TRY(hipMemcpyAsync(w.sp_bytes, special_bytes + special_offs[0], sp_total, hipMemcpyHostToDevice, hs));
+    HIP_TRY(hipMemsetAsync(w.ctrl, 0xFF, 8, hs));
+    HIP_TRY(hipMemsetAsync(w.ctrl.get() + 1, 0, 16, hs));
+
+    tgx::DecodeParams p = {};
+    p.tab.tok_len = m->d_dec_len;
+    p.tab.slots = static_cast<const tgx::DecodeSlot*>(m->d_dec_slots);
+    p.tab.bytes = m->d_dec_bytes;
+    p.tab.offs = m->d_dec_offs;
+    p.tab.sp_bytes = w.sp_bytes;
+    p.tab.sp_offs = w.sp_offs;
+    p.tab.vocab_size = m->vocab_size;
+    p.tab.n_specials = n_specials;
+    p.tab.include_special = include_special ? 1 : 0;
+    p.src = src;
+    p.meta = w.meta;
+    p.starts = w.starts;
+    p.bad_pos = w.ctrl;
+    p.n_replaced = w.ctrl.get() + 1;
+    p.n_specials_live = w.ctrl.get() + 2;
+    p.row_offs = t->d_offs;
+    HIP_TRY(tgx::launch_decode_meta(p, w.scan, scan_bytes, hs));
+    unsigned long long h_bad = ~0ull, h_raw = 0, h_replaced = 0, h_final = 0, h_specials = 0;
+    HIP_TRY(hipMemcpyAsync(&h_bad, w.ctrl, 8, hipMemcpyDeviceToHost, hs));
+    HIP_TRY(hipMemcpyAsync(&h_specials, w.ctrl.get() + 2, 8, hipMemcpyDeviceToHost, hs));
+    HIP_TRY(hipMemcpyAsync(&h_raw, w.starts.get() + N, 8, hipMemcpyDeviceToHost, hs));
+    HIP_TRY(hipStreamSynchronize(hs));
+    if (h_bad != ~0ull) {
+        int64_t x = 0;
+        union { int64_t i64; int32_t i32; uint32_t u32; } v = {};
+        HIP_TRY(hipMemcpyAsync(&v, static_cast<const char*>(src.ids) + h_bad * decode_elem_bytes(src.kind), decode_elem_bytes(src.kind), hipMemcpyDeviceToHost, hs));
+        std::vector<uint64_t> h_offs;
+        if (src.offs) {
+            h_offs.resize(S + 1);
+            HIP_TRY(hipMemcpyAsync(h_offs.data(), src.offs, (size_t)(S + 1) * 8, hipMemcpyDeviceToHost, hs));
+        }
+        HIP_TRY(hipStreamSynchronize(hs));
+        x = src.kind == tgx::kDecodeI64 ? v.i64 : src.kind == tgx::kDecodeI32 ? (int64_t)v.i32 : (int64_t)v.u32;
+        const uint64_t row = src.offs ? (uint64_t)(std::upper_bound(h_offs.begin(), h_offs.end(), (uint64_t)h_bad) - h_offs.begin()) - 1 : h_bad / src.row_len;
+        end.done();
+        return decode_oob(src.kind, x, row, bad_sample, bad_id);
+    }
+    const uint64_t T = h_raw;
+    if (T == 0) {
+        HIP_TRY(t->d_bytes.alloc(dev, 0));
+        HIP_TRY(hipMemsetAsync(t->d_offs, 0, (size_t)(S + 1) * 8, hs));
+        HIP_TRY(hipStreamSynchronize(hs));
+        end.done();
+        *out = w.text.release();
+        return TGX_OK;
+    }
+    const uint64_t G = (T + tgx::kDecodeGroup - 1) / tgx::kDecodeGroup;
+    HIP_TRY(w.raw.alloc(dev, (size_t)G * tgx::kDecodeGroup + 16));
+    HIP_TRY(w.flags.alloc(dev, (size_t)G * 4));
+    HIP_TRY(w.codes.alloc(dev, (size_t)(G + 1) * 4));
+    p.n_raw = T;
+    p.raw = w.raw;
+    p.flags = w.flags;
+    p.codes = w.codes;
+    if (h_specials) {  // only then can a run end inside a row
+        HIP_TRY(w.specials.alloc(dev, (size_t)(N + 1) * 8));
+        p.specials = w.specials;
+        HIP_TRY(tgx::launch_decode_specials(p, w.scan, scan_bytes, hs));
+    }
+    HIP_TRY(tgx::launch_decode_fill(p, hs));
+    HIP_TRY(tgx::launch_decode_rows(p, hs));
+    HIP_TRY(tgx::launch_decode_utf8(p, hs));
+    HIP_TRY(hipMemcpyAsync(&h_replaced, w.ctrl.get() + 1, 8, hipMemcpyDeviceToHost, hs));
+    HIP_TRY(hipStreamSynchronize(hs));
+    t->n_replaced = h_replaced;
+    if (h_replaced == 0) {  // the raw bytes are the text and the rows' raw starts its offsets
+        t->d_bytes = std::move(w.raw);
+        t->n_bytes = T;
+        end.done();
+        *out = w.text.release();
+        return TGX_OK;
+    }
+    size_t scan2_bytes = 0;
+    if (tgx::decode_expand_temp_bytes(G, &scan2_bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan temp-size query failed");
+    HIP_TRY(w.gpos.alloc(dev, (size_t)(G + 1) * 8));
+    HIP_TRY(w.scan2.alloc(dev, scan2_bytes));
+    p.gpos = w.gpos;
+    HIP_TRY(tgx::launch_decode_positions(p, w.scan2, scan2_bytes, hs));
+    HIP_TRY(hipMemcpyAsync(&h_final, w.gpos.get() + G, 8, hipMemcpyDeviceToHost, hs));
+    HIP_TRY(hipStreamSynchronize(hs));
+    HIP_TRY(t->d_bytes.alloc(dev, (size_t)h_final + 16));
+    p.out = t->d_bytes;
+    HIP_TRY(tgx::launch_decode_expand(p, hs));
+    HIP_TRY(hipStreamSynchronize(hs));
+    t->n_bytes = h_final;
+    end.done();
+    *out = w.text.release();
+    return TGX_OK;
+}
+
+}  // namespace
+
+tgx_status tgx_decode_result(tgx_model* m, const tgx_result* r, const uint8_t* special_bytes, const uint64_t* special_offs, uint32_t n_specials,
+                             int include_special, void* stream, tgx_text** out, uint64_t* bad_sample, uint64_t* bad_id) {
+    const char* who = "tgx_decode_result";
+    if (!m || !r || !out) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
+    *out = nullptr;
+    tgx_status st = decode_check_specials(who, m->vocab_size, special_bytes, special_offs, n_specials);
+    if (st != TGX_OK) return st;
+    if (usable_device_count() <= 0) return fail(TGX_ERR_DEVICE, "no usable HIP device (gfx950 required)");
+    if (r->device != m->device) return fail(TGX_ERR_INVALID, "%s: the result is on device %d, the model on device %d", who, r->device, m->device);
+    if ((uint64_t)r->vocab_size > (uint64_t)m->vocab_size + n_specials)
+        return fail(TGX_ERR_INVALID, "%s: the result was written for %u ids, the model has %u tokens and %u special tokens", who, r->vocab_size,
+                    m->vocab_size, n_specials);
+    DeviceScope scope;
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t hs = stream ? static_cast<hipStream_t>(stream) : layout_stream(m->device);
+    tgx::DecodeSrc src = {};
+    src.ids = r->d_ids.get();
+    src.offs = r->d_offs.get();
+    src.n_rows = r->n_samples;
+    src.n = r->n_tokens;
+    src.kind = tgx::kDecodeU32;
+    src.skip_id = TGX_NO_ID;
+    return decode_device(m, src, special_bytes, special_offs, n_specials, include_special, hs, out, bad_sample, bad_id);
+}
+
+tgx_status tgx_decode_padded(tgx_model* m, const void* d_ids, uint64_t n_rows, uint64_t row_len, uint32_t flags, const uint8_t* d_mask,
+                             const int32_t* d_lengths, uint32_t skip_id, const uint8_t* special_bytes, const uint64_t* special_offs,
+                             uint32_t n_specials, int include_special, void* stream, tgx_text** out, uint64_t* bad_sample, uint64_t* bad_id) {
+    const char* who = "tgx_decode_padded";
+    if (!m || !out) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
+    *out = nullptr;
+    tgx_status st = layout_check_flags(who, flags, TGX_LAYOUT_I64);
+    if (st == TGX_OK) st = decode_check_specials(who, m->vocab_size, special_bytes, special_offs, n_specials);
+    if (st != TGX_OK) return st;
+    if (n_rows && row_len && n_rows > 0xFFFFFFFFFFFFFFFFull / 16 / row_len) return fail(TGX_ERR_UNSUPPORTED, "%s: %llu rows of %llu elements", who, (unsigned long long)n_rows, (unsigned long long)row_len);
+    const uint64_t N = n_rows * row_len;
+    if (N && !d_ids) return fail(TGX_ERR_INVALID, "%s: d_ids is NULL", who);
+    if (usable_device_count() <= 0) return fail(TGX_ERR_DEVICE, "no usable HIP device (gfx950 required)");
+    DeviceScope scope;
+    HIP_TRY(hipSetDevice(m->device));
+    if (N) {
+        if ((st = decode_check_src(who, "d_ids", d_ids, m->device)) != TGX_OK) return st;
+        if ((st = decode_check_src(who, "d_mask", d_mask, m->device)) != TGX_OK) return st;
+        if ((st = decode_check_src(who, "d_lengths", d_lengths, m->device)) != TGX_OK) return st;
+    }
+    hipStream_t hs = stream ? static_cast<hipStream_t>(stream) : layout_stream(m->device);
+    tgx::DecodeSrc src = {};
+    src.ids = d_ids;
+    src.mask = d_mask;
+    src.lengths = d_lengths;
+    src.n_rows = n_rows;
+    src.row_len = row_len;
+    src.n = N;
+    src.kind = (flags & TGX_LAYOUT_I64) ? tgx::kDecodeI64 : tgx::kDecodeI32;
+    src.skip_id = skip_id;
+    return decode_device(m, src, special_bytes, special_offs, n_specials, include_special, hs, out, bad_sample, bad_id);
+}
+
+uint64_t tgx_text_num_rows(const tgx_text* t) { return t ? t->n_rows : 0; }
+uint64_t tgx_text_num_bytes(const tgx_text* t) { return t ? t->n_bytes : 0; }
+uint64_t tgx_text_num_replaced(const tgx_text* t) { return t ? t->n_replaced : 0; }
+int tgx_text_device(const tgx_text* t) { return t ? t->device : -1; }
+const void* tgx_text_bytes_device(const tgx_text* t) { return t ? t->d_bytes.get() : nullptr; }
+const void* tgx_text_offsets_device(const tgx_text* t) { return t ? t->d_offs.get() : nullptr; }
+// (the call that made it returned after its stream had reached its end: the buffers go straight back to the pool)
+void tgx_text_free(tgx_text* t) { delete t; }
+
+tgx_status tgx_text_copy_bytes(const tgx_text* t, uint8_t* dst, uint64_t cap) {
+    if (!t || (!dst && t->n_bytes)) return fail(TGX_ERR_INVALID, "tgx_text_copy_bytes: NULL argument");
+    if (cap < t->n_bytes) return fail(TGX_ERR_INVALID, "tgx_text_copy_bytes: %llu bytes, room for %llu", (unsigned long long)t->n_bytes, (unsigned long long)cap);
+    if (!t->n_bytes) return TGX_OK;
+    DeviceScope scope;
+    HIP_TRY(hipSetDevice(t->device));
+    HIP_TRY(copy_sync(dst, t->d_bytes, t->n_bytes, hipMemcpyDeviceToHost, t->device));
+    return TGX_OK;
+}
+
+tgx_status tgx_text_copy_offsets(const tgx_text* t, uint64_t* dst, uint64_t cap) {
+    if (!t || !dst) return fail(TGX_ERR_INVALID, "tgx_text_copy_offsets: NULL argument");
+    if (cap < t->n_rows + 1) return fail(TGX_ERR_INVALID, "tgx_text_copy_offsets: %llu offsets, room for %llu", (unsigned long long)(t->n_rows + 1), (unsigned long long)cap);
+    DeviceScope scope;
+    HIP_TRY(hipSetDevice(t->device));
+    HIP_TRY(copy_sync(dst, t->d_offs, (t->n_rows + 1) * 8, hipMemcpyDeviceToHost, t->device));
+    return TGX_OK;
+}
+
+tgx_status tgx_corpus_from_text(const tgx_text* t, tgx_corpus** out) {
+    const char* who = "tgx_corpus_from_text";
+    if (!t || !out) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
+    *out = nullptr;
+    std::vector<uint64_t> offs(t->n_rows + 1);
+    const tgx_status st = tgx_text_copy_offsets(t, offs.data(), offs.size());
+    if (st != TGX_OK) return st;
+    DeviceScope scope;
+    return corpus_create(who, t->device, t->d_bytes, true, offs.data(), t->n_rows, out);
+}
+
+tgx_status tgx_decode_rows_host(const uint8_t* vocab_bytes, const uint64_t* vocab_offs, uint32_t vocab_size, const uint8_t* special_bytes,
+                                const uint64_t* special_offs, uint32_t n_specials, const void* ids, uint32_t id_kind, const uint64_t* id_offs,
+                                uint64_t n_rows, uint64_t row_len, const uint8_t* mask, const int32_t* lengths, uint32_t skip_id, int include_special,
+                                uint8_t** out_text, uint64_t* out_offs, uint64_t* n_replaced, uint64_t* bad_sample, uint64_t* bad_id) {
+    const char* who = "tgx_decode_rows_host";
+    if (!vocab_offs || !out_text || !out_offs) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
+    *out_text = nullptr;
+    if (id_kind > tgx::kDecodeI64) return fail(TGX_ERR_INVALID, "%s: id_kind %u", who, id_kind);
+    if (id_offs && id_kind != tgx::kDecodeU32) return fail(TGX_ERR_INVALID, "%s: the offsets form takes u32 ids", who);
+    tgx_status st = decode_check_specials(who, vocab_size, special_bytes, special_offs, n_specials);
+    if (st != TGX_OK) return st;
+    if (id_offs && (st = layout_check_host(who, static_cast<const uint32_t*>(ids), id_offs, n_rows)) != TGX_OK) return st;
+    if (!id_offs && n_rows && row_len && n_rows > 0xFFFFFFFFFFFFFFFFull / 16 / row_len) return fail(TGX_ERR_UNSUPPORTED, "%s: too many elements", who);
+    const uint64_t S = n_rows, N = id_offs ? id_offs[S] : n_rows * row_len;
+    if (N && !ids) return fail(TGX_ERR_INVALID, "%s: ids is NULL", who);
+    std::vector<uint8_t> len;
+    std::vector<tgx::DecodeSlot> slots;
+    if ((st = decode_build_tables(who, vocab_bytes, vocab_offs, vocab_size, &len, &slots)) != TGX_OK) return st;
+    static const uint64_t kNoOffs[1] = {0};
+    tgx::DecodeTables tab = {};
+    tab.tok_len = len.data();
+    tab.slots = slots.data();
+    tab.bytes = vocab_bytes;
+    tab.offs = vocab_offs;
+    tab.sp_bytes = special_bytes;
+    tab.sp_offs = n_specials ? special_offs : kNoOffs;
+    tab.vocab_size = vocab_size;
+    tab.n_specials = n_specials;
+    tab.include_special = include_special ? 1 : 0;
+    tgx::DecodeSrc src = {};
+    src.ids = ids;
+    src.offs = id_offs;
+    src.mask = id_offs ? nullptr : mask;
+    src.lengths = id_offs ? nullptr : lengths;
+    src.n_rows = S;
+    src.row_len = row_len;
+    src.n = N;
+    src.kind = id_kind;
+    src.skip_id = id_offs ? TGX_NO_ID : skip_id;
+    if (n_replaced) *n_replaced = 0;
+    for (uint64_t i = 0; i <= S; i++) out_offs[i] = 0;
+    // as the device: the elements' meta words, the two scans, ...
+    std::vector<uint64_t> B(N + 1), X(N + 1);
+    uint64_t bad = ~0ull, n_live_specials = 0;
+    for (uint64_t j = 0, b = 0, x = 0; j <= N; j++) {
+        B[j] = b;
+        X[j] = x;
+        if (j == N) break;
+        const int64_t v = tgx::decode_elem(src, j);
+        if (!tgx::decode_live(src, j, v)) continue;
+        bool oob;
+        const uint32_t meta = tgx::decode_meta(tab, v, &oob);
+        if (oob && j < bad) bad = j;
+        b += meta & ~tgx::kDecodeSpecial;
+        x += meta >> 31;
+        n_live_specials += meta >> 31;
+    }
+    if (bad != ~0ull) {
+        const uint64_t row = id_offs ? (uint64_t)(std::upper_bound(id_offs, id_offs + S + 1, bad) - id_offs) - 1 : bad / row_len;
+        return decode_oob(id_kind, tgx::decode_elem(src, bad), row, bad_sample, bad_id);
+    }
+    const uint64_t T = B[N], G = (T + tgx::kDecodeGroup - 1) / tgx::kDecodeGroup;
+    uint8_t* raw = static_cast<uint8_t*>(aligned_alloc(16, (size_t)G * tgx::kDecodeGroup + 16));
+    if (!raw) return fail(TGX_ERR_INVALID, "%s: out of host memory", who);
+    if (T == 0) {
+        *out_text = raw;
+        return TGX_OK;
+    }
+    memset(raw, 0xA5, (size_t)G * tgx::kDecodeGroup + 16);  // (what lies behind the text may be anything)
+    std::vector<uint32_t> flags(G), codes(G + 1, 0);
+    // ... the fill kernel's tiles and thread slots, ...
+    for (uint64_t t0 = 0; t0 < T; t0 += tgx::kDecodeTile) {
+        const uint64_t last = tgx::decode_tile_last(t0, T);
+        const uint64_t lo = tgx::decode_find(B.data(), 0, N - 1, tgx::decode_tile_first(t0)), hi = tgx::decode_find(B.data(), 0, N - 1, last);
+        for (uint64_t e0 = t0; e0 <= last; e0 += tgx::kDecodeGroup) {
+            const uint32_t n_in = last + 1 - e0 < tgx::kDecodeGroup ? (uint32_t)(last + 1 - e0) : tgx::kDecodeGroup;
+            uint8_t v[tgx::kDecodeGroup] = {};
+            flags[e0 / tgx::kDecodeGroup] = tgx::decode_group(tab, src, B.data(), n_live_specials ? X.data() : nullptr, lo, hi, e0, n_in, v);
+            memcpy(raw + e0, v, n_in);
+        }
+    }
+    // ... the rows' raw starts, which start runs, ...
+    for (uint64_t i = 0; i <= S; i++) {
+        const uint64_t r = B[i < S ? tgx::decode_row_first(src, i) : N];
+        out_offs[i] = r;
+        if (r < T) flags[r / tgx::kDecodeGroup] |= 1u << (uint32_t)(r % tgx::kDecodeGroup);
+    }
+    // ... the UTF-8 rule per slot, ...
+    uint64_t replaced = 0;
+    for (uint64_t g = 0; g < G; g++) {
+        codes[g] = tgx::decode_utf8_slot(raw, flags.data(), T, g);
+        replaced += tgx::decode_code_replaced(codes[g]);
+    }
+    if (n_replaced) *n_replaced = replaced;
+    if (replaced == 0) {
+        *out_text = raw;
+        return TGX_OK;
+    }
+    // ... and, after a replacement, the slots' positions and the second copy
+    std::vector<uint64_t> gpos(G + 1);
+    for (uint64_t g = 0, at = 0; g <= G; g++) {
+        gpos[g] = at;
+        at += tgx::decode_code_bytes(codes[g], tgx::kDecodeGroup);
+    }
+    uint8_t* text = static_cast<uint8_t*>(malloc((size_t)std::max<uint64_t>(1, gpos[G])));
+    if (!text) {
+        free(raw);
+        return fail(TGX_ERR_INVALID, "%s: out of host memory", who);
+    }
+    for (uint64_t g = 0; g < G; g++) tgx::decode_expand_slot(raw, T, g, codes[g], text, gpos[g]);
+    for (uint64_t i = 0; i <= S; i++) out_offs[i] = tgx::decode_final_pos(gpos.data(), codes.data(), out_offs[i], T);
+    free(raw);
+    *out_text = text;
+    return TGX_OK;
 }
 
 // ---- frequency pass ------------------------------------------------------------

@@ -143,3 +143,40 @@ def to_packed(result: "_lib.NativeResult", block_len: int, *, pad_id: int, bos_i
     if drop_last and n_stream % L:
         out = {k: v[:B - 1] for k, v in out.items()}
     return out
+
+
+def decode_padded(model: "_lib.NativeModel", input_ids, *, attention_mask=None, lengths=None, skip_id: int | None = None,
+                  special_flat=(), special_offs=(0,), include_special: bool = True) -> "_lib.NativeText":
+    """A [S, L] tensor of ids (int32 or int64, contiguous, on the model's device) decoded to UTF-8 text in HBM with the
+    kernels of csrc/decode.hip -> NativeText.  attention_mask (uint8 or bool, the same shape), lengths (int32 [S]) and
+    skip_id say which elements are there at all (NativeModel.decode_padded).  Everything is checked before anything is
+    launched; the kernels are queued on torch.cuda.current_stream(device) and the call returns once that stream has
+    reached its end."""
+    import torch
+    if not torch.cuda.is_available():
+        raise _lib.TokenGeeXError("torch sees no GPU although libtgx.so does: two HIP runtimes in one process "
+                                  "(TGX_HIP_RUNTIME=system set? then import torch before tokengeex_amd)", _lib.ERR_DEVICE)
+    dev = torch.device("cuda", model.device)
+    if not isinstance(input_ids, torch.Tensor):
+        raise TypeError("input_ids must be a torch.Tensor")
+    if input_ids.dim() != 2:
+        raise ValueError(f"input_ids must have two dimensions (got {input_ids.dim()})")
+    _np_dtype(torch, input_ids.dtype)
+    S, L = input_ids.shape
+    p_ids = _check_dest(torch, "input_ids", input_ids, dev, input_ids.dtype, S * L)
+    p_mask = 0
+    if attention_mask is not None:
+        if not isinstance(attention_mask, torch.Tensor):
+            raise TypeError("attention_mask must be a torch.Tensor")
+        if attention_mask.shape != input_ids.shape:
+            raise ValueError(f"attention_mask has shape {tuple(attention_mask.shape)}, input_ids {tuple(input_ids.shape)}")
+        mask_dtype = torch.bool if attention_mask.dtype == torch.bool else torch.uint8  # a bool is one byte, 0 or 1
+        p_mask = _check_dest(torch, "attention_mask", attention_mask, dev, mask_dtype, S * L)
+    p_len = 0
+    if lengths is not None:
+        if isinstance(lengths, torch.Tensor) and lengths.shape != (S,):
+            raise ValueError(f"lengths has shape {tuple(lengths.shape)}, expected ({S},)")
+        p_len = _check_dest(torch, "lengths", lengths, dev, torch.int32, S)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    return model.decode_padded(p_ids, S, L, input_ids.dtype == torch.int64, mask_ptr=p_mask, lengths_ptr=p_len, skip_id=skip_id,
+                               special_flat=special_flat, special_offs=special_offs, include_special=include_special, stream=stream)

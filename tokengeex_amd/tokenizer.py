@@ -711,6 +711,59 @@ class Tokenizer:
         raw = text.tobytes()
         return [raw[int(to[i]):int(to[i + 1])].decode("utf-8") for i in range(len(ids))]
 
+    # -- decode on the device (NativeModel.decode_result / tensors.decode_padded over csrc/decode.hip) --
+    @staticmethod
+    def _text_flat(text: "_lib.NativeText"):
+        try:
+            return text.bytes(), text.offsets()
+        finally:
+            text.free()
+
+    @staticmethod
+    def _text_strs(text: "_lib.NativeText") -> list[str]:
+        flat, offs = Tokenizer._text_flat(text)
+        raw, o = flat.tobytes(), offs.tolist()
+        return [raw[o[i]:o[i + 1]].decode("utf-8") for i in range(len(o) - 1)]
+
+    def decode_result_text(self, result: "_lib.NativeResult", include_special_tokens: bool) -> "_lib.NativeText":
+        """decode_batch_flat over a device result (of encode_batch_result_flat, encode_corpus, sampling, ...) without its ids
+        leaving HBM -> NativeText: UTF-8 bytes and row offsets on the device (to_corpus() re-encodes them under another
+        model).  Postprocessors are the identity, as in decode_batch_flat.  The caller frees it; the result is only read."""
+        _, _, sf, so = self._vocab_packed()
+        return self._model().decode_result(result, sf, so, include_special_tokens)
+
+    def decode_result_flat(self, result: "_lib.NativeResult", include_special_tokens: bool):
+        """decode_result_text copied to the host -> (utf-8 bytes, offsets u64[S+1]), what decode_batch_flat returns."""
+        return self._text_flat(self.decode_result_text(result, include_special_tokens))
+
+    def decode_result(self, result: "_lib.NativeResult", include_special_tokens: bool) -> list[str]:
+        return self._text_strs(self.decode_result_text(result, include_special_tokens))
+
+    def _skip_id(self, skip) -> int | None:
+        if isinstance(skip, str):
+            k = self.special_token_to_id(skip)
+            if k is None:
+                raise TokenGeeXError(f"{skip!r} is not a special token of this tokenizer", _lib.ERR_INVALID)
+            return k
+        return skip
+
+    def decode_tensor_text(self, input_ids, include_special_tokens: bool, attention_mask=None, lengths=None,
+                           skip=None) -> "_lib.NativeText":
+        """decode_batch over a [S, L] torch tensor of ids on the model's device (e.g. what a model generated), decoded where
+        it lies -> NativeText.  attention_mask / lengths say which elements are there; `skip` (a special-token string or an
+        id, typically the pad token) names an id that is dropped wherever it stands."""
+        from . import tensors
+        _, _, sf, so = self._vocab_packed()
+        return tensors.decode_padded(self._model(), input_ids, attention_mask=attention_mask, lengths=lengths, skip_id=self._skip_id(skip),
+                                     special_flat=sf, special_offs=so, include_special=include_special_tokens)
+
+    def decode_tensor_flat(self, input_ids, include_special_tokens: bool, attention_mask=None, lengths=None, skip=None):
+        """decode_tensor_text copied to the host -> (utf-8 bytes, offsets u64[S+1])."""
+        return self._text_flat(self.decode_tensor_text(input_ids, include_special_tokens, attention_mask, lengths, skip))
+
+    def decode_tensor(self, input_ids, include_special_tokens: bool, attention_mask=None, lengths=None, skip=None) -> list[str]:
+        return self._text_strs(self.decode_tensor_text(input_ids, include_special_tokens, attention_mask, lengths, skip))
+
     # -- id / token queries: src/tokenizer.rs:189-259 --
     def token_to_id(self, token: bytes) -> int | None:
         r = self.base_token_to_id(token)
