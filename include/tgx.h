@@ -397,6 +397,60 @@ tgx_status tgx_decode_rows_host(const uint8_t *vocab_bytes, const uint64_t *voca
                                 int include_special, uint8_t **out_text, uint64_t *out_offs, uint64_t *n_replaced,
                                 uint64_t *bad_sample, uint64_t *bad_id);
 
+/* ---- token spans on the device: the part of its row's text that every token covers (csrc/spans.hip) ----------------
+ * The offsets mapping of a result, in bytes or in characters, written into caller-owned DEVICE memory: neither the ids nor
+ * any text visit the host, and no text is needed on the device.  The spans are a function of the ids and the vocabulary.
+ *
+ * Input: a model with base vocabulary size V; n_specials special tokens (special_bytes / special_offs: host arrays as in
+ *   tgx_decode_result); a result r with rows i = 0..S, ids x[0..T) and offsets o[0..S], on the model's device and with
+ *   tgx_result_vocab_size(r) <= V + n_specials (TGX_ERR_INVALID otherwise).  Results of encode, sampling, n-best, a
+ *   resident corpus and tgx_assemble_result are all taken.
+ * For an id x: bytes(x) = its token's bytes, for x >= V those of special token x - V; len(x) = |bytes(x)|; leads(x) = the
+ *   number of bytes of bytes(x) that are not in 80..BF; cont(x) = 1 iff len(x) > 0 and the first byte is in 80..BF.
+ * Row i's raw text is the concatenation of bytes(x[j]) for o[i] <= j < o[i+1]: with no processors the input sample byte
+ *   for byte, with CRLF or NFC the processed sample (what decode gives for valid UTF-8, special tokens included).
+ * Byte unit: b_j = the sum of len(x[k]) over o[i] <= k < j, e_j = b_j + len(x[j]); the span of token j is (b_j, e_j).
+ * Character unit (flags: TGX_SPAN_CHARS): c(p) = the number of bytes not in 80..BF among the first p bytes of the row's
+ *   raw text; the span is (c(b_j) - cont(x[j]), c(e_j)) for len(x[j]) > 0, the smallest range of code points whose bytes
+ *   cover the token (two byte tokens that split one CJK character both get that character), and (c(b_j), c(b_j)) for a
+ *   token of length 0.  On valid UTF-8 this indexes a Python str.  On invalid bytes it is the same definition over
+ *   bytes and nothing more: a token that starts with a byte in 80..BF is attributed to the character before it, and
+ *   where there is none (the row's text starts with such bytes) its start is -1.  Only the specials' lengths are read
+ *   in the byte unit (special_bytes is not looked at); the character unit reads their bytes.
+ * Spans are relative to the whole row, truncated or not.
+ * Flat form (tgx_result_spans_device): d_spans[T, 2], element (j, 0) the start and (j, 1) the end of token j.
+ * Padded form (tgx_result_pad_spans_device): d_spans[S, L, 2], aligned element for element with what
+ *   tgx_result_pad_device writes for the same row_len = L, bos_id, eos_id, TGX_LAYOUT_PAD_LEFT and
+ *   TGX_LAYOUT_TRUNC_LEFT (the same row mapping, csrc/layout.h): a kept token gets its span; bos, eos and padding get
+ *   (0, 0).  L >= 1 and L >= A, bos_id / eos_id below 2^31 or TGX_NO_ID, else TGX_ERR_INVALID.
+ * Elements are int32_t, or int64_t with TGX_LAYOUT_I64.  All sums on the device are 64-bit (a batch holds more than 2^32
+ *   bytes long before a row does).  With int32_t, if some row's total in the chosen unit is >= 2^31 the call returns
+ *   TGX_ERR_UNSUPPORTED and nothing is written: a device reduction over the rows, of which one word is read back, and
+ *   only for int32_t.
+ * Stream rule: that of the layouts above.  `stream` is a hipStream_t: pass the stream the destination's allocator
+ *   orders its memory on; NULL selects the library's blocking stream.  The work is queued on the chosen stream and the
+ *   call returns only after the stream has reached its end.  d_spans must be device memory on the result's device
+ *   (checked with hipPointerGetAttributes before anything is queued: TGX_ERR_INVALID otherwise); room for every element
+ *   written is the caller's responsibility.  NULL arguments are refused before any device call.  The calling thread's
+ *   current device is the same after the call as before.
+ * S = 0 or T = 0: TGX_OK; the padded form still fills its S·L·2 elements with 0.  The model's token words (16 bits per
+ *   token) go to its device on the first call.  tgx_last_kernel_times is not touched.
+ * tgx_spans_host is the host twin over host arrays (vocab_bytes / vocab_offs u64[V+1]; ids u32[T], may be NULL when
+ *   T = 0; offs u64[n_rows + 1], offs[0] = 0, ascending): the same semantics through the kernels' index arithmetic
+ *   (csrc/spans.h), no device.  row_len = 0 selects the flat form (bos_id, eos_id and the two side flags are then
+ *   ignored), out is [T, 2] or [n_rows, row_len, 2].  An id >= V + n_specials: TGX_ERR_TOKEN_ID_OOB. */
+#define TGX_SPAN_CHARS 8u
+tgx_status tgx_result_spans_device(tgx_model *m, const tgx_result *r, const uint8_t *special_bytes,
+                                   const uint64_t *special_offs, uint32_t n_specials, uint32_t flags, void *stream,
+                                   void *d_spans);
+tgx_status tgx_result_pad_spans_device(tgx_model *m, const tgx_result *r, const uint8_t *special_bytes,
+                                       const uint64_t *special_offs, uint32_t n_specials, uint32_t row_len,
+                                       uint32_t bos_id, uint32_t eos_id, uint32_t flags, void *stream, void *d_spans);
+tgx_status tgx_spans_host(const uint8_t *vocab_bytes, const uint64_t *vocab_offs, uint32_t vocab_size,
+                          const uint8_t *special_bytes, const uint64_t *special_offs, uint32_t n_specials,
+                          const uint32_t *ids, const uint64_t *offs, uint64_t n_rows, uint32_t row_len,
+                          uint32_t bos_id, uint32_t eos_id, uint32_t flags, void *out);
+
 /* ---- resident corpus: the prune / merge training loops -------------------- */
 /* The reference holds `samples: &[&str]` in RAM across all EM / merge passes
  * (src/prune.rs:23, src/merge.rs:33); here the batch is uploaded once and stays

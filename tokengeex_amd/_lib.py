@@ -22,6 +22,7 @@ MAX_NBEST = 16  # TGX_MAX_NBEST
 ESTEP_SNIPPET_LEN = 81920
 NO_ID = 0xFFFFFFFF  # TGX_NO_ID: no bos / eos
 LAYOUT_PAD_LEFT, LAYOUT_TRUNC_LEFT, LAYOUT_I64 = 1, 2, 4  # TGX_LAYOUT_*
+SPAN_CHARS = 8  # TGX_SPAN_CHARS
 
 # every exported symbol of include/tgx.h: name -> (restype, argtypes)
 _vp, _u64, _u32, _i, _d = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_double
@@ -129,6 +130,9 @@ SYMBOLS = {
     "tgx_corpus_from_text": (_i, [_vp, _pvp]),
     "tgx_decode_rows_host": (_i, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _u32, _vp, _u64, _u64, _vp, _vp, _u32, _i, _pvp, _vp, _pu64,
                                   _pu64, _pu64]),
+    "tgx_result_spans_device": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp]),
+    "tgx_result_pad_spans_device": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp]),
+    "tgx_spans_host": (_i, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _u64, _u32, _u32, _u32, _u32, _vp]),
 }
 
 
@@ -434,6 +438,52 @@ def decode_rows_host(vocab_flat, vocab_offs, vocab_size: int, special_flat, spec
     if st != OK:
         _raise_decode(st, bs.value, bi.value)
     return _take(txt, int(out_offs[-1]), C.c_uint8, np.uint8), out_offs, nr.value
+
+
+def span_flags(unit: str = "byte", dtype=np.int32, padding_side: str = "right", truncation_side: str = "right") -> int:
+    """The flags of a spans call: layout_flags with TGX_SPAN_CHARS for unit "char"."""
+    if unit not in ("byte", "char"):
+        raise ValueError(f"unit must be 'byte' or 'char' (got {unit!r})")
+    return layout_flags(padding_side, truncation_side, dtype) | (SPAN_CHARS if unit == "char" else 0)
+
+
+def spans_host(vocab_flat, vocab_offs, vocab_size: int, special_flat, special_offs, n_specials: int, ids: np.ndarray, offs: np.ndarray, *,
+               unit: str = "byte", dtype=np.int32, row_len: int | None = None, bos_id: int | None = None, eos_id: int | None = None,
+               padding_side: str = "right", truncation_side: str = "right", out: np.ndarray | None = None) -> np.ndarray:
+    """Host twin of NativeModel.result_spans / result_pad_spans (tgx_spans_host: the kernels' index arithmetic, no device)
+    over ids u32[T] and offsets u64[S+1] -> [T, 2] of dtype, or [S, row_len, 2] aligned with layout_pad_host's input_ids
+    (bos, eos and padding get (0, 0)).  unit "byte": the token's bytes in its row's text; "char": its code points.  The
+    byte unit reads only special_offs, so special_flat may be empty whatever they declare.  out: a C-contiguous array of
+    that shape and dtype to write into."""
+    vocab_flat = np.ascontiguousarray(vocab_flat, dtype=np.uint8)
+    vocab_offs = np.ascontiguousarray(vocab_offs, dtype=np.uint64)
+    special_flat = np.ascontiguousarray(special_flat, dtype=np.uint8)
+    special_offs = np.ascontiguousarray(special_offs, dtype=np.uint64)
+    ids = np.ascontiguousarray(ids, dtype=np.uint32)
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    n = offs.shape[0] - 1
+    if row_len is None:
+        L, flags = 0, span_flags(unit, dtype)
+        shape = (int(offs[-1]) if n else 0, 2)
+    else:
+        L, flags = _u32_arg(row_len, "row_len"), span_flags(unit, dtype, padding_side, truncation_side)
+        if L < 1:
+            raise TokenGeeXError("row_len must be at least 1", ERR_INVALID)
+        shape = (n, L, 2)
+    if out is None:
+        out = np.empty(shape, np.dtype(dtype))
+    elif out.shape != shape or out.dtype != np.dtype(dtype) or not out.flags.c_contiguous:
+        raise ValueError(f"out must be a C-contiguous {np.dtype(dtype)} array of shape {shape}")
+    st = lib.tgx_spans_host(ptr(vocab_flat) if vocab_flat.size else None, ptr(vocab_offs), _u32_arg(vocab_size, "vocab_size"),
+                            ptr(special_flat) if special_flat.size else None, ptr(special_offs), _u32_arg(n_specials, "n_specials"),
+                            ptr(ids) if ids.size else None, ptr(offs), n, L, _id_or_none(bos_id), _id_or_none(eos_id), flags,
+                            ptr(out) if out.size else None)
+    if st == ERR_TOKEN_ID_OOB:  # the row and the id, as the decode twins name them
+        bs, bi, _ = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        lib.tgx_last_error_detail(C.byref(bs), C.byref(bi), C.byref(_))
+        _raise_decode(st, bs.value, bi.value)
+    check(st)
+    return out
 
 
 def substring_df(flat: np.ndarray, part_begin: np.ndarray, part_end: np.ndarray, part_sample: np.ndarray,
@@ -897,6 +947,27 @@ class NativeModel:
         if st != OK:
             _raise_decode(st, bs.value, bi.value)
         return NativeText(h)
+
+    # -- token spans on the device (include/tgx.h: tgx_result_spans_device / tgx_result_pad_spans_device; csrc/spans.hip) --
+    def result_spans(self, result: NativeResult, special_flat, special_offs, spans_ptr: int, *, flags: int = 0, stream: int = 0) -> None:
+        """The span of every token of a result on this model's device in its row's text, written by the device into
+        caller-owned device memory given as a raw integer pointer: [num_tokens, 2] int32, or int64 with LAYOUT_I64 in flags;
+        SPAN_CHARS counts code points instead of bytes (span_flags puts the flags together).  ids >= vocab_size are the
+        special tokens, as in decode_result.  Queued on `stream` (0: the library's blocking stream); returns when the
+        stream has reached its end.  The result is only read."""
+        sf, so, n = self._specials(special_flat, special_offs)
+        check(lib.tgx_result_spans_device(self._h, result._h, ptr(sf) if sf.size else None, ptr(so), n, _u32_arg(flags, "flags"),
+                                          stream or None, spans_ptr or None))
+
+    def result_pad_spans(self, result: NativeResult, special_flat, special_offs, row_len: int, spans_ptr: int, *, bos_id: int | None = None,
+                         eos_id: int | None = None, flags: int = 0, stream: int = 0) -> None:
+        """result_spans in the padded form: [num_samples, row_len, 2], aligned element for element with what
+        NativeResult.pad_device writes for the same row_len, bos_id, eos_id and side flags; bos, eos and padding get
+        (0, 0)."""
+        sf, so, n = self._specials(special_flat, special_offs)
+        check(lib.tgx_result_pad_spans_device(self._h, result._h, ptr(sf) if sf.size else None, ptr(so), n, _u32_arg(row_len, "row_len"),
+                                              _id_or_none(bos_id), _id_or_none(eos_id), _u32_arg(flags, "flags"), stream or None,
+                                              spans_ptr or None))
 
     def encode_corpus_sample(self, corpus: NativeCorpus, alpha: float, seed: int, return_logz: bool = False):
         """encode_batch_sample_flat over a resident corpus (tgx_encode_corpus_sample)."""

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "decode.h"
+#include "spans.h"
 
 namespace tgx {
 
@@ -359,5 +360,26 @@ hipError_t launch_decode_utf8(const DecodeParams& p, hipStream_t stream);   // a
 hipError_t decode_expand_temp_bytes(uint64_t n_groups, size_t* bytes);
 hipError_t launch_decode_positions(const DecodeParams& p, void* temp, size_t temp_bytes, hipStream_t stream);
 hipError_t launch_decode_expand(const DecodeParams& p, hipStream_t stream);  // the bytes and the rows' final offsets
+
+// spans.hip: the part of its row's text that every token of a result covers, in bytes or characters (spans.h has the
+// index arithmetic).  All pointers are device memory.
+struct SpanParams {
+    SpanTables tab;
+    const uint32_t* ids;            // u32[T]
+    const uint64_t* offs;           // u64[S+1]
+    uint64_t n_rows, n;             // S, T
+    uint32_t* vals;                 // u32[T+1]: the elements' value words (the last entry belongs to the scan)
+    uint64_t* sums;                 // u64[T+1]: P, the exclusive prefix sums of the values
+    unsigned long long* row_max;    // the largest row total (zeroed by the caller)
+    uint32_t len;                   // padded: row_len
+    uint32_t bos, eos;              // padded: 0xFFFFFFFF = none
+    uint32_t flags;                 // TGX_LAYOUT_* | TGX_SPAN_CHARS
+    void* out;                      // i32 or i64 (TGX_LAYOUT_I64): [T, 2] or [S, L, 2]
+};
+hipError_t span_scan_temp_bytes(uint64_t n, size_t* bytes);
+hipError_t launch_span_sums(const SpanParams& p, void* temp, size_t temp_bytes, hipStream_t stream);  // vals and P
+hipError_t launch_span_row_max(const SpanParams& p, hipStream_t stream);                              // after the sums
+hipError_t launch_span_flat(const SpanParams& p, hipStream_t stream);
+hipError_t launch_span_pad(const SpanParams& p, hipStream_t stream);
 
 }  // namespace tgx

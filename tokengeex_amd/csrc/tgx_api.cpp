@@ -27,6 +27,7 @@
 #include "decode.h"
 #include "kernels.h"
 #include "layout.h"
+#include "spans.h"
 #include "nbest.h"
 #include "sample.h"
 #include "trie_build.h"
@@ -311,6 +312,9 @@ struct tgx_model {
     uint8_t* d_dec_bytes = nullptr;
     uint64_t* d_dec_offs = nullptr;
     bool decode_tables_ready = false;
+    // spans (spans.hip): one packed word per token (spans.h), uploaded at the first call (ensure_span_words)
+    uint16_t* d_span_words = nullptr;
+    bool span_words_ready = false;
     int estep_blocks_per_cu = 0;
     KernelTime timed[kMaxTimed] = {};
     int n_timed = 0;
@@ -1501,6 +1505,7 @@ void tgx_model_destroy(tgx_model* m) {
     if (m->d_dec_slots) (void)hipFree(m->d_dec_slots);
     if (m->d_dec_bytes) (void)hipFree(m->d_dec_bytes);
     if (m->d_dec_offs) (void)hipFree(m->d_dec_offs);
+    if (m->d_span_words) (void)hipFree(m->d_span_words);
     if (m->stream2) (void)hipStreamDestroy(m->stream2);
     if (m->ev_fork) (void)hipEventDestroy(m->ev_fork);
     if (m->ev_join) (void)hipEventDestroy(m->ev_join);
@@ -2934,6 +2939,246 @@ tgx_status tgx_decode_rows_host(const uint8_t* vocab_bytes, const uint64_t* voca
     for (uint64_t i = 0; i <= S; i++) out_offs[i] = tgx::decode_final_pos(gpos.data(), codes.data(), out_offs[i], T);
     free(raw);
     *out_text = text;
+    return TGX_OK;
+}
+
+// ---- spans: the part of its row's text that every token covers (spans.hip; spans.h has the index arithmetic) ------
+
+namespace {
+
+// one word per token of a vocabulary: what the meta kernel (a device copy) and the host twin read
+tgx_status span_build_words(const char* who, const uint8_t* bytes, const uint64_t* offs, uint32_t V, std::vector<uint16_t>* words) {
+    words->assign(V, 0);
+    for (uint32_t i = 0; i < V; i++) {
+        if (offs[i + 1] < offs[i]) return fail(TGX_ERR_INVALID, "%s: vocabulary offsets not monotone at %u", who, i);
+        const uint64_t n = offs[i + 1] - offs[i];
+        if (n > TGX_MAX_TOKEN_LEN) return fail(TGX_ERR_UNSUPPORTED, "%s: token of %llu bytes exceeds TGX_MAX_TOKEN_LEN (%d)", who, (unsigned long long)n, TGX_MAX_TOKEN_LEN);
+        (*words)[i] = tgx::span_word(bytes + offs[i], (uint32_t)n);
+    }
+    return TGX_OK;
+}
+
+// the special tokens' words; the byte unit reads no byte of theirs
+void span_special_words(const uint8_t* special_bytes, const uint64_t* special_offs, uint32_t n_specials, bool chars, std::vector<uint64_t>* words) {
+    words->assign((size_t)n_specials + 1, 0);
+    for (uint32_t k = 0; k < n_specials; k++)
+        (*words)[k] = tgx::span_special_word(chars ? special_bytes + special_offs[k] : nullptr, special_offs[k + 1] - special_offs[k]);
+}
+
+// flags, specials and the padded form's arguments: what the device entry points and the host twin check alike
+tgx_status span_check_args(const char* who, uint32_t vocab_size, const uint8_t* special_bytes, const uint64_t* special_offs, uint32_t n_specials,
+                           bool padded, uint32_t row_len, uint32_t bos_id, uint32_t eos_id, uint32_t flags) {
+    tgx_status st = layout_check_flags(who, flags, TGX_LAYOUT_I64 | TGX_SPAN_CHARS | (padded ? TGX_LAYOUT_PAD_LEFT | TGX_LAYOUT_TRUNC_LEFT : 0u));
+    static const uint8_t unread = 0;  // the byte unit does not look at special_bytes, which may then be NULL
+    if (st == TGX_OK) st = decode_check_specials(who, vocab_size, (flags & TGX_SPAN_CHARS) ? special_bytes : &unread, special_offs, n_specials);
+    if (st == TGX_OK && padded) st = layout_check_ids(who, 0, bos_id, eos_id);
+    if (st != TGX_OK) return st;
+    if (padded) {
+        const tgx::LayoutSeq seq = tgx::layout_seq(bos_id, eos_id, 0);
+        if (row_len < 1 || row_len < seq.extra) return fail(TGX_ERR_INVALID, "%s: row_len %u (needs >= 1 and >= %u for bos / eos)", who, row_len, seq.extra);
+    }
+    return TGX_OK;
+}
+
+tgx_status span_too_long(const char* who, uint64_t row_max, bool chars) {
+    return fail(TGX_ERR_UNSUPPORTED, "%s: a row of %llu %s does not fit int32 spans (TGX_LAYOUT_I64 takes it)", who, (unsigned long long)row_max,
+                chars ? "characters" : "bytes");
+}
+
+// the model's token words on its device, once (under m->mu)
+tgx_status ensure_span_words(tgx_model* m) {
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (m->span_words_ready) return TGX_OK;
+    const uint32_t V = m->vocab_size;
+    std::vector<uint16_t> words;
+    const tgx_status st = span_build_words("spans", m->vocab_bytes.data(), m->vocab_offs.data(), V, &words);
+    if (st != TGX_OK) return st;
+    if (!m->d_span_words) HIP_TRY(hipMalloc((void**)&m->d_span_words, ((size_t)V + 8) * 2));
+    if (V) HIP_TRY(hipMemcpy(m->d_span_words, words.data(), (size_t)V * 2, hipMemcpyHostToDevice));
+    m->span_words_ready = true;
+    return TGX_OK;
+}
+
+// the buffers of one call; they go back to the pool after the stream has reached its end (StreamEnd below them)
+struct SpanWork {
+    PoolBuf<uint32_t> vals;
+    PoolBuf<uint64_t> sums, sp_words;
+    PoolBuf<void> scan;
+    PoolBuf<unsigned long long> row_max;
+};
+
+// row_len = 0: the flat form
+tgx_status spans_device(const char* who, tgx_model* m, const tgx_result* r, const uint8_t* special_bytes, const uint64_t* special_offs,
+                        uint32_t n_specials, uint32_t row_len, uint32_t bos_id, uint32_t eos_id, uint32_t flags, void* stream, void* d_spans) {
+    if (!m || !r) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
+    const bool padded = row_len != 0, chars = (flags & TGX_SPAN_CHARS) != 0;
+    const tgx_status st0 = span_check_args(who, m->vocab_size, special_bytes, special_offs, n_specials, padded, row_len, bos_id, eos_id, flags);
+    if (st0 != TGX_OK) return st0;
+    const uint64_t S = r->n_samples, T = r->n_tokens;
+    const uint64_t n_pairs = padded ? S * (uint64_t)row_len : (S ? T : 0);
+    if (!d_spans && n_pairs) return fail(TGX_ERR_INVALID, "%s: d_spans is NULL", who);
+    if (usable_device_count() <= 0) return fail(TGX_ERR_DEVICE, "no usable HIP device (gfx950 required)");
+    if (r->device != m->device) return fail(TGX_ERR_INVALID, "%s: the result is on device %d, the model on device %d", who, r->device, m->device);
+    if ((uint64_t)r->vocab_size > (uint64_t)m->vocab_size + n_specials)
+        return fail(TGX_ERR_INVALID, "%s: the result was written for %u ids, the model has %u tokens and %u special tokens", who, r->vocab_size,
+                    m->vocab_size, n_specials);
+    if (n_pairs == 0) return TGX_OK;
+    DeviceScope scope;
+    HIP_TRY(hipSetDevice(m->device));
+    tgx_status st = layout_check_dest(who, "d_spans", d_spans, m->device);
+    if (st != TGX_OK) return st;
+    hipStream_t hs = stream ? static_cast<hipStream_t>(stream) : layout_stream(m->device);
+    const int dev = m->device;
+    const bool i64 = (flags & TGX_LAYOUT_I64) != 0;
+    if (T == 0) {  // the padded form of rows without tokens
+        const hipError_t e = hipMemsetAsync(d_spans, 0, (size_t)n_pairs * 2 * (i64 ? 8 : 4), hs);
+        const hipError_t es = hipStreamSynchronize(hs);
+        HIP_TRY(e);
+        HIP_TRY(es);
+        return TGX_OK;
+    }
+    if ((st = ensure_span_words(m)) != TGX_OK) return st;
+
+    std::vector<uint64_t> sp_words;  // alive until the stream has taken them
+    span_special_words(special_bytes, special_offs, n_specials, chars, &sp_words);
+    size_t scan_bytes = 0;
+    if (tgx::span_scan_temp_bytes(T, &scan_bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan temp-size query failed");
+    SpanWork w;
+    StreamEnd end(hs);  // destroyed before w: a failed call's queued work is over before its buffers change hands
+    HIP_TRY(w.vals.alloc(dev, (size_t)(T + 1) * 4));
+    HIP_TRY(w.sums.alloc(dev, (size_t)(T + 1) * 8));
+    HIP_TRY(w.scan.alloc(dev, scan_bytes));  // (never NULL: that asks the scan for its size)
+    HIP_TRY(w.sp_words.alloc(dev, sp_words.size() * 8));
+    HIP_TRY(hipMemcpyAsync(w.sp_words, sp_words.data(), sp_words.size() * 8, hipMemcpyHostToDevice, hs));
+
+    tgx::SpanParams p = {};
+    p.tab.words = m->d_span_words;
+    p.tab.sp_words = w.sp_words;
+    p.tab.vocab_size = m->vocab_size;
+    p.tab.n_specials = n_specials;
+    p.ids = r->d_ids;
+    p.offs = r->d_offs;
+    p.n_rows = S;
+    p.n = T;
+    p.vals = w.vals;
+    p.sums = w.sums;
+    p.len = row_len;
+    p.bos = bos_id;
+    p.eos = eos_id;
+    p.flags = flags;
+    p.out = d_spans;
+    HIP_TRY(tgx::launch_span_sums(p, w.scan, scan_bytes, hs));
+    if (!i64) {  // nothing is written when a row does not fit: the one word that is read back
+        unsigned long long h_max = 0;
+        HIP_TRY(w.row_max.alloc(dev, sizeof(unsigned long long)));
+        p.row_max = w.row_max;
+        HIP_TRY(hipMemsetAsync(w.row_max, 0, sizeof(unsigned long long), hs));
+        HIP_TRY(tgx::launch_span_row_max(p, hs));
+        HIP_TRY(hipMemcpyAsync(&h_max, w.row_max, sizeof(unsigned long long), hipMemcpyDeviceToHost, hs));
+        HIP_TRY(hipStreamSynchronize(hs));
+        if (h_max >= 0x80000000ull) {
+            end.done();
+            return span_too_long(who, h_max, chars);
+        }
+    }
+    HIP_TRY(padded ? tgx::launch_span_pad(p, hs) : tgx::launch_span_flat(p, hs));
+    // the stream has reached its end before the result or the destination can change hands
+    HIP_TRY(hipStreamSynchronize(hs));
+    end.done();
+    return TGX_OK;
+}
+
+extern "C++" {  // (this part of the file is inside extern "C")
+template <class T>
+void spans_host_write(const tgx::LayoutSeq& seq, const uint64_t* offs, uint64_t n_rows, uint64_t n, const uint64_t* P, const uint32_t* vals,
+                      uint32_t row_len, uint32_t flags, T* out) {
+    if (row_len) {  // as the kernel: one pair per slot
+        for (uint64_t e = 0; e < n_rows * (uint64_t)row_len; e++) {
+            tgx::SpanPair s = {0, 0};
+            if (n) s = tgx::span_pad_at(seq, offs, P, vals, row_len, flags, e);
+            out[2 * e] = (T)s.start;
+            out[2 * e + 1] = (T)s.end;
+        }
+        return;
+    }
+    // as the kernel: tiles of kSpanTile elements, the owners of a tile's ends bound the search inside it, and a group of
+    // consecutive elements walks on from row to row
+    for (uint64_t t0 = 0; t0 < n; t0 += tgx::kSpanTile) {
+        const uint64_t last = tgx::span_tile_last(t0, n);
+        const uint64_t lo = tgx::pack_find_row(offs, 0, 0, n_rows - 1, t0), hi = tgx::pack_find_row(offs, 0, 0, n_rows - 1, last);
+        for (uint64_t e0 = t0; e0 <= last; e0 += tgx::kSpanGroup) {
+            const uint32_t n_in = last + 1 - e0 < tgx::kSpanGroup ? (uint32_t)(last + 1 - e0) : tgx::kSpanGroup;
+            tgx::SpanPair v[tgx::kSpanGroup] = {};
+            tgx::span_group(offs, P, vals, lo, hi, e0, n_in, v);
+            for (uint32_t k = 0; k < n_in; k++) {
+                out[2 * (e0 + k)] = (T)v[k].start;
+                out[2 * (e0 + k) + 1] = (T)v[k].end;
+            }
+        }
+    }
+}
+}  // extern "C++"
+
+}  // namespace
+
+tgx_status tgx_result_spans_device(tgx_model* m, const tgx_result* r, const uint8_t* special_bytes, const uint64_t* special_offs,
+                                   uint32_t n_specials, uint32_t flags, void* stream, void* d_spans) {
+    return spans_device("tgx_result_spans_device", m, r, special_bytes, special_offs, n_specials, 0, TGX_NO_ID, TGX_NO_ID, flags, stream, d_spans);
+}
+
+tgx_status tgx_result_pad_spans_device(tgx_model* m, const tgx_result* r, const uint8_t* special_bytes, const uint64_t* special_offs,
+                                       uint32_t n_specials, uint32_t row_len, uint32_t bos_id, uint32_t eos_id, uint32_t flags, void* stream,
+                                       void* d_spans) {
+    const char* who = "tgx_result_pad_spans_device";
+    if (row_len == 0) return fail(TGX_ERR_INVALID, "%s: row_len 0 (needs >= 1)", who);
+    return spans_device(who, m, r, special_bytes, special_offs, n_specials, row_len, bos_id, eos_id, flags, stream, d_spans);
+}
+
+tgx_status tgx_spans_host(const uint8_t* vocab_bytes, const uint64_t* vocab_offs, uint32_t vocab_size, const uint8_t* special_bytes,
+                          const uint64_t* special_offs, uint32_t n_specials, const uint32_t* ids, const uint64_t* offs, uint64_t n_rows,
+                          uint32_t row_len, uint32_t bos_id, uint32_t eos_id, uint32_t flags, void* out) {
+    const char* who = "tgx_spans_host";
+    if (!vocab_offs) return fail(TGX_ERR_INVALID, "%s: vocab_offs is NULL", who);
+    const bool padded = row_len != 0, chars = (flags & TGX_SPAN_CHARS) != 0, i64 = (flags & TGX_LAYOUT_I64) != 0;
+    tgx_status st = span_check_args(who, vocab_size, special_bytes, special_offs, n_specials, padded, row_len, bos_id, eos_id, flags);
+    if (st == TGX_OK) st = layout_check_host(who, ids, offs, n_rows);
+    if (st != TGX_OK) return st;
+    const uint64_t S = n_rows, T = offs[S];
+    const uint64_t n_pairs = padded ? S * (uint64_t)row_len : (S ? T : 0);
+    if (n_pairs == 0) return TGX_OK;
+    if (!out) return fail(TGX_ERR_INVALID, "%s: out is NULL", who);
+    std::vector<uint16_t> words;
+    if ((st = span_build_words(who, vocab_bytes, vocab_offs, vocab_size, &words)) != TGX_OK) return st;
+    std::vector<uint64_t> sp_words;
+    span_special_words(special_bytes, special_offs, n_specials, chars, &sp_words);
+    tgx::SpanTables tab = {};
+    tab.words = words.data();
+    tab.sp_words = sp_words.data();
+    tab.vocab_size = vocab_size;
+    tab.n_specials = n_specials;
+    // the meta pass and the scan
+    std::vector<uint32_t> vals((size_t)T + 1, 0);
+    std::vector<uint64_t> P((size_t)T + 1, 0);
+    for (uint64_t j = 0; j < T; j++) {
+        bool oob;
+        vals[j] = tgx::span_val(tab, ids[j], chars, &oob);
+        if (oob) {
+            const uint64_t row = (uint64_t)(std::upper_bound(offs, offs + S + 1, j) - offs) - 1;
+            return decode_oob(tgx::kDecodeU32, ids[j], row, nullptr, nullptr);
+        }
+        P[j + 1] = P[j] + (vals[j] & ~tgx::kSpanValCont);
+    }
+    if (!i64) {
+        uint64_t row_max = 0;
+        for (uint64_t i = 0; i < S; i++) row_max = std::max(row_max, tgx::span_row_total(P.data(), offs, i));
+        if (row_max >= 0x80000000ull) return span_too_long(who, row_max, chars);
+    }
+    const tgx::LayoutSeq seq = tgx::layout_seq(bos_id, eos_id, 0);
+    const uint32_t* v = chars ? vals.data() : nullptr;
+    if (i64)
+        spans_host_write(seq, offs, S, T, P.data(), v, row_len, flags, static_cast<int64_t*>(out));
+    else
+        spans_host_write(seq, offs, S, T, P.data(), v, row_len, flags, static_cast<int32_t*>(out));
     return TGX_OK;
 }
 

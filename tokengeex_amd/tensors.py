@@ -3,7 +3,8 @@
 A NativeResult (of encode, sampling or n-best: n-best rows are just rows) holds flat u32 ids and u64 offsets in HBM.
 `to_padded` and `to_packed` lay them out for a model — [S, L] `input_ids` with `attention_mask`, or the documents
 concatenated and cut into [B, L] blocks — with the kernels of csrc/layout.hip, straight into tensors allocated with
-`torch.empty`: the ids never visit the host.
+`torch.empty`: the ids never visit the host.  `to_spans` and `to_padded_spans` give the offsets mapping the same way:
+the part of its row's text that every token covers, in bytes or characters (csrc/spans.hip).
 
 The kernels are queued on `torch.cuda.current_stream(device)`, the stream torch's caching allocator orders the
 tensors' memory on, and the call returns once that stream has reached its end: the tensors can be used by any torch op
@@ -180,3 +181,85 @@ def decode_padded(model: "_lib.NativeModel", input_ids, *, attention_mask=None, 
     stream = torch.cuda.current_stream(dev).cuda_stream
     return model.decode_padded(p_ids, S, L, input_ids.dtype == torch.int64, mask_ptr=p_mask, lengths_ptr=p_len, skip_id=skip_id,
                                special_flat=special_flat, special_offs=special_offs, include_special=include_special, stream=stream)
+
+
+# ---- token spans: which part of its row's text a token covers (csrc/spans.hip) -----------------------------------------
+
+def _special_arrays(specials):
+    """None, a list of special tokens (bytes or str), or their packed form (uint8 flat, uint64 offsets) -> the packed form."""
+    import numpy as np
+    if specials is None:
+        return np.zeros(0, np.uint8), np.zeros(1, np.uint64)
+    if isinstance(specials, tuple) and len(specials) == 2 and all(isinstance(a, np.ndarray) for a in specials):
+        return specials
+    return _lib.pack([t.encode("utf-8") if isinstance(t, str) else bytes(t) for t in specials])
+
+
+def _span_dest(torch, result, model, spans, numel: int):
+    if result.device != model.device:
+        raise ValueError(f"the result is on device {result.device}, the model on device {model.device}")
+    dev = _device_of(torch, result)
+    if not isinstance(spans, torch.Tensor):
+        raise TypeError("spans must be a torch.Tensor")
+    _np_dtype(torch, spans.dtype)
+    return dev, _check_dest(torch, "spans", spans, dev, spans.dtype, numel)
+
+
+def spans_into(result: "_lib.NativeResult", model: "_lib.NativeModel", spans, specials=None, *, unit: str = "byte") -> None:
+    """The span of every token in its row's text written into a tensor the caller owns (int32 or int64, contiguous, on the
+    result's device, at least num_tokens·2 elements; checked before anything is launched): element (j, 0) is the start
+    and (j, 1) the end of token j, in bytes or (unit "char") code points, relative to the token's own row."""
+    import torch
+    dev, p = _span_dest(torch, result, model, spans, result.num_tokens * 2 if result.num_samples else 0)
+    sf, so = _special_arrays(specials)
+    flags = _lib.span_flags(unit, _np_dtype(torch, spans.dtype))
+    model.result_spans(result, sf, so, p, flags=flags, stream=torch.cuda.current_stream(dev).cuda_stream)
+
+
+def pad_spans_into(result: "_lib.NativeResult", model: "_lib.NativeModel", spans, specials=None, *, row_len: int, unit: str = "byte",
+                   bos_id: int | None = None, eos_id: int | None = None, padding_side: str = "right",
+                   truncation_side: str = "right") -> None:
+    """spans_into in the padded form: at least S·row_len·2 elements, aligned element for element with pad_into's input_ids
+    for the same row_len, bos_id, eos_id and sides; bos, eos and padding get (0, 0)."""
+    import torch
+    L = int(row_len)
+    if L < 1:
+        raise _lib.TokenGeeXError("row_len must be at least 1", _lib.ERR_INVALID)
+    dev, p = _span_dest(torch, result, model, spans, result.num_samples * L * 2)
+    sf, so = _special_arrays(specials)
+    flags = _lib.span_flags(unit, _np_dtype(torch, spans.dtype), padding_side, truncation_side)
+    model.result_pad_spans(result, sf, so, L, p, bos_id=bos_id, eos_id=eos_id, flags=flags,
+                           stream=torch.cuda.current_stream(dev).cuda_stream)
+
+
+def to_spans(result: "_lib.NativeResult", model: "_lib.NativeModel", specials=None, unit: str = "byte", dtype=None):
+    """-> [T, 2] of dtype (torch.int64 by default, or torch.int32) on the result's device: the (start, end) of every token
+    in its row's text.  `specials`: the special tokens behind the ids >= model.vocab_size (a list of bytes or str, or
+    their packed form), None when the result has none.  torch.int32 raises TokenGeeXError (ERR_UNSUPPORTED) when a row
+    has 2^31 units or more."""
+    import torch
+    dtype = torch.int64 if dtype is None else dtype
+    _np_dtype(torch, dtype)
+    out = torch.empty((result.num_tokens if result.num_samples else 0, 2), dtype=dtype, device=_device_of(torch, result))
+    spans_into(result, model, out, specials, unit=unit)
+    return out
+
+
+def to_padded_spans(result: "_lib.NativeResult", model: "_lib.NativeModel", specials=None, unit: str = "byte", dtype=None, *,
+                    max_length: int | None = None, bos_id: int | None = None, eos_id: int | None = None,
+                    padding_side: str = "right", truncation_side: str = "right"):
+    """-> [S, L, 2] of dtype: to_spans laid out as to_padded lays the ids out for the same max_length, bos_id, eos_id and
+    sides (max_length=None: the longest row with its bos / eos, at least 1)."""
+    import torch
+    dtype = torch.int64 if dtype is None else dtype
+    _np_dtype(torch, dtype)
+    if max_length is None:
+        L = max(1, result.layout_info(bos_id, eos_id)[0])
+    else:
+        L = int(max_length)
+        if L < 1:
+            raise _lib.TokenGeeXError("max_length must be at least 1", _lib.ERR_INVALID)
+    out = torch.empty((result.num_samples, L, 2), dtype=dtype, device=_device_of(torch, result))
+    pad_spans_into(result, model, out, specials, row_len=L, unit=unit, bos_id=bos_id, eos_id=eos_id, padding_side=padding_side,
+                   truncation_side=truncation_side)
+    return out

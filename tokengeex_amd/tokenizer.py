@@ -346,6 +346,30 @@ class Tokenizer:
             raise TypeError("pad (or pad_id) is required")
         return out
 
+    @staticmethod
+    def _mapping_unit(layout: dict):
+        """Takes return_offsets_mapping out of a layout request -> None, "byte" or "char"."""
+        unit = layout.pop("return_offsets_mapping", None)
+        if unit not in (None, "byte", "char"):
+            raise ValueError(f"return_offsets_mapping must be None, 'byte' or 'char' (got {unit!r})")
+        return unit
+
+    def _with_offset_mapping(self, res, out: dict, layout: dict, unit) -> dict:
+        """Adds "offset_mapping" to a padded layout of `res` (None: a batch without samples) when a unit is asked for."""
+        if unit is None:
+            return out
+        import torch
+        from . import tensors
+        ids = out["input_ids"]
+        if res is None:
+            out["offset_mapping"] = torch.empty((0, ids.shape[1], 2), dtype=ids.dtype, device=ids.device)
+            return out
+        _, _, sf, so = self._vocab_packed()
+        out["offset_mapping"] = tensors.to_padded_spans(
+            res, self._model(), (sf, so), unit, ids.dtype, max_length=ids.shape[1], bos_id=layout.get("bos_id"), eos_id=layout.get("eos_id"),
+            padding_side=layout.get("padding_side", "right"), truncation_side=layout.get("truncation_side", "right"))
+        return out
+
     def _ordinary_result(self, flat: np.ndarray, offs: np.ndarray, dropout: float):
         """The ordinary path of encode_batch_flat up to the device result (processors run, text is not split at special
         tokens) -> NativeResult, or None for an empty batch."""
@@ -364,18 +388,21 @@ class Tokenizer:
         as torch tensors -> {"input_ids": [S, L], "attention_mask": [S, L] uint8 [, "lengths"]} on the tokenizer's device
         (tensors.to_padded: max_length, padding_side, truncation_side, dtype, return_lengths).  pad (required), bos and eos
         are ids or special-token strings (also spelt pad_id / bos_id / eos_id).  The ids go from the encode kernels to the
-        tensors without visiting the host.
+        tensors without visiting the host.  return_offsets_mapping="byte" | "char" adds "offset_mapping": [S, L, 2] in the
+        dtype of input_ids, the (start, end) of every kept token in its sample's processed text (tensors.to_padded_spans);
+        bos, eos and padding get (0, 0).
 
         This is the ORDINARY path: the processors run as in encode_ordinary_batch and the text is not split at special
         tokens — a special token's string inside a text is encoded as ordinary text.  encode_batch_padded_flat is the
         special-aware form: the same layout over encode_batch's ids, put together on the device (encode_batch_result_flat)."""
         from . import tensors
+        unit = self._mapping_unit(layout)
         layout = self._layout_ids(layout)
         res = self._ordinary_result(flat, offs, dropout)
         if res is None:
-            return self._empty_layout(True, None, layout)
+            return self._with_offset_mapping(None, self._empty_layout(True, None, layout), layout, unit)
         try:
-            return tensors.to_padded(res, **layout)
+            return self._with_offset_mapping(res, tensors.to_padded(res, **layout), layout, unit)
         finally:
             res.free()
 
@@ -495,12 +522,13 @@ class Tokenizer:
         """encode_ordinary_batch_padded_flat for the special-aware encode_batch: the text is split at special tokens, which
         get their own ids, and the ids are put together and laid out on the device (encode_batch_result_flat)."""
         from . import tensors
+        unit = self._mapping_unit(layout)
         layout = self._layout_ids(layout)
         res = self.encode_batch_result_flat(flat, offs, dropout)
         if res is None:
-            return self._empty_layout(True, None, layout)
+            return self._with_offset_mapping(None, self._empty_layout(True, None, layout), layout, unit)
         try:
-            return tensors.to_padded(res, **layout)
+            return self._with_offset_mapping(res, tensors.to_padded(res, **layout), layout, unit)
         finally:
             res.free()
 
@@ -738,6 +766,20 @@ class Tokenizer:
 
     def decode_result(self, result: "_lib.NativeResult", include_special_tokens: bool) -> list[str]:
         return self._text_strs(self.decode_result_text(result, include_special_tokens))
+
+    # -- token spans on the device (tensors.to_spans over csrc/spans.hip) --
+    def result_spans(self, result: "_lib.NativeResult", unit: str = "char", dtype=None):
+        """The (start, end) of every token of a device result (of encode_batch_result_flat, encode_corpus, sampling, n-best)
+        in its row's text -> torch tensor [T, 2] on the result's device (torch.int64 by default): code points ("char",
+        indexes a str) or bytes ("byte") of the PROCESSED text, which is what decode(ids, True) returns; a special token's
+        span is its own text.  Neither ids nor text visit the host."""
+        from . import tensors
+        _, _, sf, so = self._vocab_packed()
+        return tensors.to_spans(result, self._model(), (sf, so), unit, dtype)
+
+    def result_spans_flat(self, result: "_lib.NativeResult", unit: str = "char", dtype=None) -> np.ndarray:
+        """result_spans copied to the host -> numpy [T, 2]; row i owns [offsets[i], offsets[i+1])."""
+        return self.result_spans(result, unit, dtype).cpu().numpy()
 
     def _skip_id(self, skip) -> int | None:
         if isinstance(skip, str):
