@@ -1,0 +1,62 @@
+// What tgx_api.cpp and host_twins.cpp share, free of HIP types: the thread-local error state, and the argument checks
+// that the *_host twins (host_twins.cpp) share with the device entry points (tgx_api.cpp).  Shared helpers live in
+// tgx::host.  prune_host.cpp, frontback.cpp and unicode_norm.cpp take tgx_set_error from here.
+#pragma once
+
+#include <cstdarg>
+#include <cstdint>
+#include <cstdio>
+#include <string>
+#include <vector>
+
+#include "../../include/tgx.h"
+
+// records the message tgx_last_error() returns (thread-local); tgx_api.cpp
+tgx_status tgx_set_error(tgx_status st, const char* msg);
+
+namespace tgx {
+struct DecodeSlot;  // decode.h
+}
+
+namespace tgx::host {
+
+// ---- thread-local error state ------------------------------------------------
+inline thread_local std::string g_err_msg;
+inline thread_local uint64_t g_err_sample = 0, g_err_pos = 0, g_err_len = 0;
+
+inline tgx_status fail(tgx_status st, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    g_err_msg = buf;
+    return st;
+}
+// what tgx_last_error_detail() returns
+inline void set_error_detail(uint64_t sample, uint64_t pos, uint64_t len) {
+    g_err_sample = sample;
+    g_err_pos = pos;
+    g_err_len = len;
+}
+
+// ---- argument checks of the *_host twins and of their device entry points (host_twins.cpp) ------------------------
+tgx_status layout_check_ids(const char* who, uint32_t pad_id, uint32_t bos_id, uint32_t eos_id);
+tgx_status layout_check_flags(const char* who, uint32_t flags, uint32_t allowed);
+tgx_status layout_check_row_len(const char* who, uint32_t row_len, uint32_t extra);
+// ids and offsets of n_rows rows in host memory
+tgx_status layout_check_host(const char* who, const uint32_t* ids, const uint64_t* offs, uint64_t n_rows);
+tgx_status assemble_check(const char* who, const uint64_t* seg_offs, const int32_t* seg_special, uint64_t n_samples, uint32_t vocab_size,
+                          uint32_t n_specials, bool have_segs, uint64_t n_rows, uint64_t* n_segs);
+tgx_status decode_build_tables(const char* who, const uint8_t* bytes, const uint64_t* offs, uint32_t V, std::vector<uint8_t>* len,
+                               std::vector<tgx::DecodeSlot>* slots);
+tgx_status decode_check_specials(const char* who, uint32_t vocab_size, const uint8_t* special_bytes, const uint64_t* special_offs, uint32_t n_specials);
+// TGX_ERR_TOKEN_ID_OOB for element x (of a tgx::DecodeSrc::kind) of row `row`, with its error detail
+tgx_status decode_oob(uint32_t kind, int64_t x, uint64_t row, uint64_t* bad_sample, uint64_t* bad_id);
+tgx_status span_build_words(const char* who, const uint8_t* bytes, const uint64_t* offs, uint32_t V, std::vector<uint16_t>* words);
+void span_special_words(const uint8_t* special_bytes, const uint64_t* special_offs, uint32_t n_specials, bool chars, std::vector<uint64_t>* words);
+tgx_status span_check_args(const char* who, uint32_t vocab_size, const uint8_t* special_bytes, const uint64_t* special_offs, uint32_t n_specials,
+                           bool padded, uint32_t row_len, uint32_t bos_id, uint32_t eos_id, uint32_t flags);
+tgx_status span_too_long(const char* who, uint64_t row_max, bool chars);
+
+}  // namespace tgx::host

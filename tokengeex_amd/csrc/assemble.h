@@ -1,5 +1,5 @@
 // Index arithmetic of the assembly of a sample-level result from the result over the non-special segments and the split
-// plan (include/tgx.h: tgx_assemble_result).  The kernels of assemble.hip and the host twin in tgx_api.cpp
+// plan (include/tgx.h: tgx_assemble_result).  The kernels of assemble.hip and the host twin in host_twins.cpp
 // (tgx_assemble_host) both go through these functions, so a machine without a GPU checks the kernels' index arithmetic.
 //
 // Segment k of K is special (seg_special[k] >= 0: one id, V + seg_special[k]) or the next encoded segment.  rank[k] =

@@ -1,5 +1,5 @@
 // Index arithmetic of the decode of ids to UTF-8 text (include/tgx.h: tgx_decode_result, tgx_decode_padded).  The kernels
-// of decode.hip and the host twin in tgx_api.cpp (tgx_decode_rows_host) both go through these functions, so a machine
+// of decode.hip and the host twin in host_twins.cpp (tgx_decode_rows_host) both go through these functions, so a machine
 // without a GPU checks the kernels' arithmetic: liveness and classes of an element, the walk of a thread slot over the
 // elements that cover its 16 output bytes, and String::from_utf8_lossy as a rule that looks at most 3 bytes to either
 // side of a byte inside its run.

@@ -1,0 +1,499 @@
+// The *_host twins of the result-side device entry points (include/tgx.h): tgx_layout_pad_host, tgx_layout_pack_host,
+// tgx_assemble_host, tgx_decode_rows_host and tgx_spans_host, and the argument checks they share with the device entry
+// points of tgx_api.cpp.  A twin goes through the same index arithmetic as its kernels (layout.h, assemble.h,
+// decode.h, spans.h) on host memory.  Nothing in this file calls a HIP function, so it builds and runs without the
+// handles, the pool or a device.
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "api_internal.h"
+#include "assemble.h"
+#include "decode.h"
+#include "layout.h"
+#include "spans.h"
+
+using namespace tgx::host;
+
+// ---- argument checks ----------------------------------------------------------------
+
+namespace {
+
+// A packed list of n items: offs[0 .. n] does not decrease, and starts at 0 where from_zero.  `name` is what the messages
+// call the argument and `plural` its entries.  offs may be NULL only for an empty list that need not start at 0.
+tgx_status check_packed_list(const char* who, const char* name, const char* plural, const uint64_t* offs, uint64_t n, bool from_zero) {
+    if (!offs && (n || from_zero)) return fail(TGX_ERR_INVALID, "%s: %s is NULL", who, name);
+    if (from_zero && offs[0] != 0) return fail(TGX_ERR_INVALID, "%s: %s[0] must be 0", who, name);
+    for (uint64_t i = 0; i < n; i++)
+        if (offs[i + 1] < offs[i]) return fail(TGX_ERR_INVALID, "%s: %s not monotone at %llu", who, plural, (unsigned long long)i);
+    return TGX_OK;
+}
+
+// the special tokens' ids follow the vocabulary's, and TGX_NO_ID is none of them
+tgx_status check_id_room(const char* who, uint32_t vocab_size, uint32_t n_specials) {
+    if ((uint64_t)vocab_size + n_specials > 0xFFFFFFFEull)
+        return fail(TGX_ERR_INVALID, "%s: %u tokens and %u special tokens leave no room for their ids", who, vocab_size, n_specials);
+    return TGX_OK;
+}
+
+}  // namespace
+
+namespace tgx::host {
+
+// a padded row holds at least one element, and its bos / eos (extra: tgx::LayoutSeq::extra)
+tgx_status layout_check_row_len(const char* who, uint32_t row_len, uint32_t extra) {
+    if (row_len < 1 || row_len < extra) return fail(TGX_ERR_INVALID, "%s: row_len %u (needs >= 1 and >= %u for bos / eos)", who, row_len, extra);
+    return TGX_OK;
+}
+
+// TGX_OK when every id a layout writes besides the tokens' is below 2^31 (pad always, bos / eos when present)
+tgx_status layout_check_ids(const char* who, uint32_t pad_id, uint32_t bos_id, uint32_t eos_id) {
+    if (pad_id >= 0x80000000u) return fail(TGX_ERR_INVALID, "%s: pad_id %u is not below 2^31", who, pad_id);
+    if (bos_id != TGX_NO_ID && bos_id >= 0x80000000u) return fail(TGX_ERR_INVALID, "%s: bos_id %u is not below 2^31", who, bos_id);
+    if (eos_id != TGX_NO_ID && eos_id >= 0x80000000u) return fail(TGX_ERR_INVALID, "%s: eos_id %u is not below 2^31", who, eos_id);
+    return TGX_OK;
+}
+
+tgx_status layout_check_flags(const char* who, uint32_t flags, uint32_t allowed) {
+    if (flags & ~allowed) return fail(TGX_ERR_INVALID, "%s: unknown flags 0x%x", who, flags & ~allowed);
+    return TGX_OK;
+}
+
+tgx_status layout_check_host(const char* who, const uint32_t* ids, const uint64_t* offs, uint64_t n_rows) {
+    const tgx_status st = check_packed_list(who, "offs", "offsets", offs, n_rows, true);
+    if (st != TGX_OK) return st;
+    if (offs[n_rows] && !ids) return fail(TGX_ERR_INVALID, "%s: ids is NULL", who);
+    return TGX_OK;
+}
+
+// What tgx_assemble_result and tgx_assemble_host check of a split plan before anything runs.  n_rows: the rows of the
+// segment-level result (0 without one).  *n_segs = K.
+tgx_status assemble_check(const char* who, const uint64_t* seg_offs, const int32_t* seg_special, uint64_t n_samples, uint32_t vocab_size,
+                          uint32_t n_specials, bool have_segs, uint64_t n_rows, uint64_t* n_segs) {
+    tgx_status st = check_packed_list(who, "seg_offs", "seg_offs", seg_offs, n_samples, true);
+    if (st != TGX_OK) return st;
+    const uint64_t K = seg_offs[n_samples];
+    if (K && !seg_special) return fail(TGX_ERR_INVALID, "%s: seg_special is NULL", who);
+    if ((st = check_id_room(who, vocab_size, n_specials)) != TGX_OK) return st;
+    uint64_t E = 0;
+    for (uint64_t k = 0; k < K; k++) {
+        if (seg_special[k] < 0)
+            E++;
+        else if ((uint32_t)seg_special[k] >= n_specials)
+            return fail(TGX_ERR_INVALID, "%s: segment %llu is special token %d of %u", who, (unsigned long long)k, seg_special[k], n_specials);
+    }
+    if (E && !have_segs) return fail(TGX_ERR_INVALID, "%s: %llu encoded segments and no result over them", who, (unsigned long long)E);
+    if (E != n_rows)
+        return fail(TGX_ERR_INVALID, "%s: %llu encoded segments, the result over them has %llu rows", who, (unsigned long long)E,
+                    (unsigned long long)n_rows);
+    *n_segs = K;
+    return TGX_OK;
+}
+
+// lengths and 16-byte slots of a vocabulary's tokens: what the kernels (device copies) and the host twin read
+tgx_status decode_build_tables(const char* who, const uint8_t* bytes, const uint64_t* offs, uint32_t V, std::vector<uint8_t>* len,
+                               std::vector<tgx::DecodeSlot>* slots) {
+    const tgx_status st = check_packed_list(who, "vocabulary offsets", "vocabulary offsets", offs, V, false);
+    if (st != TGX_OK) return st;
+    len->assign(V, 0);
+    slots->assign(V, tgx::DecodeSlot{0, 0});
+    for (uint32_t i = 0; i < V; i++) {
+        const uint64_t n = offs[i + 1] - offs[i];
+        if (n > TGX_MAX_TOKEN_LEN) return fail(TGX_ERR_UNSUPPORTED, "%s: token of %llu bytes exceeds TGX_MAX_TOKEN_LEN (%d)", who, (unsigned long long)n, TGX_MAX_TOKEN_LEN);
+        (*len)[i] = (uint8_t)n;
+        if (n > tgx::kDecodeSlotLen) continue;
+        tgx::DecodeSlot& sl = (*slots)[i];
+        for (uint64_t k = 0; k < n; k++) (k < 8 ? sl.lo : sl.hi) |= (uint64_t)bytes[offs[i] + k] << (8 * (k & 7));
+    }
+    return TGX_OK;
+}
+
+tgx_status decode_check_specials(const char* who, uint32_t vocab_size, const uint8_t* special_bytes, const uint64_t* special_offs, uint32_t n_specials) {
+    tgx_status st = check_packed_list(who, "special_offs", "special_offs", special_offs, n_specials, false);
+    if (st == TGX_OK) st = check_id_room(who, vocab_size, n_specials);
+    if (st != TGX_OK) return st;
+    for (uint32_t k = 0; k < n_specials; k++)
+        if (special_offs[k + 1] - special_offs[k] >= 0x80000000ull) return fail(TGX_ERR_UNSUPPORTED, "%s: special token %u is 2 GiB or longer", who, k);
+    if (n_specials && special_offs[n_specials] > special_offs[0] && !special_bytes) return fail(TGX_ERR_INVALID, "%s: special_bytes is NULL", who);
+    return TGX_OK;
+}
+
+tgx_status decode_oob(uint32_t kind, int64_t x, uint64_t row, uint64_t* bad_sample, uint64_t* bad_id) {
+    if (bad_sample) *bad_sample = row;
+    if (bad_id) *bad_id = (uint64_t)x;
+    g_err_sample = row;
+    g_err_pos = (uint64_t)x;
+    if (kind == tgx::kDecodeU32) return fail(TGX_ERR_TOKEN_ID_OOB, "token id %llu is out of bounds", (unsigned long long)x);
+    return fail(TGX_ERR_TOKEN_ID_OOB, "token id %lld is out of bounds", (long long)x);
+}
+
+// one word per token of a vocabulary: what the meta kernel (a device copy) and the host twin read
+tgx_status span_build_words(const char* who, const uint8_t* bytes, const uint64_t* offs, uint32_t V, std::vector<uint16_t>* words) {
+    const tgx_status st = check_packed_list(who, "vocabulary offsets", "vocabulary offsets", offs, V, false);
+    if (st != TGX_OK) return st;
+    words->assign(V, 0);
+    for (uint32_t i = 0; i < V; i++) {
+        const uint64_t n = offs[i + 1] - offs[i];
+        if (n > TGX_MAX_TOKEN_LEN) return fail(TGX_ERR_UNSUPPORTED, "%s: token of %llu bytes exceeds TGX_MAX_TOKEN_LEN (%d)", who, (unsigned long long)n, TGX_MAX_TOKEN_LEN);
+        (*words)[i] = tgx::span_word(bytes + offs[i], (uint32_t)n);
+    }
+    return TGX_OK;
+}
+
+// the special tokens' words; the byte unit reads no byte of theirs
+void span_special_words(const uint8_t* special_bytes, const uint64_t* special_offs, uint32_t n_specials, bool chars, std::vector<uint64_t>* words) {
+    words->assign((size_t)n_specials + 1, 0);
+    for (uint32_t k = 0; k < n_specials; k++)
+        (*words)[k] = tgx::span_special_word(chars ? special_bytes + special_offs[k] : nullptr, special_offs[k + 1] - special_offs[k]);
+}
+
+// flags, specials and the padded form's arguments: what the device entry points and the host twin check alike
+tgx_status span_check_args(const char* who, uint32_t vocab_size, const uint8_t* special_bytes, const uint64_t* special_offs, uint32_t n_specials,
+                           bool padded, uint32_t row_len, uint32_t bos_id, uint32_t eos_id, uint32_t flags) {
+    tgx_status st = layout_check_flags(who, flags, TGX_LAYOUT_I64 | TGX_SPAN_CHARS | (padded ? TGX_LAYOUT_PAD_LEFT | TGX_LAYOUT_TRUNC_LEFT : 0u));
+    static const uint8_t unread = 0;  // the byte unit does not look at special_bytes, which may then be NULL
+    if (st == TGX_OK) st = decode_check_specials(who, vocab_size, (flags & TGX_SPAN_CHARS) ? special_bytes : &unread, special_offs, n_specials);
+    if (st == TGX_OK && padded) st = layout_check_ids(who, 0, bos_id, eos_id);
+    if (st != TGX_OK) return st;
+    return padded ? layout_check_row_len(who, row_len, tgx::layout_seq(bos_id, eos_id, 0).extra) : TGX_OK;
+}
+
+tgx_status span_too_long(const char* who, uint64_t row_max, bool chars) {
+    return fail(TGX_ERR_UNSUPPORTED, "%s: a row of %llu %s does not fit int32 spans (TGX_LAYOUT_I64 takes it)", who, (unsigned long long)row_max,
+                chars ? "characters" : "bytes");
+}
+
+}  // namespace tgx::host
+
+// ---- layouts ----------------------------------------------------------------------
+
+namespace {
+
+template <class T>
+tgx_status layout_pad_host(const tgx::LayoutSeq& seq, const uint32_t* ids, const uint64_t* offs, uint64_t n_rows, uint32_t L, uint32_t flags,
+                           T* out, uint8_t* mask, int32_t* lengths, uint64_t* n_truncated) {
+    // as the kernel: the flat [S, L] output in groups of kLayoutGroup consecutive elements, each walked by pad_group
+    const uint64_t total = n_rows * (uint64_t)L;
+    unsigned long long truncated = 0;
+    for (uint64_t e0 = 0; e0 < total; e0 += tgx::kLayoutGroup) {
+        const uint32_t n_in = total - e0 < tgx::kLayoutGroup ? (uint32_t)(total - e0) : tgx::kLayoutGroup;
+        uint32_t v[tgx::kLayoutGroup] = {0, 0, 0, 0};
+        const uint32_t m = tgx::pad_group(seq, ids, offs, L, flags, e0, n_in, lengths, v, &truncated);
+        for (uint32_t k = 0; k < n_in; k++) {
+            if (v[k] >= 0x80000000u)
+                return fail(TGX_ERR_INVALID, "tgx_layout_pad_host: id %u of row %llu is not below 2^31", v[k], (unsigned long long)((e0 + k) / L));
+            out[e0 + k] = (T)v[k];
+            if (mask) mask[e0 + k] = (uint8_t)(m >> (8 * k));
+        }
+    }
+    if (n_truncated) *n_truncated = truncated;
+    return TGX_OK;
+}
+
+template <class T>
+tgx_status layout_pack_host(const tgx::LayoutSeq& seq, const uint32_t* ids, const uint64_t* offs, uint64_t n_rows, uint64_t n_stream,
+                            uint64_t n_out, T* out, int32_t* doc, int32_t* pos) {
+    // as the kernel: tiles of kPackTile positions, the owners of a tile's ends bound the search inside it, and a
+    // group of four consecutive positions walks on from row to row
+    uint64_t lo = 0, hi = 0;
+    tgx::PackCursor cur;
+    for (uint64_t j = 0; j < n_out; j++) {
+        uint32_t id = seq.pad;
+        int32_t d = -1, q = 0;
+        if (j % tgx::kPackTile == 0 && j < n_stream) {
+            const uint64_t last = j + tgx::kPackTile - 1 < n_stream ? j + tgx::kPackTile - 1 : n_stream - 1;
+            lo = tgx::pack_find_row(offs, seq.extra, 0, n_rows - 1, j);
+            hi = tgx::pack_find_row(offs, seq.extra, 0, n_rows - 1, last);
+        }
+        if (j % 4 == 0) cur = tgx::PackCursor();
+        if (j < n_stream) {
+            const uint64_t i = tgx::pack_advance(cur, offs, seq.extra, lo, hi, j);
+            id = tgx::pack_at(seq, ids, offs, i, j, &q);
+            d = (int32_t)i;
+            if (id >= 0x80000000u) return fail(TGX_ERR_INVALID, "tgx_layout_pack_host: id %u of row %llu is not below 2^31", id, (unsigned long long)i);
+        }
+        out[j] = (T)id;
+        if (doc) doc[j] = d;
+        if (pos) pos[j] = q;
+    }
+    return TGX_OK;
+}
+
+}  // namespace
+
+tgx_status tgx_layout_pad_host(const uint32_t* ids, const uint64_t* offs, uint64_t n_rows, uint32_t row_len, uint32_t pad_id,
+                               uint32_t bos_id, uint32_t eos_id, uint32_t flags, void* out_ids, uint8_t* out_mask,
+                               int32_t* out_lengths, uint64_t* n_truncated) {
+    const char* who = "tgx_layout_pad_host";
+    if (!out_ids && n_rows) return fail(TGX_ERR_INVALID, "%s: out_ids is NULL", who);
+    tgx_status st = layout_check_host(who, ids, offs, n_rows);
+    if (st == TGX_OK) st = layout_check_flags(who, flags, TGX_LAYOUT_PAD_LEFT | TGX_LAYOUT_TRUNC_LEFT | TGX_LAYOUT_I64);
+    if (st == TGX_OK) st = layout_check_ids(who, pad_id, bos_id, eos_id);
+    if (st != TGX_OK) return st;
+    const tgx::LayoutSeq seq = tgx::layout_seq(bos_id, eos_id, pad_id);
+    if ((st = layout_check_row_len(who, row_len, seq.extra)) != TGX_OK) return st;
+    if (flags & TGX_LAYOUT_I64)
+        return layout_pad_host(seq, ids, offs, n_rows, row_len, flags, static_cast<int64_t*>(out_ids), out_mask, out_lengths, n_truncated);
+    return layout_pad_host(seq, ids, offs, n_rows, row_len, flags, static_cast<int32_t*>(out_ids), out_mask, out_lengths, n_truncated);
+}
+
+tgx_status tgx_layout_pack_host(const uint32_t* ids, const uint64_t* offs, uint64_t n_rows, uint32_t block_len, uint32_t pad_id,
+                                uint32_t bos_id, uint32_t eos_id, uint32_t flags, void* out_ids, int32_t* out_doc,
+                                int32_t* out_pos, uint64_t* n_blocks) {
+    const char* who = "tgx_layout_pack_host";
+    if (!n_blocks) return fail(TGX_ERR_INVALID, "%s: n_blocks is NULL", who);
+    tgx_status st = layout_check_host(who, ids, offs, n_rows);
+    if (st == TGX_OK) st = layout_check_flags(who, flags, TGX_LAYOUT_I64);
+    if (st == TGX_OK) st = layout_check_ids(who, pad_id, bos_id, eos_id);
+    if (st != TGX_OK) return st;
+    if (block_len < 1) return fail(TGX_ERR_INVALID, "%s: block_len is 0", who);
+    if (n_rows >= 0x80000000ull) return fail(TGX_ERR_UNSUPPORTED, "%s: 2^31 rows or more", who);
+    const tgx::LayoutSeq seq = tgx::layout_seq(bos_id, eos_id, pad_id);
+    const uint64_t n_stream = offs[n_rows] + n_rows * seq.extra;
+    const uint64_t nb = (n_stream + block_len - 1) / block_len;
+    *n_blocks = nb;
+    if (nb == 0) return TGX_OK;
+    if (!out_ids) return fail(TGX_ERR_INVALID, "%s: out_ids is NULL", who);
+    if (flags & TGX_LAYOUT_I64)
+        return layout_pack_host(seq, ids, offs, n_rows, n_stream, nb * block_len, static_cast<int64_t*>(out_ids), out_doc, out_pos);
+    return layout_pack_host(seq, ids, offs, n_rows, n_stream, nb * block_len, static_cast<int32_t*>(out_ids), out_doc, out_pos);
+}
+
+// ---- assembly ---------------------------------------------------------------------
+
+tgx_status tgx_assemble_host(const uint32_t* ids, const uint64_t* id_offs, uint64_t n_encoded, const uint64_t* seg_offs,
+                             const int32_t* seg_special, uint64_t n_samples, uint32_t vocab_size, uint32_t n_specials, uint32_t* out_ids,
+                             uint64_t ids_cap, uint64_t* out_offs) {
+    const char* who = "tgx_assemble_host";
+    if (!out_offs) return fail(TGX_ERR_INVALID, "%s: out_offs is NULL", who);
+    uint64_t K = 0;
+    tgx_status st = assemble_check(who, seg_offs, seg_special, n_samples, vocab_size, n_specials, id_offs != nullptr, n_encoded, &K);
+    if (st != TGX_OK) return st;
+    static const uint64_t kNoOffs[1] = {0};
+    if (!id_offs) id_offs = kNoOffs;
+    if ((st = layout_check_host(who, ids, id_offs, n_encoded)) != TGX_OK) return st;
+    const uint64_t n_out = id_offs[n_encoded] + (K - n_encoded);
+    if (ids_cap < n_out) return fail(TGX_ERR_INVALID, "%s: %llu ids, room for %llu", who, (unsigned long long)n_out, (unsigned long long)ids_cap);
+    if (n_out && !out_ids) return fail(TGX_ERR_INVALID, "%s: out_ids is NULL", who);
+    // as the device: the ranks, the starts with the samples' offsets, then the kernel's tiles and thread slots
+    std::vector<uint64_t> rank(K + 1), starts(K + 1);
+    for (uint64_t k = 0, r = 0; k <= K; k++) {
+        rank[k] = r;
+        if (k < K && seg_special[k] < 0) r++;
+    }
+    for (uint64_t k = 0; k <= K; k++) starts[k] = tgx::assemble_seg_start(id_offs, rank.data(), k);
+    for (uint64_t i = 0; i <= n_samples; i++) out_offs[i] = tgx::assemble_seg_start(id_offs, rank.data(), seg_offs[i]);
+    for (uint64_t t0 = 0; t0 < n_out; t0 += tgx::kAssembleTile) {
+        const uint64_t last = tgx::assemble_tile_last(t0, n_out);
+        const uint64_t lo = tgx::assemble_find_seg(starts.data(), 0, K - 1, t0), hi = tgx::assemble_find_seg(starts.data(), 0, K - 1, last);
+        for (uint64_t e0 = t0; e0 <= last; e0 += tgx::kAssembleGroup) {
+            const uint32_t n_in = last + 1 - e0 < tgx::kAssembleGroup ? (uint32_t)(last + 1 - e0) : tgx::kAssembleGroup;
+            uint32_t v[tgx::kAssembleGroup] = {0, 0, 0, 0};
+            tgx::assemble_group(ids, starts.data(), rank.data(), seg_special, vocab_size, lo, hi, e0, n_in, v);
+            for (uint32_t q = 0; q < n_in; q++) out_ids[e0 + q] = v[q];
+        }
+    }
+    return TGX_OK;
+}
+
+// ---- decode -----------------------------------------------------------------------
+
+tgx_status tgx_decode_rows_host(const uint8_t* vocab_bytes, const uint64_t* vocab_offs, uint32_t vocab_size, const uint8_t* special_bytes,
+                                const uint64_t* special_offs, uint32_t n_specials, const void* ids, uint32_t id_kind, const uint64_t* id_offs,
+                                uint64_t n_rows, uint64_t row_len, const uint8_t* mask, const int32_t* lengths, uint32_t skip_id, int include_special,
+                                uint8_t** out_text, uint64_t* out_offs, uint64_t* n_replaced, uint64_t* bad_sample, uint64_t* bad_id) {
+    const char* who = "tgx_decode_rows_host";
+    if (!vocab_offs || !out_text || !out_offs) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
+    *out_text = nullptr;
+    if (id_kind > tgx::kDecodeI64) return fail(TGX_ERR_INVALID, "%s: id_kind %u", who, id_kind);
+    if (id_offs && id_kind != tgx::kDecodeU32) return fail(TGX_ERR_INVALID, "%s: the offsets form takes u32 ids", who);
+    tgx_status st = decode_check_specials(who, vocab_size, special_bytes, special_offs, n_specials);
+    if (st != TGX_OK) return st;
+    if (id_offs && (st = layout_check_host(who, static_cast<const uint32_t*>(ids), id_offs, n_rows)) != TGX_OK) return st;
+    if (!id_offs && n_rows && row_len && n_rows > 0xFFFFFFFFFFFFFFFFull / 16 / row_len) return fail(TGX_ERR_UNSUPPORTED, "%s: too many elements", who);
+    const uint64_t S = n_rows, N = id_offs ? id_offs[S] : n_rows * row_len;
+    if (N && !ids) return fail(TGX_ERR_INVALID, "%s: ids is NULL", who);
+    std::vector<uint8_t> len;
+    std::vector<tgx::DecodeSlot> slots;
+    if ((st = decode_build_tables(who, vocab_bytes, vocab_offs, vocab_size, &len, &slots)) != TGX_OK) return st;
+    static const uint64_t kNoOffs[1] = {0};
+    tgx::DecodeTables tab = {};
+    tab.tok_len = len.data();
+    tab.slots = slots.data();
+    tab.bytes = vocab_bytes;
+    tab.offs = vocab_offs;
+    tab.sp_bytes = special_bytes;
+    tab.sp_offs = n_specials ? special_offs : kNoOffs;
+    tab.vocab_size = vocab_size;
+    tab.n_specials = n_specials;
+    tab.include_special = include_special ? 1 : 0;
+    tgx::DecodeSrc src = {};
+    src.ids = ids;
+    src.offs = id_offs;
+    src.mask = id_offs ? nullptr : mask;
+    src.lengths = id_offs ? nullptr : lengths;
+    src.n_rows = S;
+    src.row_len = row_len;
+    src.n = N;
+    src.kind = id_kind;
+    src.skip_id = id_offs ? TGX_NO_ID : skip_id;
+    if (n_replaced) *n_replaced = 0;
+    for (uint64_t i = 0; i <= S; i++) out_offs[i] = 0;
+    // as the device: the elements' meta words, the two scans, ...
+    std::vector<uint64_t> B(N + 1), X(N + 1);
+    uint64_t bad = ~0ull, n_live_specials = 0;
+    for (uint64_t j = 0, b = 0, x = 0; j <= N; j++) {
+        B[j] = b;
+        X[j] = x;
+        if (j == N) break;
+        const int64_t v = tgx::decode_elem(src, j);
+        if (!tgx::decode_live(src, j, v)) continue;
+        bool oob;
+        const uint32_t meta = tgx::decode_meta(tab, v, &oob);
+        if (oob && j < bad) bad = j;
+        b += meta & ~tgx::kDecodeSpecial;
+        x += meta >> 31;
+        n_live_specials += meta >> 31;
+    }
+    if (bad != ~0ull) {
+        const uint64_t row = id_offs ? (uint64_t)(std::upper_bound(id_offs, id_offs + S + 1, bad) - id_offs) - 1 : bad / row_len;
+        return decode_oob(id_kind, tgx::decode_elem(src, bad), row, bad_sample, bad_id);
+    }
+    const uint64_t T = B[N], G = (T + tgx::kDecodeGroup - 1) / tgx::kDecodeGroup;
+    uint8_t* raw = static_cast<uint8_t*>(aligned_alloc(16, (size_t)G * tgx::kDecodeGroup + 16));
+    if (!raw) return fail(TGX_ERR_INVALID, "%s: out of host memory", who);
+    if (T == 0) {
+        *out_text = raw;
+        return TGX_OK;
+    }
+    memset(raw, 0xA5, (size_t)G * tgx::kDecodeGroup + 16);  // (what lies behind the text may be anything)
+    std::vector<uint32_t> flags(G), codes(G + 1, 0);
+    // ... the fill kernel's tiles and thread slots, ...
+    for (uint64_t t0 = 0; t0 < T; t0 += tgx::kDecodeTile) {
+        const uint64_t last = tgx::decode_tile_last(t0, T);
+        const uint64_t lo = tgx::decode_find(B.data(), 0, N - 1, tgx::decode_tile_first(t0)), hi = tgx::decode_find(B.data(), 0, N - 1, last);
+        for (uint64_t e0 = t0; e0 <= last; e0 += tgx::kDecodeGroup) {
+            const uint32_t n_in = last + 1 - e0 < tgx::kDecodeGroup ? (uint32_t)(last + 1 - e0) : tgx::kDecodeGroup;
+            uint8_t v[tgx::kDecodeGroup] = {};
+            flags[e0 / tgx::kDecodeGroup] = tgx::decode_group(tab, src, B.data(), n_live_specials ? X.data() : nullptr, lo, hi, e0, n_in, v);
+            memcpy(raw + e0, v, n_in);
+        }
+    }
+    // ... the rows' raw starts, which start runs, ...
+    for (uint64_t i = 0; i <= S; i++) {
+        const uint64_t r = B[i < S ? tgx::decode_row_first(src, i) : N];
+        out_offs[i] = r;
+        if (r < T) flags[r / tgx::kDecodeGroup] |= 1u << (uint32_t)(r % tgx::kDecodeGroup);
+    }
+    // ... the UTF-8 rule per slot, ...
+    uint64_t replaced = 0;
+    for (uint64_t g = 0; g < G; g++) {
+        codes[g] = tgx::decode_utf8_slot(raw, flags.data(), T, g);
+        replaced += tgx::decode_code_replaced(codes[g]);
+    }
+    if (n_replaced) *n_replaced = replaced;
+    if (replaced == 0) {
+        *out_text = raw;
+        return TGX_OK;
+    }
+    // ... and, after a replacement, the slots' positions and the second copy
+    std::vector<uint64_t> gpos(G + 1);
+    for (uint64_t g = 0, at = 0; g <= G; g++) {
+        gpos[g] = at;
+        at += tgx::decode_code_bytes(codes[g], tgx::kDecodeGroup);
+    }
+    uint8_t* text = static_cast<uint8_t*>(malloc((size_t)std::max<uint64_t>(1, gpos[G])));
+    if (!text) {
+        free(raw);
+        return fail(TGX_ERR_INVALID, "%s: out of host memory", who);
+    }
+    for (uint64_t g = 0; g < G; g++) tgx::decode_expand_slot(raw, T, g, codes[g], text, gpos[g]);
+    for (uint64_t i = 0; i <= S; i++) out_offs[i] = tgx::decode_final_pos(gpos.data(), codes.data(), out_offs[i], T);
+    free(raw);
+    *out_text = text;
+    return TGX_OK;
+}
+
+// ---- spans ------------------------------------------------------------------------
+
+namespace {
+
+template <class T>
+void spans_host_write(const tgx::LayoutSeq& seq, const uint64_t* offs, uint64_t n_rows, uint64_t n, const uint64_t* P, const uint32_t* vals,
+                      uint32_t row_len, uint32_t flags, T* out) {
+    if (row_len) {  // as the kernel: one pair per slot
+        for (uint64_t e = 0; e < n_rows * (uint64_t)row_len; e++) {
+            tgx::SpanPair s = {0, 0};
+            if (n) s = tgx::span_pad_at(seq, offs, P, vals, row_len, flags, e);
+            out[2 * e] = (T)s.start;
+            out[2 * e + 1] = (T)s.end;
+        }
+        return;
+    }
+    // as the kernel: tiles of kSpanTile elements, the owners of a tile's ends bound the search inside it, and a group of
+    // consecutive elements walks on from row to row
+    for (uint64_t t0 = 0; t0 < n; t0 += tgx::kSpanTile) {
+        const uint64_t last = tgx::span_tile_last(t0, n);
+        const uint64_t lo = tgx::pack_find_row(offs, 0, 0, n_rows - 1, t0), hi = tgx::pack_find_row(offs, 0, 0, n_rows - 1, last);
+        for (uint64_t e0 = t0; e0 <= last; e0 += tgx::kSpanGroup) {
+            const uint32_t n_in = last + 1 - e0 < tgx::kSpanGroup ? (uint32_t)(last + 1 - e0) : tgx::kSpanGroup;
+            tgx::SpanPair v[tgx::kSpanGroup] = {};
+            tgx::span_group(offs, P, vals, lo, hi, e0, n_in, v);
+            for (uint32_t k = 0; k < n_in; k++) {
+                out[2 * (e0 + k)] = (T)v[k].start;
+                out[2 * (e0 + k) + 1] = (T)v[k].end;
+            }
+        }
+    }
+}
+
+}  // namespace
+
+tgx_status tgx_spans_host(const uint8_t* vocab_bytes, const uint64_t* vocab_offs, uint32_t vocab_size, const uint8_t* special_bytes,
+                          const uint64_t* special_offs, uint32_t n_specials, const uint32_t* ids, const uint64_t* offs, uint64_t n_rows,
+                          uint32_t row_len, uint32_t bos_id, uint32_t eos_id, uint32_t flags, void* out) {
+    const char* who = "tgx_spans_host";
+    if (!vocab_offs) return fail(TGX_ERR_INVALID, "%s: vocab_offs is NULL", who);
+    const bool padded = row_len != 0, chars = (flags & TGX_SPAN_CHARS) != 0, i64 = (flags & TGX_LAYOUT_I64) != 0;
+    tgx_status st = span_check_args(who, vocab_size, special_bytes, special_offs, n_specials, padded, row_len, bos_id, eos_id, flags);
+    if (st == TGX_OK) st = layout_check_host(who, ids, offs, n_rows);
+    if (st != TGX_OK) return st;
+    const uint64_t S = n_rows, T = offs[S];
+    const uint64_t n_pairs = padded ? S * (uint64_t)row_len : (S ? T : 0);
+    if (n_pairs == 0) return TGX_OK;
+    if (!out) return fail(TGX_ERR_INVALID, "%s: out is NULL", who);
+    std::vector<uint16_t> words;
+    if ((st = span_build_words(who, vocab_bytes, vocab_offs, vocab_size, &words)) != TGX_OK) return st;
+    std::vector<uint64_t> sp_words;
+    span_special_words(special_bytes, special_offs, n_specials, chars, &sp_words);
+    tgx::SpanTables tab = {};
+    tab.words = words.data();
+    tab.sp_words = sp_words.data();
+    tab.vocab_size = vocab_size;
+    tab.n_specials = n_specials;
+    // the meta pass and the scan
+    std::vector<uint32_t> vals((size_t)T + 1, 0);
+    std::vector<uint64_t> P((size_t)T + 1, 0);
+    for (uint64_t j = 0; j < T; j++) {
+        bool oob;
+        vals[j] = tgx::span_val(tab, ids[j], chars, &oob);
+        if (oob) {
+            const uint64_t row = (uint64_t)(std::upper_bound(offs, offs + S + 1, j) - offs) - 1;
+            return decode_oob(tgx::kDecodeU32, ids[j], row, nullptr, nullptr);
+        }
+        P[j + 1] = P[j] + (vals[j] & ~tgx::kSpanValCont);
+    }
+    if (!i64) {
+        uint64_t row_max = 0;
+        for (uint64_t i = 0; i < S; i++) row_max = std::max(row_max, tgx::span_row_total(P.data(), offs, i));
+        if (row_max >= 0x80000000ull) return span_too_long(who, row_max, chars);
+    }
+    const tgx::LayoutSeq seq = tgx::layout_seq(bos_id, eos_id, 0);
+    const uint32_t* v = chars ? vals.data() : nullptr;
+    if (i64)
+        spans_host_write(seq, offs, S, T, P.data(), v, row_len, flags, static_cast<int64_t*>(out));
+    else
+        spans_host_write(seq, offs, S, T, P.data(), v, row_len, flags, static_cast<int32_t*>(out));
+    return TGX_OK;
+}

@@ -1,5 +1,5 @@
 // Row mapping of the padded and packed layouts of a result (include/tgx.h: tgx_result_pad_device, tgx_result_pack_device).
-// The kernels of layout.hip and the host twins in tgx_api.cpp (tgx_layout_pad_host, tgx_layout_pack_host) both go
+// The kernels of layout.hip and the host twins in host_twins.cpp (tgx_layout_pad_host, tgx_layout_pack_host) both go
 // through these functions, so a machine without a GPU checks the kernels' index arithmetic.
 //
 // Row i has the tokens ids[offs[i] .. offs[i+1]); offs[0] = 0.  A = how many of bos / eos are present.  A written

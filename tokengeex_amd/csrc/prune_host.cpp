@@ -14,7 +14,7 @@
 #include "trie_build.h"
 
 
-tgx_status tgx_set_error(tgx_status st, const char* msg);  // tgx_api.cpp: the message tgx_last_error() returns
+#include "api_internal.h"  // tgx_set_error: the message tgx_last_error() returns
 
 namespace {
 

@@ -1,5 +1,5 @@
 // Index arithmetic of the token spans (include/tgx.h: tgx_result_spans_device, tgx_result_pad_spans_device).  The
-// kernels of spans.hip and the host twin in tgx_api.cpp (tgx_spans_host) both go through these functions, so a machine
+// kernels of spans.hip and the host twin in host_twins.cpp (tgx_spans_host) both go through these functions, so a machine
 // without a GPU checks the kernels' arithmetic: the packed word of a token, an element's value in the chosen unit, the
 // span of an element from the scanned values, and the walks of the two writers (the padded one through pad_row of
 // layout.h, the flat one through the row cursor of the packed layout with A = 0).

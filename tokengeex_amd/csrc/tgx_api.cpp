@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/tgx.h"
+#include "api_internal.h"
 #include "assemble.h"
 #include "decode.h"
 #include "kernels.h"
@@ -32,22 +33,8 @@
 #include "sample.h"
 #include "trie_build.h"
 
-namespace {
+using namespace tgx::host;
 
-// ---- thread-local error state ------------------------------------------------
-thread_local std::string g_err_msg;
-thread_local uint64_t g_err_sample = 0, g_err_pos = 0, g_err_len = 0;
-
-tgx_status fail(tgx_status st, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_err_msg = buf;
-    return st;
-}
-}  // namespace
 // shared with prune_host.cpp: records the message tgx_last_error() returns (thread-local)
 tgx_status tgx_set_error(tgx_status st, const char* msg) {
     g_err_msg = msg ? msg : "";
@@ -419,6 +406,13 @@ int usable_device_count() {
         return 0;
     }
     return n;
+}
+// TGX_ERR_DEVICE without a usable HIP device; *n_devices: how many there are
+tgx_status require_device(int* n_devices = nullptr) {
+    const int n = usable_device_count();
+    if (n_devices) *n_devices = n;
+    if (n <= 0) return fail(TGX_ERR_DEVICE, "no usable HIP device (gfx950 required)");
+    return TGX_OK;
 }
 
 // TGX_DEBUG=1: log every launch to stderr and synchronise after it, so that a
@@ -1114,9 +1108,7 @@ tgx_status check_no_path(tgx_model* m, const tgx_corpus* c) {
         return fail(TGX_ERR_DEVICE, "internal error: corrupt back-pointer (sample or text byte %llu)",
                     (unsigned long long)(bad & ~(1ULL << 62)));
     uint64_t n = c->h_offs[bad + 1] - c->h_offs[bad];
-    g_err_sample = bad;
-    g_err_pos = n;
-    g_err_len = n;
+    set_error_detail(bad, n, n);
     // Display of Error::NoPath, reference src/lib.rs:243-245
     return fail(TGX_ERR_NO_PATH, "no path to position %llu/%llu", (unsigned long long)n,
                 (unsigned long long)n);
@@ -1175,8 +1167,6 @@ tgx_status on_uploaded_batch(const tgx_model* m, const uint8_t* text, const uint
 
 }  // namespace
 
-extern "C" {
-
 const char* tgx_last_error(void) { return g_err_msg.c_str(); }
 
 void tgx_last_error_detail(uint64_t* sample, uint64_t* pos, uint64_t* len) {
@@ -1190,10 +1180,7 @@ int tgx_device_count(void) { return usable_device_count(); }
 void tgx_free(void* p) { free(p); }
 void tgx_pool_trim(int device) { pool_trim(device); }
 void* tgx_host_alloc(uint64_t bytes) {
-    if (usable_device_count() <= 0) {
-        fail(TGX_ERR_DEVICE, "no usable HIP device (gfx950 required)");
-        return nullptr;
-    }
+    if (require_device() != TGX_OK) return nullptr;
     void* p = nullptr;
     if (hipHostMalloc(&p, bytes ? (size_t)bytes : 1, hipHostMallocPortable) != hipSuccess) {
         (void)hipGetLastError();
@@ -1262,8 +1249,8 @@ tgx_status tgx_model_create_ex(const uint8_t* bytes, const uint64_t* offs, const
     *out = nullptr;
     if (vocab_size && (!offs || !scores)) return fail(TGX_ERR_INVALID, "tgx_model_create: NULL vocab");
     if (vocab_size && !bytes && offs[vocab_size] != offs[0]) return fail(TGX_ERR_INVALID, "tgx_model_create: NULL token bytes");
-    int ndev = usable_device_count();
-    if (ndev <= 0) return fail(TGX_ERR_DEVICE, "no usable HIP device (gfx950 required)");
+    int ndev = 0;
+    if (const tgx_status dst = require_device(&ndev)) return dst;
     if (device < 0 || device >= ndev)
         return fail(TGX_ERR_INVALID, "device %d out of range (have %d)", device, ndev);
 
@@ -1654,8 +1641,8 @@ static tgx_status corpus_create(const char* who, int device, const uint8_t* text
     if (!out) return fail(TGX_ERR_INVALID, "%s: out is NULL", who);
     *out = nullptr;
     if (n_samples && !offs) return fail(TGX_ERR_INVALID, "%s: offs is NULL", who);
-    int ndev = usable_device_count();
-    if (ndev <= 0) return fail(TGX_ERR_DEVICE, "no usable HIP device (gfx950 required)");
+    int ndev = 0;
+    if (const tgx_status dst = require_device(&ndev)) return dst;
     if (device < 0 || device >= ndev)
         return fail(TGX_ERR_INVALID, "device %d out of range (have %d)", device, ndev);
     if (n_samples >= 0xFFFFFFFFull) return fail(TGX_ERR_UNSUPPORTED, "more than 2^32-1 samples");
@@ -2100,7 +2087,8 @@ private:
 // What a caller gets when it passes no stream of its own: one per device.  It is a BLOCKING stream (hipStreamDefault),
 // so what is queued on it starts after everything queued earlier on the device's null stream, which is where a
 // caller that "has no stream" has its work (torch's default stream is the null stream, handle 0).
-hipStream_t layout_stream(int device) {
+hipStream_t stream_or_default(void* stream, int device) {
+    if (stream) return static_cast<hipStream_t>(stream);
     static std::mutex mu;
     static hipStream_t streams[64] = {};
     if (device < 0 || device >= 64) return nullptr;
@@ -2116,21 +2104,9 @@ hipStream_t layout_stream(int device) {
     return streams[device];
 }
 
-// TGX_OK when every id a layout writes besides the tokens' is below 2^31 (pad always, bos / eos when present)
-tgx_status layout_check_ids(const char* who, uint32_t pad_id, uint32_t bos_id, uint32_t eos_id) {
-    if (pad_id >= 0x80000000u) return fail(TGX_ERR_INVALID, "%s: pad_id %u is not below 2^31", who, pad_id);
-    if (bos_id != TGX_NO_ID && bos_id >= 0x80000000u) return fail(TGX_ERR_INVALID, "%s: bos_id %u is not below 2^31", who, bos_id);
-    if (eos_id != TGX_NO_ID && eos_id >= 0x80000000u) return fail(TGX_ERR_INVALID, "%s: eos_id %u is not below 2^31", who, eos_id);
-    return TGX_OK;
-}
-
-tgx_status layout_check_flags(const char* who, uint32_t flags, uint32_t allowed) {
-    if (flags & ~allowed) return fail(TGX_ERR_INVALID, "%s: unknown flags 0x%x", who, flags & ~allowed);
-    return TGX_OK;
-}
-
-// p (may be NULL when optional) must be device memory of `device`; the current device is `device`
-tgx_status layout_check_dest(const char* who, const char* what, const void* p, int device) {
+// p (may be NULL when optional) must be device memory of `device`, which is the current device and that of `owner`
+// ("result" or "model")
+tgx_status check_device_ptr(const char* who, const char* what, const void* p, int device, const char* owner) {
     if (!p) return TGX_OK;
     hipPointerAttribute_t attr;
     if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
@@ -2138,110 +2114,49 @@ tgx_status layout_check_dest(const char* who, const char* what, const void* p, i
         return fail(TGX_ERR_INVALID, "%s: %s is not device memory", who, what);
     }
     if (attr.type != hipMemoryTypeDevice) return fail(TGX_ERR_INVALID, "%s: %s is not device memory", who, what);
-    if (attr.device != device) return fail(TGX_ERR_INVALID, "%s: %s is on device %d, the result on device %d", who, what, attr.device, device);
+    if (attr.device != device) return fail(TGX_ERR_INVALID, "%s: %s is on device %d, the %s on device %d", who, what, attr.device, owner, device);
     return TGX_OK;
 }
 
-tgx_status layout_check_host(const char* who, const uint32_t* ids, const uint64_t* offs, uint64_t n_rows) {
-    if (!offs) return fail(TGX_ERR_INVALID, "%s: offs is NULL", who);
-    if (offs[0] != 0) return fail(TGX_ERR_INVALID, "%s: offs[0] must be 0", who);
-    for (uint64_t i = 0; i < n_rows; i++)
-        if (offs[i + 1] < offs[i]) return fail(TGX_ERR_INVALID, "%s: offsets not monotone at %llu", who, (unsigned long long)i);
-    if (offs[n_rows] && !ids) return fail(TGX_ERR_INVALID, "%s: ids is NULL", who);
-    return TGX_OK;
-}
+// One call's work on a caller's stream (or stream_or_default's).  It owns the call's pooled buffers and the host memory
+// its uploads read.  A call that fails may have queued work that still uses them, the result or the caller's
+// destination, so the stream is synchronised before anything goes back to the pool or to the caller.  A call that
+// succeeds has synchronised the stream itself and says so with done().  What must outlive the stream's work and is not
+// the guard's (a tgx_text, a buffer that moves into one, host memory a copy writes) is declared BEFORE the guard.
+// (Pass is the same for a model's own streams.)
+class StreamGuard {
+public:
+    StreamGuard(int device, hipStream_t stream) : device_(device), stream_(stream) {}
+    StreamGuard(const StreamGuard&) = delete;
+    StreamGuard& operator=(const StreamGuard&) = delete;
+    ~StreamGuard() {
+        if (!ok_) (void)hipStreamSynchronize(stream_);
+    }  // (then the members go)
 
-extern "C++" {  // (this part of the file is inside extern "C")
-template <class T>
-tgx_status layout_pad_host(const tgx::LayoutSeq& seq, const uint32_t* ids, const uint64_t* offs, uint64_t n_rows, uint32_t L, uint32_t flags,
-                           T* out, uint8_t* mask, int32_t* lengths, uint64_t* n_truncated) {
-    // as the kernel: the flat [S, L] output in groups of kLayoutGroup consecutive elements, each walked by pad_group
-    const uint64_t total = n_rows * (uint64_t)L;
-    unsigned long long truncated = 0;
-    for (uint64_t e0 = 0; e0 < total; e0 += tgx::kLayoutGroup) {
-        const uint32_t n_in = total - e0 < tgx::kLayoutGroup ? (uint32_t)(total - e0) : tgx::kLayoutGroup;
-        uint32_t v[tgx::kLayoutGroup] = {0, 0, 0, 0};
-        const uint32_t m = tgx::pad_group(seq, ids, offs, L, flags, e0, n_in, lengths, v, &truncated);
-        for (uint32_t k = 0; k < n_in; k++) {
-            if (v[k] >= 0x80000000u)
-                return fail(TGX_ERR_INVALID, "tgx_layout_pad_host: id %u of row %llu is not below 2^31", v[k], (unsigned long long)((e0 + k) / L));
-            out[e0 + k] = (T)v[k];
-            if (mask) mask[e0 + k] = (uint8_t)(m >> (8 * k));
-        }
+    template <class T>
+    hipError_t alloc(size_t bytes, T** out) {
+        PoolBuf<void> b;
+        const hipError_t e = b.alloc(device_, bytes);
+        *out = static_cast<T*>(b.get());
+        if (e == hipSuccess) bufs_.push_back(std::move(b));
+        return e;
     }
-    if (n_truncated) *n_truncated = truncated;
-    return TGX_OK;
-}
-
-template <class T>
-tgx_status layout_pack_host(const tgx::LayoutSeq& seq, const uint32_t* ids, const uint64_t* offs, uint64_t n_rows, uint64_t n_stream,
-                            uint64_t n_out, T* out, int32_t* doc, int32_t* pos) {
-    // as the kernel: tiles of kPackTile positions, the owners of a tile's ends bound the search inside it, and a
-    // group of four consecutive positions walks on from row to row
-    uint64_t lo = 0, hi = 0;
-    tgx::PackCursor cur;
-    for (uint64_t j = 0; j < n_out; j++) {
-        uint32_t id = seq.pad;
-        int32_t d = -1, q = 0;
-        if (j % tgx::kPackTile == 0 && j < n_stream) {
-            const uint64_t last = j + tgx::kPackTile - 1 < n_stream ? j + tgx::kPackTile - 1 : n_stream - 1;
-            lo = tgx::pack_find_row(offs, seq.extra, 0, n_rows - 1, j);
-            hi = tgx::pack_find_row(offs, seq.extra, 0, n_rows - 1, last);
-        }
-        if (j % 4 == 0) cur = tgx::PackCursor();
-        if (j < n_stream) {
-            const uint64_t i = tgx::pack_advance(cur, offs, seq.extra, lo, hi, j);
-            id = tgx::pack_at(seq, ids, offs, i, j, &q);
-            d = (int32_t)i;
-            if (id >= 0x80000000u) return fail(TGX_ERR_INVALID, "tgx_layout_pack_host: id %u of row %llu is not below 2^31", id, (unsigned long long)i);
-        }
-        out[j] = (T)id;
-        if (doc) doc[j] = d;
-        if (pos) pos[j] = q;
+    // src to dst (device memory) on the stream; src lives as long as the guard
+    hipError_t upload(uint64_t* dst, std::vector<uint64_t> src) {
+        staged_.push_back(std::move(src));
+        return hipMemcpyAsync(dst, staged_.back().data(), staged_.back().size() * 8, hipMemcpyHostToDevice, stream_);
     }
-    return TGX_OK;
-}
-}  // extern "C++"
+    void done() { ok_ = true; }
+
+private:
+    int device_;
+    hipStream_t stream_;
+    bool ok_ = false;
+    std::vector<PoolBuf<void>> bufs_;
+    std::vector<std::vector<uint64_t>> staged_;
+};
 
 }  // namespace
-
-tgx_status tgx_layout_pad_host(const uint32_t* ids, const uint64_t* offs, uint64_t n_rows, uint32_t row_len, uint32_t pad_id,
-                               uint32_t bos_id, uint32_t eos_id, uint32_t flags, void* out_ids, uint8_t* out_mask,
-                               int32_t* out_lengths, uint64_t* n_truncated) {
-    const char* who = "tgx_layout_pad_host";
-    if (!out_ids && n_rows) return fail(TGX_ERR_INVALID, "%s: out_ids is NULL", who);
-    tgx_status st = layout_check_host(who, ids, offs, n_rows);
-    if (st == TGX_OK) st = layout_check_flags(who, flags, TGX_LAYOUT_PAD_LEFT | TGX_LAYOUT_TRUNC_LEFT | TGX_LAYOUT_I64);
-    if (st == TGX_OK) st = layout_check_ids(who, pad_id, bos_id, eos_id);
-    if (st != TGX_OK) return st;
-    const tgx::LayoutSeq seq = tgx::layout_seq(bos_id, eos_id, pad_id);
-    if (row_len < 1 || row_len < seq.extra) return fail(TGX_ERR_INVALID, "%s: row_len %u (needs >= 1 and >= %u for bos / eos)", who, row_len, seq.extra);
-    if (flags & TGX_LAYOUT_I64)
-        return layout_pad_host(seq, ids, offs, n_rows, row_len, flags, static_cast<int64_t*>(out_ids), out_mask, out_lengths, n_truncated);
-    return layout_pad_host(seq, ids, offs, n_rows, row_len, flags, static_cast<int32_t*>(out_ids), out_mask, out_lengths, n_truncated);
-}
-
-tgx_status tgx_layout_pack_host(const uint32_t* ids, const uint64_t* offs, uint64_t n_rows, uint32_t block_len, uint32_t pad_id,
-                                uint32_t bos_id, uint32_t eos_id, uint32_t flags, void* out_ids, int32_t* out_doc,
-                                int32_t* out_pos, uint64_t* n_blocks) {
-    const char* who = "tgx_layout_pack_host";
-    if (!n_blocks) return fail(TGX_ERR_INVALID, "%s: n_blocks is NULL", who);
-    tgx_status st = layout_check_host(who, ids, offs, n_rows);
-    if (st == TGX_OK) st = layout_check_flags(who, flags, TGX_LAYOUT_I64);
-    if (st == TGX_OK) st = layout_check_ids(who, pad_id, bos_id, eos_id);
-    if (st != TGX_OK) return st;
-    if (block_len < 1) return fail(TGX_ERR_INVALID, "%s: block_len is 0", who);
-    if (n_rows >= 0x80000000ull) return fail(TGX_ERR_UNSUPPORTED, "%s: 2^31 rows or more", who);
-    const tgx::LayoutSeq seq = tgx::layout_seq(bos_id, eos_id, pad_id);
-    const uint64_t n_stream = offs[n_rows] + n_rows * seq.extra;
-    const uint64_t nb = (n_stream + block_len - 1) / block_len;
-    *n_blocks = nb;
-    if (nb == 0) return TGX_OK;
-    if (!out_ids) return fail(TGX_ERR_INVALID, "%s: out_ids is NULL", who);
-    if (flags & TGX_LAYOUT_I64)
-        return layout_pack_host(seq, ids, offs, n_rows, n_stream, nb * block_len, static_cast<int64_t*>(out_ids), out_doc, out_pos);
-    return layout_pack_host(seq, ids, offs, n_rows, n_stream, nb * block_len, static_cast<int32_t*>(out_ids), out_doc, out_pos);
-}
 
 tgx_status tgx_result_layout_info(const tgx_result* r, uint32_t bos_id, uint32_t eos_id, uint64_t* max_row_len, uint64_t* n_stream) {
     if (!r) return fail(TGX_ERR_INVALID, "tgx_result_layout_info: result is NULL");
@@ -2252,16 +2167,15 @@ tgx_status tgx_result_layout_info(const tgx_result* r, uint32_t bos_id, uint32_t
     if (r->n_samples == 0 || r->n_tokens == 0) return TGX_OK;
     DeviceScope scope;
     HIP_TRY(hipSetDevice(r->device));
-    PoolBuf<unsigned long long> d_max;
-    HIP_TRY(d_max.alloc(r->device, sizeof(unsigned long long)));
-    hipStream_t st = layout_stream(r->device);
-    unsigned long long h_max = 0;
-    hipError_t e = hipMemsetAsync(d_max, 0, sizeof(unsigned long long), st);
-    if (e == hipSuccess) e = tgx::launch_layout_max_row(r->d_offs, r->n_samples, d_max, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(&h_max, d_max, sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
-    const hipError_t es = hipStreamSynchronize(st);  // also after a failure: d_max goes back to the pool
-    HIP_TRY(e);
-    HIP_TRY(es);
+    hipStream_t st = stream_or_default(nullptr, r->device);
+    unsigned long long h_max = 0, *d_max = nullptr;
+    StreamGuard guard(r->device, st);
+    HIP_TRY(guard.alloc(sizeof(unsigned long long), &d_max));
+    HIP_TRY(hipMemsetAsync(d_max, 0, sizeof(unsigned long long), st));
+    HIP_TRY(tgx::launch_layout_max_row(r->d_offs, r->n_samples, d_max, st));
+    HIP_TRY(hipMemcpyAsync(&h_max, d_max, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    guard.done();
     *max_row_len = h_max + A;
     return TGX_OK;
 }
@@ -2277,17 +2191,18 @@ tgx_status tgx_result_pad_device(const tgx_result* r, uint32_t row_len, uint32_t
     if (st != TGX_OK) return st;
     if (r->vocab_size > 0x80000000u) return fail(TGX_ERR_INVALID, "%s: the model's ids are not all below 2^31", who);
     const tgx::LayoutSeq seq = tgx::layout_seq(bos_id, eos_id, pad_id);
-    if (row_len < 1 || row_len < seq.extra) return fail(TGX_ERR_INVALID, "%s: row_len %u (needs >= 1 and >= %u for bos / eos)", who, row_len, seq.extra);
+    if ((st = layout_check_row_len(who, row_len, seq.extra)) != TGX_OK) return st;
     if (n_truncated) *n_truncated = 0;
     if (r->n_samples == 0) return TGX_OK;
     DeviceScope scope;
     HIP_TRY(hipSetDevice(r->device));
-    if ((st = layout_check_dest(who, "d_ids", d_ids, r->device)) != TGX_OK) return st;
-    if ((st = layout_check_dest(who, "d_mask", d_mask, r->device)) != TGX_OK) return st;
-    if ((st = layout_check_dest(who, "d_lengths", d_lengths, r->device)) != TGX_OK) return st;
-    hipStream_t hs = stream ? static_cast<hipStream_t>(stream) : layout_stream(r->device);
-    PoolBuf<unsigned long long> d_count;
-    if (n_truncated) HIP_TRY(d_count.alloc(r->device, sizeof(unsigned long long)));
+    if ((st = check_device_ptr(who, "d_ids", d_ids, r->device, "result")) != TGX_OK) return st;
+    if ((st = check_device_ptr(who, "d_mask", d_mask, r->device, "result")) != TGX_OK) return st;
+    if ((st = check_device_ptr(who, "d_lengths", d_lengths, r->device, "result")) != TGX_OK) return st;
+    hipStream_t hs = stream_or_default(stream, r->device);
+    unsigned long long h_count = 0, *d_count = nullptr;
+    StreamGuard guard(r->device, hs);
+    if (n_truncated) HIP_TRY(guard.alloc(sizeof(unsigned long long), &d_count));
     tgx::LayoutParams p = {};
     p.ids = r->d_ids;
     p.offs = r->d_offs;
@@ -2300,15 +2215,13 @@ tgx_status tgx_result_pad_device(const tgx_result* r, uint32_t row_len, uint32_t
     p.out = d_ids;
     p.mask = d_mask;
     p.lengths = d_lengths;
-    p.counter = d_count.get();
-    unsigned long long h_count = 0;
-    hipError_t e = n_truncated ? hipMemsetAsync(d_count, 0, sizeof(unsigned long long), hs) : hipSuccess;
-    if (e == hipSuccess) e = tgx::launch_layout_pad(p, hs);
-    if (e == hipSuccess && n_truncated) e = hipMemcpyAsync(&h_count, d_count, sizeof(unsigned long long), hipMemcpyDeviceToHost, hs);
-    // the stream has reached its end before the result or the destination can change hands (also after a failure)
-    const hipError_t es = hipStreamSynchronize(hs);
-    HIP_TRY(e);
-    HIP_TRY(es);
+    p.counter = d_count;
+    if (n_truncated) HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), hs));
+    HIP_TRY(tgx::launch_layout_pad(p, hs));
+    if (n_truncated) HIP_TRY(hipMemcpyAsync(&h_count, d_count, sizeof(unsigned long long), hipMemcpyDeviceToHost, hs));
+    // the stream has reached its end before the result or the destination can change hands (the guard: also after a failure)
+    HIP_TRY(hipStreamSynchronize(hs));
+    guard.done();
     if (n_truncated) *n_truncated = h_count;
     return TGX_OK;
 }
@@ -2331,10 +2244,10 @@ tgx_status tgx_result_pack_device(const tgx_result* r, uint32_t block_len, uint3
     if (!d_ids) return fail(TGX_ERR_INVALID, "%s: d_ids is NULL", who);
     DeviceScope scope;
     HIP_TRY(hipSetDevice(r->device));
-    if ((st = layout_check_dest(who, "d_ids", d_ids, r->device)) != TGX_OK) return st;
-    if ((st = layout_check_dest(who, "d_doc", d_doc, r->device)) != TGX_OK) return st;
-    if ((st = layout_check_dest(who, "d_pos", d_pos, r->device)) != TGX_OK) return st;
-    hipStream_t hs = stream ? static_cast<hipStream_t>(stream) : layout_stream(r->device);
+    if ((st = check_device_ptr(who, "d_ids", d_ids, r->device, "result")) != TGX_OK) return st;
+    if ((st = check_device_ptr(who, "d_doc", d_doc, r->device, "result")) != TGX_OK) return st;
+    if ((st = check_device_ptr(who, "d_pos", d_pos, r->device, "result")) != TGX_OK) return st;
+    hipStream_t hs = stream_or_default(stream, r->device);
     tgx::LayoutParams p = {};
     p.ids = r->d_ids;
     p.offs = r->d_offs;
@@ -2347,85 +2260,20 @@ tgx_status tgx_result_pack_device(const tgx_result* r, uint32_t block_len, uint3
     p.out = d_ids;
     p.doc = d_doc;
     p.pos = d_pos;
-    const hipError_t e = tgx::launch_layout_pack(p, n_stream, nb * block_len, hs);
-    const hipError_t es = hipStreamSynchronize(hs);
-    HIP_TRY(e);
-    HIP_TRY(es);
+    StreamGuard guard(r->device, hs);
+    HIP_TRY(tgx::launch_layout_pack(p, n_stream, nb * block_len, hs));
+    HIP_TRY(hipStreamSynchronize(hs));
+    guard.done();
     return TGX_OK;
 }
 
 // ---- assembly: a sample-level result with the special tokens' ids, from the segment-level result (assemble.hip) ----
 
-namespace {
-
-// What tgx_assemble_result and tgx_assemble_host check of a split plan before anything runs.  n_rows: the rows of the
-// segment-level result (0 without one).  *n_segs = K.
-tgx_status assemble_check(const char* who, const uint64_t* seg_offs, const int32_t* seg_special, uint64_t n_samples, uint32_t vocab_size,
-                          uint32_t n_specials, bool have_segs, uint64_t n_rows, uint64_t* n_segs) {
-    if (!seg_offs) return fail(TGX_ERR_INVALID, "%s: seg_offs is NULL", who);
-    if (seg_offs[0] != 0) return fail(TGX_ERR_INVALID, "%s: seg_offs[0] must be 0", who);
-    for (uint64_t i = 0; i < n_samples; i++)
-        if (seg_offs[i + 1] < seg_offs[i]) return fail(TGX_ERR_INVALID, "%s: seg_offs not monotone at %llu", who, (unsigned long long)i);
-    const uint64_t K = seg_offs[n_samples];
-    if (K && !seg_special) return fail(TGX_ERR_INVALID, "%s: seg_special is NULL", who);
-    if ((uint64_t)vocab_size + n_specials > 0xFFFFFFFEull)
-        return fail(TGX_ERR_INVALID, "%s: %u tokens and %u special tokens leave no room for their ids", who, vocab_size, n_specials);
-    uint64_t E = 0;
-    for (uint64_t k = 0; k < K; k++) {
-        if (seg_special[k] < 0)
-            E++;
-        else if ((uint32_t)seg_special[k] >= n_specials)
-            return fail(TGX_ERR_INVALID, "%s: segment %llu is special token %d of %u", who, (unsigned long long)k, seg_special[k], n_specials);
-    }
-    if (E && !have_segs) return fail(TGX_ERR_INVALID, "%s: %llu encoded segments and no result over them", who, (unsigned long long)E);
-    if (E != n_rows)
-        return fail(TGX_ERR_INVALID, "%s: %llu encoded segments, the result over them has %llu rows", who, (unsigned long long)E,
-                    (unsigned long long)n_rows);
-    *n_segs = K;
-    return TGX_OK;
-}
-
-}  // namespace
-
-tgx_status tgx_assemble_host(const uint32_t* ids, const uint64_t* id_offs, uint64_t n_encoded, const uint64_t* seg_offs,
-                             const int32_t* seg_special, uint64_t n_samples, uint32_t vocab_size, uint32_t n_specials, uint32_t* out_ids,
-                             uint64_t ids_cap, uint64_t* out_offs) {
-    const char* who = "tgx_assemble_host";
-    if (!out_offs) return fail(TGX_ERR_INVALID, "%s: out_offs is NULL", who);
-    uint64_t K = 0;
-    tgx_status st = assemble_check(who, seg_offs, seg_special, n_samples, vocab_size, n_specials, id_offs != nullptr, n_encoded, &K);
-    if (st != TGX_OK) return st;
-    static const uint64_t kNoOffs[1] = {0};
-    if (!id_offs) id_offs = kNoOffs;
-    if ((st = layout_check_host(who, ids, id_offs, n_encoded)) != TGX_OK) return st;
-    const uint64_t n_out = id_offs[n_encoded] + (K - n_encoded);
-    if (ids_cap < n_out) return fail(TGX_ERR_INVALID, "%s: %llu ids, room for %llu", who, (unsigned long long)n_out, (unsigned long long)ids_cap);
-    if (n_out && !out_ids) return fail(TGX_ERR_INVALID, "%s: out_ids is NULL", who);
-    // as the device: the ranks, the starts with the samples' offsets, then the kernel's tiles and thread slots
-    std::vector<uint64_t> rank(K + 1), starts(K + 1);
-    for (uint64_t k = 0, r = 0; k <= K; k++) {
-        rank[k] = r;
-        if (k < K && seg_special[k] < 0) r++;
-    }
-    for (uint64_t k = 0; k <= K; k++) starts[k] = tgx::assemble_seg_start(id_offs, rank.data(), k);
-    for (uint64_t i = 0; i <= n_samples; i++) out_offs[i] = tgx::assemble_seg_start(id_offs, rank.data(), seg_offs[i]);
-    for (uint64_t t0 = 0; t0 < n_out; t0 += tgx::kAssembleTile) {
-        const uint64_t last = tgx::assemble_tile_last(t0, n_out);
-        const uint64_t lo = tgx::assemble_find_seg(starts.data(), 0, K - 1, t0), hi = tgx::assemble_find_seg(starts.data(), 0, K - 1, last);
-        for (uint64_t e0 = t0; e0 <= last; e0 += tgx::kAssembleGroup) {
-            const uint32_t n_in = last + 1 - e0 < tgx::kAssembleGroup ? (uint32_t)(last + 1 - e0) : tgx::kAssembleGroup;
-            uint32_t v[tgx::kAssembleGroup] = {0, 0, 0, 0};
-            tgx::assemble_group(ids, starts.data(), rank.data(), seg_special, vocab_size, lo, hi, e0, n_in, v);
-            for (uint32_t q = 0; q < n_in; q++) out_ids[e0 + q] = v[q];
-        }
-    }
-    return TGX_OK;
-}
-
 tgx_status tgx_assemble_result(tgx_model* m, const tgx_result* segs, const uint64_t* seg_offs, const int32_t* seg_special,
                                uint64_t n_samples, uint32_t n_specials, tgx_result** out) {
     const char* who = "tgx_assemble_result";
-    if (usable_device_count() <= 0) return fail(TGX_ERR_DEVICE, "no usable HIP device (gfx950 required)");
+    const tgx_status dst = require_device();
+    if (dst != TGX_OK) return dst;
     if (!m || !out) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
     *out = nullptr;
     uint64_t K = 0;
@@ -2499,44 +2347,6 @@ struct tgx_text {
 
 namespace {
 
-// lengths and 16-byte slots of a vocabulary's tokens: what the kernels (device copies) and the host twin read
-tgx_status decode_build_tables(const char* who, const uint8_t* bytes, const uint64_t* offs, uint32_t V, std::vector<uint8_t>* len,
-                               std::vector<tgx::DecodeSlot>* slots) {
-    len->assign(V, 0);
-    slots->assign(V, tgx::DecodeSlot{0, 0});
-    for (uint32_t i = 0; i < V; i++) {
-        if (offs[i + 1] < offs[i]) return fail(TGX_ERR_INVALID, "%s: vocabulary offsets not monotone at %u", who, i);
-        const uint64_t n = offs[i + 1] - offs[i];
-        if (n > TGX_MAX_TOKEN_LEN) return fail(TGX_ERR_UNSUPPORTED, "%s: token of %llu bytes exceeds TGX_MAX_TOKEN_LEN (%d)", who, (unsigned long long)n, TGX_MAX_TOKEN_LEN);
-        (*len)[i] = (uint8_t)n;
-        if (n > tgx::kDecodeSlotLen) continue;
-        tgx::DecodeSlot& sl = (*slots)[i];
-        for (uint64_t k = 0; k < n; k++) (k < 8 ? sl.lo : sl.hi) |= (uint64_t)bytes[offs[i] + k] << (8 * (k & 7));
-    }
-    return TGX_OK;
-}
-
-tgx_status decode_check_specials(const char* who, uint32_t vocab_size, const uint8_t* special_bytes, const uint64_t* special_offs, uint32_t n_specials) {
-    if (n_specials && !special_offs) return fail(TGX_ERR_INVALID, "%s: special_offs is NULL", who);
-    if ((uint64_t)vocab_size + n_specials > 0xFFFFFFFEull)
-        return fail(TGX_ERR_INVALID, "%s: %u tokens and %u special tokens leave no room for their ids", who, vocab_size, n_specials);
-    for (uint32_t k = 0; k < n_specials; k++) {
-        if (special_offs[k + 1] < special_offs[k]) return fail(TGX_ERR_INVALID, "%s: special_offs not monotone at %u", who, k);
-        if (special_offs[k + 1] - special_offs[k] >= 0x80000000ull) return fail(TGX_ERR_UNSUPPORTED, "%s: special token %u is 2 GiB or longer", who, k);
-    }
-    if (n_specials && special_offs[n_specials] > special_offs[0] && !special_bytes) return fail(TGX_ERR_INVALID, "%s: special_bytes is NULL", who);
-    return TGX_OK;
-}
-
-tgx_status decode_oob(uint32_t kind, int64_t x, uint64_t row, uint64_t* bad_sample, uint64_t* bad_id) {
-    if (bad_sample) *bad_sample = row;
-    if (bad_id) *bad_id = (uint64_t)x;
-    g_err_sample = row;
-    g_err_pos = (uint64_t)x;
-    if (kind == tgx::kDecodeU32) return fail(TGX_ERR_TOKEN_ID_OOB, "token id %llu is out of bounds", (unsigned long long)x);
-    return fail(TGX_ERR_TOKEN_ID_OOB, "token id %lld is out of bounds", (long long)x);
-}
-
 uint64_t decode_elem_bytes(uint32_t kind) { return kind == tgx::kDecodeI64 ? 8 : 4; }
 
 // the model's token tables on its device, once (under m->mu)
@@ -2561,51 +2371,22 @@ tgx_status ensure_decode_tables(tgx_model* m) {
     return TGX_OK;
 }
 
-// p (may be NULL when optional) must be device memory of `device`; the current device is `device`
-tgx_status decode_check_src(const char* who, const char* what, const void* p, int device) {
-    if (!p) return TGX_OK;
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(TGX_ERR_INVALID, "%s: %s is not device memory", who, what);
-    }
-    if (attr.type != hipMemoryTypeDevice) return fail(TGX_ERR_INVALID, "%s: %s is not device memory", who, what);
-    if (attr.device != device) return fail(TGX_ERR_INVALID, "%s: %s is on device %d, the model on device %d", who, what, attr.device, device);
-    return TGX_OK;
-}
-
-// the buffers of one decode; they go back to the pool after the stream has reached its end (StreamEnd below them)
-struct DecodeWork {
-    PoolBuf<uint32_t> meta, flags, codes;
-    PoolBuf<uint64_t> starts, specials, gpos, sp_offs;
-    PoolBuf<uint8_t> sp_bytes, raw;
-    PoolBuf<void> scan, scan2;
-    PoolBuf<unsigned long long> ctrl;  // [0]: lowest out-of-bounds position, [1]: replacement characters, [2]: live specials
-    std::unique_ptr<tgx_text> text;
-};
-class StreamEnd {
-public:
-    explicit StreamEnd(hipStream_t s) : s_(s) {}
-    ~StreamEnd() {
-        if (!ok_) (void)hipStreamSynchronize(s_);
-    }
-    void done() { ok_ = true; }
-
-private:
-    hipStream_t s_;
-    bool ok_ = false;
-};
-
 // The decode of src (device pointers) on stream hs of the model's device, which is current.  row_offs_dev: the offsets
 // form's offsets, read back only to name the row of an out-of-bounds id.
 tgx_status decode_device(tgx_model* m, tgx::DecodeSrc src, const uint8_t* special_bytes, const uint64_t* special_offs, uint32_t n_specials,
                          int include_special, hipStream_t hs, tgx_text** out, uint64_t* bad_sample, uint64_t* bad_id) {
     const int dev = m->device;
     const uint64_t S = src.n_rows, N = src.n;
-    DecodeWork w;
-    StreamEnd end(hs);  // destroyed before w: a failed call's queued work is over before its buffers change hands
-    w.text.reset(new tgx_text());
-    tgx_text* t = w.text.get();
+    std::unique_ptr<tgx_text> text(new tgx_text());
+    PoolBuf<uint8_t> raw;          // the raw bytes: the text's own when nothing is replaced
+    std::vector<uint64_t> h_offs;  // the offsets form's offsets, read back to name the row of an out-of-bounds id
+    StreamGuard guard(dev, hs);    // destroyed before them: a failed call's queued work is over before they go
+    uint32_t *meta = nullptr, *flags = nullptr, *codes = nullptr;
+    uint64_t *starts = nullptr, *specials = nullptr, *gpos = nullptr, *sp_offs = nullptr;
+    uint8_t* sp_bytes = nullptr;
+    void *scan = nullptr, *scan2 = nullptr;
+    unsigned long long* ctrl = nullptr;  // [0]: lowest out-of-bounds position, [1]: replacement characters, [2]: live specials
+    tgx_text* t = text.get();
     t->device = dev;
     t->n_rows = S;
     HIP_TRY(t->d_offs.alloc(dev, (size_t)(S + 1) * 8));
@@ -2613,8 +2394,8 @@ tgx_status decode_device(tgx_model* m, tgx::DecodeSrc src, const uint8_t* specia
         HIP_TRY(t->d_bytes.alloc(dev, 0));
         HIP_TRY(hipMemsetAsync(t->d_offs, 0, (size_t)(S + 1) * 8, hs));
         HIP_TRY(hipStreamSynchronize(hs));
-        end.done();
-        *out = w.text.release();
+        guard.done();
+        *out = text.release();
         return TGX_OK;
     }
     tgx_status st = ensure_decode_tables(m);
@@ -2623,47 +2404,46 @@ tgx_status decode_device(tgx_model* m, tgx::DecodeSrc src, const uint8_t* specia
     const uint64_t sp_total = n_specials ? special_offs[n_specials] - special_offs[0] : 0;
     size_t scan_bytes = 0;
     if (tgx::decode_scan_temp_bytes(N, &scan_bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan temp-size query failed");
-    HIP_TRY(w.meta.alloc(dev, (size_t)(N + 1) * 4));
-    HIP_TRY(w.starts.alloc(dev, (size_t)(N + 1) * 8));
-    HIP_TRY(w.scan.alloc(dev, scan_bytes));  // (never NULL: that asks the scan for its size)
-    HIP_TRY(w.ctrl.alloc(dev, 24));
-    HIP_TRY(w.sp_offs.alloc(dev, ((size_t)n_specials + 1) * 8));
-    HIP_TRY(w.sp_bytes.alloc(dev, (size_t)sp_total + 16));
-    std::vector<uint64_t> sp_offs0((size_t)n_specials + 1, 0);  // from 0; alive until the stream has taken them
+    HIP_TRY(guard.alloc((size_t)(N + 1) * 4, &meta));
+    HIP_TRY(guard.alloc((size_t)(N + 1) * 8, &starts));
+    HIP_TRY(guard.alloc(scan_bytes, &scan));  // (never NULL: that asks the scan for its size)
+    HIP_TRY(guard.alloc(24, &ctrl));
+    HIP_TRY(guard.alloc(((size_t)n_specials + 1) * 8, &sp_offs));
+    HIP_TRY(guard.alloc((size_t)sp_total + 16, &sp_bytes));
+    std::vector<uint64_t> sp_offs0((size_t)n_specials + 1, 0);  // from 0
     for (uint32_t k = 0; k <= n_specials && n_specials; k++) sp_offs0[k] = special_offs[k] - special_offs[0];
-    HIP_TRY(hipMemcpyAsync(w.sp_offs, sp_offs0.data(), sp_offs0.size() * 8, hipMemcpyHostToDevice, hs));
-    if (sp_total) HIP_TRY(hipMemcpyAsync(w.sp_bytes, special_bytes + special_offs[0], sp_total, hipMemcpyHostToDevice, hs));
-    HIP_TRY(hipMemsetAsync(w.ctrl, 0xFF, 8, hs));
-    HIP_TRY(hipMemsetAsync(w.ctrl.get() + 1, 0, 16, hs));
+    HIP_TRY(guard.upload(sp_offs, std::move(sp_offs0)));
+    if (sp_total) HIP_TRY(hipMemcpyAsync(sp_bytes, special_bytes + special_offs[0], sp_total, hipMemcpyHostToDevice, hs));
+    HIP_TRY(hipMemsetAsync(ctrl, 0xFF, 8, hs));
+    HIP_TRY(hipMemsetAsync(ctrl + 1, 0, 16, hs));
 
     tgx::DecodeParams p = {};
     p.tab.tok_len = m->d_dec_len;
     p.tab.slots = static_cast<const tgx::DecodeSlot*>(m->d_dec_slots);
     p.tab.bytes = m->d_dec_bytes;
     p.tab.offs = m->d_dec_offs;
-    p.tab.sp_bytes = w.sp_bytes;
-    p.tab.sp_offs = w.sp_offs;
+    p.tab.sp_bytes = sp_bytes;
+    p.tab.sp_offs = sp_offs;
     p.tab.vocab_size = m->vocab_size;
     p.tab.n_specials = n_specials;
     p.tab.include_special = include_special ? 1 : 0;
     p.src = src;
-    p.meta = w.meta;
-    p.starts = w.starts;
-    p.bad_pos = w.ctrl;
-    p.n_replaced = w.ctrl.get() + 1;
-    p.n_specials_live = w.ctrl.get() + 2;
+    p.meta = meta;
+    p.starts = starts;
+    p.bad_pos = ctrl;
+    p.n_replaced = ctrl + 1;
+    p.n_specials_live = ctrl + 2;
     p.row_offs = t->d_offs;
-    HIP_TRY(tgx::launch_decode_meta(p, w.scan, scan_bytes, hs));
+    HIP_TRY(tgx::launch_decode_meta(p, scan, scan_bytes, hs));
     unsigned long long h_bad = ~0ull, h_raw = 0, h_replaced = 0, h_final = 0, h_specials = 0;
-    HIP_TRY(hipMemcpyAsync(&h_bad, w.ctrl, 8, hipMemcpyDeviceToHost, hs));
-    HIP_TRY(hipMemcpyAsync(&h_specials, w.ctrl.get() + 2, 8, hipMemcpyDeviceToHost, hs));
-    HIP_TRY(hipMemcpyAsync(&h_raw, w.starts.get() + N, 8, hipMemcpyDeviceToHost, hs));
+    HIP_TRY(hipMemcpyAsync(&h_bad, ctrl, 8, hipMemcpyDeviceToHost, hs));
+    HIP_TRY(hipMemcpyAsync(&h_specials, ctrl + 2, 8, hipMemcpyDeviceToHost, hs));
+    HIP_TRY(hipMemcpyAsync(&h_raw, starts + N, 8, hipMemcpyDeviceToHost, hs));
     HIP_TRY(hipStreamSynchronize(hs));
     if (h_bad != ~0ull) {
         int64_t x = 0;
         union { int64_t i64; int32_t i32; uint32_t u32; } v = {};
         HIP_TRY(hipMemcpyAsync(&v, static_cast<const char*>(src.ids) + h_bad * decode_elem_bytes(src.kind), decode_elem_bytes(src.kind), hipMemcpyDeviceToHost, hs));
-        std::vector<uint64_t> h_offs;
         if (src.offs) {
             h_offs.resize(S + 1);
             HIP_TRY(hipMemcpyAsync(h_offs.data(), src.offs, (size_t)(S + 1) * 8, hipMemcpyDeviceToHost, hs));
@@ -2671,7 +2451,7 @@ tgx_status decode_device(tgx_model* m, tgx::DecodeSrc src, const uint8_t* specia
         HIP_TRY(hipStreamSynchronize(hs));
         x = src.kind == tgx::kDecodeI64 ? v.i64 : src.kind == tgx::kDecodeI32 ? (int64_t)v.i32 : (int64_t)v.u32;
         const uint64_t row = src.offs ? (uint64_t)(std::upper_bound(h_offs.begin(), h_offs.end(), (uint64_t)h_bad) - h_offs.begin()) - 1 : h_bad / src.row_len;
-        end.done();
+        guard.done();
         return decode_oob(src.kind, x, row, bad_sample, bad_id);
     }
     const uint64_t T = h_raw;
@@ -2679,51 +2459,51 @@ tgx_status decode_device(tgx_model* m, tgx::DecodeSrc src, const uint8_t* specia
         HIP_TRY(t->d_bytes.alloc(dev, 0));
         HIP_TRY(hipMemsetAsync(t->d_offs, 0, (size_t)(S + 1) * 8, hs));
         HIP_TRY(hipStreamSynchronize(hs));
-        end.done();
-        *out = w.text.release();
+        guard.done();
+        *out = text.release();
         return TGX_OK;
     }
     const uint64_t G = (T + tgx::kDecodeGroup - 1) / tgx::kDecodeGroup;
-    HIP_TRY(w.raw.alloc(dev, (size_t)G * tgx::kDecodeGroup + 16));
-    HIP_TRY(w.flags.alloc(dev, (size_t)G * 4));
-    HIP_TRY(w.codes.alloc(dev, (size_t)(G + 1) * 4));
+    HIP_TRY(raw.alloc(dev, (size_t)G * tgx::kDecodeGroup + 16));
+    HIP_TRY(guard.alloc((size_t)G * 4, &flags));
+    HIP_TRY(guard.alloc((size_t)(G + 1) * 4, &codes));
     p.n_raw = T;
-    p.raw = w.raw;
-    p.flags = w.flags;
-    p.codes = w.codes;
+    p.raw = raw;
+    p.flags = flags;
+    p.codes = codes;
     if (h_specials) {  // only then can a run end inside a row
-        HIP_TRY(w.specials.alloc(dev, (size_t)(N + 1) * 8));
-        p.specials = w.specials;
-        HIP_TRY(tgx::launch_decode_specials(p, w.scan, scan_bytes, hs));
+        HIP_TRY(guard.alloc((size_t)(N + 1) * 8, &specials));
+        p.specials = specials;
+        HIP_TRY(tgx::launch_decode_specials(p, scan, scan_bytes, hs));
     }
     HIP_TRY(tgx::launch_decode_fill(p, hs));
     HIP_TRY(tgx::launch_decode_rows(p, hs));
     HIP_TRY(tgx::launch_decode_utf8(p, hs));
-    HIP_TRY(hipMemcpyAsync(&h_replaced, w.ctrl.get() + 1, 8, hipMemcpyDeviceToHost, hs));
+    HIP_TRY(hipMemcpyAsync(&h_replaced, ctrl + 1, 8, hipMemcpyDeviceToHost, hs));
     HIP_TRY(hipStreamSynchronize(hs));
     t->n_replaced = h_replaced;
     if (h_replaced == 0) {  // the raw bytes are the text and the rows' raw starts its offsets
-        t->d_bytes = std::move(w.raw);
+        t->d_bytes = std::move(raw);
         t->n_bytes = T;
-        end.done();
-        *out = w.text.release();
+        guard.done();
+        *out = text.release();
         return TGX_OK;
     }
     size_t scan2_bytes = 0;
     if (tgx::decode_expand_temp_bytes(G, &scan2_bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan temp-size query failed");
-    HIP_TRY(w.gpos.alloc(dev, (size_t)(G + 1) * 8));
-    HIP_TRY(w.scan2.alloc(dev, scan2_bytes));
-    p.gpos = w.gpos;
-    HIP_TRY(tgx::launch_decode_positions(p, w.scan2, scan2_bytes, hs));
-    HIP_TRY(hipMemcpyAsync(&h_final, w.gpos.get() + G, 8, hipMemcpyDeviceToHost, hs));
+    HIP_TRY(guard.alloc((size_t)(G + 1) * 8, &gpos));
+    HIP_TRY(guard.alloc(scan2_bytes, &scan2));
+    p.gpos = gpos;
+    HIP_TRY(tgx::launch_decode_positions(p, scan2, scan2_bytes, hs));
+    HIP_TRY(hipMemcpyAsync(&h_final, gpos + G, 8, hipMemcpyDeviceToHost, hs));
     HIP_TRY(hipStreamSynchronize(hs));
     HIP_TRY(t->d_bytes.alloc(dev, (size_t)h_final + 16));
     p.out = t->d_bytes;
     HIP_TRY(tgx::launch_decode_expand(p, hs));
     HIP_TRY(hipStreamSynchronize(hs));
     t->n_bytes = h_final;
-    end.done();
-    *out = w.text.release();
+    guard.done();
+    *out = text.release();
     return TGX_OK;
 }
 
@@ -2736,14 +2516,14 @@ tgx_status tgx_decode_result(tgx_model* m, const tgx_result* r, const uint8_t* s
     *out = nullptr;
     tgx_status st = decode_check_specials(who, m->vocab_size, special_bytes, special_offs, n_specials);
     if (st != TGX_OK) return st;
-    if (usable_device_count() <= 0) return fail(TGX_ERR_DEVICE, "no usable HIP device (gfx950 required)");
+    if ((st = require_device()) != TGX_OK) return st;
     if (r->device != m->device) return fail(TGX_ERR_INVALID, "%s: the result is on device %d, the model on device %d", who, r->device, m->device);
     if ((uint64_t)r->vocab_size > (uint64_t)m->vocab_size + n_specials)
         return fail(TGX_ERR_INVALID, "%s: the result was written for %u ids, the model has %u tokens and %u special tokens", who, r->vocab_size,
                     m->vocab_size, n_specials);
     DeviceScope scope;
     HIP_TRY(hipSetDevice(m->device));
-    hipStream_t hs = stream ? static_cast<hipStream_t>(stream) : layout_stream(m->device);
+    hipStream_t hs = stream_or_default(stream, m->device);
     tgx::DecodeSrc src = {};
     src.ids = r->d_ids.get();
     src.offs = r->d_offs.get();
@@ -2766,15 +2546,15 @@ tgx_status tgx_decode_padded(tgx_model* m, const void* d_ids, uint64_t n_rows, u
     if (n_rows && row_len && n_rows > 0xFFFFFFFFFFFFFFFFull / 16 / row_len) return fail(TGX_ERR_UNSUPPORTED, "%s: %llu rows of %llu elements", who, (unsigned long long)n_rows, (unsigned long long)row_len);
     const uint64_t N = n_rows * row_len;
     if (N && !d_ids) return fail(TGX_ERR_INVALID, "%s: d_ids is NULL", who);
-    if (usable_device_count() <= 0) return fail(TGX_ERR_DEVICE, "no usable HIP device (gfx950 required)");
+    if ((st = require_device()) != TGX_OK) return st;
     DeviceScope scope;
     HIP_TRY(hipSetDevice(m->device));
     if (N) {
-        if ((st = decode_check_src(who, "d_ids", d_ids, m->device)) != TGX_OK) return st;
-        if ((st = decode_check_src(who, "d_mask", d_mask, m->device)) != TGX_OK) return st;
-        if ((st = decode_check_src(who, "d_lengths", d_lengths, m->device)) != TGX_OK) return st;
+        if ((st = check_device_ptr(who, "d_ids", d_ids, m->device, "model")) != TGX_OK) return st;
+        if ((st = check_device_ptr(who, "d_mask", d_mask, m->device, "model")) != TGX_OK) return st;
+        if ((st = check_device_ptr(who, "d_lengths", d_lengths, m->device, "model")) != TGX_OK) return st;
     }
-    hipStream_t hs = stream ? static_cast<hipStream_t>(stream) : layout_stream(m->device);
+    hipStream_t hs = stream_or_default(stream, m->device);
     tgx::DecodeSrc src = {};
     src.ids = d_ids;
     src.mask = d_mask;
@@ -2826,164 +2606,9 @@ tgx_status tgx_corpus_from_text(const tgx_text* t, tgx_corpus** out) {
     return corpus_create(who, t->device, t->d_bytes, true, offs.data(), t->n_rows, out);
 }
 
-tgx_status tgx_decode_rows_host(const uint8_t* vocab_bytes, const uint64_t* vocab_offs, uint32_t vocab_size, const uint8_t* special_bytes,
-                                const uint64_t* special_offs, uint32_t n_specials, const void* ids, uint32_t id_kind, const uint64_t* id_offs,
-                                uint64_t n_rows, uint64_t row_len, const uint8_t* mask, const int32_t* lengths, uint32_t skip_id, int include_special,
-                                uint8_t** out_text, uint64_t* out_offs, uint64_t* n_replaced, uint64_t* bad_sample, uint64_t* bad_id) {
-    const char* who = "tgx_decode_rows_host";
-    if (!vocab_offs || !out_text || !out_offs) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
-    *out_text = nullptr;
-    if (id_kind > tgx::kDecodeI64) return fail(TGX_ERR_INVALID, "%s: id_kind %u", who, id_kind);
-    if (id_offs && id_kind != tgx::kDecodeU32) return fail(TGX_ERR_INVALID, "%s: the offsets form takes u32 ids", who);
-    tgx_status st = decode_check_specials(who, vocab_size, special_bytes, special_offs, n_specials);
-    if (st != TGX_OK) return st;
-    if (id_offs && (st = layout_check_host(who, static_cast<const uint32_t*>(ids), id_offs, n_rows)) != TGX_OK) return st;
-    if (!id_offs && n_rows && row_len && n_rows > 0xFFFFFFFFFFFFFFFFull / 16 / row_len) return fail(TGX_ERR_UNSUPPORTED, "%s: too many elements", who);
-    const uint64_t S = n_rows, N = id_offs ? id_offs[S] : n_rows * row_len;
-    if (N && !ids) return fail(TGX_ERR_INVALID, "%s: ids is NULL", who);
-    std::vector<uint8_t> len;
-    std::vector<tgx::DecodeSlot> slots;
-    if ((st = decode_build_tables(who, vocab_bytes, vocab_offs, vocab_size, &len, &slots)) != TGX_OK) return st;
-    static const uint64_t kNoOffs[1] = {0};
-    tgx::DecodeTables tab = {};
-    tab.tok_len = len.data();
-    tab.slots = slots.data();
-    tab.bytes = vocab_bytes;
-    tab.offs = vocab_offs;
-    tab.sp_bytes = special_bytes;
-    tab.sp_offs = n_specials ? special_offs : kNoOffs;
-    tab.vocab_size = vocab_size;
-    tab.n_specials = n_specials;
-    tab.include_special = include_special ? 1 : 0;
-    tgx::DecodeSrc src = {};
-    src.ids = ids;
-    src.offs = id_offs;
-    src.mask = id_offs ? nullptr : mask;
-    src.lengths = id_offs ? nullptr : lengths;
-    src.n_rows = S;
-    src.row_len = row_len;
-    src.n = N;
-    src.kind = id_kind;
-    src.skip_id = id_offs ? TGX_NO_ID : skip_id;
-    if (n_replaced) *n_replaced = 0;
-    for (uint64_t i = 0; i <= S; i++) out_offs[i] = 0;
-    // as the device: the elements' meta words, the two scans, ...
-    std::vector<uint64_t> B(N + 1), X(N + 1);
-    uint64_t bad = ~0ull, n_live_specials = 0;
-    for (uint64_t j = 0, b = 0, x = 0; j <= N; j++) {
-        B[j] = b;
-        X[j] = x;
-        if (j == N) break;
-        const int64_t v = tgx::decode_elem(src, j);
-        if (!tgx::decode_live(src, j, v)) continue;
-        bool oob;
-        const uint32_t meta = tgx::decode_meta(tab, v, &oob);
-        if (oob && j < bad) bad = j;
-        b += meta & ~tgx::kDecodeSpecial;
-        x += meta >> 31;
-        n_live_specials += meta >> 31;
-    }
-    if (bad != ~0ull) {
-        const uint64_t row = id_offs ? (uint64_t)(std::upper_bound(id_offs, id_offs + S + 1, bad) - id_offs) - 1 : bad / row_len;
-        return decode_oob(id_kind, tgx::decode_elem(src, bad), row, bad_sample, bad_id);
-    }
-    const uint64_t T = B[N], G = (T + tgx::kDecodeGroup - 1) / tgx::kDecodeGroup;
-    uint8_t* raw = static_cast<uint8_t*>(aligned_alloc(16, (size_t)G * tgx::kDecodeGroup + 16));
-    if (!raw) return fail(TGX_ERR_INVALID, "%s: out of host memory", who);
-    if (T == 0) {
-        *out_text = raw;
-        return TGX_OK;
-    }
-    memset(raw, 0xA5, (size_t)G * tgx::kDecodeGroup + 16);  // (what lies behind the text may be anything)
-    std::vector<uint32_t> flags(G), codes(G + 1, 0);
-    // ... the fill kernel's tiles and thread slots, ...
-    for (uint64_t t0 = 0; t0 < T; t0 += tgx::kDecodeTile) {
-        const uint64_t last = tgx::decode_tile_last(t0, T);
-        const uint64_t lo = tgx::decode_find(B.data(), 0, N - 1, tgx::decode_tile_first(t0)), hi = tgx::decode_find(B.data(), 0, N - 1, last);
-        for (uint64_t e0 = t0; e0 <= last; e0 += tgx::kDecodeGroup) {
-            const uint32_t n_in = last + 1 - e0 < tgx::kDecodeGroup ? (uint32_t)(last + 1 - e0) : tgx::kDecodeGroup;
-            uint8_t v[tgx::kDecodeGroup] = {};
-            flags[e0 / tgx::kDecodeGroup] = tgx::decode_group(tab, src, B.data(), n_live_specials ? X.data() : nullptr, lo, hi, e0, n_in, v);
-            memcpy(raw + e0, v, n_in);
-        }
-    }
-    // ... the rows' raw starts, which start runs, ...
-    for (uint64_t i = 0; i <= S; i++) {
-        const uint64_t r = B[i < S ? tgx::decode_row_first(src, i) : N];
-        out_offs[i] = r;
-        if (r < T) flags[r / tgx::kDecodeGroup] |= 1u << (uint32_t)(r % tgx::kDecodeGroup);
-    }
-    // ... the UTF-8 rule per slot, ...
-    uint64_t replaced = 0;
-    for (uint64_t g = 0; g < G; g++) {
-        codes[g] = tgx::decode_utf8_slot(raw, flags.data(), T, g);
-        replaced += tgx::decode_code_replaced(codes[g]);
-    }
-    if (n_replaced) *n_replaced = replaced;
-    if (replaced == 0) {
-        *out_text = raw;
-        return TGX_OK;
-    }
-    // ... and, after a replacement, the slots' positions and the second copy
-    std::vector<uint64_t> gpos(G + 1);
-    for (uint64_t g = 0, at = 0; g <= G; g++) {
-        gpos[g] = at;
-        at += tgx::decode_code_bytes(codes[g], tgx::kDecodeGroup);
-    }
-    uint8_t* text = static_cast<uint8_t*>(malloc((size_t)std::max<uint64_t>(1, gpos[G])));
-    if (!text) {
-        free(raw);
-        return fail(TGX_ERR_INVALID, "%s: out of host memory", who);
-    }
-    for (uint64_t g = 0; g < G; g++) tgx::decode_expand_slot(raw, T, g, codes[g], text, gpos[g]);
-    for (uint64_t i = 0; i <= S; i++) out_offs[i] = tgx::decode_final_pos(gpos.data(), codes.data(), out_offs[i], T);
-    free(raw);
-    *out_text = text;
-    return TGX_OK;
-}
-
 // ---- spans: the part of its row's text that every token covers (spans.hip; spans.h has the index arithmetic) ------
 
 namespace {
-
-// one word per token of a vocabulary: what the meta kernel (a device copy) and the host twin read
-tgx_status span_build_words(const char* who, const uint8_t* bytes, const uint64_t* offs, uint32_t V, std::vector<uint16_t>* words) {
-    words->assign(V, 0);
-    for (uint32_t i = 0; i < V; i++) {
-        if (offs[i + 1] < offs[i]) return fail(TGX_ERR_INVALID, "%s: vocabulary offsets not monotone at %u", who, i);
-        const uint64_t n = offs[i + 1] - offs[i];
-        if (n > TGX_MAX_TOKEN_LEN) return fail(TGX_ERR_UNSUPPORTED, "%s: token of %llu bytes exceeds TGX_MAX_TOKEN_LEN (%d)", who, (unsigned long long)n, TGX_MAX_TOKEN_LEN);
-        (*words)[i] = tgx::span_word(bytes + offs[i], (uint32_t)n);
-    }
-    return TGX_OK;
-}
-
-// the special tokens' words; the byte unit reads no byte of theirs
-void span_special_words(const uint8_t* special_bytes, const uint64_t* special_offs, uint32_t n_specials, bool chars, std::vector<uint64_t>* words) {
-    words->assign((size_t)n_specials + 1, 0);
-    for (uint32_t k = 0; k < n_specials; k++)
-        (*words)[k] = tgx::span_special_word(chars ? special_bytes + special_offs[k] : nullptr, special_offs[k + 1] - special_offs[k]);
-}
-
-// flags, specials and the padded form's arguments: what the device entry points and the host twin check alike
-tgx_status span_check_args(const char* who, uint32_t vocab_size, const uint8_t* special_bytes, const uint64_t* special_offs, uint32_t n_specials,
-                           bool padded, uint32_t row_len, uint32_t bos_id, uint32_t eos_id, uint32_t flags) {
-    tgx_status st = layout_check_flags(who, flags, TGX_LAYOUT_I64 | TGX_SPAN_CHARS | (padded ? TGX_LAYOUT_PAD_LEFT | TGX_LAYOUT_TRUNC_LEFT : 0u));
-    static const uint8_t unread = 0;  // the byte unit does not look at special_bytes, which may then be NULL
-    if (st == TGX_OK) st = decode_check_specials(who, vocab_size, (flags & TGX_SPAN_CHARS) ? special_bytes : &unread, special_offs, n_specials);
-    if (st == TGX_OK && padded) st = layout_check_ids(who, 0, bos_id, eos_id);
-    if (st != TGX_OK) return st;
-    if (padded) {
-        const tgx::LayoutSeq seq = tgx::layout_seq(bos_id, eos_id, 0);
-        if (row_len < 1 || row_len < seq.extra) return fail(TGX_ERR_INVALID, "%s: row_len %u (needs >= 1 and >= %u for bos / eos)", who, row_len, seq.extra);
-    }
-    return TGX_OK;
-}
-
-tgx_status span_too_long(const char* who, uint64_t row_max, bool chars) {
-    return fail(TGX_ERR_UNSUPPORTED, "%s: a row of %llu %s does not fit int32 spans (TGX_LAYOUT_I64 takes it)", who, (unsigned long long)row_max,
-                chars ? "characters" : "bytes");
-}
 
 // the model's token words on its device, once (under m->mu)
 tgx_status ensure_span_words(tgx_model* m) {
@@ -2999,14 +2624,6 @@ tgx_status ensure_span_words(tgx_model* m) {
     return TGX_OK;
 }
 
-// the buffers of one call; they go back to the pool after the stream has reached its end (StreamEnd below them)
-struct SpanWork {
-    PoolBuf<uint32_t> vals;
-    PoolBuf<uint64_t> sums, sp_words;
-    PoolBuf<void> scan;
-    PoolBuf<unsigned long long> row_max;
-};
-
 // row_len = 0: the flat form
 tgx_status spans_device(const char* who, tgx_model* m, const tgx_result* r, const uint8_t* special_bytes, const uint64_t* special_offs,
                         uint32_t n_specials, uint32_t row_len, uint32_t bos_id, uint32_t eos_id, uint32_t flags, void* stream, void* d_spans) {
@@ -3017,7 +2634,8 @@ tgx_status spans_device(const char* who, tgx_model* m, const tgx_result* r, cons
     const uint64_t S = r->n_samples, T = r->n_tokens;
     const uint64_t n_pairs = padded ? S * (uint64_t)row_len : (S ? T : 0);
     if (!d_spans && n_pairs) return fail(TGX_ERR_INVALID, "%s: d_spans is NULL", who);
-    if (usable_device_count() <= 0) return fail(TGX_ERR_DEVICE, "no usable HIP device (gfx950 required)");
+    tgx_status st = require_device();
+    if (st != TGX_OK) return st;
     if (r->device != m->device) return fail(TGX_ERR_INVALID, "%s: the result is on device %d, the model on device %d", who, r->device, m->device);
     if ((uint64_t)r->vocab_size > (uint64_t)m->vocab_size + n_specials)
         return fail(TGX_ERR_INVALID, "%s: the result was written for %u ids, the model has %u tokens and %u special tokens", who, r->vocab_size,
@@ -3025,99 +2643,69 @@ tgx_status spans_device(const char* who, tgx_model* m, const tgx_result* r, cons
     if (n_pairs == 0) return TGX_OK;
     DeviceScope scope;
     HIP_TRY(hipSetDevice(m->device));
-    tgx_status st = layout_check_dest(who, "d_spans", d_spans, m->device);
-    if (st != TGX_OK) return st;
-    hipStream_t hs = stream ? static_cast<hipStream_t>(stream) : layout_stream(m->device);
+    if ((st = check_device_ptr(who, "d_spans", d_spans, m->device, "result")) != TGX_OK) return st;
+    hipStream_t hs = stream_or_default(stream, m->device);
     const int dev = m->device;
     const bool i64 = (flags & TGX_LAYOUT_I64) != 0;
     if (T == 0) {  // the padded form of rows without tokens
-        const hipError_t e = hipMemsetAsync(d_spans, 0, (size_t)n_pairs * 2 * (i64 ? 8 : 4), hs);
-        const hipError_t es = hipStreamSynchronize(hs);
-        HIP_TRY(e);
-        HIP_TRY(es);
+        StreamGuard guard(dev, hs);
+        HIP_TRY(hipMemsetAsync(d_spans, 0, (size_t)n_pairs * 2 * (i64 ? 8 : 4), hs));
+        HIP_TRY(hipStreamSynchronize(hs));
+        guard.done();
         return TGX_OK;
     }
     if ((st = ensure_span_words(m)) != TGX_OK) return st;
 
-    std::vector<uint64_t> sp_words;  // alive until the stream has taken them
+    std::vector<uint64_t> sp_words;
     span_special_words(special_bytes, special_offs, n_specials, chars, &sp_words);
     size_t scan_bytes = 0;
     if (tgx::span_scan_temp_bytes(T, &scan_bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan temp-size query failed");
-    SpanWork w;
-    StreamEnd end(hs);  // destroyed before w: a failed call's queued work is over before its buffers change hands
-    HIP_TRY(w.vals.alloc(dev, (size_t)(T + 1) * 4));
-    HIP_TRY(w.sums.alloc(dev, (size_t)(T + 1) * 8));
-    HIP_TRY(w.scan.alloc(dev, scan_bytes));  // (never NULL: that asks the scan for its size)
-    HIP_TRY(w.sp_words.alloc(dev, sp_words.size() * 8));
-    HIP_TRY(hipMemcpyAsync(w.sp_words, sp_words.data(), sp_words.size() * 8, hipMemcpyHostToDevice, hs));
+    StreamGuard guard(dev, hs);
+    uint32_t* vals = nullptr;
+    uint64_t *sums = nullptr, *d_sp_words = nullptr;
+    void* scan = nullptr;
+    HIP_TRY(guard.alloc((size_t)(T + 1) * 4, &vals));
+    HIP_TRY(guard.alloc((size_t)(T + 1) * 8, &sums));
+    HIP_TRY(guard.alloc(scan_bytes, &scan));  // (never NULL: that asks the scan for its size)
+    HIP_TRY(guard.alloc(sp_words.size() * 8, &d_sp_words));
+    HIP_TRY(guard.upload(d_sp_words, std::move(sp_words)));
 
     tgx::SpanParams p = {};
     p.tab.words = m->d_span_words;
-    p.tab.sp_words = w.sp_words;
+    p.tab.sp_words = d_sp_words;
     p.tab.vocab_size = m->vocab_size;
     p.tab.n_specials = n_specials;
     p.ids = r->d_ids;
     p.offs = r->d_offs;
     p.n_rows = S;
     p.n = T;
-    p.vals = w.vals;
-    p.sums = w.sums;
+    p.vals = vals;
+    p.sums = sums;
     p.len = row_len;
     p.bos = bos_id;
     p.eos = eos_id;
     p.flags = flags;
     p.out = d_spans;
-    HIP_TRY(tgx::launch_span_sums(p, w.scan, scan_bytes, hs));
+    HIP_TRY(tgx::launch_span_sums(p, scan, scan_bytes, hs));
     if (!i64) {  // nothing is written when a row does not fit: the one word that is read back
-        unsigned long long h_max = 0;
-        HIP_TRY(w.row_max.alloc(dev, sizeof(unsigned long long)));
-        p.row_max = w.row_max;
-        HIP_TRY(hipMemsetAsync(w.row_max, 0, sizeof(unsigned long long), hs));
+        unsigned long long h_max = 0, *row_max = nullptr;
+        HIP_TRY(guard.alloc(sizeof(unsigned long long), &row_max));
+        p.row_max = row_max;
+        HIP_TRY(hipMemsetAsync(row_max, 0, sizeof(unsigned long long), hs));
         HIP_TRY(tgx::launch_span_row_max(p, hs));
-        HIP_TRY(hipMemcpyAsync(&h_max, w.row_max, sizeof(unsigned long long), hipMemcpyDeviceToHost, hs));
+        HIP_TRY(hipMemcpyAsync(&h_max, row_max, sizeof(unsigned long long), hipMemcpyDeviceToHost, hs));
         HIP_TRY(hipStreamSynchronize(hs));
         if (h_max >= 0x80000000ull) {
-            end.done();
+            guard.done();
             return span_too_long(who, h_max, chars);
         }
     }
     HIP_TRY(padded ? tgx::launch_span_pad(p, hs) : tgx::launch_span_flat(p, hs));
     // the stream has reached its end before the result or the destination can change hands
     HIP_TRY(hipStreamSynchronize(hs));
-    end.done();
+    guard.done();
     return TGX_OK;
 }
-
-extern "C++" {  // (this part of the file is inside extern "C")
-template <class T>
-void spans_host_write(const tgx::LayoutSeq& seq, const uint64_t* offs, uint64_t n_rows, uint64_t n, const uint64_t* P, const uint32_t* vals,
-                      uint32_t row_len, uint32_t flags, T* out) {
-    if (row_len) {  // as the kernel: one pair per slot
-        for (uint64_t e = 0; e < n_rows * (uint64_t)row_len; e++) {
-            tgx::SpanPair s = {0, 0};
-            if (n) s = tgx::span_pad_at(seq, offs, P, vals, row_len, flags, e);
-            out[2 * e] = (T)s.start;
-            out[2 * e + 1] = (T)s.end;
-        }
-        return;
-    }
-    // as the kernel: tiles of kSpanTile elements, the owners of a tile's ends bound the search inside it, and a group of
-    // consecutive elements walks on from row to row
-    for (uint64_t t0 = 0; t0 < n; t0 += tgx::kSpanTile) {
-        const uint64_t last = tgx::span_tile_last(t0, n);
-        const uint64_t lo = tgx::pack_find_row(offs, 0, 0, n_rows - 1, t0), hi = tgx::pack_find_row(offs, 0, 0, n_rows - 1, last);
-        for (uint64_t e0 = t0; e0 <= last; e0 += tgx::kSpanGroup) {
-            const uint32_t n_in = last + 1 - e0 < tgx::kSpanGroup ? (uint32_t)(last + 1 - e0) : tgx::kSpanGroup;
-            tgx::SpanPair v[tgx::kSpanGroup] = {};
-            tgx::span_group(offs, P, vals, lo, hi, e0, n_in, v);
-            for (uint32_t k = 0; k < n_in; k++) {
-                out[2 * (e0 + k)] = (T)v[k].start;
-                out[2 * (e0 + k) + 1] = (T)v[k].end;
-            }
-        }
-    }
-}
-}  // extern "C++"
 
 }  // namespace
 
@@ -3132,54 +2720,6 @@ tgx_status tgx_result_pad_spans_device(tgx_model* m, const tgx_result* r, const 
     const char* who = "tgx_result_pad_spans_device";
     if (row_len == 0) return fail(TGX_ERR_INVALID, "%s: row_len 0 (needs >= 1)", who);
     return spans_device(who, m, r, special_bytes, special_offs, n_specials, row_len, bos_id, eos_id, flags, stream, d_spans);
-}
-
-tgx_status tgx_spans_host(const uint8_t* vocab_bytes, const uint64_t* vocab_offs, uint32_t vocab_size, const uint8_t* special_bytes,
-                          const uint64_t* special_offs, uint32_t n_specials, const uint32_t* ids, const uint64_t* offs, uint64_t n_rows,
-                          uint32_t row_len, uint32_t bos_id, uint32_t eos_id, uint32_t flags, void* out) {
-    const char* who = "tgx_spans_host";
-    if (!vocab_offs) return fail(TGX_ERR_INVALID, "%s: vocab_offs is NULL", who);
-    const bool padded = row_len != 0, chars = (flags & TGX_SPAN_CHARS) != 0, i64 = (flags & TGX_LAYOUT_I64) != 0;
-    tgx_status st = span_check_args(who, vocab_size, special_bytes, special_offs, n_specials, padded, row_len, bos_id, eos_id, flags);
-    if (st == TGX_OK) st = layout_check_host(who, ids, offs, n_rows);
-    if (st != TGX_OK) return st;
-    const uint64_t S = n_rows, T = offs[S];
-    const uint64_t n_pairs = padded ? S * (uint64_t)row_len : (S ? T : 0);
-    if (n_pairs == 0) return TGX_OK;
-    if (!out) return fail(TGX_ERR_INVALID, "%s: out is NULL", who);
-    std::vector<uint16_t> words;
-    if ((st = span_build_words(who, vocab_bytes, vocab_offs, vocab_size, &words)) != TGX_OK) return st;
-    std::vector<uint64_t> sp_words;
-    span_special_words(special_bytes, special_offs, n_specials, chars, &sp_words);
-    tgx::SpanTables tab = {};
-    tab.words = words.data();
-    tab.sp_words = sp_words.data();
-    tab.vocab_size = vocab_size;
-    tab.n_specials = n_specials;
-    // the meta pass and the scan
-    std::vector<uint32_t> vals((size_t)T + 1, 0);
-    std::vector<uint64_t> P((size_t)T + 1, 0);
-    for (uint64_t j = 0; j < T; j++) {
-        bool oob;
-        vals[j] = tgx::span_val(tab, ids[j], chars, &oob);
-        if (oob) {
-            const uint64_t row = (uint64_t)(std::upper_bound(offs, offs + S + 1, j) - offs) - 1;
-            return decode_oob(tgx::kDecodeU32, ids[j], row, nullptr, nullptr);
-        }
-        P[j + 1] = P[j] + (vals[j] & ~tgx::kSpanValCont);
-    }
-    if (!i64) {
-        uint64_t row_max = 0;
-        for (uint64_t i = 0; i < S; i++) row_max = std::max(row_max, tgx::span_row_total(P.data(), offs, i));
-        if (row_max >= 0x80000000ull) return span_too_long(who, row_max, chars);
-    }
-    const tgx::LayoutSeq seq = tgx::layout_seq(bos_id, eos_id, 0);
-    const uint32_t* v = chars ? vals.data() : nullptr;
-    if (i64)
-        spans_host_write(seq, offs, S, T, P.data(), v, row_len, flags, static_cast<int64_t*>(out));
-    else
-        spans_host_write(seq, offs, S, T, P.data(), v, row_len, flags, static_cast<int32_t*>(out));
-    return TGX_OK;
 }
 
 // ---- frequency pass ------------------------------------------------------------
@@ -3738,10 +3278,10 @@ static tgx_status estep_z_failure(const tgx_model* m, const tgx_corpus* c, const
     const unsigned long long bad = m->h_ctrl->err;
     if (bad == ~0ULL) return TGX_OK;
     const uint64_t smp = snip_sample ? snip_sample[bad] : bad;
-    g_err_sample = smp;
-    g_err_pos = g_err_len = c->h_offs[smp + 1] - c->h_offs[smp];
+    const uint64_t len = c->h_offs[smp + 1] - c->h_offs[smp];
+    set_error_detail(smp, len, len);
     return fail(TGX_ERR_Z_NOT_NORMAL, "normalization constant is not a normal number (sample %llu, len=%llu)",
-                (unsigned long long)smp, (unsigned long long)g_err_len);  // the reference panics here: src/prune.rs:90-96
+                (unsigned long long)smp, (unsigned long long)len);  // the reference panics here: src/prune.rs:90-96
 }
 // counts by slot of the reversed trie -> expected[id]
 static void add_slot_counts(const tgx_model* m, const std::vector<double>& h, double* expected) {
@@ -4403,7 +3943,7 @@ static tgx_status sample_corpus_locked(tgx_model* m, tgx_corpus* c, double alpha
 }
 
 tgx_status tgx_encode_corpus_sample(tgx_model* m, tgx_corpus* c, double alpha, uint64_t seed, double* logz, tgx_result** out) {
-    if (usable_device_count() <= 0) return fail(TGX_ERR_DEVICE, "no usable HIP device (gfx950 required)");
+    if (const tgx_status dst = require_device()) return dst;
     if (!m || !c || !out) return fail(TGX_ERR_INVALID, "tgx_encode_corpus_sample: NULL argument");
     *out = nullptr;
     if (m->device != c->device) return fail(TGX_ERR_INVALID, "model and corpus on different devices");
@@ -4416,7 +3956,7 @@ tgx_status tgx_encode_corpus_sample(tgx_model* m, tgx_corpus* c, double alpha, u
 
 tgx_status tgx_encode_batch_sample(tgx_model* m, const uint8_t* text, const uint64_t* offs, uint64_t n_samples, double alpha,
                                    uint64_t seed, double* logz, tgx_result** out) {
-    if (usable_device_count() <= 0) return fail(TGX_ERR_DEVICE, "no usable HIP device (gfx950 required)");
+    if (const tgx_status dst = require_device()) return dst;
     if (!m || !out) return fail(TGX_ERR_INVALID, "tgx_encode_batch_sample: NULL argument");
     *out = nullptr;
     {
@@ -4589,7 +4129,7 @@ static tgx_status nbest_corpus_locked(tgx_model* m, tgx_corpus* c, uint32_t k, d
 }
 
 tgx_status tgx_encode_corpus_nbest(tgx_model* m, tgx_corpus* c, uint32_t nbest, double* scores, uint32_t* n_found, tgx_result** out) {
-    if (usable_device_count() <= 0) return fail(TGX_ERR_DEVICE, "no usable HIP device (gfx950 required)");
+    if (const tgx_status dst = require_device()) return dst;
     if (!m || !c || !out) return fail(TGX_ERR_INVALID, "tgx_encode_corpus_nbest: NULL argument");
     *out = nullptr;
     if (m->device != c->device) return fail(TGX_ERR_INVALID, "model and corpus on different devices");
@@ -4602,7 +4142,7 @@ tgx_status tgx_encode_corpus_nbest(tgx_model* m, tgx_corpus* c, uint32_t nbest, 
 
 tgx_status tgx_encode_batch_nbest(tgx_model* m, const uint8_t* text, const uint64_t* offs, uint64_t n_samples, uint32_t nbest,
                                   double* scores, uint32_t* n_found, tgx_result** out) {
-    if (usable_device_count() <= 0) return fail(TGX_ERR_DEVICE, "no usable HIP device (gfx950 required)");
+    if (const tgx_status dst = require_device()) return dst;
     if (!m || !out) return fail(TGX_ERR_INVALID, "tgx_encode_batch_nbest: NULL argument");
     *out = nullptr;
     {
@@ -4638,5 +4178,3 @@ uint32_t tgx_last_encode_corun_cus(const tgx_model* m) { return m ? m->last_coru
 uint32_t tgx_encode_corun_timeouts(const tgx_model* m) { return m ? m->corun_wait_timeouts : 0; }
 uint32_t tgx_model_score_values(const tgx_model* m) { return m && m->have_trie8 ? m->n_values : 0u; }
 uint32_t tgx_last_encode_hot_values(const tgx_model* m) { return m ? m->last_n_hot : 0u; }
-
-}  // extern "C"

@@ -15,7 +15,7 @@
 #include "../../include/tgx.h"
 #include "unicode_tables.h"
 
-tgx_status tgx_set_error(tgx_status st, const char* msg);  // tgx_api.cpp
+#include "api_internal.h"  // tgx_set_error: the message tgx_last_error() returns
 
 namespace {
 
