@@ -201,10 +201,10 @@ __global__ __launch_bounds__(640) void encode2_kernel(EncodeParams P) {
 
 // trace_kernel (kernels.hip) for tokens of up to 32 bytes (trace_body.h).
 // PERM: the back-pointer bytes are in encode4_kernel's permuted layout (bp8_perm; encode4l_kernel), else plain
-template <bool PERM, bool CARRY>
+template <bool PERM, bool CARRY, int K>
 __global__ __launch_bounds__(256) void trace32_kernel(EncodeParams P) {
     __shared__ typename TraceRingEntry<CARRY>::type ring_all[4][kTraceRing];
-    trace_body<32, PERM, false, CARRY>(P, ring_all[threadIdx.x >> 6]);
+    trace_body<32, PERM, false, CARRY, K>(P, ring_all[threadIdx.x >> 6]);
 }
 
 // two blocks of five waves per CU: 10 x 16 KiB of LDS
@@ -219,10 +219,23 @@ hipError_t launch_encode2(const EncodeParams& p, uint32_t num_cus, bool permuted
     hipLaunchKernelGGL(fn, dim3(blocks), dim3(64u * waves), waves * kRows2Bytes, stream, p);
     return hipGetLastError();
 }
+template <bool PERM, bool CARRY>
+static void launch_trace32_stride(const EncodeParams& p, uint32_t blocks, hipStream_t stream) {
+    switch (p.trace_stride) {  // the hop stage's stride exponent (trace_body.h: trace_hops)
+        case 1: hipLaunchKernelGGL((trace32_kernel<PERM, CARRY, 1>), dim3(blocks), dim3(256), 0, stream, p); break;
+        case 2: hipLaunchKernelGGL((trace32_kernel<PERM, CARRY, 2>), dim3(blocks), dim3(256), 0, stream, p); break;
+        case 3: hipLaunchKernelGGL((trace32_kernel<PERM, CARRY, 3>), dim3(blocks), dim3(256), 0, stream, p); break;
+        default: hipLaunchKernelGGL((trace32_kernel<PERM, CARRY, 0>), dim3(blocks), dim3(256), 0, stream, p); break;
+    }
+}
 hipError_t launch_trace32(const EncodeParams& p, uint32_t blocks, bool permuted, hipStream_t stream) {
-    auto fn = permuted ? (p.trace_carry ? trace32_kernel<true, true> : trace32_kernel<true, false>)
-                       : (p.trace_carry ? trace32_kernel<false, true> : trace32_kernel<false, false>);
-    hipLaunchKernelGGL(fn, dim3(blocks), dim3(256), 0, stream, p);
+    if (permuted) {
+        if (p.trace_carry) launch_trace32_stride<true, true>(p, blocks, stream);
+        else launch_trace32_stride<true, false>(p, blocks, stream);
+    } else {
+        if (p.trace_carry) launch_trace32_stride<false, true>(p, blocks, stream);
+        else launch_trace32_stride<false, false>(p, blocks, stream);
+    }
     return hipGetLastError();
 }
 

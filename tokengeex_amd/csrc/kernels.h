@@ -8,6 +8,9 @@
 
 namespace tgx {
 
+// Default stride exponent of the trace kernels' hop stage (trace_body.h: trace_hops; TGX_TRACE_STRIDE overrides it).
+constexpr uint32_t kTraceStride = 2;
+
 struct EncodeParams {
     const uint8_t* text;            // u8[N (+ pad)]
     const uint64_t* offs;           // u64[S+1]
@@ -35,6 +38,7 @@ struct EncodeParams {
     uint32_t flags;                 // timing experiments only (TGX_FLAGS env): see kernels.hip
     unsigned long long* stamps;     // diagnostic build only (TGX_STAMPS=1): 8 u64 per wave
     uint32_t trace_carry;           // trace kernels: waiting tokens carry over from sample to sample (short samples: trace_body.h)
+    uint32_t trace_stride;          // trace kernels: the hop chain visits every 2^trace_stride-th token of a window's path (0 .. 3: trace_body.h)
 };
 
 // encode5_kernel / encode6_kernel (encode5.hip): 8-byte label-checked records, score values by rank

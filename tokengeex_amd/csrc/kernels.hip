@@ -599,10 +599,10 @@ __global__ __launch_bounds__(1024, (PPL == 1 ? 6 : 1)) void encode4_kernel(Encod
 }
 
 // Back-trace + id emission for the rows4 path (trace_body.h).
-template <bool STAMP, bool CARRY>
+template <bool STAMP, bool CARRY, int K>
 __global__ __launch_bounds__(256) void trace_kernel(EncodeParams P) {
     __shared__ typename TraceRingEntry<CARRY>::type ring_all[4][kTraceRing];
-    trace_body<16, true, STAMP, CARRY>(P, ring_all[threadIdx.x >> 6]);
+    trace_body<16, true, STAMP, CARRY, K>(P, ring_all[threadIdx.x >> 6]);
 }
 
 // counts[S] -> offsets[S+1] (exclusive prefix sum), one workgroup.
@@ -754,13 +754,22 @@ hipError_t launch_encode4(const EncodeParams& p, int ppl, int waves, uint32_t bl
     hipLaunchKernelGGL(fn, dim3(blocks), dim3(64u * (uint32_t)waves), encode4_lds_bytes(waves, stamp ? 1 : ppl, root), stream, p);
     return hipGetLastError();
 }
+template <bool STAMP, bool CARRY>
+static void launch_trace_stride(const EncodeParams& p, uint32_t blocks, hipStream_t stream) {
+    switch (p.trace_stride) {  // the hop stage's stride exponent (trace_body.h: trace_hops)
+        case 1: hipLaunchKernelGGL((trace_kernel<STAMP, CARRY, 1>), dim3(blocks), dim3(256), 0, stream, p); break;
+        case 2: hipLaunchKernelGGL((trace_kernel<STAMP, CARRY, 2>), dim3(blocks), dim3(256), 0, stream, p); break;
+        case 3: hipLaunchKernelGGL((trace_kernel<STAMP, CARRY, 3>), dim3(blocks), dim3(256), 0, stream, p); break;
+        default: hipLaunchKernelGGL((trace_kernel<STAMP, CARRY, 0>), dim3(blocks), dim3(256), 0, stream, p); break;
+    }
+}
 hipError_t launch_trace(const EncodeParams& p, uint32_t blocks, hipStream_t stream) {
     if (p.stamps)
-        hipLaunchKernelGGL((trace_kernel<true, false>), dim3(blocks), dim3(256), 0, stream, p);
+        launch_trace_stride<true, false>(p, blocks, stream);
     else if (p.trace_carry)
-        hipLaunchKernelGGL((trace_kernel<false, true>), dim3(blocks), dim3(256), 0, stream, p);
+        launch_trace_stride<false, true>(p, blocks, stream);
     else
-        hipLaunchKernelGGL((trace_kernel<false, false>), dim3(blocks), dim3(256), 0, stream, p);
+        launch_trace_stride<false, false>(p, blocks, stream);
     return hipGetLastError();
 }
 

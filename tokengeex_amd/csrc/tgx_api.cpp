@@ -644,6 +644,7 @@ tgx::EncodeParams base_encode_params(const tgx_model* m, const tgx_corpus* c, ui
     // samples of less than 2 KiB on average: the trace keeps its waiting tokens across samples (trace_body.h; 140-byte samples
     // 5.5 -> 4.6 ms per GiB, 9 KiB samples 2.93 -> 3.04)
     p.trace_carry = (c->n_samples && c->n_bytes / c->n_samples < 2048) ? 1u : 0u;
+    p.trace_stride = tgx::kTraceStride;
     return p;
 }
 
@@ -677,6 +678,7 @@ tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64
     tgx::EncodeParams p = base_encode_params(m, c, seed);
     p.dropout = dropout;
     if (const char* e = knob("TGX_TRACE_CARRY")) p.trace_carry = atoi(e) ? 1u : 0u;
+    if (const char* e = knob("TGX_TRACE_STRIDE")) p.trace_stride = (uint32_t)std::min(3, std::max(0, atoi(e)));
     p.flags = debug_flags();
     // TGX_PATH=fused forces the one-sample-per-wave kernel (A/B timing, tests of both paths)
     const char* force = knob("TGX_PATH");
@@ -994,10 +996,16 @@ tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64
         p.order = c->d_order;
         p.n_samples = c->n_samples;
         const uint32_t blocks_t = trace_blocks(m, c->n_samples);
+        // TGX_STAMPS=2: the STAMP build of trace_kernel (tokens <= 16 bytes, ring flushed per sample)
+        Stamps stamps_t;
+        if (!long_tokens) stamps_t = stamps_begin(m, pass, '2', (size_t)blocks_t * 4);
+        p.stamps = stamps_t.d;
         time_begin(m, long_tokens ? "trace32_kernel" : "trace_kernel");
         if (long_tokens) HIP_TRY(tgx::launch_trace32(p, blocks_t, true, m->stream));
         else HIP_TRY(tgx::launch_trace(p, blocks_t, m->stream));
         time_end(m);
+        if (stamps_t.d) stamps_report(m, stamps_t, 0, "trace stamps", "window", {"setup", "loads", "hops", "append+lookups", "-"});
+        p.stamps = nullptr;
     } else if (use4) {
         // Vocabularies without 8-byte records (more than 65 535 distinct score values): round 1's kernel over the
         // 16-byte records, scores through the match buffer.

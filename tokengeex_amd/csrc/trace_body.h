@@ -32,6 +32,60 @@ constexpr uint32_t kTraceRing = 128;  // entries per wave: < 64 waiting + up to 
         t_last = _now;                                                 \
     }
 
+// The hop stage of one window.  prev: per lane, where the token that ends at the lane's position starts, relative to the
+// window (always below the lane; negative: the token starts in a window below, and the value is the window's exit code,
+// -1 .. -LM).  qq: the lane the path enters the window at; on return the exit code the path leaves it with.  Returns the
+// lanes of the path (`ends`).  All 64 lanes must be active.
+//
+// K = 0 follows one back-pointer per scalar step: s_bitset1 . s_nop . v_readlane . s_cmp . s_cbranch per token, each
+// waiting for the one before.  K > 0 first squares the pointer map K times on the vector side
+// (p2 = prev o prev is one ds_bpermute for the whole window; an exit code saturates: it is kept, not followed), runs the
+// same scalar loop over prev^(2^K), which visits every 2^K-th token of the path and ends with the first negative value
+// along it, i.e. with the scalar loop's exit code, and then fills the skipped tokens in for all visited lanes at once,
+// top-down: the members so far push a flag along p_(2^k), k = K-1 .. 0.
+// The push is a ds_permute_b32 with every lane active and the same value, 1, from all of them: a member with a
+// non-negative p_(2^k) sends it to that lane, every other lane to lane 63, whose result is masked off.  No lane whose
+// result is used has two senders: the path is strictly decreasing, so p_(2^k) is injective on its members, which gives
+// lanes 0 .. 62 at most one sender each; a target is below its sender, so it is never lane 63, which is already known
+// (it is on the path only as the entry lane); and a lane that nobody writes receives 0.
+__device__ __forceinline__ int32_t trace_lane_addr(int32_t p) {  // the permutes' byte address of lane p
+    return (p < 0 ? 0 : p) << 2;  // clamped: what a lane with an exit code reads or sends is discarded
+}
+__device__ __forceinline__ int32_t trace_square(int32_t p) {  // lane i: p[p[i]], an exit code kept
+    const int32_t got = __builtin_amdgcn_ds_bpermute(trace_lane_addr(p), p);
+    return p < 0 ? p : got;
+}
+template <int K>
+__device__ __forceinline__ uint64_t trace_hops(uint32_t prev, int32_t& qq) {
+    static_assert(K >= 0 && K <= 3, "strides of 1, 2, 4, 8 tokens");
+    if constexpr (K == 0) {
+        uint64_t ends = 0;
+        while (qq >= 0) {  // model.rs:113-126, 64 positions per load
+            asm("s_bitset1_b64 %0, %1" : "+s"(ends) : "s"(qq));  // ends |= 1 << qq
+            qq = (int32_t)readlane_u32(prev, (uint32_t)qq);
+        }
+        return ends;
+    } else {
+        int32_t p[K + 1];  // p[k] = prev^(2^k)
+        p[0] = (int32_t)prev;
+#pragma unroll
+        for (int k = 1; k <= K; ++k) p[k] = trace_square(p[k - 1]);
+        uint64_t visited = 0;
+        while (qq >= 0) {
+            asm("s_bitset1_b64 %0, %1" : "+s"(visited) : "s"(qq));
+            qq = (int32_t)readlane_u32((uint32_t)p[K], (uint32_t)qq);
+        }
+        uint64_t on = visited;  // the path's lanes found so far: a wave-uniform mask, used as one (no per-lane copy of it)
+#pragma unroll
+        for (int k = K - 1; k >= 0; --k) {
+            const bool send = __builtin_amdgcn_inverse_ballot_w64(on) && p[k] >= 0;
+            const int32_t got = __builtin_amdgcn_ds_permute(send ? trace_lane_addr(p[k]) : 63 << 2, 1);
+            on |= __builtin_amdgcn_ballot_w64(got != 0) & ~(1ULL << 63);
+        }
+        return on;
+    }
+}
+
 // LM: longest token, 16 or 32 (back-pointer bytes hold length - 1 in their low 4 / 5 bits).
 // PERM: the back-pointer bytes are in encode4_kernel's permuted layout (bp8_perm), else plain.
 // `ring`: kTraceRing entries of LDS owned by the calling wave.
@@ -40,7 +94,8 @@ constexpr uint32_t kTraceRing = 128;  // entries per wave: < 64 waiting + up to 
 // of kilobytes, where a flush per sample costs nothing).
 template <bool CARRY> struct TraceRingEntry { using type = uint2; };
 template <> struct TraceRingEntry<true> { using type = uint4; };
-template <uint32_t LM, bool PERM, bool STAMP, bool CARRY>
+// K: the hop stage's stride exponent (trace_hops).
+template <uint32_t LM, bool PERM, bool STAMP, bool CARRY, int K>
 __device__ __forceinline__ void trace_body(const EncodeParams& P, typename TraceRingEntry<CARRY>::type* ring) {
     static_assert(LM == 16 || LM == 32, "token lengths of up to 16 or 32 bytes");
     constexpr uint32_t LMASK = LM - 1u;
@@ -197,12 +252,8 @@ __device__ __forceinline__ void trace_body(const EncodeParams& P, typename Trace
             uint32_t h_next = 0;
             if (wq >= 64u) h_next = (uint32_t)bp[PERM ? bp8_perm(wq - 64u + lane) : wq - 64u + lane];
             TGX_TRACE_STAMP(1)  // window loads issued / consumed
-            uint64_t ends = 0;
             int32_t qq = (int32_t)((uint32_t)q - wq);
-            while (qq >= 0) {  // model.rs:113-126, 64 positions per load
-                asm("s_bitset1_b64 %0, %1" : "+s"(ends) : "s"(qq));  // ends |= 1 << qq
-                qq = (int32_t)readlane_u32(prev, (uint32_t)qq);
-            }
+            const uint64_t ends = trace_hops<K>(prev, qq);
             q = (int64_t)wq + qq;
             const uint32_t cnt = (uint32_t)__popcll(ends);
             TGX_TRACE_STAMP(2)  // hops
