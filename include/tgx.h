@@ -294,6 +294,57 @@ tgx_status tgx_layout_pack_host(const uint32_t *ids, const uint64_t *offs, uint6
                                 uint32_t bos_id, uint32_t eos_id, uint32_t flags, void *out_ids, int32_t *out_doc,
                                 int32_t *out_pos, uint64_t *n_blocks);
 
+/* ---- overflow windows: a row longer than row_len as overlapping [W, L] windows, written on the device ------------
+ * What truncation with a stride and "return overflowing tokens" give: every token of a long row, in windows of row_len
+ * elements that each repeat `stride` tokens of the window before, each tagged with the row it came from.  Kernels of
+ * csrc/layout.hip over the window mapping of csrc/layout.h; ids, flags, elements and the stream rule as in the layouts
+ * above.
+ *
+ * With row_len = L and A as above: room = L - A tokens per window, step = room - stride.  L >= A + 1 and
+ *   0 <= stride < room, else TGX_ERR_INVALID before anything is queued.
+ * Row i with n_i tokens has nw_i = 1 windows if n_i <= room, else 1 + ceil((n_i - room) / step): an empty row is one
+ *   window of padding.  Windows are ordered by row, then by k = 0 .. nw_i - 1: Wo[i] = the exclusive prefix sum of nw,
+ *   W = Wo[S]; window w belongs to the largest i with Wo[i] <= w, and k = w - Wo[i].
+ * Window k keeps the row's tokens [k·step, min(n_i, k·step + room)); with TGX_LAYOUT_TRUNC_LEFT the windows run from the
+ *   row's end: tokens [n_i - min(n_i, k·step + room), n_i - k·step).  first_w = the first kept index, keep_w the count.
+ * Row w of out[W, L] holds [bos] + kept + [eos], len_w = keep_w + A elements, at its start, or at its end with
+ *   TGX_LAYOUT_PAD_LEFT; the rest of the row is pad_id.  d_mask (NULL or u8[W·L]): 1 on the sequence, 0 on padding.
+ *   d_lengths (NULL or i32[W]): len_w.  d_window_row (NULL or i32[W]): i, the overflow-to-sample mapping.
+ *   d_window_first (NULL or i32[W]): first_w.
+ * So window 0 of row i is row i of the padded form, and when no row is longer than room, W = S and every output equals
+ *   that of tgx_result_pad_device / tgx_result_pad_spans_device for the same arguments.
+ * tgx_result_window_spans_device writes d_spans[W, L, 2], aligned element for element with the ids: a kept token gets
+ *   exactly the span tgx_result_spans_device gives it, relative to its whole row's text (bytes, or TGX_SPAN_CHARS), so
+ *   the pairs index the sample; bos, eos and padding get (0, 0).  Model, specials, units and the int32 rule for a row's
+ *   total are those of the spans section below.
+ * tgx_result_window_info gives *n_windows = W for sizing the destinations: a count kernel, a scan over the S rows and
+ *   one read-back, on the library's stream.  The other two calls take the W the caller sized its buffers for as
+ *   n_windows, compute W again (nothing is kept on the result) and return TGX_ERR_INVALID, with nothing written, when
+ *   the two differ.  W >= 2^31, or a row of 2^31 tokens or more: TGX_ERR_UNSUPPORTED, nothing written.  S = 0: W = 0,
+ *   TGX_OK, nothing written.
+ * Host twins (tgx_layout_windows_host, tgx_window_spans_host; arrays as for the twins above and tgx_spans_host): the
+ *   same semantics through the same window mapping, no device.  They first compute W and store it to *n_windows_out;
+ *   with out_ids / out NULL that is all they do.  Otherwise n_windows must equal W as above. */
+tgx_status tgx_result_window_info(const tgx_result *r, uint32_t row_len, uint32_t stride, uint32_t bos_id, uint32_t eos_id,
+                                  uint32_t flags, uint64_t *n_windows);
+tgx_status tgx_result_window_pad_device(const tgx_result *r, uint32_t row_len, uint32_t stride, uint32_t pad_id,
+                                        uint32_t bos_id, uint32_t eos_id, uint32_t flags, void *stream, uint64_t n_windows,
+                                        void *d_ids, uint8_t *d_mask, int32_t *d_lengths, int32_t *d_window_row,
+                                        int32_t *d_window_first);
+tgx_status tgx_result_window_spans_device(tgx_model *m, const tgx_result *r, const uint8_t *special_bytes,
+                                          const uint64_t *special_offs, uint32_t n_specials, uint32_t row_len,
+                                          uint32_t stride, uint32_t bos_id, uint32_t eos_id, uint32_t flags, void *stream,
+                                          uint64_t n_windows, void *d_spans);
+tgx_status tgx_layout_windows_host(const uint32_t *ids, const uint64_t *offs, uint64_t n_rows, uint32_t row_len,
+                                   uint32_t stride, uint32_t pad_id, uint32_t bos_id, uint32_t eos_id, uint32_t flags,
+                                   uint64_t n_windows, void *out_ids, uint8_t *out_mask, int32_t *out_lengths,
+                                   int32_t *out_window_row, int32_t *out_window_first, uint64_t *n_windows_out);
+tgx_status tgx_window_spans_host(const uint8_t *vocab_bytes, const uint64_t *vocab_offs, uint32_t vocab_size,
+                                 const uint8_t *special_bytes, const uint64_t *special_offs, uint32_t n_specials,
+                                 const uint32_t *ids, const uint64_t *offs, uint64_t n_rows, uint32_t row_len,
+                                 uint32_t stride, uint32_t bos_id, uint32_t eos_id, uint32_t flags, uint64_t n_windows,
+                                 void *out, uint64_t *n_windows_out);
+
 /* ---- assembly: a sample-level result with the special tokens' ids, put together on the device ----------------
  * The special-aware encode (Tokenizer::encode_batch, src/tokenizer.rs:65-90) splits every sample at its special tokens,
  * encodes the segments between them and concatenates, per sample, the special tokens' ids and the segments' ids.

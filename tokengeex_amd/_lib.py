@@ -133,6 +133,11 @@ SYMBOLS = {
     "tgx_result_spans_device": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp]),
     "tgx_result_pad_spans_device": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, _vp]),
     "tgx_spans_host": (_i, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _u64, _u32, _u32, _u32, _u32, _vp]),
+    "tgx_result_window_info": (_i, [_vp, _u32, _u32, _u32, _u32, _u32, _pu64]),
+    "tgx_result_window_pad_device": (_i, [_vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "tgx_result_window_spans_device": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _u64, _vp]),
+    "tgx_layout_windows_host": (_i, [_vp, _vp, _u64, _u32, _u32, _u32, _u32, _u32, _u32, _u64, _vp, _vp, _vp, _vp, _vp, _pu64]),
+    "tgx_window_spans_host": (_i, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _u64, _u32, _u32, _u32, _u32, _u32, _u64, _vp, _pu64]),
 }
 
 
@@ -597,6 +602,66 @@ def layout_pack_host(ids: np.ndarray, offs: np.ndarray, block_len: int, pad_id: 
     return {"input_ids": out, "doc_ids": doc, "positions": pos}
 
 
+def layout_windows_host(ids: np.ndarray, offs: np.ndarray, row_len: int, stride: int, pad_id: int, *, bos_id: int | None = None,
+                        eos_id: int | None = None, padding_side: str = "right", truncation_side: str = "right", dtype=np.int32,
+                        n_windows: int | None = None) -> dict:
+    """Host twin of NativeResult.window_pad_device (tgx_layout_windows_host: the same window mapping, no device) over ids
+    u32[T] and offsets u64[S+1] -> {"input_ids": [W, row_len] of dtype, "attention_mask": u8 [W, row_len], "lengths",
+    "overflow_to_sample_mapping" and "window_first": i32[W]}: every row as windows of row_len elements that repeat `stride`
+    tokens of the window before.  n_windows: what the destinations are sized for (None: the twin is asked for W first)."""
+    ids = np.ascontiguousarray(ids, dtype=np.uint32)
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    n, L = offs.shape[0] - 1, _u32_arg(row_len, "row_len")
+    args = (ptr(ids) if ids.size else None, ptr(offs), n, L, _u32_arg(stride, "stride"), _u32_arg(pad_id, "pad_id"), _id_or_none(bos_id),
+            _id_or_none(eos_id), layout_flags(padding_side, truncation_side, dtype))
+    got = C.c_uint64()
+    if n_windows is None:
+        check(lib.tgx_layout_windows_host(*args, 0, None, None, None, None, None, C.byref(got)))
+        n_windows = got.value
+    W = int(n_windows)
+    out = np.empty((W, L), np.dtype(dtype))
+    mask = np.empty((W, L), np.uint8)
+    lengths, row, first = (np.empty(W, np.int32) for _ in range(3))
+    keep = np.empty(1, np.dtype(dtype))   # a destination even when W = 0: NULL asks for W alone
+    check(lib.tgx_layout_windows_host(*args, W, ptr(out) if out.size else ptr(keep), ptr(mask) if mask.size else None,
+                                      ptr(lengths) if W else None, ptr(row) if W else None, ptr(first) if W else None, C.byref(got)))
+    assert got.value == W, (got.value, W)
+    return {"input_ids": out, "attention_mask": mask, "lengths": lengths, "overflow_to_sample_mapping": row, "window_first": first}
+
+
+def window_spans_host(vocab_flat, vocab_offs, vocab_size: int, special_flat, special_offs, n_specials: int, ids: np.ndarray, offs: np.ndarray, *,
+                      row_len: int, stride: int, unit: str = "byte", dtype=np.int32, bos_id: int | None = None, eos_id: int | None = None,
+                      padding_side: str = "right", truncation_side: str = "right", n_windows: int | None = None) -> np.ndarray:
+    """Host twin of NativeResult.window_spans_device (tgx_window_spans_host) -> [W, row_len, 2] of dtype, aligned element for
+    element with layout_windows_host's input_ids: a kept token's span in its whole row's text, (0, 0) elsewhere."""
+    vocab_flat = np.ascontiguousarray(vocab_flat, dtype=np.uint8)
+    vocab_offs = np.ascontiguousarray(vocab_offs, dtype=np.uint64)
+    special_flat = np.ascontiguousarray(special_flat, dtype=np.uint8)
+    special_offs = np.ascontiguousarray(special_offs, dtype=np.uint64)
+    ids = np.ascontiguousarray(ids, dtype=np.uint32)
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    n, L = offs.shape[0] - 1, _u32_arg(row_len, "row_len")
+    args = (ptr(vocab_flat) if vocab_flat.size else None, ptr(vocab_offs), _u32_arg(vocab_size, "vocab_size"),
+            ptr(special_flat) if special_flat.size else None, ptr(special_offs), _u32_arg(n_specials, "n_specials"),
+            ptr(ids) if ids.size else None, ptr(offs), n, L, _u32_arg(stride, "stride"), _id_or_none(bos_id), _id_or_none(eos_id),
+            span_flags(unit, dtype, padding_side, truncation_side))
+    got = C.c_uint64()
+    if n_windows is None:
+        check(lib.tgx_window_spans_host(*args, 0, None, C.byref(got)))
+        n_windows = got.value
+    W = int(n_windows)
+    out = np.empty((W, L, 2), np.dtype(dtype))
+    keep = np.empty(1, np.dtype(dtype))
+    st = lib.tgx_window_spans_host(*args, W, ptr(out) if out.size else ptr(keep), C.byref(got))
+    if st == ERR_TOKEN_ID_OOB:  # the row and the id, as the decode twins name them
+        bs, bi, _ = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        lib.tgx_last_error_detail(C.byref(bs), C.byref(bi), C.byref(_))
+        _raise_decode(st, bs.value, bi.value)
+    check(st)
+    assert got.value == W, (got.value, W)
+    return out
+
+
 class NativeResult:
     """Owns a tgx_result (ids + offsets of one encode pass)."""
 
@@ -680,6 +745,39 @@ class NativeResult:
         check(lib.tgx_result_pack_device(self._h, _u32_arg(block_len, "block_len"), _u32_arg(pad_id, "pad_id"), _id_or_none(bos_id), _id_or_none(eos_id),
                                          int(flags), stream or None, ids_ptr or None, doc_ptr or None, pos_ptr or None, C.byref(nb)))
         return nb.value
+
+    # -- overflow windows (include/tgx.h: tgx_result_window_pad_device / tgx_result_window_spans_device) --
+    def window_info(self, row_len: int, stride: int = 0, *, bos_id: int | None = None, eos_id: int | None = None, flags: int = 0) -> int:
+        """-> W, the windows of row_len elements (stride tokens repeated from one to the next) that the rows give: what
+        sizes the destinations of window_pad_device / window_spans_device.  Counted and scanned on the device; one word
+        comes back."""
+        w = C.c_uint64()
+        check(lib.tgx_result_window_info(self._h, _u32_arg(row_len, "row_len"), _u32_arg(stride, "stride"), _id_or_none(bos_id),
+                                         _id_or_none(eos_id), _u32_arg(flags, "flags"), C.byref(w)))
+        return w.value
+
+    def window_pad_device(self, row_len: int, stride: int, pad_id: int, n_windows: int, ids_ptr: int, *, mask_ptr: int = 0,
+                          lengths_ptr: int = 0, window_row_ptr: int = 0, window_first_ptr: int = 0, bos_id: int | None = None,
+                          eos_id: int | None = None, flags: int = 0, stream: int = 0) -> None:
+        """Every row as overlapping windows, written by the device into caller-owned device memory given as raw integer
+        pointers (ids: i32 or, with LAYOUT_I64, i64 [W·row_len]; mask u8[W·row_len]; lengths, window_row — the row a window
+        came from — and window_first — the index of its first kept token in that row — i32[W]; 0 = not wanted), as
+        pad_device.  n_windows is the W of window_info the destinations are sized for: the call counts again and raises
+        (ERR_INVALID) without writing when it finds another number."""
+        check(lib.tgx_result_window_pad_device(self._h, _u32_arg(row_len, "row_len"), _u32_arg(stride, "stride"), _u32_arg(pad_id, "pad_id"),
+                                               _id_or_none(bos_id), _id_or_none(eos_id), int(flags), stream or None, int(n_windows),
+                                               ids_ptr or None, mask_ptr or None, lengths_ptr or None, window_row_ptr or None,
+                                               window_first_ptr or None))
+
+    def window_spans_device(self, model: "NativeModel", special_flat, special_offs, row_len: int, stride: int, n_windows: int,
+                            spans_ptr: int, *, bos_id: int | None = None, eos_id: int | None = None, flags: int = 0, stream: int = 0) -> None:
+        """The offsets mapping of window_pad_device's ids: [W, row_len, 2] int32 (int64 with LAYOUT_I64), a kept token's span
+        in its whole row's text (SPAN_CHARS: in code points), (0, 0) on bos, eos and padding; model and specials as in
+        NativeModel.result_spans."""
+        sf, so, n = model._specials(special_flat, special_offs)
+        check(lib.tgx_result_window_spans_device(model._h, self._h, ptr(sf) if sf.size else None, ptr(so), n, _u32_arg(row_len, "row_len"),
+                                                 _u32_arg(stride, "stride"), _id_or_none(bos_id), _id_or_none(eos_id), _u32_arg(flags, "flags"),
+                                                 stream or None, int(n_windows), spans_ptr or None))
 
     def pad_host(self, row_len: int, pad_id: int, **kw) -> dict:
         """layout_pad_host over the ids and offsets copied to the host."""

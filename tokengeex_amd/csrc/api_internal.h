@@ -44,6 +44,10 @@ inline void set_error_detail(uint64_t sample, uint64_t pos, uint64_t len) {
 tgx_status layout_check_ids(const char* who, uint32_t pad_id, uint32_t bos_id, uint32_t eos_id);
 tgx_status layout_check_flags(const char* who, uint32_t flags, uint32_t allowed);
 tgx_status layout_check_row_len(const char* who, uint32_t row_len, uint32_t extra);
+// the windowed layout: row_len >= extra + 1 and stride < row_len - extra; then the longest row and the windows against
+// 2^31, and the windows against what the caller sized its buffers for (sized_for, NULL when nothing is written)
+tgx_status window_check_args(const char* who, uint32_t row_len, uint32_t stride, uint32_t extra);
+tgx_status window_check_totals(const char* who, uint64_t max_row, uint64_t n_windows, const uint64_t* sized_for);
 // ids and offsets of n_rows rows in host memory
 tgx_status layout_check_host(const char* who, const uint32_t* ids, const uint64_t* offs, uint64_t n_rows);
 tgx_status assemble_check(const char* who, const uint64_t* seg_offs, const int32_t* seg_special, uint64_t n_samples, uint32_t vocab_size,

@@ -1,6 +1,6 @@
 // The *_host twins of the result-side device entry points (include/tgx.h): tgx_layout_pad_host, tgx_layout_pack_host,
-// tgx_assemble_host, tgx_decode_rows_host and tgx_spans_host, and the argument checks they share with the device entry
-// points of tgx_api.cpp.  A twin goes through the same index arithmetic as its kernels (layout.h, assemble.h,
+// tgx_layout_windows_host, tgx_assemble_host, tgx_decode_rows_host, tgx_spans_host and tgx_window_spans_host, and the
+// argument checks they share with the device entry points of tgx_api.cpp.  A twin goes through the same index arithmetic as its kernels (layout.h, assemble.h,
 // decode.h, spans.h) on host memory.  Nothing in this file calls a HIP function, so it builds and runs without the
 // handles, the pool or a device.
 #include <algorithm>
@@ -57,6 +57,23 @@ tgx_status layout_check_ids(const char* who, uint32_t pad_id, uint32_t bos_id, u
 
 tgx_status layout_check_flags(const char* who, uint32_t flags, uint32_t allowed) {
     if (flags & ~allowed) return fail(TGX_ERR_INVALID, "%s: unknown flags 0x%x", who, flags & ~allowed);
+    return TGX_OK;
+}
+
+// a window holds its bos / eos and at least one token, and moves on by at least one token
+tgx_status window_check_args(const char* who, uint32_t row_len, uint32_t stride, uint32_t extra) {
+    if (row_len < extra + 1) return fail(TGX_ERR_INVALID, "%s: row_len %u (needs >= %u: bos / eos and one token)", who, row_len, extra + 1);
+    if (stride >= row_len - extra)
+        return fail(TGX_ERR_INVALID, "%s: stride %u (needs < %u, the tokens of a window)", who, stride, row_len - extra);
+    return TGX_OK;
+}
+
+tgx_status window_check_totals(const char* who, uint64_t max_row, uint64_t n_windows, const uint64_t* sized_for) {
+    if (max_row >= 0x80000000ull) return fail(TGX_ERR_UNSUPPORTED, "%s: a row of %llu tokens (2^31 or more)", who, (unsigned long long)max_row);
+    if (n_windows >= 0x80000000ull) return fail(TGX_ERR_UNSUPPORTED, "%s: %llu windows (2^31 or more)", who, (unsigned long long)n_windows);
+    if (sized_for && *sized_for != n_windows)
+        return fail(TGX_ERR_INVALID, "%s: %llu windows, the caller's n_windows is %llu", who, (unsigned long long)n_windows,
+                    (unsigned long long)*sized_for);
     return TGX_OK;
 }
 
@@ -260,6 +277,73 @@ tgx_status tgx_layout_pack_host(const uint32_t* ids, const uint64_t* offs, uint6
     return layout_pack_host(seq, ids, offs, n_rows, n_stream, nb * block_len, static_cast<int32_t*>(out_ids), out_doc, out_pos);
 }
 
+namespace {
+
+// as the count kernel and the scan: Wo[0 .. S] and the longest row
+void windows_host_offsets(const uint64_t* offs, uint64_t n_rows, uint32_t room, uint32_t step, std::vector<uint64_t>* wo, uint64_t* max_row) {
+    wo->assign((size_t)n_rows + 1, 0);
+    *max_row = 0;
+    for (uint64_t i = 0; i < n_rows; i++) {
+        const uint64_t n = offs[i + 1] - offs[i], nw = tgx::window_count(n, room, step);
+        (*wo)[i + 1] = (*wo)[i] + (nw < 0xFFFFFFFFull ? nw : 0xFFFFFFFFull);
+        *max_row = std::max(*max_row, n);
+    }
+}
+
+template <class T>
+tgx_status layout_windows_host(const tgx::LayoutSeq& seq, const uint32_t* ids, const uint64_t* offs, const uint64_t* wo, uint64_t n_rows,
+                               uint64_t n_windows, uint32_t L, uint32_t stride, uint32_t flags, T* out, uint8_t* mask, int32_t* lengths,
+                               int32_t* window_row, int32_t* window_first) {
+    // as the kernel: tiles of kPackTile elements of the flat [W, L] output, the owners of a tile's first and last window
+    // bound the search inside it, and groups of kLayoutGroup consecutive elements are walked by win_group
+    const uint64_t total = n_windows * (uint64_t)L;
+    for (uint64_t t0 = 0; t0 < total; t0 += tgx::kPackTile) {
+        const uint64_t last = t0 + tgx::kPackTile - 1 < total ? t0 + tgx::kPackTile - 1 : total - 1;
+        const uint64_t lo = tgx::pack_find_row(wo, 0, 0, n_rows - 1, t0 / L), hi = tgx::pack_find_row(wo, 0, 0, n_rows - 1, last / L);
+        for (uint64_t e0 = t0; e0 <= last; e0 += tgx::kLayoutGroup) {
+            const uint32_t n_in = last + 1 - e0 < tgx::kLayoutGroup ? (uint32_t)(last + 1 - e0) : tgx::kLayoutGroup;
+            uint32_t v[tgx::kLayoutGroup] = {0, 0, 0, 0};
+            const uint32_t m = tgx::win_group(seq, ids, offs, wo, L, stride, flags, lo, hi, e0, n_in, lengths, window_row, window_first, v);
+            for (uint32_t k = 0; k < n_in; k++) {
+                if (v[k] >= 0x80000000u)
+                    return fail(TGX_ERR_INVALID, "tgx_layout_windows_host: id %u of window %llu is not below 2^31", v[k],
+                                (unsigned long long)((e0 + k) / L));
+                out[e0 + k] = (T)v[k];
+                if (mask) mask[e0 + k] = (uint8_t)(m >> (8 * k));
+            }
+        }
+    }
+    return TGX_OK;
+}
+
+}  // namespace
+
+tgx_status tgx_layout_windows_host(const uint32_t* ids, const uint64_t* offs, uint64_t n_rows, uint32_t row_len, uint32_t stride, uint32_t pad_id,
+                                   uint32_t bos_id, uint32_t eos_id, uint32_t flags, uint64_t n_windows, void* out_ids, uint8_t* out_mask,
+                                   int32_t* out_lengths, int32_t* out_window_row, int32_t* out_window_first, uint64_t* n_windows_out) {
+    const char* who = "tgx_layout_windows_host";
+    if (!n_windows_out) return fail(TGX_ERR_INVALID, "%s: n_windows_out is NULL", who);
+    tgx_status st = layout_check_host(who, ids, offs, n_rows);
+    if (st == TGX_OK) st = layout_check_flags(who, flags, TGX_LAYOUT_PAD_LEFT | TGX_LAYOUT_TRUNC_LEFT | TGX_LAYOUT_I64);
+    if (st == TGX_OK) st = layout_check_ids(who, pad_id, bos_id, eos_id);
+    if (st != TGX_OK) return st;
+    const tgx::LayoutSeq seq = tgx::layout_seq(bos_id, eos_id, pad_id);
+    if ((st = window_check_args(who, row_len, stride, seq.extra)) != TGX_OK) return st;
+    std::vector<uint64_t> wo;
+    uint64_t max_row = 0;
+    windows_host_offsets(offs, n_rows, row_len - seq.extra, row_len - seq.extra - stride, &wo, &max_row);
+    const uint64_t W = wo[n_rows];
+    if ((st = window_check_totals(who, max_row, W, nullptr)) != TGX_OK) return st;
+    *n_windows_out = W;
+    if (!out_ids) return TGX_OK;
+    if ((st = window_check_totals(who, max_row, W, &n_windows)) != TGX_OK || W == 0) return st;
+    if (flags & TGX_LAYOUT_I64)
+        return layout_windows_host(seq, ids, offs, wo.data(), n_rows, W, row_len, stride, flags, static_cast<int64_t*>(out_ids), out_mask,
+                                   out_lengths, out_window_row, out_window_first);
+    return layout_windows_host(seq, ids, offs, wo.data(), n_rows, W, row_len, stride, flags, static_cast<int32_t*>(out_ids), out_mask,
+                               out_lengths, out_window_row, out_window_first);
+}
+
 // ---- assembly ---------------------------------------------------------------------
 
 tgx_status tgx_assemble_host(const uint32_t* ids, const uint64_t* id_offs, uint64_t n_encoded, const uint64_t* seg_offs,
@@ -448,6 +532,54 @@ void spans_host_write(const tgx::LayoutSeq& seq, const uint64_t* offs, uint64_t 
     }
 }
 
+// as the kernel: one pair per slot
+template <class T>
+void window_spans_host_write(const tgx::LayoutSeq& seq, const uint64_t* offs, const uint64_t* wo, uint64_t n_rows, uint64_t n, uint64_t n_windows,
+                             const uint64_t* P, const uint32_t* vals, uint32_t row_len, uint32_t stride, uint32_t flags, T* out) {
+    for (uint64_t e = 0; e < n_windows * (uint64_t)row_len; e++) {
+        tgx::SpanPair s = {0, 0};
+        if (n) s = tgx::span_window_at(seq, offs, wo, n_rows, P, vals, row_len, stride, flags, e);
+        out[2 * e] = (T)s.start;
+        out[2 * e + 1] = (T)s.end;
+    }
+}
+
+// The meta pass and the scan of the span writers, and the int32 check of the rows' totals: vals[0 .. T] and P[0 .. T].
+tgx_status span_host_sums(const char* who, const uint8_t* vocab_bytes, const uint64_t* vocab_offs, uint32_t vocab_size, const uint8_t* special_bytes,
+                          const uint64_t* special_offs, uint32_t n_specials, const uint32_t* ids, const uint64_t* offs, uint64_t S, bool chars,
+                          bool i64, std::vector<uint32_t>* vals_out, std::vector<uint64_t>* P_out) {
+    const uint64_t T = offs[S];
+    std::vector<uint16_t> words;
+    const tgx_status st = span_build_words(who, vocab_bytes, vocab_offs, vocab_size, &words);
+    if (st != TGX_OK) return st;
+    std::vector<uint64_t> sp_words;
+    span_special_words(special_bytes, special_offs, n_specials, chars, &sp_words);
+    tgx::SpanTables tab = {};
+    tab.words = words.data();
+    tab.sp_words = sp_words.data();
+    tab.vocab_size = vocab_size;
+    tab.n_specials = n_specials;
+    std::vector<uint32_t>& vals = *vals_out;
+    std::vector<uint64_t>& P = *P_out;
+    vals.assign((size_t)T + 1, 0);
+    P.assign((size_t)T + 1, 0);
+    for (uint64_t j = 0; j < T; j++) {
+        bool oob;
+        vals[j] = tgx::span_val(tab, ids[j], chars, &oob);
+        if (oob) {
+            const uint64_t row = (uint64_t)(std::upper_bound(offs, offs + S + 1, j) - offs) - 1;
+            return decode_oob(tgx::kDecodeU32, ids[j], row, nullptr, nullptr);
+        }
+        P[j + 1] = P[j] + (vals[j] & ~tgx::kSpanValCont);
+    }
+    if (!i64) {
+        uint64_t row_max = 0;
+        for (uint64_t i = 0; i < S; i++) row_max = std::max(row_max, tgx::span_row_total(P.data(), offs, i));
+        if (row_max >= 0x80000000ull) return span_too_long(who, row_max, chars);
+    }
+    return TGX_OK;
+}
+
 }  // namespace
 
 tgx_status tgx_spans_host(const uint8_t* vocab_bytes, const uint64_t* vocab_offs, uint32_t vocab_size, const uint8_t* special_bytes,
@@ -463,37 +595,51 @@ tgx_status tgx_spans_host(const uint8_t* vocab_bytes, const uint64_t* vocab_offs
     const uint64_t n_pairs = padded ? S * (uint64_t)row_len : (S ? T : 0);
     if (n_pairs == 0) return TGX_OK;
     if (!out) return fail(TGX_ERR_INVALID, "%s: out is NULL", who);
-    std::vector<uint16_t> words;
-    if ((st = span_build_words(who, vocab_bytes, vocab_offs, vocab_size, &words)) != TGX_OK) return st;
-    std::vector<uint64_t> sp_words;
-    span_special_words(special_bytes, special_offs, n_specials, chars, &sp_words);
-    tgx::SpanTables tab = {};
-    tab.words = words.data();
-    tab.sp_words = sp_words.data();
-    tab.vocab_size = vocab_size;
-    tab.n_specials = n_specials;
-    // the meta pass and the scan
-    std::vector<uint32_t> vals((size_t)T + 1, 0);
-    std::vector<uint64_t> P((size_t)T + 1, 0);
-    for (uint64_t j = 0; j < T; j++) {
-        bool oob;
-        vals[j] = tgx::span_val(tab, ids[j], chars, &oob);
-        if (oob) {
-            const uint64_t row = (uint64_t)(std::upper_bound(offs, offs + S + 1, j) - offs) - 1;
-            return decode_oob(tgx::kDecodeU32, ids[j], row, nullptr, nullptr);
-        }
-        P[j + 1] = P[j] + (vals[j] & ~tgx::kSpanValCont);
-    }
-    if (!i64) {
-        uint64_t row_max = 0;
-        for (uint64_t i = 0; i < S; i++) row_max = std::max(row_max, tgx::span_row_total(P.data(), offs, i));
-        if (row_max >= 0x80000000ull) return span_too_long(who, row_max, chars);
-    }
+    std::vector<uint32_t> vals;
+    std::vector<uint64_t> P;
+    if ((st = span_host_sums(who, vocab_bytes, vocab_offs, vocab_size, special_bytes, special_offs, n_specials, ids, offs, S, chars, i64, &vals,
+                             &P)) != TGX_OK)
+        return st;
     const tgx::LayoutSeq seq = tgx::layout_seq(bos_id, eos_id, 0);
     const uint32_t* v = chars ? vals.data() : nullptr;
     if (i64)
         spans_host_write(seq, offs, S, T, P.data(), v, row_len, flags, static_cast<int64_t*>(out));
     else
         spans_host_write(seq, offs, S, T, P.data(), v, row_len, flags, static_cast<int32_t*>(out));
+    return TGX_OK;
+}
+
+tgx_status tgx_window_spans_host(const uint8_t* vocab_bytes, const uint64_t* vocab_offs, uint32_t vocab_size, const uint8_t* special_bytes,
+                                 const uint64_t* special_offs, uint32_t n_specials, const uint32_t* ids, const uint64_t* offs, uint64_t n_rows,
+                                 uint32_t row_len, uint32_t stride, uint32_t bos_id, uint32_t eos_id, uint32_t flags, uint64_t n_windows, void* out,
+                                 uint64_t* n_windows_out) {
+    const char* who = "tgx_window_spans_host";
+    if (!vocab_offs || !n_windows_out) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
+    if (row_len == 0) return fail(TGX_ERR_INVALID, "%s: row_len 0 (needs >= 1)", who);
+    const bool chars = (flags & TGX_SPAN_CHARS) != 0, i64 = (flags & TGX_LAYOUT_I64) != 0;
+    tgx_status st = span_check_args(who, vocab_size, special_bytes, special_offs, n_specials, true, row_len, bos_id, eos_id, flags);
+    const tgx::LayoutSeq seq = tgx::layout_seq(bos_id, eos_id, 0);
+    if (st == TGX_OK) st = window_check_args(who, row_len, stride, seq.extra);
+    if (st == TGX_OK) st = layout_check_host(who, ids, offs, n_rows);
+    if (st != TGX_OK) return st;
+    const uint64_t S = n_rows, T = offs[S];
+    std::vector<uint64_t> wo;
+    uint64_t max_row = 0;
+    windows_host_offsets(offs, S, row_len - seq.extra, row_len - seq.extra - stride, &wo, &max_row);
+    const uint64_t W = wo[S];
+    if ((st = window_check_totals(who, max_row, W, nullptr)) != TGX_OK) return st;
+    *n_windows_out = W;
+    if (!out) return TGX_OK;
+    if ((st = window_check_totals(who, max_row, W, &n_windows)) != TGX_OK || W == 0) return st;
+    std::vector<uint32_t> vals;
+    std::vector<uint64_t> P;
+    if ((st = span_host_sums(who, vocab_bytes, vocab_offs, vocab_size, special_bytes, special_offs, n_specials, ids, offs, S, chars, i64, &vals,
+                             &P)) != TGX_OK)
+        return st;
+    const uint32_t* v = chars ? vals.data() : nullptr;
+    if (i64)
+        window_spans_host_write(seq, offs, wo.data(), S, T, W, P.data(), v, row_len, stride, flags, static_cast<int64_t*>(out));
+    else
+        window_spans_host_write(seq, offs, wo.data(), S, T, W, P.data(), v, row_len, stride, flags, static_cast<int32_t*>(out));
     return TGX_OK;
 }

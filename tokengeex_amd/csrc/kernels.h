@@ -296,7 +296,7 @@ hipError_t scan_temp_bytes(uint64_t n, size_t* bytes);
 hipError_t launch_scan(uint32_t* counts, uint64_t* offsets, uint64_t n, void* temp, size_t temp_bytes, hipStream_t stream);
 hipError_t launch_compact(const CompactParams& p, uint32_t blocks, bool rows, hipStream_t stream);
 
-// layout.hip: a result's ids laid out as [S, L] padded rows or as a packed stream of [B, L] blocks (layout.h has the
+// layout.hip: a result's ids laid out as [S, L] padded rows, a packed stream of [B, L] blocks or [W, L] windows (layout.h has the
 // row mapping).  Outputs are caller-owned device memory; any of mask / lengths / doc / pos / counter may be null.
 struct LayoutParams {
     const uint32_t* ids;            // u32[T]
@@ -316,6 +316,19 @@ hipError_t launch_layout_max_row(const uint64_t* offs, uint64_t n_rows, unsigned
 hipError_t launch_layout_pad(const LayoutParams& p, hipStream_t stream);
 // n_stream = T + S·A positions hold ids, n_out = n_blocks · block_len elements are written
 hipError_t launch_layout_pack(const LayoutParams& p, uint64_t n_stream, uint64_t n_out, hipStream_t stream);
+// The windowed layout: base.out / mask / lengths are [W, L] / [W·L] / [W]; base.counter, doc and pos are not used.
+struct WindowParams {
+    LayoutParams base;
+    const uint64_t* wo;             // u64[S+1]: Wo, the rows' first windows (launch_scan over the counts)
+    uint32_t stride;                // tokens a window repeats of the one before: < L - A
+    int32_t* window_row;            // i32[W] or null: the row a window came from
+    int32_t* window_first;          // i32[W] or null: index of its first kept token in that row
+};
+// counts[i] = the windows of row i (u32[S+1]: the last entry belongs to the scan); the longest row goes to *max_out
+// (zeroed by the caller)
+hipError_t launch_layout_window_count(const uint64_t* offs, uint64_t n_rows, uint32_t room, uint32_t step, uint32_t* counts,
+                                      unsigned long long* max_out, hipStream_t stream);
+hipError_t launch_layout_windows(const WindowParams& q, uint64_t n_windows, hipStream_t stream);
 
 // assemble.hip: a sample-level result from the result over the non-special segments and the split plan (assemble.h has
 // the index arithmetic).  All pointers are device memory.
@@ -385,5 +398,7 @@ hipError_t launch_span_sums(const SpanParams& p, void* temp, size_t temp_bytes, 
 hipError_t launch_span_row_max(const SpanParams& p, hipStream_t stream);                              // after the sums
 hipError_t launch_span_flat(const SpanParams& p, hipStream_t stream);
 hipError_t launch_span_pad(const SpanParams& p, hipStream_t stream);
+// [W, L, 2] over the windows of WindowParams::wo (p.len = L, p.out = the pairs)
+hipError_t launch_span_windows(const SpanParams& p, const uint64_t* wo, uint32_t stride, uint64_t n_windows, hipStream_t stream);
 
 }  // namespace tgx

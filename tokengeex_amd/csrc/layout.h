@@ -1,6 +1,7 @@
-// Row mapping of the padded and packed layouts of a result (include/tgx.h: tgx_result_pad_device, tgx_result_pack_device).
-// The kernels of layout.hip and the host twins in host_twins.cpp (tgx_layout_pad_host, tgx_layout_pack_host) both go
-// through these functions, so a machine without a GPU checks the kernels' index arithmetic.
+// Row mapping of the padded, packed and windowed layouts of a result (include/tgx.h: tgx_result_pad_device,
+// tgx_result_pack_device, tgx_result_window_pad_device).  The kernels of layout.hip and the host twins in host_twins.cpp
+// (tgx_layout_pad_host, tgx_layout_pack_host, tgx_layout_windows_host) both go through these functions, so a machine
+// without a GPU checks the kernels' index arithmetic.
 //
 // Row i has the tokens ids[offs[i] .. offs[i+1]); offs[0] = 0.  A = how many of bos / eos are present.  A written
 // sequence is [bos] + kept tokens + [eos].
@@ -142,6 +143,72 @@ __host__ __device__ inline uint32_t pack_at(const LayoutSeq& s, const uint32_t* 
     const uint64_t b = offs[i], q = j - (b + i * s.extra);
     *pos = (int32_t)q;
     return layout_seq_at(s, ids, b, offs[i + 1] - b, q);
+}
+
+// ---- windows: out[w, c], w < W, c < L: a long row as overlapping windows (tgx_result_window_pad_device) -------------
+// room = L - A >= 1 tokens per window, of which stride < room repeat the window before: step = room - stride >= 1.
+__host__ __device__ inline uint64_t window_count(uint64_t n, uint32_t room, uint32_t step) {
+    return n <= room ? 1 : 1 + (n - room + step - 1) / step;
+}
+
+struct WinRow {
+    PadRow p;        // the window as a padded row: src, keep, len, col0 (truncated: the row has more than one window)
+    uint32_t first;  // index of the first kept token in its row
+};
+
+// Window w of row i, which owns it: Wo[i] <= w < Wo[i+1], Wo = the exclusive prefix sums of window_count.  Window
+// k = w - Wo[i] keeps the row's tokens [k·step, min(n, k·step + room)), counted from the row's end with
+// kLayoutTruncLeft.  k·step < n for k >= 1, so every window keeps a token unless the row is empty.
+__host__ __device__ inline WinRow win_row(const uint64_t* offs, const uint64_t* Wo, uint64_t i, uint64_t w, uint32_t L, const LayoutSeq& s,
+                                          uint32_t stride, uint32_t flags) {
+    const uint64_t b = offs[i], n = offs[i + 1] - b;
+    const uint32_t room = L - s.extra, step = room - stride;
+    const uint64_t lo = (w - Wo[i]) * step;
+    const uint64_t hi = n - lo < room ? n : lo + room;
+    const uint64_t first = (flags & kLayoutTruncLeft) ? n - hi : lo;
+    WinRow r;
+    r.p.keep = (uint32_t)(hi - lo);
+    r.p.src = b + first;
+    r.p.len = r.p.keep + s.extra;
+    r.p.col0 = (flags & kLayoutPadLeft) ? L - r.p.len : 0;
+    r.p.truncated = n > room ? 1u : 0u;
+    r.first = (uint32_t)first;
+    return r;
+}
+
+// A thread slot's walk over n_in <= kLayoutGroup consecutive elements of the flat [W, L] output from element e0 on, as
+// pad_group's.  lo / hi: the rows that own the first and last window of the slot's tile (pack_find_row over Wo with
+// A = 0: Wo is strictly increasing); a row cursor steps from window to window.  The slot that holds a window's first
+// column writes lengths[w], window_row[w] and window_first[w] (each when wanted).
+__host__ __device__ inline uint32_t win_group(const LayoutSeq& s, const uint32_t* ids, const uint64_t* offs, const uint64_t* Wo, uint32_t L,
+                                              uint32_t stride, uint32_t flags, uint64_t lo, uint64_t hi, uint64_t e0, uint32_t n_in,
+                                              int32_t* lengths, int32_t* window_row, int32_t* window_first, uint32_t (&v)[kLayoutGroup]) {
+    uint64_t w = e0 / L;
+    uint32_t c = (uint32_t)(e0 - w * L);
+    PackCursor cur;
+    uint64_t i = pack_advance(cur, Wo, 0, lo, hi, w);
+    WinRow row = win_row(offs, Wo, i, w, L, s, stride, flags);
+    uint32_t m = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < kLayoutGroup; k++) {
+        if (k < n_in) {
+            if (c == 0) {
+                if (lengths) lengths[w] = (int32_t)row.p.len;
+                if (window_row) window_row[w] = (int32_t)i;
+                if (window_first) window_first[w] = (int32_t)row.first;
+            }
+            m |= pad_at(s, row.p, ids, c, &v[k]) << (8 * k);
+            if (++c == L) {
+                c = 0;
+                w++;
+                if (k + 1 < n_in) {
+                    i = pack_advance(cur, Wo, 0, lo, hi, w);
+                    row = win_row(offs, Wo, i, w, L, s, stride, flags);
+                }
+            }
+        }
+    }
+    return m;
 }
 
 }  // namespace tgx

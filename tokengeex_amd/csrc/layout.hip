@@ -1,5 +1,6 @@
 // A result's ids laid out for a model: [S, L] padded rows with an attention mask, or the documents concatenated and
-// cut into [B, L] blocks (include/tgx.h: tgx_result_pad_device, tgx_result_pack_device).  Pure data movement: every
+// cut into [B, L] blocks, or long rows as overlapping [W, L] windows (include/tgx.h: tgx_result_pad_device,
+// tgx_result_pack_device, tgx_result_window_pad_device).  Pure data movement: every
 // thread slot owns four consecutive output elements, finds the rows they belong to (layout.h), reads each kept id
 // once and writes the four with one 16-byte store (two for i64), the mask with one 4-byte store.  Destinations that
 // are not 16-byte aligned take the same kernels with element-wide stores.
@@ -137,6 +138,61 @@ __global__ __launch_bounds__(kLayoutBlock) void layout_pack_kernel(LayoutParams 
     }
 }
 
+// counts[i] = the windows of row i; the longest row is reduced as in layout_max_row_kernel.  (A count that does not fit
+// 32 bits belongs to a row of more than 2^31 tokens, which the caller refuses on the maximum.)
+__global__ __launch_bounds__(kLayoutBlock) void layout_window_count_kernel(const uint64_t* __restrict__ offs, uint64_t n_rows, uint32_t room,
+                                                                            uint32_t step, uint32_t* __restrict__ counts,
+                                                                            unsigned long long* __restrict__ max_out) {
+    unsigned long long best = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * kLayoutBlock + threadIdx.x; i < n_rows; i += (uint64_t)gridDim.x * kLayoutBlock) {
+        const unsigned long long n = offs[i + 1] - offs[i];
+        const uint64_t nw = window_count(n, room, step);
+        counts[i] = nw < 0xFFFFFFFFull ? (uint32_t)nw : 0xFFFFFFFFu;
+        best = n > best ? n : best;
+    }
+    best = block_reduce<true>(best);
+    if (threadIdx.x == 0 && best) atomicMax(max_out, best);
+}
+
+// total = W·L elements in tiles of 1024 consecutive elements, as layout_pack_kernel: two threads search all S rows for
+// the owners of the tile's first and last window, the others step a row cursor between those two over their four
+// elements (win_group).
+template <class T, bool VEC>
+__global__ __launch_bounds__(kLayoutBlock) void layout_window_kernel(WindowParams q, uint64_t total) {
+    __shared__ uint64_t s_row[2];
+    const LayoutParams& p = q.base;
+    const LayoutSeq seq = layout_seq(p.bos, p.eos, p.pad);
+    const uint32_t L = p.len;
+    T* __restrict__ out = static_cast<T*>(p.out);
+    const uint64_t n_tiles = (total + kLayoutTile - 1) / kLayoutTile;
+    for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const uint64_t t0 = tile * kLayoutTile;
+        if (threadIdx.x < 2) {
+            uint64_t e = t0;
+            if (threadIdx.x == 1) e = t0 + kLayoutTile - 1 < total ? t0 + kLayoutTile - 1 : total - 1;
+            s_row[threadIdx.x] = pack_find_row(q.wo, 0, 0, p.n_rows - 1, e / L);
+        }
+        __syncthreads();
+        const uint64_t e0 = t0 + (uint64_t)threadIdx.x * kLayoutPerThread;
+        if (e0 < total) {
+            const uint32_t n_in = total - e0 < kLayoutPerThread ? (uint32_t)(total - e0) : kLayoutPerThread;
+            uint32_t v[kLayoutPerThread] = {0, 0, 0, 0};
+            const uint32_t m = win_group(seq, p.ids, p.offs, q.wo, L, q.stride, p.flags, s_row[0], s_row[1], e0, n_in, p.lengths, q.window_row,
+                                         q.window_first, v);
+            if (VEC && n_in == kLayoutPerThread) {
+                store4(out, e0, v);
+                if (p.mask) *reinterpret_cast<uint32_t*>(p.mask + e0) = m;
+            } else {
+                for (uint32_t k = 0; k < n_in; k++) {
+                    out[e0 + k] = (T)v[k];
+                    if (p.mask) p.mask[e0 + k] = (uint8_t)(m >> (8 * k));
+                }
+            }
+        }
+        __syncthreads();  // s_row is rewritten for the next tile
+    }
+}
+
 bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 uint32_t capped_grid(uint64_t blocks) { return (uint32_t)(blocks < kLayoutMaxBlocks ? (blocks ? blocks : 1) : kLayoutMaxBlocks); }
@@ -174,6 +230,28 @@ hipError_t launch_layout_pack(const LayoutParams& p, uint64_t n_stream, uint64_t
         vec ? launch(layout_pack_kernel<int64_t, true>) : launch(layout_pack_kernel<int64_t, false>);
     else
         vec ? launch(layout_pack_kernel<int32_t, true>) : launch(layout_pack_kernel<int32_t, false>);
+    return hipGetLastError();
+}
+
+hipError_t launch_layout_window_count(const uint64_t* offs, uint64_t n_rows, uint32_t room, uint32_t step, uint32_t* counts,
+                                      unsigned long long* max_out, hipStream_t stream) {
+    if (n_rows == 0) return hipSuccess;
+    const uint32_t grid = capped_grid((n_rows + kLayoutBlock - 1) / kLayoutBlock);
+    hipLaunchKernelGGL(layout_window_count_kernel, dim3(grid), dim3(kLayoutBlock), 0, stream, offs, n_rows, room, step, counts, max_out);
+    return hipGetLastError();
+}
+
+hipError_t launch_layout_windows(const WindowParams& q, uint64_t n_windows, hipStream_t stream) {
+    const uint64_t total = n_windows * (uint64_t)q.base.len;
+    if (total == 0 || q.base.n_rows == 0) return hipSuccess;
+    const bool i64 = (q.base.flags & kLayoutI64) != 0;
+    const bool vec = aligned(q.base.out, 16) && aligned(q.base.mask, 4);
+    const uint32_t grid = capped_grid((total + kLayoutTile - 1) / kLayoutTile);
+    auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(kLayoutBlock), 0, stream, q, total); };
+    if (i64)
+        vec ? launch(layout_window_kernel<int64_t, true>) : launch(layout_window_kernel<int64_t, false>);
+    else
+        vec ? launch(layout_window_kernel<int32_t, true>) : launch(layout_window_kernel<int32_t, false>);
     return hipGetLastError();
 }
 

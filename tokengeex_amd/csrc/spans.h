@@ -1,8 +1,9 @@
-// Index arithmetic of the token spans (include/tgx.h: tgx_result_spans_device, tgx_result_pad_spans_device).  The
-// kernels of spans.hip and the host twin in host_twins.cpp (tgx_spans_host) both go through these functions, so a machine
-// without a GPU checks the kernels' arithmetic: the packed word of a token, an element's value in the chosen unit, the
-// span of an element from the scanned values, and the walks of the two writers (the padded one through pad_row of
-// layout.h, the flat one through the row cursor of the packed layout with A = 0).
+// Index arithmetic of the token spans (include/tgx.h: tgx_result_spans_device, tgx_result_pad_spans_device,
+// tgx_result_window_spans_device).  The kernels of spans.hip and the host twins in host_twins.cpp (tgx_spans_host,
+// tgx_window_spans_host) both go through these functions, so a machine without a GPU checks the kernels' arithmetic: the
+// packed word of a token, an element's value in the chosen unit, the span of an element from the scanned values, and
+// the walks of the writers (the padded one through pad_row of layout.h, the windowed one through win_row, the flat
+// one through the row cursor of the packed layout with A = 0).
 //
 // Element j of T has the value u_j in the chosen unit: len(x[j]) bytes, or leads(x[j]) characters.  P = the exclusive
 // 64-bit prefix sums of u over the whole stream (P[T] = the total), so inside row i, which starts at element o[i],
@@ -98,6 +99,21 @@ __host__ __device__ inline SpanPair span_pad_at(const LayoutSeq& seq, const uint
     const uint32_t k = c - r.col0 - seq.has_bos;  // wraps to a large value left of the kept tokens
     SpanPair s = {0, 0};
     if (k < r.keep) s = span_of(P, offs[i], r.src + k, vals ? vals[r.src + k] : 0u);
+    return s;
+}
+
+// ---- windows: pair e = w·L + c of [W, L, 2], through the window mapping of layout.h -----------------------------------
+// The row that owns window w is the largest i with Wo[i] <= w (pack_find_row over Wo with A = 0).  A kept token gets
+// the span it has in its whole row, so the pairs index the sample's text whichever window they stand in.
+__host__ __device__ inline SpanPair span_window_at(const LayoutSeq& seq, const uint64_t* offs, const uint64_t* Wo, uint64_t n_rows, const uint64_t* P,
+                                                   const uint32_t* vals, uint32_t L, uint32_t stride, uint32_t flags, uint64_t e) {
+    const uint64_t w = e / L;
+    const uint32_t c = (uint32_t)(e - w * L);
+    const uint64_t i = pack_find_row(Wo, 0, 0, n_rows - 1, w);
+    const WinRow r = win_row(offs, Wo, i, w, L, seq, stride, flags);
+    const uint32_t k = c - r.p.col0 - seq.has_bos;  // wraps to a large value left of the kept tokens
+    SpanPair s = {0, 0};
+    if (k < r.p.keep) s = span_of(P, offs[i], r.p.src + k, vals ? vals[r.p.src + k] : 0u);
     return s;
 }
 

@@ -3,7 +3,8 @@
 // and keeps its value in the chosen unit: the token's bytes, or its bytes that start a character.  One device-wide
 // 64-bit exclusive scan (rocPRIM, as decode.hip's) turns the values into P; a span is two differences against the row's
 // base P[o[i]].  The padded writer takes one [start, end] pair per thread through the row mapping of the padded layout
-// and writes it with one 8- or 16-byte store; the flat writer walks tiles of 1024 consecutive elements, two threads
+// and writes it with one 8- or 16-byte store (the windowed writer the same through the window mapping, after a search
+// of the windows' prefix sums for the pair's row); the flat writer walks tiles of 1024 consecutive elements, two threads
 // finding the rows of the tile's ends and every thread then stepping a row cursor over its four elements, which go out
 // as two 16-byte stores (four for i64).  Pure data movement: per element 4 B of ids and 2 B of table in, 4 B of values
 // out and in again, 8 B of sums out and in, 8 or 16 B of spans out.
@@ -85,6 +86,16 @@ __global__ __launch_bounds__(kSpanBlock) void span_pad_kernel(SpanParams p, uint
     T* __restrict__ out = static_cast<T*>(p.out);
     for (uint64_t e = (uint64_t)blockIdx.x * kSpanBlock + threadIdx.x; e < total; e += (uint64_t)gridDim.x * kSpanBlock)
         store_pair<VEC>(out, e, span_pad_at(seq, p.offs, p.sums, vals, p.len, p.flags, e));
+}
+
+// total = W·L pairs, one per thread slot; each slot searches Wo for its window's row
+template <class T, bool VEC>
+__global__ __launch_bounds__(kSpanBlock) void span_window_kernel(SpanParams p, const uint64_t* __restrict__ wo, uint32_t stride, uint64_t total) {
+    const LayoutSeq seq = layout_seq(p.bos, p.eos, 0);
+    const uint32_t* vals = (p.flags & kSpanChars) ? p.vals : nullptr;
+    T* __restrict__ out = static_cast<T*>(p.out);
+    for (uint64_t e = (uint64_t)blockIdx.x * kSpanBlock + threadIdx.x; e < total; e += (uint64_t)gridDim.x * kSpanBlock)
+        store_pair<VEC>(out, e, span_window_at(seq, p.offs, wo, p.n_rows, p.sums, vals, p.len, stride, p.flags, e));
 }
 
 // T pairs in tiles of 1024 consecutive elements.  Two threads search all S rows for the owners of the tile's first and
@@ -172,6 +183,20 @@ hipError_t launch_span_pad(const SpanParams& p, hipStream_t stream) {
         vec ? launch(span_pad_kernel<int64_t, true>) : launch(span_pad_kernel<int64_t, false>);
     else
         vec ? launch(span_pad_kernel<int32_t, true>) : launch(span_pad_kernel<int32_t, false>);
+    return hipGetLastError();
+}
+
+hipError_t launch_span_windows(const SpanParams& p, const uint64_t* wo, uint32_t stride, uint64_t n_windows, hipStream_t stream) {
+    const uint64_t total = n_windows * (uint64_t)p.len;
+    if (total == 0 || p.n == 0 || p.n_rows == 0) return hipSuccess;
+    const bool i64 = (p.flags & kLayoutI64) != 0;
+    const bool vec = aligned(p.out, i64 ? 16 : 8);
+    const uint32_t grid = grid_for(total);
+    auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(kSpanBlock), 0, stream, p, wo, stride, total); };
+    if (i64)
+        vec ? launch(span_window_kernel<int64_t, true>) : launch(span_window_kernel<int64_t, false>);
+    else
+        vec ? launch(span_window_kernel<int32_t, true>) : launch(span_window_kernel<int32_t, false>);
     return hipGetLastError();
 }
 

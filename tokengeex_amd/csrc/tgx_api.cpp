@@ -2275,6 +2275,110 @@ tgx_status tgx_result_pack_device(const tgx_result* r, uint32_t block_len, uint3
     return TGX_OK;
 }
 
+// ---- overflow windows: long rows as overlapping [W, L] windows (layout.hip; layout.h has the window mapping) ---------
+
+namespace {
+
+// Wo = the rows' first windows, in pooled scratch of the guard (u64[S+1]), and *n_windows = W = Wo[S], for a result with
+// S >= 1 rows: the count kernel, the scan, and one read-back of W and the longest row, which are checked against 2^31.
+// The stream has reached its end when this returns TGX_OK.
+tgx_status window_offsets_device(const char* who, const tgx_result* r, uint32_t room, uint32_t step, hipStream_t hs, StreamGuard& guard,
+                                 const uint64_t** d_wo, uint64_t* n_windows) {
+    const uint64_t S = r->n_samples;
+    size_t scan_bytes = 0;
+    if (tgx::scan_temp_bytes(S, &scan_bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan temp-size query failed");
+    uint32_t* counts = nullptr;
+    uint64_t* wo = nullptr;  // Wo[0 .. S], then the longest row
+    void* scan = nullptr;
+    HIP_TRY(guard.alloc((size_t)(S + 1) * 4, &counts));
+    HIP_TRY(guard.alloc((size_t)(S + 2) * 8, &wo));
+    if (scan_bytes) HIP_TRY(guard.alloc(scan_bytes, &scan));
+    HIP_TRY(hipMemsetAsync(wo + S + 1, 0, 8, hs));
+    HIP_TRY(tgx::launch_layout_window_count(r->d_offs, S, room, step, counts, reinterpret_cast<unsigned long long*>(wo + S + 1), hs));
+    HIP_TRY(tgx::launch_scan(counts, wo, S, scan, scan_bytes, hs));
+    uint64_t h[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(h, wo + S, 16, hipMemcpyDeviceToHost, hs));
+    HIP_TRY(hipStreamSynchronize(hs));
+    const tgx_status st = window_check_totals(who, h[1], h[0], nullptr);
+    if (st != TGX_OK) return st;
+    *d_wo = wo;
+    *n_windows = h[0];
+    return TGX_OK;
+}
+
+}  // namespace
+
+tgx_status tgx_result_window_info(const tgx_result* r, uint32_t row_len, uint32_t stride, uint32_t bos_id, uint32_t eos_id, uint32_t flags,
+                                  uint64_t* n_windows) {
+    const char* who = "tgx_result_window_info";
+    if (!r || !n_windows) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
+    tgx_status st = layout_check_flags(who, flags, TGX_LAYOUT_PAD_LEFT | TGX_LAYOUT_TRUNC_LEFT | TGX_LAYOUT_I64 | TGX_SPAN_CHARS);
+    if (st == TGX_OK) st = layout_check_ids(who, 0, bos_id, eos_id);
+    if (st != TGX_OK) return st;
+    const tgx::LayoutSeq seq = tgx::layout_seq(bos_id, eos_id, 0);
+    if ((st = window_check_args(who, row_len, stride, seq.extra)) != TGX_OK) return st;
+    *n_windows = 0;
+    if (r->n_samples == 0) return TGX_OK;
+    DeviceScope scope;
+    HIP_TRY(hipSetDevice(r->device));
+    hipStream_t hs = stream_or_default(nullptr, r->device);
+    StreamGuard guard(r->device, hs);
+    const uint64_t* d_wo = nullptr;
+    st = window_offsets_device(who, r, row_len - seq.extra, row_len - seq.extra - stride, hs, guard, &d_wo, n_windows);
+    if (st == TGX_OK) guard.done();
+    return st;
+}
+
+tgx_status tgx_result_window_pad_device(const tgx_result* r, uint32_t row_len, uint32_t stride, uint32_t pad_id, uint32_t bos_id, uint32_t eos_id,
+                                        uint32_t flags, void* stream, uint64_t n_windows, void* d_ids, uint8_t* d_mask, int32_t* d_lengths,
+                                        int32_t* d_window_row, int32_t* d_window_first) {
+    const char* who = "tgx_result_window_pad_device";
+    if (!r) return fail(TGX_ERR_INVALID, "%s: result is NULL", who);
+    if (!d_ids && r->n_samples) return fail(TGX_ERR_INVALID, "%s: d_ids is NULL", who);
+    tgx_status st = layout_check_flags(who, flags, TGX_LAYOUT_PAD_LEFT | TGX_LAYOUT_TRUNC_LEFT | TGX_LAYOUT_I64);
+    if (st == TGX_OK) st = layout_check_ids(who, pad_id, bos_id, eos_id);
+    if (st != TGX_OK) return st;
+    if (r->vocab_size > 0x80000000u) return fail(TGX_ERR_INVALID, "%s: the model's ids are not all below 2^31", who);
+    const tgx::LayoutSeq seq = tgx::layout_seq(bos_id, eos_id, pad_id);
+    if ((st = window_check_args(who, row_len, stride, seq.extra)) != TGX_OK) return st;
+    if (r->n_samples == 0) return window_check_totals(who, 0, 0, &n_windows);
+    DeviceScope scope;
+    HIP_TRY(hipSetDevice(r->device));
+    if ((st = check_device_ptr(who, "d_ids", d_ids, r->device, "result")) != TGX_OK) return st;
+    if ((st = check_device_ptr(who, "d_mask", d_mask, r->device, "result")) != TGX_OK) return st;
+    if ((st = check_device_ptr(who, "d_lengths", d_lengths, r->device, "result")) != TGX_OK) return st;
+    if ((st = check_device_ptr(who, "d_window_row", d_window_row, r->device, "result")) != TGX_OK) return st;
+    if ((st = check_device_ptr(who, "d_window_first", d_window_first, r->device, "result")) != TGX_OK) return st;
+    hipStream_t hs = stream_or_default(stream, r->device);
+    StreamGuard guard(r->device, hs);
+    const uint64_t* d_wo = nullptr;
+    uint64_t W = 0;
+    st = window_offsets_device(who, r, row_len - seq.extra, row_len - seq.extra - stride, hs, guard, &d_wo, &W);
+    if (st == TGX_OK) st = window_check_totals(who, 0, W, &n_windows);
+    if (st != TGX_OK) return st;
+    tgx::WindowParams q = {};
+    q.base.ids = r->d_ids;
+    q.base.offs = r->d_offs;
+    q.base.n_rows = r->n_samples;
+    q.base.len = row_len;
+    q.base.pad = pad_id;
+    q.base.bos = bos_id;
+    q.base.eos = eos_id;
+    q.base.flags = flags;
+    q.base.out = d_ids;
+    q.base.mask = d_mask;
+    q.base.lengths = d_lengths;
+    q.wo = d_wo;
+    q.stride = stride;
+    q.window_row = d_window_row;
+    q.window_first = d_window_first;
+    HIP_TRY(tgx::launch_layout_windows(q, W, hs));
+    // the stream has reached its end before the result or the destination can change hands (the guard: also after a failure)
+    HIP_TRY(hipStreamSynchronize(hs));
+    guard.done();
+    return TGX_OK;
+}
+
 // ---- assembly: a sample-level result with the special tokens' ids, from the segment-level result (assemble.hip) ----
 
 tgx_status tgx_assemble_result(tgx_model* m, const tgx_result* segs, const uint64_t* seg_offs, const int32_t* seg_special,
@@ -2632,11 +2736,57 @@ tgx_status ensure_span_words(tgx_model* m) {
     return TGX_OK;
 }
 
+// The first half of a spans call over a result with T >= 1 tokens: the model's words, the specials' words, the value
+// words and their prefix sums in pooled scratch of the guard, and for int32 spans the check of the rows' totals (one
+// word is read back; nothing has been written to the destination when a row does not fit).  Fills p's tables, source
+// and scratch; p->flags is set by the caller.
+tgx_status span_sums_device(const char* who, tgx_model* m, const tgx_result* r, const uint8_t* special_bytes, const uint64_t* special_offs,
+                            uint32_t n_specials, hipStream_t hs, StreamGuard& guard, tgx::SpanParams* p) {
+    const bool chars = (p->flags & TGX_SPAN_CHARS) != 0, i64 = (p->flags & TGX_LAYOUT_I64) != 0;
+    const uint64_t T = r->n_tokens;
+    const tgx_status st = ensure_span_words(m);
+    if (st != TGX_OK) return st;
+    std::vector<uint64_t> sp_words;
+    span_special_words(special_bytes, special_offs, n_specials, chars, &sp_words);
+    size_t scan_bytes = 0;
+    if (tgx::span_scan_temp_bytes(T, &scan_bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan temp-size query failed");
+    uint32_t* vals = nullptr;
+    uint64_t *sums = nullptr, *d_sp_words = nullptr;
+    void* scan = nullptr;
+    HIP_TRY(guard.alloc((size_t)(T + 1) * 4, &vals));
+    HIP_TRY(guard.alloc((size_t)(T + 1) * 8, &sums));
+    HIP_TRY(guard.alloc(scan_bytes, &scan));  // (never NULL: that asks the scan for its size)
+    HIP_TRY(guard.alloc(sp_words.size() * 8, &d_sp_words));
+    HIP_TRY(guard.upload(d_sp_words, std::move(sp_words)));
+    p->tab.words = m->d_span_words;
+    p->tab.sp_words = d_sp_words;
+    p->tab.vocab_size = m->vocab_size;
+    p->tab.n_specials = n_specials;
+    p->ids = r->d_ids;
+    p->offs = r->d_offs;
+    p->n_rows = r->n_samples;
+    p->n = T;
+    p->vals = vals;
+    p->sums = sums;
+    HIP_TRY(tgx::launch_span_sums(*p, scan, scan_bytes, hs));
+    if (!i64) {  // nothing is written when a row does not fit: the one word that is read back
+        unsigned long long h_max = 0, *row_max = nullptr;
+        HIP_TRY(guard.alloc(sizeof(unsigned long long), &row_max));
+        p->row_max = row_max;
+        HIP_TRY(hipMemsetAsync(row_max, 0, sizeof(unsigned long long), hs));
+        HIP_TRY(tgx::launch_span_row_max(*p, hs));
+        HIP_TRY(hipMemcpyAsync(&h_max, row_max, sizeof(unsigned long long), hipMemcpyDeviceToHost, hs));
+        HIP_TRY(hipStreamSynchronize(hs));
+        if (h_max >= 0x80000000ull) return span_too_long(who, h_max, chars);
+    }
+    return TGX_OK;
+}
+
 // row_len = 0: the flat form
 tgx_status spans_device(const char* who, tgx_model* m, const tgx_result* r, const uint8_t* special_bytes, const uint64_t* special_offs,
                         uint32_t n_specials, uint32_t row_len, uint32_t bos_id, uint32_t eos_id, uint32_t flags, void* stream, void* d_spans) {
     if (!m || !r) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
-    const bool padded = row_len != 0, chars = (flags & TGX_SPAN_CHARS) != 0;
+    const bool padded = row_len != 0;
     const tgx_status st0 = span_check_args(who, m->vocab_size, special_bytes, special_offs, n_specials, padded, row_len, bos_id, eos_id, flags);
     if (st0 != TGX_OK) return st0;
     const uint64_t S = r->n_samples, T = r->n_tokens;
@@ -2662,52 +2812,14 @@ tgx_status spans_device(const char* who, tgx_model* m, const tgx_result* r, cons
         guard.done();
         return TGX_OK;
     }
-    if ((st = ensure_span_words(m)) != TGX_OK) return st;
-
-    std::vector<uint64_t> sp_words;
-    span_special_words(special_bytes, special_offs, n_specials, chars, &sp_words);
-    size_t scan_bytes = 0;
-    if (tgx::span_scan_temp_bytes(T, &scan_bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan temp-size query failed");
     StreamGuard guard(dev, hs);
-    uint32_t* vals = nullptr;
-    uint64_t *sums = nullptr, *d_sp_words = nullptr;
-    void* scan = nullptr;
-    HIP_TRY(guard.alloc((size_t)(T + 1) * 4, &vals));
-    HIP_TRY(guard.alloc((size_t)(T + 1) * 8, &sums));
-    HIP_TRY(guard.alloc(scan_bytes, &scan));  // (never NULL: that asks the scan for its size)
-    HIP_TRY(guard.alloc(sp_words.size() * 8, &d_sp_words));
-    HIP_TRY(guard.upload(d_sp_words, std::move(sp_words)));
-
     tgx::SpanParams p = {};
-    p.tab.words = m->d_span_words;
-    p.tab.sp_words = d_sp_words;
-    p.tab.vocab_size = m->vocab_size;
-    p.tab.n_specials = n_specials;
-    p.ids = r->d_ids;
-    p.offs = r->d_offs;
-    p.n_rows = S;
-    p.n = T;
-    p.vals = vals;
-    p.sums = sums;
     p.len = row_len;
     p.bos = bos_id;
     p.eos = eos_id;
     p.flags = flags;
     p.out = d_spans;
-    HIP_TRY(tgx::launch_span_sums(p, scan, scan_bytes, hs));
-    if (!i64) {  // nothing is written when a row does not fit: the one word that is read back
-        unsigned long long h_max = 0, *row_max = nullptr;
-        HIP_TRY(guard.alloc(sizeof(unsigned long long), &row_max));
-        p.row_max = row_max;
-        HIP_TRY(hipMemsetAsync(row_max, 0, sizeof(unsigned long long), hs));
-        HIP_TRY(tgx::launch_span_row_max(p, hs));
-        HIP_TRY(hipMemcpyAsync(&h_max, row_max, sizeof(unsigned long long), hipMemcpyDeviceToHost, hs));
-        HIP_TRY(hipStreamSynchronize(hs));
-        if (h_max >= 0x80000000ull) {
-            guard.done();
-            return span_too_long(who, h_max, chars);
-        }
-    }
+    if ((st = span_sums_device(who, m, r, special_bytes, special_offs, n_specials, hs, guard, &p)) != TGX_OK) return st;
     HIP_TRY(padded ? tgx::launch_span_pad(p, hs) : tgx::launch_span_flat(p, hs));
     // the stream has reached its end before the result or the destination can change hands
     HIP_TRY(hipStreamSynchronize(hs));
@@ -2728,6 +2840,52 @@ tgx_status tgx_result_pad_spans_device(tgx_model* m, const tgx_result* r, const 
     const char* who = "tgx_result_pad_spans_device";
     if (row_len == 0) return fail(TGX_ERR_INVALID, "%s: row_len 0 (needs >= 1)", who);
     return spans_device(who, m, r, special_bytes, special_offs, n_specials, row_len, bos_id, eos_id, flags, stream, d_spans);
+}
+
+tgx_status tgx_result_window_spans_device(tgx_model* m, const tgx_result* r, const uint8_t* special_bytes, const uint64_t* special_offs,
+                                          uint32_t n_specials, uint32_t row_len, uint32_t stride, uint32_t bos_id, uint32_t eos_id, uint32_t flags,
+                                          void* stream, uint64_t n_windows, void* d_spans) {
+    const char* who = "tgx_result_window_spans_device";
+    if (!m || !r) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
+    if (row_len == 0) return fail(TGX_ERR_INVALID, "%s: row_len 0 (needs >= 1)", who);
+    tgx_status st = span_check_args(who, m->vocab_size, special_bytes, special_offs, n_specials, true, row_len, bos_id, eos_id, flags);
+    const tgx::LayoutSeq seq = tgx::layout_seq(bos_id, eos_id, 0);
+    if (st == TGX_OK) st = window_check_args(who, row_len, stride, seq.extra);
+    if (st != TGX_OK) return st;
+    const uint64_t S = r->n_samples, T = r->n_tokens;
+    if (!d_spans && S) return fail(TGX_ERR_INVALID, "%s: d_spans is NULL", who);
+    if ((st = require_device()) != TGX_OK) return st;
+    if (r->device != m->device) return fail(TGX_ERR_INVALID, "%s: the result is on device %d, the model on device %d", who, r->device, m->device);
+    if ((uint64_t)r->vocab_size > (uint64_t)m->vocab_size + n_specials)
+        return fail(TGX_ERR_INVALID, "%s: the result was written for %u ids, the model has %u tokens and %u special tokens", who, r->vocab_size,
+                    m->vocab_size, n_specials);
+    if (S == 0) return window_check_totals(who, 0, 0, &n_windows);
+    DeviceScope scope;
+    HIP_TRY(hipSetDevice(m->device));
+    if ((st = check_device_ptr(who, "d_spans", d_spans, m->device, "result")) != TGX_OK) return st;
+    hipStream_t hs = stream_or_default(stream, m->device);
+    StreamGuard guard(m->device, hs);
+    const uint64_t* d_wo = nullptr;
+    uint64_t W = 0;
+    st = window_offsets_device(who, r, row_len - seq.extra, row_len - seq.extra - stride, hs, guard, &d_wo, &W);
+    if (st == TGX_OK) st = window_check_totals(who, 0, W, &n_windows);
+    if (st != TGX_OK) return st;
+    if (T == 0) {  // rows without tokens: W = S windows of padding
+        HIP_TRY(hipMemsetAsync(d_spans, 0, (size_t)W * row_len * 2 * ((flags & TGX_LAYOUT_I64) ? 8 : 4), hs));
+    } else {
+        tgx::SpanParams p = {};
+        p.len = row_len;
+        p.bos = bos_id;
+        p.eos = eos_id;
+        p.flags = flags;
+        p.out = d_spans;
+        if ((st = span_sums_device(who, m, r, special_bytes, special_offs, n_specials, hs, guard, &p)) != TGX_OK) return st;
+        HIP_TRY(tgx::launch_span_windows(p, d_wo, stride, W, hs));
+    }
+    // the stream has reached its end before the result or the destination can change hands
+    HIP_TRY(hipStreamSynchronize(hs));
+    guard.done();
+    return TGX_OK;
 }
 
 // ---- frequency pass ------------------------------------------------------------

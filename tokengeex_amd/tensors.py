@@ -4,7 +4,9 @@ A NativeResult (of encode, sampling or n-best: n-best rows are just rows) holds 
 `to_padded` and `to_packed` lay them out for a model — [S, L] `input_ids` with `attention_mask`, or the documents
 concatenated and cut into [B, L] blocks — with the kernels of csrc/layout.hip, straight into tensors allocated with
 `torch.empty`: the ids never visit the host.  `to_spans` and `to_padded_spans` give the offsets mapping the same way:
-the part of its row's text that every token covers, in bytes or characters (csrc/spans.hip).
+the part of its row's text that every token covers, in bytes or characters (csrc/spans.hip).  `to_windows` and
+`to_window_spans` keep every token of a row longer than `max_length`: overlapping [W, L] windows, each tagged with the row
+it came from (HF's `return_overflowing_tokens` with a `stride`).
 
 The kernels are queued on `torch.cuda.current_stream(device)`, the stream torch's caching allocator orders the
 tensors' memory on, and the call returns once that stream has reached its end: the tensors can be used by any torch op
@@ -146,6 +148,69 @@ def to_packed(result: "_lib.NativeResult", block_len: int, *, pad_id: int, bos_i
     return out
 
 
+def _window_len(max_length, stride) -> tuple[int, int]:
+    if max_length is None:
+        raise TypeError("max_length is required for overflow windows")
+    L, s = int(max_length), int(stride)
+    if L < 1:
+        raise _lib.TokenGeeXError("max_length must be at least 1", _lib.ERR_INVALID)
+    if s < 0:
+        raise _lib.TokenGeeXError("stride must not be negative", _lib.ERR_INVALID)
+    return L, s
+
+
+def window_into(result: "_lib.NativeResult", input_ids, attention_mask=None, lengths=None, window_row=None, window_first=None, *,
+                row_len: int, stride: int = 0, pad_id: int, n_windows: int | None = None, bos_id: int | None = None,
+                eos_id: int | None = None, padding_side: str = "right", truncation_side: str = "right") -> int:
+    """The overflow windows written into tensors the caller owns (input_ids: int32 or int64, at least W·row_len elements;
+    attention_mask: uint8, the same count; lengths, window_row, window_first: int32, W), checked as in pad_into.
+    n_windows: the W the tensors are sized for (None: result.window_info is asked).  -> W."""
+    import torch
+    dev = _device_of(torch, result)
+    L, s = _window_len(row_len, stride)
+    if not isinstance(input_ids, torch.Tensor):
+        raise TypeError("input_ids must be a torch.Tensor")
+    flags = _lib.layout_flags(padding_side, truncation_side, _np_dtype(torch, input_ids.dtype))
+    W = result.window_info(L, s, bos_id=bos_id, eos_id=eos_id, flags=flags) if n_windows is None else int(n_windows)
+    p_ids = _check_dest(torch, "input_ids", input_ids, dev, input_ids.dtype, W * L)
+    p_mask = 0 if attention_mask is None else _check_dest(torch, "attention_mask", attention_mask, dev, torch.uint8, W * L)
+    p_len, p_row, p_first = (0 if t is None else _check_dest(torch, name, t, dev, torch.int32, W)
+                             for name, t in (("lengths", lengths), ("window_row", window_row), ("window_first", window_first)))
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    result.window_pad_device(L, s, pad_id, W, p_ids, mask_ptr=p_mask, lengths_ptr=p_len, window_row_ptr=p_row, window_first_ptr=p_first,
+                             bos_id=bos_id, eos_id=eos_id, flags=flags, stream=stream)
+    return W
+
+
+def to_windows(result: "_lib.NativeResult", *, max_length: int, stride: int = 0, pad_id: int, bos_id: int | None = None,
+               eos_id: int | None = None, padding_side: str = "right", truncation_side: str = "right", dtype=None,
+               return_lengths: bool = False) -> dict:
+    """Every token of every row, long rows as overlapping windows -> {"input_ids": [W, L] of dtype (torch.int64 by
+    default, or torch.int32), "attention_mask": [W, L] torch.uint8, "overflow_to_sample_mapping": [W] torch.int32, the
+    row a window came from, "window_first": [W] torch.int32, the index of its first token in that row [, "lengths": [W]
+    torch.int32]} on the result's device.
+
+    L = max_length.  A window is [bos] + up to L - A tokens + [eos]; the next one starts stride tokens before this one
+    ends (truncation_side "left": the windows run from the row's end), so stride < L - A.  A row that fits is one
+    window, as to_padded gives it; window 0 of any row is its to_padded row."""
+    import torch
+    dtype = torch.int64 if dtype is None else dtype
+    flags = _lib.layout_flags(padding_side, truncation_side, _np_dtype(torch, dtype))
+    dev = _device_of(torch, result)
+    L, s = _window_len(max_length, stride)
+    W = result.window_info(L, s, bos_id=bos_id, eos_id=eos_id, flags=flags)
+    out = {"input_ids": torch.empty((W, L), dtype=dtype, device=dev),
+           "attention_mask": torch.empty((W, L), dtype=torch.uint8, device=dev),
+           "overflow_to_sample_mapping": torch.empty((W,), dtype=torch.int32, device=dev),
+           "window_first": torch.empty((W,), dtype=torch.int32, device=dev)}
+    if return_lengths:
+        out["lengths"] = torch.empty((W,), dtype=torch.int32, device=dev)
+    window_into(result, out["input_ids"], out["attention_mask"], out.get("lengths"), out["overflow_to_sample_mapping"], out["window_first"],
+                row_len=L, stride=s, pad_id=pad_id, n_windows=W, bos_id=bos_id, eos_id=eos_id, padding_side=padding_side,
+                truncation_side=truncation_side)
+    return out
+
+
 def decode_padded(model: "_lib.NativeModel", input_ids, *, attention_mask=None, lengths=None, skip_id: int | None = None,
                   special_flat=(), special_offs=(0,), include_special: bool = True) -> "_lib.NativeText":
     """A [S, L] tensor of ids (int32 or int64, contiguous, on the model's device) decoded to UTF-8 text in HBM with the
@@ -262,4 +327,39 @@ def to_padded_spans(result: "_lib.NativeResult", model: "_lib.NativeModel", spec
     out = torch.empty((result.num_samples, L, 2), dtype=dtype, device=_device_of(torch, result))
     pad_spans_into(result, model, out, specials, row_len=L, unit=unit, bos_id=bos_id, eos_id=eos_id, padding_side=padding_side,
                    truncation_side=truncation_side)
+    return out
+
+
+def window_spans_into(result: "_lib.NativeResult", model: "_lib.NativeModel", spans, specials=None, *, row_len: int, stride: int = 0,
+                      n_windows: int | None = None, unit: str = "byte", bos_id: int | None = None, eos_id: int | None = None,
+                      padding_side: str = "right", truncation_side: str = "right") -> int:
+    """spans_into for the overflow windows: at least W·row_len·2 elements, aligned element for element with window_into's
+    input_ids for the same row_len, stride, bos_id, eos_id and sides.  A kept token gets its span in its whole row's text,
+    whichever window it stands in; bos, eos and padding get (0, 0).  -> W."""
+    import torch
+    L, s = _window_len(row_len, stride)
+    if not isinstance(spans, torch.Tensor):
+        raise TypeError("spans must be a torch.Tensor")
+    flags = _lib.span_flags(unit, _np_dtype(torch, spans.dtype), padding_side, truncation_side)
+    W = result.window_info(L, s, bos_id=bos_id, eos_id=eos_id, flags=flags) if n_windows is None else int(n_windows)
+    dev, p = _span_dest(torch, result, model, spans, W * L * 2)
+    sf, so = _special_arrays(specials)
+    result.window_spans_device(model, sf, so, L, s, W, p, bos_id=bos_id, eos_id=eos_id, flags=flags,
+                               stream=torch.cuda.current_stream(dev).cuda_stream)
+    return W
+
+
+def to_window_spans(result: "_lib.NativeResult", model: "_lib.NativeModel", specials=None, unit: str = "byte", dtype=None, *,
+                    max_length: int, stride: int = 0, bos_id: int | None = None, eos_id: int | None = None,
+                    padding_side: str = "right", truncation_side: str = "right"):
+    """-> [W, L, 2] of dtype: to_spans laid out as to_windows lays the ids out for the same max_length, stride, bos_id,
+    eos_id and sides.  The pairs index the sample's text, so a window's tokens name the substring they came from."""
+    import torch
+    dtype = torch.int64 if dtype is None else dtype
+    flags = _lib.span_flags(unit, _np_dtype(torch, dtype), padding_side, truncation_side)
+    L, s = _window_len(max_length, stride)
+    W = result.window_info(L, s, bos_id=bos_id, eos_id=eos_id, flags=flags)
+    out = torch.empty((W, L, 2), dtype=dtype, device=_device_of(torch, result))
+    window_spans_into(result, model, out, specials, row_len=L, stride=s, n_windows=W, unit=unit, bos_id=bos_id, eos_id=eos_id,
+                      padding_side=padding_side, truncation_side=truncation_side)
     return out

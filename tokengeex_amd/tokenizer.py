@@ -370,6 +370,41 @@ class Tokenizer:
             padding_side=layout.get("padding_side", "right"), truncation_side=layout.get("truncation_side", "right"))
         return out
 
+    @staticmethod
+    def _window_stride(layout: dict):
+        """Takes stride and return_overflowing_tokens out of a layout request -> None, or the stride of the overflow windows."""
+        overflow = layout.pop("return_overflowing_tokens", False)
+        stride = layout.pop("stride", None)
+        if not overflow:
+            if stride:
+                raise ValueError("stride needs return_overflowing_tokens=True")
+            return None
+        if layout.get("max_length") is None:
+            raise TypeError("return_overflowing_tokens needs max_length")
+        return int(stride or 0)
+
+    def _windows(self, res, layout: dict, unit, stride: int) -> dict:
+        """The overflow-window form of a padded layout of `res` (None: a batch without samples): tensors.to_windows, and
+        tensors.to_window_spans when a unit is asked for."""
+        import torch
+        from . import tensors
+        if res is None:
+            out = self._empty_layout(True, None, layout)
+            ids = out["input_ids"]
+            for key in ("overflow_to_sample_mapping", "window_first"):
+                out[key] = torch.empty((0,), dtype=torch.int32, device=ids.device)
+            if unit is not None:
+                out["offset_mapping"] = torch.empty((0, ids.shape[1], 2), dtype=ids.dtype, device=ids.device)
+            return out
+        out = tensors.to_windows(res, stride=stride, **layout)
+        if unit is not None:
+            _, _, sf, so = self._vocab_packed()
+            out["offset_mapping"] = tensors.to_window_spans(
+                res, self._model(), (sf, so), unit, out["input_ids"].dtype, max_length=layout["max_length"], stride=stride,
+                bos_id=layout.get("bos_id"), eos_id=layout.get("eos_id"), padding_side=layout.get("padding_side", "right"),
+                truncation_side=layout.get("truncation_side", "right"))
+        return out
+
     def _ordinary_result(self, flat: np.ndarray, offs: np.ndarray, dropout: float):
         """The ordinary path of encode_batch_flat up to the device result (processors run, text is not split at special
         tokens) -> NativeResult, or None for an empty batch."""
@@ -392,16 +427,26 @@ class Tokenizer:
         dtype of input_ids, the (start, end) of every kept token in its sample's processed text (tensors.to_padded_spans);
         bos, eos and padding get (0, 0).
 
+        return_overflowing_tokens=True with max_length (required then) and stride=s (default 0) keeps every token: a sample
+        longer than max_length becomes several rows that each repeat s tokens of the row before (tensors.to_windows),
+        the tensors are [W, L], "overflow_to_sample_mapping" and "window_first" ([W] int32) name each row's sample and the
+        index of its first token there, and "offset_mapping" is [W, L, 2], still relative to the whole sample's text.
+
         This is the ORDINARY path: the processors run as in encode_ordinary_batch and the text is not split at special
         tokens — a special token's string inside a text is encoded as ordinary text.  encode_batch_padded_flat is the
         special-aware form: the same layout over encode_batch's ids, put together on the device (encode_batch_result_flat)."""
         from . import tensors
         unit = self._mapping_unit(layout)
+        stride = self._window_stride(layout)
         layout = self._layout_ids(layout)
         res = self._ordinary_result(flat, offs, dropout)
         if res is None:
+            if stride is not None:
+                return self._windows(None, layout, unit, stride)
             return self._with_offset_mapping(None, self._empty_layout(True, None, layout), layout, unit)
         try:
+            if stride is not None:
+                return self._windows(res, layout, unit, stride)
             return self._with_offset_mapping(res, tensors.to_padded(res, **layout), layout, unit)
         finally:
             res.free()
@@ -523,11 +568,16 @@ class Tokenizer:
         get their own ids, and the ids are put together and laid out on the device (encode_batch_result_flat)."""
         from . import tensors
         unit = self._mapping_unit(layout)
+        stride = self._window_stride(layout)
         layout = self._layout_ids(layout)
         res = self.encode_batch_result_flat(flat, offs, dropout)
         if res is None:
+            if stride is not None:
+                return self._windows(None, layout, unit, stride)
             return self._with_offset_mapping(None, self._empty_layout(True, None, layout), layout, unit)
         try:
+            if stride is not None:
+                return self._windows(res, layout, unit, stride)
             return self._with_offset_mapping(res, tensors.to_padded(res, **layout), layout, unit)
         finally:
             res.free()
