@@ -382,6 +382,70 @@ tgx_status tgx_assemble_host(const uint32_t *ids, const uint64_t *id_offs, uint6
                              uint32_t vocab_size, uint32_t n_specials,
                              uint32_t *out_ids, uint64_t ids_cap, uint64_t *out_offs);
 
+/* ---- the front end on the device: a resident corpus split at special tokens, CRLF applied (csrc/front.hip) --------
+ * What tgx_split_specials and tgx_pack_segments compute on host threads, for a corpus that is already in HBM (an upload,
+ * or tgx_corpus_from_text of a decoded text), with the plan kept on the device for tgx_assemble_result_plan: a resident
+ * text is encoded as Tokenizer::encode_batch encodes it without its bytes or the plan visiting the host.
+ *
+ * tgx_corpus_split_specials(c, specials, n_specials, flags, &segs, &plan).  The special tokens are host arrays as in
+ * tgx_split_specials (special_offs u64[n_specials + 1], any base).  With S samples of N bytes in c:
+ *   The plan is exactly what tgx_split_specials returns for the samples of c: a sample is scanned from its start; at a
+ *   position the FIRST special token in list order that the text starts with and that ends inside the sample matches
+ *   (not the longest); the earliest position wins, and the scan goes on behind the match.  The non-empty text in front of
+ *   a match is a segment of its own, and so is a non-empty tail; an empty sample has no segments.  seg_offs u64[S+1]
+ *   (sample i owns segments [seg_offs[i], seg_offs[i+1]); K = seg_offs[S]) and seg_special i32[K] (the special's index, or
+ *   -1 for a segment that is encoded) stay in HBM (pooled buffers) until tgx_plan_free; E = segments with seg_special < 0.
+ *   A special token never matches across a sample's end.
+ *   *segs is a resident corpus of the E encoded segments, in order: exactly what tgx_pack_segments(..., crlf = flags &
+ *   TGX_FRONT_CRLF) packs.  With TGX_FRONT_CRLF a '\r' is dropped iff the next byte is '\n' AND lies in the same segment:
+ *   a '\r' that ends a segment is kept whatever follows it in the buffer, and a special token that contains "\r\n" is
+ *   matched on the raw text.  Row k of *segs is segment k of the packed batch the host route builds, so dropout and
+ *   sampling hash the same (seed, row, position) and agree bit for bit.  *segs is an ordinary corpus: every entry point
+ *   that takes one takes it.  It is built as tgx_corpus_from_text builds one: the E + 1 offsets visit the host for the
+ *   longest-first order, beside three counters (candidates, K, E); no text byte and no plan array does.
+ *   n_specials = 0 is allowed: every non-empty sample is one encoded segment.
+ * Errors, before anything is queued: TGX_ERR_INVALID for NULL arguments, unknown flags, special_offs that decrease and an
+ *   empty special token (tgx_split_specials' message); TGX_ERR_UNSUPPORTED for more than 4096 special tokens or more than
+ *   65 536 bytes of them (the kernels' tables; tgx_split_specials has no such limit).
+ * c is only read and the call holds the corpus's lock, as a pass does.  S = 0 or N = 0: TGX_OK, a plan without segments
+ *   and a corpus without samples.  Stream rule: that of tgx_corpus_from_text (the library's blocking stream; the call
+ *   returns after the stream has reached its end; the caller's current device is restored).
+ * Candidates can overlap (special "aa" on "aaaaa"): they are resolved by the sequential rule above, one thread per run of
+ *   overlapping candidates, so a text that is one long run (10^6 x 'a') is slow but correct.
+ *
+ * tgx_plan_copy copies the plan to host arrays (seg_offs u64[S+1], seg_special i32[K]; caps in elements).
+ * tgx_assemble_result_plan is tgx_assemble_result with the plan read in HBM: the same result; TGX_ERR_INVALID when E
+ *   differs from segs' row count (so an n-best result is refused), segs is NULL although E > 0, the plan, segs and the
+ *   model are not on one device, segs was written for another vocabulary size, V + n_specials > 0xFFFFFFFE, or n_specials
+ *   is not the count the plan was made with.
+ * tgx_corpus_copy_text / tgx_corpus_copy_offsets copy a resident corpus's bytes (N) and offsets (u64[S+1], from 0) to the
+ *   host (caps in elements).
+ * tgx_front_host is the host twin over host arrays (offs[0] = 0), no device: the same checks and limits, the kernels'
+ *   tiles and thread slots through the same index arithmetic (csrc/front.h).  seg_offs u64[S+1] is the caller's;
+ *   *seg_special (i32[K]), *out_text and *out_offs (u64[E+1]) are malloc'd (tgx_free).
+ * tgx_front_last_times: device milliseconds of the calling thread's last tgx_corpus_split_specials, per stage (mark,
+ *   resolve, segments, keep, pack: events on the call's stream around each stage's kernels and scans); returns the
+ *   number of entries written (at most cap).  For tools/front_bench.py. */
+typedef struct tgx_plan tgx_plan;
+#define TGX_FRONT_CRLF 1u
+tgx_status tgx_corpus_split_specials(tgx_corpus *c, const uint8_t *special_bytes, const uint64_t *special_offs,
+                                     uint32_t n_specials, uint32_t flags, tgx_corpus **segs, tgx_plan **plan);
+uint64_t tgx_plan_num_samples(const tgx_plan *p);
+uint64_t tgx_plan_num_segments(const tgx_plan *p);
+uint64_t tgx_plan_num_encoded(const tgx_plan *p);
+int tgx_plan_device(const tgx_plan *p);
+tgx_status tgx_plan_copy(const tgx_plan *p, uint64_t *seg_offs, uint64_t offs_cap, int32_t *seg_special, uint64_t special_cap);
+void tgx_plan_free(tgx_plan *p);
+tgx_status tgx_assemble_result_plan(tgx_model *m, const tgx_result *segs, const tgx_plan *plan, uint32_t n_specials,
+                                    tgx_result **out);
+int tgx_front_last_times(const char **names, float *ms, int cap);
+tgx_status tgx_corpus_copy_text(const tgx_corpus *c, uint8_t *dst, uint64_t cap);
+tgx_status tgx_corpus_copy_offsets(const tgx_corpus *c, uint64_t *dst, uint64_t cap);
+tgx_status tgx_front_host(const uint8_t *text, const uint64_t *offs, uint64_t n_samples, const uint8_t *special_bytes,
+                          const uint64_t *special_offs, uint32_t n_specials, uint32_t flags, uint64_t *seg_offs,
+                          int32_t **seg_special, uint64_t *n_segments, uint8_t **out_text, uint64_t **out_offs,
+                          uint64_t *n_encoded);
+
 /* ---- decode on the device: a result's ids or a padded id tensor to UTF-8 text (csrc/decode.hip) -------------------
  * What tgx_decode_batch computes, with ids, text and row offsets all in HBM.
  *

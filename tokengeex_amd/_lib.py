@@ -22,6 +22,7 @@ MAX_NBEST = 16  # TGX_MAX_NBEST
 ESTEP_SNIPPET_LEN = 81920
 NO_ID = 0xFFFFFFFF  # TGX_NO_ID: no bos / eos
 LAYOUT_PAD_LEFT, LAYOUT_TRUNC_LEFT, LAYOUT_I64 = 1, 2, 4  # TGX_LAYOUT_*
+FRONT_CRLF = 1  # TGX_FRONT_CRLF
 SPAN_CHARS = 8  # TGX_SPAN_CHARS
 
 # every exported symbol of include/tgx.h: name -> (restype, argtypes)
@@ -138,6 +139,18 @@ SYMBOLS = {
     "tgx_result_window_spans_device": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _u64, _vp]),
     "tgx_layout_windows_host": (_i, [_vp, _vp, _u64, _u32, _u32, _u32, _u32, _u32, _u32, _u64, _vp, _vp, _vp, _vp, _vp, _pu64]),
     "tgx_window_spans_host": (_i, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _u64, _u32, _u32, _u32, _u32, _u32, _u64, _vp, _pu64]),
+    "tgx_corpus_split_specials": (_i, [_vp, _vp, _vp, _u32, _u32, _pvp, _pvp]),
+    "tgx_plan_num_samples": (_u64, [_vp]),
+    "tgx_plan_num_segments": (_u64, [_vp]),
+    "tgx_plan_num_encoded": (_u64, [_vp]),
+    "tgx_plan_device": (_i, [_vp]),
+    "tgx_plan_copy": (_i, [_vp, _vp, _u64, _vp, _u64]),
+    "tgx_plan_free": (None, [_vp]),
+    "tgx_assemble_result_plan": (_i, [_vp, _vp, _vp, _u32, _pvp]),
+    "tgx_front_last_times": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_float), _i]),
+    "tgx_corpus_copy_text": (_i, [_vp, _vp, _u64]),
+    "tgx_corpus_copy_offsets": (_i, [_vp, _vp, _u64]),
+    "tgx_front_host": (_i, [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _vp, _pvp, _pu64, _pvp, _pvp, _pu64]),
 }
 
 
@@ -377,6 +390,29 @@ def assemble_host(seg_offs: np.ndarray, seg_special: np.ndarray, ids: np.ndarray
     check(lib.tgx_assemble_host(ptr(ids) if ids.size else None, ptr(id_offs), n_enc, ptr(seg_offs), ptr(seg_special) if seg_special.size else None,
                                 n, _u32_arg(vocab_size, "vocab_size"), _u32_arg(n_specials, "n_specials"), ptr(out), cap, ptr(out_offs)))
     return out[: int(out_offs[-1])], out_offs
+
+
+def front_host(flat: np.ndarray, offs: np.ndarray, specials: list[bytes], crlf: bool):
+    """Host twin of NativeCorpus.split_specials (tgx_front_host: the kernels' index arithmetic, no device) over a packed
+    batch (offs from 0) -> (seg_offs u64[S+1], seg_special i32[K], segments' flat, segments' offsets u64[E+1]): the plan of
+    split_specials_flat and what pack_segments packs."""
+    flat = np.ascontiguousarray(flat, dtype=np.uint8)
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    sflat, soffs = pack(specials)
+    n = offs.shape[0] - 1
+    seg_offs = np.zeros(n + 1, np.uint64)
+    ss, ot, oo, k, e = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
+    check(lib.tgx_front_host(ptr(flat) if flat.size else None, ptr(offs), n, ptr(sflat) if sflat.size else None, ptr(soffs), len(specials),
+                             FRONT_CRLF if crlf else 0, ptr(seg_offs), C.byref(ss), C.byref(k), C.byref(ot), C.byref(oo), C.byref(e)))
+    out_offs = _take(oo, e.value + 1, C.c_uint64, np.uint64)
+    return seg_offs, _take(ss, k.value, C.c_int32, np.int32), _take(ot, int(out_offs[-1]), C.c_uint8, np.uint8), out_offs
+
+
+def front_last_times() -> dict[str, float]:
+    """Device milliseconds per stage of this thread's last NativeCorpus.split_specials (tgx_front_last_times)."""
+    names, ms = (C.c_char_p * 8)(), (C.c_float * 8)()
+    n = lib.tgx_front_last_times(names, ms, 8)
+    return {names[k].decode(): float(ms[k]) for k in range(n)}
 
 
 def decode_batch_flat(vocab_flat, vocab_offs, vocab_size: int, special_flat, special_offs, n_specials: int,
@@ -849,6 +885,49 @@ class NativeText:
         return c
 
 
+class NativePlan:
+    """Owns a tgx_plan: the split plan of a resident corpus (seg_offs u64[S+1], seg_special i32[K]) in HBM (csrc/front.hip)."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    def __del__(self):
+        self.free()
+
+    def free(self):
+        if getattr(self, "_h", None):
+            lib.tgx_plan_free(self._h)
+            self._h = None
+
+    @property
+    def num_samples(self) -> int:
+        return lib.tgx_plan_num_samples(self._h)
+
+    @property
+    def num_segments(self) -> int:
+        return lib.tgx_plan_num_segments(self._h)
+
+    @property
+    def num_encoded(self) -> int:
+        return lib.tgx_plan_num_encoded(self._h)
+
+    @property
+    def device(self) -> int:
+        return lib.tgx_plan_device(self._h)
+
+    def _copy(self):
+        seg_offs = np.zeros(self.num_samples + 1, np.uint64)
+        seg_special = np.zeros(self.num_segments, np.int32)
+        check(lib.tgx_plan_copy(self._h, ptr(seg_offs), seg_offs.size, ptr(seg_special) if seg_special.size else None, seg_special.size))
+        return seg_offs, seg_special
+
+    def seg_offs(self) -> np.ndarray:
+        return self._copy()[0]
+
+    def seg_special(self) -> np.ndarray:
+        return self._copy()[1]
+
+
 class NativeCorpus:
     """Owns a tgx_corpus: a packed batch resident in HBM across passes."""
 
@@ -876,6 +955,33 @@ class NativeCorpus:
     @property
     def num_bytes(self) -> int:
         return lib.tgx_corpus_num_bytes(self._h)
+
+    def bytes(self) -> np.ndarray:
+        """The corpus's text copied to the host (tgx_corpus_copy_text)."""
+        n = self.num_bytes
+        out = np.empty(n, np.uint8)
+        if n:
+            check(lib.tgx_corpus_copy_text(self._h, ptr(out), n))
+        return out
+
+    def offsets(self) -> np.ndarray:
+        """The samples' offsets u64[S+1], from 0 (tgx_corpus_copy_offsets)."""
+        out = np.empty(self.num_samples + 1, np.uint64)
+        check(lib.tgx_corpus_copy_offsets(self._h, ptr(out), out.size))
+        return out
+
+    def split_specials(self, specials: list[bytes], crlf: bool) -> "tuple[NativeCorpus, NativePlan]":
+        """The corpus split at special tokens on the device (tgx_corpus_split_specials, csrc/front.hip) -> (a resident corpus
+        of the non-special segments, CRLF-normalised on the way if asked: what pack_segments packs; the plan of
+        split_specials_flat, in HBM).  This corpus is only read."""
+        sflat, soffs = pack(specials)
+        hc, hp = C.c_void_p(), C.c_void_p()
+        check(lib.tgx_corpus_split_specials(self._h, ptr(sflat) if sflat.size else None, ptr(soffs), len(specials), FRONT_CRLF if crlf else 0,
+                                            C.byref(hc), C.byref(hp)))
+        c = NativeCorpus.__new__(NativeCorpus)
+        c._h = hc
+        c.device = self.device
+        return c, NativePlan(hp)
 
 
 class NativeModel:
@@ -1009,6 +1115,12 @@ class NativeModel:
         h = C.c_void_p()
         check(lib.tgx_assemble_result(self._h, None if segs is None else segs._h, ptr(seg_offs), ptr(seg_special) if seg_special.size else None,
                                       seg_offs.shape[0] - 1, _u32_arg(n_specials, "n_specials"), C.byref(h)))
+        return NativeResult(h)
+
+    def assemble_plan(self, segs: "NativeResult | None", plan: NativePlan, n_specials: int) -> NativeResult:
+        """assemble with the plan of NativeCorpus.split_specials, read where it is in HBM (tgx_assemble_result_plan)."""
+        h = C.c_void_p()
+        check(lib.tgx_assemble_result_plan(self._h, None if segs is None else segs._h, plan._h, _u32_arg(n_specials, "n_specials"), C.byref(h)))
         return NativeResult(h)
 
     # -- decode on the device (include/tgx.h: tgx_decode_result / tgx_decode_padded; csrc/decode.hip) --

@@ -15,7 +15,8 @@
 tgx_status tgx_set_error(tgx_status st, const char* msg);
 
 namespace tgx {
-struct DecodeSlot;  // decode.h
+struct DecodeSlot;   // decode.h
+struct FrontTables;  // front.h
 }
 
 namespace tgx::host {
@@ -62,5 +63,14 @@ void span_special_words(const uint8_t* special_bytes, const uint64_t* special_of
 tgx_status span_check_args(const char* who, uint32_t vocab_size, const uint8_t* special_bytes, const uint64_t* special_offs, uint32_t n_specials,
                            bool padded, uint32_t row_len, uint32_t bos_id, uint32_t eos_id, uint32_t flags);
 tgx_status span_too_long(const char* who, uint64_t row_max, bool chars);
+// the special tokens as the front kernels read them (front.h: FrontTables)
+struct FrontHostTables {
+    std::vector<uint32_t> first_mask, first_start, by_first, sp_offs;
+    std::vector<uint8_t> sp_bytes, firsts;  // firsts: the distinct first bytes, ascending
+    uint32_t max_len = 0;                   // the longest special
+};
+tgx::FrontTables front_tables(const FrontHostTables& t, const uint32_t* first_mask, const uint32_t* first_start, const uint32_t* by_first,
+                              const uint32_t* sp_offs, const uint8_t* sp_bytes);
+tgx_status front_build_tables(const char* who, const uint8_t* special_bytes, const uint64_t* special_offs, uint32_t n_specials, FrontHostTables* t);
 
 }  // namespace tgx::host

@@ -1,7 +1,7 @@
 // The *_host twins of the result-side device entry points (include/tgx.h): tgx_layout_pad_host, tgx_layout_pack_host,
-// tgx_layout_windows_host, tgx_assemble_host, tgx_decode_rows_host, tgx_spans_host and tgx_window_spans_host, and the
+// tgx_layout_windows_host, tgx_assemble_host, tgx_decode_rows_host, tgx_spans_host, tgx_window_spans_host and tgx_front_host, and the
 // argument checks they share with the device entry points of tgx_api.cpp.  A twin goes through the same index arithmetic as its kernels (layout.h, assemble.h,
-// decode.h, spans.h) on host memory.  Nothing in this file calls a HIP function, so it builds and runs without the
+// decode.h, spans.h, front.h) on host memory.  Nothing in this file calls a HIP function, so it builds and runs without the
 // handles, the pool or a device.
 #include <algorithm>
 #include <cstdlib>
@@ -11,6 +11,7 @@
 #include "api_internal.h"
 #include "assemble.h"
 #include "decode.h"
+#include "front.h"
 #include "layout.h"
 #include "spans.h"
 
@@ -179,6 +180,50 @@ tgx_status span_check_args(const char* who, uint32_t vocab_size, const uint8_t* 
 tgx_status span_too_long(const char* who, uint64_t row_max, bool chars) {
     return fail(TGX_ERR_UNSUPPORTED, "%s: a row of %llu %s does not fit int32 spans (TGX_LAYOUT_I64 takes it)", who, (unsigned long long)row_max,
                 chars ? "characters" : "bytes");
+}
+
+// The special tokens as the front kernels read them (front.h: FrontTables), from 0: what tgx_corpus_split_specials uploads
+// and tgx_front_host reads.  An empty special is refused as tgx_split_specials refuses it.
+tgx_status front_build_tables(const char* who, const uint8_t* special_bytes, const uint64_t* special_offs, uint32_t n_specials, FrontHostTables* t) {
+    tgx_status st = check_packed_list(who, "special_offs", "special_offs", special_offs, n_specials, false);
+    if (st != TGX_OK) return st;
+    const uint64_t total = n_specials ? special_offs[n_specials] - special_offs[0] : 0;
+    if (total && !special_bytes) return fail(TGX_ERR_INVALID, "%s: special_bytes is NULL", who);
+    for (uint32_t k = 0; k < n_specials; k++)
+        if (special_offs[k + 1] == special_offs[k]) return fail(TGX_ERR_INVALID, "empty special token (the reference's splitter would never advance)");
+    if (n_specials > tgx::kFrontMaxSpecials || total > tgx::kFrontMaxSpecialBytes)
+        return fail(TGX_ERR_UNSUPPORTED, "%s: %u special tokens of %llu bytes (at most %u of %llu bytes)", who, n_specials, (unsigned long long)total,
+                    tgx::kFrontMaxSpecials, (unsigned long long)tgx::kFrontMaxSpecialBytes);
+    t->first_mask.assign(8, 0);
+    t->first_start.assign(257, 0);
+    t->by_first.assign(n_specials, 0);
+    t->sp_offs.assign((size_t)n_specials + 1, 0);
+    t->sp_bytes.assign(special_bytes ? special_bytes + (n_specials ? special_offs[0] : 0) : nullptr,
+                       special_bytes ? special_bytes + (n_specials ? special_offs[0] : 0) + total : nullptr);
+    t->max_len = 0;
+    for (uint32_t k = 0; k < n_specials; k++) {
+        t->sp_offs[k + 1] = (uint32_t)(special_offs[k + 1] - special_offs[0]);
+        const uint32_t b = t->sp_bytes[t->sp_offs[k]];
+        t->first_mask[b >> 5] |= 1u << (b & 31);
+        t->first_start[b + 1]++;
+        t->max_len = std::max(t->max_len, t->sp_offs[k + 1] - t->sp_offs[k]);
+    }
+    t->firsts.clear();
+    for (uint32_t b = 0; b < 256; b++) {
+        if (t->first_start[b + 1]) t->firsts.push_back((uint8_t)b);
+        t->first_start[b + 1] += t->first_start[b];
+    }
+    std::vector<uint32_t> at(t->first_start.begin(), t->first_start.end() - 1);
+    for (uint32_t k = 0; k < n_specials; k++) t->by_first[at[t->sp_bytes[t->sp_offs[k]]]++] = k;  // ascending k: list order
+    return TGX_OK;
+}
+
+// the tables over the given copies of the arrays (host memory for the twin, device memory for the kernels)
+tgx::FrontTables front_tables(const FrontHostTables& t, const uint32_t* first_mask, const uint32_t* first_start, const uint32_t* by_first,
+                              const uint32_t* sp_offs, const uint8_t* sp_bytes) {
+    tgx::FrontTables tab = {first_mask, first_start, by_first, sp_offs, sp_bytes, (uint32_t)t.firsts.size(), {0, 0, 0, 0}};
+    for (size_t k = 0; k < t.firsts.size() && k < tgx::kFrontFirstBytes; k++) tab.first_bytes[k] = t.firsts[k];
+    return tab;
 }
 
 }  // namespace tgx::host
@@ -378,6 +423,152 @@ tgx_status tgx_assemble_host(const uint32_t* ids, const uint64_t* id_offs, uint6
             for (uint32_t q = 0; q < n_in; q++) out_ids[e0 + q] = v[q];
         }
     }
+    return TGX_OK;
+}
+
+// ---- front end ----------------------------------------------------------------------
+
+tgx_status tgx_front_host(const uint8_t* text, const uint64_t* offs, uint64_t n_samples, const uint8_t* special_bytes, const uint64_t* special_offs,
+                          uint32_t n_specials, uint32_t flags, uint64_t* seg_offs, int32_t** seg_special, uint64_t* n_segments, uint8_t** out_text,
+                          uint64_t** out_offs, uint64_t* n_encoded) {
+    const char* who = "tgx_front_host";
+    if (!seg_offs || !seg_special || !n_segments || !out_text || !out_offs || !n_encoded) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
+    *seg_special = nullptr;
+    *out_text = nullptr;
+    *out_offs = nullptr;
+    *n_segments = *n_encoded = 0;
+    tgx_status st = layout_check_flags(who, flags, TGX_FRONT_CRLF);
+    if (st == TGX_OK) st = check_packed_list(who, "offs", "offsets", offs, n_samples, true);
+    if (st != TGX_OK) return st;
+    FrontHostTables ht;
+    if ((st = front_build_tables(who, special_bytes, special_offs, n_specials, &ht)) != TGX_OK) return st;
+    const uint64_t S = n_samples, N = offs[S];
+    if (N && !text) return fail(TGX_ERR_INVALID, "%s: text is NULL", who);
+    const tgx::FrontTables tab = front_tables(ht, ht.first_mask.data(), ht.first_start.data(), ht.by_first.data(), ht.sp_offs.data(), ht.sp_bytes.data());
+    const uint64_t tiles = (N + tgx::kFrontTile - 1) / tgx::kFrontTile, slots = (N + tgx::kFrontGroup - 1) / tgx::kFrontGroup;
+    // mark: as the kernel, tile by tile and slot by slot
+    std::vector<uint16_t> hit(slots), crlf(slots), keep(slots);
+    std::vector<uint64_t> tile_base(tiles + 1, 0), row_lo(tiles), row_hi(tiles);
+    for (uint64_t tile = 0; tile < tiles; tile++) {
+        const uint64_t t0 = tile * tgx::kFrontTile, last = tgx::front_tile_last(t0, N);
+        row_lo[tile] = tgx::front_find_sample(offs, 0, S - 1, t0);
+        row_hi[tile] = tgx::front_find_sample(offs, 0, S - 1, last);
+        uint64_t count = 0;
+        for (uint64_t p0 = t0; p0 <= last; p0 += tgx::kFrontGroup) {
+            const uint32_t n_in = N - p0 < tgx::kFrontGroup ? (uint32_t)(N - p0) : tgx::kFrontGroup;
+            uint8_t v[tgx::kFrontGroup] = {};
+            memcpy(v, text + p0, n_in);
+            uint32_t cr = 0;
+            const uint32_t h = tgx::front_mark_slot(tab, text, offs, row_lo[tile], row_hi[tile], p0, n_in, v,
+                                                    p0 + tgx::kFrontGroup < N ? text[p0 + tgx::kFrontGroup] : 0, &cr);
+            hit[p0 / tgx::kFrontGroup] = (uint16_t)h;
+            crlf[p0 / tgx::kFrontGroup] = (uint16_t)cr;
+            count += tgx::front_popc(h);
+        }
+        tile_base[tile + 1] = tile_base[tile] + count;
+    }
+    // candidates, resolve
+    const uint64_t C = tile_base[tiles];
+    std::vector<uint64_t> cand_pos(C), cand_end(C), pm(C), acc_end(C, 0), la(C), seg_sum(C + 1, 0);
+    std::vector<uint32_t> cand_special(C), cand_sample(C), cand_segs(C + 1, 0);
+    for (uint64_t tile = 0; tile < tiles; tile++) {
+        uint64_t at = tile_base[tile];
+        const uint64_t t0 = tile * tgx::kFrontTile, last = tgx::front_tile_last(t0, N);
+        for (uint64_t p0 = t0; p0 <= last; p0 += tgx::kFrontGroup) {
+            const uint32_t h = hit[p0 / tgx::kFrontGroup];
+            if (h) tgx::front_write_slot(tab, text, offs, row_lo[tile], row_hi[tile], p0, h, at, cand_pos.data(), cand_end.data(), cand_special.data(), cand_sample.data());
+            at += tgx::front_popc(h);
+        }
+    }
+    for (uint64_t c = 0; c < C; c++) pm[c] = std::max(cand_end[c], c ? pm[c - 1] : 0);
+    for (uint64_t c = 0; c < C; c++)
+        if (tgx::front_is_head(cand_pos.data(), pm.data(), c)) tgx::front_resolve_run(cand_pos.data(), cand_end.data(), pm.data(), C, c, acc_end.data());
+    for (uint64_t c = 0; c < C; c++) la[c] = std::max(acc_end[c], c ? la[c - 1] : 0);
+    for (uint64_t c = 0; c < C; c++) {
+        cand_segs[c] = tgx::front_cand_segs(cand_pos.data(), acc_end.data(), la.data(), cand_sample.data(), offs, c);
+        seg_sum[c + 1] = seg_sum[c] + cand_segs[c];
+    }
+    // segments
+    std::vector<uint64_t> first(S + 1);
+    for (uint64_t i = 0; i <= S; i++) first[i] = tgx::front_first_cand(cand_pos.data(), C, offs[i]);
+    seg_offs[0] = 0;
+    for (uint64_t i = 0; i < S; i++) {
+        uint64_t tail;
+        seg_offs[i + 1] = seg_offs[i] + tgx::front_sample_segs(offs, first.data(), seg_sum.data(), la.data(), i, &tail);
+    }
+    const uint64_t K = seg_offs[S];
+    std::vector<uint64_t> seg_begin(K), seg_end(K);
+    int32_t* ss = static_cast<int32_t*>(malloc(sizeof(int32_t) * std::max<uint64_t>(1, K)));
+    if (!ss) return fail(TGX_ERR_INVALID, "%s: out of host memory", who);
+    for (uint64_t c = 0; c < C; c++) {
+        if (!acc_end[c]) continue;
+        const uint64_t i = cand_sample[c];
+        uint64_t k = seg_offs[i] + (seg_sum[c] - seg_sum[first[i]]);
+        if (cand_segs[c] == 2) {
+            seg_begin[k] = tgx::front_cursor_before(la.data(), c, offs[i]);
+            seg_end[k] = cand_pos[c];
+            ss[k++] = -1;
+        }
+        seg_begin[k] = cand_pos[c];
+        seg_end[k] = cand_end[c];
+        ss[k] = (int32_t)cand_special[c];
+    }
+    for (uint64_t i = 0; i < S; i++) {
+        uint64_t tail;
+        tgx::front_sample_segs(offs, first.data(), seg_sum.data(), la.data(), i, &tail);
+        if (tail < offs[i + 1]) {
+            const uint64_t k = seg_offs[i + 1] - 1;
+            seg_begin[k] = tail;
+            seg_end[k] = offs[i + 1];
+            ss[k] = -1;
+        }
+    }
+    std::vector<uint64_t> enc_begin, enc_end;
+    for (uint64_t k = 0; k < K; k++)
+        if (ss[k] < 0) {
+            enc_begin.push_back(seg_begin[k]);
+            enc_end.push_back(seg_end[k]);
+        }
+    const uint64_t E = enc_begin.size();
+    // keep, pack
+    std::vector<uint32_t> enc_local(E);
+    for (uint64_t tile = 0; tile < tiles; tile++) {
+        const uint64_t t0 = tile * tgx::kFrontTile, last = tgx::front_tile_last(t0, N);
+        const uint64_t e_lo = tgx::front_first_enc(enc_end.data(), 0, E, t0), e_hi = tgx::front_first_enc(enc_end.data(), 0, E, last);
+        uint32_t count = 0;
+        for (uint64_t p0 = t0; p0 <= last; p0 += tgx::kFrontGroup) {
+            const uint32_t n_in = N - p0 < tgx::kFrontGroup ? (uint32_t)(N - p0) : tgx::kFrontGroup;
+            uint32_t begins = 0;
+            uint64_t first_begin = 0;
+            const uint32_t kp = tgx::front_keep_slot(enc_begin.data(), enc_end.data(), E, e_lo, e_hi, p0, n_in, crlf[p0 / tgx::kFrontGroup],
+                                                     (flags & TGX_FRONT_CRLF) != 0, &begins, &first_begin);
+            keep[p0 / tgx::kFrontGroup] = (uint16_t)kp;
+            if (begins) tgx::front_slot_begins(kp, begins, first_begin, count, enc_local.data());
+            count += tgx::front_popc(kp);
+        }
+        tile_base[tile + 1] = tile_base[tile] + count;
+    }
+    const uint64_t total = tiles ? tile_base[tiles] : 0;
+    uint64_t* oo = static_cast<uint64_t*>(malloc(sizeof(uint64_t) * (E + 1)));
+    uint8_t* ot = static_cast<uint8_t*>(malloc((size_t)std::max<uint64_t>(1, total)));
+    if (!oo || !ot) {
+        free(ss);
+        free(oo);
+        free(ot);
+        return fail(TGX_ERR_INVALID, "%s: out of host memory", who);
+    }
+    for (uint64_t e = 0; e < E; e++) oo[e] = tile_base[enc_begin[e] / tgx::kFrontTile] + enc_local[e];
+    oo[E] = total;
+    for (uint64_t s = 0, at = 0; s < slots; s++) {  // at: the tile's base and the kept bytes of its slots so far
+        const uint32_t kp = keep[s];
+        for (uint32_t q = 0; q < tgx::kFrontGroup; q++)
+            if ((kp >> q) & 1u) ot[at++] = text[s * tgx::kFrontGroup + q];
+    }
+    *seg_special = ss;
+    *n_segments = K;
+    *out_text = ot;
+    *out_offs = oo;
+    *n_encoded = E;
     return TGX_OK;
 }
 

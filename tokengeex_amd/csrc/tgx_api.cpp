@@ -26,6 +26,7 @@
 #include "api_internal.h"
 #include "assemble.h"
 #include "decode.h"
+#include "front.h"
 #include "kernels.h"
 #include "layout.h"
 #include "spans.h"
@@ -1642,9 +1643,11 @@ static hipError_t copy_sync(void* dst, const void* src, size_t bytes, hipMemcpyK
     return hipStreamSynchronize(st);
 }
 
-// A resident corpus over `text` (host memory, or memory of `device` when text_on_device) and host offsets: what
-// tgx_corpus_upload and tgx_corpus_from_text share, so the two build the same corpus.
-static tgx_status corpus_create(const char* who, int device, const uint8_t* text, bool text_on_device, const uint64_t* offs,
+// A resident corpus over `text` (host memory, memory of `device`, or bytes the caller writes to d_text itself once this
+// has returned: text is then not read) and host offsets: what tgx_corpus_upload, tgx_corpus_from_text and
+// tgx_corpus_split_specials share, so the three build the same corpus.
+enum class TextFrom { Host, Device, Caller };
+static tgx_status corpus_create(const char* who, int device, const uint8_t* text, TextFrom from, const uint64_t* offs,
                                 uint64_t n_samples, tgx_corpus** out) {
     if (!out) return fail(TGX_ERR_INVALID, "%s: out is NULL", who);
     *out = nullptr;
@@ -1667,7 +1670,7 @@ static tgx_status corpus_create(const char* who, int device, const uint8_t* text
     c->n_bytes = n_samples ? offs[n_samples] - base : 0;
     c->h_offs.resize(n_samples + 1);
     for (uint64_t i = 0; i <= n_samples; i++) c->h_offs[i] = n_samples ? offs[i] - base : 0;
-    if (n_samples && c->n_bytes && !text) return fail(TGX_ERR_INVALID, "%s: text is NULL", who);
+    if (n_samples && c->n_bytes && !text && from != TextFrom::Caller) return fail(TGX_ERR_INVALID, "%s: text is NULL", who);
     // longest first: the tail of a pass is then made of short samples
     std::vector<uint32_t> order(n_samples);
     std::iota(order.begin(), order.end(), 0u);
@@ -1690,7 +1693,8 @@ static tgx_status corpus_create(const char* who, int device, const uint8_t* text
     HIP_TRY(hipMemset(c->d_text_alloc, 0, 256));
     HIP_TRY(c->d_offs.alloc(device, (size_t)(n_samples + 1) * 8));
     HIP_TRY(c->d_order.alloc(device, (size_t)n_samples * 4 + 4));
-    if (c->n_bytes) HIP_TRY(copy_sync(c->d_text, text + base, c->n_bytes, text_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, device));
+    if (c->n_bytes && from != TextFrom::Caller)
+        HIP_TRY(copy_sync(c->d_text, text + base, c->n_bytes, from == TextFrom::Device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, device));
     HIP_TRY(hipMemset(c->d_text + c->n_bytes, 0, 256));
     HIP_TRY(hipMemcpy(c->d_offs, c->h_offs.data(), (n_samples + 1) * 8, hipMemcpyHostToDevice));
     if (n_samples) HIP_TRY(hipMemcpy(c->d_order, order.data(), n_samples * 4, hipMemcpyHostToDevice));
@@ -1700,7 +1704,7 @@ static tgx_status corpus_create(const char* who, int device, const uint8_t* text
 
 tgx_status tgx_corpus_upload(int device, const uint8_t* text, const uint64_t* offs,
                              uint64_t n_samples, tgx_corpus** out) {
-    return corpus_create("tgx_corpus_upload", device, text, false, offs, n_samples, out);
+    return corpus_create("tgx_corpus_upload", device, text, TextFrom::Host, offs, n_samples, out);
 }
 
 // (every pass has finished with the corpus's buffers when it returns: they go straight back to the pool)
@@ -2381,21 +2385,26 @@ tgx_status tgx_result_window_pad_device(const tgx_result* r, uint32_t row_len, u
 
 // ---- assembly: a sample-level result with the special tokens' ids, from the segment-level result (assemble.hip) ----
 
-tgx_status tgx_assemble_result(tgx_model* m, const tgx_result* segs, const uint64_t* seg_offs, const int32_t* seg_special,
-                               uint64_t n_samples, uint32_t n_specials, tgx_result** out) {
-    const char* who = "tgx_assemble_result";
-    const tgx_status dst = require_device();
-    if (dst != TGX_OK) return dst;
-    if (!m || !out) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
-    *out = nullptr;
-    uint64_t K = 0;
-    const tgx_status cst = assemble_check(who, seg_offs, seg_special, n_samples, m->vocab_size, n_specials, segs != nullptr, segs ? segs->n_samples : 0, &K);
-    if (cst != TGX_OK) return cst;
+struct tgx_plan {
+    int device = 0;
+    uint64_t n_samples = 0, n_segs = 0, n_enc = 0;  // S, K, E
+    uint32_t n_specials = 0;                        // of the list the corpus was split with
+    PoolBuf<uint64_t> d_seg_offs;                   // u64[S+1]
+    PoolBuf<int32_t> d_special;                     // i32[K+1]: entry K belongs to the assembly's scan
+};
+
+namespace {
+
+// What tgx_assemble_result and tgx_assemble_result_plan share: everything after the checks of the plan itself.  The plan
+// is K segments of S samples, E of them encoded, in host arrays that are uploaded (h_*) or in device memory (d_*: d_special
+// with room for K + 1 entries).
+tgx_status assemble_device(const char* who, tgx_model* m, const tgx_result* segs, const uint64_t* h_seg_offs, const int32_t* h_special,
+                           const uint64_t* d_plan_offs, int32_t* d_plan_special, uint64_t S, uint64_t K, uint32_t n_specials, tgx_result** out) {
     if (segs && segs->device != m->device)
         return fail(TGX_ERR_INVALID, "%s: the result is on device %d, the model on device %d", who, segs->device, m->device);
     if (segs && segs->vocab_size != m->vocab_size)
         return fail(TGX_ERR_INVALID, "%s: the result was written for %u tokens, the model has %u", who, segs->vocab_size, m->vocab_size);
-    const uint64_t S = n_samples, E = segs ? segs->n_samples : 0;
+    const uint64_t E = segs ? segs->n_samples : 0;
     const uint64_t n_out = (segs ? segs->n_tokens : 0) + (K - E);
 
     std::lock_guard<std::mutex> lk(m->mu);
@@ -2406,24 +2415,25 @@ tgx_status tgx_assemble_result(tgx_model* m, const tgx_result* segs, const uint6
     r->vocab_size = m->vocab_size + n_specials;
     r->n_tokens = n_out;
     uint64_t *d_seg_offs = nullptr, *d_rank = nullptr, *d_starts = nullptr, *d_zero = nullptr;
-    int32_t* d_special = nullptr;
+    int32_t* d_special = d_plan_special;
     void* d_scan = nullptr;
     size_t scan_bytes = 0;
     if (tgx::assemble_scan_temp_bytes(K, &scan_bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan temp-size query failed");
     if (r->d_offs.alloc(m->device, (size_t)(S + 1) * 8) != hipSuccess || r->d_ids.alloc(m->device, (size_t)n_out * 4 + 256) != hipSuccess ||
-        pass.alloc((size_t)(S + 1) * 8, &d_seg_offs) != hipSuccess || pass.alloc((size_t)(K + 1) * 4, &d_special) != hipSuccess ||
+        (!d_plan_offs && pass.alloc((size_t)(S + 1) * 8, &d_seg_offs) != hipSuccess) ||
+        (!d_plan_special && pass.alloc((size_t)(K + 1) * 4, &d_special) != hipSuccess) ||
         pass.alloc((size_t)(K + 1) * 8, &d_rank) != hipSuccess || pass.alloc((size_t)(K + 1) * 8, &d_starts) != hipSuccess ||
         (E == 0 && pass.alloc(8, &d_zero) != hipSuccess) || pass.alloc(scan_bytes, &d_scan) != hipSuccess)  // (never NULL: that asks the scan for its size)
         return fail(TGX_ERR_DEVICE, "out of device memory (assembly)");
-    if (hipMemcpyAsync(d_seg_offs, seg_offs, (size_t)(S + 1) * 8, hipMemcpyHostToDevice, m->stream) != hipSuccess ||
-        (K && hipMemcpyAsync(d_special, seg_special, (size_t)K * 4, hipMemcpyHostToDevice, m->stream) != hipSuccess) ||
+    if ((!d_plan_offs && hipMemcpyAsync(d_seg_offs, h_seg_offs, (size_t)(S + 1) * 8, hipMemcpyHostToDevice, m->stream) != hipSuccess) ||
+        (!d_plan_special && K && hipMemcpyAsync(d_special, h_special, (size_t)K * 4, hipMemcpyHostToDevice, m->stream) != hipSuccess) ||
         (d_zero && hipMemsetAsync(d_zero, 0, 8, m->stream) != hipSuccess))
         return fail(TGX_ERR_DEVICE, "upload of the split plan failed: %s", hipGetErrorString(hipGetLastError()));
 
     tgx::AssembleParams p = {};
     p.ids = E ? segs->d_ids.get() : nullptr;
     p.offs = E ? segs->d_offs.get() : d_zero;
-    p.seg_offs = d_seg_offs;
+    p.seg_offs = d_plan_offs ? d_plan_offs : d_seg_offs;
     p.seg_special = d_special;
     p.rank = d_rank;
     p.starts = d_starts;
@@ -2446,6 +2456,40 @@ tgx_status tgx_assemble_result(tgx_model* m, const tgx_result* segs, const uint6
     if (hipStreamSynchronize(m->stream) != hipSuccess) return fail(TGX_ERR_DEVICE, "assembly failed: %s", hipGetErrorString(hipGetLastError()));
     *out = pass.release_result();
     return pass.done();
+}
+
+}  // namespace
+
+tgx_status tgx_assemble_result(tgx_model* m, const tgx_result* segs, const uint64_t* seg_offs, const int32_t* seg_special,
+                               uint64_t n_samples, uint32_t n_specials, tgx_result** out) {
+    const char* who = "tgx_assemble_result";
+    const tgx_status dst = require_device();
+    if (dst != TGX_OK) return dst;
+    if (!m || !out) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
+    *out = nullptr;
+    uint64_t K = 0;
+    const tgx_status cst = assemble_check(who, seg_offs, seg_special, n_samples, m->vocab_size, n_specials, segs != nullptr, segs ? segs->n_samples : 0, &K);
+    if (cst != TGX_OK) return cst;
+    return assemble_device(who, m, segs, seg_offs, seg_special, nullptr, nullptr, n_samples, K, n_specials, out);
+}
+
+tgx_status tgx_assemble_result_plan(tgx_model* m, const tgx_result* segs, const tgx_plan* plan, uint32_t n_specials, tgx_result** out) {
+    const char* who = "tgx_assemble_result_plan";
+    const tgx_status dst = require_device();
+    if (dst != TGX_OK) return dst;
+    if (!m || !plan || !out) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
+    *out = nullptr;
+    // what assemble_check asks of host arrays, of a plan whose arrays the split wrote
+    if ((uint64_t)m->vocab_size + n_specials > 0xFFFFFFFEull)
+        return fail(TGX_ERR_INVALID, "%s: %u tokens and %u special tokens leave no room for their ids", who, m->vocab_size, n_specials);
+    if (n_specials != plan->n_specials)
+        return fail(TGX_ERR_INVALID, "%s: %u special tokens, the plan was made with %u", who, n_specials, plan->n_specials);
+    if (plan->n_enc && !segs) return fail(TGX_ERR_INVALID, "%s: %llu encoded segments and no result over them", who, (unsigned long long)plan->n_enc);
+    if (plan->n_enc != (segs ? segs->n_samples : 0))
+        return fail(TGX_ERR_INVALID, "%s: %llu encoded segments, the result over them has %llu rows", who, (unsigned long long)plan->n_enc,
+                    (unsigned long long)(segs ? segs->n_samples : 0));
+    if (plan->device != m->device) return fail(TGX_ERR_INVALID, "%s: the plan is on device %d, the model on device %d", who, plan->device, m->device);
+    return assemble_device(who, m, segs, nullptr, nullptr, plan->d_seg_offs, plan->d_special, plan->n_samples, plan->n_segs, n_specials, out);
 }
 
 // ---- decode: ids in HBM to UTF-8 text in HBM (decode.hip; decode.h has the index arithmetic) ----------------------
@@ -2715,7 +2759,249 @@ tgx_status tgx_corpus_from_text(const tgx_text* t, tgx_corpus** out) {
     const tgx_status st = tgx_text_copy_offsets(t, offs.data(), offs.size());
     if (st != TGX_OK) return st;
     DeviceScope scope;
-    return corpus_create(who, t->device, t->d_bytes, true, offs.data(), t->n_rows, out);
+    return corpus_create(who, t->device, t->d_bytes, TextFrom::Device, offs.data(), t->n_rows, out);
+}
+
+// ---- the front end on the device: a resident corpus split at special tokens, CRLF applied (front.hip; front.h) ----
+
+tgx_status tgx_corpus_copy_text(const tgx_corpus* c, uint8_t* dst, uint64_t cap) {
+    if (!c || (!dst && c->n_bytes)) return fail(TGX_ERR_INVALID, "tgx_corpus_copy_text: NULL argument");
+    if (cap < c->n_bytes) return fail(TGX_ERR_INVALID, "tgx_corpus_copy_text: %llu bytes, room for %llu", (unsigned long long)c->n_bytes, (unsigned long long)cap);
+    if (!c->n_bytes) return TGX_OK;
+    DeviceScope scope;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(copy_sync(dst, c->d_text, c->n_bytes, hipMemcpyDeviceToHost, c->device));
+    return TGX_OK;
+}
+
+tgx_status tgx_corpus_copy_offsets(const tgx_corpus* c, uint64_t* dst, uint64_t cap) {
+    if (!c || !dst) return fail(TGX_ERR_INVALID, "tgx_corpus_copy_offsets: NULL argument");
+    if (cap < c->n_samples + 1) return fail(TGX_ERR_INVALID, "tgx_corpus_copy_offsets: %llu offsets, room for %llu", (unsigned long long)(c->n_samples + 1), (unsigned long long)cap);
+    memcpy(dst, c->h_offs.data(), (size_t)(c->n_samples + 1) * 8);  // (the corpus keeps them on the host too)
+    return TGX_OK;
+}
+
+namespace {
+
+// device time of the last tgx_corpus_split_specials of this thread, per stage (tgx_front_last_times)
+constexpr int kFrontStages = 5;
+const char* const kFrontStageNames[kFrontStages] = {"front_mark", "front_resolve", "front_segments", "front_keep", "front_pack"};
+thread_local float g_front_ms[kFrontStages] = {0, 0, 0, 0, 0};
+
+class FrontTimer {
+public:
+    explicit FrontTimer(hipStream_t hs) : hs_(hs) {
+        for (auto& e : ev_) ok_ = ok_ && hipEventCreate(&e) == hipSuccess;
+    }
+    FrontTimer(const FrontTimer&) = delete;
+    FrontTimer& operator=(const FrontTimer&) = delete;
+    ~FrontTimer() {
+        for (auto& e : ev_)
+            if (e) (void)hipEventDestroy(e);
+    }
+    void begin(int stage) {
+        if (ok_) used_[stage] = hipEventRecord(ev_[2 * stage], hs_) == hipSuccess;
+    }
+    void end(int stage) {
+        if (ok_ && used_[stage]) used_[stage] = hipEventRecord(ev_[2 * stage + 1], hs_) == hipSuccess;
+    }
+    void read() {  // after the stream has reached its end
+        for (int k = 0; k < kFrontStages; k++) {
+            g_front_ms[k] = 0;
+            if (ok_ && used_[k]) (void)hipEventElapsedTime(&g_front_ms[k], ev_[2 * k], ev_[2 * k + 1]);
+        }
+    }
+
+private:
+    hipStream_t hs_;
+    hipEvent_t ev_[2 * kFrontStages] = {};
+    bool used_[kFrontStages] = {};
+    bool ok_ = true;
+};
+
+}  // namespace
+
+int tgx_front_last_times(const char** names, float* ms, int cap) {
+    int n = 0;
+    for (; n < kFrontStages && n < cap; n++) {
+        if (names) names[n] = kFrontStageNames[n];
+        if (ms) ms[n] = g_front_ms[n];
+    }
+    return n;
+}
+
+tgx_status tgx_corpus_split_specials(tgx_corpus* c, const uint8_t* special_bytes, const uint64_t* special_offs, uint32_t n_specials, uint32_t flags,
+                                     tgx_corpus** segs, tgx_plan** plan) {
+    const char* who = "tgx_corpus_split_specials";
+    if (!c || !segs || !plan) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
+    *segs = nullptr;
+    *plan = nullptr;
+    tgx_status st = layout_check_flags(who, flags, TGX_FRONT_CRLF);
+    FrontHostTables ht;
+    if (st == TGX_OK) st = front_build_tables(who, special_bytes, special_offs, n_specials, &ht);
+    if (st == TGX_OK) st = require_device();
+    if (st != TGX_OK) return st;
+    std::lock_guard<std::mutex> lkc(c->mu);
+    DeviceScope scope;
+    const int dev = c->device;
+    HIP_TRY(hipSetDevice(dev));
+    hipStream_t hs = stream_or_default(nullptr, dev);
+    const uint64_t S = c->n_samples, N = c->n_bytes;
+    std::unique_ptr<tgx_plan> pl(new tgx_plan());
+    std::unique_ptr<tgx_corpus> out;  // the segments' corpus
+    std::vector<uint64_t> h_out_offs(1, 0);
+    unsigned long long h_count = 0;
+    StreamGuard guard(dev, hs);  // destroyed before them: a failed call's queued work is over before they go
+    FrontTimer timer(hs);
+    pl->device = dev;
+    pl->n_samples = S;
+    pl->n_specials = n_specials;
+    HIP_TRY(pl->d_seg_offs.alloc(dev, (size_t)(S + 1) * 8));
+    if (S == 0 || N == 0) {  // no segments
+        HIP_TRY(pl->d_special.alloc(dev, 4));
+        HIP_TRY(hipMemsetAsync(pl->d_seg_offs, 0, (size_t)(S + 1) * 8, hs));
+        HIP_TRY(hipStreamSynchronize(hs));
+        tgx_corpus* empty = nullptr;
+        if ((st = corpus_create(who, dev, nullptr, TextFrom::Caller, nullptr, 0, &empty)) != TGX_OK) return st;
+        guard.done();
+        *segs = empty;
+        *plan = pl.release();
+        return TGX_OK;
+    }
+
+    tgx::FrontParams p = {};
+    p.text = c->d_text;
+    p.offs = c->d_offs;
+    p.n_bytes = N;
+    p.n_samples = S;
+    p.crlf = (flags & TGX_FRONT_CRLF) ? 1u : 0u;
+    const uint64_t tiles = (N + tgx::kFrontTile - 1) / tgx::kFrontTile, slots = (N + tgx::kFrontGroup - 1) / tgx::kFrontGroup;
+    // the special tokens' tables
+    uint32_t *d_mask = nullptr, *d_first = nullptr, *d_by_first = nullptr, *d_sp_offs = nullptr;
+    uint8_t* d_sp_bytes = nullptr;
+    HIP_TRY(guard.alloc(32, &d_mask));
+    HIP_TRY(guard.alloc(257 * 4, &d_first));
+    HIP_TRY(guard.alloc((size_t)n_specials * 4 + 4, &d_by_first));
+    HIP_TRY(guard.alloc((size_t)n_specials * 4 + 4, &d_sp_offs));
+    HIP_TRY(guard.alloc(ht.sp_bytes.size() + 16, &d_sp_bytes));
+    HIP_TRY(hipMemcpyAsync(d_mask, ht.first_mask.data(), 32, hipMemcpyHostToDevice, hs));
+    HIP_TRY(hipMemcpyAsync(d_first, ht.first_start.data(), 257 * 4, hipMemcpyHostToDevice, hs));
+    if (n_specials) HIP_TRY(hipMemcpyAsync(d_by_first, ht.by_first.data(), (size_t)n_specials * 4, hipMemcpyHostToDevice, hs));
+    HIP_TRY(hipMemcpyAsync(d_sp_offs, ht.sp_offs.data(), ((size_t)n_specials + 1) * 4, hipMemcpyHostToDevice, hs));
+    if (!ht.sp_bytes.empty()) HIP_TRY(hipMemcpyAsync(d_sp_bytes, ht.sp_bytes.data(), ht.sp_bytes.size(), hipMemcpyHostToDevice, hs));
+    p.tab = front_tables(ht, d_mask, d_first, d_by_first, d_sp_offs, d_sp_bytes);
+    // every scan's scratch, asked for again when a later count is larger than the ones known so far
+    void* d_scan = nullptr;
+    size_t scan_bytes = 0;
+    uint64_t scan_n = 0;
+    auto scan_room = [&](uint64_t n) -> tgx_status {
+        if (n <= scan_n) return TGX_OK;
+        if (tgx::front_scan_temp_bytes(n, &scan_bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan temp-size query failed");
+        HIP_TRY(guard.alloc(scan_bytes, &d_scan));  // (never NULL: that asks the scan for its size)
+        scan_n = n;
+        return TGX_OK;
+    };
+    auto count_at = [&](const uint64_t* d, uint64_t* v) -> tgx_status {  // one counter to the host
+        HIP_TRY(hipMemcpyAsync(&h_count, d, 8, hipMemcpyDeviceToHost, hs));
+        HIP_TRY(hipStreamSynchronize(hs));
+        *v = h_count;
+        return TGX_OK;
+    };
+
+    // mark
+    HIP_TRY(guard.alloc((size_t)slots * 2, &p.hit_mask));
+    HIP_TRY(guard.alloc((size_t)slots * 2, &p.crlf_mask));
+    HIP_TRY(guard.alloc((size_t)slots * 2, &p.keep_mask));
+    HIP_TRY(guard.alloc((size_t)(tiles + 1) * 8, &p.tile_count));
+    HIP_TRY(guard.alloc((size_t)(tiles + 1) * 8, &p.tile_base));
+    if ((st = scan_room(std::max(tiles, S) + 1)) != TGX_OK) return st;
+    timer.begin(0);
+    HIP_TRY(tgx::launch_front_mark(p, d_scan, scan_bytes, hs));
+    timer.end(0);
+    uint64_t C = 0, K = 0, E = 0;
+    if ((st = count_at(p.tile_base + tiles, &C)) != TGX_OK) return st;
+    // candidates, resolve, the samples' segment counts
+    p.n_cand = C;
+    HIP_TRY(guard.alloc((size_t)C * 8, &p.cand_pos));
+    HIP_TRY(guard.alloc((size_t)C * 8, &p.cand_end));
+    HIP_TRY(guard.alloc((size_t)C * 8, &p.pm));
+    HIP_TRY(guard.alloc((size_t)C * 8, &p.acc_end));
+    HIP_TRY(guard.alloc((size_t)C * 8, &p.la));
+    HIP_TRY(guard.alloc((size_t)(C + 1) * 8, &p.seg_sum));
+    HIP_TRY(guard.alloc((size_t)C * 4, &p.cand_special));
+    HIP_TRY(guard.alloc((size_t)C * 4, &p.cand_sample));
+    HIP_TRY(guard.alloc((size_t)(C + 1) * 4, &p.cand_segs));
+    HIP_TRY(guard.alloc((size_t)(S + 1) * 8, &p.first));
+    HIP_TRY(guard.alloc((size_t)(S + 1) * 8, &p.sample_segs));
+    p.seg_offs = pl->d_seg_offs;
+    if ((st = scan_room(C + 1)) != TGX_OK) return st;
+    timer.begin(1);
+    HIP_TRY(tgx::launch_front_candidates(p, d_scan, scan_bytes, hs));
+    timer.end(1);
+    if ((st = count_at(p.seg_offs + S, &K)) != TGX_OK) return st;
+    // segments
+    p.n_segs = K;
+    HIP_TRY(pl->d_special.alloc(dev, (size_t)(K + 1) * 4));
+    p.seg_special = pl->d_special;
+    HIP_TRY(guard.alloc((size_t)K * 8, &p.seg_begin));
+    HIP_TRY(guard.alloc((size_t)K * 8, &p.seg_end));
+    HIP_TRY(guard.alloc((size_t)(K + 1) * 8, &p.rank));
+    if ((st = scan_room(K + 1)) != TGX_OK) return st;
+    timer.begin(2);
+    HIP_TRY(tgx::launch_front_segments(p, d_scan, scan_bytes, hs));
+    timer.end(2);
+    if ((st = count_at(p.rank + K, &E)) != TGX_OK) return st;
+    pl->n_segs = K;
+    pl->n_enc = E;
+    // keep and pack: the E + 1 offsets visit the host for the corpus's longest-first order
+    p.n_enc = E;
+    tgx_corpus* made = nullptr;
+    if (E) {
+        HIP_TRY(guard.alloc((size_t)E * 8, &p.enc_begin));
+        HIP_TRY(guard.alloc((size_t)E * 8, &p.enc_end));
+        HIP_TRY(guard.alloc((size_t)E * 4, &p.enc_local));
+        HIP_TRY(guard.alloc((size_t)(E + 1) * 8, &p.out_offs));
+        timer.begin(3);
+        HIP_TRY(tgx::launch_front_keep(p, d_scan, scan_bytes, hs));
+        timer.end(3);
+        h_out_offs.resize(E + 1);
+        HIP_TRY(hipMemcpyAsync(h_out_offs.data(), p.out_offs, (size_t)(E + 1) * 8, hipMemcpyDeviceToHost, hs));
+        HIP_TRY(hipStreamSynchronize(hs));
+        if ((st = corpus_create(who, dev, nullptr, TextFrom::Caller, h_out_offs.data(), E, &made)) != TGX_OK) return st;
+        out.reset(made);
+        p.out = out->d_text;
+        timer.begin(4);
+        if (out->n_bytes) HIP_TRY(tgx::launch_front_pack(p, hs));
+        timer.end(4);
+    } else {
+        if ((st = corpus_create(who, dev, nullptr, TextFrom::Caller, nullptr, 0, &made)) != TGX_OK) return st;
+        out.reset(made);
+    }
+    HIP_TRY(hipStreamSynchronize(hs));
+    guard.done();
+    timer.read();
+    *segs = out.release();
+    *plan = pl.release();
+    return TGX_OK;
+}
+
+uint64_t tgx_plan_num_samples(const tgx_plan* p) { return p ? p->n_samples : 0; }
+uint64_t tgx_plan_num_segments(const tgx_plan* p) { return p ? p->n_segs : 0; }
+uint64_t tgx_plan_num_encoded(const tgx_plan* p) { return p ? p->n_enc : 0; }
+int tgx_plan_device(const tgx_plan* p) { return p ? p->device : -1; }
+// (the call that made it returned after its stream had reached its end: the buffers go straight back to the pool)
+void tgx_plan_free(tgx_plan* p) { delete p; }
+
+tgx_status tgx_plan_copy(const tgx_plan* p, uint64_t* seg_offs, uint64_t offs_cap, int32_t* seg_special, uint64_t special_cap) {
+    const char* who = "tgx_plan_copy";
+    if (!p || !seg_offs || (!seg_special && p->n_segs)) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
+    if (offs_cap < p->n_samples + 1) return fail(TGX_ERR_INVALID, "%s: %llu offsets, room for %llu", who, (unsigned long long)(p->n_samples + 1), (unsigned long long)offs_cap);
+    if (special_cap < p->n_segs) return fail(TGX_ERR_INVALID, "%s: %llu segments, room for %llu", who, (unsigned long long)p->n_segs, (unsigned long long)special_cap);
+    DeviceScope scope;
+    HIP_TRY(hipSetDevice(p->device));
+    HIP_TRY(copy_sync(seg_offs, p->d_seg_offs, (size_t)(p->n_samples + 1) * 8, hipMemcpyDeviceToHost, p->device));
+    if (p->n_segs) HIP_TRY(copy_sync(seg_special, p->d_special, (size_t)p->n_segs * 4, hipMemcpyDeviceToHost, p->device));
+    return TGX_OK;
 }
 
 // ---- spans: the part of its row's text that every token covers (spans.hip; spans.h has the index arithmetic) ------

@@ -605,6 +605,102 @@ class Tokenizer:
         return self.encode_batch_packed_flat(np.frombuffer(text_b, dtype=np.uint8), np.frombuffer(offs_b, dtype=np.uint64), block_len,
                                              dropout, **layout)
 
+    # -- encode_batch over a corpus that is already resident in HBM (csrc/front.hip) --
+    def _corpus_front(self, who: str):
+        """Which device front end a resident corpus takes -> None (no special tokens and no processor: encode_corpus as it
+        is) or the CRLF flag of NativeCorpus.split_specials.  The device front end knows the processor lists [] and
+        [CrlfProcessor]; anything else (a Unicode form, or CRLF twice: "\r\r\n" shows the pass is not idempotent) stays
+        with the flat route."""
+        procs = self._processors
+        if len(procs) > 1 or (procs and not isinstance(procs[0], CrlfProcessor)):
+            raise TokenGeeXError(f"{who}: the device front end takes no processor list but [] and one CrlfProcessor; "
+                                 "download the text and use encode_batch_result_flat", _lib.ERR_UNSUPPORTED)
+        if not procs and not self._special_tokens:
+            return None
+        return bool(procs)
+
+    def _split_corpus(self, corpus: "_lib.NativeCorpus", crlf: bool):
+        return corpus.split_specials([t.encode("utf-8") for t in self._special_tokens], crlf)
+
+    def encode_corpus_result(self, corpus: "_lib.NativeCorpus", dropout: float = 0.0) -> "_lib.NativeResult":
+        """encode_batch_result_flat over a corpus that is already in HBM (an upload, or decode_result_text(...).to_corpus()):
+        the special-token split and the CRLF processor run on the device (NativeCorpus.split_specials) and the plan is
+        assembled from where it is (NativeModel.assemble_plan), so neither the text nor the plan visits the host ->
+        NativeResult whose ids() / offsets() are encode_batch_flat's over the same samples.  The caller frees it.  (Without
+        special tokens a sample is hashed for dropout by its index among the non-empty samples.)"""
+        crlf = self._corpus_front("encode_corpus_result")
+        model = self._model()
+        if crlf is None:
+            return model.encode_corpus(corpus, dropout, self._seed(dropout))
+        segs_corpus, plan = self._split_corpus(corpus, crlf)
+        segs = None
+        try:
+            if plan.num_encoded:
+                segs = model.encode_corpus(segs_corpus, dropout, self._seed(dropout))
+            return model.assemble_plan(segs, plan, len(self._special_tokens))
+        finally:
+            if segs is not None:
+                segs.free()
+            segs_corpus.free()
+            plan.free()
+
+    def encode_corpus_sample_result(self, corpus: "_lib.NativeCorpus", alpha: float, seed: int | None = None, return_logz: bool = False):
+        """encode_batch_sample_result_flat over a resident corpus, as encode_corpus_result -> NativeResult [, logz f64[S]: the
+        plan is copied to the host only for this sum over a sample's non-special segments]."""
+        crlf = self._corpus_front("encode_corpus_sample_result")
+        seed = self._sample_seed(seed)
+        model = self._model()
+        if crlf is None:
+            return model.encode_corpus_sample(corpus, alpha, seed, return_logz=return_logz)
+        n = corpus.num_samples
+        segs_corpus, plan = self._split_corpus(corpus, crlf)
+        segs, seg_logz = None, np.zeros(0, np.float64)
+        try:
+            if plan.num_encoded:
+                segs, seg_logz = model.encode_corpus_sample(segs_corpus, alpha, seed, return_logz=True)
+            res = model.assemble_plan(segs, plan, len(self._special_tokens))
+            if not return_logz:
+                return res
+            seg_offs, ss = plan.seg_offs(), plan.seg_special()
+            seg_sample = np.repeat(np.arange(n), np.diff(seg_offs.astype(np.int64)))
+            return res, np.bincount(seg_sample[ss < 0], weights=seg_logz, minlength=n).astype(np.float64)
+        finally:
+            if segs is not None:
+                segs.free()
+            segs_corpus.free()
+            plan.free()
+
+    def encode_corpus_padded(self, corpus: "_lib.NativeCorpus", dropout: float = 0.0, **layout) -> dict:
+        """encode_batch_padded_flat over a resident corpus (encode_corpus_result): the same layout requests, offset mapping and
+        overflow windows included."""
+        from . import tensors
+        unit = self._mapping_unit(layout)
+        stride = self._window_stride(layout)
+        layout = self._layout_ids(layout)
+        if corpus.num_samples == 0:
+            if stride is not None:
+                return self._windows(None, layout, unit, stride)
+            return self._with_offset_mapping(None, self._empty_layout(True, None, layout), layout, unit)
+        res = self.encode_corpus_result(corpus, dropout)
+        try:
+            if stride is not None:
+                return self._windows(res, layout, unit, stride)
+            return self._with_offset_mapping(res, tensors.to_padded(res, **layout), layout, unit)
+        finally:
+            res.free()
+
+    def encode_corpus_packed(self, corpus: "_lib.NativeCorpus", block_len: int, dropout: float = 0.0, **layout) -> dict:
+        """encode_batch_packed_flat over a resident corpus (encode_corpus_result)."""
+        from . import tensors
+        layout = self._layout_ids(layout)
+        if corpus.num_samples == 0:
+            return self._empty_layout(False, block_len, layout)
+        res = self.encode_corpus_result(corpus, dropout)
+        try:
+            return tensors.to_packed(res, block_len, **layout)
+        finally:
+            res.free()
+
     # -- subword regularisation: a segmentation drawn from the lattice (csrc/sample.hip) --
     def _sample_seed(self, seed: int | None) -> int:
         if seed is not None:
