@@ -721,6 +721,13 @@ uint32_t tgx_encode_corun_timeouts(const tgx_model *m);
  * kept in its block's LDS (the rest are read from L2 by the relaxing lanes). */
 uint32_t tgx_model_score_values(const tgx_model *m);
 uint32_t tgx_last_encode_hot_values(const tgx_model *m);
+/* Which of the lean items the kernels of the last rows5 encode pass were built with (a self-check: results do not
+ * depend on it): bits 0-7 encode5_kernel's, bits 8-15 encode6_kernel's, of 1 = lean relaxation step, 2 = broadcast
+ * through the compiler's builtin and 4 = one-instruction score fetch.  0: the kernels
+ * as they were (dropout, tokens longer than 16 bytes, TGX_E5_LEAN=0, or another encode path).  Bit 0 is set only for
+ * the build that has the lean step (every token its own score at three positions per lane) and only for a model
+ * whose scores all have a magnitude below 2^960; other models run that build without the step. */
+uint32_t tgx_last_encode_lean_items(const tgx_model *m);
 
 /* ---- dropout ---------------------------------------------------------------
  * The reference draws rand::random::<f64>() from an unseeded thread RNG

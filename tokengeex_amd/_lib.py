@@ -98,6 +98,7 @@ SYMBOLS = {
     "tgx_last_encode_redo_samples": (_u64, [_vp]),
     "tgx_model_score_values": (_u32, [_vp]),
     "tgx_last_encode_hot_values": (_u32, [_vp]),
+    "tgx_last_encode_lean_items": (_u32, [_vp]),
     "tgx_last_encode_long_samples": (_u64, [_vp]),
     "tgx_last_estep_pieces": (_u64, [_vp]),
     "tgx_last_estep_redo": (_u64, [_vp]),
@@ -1278,6 +1279,17 @@ class NativeModel:
 
     def last_encode_hot_values(self) -> int:
         return lib.tgx_last_encode_hot_values(self._h)
+
+    def last_encode_lean_items(self) -> tuple[int, int]:
+        """(encode5_kernel's, encode6_kernel's) lean items of the last rows5 encode pass: masks of 1 = lean relaxation step,
+        2 = builtin broadcast, 4 = one-instruction score fetch; 0: the kernel as it was, or
+        not launched (a self-check: results do not depend on it)."""
+        v = lib.tgx_last_encode_lean_items(self._h)
+        return v & 0xFF, (v >> 8) & 0xFF
+
+    def last_encode_lean_step(self) -> bool:
+        """Whether encode5_kernel relaxed with the lean step in the last pass (last_encode_lean_items)."""
+        return bool(self.last_encode_lean_items()[0] & 1)
 
     def last_encode_long_samples(self) -> int:
         return lib.tgx_last_encode_long_samples(self._h)

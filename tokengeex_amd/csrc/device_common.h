@@ -111,6 +111,24 @@ __device__ __forceinline__ double row_bcast_f64(double v) {
     return r;
 }
 
+// The same move through the compiler's DPP builtin (the lean steps, relax5_step): it knows the instruction, so it pads
+// the "VALU write -> DPP read" hazard itself and only where no independent instruction sits in between.
+template <int U>
+__device__ __forceinline__ double row_bcast_f64_b(double v) {
+    // (mov_dpp, not update_dpp: every lane is written, and an `old` operand would be initialised with a move of its own)
+    return __longlong_as_double(__builtin_amdgcn_mov_dpp(__double_as_longlong(v), 0x150 + U, 0xF, 0xF, false));
+}
+
+// 8 * (16-bit word H of w) in one instruction: a shift with a sub-dword source select (the compiler does not pick
+// these on its own: v_bfe + v_lshl, or v_and + v_lshl).  dst_sel:DWORD only: a partial write has a forwarding hazard.
+template <int H>
+__device__ __forceinline__ uint32_t word_times8(uint32_t w) {
+    uint32_t a;
+    if (H) asm("v_lshlrev_b32_sdwa %0, 3, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_1" : "=v"(a) : "v"(w));
+    else asm("v_lshlrev_b32_sdwa %0, 3, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_0" : "=v"(a) : "v"(w));
+    return a;
+}
+
 constexpr uint64_t kRowLane0 = 0x0001000100010001ULL;  // lane 0 of each 16-lane row
 
 // Work queues.  One lane adds to a global counter and the whole wave reads the result.  Written as
@@ -210,18 +228,66 @@ __device__ __forceinline__ void relax4_step(double sv, double& acc, uint32_t& bp
 // broadcast -> add -> max instead of broadcast -> add -> compare -> mask OR -> two selects.  Same count of
 // VALU instructions, about a third of the latency per position (a lone 64 KiB sample: 7.1 -> ms per pass).
 // (Round 4 removed two of the step's nine vector instructions as an experiment — no `fhi`, the reset by the high word
-// alone with a finite sentinel: 150 of the kernel's 1 252 static VALU instructions gone, ids still bit-exact, 12.60 ->
-// 12.66 ms per GiB.  The vector ALU is 79 % busy but it is not what the pass waits for: profiles/r04.)
-template <int U>
+// alone with a finite sentinel — and measured 12.60 -> 12.66 ms per GiB.  Redone on the kernel with compacted walks
+// (relax5_lean_step below, profiles/relax_lean): with every value in LDS the answer is the same — the lean step, the
+// broadcast without its fixed pad and the one-instruction score fetch together issue 16 % fewer vector instructions
+// (5.60 -> 4.71 G per GiB) and the kernel takes 12.00 -> 12.01 ms; the wave's wait cycles grow by what its issue cycles
+// shrink.  The score fetch alone is worth 1.0 to 1.6 % there (11.95 -> 11.83 ms in the
+// headline runs, 11.98 -> 11.80 in the per-item runs).  The lean step pays, with the other two, in the COLD build at
+// three positions per lane (13.05 -> 12.70 ms), which is where it is used: DESIGN.md section R7.)
+//
+// LN (TGX_E5_LEAN): bit 0 — the kernel runs the step below only in the groups of 16 positions that
+// hold a sample's end and relax5_lean_step in all others; bit 1 — the broadcast through the compiler's builtin.
+// LN = 0 is the step as it was.
+constexpr int kLeanStep = 1, kLeanBcast = 2, kLeanFetch = 4;
+// "not reached" in a kernel that runs lean steps: -inf, or what a lean step resets a lane to and anything a finite
+// score added to that gives — a negative value of magnitude >= 2^1023 (see relax5_lean_step)
+constexpr uint32_t kLeanResetHi = 0xFFEFFFFFu;    // high word of -DBL_MAX
+constexpr uint32_t kLeanUnreachedHi = 0xFFE00000u;  // high word (unsigned) >= this: not reached
+template <int LN>
+__device__ __forceinline__ bool relax5_reached(uint32_t fhi) { return (LN & kLeanStep) ? fhi < kLeanUnreachedHi : fhi != 0xFFF00000u; }
+
+template <int U, int LN = 0>
 __device__ __forceinline__ void relax5_step(double sv, double& acc, uint32_t& bpv, uint32_t& fin, uint32_t& fhi) {
     constexpr uint64_t MU = kRowLane0 << U;  // lanes with l == U
-    const double best = row_bcast_f64<U>(acc);
+    double best;
+    if constexpr ((LN & kLeanBcast) != 0) best = row_bcast_f64_b<U>(acc);
+    else best = row_bcast_f64<U>(acc);
     fin = sel_u32(MU, bpv, fin);
     fhi = sel_u32(MU, (uint32_t)((uint64_t)__double_as_longlong(acc) >> 32), fhi);
     const double acc_r = sel_f64(MU, -__builtin_huge_val(), acc);  // the finalised lane starts position + 16
     const double cand = best + sv;           // model.rs:98
     const uint64_t take = __builtin_amdgcn_fcmp(cand, acc_r, 2 /* OGT: model.rs:101 */);
     asm("v_max_f64 %0, %1, %2" : "=v"(acc) : "v"(acc_r), "v"(cand));  // (fmax() adds a canonicalising v_max of its own)
+    bpv = sel_imm_u32<U>(take, bpv);
+}
+
+// The lean step: seven vector instructions instead of nine.  No `fhi` capture, and the finalised lane is reset by its
+// high word alone to that of -DBL_MAX (the low word stays: any value of that high word has a magnitude of at least
+// (2 - 2^-20) 2^1023) — one select instead of the two of a 64-bit -inf.  What makes this the same computation:
+//   * a position that is not reached then holds -inf (nothing pushed but "no token" entries) or a negative value of
+//     magnitude >= 2^1023, and a finite score of magnitude < 2^970 (half an ulp there) added to such a value gives it
+//     back or -inf: the class is closed, and it is what relax5_reached<LN> tests;
+//   * no reached position can get there: the host takes the lean kernels only if every score has a magnitude
+//     below 2^960 (lean_gate.h), samples are shorter than 2^32 bytes, so a path's score stays below 2^992;
+//   * a reached candidate therefore beats a reset lane exactly as it beats -inf, and among reached candidates the
+//     compare and the maximum see the values they saw before.
+// The winner step of a position that is not reached is then arbitrary (a candidate of the class may "beat" the reset
+// value), so its back-pointer byte is: no path visits such a position, and the trace reads path positions only.  The
+// position whose reachability IS read — a sample's end: P.status, the 0xFF byte — lies in a group that runs relax5_step.
+template <int U, int LN>
+__device__ __forceinline__ void relax5_lean_step(double sv, double& acc, uint32_t& bpv, uint32_t& fin) {
+    constexpr uint64_t MU = kRowLane0 << U;  // lanes with l == U
+    double best;
+    if constexpr ((LN & kLeanBcast) != 0) best = row_bcast_f64_b<U>(acc);
+    else best = row_bcast_f64<U>(acc);
+    fin = sel_u32(MU, bpv, fin);
+    const uint64_t ab = (uint64_t)__double_as_longlong(acc);
+    const uint32_t hi_r = sel_u32(MU, kLeanResetHi, (uint32_t)(ab >> 32));  // the finalised lane starts position + 16
+    const double acc_r = __hiloint2double((int)hi_r, (int)(uint32_t)ab);
+    const double cand = best + sv;           // model.rs:98
+    const uint64_t take = __builtin_amdgcn_fcmp(cand, acc_r, 2 /* OGT: model.rs:101 */);
+    asm("v_max_f64 %0, %1, %2" : "=v"(acc) : "v"(acc_r), "v"(cand));
     bpv = sel_imm_u32<U>(take, bpv);
 }
 

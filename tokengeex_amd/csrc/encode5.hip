@@ -262,13 +262,19 @@ struct Walk5<DROPOUT, LONG, RES, PPL, 16, SKIP, CK, PK> {
 // The score values of N consecutive steps (from step `first`) of a lane, whose sixteen match indices are the 16-bit
 // words in iw[8]: index * 8 is the byte offset of the value in the block's LDS — the copy of the first hot_bytes of the
 // value table (at LDS byte offset `tab`).  Requested a quarter group ahead of use.
-template <int N>
+// LN & kLeanFetch: the offset is one shift with a word select (word_times8) and no base is added — the table is at LDS
+// offset 0, which the launch checks (the kernel has no static LDS).
+template <int N, int LN = 0>
 __device__ __forceinline__ void e5_scores_issue(uint32_t tab, const uint32_t (&iw)[8], int first, u32x2_t (&sp)[N]) {
 #pragma unroll
     for (int u = 0; u < N; ++u) {
         const int v = first + u;
-        const uint32_t a = (v & 1) ? ((iw[v >> 1] >> 16) << 3) : ((iw[v >> 1] & 0xFFFFu) << 3);
-        sp[u] = lds_ld<u32x2_t>(tab + a);
+        if constexpr ((LN & kLeanFetch) != 0) {
+            sp[u] = lds_ld<u32x2_t>((v & 1) ? word_times8<1>(iw[v >> 1]) : word_times8<0>(iw[v >> 1]));
+        } else {
+            const uint32_t a = (v & 1) ? ((iw[v >> 1] >> 16) << 3) : ((iw[v >> 1] & 0xFFFFu) << 3);
+            sp[u] = lds_ld<u32x2_t>(tab + a);
+        }
     }
 }
 __device__ __forceinline__ double e5_score_value(const u32x2_t& p) { return __hiloint2double((int)p.y, (int)p.x); }
@@ -284,15 +290,20 @@ __device__ __forceinline__ double e5_score_value(const u32x2_t& p) { return __hi
 // them into pool slots in LDS before the relaxation, with or without its L2 round trip hidden behind the group
 // before (e5_resolve: +0.4 ... +2.3 ms per GiB against this); unconditional loads whose hot lanes fall outside the
 // buffer, merged by OR (+2.7 ms).  Each removes instructions of one kind and adds more of another.
-template <int N>
+template <int N, int LN = 0>
 __device__ __forceinline__ void e5_scores_cold(uint32_t tab, __amdgpu_buffer_rsrc_t cold, const uint32_t (&iw)[8], int first,
                                                uint32_t hot_bytes, double (&sv)[N]) {
     uint32_t a[N];
 #pragma unroll
     for (int u = 0; u < N; ++u) {
         const int v = first + u;
-        a[u] = (v & 1) ? ((iw[v >> 1] >> 16) << 3) : ((iw[v >> 1] & 0xFFFFu) << 3);
-        sv[u] = lds_ld<double>(tab + (a[u] < hot_bytes ? a[u] : 0u));
+        if constexpr ((LN & kLeanFetch) != 0) {
+            a[u] = (v & 1) ? word_times8<1>(iw[v >> 1]) : word_times8<0>(iw[v >> 1]);
+            sv[u] = lds_ld<double>(a[u] < hot_bytes ? a[u] : 0u);
+        } else {
+            a[u] = (v & 1) ? ((iw[v >> 1] >> 16) << 3) : ((iw[v >> 1] & 0xFFFFu) << 3);
+            sv[u] = lds_ld<double>(tab + (a[u] < hot_bytes ? a[u] : 0u));
+        }
     }
     static_assert(N == 4 || N == 8, "e5_scores_cold: four or eight values at a time");
     if (N == 8) asm volatile("" : "+v"(sv[0]), "+v"(sv[1]), "+v"(sv[2]), "+v"(sv[3]), "+v"(sv[4 % N]), "+v"(sv[5 % N]), "+v"(sv[6 % N]), "+v"(sv[7 % N]));
@@ -398,9 +409,11 @@ __device__ __forceinline__ void e5_long_tail(__amdgpu_buffer_rsrc_t trie, const 
     }
 
 // CK: the depth at which the walks are compacted (Walk5; 0: never)
-template <bool DROPOUT, bool COLD, int PPL, bool LONG, int CK = 0>
+// LN: the lean relaxation (device_common.h: kLeanStep | kLeanBcast | kLeanFetch; 0: the kernel as it was)
+template <bool DROPOUT, bool COLD, int PPL, bool LONG, int CK = 0, int LN = 0>
 __global__ __launch_bounds__(1024, (PPL == 1 ? 8 : (PPL == 2 ? 6 : (PPL == 3 ? 4 : 1)))) void encode5_kernel(EncodeParams P, Encode5Params Q) {
     static_assert(!LONG || PPL == 4, "the long-token build runs four positions per lane");
+    static_assert(LN == 0 || (!LONG && !DROPOUT), "the long-token and dropout builds keep the kernel as it was");
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr uint32_t LM = LONG ? 32 : 16;
     constexpr uint32_t SPAN = 16u * PPL;
@@ -570,7 +583,13 @@ __global__ __launch_bounds__(1024, (PPL == 1 ? 8 : (PPL == 2 ? 6 : (PPL == 3 ? 4
             };
             u32x2_t sa[4], sb[4];
             load_iw(0, iw);
-            if (!COLD) e5_scores_issue<4>(lds0, iw, 0, sa);
+            if (!COLD) e5_scores_issue<4, LN>(lds0, iw, 0, sa);
+            uint32_t end_groups = 0;  // lean builds: bit g — some row's sample ends in group g of this trip (wave-uniform)
+            if (LN & kLeanStep) {
+                const uint32_t g_end = (live && n - p0 < SPAN) ? ((n - p0) >> 4) : 0xFFu;
+#pragma unroll
+                for (int g = 0; g < PPL; ++g) end_groups |= (__builtin_amdgcn_ballot_w64(g_end == (uint32_t)g) != 0 ? 1u : 0u) << g;
+            }
 #pragma unroll
             for (int g = 0; g < PPL; ++g) {
                 uint32_t (&cw)[8] = (g & 1) ? iwn : iw;
@@ -638,53 +657,98 @@ __global__ __launch_bounds__(1024, (PPL == 1 ? 8 : (PPL == 2 ? 6 : (PPL == 3 ? 4
                     }
                     continue;
                 }
-                if (COLD) {
-                    // both halves' cold values are requested before the first step: the loads sit behind branches, so
-                    // the compiler waits for all of them at the first use — one exposed L2 round trip per group, not two
-                    double sv[8], sw[8];
-                    e5_scores_cold<8>(lds0, cold_values, cw, 0, hot_bytes, sv);
-                    e5_scores_cold<8>(lds0, cold_values, cw, 8, hot_bytes, sw);
-                    if (g + 1 < PPL) load_iw(g + 1, nw);
-                    relax5_step<0>(sv[0], acc, bpv, fin[g], fhi);
-                    relax5_step<1>(sv[1], acc, bpv, fin[g], fhi);
-                    relax5_step<2>(sv[2], acc, bpv, fin[g], fhi);
-                    relax5_step<3>(sv[3], acc, bpv, fin[g], fhi);
-                    relax5_step<4>(sv[4], acc, bpv, fin[g], fhi);
-                    relax5_step<5>(sv[5], acc, bpv, fin[g], fhi);
-                    relax5_step<6>(sv[6], acc, bpv, fin[g], fhi);
-                    relax5_step<7>(sv[7], acc, bpv, fin[g], fhi);
-                    relax5_step<8>(sw[0], acc, bpv, fin[g], fhi);
-                    relax5_step<9>(sw[1], acc, bpv, fin[g], fhi);
-                    relax5_step<10>(sw[2], acc, bpv, fin[g], fhi);
-                    relax5_step<11>(sw[3], acc, bpv, fin[g], fhi);
-                    relax5_step<12>(sw[4], acc, bpv, fin[g], fhi);
-                    relax5_step<13>(sw[5], acc, bpv, fin[g], fhi);
-                    relax5_step<14>(sw[6], acc, bpv, fin[g], fhi);
-                    relax5_step<15>(sw[7], acc, bpv, fin[g], fhi);
+                // LN == 0 keeps the steps' text as it was, verbatim, beside the macro form below — do not fold the two: with
+                // the macro / lambda form alone 53 of this file's 70 kernels came out scheduled differently from the parent's,
+                // and TGX_E5_LEAN=0 has to run the parent's instructions (profiles/relax_lean/kernel_resources.txt)
+                if constexpr (LN == 0) {
+                    if (COLD) {
+                        // both halves' cold values are requested before the first step: the loads sit behind branches, so
+                        // the compiler waits for all of them at the first use — one exposed L2 round trip per group, not two
+                        double sv[8], sw[8];
+                        e5_scores_cold<8>(lds0, cold_values, cw, 0, hot_bytes, sv);
+                        e5_scores_cold<8>(lds0, cold_values, cw, 8, hot_bytes, sw);
+                        if (g + 1 < PPL) load_iw(g + 1, nw);
+                        relax5_step<0>(sv[0], acc, bpv, fin[g], fhi);
+                        relax5_step<1>(sv[1], acc, bpv, fin[g], fhi);
+                        relax5_step<2>(sv[2], acc, bpv, fin[g], fhi);
+                        relax5_step<3>(sv[3], acc, bpv, fin[g], fhi);
+                        relax5_step<4>(sv[4], acc, bpv, fin[g], fhi);
+                        relax5_step<5>(sv[5], acc, bpv, fin[g], fhi);
+                        relax5_step<6>(sv[6], acc, bpv, fin[g], fhi);
+                        relax5_step<7>(sv[7], acc, bpv, fin[g], fhi);
+                        relax5_step<8>(sw[0], acc, bpv, fin[g], fhi);
+                        relax5_step<9>(sw[1], acc, bpv, fin[g], fhi);
+                        relax5_step<10>(sw[2], acc, bpv, fin[g], fhi);
+                        relax5_step<11>(sw[3], acc, bpv, fin[g], fhi);
+                        relax5_step<12>(sw[4], acc, bpv, fin[g], fhi);
+                        relax5_step<13>(sw[5], acc, bpv, fin[g], fhi);
+                        relax5_step<14>(sw[6], acc, bpv, fin[g], fhi);
+                        relax5_step<15>(sw[7], acc, bpv, fin[g], fhi);
+                    } else {
+                        e5_scores_issue<4>(lds0, cw, 4, sb);
+                        if (g + 1 < PPL) load_iw(g + 1, nw);
+                        relax5_step<0>(e5_score_value(sa[0]), acc, bpv, fin[g], fhi);
+                        relax5_step<1>(e5_score_value(sa[1]), acc, bpv, fin[g], fhi);
+                        relax5_step<2>(e5_score_value(sa[2]), acc, bpv, fin[g], fhi);
+                        relax5_step<3>(e5_score_value(sa[3]), acc, bpv, fin[g], fhi);
+                        e5_scores_issue<4>(lds0, cw, 8, sa);
+                        relax5_step<4>(e5_score_value(sb[0]), acc, bpv, fin[g], fhi);
+                        relax5_step<5>(e5_score_value(sb[1]), acc, bpv, fin[g], fhi);
+                        relax5_step<6>(e5_score_value(sb[2]), acc, bpv, fin[g], fhi);
+                        relax5_step<7>(e5_score_value(sb[3]), acc, bpv, fin[g], fhi);
+                        e5_scores_issue<4>(lds0, cw, 12, sb);
+                        relax5_step<8>(e5_score_value(sa[0]), acc, bpv, fin[g], fhi);
+                        relax5_step<9>(e5_score_value(sa[1]), acc, bpv, fin[g], fhi);
+                        relax5_step<10>(e5_score_value(sa[2]), acc, bpv, fin[g], fhi);
+                        relax5_step<11>(e5_score_value(sa[3]), acc, bpv, fin[g], fhi);
+                        if (g + 1 < PPL) e5_scores_issue<4>(lds0, nw, 0, sa);
+                        relax5_step<12>(e5_score_value(sb[0]), acc, bpv, fin[g], fhi);
+                        relax5_step<13>(e5_score_value(sb[1]), acc, bpv, fin[g], fhi);
+                        relax5_step<14>(e5_score_value(sb[2]), acc, bpv, fin[g], fhi);
+                        relax5_step<15>(e5_score_value(sb[3]), acc, bpv, fin[g], fhi);
+                    }
+                    reached[g] = fhi != 0xFFF00000u;
                 } else {
-                    e5_scores_issue<4>(lds0, cw, 4, sb);
-                    if (g + 1 < PPL) load_iw(g + 1, nw);
-                    relax5_step<0>(e5_score_value(sa[0]), acc, bpv, fin[g], fhi);
-                    relax5_step<1>(e5_score_value(sa[1]), acc, bpv, fin[g], fhi);
-                    relax5_step<2>(e5_score_value(sa[2]), acc, bpv, fin[g], fhi);
-                    relax5_step<3>(e5_score_value(sa[3]), acc, bpv, fin[g], fhi);
-                    e5_scores_issue<4>(lds0, cw, 8, sa);
-                    relax5_step<4>(e5_score_value(sb[0]), acc, bpv, fin[g], fhi);
-                    relax5_step<5>(e5_score_value(sb[1]), acc, bpv, fin[g], fhi);
-                    relax5_step<6>(e5_score_value(sb[2]), acc, bpv, fin[g], fhi);
-                    relax5_step<7>(e5_score_value(sb[3]), acc, bpv, fin[g], fhi);
-                    e5_scores_issue<4>(lds0, cw, 12, sb);
-                    relax5_step<8>(e5_score_value(sa[0]), acc, bpv, fin[g], fhi);
-                    relax5_step<9>(e5_score_value(sa[1]), acc, bpv, fin[g], fhi);
-                    relax5_step<10>(e5_score_value(sa[2]), acc, bpv, fin[g], fhi);
-                    relax5_step<11>(e5_score_value(sa[3]), acc, bpv, fin[g], fhi);
-                    if (g + 1 < PPL) e5_scores_issue<4>(lds0, nw, 0, sa);
-                    relax5_step<12>(e5_score_value(sb[0]), acc, bpv, fin[g], fhi);
-                    relax5_step<13>(e5_score_value(sb[1]), acc, bpv, fin[g], fhi);
-                    relax5_step<14>(e5_score_value(sb[2]), acc, bpv, fin[g], fhi);
-                    relax5_step<15>(e5_score_value(sb[3]), acc, bpv, fin[g], fhi);
+                    // (wave-uniform) a group that holds the end of some row's sample runs the full steps: that position's
+                    // reachability is read (P.status, the 0xFF byte); every other group the lean ones
+                    const bool full = !(LN & kLeanStep) || ((end_groups >> g) & 1u) != 0u;
+#define E5_STEP(U, SV)                                                   \
+        if (FULL) relax5_step<U, LN>(SV, acc, bpv, fin[g], fhi);              \
+        else relax5_lean_step<U, LN>(SV, acc, bpv, fin[g]);
+                    auto steps = [&](auto full_tag) {
+                        constexpr bool FULL = decltype(full_tag)::value;
+                        if (COLD) {
+                            // both halves' cold values are requested before the first step: the loads sit behind branches, so
+                            // the compiler waits for all of them at the first use — one exposed L2 round trip per group, not two
+                            double sv[8], sw[8];
+                            e5_scores_cold<8, LN>(lds0, cold_values, cw, 0, hot_bytes, sv);
+                            e5_scores_cold<8, LN>(lds0, cold_values, cw, 8, hot_bytes, sw);
+                            if (g + 1 < PPL) load_iw(g + 1, nw);
+                            E5_STEP(0, sv[0]) E5_STEP(1, sv[1]) E5_STEP(2, sv[2]) E5_STEP(3, sv[3])
+                            E5_STEP(4, sv[4]) E5_STEP(5, sv[5]) E5_STEP(6, sv[6]) E5_STEP(7, sv[7])
+                            E5_STEP(8, sw[0]) E5_STEP(9, sw[1]) E5_STEP(10, sw[2]) E5_STEP(11, sw[3])
+                            E5_STEP(12, sw[4]) E5_STEP(13, sw[5]) E5_STEP(14, sw[6]) E5_STEP(15, sw[7])
+                        } else {
+                            e5_scores_issue<4, LN>(lds0, cw, 4, sb);
+                            if (g + 1 < PPL) load_iw(g + 1, nw);
+                            E5_STEP(0, e5_score_value(sa[0])) E5_STEP(1, e5_score_value(sa[1]))
+                            E5_STEP(2, e5_score_value(sa[2])) E5_STEP(3, e5_score_value(sa[3]))
+                            e5_scores_issue<4, LN>(lds0, cw, 8, sa);
+                            E5_STEP(4, e5_score_value(sb[0])) E5_STEP(5, e5_score_value(sb[1]))
+                            E5_STEP(6, e5_score_value(sb[2])) E5_STEP(7, e5_score_value(sb[3]))
+                            e5_scores_issue<4, LN>(lds0, cw, 12, sb);
+                            E5_STEP(8, e5_score_value(sa[0])) E5_STEP(9, e5_score_value(sa[1]))
+                            E5_STEP(10, e5_score_value(sa[2])) E5_STEP(11, e5_score_value(sa[3]))
+                            if (g + 1 < PPL) e5_scores_issue<4, LN>(lds0, nw, 0, sa);
+                            E5_STEP(12, e5_score_value(sb[0])) E5_STEP(13, e5_score_value(sb[1]))
+                            E5_STEP(14, e5_score_value(sb[2])) E5_STEP(15, e5_score_value(sb[3]))
+                        }
+                    };
+                    if (full) steps(std::true_type{});
+                    else steps(std::false_type{});
+#undef E5_STEP
+                    reached[g] = !full || relax5_reached<LN>(fhi);
                 }
-                reached[g] = fhi != 0xFFF00000u;
             }
         } else {
 #pragma unroll
@@ -785,21 +849,23 @@ __device__ __forceinline__ uint32_t lds_load(const uint32_t* p) { return __hip_a
 __device__ __forceinline__ void lds_store(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 
 // the four score values of a quarter group (steps 4 q .. 4 q + 3) of a lane: 16-bit ranks in iw
-template <bool COLD>
+template <bool COLD, int LN = 0>
 __device__ __forceinline__ void e6_load_quarter(uint32_t tab, __amdgpu_buffer_rsrc_t cold, uint32_t hot_bytes,
                                                 const uint32_t (&iw)[8], int q, double (&sv)[4]) {
     if (COLD) {
-        e5_scores_cold<4>(tab, cold, iw, 4 * q, hot_bytes, sv);
+        e5_scores_cold<4, LN>(tab, cold, iw, 4 * q, hot_bytes, sv);
     } else {
         u32x2_t sp[4];
-        e5_scores_issue<4>(tab, iw, 4 * q, sp);
+        e5_scores_issue<4, LN>(tab, iw, 4 * q, sp);
 #pragma unroll
         for (int u = 0; u < 4; ++u) sv[u] = e5_score_value(sp[u]);
     }
 }
 
-template <bool DROPOUT, bool COLD>
+template <bool DROPOUT, bool COLD, int LN = 0>
 __global__ __launch_bounds__(64 * (1 + 4 * kE6Walkers), 8) void encode6_kernel(EncodeParams P, Encode5Params Q) {
+    static_assert(LN == 0 || !DROPOUT, "the dropout builds keep the kernel as it was");
+    static_assert((LN & (kLeanStep | kLeanBcast)) == 0, "encode6_kernel: the score fetch only (the lean step spills here)");
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr uint32_t LM = 16;
     constexpr uint32_t K = kE6Walkers, G = kE6Slots;
@@ -910,30 +976,30 @@ __global__ __launch_bounds__(64 * (1 + 4 * kE6Walkers), 8) void encode6_kernel(E
                 uint32_t iwa[8], iwb[8];
                 double sva[4], svb[4];
                 load_iw(0, iwa);
-                e6_load_quarter<C>(lds0, values, hot_bytes, iwa, 0, sva);
+                e6_load_quarter<C, LN>(lds0, values, hot_bytes, iwa, 0, sva);
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     uint32_t (&iw)[8] = (g & 1) ? iwb : iwa;
                     uint32_t (&iwn)[8] = (g & 1) ? iwa : iwb;
                     fin[g] = kNoStep;
                     uint32_t fhi = 0xFFF00000u;
-                    e6_load_quarter<C>(lds0, values, hot_bytes, iw, 1, svb);
+                    e6_load_quarter<C, LN>(lds0, values, hot_bytes, iw, 1, svb);
                     if (g < 3) load_iw(g + 1, iwn);
                     relax5_step<0>(sva[0], acc, bpv, fin[g], fhi);
                     relax5_step<1>(sva[1], acc, bpv, fin[g], fhi);
                     relax5_step<2>(sva[2], acc, bpv, fin[g], fhi);
                     relax5_step<3>(sva[3], acc, bpv, fin[g], fhi);
-                    e6_load_quarter<C>(lds0, values, hot_bytes, iw, 2, sva);
+                    e6_load_quarter<C, LN>(lds0, values, hot_bytes, iw, 2, sva);
                     relax5_step<4>(svb[0], acc, bpv, fin[g], fhi);
                     relax5_step<5>(svb[1], acc, bpv, fin[g], fhi);
                     relax5_step<6>(svb[2], acc, bpv, fin[g], fhi);
                     relax5_step<7>(svb[3], acc, bpv, fin[g], fhi);
-                    e6_load_quarter<C>(lds0, values, hot_bytes, iw, 3, svb);
+                    e6_load_quarter<C, LN>(lds0, values, hot_bytes, iw, 3, svb);
                     relax5_step<8>(sva[0], acc, bpv, fin[g], fhi);
                     relax5_step<9>(sva[1], acc, bpv, fin[g], fhi);
                     relax5_step<10>(sva[2], acc, bpv, fin[g], fhi);
                     relax5_step<11>(sva[3], acc, bpv, fin[g], fhi);
-                    if (g < 3) e6_load_quarter<C>(lds0, values, hot_bytes, iwn, 0, sva);
+                    if (g < 3) e6_load_quarter<C, LN>(lds0, values, hot_bytes, iwn, 0, sva);
                     relax5_step<12>(svb[0], acc, bpv, fin[g], fhi);
                     relax5_step<13>(svb[1], acc, bpv, fin[g], fhi);
                     relax5_step<14>(svb[2], acc, bpv, fin[g], fhi);
@@ -1286,8 +1352,38 @@ hipError_t launch_estep5_fwd(const Estep4Params& p, Encode5Params q, bool cold, 
 }
 
 typedef void (*encode5_fn)(EncodeParams, Encode5Params);
+// What TGX_E5_LEAN=1 (the default) selects, per build: the items of DESIGN.md section R7 that paid there (device_common.h:
+// kLeanStep = 1, kLeanBcast = 2, kLeanFetch = 4).  -DTGX_E5_LEAN_ITEMS=<mask> builds the library with one set everywhere,
+// for measurements.
+// The one-instruction score fetch is used in every build.  The lean step and the builtin broadcast pay only together
+// with it in the COLD build at three positions per lane (the geometry of vocabularies in which every token has its own
+// score); where the registers are capped lower (two positions per lane, encode6_kernel's 64) the second copy of a
+// group's steps spills and costs up to 2x: encode6_kernel has no such copy.  (Walk levels with operand selects — SDWA
+// compares into scalar lane masks — were built and measured as a fourth item: +4 % on the kernel, removed)
+#ifdef TGX_E5_LEAN_ITEMS
+constexpr int kE5LeanHot = TGX_E5_LEAN_ITEMS, kE5LeanCold = TGX_E5_LEAN_ITEMS, kE5LeanCold3 = TGX_E5_LEAN_ITEMS;
+constexpr int kE6Lean = kLeanFetch;
+#else
+constexpr int kE5LeanHot = kLeanFetch;                             // every value in LDS
+constexpr int kE5LeanCold = kLeanFetch;                            // COLD builds at one, two, four positions per lane
+constexpr int kE5LeanCold3 = kLeanStep | kLeanBcast | kLeanFetch;  // COLD, three positions per lane
+constexpr int kE6Lean = kLeanFetch;                                // the long-sample kernel
+#endif
+static_assert(kE5LeanHot > 0 && kE5LeanHot <= 7 && kE5LeanCold > 0 && kE5LeanCold <= 7 && kE5LeanCold3 > 0 && kE5LeanCold3 <= 7,
+              "a mask of kLeanStep, kLeanBcast, kLeanFetch");
+// what a model whose scores fail the lean step's gate runs instead (whatever the masks are, a measurement build's too)
+constexpr int lean_without_step(int items) { return items & ~kLeanStep; }
+// the dropout and long-token builds have no lean variant: their launches run the step as it was
+bool encode5_has_lean(bool dropout, bool long_tokens) { return !dropout && !long_tokens; }
+// the items the lean build of encode5_kernel (hot / COLD, positions per lane; step_ok: the model's scores pass the lean
+// step's gate) and of encode6_kernel runs: what tgx_last_encode_lean_items reports
+int encode5_lean_items(bool cold, int ppl, bool step_ok) {
+    const int items = cold ? (ppl == 3 ? kE5LeanCold3 : kE5LeanCold) : kE5LeanHot;
+    return step_ok ? items : lean_without_step(items);
+}
+int encode6_lean_items() { return kE6Lean; }
 // compact: the depth of Walk5's compaction (0, 4 .. 8); the DROPOUT, LONG and one-position-per-lane builds never compact
-static encode5_fn pick_encode5(bool dropout, bool cold, int ppl, bool long_tokens, int compact) {
+static encode5_fn pick_encode5(bool dropout, bool cold, int ppl, bool long_tokens, int compact, bool lean, bool step_ok) {
     if (long_tokens) {  // tokens of 17..32 bytes: four positions per lane only
         if (cold) return dropout ? encode5_kernel<true, true, 4, true> : encode5_kernel<false, true, 4, true>;
         return dropout ? encode5_kernel<true, false, 4, true> : encode5_kernel<false, false, 4, true>;
@@ -1304,20 +1400,29 @@ static encode5_fn pick_encode5(bool dropout, bool cold, int ppl, bool long_token
         if (ppl == 3) return encode5_kernel<true, false, 3, false>;
         return encode5_kernel<true, false, 4, false>;
     }
-#define TGX_E5K(C, PL) \
-    (compact == 4 ? encode5_kernel<false, C, PL, false, 4> : compact == 5 ? encode5_kernel<false, C, PL, false, 5> \
-     : compact == 6 ? encode5_kernel<false, C, PL, false, 6> : compact == 7 ? encode5_kernel<false, C, PL, false, 7> \
-     : compact == 8 ? encode5_kernel<false, C, PL, false, 8> : encode5_kernel<false, C, PL, false, 0>)
-    if (cold) {
-        if (ppl == 1) return encode5_kernel<false, true, 1, false>;
-        if (ppl == 2) return TGX_E5K(true, 2);
-        if (ppl == 3) return TGX_E5K(true, 3);
-        return TGX_E5K(true, 4);
+#define TGX_E5K(C, PL, LN) \
+    (compact == 4 ? encode5_kernel<false, C, PL, false, 4, LN> : compact == 5 ? encode5_kernel<false, C, PL, false, 5, LN> \
+     : compact == 6 ? encode5_kernel<false, C, PL, false, 6, LN> : compact == 7 ? encode5_kernel<false, C, PL, false, 7, LN> \
+     : compact == 8 ? encode5_kernel<false, C, PL, false, 8, LN> : encode5_kernel<false, C, PL, false, 0, LN>)
+#define TGX_E5L(LNH, LNC, LNC3) \
+    if (cold) { \
+        if (ppl == 1) return encode5_kernel<false, true, 1, false, 0, LNC>; \
+        if (ppl == 2) return TGX_E5K(true, 2, LNC); \
+        if (ppl == 3) return TGX_E5K(true, 3, LNC3); \
+        return TGX_E5K(true, 4, LNC); \
+    } \
+    if (ppl == 1) return encode5_kernel<false, false, 1, false, 0, LNH>; \
+    if (ppl == 2) return TGX_E5K(false, 2, LNH); \
+    if (ppl == 3) return TGX_E5K(false, 3, LNH); \
+    return TGX_E5K(false, 4, LNH);
+    if (lean && step_ok) {
+        TGX_E5L(kE5LeanHot, kE5LeanCold, kE5LeanCold3)
     }
-    if (ppl == 1) return encode5_kernel<false, false, 1, false>;
-    if (ppl == 2) return TGX_E5K(false, 2);
-    if (ppl == 3) return TGX_E5K(false, 3);
-    return TGX_E5K(false, 4);
+    if (lean) {  // a score beyond the lean step's gate: the same builds without the step (0: the kernel as it was)
+        TGX_E5L(lean_without_step(kE5LeanHot), lean_without_step(kE5LeanCold), lean_without_step(kE5LeanCold3))
+    }
+    TGX_E5L(0, 0, 0)
+#undef TGX_E5L
 #undef TGX_E5K
 }
 
@@ -1339,9 +1444,9 @@ uint32_t encode5_max_hot(bool long_tokens, int waves, int ppl, uint32_t budget) 
     return budget > fixed + 64u ? (budget - fixed) / 8u : 0u;
 }
 
-hipError_t encode5_waves_per_simd(bool dropout, bool cold, int ppl, bool long_tokens, int compact, int* out) {
+hipError_t encode5_waves_per_simd(bool dropout, bool cold, int ppl, bool long_tokens, int compact, bool lean, bool step_ok, int* out) {
     hipFuncAttributes attr;
-    hipError_t e = hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(pick_encode5(dropout, cold, ppl, long_tokens, compact)));
+    hipError_t e = hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(pick_encode5(dropout, cold, ppl, long_tokens, compact, lean && encode5_has_lean(dropout, long_tokens), step_ok)));
     if (e != hipSuccess) return e;
     const int regs = (attr.numRegs + 7) & ~7;
     *out = regs > 0 ? (512 / regs > 8 ? 8 : 512 / regs) : 8;
@@ -1365,30 +1470,43 @@ uint32_t encode6_max_hot(uint32_t budget, uint32_t pool) {
     const uint32_t fixed = encode6_lds_layout(0u, pool, nullptr, nullptr, nullptr) + 512u;
     return budget > fixed + 64u ? (budget - fixed) / 8u : 0u;
 }
-hipError_t launch_encode6(const EncodeParams& p, Encode5Params q, bool cold, uint32_t blocks, hipStream_t stream) {
+// The lean score fetch adds no base to a value's offset: the table must sit at LDS offset 0, i.e. the kernel must have
+// no static LDS in front of its dynamic LDS.
+static hipError_t lean_lds_check(const void* fn) {
+    hipFuncAttributes attr;
+    const hipError_t e = hipFuncGetAttributes(&attr, fn);
+    if (e != hipSuccess) return e;
+    return attr.sharedSizeBytes == 0 ? hipSuccess : hipErrorInvalidValue;
+}
+
+hipError_t launch_encode6(const EncodeParams& p, Encode5Params q, bool cold, bool lean, uint32_t blocks, hipStream_t stream) {
     q.ring_slots = kE6Slots;
     if (!cold) q.pool = 0u;
     const uint32_t lds = encode6_lds_layout(q.n_hot, q.pool, &q.root_off, &q.ctrl_off, &q.ring_off);
     if (lds > 160u * 1024u || q.n_hot > q.n_values || (!cold && q.n_hot != q.n_values) ||
         (uint64_t)q.n_values + 4ull * kE6Slots * q.pool > 65535ull)
         return hipErrorInvalidValue;
-    auto fn = cold ? (p.dropout > 0.0 ? encode6_kernel<true, true> : encode6_kernel<false, true>)
-                   : (p.dropout > 0.0 ? encode6_kernel<true, false> : encode6_kernel<false, false>);
+    lean = lean && encode5_has_lean(p.dropout > 0.0, false);
+    auto fn = cold ? (p.dropout > 0.0 ? encode6_kernel<true, true> : lean ? encode6_kernel<false, true, kE6Lean> : encode6_kernel<false, true>)
+                   : (p.dropout > 0.0 ? encode6_kernel<true, false> : lean ? encode6_kernel<false, false, kE6Lean> : encode6_kernel<false, false>);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return e;
+    if (lean && (e = lean_lds_check(reinterpret_cast<const void*>(fn))) != hipSuccess) return e;
     hipLaunchKernelGGL(fn, dim3(blocks), dim3(64u * (1u + 4u * kE6Walkers)), lds, stream, p, q);
     return hipGetLastError();
 }
 
-hipError_t launch_encode5(const EncodeParams& p, Encode5Params q, bool cold, int ppl, bool long_tokens, int compact, int waves, uint32_t blocks,
-                          uint32_t min_lds, hipStream_t stream) {
+hipError_t launch_encode5(const EncodeParams& p, Encode5Params q, bool cold, int ppl, bool long_tokens, int compact, bool lean, bool step_ok,
+                          int waves, uint32_t blocks, uint32_t min_lds, hipStream_t stream) {
     uint32_t lds = encode5_lds_layout(q.n_hot, long_tokens, waves, ppl, &q.list_off, &q.root_off, &q.idx_off);
     if (lds > 160u * 1024u || q.n_hot > q.n_values || (!cold && q.n_hot != q.n_values) || (long_tokens && ppl != 4) ||
         (compact != 0 && (compact < 4 || compact > 8)))
         return hipErrorInvalidValue;
-    encode5_fn fn = pick_encode5(p.dropout > 0.0, cold, ppl, long_tokens, compact);
+    lean = lean && encode5_has_lean(p.dropout > 0.0, long_tokens);
+    encode5_fn fn = pick_encode5(p.dropout > 0.0, cold, ppl, long_tokens, compact, lean, step_ok);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return e;
+    if (lean && (e = lean_lds_check(reinterpret_cast<const void*>(fn))) != hipSuccess) return e;
     if (lds < min_lds && min_lds <= 160u * 1024u) lds = min_lds;  // (a launch that wants its CUs to itself)
     hipLaunchKernelGGL(fn, dim3(blocks), dim3(64u * (uint32_t)waves), lds, stream, p, q);
     return hipGetLastError();

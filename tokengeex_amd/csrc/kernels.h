@@ -278,17 +278,24 @@ uint32_t encode4_lds_bytes(int waves, int ppl, bool root);
 hipError_t launch_trace(const EncodeParams& p, uint32_t blocks, hipStream_t stream);
 uint32_t encode5_lds_layout(uint32_t n_hot, bool long_tokens, int waves, int ppl, uint32_t* list_off, uint32_t* root_off, uint32_t* idx_off);
 uint32_t encode5_max_hot(bool long_tokens, int waves, int ppl, uint32_t budget);
-hipError_t encode5_waves_per_simd(bool dropout, bool cold, int ppl, bool long_tokens, int compact, int* out);
+// lean: the kernels with the lean relaxation step (TGX_E5_LEAN; device_common.h: relax5_lean_step) — the dropout and
+// long-token builds have none and run the step as it was (encode5_has_lean)
+bool encode5_has_lean(bool dropout, bool long_tokens);
+// the items (device_common.h: kLeanStep | kLeanBcast | kLeanFetch) of the lean build of encode5_kernel (hot /
+// COLD, positions per lane; step_ok: the scores pass the lean step's gate, else the build without the step) and encode6_kernel
+int encode5_lean_items(bool cold, int ppl, bool step_ok);
+int encode6_lean_items();
+hipError_t encode5_waves_per_simd(bool dropout, bool cold, int ppl, bool long_tokens, int compact, bool lean, bool step_ok, int* out);
 uint32_t encode6_lds_layout(uint32_t n_hot, uint32_t pool, uint32_t* root_off, uint32_t* ctrl_off, uint32_t* ring_off);
 uint32_t encode6_max_hot(uint32_t budget, uint32_t pool);
 uint32_t encode6_pool_total(uint32_t pool);  // pool entries of a block (index space they take)
 // estep5_fwd_kernel (encode5.hip): the E-step's forward sweep over the 8-byte ranked records; q.values = exp(score value) by rank
 hipError_t estep5_waves_per_simd(bool dropout, bool cold, int ppl, int* out);
 hipError_t launch_estep5_fwd(const struct Estep4Params& p, Encode5Params q, bool cold, int ppl, int waves, uint32_t blocks, hipStream_t stream);
-hipError_t launch_encode6(const EncodeParams& p, Encode5Params q, bool cold, uint32_t blocks, hipStream_t stream);
+hipError_t launch_encode6(const EncodeParams& p, Encode5Params q, bool cold, bool lean, uint32_t blocks, hipStream_t stream);
 // compact: the depth at which the walks of a trip are compacted (0: never; 4 .. 8; encode5.hip: Walk5)
-hipError_t launch_encode5(const EncodeParams& p, Encode5Params q, bool cold, int ppl, bool long_tokens, int compact, int waves, uint32_t blocks,
-                          uint32_t min_lds, hipStream_t stream);
+hipError_t launch_encode5(const EncodeParams& p, Encode5Params q, bool cold, int ppl, bool long_tokens, int compact, bool lean, bool step_ok,
+                          int waves, uint32_t blocks, uint32_t min_lds, hipStream_t stream);
 hipError_t launch_encode2(const EncodeParams& p, uint32_t num_cus, bool permuted, hipStream_t stream);   // encode2.hip
 hipError_t launch_trace32(const EncodeParams& p, uint32_t blocks, bool permuted, hipStream_t stream);
 hipError_t launch_encode4l(const EncodeParams& p, uint32_t num_cus, hipStream_t stream);  // encode4l.hip

@@ -29,6 +29,7 @@
 #include "front.h"
 #include "kernels.h"
 #include "layout.h"
+#include "lean_gate.h"
 #include "spans.h"
 #include "nbest.h"
 #include "sample.h"
@@ -280,6 +281,8 @@ struct tgx_model {
     std::vector<double> value_coverage;  // [k]: expected share of the matches whose value has rank <= k
     uint32_t n_values = 0, root_base8 = 0;
     uint32_t last_n_hot = 0;           // values in the LDS copy of the last encode5 launch
+    bool lean_scores_ok = false;       // every score passes the gate of the lean relaxation step (lean_gate.h)
+    uint32_t last_lean_items = 0;      // lean items of the last pass's encode5_kernel (low byte) and encode6_kernel (next byte); 0: the kernels as they were
     bool have_trie8 = false;
     bool encode_tables_ready = false;  // tokhash / trie8 built and uploaded (ensure_encode_tables)
     bool estep_trie8_tried = false;    // ensure_estep_trie8 ran
@@ -700,6 +703,7 @@ tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64
         fprintf(stderr, "[tgx] encode: S=%llu N=%llu lm=%u path=%s slots=%zu root_base=%u values=%u\n",
                 (unsigned long long)c->n_samples, (unsigned long long)c->n_bytes, p.lm, use4 ? (use5 ? "rows5" : "rows4") : (use2 ? "rows2" : "fused"),
                 m->flat.table.size(), p.root_base, m->n_values);
+    m->last_lean_items = 0;
     if (use5) {
         {
             const tgx_status rst = ensure_value_ranks(m, c);
@@ -832,9 +836,15 @@ tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64
         // the depth at which a trip's live walks are packed into fewer lanes (encode5.hip: Walk5)
         int compact = kE5CompactDepth;
         if (const char* e = knob("TGX_E5_COMPACT")) compact = (strcmp(e, "off") == 0 || atoi(e) == 0) ? 0 : std::min(8, std::max(4, atoi(e)));
+        // the lean relaxation step (device_common.h: relax5_lean_step) for models whose scores pass
+        // the gate (lean_gate.h); TGX_E5_LEAN=0: the kernels as they were
+        // (the gate is the lean STEP's: a model that fails it runs the lean builds without the step)
+        bool lean = tgx::encode5_has_lean(dropout > 0.0, long_tokens);
+        if (const char* e = knob("TGX_E5_LEAN")) lean = lean && atoi(e) != 0;
+        const bool step_ok = m->lean_scores_ok;
         {
             int ps4 = 0;
-            HIP_TRY(tgx::encode5_waves_per_simd(dropout > 0.0, false, 4, long_tokens, compact, &ps4));
+            HIP_TRY(tgx::encode5_waves_per_simd(dropout > 0.0, false, 4, long_tokens, compact, lean, step_ok, &ps4));
             hot_waves = std::min(16, ps4 * 4);
             const int least = long_tokens ? 12 : 13;  // (the long-token build has four positions per lane only)
             while (hot_waves >= least && m->n_values > tgx::encode5_max_hot(long_tokens, hot_waves, 4, 160u * 1024u)) hot_waves--;
@@ -882,12 +892,12 @@ tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64
         const uint32_t budget = 160u * 1024u / (uint32_t)bpc;
         bool cold = false;
         int per_simd = 0;
-        HIP_TRY(tgx::encode5_waves_per_simd(dropout > 0.0, false, ppl, long_tokens, compact, &per_simd));
+        HIP_TRY(tgx::encode5_waves_per_simd(dropout > 0.0, false, ppl, long_tokens, compact, lean, step_ok, &per_simd));
         int waves = std::min(16, (per_simd / bpc) * 4);
         if ((ppl == 4 || ppl == 3) && bpc == 1 && hot_waves > 0) waves = std::min(waves, hot_waves);
         if (m->n_values > tgx::encode5_max_hot(long_tokens, waves, ppl, budget)) {
             cold = true;
-            HIP_TRY(tgx::encode5_waves_per_simd(dropout > 0.0, true, ppl, long_tokens, compact, &per_simd));
+            HIP_TRY(tgx::encode5_waves_per_simd(dropout > 0.0, true, ppl, long_tokens, compact, lean, step_ok, &per_simd));
             waves = std::min(16, (per_simd / bpc) * 4);
         }
         if (balance_waves > 0 && ppl == 4 && bpc == 1) waves = std::min(waves, balance_waves);
@@ -898,6 +908,9 @@ tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64
         n_hot = knob_cap_hot("TGX_E5_HOT", n_hot);
         cold = n_hot < m->n_values;
         m->last_n_hot = n_hot;
+        // (self-check) the lean items of this pass's kernels: encode5_kernel's in the low byte, encode6_kernel's in the next
+        m->last_lean_items = !lean ? 0u : ((rest_n ? (uint32_t)tgx::encode5_lean_items(cold, ppl, step_ok) : 0u) |
+                                           (n_long ? (uint32_t)tgx::encode6_lean_items() << 8 : 0u));
         // whole blocks only: a block's waves are dealt round-robin to the SIMDs, ceil(waves / 4) on the fullest
         m->last_encode_waves_per_cu = std::min(bpc, per_simd / ((waves + 3) / 4)) * waves;
         const uint64_t rows_per_block = 4 * (uint64_t)waves;
@@ -925,7 +938,7 @@ tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64
             q6.pool = cold6 ? pool6 : 0u;
             if (!corun_cus) {
                 time_begin(m, "encode6_kernel");
-                HIP_TRY(tgx::launch_encode6(p6, q6, cold6, blocks6, m->stream));
+                HIP_TRY(tgx::launch_encode6(p6, q6, cold6, lean, blocks6, m->stream));
                 time_end(m);
                 HIP_TRY(hipMemsetAsync(&m->d_ctrl->queue, 0x00, 8, m->stream));  // the work queue, for encode5_kernel
             } else {
@@ -955,7 +968,7 @@ tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64
                 HIP_TRY(hipMemsetAsync(&m->d_ctrl->encode_redo, 0x00, 8, m->stream));
             }
             // (co-run: more than half of the CU's LDS, so that no block of the long-sample kernel shares the CU)
-            const hipError_t le = tgx::launch_encode5(p, q, cold, ppl, long_tokens, compact, waves, blocks5, corun_cus && n_long ? 84u * 1024u : 0u, m->stream);
+            const hipError_t le = tgx::launch_encode5(p, q, cold, ppl, long_tokens, compact, lean, step_ok, waves, blocks5, corun_cus && n_long ? 84u * 1024u : 0u, m->stream);
             if (le != hipSuccess) return fail(TGX_ERR_DEVICE, "encode5 launch failed: %s", hipGetErrorString(le));
         }
         bool joined = false, joined_slot = false;
@@ -976,7 +989,7 @@ tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64
                 }
                 if (timed_out && *started < blocks5) m->corun_wait_timeouts++;
             }
-            const hipError_t l6 = tgx::launch_encode6(p6, q6, cold6, blocks6, m->stream2);
+            const hipError_t l6 = tgx::launch_encode6(p6, q6, cold6, lean, blocks6, m->stream2);
             if (slot) (void)hipEventRecord(m->timed[m->n_timed + 1].stop, m->stream2);
             (void)hipEventRecord(m->ev_join, m->stream2);
             if (l6 != hipSuccess) return fail(TGX_ERR_DEVICE, "encode6 launch failed: %s", hipGetErrorString(l6));
@@ -1338,6 +1351,7 @@ static tgx_status finish_model_create(tgx_model* m, const uint8_t* bytes, const 
         m->vocab_scores.assign(scores, scores + vocab_size);
         for (uint32_t i = 0; i < vocab_size; i++)
             if (!(scores[i] - scores[i] == 0.0)) m->scores_finite = false;  // inf or NaN
+        m->lean_scores_ok = tgx::lean_scores_ok(scores, vocab_size);
     } else {
         m->vocab_offs.assign(1, 0);
     }
@@ -4630,3 +4644,4 @@ uint32_t tgx_last_encode_corun_cus(const tgx_model* m) { return m ? m->last_coru
 uint32_t tgx_encode_corun_timeouts(const tgx_model* m) { return m ? m->corun_wait_timeouts : 0; }
 uint32_t tgx_model_score_values(const tgx_model* m) { return m && m->have_trie8 ? m->n_values : 0u; }
 uint32_t tgx_last_encode_hot_values(const tgx_model* m) { return m ? m->last_n_hot : 0u; }
+uint32_t tgx_last_encode_lean_items(const tgx_model* m) { return m ? m->last_lean_items : 0u; }
