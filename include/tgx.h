@@ -446,6 +446,52 @@ tgx_status tgx_front_host(const uint8_t *text, const uint64_t *offs, uint64_t n_
                           int32_t **seg_special, uint64_t *n_segments, uint8_t **out_text, uint64_t **out_offs,
                           uint64_t *n_encoded);
 
+/* ---- Unicode normalisation on the device: a resident corpus to a resident corpus (csrc/norm.hip) -----------------
+ * What tgx_normalize_segments computes on host threads, for a corpus that is already in HBM.
+ *
+ * tgx_corpus_normalize(c, form, &out, &n_pieces).  form as tgx_normalize_segments: 0 NFD, 1 NFC, 2 NFKD, 3 NFKC.  With E
+ * rows in c, *out is a resident corpus of E rows on c's device, and row k holds exactly the bytes tgx_normalize_segments
+ * produces for row k.
+ *   Units.  A row is read as units by the strict UTF-8 decoder of csrc/unicode_norm.cpp (no overlong forms, no
+ *   surrogates, <= 0x10FFFF): a unit is a scalar value, or an offending byte that travels alone as a raw byte.  Decoding
+ *   is bounded by the row's end, so a UTF-8 sequence cut by a row end is raw bytes on both sides.  Raw bytes are never
+ *   changed and nothing combines with them.
+ *   Active units.  Under a form a scalar value cp is ACTIVE when ccc(cp) != 0, or normalising cp alone under the form
+ *   changes it, or (NFC and NFKC only) cp is the second of a primary composition pair, a Hangul V jamo (U+1161..U+1175)
+ *   or a Hangul T jamo (U+11A8..U+11C2).  Everything else is INERT: raw bytes, all of ASCII, and the rest.  With the
+ *   Unicode 13.0.0 data of csrc/unicode_tables.h: 14 101 active scalar values under NFD, 2 060 under NFC, 17 776 under
+ *   NFKD, 5 747 under NFKC.  The property is built once per process from that data and the normaliser itself, as a
+ *   two-stage table over cp >> 8 whose block 0 is "all inert", and uploaded once per device.
+ *   Pieces.  A piece starts at a HEAD: an inert unit whose next unit in the same row is active, or an active unit that
+ *   is the first of its row.  It runs through the active units that follow the head.  Every byte outside a piece is
+ *   copied verbatim; every piece is replaced by its normalisation in isolation.  Pieces never cross rows.
+ *   Window.  One thread normalises a piece as a stream and keeps only the decomposed stream since its last starter: one
+ *   starter and the non-starters after it.  A source scalar's full decomposition is fed one scalar at a time; a
+ *   non-starter is appended to the window; on a starter the window's marks are put in canonical order (a stable sort by
+ *   class) and, for the composed forms, composed as tgx_normalize_segments composes them; if the window is then a single
+ *   starter that composes with the new one, the composite replaces it; otherwise the window is emitted and a new one
+ *   starts with the starter.  The window holds 32 scalars (a starter and 31 non-starters; UAX #15 Stream-Safe text has
+ *   at most 30 non-starters in a row, and one scalar's decomposition adds at most 3).  A row that needs more is refused.
+ *   Result.  *out is an ordinary corpus, built as tgx_corpus_split_specials builds *segs: only the E + 1 offsets and
+ *   three counters visit the host.  Row count and row order are kept and no non-empty row becomes empty, so dropout and
+ *   sampling hash the same (seed, row, position) as the host route.  *n_pieces = the number of pieces; with 0 pieces the
+ *   output is a device-to-device copy.  E = 0 or no bytes: TGX_OK and a copy.
+ * Errors, before anything is queued: TGX_ERR_INVALID for NULL arguments and for form > 3.  After the length pass, with
+ *   nothing returned: TGX_ERR_UNSUPPORTED for a window overflow (tgx_last_error names the limit; the sample of
+ *   tgx_last_error_detail is the LOWEST offending row, a device minimum, so it does not depend on timing).
+ * c is only read and the call holds the corpus's lock.  Stream rule and device restoration: those of
+ *   tgx_corpus_split_specials.
+ *
+ * tgx_normalize_host is the host twin over host arrays (offs u64[n_rows + 1], offs[0] = 0), no device: the kernels'
+ *   tiles, thread slots and pieces through the same decoder, stream machine and index arithmetic (csrc/norm.h); the same
+ *   limit and the same error.  *out_text (at least one byte) and *out_offs (u64[n_rows + 1]) are malloc'd (tgx_free).
+ * tgx_norm_last_times: device milliseconds of the calling thread's last tgx_corpus_normalize, per stage (mark, pieces,
+ *   length, places, write), as tgx_front_last_times.  For tools/norm_bench.py. */
+tgx_status tgx_corpus_normalize(tgx_corpus *c, uint32_t form, tgx_corpus **out, uint64_t *n_pieces);
+tgx_status tgx_normalize_host(uint32_t form, const uint8_t *text, const uint64_t *offs, uint64_t n_rows,
+                              uint8_t **out_text, uint64_t **out_offs, uint64_t *n_pieces);
+int tgx_norm_last_times(const char **names, float *ms, int cap);
+
 /* ---- decode on the device: a result's ids or a padded id tensor to UTF-8 text (csrc/decode.hip) -------------------
  * What tgx_decode_batch computes, with ids, text and row offsets all in HBM.
  *

@@ -152,6 +152,9 @@ SYMBOLS = {
     "tgx_corpus_copy_text": (_i, [_vp, _vp, _u64]),
     "tgx_corpus_copy_offsets": (_i, [_vp, _vp, _u64]),
     "tgx_front_host": (_i, [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _vp, _pvp, _pu64, _pvp, _pvp, _pu64]),
+    "tgx_corpus_normalize": (_i, [_vp, _u32, _pvp, _pu64]),
+    "tgx_normalize_host": (_i, [_u32, _vp, _vp, _u64, _pvp, _pvp, _pu64]),
+    "tgx_norm_last_times": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_float), _i]),
 }
 
 
@@ -413,6 +416,36 @@ def front_last_times() -> dict[str, float]:
     """Device milliseconds per stage of this thread's last NativeCorpus.split_specials (tgx_front_last_times)."""
     names, ms = (C.c_char_p * 8)(), (C.c_float * 8)()
     n = lib.tgx_front_last_times(names, ms, 8)
+    return {names[k].decode(): float(ms[k]) for k in range(n)}
+
+
+def _check_norm(status: int) -> None:
+    """check(), with the row of a window overflow (ERR_UNSUPPORTED: tgx_last_error_detail's sample) on the exception."""
+    if status == ERR_UNSUPPORTED:
+        msg = (lib.tgx_last_error() or b"").decode("utf-8", "replace")
+        s, p, l = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        lib.tgx_last_error_detail(C.byref(s), C.byref(p), C.byref(l))
+        raise TokenGeeXError(msg, status, s.value)
+    check(status)
+
+
+def normalize_host_twin(form: str, flat: np.ndarray, offs: np.ndarray):
+    """Host twin of NativeCorpus.normalize (tgx_normalize_host: the kernels' decoder, stream machine and index arithmetic,
+    no device) over a packed batch (offs from 0) -> (flat, offsets u64[S+1], the number of pieces): normalize_flat's
+    bytes.  A row whose stream window overflows raises ERR_UNSUPPORTED with the lowest such row as .sample."""
+    flat = np.ascontiguousarray(flat, dtype=np.uint8)
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    n = offs.shape[0] - 1
+    ot, oo, k = C.c_void_p(), C.c_void_p(), C.c_uint64()
+    _check_norm(lib.tgx_normalize_host(NORMAL_FORMS[form], ptr(flat) if flat.size else None, ptr(offs), n, C.byref(ot), C.byref(oo), C.byref(k)))
+    out_offs = _take(oo, n + 1, C.c_uint64, np.uint64)
+    return _take(ot, int(out_offs[-1]), C.c_uint8, np.uint8), out_offs, k.value
+
+
+def norm_last_times() -> dict[str, float]:
+    """Device milliseconds per stage of this thread's last NativeCorpus.normalize (tgx_norm_last_times)."""
+    names, ms = (C.c_char_p * 8)(), (C.c_float * 8)()
+    n = lib.tgx_norm_last_times(names, ms, 8)
     return {names[k].decode(): float(ms[k]) for k in range(n)}
 
 
@@ -983,6 +1016,19 @@ class NativeCorpus:
         c._h = hc
         c.device = self.device
         return c, NativePlan(hp)
+
+    def normalize(self, form: str) -> "NativeCorpus":
+        """The corpus under a Unicode normalisation form ("nfd", "nfc", "nfkd", "nfkc") on the device (tgx_corpus_normalize,
+        csrc/norm.hip) -> a resident corpus of the same rows with normalize_flat's bytes; .n_pieces says how many stretches
+        were rewritten (0: a device-to-device copy).  This corpus is only read.  A row whose stream window overflows raises
+        ERR_UNSUPPORTED with the lowest such row as .sample."""
+        hc, k = C.c_void_p(), C.c_uint64()
+        _check_norm(lib.tgx_corpus_normalize(self._h, NORMAL_FORMS[form], C.byref(hc), C.byref(k)))
+        c = NativeCorpus.__new__(NativeCorpus)
+        c._h = hc
+        c.device = self.device
+        c.n_pieces = k.value
+        return c
 
 
 class NativeModel:

@@ -17,6 +17,7 @@ tgx_status tgx_set_error(tgx_status st, const char* msg);
 namespace tgx {
 struct DecodeSlot;   // decode.h
 struct FrontTables;  // front.h
+struct NormTables;   // norm.h
 }
 
 namespace tgx::host {
@@ -72,5 +73,18 @@ struct FrontHostTables {
 tgx::FrontTables front_tables(const FrontHostTables& t, const uint32_t* first_mask, const uint32_t* first_start, const uint32_t* by_first,
                               const uint32_t* sp_offs, const uint8_t* sp_bytes);
 tgx_status front_build_tables(const char* who, const uint8_t* special_bytes, const uint64_t* special_offs, uint32_t n_specials, FrontHostTables* t);
+// the normaliser's tables over host memory (norm.h: NormTables; the data of unicode_tables.h and the two-stage activity
+// table made from it), built once per process; sizes in bytes of what tgx_corpus_normalize uploads once per device
+struct NormHostTables {
+    std::vector<uint16_t> stage1;
+    std::vector<uint8_t> stage2;
+    uint64_t n_active[4] = {0, 0, 0, 0};  // active scalar values per form
+    size_t ccc_cp_bytes = 0, ccc_val_bytes = 0, canon_cp_bytes = 0, canon_off_bytes = 0, canon_len_bytes = 0, canon_seq_bytes = 0, compat_cp_bytes = 0,
+           compat_off_bytes = 0, compat_len_bytes = 0, compat_seq_bytes = 0, pair_bytes = 0;
+};
+const NormHostTables& norm_host_tables();
+const tgx::NormTables& norm_tables_on_host();
+// TGX_ERR_UNSUPPORTED for a row whose stream window overflows, with its error detail
+tgx_status norm_overflow(const char* who, uint64_t row);
 
 }  // namespace tgx::host

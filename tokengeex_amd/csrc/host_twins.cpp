@@ -1,7 +1,8 @@
 // The *_host twins of the result-side device entry points (include/tgx.h): tgx_layout_pad_host, tgx_layout_pack_host,
-// tgx_layout_windows_host, tgx_assemble_host, tgx_decode_rows_host, tgx_spans_host, tgx_window_spans_host and tgx_front_host, and the
+// tgx_layout_windows_host, tgx_assemble_host, tgx_decode_rows_host, tgx_spans_host, tgx_window_spans_host, tgx_front_host and
+// tgx_normalize_host, and the
 // argument checks they share with the device entry points of tgx_api.cpp.  A twin goes through the same index arithmetic as its kernels (layout.h, assemble.h,
-// decode.h, spans.h, front.h) on host memory.  Nothing in this file calls a HIP function, so it builds and runs without the
+// decode.h, spans.h, front.h, norm.h) on host memory.  Nothing in this file calls a HIP function, so it builds and runs without the
 // handles, the pool or a device.
 #include <algorithm>
 #include <cstdlib>
@@ -13,7 +14,9 @@
 #include "decode.h"
 #include "front.h"
 #include "layout.h"
+#include "norm.h"
 #include "spans.h"
+#include "unicode_tables.h"
 
 using namespace tgx::host;
 
@@ -569,6 +572,199 @@ tgx_status tgx_front_host(const uint8_t* text, const uint64_t* offs, uint64_t n_
     *out_text = ot;
     *out_offs = oo;
     *n_encoded = E;
+    return TGX_OK;
+}
+
+// ---- Unicode normalisation --------------------------------------------------------
+
+namespace tgx::host {
+
+namespace {
+// the normaliser's data of unicode_tables.h behind an activity table (norm.h: NormTables' order)
+tgx::NormTables norm_tables_over(const uint16_t* stage1, const uint8_t* stage2) {
+    return {stage1,     stage2,     kCccCp,     kCccVal,     kCanonCp,       kCanonOff, kCanonSeq, kCanonLen, kCompatCp, kCompatOff,
+            kCompatSeq, kCompatLen, kPairFirst, kPairSecond, kPairComposite, kCccN,     kCanonN,   kCompatN,  kPairN};
+}
+}  // namespace
+
+const tgx::NormTables& norm_tables_on_host() {
+    static const tgx::NormTables tab = norm_tables_over(norm_host_tables().stage1.data(), norm_host_tables().stage2.data());
+    return tab;
+}
+
+// The activity of every scalar value (include/tgx.h: tgx_corpus_normalize), from the data of unicode_tables.h and the
+// stream machine itself: a scalar that has no decomposition and is no Hangul syllable goes through the machine unchanged.
+const NormHostTables& norm_host_tables() {
+    static const NormHostTables tables = [] {
+        NormHostTables h;
+        h.ccc_cp_bytes = sizeof(kCccCp);
+        h.ccc_val_bytes = sizeof(kCccVal);
+        h.canon_cp_bytes = sizeof(kCanonCp);
+        h.canon_off_bytes = sizeof(kCanonOff);
+        h.canon_len_bytes = sizeof(kCanonLen);
+        h.canon_seq_bytes = sizeof(kCanonSeq);
+        h.compat_cp_bytes = sizeof(kCompatCp);
+        h.compat_off_bytes = sizeof(kCompatOff);
+        h.compat_len_bytes = sizeof(kCompatLen);
+        h.compat_seq_bytes = sizeof(kCompatSeq);
+        h.pair_bytes = sizeof(kPairFirst);
+        const tgx::NormTables tab = norm_tables_over(nullptr, nullptr);  // the machine needs no activity table for a scalar alone
+        std::vector<uint8_t> act(0x110000, 0);
+        auto changes_alone = [&](uint32_t cp, uint32_t form) {
+            uint32_t wcp[tgx::kNormWindow];
+            uint8_t wcc[tgx::kNormWindow], out[128], self[4];
+            tgx::NormStream s = {wcp, wcc, 1, out}, id = {wcp, wcc, 1, self};
+            tgx::norm_emit(id, cp);
+            const tgx::NormDecomp d = tgx::norm_decompose(tab, cp, (form & 2u) != 0);
+            for (uint32_t k = 0; k < d.n; k++) tgx::norm_feed(tab, s, tgx::norm_decomp_at(d, k), (form & 1u) != 0);  // (at most 18 scalars of 4 bytes)
+            tgx::norm_finalize(tab, s, (form & 1u) != 0);
+            tgx::norm_flush(s);
+            return s.produced != id.produced || memcmp(out, self, (size_t)id.produced) != 0;
+        };
+        for (uint32_t form = 0; form < 4; form++) {
+            const uint8_t bit = (uint8_t)(1u << form);
+            for (uint32_t k = 0; k < kCccN; k++) act[kCccCp[k]] |= bit;
+            const uint32_t* cps = (form & 2u) ? kCompatCp : kCanonCp;
+            const uint32_t n = (form & 2u) ? kCompatN : kCanonN;
+            for (uint32_t k = 0; k < n; k++)
+                if (changes_alone(cps[k], form)) act[cps[k]] |= bit;
+            for (uint32_t cp = tgx::norm_hangul::S_BASE; cp < tgx::norm_hangul::S_BASE + tgx::norm_hangul::S_COUNT; cp++)
+                if (changes_alone(cp, form)) act[cp] |= bit;
+            if (form & 1u) {
+                for (uint32_t k = 0; k < kPairN; k++) act[kPairSecond[k]] |= bit;
+                for (uint32_t cp = 0x1161; cp <= 0x1175; cp++) act[cp] |= bit;
+                for (uint32_t cp = 0x11A8; cp <= 0x11C2; cp++) act[cp] |= bit;
+            }
+            for (uint32_t cp = 0; cp < 0x110000; cp++) h.n_active[form] += (act[cp] >> form) & 1u;
+        }
+        h.stage1.assign(tgx::kNormStage1, 0);
+        h.stage2.assign(256, 0);  // block 0: all inert
+        for (uint32_t b = 0; b < tgx::kNormStage1; b++) {
+            const uint8_t* blk = act.data() + (size_t)b * 256;
+            if (std::all_of(blk, blk + 256, [](uint8_t x) { return x == 0; })) continue;
+            h.stage1[b] = (uint16_t)(h.stage2.size() / 256);
+            h.stage2.insert(h.stage2.end(), blk, blk + 256);
+        }
+        return h;
+    }();
+    return tables;
+}
+
+tgx_status norm_overflow(const char* who, uint64_t row) {
+    set_error_detail(row, 0, 0);
+    return fail(TGX_ERR_UNSUPPORTED, "%s: row %llu needs a stream window of more than %u scalars (a starter and %u non-starters; UAX #15 Stream-Safe text has at most 30 non-starters in a row)",
+                who, (unsigned long long)row, tgx::kNormWindow, tgx::kNormWindow - 1);
+}
+
+}  // namespace tgx::host
+
+tgx_status tgx_normalize_host(uint32_t form, const uint8_t* text, const uint64_t* offs, uint64_t n_rows, uint8_t** out_text, uint64_t** out_offs,
+                              uint64_t* n_pieces) {
+    const char* who = "tgx_normalize_host";
+    if (!out_text || !out_offs || !n_pieces) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
+    *out_text = nullptr;
+    *out_offs = nullptr;
+    *n_pieces = 0;
+    if (form > 3) return fail(TGX_ERR_INVALID, "%s: form must be 0 (NFD), 1 (NFC), 2 (NFKD) or 3 (NFKC)", who);
+    tgx_status st = check_packed_list(who, "offs", "offsets", offs, n_rows, true);
+    if (st != TGX_OK) return st;
+    const uint64_t S = n_rows, N = offs[S];
+    if (N && !text) return fail(TGX_ERR_INVALID, "%s: text is NULL", who);
+    const tgx::NormTables& tab = norm_tables_on_host();
+    const uint64_t tiles = (N + tgx::kFrontTile - 1) / tgx::kFrontTile, slots = (N + tgx::kFrontGroup - 1) / tgx::kFrontGroup;
+    // mark: as the kernel, tile by tile and slot by slot
+    std::vector<uint32_t> mask(slots), slot_pre(slots);
+    std::vector<uint64_t> tile_base(tiles + 1, 0), tile_place(tiles + 1, 0), row_lo(tiles), row_hi(tiles);
+    for (uint64_t tile = 0; tile < tiles; tile++) {
+        const uint64_t t0 = tile * tgx::kFrontTile, last = tgx::front_tile_last(t0, N);
+        row_lo[tile] = tgx::front_find_sample(offs, 0, S - 1, t0);
+        row_hi[tile] = tgx::front_find_sample(offs, 0, S - 1, last);
+        uint64_t count = 0;
+        for (uint64_t p0 = t0; p0 <= last; p0 += tgx::kFrontGroup) {
+            const uint32_t n_in = N - p0 < tgx::kFrontGroup ? (uint32_t)(N - p0) : tgx::kFrontGroup;
+            uint8_t v[tgx::kFrontGroup] = {};
+            memcpy(v, text + p0, n_in);
+            const uint32_t m = tgx::norm_mark_slot(tab, form, text, offs, row_lo[tile], row_hi[tile], p0, n_in, v,
+                                                   p0 + tgx::kFrontGroup < N ? text[p0 + tgx::kFrontGroup] : 0);
+            mask[p0 / tgx::kFrontGroup] = m;
+            count += tgx::front_popc(m >> 16);
+        }
+        tile_base[tile + 1] = tile_base[tile] + count;
+    }
+    const uint64_t P = tile_base[tiles];
+    uint64_t* oo = static_cast<uint64_t*>(malloc(sizeof(uint64_t) * (S + 1)));
+    if (!oo) return fail(TGX_ERR_INVALID, "%s: out of host memory", who);
+    if (P == 0) {  // nothing to rewrite: a copy
+        uint8_t* ot = static_cast<uint8_t*>(malloc((size_t)std::max<uint64_t>(1, N)));
+        if (!ot) {
+            free(oo);
+            return fail(TGX_ERR_INVALID, "%s: out of host memory", who);
+        }
+        if (N) memcpy(ot, text, (size_t)N);
+        memcpy(oo, offs, sizeof(uint64_t) * (S + 1));
+        *out_text = ot;
+        *out_offs = oo;
+        return TGX_OK;
+    }
+    // pieces
+    std::vector<uint64_t> piece_begin(P), piece_row(P), piece_sum(P + 1, 0);
+    for (uint64_t tile = 0; tile < tiles; tile++) {
+        uint64_t at = tile_base[tile];
+        const uint64_t t0 = tile * tgx::kFrontTile, last = tgx::front_tile_last(t0, N);
+        for (uint64_t p0 = t0; p0 <= last; p0 += tgx::kFrontGroup) {
+            const uint32_t heads = mask[p0 / tgx::kFrontGroup] >> 16;
+            if (heads) tgx::norm_write_pieces(offs, row_lo[tile], row_hi[tile], p0, heads, at, piece_begin.data(), piece_row.data());
+            at += tgx::front_popc(heads);
+        }
+    }
+    // length
+    uint32_t wcp[tgx::kNormWindow];
+    uint8_t wcc[tgx::kNormWindow];
+    uint64_t overflow_row = tgx::kNormNoRow;
+    for (uint64_t k = 0; k < P; k++) {
+        tgx::NormStream s = {wcp, wcc, 1, nullptr};
+        tgx::norm_run_piece(tab, form, text, piece_begin[k], offs[piece_row[k] + 1], s);
+        piece_sum[k + 1] = piece_sum[k] + s.produced;
+        if (s.overflow) overflow_row = std::min(overflow_row, piece_row[k]);
+    }
+    if (overflow_row != tgx::kNormNoRow) {
+        free(oo);
+        return norm_overflow(who, overflow_row);
+    }
+    // places
+    for (uint64_t tile = 0; tile < tiles; tile++) {
+        const uint64_t t0 = tile * tgx::kFrontTile, last = tgx::front_tile_last(t0, N);
+        uint32_t copied = 0, heads = 0;
+        for (uint64_t p0 = t0; p0 <= last; p0 += tgx::kFrontGroup) {
+            const uint32_t n_in = N - p0 < tgx::kFrontGroup ? (uint32_t)(N - p0) : tgx::kFrontGroup, m = mask[p0 / tgx::kFrontGroup];
+            slot_pre[p0 / tgx::kFrontGroup] = copied | heads << 16;
+            copied += tgx::front_popc(tgx::norm_verbatim(m, n_in));
+            heads += tgx::front_popc(m >> 16);
+        }
+        tile_place[tile + 1] = tile_place[tile] + tgx::norm_tile_bytes(tile_base.data(), piece_sum.data(), tile, copied);
+    }
+    const tgx::NormPlaces pl = {mask.data(), slot_pre.data(), tile_base.data(), piece_sum.data(), tile_place.data()};
+    const uint64_t total = tile_place[tiles];
+    for (uint64_t r = 0; r <= S; r++) oo[r] = offs[r] < N ? tgx::norm_place(pl, offs[r]) : total;
+    // write
+    uint8_t* ot = static_cast<uint8_t*>(malloc((size_t)std::max<uint64_t>(1, total)));
+    if (!ot) {
+        free(oo);
+        return fail(TGX_ERR_INVALID, "%s: out of host memory", who);
+    }
+    for (uint64_t p0 = 0; p0 < N; p0 += tgx::kFrontGroup) {
+        const uint32_t n_in = N - p0 < tgx::kFrontGroup ? (uint32_t)(N - p0) : tgx::kFrontGroup;
+        uint8_t v[tgx::kFrontGroup] = {};
+        memcpy(v, text + p0, n_in);
+        tgx::norm_copy_slot(pl, p0, n_in, v, ot);
+    }
+    for (uint64_t k = 0; k < P; k++) {
+        tgx::NormStream s = {wcp, wcc, 1, ot + tgx::norm_place(pl, piece_begin[k])};
+        tgx::norm_run_piece(tab, form, text, piece_begin[k], offs[piece_row[k] + 1], s);
+    }
+    *out_text = ot;
+    *out_offs = oo;
+    *n_pieces = P;
     return TGX_OK;
 }
 

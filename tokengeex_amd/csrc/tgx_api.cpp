@@ -32,6 +32,7 @@
 #include "lean_gate.h"
 #include "spans.h"
 #include "nbest.h"
+#include "norm.h"
 #include "sample.h"
 #include "trie_build.h"
 
@@ -2804,7 +2805,7 @@ thread_local float g_front_ms[kFrontStages] = {0, 0, 0, 0, 0};
 
 class FrontTimer {
 public:
-    explicit FrontTimer(hipStream_t hs) : hs_(hs) {
+    explicit FrontTimer(hipStream_t hs, float* ms = g_front_ms) : hs_(hs), ms_(ms) {  // ms: kFrontStages entries
         for (auto& e : ev_) ok_ = ok_ && hipEventCreate(&e) == hipSuccess;
     }
     FrontTimer(const FrontTimer&) = delete;
@@ -2821,13 +2822,14 @@ public:
     }
     void read() {  // after the stream has reached its end
         for (int k = 0; k < kFrontStages; k++) {
-            g_front_ms[k] = 0;
-            if (ok_ && used_[k]) (void)hipEventElapsedTime(&g_front_ms[k], ev_[2 * k], ev_[2 * k + 1]);
+            ms_[k] = 0;
+            if (ok_ && used_[k]) (void)hipEventElapsedTime(&ms_[k], ev_[2 * k], ev_[2 * k + 1]);
         }
     }
 
 private:
     hipStream_t hs_;
+    float* ms_;
     hipEvent_t ev_[2 * kFrontStages] = {};
     bool used_[kFrontStages] = {};
     bool ok_ = true;
@@ -2996,6 +2998,189 @@ tgx_status tgx_corpus_split_specials(tgx_corpus* c, const uint8_t* special_bytes
     timer.read();
     *segs = out.release();
     *plan = pl.release();
+    return TGX_OK;
+}
+
+// ---- Unicode normalisation on the device (norm.hip; norm.h) -------------------------------------------------------
+
+namespace {
+
+// device time of the last tgx_corpus_normalize of this thread, per stage (tgx_norm_last_times)
+const char* const kNormStageNames[kFrontStages] = {"norm_mark", "norm_pieces", "norm_length", "norm_places", "norm_write"};
+thread_local float g_norm_ms[kFrontStages] = {0, 0, 0, 0, 0};
+
+// the normaliser's tables on a device: uploaded by the first call that needs them there and kept for the process
+std::mutex g_norm_mu;
+struct NormDeviceTables {
+    bool ready = false;
+    tgx::NormTables tab = {};
+} g_norm_dev[64];
+
+tgx_status norm_device_tables(int dev, tgx::NormTables* out) {
+    if (dev < 0 || dev >= 64) return fail(TGX_ERR_INVALID, "device %d out of range", dev);
+    std::lock_guard<std::mutex> lk(g_norm_mu);
+    NormDeviceTables& d = g_norm_dev[dev];
+    if (!d.ready) {
+        const NormHostTables& h = norm_host_tables();
+        const tgx::NormTables& t = norm_tables_on_host();
+        const void* src[15] = {t.stage1,    t.stage2,     t.ccc_cp,     t.ccc_val,    t.canon_cp,   t.canon_off,   t.canon_seq,      t.canon_len,
+                               t.compat_cp, t.compat_off, t.compat_seq, t.compat_len, t.pair_first, t.pair_second, t.pair_composite};
+        const size_t bytes[15] = {h.stage1.size() * 2, h.stage2.size(),    h.ccc_cp_bytes,    h.ccc_val_bytes,   h.canon_cp_bytes,
+                                  h.canon_off_bytes,   h.canon_seq_bytes,  h.canon_len_bytes, h.compat_cp_bytes, h.compat_off_bytes,
+                                  h.compat_seq_bytes,  h.compat_len_bytes, h.pair_bytes,      h.pair_bytes,      h.pair_bytes};
+        size_t at[15], total = 0;
+        for (int k = 0; k < 15; k++) {
+            at[k] = total;
+            total += (bytes[k] + 255) & ~(size_t)255;
+        }
+        uint8_t* base = nullptr;
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&base), total));
+        for (int k = 0; k < 15; k++) {
+            const hipError_t e = hipMemcpy(base + at[k], src[k], bytes[k], hipMemcpyHostToDevice);
+            if (e != hipSuccess) {
+                (void)hipFree(base);
+                HIP_TRY(e);
+            }
+        }
+        auto u32 = [&](int k) { return reinterpret_cast<const uint32_t*>(base + at[k]); };
+        d.tab = t;
+        d.tab.stage1 = reinterpret_cast<const uint16_t*>(base + at[0]);
+        d.tab.stage2 = base + at[1];
+        d.tab.ccc_cp = u32(2);
+        d.tab.ccc_val = base + at[3];
+        d.tab.canon_cp = u32(4);
+        d.tab.canon_off = u32(5);
+        d.tab.canon_seq = u32(6);
+        d.tab.canon_len = base + at[7];
+        d.tab.compat_cp = u32(8);
+        d.tab.compat_off = u32(9);
+        d.tab.compat_seq = u32(10);
+        d.tab.compat_len = base + at[11];
+        d.tab.pair_first = u32(12);
+        d.tab.pair_second = u32(13);
+        d.tab.pair_composite = u32(14);
+        d.ready = true;
+    }
+    *out = d.tab;
+    return TGX_OK;
+}
+
+}  // namespace
+
+int tgx_norm_last_times(const char** names, float* ms, int cap) {
+    int n = 0;
+    for (; n < kFrontStages && n < cap; n++) {
+        if (names) names[n] = kNormStageNames[n];
+        if (ms) ms[n] = g_norm_ms[n];
+    }
+    return n;
+}
+
+tgx_status tgx_corpus_normalize(tgx_corpus* c, uint32_t form, tgx_corpus** out, uint64_t* n_pieces) {
+    const char* who = "tgx_corpus_normalize";
+    if (!c || !out || !n_pieces) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
+    *out = nullptr;
+    *n_pieces = 0;
+    if (form > 3) return fail(TGX_ERR_INVALID, "%s: form must be 0 (NFD), 1 (NFC), 2 (NFKD) or 3 (NFKC)", who);
+    tgx_status st = require_device();
+    if (st != TGX_OK) return st;
+    std::lock_guard<std::mutex> lkc(c->mu);
+    DeviceScope scope;
+    const int dev = c->device;
+    HIP_TRY(hipSetDevice(dev));
+    hipStream_t hs = stream_or_default(nullptr, dev);
+    const uint64_t S = c->n_samples, N = c->n_bytes;
+    std::unique_ptr<tgx_corpus> made_owner;  // the new corpus
+    std::vector<uint64_t> h_out_offs;
+    unsigned long long h_count = 0;
+    StreamGuard guard(dev, hs);  // destroyed before them: a failed call's queued work is over before they go
+    FrontTimer timer(hs, g_norm_ms);
+    tgx_corpus* made = nullptr;
+    auto copy_of_c = [&]() -> tgx_status {  // no piece: the same rows, device to device
+        if ((st = corpus_create(who, dev, c->d_text, TextFrom::Device, S ? c->h_offs.data() : nullptr, S, &made)) != TGX_OK) return st;
+        guard.done();
+        timer.read();
+        *out = made;
+        return TGX_OK;
+    };
+    if (S == 0 || N == 0) return copy_of_c();
+
+    tgx::NormParams p = {};
+    p.text = c->d_text;
+    p.offs = c->d_offs;
+    p.n_bytes = N;
+    p.n_rows = S;
+    p.form = form;
+    if ((st = norm_device_tables(dev, &p.tab)) != TGX_OK) return st;
+    const uint64_t tiles = (N + tgx::kFrontTile - 1) / tgx::kFrontTile, slots = (N + tgx::kFrontGroup - 1) / tgx::kFrontGroup;
+    void* d_scan = nullptr;
+    size_t scan_bytes = 0;
+    uint64_t scan_n = 0;
+    auto scan_room = [&](uint64_t n) -> tgx_status {
+        if (n <= scan_n) return TGX_OK;
+        if (tgx::norm_scan_temp_bytes(n, &scan_bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan temp-size query failed");
+        HIP_TRY(guard.alloc(scan_bytes, &d_scan));  // (never NULL: that asks the scan for its size)
+        scan_n = n;
+        return TGX_OK;
+    };
+    auto count_at = [&](const uint64_t* d, uint64_t* v) -> tgx_status {  // one counter to the host
+        HIP_TRY(hipMemcpyAsync(&h_count, d, 8, hipMemcpyDeviceToHost, hs));
+        HIP_TRY(hipStreamSynchronize(hs));
+        *v = h_count;
+        return TGX_OK;
+    };
+    // mark
+    HIP_TRY(guard.alloc((size_t)slots * 4, &p.mask));
+    HIP_TRY(guard.alloc((size_t)(tiles + 1) * 8, &p.tile_count));
+    HIP_TRY(guard.alloc((size_t)(tiles + 1) * 8, &p.tile_base));
+    if ((st = scan_room(tiles + 1)) != TGX_OK) return st;
+    timer.begin(0);
+    HIP_TRY(tgx::launch_norm_mark(p, d_scan, scan_bytes, hs));
+    timer.end(0);
+    uint64_t P = 0, overflow_row = tgx::kNormNoRow;
+    if ((st = count_at(p.tile_base + tiles, &P)) != TGX_OK) return st;
+    if (P == 0) return copy_of_c();
+    // pieces, their lengths
+    p.n_pieces = P;
+    HIP_TRY(guard.alloc((size_t)P * 8, &p.piece_begin));
+    HIP_TRY(guard.alloc((size_t)P * 8, &p.piece_row));
+    HIP_TRY(guard.alloc((size_t)(P + 1) * 8, &p.piece_len));
+    HIP_TRY(guard.alloc((size_t)(P + 1) * 8, &p.piece_sum));
+    HIP_TRY(guard.alloc(8, &p.overflow_row));
+    if ((st = scan_room(P + 1)) != TGX_OK) return st;
+    timer.begin(1);
+    HIP_TRY(tgx::launch_norm_pieces(p, hs));
+    timer.end(1);
+    timer.begin(2);
+    HIP_TRY(tgx::launch_norm_length(p, d_scan, scan_bytes, hs));
+    timer.end(2);
+    if ((st = count_at(p.overflow_row, &overflow_row)) != TGX_OK) return st;
+    if (overflow_row != tgx::kNormNoRow) {
+        guard.done();  // (the stream has reached its end)
+        return norm_overflow(who, overflow_row);
+    }
+    // places: the S + 1 offsets visit the host for the corpus's longest-first order
+    HIP_TRY(guard.alloc((size_t)slots * 4, &p.slot_pre));
+    HIP_TRY(guard.alloc((size_t)(tiles + 1) * 8, &p.tile_bytes));
+    HIP_TRY(guard.alloc((size_t)(tiles + 1) * 8, &p.tile_place));
+    HIP_TRY(guard.alloc((size_t)(S + 1) * 8, &p.out_offs));
+    timer.begin(3);
+    HIP_TRY(tgx::launch_norm_places(p, d_scan, scan_bytes, hs));
+    timer.end(3);
+    h_out_offs.resize(S + 1);
+    HIP_TRY(hipMemcpyAsync(h_out_offs.data(), p.out_offs, (size_t)(S + 1) * 8, hipMemcpyDeviceToHost, hs));
+    HIP_TRY(hipStreamSynchronize(hs));
+    if ((st = corpus_create(who, dev, nullptr, TextFrom::Caller, h_out_offs.data(), S, &made)) != TGX_OK) return st;
+    made_owner.reset(made);
+    p.out = made->d_text;
+    timer.begin(4);
+    HIP_TRY(tgx::launch_norm_write(p, hs));
+    timer.end(4);
+    HIP_TRY(hipStreamSynchronize(hs));
+    guard.done();
+    timer.read();
+    *out = made_owner.release();
+    *n_pieces = P;
     return TGX_OK;
 }
 

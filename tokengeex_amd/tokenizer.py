@@ -196,6 +196,9 @@ class Tokenizer:
         self._device = device
         self._native: _lib.NativeModel | None = None
         self.seed: int | None = None  # dropout seed; None = fresh random seed per call
+        # the encode_corpus_* methods normalise on the device (csrc/norm.hip) when asked: [UnicodeProcessor] and
+        # [CrlfProcessor, UnicodeProcessor] are then taken instead of refused (_corpus_front)
+        self.device_unicode = False
         self.add_special_tokens(list(special_tokens or []))
 
     # -- native model (lazy: building it needs the GPU) --
@@ -607,32 +610,58 @@ class Tokenizer:
 
     # -- encode_batch over a corpus that is already resident in HBM (csrc/front.hip) --
     def _corpus_front(self, who: str):
-        """Which device front end a resident corpus takes -> None (no special tokens and no processor: encode_corpus as it
-        is) or the CRLF flag of NativeCorpus.split_specials.  The device front end knows the processor lists [] and
-        [CrlfProcessor]; anything else (a Unicode form, or CRLF twice: "\r\r\n" shows the pass is not idempotent) stays
-        with the flat route."""
+        """Which device front end a resident corpus takes -> (crlf, form).  crlf: None (no special tokens and no CRLF pass:
+        the rows are encoded as they are) or the CRLF flag of NativeCorpus.split_specials; form: None or the Unicode form of
+        NativeCorpus.normalize.  The device front end knows the processor lists [] and [CrlfProcessor] and, with
+        device_unicode, [UnicodeProcessor] and [CrlfProcessor, UnicodeProcessor]; anything else (a Unicode form in front of
+        CRLF, or a processor twice: "\r\r\n" shows the CRLF pass is not idempotent) stays with the flat route."""
         procs = self._processors
-        if len(procs) > 1 or (procs and not isinstance(procs[0], CrlfProcessor)):
+        kinds = [type(p) for p in procs]
+        form = None
+        if self.device_unicode and kinds in ([UnicodeProcessor], [CrlfProcessor, UnicodeProcessor]):
+            form = procs[-1].form
+        elif len(procs) > 1 or (procs and not isinstance(procs[0], CrlfProcessor)):
             raise TokenGeeXError(f"{who}: the device front end takes no processor list but [] and one CrlfProcessor; "
                                  "download the text and use encode_batch_result_flat", _lib.ERR_UNSUPPORTED)
-        if not procs and not self._special_tokens:
-            return None
-        return bool(procs)
+        crlf = bool(procs) and isinstance(procs[0], CrlfProcessor)
+        if not crlf and not self._special_tokens:
+            return None, form
+        return crlf, form
 
-    def _split_corpus(self, corpus: "_lib.NativeCorpus", crlf: bool):
-        return corpus.split_specials([t.encode("utf-8") for t in self._special_tokens], crlf)
+    def _split_corpus(self, corpus: "_lib.NativeCorpus", crlf: bool, form: str | None = None):
+        """The corpus split at the special tokens, its segments CRLF-normalised if asked and then, as _preprocess_flat orders
+        the two, under the Unicode form if one is given -> (the segments' corpus, the plan); the caller frees both.  (A
+        window overflow names the segment, not the sample.)"""
+        segs, plan = corpus.split_specials([t.encode("utf-8") for t in self._special_tokens], crlf)
+        if form is None or not plan.num_encoded:
+            return segs, plan
+        try:
+            return segs.normalize(form), plan
+        except BaseException:
+            plan.free()
+            raise
+        finally:
+            segs.free()
 
     def encode_corpus_result(self, corpus: "_lib.NativeCorpus", dropout: float = 0.0) -> "_lib.NativeResult":
         """encode_batch_result_flat over a corpus that is already in HBM (an upload, or decode_result_text(...).to_corpus()):
         the special-token split and the CRLF processor run on the device (NativeCorpus.split_specials) and the plan is
         assembled from where it is (NativeModel.assemble_plan), so neither the text nor the plan visits the host ->
         NativeResult whose ids() / offsets() are encode_batch_flat's over the same samples.  The caller frees it.  (Without
-        special tokens a sample is hashed for dropout by its index among the non-empty samples.)"""
-        crlf = self._corpus_front("encode_corpus_result")
+        special tokens a sample is hashed for dropout by its index among the non-empty samples.)  With device_unicode a
+        Unicode form behind them runs on the device too (NativeCorpus.normalize); alone and without special tokens it keeps
+        every row, so dropout hashes a sample as the flat route does."""
+        crlf, form = self._corpus_front("encode_corpus_result")
         model = self._model()
-        if crlf is None:
+        if crlf is None and form is None:
             return model.encode_corpus(corpus, dropout, self._seed(dropout))
-        segs_corpus, plan = self._split_corpus(corpus, crlf)
+        if crlf is None:  # every row is kept, so a row is hashed for dropout as the flat route hashes it
+            rows = corpus.normalize(form)
+            try:
+                return model.encode_corpus(rows, dropout, self._seed(dropout))
+            finally:
+                rows.free()
+        segs_corpus, plan = self._split_corpus(corpus, crlf, form)
         segs = None
         try:
             if plan.num_encoded:
@@ -647,13 +676,19 @@ class Tokenizer:
     def encode_corpus_sample_result(self, corpus: "_lib.NativeCorpus", alpha: float, seed: int | None = None, return_logz: bool = False):
         """encode_batch_sample_result_flat over a resident corpus, as encode_corpus_result -> NativeResult [, logz f64[S]: the
         plan is copied to the host only for this sum over a sample's non-special segments]."""
-        crlf = self._corpus_front("encode_corpus_sample_result")
+        crlf, form = self._corpus_front("encode_corpus_sample_result")
         seed = self._sample_seed(seed)
         model = self._model()
-        if crlf is None:
+        if crlf is None and form is None:
             return model.encode_corpus_sample(corpus, alpha, seed, return_logz=return_logz)
+        if crlf is None:
+            rows = corpus.normalize(form)
+            try:
+                return model.encode_corpus_sample(rows, alpha, seed, return_logz=return_logz)
+            finally:
+                rows.free()
         n = corpus.num_samples
-        segs_corpus, plan = self._split_corpus(corpus, crlf)
+        segs_corpus, plan = self._split_corpus(corpus, crlf, form)
         segs, seg_logz = None, np.zeros(0, np.float64)
         try:
             if plan.num_encoded:
