@@ -382,6 +382,69 @@ tgx_status tgx_assemble_host(const uint32_t *ids, const uint64_t *id_offs, uint6
                              uint32_t vocab_size, uint32_t n_specials,
                              uint32_t *out_ids, uint64_t ids_cap, uint64_t *out_offs);
 
+/* ---- fill-in-the-middle on the device: PSM / SPM rows from a result (csrc/fim.hip) ---------------------------------
+ * Code LMs are trained on documents whose tokens are cut into prefix, middle and suffix and re-ordered behind three
+ * sentinels (Bavarian et al. 2022, "Efficient Training of Language Models to Fill in the Middle"): PSM is prefix,
+ * suffix, middle and SPM suffix, prefix, middle.  tgx_result_fim does that to the rows of a result in HBM, between
+ * encode (or the assembly above) and the layouts, so the ids do not visit the host.
+ *
+ * In: a result r with S rows, row i with the tokens t_i[0..n_i); three pairwise distinct sentinel ids PRE, SUF, MID
+ * (prefix_id, suffix_id, middle_id); rate and spm_rate in [0, 1]; seed; first_row.
+ *
+ * The uniform.  tgx_fim_u01(seed, row, draw): x = seed ^ TGX_FIM_SALT ^ row·0x9E3779B97F4A7C15 ^
+ * draw·0xC2B2AE3D27D4EB4F, the three xor-shift / multiply rounds of tgx_dropout_u01, u = (x >> 11) · 2^-53 in f64, so u
+ * lies in [0, 1).
+ *
+ * Row i, with g = first_row + i (all arithmetic on g wraps at 2^64):
+ *   The row is REARRANGED iff n_i >= 1 and u01(seed, g, 0) < rate: rate = 0 rearranges nothing, rate = 1 every
+ *     non-empty row.
+ *   A rearranged row is SPM iff u01(seed, g, 1) < spm_rate, otherwise PSM.
+ *   The cuts are c_d = min(n_i, (uint64_t)(u01(seed, g, d) · (double)(n_i + 1))) for d = 2, 3; a = min(c_2, c_3),
+ *     b = max(c_2, c_3).  The multiplication and the conversion are the plain IEEE f64 operations, so host and device
+ *     agree bit for bit; the clamp is there because the product can round up to n_i + 1.
+ *   prefix = t[0:a), middle = t[a:b), suffix = t[b:n_i); any of them may be empty.
+ *   A PSM row is  PRE prefix SUF suffix MID middle,  an SPM row  PRE SUF suffix MID prefix middle:  n_i + 3 tokens.
+ *   A row that is not rearranged is copied.
+ * first_row makes a shard of a larger batch draw what the whole batch draws: rows [k, S) with first_row = k give the
+ * tail of what all rows give with first_row = 0.
+ *
+ * Out: a new result with S rows, T' = T + 3 · n_applied ids and offsets from 0, on r's device, whose vocabulary size is
+ * max(tgx_result_vocab_size(r), 1 + max(PRE, SUF, MID)) — so a result of ordinary encoding, whose ids are all below V,
+ * takes sentinels at V + k.  r is only read and stays valid; the caller frees both.  Every entry point that takes a
+ * result takes the new one.  An n-best result is accepted: its rows are rows.  S = 0 gives an empty result with
+ * offsets [0].  Optional host outputs: mode (NULL or u8[S]): 0 copied, 1 PSM, 2 SPM; cuts (NULL or u64[2S]): a and b,
+ * (0, 0) for a copied row; n_applied (NULL or u64*).
+ *
+ * TGX_ERR_INVALID, before anything is queued: r or out NULL; rate or spm_rate NaN or outside [0, 1]; a sentinel equal
+ * to TGX_NO_ID; two equal sentinels.  No model is needed.  stream: as in the layouts above — the work is queued on it
+ * (NULL: the library's stream) and the call returns only after the stream has reached its end.  One word visits the
+ * host in between: T', the last of the new offsets, which sizes the id buffer.  The calling thread's current device is
+ * the same after the call as before.
+ *
+ * tgx_fim_host is the host twin over host arrays (ids u32[T], may be NULL when T = 0; offs u64[n_rows + 1]): the same
+ * checks, plus offs[0] = 0 and ascending, every id below vocab_size, vocab_size <= 0xFFFFFFFE and ids_cap >= T'; no
+ * device — it walks the kernel's tiles and thread slots through the same index arithmetic (csrc/fim.h).  out_offs
+ * u64[n_rows + 1]; out_ids may be NULL when T' = 0.
+ *
+ * tgx_result_from_ids makes a result on `device` from host arrays: pre-tokenised corpora are what fill-in-the-middle is
+ * most often applied to, and the layouts and decode become usable on ids that came from elsewhere.  It is checked on
+ * the host as the twin checks its input (TGX_ERR_INVALID); the arrays are copied, the caller keeps its own.
+ *
+ * tgx_fim_last_times: device time of the calling thread's last tgx_result_fim per stage (the offsets' scan, fim_fill_kernel,
+ * fim_info_kernel), as tgx_front_last_times; for tools/fim_bench.py. */
+#define TGX_FIM_SALT 0xA0761D6478BD642FULL
+int tgx_fim_last_times(const char **names, float *ms, int cap);
+double tgx_fim_u01(uint64_t seed, uint64_t row, uint64_t draw);
+tgx_status tgx_result_fim(const tgx_result *r, uint32_t prefix_id, uint32_t suffix_id, uint32_t middle_id, double rate,
+                          double spm_rate, uint64_t seed, uint64_t first_row, void *stream, uint8_t *mode, uint64_t *cuts,
+                          uint64_t *n_applied, tgx_result **out);
+tgx_status tgx_fim_host(const uint32_t *ids, const uint64_t *offs, uint64_t n_rows, uint32_t vocab_size,
+                        uint32_t prefix_id, uint32_t suffix_id, uint32_t middle_id, double rate, double spm_rate,
+                        uint64_t seed, uint64_t first_row, uint32_t *out_ids, uint64_t ids_cap, uint64_t *out_offs,
+                        uint8_t *mode, uint64_t *cuts, uint64_t *n_applied);
+tgx_status tgx_result_from_ids(int device, const uint32_t *ids, const uint64_t *offs, uint64_t n_rows,
+                               uint32_t vocab_size, tgx_result **out);
+
 /* ---- the front end on the device: a resident corpus split at special tokens, CRLF applied (csrc/front.hip) --------
  * What tgx_split_specials and tgx_pack_segments compute on host threads, for a corpus that is already in HBM (an upload,
  * or tgx_corpus_from_text of a decoded text), with the plan kept on the device for tgx_assemble_result_plan: a resident

@@ -155,6 +155,11 @@ SYMBOLS = {
     "tgx_corpus_normalize": (_i, [_vp, _u32, _pvp, _pu64]),
     "tgx_normalize_host": (_i, [_u32, _vp, _vp, _u64, _pvp, _pvp, _pu64]),
     "tgx_norm_last_times": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_float), _i]),
+    "tgx_fim_u01": (_d, [_u64, _u64, _u64]),
+    "tgx_result_fim": (_i, [_vp, _u32, _u32, _u32, _d, _d, _u64, _u64, _vp, _vp, _vp, _pu64, _pvp]),
+    "tgx_fim_host": (_i, [_vp, _vp, _u64, _u32, _u32, _u32, _u32, _d, _d, _u64, _u64, _vp, _u64, _vp, _vp, _vp, _pu64]),
+    "tgx_result_from_ids": (_i, [_i, _vp, _vp, _u64, _u32, _pvp]),
+    "tgx_fim_last_times": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_float), _i]),
 }
 
 
@@ -394,6 +399,42 @@ def assemble_host(seg_offs: np.ndarray, seg_special: np.ndarray, ids: np.ndarray
     check(lib.tgx_assemble_host(ptr(ids) if ids.size else None, ptr(id_offs), n_enc, ptr(seg_offs), ptr(seg_special) if seg_special.size else None,
                                 n, _u32_arg(vocab_size, "vocab_size"), _u32_arg(n_specials, "n_specials"), ptr(out), cap, ptr(out_offs)))
     return out[: int(out_offs[-1])], out_offs
+
+
+def fim_u01(seed: int, row: int, draw: int) -> float:
+    """The uniform of the fill-in-the-middle decisions (tgx_fim_u01), in [0, 1)."""
+    m = 2**64 - 1
+    return lib.tgx_fim_u01(seed & m, row & m, draw & m)
+
+
+def fim_host(ids: np.ndarray, offs: np.ndarray, vocab_size: int, prefix_id: int, suffix_id: int, middle_id: int, *, rate: float = 1.0,
+             spm_rate: float = 0.5, seed: int = 0, first_row: int = 0, ids_cap: int | None = None):
+    """Host twin of NativeResult.fim (tgx_fim_host: the kernels' index arithmetic, no device) over ids u32[T] and offsets
+    u64[S+1] -> (ids u32[T'], offsets u64[S+1], vocab_size, mode u8[S], cuts u64[S, 2], n_applied).  ids_cap: room at
+    the destination (default: what can be needed, T + 3·S)."""
+    ids = np.ascontiguousarray(ids, dtype=np.uint32)
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    n = offs.shape[0] - 1
+    cap = ids.shape[0] + 3 * max(n, 0) if ids_cap is None else int(ids_cap)
+    out = np.empty(max(1, cap), np.uint32)
+    out_offs = np.zeros(max(n, 0) + 1, np.uint64)
+    mode = np.zeros(max(n, 0), np.uint8)
+    cuts = np.zeros((max(n, 0), 2), np.uint64)
+    na = C.c_uint64()
+    pre, suf, mid = (_u32_arg(v, "sentinel id") for v in (prefix_id, suffix_id, middle_id))
+    m = 2**64 - 1
+    check(lib.tgx_fim_host(ptr(ids) if ids.size else None, ptr(offs) if offs.size else None, max(n, 0), _u32_arg(vocab_size, "vocab_size"), pre, suf,
+                           mid, float(rate), float(spm_rate), int(seed) & m, int(first_row) & m, ptr(out), cap, ptr(out_offs),
+                           ptr(mode) if n > 0 else None, ptr(cuts) if n > 0 else None, C.byref(na)))
+    return out[: int(out_offs[-1])], out_offs, max(int(vocab_size), 1 + max(pre, suf, mid)), mode, cuts, na.value
+
+
+def fim_last_times() -> dict[str, float]:
+    """Device time in ms of each stage of the calling thread's last NativeResult.fim (tgx_fim_last_times)."""
+    names = (C.c_char_p * 8)()
+    ms = (C.c_float * 8)()
+    n = lib.tgx_fim_last_times(names, ms, 8)
+    return {names[i].decode(): float(ms[i]) for i in range(n)}
 
 
 def front_host(flat: np.ndarray, offs: np.ndarray, specials: list[bytes], crlf: bool):
@@ -848,6 +889,36 @@ class NativeResult:
         check(lib.tgx_result_window_spans_device(model._h, self._h, ptr(sf) if sf.size else None, ptr(so), n, _u32_arg(row_len, "row_len"),
                                                  _u32_arg(stride, "stride"), _id_or_none(bos_id), _id_or_none(eos_id), _u32_arg(flags, "flags"),
                                                  stream or None, int(n_windows), spans_ptr or None))
+
+    # -- fill-in-the-middle (include/tgx.h: tgx_result_fim; csrc/fim.hip) --
+    @classmethod
+    def from_ids(cls, ids: np.ndarray, offs: np.ndarray, vocab_size: int, device: int = 0) -> "NativeResult":
+        """A result on `device` from host arrays (ids u32[T], offsets u64[S+1] from 0, every id below vocab_size): ids that
+        were tokenised elsewhere, for fim, the layouts and decode_result."""
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        h = C.c_void_p()
+        check(lib.tgx_result_from_ids(int(device), ptr(ids) if ids.size else None, ptr(offs) if offs.size else None, max(offs.shape[0] - 1, 0),
+                                      _u32_arg(vocab_size, "vocab_size"), C.byref(h)))
+        return cls(h)
+
+    def fim(self, prefix_id: int, suffix_id: int, middle_id: int, *, rate: float = 1.0, spm_rate: float = 0.5, seed: int = 0,
+            first_row: int = 0, return_info: bool = False, stream: int = 0):
+        """The rows rearranged for fill-in-the-middle on the device -> a new NativeResult (this one is only read): a row
+        is rearranged with probability `rate` into PRE prefix SUF suffix MID middle (PSM) or, with probability spm_rate
+        of those, PRE SUF suffix MID prefix middle (SPM), at two cuts drawn per row from (seed, first_row + row).
+        return_info=True -> (NativeResult, mode u8[S]: 0 copied / 1 PSM / 2 SPM, cuts u64[S, 2]).  stream as in
+        pad_device."""
+        n = self.num_samples
+        mode = np.zeros(n, np.uint8) if return_info else None
+        cuts = np.zeros((n, 2), np.uint64) if return_info else None
+        h = C.c_void_p()
+        m = 2**64 - 1
+        check(lib.tgx_result_fim(self._h, _u32_arg(prefix_id, "sentinel id"), _u32_arg(suffix_id, "sentinel id"), _u32_arg(middle_id, "sentinel id"),
+                                 float(rate), float(spm_rate), int(seed) & m, int(first_row) & m, stream or None,
+                                 ptr(mode) if return_info and n else None, ptr(cuts) if return_info and n else None, None, C.byref(h)))
+        res = NativeResult(h)
+        return (res, mode, cuts) if return_info else res
 
     def pad_host(self, row_len: int, pad_id: int, **kw) -> dict:
         """layout_pad_host over the ids and offsets copied to the host."""

@@ -54,6 +54,12 @@ tgx_status window_check_totals(const char* who, uint64_t max_row, uint64_t n_win
 tgx_status layout_check_host(const char* who, const uint32_t* ids, const uint64_t* offs, uint64_t n_rows);
 tgx_status assemble_check(const char* who, const uint64_t* seg_offs, const int32_t* seg_special, uint64_t n_samples, uint32_t vocab_size,
                           uint32_t n_specials, bool have_segs, uint64_t n_rows, uint64_t* n_segs);
+// fill-in-the-middle: the rates in [0, 1] and three pairwise distinct sentinels, none of them TGX_NO_ID; the output's
+// vocabulary size for an input of vocab_size
+tgx_status fim_check(const char* who, uint32_t prefix_id, uint32_t suffix_id, uint32_t middle_id, double rate, double spm_rate);
+uint32_t fim_vocab_size(uint32_t vocab_size, uint32_t prefix_id, uint32_t suffix_id, uint32_t middle_id);
+// ids and offsets in host memory as a result's: layout_check_host, vocab_size <= 0xFFFFFFFE and every id below it
+tgx_status result_check_host(const char* who, const uint32_t* ids, const uint64_t* offs, uint64_t n_rows, uint32_t vocab_size);
 tgx_status decode_build_tables(const char* who, const uint8_t* bytes, const uint64_t* offs, uint32_t V, std::vector<uint8_t>* len,
                                std::vector<tgx::DecodeSlot>* slots);
 tgx_status decode_check_specials(const char* who, uint32_t vocab_size, const uint8_t* special_bytes, const uint64_t* special_offs, uint32_t n_specials);

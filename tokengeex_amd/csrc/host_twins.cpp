@@ -1,8 +1,8 @@
 // The *_host twins of the result-side device entry points (include/tgx.h): tgx_layout_pad_host, tgx_layout_pack_host,
-// tgx_layout_windows_host, tgx_assemble_host, tgx_decode_rows_host, tgx_spans_host, tgx_window_spans_host, tgx_front_host and
+// tgx_layout_windows_host, tgx_assemble_host, tgx_fim_host, tgx_decode_rows_host, tgx_spans_host, tgx_window_spans_host, tgx_front_host and
 // tgx_normalize_host, and the
 // argument checks they share with the device entry points of tgx_api.cpp.  A twin goes through the same index arithmetic as its kernels (layout.h, assemble.h,
-// decode.h, spans.h, front.h, norm.h) on host memory.  Nothing in this file calls a HIP function, so it builds and runs without the
+// fim.h, decode.h, spans.h, front.h, norm.h) on host memory.  Nothing in this file calls a HIP function, so it builds and runs without the
 // handles, the pool or a device.
 #include <algorithm>
 #include <cstdlib>
@@ -12,6 +12,7 @@
 #include "api_internal.h"
 #include "assemble.h"
 #include "decode.h"
+#include "fim.h"
 #include "front.h"
 #include "layout.h"
 #include "norm.h"
@@ -85,6 +86,29 @@ tgx_status layout_check_host(const char* who, const uint32_t* ids, const uint64_
     const tgx_status st = check_packed_list(who, "offs", "offsets", offs, n_rows, true);
     if (st != TGX_OK) return st;
     if (offs[n_rows] && !ids) return fail(TGX_ERR_INVALID, "%s: ids is NULL", who);
+    return TGX_OK;
+}
+
+tgx_status fim_check(const char* who, uint32_t prefix_id, uint32_t suffix_id, uint32_t middle_id, double rate, double spm_rate) {
+    if (!(rate >= 0.0 && rate <= 1.0)) return fail(TGX_ERR_INVALID, "%s: rate %g is not in [0, 1]", who, rate);
+    if (!(spm_rate >= 0.0 && spm_rate <= 1.0)) return fail(TGX_ERR_INVALID, "%s: spm_rate %g is not in [0, 1]", who, spm_rate);
+    if (prefix_id == TGX_NO_ID || suffix_id == TGX_NO_ID || middle_id == TGX_NO_ID)
+        return fail(TGX_ERR_INVALID, "%s: a sentinel id is TGX_NO_ID", who);
+    if (prefix_id == suffix_id || prefix_id == middle_id || suffix_id == middle_id)
+        return fail(TGX_ERR_INVALID, "%s: the sentinel ids %u, %u, %u are not pairwise distinct", who, prefix_id, suffix_id, middle_id);
+    return TGX_OK;
+}
+
+uint32_t fim_vocab_size(uint32_t vocab_size, uint32_t prefix_id, uint32_t suffix_id, uint32_t middle_id) {
+    return std::max(vocab_size, 1u + std::max(prefix_id, std::max(suffix_id, middle_id)));  // (no sentinel is 0xFFFFFFFF)
+}
+
+tgx_status result_check_host(const char* who, const uint32_t* ids, const uint64_t* offs, uint64_t n_rows, uint32_t vocab_size) {
+    const tgx_status st = layout_check_host(who, ids, offs, n_rows);
+    if (st != TGX_OK) return st;
+    if (vocab_size > 0xFFFFFFFEu) return fail(TGX_ERR_INVALID, "%s: vocab_size %u leaves no room for TGX_NO_ID", who, vocab_size);
+    for (uint64_t j = 0, T = offs[n_rows]; j < T; j++)
+        if (ids[j] >= vocab_size) return fail(TGX_ERR_INVALID, "%s: id %u at %llu is not below vocab_size %u", who, ids[j], (unsigned long long)j, vocab_size);
     return TGX_OK;
 }
 
@@ -426,6 +450,48 @@ tgx_status tgx_assemble_host(const uint32_t* ids, const uint64_t* id_offs, uint6
             for (uint32_t q = 0; q < n_in; q++) out_ids[e0 + q] = v[q];
         }
     }
+    return TGX_OK;
+}
+
+// ---- fill-in-the-middle -------------------------------------------------------------
+
+double tgx_fim_u01(uint64_t seed, uint64_t row, uint64_t draw) { return tgx::fim_u01(seed, row, draw); }
+
+tgx_status tgx_fim_host(const uint32_t* ids, const uint64_t* offs, uint64_t n_rows, uint32_t vocab_size, uint32_t prefix_id, uint32_t suffix_id,
+                        uint32_t middle_id, double rate, double spm_rate, uint64_t seed, uint64_t first_row, uint32_t* out_ids, uint64_t ids_cap,
+                        uint64_t* out_offs, uint8_t* mode, uint64_t* cuts, uint64_t* n_applied) {
+    const char* who = "tgx_fim_host";
+    if (!out_offs) return fail(TGX_ERR_INVALID, "%s: out_offs is NULL", who);
+    tgx_status st = fim_check(who, prefix_id, suffix_id, middle_id, rate, spm_rate);
+    if (st == TGX_OK) st = result_check_host(who, ids, offs, n_rows, vocab_size);
+    if (st != TGX_OK) return st;
+    // as the device: the new offsets from the rows' output lengths, then the kernel's tiles and thread slots
+    uint64_t n_out = 0;
+    for (uint64_t i = 0; i < n_rows; i++) n_out += tgx::fim_out_len(seed, first_row + i, offs[i + 1] - offs[i], rate);
+    if (ids_cap < n_out) return fail(TGX_ERR_INVALID, "%s: %llu ids, room for %llu", who, (unsigned long long)n_out, (unsigned long long)ids_cap);
+    if (n_out && !out_ids) return fail(TGX_ERR_INVALID, "%s: out_ids is NULL", who);
+    out_offs[0] = 0;
+    for (uint64_t i = 0; i < n_rows; i++) out_offs[i + 1] = out_offs[i] + tgx::fim_out_len(seed, first_row + i, offs[i + 1] - offs[i], rate);
+    const tgx::FimArgs f = {seed, first_row, rate, spm_rate, prefix_id, suffix_id, middle_id};
+    for (uint64_t t0 = 0; t0 < n_out; t0 += tgx::kFimTile) {
+        const uint64_t last = tgx::fim_tile_last(t0, n_out);
+        const uint64_t lo = tgx::pack_find_row(out_offs, 0, 0, n_rows - 1, t0), hi = tgx::pack_find_row(out_offs, 0, 0, n_rows - 1, last);
+        for (uint64_t e0 = t0; e0 <= last; e0 += tgx::kFimGroup) {
+            const uint32_t n_in = last + 1 - e0 < tgx::kFimGroup ? (uint32_t)(last + 1 - e0) : tgx::kFimGroup;
+            uint32_t v[tgx::kFimGroup] = {0, 0, 0, 0};
+            tgx::fim_group(f, ids, offs, out_offs, lo, hi, e0, n_in, v);
+            for (uint32_t q = 0; q < n_in; q++) out_ids[e0 + q] = v[q];
+        }
+    }
+    for (uint64_t i = 0; i < n_rows && (mode || cuts); i++) {  // as fim_info_kernel
+        const tgx::FimRow r = tgx::fim_row(seed, first_row + i, offs[i + 1] - offs[i], rate, spm_rate);
+        if (mode) mode[i] = (uint8_t)r.mode;
+        if (cuts) {
+            cuts[2 * i] = r.a;
+            cuts[2 * i + 1] = r.b;
+        }
+    }
+    if (n_applied) *n_applied = (n_out - offs[n_rows]) / 3;
     return TGX_OK;
 }
 

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "decode.h"
+#include "fim.h"
 #include "spans.h"
 
 namespace tgx {
@@ -356,6 +357,23 @@ hipError_t assemble_scan_temp_bytes(uint64_t n_segs, size_t* bytes);
 hipError_t launch_assemble_ranks(int32_t* seg_special, uint64_t* rank, uint64_t n_segs, void* temp, size_t temp_bytes, hipStream_t stream);
 hipError_t launch_assemble_starts(const AssembleParams& p, hipStream_t stream);
 hipError_t launch_assemble_fill(const AssembleParams& p, hipStream_t stream);
+
+// fim.hip: the rows of a result rearranged for fill-in-the-middle (fim.h has the index arithmetic).  All pointers are
+// device memory.
+struct FimParams {
+    const uint32_t* ids;            // u32[T]: the input result
+    const uint64_t* offs;           // u64[S+1]: its offsets
+    uint64_t n_rows;                // S
+    FimArgs f;                      // seed, first_row, rates and the three sentinel ids
+    uint64_t n_out;                 // T' = out_offs[S] (the fill)
+    uint32_t* out_ids;              // u32[T'], 16-byte aligned
+    uint64_t* out_offs;             // u64[S+1], written by launch_fim_offsets
+};
+hipError_t fim_scan_temp_bytes(uint64_t n_rows, size_t* bytes);
+hipError_t launch_fim_offsets(const FimParams& p, void* temp, size_t temp_bytes, hipStream_t stream);
+hipError_t launch_fim_fill(const FimParams& p, hipStream_t stream);
+// mode u8[S] and cuts u64[2S] (either may be null)
+hipError_t launch_fim_info(const FimParams& p, uint8_t* mode, uint64_t* cuts, hipStream_t stream);
 
 // decode.hip: ids decoded to UTF-8 text (decode.h has the index arithmetic).  All pointers are device memory.
 struct DecodeParams {

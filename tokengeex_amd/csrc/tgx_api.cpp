@@ -3203,6 +3203,116 @@ tgx_status tgx_plan_copy(const tgx_plan* p, uint64_t* seg_offs, uint64_t offs_ca
     return TGX_OK;
 }
 
+// ---- fill-in-the-middle: a result's rows rearranged behind three sentinels (fim.hip; fim.h has the index arithmetic) ----
+
+namespace {
+
+// device time of the last tgx_result_fim of this thread, per stage (tgx_fim_last_times; a FrontTimer's array)
+constexpr int kFimStages = 3;
+const char* const kFimStageNames[kFimStages] = {"fim_offsets_scan", "fim_fill_kernel", "fim_info_kernel"};
+thread_local float g_fim_ms[kFrontStages] = {0, 0, 0, 0, 0};
+static_assert(kFimStages <= kFrontStages, "the stages share FrontTimer");
+
+}  // namespace
+
+int tgx_fim_last_times(const char** names, float* ms, int cap) {
+    int n = 0;
+    for (; n < kFimStages && n < cap; n++) {
+        if (names) names[n] = kFimStageNames[n];
+        if (ms) ms[n] = g_fim_ms[n];
+    }
+    return n;
+}
+
+tgx_status tgx_result_from_ids(int device, const uint32_t* ids, const uint64_t* offs, uint64_t n_rows, uint32_t vocab_size, tgx_result** out) {
+    const char* who = "tgx_result_from_ids";
+    if (!out) return fail(TGX_ERR_INVALID, "%s: out is NULL", who);
+    *out = nullptr;
+    tgx_status st = result_check_host(who, ids, offs, n_rows, vocab_size);
+    if (st != TGX_OK) return st;
+    int n_devices = 0;
+    if ((st = require_device(&n_devices)) != TGX_OK) return st;
+    if (device < 0 || device >= n_devices) return fail(TGX_ERR_INVALID, "%s: device %d of %d", who, device, n_devices);
+    DeviceScope scope;
+    HIP_TRY(hipSetDevice(device));
+    std::unique_ptr<tgx_result> r(new tgx_result());
+    r->device = device;
+    r->vocab_size = vocab_size;
+    r->n_samples = n_rows;
+    r->n_tokens = offs[n_rows];
+    if (r->d_offs.alloc(device, (size_t)(n_rows + 1) * 8) != hipSuccess || r->d_ids.alloc(device, (size_t)r->n_tokens * 4 + 256) != hipSuccess)
+        return fail(TGX_ERR_DEVICE, "out of device memory (result from ids)");
+    HIP_TRY(copy_sync(r->d_offs, offs, (size_t)(n_rows + 1) * 8, hipMemcpyHostToDevice, device));
+    if (r->n_tokens) HIP_TRY(copy_sync(r->d_ids, ids, (size_t)r->n_tokens * 4, hipMemcpyHostToDevice, device));
+    *out = r.release();
+    return TGX_OK;
+}
+
+tgx_status tgx_result_fim(const tgx_result* r, uint32_t prefix_id, uint32_t suffix_id, uint32_t middle_id, double rate, double spm_rate,
+                          uint64_t seed, uint64_t first_row, void* stream, uint8_t* mode, uint64_t* cuts, uint64_t* n_applied, tgx_result** out) {
+    const char* who = "tgx_result_fim";
+    if (!r || !out) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
+    *out = nullptr;
+    tgx_status st = fim_check(who, prefix_id, suffix_id, middle_id, rate, spm_rate);
+    if (st != TGX_OK) return st;
+    const uint64_t S = r->n_samples;
+    DeviceScope scope;
+    HIP_TRY(hipSetDevice(r->device));
+    hipStream_t hs = stream_or_default(stream, r->device);
+    std::unique_ptr<tgx_result> res(new tgx_result());  // before the guard: its buffers go back after the stream's end
+    uint64_t h_total = 0;
+    FrontTimer timer(hs, g_fim_ms);  // (before the guard: its events outlive the stream's work)
+    StreamGuard guard(r->device, hs);
+    res->device = r->device;
+    res->vocab_size = fim_vocab_size(r->vocab_size, prefix_id, suffix_id, middle_id);
+    res->n_samples = S;
+    size_t scan_bytes = 0;
+    if (tgx::fim_scan_temp_bytes(S, &scan_bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan temp-size query failed");
+    void* d_scan = nullptr;
+    if (res->d_offs.alloc(r->device, (size_t)(S + 1) * 8) != hipSuccess || guard.alloc(scan_bytes, &d_scan) != hipSuccess)  // (never NULL: that asks the scan for its size)
+        return fail(TGX_ERR_DEVICE, "out of device memory (fill-in-the-middle)");
+    tgx::FimParams p = {};
+    p.ids = r->d_ids;
+    p.offs = r->d_offs;
+    p.n_rows = S;
+    p.f = tgx::FimArgs{seed, first_row, rate, spm_rate, prefix_id, suffix_id, middle_id};
+    p.out_offs = res->d_offs;
+    timer.begin(0);
+    if (tgx::launch_fim_offsets(p, d_scan, scan_bytes, hs) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan launch failed");
+    timer.end(0);
+    // the one word that visits the host: T' sizes the id buffer
+    HIP_TRY(hipMemcpyAsync(&h_total, res->d_offs.get() + S, 8, hipMemcpyDeviceToHost, hs));
+    HIP_TRY(hipStreamSynchronize(hs));
+    if (h_total < r->n_tokens || (h_total - r->n_tokens) % 3 || (h_total - r->n_tokens) / 3 > S)
+        return fail(TGX_ERR_DEVICE, "%s: %llu ids from %llu over %llu rows", who, (unsigned long long)h_total, (unsigned long long)r->n_tokens,
+                    (unsigned long long)S);
+    res->n_tokens = h_total;
+    if (res->d_ids.alloc(r->device, (size_t)h_total * 4 + 256) != hipSuccess) return fail(TGX_ERR_DEVICE, "out of device memory (fill-in-the-middle)");
+    p.n_out = h_total;
+    p.out_ids = res->d_ids;
+    timer.begin(1);
+    if (tgx::launch_fim_fill(p, hs) != hipSuccess) return fail(TGX_ERR_DEVICE, "fim_fill_kernel launch failed");
+    timer.end(1);
+    if (S && (mode || cuts)) {
+        uint8_t* d_mode = nullptr;
+        uint64_t* d_cuts = nullptr;
+        if (mode) HIP_TRY(guard.alloc((size_t)S, &d_mode));
+        if (cuts) HIP_TRY(guard.alloc((size_t)S * 16, &d_cuts));
+        timer.begin(2);
+        if (tgx::launch_fim_info(p, d_mode, d_cuts, hs) != hipSuccess) return fail(TGX_ERR_DEVICE, "fim_info_kernel launch failed");
+        timer.end(2);
+        if (mode) HIP_TRY(hipMemcpyAsync(mode, d_mode, (size_t)S, hipMemcpyDeviceToHost, hs));
+        if (cuts) HIP_TRY(hipMemcpyAsync(cuts, d_cuts, (size_t)S * 16, hipMemcpyDeviceToHost, hs));
+    }
+    // the stream has reached its end before either result can change hands (the guard: also after a failure)
+    HIP_TRY(hipStreamSynchronize(hs));
+    guard.done();
+    timer.read();
+    if (n_applied) *n_applied = (h_total - r->n_tokens) / 3;
+    *out = res.release();
+    return TGX_OK;
+}
+
 // ---- spans: the part of its row's text that every token covers (spans.hip; spans.h has the index arithmetic) ------
 
 namespace {

@@ -408,6 +408,56 @@ class Tokenizer:
                 truncation_side=layout.get("truncation_side", "right"))
         return out
 
+    # -- fill-in-the-middle on the device (csrc/fim.hip) --
+    def _fim_request(self, layout: dict):
+        """Takes fim out of a layout request -> None, or the arguments of NativeResult.fim: the sentinels given as ids or
+        special-token strings, resolved as _layout_ids resolves pad."""
+        fim = layout.pop("fim", None)
+        if fim is None:
+            return None
+        if layout.get("return_offsets_mapping") is not None or layout.get("return_overflowing_tokens"):
+            raise ValueError("fim cannot be combined with return_offsets_mapping or return_overflowing_tokens: "
+                             "a rearranged row no longer follows its text")
+        fim = dict(fim)
+        unknown = set(fim) - {"prefix", "suffix", "middle", "rate", "spm_rate", "seed", "first_row"}
+        if unknown:
+            raise TypeError(f"fim: unknown keys {sorted(unknown)}")
+        ids = []
+        for key in ("prefix", "suffix", "middle"):
+            if fim.get(key) is None:
+                raise TypeError(f"fim: {key} is required")
+            v = fim[key]
+            if isinstance(v, str):
+                k = self.special_token_to_id(v)
+                if k is None:
+                    raise TokenGeeXError(f"{v!r} is not a special token of this tokenizer", _lib.ERR_INVALID)
+                v = k
+            ids.append(int(v))
+        return dict(prefix_id=ids[0], suffix_id=ids[1], middle_id=ids[2], rate=float(fim.get("rate", 1.0)),
+                    spm_rate=float(fim.get("spm_rate", 0.5)), seed=self._sample_seed(fim.get("seed")), first_row=int(fim.get("first_row", 0)))
+
+    def fim_result(self, result: "_lib.NativeResult", *, prefix, suffix, middle, rate: float = 1.0, spm_rate: float = 0.5,
+                   seed: int | None = None, first_row: int = 0) -> "_lib.NativeResult":
+        """The rows of a device result rearranged for fill-in-the-middle training (NativeResult.fim) -> a new NativeResult;
+        `result` is only read, and the caller frees both.  A row is rearranged with probability `rate`, into
+        PRE prefix SUF suffix MID middle (PSM) or, with probability spm_rate of those, PRE SUF suffix MID prefix middle (SPM),
+        at two cuts drawn uniformly per row.  prefix / suffix / middle: the sentinels, ids or special-token strings.
+        seed: None takes the tokenizer's seed (a fresh one when that is None too); first_row: the index of the result's
+        first row in the batch the draws are made for."""
+        req = self._fim_request({"fim": dict(prefix=prefix, suffix=suffix, middle=middle, rate=rate, spm_rate=spm_rate, seed=seed,
+                                             first_row=first_row)})
+        return result.fim(**req)
+
+    @staticmethod
+    def _fim_applied(res, fim):
+        """`res` (None: a batch without samples) behind the fim request of a layout call; the intermediate result is freed."""
+        if res is None or fim is None:
+            return res
+        try:
+            return res.fim(**fim)
+        finally:
+            res.free()
+
     def _ordinary_result(self, flat: np.ndarray, offs: np.ndarray, dropout: float):
         """The ordinary path of encode_batch_flat up to the device result (processors run, text is not split at special
         tokens) -> NativeResult, or None for an empty batch."""
@@ -435,14 +485,21 @@ class Tokenizer:
         the tensors are [W, L], "overflow_to_sample_mapping" and "window_first" ([W] int32) name each row's sample and the
         index of its first token there, and "offset_mapping" is [W, L, 2], still relative to the whole sample's text.
 
+        fim=dict(prefix=, suffix=, middle= [, rate=1.0, spm_rate=0.5, seed=None, first_row=0]) rearranges the samples' ids
+        for fill-in-the-middle training on the device before they are laid out (fim_result; the sentinels are ids or
+        special-token strings).  It cannot be combined with return_offsets_mapping or return_overflowing_tokens (ValueError):
+        those map rows onto their text, which a rearranged row no longer follows.  The packed forms and the encode_batch_* /
+        encode_corpus_* forms take the same keyword.
+
         This is the ORDINARY path: the processors run as in encode_ordinary_batch and the text is not split at special
         tokens — a special token's string inside a text is encoded as ordinary text.  encode_batch_padded_flat is the
         special-aware form: the same layout over encode_batch's ids, put together on the device (encode_batch_result_flat)."""
         from . import tensors
+        fim = self._fim_request(layout)
         unit = self._mapping_unit(layout)
         stride = self._window_stride(layout)
         layout = self._layout_ids(layout)
-        res = self._ordinary_result(flat, offs, dropout)
+        res = self._fim_applied(self._ordinary_result(flat, offs, dropout), fim)
         if res is None:
             if stride is not None:
                 return self._windows(None, layout, unit, stride)
@@ -460,8 +517,9 @@ class Tokenizer:
         concatenated and cut into blocks -> {"input_ids": [B, block_len] [, "doc_ids", "positions"]} (tensors.to_packed:
         dtype, return_doc, drop_last).  The ORDINARY path as well; encode_batch_packed_flat is the special-aware form."""
         from . import tensors
+        fim = self._fim_request(layout)
         layout = self._layout_ids(layout)
-        res = self._ordinary_result(flat, offs, dropout)
+        res = self._fim_applied(self._ordinary_result(flat, offs, dropout), fim)
         if res is None:
             return self._empty_layout(False, block_len, layout)
         try:
@@ -570,10 +628,11 @@ class Tokenizer:
         """encode_ordinary_batch_padded_flat for the special-aware encode_batch: the text is split at special tokens, which
         get their own ids, and the ids are put together and laid out on the device (encode_batch_result_flat)."""
         from . import tensors
+        fim = self._fim_request(layout)
         unit = self._mapping_unit(layout)
         stride = self._window_stride(layout)
         layout = self._layout_ids(layout)
-        res = self.encode_batch_result_flat(flat, offs, dropout)
+        res = self._fim_applied(self.encode_batch_result_flat(flat, offs, dropout), fim)
         if res is None:
             if stride is not None:
                 return self._windows(None, layout, unit, stride)
@@ -588,8 +647,9 @@ class Tokenizer:
     def encode_batch_packed_flat(self, flat: np.ndarray, offs: np.ndarray, block_len: int, dropout: float = 0.0, **layout) -> dict:
         """encode_ordinary_batch_packed_flat for the special-aware encode_batch (encode_batch_result_flat)."""
         from . import tensors
+        fim = self._fim_request(layout)
         layout = self._layout_ids(layout)
-        res = self.encode_batch_result_flat(flat, offs, dropout)
+        res = self._fim_applied(self.encode_batch_result_flat(flat, offs, dropout), fim)
         if res is None:
             return self._empty_layout(False, block_len, layout)
         try:
@@ -709,6 +769,7 @@ class Tokenizer:
         """encode_batch_padded_flat over a resident corpus (encode_corpus_result): the same layout requests, offset mapping and
         overflow windows included."""
         from . import tensors
+        fim = self._fim_request(layout)
         unit = self._mapping_unit(layout)
         stride = self._window_stride(layout)
         layout = self._layout_ids(layout)
@@ -716,7 +777,7 @@ class Tokenizer:
             if stride is not None:
                 return self._windows(None, layout, unit, stride)
             return self._with_offset_mapping(None, self._empty_layout(True, None, layout), layout, unit)
-        res = self.encode_corpus_result(corpus, dropout)
+        res = self._fim_applied(self.encode_corpus_result(corpus, dropout), fim)
         try:
             if stride is not None:
                 return self._windows(res, layout, unit, stride)
@@ -727,10 +788,11 @@ class Tokenizer:
     def encode_corpus_packed(self, corpus: "_lib.NativeCorpus", block_len: int, dropout: float = 0.0, **layout) -> dict:
         """encode_batch_packed_flat over a resident corpus (encode_corpus_result)."""
         from . import tensors
+        fim = self._fim_request(layout)
         layout = self._layout_ids(layout)
         if corpus.num_samples == 0:
             return self._empty_layout(False, block_len, layout)
-        res = self.encode_corpus_result(corpus, dropout)
+        res = self._fim_applied(self.encode_corpus_result(corpus, dropout), fim)
         try:
             return tensors.to_packed(res, block_len, **layout)
         finally:
