@@ -837,6 +837,12 @@ uint32_t tgx_last_encode_hot_values(const tgx_model *m);
  * the build that has the lean step (every token its own score at three positions per lane) and only for a model
  * whose scores all have a magnitude below 2^960; other models run that build without the step. */
 uint32_t tgx_last_encode_lean_items(const tgx_model *m);
+/* 1 when the last encode pass wrote its ids in place (a self-check: results do not depend on it): encode5_kernel
+ * counted every sample's tokens in its relaxation, the counts were scanned into the result's offsets and the trace
+ * wrote each id where it belongs — no scratch of 4 bytes per text byte, no compaction.  0: the pass went through that
+ * scratch and compact_kernel (dropout, tokens longer than 16 bytes, samples sent to encode6_kernel, a sample of 2^24
+ * bytes or more, a build of encode5_kernel that does not count, TGX_IDS_IN_PLACE=0, or another encode path). */
+int tgx_last_encode_ids_in_place(const tgx_model *m);
 
 /* ---- dropout ---------------------------------------------------------------
  * The reference draws rand::random::<f64>() from an unseeded thread RNG

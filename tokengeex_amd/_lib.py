@@ -99,6 +99,7 @@ SYMBOLS = {
     "tgx_model_score_values": (_u32, [_vp]),
     "tgx_last_encode_hot_values": (_u32, [_vp]),
     "tgx_last_encode_lean_items": (_u32, [_vp]),
+    "tgx_last_encode_ids_in_place": (_i, [_vp]),
     "tgx_last_encode_long_samples": (_u64, [_vp]),
     "tgx_last_estep_pieces": (_u64, [_vp]),
     "tgx_last_estep_redo": (_u64, [_vp]),
@@ -1407,6 +1408,11 @@ class NativeModel:
     def last_encode_lean_step(self) -> bool:
         """Whether encode5_kernel relaxed with the lean step in the last pass (last_encode_lean_items)."""
         return bool(self.last_encode_lean_items()[0] & 1)
+
+    def last_encode_ids_in_place(self) -> bool:
+        """Whether the last encode pass wrote its ids in place: token counts from encode5_kernel's relaxation, no scratch
+        of 4 bytes per text byte, no compact_kernel (a self-check: results do not depend on it)."""
+        return bool(lib.tgx_last_encode_ids_in_place(self._h))
 
     def last_encode_long_samples(self) -> int:
         return lib.tgx_last_encode_long_samples(self._h)

@@ -247,7 +247,28 @@ constexpr uint32_t kLeanUnreachedHi = 0xFFE00000u;  // high word (unsigned) >= t
 template <int LN>
 __device__ __forceinline__ bool relax5_reached(uint32_t fhi) { return (LN & kLeanStep) ? fhi < kLeanUnreachedHi : fhi != 0xFFF00000u; }
 
-template <int U, int LN = 0>
+// CNT: the winner word carries the position's token count above the step, count << 8 | step.  A
+// candidate of step U comes from position p0 + U — lane U, whose word is final now and is what `fin` captures — so it
+// offers that position's count plus one: (bcast_U(bpv) & ~0xFF) + (0x100 | U), written (x | 0xFF) + (1 + U).  Two more
+// vector instructions per step (an OR that takes the broadcast as its DPP operand, an add), off the chain broadcast ->
+// add -> max; the select that chose the immediate U now chooses this register.  One register lives across steps beside
+// the word itself: the OR's mask.  kNoStep is count 0 (a sample's first position).  Every reader of the step reads its low four bits
+// ((l - fin - 1) & 15), so the count above them changes nothing there.  The count of a position that is not reached is
+// arbitrary, like its step; it never exceeds the position (every hop adds one token and at least one byte), so a sample
+// shorter than 2^24 bytes cannot overflow the field.  CNT = false is the step as it was.
+template <int U>
+__device__ __forceinline__ uint32_t relax5_count_cand(uint32_t bpv) {
+    // The OR takes the broadcast as its DPP operand (one v_or_b32_dpp) only in this form: update_dpp with the OR's
+    // identity as `old` — mov_dpp is not combined — and the mask in a register, since a DPP instruction has no literal.
+    // With a literal mask the step is a v_mov_b32_dpp, a v_or and a v_add: three instructions, +0.46 ms per GiB in the
+    // headline build against +0.32 with the two here (profiles/ids_in_place).
+    uint32_t ff = 0xFFu;
+    asm("" : "+v"(ff));
+    const uint32_t from = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)bpv, 0x150 + U, 0xF, 0xF, false);  // row_newbcast:U
+    return (from | ff) + (1u + (uint32_t)U);
+}
+
+template <int U, int LN = 0, bool CNT = false>
 __device__ __forceinline__ void relax5_step(double sv, double& acc, uint32_t& bpv, uint32_t& fin, uint32_t& fhi) {
     constexpr uint64_t MU = kRowLane0 << U;  // lanes with l == U
     double best;
@@ -259,7 +280,8 @@ __device__ __forceinline__ void relax5_step(double sv, double& acc, uint32_t& bp
     const double cand = best + sv;           // model.rs:98
     const uint64_t take = __builtin_amdgcn_fcmp(cand, acc_r, 2 /* OGT: model.rs:101 */);
     asm("v_max_f64 %0, %1, %2" : "=v"(acc) : "v"(acc_r), "v"(cand));  // (fmax() adds a canonicalising v_max of its own)
-    bpv = sel_imm_u32<U>(take, bpv);
+    if constexpr (CNT) bpv = sel_u32(take, relax5_count_cand<U>(bpv), bpv);
+    else bpv = sel_imm_u32<U>(take, bpv);
 }
 
 // The lean step: seven vector instructions instead of nine.  No `fhi` capture, and the finalised lane is reset by its
@@ -275,7 +297,7 @@ __device__ __forceinline__ void relax5_step(double sv, double& acc, uint32_t& bp
 // The winner step of a position that is not reached is then arbitrary (a candidate of the class may "beat" the reset
 // value), so its back-pointer byte is: no path visits such a position, and the trace reads path positions only.  The
 // position whose reachability IS read — a sample's end: P.status, the 0xFF byte — lies in a group that runs relax5_step.
-template <int U, int LN>
+template <int U, int LN, bool CNT = false>
 __device__ __forceinline__ void relax5_lean_step(double sv, double& acc, uint32_t& bpv, uint32_t& fin) {
     constexpr uint64_t MU = kRowLane0 << U;  // lanes with l == U
     double best;
@@ -288,7 +310,8 @@ __device__ __forceinline__ void relax5_lean_step(double sv, double& acc, uint32_
     const double cand = best + sv;           // model.rs:98
     const uint64_t take = __builtin_amdgcn_fcmp(cand, acc_r, 2 /* OGT: model.rs:101 */);
     asm("v_max_f64 %0, %1, %2" : "=v"(acc) : "v"(acc_r), "v"(cand));
-    bpv = sel_imm_u32<U>(take, bpv);
+    if constexpr (CNT) bpv = sel_u32(take, relax5_count_cand<U>(bpv), bpv);
+    else bpv = sel_imm_u32<U>(take, bpv);
 }
 
 

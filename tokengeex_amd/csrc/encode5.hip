@@ -410,10 +410,12 @@ __device__ __forceinline__ void e5_long_tail(__amdgpu_buffer_rsrc_t trie, const 
 
 // CK: the depth at which the walks are compacted (Walk5; 0: never)
 // LN: the lean relaxation (device_common.h: kLeanStep | kLeanBcast | kLeanFetch; 0: the kernel as it was)
-template <bool DROPOUT, bool COLD, int PPL, bool LONG, int CK = 0, int LN = 0>
+// CNT: the relaxation counts tokens (device_common.h: relax5_step) and the lane that writes a sample's
+// status writes its token count to P.counts beside it, so that the trace can write ids in place; false: the kernel as it was
+template <bool DROPOUT, bool COLD, int PPL, bool LONG, int CK = 0, int LN = 0, bool CNT = false>
 __global__ __launch_bounds__(1024, (PPL == 1 ? 8 : (PPL == 2 ? 6 : (PPL == 3 ? 4 : 1)))) void encode5_kernel(EncodeParams P, Encode5Params Q) {
     static_assert(!LONG || PPL == 4, "the long-token build runs four positions per lane");
-    static_assert(LN == 0 || (!LONG && !DROPOUT), "the long-token and dropout builds keep the kernel as it was");
+    static_assert((LN == 0 && !CNT) || (!LONG && !DROPOUT), "the long-token and dropout builds keep the kernel as it was");
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr uint32_t LM = LONG ? 32 : 16;
     constexpr uint32_t SPAN = 16u * PPL;
@@ -660,7 +662,7 @@ __global__ __launch_bounds__(1024, (PPL == 1 ? 8 : (PPL == 2 ? 6 : (PPL == 3 ? 4
                 // LN == 0 keeps the steps' text as it was, verbatim, beside the macro form below — do not fold the two: with
                 // the macro / lambda form alone 53 of this file's 70 kernels came out scheduled differently from the parent's,
                 // and TGX_E5_LEAN=0 has to run the parent's instructions (profiles/relax_lean/kernel_resources.txt)
-                if constexpr (LN == 0) {
+                if constexpr (LN == 0 && !CNT) {
                     if (COLD) {
                         // both halves' cold values are requested before the first step: the loads sit behind branches, so
                         // the compiler waits for all of them at the first use — one exposed L2 round trip per group, not two
@@ -713,8 +715,8 @@ __global__ __launch_bounds__(1024, (PPL == 1 ? 8 : (PPL == 2 ? 6 : (PPL == 3 ? 4
                     // reachability is read (P.status, the 0xFF byte); every other group the lean ones
                     const bool full = !(LN & kLeanStep) || ((end_groups >> g) & 1u) != 0u;
 #define E5_STEP(U, SV)                                                   \
-        if (FULL) relax5_step<U, LN>(SV, acc, bpv, fin[g], fhi);              \
-        else relax5_lean_step<U, LN>(SV, acc, bpv, fin[g]);
+        if (FULL) relax5_step<U, LN, CNT>(SV, acc, bpv, fin[g], fhi);         \
+        else relax5_lean_step<U, LN, CNT>(SV, acc, bpv, fin[g]);
                     auto steps = [&](auto full_tag) {
                         constexpr bool FULL = decltype(full_tag)::value;
                         if (COLD) {
@@ -792,7 +794,10 @@ __global__ __launch_bounds__(1024, (PPL == 1 ? 8 : (PPL == 2 ? 6 : (PPL == 3 ? 4
             if (left < SPAN) {
 #pragma unroll
                 for (int g = 0; g < PPL; ++g)
-                    if (left == 16u * g + l) P.status[s] = (n == 0u || reached[g]) ? 1u : 0u;
+                    if (left == 16u * g + l) {
+                        P.status[s] = (n == 0u || reached[g]) ? 1u : 0u;
+                        if constexpr (CNT) P.counts[s] = (n != 0u && reached[g]) ? fin[g] >> 8 : 0u;  // (an end not reached: no ids)
+                    }
                 need_new = true;
             } else {
                 p0 += SPAN;
@@ -1382,8 +1387,26 @@ int encode5_lean_items(bool cold, int ppl, bool step_ok) {
     return step_ok ? items : lean_without_step(items);
 }
 int encode6_lean_items() { return kE6Lean; }
+// Which builds count tokens in the relaxation (the kernel's CNT), decided per build by measurement
+// like the lean items above: a build that spills with the count, or whose guard workload got slower, keeps it off, and its
+// passes write ids through `tmp` and compact_kernel as before.  -DTGX_E5_CNT=<0|1> builds the library with one answer
+// everywhere, for measurements.
+#ifdef TGX_E5_CNT
+constexpr bool kE5CntHot = TGX_E5_CNT != 0, kE5CntHot2 = TGX_E5_CNT != 0, kE5CntCold = TGX_E5_CNT != 0, kE5CntCold3 = TGX_E5_CNT != 0;
+#else
+constexpr bool kE5CntHot = true;    // every value in LDS: one, three, four positions per lane
+constexpr bool kE5CntHot2 = true;   // ... two positions per lane (80 registers)
+constexpr bool kE5CntCold = true;   // COLD builds at one, two, four positions per lane
+constexpr bool kE5CntCold3 = true;  // COLD, three positions per lane
+#endif
+// the dropout and long-token builds never count
+bool encode5_counts(bool dropout, bool cold, int ppl, bool long_tokens) {
+    if (dropout || long_tokens) return false;
+    return cold ? (ppl == 3 ? kE5CntCold3 : kE5CntCold) : (ppl == 2 ? kE5CntHot2 : kE5CntHot);
+}
 // compact: the depth of Walk5's compaction (0, 4 .. 8); the DROPOUT, LONG and one-position-per-lane builds never compact
-static encode5_fn pick_encode5(bool dropout, bool cold, int ppl, bool long_tokens, int compact, bool lean, bool step_ok) {
+// count: the counting build (the caller asks for it only where encode5_counts() says the build has one)
+static encode5_fn pick_encode5(bool dropout, bool cold, int ppl, bool long_tokens, int compact, bool lean, bool step_ok, bool count) {
     if (long_tokens) {  // tokens of 17..32 bytes: four positions per lane only
         if (cold) return dropout ? encode5_kernel<true, true, 4, true> : encode5_kernel<false, true, 4, true>;
         return dropout ? encode5_kernel<true, false, 4, true> : encode5_kernel<false, false, 4, true>;
@@ -1400,28 +1423,34 @@ static encode5_fn pick_encode5(bool dropout, bool cold, int ppl, bool long_token
         if (ppl == 3) return encode5_kernel<true, false, 3, false>;
         return encode5_kernel<true, false, 4, false>;
     }
-#define TGX_E5K(C, PL, LN) \
-    (compact == 4 ? encode5_kernel<false, C, PL, false, 4, LN> : compact == 5 ? encode5_kernel<false, C, PL, false, 5, LN> \
-     : compact == 6 ? encode5_kernel<false, C, PL, false, 6, LN> : compact == 7 ? encode5_kernel<false, C, PL, false, 7, LN> \
-     : compact == 8 ? encode5_kernel<false, C, PL, false, 8, LN> : encode5_kernel<false, C, PL, false, 0, LN>)
-#define TGX_E5L(LNH, LNC, LNC3) \
+#define TGX_E5K(C, PL, LN, CN) \
+    (compact == 4 ? encode5_kernel<false, C, PL, false, 4, LN, CN> : compact == 5 ? encode5_kernel<false, C, PL, false, 5, LN, CN> \
+     : compact == 6 ? encode5_kernel<false, C, PL, false, 6, LN, CN> : compact == 7 ? encode5_kernel<false, C, PL, false, 7, LN, CN> \
+     : compact == 8 ? encode5_kernel<false, C, PL, false, 8, LN, CN> : encode5_kernel<false, C, PL, false, 0, LN, CN>)
+#define TGX_E5L(LNH, LNC, LNC3, CN) \
     if (cold) { \
-        if (ppl == 1) return encode5_kernel<false, true, 1, false, 0, LNC>; \
-        if (ppl == 2) return TGX_E5K(true, 2, LNC); \
-        if (ppl == 3) return TGX_E5K(true, 3, LNC3); \
-        return TGX_E5K(true, 4, LNC); \
+        if (ppl == 1) return encode5_kernel<false, true, 1, false, 0, LNC, CN && kE5CntCold>; \
+        if (ppl == 2) return TGX_E5K(true, 2, LNC, CN && kE5CntCold); \
+        if (ppl == 3) return TGX_E5K(true, 3, LNC3, CN && kE5CntCold3); \
+        return TGX_E5K(true, 4, LNC, CN && kE5CntCold); \
     } \
-    if (ppl == 1) return encode5_kernel<false, false, 1, false, 0, LNH>; \
-    if (ppl == 2) return TGX_E5K(false, 2, LNH); \
-    if (ppl == 3) return TGX_E5K(false, 3, LNH); \
-    return TGX_E5K(false, 4, LNH);
-    if (lean && step_ok) {
-        TGX_E5L(kE5LeanHot, kE5LeanCold, kE5LeanCold3)
+    if (ppl == 1) return encode5_kernel<false, false, 1, false, 0, LNH, CN && kE5CntHot>; \
+    if (ppl == 2) return TGX_E5K(false, 2, LNH, CN && kE5CntHot2); \
+    if (ppl == 3) return TGX_E5K(false, 3, LNH, CN && kE5CntHot); \
+    return TGX_E5K(false, 4, LNH, CN && kE5CntHot);
+#define TGX_E5C(CN) \
+    if (lean && step_ok) { \
+        TGX_E5L(kE5LeanHot, kE5LeanCold, kE5LeanCold3, CN) \
+    } \
+    if (lean) {  /* a score beyond the lean step's gate: the same builds without the step (0: the kernel as it was) */ \
+        TGX_E5L(lean_without_step(kE5LeanHot), lean_without_step(kE5LeanCold), lean_without_step(kE5LeanCold3), CN) \
+    } \
+    TGX_E5L(0, 0, 0, CN)
+    if (count) {  // (a build whose count is off by default has no counting instance: the flag then selects its plain one)
+        TGX_E5C(true)
     }
-    if (lean) {  // a score beyond the lean step's gate: the same builds without the step (0: the kernel as it was)
-        TGX_E5L(lean_without_step(kE5LeanHot), lean_without_step(kE5LeanCold), lean_without_step(kE5LeanCold3))
-    }
-    TGX_E5L(0, 0, 0)
+    TGX_E5C(false)
+#undef TGX_E5C
 #undef TGX_E5L
 #undef TGX_E5K
 }
@@ -1444,9 +1473,10 @@ uint32_t encode5_max_hot(bool long_tokens, int waves, int ppl, uint32_t budget) 
     return budget > fixed + 64u ? (budget - fixed) / 8u : 0u;
 }
 
-hipError_t encode5_waves_per_simd(bool dropout, bool cold, int ppl, bool long_tokens, int compact, bool lean, bool step_ok, int* out) {
+hipError_t encode5_waves_per_simd(bool dropout, bool cold, int ppl, bool long_tokens, int compact, bool lean, bool step_ok, bool count, int* out) {
     hipFuncAttributes attr;
-    hipError_t e = hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(pick_encode5(dropout, cold, ppl, long_tokens, compact, lean && encode5_has_lean(dropout, long_tokens), step_ok)));
+    hipError_t e = hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(pick_encode5(dropout, cold, ppl, long_tokens, compact, lean && encode5_has_lean(dropout, long_tokens), step_ok,
+                                                                                             count && encode5_counts(dropout, cold, ppl, long_tokens))));
     if (e != hipSuccess) return e;
     const int regs = (attr.numRegs + 7) & ~7;
     *out = regs > 0 ? (512 / regs > 8 ? 8 : 512 / regs) : 8;
@@ -1496,14 +1526,15 @@ hipError_t launch_encode6(const EncodeParams& p, Encode5Params q, bool cold, boo
     return hipGetLastError();
 }
 
-hipError_t launch_encode5(const EncodeParams& p, Encode5Params q, bool cold, int ppl, bool long_tokens, int compact, bool lean, bool step_ok,
+hipError_t launch_encode5(const EncodeParams& p, Encode5Params q, bool cold, int ppl, bool long_tokens, int compact, bool lean, bool step_ok, bool count,
                           int waves, uint32_t blocks, uint32_t min_lds, hipStream_t stream) {
     uint32_t lds = encode5_lds_layout(q.n_hot, long_tokens, waves, ppl, &q.list_off, &q.root_off, &q.idx_off);
     if (lds > 160u * 1024u || q.n_hot > q.n_values || (!cold && q.n_hot != q.n_values) || (long_tokens && ppl != 4) ||
         (compact != 0 && (compact < 4 || compact > 8)))
         return hipErrorInvalidValue;
     lean = lean && encode5_has_lean(p.dropout > 0.0, long_tokens);
-    encode5_fn fn = pick_encode5(p.dropout > 0.0, cold, ppl, long_tokens, compact, lean, step_ok);
+    if (count && !encode5_counts(p.dropout > 0.0, cold, ppl, long_tokens)) return hipErrorInvalidValue;  // the caller relies on the counts
+    encode5_fn fn = pick_encode5(p.dropout > 0.0, cold, ppl, long_tokens, compact, lean, step_ok, count);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return e;
     if (lean && (e = lean_lds_check(reinterpret_cast<const void*>(fn))) != hipSuccess) return e;

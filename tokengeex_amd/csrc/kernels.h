@@ -277,6 +277,16 @@ hipError_t encode4_waves_per_simd(bool dropout, int ppl, bool root, int* out);
 hipError_t launch_encode4(const EncodeParams& p, int ppl, int waves, uint32_t blocks, bool root, hipStream_t stream);
 uint32_t encode4_lds_bytes(int waves, int ppl, bool root);
 hipError_t launch_trace(const EncodeParams& p, uint32_t blocks, hipStream_t stream);
+// The trace that writes ids in place (trace_body.h: INPLACE): p.counts holds every sample's token count already
+// (encode5_kernel's counting builds) and o.out_offs their scan.  p.tmp is not used.
+struct TraceInPlace {
+    const uint64_t* out_offs;  // u64[S+1]: the result's offsets
+    uint32_t* ids;             // u32[out_offs[S]]: the result's ids
+};
+hipError_t launch_trace_in_place(const EncodeParams& p, const TraceInPlace& o, uint32_t blocks, hipStream_t stream);
+// err_sample code bits of the trace kernels (the plain value: the lowest sample whose end is not reached)
+constexpr unsigned long long kErrCorruptBp = 1ULL << 62;      // a back-pointer that names no vocabulary token (low bits: the text byte)
+constexpr unsigned long long kErrCountMismatch = 1ULL << 61;  // in place: the trace's token count differs from P.counts (low bits: the sample)
 uint32_t encode5_lds_layout(uint32_t n_hot, bool long_tokens, int waves, int ppl, uint32_t* list_off, uint32_t* root_off, uint32_t* idx_off);
 uint32_t encode5_max_hot(bool long_tokens, int waves, int ppl, uint32_t budget);
 // lean: the kernels with the lean relaxation step (TGX_E5_LEAN; device_common.h: relax5_lean_step) — the dropout and
@@ -286,7 +296,11 @@ bool encode5_has_lean(bool dropout, bool long_tokens);
 // COLD, positions per lane; step_ok: the scores pass the lean step's gate, else the build without the step) and encode6_kernel
 int encode5_lean_items(bool cold, int ppl, bool step_ok);
 int encode6_lean_items();
-hipError_t encode5_waves_per_simd(bool dropout, bool cold, int ppl, bool long_tokens, int compact, bool lean, bool step_ok, int* out);
+// whether the build of encode5_kernel counts tokens in its relaxation and writes them to P.counts (DESIGN.md section R8;
+// decided per build in encode5.hip): the passes of such a build may write ids in place (ids_in_place.h)
+bool encode5_counts(bool dropout, bool cold, int ppl, bool long_tokens);
+// count: ask for the counting build where the geometry has one
+hipError_t encode5_waves_per_simd(bool dropout, bool cold, int ppl, bool long_tokens, int compact, bool lean, bool step_ok, bool count, int* out);
 uint32_t encode6_lds_layout(uint32_t n_hot, uint32_t pool, uint32_t* root_off, uint32_t* ctrl_off, uint32_t* ring_off);
 uint32_t encode6_max_hot(uint32_t budget, uint32_t pool);
 uint32_t encode6_pool_total(uint32_t pool);  // pool entries of a block (index space they take)
@@ -295,7 +309,8 @@ hipError_t estep5_waves_per_simd(bool dropout, bool cold, int ppl, int* out);
 hipError_t launch_estep5_fwd(const struct Estep4Params& p, Encode5Params q, bool cold, int ppl, int waves, uint32_t blocks, hipStream_t stream);
 hipError_t launch_encode6(const EncodeParams& p, Encode5Params q, bool cold, bool lean, uint32_t blocks, hipStream_t stream);
 // compact: the depth at which the walks of a trip are compacted (0: never; 4 .. 8; encode5.hip: Walk5)
-hipError_t launch_encode5(const EncodeParams& p, Encode5Params q, bool cold, int ppl, bool long_tokens, int compact, bool lean, bool step_ok,
+// count: the counting build (an error where encode5_counts() says the build has none)
+hipError_t launch_encode5(const EncodeParams& p, Encode5Params q, bool cold, int ppl, bool long_tokens, int compact, bool lean, bool step_ok, bool count,
                           int waves, uint32_t blocks, uint32_t min_lds, hipStream_t stream);
 hipError_t launch_encode2(const EncodeParams& p, uint32_t num_cus, bool permuted, hipStream_t stream);   // encode2.hip
 hipError_t launch_trace32(const EncodeParams& p, uint32_t blocks, bool permuted, hipStream_t stream);

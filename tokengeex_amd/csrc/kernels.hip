@@ -599,10 +599,15 @@ __global__ __launch_bounds__(1024, (PPL == 1 ? 6 : 1)) void encode4_kernel(Encod
 }
 
 // Back-trace + id emission for the rows4 path (trace_body.h).
-template <bool STAMP, bool CARRY, int K>
-__global__ __launch_bounds__(256) void trace_kernel(EncodeParams P) {
+// INPLACE: the ids go straight into the result (O; trace_body.h), else right-aligned into P.tmp (O is not read)
+// (the grid is eight blocks per CU with static shares of the samples — trace_blocks — so a build must keep eight waves
+// per SIMD: the in-place builds are told so, since their extra scalars put the carrying one at 82 scalar registers, where
+// a SIMD holds seven; the others are at 75 to 78 of 80 on their own and stay as they were)
+template <bool STAMP, bool CARRY, int K, bool INPLACE = false>
+__global__ __launch_bounds__(256, INPLACE ? 8 : 1) void trace_kernel(EncodeParams P, TraceInPlace O) {
+    static_assert(!(STAMP && INPLACE), "the stamped build writes through tmp");
     __shared__ typename TraceRingEntry<CARRY>::type ring_all[4][kTraceRing];
-    trace_body<16, true, STAMP, CARRY, K>(P, ring_all[threadIdx.x >> 6]);
+    trace_body<16, true, STAMP, CARRY, K, INPLACE>(P, ring_all[threadIdx.x >> 6], O);
 }
 
 // counts[S] -> offsets[S+1] (exclusive prefix sum), one workgroup.
@@ -757,10 +762,10 @@ hipError_t launch_encode4(const EncodeParams& p, int ppl, int waves, uint32_t bl
 template <bool STAMP, bool CARRY>
 static void launch_trace_stride(const EncodeParams& p, uint32_t blocks, hipStream_t stream) {
     switch (p.trace_stride) {  // the hop stage's stride exponent (trace_body.h: trace_hops)
-        case 1: hipLaunchKernelGGL((trace_kernel<STAMP, CARRY, 1>), dim3(blocks), dim3(256), 0, stream, p); break;
-        case 2: hipLaunchKernelGGL((trace_kernel<STAMP, CARRY, 2>), dim3(blocks), dim3(256), 0, stream, p); break;
-        case 3: hipLaunchKernelGGL((trace_kernel<STAMP, CARRY, 3>), dim3(blocks), dim3(256), 0, stream, p); break;
-        default: hipLaunchKernelGGL((trace_kernel<STAMP, CARRY, 0>), dim3(blocks), dim3(256), 0, stream, p); break;
+        case 1: hipLaunchKernelGGL((trace_kernel<STAMP, CARRY, 1>), dim3(blocks), dim3(256), 0, stream, p, TraceInPlace{nullptr, nullptr}); break;
+        case 2: hipLaunchKernelGGL((trace_kernel<STAMP, CARRY, 2>), dim3(blocks), dim3(256), 0, stream, p, TraceInPlace{nullptr, nullptr}); break;
+        case 3: hipLaunchKernelGGL((trace_kernel<STAMP, CARRY, 3>), dim3(blocks), dim3(256), 0, stream, p, TraceInPlace{nullptr, nullptr}); break;
+        default: hipLaunchKernelGGL((trace_kernel<STAMP, CARRY, 0>), dim3(blocks), dim3(256), 0, stream, p, TraceInPlace{nullptr, nullptr}); break;
     }
 }
 hipError_t launch_trace(const EncodeParams& p, uint32_t blocks, hipStream_t stream) {
@@ -770,6 +775,24 @@ hipError_t launch_trace(const EncodeParams& p, uint32_t blocks, hipStream_t stre
         launch_trace_stride<false, true>(p, blocks, stream);
     else
         launch_trace_stride<false, false>(p, blocks, stream);
+    return hipGetLastError();
+}
+
+template <bool CARRY>
+static void launch_trace_in_place_stride(const EncodeParams& p, const TraceInPlace& o, uint32_t blocks, hipStream_t stream) {
+    switch (p.trace_stride) {
+        case 1: hipLaunchKernelGGL((trace_kernel<false, CARRY, 1, true>), dim3(blocks), dim3(256), 0, stream, p, o); break;
+        case 2: hipLaunchKernelGGL((trace_kernel<false, CARRY, 2, true>), dim3(blocks), dim3(256), 0, stream, p, o); break;
+        case 3: hipLaunchKernelGGL((trace_kernel<false, CARRY, 3, true>), dim3(blocks), dim3(256), 0, stream, p, o); break;
+        default: hipLaunchKernelGGL((trace_kernel<false, CARRY, 0, true>), dim3(blocks), dim3(256), 0, stream, p, o); break;
+    }
+}
+hipError_t launch_trace_in_place(const EncodeParams& p, const TraceInPlace& o, uint32_t blocks, hipStream_t stream) {
+    if (p.stamps || !o.out_offs || !o.ids) return hipErrorInvalidValue;  // (the stamped build writes through tmp)
+    if (p.trace_carry)
+        launch_trace_in_place_stride<true>(p, o, blocks, stream);
+    else
+        launch_trace_in_place_stride<false>(p, o, blocks, stream);
     return hipGetLastError();
 }
 

@@ -29,6 +29,7 @@
 #include "front.h"
 #include "kernels.h"
 #include "layout.h"
+#include "ids_in_place.h"
 #include "lean_gate.h"
 #include "spans.h"
 #include "nbest.h"
@@ -283,6 +284,7 @@ struct tgx_model {
     uint32_t n_values = 0, root_base8 = 0;
     uint32_t last_n_hot = 0;           // values in the LDS copy of the last encode5 launch
     bool lean_scores_ok = false;       // every score passes the gate of the lean relaxation step (lean_gate.h)
+    bool last_ids_in_place = false;    // the last encode pass wrote its ids in place (ids_in_place.h): no tmp, no compact_kernel
     uint32_t last_lean_items = 0;      // lean items of the last pass's encode5_kernel (low byte) and encode6_kernel (next byte); 0: the kernels as they were
     bool have_trie8 = false;
     bool encode_tables_ready = false;  // tokhash / trie8 built and uploaded (ensure_encode_tables)
@@ -465,14 +467,16 @@ void time_end(tgx_model* m) {
     m->n_timed++;
 }
 
-// the encode and sampling passes' scratch: back-pointers, ids right-aligned in `tmp` (then compacted), counts, status
-tgx_status ensure_scratch(tgx_corpus* c) {
+// the encode and sampling passes' scratch: back-pointers, ids right-aligned in `tmp` (then compacted), counts, status.
+// with_tmp = false: a pass that writes its ids in place (ids_in_place.h) needs no `tmp` — 4 bytes per text byte that a
+// corpus which only ever sees such passes never allocates.
+tgx_status ensure_scratch(tgx_corpus* c, bool with_tmp = true) {
     HIP_TRY(hipSetDevice(c->device));
     // u32[N] for the one-sample-per-wave kernel; the rows4 kernels use it as bytes, N + 128 per sample
     if (!c->d_bp) HIP_TRY(c->d_bp.alloc(c->device, std::max((size_t)c->n_bytes * 4 + 256, (size_t)c->n_bytes + 128 * (size_t)c->n_samples + 512)));
     if (!c->d_counts) HIP_TRY(c->d_counts.alloc(c->device, (size_t)c->n_samples * 4 + 256));
     if (!c->d_status) HIP_TRY(c->d_status.alloc(c->device, (size_t)c->n_samples * 4 + 256));
-    if (!c->d_tmp) HIP_TRY(c->d_tmp.alloc(c->device, (size_t)c->n_bytes * 4 + 256));
+    if (with_tmp && !c->d_tmp) HIP_TRY(c->d_tmp.alloc(c->device, (size_t)c->n_bytes * 4 + 256));
     return TGX_OK;
 }
 
@@ -673,10 +677,18 @@ tgx_status redo_long_matches(tgx_model* m, tgx_corpus* c, const tgx::EncodeParam
     return TGX_OK;
 }
 
+tgx_status check_no_path(tgx_model* m, const tgx_corpus* c);
+tgx_status scan_ids_offsets(tgx_model* m, tgx_corpus* c, tgx_result* r, const char* what, bool with_err);
+
 // Queues the encode kernels and the back-trace over the corpus: every sample's token count in c->d_counts, its ids
 // right-aligned in c->d_tmp, the lowest failing sample in d_ctrl->err.  Diagnostic scratch belongs to `pass`.
-tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64_t seed, Pass& pass) {
-    tgx_status st = ensure_scratch(c);
+// A pass that can (ids_in_place.h) writes the ids in place instead: encode5_kernel leaves the counts,
+// they are scanned into r's offsets, the host waits once for the total and sizes r's ids, and the trace writes them
+// there.  m->last_ids_in_place tells the caller, which then has neither scan nor compaction left to do: it reads
+// d_ctrl->err once the trace is through.
+tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64_t seed, Pass& pass, tgx_result* r) {
+    m->last_ids_in_place = false;
+    tgx_status st = ensure_scratch(c, false);  // (`tmp` once the pass knows that it writes through it)
     if (st != TGX_OK) return st;
     HIP_TRY(hipMemsetAsync(&m->d_ctrl->queue, 0x00, 8, m->stream));
     HIP_TRY(hipMemsetAsync(&m->d_ctrl->err, 0xFF, 8, m->stream));
@@ -705,6 +717,10 @@ tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64
                 (unsigned long long)c->n_samples, (unsigned long long)c->n_bytes, p.lm, use4 ? (use5 ? "rows5" : "rows4") : (use2 ? "rows2" : "fused"),
                 m->flat.table.size(), p.root_base, m->n_values);
     m->last_lean_items = 0;
+    if (!use5) {
+        if ((st = ensure_scratch(c, true)) != TGX_OK) return st;
+        p.tmp = c->d_tmp;
+    }
     if (use5) {
         {
             const tgx_status rst = ensure_value_ranks(m, c);
@@ -843,9 +859,21 @@ tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64
         bool lean = tgx::encode5_has_lean(dropout > 0.0, long_tokens);
         if (const char* e = knob("TGX_E5_LEAN")) lean = lean && atoi(e) != 0;
         const bool step_ok = m->lean_scores_ok;
+        // ids in place (ids_in_place.h): everything but the build's own term is known here, and the geometry below is
+        // sized by the registers of the build that will run — the counting one where this holds and the build has one
+        tgx::IdsInPlaceQuery iq{};
+        iq.rows5 = true;
+        iq.long_tokens = long_tokens;
+        iq.dropout = dropout > 0.0;
+        iq.n_long = n_long;
+        iq.build_counts = true;  // (set below, once the build is chosen)
+        iq.max_len = c->max_len;
+        iq.switched_on = !(knob("TGX_IDS_IN_PLACE") && atoi(knob("TGX_IDS_IN_PLACE")) == 0);
+        iq.diagnostics = p.flags != 0u || (debug_on() && getenv("TGX_STAMPS") != nullptr);
+        const bool want_count = r != nullptr && tgx::ids_in_place(iq);
         {
             int ps4 = 0;
-            HIP_TRY(tgx::encode5_waves_per_simd(dropout > 0.0, false, 4, long_tokens, compact, lean, step_ok, &ps4));
+            HIP_TRY(tgx::encode5_waves_per_simd(dropout > 0.0, false, 4, long_tokens, compact, lean, step_ok, want_count, &ps4));
             hot_waves = std::min(16, ps4 * 4);
             const int least = long_tokens ? 12 : 13;  // (the long-token build has four positions per lane only)
             while (hot_waves >= least && m->n_values > tgx::encode5_max_hot(long_tokens, hot_waves, 4, 160u * 1024u)) hot_waves--;
@@ -893,12 +921,12 @@ tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64
         const uint32_t budget = 160u * 1024u / (uint32_t)bpc;
         bool cold = false;
         int per_simd = 0;
-        HIP_TRY(tgx::encode5_waves_per_simd(dropout > 0.0, false, ppl, long_tokens, compact, lean, step_ok, &per_simd));
+        HIP_TRY(tgx::encode5_waves_per_simd(dropout > 0.0, false, ppl, long_tokens, compact, lean, step_ok, want_count, &per_simd));
         int waves = std::min(16, (per_simd / bpc) * 4);
         if ((ppl == 4 || ppl == 3) && bpc == 1 && hot_waves > 0) waves = std::min(waves, hot_waves);
         if (m->n_values > tgx::encode5_max_hot(long_tokens, waves, ppl, budget)) {
             cold = true;
-            HIP_TRY(tgx::encode5_waves_per_simd(dropout > 0.0, true, ppl, long_tokens, compact, lean, step_ok, &per_simd));
+            HIP_TRY(tgx::encode5_waves_per_simd(dropout > 0.0, true, ppl, long_tokens, compact, lean, step_ok, want_count, &per_simd));
             waves = std::min(16, (per_simd / bpc) * 4);
         }
         if (balance_waves > 0 && ppl == 4 && bpc == 1) waves = std::min(waves, balance_waves);
@@ -909,6 +937,12 @@ tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64
         n_hot = knob_cap_hot("TGX_E5_HOT", n_hot);
         cold = n_hot < m->n_values;
         m->last_n_hot = n_hot;
+        iq.build_counts = tgx::encode5_counts(dropout > 0.0, cold, ppl, long_tokens);
+        const bool in_place = want_count && tgx::ids_in_place(iq);
+        if (!in_place) {  // the trace writes through `tmp`
+            if ((st = ensure_scratch(c, true)) != TGX_OK) return st;
+            p.tmp = c->d_tmp;
+        }
         // (self-check) the lean items of this pass's kernels: encode5_kernel's in the low byte, encode6_kernel's in the next
         m->last_lean_items = !lean ? 0u : ((rest_n ? (uint32_t)tgx::encode5_lean_items(cold, ppl, step_ok) : 0u) |
                                            (n_long ? (uint32_t)tgx::encode6_lean_items() << 8 : 0u));
@@ -969,7 +1003,7 @@ tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64
                 HIP_TRY(hipMemsetAsync(&m->d_ctrl->encode_redo, 0x00, 8, m->stream));
             }
             // (co-run: more than half of the CU's LDS, so that no block of the long-sample kernel shares the CU)
-            const hipError_t le = tgx::launch_encode5(p, q, cold, ppl, long_tokens, compact, lean, step_ok, waves, blocks5, corun_cus && n_long ? 84u * 1024u : 0u, m->stream);
+            const hipError_t le = tgx::launch_encode5(p, q, cold, ppl, long_tokens, compact, lean, step_ok, in_place, waves, blocks5, corun_cus && n_long ? 84u * 1024u : 0u, m->stream);
             if (le != hipSuccess) return fail(TGX_ERR_DEVICE, "encode5 launch failed: %s", hipGetErrorString(le));
         }
         bool joined = false, joined_slot = false;
@@ -1011,6 +1045,16 @@ tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64
         p.order = c->d_order;
         p.n_samples = c->n_samples;
         const uint32_t blocks_t = trace_blocks(m, c->n_samples);
+        if (in_place) {
+            // the counts are there before the trace: offsets, total (the pass's one wait), the ids buffer, and the trace
+            // writes every id where it belongs.  d_ctrl->err is the caller's to read, after the trace.
+            if ((st = scan_ids_offsets(m, c, r, "encode", false)) != TGX_OK) return st;
+            time_begin(m, "trace_kernel");
+            HIP_TRY(tgx::launch_trace_in_place(p, tgx::TraceInPlace{r->d_offs, r->d_ids}, blocks_t, m->stream));
+            time_end(m);
+            m->last_ids_in_place = true;
+            return TGX_OK;
+        }
         // TGX_STAMPS=2: the STAMP build of trace_kernel (tokens <= 16 bytes, ring flushed per sample)
         Stamps stamps_t;
         if (!long_tokens) stamps_t = stamps_begin(m, pass, '2', (size_t)blocks_t * 4);
@@ -1127,9 +1171,12 @@ tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64
 tgx_status check_no_path(tgx_model* m, const tgx_corpus* c) {
     unsigned long long bad = m->h_ctrl->err;
     if (bad == ~0ULL) return TGX_OK;
-    if (bad & (1ULL << 62))
+    if (bad & tgx::kErrCorruptBp)
         return fail(TGX_ERR_DEVICE, "internal error: corrupt back-pointer (sample or text byte %llu)",
-                    (unsigned long long)(bad & ~(1ULL << 62)));
+                    (unsigned long long)(bad & ~tgx::kErrCorruptBp));
+    if (bad & tgx::kErrCountMismatch)  // (the in-place trace's self-check: ids_in_place.h)
+        return fail(TGX_ERR_DEVICE, "internal error: the token count of sample %llu differs between the relaxation and the trace",
+                    (unsigned long long)(bad & ~tgx::kErrCountMismatch));
     uint64_t n = c->h_offs[bad + 1] - c->h_offs[bad];
     set_error_detail(bad, n, n);
     // Display of Error::NoPath, reference src/lib.rs:243-245
@@ -1137,10 +1184,10 @@ tgx_status check_no_path(tgx_model* m, const tgx_corpus* c) {
                 (unsigned long long)n);
 }
 
-// The ids of an encode or sampling pass whose kernels left every sample's token count in c->d_counts and its ids
-// right-aligned in c->d_tmp: the counts scanned into r's offsets, the lowest failing sample and the total read back,
-// the ids buffer, the compaction.  The compaction is queued, not waited for.  `what` names the pass in messages.
-tgx_status compact_ids(tgx_model* m, tgx_corpus* c, tgx_result* r, const char* what) {
+// The first half of what follows a pass's counts (c->d_counts): the counts scanned into r's offsets, the total read back —
+// the pass's one mid-pass synchronisation — and the ids buffer allocated.  with_err: the trace has run, so the lowest
+// failing sample is read in the same wait and checked (a pass that traces in place reads it after its trace instead).
+tgx_status scan_ids_offsets(tgx_model* m, tgx_corpus* c, tgx_result* r, const char* what, bool with_err) {
     const uint64_t S = c->n_samples;
     if (!c->d_scan_tmp) {  // scratch of the device-wide scan (large sample counts only), kept on the corpus
         if (tgx::scan_temp_bytes(S, &c->scan_tmp_bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan temp-size query failed");
@@ -1151,15 +1198,28 @@ tgx_status compact_ids(tgx_model* m, tgx_corpus* c, tgx_result* r, const char* w
     if (tgx::launch_scan(c->d_counts, r->d_offs, S, c->d_scan_tmp, c->scan_tmp_bytes, m->stream) != hipSuccess)
         return fail(TGX_ERR_DEVICE, "scan launch failed");
     time_end(m);
-    if (hipMemcpyAsync(&m->h_ctrl->err, &m->d_ctrl->err, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
+    if ((with_err && hipMemcpyAsync(&m->h_ctrl->err, &m->d_ctrl->err, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess) ||
         hipMemcpyAsync(&m->h_ctrl->total_tokens, r->d_offs + S, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
         hipStreamSynchronize(m->stream) != hipSuccess)
         return fail(TGX_ERR_DEVICE, "%s pass failed: %s", what, hipGetErrorString(hipGetLastError()));
-    const tgx_status st = check_no_path(m, c);
-    if (st != TGX_OK) return st;
+    if (with_err) {
+        const tgx_status st = check_no_path(m, c);
+        if (st != TGX_OK) return st;
+    }
     r->n_tokens = m->h_ctrl->total_tokens;
+    if (r->n_tokens > c->n_bytes) return fail(TGX_ERR_DEVICE, "internal error: %s pass counted more tokens than bytes", what);
     if (r->d_ids.alloc(m->device, (size_t)r->n_tokens * 4 + 256) != hipSuccess)
         return fail(TGX_ERR_DEVICE, "out of device memory (result ids)");
+    return TGX_OK;
+}
+
+// The ids of an encode or sampling pass whose kernels left every sample's token count in c->d_counts and its ids
+// right-aligned in c->d_tmp: the counts scanned into r's offsets, the lowest failing sample and the total read back,
+// the ids buffer, the compaction.  The compaction is queued, not waited for.  `what` names the pass in messages.
+tgx_status compact_ids(tgx_model* m, tgx_corpus* c, tgx_result* r, const char* what) {
+    const uint64_t S = c->n_samples;
+    const tgx_status sst = scan_ids_offsets(m, c, r, what, true);
+    if (sst != TGX_OK) return sst;
     tgx::CompactParams cp{};
     cp.offs = c->d_offs;
     cp.order = c->d_order;
@@ -1745,12 +1805,22 @@ static tgx_status encode_corpus_locked(tgx_model* m, tgx_corpus* c, double dropo
     tgx_result* r = pass.new_result(S);
     if (r->d_offs.alloc(m->device, (size_t)(S + 1) * 8) != hipSuccess)
         return fail(TGX_ERR_DEVICE, "out of device memory (result offsets)");
-    tgx_status st = run_encode_kernel(m, c, dropout, seed, pass);
+    tgx_status st = run_encode_kernel(m, c, dropout, seed, pass, r);
     if (st != TGX_OK) return st;
-    st = compact_ids(m, c, r, "encode");
-    if (st != TGX_OK) return st;
-    if (hipStreamSynchronize(m->stream) != hipSuccess)
-        return fail(TGX_ERR_DEVICE, "compact failed: %s", hipGetErrorString(hipGetLastError()));
+    if (m->last_ids_in_place) {
+        // offsets and ids are in r already: what is left is the lowest failing sample (no path, or the trace's check of
+        // the relaxation's counts), read in the wait that ends the pass
+        if (hipMemcpyAsync(&m->h_ctrl->err, &m->d_ctrl->err, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
+            hipStreamSynchronize(m->stream) != hipSuccess)
+            return fail(TGX_ERR_DEVICE, "encode pass failed: %s", hipGetErrorString(hipGetLastError()));
+        st = check_no_path(m, c);
+        if (st != TGX_OK) return st;
+    } else {
+        st = compact_ids(m, c, r, "encode");
+        if (st != TGX_OK) return st;
+        if (hipStreamSynchronize(m->stream) != hipSuccess)
+            return fail(TGX_ERR_DEVICE, "compact failed: %s", hipGetErrorString(hipGetLastError()));
+    }
     // N + 4T + 16(S+1)
     m->last_alg_bytes = c->n_bytes + 4 * r->n_tokens + 16 * (S + 1);
     *out = pass.release_result();
@@ -4940,3 +5010,4 @@ uint32_t tgx_encode_corun_timeouts(const tgx_model* m) { return m ? m->corun_wai
 uint32_t tgx_model_score_values(const tgx_model* m) { return m && m->have_trie8 ? m->n_values : 0u; }
 uint32_t tgx_last_encode_hot_values(const tgx_model* m) { return m ? m->last_n_hot : 0u; }
 uint32_t tgx_last_encode_lean_items(const tgx_model* m) { return m ? m->last_lean_items : 0u; }
+int tgx_last_encode_ids_in_place(const tgx_model* m) { return (m && m->last_ids_in_place) ? 1 : 0; }

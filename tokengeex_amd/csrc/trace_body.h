@@ -95,8 +95,13 @@ __device__ __forceinline__ uint64_t trace_hops(uint32_t prev, int32_t& qq) {
 template <bool CARRY> struct TraceRingEntry { using type = uint2; };
 template <> struct TraceRingEntry<true> { using type = uint4; };
 // K: the hop stage's stride exponent (trace_hops).
-template <uint32_t LM, bool PERM, bool STAMP, bool CARRY, int K>
-__device__ __forceinline__ void trace_body(const EncodeParams& P, typename TraceRingEntry<CARRY>::type* ring) {
+// INPLACE (trace_kernel only): the encode kernel has counted every sample's tokens (P.counts, read
+// here, not written) and O.out_offs is their scan, so a sample's ids go straight to their place in the result, O.ids,
+// right-aligned to out_offs[s + 1] — no `tmp`, no compaction.  The trace checks the count it was given against its own:
+// it stops a sample before it would pass the count (no id is ever written outside the sample's own slots of O.ids) and
+// reports a sample whose totals differ through err_sample (kErrCountMismatch), so a wrong count cannot pass as shifted ids.
+template <uint32_t LM, bool PERM, bool STAMP, bool CARRY, int K, bool INPLACE = false>
+__device__ __forceinline__ void trace_body(const EncodeParams& P, typename TraceRingEntry<CARRY>::type* ring, const TraceInPlace O = TraceInPlace{nullptr, nullptr}) {
     static_assert(LM == 16 || LM == 32, "token lengths of up to 16 or 32 bytes");
     constexpr uint32_t LMASK = LM - 1u;
     constexpr int NW = (int)LM / 4;  // dwords of token bytes
@@ -128,27 +133,39 @@ __device__ __forceinline__ void trace_body(const EncodeParams& P, typename Trace
     struct MetaRaw {
         uint64_t beg, end;
         uint32_t reach;
+        uint64_t out_end;  // INPLACE: one past the sample's last slot of O.ids ...
+        uint32_t count;    // ... and the token count the encode kernel found
     };
     struct Meta {
         uint32_t s;
         uint64_t beg;
         uint32_t n, reach_n;
+        uint64_t out_end;
+        uint32_t count;
     };
     auto meta_request = [&](uint32_t smp) -> MetaRaw {  // smp: scalar
-        MetaRaw r{0, 0, 1u};
+        MetaRaw r{0, 0, 1u, 0, 0u};
         if (smp != kNone) {
             r.beg = P.offs[smp];
             r.end = P.offs[smp + 1];
             r.reach = P.status[smp];
+            if constexpr (INPLACE) {
+                r.out_end = O.out_offs[smp + 1];
+                r.count = P.counts[smp];
+            }
         }
         return r;
     };
     auto meta_read = [&](uint32_t smp, const MetaRaw& r) -> Meta {
-        Meta mt{smp, 0, 0, 1u};
+        Meta mt{smp, 0, 0, 1u, 0, 0u};
         if (smp != kNone) {
             mt.beg = first_u64(r.beg);
             mt.n = (uint32_t)(first_u64(r.end) - mt.beg);
             mt.reach_n = (mt.n == 0) ? 1u : (uint32_t)__builtin_amdgcn_readfirstlane((int)r.reach);
+            if constexpr (INPLACE) {
+                mt.out_end = first_u64(r.out_end);
+                mt.count = (uint32_t)__builtin_amdgcn_readfirstlane((int)r.count);
+            }
         }
         return mt;
     };
@@ -204,7 +221,8 @@ __device__ __forceinline__ void trace_body(const EncodeParams& P, typename Trace
             }
             // cannot happen unless a kernel bug corrupted a back-pointer: report (the text position), do not fault
             if (!found) atomicMin(P.err_sample, (unsigned long long)((end - len) & ((1ULL << 62) - 1ULL)) | (1ULL << 62));
-            P.tmp[out] = id;
+            if constexpr (INPLACE) O.ids[out] = id;
+            else P.tmp[out] = id;
         }
         if constexpr (!CARRY) flush_out_top -= m;
         head = (head + m) & (kTraceRing - 1u);
@@ -227,8 +245,11 @@ __device__ __forceinline__ void trace_body(const EncodeParams& P, typename Trace
         const uint32_t reach_n = cur.reach_n;
         const bool have = s != kNone;
         const uint8_t* __restrict__ bp = P.bp8 + (have ? bp8_base(beg, s) : 0);
-        uint32_t total = 0;
-        uint64_t out_top = beg + n;   // one past the tmp slot of the sample's next token (ids are right-aligned)
+        // tokens found so far; INPLACE: tokens still to find of the encode kernel's count (one scalar less than count and
+        // total: at 82 scalar registers instead of 80 a SIMD holds seven waves, not eight, and an eighth of the grid's
+        // blocks — sized for eight per CU, static shares of the samples — ran after the others: 2.5 -> 4.0 ms per GiB)
+        uint32_t total = INPLACE ? cur.count : 0u;
+        uint64_t out_top = INPLACE ? cur.out_end : beg + n;   // one past the tmp (INPLACE: ids) slot of the sample's next token (ids are right-aligned)
         flush_beg = beg;
         flush_out_top = out_top;
         int64_t q = (have && reach_n) ? (int64_t)n - 1 : (int64_t)-1;  // Error::NoPath(n, n) otherwise (model.rs:119)
@@ -253,9 +274,18 @@ __device__ __forceinline__ void trace_body(const EncodeParams& P, typename Trace
             if (wq >= 64u) h_next = (uint32_t)bp[PERM ? bp8_perm(wq - 64u + lane) : wq - 64u + lane];
             TGX_TRACE_STAMP(1)  // window loads issued / consumed
             int32_t qq = (int32_t)((uint32_t)q - wq);
-            const uint64_t ends = trace_hops<K>(prev, qq);
+            uint64_t ends = trace_hops<K>(prev, qq);
             q = (int64_t)wq + qq;
-            const uint32_t cnt = (uint32_t)__popcll(ends);
+            uint32_t cnt = (uint32_t)__popcll(ends);
+            if constexpr (INPLACE) {
+                // more tokens than counted: their slots are another sample's.  The window's tokens are dropped, the
+                // sample ends here, and what is left to find is set to a value that reports it below.
+                const bool ov = cnt > total;
+                ends = ov ? 0ULL : ends;
+                cnt = ov ? 0u : cnt;
+                q = ov ? (int64_t)-1 : q;
+                total = ov ? 0xFFFFFFFFu : total;
+            }
             TGX_TRACE_STAMP(2)  // hops
             if ((ends >> lane) & 1ULL) {
                 const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(ends >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ends, 0u));
@@ -268,7 +298,8 @@ __device__ __forceinline__ void trace_body(const EncodeParams& P, typename Trace
                 }
             }
             fill += cnt;
-            total += cnt;
+            if constexpr (INPLACE) total -= cnt;
+            else total += cnt;
             out_top -= cnt;
             __builtin_amdgcn_wave_barrier();
             if (fill >= 64u) lookup(64u);
@@ -281,7 +312,11 @@ __device__ __forceinline__ void trace_body(const EncodeParams& P, typename Trace
             if (fill) lookup(fill);
         }
         if (have && lane == 0) {
-            P.counts[s] = total;
+            if constexpr (INPLACE) {
+                if (total != 0u) atomicMin(P.err_sample, kErrCountMismatch | (unsigned long long)s);
+            } else {
+                P.counts[s] = total;
+            }
             if (!reach_n) atomicMin(P.err_sample, (unsigned long long)s);
         }
         cur = nxt;
