@@ -3643,7 +3643,18 @@ static tgx_status count_pairs_impl(tgx_model* m, tgx_corpus* c, uint64_t max_pai
     void* d_temp = nullptr;
     size_t tb1 = 0, tb2 = 0;
     const size_t kb = (size_t)T * 8 + 256, cb = (size_t)T * 4 + 256;
-    if (T == 0) return pass.done();
+    if (T == 0) {
+        // no token at all (no sample, or only empty ones): an empty table, in malloc'd arrays like every other
+        *keys = (uint64_t*)malloc(sizeof(uint64_t));
+        *counts = (uint64_t*)malloc(sizeof(uint64_t));
+        if (!*keys || !*counts) {
+            free(*keys);
+            free(*counts);
+            *keys = *counts = nullptr;
+            return fail(TGX_ERR_DEVICE, "out of host memory (pair table of 0 entries)");
+        }
+        return pass.done();
+    }
     if (tgx::pair_sort_temp_bytes(T, &tb1) != hipSuccess || tgx::pair_rle_temp_bytes(T, &tb2) != hipSuccess)
         return fail(TGX_ERR_DEVICE, "rocPRIM temp-size query failed");
     if (pass.alloc(kb, &d_keys) != hipSuccess || pass.alloc(kb, &d_sorted) != hipSuccess || pass.alloc(kb, &d_unique) != hipSuccess ||
