@@ -94,6 +94,19 @@ def test_no_rows_one_row_and_the_optional_outputs():
     src.free()
 
 
+def test_stage_times_name_the_three_stages():
+    """fim_last_times after a call that asks for the mode, so that fim_info_kernel runs too: the three stages in order,
+    every time finite and not negative"""
+    src = _lib.NativeResult.from_ids(np.arange(5, dtype=np.uint32), np.array([0, 5], np.uint64), 10)
+    res, mode, _ = src.fim(20, 11, 12, seed=3, return_info=True)
+    assert mode.size == 1
+    times = _lib.fim_last_times()
+    assert list(times) == ["fim_offsets_scan", "fim_fill_kernel", "fim_info_kernel"], times
+    assert all(np.isfinite(v) and v >= 0 for v in times.values()), times
+    res.free()
+    src.free()
+
+
 def test_invalid_arguments_are_refused():
     src = _lib.NativeResult.from_ids(np.arange(6, dtype=np.uint32), np.array([0, 2, 2, 6], np.uint64), 10)
 

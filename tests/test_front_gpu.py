@@ -143,6 +143,23 @@ def test_refusals():
         r.free()
 
 
+def test_stage_times_are_the_front_ends_own():
+    """front_last_times after a split: the five stages in order, every time finite and not negative; a normalize on the
+    same thread in between leaves them as they were (each subsystem keeps its own)."""
+    corpus = tgx.NativeCorpus(*tgx.pack([b"ab<s>cd", b"<s>", b"ef"]))
+    segs, plan = corpus.split_specials([b"<s>", b"</s>"], False)
+    assert plan.num_encoded == 3 and segs.num_bytes == 6   # every stage ran, the pack included
+    times = _lib.front_last_times()
+    assert list(times) == ["front_mark", "front_resolve", "front_segments", "front_keep", "front_pack"], times
+    assert all(np.isfinite(v) and v >= 0 for v in times.values()), times
+    other = tgx.NativeCorpus(*tgx.pack([b"cafe\xcc\x81", b"A\xcc\x8a and \xef\xbc\xa1", b"plain"]))   # combining marks, a fullwidth letter
+    out = other.normalize("nfkc")
+    assert out.n_pieces > 0 and list(_lib.norm_last_times()) == ["norm_mark", "norm_pieces", "norm_length", "norm_places", "norm_write"]
+    assert _lib.front_last_times() == times
+    for h in (out, other, segs, plan, corpus):
+        h.free()
+
+
 def test_a_plan_on_another_device_is_refused():
     if tgx.device_count() < 2:
         pytest.skip("needs two visible devices")

@@ -1,0 +1,861 @@
+// The C ABI's transforms of a resident result (include/tgx.h): layouts and windows, assembly, fill-in-the-middle,
+// decode and the text handle, spans.  They run on the caller's stream under a StreamGuard (assembly: on the model's,
+// under a Pass) and share device_internal.h with the passes of tgx_api.cpp.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <memory>
+#include <mutex>
+#include <vector>
+
+#include "../../include/tgx.h"
+#include "api_internal.h"
+#include "device_internal.h"
+#include "assemble.h"
+#include "decode.h"
+#include "fim.h"
+#include "kernels.h"
+#include "layout.h"
+#include "spans.h"
+
+using namespace tgx::host;
+using namespace tgx::dev;
+
+// ---- layouts: padded rows / packed blocks of a result, in caller-owned device memory (layout.hip) ----------------
+
+tgx_status tgx_result_layout_info(const tgx_result* r, uint32_t bos_id, uint32_t eos_id, uint64_t* max_row_len, uint64_t* n_stream) {
+    if (!r) return fail(TGX_ERR_INVALID, "tgx_result_layout_info: result is NULL");
+    const uint64_t A = (bos_id != TGX_NO_ID ? 1 : 0) + (eos_id != TGX_NO_ID ? 1 : 0);
+    if (n_stream) *n_stream = r->n_tokens + r->n_samples * A;
+    if (!max_row_len) return TGX_OK;
+    *max_row_len = A;
+    if (r->n_samples == 0 || r->n_tokens == 0) return TGX_OK;
+    DeviceScope scope;
+    HIP_TRY(hipSetDevice(r->device));
+    hipStream_t st = stream_or_default(nullptr, r->device);
+    unsigned long long h_max = 0, *d_max = nullptr;
+    StreamGuard guard(r->device, st);
+    HIP_TRY(guard.alloc(sizeof(unsigned long long), &d_max));
+    HIP_TRY(hipMemsetAsync(d_max, 0, sizeof(unsigned long long), st));
+    HIP_TRY(tgx::launch_layout_max_row(r->d_offs, r->n_samples, d_max, st));
+    const tgx_status rst = read_u64(st, d_max, &h_max);
+    if (rst != TGX_OK) return rst;
+    guard.done();
+    *max_row_len = h_max + A;
+    return TGX_OK;
+}
+
+tgx_status tgx_result_pad_device(const tgx_result* r, uint32_t row_len, uint32_t pad_id, uint32_t bos_id, uint32_t eos_id,
+                                 uint32_t flags, void* stream, void* d_ids, uint8_t* d_mask, int32_t* d_lengths,
+                                 uint64_t* n_truncated) {
+    const char* who = "tgx_result_pad_device";
+    if (!r) return fail(TGX_ERR_INVALID, "%s: result is NULL", who);
+    if (!d_ids && r->n_samples) return fail(TGX_ERR_INVALID, "%s: d_ids is NULL", who);
+    tgx_status st = layout_check_flags(who, flags, TGX_LAYOUT_PAD_LEFT | TGX_LAYOUT_TRUNC_LEFT | TGX_LAYOUT_I64);
+    if (st == TGX_OK) st = layout_check_ids(who, pad_id, bos_id, eos_id);
+    if (st != TGX_OK) return st;
+    if (r->vocab_size > 0x80000000u) return fail(TGX_ERR_INVALID, "%s: the model's ids are not all below 2^31", who);
+    const tgx::LayoutSeq seq = tgx::layout_seq(bos_id, eos_id, pad_id);
+    if ((st = layout_check_row_len(who, row_len, seq.extra)) != TGX_OK) return st;
+    if (n_truncated) *n_truncated = 0;
+    if (r->n_samples == 0) return TGX_OK;
+    DeviceScope scope;
+    HIP_TRY(hipSetDevice(r->device));
+    if ((st = check_device_ptr(who, "d_ids", d_ids, r->device, "result")) != TGX_OK) return st;
+    if ((st = check_device_ptr(who, "d_mask", d_mask, r->device, "result")) != TGX_OK) return st;
+    if ((st = check_device_ptr(who, "d_lengths", d_lengths, r->device, "result")) != TGX_OK) return st;
+    hipStream_t hs = stream_or_default(stream, r->device);
+    unsigned long long h_count = 0, *d_count = nullptr;
+    StreamGuard guard(r->device, hs);
+    if (n_truncated) HIP_TRY(guard.alloc(sizeof(unsigned long long), &d_count));
+    tgx::LayoutParams p = {};
+    p.ids = r->d_ids;
+    p.offs = r->d_offs;
+    p.n_rows = r->n_samples;
+    p.len = row_len;
+    p.pad = pad_id;
+    p.bos = bos_id;
+    p.eos = eos_id;
+    p.flags = flags;
+    p.out = d_ids;
+    p.mask = d_mask;
+    p.lengths = d_lengths;
+    p.counter = d_count;
+    if (n_truncated) HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), hs));
+    HIP_TRY(tgx::launch_layout_pad(p, hs));
+    if (n_truncated) HIP_TRY(hipMemcpyAsync(&h_count, d_count, sizeof(unsigned long long), hipMemcpyDeviceToHost, hs));
+    // the stream has reached its end before the result or the destination can change hands (the guard: also after a failure)
+    HIP_TRY(hipStreamSynchronize(hs));
+    guard.done();
+    if (n_truncated) *n_truncated = h_count;
+    return TGX_OK;
+}
+
+tgx_status tgx_result_pack_device(const tgx_result* r, uint32_t block_len, uint32_t pad_id, uint32_t bos_id, uint32_t eos_id,
+                                  uint32_t flags, void* stream, void* d_ids, int32_t* d_doc, int32_t* d_pos, uint64_t* n_blocks) {
+    const char* who = "tgx_result_pack_device";
+    if (!r || !n_blocks) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
+    tgx_status st = layout_check_flags(who, flags, TGX_LAYOUT_I64);
+    if (st == TGX_OK) st = layout_check_ids(who, pad_id, bos_id, eos_id);
+    if (st != TGX_OK) return st;
+    if (r->vocab_size > 0x80000000u) return fail(TGX_ERR_INVALID, "%s: the model's ids are not all below 2^31", who);
+    if (block_len < 1) return fail(TGX_ERR_INVALID, "%s: block_len is 0", who);
+    if (r->n_samples >= 0x80000000ull) return fail(TGX_ERR_UNSUPPORTED, "%s: 2^31 rows or more", who);
+    const tgx::LayoutSeq seq = tgx::layout_seq(bos_id, eos_id, pad_id);
+    const uint64_t n_stream = r->n_tokens + r->n_samples * seq.extra;
+    const uint64_t nb = (n_stream + block_len - 1) / block_len;
+    *n_blocks = nb;
+    if (nb == 0) return TGX_OK;
+    if (!d_ids) return fail(TGX_ERR_INVALID, "%s: d_ids is NULL", who);
+    DeviceScope scope;
+    HIP_TRY(hipSetDevice(r->device));
+    if ((st = check_device_ptr(who, "d_ids", d_ids, r->device, "result")) != TGX_OK) return st;
+    if ((st = check_device_ptr(who, "d_doc", d_doc, r->device, "result")) != TGX_OK) return st;
+    if ((st = check_device_ptr(who, "d_pos", d_pos, r->device, "result")) != TGX_OK) return st;
+    hipStream_t hs = stream_or_default(stream, r->device);
+    tgx::LayoutParams p = {};
+    p.ids = r->d_ids;
+    p.offs = r->d_offs;
+    p.n_rows = r->n_samples;
+    p.len = block_len;
+    p.pad = pad_id;
+    p.bos = bos_id;
+    p.eos = eos_id;
+    p.flags = flags;
+    p.out = d_ids;
+    p.doc = d_doc;
+    p.pos = d_pos;
+    StreamGuard guard(r->device, hs);
+    HIP_TRY(tgx::launch_layout_pack(p, n_stream, nb * block_len, hs));
+    HIP_TRY(hipStreamSynchronize(hs));
+    guard.done();
+    return TGX_OK;
+}
+
+// ---- overflow windows: long rows as overlapping [W, L] windows (layout.hip; layout.h has the window mapping) ---------
+
+namespace {
+
+// Wo = the rows' first windows, in pooled scratch of the guard (u64[S+1]), and *n_windows = W = Wo[S], for a result with
+// S >= 1 rows: the count kernel, the scan, and one read-back of W and the longest row, which are checked against 2^31.
+// The stream has reached its end when this returns TGX_OK.
+tgx_status window_offsets_device(const char* who, const tgx_result* r, uint32_t room, uint32_t step, hipStream_t hs, StreamGuard& guard,
+                                 const uint64_t** d_wo, uint64_t* n_windows) {
+    const uint64_t S = r->n_samples;
+    size_t scan_bytes = 0;
+    if (tgx::scan_temp_bytes(S, &scan_bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan temp-size query failed");
+    uint32_t* counts = nullptr;
+    uint64_t* wo = nullptr;  // Wo[0 .. S], then the longest row
+    void* scan = nullptr;
+    HIP_TRY(guard.alloc((size_t)(S + 1) * 4, &counts));
+    HIP_TRY(guard.alloc((size_t)(S + 2) * 8, &wo));
+    if (scan_bytes) HIP_TRY(guard.alloc(scan_bytes, &scan));
+    HIP_TRY(hipMemsetAsync(wo + S + 1, 0, 8, hs));
+    HIP_TRY(tgx::launch_layout_window_count(r->d_offs, S, room, step, counts, reinterpret_cast<unsigned long long*>(wo + S + 1), hs));
+    HIP_TRY(tgx::launch_scan(counts, wo, S, scan, scan_bytes, hs));
+    uint64_t h[2] = {0, 0};
+    tgx_status st = read_u64(hs, wo + S, h, 2);
+    if (st == TGX_OK) st = window_check_totals(who, h[1], h[0], nullptr);
+    if (st != TGX_OK) return st;
+    *d_wo = wo;
+    *n_windows = h[0];
+    return TGX_OK;
+}
+
+}  // namespace
+
+tgx_status tgx_result_window_info(const tgx_result* r, uint32_t row_len, uint32_t stride, uint32_t bos_id, uint32_t eos_id, uint32_t flags,
+                                  uint64_t* n_windows) {
+    const char* who = "tgx_result_window_info";
+    if (!r || !n_windows) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
+    tgx_status st = layout_check_flags(who, flags, TGX_LAYOUT_PAD_LEFT | TGX_LAYOUT_TRUNC_LEFT | TGX_LAYOUT_I64 | TGX_SPAN_CHARS);
+    if (st == TGX_OK) st = layout_check_ids(who, 0, bos_id, eos_id);
+    if (st != TGX_OK) return st;
+    const tgx::LayoutSeq seq = tgx::layout_seq(bos_id, eos_id, 0);
+    if ((st = window_check_args(who, row_len, stride, seq.extra)) != TGX_OK) return st;
+    *n_windows = 0;
+    if (r->n_samples == 0) return TGX_OK;
+    DeviceScope scope;
+    HIP_TRY(hipSetDevice(r->device));
+    hipStream_t hs = stream_or_default(nullptr, r->device);
+    StreamGuard guard(r->device, hs);
+    const uint64_t* d_wo = nullptr;
+    st = window_offsets_device(who, r, row_len - seq.extra, row_len - seq.extra - stride, hs, guard, &d_wo, n_windows);
+    if (st == TGX_OK) guard.done();
+    return st;
+}
+
+tgx_status tgx_result_window_pad_device(const tgx_result* r, uint32_t row_len, uint32_t stride, uint32_t pad_id, uint32_t bos_id, uint32_t eos_id,
+                                        uint32_t flags, void* stream, uint64_t n_windows, void* d_ids, uint8_t* d_mask, int32_t* d_lengths,
+                                        int32_t* d_window_row, int32_t* d_window_first) {
+    const char* who = "tgx_result_window_pad_device";
+    if (!r) return fail(TGX_ERR_INVALID, "%s: result is NULL", who);
+    if (!d_ids && r->n_samples) return fail(TGX_ERR_INVALID, "%s: d_ids is NULL", who);
+    tgx_status st = layout_check_flags(who, flags, TGX_LAYOUT_PAD_LEFT | TGX_LAYOUT_TRUNC_LEFT | TGX_LAYOUT_I64);
+    if (st == TGX_OK) st = layout_check_ids(who, pad_id, bos_id, eos_id);
+    if (st != TGX_OK) return st;
+    if (r->vocab_size > 0x80000000u) return fail(TGX_ERR_INVALID, "%s: the model's ids are not all below 2^31", who);
+    const tgx::LayoutSeq seq = tgx::layout_seq(bos_id, eos_id, pad_id);
+    if ((st = window_check_args(who, row_len, stride, seq.extra)) != TGX_OK) return st;
+    if (r->n_samples == 0) return window_check_totals(who, 0, 0, &n_windows);
+    DeviceScope scope;
+    HIP_TRY(hipSetDevice(r->device));
+    if ((st = check_device_ptr(who, "d_ids", d_ids, r->device, "result")) != TGX_OK) return st;
+    if ((st = check_device_ptr(who, "d_mask", d_mask, r->device, "result")) != TGX_OK) return st;
+    if ((st = check_device_ptr(who, "d_lengths", d_lengths, r->device, "result")) != TGX_OK) return st;
+    if ((st = check_device_ptr(who, "d_window_row", d_window_row, r->device, "result")) != TGX_OK) return st;
+    if ((st = check_device_ptr(who, "d_window_first", d_window_first, r->device, "result")) != TGX_OK) return st;
+    hipStream_t hs = stream_or_default(stream, r->device);
+    StreamGuard guard(r->device, hs);
+    const uint64_t* d_wo = nullptr;
+    uint64_t W = 0;
+    st = window_offsets_device(who, r, row_len - seq.extra, row_len - seq.extra - stride, hs, guard, &d_wo, &W);
+    if (st == TGX_OK) st = window_check_totals(who, 0, W, &n_windows);
+    if (st != TGX_OK) return st;
+    tgx::WindowParams q = {};
+    q.base.ids = r->d_ids;
+    q.base.offs = r->d_offs;
+    q.base.n_rows = r->n_samples;
+    q.base.len = row_len;
+    q.base.pad = pad_id;
+    q.base.bos = bos_id;
+    q.base.eos = eos_id;
+    q.base.flags = flags;
+    q.base.out = d_ids;
+    q.base.mask = d_mask;
+    q.base.lengths = d_lengths;
+    q.wo = d_wo;
+    q.stride = stride;
+    q.window_row = d_window_row;
+    q.window_first = d_window_first;
+    HIP_TRY(tgx::launch_layout_windows(q, W, hs));
+    // the stream has reached its end before the result or the destination can change hands (the guard: also after a failure)
+    HIP_TRY(hipStreamSynchronize(hs));
+    guard.done();
+    return TGX_OK;
+}
+
+// ---- assembly: a sample-level result with the special tokens' ids, from the segment-level result (assemble.hip) ----
+
+namespace {
+
+// What tgx_assemble_result and tgx_assemble_result_plan share: everything after the checks of the plan itself.  The plan
+// is K segments of S samples, E of them encoded, in host arrays that are uploaded (h_*) or in device memory (d_*: d_special
+// with room for K + 1 entries).
+tgx_status assemble_device(const char* who, tgx_model* m, const tgx_result* segs, const uint64_t* h_seg_offs, const int32_t* h_special,
+                           const uint64_t* d_plan_offs, int32_t* d_plan_special, uint64_t S, uint64_t K, uint32_t n_specials, tgx_result** out) {
+    if (segs && segs->device != m->device)
+        return fail(TGX_ERR_INVALID, "%s: the result is on device %d, the model on device %d", who, segs->device, m->device);
+    if (segs && segs->vocab_size != m->vocab_size)
+        return fail(TGX_ERR_INVALID, "%s: the result was written for %u tokens, the model has %u", who, segs->vocab_size, m->vocab_size);
+    const uint64_t E = segs ? segs->n_samples : 0;
+    const uint64_t n_out = (segs ? segs->n_tokens : 0) + (K - E);
+
+    std::lock_guard<std::mutex> lk(m->mu);
+    HIP_TRY(hipSetDevice(m->device));
+    m->n_timed = 0;
+    Pass pass(m);
+    tgx_result* r = pass.new_result(S);
+    r->vocab_size = m->vocab_size + n_specials;
+    r->n_tokens = n_out;
+    uint64_t *d_seg_offs = nullptr, *d_rank = nullptr, *d_starts = nullptr, *d_zero = nullptr;
+    int32_t* d_special = d_plan_special;
+    void* d_scan = nullptr;
+    size_t scan_bytes = 0;
+    if (tgx::assemble_scan_temp_bytes(K, &scan_bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan temp-size query failed");
+    if (r->d_offs.alloc(m->device, (size_t)(S + 1) * 8) != hipSuccess || r->d_ids.alloc(m->device, (size_t)n_out * 4 + 256) != hipSuccess ||
+        (!d_plan_offs && pass.alloc((size_t)(S + 1) * 8, &d_seg_offs) != hipSuccess) ||
+        (!d_plan_special && pass.alloc((size_t)(K + 1) * 4, &d_special) != hipSuccess) ||
+        pass.alloc((size_t)(K + 1) * 8, &d_rank) != hipSuccess || pass.alloc((size_t)(K + 1) * 8, &d_starts) != hipSuccess ||
+        (E == 0 && pass.alloc(8, &d_zero) != hipSuccess) || pass.alloc(scan_bytes, &d_scan) != hipSuccess)  // (never NULL: that asks the scan for its size)
+        return fail(TGX_ERR_DEVICE, "out of device memory (assembly)");
+    if ((!d_plan_offs && hipMemcpyAsync(d_seg_offs, h_seg_offs, (size_t)(S + 1) * 8, hipMemcpyHostToDevice, m->stream) != hipSuccess) ||
+        (!d_plan_special && K && hipMemcpyAsync(d_special, h_special, (size_t)K * 4, hipMemcpyHostToDevice, m->stream) != hipSuccess) ||
+        (d_zero && hipMemsetAsync(d_zero, 0, 8, m->stream) != hipSuccess))
+        return fail(TGX_ERR_DEVICE, "upload of the split plan failed: %s", hipGetErrorString(hipGetLastError()));
+
+    tgx::AssembleParams p = {};
+    p.ids = E ? segs->d_ids.get() : nullptr;
+    p.offs = E ? segs->d_offs.get() : d_zero;
+    p.seg_offs = d_plan_offs ? d_plan_offs : d_seg_offs;
+    p.seg_special = d_special;
+    p.rank = d_rank;
+    p.starts = d_starts;
+    p.n_segs = K;
+    p.n_samples = S;
+    p.n_out = n_out;
+    p.vocab_size = m->vocab_size;
+    p.out_ids = r->d_ids;
+    p.out_offs = r->d_offs;
+    time_begin(m, "assemble_ranks_scan");
+    if (tgx::launch_assemble_ranks(d_special, d_rank, K, d_scan, scan_bytes, m->stream) != hipSuccess)
+        return fail(TGX_ERR_DEVICE, "scan launch failed");
+    time_end(m);
+    time_begin(m, "assemble_starts_kernel");
+    if (tgx::launch_assemble_starts(p, m->stream) != hipSuccess) return fail(TGX_ERR_DEVICE, "assemble_starts_kernel launch failed");
+    time_end(m);
+    time_begin(m, "assemble_fill_kernel");
+    if (tgx::launch_assemble_fill(p, m->stream) != hipSuccess) return fail(TGX_ERR_DEVICE, "assemble_fill_kernel launch failed");
+    time_end(m);
+    if (hipStreamSynchronize(m->stream) != hipSuccess) return fail(TGX_ERR_DEVICE, "assembly failed: %s", hipGetErrorString(hipGetLastError()));
+    *out = pass.release_result();
+    return pass.done();
+}
+
+}  // namespace
+
+tgx_status tgx_assemble_result(tgx_model* m, const tgx_result* segs, const uint64_t* seg_offs, const int32_t* seg_special,
+                               uint64_t n_samples, uint32_t n_specials, tgx_result** out) {
+    const char* who = "tgx_assemble_result";
+    const tgx_status dst = require_device();
+    if (dst != TGX_OK) return dst;
+    if (!m || !out) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
+    *out = nullptr;
+    uint64_t K = 0;
+    const tgx_status cst = assemble_check(who, seg_offs, seg_special, n_samples, m->vocab_size, n_specials, segs != nullptr, segs ? segs->n_samples : 0, &K);
+    if (cst != TGX_OK) return cst;
+    return assemble_device(who, m, segs, seg_offs, seg_special, nullptr, nullptr, n_samples, K, n_specials, out);
+}
+
+tgx_status tgx_assemble_result_plan(tgx_model* m, const tgx_result* segs, const tgx_plan* plan, uint32_t n_specials, tgx_result** out) {
+    const char* who = "tgx_assemble_result_plan";
+    const tgx_status dst = require_device();
+    if (dst != TGX_OK) return dst;
+    if (!m || !plan || !out) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
+    *out = nullptr;
+    // what assemble_check asks of host arrays, of a plan whose arrays the split wrote
+    if ((uint64_t)m->vocab_size + n_specials > 0xFFFFFFFEull)
+        return fail(TGX_ERR_INVALID, "%s: %u tokens and %u special tokens leave no room for their ids", who, m->vocab_size, n_specials);
+    if (n_specials != plan->n_specials)
+        return fail(TGX_ERR_INVALID, "%s: %u special tokens, the plan was made with %u", who, n_specials, plan->n_specials);
+    if (plan->n_enc && !segs) return fail(TGX_ERR_INVALID, "%s: %llu encoded segments and no result over them", who, (unsigned long long)plan->n_enc);
+    if (plan->n_enc != (segs ? segs->n_samples : 0))
+        return fail(TGX_ERR_INVALID, "%s: %llu encoded segments, the result over them has %llu rows", who, (unsigned long long)plan->n_enc,
+                    (unsigned long long)(segs ? segs->n_samples : 0));
+    if (plan->device != m->device) return fail(TGX_ERR_INVALID, "%s: the plan is on device %d, the model on device %d", who, plan->device, m->device);
+    return assemble_device(who, m, segs, nullptr, nullptr, plan->d_seg_offs, plan->d_special, plan->n_samples, plan->n_segs, n_specials, out);
+}
+
+// ---- decode: ids in HBM to UTF-8 text in HBM (decode.hip; decode.h has the index arithmetic) ----------------------
+
+namespace {
+
+uint64_t decode_elem_bytes(uint32_t kind) { return kind == tgx::kDecodeI64 ? 8 : 4; }
+
+// the model's token tables on its device, once (under m->mu)
+tgx_status ensure_decode_tables(tgx_model* m) {
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (m->decode_tables_ready) return TGX_OK;
+    const uint32_t V = m->vocab_size;
+    std::vector<uint8_t> len;
+    std::vector<tgx::DecodeSlot> slots;
+    const tgx_status st = decode_build_tables("decode", m->vocab_bytes.data(), m->vocab_offs.data(), V, &len, &slots);
+    if (st != TGX_OK) return st;
+    const size_t nb = m->vocab_bytes.size();
+    if (!m->d_dec_len) HIP_TRY(hipMalloc((void**)&m->d_dec_len, (size_t)V + 16));
+    if (!m->d_dec_slots) HIP_TRY(hipMalloc(&m->d_dec_slots, ((size_t)V + 1) * sizeof(tgx::DecodeSlot)));
+    if (!m->d_dec_bytes) HIP_TRY(hipMalloc((void**)&m->d_dec_bytes, nb + 16));
+    if (!m->d_dec_offs) HIP_TRY(hipMalloc((void**)&m->d_dec_offs, ((size_t)V + 1) * 8));
+    if (V) HIP_TRY(hipMemcpy(m->d_dec_len, len.data(), V, hipMemcpyHostToDevice));
+    if (V) HIP_TRY(hipMemcpy(m->d_dec_slots, slots.data(), (size_t)V * sizeof(tgx::DecodeSlot), hipMemcpyHostToDevice));
+    if (nb) HIP_TRY(hipMemcpy(m->d_dec_bytes, m->vocab_bytes.data(), nb, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(m->d_dec_offs, m->vocab_offs.data(), ((size_t)V + 1) * 8, hipMemcpyHostToDevice));
+    m->decode_tables_ready = true;
+    return TGX_OK;
+}
+
+// The decode of src (device pointers) on stream hs of the model's device, which is current.  row_offs_dev: the offsets
+// form's offsets, read back only to name the row of an out-of-bounds id.
+tgx_status decode_device(tgx_model* m, tgx::DecodeSrc src, const uint8_t* special_bytes, const uint64_t* special_offs, uint32_t n_specials,
+                         int include_special, hipStream_t hs, tgx_text** out, uint64_t* bad_sample, uint64_t* bad_id) {
+    const int dev = m->device;
+    const uint64_t S = src.n_rows, N = src.n;
+    std::unique_ptr<tgx_text> text(new tgx_text());
+    PoolBuf<uint8_t> raw;          // the raw bytes: the text's own when nothing is replaced
+    std::vector<uint64_t> h_offs;  // the offsets form's offsets, read back to name the row of an out-of-bounds id
+    StreamGuard guard(dev, hs);    // destroyed before them: a failed call's queued work is over before they go
+    uint32_t *meta = nullptr, *flags = nullptr, *codes = nullptr;
+    uint64_t *starts = nullptr, *specials = nullptr, *gpos = nullptr, *sp_offs = nullptr;
+    uint8_t* sp_bytes = nullptr;
+    void *scan = nullptr, *scan2 = nullptr;
+    unsigned long long* ctrl = nullptr;  // [0]: lowest out-of-bounds position, [1]: replacement characters, [2]: live specials
+    tgx_text* t = text.get();
+    t->device = dev;
+    t->n_rows = S;
+    HIP_TRY(t->d_offs.alloc(dev, (size_t)(S + 1) * 8));
+    if (S == 0 || N == 0) {
+        HIP_TRY(t->d_bytes.alloc(dev, 0));
+        HIP_TRY(hipMemsetAsync(t->d_offs, 0, (size_t)(S + 1) * 8, hs));
+        HIP_TRY(hipStreamSynchronize(hs));
+        guard.done();
+        *out = text.release();
+        return TGX_OK;
+    }
+    tgx_status st = ensure_decode_tables(m);
+    if (st != TGX_OK) return st;
+
+    const uint64_t sp_total = n_specials ? special_offs[n_specials] - special_offs[0] : 0;
+    size_t scan_bytes = 0;
+    if (tgx::decode_scan_temp_bytes(N, &scan_bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan temp-size query failed");
+    HIP_TRY(guard.alloc((size_t)(N + 1) * 4, &meta));
+    HIP_TRY(guard.alloc((size_t)(N + 1) * 8, &starts));
+    HIP_TRY(guard.alloc(scan_bytes, &scan));  // (never NULL: that asks the scan for its size)
+    HIP_TRY(guard.alloc(24, &ctrl));
+    HIP_TRY(guard.alloc(((size_t)n_specials + 1) * 8, &sp_offs));
+    HIP_TRY(guard.alloc((size_t)sp_total + 16, &sp_bytes));
+    std::vector<uint64_t> sp_offs0((size_t)n_specials + 1, 0);  // from 0
+    for (uint32_t k = 0; k <= n_specials && n_specials; k++) sp_offs0[k] = special_offs[k] - special_offs[0];
+    HIP_TRY(guard.upload(sp_offs, std::move(sp_offs0)));
+    if (sp_total) HIP_TRY(hipMemcpyAsync(sp_bytes, special_bytes + special_offs[0], sp_total, hipMemcpyHostToDevice, hs));
+    HIP_TRY(hipMemsetAsync(ctrl, 0xFF, 8, hs));
+    HIP_TRY(hipMemsetAsync(ctrl + 1, 0, 16, hs));
+
+    tgx::DecodeParams p = {};
+    p.tab.tok_len = m->d_dec_len;
+    p.tab.slots = static_cast<const tgx::DecodeSlot*>(m->d_dec_slots);
+    p.tab.bytes = m->d_dec_bytes;
+    p.tab.offs = m->d_dec_offs;
+    p.tab.sp_bytes = sp_bytes;
+    p.tab.sp_offs = sp_offs;
+    p.tab.vocab_size = m->vocab_size;
+    p.tab.n_specials = n_specials;
+    p.tab.include_special = include_special ? 1 : 0;
+    p.src = src;
+    p.meta = meta;
+    p.starts = starts;
+    p.bad_pos = ctrl;
+    p.n_replaced = ctrl + 1;
+    p.n_specials_live = ctrl + 2;
+    p.row_offs = t->d_offs;
+    HIP_TRY(tgx::launch_decode_meta(p, scan, scan_bytes, hs));
+    unsigned long long h_bad = ~0ull, h_raw = 0, h_replaced = 0, h_final = 0, h_specials = 0;
+    HIP_TRY(hipMemcpyAsync(&h_bad, ctrl, 8, hipMemcpyDeviceToHost, hs));
+    HIP_TRY(hipMemcpyAsync(&h_specials, ctrl + 2, 8, hipMemcpyDeviceToHost, hs));
+    HIP_TRY(hipMemcpyAsync(&h_raw, starts + N, 8, hipMemcpyDeviceToHost, hs));
+    HIP_TRY(hipStreamSynchronize(hs));
+    if (h_bad != ~0ull) {
+        int64_t x = 0;
+        union { int64_t i64; int32_t i32; uint32_t u32; } v = {};
+        HIP_TRY(hipMemcpyAsync(&v, static_cast<const char*>(src.ids) + h_bad * decode_elem_bytes(src.kind), decode_elem_bytes(src.kind), hipMemcpyDeviceToHost, hs));
+        if (src.offs) {
+            h_offs.resize(S + 1);
+            HIP_TRY(hipMemcpyAsync(h_offs.data(), src.offs, (size_t)(S + 1) * 8, hipMemcpyDeviceToHost, hs));
+        }
+        HIP_TRY(hipStreamSynchronize(hs));
+        x = src.kind == tgx::kDecodeI64 ? v.i64 : src.kind == tgx::kDecodeI32 ? (int64_t)v.i32 : (int64_t)v.u32;
+        const uint64_t row = src.offs ? (uint64_t)(std::upper_bound(h_offs.begin(), h_offs.end(), (uint64_t)h_bad) - h_offs.begin()) - 1 : h_bad / src.row_len;
+        guard.done();
+        return decode_oob(src.kind, x, row, bad_sample, bad_id);
+    }
+    const uint64_t T = h_raw;
+    if (T == 0) {
+        HIP_TRY(t->d_bytes.alloc(dev, 0));
+        HIP_TRY(hipMemsetAsync(t->d_offs, 0, (size_t)(S + 1) * 8, hs));
+        HIP_TRY(hipStreamSynchronize(hs));
+        guard.done();
+        *out = text.release();
+        return TGX_OK;
+    }
+    const uint64_t G = (T + tgx::kDecodeGroup - 1) / tgx::kDecodeGroup;
+    HIP_TRY(raw.alloc(dev, (size_t)G * tgx::kDecodeGroup + 16));
+    HIP_TRY(guard.alloc((size_t)G * 4, &flags));
+    HIP_TRY(guard.alloc((size_t)(G + 1) * 4, &codes));
+    p.n_raw = T;
+    p.raw = raw;
+    p.flags = flags;
+    p.codes = codes;
+    if (h_specials) {  // only then can a run end inside a row
+        HIP_TRY(guard.alloc((size_t)(N + 1) * 8, &specials));
+        p.specials = specials;
+        HIP_TRY(tgx::launch_decode_specials(p, scan, scan_bytes, hs));
+    }
+    HIP_TRY(tgx::launch_decode_fill(p, hs));
+    HIP_TRY(tgx::launch_decode_rows(p, hs));
+    HIP_TRY(tgx::launch_decode_utf8(p, hs));
+    HIP_TRY(hipMemcpyAsync(&h_replaced, ctrl + 1, 8, hipMemcpyDeviceToHost, hs));
+    HIP_TRY(hipStreamSynchronize(hs));
+    t->n_replaced = h_replaced;
+    if (h_replaced == 0) {  // the raw bytes are the text and the rows' raw starts its offsets
+        t->d_bytes = std::move(raw);
+        t->n_bytes = T;
+        guard.done();
+        *out = text.release();
+        return TGX_OK;
+    }
+    size_t scan2_bytes = 0;
+    if (tgx::decode_expand_temp_bytes(G, &scan2_bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan temp-size query failed");
+    HIP_TRY(guard.alloc((size_t)(G + 1) * 8, &gpos));
+    HIP_TRY(guard.alloc(scan2_bytes, &scan2));
+    p.gpos = gpos;
+    HIP_TRY(tgx::launch_decode_positions(p, scan2, scan2_bytes, hs));
+    HIP_TRY(hipMemcpyAsync(&h_final, gpos + G, 8, hipMemcpyDeviceToHost, hs));
+    HIP_TRY(hipStreamSynchronize(hs));
+    HIP_TRY(t->d_bytes.alloc(dev, (size_t)h_final + 16));
+    p.out = t->d_bytes;
+    HIP_TRY(tgx::launch_decode_expand(p, hs));
+    HIP_TRY(hipStreamSynchronize(hs));
+    t->n_bytes = h_final;
+    guard.done();
+    *out = text.release();
+    return TGX_OK;
+}
+
+}  // namespace
+
+tgx_status tgx_decode_result(tgx_model* m, const tgx_result* r, const uint8_t* special_bytes, const uint64_t* special_offs, uint32_t n_specials,
+                             int include_special, void* stream, tgx_text** out, uint64_t* bad_sample, uint64_t* bad_id) {
+    const char* who = "tgx_decode_result";
+    if (!m || !r || !out) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
+    *out = nullptr;
+    tgx_status st = decode_check_specials(who, m->vocab_size, special_bytes, special_offs, n_specials);
+    if (st != TGX_OK) return st;
+    if ((st = require_device()) != TGX_OK) return st;
+    if (r->device != m->device) return fail(TGX_ERR_INVALID, "%s: the result is on device %d, the model on device %d", who, r->device, m->device);
+    if ((uint64_t)r->vocab_size > (uint64_t)m->vocab_size + n_specials)
+        return fail(TGX_ERR_INVALID, "%s: the result was written for %u ids, the model has %u tokens and %u special tokens", who, r->vocab_size,
+                    m->vocab_size, n_specials);
+    DeviceScope scope;
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t hs = stream_or_default(stream, m->device);
+    tgx::DecodeSrc src = {};
+    src.ids = r->d_ids.get();
+    src.offs = r->d_offs.get();
+    src.n_rows = r->n_samples;
+    src.n = r->n_tokens;
+    src.kind = tgx::kDecodeU32;
+    src.skip_id = TGX_NO_ID;
+    return decode_device(m, src, special_bytes, special_offs, n_specials, include_special, hs, out, bad_sample, bad_id);
+}
+
+tgx_status tgx_decode_padded(tgx_model* m, const void* d_ids, uint64_t n_rows, uint64_t row_len, uint32_t flags, const uint8_t* d_mask,
+                             const int32_t* d_lengths, uint32_t skip_id, const uint8_t* special_bytes, const uint64_t* special_offs,
+                             uint32_t n_specials, int include_special, void* stream, tgx_text** out, uint64_t* bad_sample, uint64_t* bad_id) {
+    const char* who = "tgx_decode_padded";
+    if (!m || !out) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
+    *out = nullptr;
+    tgx_status st = layout_check_flags(who, flags, TGX_LAYOUT_I64);
+    if (st == TGX_OK) st = decode_check_specials(who, m->vocab_size, special_bytes, special_offs, n_specials);
+    if (st != TGX_OK) return st;
+    if (n_rows && row_len && n_rows > 0xFFFFFFFFFFFFFFFFull / 16 / row_len) return fail(TGX_ERR_UNSUPPORTED, "%s: %llu rows of %llu elements", who, (unsigned long long)n_rows, (unsigned long long)row_len);
+    const uint64_t N = n_rows * row_len;
+    if (N && !d_ids) return fail(TGX_ERR_INVALID, "%s: d_ids is NULL", who);
+    if ((st = require_device()) != TGX_OK) return st;
+    DeviceScope scope;
+    HIP_TRY(hipSetDevice(m->device));
+    if (N) {
+        if ((st = check_device_ptr(who, "d_ids", d_ids, m->device, "model")) != TGX_OK) return st;
+        if ((st = check_device_ptr(who, "d_mask", d_mask, m->device, "model")) != TGX_OK) return st;
+        if ((st = check_device_ptr(who, "d_lengths", d_lengths, m->device, "model")) != TGX_OK) return st;
+    }
+    hipStream_t hs = stream_or_default(stream, m->device);
+    tgx::DecodeSrc src = {};
+    src.ids = d_ids;
+    src.mask = d_mask;
+    src.lengths = d_lengths;
+    src.n_rows = n_rows;
+    src.row_len = row_len;
+    src.n = N;
+    src.kind = (flags & TGX_LAYOUT_I64) ? tgx::kDecodeI64 : tgx::kDecodeI32;
+    src.skip_id = skip_id;
+    return decode_device(m, src, special_bytes, special_offs, n_specials, include_special, hs, out, bad_sample, bad_id);
+}
+
+uint64_t tgx_text_num_rows(const tgx_text* t) { return t ? t->n_rows : 0; }
+uint64_t tgx_text_num_bytes(const tgx_text* t) { return t ? t->n_bytes : 0; }
+uint64_t tgx_text_num_replaced(const tgx_text* t) { return t ? t->n_replaced : 0; }
+int tgx_text_device(const tgx_text* t) { return t ? t->device : -1; }
+const void* tgx_text_bytes_device(const tgx_text* t) { return t ? t->d_bytes.get() : nullptr; }
+const void* tgx_text_offsets_device(const tgx_text* t) { return t ? t->d_offs.get() : nullptr; }
+// (the call that made it returned after its stream had reached its end: the buffers go straight back to the pool)
+void tgx_text_free(tgx_text* t) { delete t; }
+
+tgx_status tgx_text_copy_bytes(const tgx_text* t, uint8_t* dst, uint64_t cap) {
+    if (!t || (!dst && t->n_bytes)) return fail(TGX_ERR_INVALID, "tgx_text_copy_bytes: NULL argument");
+    if (cap < t->n_bytes) return fail(TGX_ERR_INVALID, "tgx_text_copy_bytes: %llu bytes, room for %llu", (unsigned long long)t->n_bytes, (unsigned long long)cap);
+    if (!t->n_bytes) return TGX_OK;
+    DeviceScope scope;
+    HIP_TRY(hipSetDevice(t->device));
+    HIP_TRY(copy_sync(dst, t->d_bytes, t->n_bytes, hipMemcpyDeviceToHost, t->device));
+    return TGX_OK;
+}
+
+tgx_status tgx_text_copy_offsets(const tgx_text* t, uint64_t* dst, uint64_t cap) {
+    if (!t || !dst) return fail(TGX_ERR_INVALID, "tgx_text_copy_offsets: NULL argument");
+    if (cap < t->n_rows + 1) return fail(TGX_ERR_INVALID, "tgx_text_copy_offsets: %llu offsets, room for %llu", (unsigned long long)(t->n_rows + 1), (unsigned long long)cap);
+    DeviceScope scope;
+    HIP_TRY(hipSetDevice(t->device));
+    HIP_TRY(copy_sync(dst, t->d_offs, (t->n_rows + 1) * 8, hipMemcpyDeviceToHost, t->device));
+    return TGX_OK;
+}
+
+// ---- fill-in-the-middle: a result's rows rearranged behind three sentinels (fim.hip; fim.h has the index arithmetic) ----
+
+namespace {
+
+// device time of the last tgx_result_fim of this thread, per stage (tgx_fim_last_times)
+constexpr int kFimStages = 3;
+const char* const kFimStageNames[kFimStages] = {"fim_offsets_scan", "fim_fill_kernel", "fim_info_kernel"};
+thread_local float g_fim_ms[kFimStages] = {0, 0, 0};
+
+}  // namespace
+
+int tgx_fim_last_times(const char** names, float* ms, int cap) { return stage_times(kFimStageNames, g_fim_ms, kFimStages, names, ms, cap); }
+
+tgx_status tgx_result_from_ids(int device, const uint32_t* ids, const uint64_t* offs, uint64_t n_rows, uint32_t vocab_size, tgx_result** out) {
+    const char* who = "tgx_result_from_ids";
+    if (!out) return fail(TGX_ERR_INVALID, "%s: out is NULL", who);
+    *out = nullptr;
+    tgx_status st = result_check_host(who, ids, offs, n_rows, vocab_size);
+    if (st != TGX_OK) return st;
+    int n_devices = 0;
+    if ((st = require_device(&n_devices)) != TGX_OK) return st;
+    if (device < 0 || device >= n_devices) return fail(TGX_ERR_INVALID, "%s: device %d of %d", who, device, n_devices);
+    DeviceScope scope;
+    HIP_TRY(hipSetDevice(device));
+    std::unique_ptr<tgx_result> r(new tgx_result());
+    r->device = device;
+    r->vocab_size = vocab_size;
+    r->n_samples = n_rows;
+    r->n_tokens = offs[n_rows];
+    if (r->d_offs.alloc(device, (size_t)(n_rows + 1) * 8) != hipSuccess || r->d_ids.alloc(device, (size_t)r->n_tokens * 4 + 256) != hipSuccess)
+        return fail(TGX_ERR_DEVICE, "out of device memory (result from ids)");
+    HIP_TRY(copy_sync(r->d_offs, offs, (size_t)(n_rows + 1) * 8, hipMemcpyHostToDevice, device));
+    if (r->n_tokens) HIP_TRY(copy_sync(r->d_ids, ids, (size_t)r->n_tokens * 4, hipMemcpyHostToDevice, device));
+    *out = r.release();
+    return TGX_OK;
+}
+
+tgx_status tgx_result_fim(const tgx_result* r, uint32_t prefix_id, uint32_t suffix_id, uint32_t middle_id, double rate, double spm_rate,
+                          uint64_t seed, uint64_t first_row, void* stream, uint8_t* mode, uint64_t* cuts, uint64_t* n_applied, tgx_result** out) {
+    const char* who = "tgx_result_fim";
+    if (!r || !out) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
+    *out = nullptr;
+    tgx_status st = fim_check(who, prefix_id, suffix_id, middle_id, rate, spm_rate);
+    if (st != TGX_OK) return st;
+    const uint64_t S = r->n_samples;
+    DeviceScope scope;
+    HIP_TRY(hipSetDevice(r->device));
+    hipStream_t hs = stream_or_default(stream, r->device);
+    std::unique_ptr<tgx_result> res(new tgx_result());  // before the guard: its buffers go back after the stream's end
+    uint64_t h_total = 0;
+    StageTimer<kFimStages> timer(hs, g_fim_ms);  // (before the guard: its events outlive the stream's work)
+    StreamGuard guard(r->device, hs);
+    res->device = r->device;
+    res->vocab_size = fim_vocab_size(r->vocab_size, prefix_id, suffix_id, middle_id);
+    res->n_samples = S;
+    size_t scan_bytes = 0;
+    if (tgx::fim_scan_temp_bytes(S, &scan_bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan temp-size query failed");
+    void* d_scan = nullptr;
+    if (res->d_offs.alloc(r->device, (size_t)(S + 1) * 8) != hipSuccess || guard.alloc(scan_bytes, &d_scan) != hipSuccess)  // (never NULL: that asks the scan for its size)
+        return fail(TGX_ERR_DEVICE, "out of device memory (fill-in-the-middle)");
+    tgx::FimParams p = {};
+    p.ids = r->d_ids;
+    p.offs = r->d_offs;
+    p.n_rows = S;
+    p.f = tgx::FimArgs{seed, first_row, rate, spm_rate, prefix_id, suffix_id, middle_id};
+    p.out_offs = res->d_offs;
+    timer.begin(0);
+    if (tgx::launch_fim_offsets(p, d_scan, scan_bytes, hs) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan launch failed");
+    timer.end(0);
+    // the one word that visits the host: T' sizes the id buffer
+    if ((st = read_u64(hs, res->d_offs.get() + S, &h_total)) != TGX_OK) return st;
+    if (h_total < r->n_tokens || (h_total - r->n_tokens) % 3 || (h_total - r->n_tokens) / 3 > S)
+        return fail(TGX_ERR_DEVICE, "%s: %llu ids from %llu over %llu rows", who, (unsigned long long)h_total, (unsigned long long)r->n_tokens,
+                    (unsigned long long)S);
+    res->n_tokens = h_total;
+    if (res->d_ids.alloc(r->device, (size_t)h_total * 4 + 256) != hipSuccess) return fail(TGX_ERR_DEVICE, "out of device memory (fill-in-the-middle)");
+    p.n_out = h_total;
+    p.out_ids = res->d_ids;
+    timer.begin(1);
+    if (tgx::launch_fim_fill(p, hs) != hipSuccess) return fail(TGX_ERR_DEVICE, "fim_fill_kernel launch failed");
+    timer.end(1);
+    if (S && (mode || cuts)) {
+        uint8_t* d_mode = nullptr;
+        uint64_t* d_cuts = nullptr;
+        if (mode) HIP_TRY(guard.alloc((size_t)S, &d_mode));
+        if (cuts) HIP_TRY(guard.alloc((size_t)S * 16, &d_cuts));
+        timer.begin(2);
+        if (tgx::launch_fim_info(p, d_mode, d_cuts, hs) != hipSuccess) return fail(TGX_ERR_DEVICE, "fim_info_kernel launch failed");
+        timer.end(2);
+        if (mode) HIP_TRY(hipMemcpyAsync(mode, d_mode, (size_t)S, hipMemcpyDeviceToHost, hs));
+        if (cuts) HIP_TRY(hipMemcpyAsync(cuts, d_cuts, (size_t)S * 16, hipMemcpyDeviceToHost, hs));
+    }
+    // the stream has reached its end before either result can change hands (the guard: also after a failure)
+    HIP_TRY(hipStreamSynchronize(hs));
+    guard.done();
+    timer.read();
+    if (n_applied) *n_applied = (h_total - r->n_tokens) / 3;
+    *out = res.release();
+    return TGX_OK;
+}
+
+// ---- spans: the part of its row's text that every token covers (spans.hip; spans.h has the index arithmetic) ------
+
+namespace {
+
+// the model's token words on its device, once (under m->mu)
+tgx_status ensure_span_words(tgx_model* m) {
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (m->span_words_ready) return TGX_OK;
+    const uint32_t V = m->vocab_size;
+    std::vector<uint16_t> words;
+    const tgx_status st = span_build_words("spans", m->vocab_bytes.data(), m->vocab_offs.data(), V, &words);
+    if (st != TGX_OK) return st;
+    if (!m->d_span_words) HIP_TRY(hipMalloc((void**)&m->d_span_words, ((size_t)V + 8) * 2));
+    if (V) HIP_TRY(hipMemcpy(m->d_span_words, words.data(), (size_t)V * 2, hipMemcpyHostToDevice));
+    m->span_words_ready = true;
+    return TGX_OK;
+}
+
+// The first half of a spans call over a result with T >= 1 tokens: the model's words, the specials' words, the value
+// words and their prefix sums in pooled scratch of the guard, and for int32 spans the check of the rows' totals (one
+// word is read back; nothing has been written to the destination when a row does not fit).  Fills p's tables, source
+// and scratch; p->flags is set by the caller.
+tgx_status span_sums_device(const char* who, tgx_model* m, const tgx_result* r, const uint8_t* special_bytes, const uint64_t* special_offs,
+                            uint32_t n_specials, hipStream_t hs, StreamGuard& guard, tgx::SpanParams* p) {
+    const bool chars = (p->flags & TGX_SPAN_CHARS) != 0, i64 = (p->flags & TGX_LAYOUT_I64) != 0;
+    const uint64_t T = r->n_tokens;
+    const tgx_status st = ensure_span_words(m);
+    if (st != TGX_OK) return st;
+    std::vector<uint64_t> sp_words;
+    span_special_words(special_bytes, special_offs, n_specials, chars, &sp_words);
+    size_t scan_bytes = 0;
+    if (tgx::span_scan_temp_bytes(T, &scan_bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan temp-size query failed");
+    uint32_t* vals = nullptr;
+    uint64_t *sums = nullptr, *d_sp_words = nullptr;
+    void* scan = nullptr;
+    HIP_TRY(guard.alloc((size_t)(T + 1) * 4, &vals));
+    HIP_TRY(guard.alloc((size_t)(T + 1) * 8, &sums));
+    HIP_TRY(guard.alloc(scan_bytes, &scan));  // (never NULL: that asks the scan for its size)
+    HIP_TRY(guard.alloc(sp_words.size() * 8, &d_sp_words));
+    HIP_TRY(guard.upload(d_sp_words, std::move(sp_words)));
+    p->tab.words = m->d_span_words;
+    p->tab.sp_words = d_sp_words;
+    p->tab.vocab_size = m->vocab_size;
+    p->tab.n_specials = n_specials;
+    p->ids = r->d_ids;
+    p->offs = r->d_offs;
+    p->n_rows = r->n_samples;
+    p->n = T;
+    p->vals = vals;
+    p->sums = sums;
+    HIP_TRY(tgx::launch_span_sums(*p, scan, scan_bytes, hs));
+    if (!i64) {  // nothing is written when a row does not fit: the one word that is read back
+        unsigned long long h_max = 0, *row_max = nullptr;
+        HIP_TRY(guard.alloc(sizeof(unsigned long long), &row_max));
+        p->row_max = row_max;
+        HIP_TRY(hipMemsetAsync(row_max, 0, sizeof(unsigned long long), hs));
+        HIP_TRY(tgx::launch_span_row_max(*p, hs));
+        HIP_TRY(hipMemcpyAsync(&h_max, row_max, sizeof(unsigned long long), hipMemcpyDeviceToHost, hs));
+        HIP_TRY(hipStreamSynchronize(hs));
+        if (h_max >= 0x80000000ull) return span_too_long(who, h_max, chars);
+    }
+    return TGX_OK;
+}
+
+// row_len = 0: the flat form
+tgx_status spans_device(const char* who, tgx_model* m, const tgx_result* r, const uint8_t* special_bytes, const uint64_t* special_offs,
+                        uint32_t n_specials, uint32_t row_len, uint32_t bos_id, uint32_t eos_id, uint32_t flags, void* stream, void* d_spans) {
+    if (!m || !r) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
+    const bool padded = row_len != 0;
+    const tgx_status st0 = span_check_args(who, m->vocab_size, special_bytes, special_offs, n_specials, padded, row_len, bos_id, eos_id, flags);
+    if (st0 != TGX_OK) return st0;
+    const uint64_t S = r->n_samples, T = r->n_tokens;
+    const uint64_t n_pairs = padded ? S * (uint64_t)row_len : (S ? T : 0);
+    if (!d_spans && n_pairs) return fail(TGX_ERR_INVALID, "%s: d_spans is NULL", who);
+    tgx_status st = require_device();
+    if (st != TGX_OK) return st;
+    if (r->device != m->device) return fail(TGX_ERR_INVALID, "%s: the result is on device %d, the model on device %d", who, r->device, m->device);
+    if ((uint64_t)r->vocab_size > (uint64_t)m->vocab_size + n_specials)
+        return fail(TGX_ERR_INVALID, "%s: the result was written for %u ids, the model has %u tokens and %u special tokens", who, r->vocab_size,
+                    m->vocab_size, n_specials);
+    if (n_pairs == 0) return TGX_OK;
+    DeviceScope scope;
+    HIP_TRY(hipSetDevice(m->device));
+    if ((st = check_device_ptr(who, "d_spans", d_spans, m->device, "result")) != TGX_OK) return st;
+    hipStream_t hs = stream_or_default(stream, m->device);
+    const int dev = m->device;
+    const bool i64 = (flags & TGX_LAYOUT_I64) != 0;
+    if (T == 0) {  // the padded form of rows without tokens
+        StreamGuard guard(dev, hs);
+        HIP_TRY(hipMemsetAsync(d_spans, 0, (size_t)n_pairs * 2 * (i64 ? 8 : 4), hs));
+        HIP_TRY(hipStreamSynchronize(hs));
+        guard.done();
+        return TGX_OK;
+    }
+    StreamGuard guard(dev, hs);
+    tgx::SpanParams p = {};
+    p.len = row_len;
+    p.bos = bos_id;
+    p.eos = eos_id;
+    p.flags = flags;
+    p.out = d_spans;
+    if ((st = span_sums_device(who, m, r, special_bytes, special_offs, n_specials, hs, guard, &p)) != TGX_OK) return st;
+    HIP_TRY(padded ? tgx::launch_span_pad(p, hs) : tgx::launch_span_flat(p, hs));
+    // the stream has reached its end before the result or the destination can change hands
+    HIP_TRY(hipStreamSynchronize(hs));
+    guard.done();
+    return TGX_OK;
+}
+
+}  // namespace
+
+tgx_status tgx_result_spans_device(tgx_model* m, const tgx_result* r, const uint8_t* special_bytes, const uint64_t* special_offs,
+                                   uint32_t n_specials, uint32_t flags, void* stream, void* d_spans) {
+    return spans_device("tgx_result_spans_device", m, r, special_bytes, special_offs, n_specials, 0, TGX_NO_ID, TGX_NO_ID, flags, stream, d_spans);
+}
+
+tgx_status tgx_result_pad_spans_device(tgx_model* m, const tgx_result* r, const uint8_t* special_bytes, const uint64_t* special_offs,
+                                       uint32_t n_specials, uint32_t row_len, uint32_t bos_id, uint32_t eos_id, uint32_t flags, void* stream,
+                                       void* d_spans) {
+    const char* who = "tgx_result_pad_spans_device";
+    if (row_len == 0) return fail(TGX_ERR_INVALID, "%s: row_len 0 (needs >= 1)", who);
+    return spans_device(who, m, r, special_bytes, special_offs, n_specials, row_len, bos_id, eos_id, flags, stream, d_spans);
+}
+
+tgx_status tgx_result_window_spans_device(tgx_model* m, const tgx_result* r, const uint8_t* special_bytes, const uint64_t* special_offs,
+                                          uint32_t n_specials, uint32_t row_len, uint32_t stride, uint32_t bos_id, uint32_t eos_id, uint32_t flags,
+                                          void* stream, uint64_t n_windows, void* d_spans) {
+    const char* who = "tgx_result_window_spans_device";
+    if (!m || !r) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
+    if (row_len == 0) return fail(TGX_ERR_INVALID, "%s: row_len 0 (needs >= 1)", who);
+    tgx_status st = span_check_args(who, m->vocab_size, special_bytes, special_offs, n_specials, true, row_len, bos_id, eos_id, flags);
+    const tgx::LayoutSeq seq = tgx::layout_seq(bos_id, eos_id, 0);
+    if (st == TGX_OK) st = window_check_args(who, row_len, stride, seq.extra);
+    if (st != TGX_OK) return st;
+    const uint64_t S = r->n_samples, T = r->n_tokens;
+    if (!d_spans && S) return fail(TGX_ERR_INVALID, "%s: d_spans is NULL", who);
+    if ((st = require_device()) != TGX_OK) return st;
+    if (r->device != m->device) return fail(TGX_ERR_INVALID, "%s: the result is on device %d, the model on device %d", who, r->device, m->device);
+    if ((uint64_t)r->vocab_size > (uint64_t)m->vocab_size + n_specials)
+        return fail(TGX_ERR_INVALID, "%s: the result was written for %u ids, the model has %u tokens and %u special tokens", who, r->vocab_size,
+                    m->vocab_size, n_specials);
+    if (S == 0) return window_check_totals(who, 0, 0, &n_windows);
+    DeviceScope scope;
+    HIP_TRY(hipSetDevice(m->device));
+    if ((st = check_device_ptr(who, "d_spans", d_spans, m->device, "result")) != TGX_OK) return st;
+    hipStream_t hs = stream_or_default(stream, m->device);
+    StreamGuard guard(m->device, hs);
+    const uint64_t* d_wo = nullptr;
+    uint64_t W = 0;
+    st = window_offsets_device(who, r, row_len - seq.extra, row_len - seq.extra - stride, hs, guard, &d_wo, &W);
+    if (st == TGX_OK) st = window_check_totals(who, 0, W, &n_windows);
+    if (st != TGX_OK) return st;
+    if (T == 0) {  // rows without tokens: W = S windows of padding
+        HIP_TRY(hipMemsetAsync(d_spans, 0, (size_t)W * row_len * 2 * ((flags & TGX_LAYOUT_I64) ? 8 : 4), hs));
+    } else {
+        tgx::SpanParams p = {};
+        p.len = row_len;
+        p.bos = bos_id;
+        p.eos = eos_id;
+        p.flags = flags;
+        p.out = d_spans;
+        if ((st = span_sums_device(who, m, r, special_bytes, special_offs, n_specials, hs, guard, &p)) != TGX_OK) return st;
+        HIP_TRY(tgx::launch_span_windows(p, d_wo, stride, W, hs));
+    }
+    // the stream has reached its end before the result or the destination can change hands
+    HIP_TRY(hipStreamSynchronize(hs));
+    guard.done();
+    return TGX_OK;
+}

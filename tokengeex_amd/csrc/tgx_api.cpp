@@ -2,6 +2,8 @@
 // sequencing, error reporting.  Host side of the reference's batch loops
 // (src/tokenizer.rs:102-123, src/prune.rs:205-244); there is no CPU fallback —
 // without a usable gfx950 device every compute entry point returns TGX_ERR_DEVICE.
+// Here: the error state, the buffer pool, models and corpora, and every pass on a model's own streams.  The transforms
+// of a resident result or corpus on a caller's stream are in result_ops.cpp and corpus_ops.cpp (device_internal.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -24,20 +26,16 @@
 
 #include "../../include/tgx.h"
 #include "api_internal.h"
-#include "assemble.h"
-#include "decode.h"
-#include "front.h"
+#include "device_internal.h"
 #include "kernels.h"
-#include "layout.h"
 #include "ids_in_place.h"
 #include "lean_gate.h"
-#include "spans.h"
 #include "nbest.h"
-#include "norm.h"
 #include "sample.h"
 #include "trie_build.h"
 
 using namespace tgx::host;
+using namespace tgx::dev;
 
 // shared with prune_host.cpp: records the message tgx_last_error() returns (thread-local)
 tgx_status tgx_set_error(tgx_status st, const char* msg) {
@@ -45,14 +43,6 @@ tgx_status tgx_set_error(tgx_status st, const char* msg) {
     return st;
 }
 namespace {
-
-#define HIP_TRY(expr)                                                                     \
-    do {                                                                                  \
-        hipError_t _e = (expr);                                                           \
-        if (_e != hipSuccess)                                                             \
-            return fail(TGX_ERR_DEVICE, "HIP error %d (%s) at %s:%d: %s", (int)_e,        \
-                        hipGetErrorString(_e), __FILE__, __LINE__, #expr);                \
-    } while (0)
 
 // ---- device buffer pool --------------------------------------------------------
 // hipMalloc/hipFree cost far more than a kernel launch; scratch and result
@@ -66,6 +56,10 @@ std::mutex g_pool_mu;
 std::vector<PoolEntry> g_pool;
 size_t g_pool_bytes = 0;
 constexpr size_t kPoolMaxBytes = 64ull << 30;
+
+}  // namespace
+
+namespace tgx::dev {
 
 // hipFree of every pooled buffer of `device` (all devices if < 0); the caller's current device is kept
 void pool_trim(int device) {
@@ -127,7 +121,7 @@ size_t rounded(size_t bytes) {
 }
 
 // Pooled bytes per process: at most a quarter of the device's memory (and never more than kPoolMaxBytes).
-size_t pool_cap(int device) {
+static size_t pool_cap(int device) {
     static size_t cap[16] = {0};
     if (device < 0 || device >= 16) return kPoolMaxBytes;
     if (cap[device] == 0) {
@@ -160,251 +154,12 @@ void pool_free(int device, void* ptr, size_t bytes) {
     if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
 }
 
-// A pooled device buffer with one owner: (device, ptr, bytes), bytes being the rounded size it was asked with (what the
-// pool files it under).  It goes back to the pool exactly once: on reset(), on the next alloc() or with its owner.
-template <class T>
-class PoolBuf {
-public:
-    PoolBuf() = default;
-    PoolBuf(const PoolBuf&) = delete;
-    PoolBuf& operator=(const PoolBuf&) = delete;
-    PoolBuf(PoolBuf&& o) noexcept : device_(o.device_), ptr_(o.ptr_), bytes_(o.bytes_) { o.ptr_ = nullptr; }
-    PoolBuf& operator=(PoolBuf&& o) noexcept {
-        if (this != &o) {
-            reset();
-            device_ = o.device_;
-            ptr_ = o.ptr_;
-            bytes_ = o.bytes_;
-            o.ptr_ = nullptr;
-        }
-        return *this;
-    }
-    ~PoolBuf() { reset(); }
-
-    hipError_t alloc(int device, size_t bytes) {
-        reset();
-        void* p = nullptr;
-        const hipError_t e = pool_alloc(device, bytes, &p);
-        if (e != hipSuccess) return e;
-        device_ = device;
-        ptr_ = static_cast<T*>(p);
-        bytes_ = rounded(bytes);
-        return hipSuccess;
-    }
-    void reset() {
-        if (ptr_) pool_free(device_, ptr_, bytes_);
-        ptr_ = nullptr;
-    }
-    T* get() const { return ptr_; }
-    operator T*() const { return ptr_; }
-
-private:
-    int device_ = 0;
-    T* ptr_ = nullptr;
-    size_t bytes_ = 0;
-};
-
-struct KernelTime {
-    const char* name;
-    hipEvent_t start, stop;
-    bool used;
-};
-constexpr int kMaxTimed = 8;
-// encode5_kernel: the depth at which a trip's live walks are compacted (0: never; TGX_E5_COMPACT=off|4..8 overrides)
-constexpr int kE5CompactDepth = 5;
-
-// The model's control words in device memory: the counters and flags its kernels share with the host, one member per
-// role (this is the only place that says which kernel uses which).  Kernels take `unsigned long long*` to a member.  A
-// pass holds m->mu, so one pass uses them at a time; each pass resets the ones it reads.
-struct DeviceCtrl {
-    unsigned long long queue;        // work queue of encode4 / encode4l / encode2 / encode5_kernel and the sampling kernels
-    unsigned long long err;          // lowest failing sample (encode, sampling, n-best) or snippet (E-step); ~0: none
-    unsigned long long queue6;       // encode6_kernel's own work queue when it runs beside encode5_kernel (co-run)
-    struct Estep {                   // contiguous: an E-step pass clears these with ONE hipMemsetAsync over `estep`
-        unsigned long long queue;       // estep7_kernel, estep7_redo_kernel, the forward kernels of estep4 / estep4l / estep5
-        unsigned long long redo_count;  // estep7_kernel: stretches left to estep7_redo_kernel
-        unsigned long long queue_bwd;   // the backward kernels of estep4 / estep4l
-        unsigned long long range_flag;  // every linear-domain E-step kernel: the pass belongs to the log-domain kernels
-    } estep;
-    unsigned long long encode_redo;  // encode4l_kernel, the LONG build of encode5_kernel: samples left to encode2_kernel
-    unsigned long long longest;      // estep_pieces_build: the longest piece (piece_len_kernel)
-    unsigned long long err_piece;    // err_snip of the chained E-step kernels on pieces (z is checked per snippet afterwards)
-};
-static_assert(offsetof(DeviceCtrl::Estep, redo_count) == 8 && offsetof(DeviceCtrl::Estep, queue_bwd) == 16 &&
-                  offsetof(DeviceCtrl::Estep, range_flag) == 24 && sizeof(DeviceCtrl::Estep) == 32,
-              "the E-step words are cleared by one memset");
-// what a pass reads back into page-locked host memory
-struct HostCtrl {
-    unsigned long long err;           // DeviceCtrl::err
-    unsigned long long total_tokens;  // the last entry of the scanned token counts
-};
-
-}  // namespace
-
-struct tgx_model {
-    int device = 0;
-    uint32_t vocab_size = 0;
-    uint32_t lm = 0;  // max token length rounded up to a multiple of 4 (>= 4)
-    bool scores_finite = true;  // the four-samples-per-wave kernel encodes 'no token' as -inf
-    tgx::FlatTrie flat;
-    void* d_trie = nullptr;
-    uint32_t* d_tokid = nullptr;
-    DeviceCtrl* d_ctrl = nullptr;
-    HostCtrl* h_ctrl = nullptr;  // page-locked
-    hipStream_t stream = nullptr;
-    hipStream_t stream2 = nullptr;          // encode6_kernel beside encode5_kernel (run_encode_kernel: co-run)
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    unsigned int* h_started = nullptr;      // page-locked, device-visible: blocks of encode5_kernel that are resident (co-run)
-    int num_cus = 0;
-    int blocks_per_cu = 0;  // encode_kernel (one sample per wave)
-    // E-step only (built on first use): trie of the reversed tokens
-    std::vector<uint8_t> vocab_bytes;
-    std::vector<uint64_t> vocab_offs;
-    std::vector<double> vocab_scores;
-    tgx::FlatTrie flat_rev;
-    void* d_trie_rev = nullptr;
-    bool rev_host_built = false;    // flat_rev was built at creation (TGX_MODEL_FOR_ESTEP)
-    void* d_trie_w = nullptr;       // forward / reversed tables with w = exp(score) in place of the score
-    void* d_trie_rev_w = nullptr;   //   (linear-domain E-step, estep4l.hip)
-    uint64_t last_long_samples = 0;    // samples the last pass gave a block of their own (encode6_kernel)
-    uint64_t last_estep_pieces = 0;    // pieces the last E-step cut its snippets into (0: uncut)
-    uint32_t last_corun_cus = 0;       // CUs the long-sample kernel had to itself beside encode5_kernel in the last pass (0: one after the other)
-    double e7_overflow_share = 0.0;    // share of the sample's matches whose token ranks beyond 65 535 (ensure_estep_trie8t; 0 without counts)
-    bool values_ranked = false;        // the score values were re-ranked by how often a sample of some corpus reads them (ensure_value_ranks)
-    uint32_t corun_wait_timeouts = 0;  // co-run passes whose host wait for encode5_kernel's blocks ran into its 2 ms limit (then: no more co-runs)
-    uint64_t last_redo_samples = 0;    // samples the last encode4l pass left to encode2_kernel
-    int last_encode_waves_per_cu = 0;  // resident waves per CU of the last rows4 encode launch (self-check)
-    bool estep_linear_ok = false;   // tables for the linear-domain E-step kernels exist
-    tgx::TokHashTable tokhash;      // token bytes -> id (rows4 trace); ok == false: not usable
-    void* d_tokhash = nullptr;
-    // encode5_kernel: 8-byte label-checked records + table of distinct score values (trie_build.h: Trie8)
-    void* d_trie8 = nullptr;
-    double* d_values = nullptr;        // f64[n_values + 1]: -inf, then the distinct score values by rank (trie_build.h: Trie8)
-    std::vector<double> value_coverage;  // [k]: expected share of the matches whose value has rank <= k
-    uint32_t n_values = 0, root_base8 = 0;
-    uint32_t last_n_hot = 0;           // values in the LDS copy of the last encode5 launch
-    bool lean_scores_ok = false;       // every score passes the gate of the lean relaxation step (lean_gate.h)
-    bool last_ids_in_place = false;    // the last encode pass wrote its ids in place (ids_in_place.h): no tmp, no compact_kernel
-    uint32_t last_lean_items = 0;      // lean items of the last pass's encode5_kernel (low byte) and encode6_kernel (next byte); 0: the kernels as they were
-    bool have_trie8 = false;
-    bool encode_tables_ready = false;  // tokhash / trie8 built and uploaded (ensure_encode_tables)
-    bool estep_trie8_tried = false;    // ensure_estep_trie8 ran
-    uint64_t estep_calls = 0;          // E-step passes this model has run (estep_rows4)
-    bool have_wvalues = false;         // d_trie8 / d_wvalues are there for estep5_fwd_kernel
-    double* d_wvalues = nullptr;       // f64[n_values + 1]: [0] = 0, [r] = exp(score value of rank r)
-    bool tokhash_host_built = false;   // m->tokhash was built beside the forward trie at creation
-    // estep7_kernel: token-ranked 8-byte records, w by rank (trie_build.h: Trie8T), built at the first E-step
-    void* d_trie8t = nullptr;
-    double* d_wtab = nullptr;          // f64[n_tok7 + 1]
-    std::vector<uint32_t> id_of_rank;  // [r] = vocabulary id of the token of rank r (1 .. n_tok7)
-    uint32_t n_tok7 = 0, root_base7 = 0;
-    bool trie8t_tried = false, have_trie8t = false;
-    uint64_t last_estep_redo = 0;      // stretches the last fused E-step left to the chained kernels
-    // decode (decode.hip): the tokens' lengths, 16-byte slots and packed bytes, uploaded at the first decode (ensure_decode_tables)
-    uint8_t* d_dec_len = nullptr;
-    void* d_dec_slots = nullptr;
-    uint8_t* d_dec_bytes = nullptr;
-    uint64_t* d_dec_offs = nullptr;
-    bool decode_tables_ready = false;
-    // spans (spans.hip): one packed word per token (spans.h), uploaded at the first call (ensure_span_words)
-    uint16_t* d_span_words = nullptr;
-    bool span_words_ready = false;
-    int estep_blocks_per_cu = 0;
-    KernelTime timed[kMaxTimed] = {};
-    int n_timed = 0;
-    uint64_t last_alg_bytes = 0;
-    std::mutex mu;  // one pass at a time per handle (its stream, counters and events)
-};
-
-struct tgx_corpus {
-    int device = 0;
-    uint64_t n_samples = 0, n_bytes = 0, max_len = 0;  // max_len: longest sample in bytes
-    std::vector<uint64_t> h_offs;
-    std::vector<uint32_t> h_sorted_len;  // sample lengths in the order of d_order (longest first) ...
-    std::vector<uint64_t> h_sorted_cum;  // ... and their running sum
-    PoolBuf<uint8_t> d_text_alloc;
-    uint8_t* d_text = nullptr;        // = d_text_alloc + 256 (the backward E-step sweep reads before a position)
-    PoolBuf<uint64_t> d_offs;
-    PoolBuf<uint32_t> d_order;
-    PoolBuf<uint32_t> d_bp, d_tmp, d_counts, d_status;  // scratch, allocated on first pass (ensure_scratch)
-    PoolBuf<void> d_scan_tmp;
-    size_t scan_tmp_bytes = 0;
-    // E-step work list of the corpus (every sample cut at multiples of snippet_len, longest snippet first) and its
-    // device copies: built on the first pass with a given snippet length, reused by the following ones (prune
-    // runs two E-steps per iteration over the same corpus; building and sorting the list took 5 of 65 ms at 1 GiB)
-    struct EstepWork {
-        uint64_t snippet_len = 0;
-        std::vector<uint64_t> soffs, sbase;
-        std::vector<uint32_t> ssample, order;
-        PoolBuf<uint64_t> d_soffs, d_sbase;
-        PoolBuf<uint32_t> d_order, d_ssample;
-        // windows of the snippets (cuts.hip: one boundary is sought per window): built with the work list
-        uint32_t window = 0;
-        uint64_t n_windows = 0;
-        PoolBuf<uint32_t> d_win_snip, d_win_k;
-    } es;
-    // the scratch above belongs to the corpus, so a pass holds this lock too (always after its model's):
-    // two models may work on one resident corpus from two host threads (prune and merge do, src/prune.rs:48)
-    std::mutex mu;
-};
-
-struct tgx_result {
-    int device = 0;
-    uint32_t vocab_size = 0;  // of the model that wrote it: every id is below it
-    uint64_t n_samples = 0, n_tokens = 0;
-    PoolBuf<uint32_t> d_ids;
-    PoolBuf<uint64_t> d_offs;
-    std::unique_ptr<uint32_t[]> h_ids;  // uninitialised: a vector would zero a GB first
-    std::vector<uint64_t> h_offs;
-    bool have_ids = false, have_offs = false;
-};
+}  // namespace tgx::dev
 
 namespace {
 
-// One pass over a corpus (encode, sampling, n-best, a frequency, pair or E-step pass, a re-rank of a model's tables): it
-// owns the pass's scratch and the result it builds.  A pass that fails may have queued kernels that still read or write
-// those buffers, the corpus's scratch or the result, so the model's streams are synchronised before anything goes back to
-// the pool, where another caller could take it.  A pass that succeeds says so with done(): every success path has
-// synchronised its stream already (or ended in a synchronous copy), and gains no synchronisation here.
-class Pass {
-public:
-    explicit Pass(tgx_model* m) : m_(m) {}
-    Pass(const Pass&) = delete;
-    Pass& operator=(const Pass&) = delete;
-    ~Pass() {
-        if (ok_) return;
-        (void)hipStreamSynchronize(m_->stream);
-        if (m_->stream2) (void)hipStreamSynchronize(m_->stream2);
-    }  // (then the members go: the scratch and an unclaimed result)
-
-    template <class T>
-    hipError_t alloc(size_t bytes, T** out) {
-        PoolBuf<void> b;
-        const hipError_t e = b.alloc(m_->device, bytes);
-        *out = static_cast<T*>(b.get());
-        if (e == hipSuccess) scratch_.push_back(std::move(b));
-        return e;
-    }
-    tgx_result* new_result(uint64_t n_samples) {
-        result_.reset(new tgx_result());
-        result_->device = m_->device;
-        result_->vocab_size = m_->vocab_size;
-        result_->n_samples = n_samples;
-        return result_.get();
-    }
-    tgx_result* release_result() { return result_.release(); }
-    void adopt_result(tgx_result* r) { result_.reset(r); }
-    tgx_status done() {
-        ok_ = true;
-        return TGX_OK;
-    }
-
-private:
-    tgx_model* m_;
-    bool ok_ = false;
-    std::vector<PoolBuf<void>> scratch_;
-    std::unique_ptr<tgx_result> result_;
-};
+// encode5_kernel: the depth at which a trip's live walks are compacted (0: never; TGX_E5_COMPACT=off|4..8 overrides)
+constexpr int kE5CompactDepth = 5;
 
 int usable_device_count() {
     int n = 0;
@@ -413,13 +168,6 @@ int usable_device_count() {
         return 0;
     }
     return n;
-}
-// TGX_ERR_DEVICE without a usable HIP device; *n_devices: how many there are
-tgx_status require_device(int* n_devices = nullptr) {
-    const int n = usable_device_count();
-    if (n_devices) *n_devices = n;
-    if (n <= 0) return fail(TGX_ERR_DEVICE, "no usable HIP device (gfx950 required)");
-    return TGX_OK;
 }
 
 // TGX_DEBUG=1: log every launch to stderr and synchronise after it, so that a
@@ -445,6 +193,17 @@ const char* knob(const char* name) {
     return on == 1 ? getenv(name) : nullptr;
 }
 
+}  // namespace
+
+namespace tgx::dev {
+
+tgx_status require_device(int* n_devices) {
+    const int n = usable_device_count();
+    if (n_devices) *n_devices = n;
+    if (n <= 0) return fail(TGX_ERR_DEVICE, "no usable HIP device (gfx950 required)");
+    return TGX_OK;
+}
+
 void time_begin(tgx_model* m, const char* name) {
     if (debug_on()) {
         fprintf(stderr, "[tgx] launch %s\n", name);
@@ -466,6 +225,10 @@ void time_end(tgx_model* m) {
     (void)hipEventRecord(m->timed[m->n_timed].stop, m->stream);
     m->n_timed++;
 }
+
+}  // namespace tgx::dev
+
+namespace {
 
 // the encode and sampling passes' scratch: back-pointers, ids right-aligned in `tmp` (then compacted), counts, status.
 // with_tmp = false: a pass that writes its ids in place (ids_in_place.h) needs no `tmp` — 4 bytes per text byte that a
@@ -1711,7 +1474,7 @@ static hipStream_t copy_stream(int device, int dir) {
     }
     return streams[device][dir];
 }
-static hipError_t copy_sync(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, int device) {
+hipError_t tgx::dev::copy_sync(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, int device) {
     hipStream_t st = copy_stream(device, kind == hipMemcpyHostToDevice ? 0 : 1);
     hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, st);
     if (e != hipSuccess) return e;
@@ -1721,9 +1484,8 @@ static hipError_t copy_sync(void* dst, const void* src, size_t bytes, hipMemcpyK
 // A resident corpus over `text` (host memory, memory of `device`, or bytes the caller writes to d_text itself once this
 // has returned: text is then not read) and host offsets: what tgx_corpus_upload, tgx_corpus_from_text and
 // tgx_corpus_split_specials share, so the three build the same corpus.
-enum class TextFrom { Host, Device, Caller };
-static tgx_status corpus_create(const char* who, int device, const uint8_t* text, TextFrom from, const uint64_t* offs,
-                                uint64_t n_samples, tgx_corpus** out) {
+tgx_status tgx::dev::corpus_create(const char* who, int device, const uint8_t* text, TextFrom from, const uint64_t* offs,
+                                   uint64_t n_samples, tgx_corpus** out) {
     if (!out) return fail(TGX_ERR_INVALID, "%s: out is NULL", who);
     *out = nullptr;
     if (n_samples && !offs) return fail(TGX_ERR_INVALID, "%s: offs is NULL", who);
@@ -2163,23 +1925,9 @@ void tgx_result_free(tgx_result* r) { delete r; }
 int tgx_result_device(const tgx_result* r) { return r ? r->device : -1; }
 uint32_t tgx_result_vocab_size(const tgx_result* r) { return r ? r->vocab_size : 0; }
 
-// ---- layouts: padded rows / packed blocks of a result, in caller-owned device memory (layout.hip) ----------------
+// ---- what the calls on a caller's stream share (device_internal.h; result_ops.cpp, corpus_ops.cpp) -----------------
 
-namespace {
-
-// the calling thread's current device is put back when a layout entry point that had to change it returns
-class DeviceScope {
-public:
-    DeviceScope() { (void)hipGetDevice(&prev_); }
-    ~DeviceScope() {
-        if (prev_ >= 0) (void)hipSetDevice(prev_);
-    }
-    DeviceScope(const DeviceScope&) = delete;
-    DeviceScope& operator=(const DeviceScope&) = delete;
-
-private:
-    int prev_ = -1;
-};
+namespace tgx::dev {
 
 // What a caller gets when it passes no stream of its own: one per device.  It is a BLOCKING stream (hipStreamDefault),
 // so what is queued on it starts after everything queued earlier on the device's null stream, which is where a
@@ -2215,1343 +1963,30 @@ tgx_status check_device_ptr(const char* who, const char* what, const void* p, in
     return TGX_OK;
 }
 
-// One call's work on a caller's stream (or stream_or_default's).  It owns the call's pooled buffers and the host memory
-// its uploads read.  A call that fails may have queued work that still uses them, the result or the caller's
-// destination, so the stream is synchronised before anything goes back to the pool or to the caller.  A call that
-// succeeds has synchronised the stream itself and says so with done().  What must outlive the stream's work and is not
-// the guard's (a tgx_text, a buffer that moves into one, host memory a copy writes) is declared BEFORE the guard.
-// (Pass is the same for a model's own streams.)
-class StreamGuard {
-public:
-    StreamGuard(int device, hipStream_t stream) : device_(device), stream_(stream) {}
-    StreamGuard(const StreamGuard&) = delete;
-    StreamGuard& operator=(const StreamGuard&) = delete;
-    ~StreamGuard() {
-        if (!ok_) (void)hipStreamSynchronize(stream_);
-    }  // (then the members go)
-
-    template <class T>
-    hipError_t alloc(size_t bytes, T** out) {
-        PoolBuf<void> b;
-        const hipError_t e = b.alloc(device_, bytes);
-        *out = static_cast<T*>(b.get());
-        if (e == hipSuccess) bufs_.push_back(std::move(b));
-        return e;
+int stage_times(const char* const* stage_names, const float* stage_ms, int n, const char** names, float* ms, int cap) {
+    int k = 0;
+    for (; k < n && k < cap; k++) {
+        if (names) names[k] = stage_names[k];
+        if (ms) ms[k] = stage_ms[k];
     }
-    // src to dst (device memory) on the stream; src lives as long as the guard
-    hipError_t upload(uint64_t* dst, std::vector<uint64_t> src) {
-        staged_.push_back(std::move(src));
-        return hipMemcpyAsync(dst, staged_.back().data(), staged_.back().size() * 8, hipMemcpyHostToDevice, stream_);
-    }
-    void done() { ok_ = true; }
-
-private:
-    int device_;
-    hipStream_t stream_;
-    bool ok_ = false;
-    std::vector<PoolBuf<void>> bufs_;
-    std::vector<std::vector<uint64_t>> staged_;
-};
-
-}  // namespace
-
-tgx_status tgx_result_layout_info(const tgx_result* r, uint32_t bos_id, uint32_t eos_id, uint64_t* max_row_len, uint64_t* n_stream) {
-    if (!r) return fail(TGX_ERR_INVALID, "tgx_result_layout_info: result is NULL");
-    const uint64_t A = (bos_id != TGX_NO_ID ? 1 : 0) + (eos_id != TGX_NO_ID ? 1 : 0);
-    if (n_stream) *n_stream = r->n_tokens + r->n_samples * A;
-    if (!max_row_len) return TGX_OK;
-    *max_row_len = A;
-    if (r->n_samples == 0 || r->n_tokens == 0) return TGX_OK;
-    DeviceScope scope;
-    HIP_TRY(hipSetDevice(r->device));
-    hipStream_t st = stream_or_default(nullptr, r->device);
-    unsigned long long h_max = 0, *d_max = nullptr;
-    StreamGuard guard(r->device, st);
-    HIP_TRY(guard.alloc(sizeof(unsigned long long), &d_max));
-    HIP_TRY(hipMemsetAsync(d_max, 0, sizeof(unsigned long long), st));
-    HIP_TRY(tgx::launch_layout_max_row(r->d_offs, r->n_samples, d_max, st));
-    HIP_TRY(hipMemcpyAsync(&h_max, d_max, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    guard.done();
-    *max_row_len = h_max + A;
-    return TGX_OK;
+    return k;
 }
 
-tgx_status tgx_result_pad_device(const tgx_result* r, uint32_t row_len, uint32_t pad_id, uint32_t bos_id, uint32_t eos_id,
-                                 uint32_t flags, void* stream, void* d_ids, uint8_t* d_mask, int32_t* d_lengths,
-                                 uint64_t* n_truncated) {
-    const char* who = "tgx_result_pad_device";
-    if (!r) return fail(TGX_ERR_INVALID, "%s: result is NULL", who);
-    if (!d_ids && r->n_samples) return fail(TGX_ERR_INVALID, "%s: d_ids is NULL", who);
-    tgx_status st = layout_check_flags(who, flags, TGX_LAYOUT_PAD_LEFT | TGX_LAYOUT_TRUNC_LEFT | TGX_LAYOUT_I64);
-    if (st == TGX_OK) st = layout_check_ids(who, pad_id, bos_id, eos_id);
-    if (st != TGX_OK) return st;
-    if (r->vocab_size > 0x80000000u) return fail(TGX_ERR_INVALID, "%s: the model's ids are not all below 2^31", who);
-    const tgx::LayoutSeq seq = tgx::layout_seq(bos_id, eos_id, pad_id);
-    if ((st = layout_check_row_len(who, row_len, seq.extra)) != TGX_OK) return st;
-    if (n_truncated) *n_truncated = 0;
-    if (r->n_samples == 0) return TGX_OK;
-    DeviceScope scope;
-    HIP_TRY(hipSetDevice(r->device));
-    if ((st = check_device_ptr(who, "d_ids", d_ids, r->device, "result")) != TGX_OK) return st;
-    if ((st = check_device_ptr(who, "d_mask", d_mask, r->device, "result")) != TGX_OK) return st;
-    if ((st = check_device_ptr(who, "d_lengths", d_lengths, r->device, "result")) != TGX_OK) return st;
-    hipStream_t hs = stream_or_default(stream, r->device);
-    unsigned long long h_count = 0, *d_count = nullptr;
-    StreamGuard guard(r->device, hs);
-    if (n_truncated) HIP_TRY(guard.alloc(sizeof(unsigned long long), &d_count));
-    tgx::LayoutParams p = {};
-    p.ids = r->d_ids;
-    p.offs = r->d_offs;
-    p.n_rows = r->n_samples;
-    p.len = row_len;
-    p.pad = pad_id;
-    p.bos = bos_id;
-    p.eos = eos_id;
-    p.flags = flags;
-    p.out = d_ids;
-    p.mask = d_mask;
-    p.lengths = d_lengths;
-    p.counter = d_count;
-    if (n_truncated) HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), hs));
-    HIP_TRY(tgx::launch_layout_pad(p, hs));
-    if (n_truncated) HIP_TRY(hipMemcpyAsync(&h_count, d_count, sizeof(unsigned long long), hipMemcpyDeviceToHost, hs));
-    // the stream has reached its end before the result or the destination can change hands (the guard: also after a failure)
+tgx_status read_u64(hipStream_t hs, const void* d_src, void* host_words, size_t n) {
+    HIP_TRY(hipMemcpyAsync(host_words, d_src, n * 8, hipMemcpyDeviceToHost, hs));
     HIP_TRY(hipStreamSynchronize(hs));
-    guard.done();
-    if (n_truncated) *n_truncated = h_count;
     return TGX_OK;
 }
 
-tgx_status tgx_result_pack_device(const tgx_result* r, uint32_t block_len, uint32_t pad_id, uint32_t bos_id, uint32_t eos_id,
-                                  uint32_t flags, void* stream, void* d_ids, int32_t* d_doc, int32_t* d_pos, uint64_t* n_blocks) {
-    const char* who = "tgx_result_pack_device";
-    if (!r || !n_blocks) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
-    tgx_status st = layout_check_flags(who, flags, TGX_LAYOUT_I64);
-    if (st == TGX_OK) st = layout_check_ids(who, pad_id, bos_id, eos_id);
-    if (st != TGX_OK) return st;
-    if (r->vocab_size > 0x80000000u) return fail(TGX_ERR_INVALID, "%s: the model's ids are not all below 2^31", who);
-    if (block_len < 1) return fail(TGX_ERR_INVALID, "%s: block_len is 0", who);
-    if (r->n_samples >= 0x80000000ull) return fail(TGX_ERR_UNSUPPORTED, "%s: 2^31 rows or more", who);
-    const tgx::LayoutSeq seq = tgx::layout_seq(bos_id, eos_id, pad_id);
-    const uint64_t n_stream = r->n_tokens + r->n_samples * seq.extra;
-    const uint64_t nb = (n_stream + block_len - 1) / block_len;
-    *n_blocks = nb;
-    if (nb == 0) return TGX_OK;
-    if (!d_ids) return fail(TGX_ERR_INVALID, "%s: d_ids is NULL", who);
-    DeviceScope scope;
-    HIP_TRY(hipSetDevice(r->device));
-    if ((st = check_device_ptr(who, "d_ids", d_ids, r->device, "result")) != TGX_OK) return st;
-    if ((st = check_device_ptr(who, "d_doc", d_doc, r->device, "result")) != TGX_OK) return st;
-    if ((st = check_device_ptr(who, "d_pos", d_pos, r->device, "result")) != TGX_OK) return st;
-    hipStream_t hs = stream_or_default(stream, r->device);
-    tgx::LayoutParams p = {};
-    p.ids = r->d_ids;
-    p.offs = r->d_offs;
-    p.n_rows = r->n_samples;
-    p.len = block_len;
-    p.pad = pad_id;
-    p.bos = bos_id;
-    p.eos = eos_id;
-    p.flags = flags;
-    p.out = d_ids;
-    p.doc = d_doc;
-    p.pos = d_pos;
-    StreamGuard guard(r->device, hs);
-    HIP_TRY(tgx::launch_layout_pack(p, n_stream, nb * block_len, hs));
-    HIP_TRY(hipStreamSynchronize(hs));
-    guard.done();
+tgx_status scan_room(ScanScratch* s, StreamGuard& guard, hipError_t (*temp_bytes)(uint64_t, size_t*), uint64_t n) {
+    if (n <= s->n) return TGX_OK;
+    if (temp_bytes(n, &s->bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan temp-size query failed");
+    HIP_TRY(guard.alloc(s->bytes, &s->ptr));  // (never NULL: that asks the scan for its size)
+    s->n = n;
     return TGX_OK;
 }
 
-// ---- overflow windows: long rows as overlapping [W, L] windows (layout.hip; layout.h has the window mapping) ---------
-
-namespace {
-
-// Wo = the rows' first windows, in pooled scratch of the guard (u64[S+1]), and *n_windows = W = Wo[S], for a result with
-// S >= 1 rows: the count kernel, the scan, and one read-back of W and the longest row, which are checked against 2^31.
-// The stream has reached its end when this returns TGX_OK.
-tgx_status window_offsets_device(const char* who, const tgx_result* r, uint32_t room, uint32_t step, hipStream_t hs, StreamGuard& guard,
-                                 const uint64_t** d_wo, uint64_t* n_windows) {
-    const uint64_t S = r->n_samples;
-    size_t scan_bytes = 0;
-    if (tgx::scan_temp_bytes(S, &scan_bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan temp-size query failed");
-    uint32_t* counts = nullptr;
-    uint64_t* wo = nullptr;  // Wo[0 .. S], then the longest row
-    void* scan = nullptr;
-    HIP_TRY(guard.alloc((size_t)(S + 1) * 4, &counts));
-    HIP_TRY(guard.alloc((size_t)(S + 2) * 8, &wo));
-    if (scan_bytes) HIP_TRY(guard.alloc(scan_bytes, &scan));
-    HIP_TRY(hipMemsetAsync(wo + S + 1, 0, 8, hs));
-    HIP_TRY(tgx::launch_layout_window_count(r->d_offs, S, room, step, counts, reinterpret_cast<unsigned long long*>(wo + S + 1), hs));
-    HIP_TRY(tgx::launch_scan(counts, wo, S, scan, scan_bytes, hs));
-    uint64_t h[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(h, wo + S, 16, hipMemcpyDeviceToHost, hs));
-    HIP_TRY(hipStreamSynchronize(hs));
-    const tgx_status st = window_check_totals(who, h[1], h[0], nullptr);
-    if (st != TGX_OK) return st;
-    *d_wo = wo;
-    *n_windows = h[0];
-    return TGX_OK;
-}
-
-}  // namespace
-
-tgx_status tgx_result_window_info(const tgx_result* r, uint32_t row_len, uint32_t stride, uint32_t bos_id, uint32_t eos_id, uint32_t flags,
-                                  uint64_t* n_windows) {
-    const char* who = "tgx_result_window_info";
-    if (!r || !n_windows) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
-    tgx_status st = layout_check_flags(who, flags, TGX_LAYOUT_PAD_LEFT | TGX_LAYOUT_TRUNC_LEFT | TGX_LAYOUT_I64 | TGX_SPAN_CHARS);
-    if (st == TGX_OK) st = layout_check_ids(who, 0, bos_id, eos_id);
-    if (st != TGX_OK) return st;
-    const tgx::LayoutSeq seq = tgx::layout_seq(bos_id, eos_id, 0);
-    if ((st = window_check_args(who, row_len, stride, seq.extra)) != TGX_OK) return st;
-    *n_windows = 0;
-    if (r->n_samples == 0) return TGX_OK;
-    DeviceScope scope;
-    HIP_TRY(hipSetDevice(r->device));
-    hipStream_t hs = stream_or_default(nullptr, r->device);
-    StreamGuard guard(r->device, hs);
-    const uint64_t* d_wo = nullptr;
-    st = window_offsets_device(who, r, row_len - seq.extra, row_len - seq.extra - stride, hs, guard, &d_wo, n_windows);
-    if (st == TGX_OK) guard.done();
-    return st;
-}
-
-tgx_status tgx_result_window_pad_device(const tgx_result* r, uint32_t row_len, uint32_t stride, uint32_t pad_id, uint32_t bos_id, uint32_t eos_id,
-                                        uint32_t flags, void* stream, uint64_t n_windows, void* d_ids, uint8_t* d_mask, int32_t* d_lengths,
-                                        int32_t* d_window_row, int32_t* d_window_first) {
-    const char* who = "tgx_result_window_pad_device";
-    if (!r) return fail(TGX_ERR_INVALID, "%s: result is NULL", who);
-    if (!d_ids && r->n_samples) return fail(TGX_ERR_INVALID, "%s: d_ids is NULL", who);
-    tgx_status st = layout_check_flags(who, flags, TGX_LAYOUT_PAD_LEFT | TGX_LAYOUT_TRUNC_LEFT | TGX_LAYOUT_I64);
-    if (st == TGX_OK) st = layout_check_ids(who, pad_id, bos_id, eos_id);
-    if (st != TGX_OK) return st;
-    if (r->vocab_size > 0x80000000u) return fail(TGX_ERR_INVALID, "%s: the model's ids are not all below 2^31", who);
-    const tgx::LayoutSeq seq = tgx::layout_seq(bos_id, eos_id, pad_id);
-    if ((st = window_check_args(who, row_len, stride, seq.extra)) != TGX_OK) return st;
-    if (r->n_samples == 0) return window_check_totals(who, 0, 0, &n_windows);
-    DeviceScope scope;
-    HIP_TRY(hipSetDevice(r->device));
-    if ((st = check_device_ptr(who, "d_ids", d_ids, r->device, "result")) != TGX_OK) return st;
-    if ((st = check_device_ptr(who, "d_mask", d_mask, r->device, "result")) != TGX_OK) return st;
-    if ((st = check_device_ptr(who, "d_lengths", d_lengths, r->device, "result")) != TGX_OK) return st;
-    if ((st = check_device_ptr(who, "d_window_row", d_window_row, r->device, "result")) != TGX_OK) return st;
-    if ((st = check_device_ptr(who, "d_window_first", d_window_first, r->device, "result")) != TGX_OK) return st;
-    hipStream_t hs = stream_or_default(stream, r->device);
-    StreamGuard guard(r->device, hs);
-    const uint64_t* d_wo = nullptr;
-    uint64_t W = 0;
-    st = window_offsets_device(who, r, row_len - seq.extra, row_len - seq.extra - stride, hs, guard, &d_wo, &W);
-    if (st == TGX_OK) st = window_check_totals(who, 0, W, &n_windows);
-    if (st != TGX_OK) return st;
-    tgx::WindowParams q = {};
-    q.base.ids = r->d_ids;
-    q.base.offs = r->d_offs;
-    q.base.n_rows = r->n_samples;
-    q.base.len = row_len;
-    q.base.pad = pad_id;
-    q.base.bos = bos_id;
-    q.base.eos = eos_id;
-    q.base.flags = flags;
-    q.base.out = d_ids;
-    q.base.mask = d_mask;
-    q.base.lengths = d_lengths;
-    q.wo = d_wo;
-    q.stride = stride;
-    q.window_row = d_window_row;
-    q.window_first = d_window_first;
-    HIP_TRY(tgx::launch_layout_windows(q, W, hs));
-    // the stream has reached its end before the result or the destination can change hands (the guard: also after a failure)
-    HIP_TRY(hipStreamSynchronize(hs));
-    guard.done();
-    return TGX_OK;
-}
-
-// ---- assembly: a sample-level result with the special tokens' ids, from the segment-level result (assemble.hip) ----
-
-struct tgx_plan {
-    int device = 0;
-    uint64_t n_samples = 0, n_segs = 0, n_enc = 0;  // S, K, E
-    uint32_t n_specials = 0;                        // of the list the corpus was split with
-    PoolBuf<uint64_t> d_seg_offs;                   // u64[S+1]
-    PoolBuf<int32_t> d_special;                     // i32[K+1]: entry K belongs to the assembly's scan
-};
-
-namespace {
-
-// What tgx_assemble_result and tgx_assemble_result_plan share: everything after the checks of the plan itself.  The plan
-// is K segments of S samples, E of them encoded, in host arrays that are uploaded (h_*) or in device memory (d_*: d_special
-// with room for K + 1 entries).
-tgx_status assemble_device(const char* who, tgx_model* m, const tgx_result* segs, const uint64_t* h_seg_offs, const int32_t* h_special,
-                           const uint64_t* d_plan_offs, int32_t* d_plan_special, uint64_t S, uint64_t K, uint32_t n_specials, tgx_result** out) {
-    if (segs && segs->device != m->device)
-        return fail(TGX_ERR_INVALID, "%s: the result is on device %d, the model on device %d", who, segs->device, m->device);
-    if (segs && segs->vocab_size != m->vocab_size)
-        return fail(TGX_ERR_INVALID, "%s: the result was written for %u tokens, the model has %u", who, segs->vocab_size, m->vocab_size);
-    const uint64_t E = segs ? segs->n_samples : 0;
-    const uint64_t n_out = (segs ? segs->n_tokens : 0) + (K - E);
-
-    std::lock_guard<std::mutex> lk(m->mu);
-    HIP_TRY(hipSetDevice(m->device));
-    m->n_timed = 0;
-    Pass pass(m);
-    tgx_result* r = pass.new_result(S);
-    r->vocab_size = m->vocab_size + n_specials;
-    r->n_tokens = n_out;
-    uint64_t *d_seg_offs = nullptr, *d_rank = nullptr, *d_starts = nullptr, *d_zero = nullptr;
-    int32_t* d_special = d_plan_special;
-    void* d_scan = nullptr;
-    size_t scan_bytes = 0;
-    if (tgx::assemble_scan_temp_bytes(K, &scan_bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan temp-size query failed");
-    if (r->d_offs.alloc(m->device, (size_t)(S + 1) * 8) != hipSuccess || r->d_ids.alloc(m->device, (size_t)n_out * 4 + 256) != hipSuccess ||
-        (!d_plan_offs && pass.alloc((size_t)(S + 1) * 8, &d_seg_offs) != hipSuccess) ||
-        (!d_plan_special && pass.alloc((size_t)(K + 1) * 4, &d_special) != hipSuccess) ||
-        pass.alloc((size_t)(K + 1) * 8, &d_rank) != hipSuccess || pass.alloc((size_t)(K + 1) * 8, &d_starts) != hipSuccess ||
-        (E == 0 && pass.alloc(8, &d_zero) != hipSuccess) || pass.alloc(scan_bytes, &d_scan) != hipSuccess)  // (never NULL: that asks the scan for its size)
-        return fail(TGX_ERR_DEVICE, "out of device memory (assembly)");
-    if ((!d_plan_offs && hipMemcpyAsync(d_seg_offs, h_seg_offs, (size_t)(S + 1) * 8, hipMemcpyHostToDevice, m->stream) != hipSuccess) ||
-        (!d_plan_special && K && hipMemcpyAsync(d_special, h_special, (size_t)K * 4, hipMemcpyHostToDevice, m->stream) != hipSuccess) ||
-        (d_zero && hipMemsetAsync(d_zero, 0, 8, m->stream) != hipSuccess))
-        return fail(TGX_ERR_DEVICE, "upload of the split plan failed: %s", hipGetErrorString(hipGetLastError()));
-
-    tgx::AssembleParams p = {};
-    p.ids = E ? segs->d_ids.get() : nullptr;
-    p.offs = E ? segs->d_offs.get() : d_zero;
-    p.seg_offs = d_plan_offs ? d_plan_offs : d_seg_offs;
-    p.seg_special = d_special;
-    p.rank = d_rank;
-    p.starts = d_starts;
-    p.n_segs = K;
-    p.n_samples = S;
-    p.n_out = n_out;
-    p.vocab_size = m->vocab_size;
-    p.out_ids = r->d_ids;
-    p.out_offs = r->d_offs;
-    time_begin(m, "assemble_ranks_scan");
-    if (tgx::launch_assemble_ranks(d_special, d_rank, K, d_scan, scan_bytes, m->stream) != hipSuccess)
-        return fail(TGX_ERR_DEVICE, "scan launch failed");
-    time_end(m);
-    time_begin(m, "assemble_starts_kernel");
-    if (tgx::launch_assemble_starts(p, m->stream) != hipSuccess) return fail(TGX_ERR_DEVICE, "assemble_starts_kernel launch failed");
-    time_end(m);
-    time_begin(m, "assemble_fill_kernel");
-    if (tgx::launch_assemble_fill(p, m->stream) != hipSuccess) return fail(TGX_ERR_DEVICE, "assemble_fill_kernel launch failed");
-    time_end(m);
-    if (hipStreamSynchronize(m->stream) != hipSuccess) return fail(TGX_ERR_DEVICE, "assembly failed: %s", hipGetErrorString(hipGetLastError()));
-    *out = pass.release_result();
-    return pass.done();
-}
-
-}  // namespace
-
-tgx_status tgx_assemble_result(tgx_model* m, const tgx_result* segs, const uint64_t* seg_offs, const int32_t* seg_special,
-                               uint64_t n_samples, uint32_t n_specials, tgx_result** out) {
-    const char* who = "tgx_assemble_result";
-    const tgx_status dst = require_device();
-    if (dst != TGX_OK) return dst;
-    if (!m || !out) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
-    *out = nullptr;
-    uint64_t K = 0;
-    const tgx_status cst = assemble_check(who, seg_offs, seg_special, n_samples, m->vocab_size, n_specials, segs != nullptr, segs ? segs->n_samples : 0, &K);
-    if (cst != TGX_OK) return cst;
-    return assemble_device(who, m, segs, seg_offs, seg_special, nullptr, nullptr, n_samples, K, n_specials, out);
-}
-
-tgx_status tgx_assemble_result_plan(tgx_model* m, const tgx_result* segs, const tgx_plan* plan, uint32_t n_specials, tgx_result** out) {
-    const char* who = "tgx_assemble_result_plan";
-    const tgx_status dst = require_device();
-    if (dst != TGX_OK) return dst;
-    if (!m || !plan || !out) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
-    *out = nullptr;
-    // what assemble_check asks of host arrays, of a plan whose arrays the split wrote
-    if ((uint64_t)m->vocab_size + n_specials > 0xFFFFFFFEull)
-        return fail(TGX_ERR_INVALID, "%s: %u tokens and %u special tokens leave no room for their ids", who, m->vocab_size, n_specials);
-    if (n_specials != plan->n_specials)
-        return fail(TGX_ERR_INVALID, "%s: %u special tokens, the plan was made with %u", who, n_specials, plan->n_specials);
-    if (plan->n_enc && !segs) return fail(TGX_ERR_INVALID, "%s: %llu encoded segments and no result over them", who, (unsigned long long)plan->n_enc);
-    if (plan->n_enc != (segs ? segs->n_samples : 0))
-        return fail(TGX_ERR_INVALID, "%s: %llu encoded segments, the result over them has %llu rows", who, (unsigned long long)plan->n_enc,
-                    (unsigned long long)(segs ? segs->n_samples : 0));
-    if (plan->device != m->device) return fail(TGX_ERR_INVALID, "%s: the plan is on device %d, the model on device %d", who, plan->device, m->device);
-    return assemble_device(who, m, segs, nullptr, nullptr, plan->d_seg_offs, plan->d_special, plan->n_samples, plan->n_segs, n_specials, out);
-}
-
-// ---- decode: ids in HBM to UTF-8 text in HBM (decode.hip; decode.h has the index arithmetic) ----------------------
-
-struct tgx_text {
-    int device = 0;
-    uint64_t n_rows = 0, n_bytes = 0, n_replaced = 0;
-    PoolBuf<uint8_t> d_bytes;
-    PoolBuf<uint64_t> d_offs;
-};
-
-namespace {
-
-uint64_t decode_elem_bytes(uint32_t kind) { return kind == tgx::kDecodeI64 ? 8 : 4; }
-
-// the model's token tables on its device, once (under m->mu)
-tgx_status ensure_decode_tables(tgx_model* m) {
-    std::lock_guard<std::mutex> lk(m->mu);
-    if (m->decode_tables_ready) return TGX_OK;
-    const uint32_t V = m->vocab_size;
-    std::vector<uint8_t> len;
-    std::vector<tgx::DecodeSlot> slots;
-    const tgx_status st = decode_build_tables("decode", m->vocab_bytes.data(), m->vocab_offs.data(), V, &len, &slots);
-    if (st != TGX_OK) return st;
-    const size_t nb = m->vocab_bytes.size();
-    if (!m->d_dec_len) HIP_TRY(hipMalloc((void**)&m->d_dec_len, (size_t)V + 16));
-    if (!m->d_dec_slots) HIP_TRY(hipMalloc(&m->d_dec_slots, ((size_t)V + 1) * sizeof(tgx::DecodeSlot)));
-    if (!m->d_dec_bytes) HIP_TRY(hipMalloc((void**)&m->d_dec_bytes, nb + 16));
-    if (!m->d_dec_offs) HIP_TRY(hipMalloc((void**)&m->d_dec_offs, ((size_t)V + 1) * 8));
-    if (V) HIP_TRY(hipMemcpy(m->d_dec_len, len.data(), V, hipMemcpyHostToDevice));
-    if (V) HIP_TRY(hipMemcpy(m->d_dec_slots, slots.data(), (size_t)V * sizeof(tgx::DecodeSlot), hipMemcpyHostToDevice));
-    if (nb) HIP_TRY(hipMemcpy(m->d_dec_bytes, m->vocab_bytes.data(), nb, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(m->d_dec_offs, m->vocab_offs.data(), ((size_t)V + 1) * 8, hipMemcpyHostToDevice));
-    m->decode_tables_ready = true;
-    return TGX_OK;
-}
-
-// The decode of src (device pointers) on stream hs of the model's device, which is current.  row_offs_dev: the offsets
-// form's offsets, read back only to name the row of an out-of-bounds id.
-tgx_status decode_device(tgx_model* m, tgx::DecodeSrc src, const uint8_t* special_bytes, const uint64_t* special_offs, uint32_t n_specials,
-                         int include_special, hipStream_t hs, tgx_text** out, uint64_t* bad_sample, uint64_t* bad_id) {
-    const int dev = m->device;
-    const uint64_t S = src.n_rows, N = src.n;
-    std::unique_ptr<tgx_text> text(new tgx_text());
-    PoolBuf<uint8_t> raw;          // the raw bytes: the text's own when nothing is replaced
-    std::vector<uint64_t> h_offs;  // the offsets form's offsets, read back to name the row of an out-of-bounds id
-    StreamGuard guard(dev, hs);    // destroyed before them: a failed call's queued work is over before they go
-    uint32_t *meta = nullptr, *flags = nullptr, *codes = nullptr;
-    uint64_t *starts = nullptr, *specials = nullptr, *gpos = nullptr, *sp_offs = nullptr;
-    uint8_t* sp_bytes = nullptr;
-    void *scan = nullptr, *scan2 = nullptr;
-    unsigned long long* ctrl = nullptr;  // [0]: lowest out-of-bounds position, [1]: replacement characters, [2]: live specials
-    tgx_text* t = text.get();
-    t->device = dev;
-    t->n_rows = S;
-    HIP_TRY(t->d_offs.alloc(dev, (size_t)(S + 1) * 8));
-    if (S == 0 || N == 0) {
-        HIP_TRY(t->d_bytes.alloc(dev, 0));
-        HIP_TRY(hipMemsetAsync(t->d_offs, 0, (size_t)(S + 1) * 8, hs));
-        HIP_TRY(hipStreamSynchronize(hs));
-        guard.done();
-        *out = text.release();
-        return TGX_OK;
-    }
-    tgx_status st = ensure_decode_tables(m);
-    if (st != TGX_OK) return st;
-
-    const uint64_t sp_total = n_specials ? special_offs[n_specials] - special_offs[0] : 0;
-    size_t scan_bytes = 0;
-    if (tgx::decode_scan_temp_bytes(N, &scan_bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan temp-size query failed");
-    HIP_TRY(guard.alloc((size_t)(N + 1) * 4, &meta));
-    HIP_TRY(guard.alloc((size_t)(N + 1) * 8, &starts));
-    HIP_TRY(guard.alloc(scan_bytes, &scan));  // (never NULL: that asks the scan for its size)
-    HIP_TRY(guard.alloc(24, &ctrl));
-    HIP_TRY(guard.alloc(((size_t)n_specials + 1) * 8, &sp_offs));
-    HIP_TRY(guard.alloc((size_t)sp_total + 16, &sp_bytes));
-    std::vector<uint64_t> sp_offs0((size_t)n_specials + 1, 0);  // from 0
-    for (uint32_t k = 0; k <= n_specials && n_specials; k++) sp_offs0[k] = special_offs[k] - special_offs[0];
-    HIP_TRY(guard.upload(sp_offs, std::move(sp_offs0)));
-    if (sp_total) HIP_TRY(hipMemcpyAsync(sp_bytes, special_bytes + special_offs[0], sp_total, hipMemcpyHostToDevice, hs));
-    HIP_TRY(hipMemsetAsync(ctrl, 0xFF, 8, hs));
-    HIP_TRY(hipMemsetAsync(ctrl + 1, 0, 16, hs));
-
-    tgx::DecodeParams p = {};
-    p.tab.tok_len = m->d_dec_len;
-    p.tab.slots = static_cast<const tgx::DecodeSlot*>(m->d_dec_slots);
-    p.tab.bytes = m->d_dec_bytes;
-    p.tab.offs = m->d_dec_offs;
-    p.tab.sp_bytes = sp_bytes;
-    p.tab.sp_offs = sp_offs;
-    p.tab.vocab_size = m->vocab_size;
-    p.tab.n_specials = n_specials;
-    p.tab.include_special = include_special ? 1 : 0;
-    p.src = src;
-    p.meta = meta;
-    p.starts = starts;
-    p.bad_pos = ctrl;
-    p.n_replaced = ctrl + 1;
-    p.n_specials_live = ctrl + 2;
-    p.row_offs = t->d_offs;
-    HIP_TRY(tgx::launch_decode_meta(p, scan, scan_bytes, hs));
-    unsigned long long h_bad = ~0ull, h_raw = 0, h_replaced = 0, h_final = 0, h_specials = 0;
-    HIP_TRY(hipMemcpyAsync(&h_bad, ctrl, 8, hipMemcpyDeviceToHost, hs));
-    HIP_TRY(hipMemcpyAsync(&h_specials, ctrl + 2, 8, hipMemcpyDeviceToHost, hs));
-    HIP_TRY(hipMemcpyAsync(&h_raw, starts + N, 8, hipMemcpyDeviceToHost, hs));
-    HIP_TRY(hipStreamSynchronize(hs));
-    if (h_bad != ~0ull) {
-        int64_t x = 0;
-        union { int64_t i64; int32_t i32; uint32_t u32; } v = {};
-        HIP_TRY(hipMemcpyAsync(&v, static_cast<const char*>(src.ids) + h_bad * decode_elem_bytes(src.kind), decode_elem_bytes(src.kind), hipMemcpyDeviceToHost, hs));
-        if (src.offs) {
-            h_offs.resize(S + 1);
-            HIP_TRY(hipMemcpyAsync(h_offs.data(), src.offs, (size_t)(S + 1) * 8, hipMemcpyDeviceToHost, hs));
-        }
-        HIP_TRY(hipStreamSynchronize(hs));
-        x = src.kind == tgx::kDecodeI64 ? v.i64 : src.kind == tgx::kDecodeI32 ? (int64_t)v.i32 : (int64_t)v.u32;
-        const uint64_t row = src.offs ? (uint64_t)(std::upper_bound(h_offs.begin(), h_offs.end(), (uint64_t)h_bad) - h_offs.begin()) - 1 : h_bad / src.row_len;
-        guard.done();
-        return decode_oob(src.kind, x, row, bad_sample, bad_id);
-    }
-    const uint64_t T = h_raw;
-    if (T == 0) {
-        HIP_TRY(t->d_bytes.alloc(dev, 0));
-        HIP_TRY(hipMemsetAsync(t->d_offs, 0, (size_t)(S + 1) * 8, hs));
-        HIP_TRY(hipStreamSynchronize(hs));
-        guard.done();
-        *out = text.release();
-        return TGX_OK;
-    }
-    const uint64_t G = (T + tgx::kDecodeGroup - 1) / tgx::kDecodeGroup;
-    HIP_TRY(raw.alloc(dev, (size_t)G * tgx::kDecodeGroup + 16));
-    HIP_TRY(guard.alloc((size_t)G * 4, &flags));
-    HIP_TRY(guard.alloc((size_t)(G + 1) * 4, &codes));
-    p.n_raw = T;
-    p.raw = raw;
-    p.flags = flags;
-    p.codes = codes;
-    if (h_specials) {  // only then can a run end inside a row
-        HIP_TRY(guard.alloc((size_t)(N + 1) * 8, &specials));
-        p.specials = specials;
-        HIP_TRY(tgx::launch_decode_specials(p, scan, scan_bytes, hs));
-    }
-    HIP_TRY(tgx::launch_decode_fill(p, hs));
-    HIP_TRY(tgx::launch_decode_rows(p, hs));
-    HIP_TRY(tgx::launch_decode_utf8(p, hs));
-    HIP_TRY(hipMemcpyAsync(&h_replaced, ctrl + 1, 8, hipMemcpyDeviceToHost, hs));
-    HIP_TRY(hipStreamSynchronize(hs));
-    t->n_replaced = h_replaced;
-    if (h_replaced == 0) {  // the raw bytes are the text and the rows' raw starts its offsets
-        t->d_bytes = std::move(raw);
-        t->n_bytes = T;
-        guard.done();
-        *out = text.release();
-        return TGX_OK;
-    }
-    size_t scan2_bytes = 0;
-    if (tgx::decode_expand_temp_bytes(G, &scan2_bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan temp-size query failed");
-    HIP_TRY(guard.alloc((size_t)(G + 1) * 8, &gpos));
-    HIP_TRY(guard.alloc(scan2_bytes, &scan2));
-    p.gpos = gpos;
-    HIP_TRY(tgx::launch_decode_positions(p, scan2, scan2_bytes, hs));
-    HIP_TRY(hipMemcpyAsync(&h_final, gpos + G, 8, hipMemcpyDeviceToHost, hs));
-    HIP_TRY(hipStreamSynchronize(hs));
-    HIP_TRY(t->d_bytes.alloc(dev, (size_t)h_final + 16));
-    p.out = t->d_bytes;
-    HIP_TRY(tgx::launch_decode_expand(p, hs));
-    HIP_TRY(hipStreamSynchronize(hs));
-    t->n_bytes = h_final;
-    guard.done();
-    *out = text.release();
-    return TGX_OK;
-}
-
-}  // namespace
-
-tgx_status tgx_decode_result(tgx_model* m, const tgx_result* r, const uint8_t* special_bytes, const uint64_t* special_offs, uint32_t n_specials,
-                             int include_special, void* stream, tgx_text** out, uint64_t* bad_sample, uint64_t* bad_id) {
-    const char* who = "tgx_decode_result";
-    if (!m || !r || !out) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
-    *out = nullptr;
-    tgx_status st = decode_check_specials(who, m->vocab_size, special_bytes, special_offs, n_specials);
-    if (st != TGX_OK) return st;
-    if ((st = require_device()) != TGX_OK) return st;
-    if (r->device != m->device) return fail(TGX_ERR_INVALID, "%s: the result is on device %d, the model on device %d", who, r->device, m->device);
-    if ((uint64_t)r->vocab_size > (uint64_t)m->vocab_size + n_specials)
-        return fail(TGX_ERR_INVALID, "%s: the result was written for %u ids, the model has %u tokens and %u special tokens", who, r->vocab_size,
-                    m->vocab_size, n_specials);
-    DeviceScope scope;
-    HIP_TRY(hipSetDevice(m->device));
-    hipStream_t hs = stream_or_default(stream, m->device);
-    tgx::DecodeSrc src = {};
-    src.ids = r->d_ids.get();
-    src.offs = r->d_offs.get();
-    src.n_rows = r->n_samples;
-    src.n = r->n_tokens;
-    src.kind = tgx::kDecodeU32;
-    src.skip_id = TGX_NO_ID;
-    return decode_device(m, src, special_bytes, special_offs, n_specials, include_special, hs, out, bad_sample, bad_id);
-}
-
-tgx_status tgx_decode_padded(tgx_model* m, const void* d_ids, uint64_t n_rows, uint64_t row_len, uint32_t flags, const uint8_t* d_mask,
-                             const int32_t* d_lengths, uint32_t skip_id, const uint8_t* special_bytes, const uint64_t* special_offs,
-                             uint32_t n_specials, int include_special, void* stream, tgx_text** out, uint64_t* bad_sample, uint64_t* bad_id) {
-    const char* who = "tgx_decode_padded";
-    if (!m || !out) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
-    *out = nullptr;
-    tgx_status st = layout_check_flags(who, flags, TGX_LAYOUT_I64);
-    if (st == TGX_OK) st = decode_check_specials(who, m->vocab_size, special_bytes, special_offs, n_specials);
-    if (st != TGX_OK) return st;
-    if (n_rows && row_len && n_rows > 0xFFFFFFFFFFFFFFFFull / 16 / row_len) return fail(TGX_ERR_UNSUPPORTED, "%s: %llu rows of %llu elements", who, (unsigned long long)n_rows, (unsigned long long)row_len);
-    const uint64_t N = n_rows * row_len;
-    if (N && !d_ids) return fail(TGX_ERR_INVALID, "%s: d_ids is NULL", who);
-    if ((st = require_device()) != TGX_OK) return st;
-    DeviceScope scope;
-    HIP_TRY(hipSetDevice(m->device));
-    if (N) {
-        if ((st = check_device_ptr(who, "d_ids", d_ids, m->device, "model")) != TGX_OK) return st;
-        if ((st = check_device_ptr(who, "d_mask", d_mask, m->device, "model")) != TGX_OK) return st;
-        if ((st = check_device_ptr(who, "d_lengths", d_lengths, m->device, "model")) != TGX_OK) return st;
-    }
-    hipStream_t hs = stream_or_default(stream, m->device);
-    tgx::DecodeSrc src = {};
-    src.ids = d_ids;
-    src.mask = d_mask;
-    src.lengths = d_lengths;
-    src.n_rows = n_rows;
-    src.row_len = row_len;
-    src.n = N;
-    src.kind = (flags & TGX_LAYOUT_I64) ? tgx::kDecodeI64 : tgx::kDecodeI32;
-    src.skip_id = skip_id;
-    return decode_device(m, src, special_bytes, special_offs, n_specials, include_special, hs, out, bad_sample, bad_id);
-}
-
-uint64_t tgx_text_num_rows(const tgx_text* t) { return t ? t->n_rows : 0; }
-uint64_t tgx_text_num_bytes(const tgx_text* t) { return t ? t->n_bytes : 0; }
-uint64_t tgx_text_num_replaced(const tgx_text* t) { return t ? t->n_replaced : 0; }
-int tgx_text_device(const tgx_text* t) { return t ? t->device : -1; }
-const void* tgx_text_bytes_device(const tgx_text* t) { return t ? t->d_bytes.get() : nullptr; }
-const void* tgx_text_offsets_device(const tgx_text* t) { return t ? t->d_offs.get() : nullptr; }
-// (the call that made it returned after its stream had reached its end: the buffers go straight back to the pool)
-void tgx_text_free(tgx_text* t) { delete t; }
-
-tgx_status tgx_text_copy_bytes(const tgx_text* t, uint8_t* dst, uint64_t cap) {
-    if (!t || (!dst && t->n_bytes)) return fail(TGX_ERR_INVALID, "tgx_text_copy_bytes: NULL argument");
-    if (cap < t->n_bytes) return fail(TGX_ERR_INVALID, "tgx_text_copy_bytes: %llu bytes, room for %llu", (unsigned long long)t->n_bytes, (unsigned long long)cap);
-    if (!t->n_bytes) return TGX_OK;
-    DeviceScope scope;
-    HIP_TRY(hipSetDevice(t->device));
-    HIP_TRY(copy_sync(dst, t->d_bytes, t->n_bytes, hipMemcpyDeviceToHost, t->device));
-    return TGX_OK;
-}
-
-tgx_status tgx_text_copy_offsets(const tgx_text* t, uint64_t* dst, uint64_t cap) {
-    if (!t || !dst) return fail(TGX_ERR_INVALID, "tgx_text_copy_offsets: NULL argument");
-    if (cap < t->n_rows + 1) return fail(TGX_ERR_INVALID, "tgx_text_copy_offsets: %llu offsets, room for %llu", (unsigned long long)(t->n_rows + 1), (unsigned long long)cap);
-    DeviceScope scope;
-    HIP_TRY(hipSetDevice(t->device));
-    HIP_TRY(copy_sync(dst, t->d_offs, (t->n_rows + 1) * 8, hipMemcpyDeviceToHost, t->device));
-    return TGX_OK;
-}
-
-tgx_status tgx_corpus_from_text(const tgx_text* t, tgx_corpus** out) {
-    const char* who = "tgx_corpus_from_text";
-    if (!t || !out) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
-    *out = nullptr;
-    std::vector<uint64_t> offs(t->n_rows + 1);
-    const tgx_status st = tgx_text_copy_offsets(t, offs.data(), offs.size());
-    if (st != TGX_OK) return st;
-    DeviceScope scope;
-    return corpus_create(who, t->device, t->d_bytes, TextFrom::Device, offs.data(), t->n_rows, out);
-}
-
-// ---- the front end on the device: a resident corpus split at special tokens, CRLF applied (front.hip; front.h) ----
-
-tgx_status tgx_corpus_copy_text(const tgx_corpus* c, uint8_t* dst, uint64_t cap) {
-    if (!c || (!dst && c->n_bytes)) return fail(TGX_ERR_INVALID, "tgx_corpus_copy_text: NULL argument");
-    if (cap < c->n_bytes) return fail(TGX_ERR_INVALID, "tgx_corpus_copy_text: %llu bytes, room for %llu", (unsigned long long)c->n_bytes, (unsigned long long)cap);
-    if (!c->n_bytes) return TGX_OK;
-    DeviceScope scope;
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(copy_sync(dst, c->d_text, c->n_bytes, hipMemcpyDeviceToHost, c->device));
-    return TGX_OK;
-}
-
-tgx_status tgx_corpus_copy_offsets(const tgx_corpus* c, uint64_t* dst, uint64_t cap) {
-    if (!c || !dst) return fail(TGX_ERR_INVALID, "tgx_corpus_copy_offsets: NULL argument");
-    if (cap < c->n_samples + 1) return fail(TGX_ERR_INVALID, "tgx_corpus_copy_offsets: %llu offsets, room for %llu", (unsigned long long)(c->n_samples + 1), (unsigned long long)cap);
-    memcpy(dst, c->h_offs.data(), (size_t)(c->n_samples + 1) * 8);  // (the corpus keeps them on the host too)
-    return TGX_OK;
-}
-
-namespace {
-
-// device time of the last tgx_corpus_split_specials of this thread, per stage (tgx_front_last_times)
-constexpr int kFrontStages = 5;
-const char* const kFrontStageNames[kFrontStages] = {"front_mark", "front_resolve", "front_segments", "front_keep", "front_pack"};
-thread_local float g_front_ms[kFrontStages] = {0, 0, 0, 0, 0};
-
-class FrontTimer {
-public:
-    explicit FrontTimer(hipStream_t hs, float* ms = g_front_ms) : hs_(hs), ms_(ms) {  // ms: kFrontStages entries
-        for (auto& e : ev_) ok_ = ok_ && hipEventCreate(&e) == hipSuccess;
-    }
-    FrontTimer(const FrontTimer&) = delete;
-    FrontTimer& operator=(const FrontTimer&) = delete;
-    ~FrontTimer() {
-        for (auto& e : ev_)
-            if (e) (void)hipEventDestroy(e);
-    }
-    void begin(int stage) {
-        if (ok_) used_[stage] = hipEventRecord(ev_[2 * stage], hs_) == hipSuccess;
-    }
-    void end(int stage) {
-        if (ok_ && used_[stage]) used_[stage] = hipEventRecord(ev_[2 * stage + 1], hs_) == hipSuccess;
-    }
-    void read() {  // after the stream has reached its end
-        for (int k = 0; k < kFrontStages; k++) {
-            ms_[k] = 0;
-            if (ok_ && used_[k]) (void)hipEventElapsedTime(&ms_[k], ev_[2 * k], ev_[2 * k + 1]);
-        }
-    }
-
-private:
-    hipStream_t hs_;
-    float* ms_;
-    hipEvent_t ev_[2 * kFrontStages] = {};
-    bool used_[kFrontStages] = {};
-    bool ok_ = true;
-};
-
-}  // namespace
-
-int tgx_front_last_times(const char** names, float* ms, int cap) {
-    int n = 0;
-    for (; n < kFrontStages && n < cap; n++) {
-        if (names) names[n] = kFrontStageNames[n];
-        if (ms) ms[n] = g_front_ms[n];
-    }
-    return n;
-}
-
-tgx_status tgx_corpus_split_specials(tgx_corpus* c, const uint8_t* special_bytes, const uint64_t* special_offs, uint32_t n_specials, uint32_t flags,
-                                     tgx_corpus** segs, tgx_plan** plan) {
-    const char* who = "tgx_corpus_split_specials";
-    if (!c || !segs || !plan) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
-    *segs = nullptr;
-    *plan = nullptr;
-    tgx_status st = layout_check_flags(who, flags, TGX_FRONT_CRLF);
-    FrontHostTables ht;
-    if (st == TGX_OK) st = front_build_tables(who, special_bytes, special_offs, n_specials, &ht);
-    if (st == TGX_OK) st = require_device();
-    if (st != TGX_OK) return st;
-    std::lock_guard<std::mutex> lkc(c->mu);
-    DeviceScope scope;
-    const int dev = c->device;
-    HIP_TRY(hipSetDevice(dev));
-    hipStream_t hs = stream_or_default(nullptr, dev);
-    const uint64_t S = c->n_samples, N = c->n_bytes;
-    std::unique_ptr<tgx_plan> pl(new tgx_plan());
-    std::unique_ptr<tgx_corpus> out;  // the segments' corpus
-    std::vector<uint64_t> h_out_offs(1, 0);
-    unsigned long long h_count = 0;
-    StreamGuard guard(dev, hs);  // destroyed before them: a failed call's queued work is over before they go
-    FrontTimer timer(hs);
-    pl->device = dev;
-    pl->n_samples = S;
-    pl->n_specials = n_specials;
-    HIP_TRY(pl->d_seg_offs.alloc(dev, (size_t)(S + 1) * 8));
-    if (S == 0 || N == 0) {  // no segments
-        HIP_TRY(pl->d_special.alloc(dev, 4));
-        HIP_TRY(hipMemsetAsync(pl->d_seg_offs, 0, (size_t)(S + 1) * 8, hs));
-        HIP_TRY(hipStreamSynchronize(hs));
-        tgx_corpus* empty = nullptr;
-        if ((st = corpus_create(who, dev, nullptr, TextFrom::Caller, nullptr, 0, &empty)) != TGX_OK) return st;
-        guard.done();
-        *segs = empty;
-        *plan = pl.release();
-        return TGX_OK;
-    }
-
-    tgx::FrontParams p = {};
-    p.text = c->d_text;
-    p.offs = c->d_offs;
-    p.n_bytes = N;
-    p.n_samples = S;
-    p.crlf = (flags & TGX_FRONT_CRLF) ? 1u : 0u;
-    const uint64_t tiles = (N + tgx::kFrontTile - 1) / tgx::kFrontTile, slots = (N + tgx::kFrontGroup - 1) / tgx::kFrontGroup;
-    // the special tokens' tables
-    uint32_t *d_mask = nullptr, *d_first = nullptr, *d_by_first = nullptr, *d_sp_offs = nullptr;
-    uint8_t* d_sp_bytes = nullptr;
-    HIP_TRY(guard.alloc(32, &d_mask));
-    HIP_TRY(guard.alloc(257 * 4, &d_first));
-    HIP_TRY(guard.alloc((size_t)n_specials * 4 + 4, &d_by_first));
-    HIP_TRY(guard.alloc((size_t)n_specials * 4 + 4, &d_sp_offs));
-    HIP_TRY(guard.alloc(ht.sp_bytes.size() + 16, &d_sp_bytes));
-    HIP_TRY(hipMemcpyAsync(d_mask, ht.first_mask.data(), 32, hipMemcpyHostToDevice, hs));
-    HIP_TRY(hipMemcpyAsync(d_first, ht.first_start.data(), 257 * 4, hipMemcpyHostToDevice, hs));
-    if (n_specials) HIP_TRY(hipMemcpyAsync(d_by_first, ht.by_first.data(), (size_t)n_specials * 4, hipMemcpyHostToDevice, hs));
-    HIP_TRY(hipMemcpyAsync(d_sp_offs, ht.sp_offs.data(), ((size_t)n_specials + 1) * 4, hipMemcpyHostToDevice, hs));
-    if (!ht.sp_bytes.empty()) HIP_TRY(hipMemcpyAsync(d_sp_bytes, ht.sp_bytes.data(), ht.sp_bytes.size(), hipMemcpyHostToDevice, hs));
-    p.tab = front_tables(ht, d_mask, d_first, d_by_first, d_sp_offs, d_sp_bytes);
-    // every scan's scratch, asked for again when a later count is larger than the ones known so far
-    void* d_scan = nullptr;
-    size_t scan_bytes = 0;
-    uint64_t scan_n = 0;
-    auto scan_room = [&](uint64_t n) -> tgx_status {
-        if (n <= scan_n) return TGX_OK;
-        if (tgx::front_scan_temp_bytes(n, &scan_bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan temp-size query failed");
-        HIP_TRY(guard.alloc(scan_bytes, &d_scan));  // (never NULL: that asks the scan for its size)
-        scan_n = n;
-        return TGX_OK;
-    };
-    auto count_at = [&](const uint64_t* d, uint64_t* v) -> tgx_status {  // one counter to the host
-        HIP_TRY(hipMemcpyAsync(&h_count, d, 8, hipMemcpyDeviceToHost, hs));
-        HIP_TRY(hipStreamSynchronize(hs));
-        *v = h_count;
-        return TGX_OK;
-    };
-
-    // mark
-    HIP_TRY(guard.alloc((size_t)slots * 2, &p.hit_mask));
-    HIP_TRY(guard.alloc((size_t)slots * 2, &p.crlf_mask));
-    HIP_TRY(guard.alloc((size_t)slots * 2, &p.keep_mask));
-    HIP_TRY(guard.alloc((size_t)(tiles + 1) * 8, &p.tile_count));
-    HIP_TRY(guard.alloc((size_t)(tiles + 1) * 8, &p.tile_base));
-    if ((st = scan_room(std::max(tiles, S) + 1)) != TGX_OK) return st;
-    timer.begin(0);
-    HIP_TRY(tgx::launch_front_mark(p, d_scan, scan_bytes, hs));
-    timer.end(0);
-    uint64_t C = 0, K = 0, E = 0;
-    if ((st = count_at(p.tile_base + tiles, &C)) != TGX_OK) return st;
-    // candidates, resolve, the samples' segment counts
-    p.n_cand = C;
-    HIP_TRY(guard.alloc((size_t)C * 8, &p.cand_pos));
-    HIP_TRY(guard.alloc((size_t)C * 8, &p.cand_end));
-    HIP_TRY(guard.alloc((size_t)C * 8, &p.pm));
-    HIP_TRY(guard.alloc((size_t)C * 8, &p.acc_end));
-    HIP_TRY(guard.alloc((size_t)C * 8, &p.la));
-    HIP_TRY(guard.alloc((size_t)(C + 1) * 8, &p.seg_sum));
-    HIP_TRY(guard.alloc((size_t)C * 4, &p.cand_special));
-    HIP_TRY(guard.alloc((size_t)C * 4, &p.cand_sample));
-    HIP_TRY(guard.alloc((size_t)(C + 1) * 4, &p.cand_segs));
-    HIP_TRY(guard.alloc((size_t)(S + 1) * 8, &p.first));
-    HIP_TRY(guard.alloc((size_t)(S + 1) * 8, &p.sample_segs));
-    p.seg_offs = pl->d_seg_offs;
-    if ((st = scan_room(C + 1)) != TGX_OK) return st;
-    timer.begin(1);
-    HIP_TRY(tgx::launch_front_candidates(p, d_scan, scan_bytes, hs));
-    timer.end(1);
-    if ((st = count_at(p.seg_offs + S, &K)) != TGX_OK) return st;
-    // segments
-    p.n_segs = K;
-    HIP_TRY(pl->d_special.alloc(dev, (size_t)(K + 1) * 4));
-    p.seg_special = pl->d_special;
-    HIP_TRY(guard.alloc((size_t)K * 8, &p.seg_begin));
-    HIP_TRY(guard.alloc((size_t)K * 8, &p.seg_end));
-    HIP_TRY(guard.alloc((size_t)(K + 1) * 8, &p.rank));
-    if ((st = scan_room(K + 1)) != TGX_OK) return st;
-    timer.begin(2);
-    HIP_TRY(tgx::launch_front_segments(p, d_scan, scan_bytes, hs));
-    timer.end(2);
-    if ((st = count_at(p.rank + K, &E)) != TGX_OK) return st;
-    pl->n_segs = K;
-    pl->n_enc = E;
-    // keep and pack: the E + 1 offsets visit the host for the corpus's longest-first order
-    p.n_enc = E;
-    tgx_corpus* made = nullptr;
-    if (E) {
-        HIP_TRY(guard.alloc((size_t)E * 8, &p.enc_begin));
-        HIP_TRY(guard.alloc((size_t)E * 8, &p.enc_end));
-        HIP_TRY(guard.alloc((size_t)E * 4, &p.enc_local));
-        HIP_TRY(guard.alloc((size_t)(E + 1) * 8, &p.out_offs));
-        timer.begin(3);
-        HIP_TRY(tgx::launch_front_keep(p, d_scan, scan_bytes, hs));
-        timer.end(3);
-        h_out_offs.resize(E + 1);
-        HIP_TRY(hipMemcpyAsync(h_out_offs.data(), p.out_offs, (size_t)(E + 1) * 8, hipMemcpyDeviceToHost, hs));
-        HIP_TRY(hipStreamSynchronize(hs));
-        if ((st = corpus_create(who, dev, nullptr, TextFrom::Caller, h_out_offs.data(), E, &made)) != TGX_OK) return st;
-        out.reset(made);
-        p.out = out->d_text;
-        timer.begin(4);
-        if (out->n_bytes) HIP_TRY(tgx::launch_front_pack(p, hs));
-        timer.end(4);
-    } else {
-        if ((st = corpus_create(who, dev, nullptr, TextFrom::Caller, nullptr, 0, &made)) != TGX_OK) return st;
-        out.reset(made);
-    }
-    HIP_TRY(hipStreamSynchronize(hs));
-    guard.done();
-    timer.read();
-    *segs = out.release();
-    *plan = pl.release();
-    return TGX_OK;
-}
-
-// ---- Unicode normalisation on the device (norm.hip; norm.h) -------------------------------------------------------
-
-namespace {
-
-// device time of the last tgx_corpus_normalize of this thread, per stage (tgx_norm_last_times)
-const char* const kNormStageNames[kFrontStages] = {"norm_mark", "norm_pieces", "norm_length", "norm_places", "norm_write"};
-thread_local float g_norm_ms[kFrontStages] = {0, 0, 0, 0, 0};
-
-// the normaliser's tables on a device: uploaded by the first call that needs them there and kept for the process
-std::mutex g_norm_mu;
-struct NormDeviceTables {
-    bool ready = false;
-    tgx::NormTables tab = {};
-} g_norm_dev[64];
-
-tgx_status norm_device_tables(int dev, tgx::NormTables* out) {
-    if (dev < 0 || dev >= 64) return fail(TGX_ERR_INVALID, "device %d out of range", dev);
-    std::lock_guard<std::mutex> lk(g_norm_mu);
-    NormDeviceTables& d = g_norm_dev[dev];
-    if (!d.ready) {
-        const NormHostTables& h = norm_host_tables();
-        const tgx::NormTables& t = norm_tables_on_host();
-        const void* src[15] = {t.stage1,    t.stage2,     t.ccc_cp,     t.ccc_val,    t.canon_cp,   t.canon_off,   t.canon_seq,      t.canon_len,
-                               t.compat_cp, t.compat_off, t.compat_seq, t.compat_len, t.pair_first, t.pair_second, t.pair_composite};
-        const size_t bytes[15] = {h.stage1.size() * 2, h.stage2.size(),    h.ccc_cp_bytes,    h.ccc_val_bytes,   h.canon_cp_bytes,
-                                  h.canon_off_bytes,   h.canon_seq_bytes,  h.canon_len_bytes, h.compat_cp_bytes, h.compat_off_bytes,
-                                  h.compat_seq_bytes,  h.compat_len_bytes, h.pair_bytes,      h.pair_bytes,      h.pair_bytes};
-        size_t at[15], total = 0;
-        for (int k = 0; k < 15; k++) {
-            at[k] = total;
-            total += (bytes[k] + 255) & ~(size_t)255;
-        }
-        uint8_t* base = nullptr;
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&base), total));
-        for (int k = 0; k < 15; k++) {
-            const hipError_t e = hipMemcpy(base + at[k], src[k], bytes[k], hipMemcpyHostToDevice);
-            if (e != hipSuccess) {
-                (void)hipFree(base);
-                HIP_TRY(e);
-            }
-        }
-        auto u32 = [&](int k) { return reinterpret_cast<const uint32_t*>(base + at[k]); };
-        d.tab = t;
-        d.tab.stage1 = reinterpret_cast<const uint16_t*>(base + at[0]);
-        d.tab.stage2 = base + at[1];
-        d.tab.ccc_cp = u32(2);
-        d.tab.ccc_val = base + at[3];
-        d.tab.canon_cp = u32(4);
-        d.tab.canon_off = u32(5);
-        d.tab.canon_seq = u32(6);
-        d.tab.canon_len = base + at[7];
-        d.tab.compat_cp = u32(8);
-        d.tab.compat_off = u32(9);
-        d.tab.compat_seq = u32(10);
-        d.tab.compat_len = base + at[11];
-        d.tab.pair_first = u32(12);
-        d.tab.pair_second = u32(13);
-        d.tab.pair_composite = u32(14);
-        d.ready = true;
-    }
-    *out = d.tab;
-    return TGX_OK;
-}
-
-}  // namespace
-
-int tgx_norm_last_times(const char** names, float* ms, int cap) {
-    int n = 0;
-    for (; n < kFrontStages && n < cap; n++) {
-        if (names) names[n] = kNormStageNames[n];
-        if (ms) ms[n] = g_norm_ms[n];
-    }
-    return n;
-}
-
-tgx_status tgx_corpus_normalize(tgx_corpus* c, uint32_t form, tgx_corpus** out, uint64_t* n_pieces) {
-    const char* who = "tgx_corpus_normalize";
-    if (!c || !out || !n_pieces) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
-    *out = nullptr;
-    *n_pieces = 0;
-    if (form > 3) return fail(TGX_ERR_INVALID, "%s: form must be 0 (NFD), 1 (NFC), 2 (NFKD) or 3 (NFKC)", who);
-    tgx_status st = require_device();
-    if (st != TGX_OK) return st;
-    std::lock_guard<std::mutex> lkc(c->mu);
-    DeviceScope scope;
-    const int dev = c->device;
-    HIP_TRY(hipSetDevice(dev));
-    hipStream_t hs = stream_or_default(nullptr, dev);
-    const uint64_t S = c->n_samples, N = c->n_bytes;
-    std::unique_ptr<tgx_corpus> made_owner;  // the new corpus
-    std::vector<uint64_t> h_out_offs;
-    unsigned long long h_count = 0;
-    StreamGuard guard(dev, hs);  // destroyed before them: a failed call's queued work is over before they go
-    FrontTimer timer(hs, g_norm_ms);
-    tgx_corpus* made = nullptr;
-    auto copy_of_c = [&]() -> tgx_status {  // no piece: the same rows, device to device
-        if ((st = corpus_create(who, dev, c->d_text, TextFrom::Device, S ? c->h_offs.data() : nullptr, S, &made)) != TGX_OK) return st;
-        guard.done();
-        timer.read();
-        *out = made;
-        return TGX_OK;
-    };
-    if (S == 0 || N == 0) return copy_of_c();
-
-    tgx::NormParams p = {};
-    p.text = c->d_text;
-    p.offs = c->d_offs;
-    p.n_bytes = N;
-    p.n_rows = S;
-    p.form = form;
-    if ((st = norm_device_tables(dev, &p.tab)) != TGX_OK) return st;
-    const uint64_t tiles = (N + tgx::kFrontTile - 1) / tgx::kFrontTile, slots = (N + tgx::kFrontGroup - 1) / tgx::kFrontGroup;
-    void* d_scan = nullptr;
-    size_t scan_bytes = 0;
-    uint64_t scan_n = 0;
-    auto scan_room = [&](uint64_t n) -> tgx_status {
-        if (n <= scan_n) return TGX_OK;
-        if (tgx::norm_scan_temp_bytes(n, &scan_bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan temp-size query failed");
-        HIP_TRY(guard.alloc(scan_bytes, &d_scan));  // (never NULL: that asks the scan for its size)
-        scan_n = n;
-        return TGX_OK;
-    };
-    auto count_at = [&](const uint64_t* d, uint64_t* v) -> tgx_status {  // one counter to the host
-        HIP_TRY(hipMemcpyAsync(&h_count, d, 8, hipMemcpyDeviceToHost, hs));
-        HIP_TRY(hipStreamSynchronize(hs));
-        *v = h_count;
-        return TGX_OK;
-    };
-    // mark
-    HIP_TRY(guard.alloc((size_t)slots * 4, &p.mask));
-    HIP_TRY(guard.alloc((size_t)(tiles + 1) * 8, &p.tile_count));
-    HIP_TRY(guard.alloc((size_t)(tiles + 1) * 8, &p.tile_base));
-    if ((st = scan_room(tiles + 1)) != TGX_OK) return st;
-    timer.begin(0);
-    HIP_TRY(tgx::launch_norm_mark(p, d_scan, scan_bytes, hs));
-    timer.end(0);
-    uint64_t P = 0, overflow_row = tgx::kNormNoRow;
-    if ((st = count_at(p.tile_base + tiles, &P)) != TGX_OK) return st;
-    if (P == 0) return copy_of_c();
-    // pieces, their lengths
-    p.n_pieces = P;
-    HIP_TRY(guard.alloc((size_t)P * 8, &p.piece_begin));
-    HIP_TRY(guard.alloc((size_t)P * 8, &p.piece_row));
-    HIP_TRY(guard.alloc((size_t)(P + 1) * 8, &p.piece_len));
-    HIP_TRY(guard.alloc((size_t)(P + 1) * 8, &p.piece_sum));
-    HIP_TRY(guard.alloc(8, &p.overflow_row));
-    if ((st = scan_room(P + 1)) != TGX_OK) return st;
-    timer.begin(1);
-    HIP_TRY(tgx::launch_norm_pieces(p, hs));
-    timer.end(1);
-    timer.begin(2);
-    HIP_TRY(tgx::launch_norm_length(p, d_scan, scan_bytes, hs));
-    timer.end(2);
-    if ((st = count_at(p.overflow_row, &overflow_row)) != TGX_OK) return st;
-    if (overflow_row != tgx::kNormNoRow) {
-        guard.done();  // (the stream has reached its end)
-        return norm_overflow(who, overflow_row);
-    }
-    // places: the S + 1 offsets visit the host for the corpus's longest-first order
-    HIP_TRY(guard.alloc((size_t)slots * 4, &p.slot_pre));
-    HIP_TRY(guard.alloc((size_t)(tiles + 1) * 8, &p.tile_bytes));
-    HIP_TRY(guard.alloc((size_t)(tiles + 1) * 8, &p.tile_place));
-    HIP_TRY(guard.alloc((size_t)(S + 1) * 8, &p.out_offs));
-    timer.begin(3);
-    HIP_TRY(tgx::launch_norm_places(p, d_scan, scan_bytes, hs));
-    timer.end(3);
-    h_out_offs.resize(S + 1);
-    HIP_TRY(hipMemcpyAsync(h_out_offs.data(), p.out_offs, (size_t)(S + 1) * 8, hipMemcpyDeviceToHost, hs));
-    HIP_TRY(hipStreamSynchronize(hs));
-    if ((st = corpus_create(who, dev, nullptr, TextFrom::Caller, h_out_offs.data(), S, &made)) != TGX_OK) return st;
-    made_owner.reset(made);
-    p.out = made->d_text;
-    timer.begin(4);
-    HIP_TRY(tgx::launch_norm_write(p, hs));
-    timer.end(4);
-    HIP_TRY(hipStreamSynchronize(hs));
-    guard.done();
-    timer.read();
-    *out = made_owner.release();
-    *n_pieces = P;
-    return TGX_OK;
-}
-
-uint64_t tgx_plan_num_samples(const tgx_plan* p) { return p ? p->n_samples : 0; }
-uint64_t tgx_plan_num_segments(const tgx_plan* p) { return p ? p->n_segs : 0; }
-uint64_t tgx_plan_num_encoded(const tgx_plan* p) { return p ? p->n_enc : 0; }
-int tgx_plan_device(const tgx_plan* p) { return p ? p->device : -1; }
-// (the call that made it returned after its stream had reached its end: the buffers go straight back to the pool)
-void tgx_plan_free(tgx_plan* p) { delete p; }
-
-tgx_status tgx_plan_copy(const tgx_plan* p, uint64_t* seg_offs, uint64_t offs_cap, int32_t* seg_special, uint64_t special_cap) {
-    const char* who = "tgx_plan_copy";
-    if (!p || !seg_offs || (!seg_special && p->n_segs)) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
-    if (offs_cap < p->n_samples + 1) return fail(TGX_ERR_INVALID, "%s: %llu offsets, room for %llu", who, (unsigned long long)(p->n_samples + 1), (unsigned long long)offs_cap);
-    if (special_cap < p->n_segs) return fail(TGX_ERR_INVALID, "%s: %llu segments, room for %llu", who, (unsigned long long)p->n_segs, (unsigned long long)special_cap);
-    DeviceScope scope;
-    HIP_TRY(hipSetDevice(p->device));
-    HIP_TRY(copy_sync(seg_offs, p->d_seg_offs, (size_t)(p->n_samples + 1) * 8, hipMemcpyDeviceToHost, p->device));
-    if (p->n_segs) HIP_TRY(copy_sync(seg_special, p->d_special, (size_t)p->n_segs * 4, hipMemcpyDeviceToHost, p->device));
-    return TGX_OK;
-}
-
-// ---- fill-in-the-middle: a result's rows rearranged behind three sentinels (fim.hip; fim.h has the index arithmetic) ----
-
-namespace {
-
-// device time of the last tgx_result_fim of this thread, per stage (tgx_fim_last_times; a FrontTimer's array)
-constexpr int kFimStages = 3;
-const char* const kFimStageNames[kFimStages] = {"fim_offsets_scan", "fim_fill_kernel", "fim_info_kernel"};
-thread_local float g_fim_ms[kFrontStages] = {0, 0, 0, 0, 0};
-static_assert(kFimStages <= kFrontStages, "the stages share FrontTimer");
-
-}  // namespace
-
-int tgx_fim_last_times(const char** names, float* ms, int cap) {
-    int n = 0;
-    for (; n < kFimStages && n < cap; n++) {
-        if (names) names[n] = kFimStageNames[n];
-        if (ms) ms[n] = g_fim_ms[n];
-    }
-    return n;
-}
-
-tgx_status tgx_result_from_ids(int device, const uint32_t* ids, const uint64_t* offs, uint64_t n_rows, uint32_t vocab_size, tgx_result** out) {
-    const char* who = "tgx_result_from_ids";
-    if (!out) return fail(TGX_ERR_INVALID, "%s: out is NULL", who);
-    *out = nullptr;
-    tgx_status st = result_check_host(who, ids, offs, n_rows, vocab_size);
-    if (st != TGX_OK) return st;
-    int n_devices = 0;
-    if ((st = require_device(&n_devices)) != TGX_OK) return st;
-    if (device < 0 || device >= n_devices) return fail(TGX_ERR_INVALID, "%s: device %d of %d", who, device, n_devices);
-    DeviceScope scope;
-    HIP_TRY(hipSetDevice(device));
-    std::unique_ptr<tgx_result> r(new tgx_result());
-    r->device = device;
-    r->vocab_size = vocab_size;
-    r->n_samples = n_rows;
-    r->n_tokens = offs[n_rows];
-    if (r->d_offs.alloc(device, (size_t)(n_rows + 1) * 8) != hipSuccess || r->d_ids.alloc(device, (size_t)r->n_tokens * 4 + 256) != hipSuccess)
-        return fail(TGX_ERR_DEVICE, "out of device memory (result from ids)");
-    HIP_TRY(copy_sync(r->d_offs, offs, (size_t)(n_rows + 1) * 8, hipMemcpyHostToDevice, device));
-    if (r->n_tokens) HIP_TRY(copy_sync(r->d_ids, ids, (size_t)r->n_tokens * 4, hipMemcpyHostToDevice, device));
-    *out = r.release();
-    return TGX_OK;
-}
-
-tgx_status tgx_result_fim(const tgx_result* r, uint32_t prefix_id, uint32_t suffix_id, uint32_t middle_id, double rate, double spm_rate,
-                          uint64_t seed, uint64_t first_row, void* stream, uint8_t* mode, uint64_t* cuts, uint64_t* n_applied, tgx_result** out) {
-    const char* who = "tgx_result_fim";
-    if (!r || !out) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
-    *out = nullptr;
-    tgx_status st = fim_check(who, prefix_id, suffix_id, middle_id, rate, spm_rate);
-    if (st != TGX_OK) return st;
-    const uint64_t S = r->n_samples;
-    DeviceScope scope;
-    HIP_TRY(hipSetDevice(r->device));
-    hipStream_t hs = stream_or_default(stream, r->device);
-    std::unique_ptr<tgx_result> res(new tgx_result());  // before the guard: its buffers go back after the stream's end
-    uint64_t h_total = 0;
-    FrontTimer timer(hs, g_fim_ms);  // (before the guard: its events outlive the stream's work)
-    StreamGuard guard(r->device, hs);
-    res->device = r->device;
-    res->vocab_size = fim_vocab_size(r->vocab_size, prefix_id, suffix_id, middle_id);
-    res->n_samples = S;
-    size_t scan_bytes = 0;
-    if (tgx::fim_scan_temp_bytes(S, &scan_bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan temp-size query failed");
-    void* d_scan = nullptr;
-    if (res->d_offs.alloc(r->device, (size_t)(S + 1) * 8) != hipSuccess || guard.alloc(scan_bytes, &d_scan) != hipSuccess)  // (never NULL: that asks the scan for its size)
-        return fail(TGX_ERR_DEVICE, "out of device memory (fill-in-the-middle)");
-    tgx::FimParams p = {};
-    p.ids = r->d_ids;
-    p.offs = r->d_offs;
-    p.n_rows = S;
-    p.f = tgx::FimArgs{seed, first_row, rate, spm_rate, prefix_id, suffix_id, middle_id};
-    p.out_offs = res->d_offs;
-    timer.begin(0);
-    if (tgx::launch_fim_offsets(p, d_scan, scan_bytes, hs) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan launch failed");
-    timer.end(0);
-    // the one word that visits the host: T' sizes the id buffer
-    HIP_TRY(hipMemcpyAsync(&h_total, res->d_offs.get() + S, 8, hipMemcpyDeviceToHost, hs));
-    HIP_TRY(hipStreamSynchronize(hs));
-    if (h_total < r->n_tokens || (h_total - r->n_tokens) % 3 || (h_total - r->n_tokens) / 3 > S)
-        return fail(TGX_ERR_DEVICE, "%s: %llu ids from %llu over %llu rows", who, (unsigned long long)h_total, (unsigned long long)r->n_tokens,
-                    (unsigned long long)S);
-    res->n_tokens = h_total;
-    if (res->d_ids.alloc(r->device, (size_t)h_total * 4 + 256) != hipSuccess) return fail(TGX_ERR_DEVICE, "out of device memory (fill-in-the-middle)");
-    p.n_out = h_total;
-    p.out_ids = res->d_ids;
-    timer.begin(1);
-    if (tgx::launch_fim_fill(p, hs) != hipSuccess) return fail(TGX_ERR_DEVICE, "fim_fill_kernel launch failed");
-    timer.end(1);
-    if (S && (mode || cuts)) {
-        uint8_t* d_mode = nullptr;
-        uint64_t* d_cuts = nullptr;
-        if (mode) HIP_TRY(guard.alloc((size_t)S, &d_mode));
-        if (cuts) HIP_TRY(guard.alloc((size_t)S * 16, &d_cuts));
-        timer.begin(2);
-        if (tgx::launch_fim_info(p, d_mode, d_cuts, hs) != hipSuccess) return fail(TGX_ERR_DEVICE, "fim_info_kernel launch failed");
-        timer.end(2);
-        if (mode) HIP_TRY(hipMemcpyAsync(mode, d_mode, (size_t)S, hipMemcpyDeviceToHost, hs));
-        if (cuts) HIP_TRY(hipMemcpyAsync(cuts, d_cuts, (size_t)S * 16, hipMemcpyDeviceToHost, hs));
-    }
-    // the stream has reached its end before either result can change hands (the guard: also after a failure)
-    HIP_TRY(hipStreamSynchronize(hs));
-    guard.done();
-    timer.read();
-    if (n_applied) *n_applied = (h_total - r->n_tokens) / 3;
-    *out = res.release();
-    return TGX_OK;
-}
-
-// ---- spans: the part of its row's text that every token covers (spans.hip; spans.h has the index arithmetic) ------
-
-namespace {
-
-// the model's token words on its device, once (under m->mu)
-tgx_status ensure_span_words(tgx_model* m) {
-    std::lock_guard<std::mutex> lk(m->mu);
-    if (m->span_words_ready) return TGX_OK;
-    const uint32_t V = m->vocab_size;
-    std::vector<uint16_t> words;
-    const tgx_status st = span_build_words("spans", m->vocab_bytes.data(), m->vocab_offs.data(), V, &words);
-    if (st != TGX_OK) return st;
-    if (!m->d_span_words) HIP_TRY(hipMalloc((void**)&m->d_span_words, ((size_t)V + 8) * 2));
-    if (V) HIP_TRY(hipMemcpy(m->d_span_words, words.data(), (size_t)V * 2, hipMemcpyHostToDevice));
-    m->span_words_ready = true;
-    return TGX_OK;
-}
-
-// The first half of a spans call over a result with T >= 1 tokens: the model's words, the specials' words, the value
-// words and their prefix sums in pooled scratch of the guard, and for int32 spans the check of the rows' totals (one
-// word is read back; nothing has been written to the destination when a row does not fit).  Fills p's tables, source
-// and scratch; p->flags is set by the caller.
-tgx_status span_sums_device(const char* who, tgx_model* m, const tgx_result* r, const uint8_t* special_bytes, const uint64_t* special_offs,
-                            uint32_t n_specials, hipStream_t hs, StreamGuard& guard, tgx::SpanParams* p) {
-    const bool chars = (p->flags & TGX_SPAN_CHARS) != 0, i64 = (p->flags & TGX_LAYOUT_I64) != 0;
-    const uint64_t T = r->n_tokens;
-    const tgx_status st = ensure_span_words(m);
-    if (st != TGX_OK) return st;
-    std::vector<uint64_t> sp_words;
-    span_special_words(special_bytes, special_offs, n_specials, chars, &sp_words);
-    size_t scan_bytes = 0;
-    if (tgx::span_scan_temp_bytes(T, &scan_bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan temp-size query failed");
-    uint32_t* vals = nullptr;
-    uint64_t *sums = nullptr, *d_sp_words = nullptr;
-    void* scan = nullptr;
-    HIP_TRY(guard.alloc((size_t)(T + 1) * 4, &vals));
-    HIP_TRY(guard.alloc((size_t)(T + 1) * 8, &sums));
-    HIP_TRY(guard.alloc(scan_bytes, &scan));  // (never NULL: that asks the scan for its size)
-    HIP_TRY(guard.alloc(sp_words.size() * 8, &d_sp_words));
-    HIP_TRY(guard.upload(d_sp_words, std::move(sp_words)));
-    p->tab.words = m->d_span_words;
-    p->tab.sp_words = d_sp_words;
-    p->tab.vocab_size = m->vocab_size;
-    p->tab.n_specials = n_specials;
-    p->ids = r->d_ids;
-    p->offs = r->d_offs;
-    p->n_rows = r->n_samples;
-    p->n = T;
-    p->vals = vals;
-    p->sums = sums;
-    HIP_TRY(tgx::launch_span_sums(*p, scan, scan_bytes, hs));
-    if (!i64) {  // nothing is written when a row does not fit: the one word that is read back
-        unsigned long long h_max = 0, *row_max = nullptr;
-        HIP_TRY(guard.alloc(sizeof(unsigned long long), &row_max));
-        p->row_max = row_max;
-        HIP_TRY(hipMemsetAsync(row_max, 0, sizeof(unsigned long long), hs));
-        HIP_TRY(tgx::launch_span_row_max(*p, hs));
-        HIP_TRY(hipMemcpyAsync(&h_max, row_max, sizeof(unsigned long long), hipMemcpyDeviceToHost, hs));
-        HIP_TRY(hipStreamSynchronize(hs));
-        if (h_max >= 0x80000000ull) return span_too_long(who, h_max, chars);
-    }
-    return TGX_OK;
-}
-
-// row_len = 0: the flat form
-tgx_status spans_device(const char* who, tgx_model* m, const tgx_result* r, const uint8_t* special_bytes, const uint64_t* special_offs,
-                        uint32_t n_specials, uint32_t row_len, uint32_t bos_id, uint32_t eos_id, uint32_t flags, void* stream, void* d_spans) {
-    if (!m || !r) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
-    const bool padded = row_len != 0;
-    const tgx_status st0 = span_check_args(who, m->vocab_size, special_bytes, special_offs, n_specials, padded, row_len, bos_id, eos_id, flags);
-    if (st0 != TGX_OK) return st0;
-    const uint64_t S = r->n_samples, T = r->n_tokens;
-    const uint64_t n_pairs = padded ? S * (uint64_t)row_len : (S ? T : 0);
-    if (!d_spans && n_pairs) return fail(TGX_ERR_INVALID, "%s: d_spans is NULL", who);
-    tgx_status st = require_device();
-    if (st != TGX_OK) return st;
-    if (r->device != m->device) return fail(TGX_ERR_INVALID, "%s: the result is on device %d, the model on device %d", who, r->device, m->device);
-    if ((uint64_t)r->vocab_size > (uint64_t)m->vocab_size + n_specials)
-        return fail(TGX_ERR_INVALID, "%s: the result was written for %u ids, the model has %u tokens and %u special tokens", who, r->vocab_size,
-                    m->vocab_size, n_specials);
-    if (n_pairs == 0) return TGX_OK;
-    DeviceScope scope;
-    HIP_TRY(hipSetDevice(m->device));
-    if ((st = check_device_ptr(who, "d_spans", d_spans, m->device, "result")) != TGX_OK) return st;
-    hipStream_t hs = stream_or_default(stream, m->device);
-    const int dev = m->device;
-    const bool i64 = (flags & TGX_LAYOUT_I64) != 0;
-    if (T == 0) {  // the padded form of rows without tokens
-        StreamGuard guard(dev, hs);
-        HIP_TRY(hipMemsetAsync(d_spans, 0, (size_t)n_pairs * 2 * (i64 ? 8 : 4), hs));
-        HIP_TRY(hipStreamSynchronize(hs));
-        guard.done();
-        return TGX_OK;
-    }
-    StreamGuard guard(dev, hs);
-    tgx::SpanParams p = {};
-    p.len = row_len;
-    p.bos = bos_id;
-    p.eos = eos_id;
-    p.flags = flags;
-    p.out = d_spans;
-    if ((st = span_sums_device(who, m, r, special_bytes, special_offs, n_specials, hs, guard, &p)) != TGX_OK) return st;
-    HIP_TRY(padded ? tgx::launch_span_pad(p, hs) : tgx::launch_span_flat(p, hs));
-    // the stream has reached its end before the result or the destination can change hands
-    HIP_TRY(hipStreamSynchronize(hs));
-    guard.done();
-    return TGX_OK;
-}
-
-}  // namespace
-
-tgx_status tgx_result_spans_device(tgx_model* m, const tgx_result* r, const uint8_t* special_bytes, const uint64_t* special_offs,
-                                   uint32_t n_specials, uint32_t flags, void* stream, void* d_spans) {
-    return spans_device("tgx_result_spans_device", m, r, special_bytes, special_offs, n_specials, 0, TGX_NO_ID, TGX_NO_ID, flags, stream, d_spans);
-}
-
-tgx_status tgx_result_pad_spans_device(tgx_model* m, const tgx_result* r, const uint8_t* special_bytes, const uint64_t* special_offs,
-                                       uint32_t n_specials, uint32_t row_len, uint32_t bos_id, uint32_t eos_id, uint32_t flags, void* stream,
-                                       void* d_spans) {
-    const char* who = "tgx_result_pad_spans_device";
-    if (row_len == 0) return fail(TGX_ERR_INVALID, "%s: row_len 0 (needs >= 1)", who);
-    return spans_device(who, m, r, special_bytes, special_offs, n_specials, row_len, bos_id, eos_id, flags, stream, d_spans);
-}
-
-tgx_status tgx_result_window_spans_device(tgx_model* m, const tgx_result* r, const uint8_t* special_bytes, const uint64_t* special_offs,
-                                          uint32_t n_specials, uint32_t row_len, uint32_t stride, uint32_t bos_id, uint32_t eos_id, uint32_t flags,
-                                          void* stream, uint64_t n_windows, void* d_spans) {
-    const char* who = "tgx_result_window_spans_device";
-    if (!m || !r) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
-    if (row_len == 0) return fail(TGX_ERR_INVALID, "%s: row_len 0 (needs >= 1)", who);
-    tgx_status st = span_check_args(who, m->vocab_size, special_bytes, special_offs, n_specials, true, row_len, bos_id, eos_id, flags);
-    const tgx::LayoutSeq seq = tgx::layout_seq(bos_id, eos_id, 0);
-    if (st == TGX_OK) st = window_check_args(who, row_len, stride, seq.extra);
-    if (st != TGX_OK) return st;
-    const uint64_t S = r->n_samples, T = r->n_tokens;
-    if (!d_spans && S) return fail(TGX_ERR_INVALID, "%s: d_spans is NULL", who);
-    if ((st = require_device()) != TGX_OK) return st;
-    if (r->device != m->device) return fail(TGX_ERR_INVALID, "%s: the result is on device %d, the model on device %d", who, r->device, m->device);
-    if ((uint64_t)r->vocab_size > (uint64_t)m->vocab_size + n_specials)
-        return fail(TGX_ERR_INVALID, "%s: the result was written for %u ids, the model has %u tokens and %u special tokens", who, r->vocab_size,
-                    m->vocab_size, n_specials);
-    if (S == 0) return window_check_totals(who, 0, 0, &n_windows);
-    DeviceScope scope;
-    HIP_TRY(hipSetDevice(m->device));
-    if ((st = check_device_ptr(who, "d_spans", d_spans, m->device, "result")) != TGX_OK) return st;
-    hipStream_t hs = stream_or_default(stream, m->device);
-    StreamGuard guard(m->device, hs);
-    const uint64_t* d_wo = nullptr;
-    uint64_t W = 0;
-    st = window_offsets_device(who, r, row_len - seq.extra, row_len - seq.extra - stride, hs, guard, &d_wo, &W);
-    if (st == TGX_OK) st = window_check_totals(who, 0, W, &n_windows);
-    if (st != TGX_OK) return st;
-    if (T == 0) {  // rows without tokens: W = S windows of padding
-        HIP_TRY(hipMemsetAsync(d_spans, 0, (size_t)W * row_len * 2 * ((flags & TGX_LAYOUT_I64) ? 8 : 4), hs));
-    } else {
-        tgx::SpanParams p = {};
-        p.len = row_len;
-        p.bos = bos_id;
-        p.eos = eos_id;
-        p.flags = flags;
-        p.out = d_spans;
-        if ((st = span_sums_device(who, m, r, special_bytes, special_offs, n_specials, hs, guard, &p)) != TGX_OK) return st;
-        HIP_TRY(tgx::launch_span_windows(p, d_wo, stride, W, hs));
-    }
-    // the stream has reached its end before the result or the destination can change hands
-    HIP_TRY(hipStreamSynchronize(hs));
-    guard.done();
-    return TGX_OK;
-}
+}  // namespace tgx::dev
 
 // ---- frequency pass ------------------------------------------------------------
 
