@@ -712,6 +712,31 @@ tgx_status tgx_encode_batch_sample(tgx_model *m, const uint8_t *text, const uint
 tgx_status tgx_encode_corpus_sample(tgx_model *m, tgx_corpus *c, double alpha, uint64_t seed,
                                     double *logz, tgx_result **out);
 
+/* ---- lattice statistics: log Z, expected score and expected token count per sample ---
+ * A forward-only sweep over the lattice sampling draws from: for a sample of n bytes the matches are what encode sees
+ * with dropout 0, and P(x) ∝ exp(alpha · Σ_{t ∈ x} score(t)) over the segmentations x of the sample.  Per sample:
+ *   logz    = log Σ_x exp(alpha · score(x)): the A[n] that tgx_encode_batch_sample reports, log P(text) at alpha = 1;
+ *   escore  = E_P[Σ_t score(t)], on the raw scores (not multiplied by alpha);
+ *   etokens = E_P[number of tokens of x].
+ * The entropy of P is logz − alpha · escore (nats).  Nothing is drawn, traced or returned as ids: the sweep carries the
+ * expectation semiring (a, r, c) with r[p] = Σ (r[q]·w + a[q]·w·s), c[p] = Σ (c[q]·w + a[q]·w) over the matches
+ * (q, len, w = exp(alpha · s)) ending at p, escore = r[n] / a[n], etokens = c[n] / a[n].
+ *   logz, escore, etokens: each NULL or f64[n_samples] in host memory, input order.
+ *   An empty sample gives 0, 0, 0.  A sample whose end no path reaches gives logz = −inf and escore = etokens = NaN;
+ *   the call still returns TGX_OK, and the number of such samples goes to *n_no_path (NULL or one u64).
+ *   alpha must be finite and >= 0, and alpha · score finite for every token (else TGX_ERR_INVALID); a non-finite
+ *   score gives TGX_ERR_UNSUPPORTED: the statuses of tgx_encode_batch_sample.  alpha = 0 is the uniform distribution:
+ *   logz = log(number of segmentations).  A later duplicate token overrides an earlier one, as in the model.
+ *   tgx_lattice_stats_host is the twin: plain f64 on the host over the vocabulary arrays (vocab_offs u64[vocab_size + 1],
+ *   any base), in the log-domain formulation of the generic kernel; no device, no model. */
+tgx_status tgx_lattice_stats_corpus(tgx_model *m, tgx_corpus *c, double alpha,
+                                    double *logz, double *escore, double *etokens, uint64_t *n_no_path);
+tgx_status tgx_lattice_stats_batch(tgx_model *m, const uint8_t *text, const uint64_t *offs, uint64_t n_samples,
+                                   double alpha, double *logz, double *escore, double *etokens, uint64_t *n_no_path);
+tgx_status tgx_lattice_stats_host(const uint8_t *vocab_bytes, const uint64_t *vocab_offs, const double *scores,
+                                  uint32_t vocab_size, const uint8_t *text, const uint64_t *offs, uint64_t n_samples,
+                                  double alpha, double *logz, double *escore, double *etokens, uint64_t *n_no_path);
+
 /* ---- n-best segmentation: the k highest-scoring segmentations per sample ---
  * SentencePiece's NBestEncode (and the list that SampleEncode with nbest_size > 1 draws from).  For a sample of n
  * bytes the matches are what encode sees with dropout 0: a match is (q, len, id, s), s = score[id].  Every position p

@@ -3,6 +3,6 @@
 the MI355X implementation in `tokengeex_amd`: code written against the reference's package runs unchanged.
 (The reference creates TokenGeeXError but never adds it to its module, bindings/python/src/lib.rs:226-233;
 it is exported here, as its stub promises.)"""
-from tokengeex_amd import TokenGeeXError, Tokenizer  # noqa: F401
+from tokengeex_amd import LatticeStats, TokenGeeXError, Tokenizer  # noqa: F401  (LatticeStats: what Tokenizer.lattice_stats returns)
 
-__all__ = ["Tokenizer", "TokenGeeXError"]
+__all__ = ["Tokenizer", "TokenGeeXError", "LatticeStats"]

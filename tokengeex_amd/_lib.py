@@ -108,6 +108,9 @@ SYMBOLS = {
     "tgx_sample_u01": (_d, [_u64, _u64, _u64, _u32]),
     "tgx_encode_batch_sample": (_i, [_vp, _vp, _vp, _u64, _d, _u64, _vp, _pvp]),
     "tgx_encode_corpus_sample": (_i, [_vp, _vp, _d, _u64, _vp, _pvp]),
+    "tgx_lattice_stats_corpus": (_i, [_vp, _vp, _d, _vp, _vp, _vp, _pu64]),
+    "tgx_lattice_stats_batch": (_i, [_vp, _vp, _vp, _u64, _d, _vp, _vp, _vp, _pu64]),
+    "tgx_lattice_stats_host": (_i, [_vp, _vp, _vp, _u32, _vp, _vp, _u64, _d, _vp, _vp, _vp, _pu64]),
     "tgx_encode_batch_nbest": (_i, [_vp, _vp, _vp, _u64, _u32, _vp, _vp, _pvp]),
     "tgx_encode_corpus_nbest": (_i, [_vp, _vp, _u32, _vp, _vp, _pvp]),
     "tgx_result_device": (_i, [_vp]),
@@ -774,6 +777,54 @@ def window_spans_host(vocab_flat, vocab_offs, vocab_size: int, special_flat, spe
     return out
 
 
+class LatticeStats:
+    """Per-sample statistics of the Unigram lattice under P(x) ∝ exp(alpha · Σ score) (include/tgx.h: lattice statistics):
+    logz, expected_score (raw scores), expected_tokens and n_bytes, f64 / u64 arrays in input order.  A sample whose
+    end no path reaches has logz = -inf and NaN in the other two (no_path); n_no_path counts them."""
+
+    def __init__(self, logz, expected_score, expected_tokens, n_bytes, alpha: float, n_no_path: int | None = None):
+        self.logz = np.asarray(logz, np.float64)
+        self.expected_score = np.asarray(expected_score, np.float64)
+        self.expected_tokens = np.asarray(expected_tokens, np.float64)
+        self.n_bytes = np.asarray(n_bytes, np.uint64)
+        self.alpha = float(alpha)
+        self.n_no_path = int(np.count_nonzero(np.isneginf(self.logz))) if n_no_path is None else int(n_no_path)
+
+    def __len__(self) -> int:
+        return self.logz.shape[0]
+
+    @property
+    def no_path(self) -> np.ndarray:
+        return np.isneginf(self.logz)
+
+    @property
+    def entropy(self) -> np.ndarray:
+        """Entropy of the segmentation distribution in nats: logz − alpha · expected_score (NaN where no_path)."""
+        with np.errstate(invalid="ignore"):
+            return self.logz - self.alpha * self.expected_score
+
+    @property
+    def bits_per_byte(self) -> np.ndarray:
+        """−logz / (n_bytes · ln 2): at alpha = 1 the text's cost under the unigram LM (NaN for an empty sample)."""
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return -self.logz / (self.n_bytes.astype(np.float64) * np.log(2.0))
+
+
+def lattice_stats_host(tokens: list[bytes], scores, flat: np.ndarray, offs: np.ndarray, alpha: float = 1.0) -> LatticeStats:
+    """The host twin of NativeModel.lattice_stats_flat (tgx_lattice_stats_host): plain f64, no device, no model."""
+    vflat, voffs = pack(tokens)
+    scores = np.ascontiguousarray(scores, dtype=np.float64)
+    flat = np.ascontiguousarray(flat, dtype=np.uint8)
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    n = offs.shape[0] - 1
+    out = np.zeros((3, max(n, 1)), np.float64)
+    bad = C.c_uint64(0)
+    check(lib.tgx_lattice_stats_host(ptr(vflat) if vflat.size else None, ptr(voffs), ptr(scores) if scores.size else None, len(tokens),
+                                     ptr(flat) if flat.size else None, ptr(offs), n, float(alpha), ptr(out[0]), ptr(out[1]), ptr(out[2]),
+                                     C.byref(bad)))
+    return LatticeStats(out[0, :n].copy(), out[1, :n].copy(), out[2, :n].copy(), np.diff(offs), alpha, bad.value)
+
+
 class NativeResult:
     """Owns a tgx_result (ids + offsets of one encode pass)."""
 
@@ -1223,6 +1274,28 @@ class NativeModel:
         check(lib.tgx_encode_batch_sample(self._h, ptr(flat) if flat.size else None, ptr(offs), n, float(alpha),
                                           seed & (2**64 - 1), ptr(logz) if return_logz else None, C.byref(h)))
         return (NativeResult(h), logz[:n]) if return_logz else NativeResult(h)
+
+    def lattice_stats_flat(self, flat: np.ndarray, offs: np.ndarray, alpha: float = 1.0) -> LatticeStats:
+        """log Z, expected score and expected token count of every sample's lattice under temperature alpha, by one
+        forward sweep on the device (tgx_lattice_stats_batch).  No sample fails the call: see LatticeStats.no_path."""
+        flat = np.ascontiguousarray(flat, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        n = offs.shape[0] - 1
+        out = np.zeros((3, max(n, 1)), np.float64)
+        bad = C.c_uint64(0)
+        if n <= 0:  # nothing to upload
+            return LatticeStats(out[0, :0], out[1, :0], out[2, :0], np.zeros(0, np.uint64), alpha, 0)
+        check(lib.tgx_lattice_stats_batch(self._h, ptr(flat) if flat.size else None, ptr(offs), n, float(alpha), ptr(out[0]), ptr(out[1]),
+                                          ptr(out[2]), C.byref(bad)))
+        return LatticeStats(out[0, :n].copy(), out[1, :n].copy(), out[2, :n].copy(), np.diff(offs), alpha, bad.value)
+
+    def lattice_stats_corpus(self, corpus: NativeCorpus, alpha: float = 1.0) -> LatticeStats:
+        """lattice_stats_flat over a resident corpus (tgx_lattice_stats_corpus)."""
+        n = corpus.num_samples
+        out = np.zeros((3, max(n, 1)), np.float64)
+        bad = C.c_uint64(0)
+        check(lib.tgx_lattice_stats_corpus(self._h, corpus._h, float(alpha), ptr(out[0]), ptr(out[1]), ptr(out[2]), C.byref(bad)))
+        return LatticeStats(out[0, :n].copy(), out[1, :n].copy(), out[2, :n].copy(), np.diff(corpus.offsets()), alpha, bad.value)
 
     def assemble(self, segs: "NativeResult | None", seg_offs: np.ndarray, seg_special: np.ndarray, n_specials: int) -> NativeResult:
         """The sample-level result of a batch split at special tokens, put together on the device (tgx_assemble_result,

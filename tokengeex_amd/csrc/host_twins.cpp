@@ -1,12 +1,14 @@
 // The *_host twins of the result-side device entry points (include/tgx.h): tgx_layout_pad_host, tgx_layout_pack_host,
-// tgx_layout_windows_host, tgx_assemble_host, tgx_fim_host, tgx_decode_rows_host, tgx_spans_host, tgx_window_spans_host, tgx_front_host and
-// tgx_normalize_host, and the
+// tgx_layout_windows_host, tgx_assemble_host, tgx_fim_host, tgx_decode_rows_host, tgx_spans_host, tgx_window_spans_host, tgx_front_host,
+// tgx_normalize_host and tgx_lattice_stats_host, and the
 // argument checks they share with the device entry points of tgx_api.cpp.  A twin goes through the same index arithmetic as its kernels (layout.h, assemble.h,
 // fim.h, decode.h, spans.h, front.h, norm.h) on host memory.  Nothing in this file calls a HIP function, so it builds and runs without the
 // handles, the pool or a device.
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <unordered_map>
 #include <vector>
 
 #include "api_internal.h"
@@ -1094,5 +1096,104 @@ tgx_status tgx_window_spans_host(const uint8_t* vocab_bytes, const uint64_t* voc
         window_spans_host_write(seq, offs, wo.data(), S, T, W, P.data(), v, row_len, stride, flags, static_cast<int64_t*>(out));
     else
         window_spans_host_write(seq, offs, wo.data(), S, T, W, P.data(), v, row_len, stride, flags, static_cast<int32_t*>(out));
+    return TGX_OK;
+}
+
+// ---- lattice statistics -------------------------------------------------------------
+
+namespace {
+
+// the vocabulary as a byte trie of its own: child (node, byte) by hash, a later duplicate token overrides an earlier one
+struct StatsTrie {
+    std::unordered_map<uint64_t, uint32_t> next;  // node << 8 | byte -> node
+    std::vector<double> score;                    // per node
+    std::vector<uint8_t> terminal;
+};
+
+// log(exp(a) + exp(b)) for a, b finite or -inf (stats.hip: stats_log_add)
+double stats_log_add_host(double a, double b) {
+    const double hi = a > b ? a : b, lo = a > b ? b : a;
+    if (lo == -HUGE_VAL) return hi;
+    return hi + log1p(exp(lo - hi));
+}
+
+}  // namespace
+
+tgx_status tgx_lattice_stats_host(const uint8_t* vocab_bytes, const uint64_t* vocab_offs, const double* scores, uint32_t vocab_size,
+                                  const uint8_t* text, const uint64_t* offs, uint64_t n_samples, double alpha, double* logz, double* escore,
+                                  double* etokens, uint64_t* n_no_path) {
+    const char* who = "tgx_lattice_stats_host";
+    // alpha and the scores as sample_check (tgx_api.cpp) takes them, with its statuses
+    if (!(alpha >= 0.0) || !std::isfinite(alpha)) return fail(TGX_ERR_INVALID, "alpha must be finite and >= 0 (got %g)", alpha);
+    if (vocab_size && !scores) return fail(TGX_ERR_INVALID, "%s: scores is NULL", who);
+    tgx_status st = check_packed_list(who, "vocabulary offsets", "vocabulary offsets", vocab_offs, vocab_size, false);
+    if (st == TGX_OK) st = check_packed_list(who, "offs", "offsets", offs, n_samples, true);
+    if (st != TGX_OK) return st;
+    for (uint32_t i = 0; i < vocab_size; i++)
+        if (!std::isfinite(scores[i])) return fail(TGX_ERR_UNSUPPORTED, "sampling needs every score to be finite");
+    for (uint32_t i = 0; i < vocab_size; i++)
+        if (!std::isfinite(alpha * scores[i])) return fail(TGX_ERR_INVALID, "alpha * score overflows (alpha %g)", alpha);
+    const uint64_t S = n_samples, N = offs[S];
+    if (N && !text) return fail(TGX_ERR_INVALID, "%s: text is NULL", who);
+    if (vocab_size && vocab_offs[vocab_size] > vocab_offs[0] && !vocab_bytes) return fail(TGX_ERR_INVALID, "%s: vocab_bytes is NULL", who);
+
+    StatsTrie trie;
+    trie.score.assign(1, 0.0);
+    trie.terminal.assign(1, 0);
+    for (uint32_t i = 0; i < vocab_size; i++) {
+        const uint64_t len = vocab_offs[i + 1] - vocab_offs[i];
+        if (len > TGX_MAX_TOKEN_LEN)
+            return fail(TGX_ERR_UNSUPPORTED, "%s: token of %llu bytes exceeds TGX_MAX_TOKEN_LEN (%d)", who, (unsigned long long)len, TGX_MAX_TOKEN_LEN);
+        if (len == 0) continue;  // matches nothing
+        uint32_t node = 0;
+        for (uint64_t k = 0; k < len; k++) {
+            const uint64_t key = ((uint64_t)node << 8) | vocab_bytes[vocab_offs[i] + k];
+            auto it = trie.next.find(key);
+            if (it == trie.next.end()) {
+                it = trie.next.emplace(key, (uint32_t)trie.score.size()).first;
+                trie.score.push_back(0.0);
+                trie.terminal.push_back(0);
+            }
+            node = it->second;
+        }
+        trie.terminal[node] = 1;
+        trie.score[node] = scores[i];
+    }
+
+    // as stats_kernel: A[p] by log_add over the matches ending at p in ascending order of their start, and with every
+    // log_add the normalised expectations m[p], t[p] move towards the new term's by its share exp(x - A')
+    uint64_t bad = 0;
+    std::vector<double> A, M, T;
+    for (uint64_t i = 0; i < S; i++) {
+        const uint64_t beg = offs[i], n = offs[i + 1] - beg;
+        A.assign(n + 1, -HUGE_VAL);
+        M.assign(n + 1, 0.0);
+        T.assign(n + 1, 0.0);
+        A[0] = 0.0;
+        for (uint64_t q = 0; q < n; q++) {
+            if (A[q] == -HUGE_VAL) continue;
+            uint32_t node = 0;
+            for (uint64_t d = 0; d < TGX_MAX_TOKEN_LEN && q + d < n; d++) {
+                const auto it = trie.next.find(((uint64_t)node << 8) | text[beg + q + d]);
+                if (it == trie.next.end()) break;
+                node = it->second;
+                if (!trie.terminal[node]) continue;
+                const uint64_t p = q + d + 1;
+                const double s = trie.score[node];
+                const double x = A[q] + alpha * s;
+                const double nw = stats_log_add_host(A[p], x);
+                const double pi = exp(x - nw);
+                M[p] = M[p] + pi * ((M[q] + s) - M[p]);
+                T[p] = T[p] + pi * ((T[q] + 1.0) - T[p]);
+                A[p] = nw;
+            }
+        }
+        const bool reached = A[n] != -HUGE_VAL;
+        if (!reached) bad++;
+        if (logz) logz[i] = A[n];
+        if (escore) escore[i] = reached ? M[n] : NAN;
+        if (etokens) etokens[i] = reached ? T[n] : NAN;
+    }
+    if (n_no_path) *n_no_path = bad;
     return TGX_OK;
 }

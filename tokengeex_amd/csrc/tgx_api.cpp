@@ -32,6 +32,7 @@
 #include "lean_gate.h"
 #include "nbest.h"
 #include "sample.h"
+#include "stats.h"
 #include "trie_build.h"
 
 using namespace tgx::host;
@@ -3242,6 +3243,121 @@ tgx_status tgx_encode_batch_sample(tgx_model* m, const uint8_t* text, const uint
         if (st != TGX_OK) return st;
     }
     return on_uploaded_batch(m, text, offs, n_samples, [&](tgx_corpus* c) { return tgx_encode_corpus_sample(m, c, alpha, seed, logz, out); });
+}
+
+// ---- lattice statistics (stats.hip) ---------------------------------------------------
+
+// caller holds m->mu and c->mu
+static tgx_status stats_corpus_locked(tgx_model* m, tgx_corpus* c, double alpha, double* logz, double* escore, double* etokens,
+                                      uint64_t* n_no_path) {
+    HIP_TRY(hipSetDevice(m->device));
+    m->n_timed = 0;
+    const uint64_t S = c->n_samples;
+    const uint32_t n_slots = (uint32_t)m->flat.table.size();
+    if (S == 0) {  // nothing to launch, nothing to write
+        if (n_no_path) *n_no_path = 0;
+        return TGX_OK;
+    }
+
+    // the rows kernel: tokens <= 32 bytes, every w = exp(alpha · score) in [2^-300, 2^300] (sampling's rule; nothing is
+    // traced, so the token hash table is not asked for)
+    bool rows = m->lm <= 32;
+    for (double sc : m->vocab_scores)
+        if (!(std::fabs(alpha * sc) <= 207.0)) rows = false;
+    bool forced_rows = false;
+    if (const char* e = knob("TGX_STATS_PATH")) {
+        if (strcmp(e, "generic") == 0) rows = false;
+        if (strcmp(e, "rows") == 0) {
+            if (!rows) return fail(TGX_ERR_UNSUPPORTED, "TGX_STATS_PATH=rows: the rows kernel cannot take this model at alpha %g", alpha);
+            forced_rows = true;
+        }
+    }
+
+    Pass pass(m);
+    double* d_out = nullptr;    // f64[3 S]: logz, escore, etokens; then the range flag
+    double* d_wslot = nullptr;  // f64[n_slots]
+    const size_t ob = (size_t)S * 24 + 16, wb = (size_t)n_slots * 8 + 16;
+    if (pass.alloc(ob, &d_out) != hipSuccess || (rows && pass.alloc(wb, &d_wslot) != hipSuccess))
+        return fail(TGX_ERR_DEVICE, "out of device memory (lattice statistics)");
+    unsigned long long* d_range = reinterpret_cast<unsigned long long*>(d_out + 3 * S);
+    if (hipMemsetAsync(&m->d_ctrl->queue, 0x00, 8, m->stream) != hipSuccess || hipMemsetAsync(d_range, 0x00, 8, m->stream) != hipSuccess)
+        return fail(TGX_ERR_DEVICE, "memset failed");
+
+    const tgx::EncodeParams p = base_encode_params(m, c, 0);
+    tgx::StatsParams q{};
+    q.alpha = alpha;
+    q.logz = d_out;
+    q.escore = d_out + S;
+    q.etokens = d_out + 2 * S;
+    q.wslot = d_wslot;
+    q.range_flag = d_range;
+    if (rows) {
+        time_begin(m, "sample_wslot_kernel");
+        if (tgx::launch_sample_wslot(m->d_trie, n_slots, alpha, d_wslot, m->stream) != hipSuccess)
+            return fail(TGX_ERR_DEVICE, "sample_wslot_kernel launch failed");
+        time_end(m);
+        time_begin(m, "stats_rows_kernel");
+        if (tgx::launch_stats_rows(p, q, (uint32_t)m->num_cus, m->stream) != hipSuccess)
+            return fail(TGX_ERR_DEVICE, "stats_rows_kernel launch failed");
+        time_end(m);
+        unsigned long long range = 0;
+        if (hipMemcpyAsync(&range, d_range, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess || hipStreamSynchronize(m->stream) != hipSuccess)
+            return fail(TGX_ERR_DEVICE, "lattice statistics pass failed: %s", hipGetErrorString(hipGetLastError()));
+        if (range) {  // a value the linear domain cannot hold exactly: the whole call on the log-domain kernel
+            if (forced_rows) return fail(TGX_ERR_UNSUPPORTED, "TGX_STATS_PATH=rows: a value left the range of the rows kernel");
+            rows = false;
+            if (hipMemsetAsync(&m->d_ctrl->queue, 0x00, 8, m->stream) != hipSuccess) return fail(TGX_ERR_DEVICE, "memset failed");
+        }
+    }
+    if (!rows) {
+        time_begin(m, "stats_kernel");
+        if (tgx::launch_stats(p, q, (uint32_t)m->num_cus, m->stream) != hipSuccess) return fail(TGX_ERR_DEVICE, "stats_kernel launch failed");
+        time_end(m);
+    }
+
+    std::vector<double> h_logz;
+    if (n_no_path && !logz && S) {  // the count reads logz
+        h_logz.resize(S);
+        logz = h_logz.data();
+    }
+    if (S && ((logz && hipMemcpyAsync(logz, q.logz, (size_t)S * 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess) ||
+              (escore && hipMemcpyAsync(escore, q.escore, (size_t)S * 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess) ||
+              (etokens && hipMemcpyAsync(etokens, q.etokens, (size_t)S * 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess)))
+        return fail(TGX_ERR_DEVICE, "lattice statistics: copy failed: %s", hipGetErrorString(hipGetLastError()));
+    if (hipStreamSynchronize(m->stream) != hipSuccess)
+        return fail(TGX_ERR_DEVICE, "lattice statistics pass failed: %s", hipGetErrorString(hipGetLastError()));
+    if (n_no_path) {
+        uint64_t bad = 0;
+        for (uint64_t i = 0; i < S; i++) bad += logz[i] == -HUGE_VAL ? 1u : 0u;
+        *n_no_path = bad;
+    }
+    m->last_alg_bytes = c->n_bytes + 24 * S + 8 * (S + 1);
+    return pass.done();
+}
+
+tgx_status tgx_lattice_stats_corpus(tgx_model* m, tgx_corpus* c, double alpha, double* logz, double* escore, double* etokens,
+                                    uint64_t* n_no_path) {
+    if (const tgx_status dst = require_device()) return dst;
+    if (!m || !c) return fail(TGX_ERR_INVALID, "tgx_lattice_stats_corpus: NULL argument");
+    if (m->device != c->device) return fail(TGX_ERR_INVALID, "model and corpus on different devices");
+    std::lock_guard<std::mutex> lk(m->mu);
+    const tgx_status st = sample_check(m, alpha);
+    if (st != TGX_OK) return st;
+    std::lock_guard<std::mutex> lkc(c->mu);
+    return stats_corpus_locked(m, c, alpha, logz, escore, etokens, n_no_path);
+}
+
+tgx_status tgx_lattice_stats_batch(tgx_model* m, const uint8_t* text, const uint64_t* offs, uint64_t n_samples, double alpha, double* logz,
+                                   double* escore, double* etokens, uint64_t* n_no_path) {
+    if (const tgx_status dst = require_device()) return dst;
+    if (!m) return fail(TGX_ERR_INVALID, "tgx_lattice_stats_batch: NULL argument");
+    {
+        std::lock_guard<std::mutex> lk(m->mu);
+        const tgx_status st = sample_check(m, alpha);
+        if (st != TGX_OK) return st;
+    }
+    return on_uploaded_batch(m, text, offs, n_samples,
+                             [&](tgx_corpus* c) { return tgx_lattice_stats_corpus(m, c, alpha, logz, escore, etokens, n_no_path); });
 }
 
 // ---- n-best segmentation (nbest.hip) ------------------------------------------------

@@ -856,6 +856,74 @@ class Tokenizer:
         logz = np.bincount(seg_sample[ss < 0], weights=seg_logz, minlength=n).astype(np.float64) if n else np.zeros(0)
         return out[0], out[1], logz
 
+    # -- lattice statistics: log Z, expected score and expected tokens per sample (csrc/stats.hip) --
+    @staticmethod
+    def _sum_segment_stats(seg: "_lib.LatticeStats | None", seg_offs: np.ndarray, ss: np.ndarray, n_bytes: np.ndarray, alpha: float):
+        """A sample's values are the sums over its non-special segments, added on the host as encode_corpus_sample_result
+        adds logz; every special token is one more expected token.  An unreachable segment (-inf, NaN, NaN) makes its sample
+        no_path through the sums themselves."""
+        n = seg_offs.shape[0] - 1
+        seg_sample = np.repeat(np.arange(n), np.diff(seg_offs.astype(np.int64)))
+        enc = seg_sample[ss < 0]
+        zero = np.zeros(0, np.float64)
+        logz, escore, etokens = (zero, zero, zero) if seg is None else (seg.logz, seg.expected_score, seg.expected_tokens)
+        with np.errstate(invalid="ignore"):
+            return _lib.LatticeStats(np.bincount(enc, weights=logz, minlength=n).astype(np.float64),
+                                     np.bincount(enc, weights=escore, minlength=n).astype(np.float64),
+                                     np.bincount(enc, weights=etokens, minlength=n) + np.bincount(seg_sample[ss >= 0], minlength=n),
+                                     n_bytes, alpha)
+
+    def lattice_stats(self, texts: list[str], alpha: float = 1.0) -> "_lib.LatticeStats":
+        """Per text: log Z, expected score, expected token count (and entropy, bits per byte) of its segmentation
+        distribution under temperature alpha — what encode_batch_sample draws from, without drawing."""
+        text_b, offs_b = _fast.pack_strs(texts)
+        return self.lattice_stats_flat(np.frombuffer(text_b, dtype=np.uint8), np.frombuffer(offs_b, dtype=np.uint64), alpha)
+
+    def lattice_stats_flat(self, flat: np.ndarray, offs: np.ndarray, alpha: float = 1.0) -> "_lib.LatticeStats":
+        """lattice_stats over a packed batch: special-token split and processors as encode_batch_flat; n_bytes counts the
+        samples as given."""
+        if not self._native_front():
+            raise TokenGeeXError("lattice_stats_flat: a processor without a packed-buffer form", _lib.ERR_UNSUPPORTED)
+        flat = np.ascontiguousarray(flat, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        n = offs.shape[0] - 1
+        n_bytes = np.diff(offs)
+        if n <= 0:
+            zero = np.zeros(0, np.float64)
+            return _lib.LatticeStats(zero, zero, zero, np.zeros(0, np.uint64), alpha)
+        model = self._model()
+        if not self._special_tokens:
+            if self._processors:
+                flat, offs = self._preprocess_flat(flat, offs)
+            st = model.lattice_stats_flat(flat, offs, alpha)
+            return _lib.LatticeStats(st.logz, st.expected_score, st.expected_tokens, n_bytes, alpha, st.n_no_path)
+        seg_offs, ss, pflat, poffs = self._split_segments(flat, offs)
+        seg = model.lattice_stats_flat(pflat, poffs, alpha) if poffs.shape[0] > 1 else None
+        return self._sum_segment_stats(seg, seg_offs, ss, n_bytes, alpha)
+
+    def lattice_stats_corpus(self, corpus: "_lib.NativeCorpus", alpha: float = 1.0) -> "_lib.LatticeStats":
+        """lattice_stats_flat over a resident corpus, with the device front end of encode_corpus_result (special-token
+        split, CRLF and, with device_unicode, the Unicode form run in HBM)."""
+        crlf, form = self._corpus_front("lattice_stats_corpus")
+        model = self._model()
+        n_bytes = np.diff(corpus.offsets())
+        if crlf is None and form is None:
+            return model.lattice_stats_corpus(corpus, alpha)
+        if crlf is None:
+            rows = corpus.normalize(form)
+            try:
+                st = model.lattice_stats_corpus(rows, alpha)
+            finally:
+                rows.free()
+            return _lib.LatticeStats(st.logz, st.expected_score, st.expected_tokens, n_bytes, alpha, st.n_no_path)
+        segs_corpus, plan = self._split_corpus(corpus, crlf, form)
+        try:
+            seg = model.lattice_stats_corpus(segs_corpus, alpha) if plan.num_encoded else None
+            return self._sum_segment_stats(seg, plan.seg_offs(), plan.seg_special(), n_bytes, alpha)
+        finally:
+            segs_corpus.free()
+            plan.free()
+
     # -- n-best segmentation: the k highest-scoring segmentations per sample (csrc/nbest.hip) --
     def encode_nbest(self, text: str, nbest: int) -> list[list[int]]:
         return self.encode_batch_nbest([text], nbest)[0]
