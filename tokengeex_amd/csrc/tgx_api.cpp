@@ -1249,37 +1249,10 @@ tgx_status tgx_model_create_derived(const tgx_model* parent, const uint32_t* kee
     for (uint32_t i = 0; i < n_keep; i++) new_id[keep_ids[i]] = i;
     // the new vocabulary's bytes (the tail of creation copies them into the model)
     std::vector<uint8_t> bytes;
-    std::vector<uint64_t> offs(n_keep + 1, 0);
-    uint32_t longest = 0;
-    for (uint32_t i = 0; i < n_keep; i++) {
-        const uint64_t b = parent->vocab_offs[keep_ids[i]], e = parent->vocab_offs[keep_ids[i] + 1];
-        offs[i + 1] = offs[i] + (e - b);
-        longest = std::max<uint32_t>(longest, (uint32_t)(e - b));
-    }
-    bytes.resize(offs[n_keep]);
-    for (uint32_t i = 0; i < n_keep; i++) {
-        const uint64_t b = parent->vocab_offs[keep_ids[i]], e = parent->vocab_offs[keep_ids[i] + 1];
-        if (e > b) memcpy(bytes.data() + offs[i], parent->vocab_bytes.data() + b, (size_t)(e - b));
-    }
+    std::vector<uint64_t> offs;
+    const uint32_t longest = tgx::gather_derived_vocab(parent->vocab_bytes.data(), parent->vocab_offs.data(), keep_ids, n_keep, &bytes, &offs);
     hp.mark("checks + bytes");
-    auto derive = [&](const tgx::FlatTrie& src, tgx::FlatTrie* dst) {
-        *dst = src;
-        dst->max_token_len = longest;
-        for (size_t t = 0; t < dst->tokid.size(); t++) {
-            const uint32_t old = dst->tokid[t];
-            if (old == tgx::kNoToken) continue;
-            const uint32_t nid = new_id[old];
-            tgx::TrieRec& r = dst->table[t];
-            if (nid == tgx::kNoToken) {
-                dst->tokid[t] = tgx::kNoToken;
-                r.base &= ~tgx::kTerminalBit;
-                r.score_bits = 0;
-            } else {
-                dst->tokid[t] = nid;
-                memcpy(&r.score_bits, &scores[nid], 8);
-            }
-        }
-    };
+    auto derive = [&](const tgx::FlatTrie& src, tgx::FlatTrie* dst) { tgx::derive_flat_trie(src, new_id, scores, longest, dst); };
     // (the parent's reversed table is built, if ever, under its lock: ensure_reverse_trie)
     std::unique_lock<std::mutex> parent_lock(const_cast<tgx_model*>(parent)->mu);
     std::thread rev_deriver;

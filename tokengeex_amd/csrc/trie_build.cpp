@@ -600,4 +600,42 @@ uint64_t flat_common_prefix_search(const FlatTrie& t, const uint8_t* s, uint64_t
     return found;
 }
 
+// ---- tables of a subset of the vocabulary (tgx_model_create_derived) ---------------------------------------------------
+uint32_t gather_derived_vocab(const uint8_t* parent_bytes, const uint64_t* parent_offs, const uint32_t* keep_ids, uint32_t n_keep,
+                              std::vector<uint8_t>* bytes, std::vector<uint64_t>* offs) {
+    offs->assign((size_t)n_keep + 1, 0);
+    uint32_t longest = 0;
+    for (uint32_t i = 0; i < n_keep; i++) {
+        const uint64_t b = parent_offs[keep_ids[i]], e = parent_offs[keep_ids[i] + 1];
+        (*offs)[i + 1] = (*offs)[i] + (e - b);
+        longest = std::max<uint32_t>(longest, (uint32_t)(e - b));
+    }
+    bytes->resize((*offs)[n_keep]);
+    for (uint32_t i = 0; i < n_keep; i++) {
+        const uint64_t b = parent_offs[keep_ids[i]], e = parent_offs[keep_ids[i] + 1];
+        if (e > b) std::memcpy(bytes->data() + (*offs)[i], parent_bytes + b, (size_t)(e - b));
+    }
+    return longest;
+}
+
+void derive_flat_trie(const FlatTrie& src, const std::vector<uint32_t>& new_id, const double* scores, uint32_t longest,
+                      FlatTrie* dst) {
+    *dst = src;
+    dst->max_token_len = longest;
+    for (size_t t = 0; t < dst->tokid.size(); t++) {
+        const uint32_t old = dst->tokid[t];
+        if (old == kNoToken) continue;
+        const uint32_t nid = new_id[old];
+        TrieRec& r = dst->table[t];
+        if (nid == kNoToken) {
+            dst->tokid[t] = kNoToken;
+            r.base &= ~kTerminalBit;
+            r.score_bits = 0;
+        } else {
+            dst->tokid[t] = nid;
+            std::memcpy(&r.score_bits, &scores[nid], 8);
+        }
+    }
+}
+
 }  // namespace tgx

@@ -181,9 +181,21 @@ void build_tok_hash(const uint8_t* bytes, const uint64_t* offs, uint32_t vocab_s
 uint64_t flat_common_prefix_search(const FlatTrie& t, const uint8_t* s, uint64_t n, uint32_t* ids,
                                    uint32_t* lens, uint64_t cap);
 
+// The tables of a model for a SUBSET of the vocabulary `src` was built (or derived) for, with new scores
+// (tgx_model_create_derived): a copy of src in which the slot of a token with new_id[old id] == kNoToken loses its terminal
+// bit, its id and its score, and every other terminal slot gets new_id[old id] and scores[new id]; max_token_len becomes
+// `longest` (the longest kept token).  No slot moves and none is freed, so unlike a table of build_flat_trie the result may
+// hold used slots below which no token ends (dead branches, deeper than max_token_len too) and leaves that are not
+// terminal; every walk ends a match on the terminal bit (or tokid / sref / tok of the records built over it), never on
+// the shape.  new_id has one entry per id of src's vocabulary.
+void derive_flat_trie(const FlatTrie& src, const std::vector<uint32_t>& new_id, const double* scores, uint32_t longest,
+                      FlatTrie* dst);
+// The kept tokens' bytes, packed in the order of keep_ids (offs gets n_keep + 1 entries from 0) -> the longest one's length.
+uint32_t gather_derived_vocab(const uint8_t* parent_bytes, const uint64_t* parent_offs, const uint32_t* keep_ids, uint32_t n_keep,
+                              std::vector<uint8_t>* bytes, std::vector<uint64_t>* offs);
+
 }  // namespace tgx
 
-// prune_host.cpp: tgx_prune_alternatives over a table that already exists (a handle's, or a model's own)
 // prune_host.cpp: tgx_prune_alternatives over a table that already exists (a handle's, or a model's own);
 // returns a tgx_status
 extern "C" int tgx_prune_alternatives_flat(const tgx::FlatTrie* flat_trie, const uint8_t* bytes, const uint64_t* offs,
