@@ -42,6 +42,32 @@ def test_fails_loudly_without_gpu():
         VocabularyGenerator(8, 1.0).feed(["abc abc"])
 
 
+def test_pass_entry_points_reject_null_handles_in_order():
+    """The E-step's and the lattice passes' entry points (csrc/estep_pass.cpp, csrc/lattice_pass.cpp) with NULL handles:
+    which check comes first decides the status and the message.  The six lattice entry points ask for a device before
+    they look at their arguments; tgx_estep looks at its arguments first and never asks."""
+    lib = _lib.lib
+    out = ctypes.c_void_p()
+    calls = {
+        "tgx_estep": lambda: lib.tgx_estep(None, None, 0, 0.0, 0, None, None),
+        "tgx_encode_corpus_sample": lambda: lib.tgx_encode_corpus_sample(None, None, 1.0, 0, None, ctypes.byref(out)),
+        "tgx_encode_batch_sample": lambda: lib.tgx_encode_batch_sample(None, None, None, 0, 1.0, 0, None, ctypes.byref(out)),
+        "tgx_lattice_stats_corpus": lambda: lib.tgx_lattice_stats_corpus(None, None, 1.0, None, None, None, None),
+        "tgx_lattice_stats_batch": lambda: lib.tgx_lattice_stats_batch(None, None, None, 0, 1.0, None, None, None, None),
+        "tgx_encode_corpus_nbest": lambda: lib.tgx_encode_corpus_nbest(None, None, 1, None, None, ctypes.byref(out)),
+        "tgx_encode_batch_nbest": lambda: lib.tgx_encode_batch_nbest(None, None, None, 0, 1, None, None, ctypes.byref(out)),
+    }
+    have_gpu = tgx.device_count() > 0
+    for name, call in calls.items():
+        status = call()
+        msg = (lib.tgx_last_error() or b"").decode()
+        if name == "tgx_estep" or have_gpu:
+            assert (status, msg) == (_lib.ERR_INVALID, name + ": NULL argument"), name
+        else:
+            assert (status, msg) == (_lib.ERR_DEVICE, "no usable HIP device (gfx950 required)"), name
+    assert out.value is None
+
+
 def test_packed_vocabulary_container():
     """_lib.Packed: the prune driver's vocabulary between passes — subsets without a Python loop."""
     rng = np.random.default_rng(3)

@@ -640,7 +640,7 @@ def test_estep7_with_more_than_65535_tokens():
 def test_estep7_after_an_m_step_ranks_by_match_counts(monkeypatch):
     """prune's second sub-iteration (src/prune.rs:36-56): the E-step of a DERIVED model with the scores an M-step leaves
     — kept single-byte tokens with tiny scores that still match at every occurrence of their byte.  The ranks that stay in
-    LDS come from match counts over a sample of the corpus (tgx_api.cpp ensure_estep_trie8t); the result must not depend
+    LDS come from match counts over a sample of the corpus (estep_pass.cpp ensure_estep_trie8t); the result must not depend
     on that choice: the same expected counts with the model's own order (TGX_E7_RANK=model), with a small table
     (TGX_E7_HOT) and against the oracle."""
     from tokengeex_amd import _lib
@@ -675,7 +675,7 @@ def test_estep7_after_an_m_step_ranks_by_match_counts(monkeypatch):
 def test_estep7_overflow_build_for_vocabularies_of_a_few_more_than_65535_tokens(monkeypatch):
     """16-bit match entries hold 65 535 ranks; a vocabulary of up to 1 024 more tokens (the usual "64 K": the committed
     65 536-entry spec vocabulary) keeps them and hands the trips in which a token of a rank beyond matches to the redo
-    kernel, which then has 32-bit entries (tgx_api.cpp estep_fused, estep7.hip OVF).  Against the oracle: the spec
+    kernel, which then has 32-bit entries (estep_pass.cpp estep_fused, estep7.hip OVF).  Against the oracle: the spec
     vocabulary as it is, and a small vocabulary whose ranks beyond 1 500 / 40 are treated that way (TGX_E7_OVF_AT), so
     that a large share of the trips takes the path — with dropout, with the model's own rank order and with a tiny table."""
     toks, scores, _ = synth.load_spec_vocab(65536)

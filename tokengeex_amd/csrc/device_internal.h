@@ -1,6 +1,7 @@
-// What the device-side host code shares (tgx_api.cpp: the passes on a model's own streams; result_ops.cpp and
-// corpus_ops.cpp: the calls on a caller's stream): the handle structs, the buffer pool's interface, the guards of a
-// pass and of a call, the stage timer.  api_internal.h stays free of HIP for host_twins.cpp; this header is not.
+// What the device-side host code shares (tgx_api.cpp, estep_pass.cpp and lattice_pass.cpp: the passes on a model's own
+// streams, which share pass_internal.h too; result_ops.cpp and corpus_ops.cpp: the calls on a caller's stream): the
+// handle structs, the buffer pool's interface, the guards of a pass and of a call, the stage timer.  api_internal.h
+// stays free of HIP for host_twins.cpp; this header is not.
 // Everything with state (the pool, the default and copy streams) is DEFINED once, in tgx_api.cpp, and only declared
 // here; the types live in tgx::dev, so that a handle struct is the same type in every translation unit.
 #pragma once

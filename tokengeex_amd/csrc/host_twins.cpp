@@ -1123,7 +1123,7 @@ tgx_status tgx_lattice_stats_host(const uint8_t* vocab_bytes, const uint64_t* vo
                                   const uint8_t* text, const uint64_t* offs, uint64_t n_samples, double alpha, double* logz, double* escore,
                                   double* etokens, uint64_t* n_no_path) {
     const char* who = "tgx_lattice_stats_host";
-    // alpha and the scores as sample_check (tgx_api.cpp) takes them, with its statuses
+    // alpha and the scores as sample_check (lattice_pass.cpp) takes them, with its statuses
     if (!(alpha >= 0.0) || !std::isfinite(alpha)) return fail(TGX_ERR_INVALID, "alpha must be finite and >= 0 (got %g)", alpha);
     if (vocab_size && !scores) return fail(TGX_ERR_INVALID, "%s: scores is NULL", who);
     tgx_status st = check_packed_list(who, "vocabulary offsets", "vocabulary offsets", vocab_offs, vocab_size, false);

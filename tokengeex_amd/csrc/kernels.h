@@ -1,4 +1,4 @@
-// Kernel parameter blocks and launchers shared by kernels.hip and tgx_api.cpp.
+// Kernel parameter blocks and launchers shared by kernels.hip and the passes (tgx_api.cpp, estep_pass.cpp, lattice_pass.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -243,7 +243,7 @@ hipError_t estep7_waves_per_simd(bool dropout, bool cold, bool wide, int ppl, in
 hipError_t launch_estep7(Estep7Params p, bool wide, int ppl, int waves, uint32_t blocks, hipStream_t stream);
 // How often every token MATCHES in a sample of the text (chunks of `chunk` bytes every `stride` bytes): counts[rank] += 1
 // per position of the sample and token that is a prefix of the text there.  The E-step adds to a token's expected count
-// once per match, whatever its score: the ranks that stay in LDS are chosen by these counts (tgx_api.cpp).
+// once per match, whatever its score: the ranks that stay in LDS are chosen by these counts (estep_pass.cpp).
 hipError_t launch_match_count(const uint8_t* text, uint64_t n_bytes, uint32_t chunk, uint64_t stride, const void* trie8t, uint32_t n_slots,
                               uint32_t root_base, uint32_t n_tok, unsigned int* counts, uint32_t num_cus, hipStream_t stream);
 // the same over encode5_kernel's records: counts[rank of the score value] (walks of up to max_len bytes)

@@ -1,4 +1,4 @@
-// N-best segmentation (nbest.hip): parameters and launchers used by tgx_api.cpp.
+// N-best segmentation (nbest.hip): parameters and launchers used by lattice_pass.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

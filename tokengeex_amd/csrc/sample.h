@@ -1,4 +1,4 @@
-// Sampling a segmentation from the lattice (sample.hip): parameters and launchers used by tgx_api.cpp.
+// Sampling a segmentation from the lattice (sample.hip): parameters and launchers used by lattice_pass.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

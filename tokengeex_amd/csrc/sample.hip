@@ -25,7 +25,7 @@
 
 namespace tgx {
 
-// same function as tgx_sample_u01 (tgx_api.cpp): tgx_dropout_u01's rounds over its own start value, and a result in (0, 1)
+// same function as tgx_sample_u01 (lattice_pass.cpp): tgx_dropout_u01's rounds over its own start value, and a result in (0, 1)
 __device__ __forceinline__ double sample_u01(uint64_t seed, uint64_t sample, uint64_t pos, uint32_t len) {
     uint64_t x = seed ^ 0xD6E8FEB86659FD93ULL ^ (sample * 0x9E3779B97F4A7C15ULL) ^ (pos * 0xC2B2AE3D27D4EB4FULL) ^
                  ((uint64_t)len * 0x165667B19E3779F9ULL);

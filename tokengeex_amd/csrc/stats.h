@@ -1,4 +1,4 @@
-// Per-sample lattice statistics (stats.hip): parameters and launchers used by tgx_api.cpp.
+// Per-sample lattice statistics (stats.hip): parameters and launchers used by lattice_pass.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
