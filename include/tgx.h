@@ -445,6 +445,77 @@ tgx_status tgx_fim_host(const uint32_t *ids, const uint64_t *offs, uint64_t n_ro
 tgx_status tgx_result_from_ids(int device, const uint32_t *ids, const uint64_t *offs, uint64_t n_rows,
                                uint32_t vocab_size, tgx_result **out);
 
+/* ---- rows selected and reordered on the device: of a result or of a corpus (csrc/select.hip) ------------------------
+ * A resident result or corpus is otherwise consumed whole and in the order it was produced.  A new document order per
+ * epoch, dropping rows (length or quality filters) and taking some rows (a mini-batch, a split, length-grouped batches)
+ * are one primitive: a new result (or corpus) whose row k is row rows[k] of the old one — any order, any subset,
+ * repeats allowed.  The indices come from anywhere (torch's argsort, nonzero or masks on the device; the seeded
+ * permutation below); moving the ragged rows through them happens in HBM.
+ *
+ * tgx_result_select(r, rows, M, flags, stream, &out).  In: a result r with S rows, T ids and offsets o[0..S], row i with
+ * n_i = o[i+1] - o[i] ids; rows, int64_t[M]; flags; stream.
+ *   Out: a new result with M rows, on r's device and with r's vocabulary size:
+ *     out_offs[k] = the sum of n_{rows[k']} over k' < k,  T' = out_offs[M],
+ *     out_ids[out_offs[k] + t] = ids[o[rows[k]] + t]  for t < n_{rows[k]}.
+ *   r is only read and stays valid; the caller frees both.  Every entry point that takes a result takes the new one.  An
+ *   n-best result is accepted: its rows are rows (selecting by sample while keeping the nbest grouping is the caller's:
+ *   select the sample's rows).  M = 0 gives an empty result with offsets [0], also when S = 0; rows may then be NULL.
+ *   rows is host memory and is uploaded by the call; with TGX_SELECT_ROWS_DEVICE it is device memory on r's device, read
+ *   in stream order.  That is checked with hipPointerGetAttributes before anything is queued, as the layouts check their
+ *   destinations: the flag with a pointer that is not device memory there gives TGX_ERR_INVALID.
+ *   Every index must satisfy 0 <= rows[k] < S.  Otherwise the call returns TGX_ERR_INVALID with *out = NULL, and
+ *   tgx_last_error names the smallest offending k and its value.  Host rows are checked on the host before any device
+ *   call.  Device rows are checked by the device: an index out of range contributes length 0, and the smallest such k
+ *   comes back in a word read together with T' — before the id buffer is sized, so a bad index never becomes an address.
+ *   TGX_ERR_INVALID also for r, out or (with M > 0) rows NULL and for unknown flags.
+ *   stream: the stream rule of the layouts above — the work is queued on it (NULL: the library's blocking stream), the
+ *   call returns after the stream has reached its end, and the calling thread's current device is the same after the
+ *   call as before.  One host visit in between: T' and the bad-index word.
+ *   Token spans of a selected result keep their meaning only against the equally selected corpus or text.
+ *
+ * tgx_result_lengths_device(r, stream, d_lengths) writes n_i for i < S as int64 into caller-owned device memory on r's
+ * device (checked as the layouts' destinations; S = 0 writes nothing): what a caller filters and sorts on without a host
+ * trip.
+ *
+ * tgx_corpus_select(c, rows, M, flags, stream, &out): the same mapping over the corpus's text bytes and byte offsets.
+ * The output is a corpus like any other: every pass accepts it (encode, sampling, n-best, stats, the E-step, the counts,
+ * tgx_corpus_split_specials, tgx_corpus_normalize).  Index checks, flag, stream rule and M = 0 as above; with device rows
+ * the M + 1 new offsets visit the host too (a corpus keeps them there).  The limits of tgx_corpus_upload apply:
+ * M >= 2^32 - 1 gives TGX_ERR_UNSUPPORTED.  c is only read; the call holds the corpus's lock, as
+ * tgx_corpus_split_specials does.
+ *
+ * The seeded permutation: the same on every machine, on the host and for a caller without torch.
+ *   tgx_shuffle_key(seed, g): x = seed ^ TGX_SHUFFLE_SALT ^ g·0x9E3779B97F4A7C15 (wrapping at 2^64), then the three
+ *   xor-shift / multiply rounds of tgx_fim_u01; all 64 bits are the key.
+ *   The permutation of n rows is 0 .. n-1 sorted ascending by (key, index).
+ *   tgx_shuffled_rows_device(device, n, seed, stream, d_rows) writes it as int64[n] into caller-owned device memory on
+ *   `device` (checked as above): a key kernel, then a stable radix sort of the keys with the indices as values.  Stream
+ *   rule as above.  tgx_shuffled_rows_host(n, seed, rows) is the host twin.  n = 0 writes nothing; n >= 2^31 gives
+ *   TGX_ERR_UNSUPPORTED.
+ *
+ * Host twins, no device: tgx_select_host over ids u32[T] (may be NULL when T = 0) and offs u64[n_rows + 1], and
+ * tgx_select_text_host over text bytes u8[N] — the same checks, plus offs[0] = 0 and ascending offsets and cap >= T'
+ * (nothing is written otherwise); they walk the kernels' tiles and thread slots through the same index arithmetic
+ * (csrc/select.h).  out_offs u64[n_select + 1]; out may be NULL when T' = 0.
+ *
+ * tgx_select_last_times: device time of the calling thread's last tgx_result_select or tgx_corpus_select per stage (the
+ * check of device rows, the offsets' scan, the fill), as tgx_fim_last_times; for tools/select_bench.py. */
+#define TGX_SELECT_ROWS_DEVICE 1u
+#define TGX_SHUFFLE_SALT 0xD6E8FEB86659FD93ULL
+int tgx_select_last_times(const char **names, float *ms, int cap);
+tgx_status tgx_result_select(const tgx_result *r, const int64_t *rows, uint64_t n_select, uint32_t flags, void *stream,
+                             tgx_result **out);
+tgx_status tgx_result_lengths_device(const tgx_result *r, void *stream, int64_t *d_lengths);
+tgx_status tgx_corpus_select(tgx_corpus *c, const int64_t *rows, uint64_t n_select, uint32_t flags, void *stream,
+                             tgx_corpus **out);
+uint64_t tgx_shuffle_key(uint64_t seed, uint64_t g);
+tgx_status tgx_shuffled_rows_device(int device, uint64_t n, uint64_t seed, void *stream, int64_t *d_rows);
+tgx_status tgx_shuffled_rows_host(uint64_t n, uint64_t seed, int64_t *rows);
+tgx_status tgx_select_host(const uint32_t *ids, const uint64_t *offs, uint64_t n_rows, const int64_t *rows,
+                           uint64_t n_select, uint32_t *out_ids, uint64_t ids_cap, uint64_t *out_offs);
+tgx_status tgx_select_text_host(const uint8_t *text, const uint64_t *offs, uint64_t n_rows, const int64_t *rows,
+                                uint64_t n_select, uint8_t *out_text, uint64_t text_cap, uint64_t *out_offs);
+
 /* ---- the front end on the device: a resident corpus split at special tokens, CRLF applied (csrc/front.hip) --------
  * What tgx_split_specials and tgx_pack_segments compute on host threads, for a corpus that is already in HBM (an upload,
  * or tgx_corpus_from_text of a decoded text), with the plan kept on the device for tgx_assemble_result_plan: a resident

@@ -24,6 +24,7 @@ NO_ID = 0xFFFFFFFF  # TGX_NO_ID: no bos / eos
 LAYOUT_PAD_LEFT, LAYOUT_TRUNC_LEFT, LAYOUT_I64 = 1, 2, 4  # TGX_LAYOUT_*
 FRONT_CRLF = 1  # TGX_FRONT_CRLF
 SPAN_CHARS = 8  # TGX_SPAN_CHARS
+SELECT_ROWS_DEVICE = 1  # TGX_SELECT_ROWS_DEVICE
 
 # every exported symbol of include/tgx.h: name -> (restype, argtypes)
 _vp, _u64, _u32, _i, _d = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_double
@@ -164,6 +165,15 @@ SYMBOLS = {
     "tgx_fim_host": (_i, [_vp, _vp, _u64, _u32, _u32, _u32, _u32, _d, _d, _u64, _u64, _vp, _u64, _vp, _vp, _vp, _pu64]),
     "tgx_result_from_ids": (_i, [_i, _vp, _vp, _u64, _u32, _pvp]),
     "tgx_fim_last_times": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_float), _i]),
+    "tgx_select_last_times": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_float), _i]),
+    "tgx_result_select": (_i, [_vp, _vp, _u64, _u32, _vp, _pvp]),
+    "tgx_result_lengths_device": (_i, [_vp, _vp, _vp]),
+    "tgx_corpus_select": (_i, [_vp, _vp, _u64, _u32, _vp, _pvp]),
+    "tgx_shuffle_key": (_u64, [_u64, _u64]),
+    "tgx_shuffled_rows_device": (_i, [_i, _u64, _u64, _vp, _vp]),
+    "tgx_shuffled_rows_host": (_i, [_u64, _u64, _vp]),
+    "tgx_select_host": (_i, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp]),
+    "tgx_select_text_host": (_i, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp]),
 }
 
 
@@ -438,6 +448,111 @@ def fim_last_times() -> dict[str, float]:
     names = (C.c_char_p * 8)()
     ms = (C.c_float * 8)()
     n = lib.tgx_fim_last_times(names, ms, 8)
+    return {names[i].decode(): float(ms[i]) for i in range(n)}
+
+
+def _is_device_tensor(rows) -> bool:
+    """A CUDA torch tensor, recognised without importing torch."""
+    return bool(getattr(rows, "is_cuda", False)) and hasattr(rows, "data_ptr")
+
+
+def _host_rows(rows, n_src: int) -> np.ndarray:
+    """Indices given as a list, any numpy integer array, or a boolean mask of length n_src (numpy, or a torch tensor on
+    the host) -> contiguous int64 indices."""
+    if hasattr(rows, "detach") and hasattr(rows, "numpy"):   # a torch tensor on the host
+        rows = rows.detach().numpy()
+    a = np.asarray(rows)
+    if a.dtype == np.bool_:
+        if a.ndim != 1 or a.shape[0] != n_src:
+            raise ValueError(f"a boolean mask must have one entry per row ({n_src}), got shape {a.shape}")
+        return np.flatnonzero(a).astype(np.int64)
+    if a.size == 0:
+        return np.zeros(0, np.int64)
+    if a.ndim != 1 or not np.issubdtype(a.dtype, np.integer):
+        raise TypeError(f"rows must be a one-dimensional array of integers or a boolean mask (got {a.dtype}, {a.ndim} dimensions)")
+    if a.dtype == np.uint64 and a.size and int(a.max()) > 2**63 - 1:
+        raise ValueError("an index does not fit int64")
+    return np.ascontiguousarray(a, dtype=np.int64)
+
+
+def _select_args(rows, n_src: int, device: int, stream: int):
+    """-> (pointer or None, M, flags, stream, what keeps the pointer alive) for tgx_result_select / tgx_corpus_select"""
+    if _is_device_tensor(rows):
+        index = getattr(rows.device, "index", None)
+        if index is not None and index != device:
+            raise ValueError(f"rows is on {rows.device}, the source on device {device}")
+        if "bool" in str(rows.dtype):
+            if rows.dim() != 1 or rows.shape[0] != n_src:
+                raise ValueError(f"a boolean mask must have one entry per row ({n_src}), got shape {tuple(rows.shape)}")
+            rows = rows.nonzero().reshape(-1)
+        if rows.dim() != 1:
+            raise TypeError("rows must be one-dimensional")
+        if "int64" not in str(rows.dtype):
+            if "int" not in str(rows.dtype):
+                raise TypeError(f"rows must hold integers or be a boolean mask (got {rows.dtype})")
+            rows = rows.long()
+        rows = rows.contiguous()
+        if not stream:
+            import sys
+            stream = sys.modules["torch"].cuda.current_stream(rows.device).cuda_stream   # (the tensor's module is loaded)
+        m = int(rows.shape[0])
+        return (rows.data_ptr() or None) if m else None, m, SELECT_ROWS_DEVICE, stream, rows
+    a = _host_rows(rows, n_src)
+    return ptr(a) if a.size else None, int(a.size), 0, stream, a
+
+
+def select_host(ids: np.ndarray, offs: np.ndarray, rows, cap: int | None = None):
+    """Host twin of NativeResult.select (tgx_select_host: the kernel's index arithmetic, no device) over ids u32[T] and
+    offsets u64[S+1] -> (ids u32[T'], offsets u64[M+1]).  cap: room at the destination (default: what is needed)."""
+    return _select_twin(lib.tgx_select_host, np.uint32, ids, offs, rows, cap)
+
+
+def select_text_host(flat: np.ndarray, offs: np.ndarray, rows, cap: int | None = None):
+    """Host twin of NativeCorpus.select (tgx_select_text_host) over text bytes u8[N] and offsets u64[S+1] -> (bytes,
+    offsets u64[M+1])."""
+    return _select_twin(lib.tgx_select_text_host, np.uint8, flat, offs, rows, cap)
+
+
+def _select_twin(fn, dtype, data, offs, rows, cap):
+    data = np.ascontiguousarray(data, dtype=dtype)
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    n = max(offs.shape[0] - 1, 0)
+    rows = _host_rows(rows, n)
+    if cap is None:   # what is needed, for indices in range (the twin refuses the others before it writes)
+        ok = rows[(rows >= 0) & (rows < n)]
+        cap = int((offs[1:][ok].astype(np.int64) - offs[:-1][ok].astype(np.int64)).sum()) if ok.size else 0
+    out = np.empty(max(1, int(cap)), dtype)
+    out_offs = np.zeros(rows.size + 1, np.uint64)
+    check(fn(ptr(data) if data.size else None, ptr(offs) if offs.size else None, n, ptr(rows) if rows.size else None, rows.size, ptr(out), int(cap),
+             ptr(out_offs)))
+    return out[: int(out_offs[-1])], out_offs
+
+
+def shuffle_key(seed: int, g: int) -> int:
+    """The key of row g under `seed` in the seeded permutation (tgx_shuffle_key), a 64-bit integer."""
+    m = 2**64 - 1
+    return lib.tgx_shuffle_key(int(seed) & m, int(g) & m)
+
+
+def shuffled_rows_host(n: int, seed: int) -> np.ndarray:
+    """The seeded permutation of 0 .. n-1 as int64[n] (tgx_shuffled_rows_host): the rows sorted by (shuffle_key, index)."""
+    rows = np.empty(int(n), np.int64)
+    check(lib.tgx_shuffled_rows_host(int(n), int(seed) & (2**64 - 1), ptr(rows) if n else None))
+    return rows
+
+
+def shuffled_rows_device(device: int, n: int, seed: int, rows_ptr: int, stream: int = 0) -> None:
+    """The same permutation written by the device into caller-owned device memory (int64[n], a raw integer pointer;
+    tgx_shuffled_rows_device), queued on `stream` as in NativeResult.pad_device."""
+    check(lib.tgx_shuffled_rows_device(int(device), int(n), int(seed) & (2**64 - 1), stream or None, rows_ptr or None))
+
+
+def select_last_times() -> dict[str, float]:
+    """Device time in ms of each stage of the calling thread's last NativeResult.select or NativeCorpus.select
+    (tgx_select_last_times)."""
+    names = (C.c_char_p * 8)()
+    ms = (C.c_float * 8)()
+    n = lib.tgx_select_last_times(names, ms, 8)
     return {names[i].decode(): float(ms[i]) for i in range(n)}
 
 
@@ -972,6 +1087,24 @@ class NativeResult:
         res = NativeResult(h)
         return (res, mode, cuts) if return_info else res
 
+    # -- rows selected and reordered (include/tgx.h: tgx_result_select; csrc/select.hip) --
+    def select(self, rows, *, stream: int = 0) -> "NativeResult":
+        """A new result whose row k is row rows[k] of this one (any order, any subset, repeats allowed), moved on the
+        device; this result is only read.  rows: a list or numpy integer array (uploaded), a boolean mask of length
+        num_samples (its nonzero indices), or a CUDA torch tensor on the result's device (read in place, in the order of
+        torch.cuda.current_stream unless a stream is given).  An index outside [0, num_samples) raises ERR_INVALID
+        naming the first such k."""
+        p, m, flags, stream, keep = _select_args(rows, self.num_samples, self.device, stream)
+        h = C.c_void_p()
+        check(lib.tgx_result_select(self._h, p, m, flags, stream or None, C.byref(h)))
+        del keep
+        return NativeResult(h)
+
+    def lengths_device(self, ptr_: int, stream: int = 0) -> None:
+        """The rows' lengths as int64[num_samples] written by the device into caller-owned device memory (a raw integer
+        pointer; tgx_result_lengths_device), queued on `stream` as in pad_device."""
+        check(lib.tgx_result_lengths_device(self._h, stream or None, ptr_ or None))
+
     def pad_host(self, row_len: int, pad_id: int, **kw) -> dict:
         """layout_pad_host over the ids and offsets copied to the host."""
         return layout_pad_host(self.ids(), self.offsets(), row_len, pad_id, **kw)
@@ -1139,6 +1272,18 @@ class NativeCorpus:
         c._h = hc
         c.device = self.device
         return c, NativePlan(hp)
+
+    def select(self, rows, *, stream: int = 0) -> "NativeCorpus":
+        """A new resident corpus whose sample k is sample rows[k] of this one, moved on the device (tgx_corpus_select);
+        rows as in NativeResult.select.  With the same rows, corpus and result stay aligned.  This corpus is only read."""
+        p, m, flags, stream, keep = _select_args(rows, self.num_samples, self.device, stream)
+        hc = C.c_void_p()
+        check(lib.tgx_corpus_select(self._h, p, m, flags, stream or None, C.byref(hc)))
+        del keep
+        c = NativeCorpus.__new__(NativeCorpus)
+        c._h = hc
+        c.device = self.device
+        return c
 
     def normalize(self, form: str) -> "NativeCorpus":
         """The corpus under a Unicode normalisation form ("nfd", "nfc", "nfkd", "nfkc") on the device (tgx_corpus_normalize,

@@ -59,6 +59,10 @@ tgx_status assemble_check(const char* who, const uint64_t* seg_offs, const int32
 // vocabulary size for an input of vocab_size
 tgx_status fim_check(const char* who, uint32_t prefix_id, uint32_t suffix_id, uint32_t middle_id, double rate, double spm_rate);
 uint32_t fim_vocab_size(uint32_t vocab_size, uint32_t prefix_id, uint32_t suffix_id, uint32_t middle_id);
+// row selection: TGX_ERR_INVALID naming output row k and its index `value`, which is not a row of n_src; every index of
+// host rows against n_src (the smallest offending k is named)
+tgx_status select_index_error(const char* who, uint64_t k, int64_t value, uint64_t n_src);
+tgx_status select_check_rows(const char* who, const int64_t* rows, uint64_t n_select, uint64_t n_src);
 // ids and offsets in host memory as a result's: layout_check_host, vocab_size <= 0xFFFFFFFE and every id below it
 tgx_status result_check_host(const char* who, const uint32_t* ids, const uint64_t* offs, uint64_t n_rows, uint32_t vocab_size);
 tgx_status decode_build_tables(const char* who, const uint8_t* bytes, const uint64_t* offs, uint32_t V, std::vector<uint8_t>* len,

@@ -1,5 +1,5 @@
 // The C ABI's transforms of a resident corpus (include/tgx.h): its read-backs, a corpus from decoded text, the front end
-// (special-token split and CRLF), Unicode normalisation, and the split plan's handle.  They run on a stream of their own
+// (special-token split and CRLF), Unicode normalisation, row selection, and the split plan's handle.  They run on a stream of their own
 // under a StreamGuard and share device_internal.h with the passes of tgx_api.cpp.
 #include <hip/hip_runtime.h>
 
@@ -14,7 +14,9 @@
 #include "api_internal.h"
 #include "device_internal.h"
 #include "front.h"
+#include "kernels.h"
 #include "norm.h"
+#include "select.h"
 
 using namespace tgx::host;
 using namespace tgx::dev;
@@ -364,6 +366,78 @@ tgx_status tgx_corpus_normalize(tgx_corpus* c, uint32_t form, tgx_corpus** out, 
     timer.read();
     *out = made_owner.release();
     *n_pieces = P;
+    return TGX_OK;
+}
+
+// ---- row selection: samples of a corpus through an index (select.hip; select.h; result_ops.cpp has the shared steps) ----
+
+tgx_status tgx_corpus_select(tgx_corpus* c, const int64_t* rows, uint64_t n_select, uint32_t flags, void* stream, tgx_corpus** out) {
+    const char* who = "tgx_corpus_select";
+    if (!c || !out) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
+    *out = nullptr;
+    if (n_select && !rows) return fail(TGX_ERR_INVALID, "%s: rows is NULL", who);
+    tgx_status st = layout_check_flags(who, flags, TGX_SELECT_ROWS_DEVICE);
+    if (st != TGX_OK) return st;
+    const uint64_t M = n_select;
+    if (M >= 0xFFFFFFFFull) return fail(TGX_ERR_UNSUPPORTED, "%s: more than 2^32-1 samples", who);
+    const bool on_device = (flags & TGX_SELECT_ROWS_DEVICE) != 0;
+    std::lock_guard<std::mutex> lkc(c->mu);
+    const uint64_t S = c->n_samples;
+    std::vector<uint64_t> h_out_offs(M + 1, 0);
+    if (!on_device) {  // before any device call: the check, and the new offsets from the corpus's host copy
+        if ((st = select_check_rows(who, rows, M, S)) != TGX_OK) return st;
+        for (uint64_t k = 0; k < M; k++) h_out_offs[k + 1] = h_out_offs[k] + tgx::select_out_len(c->h_offs.data(), S, rows, k);
+    }
+    if ((st = require_device()) != TGX_OK) return st;
+    DeviceScope scope;
+    const int dev = c->device;
+    HIP_TRY(hipSetDevice(dev));
+    hipStream_t hs = stream_or_default(stream, dev);
+    std::unique_ptr<tgx_corpus> made_owner;  // the new corpus
+    unsigned long long h_bad = tgx::kSelectNoBad;
+    StageTimer<kSelectStages> timer(hs, select_stage_ms());  // (before the guard: its events outlive the stream's work)
+    StreamGuard guard(dev, hs);  // destroyed before them: a failed call's queued work is over before they go
+    tgx::SelectParams p = {};
+    if ((st = select_rows_device(who, rows, M, flags, dev, guard, &p.rows)) != TGX_OK) return st;
+    p.data = c->d_text;
+    p.offs = c->d_offs;
+    p.n_src = S;
+    p.n_rows = M;
+    if (on_device && M) {  // the device's check and scan; the M + 1 offsets visit the host, which corpus_create needs anyway
+        size_t scan_bytes = 0;
+        if (tgx::select_scan_temp_bytes(M, &scan_bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan temp-size query failed");
+        void* d_scan = nullptr;
+        unsigned long long* d_bad = nullptr;
+        HIP_TRY(guard.alloc(scan_bytes, &d_scan));  // (never NULL: that asks the scan for its size)
+        HIP_TRY(guard.alloc(sizeof(unsigned long long), &d_bad));
+        HIP_TRY(guard.alloc((size_t)(M + 1) * 8, &p.out_offs));
+        HIP_TRY(hipMemsetAsync(d_bad, 0xFF, sizeof(unsigned long long), hs));
+        timer.begin(0);
+        if (tgx::launch_select_check(p, d_bad, hs) != hipSuccess) return fail(TGX_ERR_DEVICE, "select_check_kernel launch failed");
+        timer.end(0);
+        timer.begin(1);
+        if (tgx::launch_select_offsets(p, d_scan, scan_bytes, hs) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan launch failed");
+        timer.end(1);
+        HIP_TRY(hipMemcpyAsync(&h_bad, d_bad, sizeof(unsigned long long), hipMemcpyDeviceToHost, hs));
+        if ((st = read_u64(hs, p.out_offs, h_out_offs.data(), (size_t)(M + 1))) != TGX_OK) return st;
+        if ((st = select_bad_index(who, h_bad, p.rows, S, hs)) != TGX_OK) {
+            guard.done();  // (the stream has reached its end)
+            return st;
+        }
+    }
+    tgx_corpus* made = nullptr;
+    if ((st = corpus_create(who, dev, nullptr, TextFrom::Caller, M ? h_out_offs.data() : nullptr, M, &made)) != TGX_OK) return st;
+    made_owner.reset(made);
+    p.out_offs = made->d_offs;  // (the same offsets, now the new corpus's own)
+    p.n_out = made->n_bytes;
+    p.out = made->d_text;
+    timer.begin(2);
+    if (tgx::launch_select_fill_text(p, hs) != hipSuccess) return fail(TGX_ERR_DEVICE, "select_fill_kernel launch failed");
+    timer.end(2);
+    HIP_TRY(hipStreamSynchronize(hs));
+    guard.done();
+    timer.read();
+    *out = made_owner.release();
     return TGX_OK;
 }
 

@@ -418,6 +418,20 @@ struct ScanScratch {
 };
 tgx_status scan_room(ScanScratch* s, StreamGuard& guard, hipError_t (*temp_bytes)(uint64_t, size_t*), uint64_t n);
 
+// ---- row selection (result_ops.cpp; tgx_corpus_select in corpus_ops.cpp shares it) ------------------------------------
+// device time of the calling thread's last select per stage (tgx_select_last_times)
+constexpr int kSelectStages = 3;
+float* select_stage_ms();
+// The indices of a select on the device.  Host rows (no TGX_SELECT_ROWS_DEVICE; the caller has checked every index with
+// select_check_rows before its first device call) are uploaded on the guard's stream into pooled memory of the guard.
+// Device rows: the pointer is checked (the current device is `device`), nothing is queued.  *d_rows: what the kernels
+// read (NULL when M = 0).
+tgx_status select_rows_device(const char* who, const int64_t* rows, uint64_t n_select, uint32_t flags, int device, StreamGuard& guard,
+                              const int64_t** d_rows);
+// The bad-index word of device rows: what select_check_kernel left (kSelectNoBad: every index in range) -> TGX_OK, or
+// TGX_ERR_INVALID naming k and rows[k], which is read from the device for the message.
+tgx_status select_bad_index(const char* who, uint64_t bad_k, const int64_t* d_rows, uint64_t n_src, hipStream_t hs);
+
 // ---- corpora (tgx_api.cpp) ----------------------------------------------------------
 // a copy on the device's copy stream of that direction, and the stream's end
 hipError_t copy_sync(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, int device);

@@ -1,8 +1,8 @@
 // The *_host twins of the result-side device entry points (include/tgx.h): tgx_layout_pad_host, tgx_layout_pack_host,
-// tgx_layout_windows_host, tgx_assemble_host, tgx_fim_host, tgx_decode_rows_host, tgx_spans_host, tgx_window_spans_host, tgx_front_host,
+// tgx_layout_windows_host, tgx_assemble_host, tgx_fim_host, tgx_select_host, tgx_select_text_host, tgx_shuffled_rows_host, tgx_decode_rows_host, tgx_spans_host, tgx_window_spans_host, tgx_front_host,
 // tgx_normalize_host and tgx_lattice_stats_host, and the
 // argument checks they share with the device entry points of tgx_api.cpp.  A twin goes through the same index arithmetic as its kernels (layout.h, assemble.h,
-// fim.h, decode.h, spans.h, front.h, norm.h) on host memory.  Nothing in this file calls a HIP function, so it builds and runs without the
+// fim.h, select.h, decode.h, spans.h, front.h, norm.h) on host memory.  Nothing in this file calls a HIP function, so it builds and runs without the
 // handles, the pool or a device.
 #include <algorithm>
 #include <cmath>
@@ -18,6 +18,7 @@
 #include "front.h"
 #include "layout.h"
 #include "norm.h"
+#include "select.h"
 #include "spans.h"
 #include "unicode_tables.h"
 
@@ -494,6 +495,99 @@ tgx_status tgx_fim_host(const uint32_t* ids, const uint64_t* offs, uint64_t n_ro
         }
     }
     if (n_applied) *n_applied = (n_out - offs[n_rows]) / 3;
+    return TGX_OK;
+}
+
+// ---- row selection and the seeded permutation -----------------------------------------
+
+namespace tgx::host {
+
+tgx_status select_index_error(const char* who, uint64_t k, int64_t value, uint64_t n_src) {
+    return fail(TGX_ERR_INVALID, "%s: rows[%llu] = %lld is not a row of %llu", who, (unsigned long long)k, (long long)value, (unsigned long long)n_src);
+}
+
+tgx_status select_check_rows(const char* who, const int64_t* rows, uint64_t n_select, uint64_t n_src) {
+    if (n_select && !rows) return fail(TGX_ERR_INVALID, "%s: rows is NULL", who);
+    for (uint64_t k = 0; k < n_select; k++)
+        if (!tgx::select_in_range(rows[k], n_src)) return select_index_error(who, k, rows[k], n_src);
+    return TGX_OK;
+}
+
+}  // namespace tgx::host
+
+namespace {
+
+// What the two select twins share.  T = uint32_t: as select_fill_kernel<uint32_t>.  T = uint8_t: as
+// select_fill_kernel<uint8_t>, whose slots inside one source row go through the aligned dwords' shift; the twin takes
+// those dwords byte by byte (zero outside the text, where the device reads its allocation's zeroed slack), with the
+// source index in the place of the address.
+template <class T>
+tgx_status select_host(const char* who, const char* what, const T* data, const uint64_t* offs, uint64_t n_rows, const int64_t* rows, uint64_t M, T* out,
+                       uint64_t cap, uint64_t* out_offs) {
+    constexpr bool kText = sizeof(T) == 1;
+    constexpr uint32_t kGroup = kText ? tgx::kSelectByteGroup : tgx::kSelectGroup;
+    constexpr uint64_t kTile = kText ? tgx::kSelectByteTile : tgx::kSelectTile;
+    if (!out_offs) return fail(TGX_ERR_INVALID, "%s: out_offs is NULL", who);
+    tgx_status st = check_packed_list(who, "offs", "offsets", offs, n_rows, true);
+    if (st != TGX_OK) return st;
+    const uint64_t n_data = offs[n_rows];
+    if (n_data && !data) return fail(TGX_ERR_INVALID, "%s: %s is NULL", who, what);
+    if ((st = select_check_rows(who, rows, M, n_rows)) != TGX_OK) return st;
+    uint64_t n_out = 0;
+    for (uint64_t k = 0; k < M; k++) n_out += tgx::select_out_len(offs, n_rows, rows, k);
+    if (cap < n_out) return fail(TGX_ERR_INVALID, "%s: %llu elements, room for %llu", who, (unsigned long long)n_out, (unsigned long long)cap);
+    if (n_out && !out) return fail(TGX_ERR_INVALID, "%s: the destination is NULL", who);
+    out_offs[0] = 0;
+    for (uint64_t k = 0; k < M; k++) out_offs[k + 1] = out_offs[k] + tgx::select_out_len(offs, n_rows, rows, k);
+    for (uint64_t t0 = 0; t0 < n_out; t0 += kTile) {
+        const uint64_t last = tgx::select_tile_last(t0, kTile, n_out);
+        const uint64_t lo = tgx::pack_find_row(out_offs, 0, 0, M - 1, t0), hi = tgx::pack_find_row(out_offs, 0, 0, M - 1, last);
+        for (uint64_t e0 = t0; e0 <= last; e0 += kGroup) {
+            const uint32_t n_in = last + 1 - e0 < kGroup ? (uint32_t)(last + 1 - e0) : kGroup;
+            T v[kGroup] = {};
+            tgx::SelectCursor cur;
+            tgx::select_enter(cur, offs, rows, out_offs, lo, hi, e0);
+            if (kText && tgx::select_slot_inside(cur, e0, n_in)) {
+                const uint64_t s = tgx::select_slot_source(cur, e0), base = s & ~3ull;
+                uint32_t d[5] = {0, 0, 0, 0, 0}, w[4];
+                for (uint32_t b = 0; b < 20; b++)
+                    if (base + b < n_data) d[b / 4] |= (uint32_t)data[base + b] << (8 * (b % 4));
+                tgx::select_shift16(d, (uint32_t)(s & 3u), w);
+                for (uint32_t q = 0; q < kGroup; q++) v[q] = (T)(w[q / 4] >> (8 * (q % 4)));
+            } else {
+                tgx::select_walk<kGroup, T>(cur, data, offs, rows, out_offs, lo, hi, e0, n_in, v);
+            }
+            for (uint32_t q = 0; q < n_in; q++) out[e0 + q] = v[q];
+        }
+    }
+    return TGX_OK;
+}
+
+}  // namespace
+
+tgx_status tgx_select_host(const uint32_t* ids, const uint64_t* offs, uint64_t n_rows, const int64_t* rows, uint64_t n_select, uint32_t* out_ids,
+                           uint64_t ids_cap, uint64_t* out_offs) {
+    return select_host<uint32_t>("tgx_select_host", "ids", ids, offs, n_rows, rows, n_select, out_ids, ids_cap, out_offs);
+}
+
+tgx_status tgx_select_text_host(const uint8_t* text, const uint64_t* offs, uint64_t n_rows, const int64_t* rows, uint64_t n_select, uint8_t* out_text,
+                                uint64_t text_cap, uint64_t* out_offs) {
+    return select_host<uint8_t>("tgx_select_text_host", "text", text, offs, n_rows, rows, n_select, out_text, text_cap, out_offs);
+}
+
+uint64_t tgx_shuffle_key(uint64_t seed, uint64_t g) { return tgx::shuffle_key(seed, g); }
+
+tgx_status tgx_shuffled_rows_host(uint64_t n, uint64_t seed, int64_t* rows) {
+    const char* who = "tgx_shuffled_rows_host";
+    if (n >= 0x80000000ull) return fail(TGX_ERR_UNSUPPORTED, "%s: 2^31 rows or more", who);
+    if (n == 0) return TGX_OK;
+    if (!rows) return fail(TGX_ERR_INVALID, "%s: rows is NULL", who);
+    std::vector<uint64_t> keys(n);
+    for (uint64_t g = 0; g < n; g++) {
+        keys[g] = tgx::shuffle_key(seed, g);
+        rows[g] = (int64_t)g;
+    }
+    std::stable_sort(rows, rows + n, [&keys](int64_t a, int64_t b) { return keys[a] < keys[b]; });
     return TGX_OK;
 }
 

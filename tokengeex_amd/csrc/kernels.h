@@ -390,6 +390,31 @@ hipError_t launch_fim_fill(const FimParams& p, hipStream_t stream);
 // mode u8[S] and cuts u64[2S] (either may be null)
 hipError_t launch_fim_info(const FimParams& p, uint8_t* mode, uint64_t* cuts, hipStream_t stream);
 
+// select.hip: rows of a result (u32 ids) or of a corpus (u8 text) selected and reordered through an index (select.h has
+// the index arithmetic); the keys and the sort of the seeded permutation.  All pointers are device memory.
+struct SelectParams {
+    const void* data;               // u32[T] ids or u8[N] text of the source
+    const uint64_t* offs;           // u64[S+1]: its offsets
+    uint64_t n_src;                 // S
+    const int64_t* rows;            // i64[M]: output row k is source row rows[k]
+    uint64_t n_rows;                // M
+    uint64_t* out_offs;             // u64[M+1], written by launch_select_offsets
+    uint64_t n_out;                 // T' = out_offs[M] (the fill)
+    void* out;                      // u32[T'] or u8[T'], 16-byte aligned
+};
+hipError_t select_scan_temp_bytes(uint64_t n_rows, size_t* bytes);
+// *bad (set to kSelectNoBad by the caller) = the smallest k whose rows[k] is outside [0, S)
+hipError_t launch_select_check(const SelectParams& p, unsigned long long* bad, hipStream_t stream);
+hipError_t launch_select_offsets(const SelectParams& p, void* temp, size_t temp_bytes, hipStream_t stream);
+hipError_t launch_select_fill_ids(const SelectParams& p, hipStream_t stream);
+// (the source is a corpus's text: up to 3 bytes on either side of it are read, and lie in the allocation's slack)
+hipError_t launch_select_fill_text(const SelectParams& p, hipStream_t stream);
+hipError_t launch_select_lengths(const uint64_t* offs, uint64_t n_src, int64_t* lengths, hipStream_t stream);
+// the permutation of 0 .. n-1 by (tgx_shuffle_key, index): keys_in, keys_out, vals_in are u64[n] / u64[n] / i64[n] scratch
+hipError_t shuffle_sort_temp_bytes(uint64_t n, size_t* bytes);
+hipError_t launch_shuffled_rows(uint64_t n, uint64_t seed, uint64_t* keys_in, uint64_t* keys_out, int64_t* vals_in, int64_t* rows, void* temp,
+                                size_t temp_bytes, hipStream_t stream);
+
 // decode.hip: ids decoded to UTF-8 text (decode.h has the index arithmetic).  All pointers are device memory.
 struct DecodeParams {
     DecodeTables tab;

@@ -1,5 +1,5 @@
-// The C ABI's transforms of a resident result (include/tgx.h): layouts and windows, assembly, fill-in-the-middle,
-// decode and the text handle, spans.  They run on the caller's stream under a StreamGuard (assembly: on the model's,
+// The C ABI's transforms of a resident result (include/tgx.h): layouts and windows, assembly, fill-in-the-middle, row
+// selection and the seeded permutation, decode and the text handle, spans.  They run on the caller's stream under a StreamGuard (assembly: on the model's,
 // under a Pass) and share device_internal.h with the passes of tgx_api.cpp.
 #include <hip/hip_runtime.h>
 
@@ -17,6 +17,7 @@
 #include "fim.h"
 #include "kernels.h"
 #include "layout.h"
+#include "select.h"
 #include "spans.h"
 
 using namespace tgx::host;
@@ -687,6 +688,158 @@ tgx_status tgx_result_fim(const tgx_result* r, uint32_t prefix_id, uint32_t suff
     timer.read();
     if (n_applied) *n_applied = (h_total - r->n_tokens) / 3;
     *out = res.release();
+    return TGX_OK;
+}
+
+// ---- row selection: rows of a result through an index, the rows' lengths, the seeded permutation (select.hip; select.h) ----
+
+namespace {
+
+const char* const kSelectStageNames[kSelectStages] = {"select_check", "select_offsets_scan", "select_fill_kernel"};
+thread_local float g_select_ms[kSelectStages] = {0, 0, 0};
+
+}  // namespace
+
+namespace tgx::dev {
+
+float* select_stage_ms() { return g_select_ms; }
+
+tgx_status select_rows_device(const char* who, const int64_t* rows, uint64_t n_select, uint32_t flags, int device, StreamGuard& guard,
+                              const int64_t** d_rows) {
+    *d_rows = nullptr;
+    if (n_select == 0) return TGX_OK;
+    if (flags & TGX_SELECT_ROWS_DEVICE) {
+        *d_rows = rows;
+        return check_device_ptr(who, "rows", rows, device, "source");
+    }
+    uint64_t* up = nullptr;
+    HIP_TRY(guard.alloc((size_t)n_select * 8, &up));
+    HIP_TRY(guard.upload(up, std::vector<uint64_t>(reinterpret_cast<const uint64_t*>(rows), reinterpret_cast<const uint64_t*>(rows) + n_select)));
+    *d_rows = reinterpret_cast<const int64_t*>(up);
+    return TGX_OK;
+}
+
+tgx_status select_bad_index(const char* who, uint64_t bad_k, const int64_t* d_rows, uint64_t n_src, hipStream_t hs) {
+    if (bad_k == tgx::kSelectNoBad) return TGX_OK;
+    int64_t value = 0;
+    const tgx_status st = read_u64(hs, d_rows + bad_k, &value);
+    if (st != TGX_OK) return st;
+    return select_index_error(who, bad_k, value, n_src);
+}
+
+}  // namespace tgx::dev
+
+int tgx_select_last_times(const char** names, float* ms, int cap) { return stage_times(kSelectStageNames, g_select_ms, kSelectStages, names, ms, cap); }
+
+tgx_status tgx_result_select(const tgx_result* r, const int64_t* rows, uint64_t n_select, uint32_t flags, void* stream, tgx_result** out) {
+    const char* who = "tgx_result_select";
+    if (!r || !out) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
+    *out = nullptr;
+    if (n_select && !rows) return fail(TGX_ERR_INVALID, "%s: rows is NULL", who);
+    tgx_status st = layout_check_flags(who, flags, TGX_SELECT_ROWS_DEVICE);
+    if (st != TGX_OK) return st;
+    const bool on_device = (flags & TGX_SELECT_ROWS_DEVICE) != 0;
+    if (!on_device && (st = select_check_rows(who, rows, n_select, r->n_samples)) != TGX_OK) return st;  // before any device call
+    const uint64_t S = r->n_samples, M = n_select;
+    DeviceScope scope;
+    HIP_TRY(hipSetDevice(r->device));
+    hipStream_t hs = stream_or_default(stream, r->device);
+    std::unique_ptr<tgx_result> res(new tgx_result());  // before the guard: its buffers go back after the stream's end
+    unsigned long long h_words[2] = {0, tgx::kSelectNoBad};  // T' and the bad-index word
+    StageTimer<kSelectStages> timer(hs, g_select_ms);  // (before the guard: its events outlive the stream's work)
+    StreamGuard guard(r->device, hs);
+    res->device = r->device;
+    res->vocab_size = r->vocab_size;
+    res->n_samples = M;
+    tgx::SelectParams p = {};
+    if ((st = select_rows_device(who, rows, M, flags, r->device, guard, &p.rows)) != TGX_OK) return st;
+    size_t scan_bytes = 0;
+    if (tgx::select_scan_temp_bytes(M, &scan_bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan temp-size query failed");
+    void* d_scan = nullptr;
+    unsigned long long* d_bad = nullptr;
+    if (res->d_offs.alloc(r->device, (size_t)(M + 1) * 8) != hipSuccess || guard.alloc(scan_bytes, &d_scan) != hipSuccess ||  // (never NULL: that asks the scan for its size)
+        guard.alloc(sizeof(unsigned long long), &d_bad) != hipSuccess)
+        return fail(TGX_ERR_DEVICE, "out of device memory (select)");
+    p.data = r->d_ids;
+    p.offs = r->d_offs;
+    p.n_src = S;
+    p.n_rows = M;
+    p.out_offs = res->d_offs;
+    if (on_device && M) {
+        HIP_TRY(hipMemsetAsync(d_bad, 0xFF, sizeof(unsigned long long), hs));
+        timer.begin(0);
+        if (tgx::launch_select_check(p, d_bad, hs) != hipSuccess) return fail(TGX_ERR_DEVICE, "select_check_kernel launch failed");
+        timer.end(0);
+        HIP_TRY(hipMemcpyAsync(&h_words[1], d_bad, sizeof(unsigned long long), hipMemcpyDeviceToHost, hs));
+    }
+    timer.begin(1);
+    if (tgx::launch_select_offsets(p, d_scan, scan_bytes, hs) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan launch failed");
+    timer.end(1);
+    // the one host visit: T' sizes the id buffer, and the bad-index word comes with it
+    if ((st = read_u64(hs, res->d_offs.get() + M, &h_words[0])) != TGX_OK) return st;
+    if ((st = select_bad_index(who, h_words[1], p.rows, S, hs)) != TGX_OK) {
+        guard.done();  // (the stream has reached its end)
+        return st;
+    }
+    const uint64_t h_total = h_words[0];
+    res->n_tokens = h_total;
+    if (res->d_ids.alloc(r->device, (size_t)h_total * 4 + 256) != hipSuccess) return fail(TGX_ERR_DEVICE, "out of device memory (select)");
+    p.n_out = h_total;
+    p.out = res->d_ids;
+    timer.begin(2);
+    if (tgx::launch_select_fill_ids(p, hs) != hipSuccess) return fail(TGX_ERR_DEVICE, "select_fill_kernel launch failed");
+    timer.end(2);
+    // the stream has reached its end before either result can change hands (the guard: also after a failure)
+    HIP_TRY(hipStreamSynchronize(hs));
+    guard.done();
+    timer.read();
+    *out = res.release();
+    return TGX_OK;
+}
+
+tgx_status tgx_result_lengths_device(const tgx_result* r, void* stream, int64_t* d_lengths) {
+    const char* who = "tgx_result_lengths_device";
+    if (!r) return fail(TGX_ERR_INVALID, "%s: result is NULL", who);
+    if (r->n_samples == 0) return TGX_OK;
+    if (!d_lengths) return fail(TGX_ERR_INVALID, "%s: d_lengths is NULL", who);
+    DeviceScope scope;
+    HIP_TRY(hipSetDevice(r->device));
+    const tgx_status st = check_device_ptr(who, "d_lengths", d_lengths, r->device, "result");
+    if (st != TGX_OK) return st;
+    hipStream_t hs = stream_or_default(stream, r->device);
+    StreamGuard guard(r->device, hs);
+    HIP_TRY(tgx::launch_select_lengths(r->d_offs, r->n_samples, d_lengths, hs));
+    HIP_TRY(hipStreamSynchronize(hs));
+    guard.done();
+    return TGX_OK;
+}
+
+tgx_status tgx_shuffled_rows_device(int device, uint64_t n, uint64_t seed, void* stream, int64_t* d_rows) {
+    const char* who = "tgx_shuffled_rows_device";
+    if (n >= 0x80000000ull) return fail(TGX_ERR_UNSUPPORTED, "%s: 2^31 rows or more", who);
+    int n_devices = 0;
+    tgx_status st = require_device(&n_devices);
+    if (st != TGX_OK) return st;
+    if (device < 0 || device >= n_devices) return fail(TGX_ERR_INVALID, "%s: device %d of %d", who, device, n_devices);
+    if (n == 0) return TGX_OK;
+    if (!d_rows) return fail(TGX_ERR_INVALID, "%s: d_rows is NULL", who);
+    DeviceScope scope;
+    HIP_TRY(hipSetDevice(device));
+    if ((st = check_device_ptr(who, "d_rows", d_rows, device, "call")) != TGX_OK) return st;
+    hipStream_t hs = stream_or_default(stream, device);
+    StreamGuard guard(device, hs);
+    size_t sort_bytes = 0;
+    if (tgx::shuffle_sort_temp_bytes(n, &sort_bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "sort temp-size query failed");
+    uint64_t *keys_in = nullptr, *keys_out = nullptr;
+    int64_t* vals_in = nullptr;
+    void* d_sort = nullptr;
+    HIP_TRY(guard.alloc((size_t)n * 8, &keys_in));
+    HIP_TRY(guard.alloc((size_t)n * 8, &keys_out));
+    HIP_TRY(guard.alloc((size_t)n * 8, &vals_in));
+    HIP_TRY(guard.alloc(sort_bytes + 8, &d_sort));  // (never NULL: that asks the sort for its size)
+    HIP_TRY(tgx::launch_shuffled_rows(n, seed, keys_in, keys_out, vals_in, d_rows, d_sort, sort_bytes, hs));
+    HIP_TRY(hipStreamSynchronize(hs));
+    guard.done();
     return TGX_OK;
 }
 

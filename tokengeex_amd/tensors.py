@@ -148,6 +148,38 @@ def to_packed(result: "_lib.NativeResult", block_len: int, *, pad_id: int, bos_i
     return out
 
 
+# ---- rows selected and reordered on the device (csrc/select.hip) ---------------------------------------------------------
+
+def select(obj, rows):
+    """A NativeResult or NativeCorpus whose row k is row rows[k] of `obj` (any order, any subset, repeats allowed), moved
+    on the device.  rows: a torch tensor of indices or a boolean mask (on obj's device: read in place, in the order of
+    torch.cuda.current_stream; on the host: uploaded), a list or a numpy array."""
+    return obj.select(rows)
+
+
+def row_lengths(result: "_lib.NativeResult"):
+    """-> [S] torch.int64 on the result's device: the rows' token counts, for filtering and sorting without a host trip."""
+    import torch
+    dev = _device_of(torch, result)
+    out = torch.empty((result.num_samples,), dtype=torch.int64, device=dev)
+    result.lengths_device(out.data_ptr() if out.numel() else 0, stream=torch.cuda.current_stream(dev).cuda_stream)
+    return out
+
+
+def shuffled_rows(n: int, seed: int, device=0):
+    """-> [n] torch.int64 on `device` (an index, or a torch.device): the seeded permutation of 0 .. n-1, the same on
+    every machine and on the host (_lib.shuffled_rows_host): the rows sorted by (tgx_shuffle_key(seed, row), row)."""
+    import torch
+    if not torch.cuda.is_available():
+        raise _lib.TokenGeeXError("torch sees no GPU", _lib.ERR_DEVICE)
+    dev = device if isinstance(device, torch.device) else torch.device("cuda", int(device))
+    index = torch.cuda.current_device() if dev.index is None else dev.index
+    dev = torch.device("cuda", index)
+    out = torch.empty((int(n),), dtype=torch.int64, device=dev)
+    _lib.shuffled_rows_device(index, int(n), seed, out.data_ptr() if out.numel() else 0, stream=torch.cuda.current_stream(dev).cuda_stream)
+    return out
+
+
 def _window_len(max_length, stride) -> tuple[int, int]:
     if max_length is None:
         raise TypeError("max_length is required for overflow windows")
