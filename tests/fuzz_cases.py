@@ -1,5 +1,7 @@
 """The randomised cases of tests/measure/fuzz_gpu.py, one importable function: the fuzzer, tools/dev/fuzz_case.py and the
-regression tests (tests/test_estep_pairs_gpu.py) rebuild a case from its (seed, case) pair."""
+regression tests (tests/test_estep_pairs_gpu.py) rebuild a case from its (seed, case) pair.  This generator covers the
+encode ids (all its entry points and kernels) and the E-step counts; sampling, n-best and the lattice statistics have a
+generator of their own, tests/lattice_fuzz_cases.py."""
 from __future__ import annotations
 
 import functools

@@ -5,7 +5,8 @@ vocabulary shape (max token length 1..40, with or without full byte cover, dupli
 variant knobs (positions per lane); encode ids must be bit-identical.  The E-step is gated two-sided against the truth
 (orc_estep_ext, 80-bit): a case fails when a kernel misses it (util.estep_gate: 1e-10 for the linear-domain kernels,
 rtol_for for the log-domain ones); the f64 oracle's own distance from the truth is printed and summarised, not treated
-as a kernel failure."""
+as a kernel failure.  The passes covered are encode and the E-step; sampling, n-best and the lattice statistics are run
+by tests/measure/fuzz_lattice_gpu.py over tests/lattice_fuzz_cases.make_case."""
 import os, sys, time
 os.environ["TGX_KNOBS"] = "1"  # the library honours its kernel switches only in processes that opt in
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
