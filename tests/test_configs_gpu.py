@@ -144,7 +144,7 @@ def test_two_models_share_one_resident_corpus_from_two_threads():
 
 
 def test_default_decisions_by_batch_size_on_the_spec_vocabulary():
-    """The launch decisions of run_encode_kernel (tgx_api.cpp) at the sizes they were measured on, with the committed
+    """The launch decisions of run_encode_kernel (encode_pass.cpp) at the sizes they were measured on, with the committed
     32 000-entry spec vocabulary and no switches: 64 MiB -> the long-sample kernel takes the long samples; 256 MiB -> both
     encode kernels at once on CUs of their own; 512 MiB -> encode5_kernel alone on rows = bytes / longest sample.  Ids
     bit-exact against the oracle at every size (the oracle on all host threads)."""
@@ -169,7 +169,7 @@ def test_default_decisions_by_batch_size_on_the_spec_vocabulary():
 
 
 def test_the_cost_model_picks_a_near_best_launch(monkeypatch):
-    """run_encode_kernel (tgx_api.cpp) chooses between the long-sample kernel, both encode kernels at once and
+    """run_encode_kernel (encode_pass.cpp; the cost model: encode_split.h) chooses between the long-sample kernel, both encode kernels at once and
     encode5_kernel alone from constants measured once (bytes per second of each kernel, seconds per byte of a chain).
     This is the check that they still hold on the box at hand: at every size the default must be within 15 % of the best
     of the forced alternatives (no long-sample kernel; the long-sample kernel without co-run), best of five passes each —

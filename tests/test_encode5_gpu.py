@@ -226,7 +226,7 @@ def test_long_and_short_samples_at_once(monkeypatch, cus):
 def test_values_reranked_by_match_counts_after_an_m_step(monkeypatch):
     """A vocabulary as an M-step leaves it (src/prune.rs:124-170: one value per token, kept single-byte tokens with tiny
     scores that still match everywhere): encode5_kernel's values are re-ranked by how often a sample of the first corpus
-    reads them (tgx_api.cpp ensure_value_ranks).  Ids must not depend on the order: bit-exact against the oracle with the
+    reads them (encode_pass.cpp ensure_value_ranks).  Ids must not depend on the order: bit-exact against the oracle with the
     re-ranked values, with build_trie8's order (TGX_VALUE_RANK=model), with dropout, on a second corpus, and after an
     E-step on the chained kernels rewrote the tables."""
     from tokengeex_amd import _lib

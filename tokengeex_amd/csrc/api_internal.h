@@ -1,4 +1,4 @@
-// What the device-side host code (tgx_api.cpp, estep_pass.cpp, lattice_pass.cpp, result_ops.cpp, corpus_ops.cpp) and host_twins.cpp share, free of HIP
+// What the device-side host code (tgx_api.cpp, encode_pass.cpp, estep_pass.cpp, lattice_pass.cpp, result_ops.cpp, corpus_ops.cpp) and host_twins.cpp share, free of HIP
 // types: the thread-local error state, and the argument checks that the *_host twins (host_twins.cpp) share with the
 // device entry points.  Shared helpers live in tgx::host; what needs HIP types is in device_internal.h.  prune_host.cpp,
 // frontback.cpp and unicode_norm.cpp take tgx_set_error from here.

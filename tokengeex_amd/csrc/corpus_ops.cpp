@@ -1,6 +1,6 @@
 // The C ABI's transforms of a resident corpus (include/tgx.h): its read-backs, a corpus from decoded text, the front end
 // (special-token split and CRLF), Unicode normalisation, row selection, and the split plan's handle.  They run on a stream of their own
-// under a StreamGuard and share device_internal.h with the passes of tgx_api.cpp.
+// under a StreamGuard and share device_internal.h with the passes (tgx_api.cpp, encode_pass.cpp, estep_pass.cpp, lattice_pass.cpp).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

@@ -1,5 +1,5 @@
-// What the device-side host code shares (tgx_api.cpp, estep_pass.cpp and lattice_pass.cpp: the passes on a model's own
-// streams, which share pass_internal.h too; result_ops.cpp and corpus_ops.cpp: the calls on a caller's stream): the
+// What the device-side host code shares (tgx_api.cpp, encode_pass.cpp, estep_pass.cpp and lattice_pass.cpp: the passes on
+// a model's own streams, which share pass_internal.h too; result_ops.cpp and corpus_ops.cpp: the calls on a caller's stream): the
 // handle structs, the buffer pool's interface, the guards of a pass and of a call, the stage timer.  api_internal.h
 // stays free of HIP for host_twins.cpp; this header is not.
 // Everything with state (the pool, the default and copy streams) is DEFINED once, in tgx_api.cpp, and only declared
@@ -133,7 +133,7 @@ struct tgx_model {
     DeviceCtrl* d_ctrl = nullptr;
     HostCtrl* h_ctrl = nullptr;  // page-locked
     hipStream_t stream = nullptr;
-    hipStream_t stream2 = nullptr;          // encode6_kernel beside encode5_kernel (run_encode_kernel: co-run)
+    hipStream_t stream2 = nullptr;          // encode6_kernel beside encode5_kernel (encode_pass.cpp, encode_rows5: co-run)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     unsigned int* h_started = nullptr;      // page-locked, device-visible: blocks of encode5_kernel that are resident (co-run)
     int num_cus = 0;

@@ -10,7 +10,7 @@ namespace tgx {
 // and no position's count exceeds the position, so samples shorter than this cannot overflow the field.
 constexpr uint64_t kCountFieldSamples = 1ull << 24;
 
-// What a pass knows when it decides (run_encode_kernel)
+// What a pass knows when it decides (encode_pass.cpp: choose_encode5)
 struct IdsInPlaceQuery {
     bool rows5;          // the pass runs encode5_kernel / encode6_kernel (8-byte records, ranked values)
     bool long_tokens;    // tokens of 17..32 bytes: the LONG build, trace32_kernel

@@ -1,4 +1,5 @@
-// Kernel parameter blocks and launchers shared by kernels.hip and the passes (tgx_api.cpp, estep_pass.cpp, lattice_pass.cpp).
+// Kernel parameter blocks and launchers shared by kernels.hip and the passes (tgx_api.cpp, encode_pass.cpp, estep_pass.cpp,
+// lattice_pass.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

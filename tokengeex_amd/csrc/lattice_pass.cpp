@@ -1,7 +1,7 @@
 // The C ABI's passes over the whole lattice of a sample (include/tgx.h): sampling (sample.hip), lattice statistics
 // (stats.hip) and n-best (nbest.hip), each over a resident corpus or an uploaded batch.  They run on the model's own
-// stream under a Pass and share the corpus's scratch, the encode parameters and the end of a pass with encode in
-// tgx_api.cpp (pass_internal.h).
+// stream under a Pass, take the knobs and the corpus's scratch from tgx_api.cpp, and share the encode parameters, the
+// tables and the end of a pass with encode in encode_pass.cpp (pass_internal.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

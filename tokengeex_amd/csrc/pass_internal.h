@@ -1,8 +1,10 @@
-// What a pass on a model's own streams (estep_pass.cpp, lattice_pass.cpp) takes from tgx_api.cpp, beside
-// device_internal.h: the knobs, the launch arithmetic and the phase stamps of the E-step; the scratch, the encode
-// parameters, the tables and the end of a pass that the lattice passes share with encode.  Everything is DEFINED once, in
-// tgx_api.cpp (as device_internal.h requires of what has state: knob() and debug_flags() read the environment once),
-// except the one template.  result_ops.cpp and corpus_ops.cpp run on a caller's stream and do not include this.
+// What a pass on a model's own streams (encode_pass.cpp, estep_pass.cpp, lattice_pass.cpp) and the counting passes of
+// tgx_api.cpp share, beside device_internal.h: the knobs, the launch arithmetic and the phase stamps of encode and the
+// E-step, and the scratch, all from tgx_api.cpp; the encode parameters, the tables, the encode pass under the caller's
+// locks and the end of a pass, which the lattice and counting passes share with encode, from encode_pass.cpp.
+// Everything is DEFINED once (as device_internal.h requires of what has state: knob(), debug_on() and debug_flags()
+// read the environment once), except the one template.  result_ops.cpp and corpus_ops.cpp run on a caller's stream
+// and do not include this.
 #pragma once
 
 #include <cstddef>
@@ -14,7 +16,9 @@
 
 namespace tgx::dev {
 
-// ---- knobs ---------------------------------------------------------------------------
+// ---- knobs (tgx_api.cpp) ---------------------------------------------------------------
+// TGX_DEBUG=1: every launch logged to stderr and waited for
+bool debug_on();
 // an environment switch among the library's kernels and geometries; NULL unless the process opted in (TGX_KNOBS=1)
 const char* knob(const char* name);
 // an integer knob that holds only inside [lo, hi]
@@ -24,7 +28,7 @@ uint32_t knob_cap_hot(const char* name, uint32_t n_hot);
 // TGX_FLAGS (timing experiments; with TGX_DEBUG=1 only)
 uint32_t debug_flags();
 
-// ---- launch arithmetic -----------------------------------------------------------------
+// ---- launch arithmetic (tgx_api.cpp) -----------------------------------------------------
 // blocks of the trace kernels: four samples per block and round, eight blocks per CU
 uint32_t trace_blocks(const tgx_model* m, uint64_t n_samples);
 // fewer waves (of four rows) per block when the pass has fewer units than the chip has rows
@@ -41,8 +45,8 @@ struct Stamps {
 Stamps stamps_begin(tgx_model* m, Pass& pass, char which, size_t n_waves);
 void stamps_report(tgx_model* m, const Stamps& st, int ppl, const char* what, const char* unit, std::initializer_list<const char*> phases);
 
-// ---- what sampling, statistics and n-best share with encode ----------------------------------
-// the corpus's scratch: back-pointers, counts, status and (with_tmp) the right-aligned ids
+// ---- what sampling, statistics, n-best and the counting passes share with encode (encode_pass.cpp) ------------
+// the corpus's scratch: back-pointers, counts, status and (with_tmp) the right-aligned ids (tgx_api.cpp)
 tgx_status ensure_scratch(tgx_corpus* c, bool with_tmp = true);
 // what every encode and sampling kernel is told about the model, the corpus and its scratch
 tgx::EncodeParams base_encode_params(const tgx_model* m, const tgx_corpus* c, uint64_t seed);
@@ -52,6 +56,8 @@ tgx_status ensure_encode_tables(tgx_model* m);
 tgx_status check_no_path(tgx_model* m, const tgx_corpus* c);
 // counts in c->d_counts and ids right-aligned in c->d_tmp -> r's offsets and ids (the compaction is queued, not waited for)
 tgx_status compact_ids(tgx_model* m, tgx_corpus* c, tgx_result* r, const char* what);
+// tgx_encode_corpus under the caller's locks (m->mu, c->mu): the counting passes start with it
+tgx_status encode_corpus_locked(tgx_model* m, tgx_corpus* c, double dropout, uint64_t seed, tgx_result** out);
 
 // the tgx_encode_batch* entry points: the batch uploaded, `run` over the corpus, the corpus freed
 template <class Run>

@@ -1,6 +1,6 @@
 // The C ABI's transforms of a resident result (include/tgx.h): layouts and windows, assembly, fill-in-the-middle, row
 // selection and the seeded permutation, decode and the text handle, spans.  They run on the caller's stream under a StreamGuard (assembly: on the model's,
-// under a Pass) and share device_internal.h with the passes of tgx_api.cpp.
+// under a Pass) and share device_internal.h with the passes (tgx_api.cpp, encode_pass.cpp, estep_pass.cpp, lattice_pass.cpp).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

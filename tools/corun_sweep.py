@@ -1,4 +1,4 @@
-"""Co-run of the long-sample kernel and encode5_kernel on disjoint CUs (tgx_api.cpp): pass time by length threshold and
+"""Co-run of the long-sample kernel and encode5_kernel on disjoint CUs (encode_pass.cpp: encode_rows5; the choice: encode_split.h): pass time by length threshold and
 by the CUs given to the long-sample kernel, against the default decision.  usage: python tools/corun_sweep.py [MiB ...]"""
 import os, sys
 os.environ["TGX_KNOBS"] = "1"
