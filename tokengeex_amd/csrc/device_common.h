@@ -166,6 +166,18 @@ __device__ __forceinline__ uint64_t claim_rows(unsigned long long* queue, bool n
     return k;
 }
 
+// The same for the two 32-lane rows of the two-rows-per-wave lattice kernels (lattice_walk.h; encode2_kernel keeps its
+// own copy: taking this one moves an instruction of its compiled stream)
+__device__ __forceinline__ uint64_t claim_rows32(unsigned long long* queue, bool need_new, uint32_t r) {
+    const uint64_t want = __builtin_amdgcn_ballot_w64(need_new) & 0x0000000100000001ULL;  // bit 32 r: row r needs one
+    uint64_t k = ~0ull;
+    if (want != 0) {  // wave-uniform
+        const uint64_t base = wave_fetch_add(queue, (uint32_t)__builtin_popcountll(want));
+        if (need_new) k = base + (uint64_t)__builtin_popcountll(want & ((1ull << (r * 32u)) - 1ull));
+    }
+    return k;
+}
+
 // The same with `chunk` consecutive indices per claiming row: returns the first, the row hands out the rest itself
 __device__ __forceinline__ uint64_t claim_rows_chunk(unsigned long long* queue, bool need_new, uint32_t r, uint32_t chunk) {
     const uint64_t want = __builtin_amdgcn_ballot_w64(need_new) & kRowLane0;

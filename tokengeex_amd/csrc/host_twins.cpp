@@ -1204,7 +1204,7 @@ struct StatsTrie {
     std::vector<uint8_t> terminal;
 };
 
-// log(exp(a) + exp(b)) for a, b finite or -inf (stats.hip: stats_log_add)
+// log(exp(a) + exp(b)) for a, b finite or -inf (lattice_walk.h: log_add)
 double stats_log_add_host(double a, double b) {
     const double hi = a > b ? a : b, lo = a > b ? b : a;
     if (lo == -HUGE_VAL) return hi;

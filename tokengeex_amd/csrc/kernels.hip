@@ -29,6 +29,7 @@
 #include "kernels.h"
 #include "trace_body.h"
 #include "device_common.h"
+#include "lattice_walk.h"
 
 namespace tgx {
 
@@ -222,46 +223,6 @@ __device__ __forceinline__ void block_fast(const WaveCtx& C, const uint8_t* __re
     if (lane >= 32u) bp[p - 1] = bpv;  // positions p0+32 .. p0+63
 }
 
-__device__ __forceinline__ void trace_sample(const EncodeParams& P, uint32_t s, uint64_t beg, uint32_t n,
-                                             uint32_t lane, const uint32_t* __restrict__ bp, uint32_t reach_n) {
-    // follow the back-pointers from n (model.rs:113-126), 64 positions per hop group
-    __threadfence_block();  // this wave's bp stores are read back below
-    uint32_t total = 0;
-    uint64_t cursor = beg + n;  // one past this sample's slice of tmp
-    // Error::NoPath(n, n), model.rs:119: nothing to trace, the sample is reported below
-    int64_t q = reach_n ? (int64_t)n - 1 : (int64_t)-1;  // index into bp of the current end position
-    if (P.flags & 4u) q = -1;  // experiment: no trace
-    while (q >= 0) {
-        const uint32_t wq = (uint32_t)q & ~63u;
-        const uint32_t idx = wq + lane;
-        const uint32_t h = (idx < n) ? bp[idx] : 0u;
-        uint64_t ends = 0;
-        int32_t qq = (int32_t)((uint32_t)q - wq);
-        while (qq >= 0) {
-            const uint32_t hh = readlane_u32(h, (uint32_t)qq);
-            ends |= 1ULL << qq;
-            qq -= (int32_t)(hh & 63u) + 1;
-        }
-        q = (int64_t)wq + qq;
-        const uint32_t cnt = (uint32_t)__popcll(ends);
-        if ((ends >> lane) & 1ULL) {
-            // a handle outside the table can only come from a kernel bug; report it as a
-            // failed sample instead of faulting the device
-            const uint32_t slot = h >> 6;
-            if (slot >= P.n_slots) atomicMin(P.err_sample, (unsigned long long)s | (1ULL << 62));
-            const uint32_t id = slot < P.n_slots ? P.tokid[slot] : 0u;
-            const uint32_t above = (uint32_t)__popcll((ends >> lane) >> 1);
-            P.tmp[cursor - 1 - above] = id;
-        }
-        cursor -= cnt;
-        total += cnt;
-    }
-    if (lane == 0) {
-        P.counts[s] = total;
-        if (!reach_n) atomicMin(P.err_sample, (unsigned long long)s);
-    }
-}
-
 // LMT = 0: generic (runtime LM <= 64); LMT = 16 / 32: fast path for full blocks.
 template <int LMT>
 __global__ __launch_bounds__(256) void encode_kernel(EncodeParams P) {
@@ -307,7 +268,7 @@ __global__ __launch_bounds__(256) void encode_kernel(EncodeParams P) {
         for (; p0 <= n; p0 += 64u)
             block_generic(C, text, n, s, p0, lane, LM, sc, hl, txt, bp, acc, bpv, reach, reach_n);
 
-        trace_sample(P, s, beg, n, lane, bp, reach_n);
+        trace_sample(P, s, beg, n, lane, bp, reach_n, (P.flags & 4u) == 0);  // (bit 2: experiment, no trace)
     }
 }
 

@@ -21,6 +21,7 @@
 
 #include "device_common.h"
 #include "kernels.h"
+#include "lattice_walk.h"
 #include "nbest.h"
 
 namespace tgx {
@@ -64,38 +65,11 @@ template <int K>
 __device__ __forceinline__ void nbest_block(const NbestParams& P, const uint8_t* __restrict__ text, uint32_t n, uint32_t p0, uint32_t lane,
                                             uint32_t LM, double* sv, uint32_t* hid, uint8_t* txt, uint32_t* __restrict__ bp,
                                             double (&A)[K], uint32_t (&AK)[K]) {
-    const uint4* __restrict__ trie = reinterpret_cast<const uint4*>(P.trie);
-    const uint32_t p = p0 + lane;
-    txt[lane] = (p < n) ? text[p] : (uint8_t)0;
-    txt[lane + 64] = (p + 64 < n) ? text[p + 64] : (uint8_t)0;
-    __builtin_amdgcn_wave_barrier();
-
-    // match: every lane walks the trie from its own position
-    const uint32_t rem = (p < n) ? (n - p) : 0u;
-    const uint32_t maxd = rem < LM ? rem : LM;
-    uint32_t cur = 0, base = P.root_base;
-    uint64_t m = 0;
-    bool alive = maxd > 0;
-    for (uint32_t d = 0; d < LM; ++d) {
-        alive = alive && (d < maxd);
-        if (__builtin_amdgcn_ballot_w64(alive) == 0) break;
-        if (alive) {
-            const uint32_t t = base ^ (uint32_t)txt[lane + d];
-            const uint4 r = load_rec(trie, t);
-            if (r.x == cur) {
-                cur = t;
-                base = r.y & 0x7FFFFFFFu;
-                if (r.y >> 31) {
-                    m |= 1ULL << d;
-                    sv[kFront + lane * LM + d] = __hiloint2double((int)r.w, (int)r.z);
-                    hid[kFront + lane * LM + d] = t < P.n_slots ? P.tokid[t] : 0u;
-                }
-            } else {
-                alive = false;
-            }
-        }
-    }
-    __builtin_amdgcn_wave_barrier();
+    const uint64_t m = walk_block64(reinterpret_cast<const uint4*>(P.trie), P.root_base, text, n, p0, lane, LM, txt,
+                                    [&](uint32_t d, uint32_t t, const uint4& rec) {
+                                        sv[kFront + lane * LM + d] = rec_score(rec);
+                                        hid[kFront + lane * LM + d] = t < P.n_slots ? P.tokid[t] : 0u;
+                                    });
 
     // relax positions p0 .. p0 + 63 in order
     const double ninf = -__builtin_huge_val();
@@ -236,17 +210,7 @@ __global__ __launch_bounds__(256) void offs_add_kernel(uint64_t* offs, uint64_t 
 // ---- launchers ---------------------------------------------------------------------------------------------------
 template <int K>
 static hipError_t launch_nbest_k(const NbestParams& p, uint32_t num_cus, hipStream_t stream) {
-    const uint32_t wb = wave_lds_bytes(p.lm);
-    uint32_t wpb = (160u * 1024u) / wb;
-    wpb = wpb < 1u ? 1u : (wpb > 4u ? 4u : wpb);
-    const uint64_t want = (p.n_samples + wpb - 1) / wpb;
-    const uint64_t per_cu = (160u * 1024u) / (wpb * wb) > 0 ? (160u * 1024u) / (wpb * wb) : 1u;
-    const uint64_t cap = (uint64_t)num_cus * per_cu;
-    const uint32_t blocks = (uint32_t)(want < 1 ? 1 : (want < cap ? want : cap));
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(nbest_kernel<K>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(nbest_kernel<K>, dim3(blocks), dim3(64u * wpb), wpb * wb, stream, p);
-    return hipGetLastError();
+    return launch_lattice(nbest_kernel<K>, generic_lattice_grid(p.n_samples, wave_lds_bytes(p.lm), num_cus), stream, p);
 }
 
 hipError_t launch_nbest(const NbestParams& p, uint32_t K, uint32_t num_cus, hipStream_t stream) {

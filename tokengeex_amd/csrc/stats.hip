@@ -15,61 +15,27 @@
 //   stats_rows_kernel  tokens <= 32 bytes: two samples per wave on 32-lane rows, linear domain, sample_rows_kernel's
 //                      structure, rescale and range rule; LDS per match holds w and w·s.  The forward value goes
 //                      through sample_rows_kernel's operations in its order: the same logz, bit for bit.
+//
+// The trie walk, the rows scaffold and the grids are lattice_walk.h's; here are the two semirings.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "device_common.h"
 #include "kernels.h"
+#include "lattice_walk.h"
 #include "stats.h"
 
 namespace tgx {
 
-// log(exp(a) + exp(b)) for a, b finite or -inf (sample.hip's)
-__device__ __forceinline__ double stats_log_add(double a, double b) {
-    const double hi = a > b ? a : b, lo = a > b ? b : a;
-    if (lo == -__builtin_huge_val()) return hi;
-    return hi + log1p(exp(lo - hi));
-}
-
 // ---- generic kernel --------------------------------------------------------------------------------------------
-// LDS per wave: rs[row u = start position in the 64-block][len - 1] = the raw score, then 128 bytes of staged text.
-// Same row stride and padding as sample_kernel.
-__host__ __device__ inline uint32_t stats_wave_lds_bytes(uint32_t lm) { return (wave_lds_entries(lm) * 8u + 128u + 15u) & ~15u; }
+// LDS entry per match: rs = the raw score
+constexpr uint32_t kStatsEntryBytes = 8u;
 
 __device__ __forceinline__ void stats_block(const EncodeParams& P, const StatsParams& Q, const uint8_t* __restrict__ text, uint32_t n,
                                             uint32_t p0, uint32_t lane, uint32_t LM, double* rs, uint8_t* txt, double& acc, double& macc,
                                             double& tacc, double& z_n, double& m_n, double& t_n) {
-    const uint4* __restrict__ trie = reinterpret_cast<const uint4*>(P.trie);
-    const uint32_t p = p0 + lane;
-    txt[lane] = (p < n) ? text[p] : (uint8_t)0;
-    txt[lane + 64] = (p + 64 < n) ? text[p + 64] : (uint8_t)0;
-    __builtin_amdgcn_wave_barrier();
-
-    // match: every lane walks the trie from its own position
-    const uint32_t rem = (p < n) ? (n - p) : 0u;
-    const uint32_t maxd = rem < LM ? rem : LM;
-    uint32_t cur = 0, base = P.root_base;
-    uint64_t m = 0;
-    bool alive = maxd > 0;
-    for (uint32_t d = 0; d < LM; ++d) {
-        alive = alive && (d < maxd);
-        if (__builtin_amdgcn_ballot_w64(alive) == 0) break;
-        if (alive) {
-            const uint32_t t = base ^ (uint32_t)txt[lane + d];
-            const uint4 r = load_rec(trie, t);
-            if (r.x == cur) {
-                cur = t;
-                base = r.y & 0x7FFFFFFFu;
-                if (r.y >> 31) {
-                    m |= 1ULL << d;
-                    rs[kFront + lane * LM + d] = __hiloint2double((int)r.w, (int)r.z);
-                }
-            } else {
-                alive = false;
-            }
-        }
-    }
-    __builtin_amdgcn_wave_barrier();
+    const uint64_t m = walk_block64(reinterpret_cast<const uint4*>(P.trie), P.root_base, text, n, p0, lane, LM, txt,
+                                    [&](uint32_t d, uint32_t, const uint4& rec) { rs[kFront + lane * LM + d] = rec_score(rec); });
 
     // relax positions p0 .. p0 + 63 in order; -inf = "no value yet" in acc (macc and tacc are then 0)
     const double ninf = -__builtin_huge_val();
@@ -89,7 +55,7 @@ __device__ __forceinline__ void stats_block(const EncodeParams& P, const StatsPa
         if ((active >> lane) & 1ULL) {
             const double s = rs[kFront + i * LM + ((lane - i - 1u) & 63u)];
             const double x = best + Q.alpha * s;
-            const double nw = stats_log_add(acc, x);
+            const double nw = log_add(acc, x);
             const double pi = exp(x - nw);  // the new term's share of the sum; 1 when it is the first
             macc = macc + pi * ((bm + s) - macc);
             tacc = tacc + pi * ((bt + 1.0) - tacc);
@@ -108,7 +74,7 @@ __global__ __launch_bounds__(256) void stats_kernel(EncodeParams P, StatsParams 
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = threadIdx.x >> 6;
     const uint32_t LM = P.lm;
-    unsigned char* wbase = smem + (size_t)wave * stats_wave_lds_bytes(LM);
+    unsigned char* wbase = smem + (size_t)wave * lattice_wave_lds_bytes(LM, kStatsEntryBytes);
     double* rs = reinterpret_cast<double*>(wbase);
     uint8_t* txt = wbase + (size_t)wave_lds_entries(LM) * 8u;
 
@@ -133,15 +99,14 @@ __global__ __launch_bounds__(256) void stats_kernel(EncodeParams P, StatsParams 
 }
 
 // ---- rows kernel -----------------------------------------------------------------------------------------------
-// sample_rows_kernel's linear domain: a row's values are stored as v · 2^scale with one scale per row, renormalised at
-// the start of every block of 32 positions by the exponent of the largest `a`, applied to a, r and c with the same
-// exact ldexp.  Match (position, len) holds w = exp(alpha·s) (from `wslot`) and ws = w · s (s from the trie record).
-// Step U hands the row the final (a, r, c) of position p0 + U and every lane adds the candidate of its own length:
+// Linear domain (lattice_walk.h): the row is renormalised by the exponent of its largest `a`, applied to a, r and c with
+// the same exact ldexp.  Match (position, len) holds w = exp(alpha·s) (from `wslot`) and ws = w · s (s from the trie
+// record).  Step U hands the row the final (a, r, c) of position p0 + U and every lane adds the candidate of its own
+// length:
 //   a += a_U·w,   r += r_U·w + a_U·ws,   c += c_U·w + a_U·w.
 // The launcher only picks this kernel when every w lies in [2^-300, 2^300]; a reachable position whose `a` falls
 // outside [2^-600, 2^600] of its row's scale, or an r or c that is not finite in the block of its sample's end, sets
 // *range_flag.
-constexpr uint32_t kStatsRowsBytes = 2u * 64u * 32u * 8u;  // 32 KiB per wave: w and ws, 64 positions x 32 lengths
 
 // Lane U of each 32-lane row to all lanes of its row, without the scalar round trip of sample_rows_kernel's broadcast
 // (per f64: four v_readlane, four moves of the scalars back into vector registers, two selects by half).  A 32-lane row
@@ -220,104 +185,35 @@ __device__ __forceinline__ void stats_rows_relax(const double* wl, const double*
 
 __global__ __launch_bounds__(320) void stats_rows_kernel(EncodeParams P, StatsParams Q) {
     extern __shared__ __align__(16) unsigned char smem[];
-    constexpr uint32_t LM = 32;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t l = lane & 31u, r = lane >> 5;
     const uint32_t wave = threadIdx.x >> 6;
-    const uint4* __restrict__ trie = reinterpret_cast<const uint4*>(P.trie);
-    double* wl = reinterpret_cast<double*>(smem + (size_t)wave * kStatsRowsBytes);
+    double* wl = reinterpret_cast<double*>(smem + (size_t)wave * kRows32WaveBytes);  // w, then ws
     double* sl = wl + 64u * 32u;
 
-    uint32_t s = 0, n = 0, p0 = 0;
-    uint64_t beg = 0;
-    int64_t scale = 0;  // the row's values are v · 2^scale
-    bool live = false, need_new = true;
+    Rows32 R;
     double acc = 0.0, racc = 0.0, cacc = 0.0;
 
     for (;;) {
-        {
-            const uint64_t want = __builtin_amdgcn_ballot_w64(need_new) & 0x0000000100000001ULL;
-            uint64_t k = ~0ull;
-            if (want != 0) {  // wave-uniform
-                const uint64_t b = wave_fetch_add(P.queue, (uint32_t)__builtin_popcountll(want));
-                if (need_new) k = b + (uint64_t)__builtin_popcountll(want & ((1ull << (r * 32u)) - 1ull));
-            }
-            if (need_new) {
-                live = k < P.n_samples;
-                if (live) {
-                    s = P.order[k];
-                    beg = P.offs[s];
-                    n = (uint32_t)(P.offs[s + 1] - beg);
-                }
-                p0 = 0;
-                scale = 0;
-                acc = (l == 0u) ? 1.0 : 0.0;  // a[0] = 1, r[0] = c[0] = 0
-                racc = 0.0;
-                cacc = 0.0;
-            }
-        }
-        need_new = false;
-        if (__builtin_amdgcn_ballot_w64(live) == 0) break;
+        rows32_next(P, R, r, [&] {
+            acc = (l == 0u) ? 1.0 : 0.0;  // a[0] = 1, r[0] = c[0] = 0
+            racc = 0.0;
+            cacc = 0.0;
+        });
+        if (__builtin_amdgcn_ballot_w64(R.live) == 0) break;
 
-        // ---- match: lane (r, l) walks from position p0 + l
-        const uintptr_t addr = reinterpret_cast<uintptr_t>(P.text + (live ? beg + p0 + l : 0));
-        const uint32_t sh = (uint32_t)(addr & 3u);
-        const uint32_t* __restrict__ wp = reinterpret_cast<const uint32_t*>(addr & ~uintptr_t(3));
-        uint32_t w9[9];
-#pragma unroll
-        for (int q = 0; q < 9; ++q) w9[q] = wp[q];
-        uint32_t bytes[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) bytes[q] = __builtin_amdgcn_alignbyte(w9[q + 1], w9[q], sh);
-        {
-            double2* grp = reinterpret_cast<double2*>(wl);  // w and ws of the wave: 32 KiB, swept linearly
-#pragma unroll
-            for (int q = 0; q < 32; ++q) grp[q * 64 + lane] = make_double2(0.0, 0.0);
-        }
-        __builtin_amdgcn_wave_barrier();
-        const uint32_t pg = p0 + l;
-        const uint32_t rem = (live && pg < n) ? (n - pg) : 0u;
-        const uint32_t maxd = rem < LM ? rem : LM;
-        uint32_t cur = 0, base = P.root_base;
-        bool alive = maxd > 0;
-#pragma unroll
-        for (int d = 0; d < (int)LM; ++d) {
-            alive = alive && ((uint32_t)d < maxd);
-            if (__builtin_amdgcn_ballot_w64(alive) == 0) break;
-            if (alive) {
-                const uint32_t ch = (bytes[d >> 2] >> ((d & 3) * 8)) & 0xFFu;
-                const uint32_t t = base ^ ch;
-                const uint4 rec = load_rec(trie, t);
-                alive = rec.x == cur;
-                if (alive) {
-                    cur = t;
-                    base = rec.y & 0x7FFFFFFFu;
-                    if (rec.y >> 31) {
-                        const double w = Q.wslot[t];
-                        const uint32_t col = lane * LM + (((uint32_t)d + l) & 31u);  // reader's column is a per-lane constant
-                        wl[col] = w;
-                        sl[col] = w * __hiloint2double((int)rec.w, (int)rec.z);
-                    }
-                }
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-
-        // ---- renormalise the row: positions p0 .. p0 + 31 are in its lanes (partial sums)
-        {
-            int ex = (acc == 0.0) ? -100000 : __builtin_amdgcn_frexp_exp(acc);
-#pragma unroll
-            for (int o = 1; o < 32; o <<= 1) ex = max(ex, __shfl_xor(ex, o, 32));
-            if (ex == -100000) ex = 0;
-            acc = __builtin_amdgcn_ldexp(acc, -ex);
-            racc = __builtin_amdgcn_ldexp(racc, -ex);
-            cacc = __builtin_amdgcn_ldexp(cacc, -ex);
-            scale += ex;
-        }
+        const uint32_t pg = R.p0 + l;
+        match_rows32(P, R, lane, pg, wl, [&](int d, uint32_t t, const uint4& rec) {
+            const double w = Q.wslot[t];
+            const uint32_t col = rows32_col(lane, (uint32_t)d);
+            wl[col] = w;
+            sl[col] = w * rec_score(rec);
+        });
+        R.scale += renorm_row32(acc, racc, cacc);
 
         // ---- relax (the wave takes the LAST build when the end of either row's sample lies in this block)
         double fa = 0.0, fr = 0.0, fc = 0.0;
-        const bool last = live && n - p0 < 32u;
+        const bool last = R.live && R.n - R.p0 < 32u;
         const bool any_last = __builtin_amdgcn_ballot_w64(last) != 0;  // wave-uniform
         {
             const uint32_t ofs = r * 1024u + ((l - 1u) & 31u);
@@ -327,47 +223,24 @@ __global__ __launch_bounds__(320) void stats_rows_kernel(EncodeParams P, StatsPa
         __builtin_amdgcn_wave_barrier();
         const bool reached = fa > 0.0;
         const bool finite_rc = __builtin_fabs(fr) < __builtin_huge_val() && __builtin_fabs(fc) < __builtin_huge_val();  // (false for NaN)
-        if (live && pg <= n && reached && (fa < 0x1p-600 || fa > 0x1p600 || (last && !finite_rc))) atomicOr(Q.range_flag, 1ull);
+        if (R.live && pg <= R.n && reached && (fa < 0x1p-600 || fa > 0x1p600 || (last && !finite_rc))) atomicOr(Q.range_flag, 1ull);
 
-        if (live) {
-            const uint32_t left = n - p0;
-            if (left < 32u) {  // position n lies in this block: the sample is done
-                if (left == l) {
-                    Q.logz[s] = reached ? log(fa) + (double)scale * 0.69314718055994530942 : -__builtin_huge_val();
-                    Q.escore[s] = reached ? fr / fa : __builtin_nan("");
-                    Q.etokens[s] = reached ? fc / fa : __builtin_nan("");
-                }
-                need_new = true;
-            } else {
-                p0 += 32u;
-            }
-        }
+        rows32_advance(R, l, [&] {  // this lane holds position n: the sample is done
+            Q.logz[R.s] = reached ? rows32_log(fa, R.scale) : -__builtin_huge_val();
+            Q.escore[R.s] = reached ? fr / fa : __builtin_nan("");
+            Q.etokens[R.s] = reached ? fc / fa : __builtin_nan("");
+        });
     }
 }
 
 // ---- launchers ---------------------------------------------------------------------------------------------------
 hipError_t launch_stats(const EncodeParams& p, const StatsParams& q, uint32_t num_cus, hipStream_t stream) {
-    const uint32_t wb = stats_wave_lds_bytes(p.lm);
-    uint32_t wpb = (160u * 1024u) / wb;
-    wpb = wpb < 1u ? 1u : (wpb > 4u ? 4u : wpb);
-    const uint64_t want = (p.n_samples + wpb - 1) / wpb;
-    const uint64_t cap = (uint64_t)num_cus * ((160u * 1024u) / (wpb * wb) > 0 ? (160u * 1024u) / (wpb * wb) : 1u);
-    const uint32_t blocks = (uint32_t)(want < 1 ? 1 : (want < cap ? want : cap));
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(stats_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(stats_kernel, dim3(blocks), dim3(64u * wpb), wpb * wb, stream, p, q);
-    return hipGetLastError();
+    const LatticeGrid g = generic_lattice_grid(p.n_samples, lattice_wave_lds_bytes(p.lm, kStatsEntryBytes), num_cus);
+    return launch_lattice(stats_kernel, g, stream, p, q);
 }
 
-// one block of five waves per CU: 5 x 32 KiB of LDS
 hipError_t launch_stats_rows(const EncodeParams& p, const StatsParams& q, uint32_t num_cus, hipStream_t stream) {
-    const uint32_t waves = 5;
-    const uint64_t want = (p.n_samples + 2 * waves - 1) / (2 * waves);
-    const uint32_t blocks = (uint32_t)(want < (uint64_t)num_cus ? (want ? want : 1) : (uint64_t)num_cus);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(stats_rows_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(stats_rows_kernel, dim3(blocks), dim3(64u * waves), waves * kStatsRowsBytes, stream, p, q);
-    return hipGetLastError();
+    return launch_lattice(stats_rows_kernel, rows_lattice_grid(p.n_samples, num_cus), stream, p, q);
 }
 
 }  // namespace tgx
