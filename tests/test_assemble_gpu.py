@@ -17,6 +17,7 @@ import tokengeex_amd as tgx
 from tokengeex_amd import _lib, synth, tensors
 
 import layout_checker as lc
+import past_cap
 
 N_SPECIALS = 6
 PAD = 7
@@ -354,3 +355,41 @@ def test_a_byte_without_a_token_fails_as_encode_batch_flat_does():
     assert np.array_equal(res.ids(), w_ids) and np.array_equal(res.offsets(), w_offs)
     assert w_ids.tolist() == [2, 3, 0, 3, 1, 3, 3, 2]
     res.free()
+
+
+def _pattern_rows_against_the_twin(lens):
+    """A row of the pattern (tests/past_cap.py) is a segment: every third one-id row a special token, the others encoded
+    segments of as many ids; five segments to a sample; against the host twin"""
+    nat = _native()
+    V = nat.vocab_size
+    ones = np.flatnonzero(lens == 1)
+    ss = np.full(lens.size, -1, np.int32)
+    ss[ones[::3]] = np.arange(ones[::3].size) % N_SPECIALS
+    enc = lens[ss < 0]
+    oo = np.concatenate([np.zeros(1, np.uint64), np.cumsum(enc, dtype=np.uint64)])
+    ids = (np.arange(int(oo[-1]), dtype=np.uint64) * 7 % V).astype(np.uint32)
+    seg_offs = np.unique(np.append(np.arange(0, lens.size, 5), lens.size)).astype(np.uint64)
+    want_ids, want_offs = _lib.assemble_host(seg_offs, ss, ids, oo, V, N_SPECIALS)
+    assert want_ids.size == int(lens.sum())
+    segs = _lib.NativeResult.from_ids(ids, oo, V)
+    res = nat.assemble(segs, seg_offs, ss, N_SPECIALS)
+    try:
+        assert np.array_equal(res.offsets(), want_offs)
+        assert np.array_equal(res.ids(), want_ids)
+    finally:
+        res.free()
+        segs.free()
+
+
+def test_the_second_trip_of_the_strided_tile_loop():
+    """T' = 2048 tiles + one tile + 1: blocks 0 and 1 of assemble_fill_kernel take a second tile; segments of 0, 1 and
+    (once) more than a tile of ids"""
+    lens = past_cap.lengths(2048, 1024)
+    assert int(lens.sum()) == past_cap.n_out(2048, 1024)
+    _pattern_rows_against_the_twin(lens)
+
+
+@pytest.mark.parametrize("n_out", past_cap.edge_sizes(4, 1024))
+def test_outputs_that_end_at_the_edges_of_a_slot_and_a_tile(n_out):
+    """T' = 0, 1, a thread's slot of 4 ids and the tile of 1024, each less one, full and one over"""
+    _pattern_rows_against_the_twin(past_cap.edge_lengths(n_out))

@@ -16,6 +16,7 @@ import tokengeex_amd as tgx
 from tokengeex_amd import _lib, synth, tensors
 
 import decode_checker as dc
+import past_cap
 
 N_SPECIALS = 6
 SPECIALS = ["<|endoftext|>", "<|fim", "<|fim|>", "<pad>", "<s>", "</s>"]
@@ -466,3 +467,38 @@ def test_handles_pool_and_current_device():
     tgx.pool_trim()
     assert torch.cuda.current_device() == before
     _check_against_host(m, res, ids, offs, True)     # and everything still works on fresh buffers
+
+
+def _pattern_rows_against_the_twin(lens):
+    """A row of the pattern (tests/past_cap.py) is an element: a one-byte token, a special token without bytes, and a
+    special token of as many bytes as the one longer row has; seven elements to a row; against the host twin"""
+    long_len = int(lens.max()) if int(lens.max()) > 1 else 0
+    toks = [bytes([b]) for b in range(256)]
+    m = Model(toks, np.full(256, -1.0), [b"", bytes(97 + k % 26 for k in range(long_len))])
+    ids = (np.arange(lens.size, dtype=np.uint64) * 7 % 26 + 97).astype(np.uint32)
+    ids[lens == 0] = 256
+    if long_len:
+        ids[lens == long_len] = 257
+    offs = np.unique(np.append(np.arange(0, lens.size, 7), lens.size)).astype(np.uint64)
+    want = m.twin(ids, offs, True)
+    assert want[0].size == int(lens.sum()) and want[2] == 0
+    res = _lib.NativeResult.from_ids(ids, offs, 258)
+    try:
+        got = _take(m.decode(res, True))
+    finally:
+        res.free()
+    assert np.array_equal(got[1], want[1]) and np.array_equal(got[0], want[0]) and got[2] == 0
+
+
+def test_the_second_trip_of_the_strided_tile_loop():
+    """2048 tiles + one tile + 1 raw bytes: blocks 0 and 1 of decode_fill_kernel take a second tile; one special token has
+    more than a tile of bytes"""
+    lens = past_cap.lengths(2048, 4096)
+    assert int(lens.sum()) == past_cap.n_out(2048, 4096) and int(lens.max()) > 4096
+    _pattern_rows_against_the_twin(lens)
+
+
+@pytest.mark.parametrize("n_raw", past_cap.edge_sizes(16, 4096))
+def test_outputs_that_end_at_the_edges_of_a_slot_and_a_tile(n_raw):
+    """0 and 1 raw bytes, a thread's slot of 16 bytes and the tile of 4096, each less one, full and one over"""
+    _pattern_rows_against_the_twin(past_cap.edge_lengths(n_raw))

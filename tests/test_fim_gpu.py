@@ -20,6 +20,7 @@ from tokengeex_amd import _lib, synth, tensors
 import fim_cases
 import fim_checker as fc
 import layout_checker as lc
+import past_cap
 
 SPECIALS = ["<|eos|>", "<|pad|>", "<|lang|>", "<|filename|>", "<|suffix|>", "<|prefix|>", "<|middle|>"]
 FIM = dict(prefix="<|prefix|>", suffix="<|suffix|>", middle="<|middle|>", rate=0.5, spm_rate=0.5, seed=1)
@@ -265,3 +266,48 @@ def test_tokenizer_layouts_with_fim():
         tk.encode_batch_packed(texts[:4], 64, pad=pad, fim=dict(FIM, prefix="<|nope|>"))
     with pytest.raises(TypeError):
         tk.encode_batch_packed(texts[:4], 64, pad=pad, fim=dict(prefix=1, suffix=2))
+
+
+def _edge_case(target):
+    """Rows of tests/past_cap.py's pattern whose T' is target.  A rearranged row grows by three sentinels, and whether a
+    row is rearranged depends on the seed and its index alone, so the pattern is shortened until T' is at most the
+    target, under one seed after another until it is the target."""
+    V = 1000
+    for seed in range(1, 200):
+        fim = dict(rate=0.5, spm_rate=0.5, seed=seed, first_row=5)
+        for t in range(target, -1, -1):
+            offs = past_cap.edge_offsets(t)
+            ids = (np.arange(t, dtype=np.uint64) * 7 % V).astype(np.uint32)
+            want = _lib.fim_host(ids, offs, V, V + 2, V, V + 1, **fim)
+            if int(want[1][-1]) <= target:
+                break
+        if int(want[1][-1]) == target and (want[5] > 0 or target < 4):
+            return dict(ids=ids, offs=offs, vocab_size=V, pre=V + 2, suf=V, mid=V + 1, **fim)
+    raise AssertionError(f"no seed gives T' = {target}")
+
+
+@pytest.mark.parametrize("n_out", past_cap.edge_sizes(4, 1024))
+def test_outputs_that_end_at_the_edges_of_a_slot_and_a_tile(n_out):
+    """T' = 0, 1, a thread's slot of 4 ids and the tile of 1024, each less one, full and one over"""
+    case = _edge_case(n_out)
+    got, twin = _device_and_twin(case)
+    assert int(twin[1][-1]) == n_out
+    _same(got, twin, n_out)
+    _same(got, fc.fim(case["ids"], case["offs"], case["vocab_size"], case["pre"], case["suf"], case["mid"], **fim_cases.args(case)), n_out)
+
+
+def test_the_second_trip_of_the_strided_tile_loop():
+    """T' = 2048 tiles + one tile + 1 (tests/past_cap.py): blocks 0 and 1 of fim_fill_kernel take a second tile"""
+    V, target = 1000, past_cap.n_out(2048, 1024)
+    lens = past_cap.lengths(2048, 1024)
+    long_at = int(np.argmax(lens))
+    fim = dict(rate=0.5, spm_rate=0.5, seed=11, first_row=5)
+    for _ in range(2):  # whether a row is rearranged does not depend on its length, as long as it has a token: shorten the long row by the sentinels
+        offs = np.concatenate([np.zeros(1, np.uint64), np.cumsum(lens, dtype=np.uint64)])
+        ids = (np.arange(int(offs[-1]), dtype=np.uint64) * 7 % V).astype(np.uint32)
+        want = _lib.fim_host(ids, offs, V, V + 2, V, V + 1, **fim)
+        lens[long_at] -= np.uint64(int(want[1][-1]) - target)
+    assert int(want[1][-1]) == target and want[5] > 1000 and lens[long_at] > 1024
+    case = dict(ids=ids, offs=offs, vocab_size=V, pre=V + 2, suf=V, mid=V + 1, **fim)
+    got, twin = _device_and_twin(case)
+    _same(got, twin, "past the cap")

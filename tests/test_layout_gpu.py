@@ -17,6 +17,7 @@ import tokengeex_amd as tgx
 from tokengeex_amd import _lib, synth, tensors
 
 import layout_checker as lc
+import past_cap
 
 PAD = 7
 BOS_EOS = [(None, None), (1, None), (None, 2), (1, 2)]
@@ -263,6 +264,24 @@ def test_packed_stream_of_more_than_2_pow_24_elements():
     assert np.array_equal(got["input_ids"][rows].cpu().numpy(), w)
     assert int(got["attention_mask"].sum()) == int((first + 1).sum())
     res.free()
+
+
+@pytest.mark.parametrize("n_out", past_cap.edge_sizes(4, 1024))
+def test_packed_outputs_that_end_at_the_edges_of_a_slot_and_a_tile(n_out):
+    """B·L = 0, 1, a thread's slot of 4 elements and the tile of 1024, each less one, full and one over: rows of
+    tests/past_cap.py's pattern packed into blocks of one element, so that B·L is the stream's length; against the host twin"""
+    torch = _torch()
+    offs = past_cap.edge_offsets(n_out)
+    ids = (np.arange(n_out, dtype=np.uint64) * 7 % 1000).astype(np.uint32)
+    want = _lib.layout_pack_host(ids, offs, 1, PAD)
+    assert want["input_ids"].shape == (n_out, 1)
+    res = _lib.NativeResult.from_ids(ids, offs, 1000)
+    try:
+        got = tensors.to_packed(res, 1, pad_id=PAD, dtype=torch.int32, return_doc=True)
+        for name in ("input_ids", "doc_ids", "positions"):
+            assert np.array_equal(got[name].cpu().numpy(), want[name]), name
+    finally:
+        res.free()
 
 
 def test_torch_layer():

@@ -20,6 +20,7 @@ import tokengeex_amd as tgx
 from tokengeex_amd import _lib, synth, tensors
 
 import layout_checker as lc
+import past_cap
 import select_cases
 import select_checker as sc
 
@@ -381,3 +382,37 @@ def test_stage_times_name_the_three_stages():
         assert all(np.isfinite(v) and v >= 0 for v in times.values()), times
         out.free()
     src.free()
+
+
+def _pattern_rows_against_the_twin(kind, offs):
+    """Rows of tests/past_cap.py's pattern, selected in their order, so that the output's rows are the pattern's; against
+    the host twin"""
+    n = int(offs[-1])
+    data = (np.arange(n, dtype=np.uint64) * 7 % 251 + 1).astype(np.uint32 if kind == "ids" else np.uint8)
+    rows = np.arange(offs.size - 1, dtype=np.int64)
+    want = TWIN[kind](data, offs, rows)
+    assert want[0].size == n
+    src = _source(dict(data=data, offs=offs, vocab_size=1000), kind)
+    try:
+        out = src.select(rows)
+        try:
+            _same(_read(out, kind), want, (kind, n))
+        finally:
+            out.free()
+    finally:
+        src.free()
+
+
+@pytest.mark.parametrize("kind", ["ids", "bytes"])
+def test_the_second_trip_of_the_strided_tile_loop(kind):
+    """T' = 2048 tiles + one tile + 1: blocks 0 and 1 of select_fill_kernel take a second tile"""
+    tile = 1024 if kind == "ids" else 4096
+    offs = past_cap.offsets(2048, tile)
+    assert int(offs[-1]) == past_cap.n_out(2048, tile)
+    _pattern_rows_against_the_twin(kind, offs)
+
+
+@pytest.mark.parametrize("kind,n_out", [("ids", n) for n in past_cap.edge_sizes(4, 1024)] + [("bytes", n) for n in past_cap.edge_sizes(16, 4096)])
+def test_outputs_that_end_at_the_edges_of_a_slot_and_a_tile(kind, n_out):
+    """T' = 0, 1, a thread's slot (4 ids, 16 bytes) and the tile (1024 ids, 4096 bytes), each less one, full and one over"""
+    _pattern_rows_against_the_twin(kind, past_cap.edge_offsets(n_out))

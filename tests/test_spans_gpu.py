@@ -15,6 +15,7 @@ pytestmark = pytest.mark.gpu
 import tokengeex_amd as tgx
 from tokengeex_amd import _lib, synth, tensors
 
+import past_cap
 import spans_checker as sc
 from test_layout_gpu import SOURCES, _native, _source, _texts
 
@@ -348,3 +349,37 @@ def test_on_a_side_stream_the_tensor_is_usable_at_once():
     assert int(total) == int(w.sum())
     want = sc.padded(ids, offs, sc.vocab_lookup(_spec_tokens()), "byte", 64, None, 2, flat_spans=_want_flat("encode", "byte"))
     assert int(ptotal) == int(want.sum()) and torch.cuda.current_device() == before
+
+
+@functools.lru_cache(maxsize=None)
+def _byte_model():
+    toks = [bytes([b]) for b in range(256)]
+    return tgx.NativeModel(toks, np.full(256, -1.0)), _lib.pack(toks)
+
+
+def _pattern_rows_against_the_twin(offs):
+    """rows of tests/past_cap.py's pattern over one-byte tokens, the character unit, against the host twin"""
+    torch = _torch()
+    nat, (vf, vo) = _byte_model()
+    ids = (np.arange(int(offs[-1]), dtype=np.uint64) * 7 % 256).astype(np.uint32)
+    want = _lib.spans_host(vf, vo, 256, np.zeros(0, np.uint8), np.zeros(1, np.uint64), 0, ids, offs, unit="char", dtype=np.int32)
+    assert want.shape == (int(offs[-1]), 2)
+    res = _lib.NativeResult.from_ids(ids, offs, 256)
+    try:
+        got = tensors.to_spans(res, nat, unit="char", dtype=torch.int32).cpu().numpy()
+    finally:
+        res.free()
+    assert np.array_equal(got, want)
+
+
+def test_the_second_trip_of_the_strided_tile_loop():
+    """T = 2048 tiles + one tile + 1 tokens: blocks 0 and 1 of span_flat_kernel take a second tile"""
+    offs = past_cap.offsets(2048, 1024)
+    assert int(offs[-1]) == past_cap.n_out(2048, 1024)
+    _pattern_rows_against_the_twin(offs)
+
+
+@pytest.mark.parametrize("n_tokens", past_cap.edge_sizes(4, 1024))
+def test_outputs_that_end_at_the_edges_of_a_slot_and_a_tile(n_tokens):
+    """T = 0, 1, a thread's slot of 4 pairs and the tile of 1024, each less one, full and one over"""
+    _pattern_rows_against_the_twin(past_cap.edge_offsets(n_tokens))

@@ -18,6 +18,7 @@ import tokengeex_amd as tgx
 from tokengeex_amd import _lib, synth, tensors
 
 import layout_checker as lc
+import past_cap
 import spans_checker as sc
 import windows_checker as wc
 
@@ -441,3 +442,35 @@ def test_tokenizer_overflowing_tokens():
     with pytest.raises(tgx.TokenGeeXError) as err:
         tk.encode_batch_padded(texts, pad=pad, bos=bos, max_length=16, stride=15, return_overflowing_tokens=True)
     assert err.value.status == _lib.ERR_INVALID
+
+
+def _pattern_rows_against_the_twin(lens, n_out):
+    """Rows of tests/past_cap.py's pattern as windows of L = 1, so that a window is a token and W·L = n_out can be any
+    number; an empty row has one window of padding; against the host twin"""
+    offs = np.concatenate([np.zeros(1, np.uint64), np.cumsum(lens, dtype=np.uint64)])
+    ids = (np.arange(int(offs[-1]), dtype=np.uint64) * 7 % 1000).astype(np.uint32)
+    want = _lib.layout_windows_host(ids, offs, 1, 0, PAD)
+    assert want["input_ids"].shape == (n_out, 1)
+    res = _lib.NativeResult.from_ids(ids, offs, 1000)
+    try:
+        got = _run(res, 1, 0, None, None, "right", "right", np.int32)
+    finally:
+        res.free()
+    for g, name in zip(got, ("input_ids", "attention_mask", "lengths", "overflow_to_sample_mapping", "window_first")):
+        assert np.array_equal(g, want[name]), name
+
+
+def test_the_second_trip_of_the_strided_tile_loop():
+    """W·L = 2048 tiles + one tile + 1 elements (the number is prime, so L = 1): blocks 0 and 1 of layout_window_kernel take
+    a second tile.  The pattern's rows of 0 and 1 tokens are all one window wide, so the rows' windows sum to the
+    pattern's total when the long row gives up its empty rows' share"""
+    lens = past_cap.lengths(2048, 1024)
+    lens[int(np.argmax(lens))] -= np.uint64(int((lens == 0).sum()))   # every empty row adds a window of padding
+    _pattern_rows_against_the_twin(lens, past_cap.n_out(2048, 1024))
+
+
+@pytest.mark.parametrize("n_out", past_cap.edge_sizes(4, 1024))
+def test_outputs_that_end_at_the_edges_of_a_slot_and_a_tile(n_out):
+    """W·L = 0 (no row), 1, a thread's slot of 4 elements and the tile of 1024, each less one, full and one over: as many
+    rows of 0 and 1 tokens, one window each"""
+    _pattern_rows_against_the_twin(past_cap.edge_rows(n_out), n_out)

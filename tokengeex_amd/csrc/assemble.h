@@ -9,6 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "tile_fill.h"
+
 namespace tgx {
 
 constexpr uint32_t kAssembleGroup = 4;    // consecutive positions of a thread slot: one 16-byte store
@@ -20,20 +22,8 @@ __host__ __device__ inline uint64_t assemble_seg_start(const uint64_t* offs, con
     return offs[r] + (k - r);
 }
 
-// The segment that owns position j: the LARGEST k in [lo, hi] with D_k <= j, so a run of segments with equal D (encoded
-// segments without ids) is stepped over and its last one, the one with D_{k+1} > j, is found.  Needs D_lo <= j and the
-// owner to be <= hi.  (pack_find_row of layout.h over an array of starts.)
-__host__ __device__ inline uint64_t assemble_find_seg(const uint64_t* D, uint64_t lo, uint64_t hi, uint64_t j) {
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo + 1) / 2;
-        if (D[mid] <= j)
-            lo = mid;
-        else
-            hi = mid - 1;
-    }
-    return lo;
-}
-
+// The segment that owns position j is the LARGEST k with D_k <= j (pack_find_row of tile_fill.h over D with A = 0), so a run
+// of segments with equal D (encoded segments without ids) is stepped over.
 // A walk over ascending positions that all lie between the positions owned by segments lo and hi (a tile's first and
 // last): the first position searches [lo, hi], a later one stays on its segment until the next one's start and then
 // searches from the segment after it.  What does not change inside a segment is read once per segment.
@@ -48,7 +38,7 @@ struct AssembleCursor {
 __host__ __device__ inline uint32_t assemble_at(AssembleCursor& cur, const uint32_t* ids, const uint64_t* D, const uint64_t* rank,
                                                 const int32_t* seg_special, uint32_t vocab_size, uint64_t lo, uint64_t hi, uint64_t j) {
     if (!cur.have || j >= cur.next) {
-        cur.k = assemble_find_seg(D, cur.have ? cur.k + 1 : lo, hi, j);
+        cur.k = pack_find_row(D, 0, cur.have ? cur.k + 1 : lo, hi, j);
         cur.next = D[cur.k + 1];
         cur.special = seg_special[cur.k];
         cur.shift = cur.special < 0 ? cur.k - rank[cur.k] : 0;
@@ -66,11 +56,6 @@ __host__ __device__ inline void assemble_group(const uint32_t* ids, const uint64
 #pragma unroll
     for (uint32_t q = 0; q < kAssembleGroup; q++)
         if (q < n_in) v[q] = assemble_at(cur, ids, D, rank, seg_special, vocab_size, lo, hi, e0 + q);
-}
-
-// the last position of the tile that starts at t0 (t0 < n_out)
-__host__ __device__ inline uint64_t assemble_tile_last(uint64_t t0, uint64_t n_out) {
-    return t0 + kAssembleTile - 1 < n_out ? t0 + kAssembleTile - 1 : n_out - 1;
 }
 
 }  // namespace tgx

@@ -1,7 +1,7 @@
 // A sample-level result put together on the device from the result over the non-special segments and the split plan
 // (include/tgx.h: tgx_assemble_result; assemble.h has the index arithmetic).  Three steps: the ranks r_k of the segments
 // (a device-wide exclusive scan of "segment k is encoded", rocPRIM, as the scan of the encode pass's token counts), the
-// segment starts D_k with the samples' offsets, and the fill.  The fill is output-centric like layout_pack_kernel: a tile of
+// segment starts D_k with the samples' offsets, and the fill.  The fill is the tiled fill of DESIGN.md, section L.9, in a copy of its own (tile_fill.h's template measured slower here): a tile of
 // 1024 consecutive output positions per block, the owners of the tile's ends found by two threads over all of D, every
 // thread then walking its four positions between those two and writing them with one 16-byte store.  A special segment
 // is one position and a long sample's segment thousands, so no unit of work is a segment.
@@ -35,6 +35,7 @@ __global__ __launch_bounds__(kAssembleBlock) void assemble_starts_kernel(Assembl
     }
 }
 
+// (tile_fill.h's loop, written out: profiles/tile_fill)
 __global__ __launch_bounds__(kAssembleBlock) void assemble_fill_kernel(AssembleParams p) {
     __shared__ uint64_t s_seg[2];
     const uint64_t n_out = p.n_out;
@@ -42,7 +43,7 @@ __global__ __launch_bounds__(kAssembleBlock) void assemble_fill_kernel(AssembleP
     const uint64_t n_tiles = (n_out + kAssembleTile - 1) / kAssembleTile;
     for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const uint64_t t0 = tile * kAssembleTile;
-        if (threadIdx.x < 2) s_seg[threadIdx.x] = assemble_find_seg(p.starts, 0, p.n_segs - 1, threadIdx.x ? assemble_tile_last(t0, n_out) : t0);
+        if (threadIdx.x < 2) s_seg[threadIdx.x] = pack_find_row(p.starts, 0, 0, p.n_segs - 1, threadIdx.x ? tile_last(t0, kAssembleTile, n_out) : t0);
         __syncthreads();
         const uint64_t e0 = t0 + (uint64_t)threadIdx.x * kAssembleGroup;
         if (e0 < n_out) {
@@ -58,8 +59,6 @@ __global__ __launch_bounds__(kAssembleBlock) void assemble_fill_kernel(AssembleP
         __syncthreads();  // s_seg is rewritten for the next tile
     }
 }
-
-uint32_t capped_grid(uint64_t blocks) { return (uint32_t)(blocks < kAssembleMaxBlocks ? (blocks ? blocks : 1) : kAssembleMaxBlocks); }
 
 }  // namespace
 
@@ -80,14 +79,14 @@ hipError_t launch_assemble_ranks(int32_t* seg_special, uint64_t* rank, uint64_t 
 
 hipError_t launch_assemble_starts(const AssembleParams& p, hipStream_t stream) {
     const uint64_t n = (p.n_segs > p.n_samples ? p.n_segs : p.n_samples) + 1;
-    hipLaunchKernelGGL(assemble_starts_kernel, dim3(capped_grid((n + kAssembleBlock - 1) / kAssembleBlock)), dim3(kAssembleBlock), 0, stream, p);
+    hipLaunchKernelGGL(assemble_starts_kernel, dim3(grid_for(n, kAssembleBlock, kAssembleMaxBlocks)), dim3(kAssembleBlock), 0, stream, p);
     return hipGetLastError();
 }
 
 hipError_t launch_assemble_fill(const AssembleParams& p, hipStream_t stream) {
     if (p.n_out == 0) return hipSuccess;
     if (p.n_segs == 0 || (reinterpret_cast<uintptr_t>(p.out_ids) & 15u)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(assemble_fill_kernel, dim3(capped_grid((p.n_out + kAssembleTile - 1) / kAssembleTile)), dim3(kAssembleBlock), 0, stream, p);
+    hipLaunchKernelGGL(assemble_fill_kernel, dim3(grid_for(p.n_out, kAssembleTile, kAssembleMaxBlocks)), dim3(kAssembleBlock), 0, stream, p);
     return hipGetLastError();
 }
 

@@ -404,11 +404,9 @@ tgx_status tgx_corpus_select(tgx_corpus* c, const int64_t* rows, uint64_t n_sele
     p.n_src = S;
     p.n_rows = M;
     if (on_device && M) {  // the device's check and scan; the M + 1 offsets visit the host, which corpus_create needs anyway
-        size_t scan_bytes = 0;
-        if (tgx::select_scan_temp_bytes(M, &scan_bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan temp-size query failed");
-        void* d_scan = nullptr;
+        ScanScratch scan;
         unsigned long long* d_bad = nullptr;
-        HIP_TRY(guard.alloc(scan_bytes, &d_scan));  // (never NULL: that asks the scan for its size)
+        if ((st = scan_room(&scan, guard, tgx::select_scan_temp_bytes, M)) != TGX_OK) return st;
         HIP_TRY(guard.alloc(sizeof(unsigned long long), &d_bad));
         HIP_TRY(guard.alloc((size_t)(M + 1) * 8, &p.out_offs));
         HIP_TRY(hipMemsetAsync(d_bad, 0xFF, sizeof(unsigned long long), hs));
@@ -416,7 +414,7 @@ tgx_status tgx_corpus_select(tgx_corpus* c, const int64_t* rows, uint64_t n_sele
         if (tgx::launch_select_check(p, d_bad, hs) != hipSuccess) return fail(TGX_ERR_DEVICE, "select_check_kernel launch failed");
         timer.end(0);
         timer.begin(1);
-        if (tgx::launch_select_offsets(p, d_scan, scan_bytes, hs) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan launch failed");
+        if (tgx::launch_select_offsets(p, scan.ptr, scan.bytes, hs) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan launch failed");
         timer.end(1);
         HIP_TRY(hipMemcpyAsync(&h_bad, d_bad, sizeof(unsigned long long), hipMemcpyDeviceToHost, hs));
         if ((st = read_u64(hs, p.out_offs, h_out_offs.data(), (size_t)(M + 1))) != TGX_OK) return st;

@@ -13,6 +13,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "tile_fill.h"
+
 namespace tgx {
 
 constexpr uint32_t kDecodeGroup = 16;    // consecutive raw bytes of a thread slot: one 16-byte store
@@ -80,30 +82,17 @@ __host__ __device__ inline uint32_t decode_meta(const DecodeTables& t, int64_t x
 // the first element of row i <= S
 __host__ __device__ inline uint64_t decode_row_first(const DecodeSrc& s, uint64_t i) { return s.offs ? s.offs[i] : i * s.row_len; }
 
-// The element that owns raw byte b: the LARGEST j in [lo, hi] with B[j] <= b, so elements without bytes are stepped
-// over.  Needs B[lo] <= b and the owner to be <= hi.  (assemble_find_seg of assemble.h.)
-__host__ __device__ inline uint64_t decode_find(const uint64_t* B, uint64_t lo, uint64_t hi, uint64_t b) {
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo + 1) / 2;
-        if (B[mid] <= b)
-            lo = mid;
-        else
-            hi = mid - 1;
-    }
-    return lo;
-}
+// The element that owns raw byte b is the LARGEST j with B[j] <= b (pack_find_row of tile_fill.h over B with A = 0), so
+// elements without bytes are stepped over.
 
 // the owner of byte b >= B[j+1], which is the next element whenever that one has bytes
 __host__ __device__ inline uint64_t decode_step(const uint64_t* B, uint64_t j, uint64_t hi, uint64_t b) {
-    return B[j + 2] > b ? j + 1 : decode_find(B, j + 2, hi, b);
+    return B[j + 2] > b ? j + 1 : pack_find_row(B, 0, j + 2, hi, b);
 }
 
-// the first and last raw byte whose owners bound the searches of the tile that starts at t0 < n_raw: the byte before the
-// tile belongs to it, because a slot asks who owns the byte before its first one
-__host__ __device__ inline uint64_t decode_tile_first(uint64_t t0) { return t0 ? t0 - 1 : 0; }
-__host__ __device__ inline uint64_t decode_tile_last(uint64_t t0, uint64_t n_raw) {
-    return t0 + kDecodeTile - 1 < n_raw ? t0 + kDecodeTile - 1 : n_raw - 1;
-}
+// The owners that bound the searches of a tile are those of the byte before it and of its last byte (tile_first with
+// kDecodeBack, tile_last): a slot asks who owns the byte before its first one.
+constexpr uint32_t kDecodeBack = 1;
 
 // the element a slot's walk stands on
 struct DecodeCursor {
@@ -139,14 +128,14 @@ __host__ __device__ inline uint8_t decode_byte(const DecodeCursor& c, uint64_t b
 }
 
 // A thread slot's walk: v[q] = raw byte e0 + q for q < n_in <= kDecodeGroup -> the slot's flag word.  lo / hi: the owners
-// of decode_tile_first / decode_tile_last of the slot's tile.
+// of tile_first (kDecodeBack) / tile_last of the slot's tile.
 __host__ __device__ inline uint32_t decode_group(const DecodeTables& t, const DecodeSrc& s, const uint64_t* B, const uint64_t* X, uint64_t lo,
                                                  uint64_t hi, uint64_t e0, uint32_t n_in, uint8_t (&v)[kDecodeGroup]) {
     DecodeCursor c;
-    decode_enter(c, t, s, B, X, decode_find(B, lo, hi, e0));
+    decode_enter(c, t, s, B, X, pack_find_row(B, 0, lo, hi, e0));
     // X of the owner of the byte before the one looked at: a special in between (or that owner itself) ends a run
     uint64_t xprev = c.x;
-    if (X && e0 == c.start && e0 > 0) xprev = X[decode_find(B, lo, c.j - 1, e0 - 1)];
+    if (X && e0 == c.start && e0 > 0) xprev = X[pack_find_row(B, 0, lo, c.j - 1, e0 - 1)];
     uint32_t flags = 0;
 #pragma unroll
     for (uint32_t q = 0; q < kDecodeGroup; q++) {

@@ -1,7 +1,7 @@
 // Ids in HBM decoded to UTF-8 text in HBM (include/tgx.h: tgx_decode_result, tgx_decode_padded; decode.h has the index
 // arithmetic).  The meta kernel gives every element its raw length and class and takes the out-of-bounds atomicMin; two
 // device-wide exclusive scans (rocPRIM, as the scan of the assembly's ranks) turn them into byte starts B and special
-// counts X.  The fill is output-centric like assemble_fill_kernel: a tile of 4096 consecutive raw bytes per block, the
+// counts X.  The fill is the tiled fill of tile_fill.h: a tile of 4096 consecutive raw bytes per block, the
 // owners of the tile's ends found by two threads over all of B, every thread then walking the few elements that cover its
 // 16 bytes and writing them with one 16-byte store.  A token of up to 16 bytes is one 16-byte load from its slot, so no
 // unit of work is a token (4-byte tokens would make 4-byte unaligned stores).  The UTF-8 kernel applies from_utf8_lossy
@@ -60,20 +60,12 @@ __global__ __launch_bounds__(kDecodeBlock) void decode_meta_kernel(DecodeParams 
 }
 
 __global__ __launch_bounds__(kDecodeBlock) void decode_fill_kernel(DecodeParams p) {
-    __shared__ uint64_t s_own[2];
-    const uint64_t n_raw = p.n_raw;
-    const uint64_t n_tiles = (n_raw + kDecodeTile - 1) / kDecodeTile;
-    for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const uint64_t t0 = tile * kDecodeTile;
-        if (threadIdx.x < 2)
-            s_own[threadIdx.x] = decode_find(p.starts, 0, p.src.n - 1, threadIdx.x ? decode_tile_last(t0, n_raw) : decode_tile_first(t0));
-        __syncthreads();
-        const uint64_t e0 = t0 + (uint64_t)threadIdx.x * kDecodeGroup;
-        if (e0 < n_raw) {
-            const uint32_t n_in = n_raw - e0 < kDecodeGroup ? (uint32_t)(n_raw - e0) : kDecodeGroup;
+    tiled_fill<kDecodeTile, kDecodeGroup, kDecodeBack>(
+        p.n_raw, p.n_raw, [p](uint64_t b) { return pack_find_row(p.starts, 0, 0, p.src.n - 1, b); },
+        [p](uint64_t lo, uint64_t hi, uint64_t e0, uint32_t n_in) {
             uint8_t v[kDecodeGroup] = {};
-            const uint32_t flags = decode_group(p.tab, p.src, p.starts, p.specials, s_own[0], s_own[1], e0, n_in, v);
-            uint32_t w[4];
+            const uint32_t flags = decode_group(p.tab, p.src, p.starts, p.specials, lo, hi, e0, n_in, v);
+            uint32_t w[4];  // (not store_bytes16: with it the kernel loses a wave of occupancy, profiles/tile_fill/README.md)
 #pragma unroll
             for (uint32_t k = 0; k < 4; k++)
                 w[k] = (uint32_t)v[4 * k] | ((uint32_t)v[4 * k + 1] << 8) | ((uint32_t)v[4 * k + 2] << 16) | ((uint32_t)v[4 * k + 3] << 24);
@@ -83,9 +75,7 @@ __global__ __launch_bounds__(kDecodeBlock) void decode_fill_kernel(DecodeParams 
                 for (uint32_t q = 0; q < n_in; q++) p.raw[e0 + q] = v[q];
             }
             p.flags[e0 / kDecodeGroup] = flags;
-        }
-        __syncthreads();  // s_own is rewritten for the next tile
-    }
+        });
 }
 
 // row_offs[0..S] = the rows' raw starts; after the fill: every row start starts a run
@@ -128,9 +118,6 @@ __global__ __launch_bounds__(kDecodeBlock) void decode_final_rows_kernel(DecodeP
         p.row_offs[i] = decode_final_pos(p.gpos, p.codes, p.row_offs[i], p.n_raw);
 }
 
-uint32_t capped_grid(uint64_t blocks) { return (uint32_t)(blocks < kDecodeMaxBlocks ? (blocks ? blocks : 1) : kDecodeMaxBlocks); }
-uint32_t grid_for(uint64_t slots) { return capped_grid((slots + kDecodeBlock - 1) / kDecodeBlock); }
-
 }  // namespace
 
 hipError_t decode_scan_temp_bytes(uint64_t n, size_t* bytes) {
@@ -144,7 +131,7 @@ hipError_t launch_decode_meta(const DecodeParams& p, void* temp, size_t temp_byt
     const uint64_t n = p.src.n;
     hipError_t e = hipMemsetAsync(p.meta + n, 0, 4, stream);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(decode_meta_kernel, dim3(grid_for(n)), dim3(kDecodeBlock), 0, stream, p);
+    hipLaunchKernelGGL(decode_meta_kernel, dim3(grid_for(n, kDecodeBlock, kDecodeMaxBlocks)), dim3(kDecodeBlock), 0, stream, p);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     auto len = rocprim::make_transform_iterator((const uint32_t*)p.meta, MetaLen());
     return rocprim::exclusive_scan(temp, temp_bytes, len, p.starts, (uint64_t)0, (size_t)(n + 1), rocprim::plus<uint64_t>(), stream);
@@ -158,18 +145,18 @@ hipError_t launch_decode_specials(const DecodeParams& p, void* temp, size_t temp
 
 hipError_t launch_decode_fill(const DecodeParams& p, hipStream_t stream) {
     if (p.n_raw == 0 || p.src.n == 0 || (reinterpret_cast<uintptr_t>(p.raw) & 15u)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(decode_fill_kernel, dim3(capped_grid((p.n_raw + kDecodeTile - 1) / kDecodeTile)), dim3(kDecodeBlock), 0, stream, p);
+    hipLaunchKernelGGL(decode_fill_kernel, dim3(grid_for(p.n_raw, kDecodeTile, kDecodeMaxBlocks)), dim3(kDecodeBlock), 0, stream, p);
     return hipGetLastError();
 }
 
 hipError_t launch_decode_rows(const DecodeParams& p, hipStream_t stream) {
-    hipLaunchKernelGGL(decode_rows_kernel, dim3(grid_for(p.src.n_rows + 1)), dim3(kDecodeBlock), 0, stream, p);
+    hipLaunchKernelGGL(decode_rows_kernel, dim3(grid_for(p.src.n_rows + 1, kDecodeBlock, kDecodeMaxBlocks)), dim3(kDecodeBlock), 0, stream, p);
     return hipGetLastError();
 }
 
 hipError_t launch_decode_utf8(const DecodeParams& p, hipStream_t stream) {
     if (p.n_raw == 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(decode_utf8_kernel, dim3(grid_for((p.n_raw + kDecodeGroup - 1) / kDecodeGroup)), dim3(kDecodeBlock), 0, stream, p);
+    hipLaunchKernelGGL(decode_utf8_kernel, dim3(grid_for((p.n_raw + kDecodeGroup - 1) / kDecodeGroup, kDecodeBlock, kDecodeMaxBlocks)), dim3(kDecodeBlock), 0, stream, p);
     return hipGetLastError();
 }
 
@@ -189,10 +176,10 @@ hipError_t launch_decode_positions(const DecodeParams& p, void* temp, size_t tem
 }
 
 hipError_t launch_decode_expand(const DecodeParams& p, hipStream_t stream) {
-    hipLaunchKernelGGL(decode_expand_kernel, dim3(grid_for((p.n_raw + kDecodeGroup - 1) / kDecodeGroup)), dim3(kDecodeBlock), 0, stream, p);
+    hipLaunchKernelGGL(decode_expand_kernel, dim3(grid_for((p.n_raw + kDecodeGroup - 1) / kDecodeGroup, kDecodeBlock, kDecodeMaxBlocks)), dim3(kDecodeBlock), 0, stream, p);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(decode_final_rows_kernel, dim3(grid_for(p.src.n_rows + 1)), dim3(kDecodeBlock), 0, stream, p);
+    hipLaunchKernelGGL(decode_final_rows_kernel, dim3(grid_for(p.src.n_rows + 1, kDecodeBlock, kDecodeMaxBlocks)), dim3(kDecodeBlock), 0, stream, p);
     return hipGetLastError();
 }
 

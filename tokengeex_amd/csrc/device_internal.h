@@ -409,14 +409,17 @@ int stage_times(const char* const* stage_names, const float* stage_ms, int n, co
 // and declared before its guard: after a failure the copy may still write them until the guard has synchronised.
 tgx_status read_u64(hipStream_t hs, const void* d_src, void* host_words, size_t n = 1);
 
-// A call's scratch for scans of up to n elements, in pooled memory of its guard: asked for again only when n exceeds
-// what is known so far.  temp_bytes: the subsystem's size query.
+// A call's scratch for scans of up to n elements, in pooled memory of its guard (a StreamGuard or a Pass): asked for again
+// only when n exceeds what is known so far.  temp_bytes: the subsystem's size query.  After TGX_OK ptr is never NULL, which
+// would ask a scan for its size, whatever n is.  oom: the error's text when the allocation fails, for the calls that
+// report "out of device memory (...)" (default: the HIP error's).
 struct ScanScratch {
     void* ptr = nullptr;
     size_t bytes = 0;
     uint64_t n = 0;
 };
-tgx_status scan_room(ScanScratch* s, StreamGuard& guard, hipError_t (*temp_bytes)(uint64_t, size_t*), uint64_t n);
+tgx_status scan_room(ScanScratch* s, StreamGuard& guard, hipError_t (*temp_bytes)(uint64_t, size_t*), uint64_t n, const char* oom = nullptr);
+tgx_status scan_room(ScanScratch* s, Pass& pass, hipError_t (*temp_bytes)(uint64_t, size_t*), uint64_t n, const char* oom = nullptr);
 
 // ---- row selection (result_ops.cpp; tgx_corpus_select in corpus_ops.cpp shares it) ------------------------------------
 // device time of the calling thread's last select per stage (tgx_select_last_times)

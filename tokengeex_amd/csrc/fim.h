@@ -132,9 +132,4 @@ __host__ __device__ inline void fim_group(const FimArgs& f, const uint32_t* ids,
         if (q < n_in) v[q] = fim_at(cur, f, ids, offs, out_offs, lo, hi, e0 + q);
 }
 
-// the last position of the tile that starts at t0 (t0 < n_out)
-__host__ __device__ inline uint64_t fim_tile_last(uint64_t t0, uint64_t n_out) {
-    return t0 + kFimTile - 1 < n_out ? t0 + kFimTile - 1 : n_out - 1;
-}
-
 }  // namespace tgx

@@ -18,6 +18,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "tile_fill.h"
+
 namespace tgx {
 
 constexpr uint32_t kFrontGroup = 16;    // consecutive bytes of a thread slot: one 16-byte load
@@ -44,20 +46,8 @@ __host__ __device__ inline uint32_t front_has_byte(uint32_t w, uint32_t b) {
     return (z - 0x01010101u) & ~z & 0x80808080u;
 }
 
-// The sample that owns byte p < N: the LARGEST i in [lo, hi] with offs[i] <= p, so empty samples are stepped over.
-__host__ __device__ inline uint64_t front_find_sample(const uint64_t* offs, uint64_t lo, uint64_t hi, uint64_t p) {
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo + 1) / 2;
-        if (offs[mid] <= p)
-            lo = mid;
-        else
-            hi = mid - 1;
-    }
-    return lo;
-}
-
-// the last byte of the tile that starts at t0 (t0 < n)
-__host__ __device__ inline uint64_t front_tile_last(uint64_t t0, uint64_t n) { return t0 + kFrontTile - 1 < n ? t0 + kFrontTile - 1 : n - 1; }
+// The sample that owns byte p < N is the LARGEST i with offs[i] <= p (pack_find_row of tile_fill.h with A = 0), so empty
+// samples are stepped over; a tile's last byte is tile_last(t0, kFrontTile, n).
 
 // a walk over ascending bytes of one tile, whose first and last byte belong to samples lo and hi
 struct FrontCursor {
@@ -66,7 +56,7 @@ struct FrontCursor {
 };
 __host__ __device__ inline void front_advance(FrontCursor& cur, const uint64_t* offs, uint64_t lo, uint64_t hi, uint64_t p) {
     if (cur.have && p < cur.end) return;
-    cur.i = front_find_sample(offs, cur.have ? cur.i + 1 : lo, hi, p);
+    cur.i = pack_find_row(offs, 0, cur.have ? cur.i + 1 : lo, hi, p);
     cur.end = offs[cur.i + 1];
     cur.have = true;
 }

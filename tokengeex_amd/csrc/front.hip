@@ -7,11 +7,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <rocprim/device/device_scan.hpp>
-#include <rocprim/iterator/transform_iterator.hpp>
-
 #include "front.h"
 #include "kernels.h"
+#include "scan_helpers.h"
 
 namespace tgx {
 
@@ -25,37 +23,6 @@ struct Widen {
     __host__ __device__ uint64_t operator()(uint32_t v) const { return v; }
 };
 
-// exclusive sums of v over the block's threads in thread order; *total: the block's sum.  part: u32[kFrontBlock / 64] of LDS
-__device__ inline uint32_t block_exclusive_sum(uint32_t v, uint32_t* part, uint32_t* total) {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t incl = v;
-#pragma unroll
-    for (uint32_t off = 1; off < 64; off <<= 1) {
-        const uint32_t y = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += y;
-    }
-    if (lane == 63) part[wave] = incl;
-    __syncthreads();
-    uint32_t base = 0, all = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < kFrontBlock / 64; w++) {
-        const uint32_t s = part[w];
-        if (w < wave) base += s;
-        all += s;
-    }
-    __syncthreads();  // part is rewritten by the next call
-    *total = all;
-    return base + incl - v;
-}
-
-// the slot's 16 bytes with one load (text is 16-byte aligned and readable to the end of the slot)
-__device__ inline void load_slot(const uint8_t* text, uint64_t p0, uint8_t (&v)[kFrontGroup]) {
-    const uint4 w = *reinterpret_cast<const uint4*>(text + p0);
-    const uint32_t x[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-    for (uint32_t q = 0; q < kFrontGroup; q++) v[q] = (uint8_t)(x[q >> 2] >> (8 * (q & 3)));
-}
-
 __global__ __launch_bounds__(kFrontBlock) void front_mark_kernel(FrontParams p) {
     __shared__ uint32_t s_mask[8];
     __shared__ uint64_t s_row[2];
@@ -66,7 +33,7 @@ __global__ __launch_bounds__(kFrontBlock) void front_mark_kernel(FrontParams p) 
     const uint64_t n = p.n_bytes, n_tiles = (n + kFrontTile - 1) / kFrontTile;
     for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const uint64_t t0 = tile * kFrontTile;
-        if (threadIdx.x < 2) s_row[threadIdx.x] = front_find_sample(p.offs, 0, p.n_samples - 1, threadIdx.x ? front_tile_last(t0, n) : t0);
+        if (threadIdx.x < 2) s_row[threadIdx.x] = pack_find_row(p.offs, 0, 0, p.n_samples - 1, threadIdx.x ? tile_last(t0, kFrontTile, n) : t0);
         __syncthreads();
         const uint64_t p0 = t0 + (uint64_t)threadIdx.x * kFrontGroup;
         uint32_t hits = 0;
@@ -81,7 +48,7 @@ __global__ __launch_bounds__(kFrontBlock) void front_mark_kernel(FrontParams p) 
             p.crlf_mask[p0 / kFrontGroup] = (uint16_t)cr;
         }
         uint32_t total;
-        block_exclusive_sum(front_popc(hits), s_part, &total);  // (its barriers also keep s_row for the whole tile)
+        block_exclusive_sum<kFrontBlock>(front_popc(hits), s_part, &total);  // (its barriers also keep s_row for the whole tile)
         if (threadIdx.x == 0) p.tile_count[tile] = total;
     }
 }
@@ -98,12 +65,12 @@ __global__ __launch_bounds__(kFrontBlock) void front_candidates_kernel(FrontPara
         const uint64_t base = p.tile_base[tile];
         if (p.tile_base[tile + 1] == base) continue;  // (the whole block takes the same way)
         const uint64_t t0 = tile * kFrontTile;
-        if (threadIdx.x < 2) s_row[threadIdx.x] = front_find_sample(p.offs, 0, p.n_samples - 1, threadIdx.x ? front_tile_last(t0, n) : t0);
+        if (threadIdx.x < 2) s_row[threadIdx.x] = pack_find_row(p.offs, 0, 0, p.n_samples - 1, threadIdx.x ? tile_last(t0, kFrontTile, n) : t0);
         __syncthreads();
         const uint64_t p0 = t0 + (uint64_t)threadIdx.x * kFrontGroup;
         const uint32_t hits = p0 < n ? p.hit_mask[p0 / kFrontGroup] : 0u;
         uint32_t total;
-        const uint32_t before = block_exclusive_sum(front_popc(hits), s_part, &total);
+        const uint32_t before = block_exclusive_sum<kFrontBlock>(front_popc(hits), s_part, &total);
         if (hits)
             front_write_slot(tab, p.text, p.offs, s_row[0], s_row[1], p0, hits, base + before, p.cand_pos, p.cand_end, p.cand_special, p.cand_sample);
         __syncthreads();  // s_row is rewritten for the next tile
@@ -176,7 +143,7 @@ __global__ __launch_bounds__(kFrontBlock) void front_keep_kernel(FrontParams p) 
     const uint64_t n = p.n_bytes, n_tiles = (n + kFrontTile - 1) / kFrontTile;
     for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const uint64_t t0 = tile * kFrontTile;
-        if (threadIdx.x < 2) s_enc[threadIdx.x] = front_first_enc(p.enc_end, 0, p.n_enc, threadIdx.x ? front_tile_last(t0, n) : t0);
+        if (threadIdx.x < 2) s_enc[threadIdx.x] = front_first_enc(p.enc_end, 0, p.n_enc, threadIdx.x ? tile_last(t0, kFrontTile, n) : t0);
         __syncthreads();
         const uint64_t p0 = t0 + (uint64_t)threadIdx.x * kFrontGroup;
         uint32_t keep = 0, begins = 0;
@@ -187,7 +154,7 @@ __global__ __launch_bounds__(kFrontBlock) void front_keep_kernel(FrontParams p) 
             p.keep_mask[p0 / kFrontGroup] = (uint16_t)keep;
         }
         uint32_t total;
-        const uint32_t before = block_exclusive_sum(front_popc(keep), s_part, &total);  // (its barriers also keep s_enc for the whole tile)
+        const uint32_t before = block_exclusive_sum<kFrontBlock>(front_popc(keep), s_part, &total);  // (its barriers also keep s_enc for the whole tile)
         if (begins) front_slot_begins(keep, begins, first_begin, before, p.enc_local);
         if (threadIdx.x == 0) p.tile_count[tile] = total;
     }
@@ -210,7 +177,7 @@ __global__ __launch_bounds__(kFrontBlock) void front_pack_kernel(FrontParams p) 
         const uint64_t p0 = tile * kFrontTile + (uint64_t)threadIdx.x * kFrontGroup;
         const uint32_t keep = p0 < n ? p.keep_mask[p0 / kFrontGroup] : 0u;
         uint32_t total;
-        uint64_t at = base + block_exclusive_sum(front_popc(keep), s_part, &total);
+        uint64_t at = base + block_exclusive_sum<kFrontBlock>(front_popc(keep), s_part, &total);
         if (!keep) continue;  // (after the block's barriers)
         uint8_t v[kFrontGroup];
         load_slot(p.text, p0, v);
@@ -220,13 +187,8 @@ __global__ __launch_bounds__(kFrontBlock) void front_pack_kernel(FrontParams p) 
     }
 }
 
-uint32_t capped_grid(uint64_t blocks) { return (uint32_t)(blocks < kFrontMaxBlocks ? (blocks ? blocks : 1) : kFrontMaxBlocks); }
-uint32_t grid_for(uint64_t slots) { return capped_grid((slots + kFrontBlock - 1) / kFrontBlock); }
 uint64_t tiles_of(uint64_t n) { return (n + kFrontTile - 1) / kFrontTile; }
 
-hipError_t sum_scan(const uint64_t* in, uint64_t* out, uint64_t n, void* temp, size_t& temp_bytes, hipStream_t stream) {
-    return rocprim::exclusive_scan(temp, temp_bytes, in, out, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), stream);
-}
 hipError_t max_scan(const uint64_t* in, uint64_t* out, uint64_t n, void* temp, size_t& temp_bytes, hipStream_t stream) {
     return rocprim::inclusive_scan(temp, temp_bytes, in, out, (size_t)n, rocprim::maximum<uint64_t>(), stream);
 }
@@ -261,7 +223,7 @@ hipError_t launch_front_mark(const FrontParams& p, void* temp, size_t temp_bytes
     if (p.n_bytes == 0 || p.n_samples == 0 || (reinterpret_cast<uintptr_t>(p.text) & 15u)) return hipErrorInvalidValue;
     const uint64_t tiles = tiles_of(p.n_bytes);
     FRONT_TRY(hipMemsetAsync(p.tile_count + tiles, 0, 8, stream));
-    hipLaunchKernelGGL(front_mark_kernel, dim3(capped_grid(tiles)), dim3(kFrontBlock), 0, stream, p);
+    hipLaunchKernelGGL(front_mark_kernel, dim3(capped_grid(tiles, kFrontMaxBlocks)), dim3(kFrontBlock), 0, stream, p);
     FRONT_TRY(hipGetLastError());
     return sum_scan(p.tile_count, p.tile_base, tiles + 1, temp, temp_bytes, stream);
 }
@@ -270,17 +232,17 @@ hipError_t launch_front_mark(const FrontParams& p, void* temp, size_t temp_bytes
 hipError_t launch_front_candidates(const FrontParams& p, void* temp, size_t temp_bytes, hipStream_t stream) {
     const uint64_t C = p.n_cand, S = p.n_samples;
     if (C) {
-        hipLaunchKernelGGL(front_candidates_kernel, dim3(capped_grid(tiles_of(p.n_bytes))), dim3(kFrontBlock), 0, stream, p);
+        hipLaunchKernelGGL(front_candidates_kernel, dim3(capped_grid(tiles_of(p.n_bytes), kFrontMaxBlocks)), dim3(kFrontBlock), 0, stream, p);
         FRONT_TRY(hipGetLastError());
         FRONT_TRY(max_scan(p.cand_end, p.pm, C, temp, temp_bytes, stream));
-        hipLaunchKernelGGL(front_resolve_kernel, dim3(grid_for(C)), dim3(kFrontBlock), 0, stream, p);
+        hipLaunchKernelGGL(front_resolve_kernel, dim3(grid_for(C, kFrontBlock, kFrontMaxBlocks)), dim3(kFrontBlock), 0, stream, p);
         FRONT_TRY(hipGetLastError());
         FRONT_TRY(max_scan(p.acc_end, p.la, C, temp, temp_bytes, stream));
     }
-    hipLaunchKernelGGL(front_cand_segs_kernel, dim3(grid_for((C > S ? C : S) + 1)), dim3(kFrontBlock), 0, stream, p);
+    hipLaunchKernelGGL(front_cand_segs_kernel, dim3(grid_for((C > S ? C : S) + 1, kFrontBlock, kFrontMaxBlocks)), dim3(kFrontBlock), 0, stream, p);
     FRONT_TRY(hipGetLastError());
     FRONT_TRY(wide_scan(p.cand_segs, p.seg_sum, C + 1, temp, temp_bytes, stream));
-    hipLaunchKernelGGL(front_sample_segs_kernel, dim3(grid_for(S + 1)), dim3(kFrontBlock), 0, stream, p);
+    hipLaunchKernelGGL(front_sample_segs_kernel, dim3(grid_for(S + 1, kFrontBlock, kFrontMaxBlocks)), dim3(kFrontBlock), 0, stream, p);
     FRONT_TRY(hipGetLastError());
     return sum_scan(p.sample_segs, p.seg_offs, S + 1, temp, temp_bytes, stream);
 }
@@ -288,7 +250,7 @@ hipError_t launch_front_candidates(const FrontParams& p, void* temp, size_t temp
 // seg_begin, seg_end, seg_special[0..K) and rank[0..K]: rank[K] = E.  seg_special has room for K + 1 entries.
 hipError_t launch_front_segments(const FrontParams& p, void* temp, size_t temp_bytes, hipStream_t stream) {
     if (p.n_segs) {
-        hipLaunchKernelGGL(front_segments_kernel, dim3(grid_for(p.n_cand > p.n_samples ? p.n_cand : p.n_samples)), dim3(kFrontBlock), 0, stream, p);
+        hipLaunchKernelGGL(front_segments_kernel, dim3(grid_for(p.n_cand > p.n_samples ? p.n_cand : p.n_samples, kFrontBlock, kFrontMaxBlocks)), dim3(kFrontBlock), 0, stream, p);
         FRONT_TRY(hipGetLastError());
     }
     return launch_assemble_ranks(p.seg_special, p.rank, p.n_segs, temp, temp_bytes, stream);
@@ -298,20 +260,20 @@ hipError_t launch_front_segments(const FrontParams& p, void* temp, size_t temp_b
 hipError_t launch_front_keep(const FrontParams& p, void* temp, size_t temp_bytes, hipStream_t stream) {
     if (p.n_enc == 0) return hipErrorInvalidValue;
     const uint64_t tiles = tiles_of(p.n_bytes);
-    hipLaunchKernelGGL(front_encoded_kernel, dim3(grid_for(p.n_segs)), dim3(kFrontBlock), 0, stream, p);
+    hipLaunchKernelGGL(front_encoded_kernel, dim3(grid_for(p.n_segs, kFrontBlock, kFrontMaxBlocks)), dim3(kFrontBlock), 0, stream, p);
     FRONT_TRY(hipGetLastError());
     FRONT_TRY(hipMemsetAsync(p.tile_count + tiles, 0, 8, stream));
-    hipLaunchKernelGGL(front_keep_kernel, dim3(capped_grid(tiles)), dim3(kFrontBlock), 0, stream, p);
+    hipLaunchKernelGGL(front_keep_kernel, dim3(capped_grid(tiles, kFrontMaxBlocks)), dim3(kFrontBlock), 0, stream, p);
     FRONT_TRY(hipGetLastError());
     FRONT_TRY(sum_scan(p.tile_count, p.tile_base, tiles + 1, temp, temp_bytes, stream));
-    hipLaunchKernelGGL(front_offsets_kernel, dim3(grid_for(p.n_enc + 1)), dim3(kFrontBlock), 0, stream, p);
+    hipLaunchKernelGGL(front_offsets_kernel, dim3(grid_for(p.n_enc + 1, kFrontBlock, kFrontMaxBlocks)), dim3(kFrontBlock), 0, stream, p);
     return hipGetLastError();
 }
 
 // the kept bytes to out[0 .. out_offs[E])
 hipError_t launch_front_pack(const FrontParams& p, hipStream_t stream) {
     if (p.n_enc == 0 || !p.out) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(front_pack_kernel, dim3(capped_grid(tiles_of(p.n_bytes))), dim3(kFrontBlock), 0, stream, p);
+    hipLaunchKernelGGL(front_pack_kernel, dim3(capped_grid(tiles_of(p.n_bytes), kFrontMaxBlocks)), dim3(kFrontBlock), 0, stream, p);
     return hipGetLastError();
 }
 

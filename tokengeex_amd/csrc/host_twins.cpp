@@ -4,6 +4,7 @@
 // argument checks they share with the device entry points of tgx_api.cpp.  A twin goes through the same index arithmetic as its kernels (layout.h, assemble.h,
 // fim.h, select.h, decode.h, spans.h, front.h, norm.h) on host memory.  Nothing in this file calls a HIP function, so it builds and runs without the
 // handles, the pool or a device.
+#define TGX_HOST_ONLY  // tile_fill.h: the host loop, no kernel side
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -286,30 +287,32 @@ tgx_status layout_pad_host(const tgx::LayoutSeq& seq, const uint32_t* ids, const
 template <class T>
 tgx_status layout_pack_host(const tgx::LayoutSeq& seq, const uint32_t* ids, const uint64_t* offs, uint64_t n_rows, uint64_t n_stream,
                             uint64_t n_out, T* out, int32_t* doc, int32_t* pos) {
-    // as the kernel: tiles of kPackTile positions, the owners of a tile's ends bound the search inside it, and a
-    // group of four consecutive positions walks on from row to row
-    uint64_t lo = 0, hi = 0;
-    tgx::PackCursor cur;
-    for (uint64_t j = 0; j < n_out; j++) {
-        uint32_t id = seq.pad;
-        int32_t d = -1, q = 0;
-        if (j % tgx::kPackTile == 0 && j < n_stream) {
-            const uint64_t last = j + tgx::kPackTile - 1 < n_stream ? j + tgx::kPackTile - 1 : n_stream - 1;
-            lo = tgx::pack_find_row(offs, seq.extra, 0, n_rows - 1, j);
-            hi = tgx::pack_find_row(offs, seq.extra, 0, n_rows - 1, last);
-        }
-        if (j % 4 == 0) cur = tgx::PackCursor();
-        if (j < n_stream) {
-            const uint64_t i = tgx::pack_advance(cur, offs, seq.extra, lo, hi, j);
-            id = tgx::pack_at(seq, ids, offs, i, j, &q);
-            d = (int32_t)i;
-            if (id >= 0x80000000u) return fail(TGX_ERR_INVALID, "tgx_layout_pack_host: id %u of row %llu is not below 2^31", id, (unsigned long long)i);
-        }
-        out[j] = (T)id;
-        if (doc) doc[j] = d;
-        if (pos) pos[j] = q;
-    }
-    return TGX_OK;
+    // as the kernel: the tiled fill over the stream's positions, which runs on over the padding of the last block
+    tgx_status st = TGX_OK;
+    tgx::tiled_fill_host(
+        n_out, n_stream, tgx::kPackTile, tgx::kLayoutGroup, 0, [&](uint64_t j) { return tgx::pack_find_row(offs, seq.extra, 0, n_rows - 1, j); },
+        [&](uint64_t lo, uint64_t hi, uint64_t e0, uint32_t n_in) {
+            tgx::PackCursor cur;
+            for (uint32_t k = 0; k < n_in; k++) {
+                const uint64_t j = e0 + k;
+                uint32_t id = seq.pad;
+                int32_t d = -1, q = 0;
+                if (j < n_stream) {
+                    const uint64_t i = tgx::pack_advance(cur, offs, seq.extra, lo, hi, j);
+                    id = tgx::pack_at(seq, ids, offs, i, j, &q);
+                    d = (int32_t)i;
+                    if (id >= 0x80000000u) {
+                        st = fail(TGX_ERR_INVALID, "tgx_layout_pack_host: id %u of row %llu is not below 2^31", id, (unsigned long long)i);
+                        return false;
+                    }
+                }
+                out[j] = (T)id;
+                if (doc) doc[j] = d;
+                if (pos) pos[j] = q;
+            }
+            return true;
+        });
+    return st;
 }
 
 }  // namespace
@@ -369,26 +372,26 @@ template <class T>
 tgx_status layout_windows_host(const tgx::LayoutSeq& seq, const uint32_t* ids, const uint64_t* offs, const uint64_t* wo, uint64_t n_rows,
                                uint64_t n_windows, uint32_t L, uint32_t stride, uint32_t flags, T* out, uint8_t* mask, int32_t* lengths,
                                int32_t* window_row, int32_t* window_first) {
-    // as the kernel: tiles of kPackTile elements of the flat [W, L] output, the owners of a tile's first and last window
-    // bound the search inside it, and groups of kLayoutGroup consecutive elements are walked by win_group
+    // as the kernel: the tiled fill over the elements of the flat [W, L] output, whose owners are the rows of their windows
     const uint64_t total = n_windows * (uint64_t)L;
-    for (uint64_t t0 = 0; t0 < total; t0 += tgx::kPackTile) {
-        const uint64_t last = t0 + tgx::kPackTile - 1 < total ? t0 + tgx::kPackTile - 1 : total - 1;
-        const uint64_t lo = tgx::pack_find_row(wo, 0, 0, n_rows - 1, t0 / L), hi = tgx::pack_find_row(wo, 0, 0, n_rows - 1, last / L);
-        for (uint64_t e0 = t0; e0 <= last; e0 += tgx::kLayoutGroup) {
-            const uint32_t n_in = last + 1 - e0 < tgx::kLayoutGroup ? (uint32_t)(last + 1 - e0) : tgx::kLayoutGroup;
+    tgx_status st = TGX_OK;
+    tgx::tiled_fill_host(
+        total, total, tgx::kPackTile, tgx::kLayoutGroup, 0, [&](uint64_t e) { return tgx::pack_find_row(wo, 0, 0, n_rows - 1, e / L); },
+        [&](uint64_t lo, uint64_t hi, uint64_t e0, uint32_t n_in) {
             uint32_t v[tgx::kLayoutGroup] = {0, 0, 0, 0};
             const uint32_t m = tgx::win_group(seq, ids, offs, wo, L, stride, flags, lo, hi, e0, n_in, lengths, window_row, window_first, v);
             for (uint32_t k = 0; k < n_in; k++) {
-                if (v[k] >= 0x80000000u)
-                    return fail(TGX_ERR_INVALID, "tgx_layout_windows_host: id %u of window %llu is not below 2^31", v[k],
-                                (unsigned long long)((e0 + k) / L));
+                if (v[k] >= 0x80000000u) {
+                    st = fail(TGX_ERR_INVALID, "tgx_layout_windows_host: id %u of window %llu is not below 2^31", v[k],
+                              (unsigned long long)((e0 + k) / L));
+                    return false;
+                }
                 out[e0 + k] = (T)v[k];
                 if (mask) mask[e0 + k] = (uint8_t)(m >> (8 * k));
             }
-        }
-    }
-    return TGX_OK;
+            return true;
+        });
+    return st;
 }
 
 }  // namespace
@@ -443,16 +446,14 @@ tgx_status tgx_assemble_host(const uint32_t* ids, const uint64_t* id_offs, uint6
     }
     for (uint64_t k = 0; k <= K; k++) starts[k] = tgx::assemble_seg_start(id_offs, rank.data(), k);
     for (uint64_t i = 0; i <= n_samples; i++) out_offs[i] = tgx::assemble_seg_start(id_offs, rank.data(), seg_offs[i]);
-    for (uint64_t t0 = 0; t0 < n_out; t0 += tgx::kAssembleTile) {
-        const uint64_t last = tgx::assemble_tile_last(t0, n_out);
-        const uint64_t lo = tgx::assemble_find_seg(starts.data(), 0, K - 1, t0), hi = tgx::assemble_find_seg(starts.data(), 0, K - 1, last);
-        for (uint64_t e0 = t0; e0 <= last; e0 += tgx::kAssembleGroup) {
-            const uint32_t n_in = last + 1 - e0 < tgx::kAssembleGroup ? (uint32_t)(last + 1 - e0) : tgx::kAssembleGroup;
+    tgx::tiled_fill_host(
+        n_out, n_out, tgx::kAssembleTile, tgx::kAssembleGroup, 0, [&](uint64_t j) { return tgx::pack_find_row(starts.data(), 0, 0, K - 1, j); },
+        [&](uint64_t lo, uint64_t hi, uint64_t e0, uint32_t n_in) {
             uint32_t v[tgx::kAssembleGroup] = {0, 0, 0, 0};
             tgx::assemble_group(ids, starts.data(), rank.data(), seg_special, vocab_size, lo, hi, e0, n_in, v);
             for (uint32_t q = 0; q < n_in; q++) out_ids[e0 + q] = v[q];
-        }
-    }
+            return true;
+        });
     return TGX_OK;
 }
 
@@ -476,16 +477,14 @@ tgx_status tgx_fim_host(const uint32_t* ids, const uint64_t* offs, uint64_t n_ro
     out_offs[0] = 0;
     for (uint64_t i = 0; i < n_rows; i++) out_offs[i + 1] = out_offs[i] + tgx::fim_out_len(seed, first_row + i, offs[i + 1] - offs[i], rate);
     const tgx::FimArgs f = {seed, first_row, rate, spm_rate, prefix_id, suffix_id, middle_id};
-    for (uint64_t t0 = 0; t0 < n_out; t0 += tgx::kFimTile) {
-        const uint64_t last = tgx::fim_tile_last(t0, n_out);
-        const uint64_t lo = tgx::pack_find_row(out_offs, 0, 0, n_rows - 1, t0), hi = tgx::pack_find_row(out_offs, 0, 0, n_rows - 1, last);
-        for (uint64_t e0 = t0; e0 <= last; e0 += tgx::kFimGroup) {
-            const uint32_t n_in = last + 1 - e0 < tgx::kFimGroup ? (uint32_t)(last + 1 - e0) : tgx::kFimGroup;
+    tgx::tiled_fill_host(
+        n_out, n_out, tgx::kFimTile, tgx::kFimGroup, 0, [&](uint64_t j) { return tgx::pack_find_row(out_offs, 0, 0, n_rows - 1, j); },
+        [&](uint64_t lo, uint64_t hi, uint64_t e0, uint32_t n_in) {
             uint32_t v[tgx::kFimGroup] = {0, 0, 0, 0};
             tgx::fim_group(f, ids, offs, out_offs, lo, hi, e0, n_in, v);
             for (uint32_t q = 0; q < n_in; q++) out_ids[e0 + q] = v[q];
-        }
-    }
+            return true;
+        });
     for (uint64_t i = 0; i < n_rows && (mode || cuts); i++) {  // as fim_info_kernel
         const tgx::FimRow r = tgx::fim_row(seed, first_row + i, offs[i + 1] - offs[i], rate, spm_rate);
         if (mode) mode[i] = (uint8_t)r.mode;
@@ -526,7 +525,7 @@ tgx_status select_host(const char* who, const char* what, const T* data, const u
                        uint64_t cap, uint64_t* out_offs) {
     constexpr bool kText = sizeof(T) == 1;
     constexpr uint32_t kGroup = kText ? tgx::kSelectByteGroup : tgx::kSelectGroup;
-    constexpr uint64_t kTile = kText ? tgx::kSelectByteTile : tgx::kSelectTile;
+    constexpr uint32_t kTile = kText ? tgx::kSelectByteTile : tgx::kSelectTile;
     if (!out_offs) return fail(TGX_ERR_INVALID, "%s: out_offs is NULL", who);
     tgx_status st = check_packed_list(who, "offs", "offsets", offs, n_rows, true);
     if (st != TGX_OK) return st;
@@ -539,11 +538,9 @@ tgx_status select_host(const char* who, const char* what, const T* data, const u
     if (n_out && !out) return fail(TGX_ERR_INVALID, "%s: the destination is NULL", who);
     out_offs[0] = 0;
     for (uint64_t k = 0; k < M; k++) out_offs[k + 1] = out_offs[k] + tgx::select_out_len(offs, n_rows, rows, k);
-    for (uint64_t t0 = 0; t0 < n_out; t0 += kTile) {
-        const uint64_t last = tgx::select_tile_last(t0, kTile, n_out);
-        const uint64_t lo = tgx::pack_find_row(out_offs, 0, 0, M - 1, t0), hi = tgx::pack_find_row(out_offs, 0, 0, M - 1, last);
-        for (uint64_t e0 = t0; e0 <= last; e0 += kGroup) {
-            const uint32_t n_in = last + 1 - e0 < kGroup ? (uint32_t)(last + 1 - e0) : kGroup;
+    tgx::tiled_fill_host(
+        n_out, n_out, kTile, kGroup, 0, [&](uint64_t j) { return tgx::pack_find_row(out_offs, 0, 0, M - 1, j); },
+        [&](uint64_t lo, uint64_t hi, uint64_t e0, uint32_t n_in) {
             T v[kGroup] = {};
             tgx::SelectCursor cur;
             tgx::select_enter(cur, offs, rows, out_offs, lo, hi, e0);
@@ -558,8 +555,8 @@ tgx_status select_host(const char* who, const char* what, const T* data, const u
                 tgx::select_walk<kGroup, T>(cur, data, offs, rows, out_offs, lo, hi, e0, n_in, v);
             }
             for (uint32_t q = 0; q < n_in; q++) out[e0 + q] = v[q];
-        }
-    }
+            return true;
+        });
     return TGX_OK;
 }
 
@@ -615,9 +612,9 @@ tgx_status tgx_front_host(const uint8_t* text, const uint64_t* offs, uint64_t n_
     std::vector<uint16_t> hit(slots), crlf(slots), keep(slots);
     std::vector<uint64_t> tile_base(tiles + 1, 0), row_lo(tiles), row_hi(tiles);
     for (uint64_t tile = 0; tile < tiles; tile++) {
-        const uint64_t t0 = tile * tgx::kFrontTile, last = tgx::front_tile_last(t0, N);
-        row_lo[tile] = tgx::front_find_sample(offs, 0, S - 1, t0);
-        row_hi[tile] = tgx::front_find_sample(offs, 0, S - 1, last);
+        const uint64_t t0 = tile * tgx::kFrontTile, last = tgx::tile_last(t0, tgx::kFrontTile, N);
+        row_lo[tile] = tgx::pack_find_row(offs, 0, 0, S - 1, t0);
+        row_hi[tile] = tgx::pack_find_row(offs, 0, 0, S - 1, last);
         uint64_t count = 0;
         for (uint64_t p0 = t0; p0 <= last; p0 += tgx::kFrontGroup) {
             const uint32_t n_in = N - p0 < tgx::kFrontGroup ? (uint32_t)(N - p0) : tgx::kFrontGroup;
@@ -638,7 +635,7 @@ tgx_status tgx_front_host(const uint8_t* text, const uint64_t* offs, uint64_t n_
     std::vector<uint32_t> cand_special(C), cand_sample(C), cand_segs(C + 1, 0);
     for (uint64_t tile = 0; tile < tiles; tile++) {
         uint64_t at = tile_base[tile];
-        const uint64_t t0 = tile * tgx::kFrontTile, last = tgx::front_tile_last(t0, N);
+        const uint64_t t0 = tile * tgx::kFrontTile, last = tgx::tile_last(t0, tgx::kFrontTile, N);
         for (uint64_t p0 = t0; p0 <= last; p0 += tgx::kFrontGroup) {
             const uint32_t h = hit[p0 / tgx::kFrontGroup];
             if (h) tgx::front_write_slot(tab, text, offs, row_lo[tile], row_hi[tile], p0, h, at, cand_pos.data(), cand_end.data(), cand_special.data(), cand_sample.data());
@@ -698,7 +695,7 @@ tgx_status tgx_front_host(const uint8_t* text, const uint64_t* offs, uint64_t n_
     // keep, pack
     std::vector<uint32_t> enc_local(E);
     for (uint64_t tile = 0; tile < tiles; tile++) {
-        const uint64_t t0 = tile * tgx::kFrontTile, last = tgx::front_tile_last(t0, N);
+        const uint64_t t0 = tile * tgx::kFrontTile, last = tgx::tile_last(t0, tgx::kFrontTile, N);
         const uint64_t e_lo = tgx::front_first_enc(enc_end.data(), 0, E, t0), e_hi = tgx::front_first_enc(enc_end.data(), 0, E, last);
         uint32_t count = 0;
         for (uint64_t p0 = t0; p0 <= last; p0 += tgx::kFrontGroup) {
@@ -838,9 +835,9 @@ tgx_status tgx_normalize_host(uint32_t form, const uint8_t* text, const uint64_t
     std::vector<uint32_t> mask(slots), slot_pre(slots);
     std::vector<uint64_t> tile_base(tiles + 1, 0), tile_place(tiles + 1, 0), row_lo(tiles), row_hi(tiles);
     for (uint64_t tile = 0; tile < tiles; tile++) {
-        const uint64_t t0 = tile * tgx::kFrontTile, last = tgx::front_tile_last(t0, N);
-        row_lo[tile] = tgx::front_find_sample(offs, 0, S - 1, t0);
-        row_hi[tile] = tgx::front_find_sample(offs, 0, S - 1, last);
+        const uint64_t t0 = tile * tgx::kFrontTile, last = tgx::tile_last(t0, tgx::kFrontTile, N);
+        row_lo[tile] = tgx::pack_find_row(offs, 0, 0, S - 1, t0);
+        row_hi[tile] = tgx::pack_find_row(offs, 0, 0, S - 1, last);
         uint64_t count = 0;
         for (uint64_t p0 = t0; p0 <= last; p0 += tgx::kFrontGroup) {
             const uint32_t n_in = N - p0 < tgx::kFrontGroup ? (uint32_t)(N - p0) : tgx::kFrontGroup;
@@ -872,7 +869,7 @@ tgx_status tgx_normalize_host(uint32_t form, const uint8_t* text, const uint64_t
     std::vector<uint64_t> piece_begin(P), piece_row(P), piece_sum(P + 1, 0);
     for (uint64_t tile = 0; tile < tiles; tile++) {
         uint64_t at = tile_base[tile];
-        const uint64_t t0 = tile * tgx::kFrontTile, last = tgx::front_tile_last(t0, N);
+        const uint64_t t0 = tile * tgx::kFrontTile, last = tgx::tile_last(t0, tgx::kFrontTile, N);
         for (uint64_t p0 = t0; p0 <= last; p0 += tgx::kFrontGroup) {
             const uint32_t heads = mask[p0 / tgx::kFrontGroup] >> 16;
             if (heads) tgx::norm_write_pieces(offs, row_lo[tile], row_hi[tile], p0, heads, at, piece_begin.data(), piece_row.data());
@@ -895,7 +892,7 @@ tgx_status tgx_normalize_host(uint32_t form, const uint8_t* text, const uint64_t
     }
     // places
     for (uint64_t tile = 0; tile < tiles; tile++) {
-        const uint64_t t0 = tile * tgx::kFrontTile, last = tgx::front_tile_last(t0, N);
+        const uint64_t t0 = tile * tgx::kFrontTile, last = tgx::tile_last(t0, tgx::kFrontTile, N);
         uint32_t copied = 0, heads = 0;
         for (uint64_t p0 = t0; p0 <= last; p0 += tgx::kFrontGroup) {
             const uint32_t n_in = N - p0 < tgx::kFrontGroup ? (uint32_t)(N - p0) : tgx::kFrontGroup, m = mask[p0 / tgx::kFrontGroup];
@@ -1003,16 +1000,14 @@ tgx_status tgx_decode_rows_host(const uint8_t* vocab_bytes, const uint64_t* voca
     memset(raw, 0xA5, (size_t)G * tgx::kDecodeGroup + 16);  // (what lies behind the text may be anything)
     std::vector<uint32_t> flags(G), codes(G + 1, 0);
     // ... the fill kernel's tiles and thread slots, ...
-    for (uint64_t t0 = 0; t0 < T; t0 += tgx::kDecodeTile) {
-        const uint64_t last = tgx::decode_tile_last(t0, T);
-        const uint64_t lo = tgx::decode_find(B.data(), 0, N - 1, tgx::decode_tile_first(t0)), hi = tgx::decode_find(B.data(), 0, N - 1, last);
-        for (uint64_t e0 = t0; e0 <= last; e0 += tgx::kDecodeGroup) {
-            const uint32_t n_in = last + 1 - e0 < tgx::kDecodeGroup ? (uint32_t)(last + 1 - e0) : tgx::kDecodeGroup;
+    tgx::tiled_fill_host(
+        T, T, tgx::kDecodeTile, tgx::kDecodeGroup, tgx::kDecodeBack, [&](uint64_t b) { return tgx::pack_find_row(B.data(), 0, 0, N - 1, b); },
+        [&](uint64_t lo, uint64_t hi, uint64_t e0, uint32_t n_in) {
             uint8_t v[tgx::kDecodeGroup] = {};
             flags[e0 / tgx::kDecodeGroup] = tgx::decode_group(tab, src, B.data(), n_live_specials ? X.data() : nullptr, lo, hi, e0, n_in, v);
             memcpy(raw + e0, v, n_in);
-        }
-    }
+            return true;
+        });
     // ... the rows' raw starts, which start runs, ...
     for (uint64_t i = 0; i <= S; i++) {
         const uint64_t r = B[i < S ? tgx::decode_row_first(src, i) : N];
@@ -1064,21 +1059,18 @@ void spans_host_write(const tgx::LayoutSeq& seq, const uint64_t* offs, uint64_t 
         }
         return;
     }
-    // as the kernel: tiles of kSpanTile elements, the owners of a tile's ends bound the search inside it, and a group of
-    // consecutive elements walks on from row to row
-    for (uint64_t t0 = 0; t0 < n; t0 += tgx::kSpanTile) {
-        const uint64_t last = tgx::span_tile_last(t0, n);
-        const uint64_t lo = tgx::pack_find_row(offs, 0, 0, n_rows - 1, t0), hi = tgx::pack_find_row(offs, 0, 0, n_rows - 1, last);
-        for (uint64_t e0 = t0; e0 <= last; e0 += tgx::kSpanGroup) {
-            const uint32_t n_in = last + 1 - e0 < tgx::kSpanGroup ? (uint32_t)(last + 1 - e0) : tgx::kSpanGroup;
+    // as the kernel: the tiled fill over the stream's elements
+    tgx::tiled_fill_host(
+        n, n, tgx::kSpanTile, tgx::kSpanGroup, 0, [&](uint64_t j) { return tgx::pack_find_row(offs, 0, 0, n_rows - 1, j); },
+        [&](uint64_t lo, uint64_t hi, uint64_t e0, uint32_t n_in) {
             tgx::SpanPair v[tgx::kSpanGroup] = {};
             tgx::span_group(offs, P, vals, lo, hi, e0, n_in, v);
             for (uint32_t k = 0; k < n_in; k++) {
                 out[2 * (e0 + k)] = (T)v[k].start;
                 out[2 * (e0 + k) + 1] = (T)v[k].end;
             }
-        }
-    }
+            return true;
+        });
 }
 
 // as the kernel: one pair per slot

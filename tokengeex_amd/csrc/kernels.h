@@ -1,5 +1,8 @@
 // Kernel parameter blocks and launchers shared by kernels.hip and the passes (tgx_api.cpp, encode_pass.cpp, estep_pass.cpp,
-// lattice_pass.cpp).
+// lattice_pass.cpp).  The fills of the result- and corpus-side transforms (assemble, fim, select, pack, windows, flat spans,
+// decode) share one owner search, tile arithmetic and launch geometry, and fim, select and decode one tile loop and its stores:
+// tile_fill.h, which the headers below include.  scan_helpers.h beside it has the block sum and the rocPRIM scans that
+// front.hip, norm.hip, fim.hip and select.hip share; only translation units with kernels include it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

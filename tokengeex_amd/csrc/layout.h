@@ -9,6 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "tile_fill.h"
+
 namespace tgx {
 
 constexpr uint32_t kLayoutNoId = 0xFFFFFFFFu;    // TGX_NO_ID
@@ -103,22 +105,7 @@ __host__ __device__ inline uint32_t pad_group(const LayoutSeq& s, const uint32_t
 }
 
 // ---- packed: stream position j < n_stream = T + S·A -----------------------------------------------------------
-// row i starts at P_i = offs[i] + i·A (P_S = n_stream)
-__host__ __device__ inline uint64_t pack_row_start(const uint64_t* offs, uint64_t A, uint64_t i) { return offs[i] + i * A; }
-
-// The row that owns position j: the LARGEST i in [lo, hi] with P_i <= j, so a run of rows with equal P (rows that
-// contribute nothing) is stepped over and its last row, the one with P_{i+1} > j, is found.  Needs P_lo <= j and the
-// owner to be <= hi.
-__host__ __device__ inline uint64_t pack_find_row(const uint64_t* offs, uint64_t A, uint64_t lo, uint64_t hi, uint64_t j) {
-    while (lo < hi) {
-        const uint64_t mid = lo + (hi - lo + 1) / 2;
-        if (pack_row_start(offs, A, mid) <= j)
-            lo = mid;
-        else
-            hi = mid - 1;
-    }
-    return lo;
-}
+// row i starts at P_i = offs[i] + i·A (P_S = n_stream): pack_row_start and pack_find_row of tile_fill.h
 
 // A walk over ascending stream positions that all lie between the positions owned by rows lo and hi (a tile's first
 // and last): the first position searches [lo, hi], a later one stays on its row until the next row's start and then

@@ -85,9 +85,10 @@ __global__ __launch_bounds__(kLayoutBlock) void layout_pad_kernel(LayoutParams p
     }
 }
 
-// n_out elements in tiles of 1024 consecutive positions.  Two threads search all S rows for the owners of the tile's
-// first and last stream position; the others then search between those two, which for rows of more than a few
-// tokens is a handful of rows.
+// n_out elements in tiles of 1024 consecutive positions: the tiled fill of DESIGN.md, section L.9, in a copy of its own
+// (tile_fill.h's template measured slower here and in layout_window_kernel: profiles/tile_fill).  Two threads search all
+// S rows for the owners of the tile's first and last stream position; the others then search between those two, which
+// for rows of more than a few tokens is a handful of rows.  The fill runs on over the padding of the last block.
 template <class T, bool VEC>
 __global__ __launch_bounds__(kLayoutBlock) void layout_pack_kernel(LayoutParams p, uint64_t n_stream, uint64_t n_out) {
     __shared__ uint64_t s_row[2];
@@ -99,7 +100,7 @@ __global__ __launch_bounds__(kLayoutBlock) void layout_pack_kernel(LayoutParams 
         const uint64_t t0 = tile * kLayoutTile;
         if (threadIdx.x < 2 && t0 < n_stream) {
             uint64_t j = t0;
-            if (threadIdx.x == 1) j = t0 + kLayoutTile - 1 < n_stream ? t0 + kLayoutTile - 1 : n_stream - 1;
+            if (threadIdx.x == 1) j = tile_last(t0, kLayoutTile, n_stream);
             s_row[threadIdx.x] = pack_find_row(p.offs, A, 0, p.n_rows - 1, j);
         }
         __syncthreads();
@@ -169,7 +170,7 @@ __global__ __launch_bounds__(kLayoutBlock) void layout_window_kernel(WindowParam
         const uint64_t t0 = tile * kLayoutTile;
         if (threadIdx.x < 2) {
             uint64_t e = t0;
-            if (threadIdx.x == 1) e = t0 + kLayoutTile - 1 < total ? t0 + kLayoutTile - 1 : total - 1;
+            if (threadIdx.x == 1) e = tile_last(t0, kLayoutTile, total);
             s_row[threadIdx.x] = pack_find_row(q.wo, 0, 0, p.n_rows - 1, e / L);
         }
         __syncthreads();
@@ -195,13 +196,11 @@ __global__ __launch_bounds__(kLayoutBlock) void layout_window_kernel(WindowParam
 
 bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
-uint32_t capped_grid(uint64_t blocks) { return (uint32_t)(blocks < kLayoutMaxBlocks ? (blocks ? blocks : 1) : kLayoutMaxBlocks); }
-
 }  // namespace
 
 hipError_t launch_layout_max_row(const uint64_t* offs, uint64_t n_rows, unsigned long long* max_out, hipStream_t stream) {
     if (n_rows == 0) return hipSuccess;
-    const uint32_t grid = capped_grid((n_rows + kLayoutBlock - 1) / kLayoutBlock);
+    const uint32_t grid = grid_for(n_rows, kLayoutBlock, kLayoutMaxBlocks);
     hipLaunchKernelGGL(layout_max_row_kernel, dim3(grid), dim3(kLayoutBlock), 0, stream, offs, n_rows, max_out);
     return hipGetLastError();
 }
@@ -211,7 +210,7 @@ hipError_t launch_layout_pad(const LayoutParams& p, hipStream_t stream) {
     if (total == 0) return hipSuccess;
     const bool i64 = (p.flags & kLayoutI64) != 0;
     const bool vec = aligned(p.out, 16) && aligned(p.mask, 4);
-    const uint32_t grid = capped_grid((total + kLayoutTile - 1) / kLayoutTile);
+    const uint32_t grid = grid_for(total, kLayoutTile, kLayoutMaxBlocks);
     auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(kLayoutBlock), 0, stream, p, total); };
     if (i64)
         vec ? launch(layout_pad_kernel<int64_t, true>) : launch(layout_pad_kernel<int64_t, false>);
@@ -224,7 +223,7 @@ hipError_t launch_layout_pack(const LayoutParams& p, uint64_t n_stream, uint64_t
     if (n_out == 0) return hipSuccess;
     const bool i64 = (p.flags & kLayoutI64) != 0;
     const bool vec = aligned(p.out, 16) && aligned(p.doc, 16) && aligned(p.pos, 16);
-    const uint32_t grid = capped_grid((n_out + kLayoutTile - 1) / kLayoutTile);
+    const uint32_t grid = grid_for(n_out, kLayoutTile, kLayoutMaxBlocks);
     auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(kLayoutBlock), 0, stream, p, n_stream, n_out); };
     if (i64)
         vec ? launch(layout_pack_kernel<int64_t, true>) : launch(layout_pack_kernel<int64_t, false>);
@@ -236,7 +235,7 @@ hipError_t launch_layout_pack(const LayoutParams& p, uint64_t n_stream, uint64_t
 hipError_t launch_layout_window_count(const uint64_t* offs, uint64_t n_rows, uint32_t room, uint32_t step, uint32_t* counts,
                                       unsigned long long* max_out, hipStream_t stream) {
     if (n_rows == 0) return hipSuccess;
-    const uint32_t grid = capped_grid((n_rows + kLayoutBlock - 1) / kLayoutBlock);
+    const uint32_t grid = grid_for(n_rows, kLayoutBlock, kLayoutMaxBlocks);
     hipLaunchKernelGGL(layout_window_count_kernel, dim3(grid), dim3(kLayoutBlock), 0, stream, offs, n_rows, room, step, counts, max_out);
     return hipGetLastError();
 }
@@ -246,7 +245,7 @@ hipError_t launch_layout_windows(const WindowParams& q, uint64_t n_windows, hipS
     if (total == 0 || q.base.n_rows == 0) return hipSuccess;
     const bool i64 = (q.base.flags & kLayoutI64) != 0;
     const bool vec = aligned(q.base.out, 16) && aligned(q.base.mask, 4);
-    const uint32_t grid = capped_grid((total + kLayoutTile - 1) / kLayoutTile);
+    const uint32_t grid = grid_for(total, kLayoutTile, kLayoutMaxBlocks);
     auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(kLayoutBlock), 0, stream, q, total); };
     if (i64)
         vec ? launch(layout_window_kernel<int64_t, true>) : launch(layout_window_kernel<int64_t, false>);

@@ -6,9 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <rocprim/device/device_scan.hpp>
-
 #include "norm.h"
+#include "scan_helpers.h"
 
 namespace tgx {
 
@@ -19,37 +18,6 @@ static_assert(kNormBlock * kFrontGroup == kFrontTile, "the host twin walks the k
 constexpr uint64_t kNormMaxBlocks = 4096;  // memory-bound: a capped grid that strides over the rest
 constexpr uint32_t kPieceBlock = 64;       // one wave: 64 windows of kNormWindow x 5 bytes of LDS
 
-// exclusive sums of v over the block's threads in thread order; *total: the block's sum.  part: u32[kNormBlock / 64] of LDS
-__device__ inline uint32_t block_exclusive_sum(uint32_t v, uint32_t* part, uint32_t* total) {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t incl = v;
-#pragma unroll
-    for (uint32_t off = 1; off < 64; off <<= 1) {
-        const uint32_t y = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += y;
-    }
-    if (lane == 63) part[wave] = incl;
-    __syncthreads();
-    uint32_t base = 0, all = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < kNormBlock / 64; w++) {
-        const uint32_t s = part[w];
-        if (w < wave) base += s;
-        all += s;
-    }
-    __syncthreads();  // part is rewritten by the next call
-    *total = all;
-    return base + incl - v;
-}
-
-// the slot's 16 bytes with one load (text is 16-byte aligned and readable to the end of the slot)
-__device__ inline void load_slot(const uint8_t* text, uint64_t p0, uint8_t (&v)[kFrontGroup]) {
-    const uint4 w = *reinterpret_cast<const uint4*>(text + p0);
-    const uint32_t x[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-    for (uint32_t q = 0; q < kFrontGroup; q++) v[q] = (uint8_t)(x[q >> 2] >> (8 * (q & 3)));
-}
-
 __device__ inline NormPlaces places_of(const NormParams& p) { return {p.mask, p.slot_pre, p.tile_base, p.piece_sum, p.tile_place}; }
 
 __global__ __launch_bounds__(kNormBlock) void norm_mark_kernel(NormParams p) {
@@ -58,7 +26,7 @@ __global__ __launch_bounds__(kNormBlock) void norm_mark_kernel(NormParams p) {
     const uint64_t n = p.n_bytes, n_tiles = (n + kFrontTile - 1) / kFrontTile;
     for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const uint64_t t0 = tile * kFrontTile;
-        if (threadIdx.x < 2) s_row[threadIdx.x] = front_find_sample(p.offs, 0, p.n_rows - 1, threadIdx.x ? front_tile_last(t0, n) : t0);
+        if (threadIdx.x < 2) s_row[threadIdx.x] = pack_find_row(p.offs, 0, 0, p.n_rows - 1, threadIdx.x ? tile_last(t0, kFrontTile, n) : t0);
         __syncthreads();
         const uint64_t p0 = t0 + (uint64_t)threadIdx.x * kFrontGroup;
         uint32_t m = 0;
@@ -71,7 +39,7 @@ __global__ __launch_bounds__(kNormBlock) void norm_mark_kernel(NormParams p) {
             p.mask[p0 / kFrontGroup] = m;
         }
         uint32_t total;
-        block_exclusive_sum(front_popc(m >> 16), s_part, &total);  // (its barriers also keep s_row for the whole tile)
+        block_exclusive_sum<kNormBlock>(front_popc(m >> 16), s_part, &total);  // (its barriers also keep s_row for the whole tile)
         if (threadIdx.x == 0) p.tile_count[tile] = total;
     }
 }
@@ -84,12 +52,12 @@ __global__ __launch_bounds__(kNormBlock) void norm_pieces_kernel(NormParams p) {
         const uint64_t base = p.tile_base[tile];
         if (p.tile_base[tile + 1] == base) continue;  // (the whole block takes the same way)
         const uint64_t t0 = tile * kFrontTile;
-        if (threadIdx.x < 2) s_row[threadIdx.x] = front_find_sample(p.offs, 0, p.n_rows - 1, threadIdx.x ? front_tile_last(t0, n) : t0);
+        if (threadIdx.x < 2) s_row[threadIdx.x] = pack_find_row(p.offs, 0, 0, p.n_rows - 1, threadIdx.x ? tile_last(t0, kFrontTile, n) : t0);
         __syncthreads();
         const uint64_t p0 = t0 + (uint64_t)threadIdx.x * kFrontGroup;
         const uint32_t heads = p0 < n ? p.mask[p0 / kFrontGroup] >> 16 : 0u;
         uint32_t total;
-        const uint32_t before = block_exclusive_sum(front_popc(heads), s_part, &total);
+        const uint32_t before = block_exclusive_sum<kNormBlock>(front_popc(heads), s_part, &total);
         if (heads) norm_write_pieces(p.offs, s_row[0], s_row[1], p0, heads, base + before, p.piece_begin, p.piece_row);
         __syncthreads();  // s_row is rewritten for the next tile
     }
@@ -124,8 +92,8 @@ __global__ __launch_bounds__(kNormBlock) void norm_places_kernel(NormParams p) {
             m = p.mask[p0 / kFrontGroup];
         }
         uint32_t copied, heads;
-        const uint32_t copied_before = block_exclusive_sum(front_popc(norm_verbatim(m, n_in)), s_part, &copied);
-        const uint32_t heads_before = block_exclusive_sum(front_popc(m >> 16), s_part, &heads);
+        const uint32_t copied_before = block_exclusive_sum<kNormBlock>(front_popc(norm_verbatim(m, n_in)), s_part, &copied);
+        const uint32_t heads_before = block_exclusive_sum<kNormBlock>(front_popc(m >> 16), s_part, &heads);
         if (p0 < n) p.slot_pre[p0 / kFrontGroup] = copied_before | heads_before << 16;
         if (threadIdx.x == 0) p.tile_bytes[tile] = norm_tile_bytes(p.tile_base, p.piece_sum, tile, copied);
     }
@@ -165,13 +133,7 @@ __global__ __launch_bounds__(kPieceBlock) void norm_write_kernel(NormParams p) {
     }
 }
 
-uint32_t capped_grid(uint64_t blocks) { return (uint32_t)(blocks < kNormMaxBlocks ? (blocks ? blocks : 1) : kNormMaxBlocks); }
-uint32_t grid_for(uint64_t items, uint32_t block) { return capped_grid((items + block - 1) / block); }
 uint64_t tiles_of(uint64_t n) { return (n + kFrontTile - 1) / kFrontTile; }
-
-hipError_t sum_scan(const uint64_t* in, uint64_t* out, uint64_t n, void* temp, size_t& temp_bytes, hipStream_t stream) {
-    return rocprim::exclusive_scan(temp, temp_bytes, in, out, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), stream);
-}
 
 #define NORM_TRY(expr)                   \
     do {                                 \
@@ -192,7 +154,7 @@ hipError_t launch_norm_mark(const NormParams& p, void* temp, size_t temp_bytes, 
     if (p.n_bytes == 0 || p.n_rows == 0 || p.form > 3 || (reinterpret_cast<uintptr_t>(p.text) & 15u)) return hipErrorInvalidValue;
     const uint64_t tiles = tiles_of(p.n_bytes);
     NORM_TRY(hipMemsetAsync(p.tile_count + tiles, 0, 8, stream));
-    hipLaunchKernelGGL(norm_mark_kernel, dim3(capped_grid(tiles)), dim3(kNormBlock), 0, stream, p);
+    hipLaunchKernelGGL(norm_mark_kernel, dim3(capped_grid(tiles, kNormMaxBlocks)), dim3(kNormBlock), 0, stream, p);
     NORM_TRY(hipGetLastError());
     return sum_scan(p.tile_count, p.tile_base, tiles + 1, temp, temp_bytes, stream);
 }
@@ -200,7 +162,7 @@ hipError_t launch_norm_mark(const NormParams& p, void* temp, size_t temp_bytes, 
 // piece_begin and piece_row of the P = n_pieces >= 1 pieces
 hipError_t launch_norm_pieces(const NormParams& p, hipStream_t stream) {
     if (p.n_pieces == 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(norm_pieces_kernel, dim3(capped_grid(tiles_of(p.n_bytes))), dim3(kNormBlock), 0, stream, p);
+    hipLaunchKernelGGL(norm_pieces_kernel, dim3(capped_grid(tiles_of(p.n_bytes), kNormMaxBlocks)), dim3(kNormBlock), 0, stream, p);
     return hipGetLastError();
 }
 
@@ -208,7 +170,7 @@ hipError_t launch_norm_pieces(const NormParams& p, hipStream_t stream) {
 hipError_t launch_norm_length(const NormParams& p, void* temp, size_t temp_bytes, hipStream_t stream) {
     if (p.n_pieces == 0) return hipErrorInvalidValue;
     NORM_TRY(hipMemsetAsync(p.overflow_row, 0xFF, 8, stream));
-    hipLaunchKernelGGL(norm_length_kernel, dim3(grid_for(p.n_pieces + 1, kPieceBlock)), dim3(kPieceBlock), 0, stream, p);
+    hipLaunchKernelGGL(norm_length_kernel, dim3(grid_for(p.n_pieces + 1, kPieceBlock, kNormMaxBlocks)), dim3(kPieceBlock), 0, stream, p);
     NORM_TRY(hipGetLastError());
     return sum_scan(p.piece_len, p.piece_sum, p.n_pieces + 1, temp, temp_bytes, stream);
 }
@@ -218,19 +180,19 @@ hipError_t launch_norm_places(const NormParams& p, void* temp, size_t temp_bytes
     if (p.n_pieces == 0) return hipErrorInvalidValue;
     const uint64_t tiles = tiles_of(p.n_bytes);
     NORM_TRY(hipMemsetAsync(p.tile_bytes + tiles, 0, 8, stream));
-    hipLaunchKernelGGL(norm_places_kernel, dim3(capped_grid(tiles)), dim3(kNormBlock), 0, stream, p);
+    hipLaunchKernelGGL(norm_places_kernel, dim3(capped_grid(tiles, kNormMaxBlocks)), dim3(kNormBlock), 0, stream, p);
     NORM_TRY(hipGetLastError());
     NORM_TRY(sum_scan(p.tile_bytes, p.tile_place, tiles + 1, temp, temp_bytes, stream));
-    hipLaunchKernelGGL(norm_offsets_kernel, dim3(grid_for(p.n_rows + 1, kNormBlock)), dim3(kNormBlock), 0, stream, p);
+    hipLaunchKernelGGL(norm_offsets_kernel, dim3(grid_for(p.n_rows + 1, kNormBlock, kNormMaxBlocks)), dim3(kNormBlock), 0, stream, p);
     return hipGetLastError();
 }
 
 // the copied bytes and the pieces to out[0 .. tile_place[tiles])
 hipError_t launch_norm_write(const NormParams& p, hipStream_t stream) {
     if (p.n_pieces == 0 || !p.out) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(norm_copy_kernel, dim3(grid_for((p.n_bytes + kFrontGroup - 1) / kFrontGroup, kNormBlock)), dim3(kNormBlock), 0, stream, p);
+    hipLaunchKernelGGL(norm_copy_kernel, dim3(grid_for((p.n_bytes + kFrontGroup - 1) / kFrontGroup, kNormBlock, kNormMaxBlocks)), dim3(kNormBlock), 0, stream, p);
     NORM_TRY(hipGetLastError());
-    hipLaunchKernelGGL(norm_write_kernel, dim3(grid_for(p.n_pieces, kPieceBlock)), dim3(kPieceBlock), 0, stream, p);
+    hipLaunchKernelGGL(norm_write_kernel, dim3(grid_for(p.n_pieces, kPieceBlock, kNormMaxBlocks)), dim3(kPieceBlock), 0, stream, p);
     return hipGetLastError();
 }
 

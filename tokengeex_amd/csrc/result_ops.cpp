@@ -262,15 +262,15 @@ tgx_status assemble_device(const char* who, tgx_model* m, const tgx_result* segs
     r->n_tokens = n_out;
     uint64_t *d_seg_offs = nullptr, *d_rank = nullptr, *d_starts = nullptr, *d_zero = nullptr;
     int32_t* d_special = d_plan_special;
-    void* d_scan = nullptr;
-    size_t scan_bytes = 0;
-    if (tgx::assemble_scan_temp_bytes(K, &scan_bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan temp-size query failed");
+    ScanScratch scan;
     if (r->d_offs.alloc(m->device, (size_t)(S + 1) * 8) != hipSuccess || r->d_ids.alloc(m->device, (size_t)n_out * 4 + 256) != hipSuccess ||
         (!d_plan_offs && pass.alloc((size_t)(S + 1) * 8, &d_seg_offs) != hipSuccess) ||
         (!d_plan_special && pass.alloc((size_t)(K + 1) * 4, &d_special) != hipSuccess) ||
         pass.alloc((size_t)(K + 1) * 8, &d_rank) != hipSuccess || pass.alloc((size_t)(K + 1) * 8, &d_starts) != hipSuccess ||
-        (E == 0 && pass.alloc(8, &d_zero) != hipSuccess) || pass.alloc(scan_bytes, &d_scan) != hipSuccess)  // (never NULL: that asks the scan for its size)
+        (E == 0 && pass.alloc(8, &d_zero) != hipSuccess))
         return fail(TGX_ERR_DEVICE, "out of device memory (assembly)");
+    const tgx_status scan_st = scan_room(&scan, pass, tgx::assemble_scan_temp_bytes, K, "out of device memory (assembly)");
+    if (scan_st != TGX_OK) return scan_st;
     if ((!d_plan_offs && hipMemcpyAsync(d_seg_offs, h_seg_offs, (size_t)(S + 1) * 8, hipMemcpyHostToDevice, m->stream) != hipSuccess) ||
         (!d_plan_special && K && hipMemcpyAsync(d_special, h_special, (size_t)K * 4, hipMemcpyHostToDevice, m->stream) != hipSuccess) ||
         (d_zero && hipMemsetAsync(d_zero, 0, 8, m->stream) != hipSuccess))
@@ -290,7 +290,7 @@ tgx_status assemble_device(const char* who, tgx_model* m, const tgx_result* segs
     p.out_ids = r->d_ids;
     p.out_offs = r->d_offs;
     time_begin(m, "assemble_ranks_scan");
-    if (tgx::launch_assemble_ranks(d_special, d_rank, K, d_scan, scan_bytes, m->stream) != hipSuccess)
+    if (tgx::launch_assemble_ranks(d_special, d_rank, K, scan.ptr, scan.bytes, m->stream) != hipSuccess)
         return fail(TGX_ERR_DEVICE, "scan launch failed");
     time_end(m);
     time_begin(m, "assemble_starts_kernel");
@@ -379,7 +379,7 @@ tgx_status decode_device(tgx_model* m, tgx::DecodeSrc src, const uint8_t* specia
     uint32_t *meta = nullptr, *flags = nullptr, *codes = nullptr;
     uint64_t *starts = nullptr, *specials = nullptr, *gpos = nullptr, *sp_offs = nullptr;
     uint8_t* sp_bytes = nullptr;
-    void *scan = nullptr, *scan2 = nullptr;
+    ScanScratch scan, scan2;
     unsigned long long* ctrl = nullptr;  // [0]: lowest out-of-bounds position, [1]: replacement characters, [2]: live specials
     tgx_text* t = text.get();
     t->device = dev;
@@ -397,11 +397,9 @@ tgx_status decode_device(tgx_model* m, tgx::DecodeSrc src, const uint8_t* specia
     if (st != TGX_OK) return st;
 
     const uint64_t sp_total = n_specials ? special_offs[n_specials] - special_offs[0] : 0;
-    size_t scan_bytes = 0;
-    if (tgx::decode_scan_temp_bytes(N, &scan_bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan temp-size query failed");
     HIP_TRY(guard.alloc((size_t)(N + 1) * 4, &meta));
     HIP_TRY(guard.alloc((size_t)(N + 1) * 8, &starts));
-    HIP_TRY(guard.alloc(scan_bytes, &scan));  // (never NULL: that asks the scan for its size)
+    if ((st = scan_room(&scan, guard, tgx::decode_scan_temp_bytes, N)) != TGX_OK) return st;
     HIP_TRY(guard.alloc(24, &ctrl));
     HIP_TRY(guard.alloc(((size_t)n_specials + 1) * 8, &sp_offs));
     HIP_TRY(guard.alloc((size_t)sp_total + 16, &sp_bytes));
@@ -429,7 +427,7 @@ tgx_status decode_device(tgx_model* m, tgx::DecodeSrc src, const uint8_t* specia
     p.n_replaced = ctrl + 1;
     p.n_specials_live = ctrl + 2;
     p.row_offs = t->d_offs;
-    HIP_TRY(tgx::launch_decode_meta(p, scan, scan_bytes, hs));
+    HIP_TRY(tgx::launch_decode_meta(p, scan.ptr, scan.bytes, hs));
     unsigned long long h_bad = ~0ull, h_raw = 0, h_replaced = 0, h_final = 0, h_specials = 0;
     HIP_TRY(hipMemcpyAsync(&h_bad, ctrl, 8, hipMemcpyDeviceToHost, hs));
     HIP_TRY(hipMemcpyAsync(&h_specials, ctrl + 2, 8, hipMemcpyDeviceToHost, hs));
@@ -469,7 +467,7 @@ tgx_status decode_device(tgx_model* m, tgx::DecodeSrc src, const uint8_t* specia
     if (h_specials) {  // only then can a run end inside a row
         HIP_TRY(guard.alloc((size_t)(N + 1) * 8, &specials));
         p.specials = specials;
-        HIP_TRY(tgx::launch_decode_specials(p, scan, scan_bytes, hs));
+        HIP_TRY(tgx::launch_decode_specials(p, scan.ptr, scan.bytes, hs));
     }
     HIP_TRY(tgx::launch_decode_fill(p, hs));
     HIP_TRY(tgx::launch_decode_rows(p, hs));
@@ -484,12 +482,10 @@ tgx_status decode_device(tgx_model* m, tgx::DecodeSrc src, const uint8_t* specia
         *out = text.release();
         return TGX_OK;
     }
-    size_t scan2_bytes = 0;
-    if (tgx::decode_expand_temp_bytes(G, &scan2_bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan temp-size query failed");
     HIP_TRY(guard.alloc((size_t)(G + 1) * 8, &gpos));
-    HIP_TRY(guard.alloc(scan2_bytes, &scan2));
+    if ((st = scan_room(&scan2, guard, tgx::decode_expand_temp_bytes, G)) != TGX_OK) return st;
     p.gpos = gpos;
-    HIP_TRY(tgx::launch_decode_positions(p, scan2, scan2_bytes, hs));
+    HIP_TRY(tgx::launch_decode_positions(p, scan2.ptr, scan2.bytes, hs));
     HIP_TRY(hipMemcpyAsync(&h_final, gpos + G, 8, hipMemcpyDeviceToHost, hs));
     HIP_TRY(hipStreamSynchronize(hs));
     HIP_TRY(t->d_bytes.alloc(dev, (size_t)h_final + 16));
@@ -645,11 +641,9 @@ tgx_status tgx_result_fim(const tgx_result* r, uint32_t prefix_id, uint32_t suff
     res->device = r->device;
     res->vocab_size = fim_vocab_size(r->vocab_size, prefix_id, suffix_id, middle_id);
     res->n_samples = S;
-    size_t scan_bytes = 0;
-    if (tgx::fim_scan_temp_bytes(S, &scan_bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan temp-size query failed");
-    void* d_scan = nullptr;
-    if (res->d_offs.alloc(r->device, (size_t)(S + 1) * 8) != hipSuccess || guard.alloc(scan_bytes, &d_scan) != hipSuccess)  // (never NULL: that asks the scan for its size)
-        return fail(TGX_ERR_DEVICE, "out of device memory (fill-in-the-middle)");
+    ScanScratch scan;
+    if (res->d_offs.alloc(r->device, (size_t)(S + 1) * 8) != hipSuccess) return fail(TGX_ERR_DEVICE, "out of device memory (fill-in-the-middle)");
+    if ((st = scan_room(&scan, guard, tgx::fim_scan_temp_bytes, S, "out of device memory (fill-in-the-middle)")) != TGX_OK) return st;
     tgx::FimParams p = {};
     p.ids = r->d_ids;
     p.offs = r->d_offs;
@@ -657,7 +651,7 @@ tgx_status tgx_result_fim(const tgx_result* r, uint32_t prefix_id, uint32_t suff
     p.f = tgx::FimArgs{seed, first_row, rate, spm_rate, prefix_id, suffix_id, middle_id};
     p.out_offs = res->d_offs;
     timer.begin(0);
-    if (tgx::launch_fim_offsets(p, d_scan, scan_bytes, hs) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan launch failed");
+    if (tgx::launch_fim_offsets(p, scan.ptr, scan.bytes, hs) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan launch failed");
     timer.end(0);
     // the one word that visits the host: T' sizes the id buffer
     if ((st = read_u64(hs, res->d_offs.get() + S, &h_total)) != TGX_OK) return st;
@@ -753,13 +747,11 @@ tgx_status tgx_result_select(const tgx_result* r, const int64_t* rows, uint64_t 
     res->n_samples = M;
     tgx::SelectParams p = {};
     if ((st = select_rows_device(who, rows, M, flags, r->device, guard, &p.rows)) != TGX_OK) return st;
-    size_t scan_bytes = 0;
-    if (tgx::select_scan_temp_bytes(M, &scan_bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan temp-size query failed");
-    void* d_scan = nullptr;
+    ScanScratch scan;
     unsigned long long* d_bad = nullptr;
-    if (res->d_offs.alloc(r->device, (size_t)(M + 1) * 8) != hipSuccess || guard.alloc(scan_bytes, &d_scan) != hipSuccess ||  // (never NULL: that asks the scan for its size)
-        guard.alloc(sizeof(unsigned long long), &d_bad) != hipSuccess)
-        return fail(TGX_ERR_DEVICE, "out of device memory (select)");
+    if (res->d_offs.alloc(r->device, (size_t)(M + 1) * 8) != hipSuccess) return fail(TGX_ERR_DEVICE, "out of device memory (select)");
+    if ((st = scan_room(&scan, guard, tgx::select_scan_temp_bytes, M, "out of device memory (select)")) != TGX_OK) return st;
+    if (guard.alloc(sizeof(unsigned long long), &d_bad) != hipSuccess) return fail(TGX_ERR_DEVICE, "out of device memory (select)");
     p.data = r->d_ids;
     p.offs = r->d_offs;
     p.n_src = S;
@@ -773,7 +765,7 @@ tgx_status tgx_result_select(const tgx_result* r, const int64_t* rows, uint64_t 
         HIP_TRY(hipMemcpyAsync(&h_words[1], d_bad, sizeof(unsigned long long), hipMemcpyDeviceToHost, hs));
     }
     timer.begin(1);
-    if (tgx::launch_select_offsets(p, d_scan, scan_bytes, hs) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan launch failed");
+    if (tgx::launch_select_offsets(p, scan.ptr, scan.bytes, hs) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan launch failed");
     timer.end(1);
     // the one host visit: T' sizes the id buffer, and the bad-index word comes with it
     if ((st = read_u64(hs, res->d_offs.get() + M, &h_words[0])) != TGX_OK) return st;
@@ -873,14 +865,13 @@ tgx_status span_sums_device(const char* who, tgx_model* m, const tgx_result* r, 
     if (st != TGX_OK) return st;
     std::vector<uint64_t> sp_words;
     span_special_words(special_bytes, special_offs, n_specials, chars, &sp_words);
-    size_t scan_bytes = 0;
-    if (tgx::span_scan_temp_bytes(T, &scan_bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan temp-size query failed");
     uint32_t* vals = nullptr;
     uint64_t *sums = nullptr, *d_sp_words = nullptr;
-    void* scan = nullptr;
+    ScanScratch scan;
     HIP_TRY(guard.alloc((size_t)(T + 1) * 4, &vals));
     HIP_TRY(guard.alloc((size_t)(T + 1) * 8, &sums));
-    HIP_TRY(guard.alloc(scan_bytes, &scan));  // (never NULL: that asks the scan for its size)
+    const tgx_status scan_st = scan_room(&scan, guard, tgx::span_scan_temp_bytes, T);
+    if (scan_st != TGX_OK) return scan_st;
     HIP_TRY(guard.alloc(sp_words.size() * 8, &d_sp_words));
     HIP_TRY(guard.upload(d_sp_words, std::move(sp_words)));
     p->tab.words = m->d_span_words;
@@ -893,7 +884,7 @@ tgx_status span_sums_device(const char* who, tgx_model* m, const tgx_result* r, 
     p->n = T;
     p->vals = vals;
     p->sums = sums;
-    HIP_TRY(tgx::launch_span_sums(*p, scan, scan_bytes, hs));
+    HIP_TRY(tgx::launch_span_sums(*p, scan.ptr, scan.bytes, hs));
     if (!i64) {  // nothing is written when a row does not fit: the one word that is read back
         unsigned long long h_max = 0, *row_max = nullptr;
         HIP_TRY(guard.alloc(sizeof(unsigned long long), &row_max));

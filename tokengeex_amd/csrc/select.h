@@ -97,9 +97,4 @@ __host__ __device__ inline void select_shift16(const uint32_t (&d)[5], uint32_t 
     for (uint32_t q = 0; q < 4; q++) w[q] = sh ? (d[q] >> sh) | (d[q + 1] << (32 - sh)) : d[q];
 }
 
-// the last position of the tile of `tile` positions that starts at t0 (t0 < n_out)
-__host__ __device__ inline uint64_t select_tile_last(uint64_t t0, uint64_t tile, uint64_t n_out) {
-    return t0 + tile - 1 < n_out ? t0 + tile - 1 : n_out - 1;
-}
-
 }  // namespace tgx

@@ -2,7 +2,7 @@
 // tgx_corpus_select; select.h has the index arithmetic), the rows' lengths (tgx_result_lengths_device) and the seeded
 // permutation (tgx_shuffled_rows_device).  Two steps, as fim.hip's: the new offsets (a device-wide exclusive scan,
 // rocPRIM, over an iterator that computes a length from offs[rows[k]]: no length array is written) and the fill.  The fill
-// is output-centric like fim_fill_kernel, assemble_fill_kernel and layout_pack_kernel: a tile of consecutive output
+// is the tiled fill of tile_fill.h: a tile of consecutive output
 // positions per block, the owners of the tile's ends found by two threads over the new offsets, every thread then walking
 // its slot between those two and writing it with one 16-byte store.  A row is 0 to 10^5 elements, so no unit of work is
 // a row.
@@ -10,11 +10,9 @@
 #include <stdint.h>
 
 #include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
-#include <rocprim/iterator/transform_iterator.hpp>
 
 #include "kernels.h"
+#include "scan_helpers.h"
 #include "select.h"
 
 namespace tgx {
@@ -82,85 +80,63 @@ template <class T>
 __global__ __launch_bounds__(kSelectBlock) void select_fill_kernel(SelectParams p) {
     constexpr bool kText = sizeof(T) == 1;
     constexpr uint32_t kGroup = kText ? kSelectByteGroup : kSelectGroup;
-    constexpr uint64_t kTile = kText ? kSelectByteTile : kSelectTile;
-    __shared__ uint64_t s_row[2];
-    const uint64_t n_out = p.n_out;
-    const T* __restrict__ data = static_cast<const T*>(p.data);
-    T* __restrict__ out = static_cast<T*>(p.out);
-    const uint64_t n_tiles = (n_out + kTile - 1) / kTile;
-    for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const uint64_t t0 = tile * kTile;
-        if (threadIdx.x < 2) s_row[threadIdx.x] = pack_find_row(p.out_offs, 0, 0, p.n_rows - 1, threadIdx.x ? select_tile_last(t0, kTile, n_out) : t0);
-        __syncthreads();
-        const uint64_t e0 = t0 + (uint64_t)threadIdx.x * kGroup;
-        if (e0 < n_out) {
-            const uint32_t n_in = n_out - e0 < kGroup ? (uint32_t)(n_out - e0) : kGroup;
-            const uint64_t lo = s_row[0], hi = s_row[1];
+    constexpr uint32_t kTile = kText ? kSelectByteTile : kSelectTile;
+    tiled_fill<kTile, kGroup>(
+        p.n_out, p.n_out, [p](uint64_t j) { return pack_find_row(p.out_offs, 0, 0, p.n_rows - 1, j); },
+        [p](uint64_t lo, uint64_t hi, uint64_t e0, uint32_t n_in) {
+            const T* __restrict__ data = static_cast<const T*>(p.data);
+            T* __restrict__ out = static_cast<T*>(p.out);
             if constexpr (kText) {
                 SelectCursor cur;
                 select_enter(cur, p.offs, p.rows, p.out_offs, lo, hi, e0);
-                uint32_t w[4];
                 if (select_slot_inside(cur, e0, n_in)) {
-                    uint32_t d[5];
+                    uint32_t d[5], w[4];
                     const uint32_t r = select_load5(data, select_slot_source(cur, e0), d);
                     select_shift16(d, r, w);
                     *reinterpret_cast<uint4*>(out + e0) = make_uint4(w[0], w[1], w[2], w[3]);
                 } else {
                     uint8_t v[kSelectByteGroup] = {};
                     select_walk<kSelectByteGroup, uint8_t>(cur, data, p.offs, p.rows, p.out_offs, lo, hi, e0, n_in, v);
-                    if (n_in == kSelectByteGroup) {  // out is 16-byte aligned (checked by the launcher) and e0 a multiple of 16
-#pragma unroll
-                        for (uint32_t q = 0; q < 4; q++)
-                            w[q] = (uint32_t)v[4 * q] | ((uint32_t)v[4 * q + 1] << 8) | ((uint32_t)v[4 * q + 2] << 16) | ((uint32_t)v[4 * q + 3] << 24);
-                        *reinterpret_cast<uint4*>(out + e0) = make_uint4(w[0], w[1], w[2], w[3]);
-                    } else {  // the tail of the last tile: exactly n_out bytes are written
-#pragma unroll
-                        for (uint32_t q = 0; q < kSelectByteGroup; q++)
-                            if (q < n_in) out[e0 + q] = v[q];
-                    }
+                    store_bytes16(out, e0, v, n_in);  // (the tail of the last tile: exactly n_out bytes are written)
                 }
             } else {
                 uint32_t v[kSelectGroup] = {0, 0, 0, 0};
                 select_group<kSelectGroup, uint32_t>(data, p.offs, p.rows, p.out_offs, lo, hi, e0, n_in, v);
-                if (n_in == kSelectGroup) {  // out is 16-byte aligned (checked by the launcher) and e0 a multiple of 4
-                    *reinterpret_cast<uint4*>(out + e0) = make_uint4(v[0], v[1], v[2], v[3]);
-                } else {  // the tail of the last tile
-                    for (uint32_t q = 0; q < n_in; q++) out[e0 + q] = v[q];
-                }
+                store_ids4(out, e0, v, n_in);
             }
-        }
-        __syncthreads();  // s_row is rewritten for the next tile
-    }
+        });
 }
-
-uint32_t capped_grid(uint64_t blocks) { return (uint32_t)(blocks < kSelectMaxBlocks ? (blocks ? blocks : 1) : kSelectMaxBlocks); }
 
 template <class T>
 hipError_t launch_fill(const SelectParams& p, uint64_t tile, hipStream_t stream) {
     if (p.n_out == 0) return hipSuccess;
     if (p.n_rows == 0 || p.n_src == 0 || (reinterpret_cast<uintptr_t>(p.out) & 15u)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(select_fill_kernel<T>, dim3(capped_grid((p.n_out + tile - 1) / tile)), dim3(kSelectBlock), 0, stream, p);
+    hipLaunchKernelGGL(select_fill_kernel<T>, dim3(grid_for(p.n_out, tile, kSelectMaxBlocks)), dim3(kSelectBlock), 0, stream, p);
     return hipGetLastError();
+}
+
+// out_offs[0 .. M]: the exclusive prefix sums of the selected rows' lengths, so out_offs[M] = T'.  temp == NULL: the size query
+hipError_t offsets_scan(const SelectParams& p, void* temp, size_t& temp_bytes, hipStream_t stream) {
+    return scan_of(SelectOutLen{p.offs, p.rows, p.n_src, p.n_rows}, p.n_rows + 1, p.out_offs, temp, temp_bytes, stream);
 }
 
 }  // namespace
 
 hipError_t select_scan_temp_bytes(uint64_t n_rows, size_t* bytes) {
+    SelectParams p = {};
+    p.n_rows = n_rows;
     *bytes = 0;
-    auto in = rocprim::make_transform_iterator(rocprim::counting_iterator<uint64_t>(0), SelectOutLen{nullptr, nullptr, 0, 0});
-    return rocprim::exclusive_scan(nullptr, *bytes, in, (uint64_t*)nullptr, (uint64_t)0, (size_t)(n_rows + 1), rocprim::plus<uint64_t>());
+    return offsets_scan(p, nullptr, *bytes, nullptr);
 }
 
 hipError_t launch_select_check(const SelectParams& p, unsigned long long* bad, hipStream_t stream) {
     if (p.n_rows == 0) return hipSuccess;
-    hipLaunchKernelGGL(select_check_kernel, dim3(capped_grid((p.n_rows + kSelectBlock - 1) / kSelectBlock)), dim3(kSelectBlock), 0, stream, p, bad);
+    hipLaunchKernelGGL(select_check_kernel, dim3(grid_for(p.n_rows, kSelectBlock, kSelectMaxBlocks)), dim3(kSelectBlock), 0, stream, p, bad);
     return hipGetLastError();
 }
 
-// out_offs[0 .. M]: the exclusive prefix sums of the selected rows' lengths, so out_offs[M] = T'
 hipError_t launch_select_offsets(const SelectParams& p, void* temp, size_t temp_bytes, hipStream_t stream) {
-    auto in = rocprim::make_transform_iterator(rocprim::counting_iterator<uint64_t>(0), SelectOutLen{p.offs, p.rows, p.n_src, p.n_rows});
-    return rocprim::exclusive_scan(temp, temp_bytes, in, p.out_offs, (uint64_t)0, (size_t)(p.n_rows + 1), rocprim::plus<uint64_t>(), stream);
+    return offsets_scan(p, temp, temp_bytes, stream);
 }
 
 hipError_t launch_select_fill_ids(const SelectParams& p, hipStream_t stream) { return launch_fill<uint32_t>(p, kSelectTile, stream); }
@@ -168,7 +144,7 @@ hipError_t launch_select_fill_text(const SelectParams& p, hipStream_t stream) { 
 
 hipError_t launch_select_lengths(const uint64_t* offs, uint64_t n_src, int64_t* lengths, hipStream_t stream) {
     if (n_src == 0) return hipSuccess;
-    hipLaunchKernelGGL(select_lengths_kernel, dim3(capped_grid((n_src + kSelectBlock - 1) / kSelectBlock)), dim3(kSelectBlock), 0, stream, offs, n_src,
+    hipLaunchKernelGGL(select_lengths_kernel, dim3(grid_for(n_src, kSelectBlock, kSelectMaxBlocks)), dim3(kSelectBlock), 0, stream, offs, n_src,
                        lengths);
     return hipGetLastError();
 }
@@ -186,7 +162,7 @@ hipError_t shuffle_sort_temp_bytes(uint64_t n, size_t* bytes) {
 hipError_t launch_shuffled_rows(uint64_t n, uint64_t seed, uint64_t* keys_in, uint64_t* keys_out, int64_t* vals_in, int64_t* rows, void* temp,
                                 size_t temp_bytes, hipStream_t stream) {
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(shuffle_keys_kernel, dim3(capped_grid((n + kSelectBlock - 1) / kSelectBlock)), dim3(kSelectBlock), 0, stream, n, seed, keys_in,
+    hipLaunchKernelGGL(shuffle_keys_kernel, dim3(grid_for(n, kSelectBlock, kSelectMaxBlocks)), dim3(kSelectBlock), 0, stream, n, seed, keys_in,
                        vals_in);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;

@@ -121,7 +121,6 @@ __host__ __device__ inline SpanPair span_window_at(const LayoutSeq& seq, const u
 // The row that owns element j is the largest i with offs[i] <= j: pack_find_row / pack_advance of layout.h with A = 0.
 constexpr uint32_t kSpanGroup = 4;             // consecutive elements of a thread slot: 32 bytes of i32 pairs, 64 of i64
 constexpr uint32_t kSpanTile = kPackTile;      // elements per tile: the kernel's block of 256 threads x 4 elements
-__host__ __device__ inline uint64_t span_tile_last(uint64_t t0, uint64_t n) { return t0 + kSpanTile - 1 < n ? t0 + kSpanTile - 1 : n - 1; }
 
 // A thread slot's walk: v[k] = the span of element e0 + k for k < n_in <= kSpanGroup.  lo / hi: the rows that own the
 // first and last element of the slot's tile.  Every sum is read once (an element's end is the next one's start) and the

@@ -98,7 +98,8 @@ __global__ __launch_bounds__(kSpanBlock) void span_window_kernel(SpanParams p, c
         store_pair<VEC>(out, e, span_window_at(seq, p.offs, wo, p.n_rows, p.sums, vals, p.len, stride, p.flags, e));
 }
 
-// T pairs in tiles of 1024 consecutive elements.  Two threads search all S rows for the owners of the tile's first and
+// T pairs in tiles of 1024 consecutive elements: the tiled fill of DESIGN.md, section L.9, in a copy of its own
+// (tile_fill.h's template measured slower here: profiles/tile_fill).  Two threads search all S rows for the owners of the tile's first and
 // last element; the others then search between those two, which for rows of more than a few tokens is a handful of rows.
 template <class T, bool VEC>
 __global__ __launch_bounds__(kSpanBlock) void span_flat_kernel(SpanParams p) {
@@ -109,7 +110,7 @@ __global__ __launch_bounds__(kSpanBlock) void span_flat_kernel(SpanParams p) {
     const uint64_t n_tiles = (n + kSpanTile - 1) / kSpanTile;
     for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const uint64_t t0 = tile * kSpanTile;
-        if (threadIdx.x < 2) s_row[threadIdx.x] = pack_find_row(p.offs, 0, 0, p.n_rows - 1, threadIdx.x ? span_tile_last(t0, n) : t0);
+        if (threadIdx.x < 2) s_row[threadIdx.x] = pack_find_row(p.offs, 0, 0, p.n_rows - 1, threadIdx.x ? tile_last(t0, kSpanTile, n) : t0);
         __syncthreads();
         const uint64_t e0 = t0 + (uint64_t)threadIdx.x * kSpanGroup;
         if (e0 < n) {
@@ -131,8 +132,6 @@ __global__ __launch_bounds__(kSpanBlock) void span_flat_kernel(SpanParams p) {
 }
 
 bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-uint32_t capped_grid(uint64_t blocks) { return (uint32_t)(blocks < kSpanMaxBlocks ? (blocks ? blocks : 1) : kSpanMaxBlocks); }
-uint32_t grid_for(uint64_t slots) { return capped_grid((slots + kSpanBlock - 1) / kSpanBlock); }
 
 }  // namespace
 
@@ -147,7 +146,7 @@ hipError_t launch_span_sums(const SpanParams& p, void* temp, size_t temp_bytes, 
     if (p.n == 0) return hipErrorInvalidValue;
     hipError_t e = hipMemsetAsync(p.vals + p.n, 0, 4, stream);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(span_meta_kernel, dim3(grid_for(p.n)), dim3(kSpanBlock), 0, stream, p);
+    hipLaunchKernelGGL(span_meta_kernel, dim3(grid_for(p.n, kSpanBlock, kSpanMaxBlocks)), dim3(kSpanBlock), 0, stream, p);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     auto in = rocprim::make_transform_iterator((const uint32_t*)p.vals, SpanValue());
     return rocprim::exclusive_scan(temp, temp_bytes, in, p.sums, (uint64_t)0, (size_t)(p.n + 1), rocprim::plus<uint64_t>(), stream);
@@ -155,7 +154,7 @@ hipError_t launch_span_sums(const SpanParams& p, void* temp, size_t temp_bytes, 
 
 hipError_t launch_span_row_max(const SpanParams& p, hipStream_t stream) {
     if (p.n_rows == 0) return hipSuccess;
-    hipLaunchKernelGGL(span_row_max_kernel, dim3(grid_for(p.n_rows)), dim3(kSpanBlock), 0, stream, p);
+    hipLaunchKernelGGL(span_row_max_kernel, dim3(grid_for(p.n_rows, kSpanBlock, kSpanMaxBlocks)), dim3(kSpanBlock), 0, stream, p);
     return hipGetLastError();
 }
 
@@ -163,7 +162,7 @@ hipError_t launch_span_flat(const SpanParams& p, hipStream_t stream) {
     if (p.n == 0 || p.n_rows == 0) return hipSuccess;
     const bool i64 = (p.flags & kLayoutI64) != 0;
     const bool vec = aligned(p.out, 16);
-    const uint32_t grid = capped_grid((p.n + kSpanTile - 1) / kSpanTile);
+    const uint32_t grid = grid_for(p.n, kSpanTile, kSpanMaxBlocks);
     auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(kSpanBlock), 0, stream, p); };
     if (i64)
         vec ? launch(span_flat_kernel<int64_t, true>) : launch(span_flat_kernel<int64_t, false>);
@@ -177,7 +176,7 @@ hipError_t launch_span_pad(const SpanParams& p, hipStream_t stream) {
     if (total == 0 || p.n == 0) return hipSuccess;
     const bool i64 = (p.flags & kLayoutI64) != 0;
     const bool vec = aligned(p.out, i64 ? 16 : 8);
-    const uint32_t grid = grid_for(total);
+    const uint32_t grid = grid_for(total, kSpanBlock, kSpanMaxBlocks);
     auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(kSpanBlock), 0, stream, p, total); };
     if (i64)
         vec ? launch(span_pad_kernel<int64_t, true>) : launch(span_pad_kernel<int64_t, false>);
@@ -191,7 +190,7 @@ hipError_t launch_span_windows(const SpanParams& p, const uint64_t* wo, uint32_t
     if (total == 0 || p.n == 0 || p.n_rows == 0) return hipSuccess;
     const bool i64 = (p.flags & kLayoutI64) != 0;
     const bool vec = aligned(p.out, i64 ? 16 : 8);
-    const uint32_t grid = grid_for(total);
+    const uint32_t grid = grid_for(total, kSpanBlock, kSpanMaxBlocks);
     auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(kSpanBlock), 0, stream, p, wo, stride, total); };
     if (i64)
         vec ? launch(span_window_kernel<int64_t, true>) : launch(span_window_kernel<int64_t, false>);

@@ -888,12 +888,23 @@ tgx_status read_u64(hipStream_t hs, const void* d_src, void* host_words, size_t 
     return TGX_OK;
 }
 
-tgx_status scan_room(ScanScratch* s, StreamGuard& guard, hipError_t (*temp_bytes)(uint64_t, size_t*), uint64_t n) {
-    if (n <= s->n) return TGX_OK;
+namespace {
+template <class Guard>
+tgx_status scan_room_of(ScanScratch* s, Guard& guard, hipError_t (*temp_bytes)(uint64_t, size_t*), uint64_t n, const char* oom) {
+    if (s->ptr && n <= s->n) return TGX_OK;
     if (temp_bytes(n, &s->bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "scan temp-size query failed");
-    HIP_TRY(guard.alloc(s->bytes, &s->ptr));  // (never NULL: that asks the scan for its size)
+    const hipError_t e = guard.alloc(s->bytes, &s->ptr);  // (never NULL: that asks the scan for its size)
+    if (e != hipSuccess && oom) return fail(TGX_ERR_DEVICE, "%s", oom);
+    HIP_TRY(e);
     s->n = n;
     return TGX_OK;
+}
+}  // namespace
+tgx_status scan_room(ScanScratch* s, StreamGuard& guard, hipError_t (*temp_bytes)(uint64_t, size_t*), uint64_t n, const char* oom) {
+    return scan_room_of(s, guard, temp_bytes, n, oom);
+}
+tgx_status scan_room(ScanScratch* s, Pass& pass, hipError_t (*temp_bytes)(uint64_t, size_t*), uint64_t n, const char* oom) {
+    return scan_room_of(s, pass, temp_bytes, n, oom);
 }
 
 }  // namespace tgx::dev
