@@ -516,6 +516,75 @@ tgx_status tgx_select_host(const uint32_t *ids, const uint64_t *offs, uint64_t n
 tgx_status tgx_select_text_host(const uint8_t *text, const uint64_t *offs, uint64_t n_rows, const int64_t *rows,
                                 uint64_t n_select, uint8_t *out_text, uint64_t text_cap, uint64_t *out_offs);
 
+/* ---- exact row deduplication on the device: of a result or of a corpus (csrc/dedup.hip) ------------------------------
+ * The mask that drops duplicate documents, made where the documents are.  For a corpus c, S rows are given by byte
+ * offsets o[0..S] over its text; for a result r, S rows by id offsets over its u32 ids.  Two rows are EQUAL iff they have
+ * the same length and the same elements; two empty rows are equal.
+ *
+ *     first[k] = min { i : row i equals row k }        (int64, 0 <= first[k] <= k)
+ *     n_unique = #{ k : first[k] == k }
+ *
+ * The result is exact: a hash only finds candidates, and every first[k] != k rests on an element-by-element comparison.
+ * first == arange(S) selects the unique rows (tgx_result_select, tgx_corpus_select), and a histogram of first gives the
+ * group sizes.
+ *
+ * tgx_corpus_first_equal_device(c, flags, stream, d_first, &n_unique), tgx_result_first_equal_device(r, ...):
+ *   d_first is caller-owned device memory on the object's device, int64[S], checked with hipPointerGetAttributes before
+ *   anything is queued, as the destination of tgx_result_lengths_device.  S = 0 writes nothing, and d_first may then be
+ *   NULL.  n_unique is host memory and may be NULL.  flags must be 0.  The stream rule is that of the select block: the
+ *   work is queued on stream (NULL: the library's blocking stream), the call returns after the stream has reached its
+ *   end, and the calling thread's current device is unchanged.  The object is only read; the corpus call holds the
+ *   corpus's lock, as tgx_corpus_select does.  An n-best result is accepted: its rows are rows.
+ *   Without a device: TGX_ERR_DEVICE (asked first).  A NULL handle, unknown flags, d_first NULL with S > 0 or memory of
+ *   the wrong kind: TGX_ERR_INVALID.  S >= 2^32 - 1: TGX_ERR_UNSUPPORTED.  Out of device memory: TGX_ERR_DEVICE, with
+ *   nothing kept.  Scratch is about 46 bytes per row plus the sort's temporaries, allocated once per call.
+ *   Rounds over a list of unresolved rows, ascending by row, all rows at first: (1) the key of every listed row, the top
+ *   bits of tgx_row_hash with the round's number as seed; (2) a stable radix sort of (key, row), so each run of equal keys
+ *   begins with its smallest row, its head; (3) every other row of a run compared with the head, lengths first; (4) a head
+ *   gets first = itself, a row equal to its head first = the head, and the rows that differ form the next round's list.
+ *   One host visit per round reads how many are left.  Equal rows share a key in every round and so the same verdict
+ *   against the same head: the unresolved rows are closed under equality, a head has no equal row before it, and
+ *   first is the minimum.  Every round resolves its heads, so the rounds end; with 64 key bits a second round takes a
+ *   collision of two 64-bit hashes.
+ *
+ * tgx_row_hash(bytes, n, seed), an exported function, the same on every machine.  All arithmetic wraps at 2^64;
+ *   R(x) is the three xor-shift / multiply rounds of tgx_dropout_u01 (x ^= x>>30; x *= 0xBF58476D1CE4E5B9; x ^= x>>27;
+ *   x *= 0x94D049BB133111EB; x ^= x>>31).
+ *     s    = R(seed ^ TGX_DEDUP_SALT)
+ *     w_j  = bytes[8j .. 8j+8) as a little-endian u64, bytes past n read as 0,   j < W = ceil(n/8)
+ *     acc  = the sum over j < W of  R( w_j ^ ((j+1)·0x9E3779B97F4A7C15) ^ s )
+ *     hash = R( acc ^ (n·0xC2B2AE3D27D4EB4F) ^ s )
+ *   A term depends only on a word and its position in the row, so a row of any length is hashed by any number of
+ *   threads in any order, and integer addition gives the same bits every time.  A row of a result is hashed as the 4·n_i
+ *   little-endian bytes of its ids.  (Rows that differ only in trailing zero bytes have equal sums: n tells them apart.)
+ * tgx_corpus_row_hashes_device(c, seed, stream, d_hashes), tgx_result_row_hashes_device(r, ...) write the hash of every
+ *   row as u64[S] into caller-owned device memory; checks and stream rule as above.  With an all-gather they are a
+ *   probabilistic deduplication across ranks; an exact one is not offered.
+ *
+ * tgx_first_equal_host(data, elem_bytes, offs, n_rows, hash_bits, first, &n_unique, &n_rounds): the host twin, no
+ *   device, over data of elem_bytes 1 (bytes) or 4 (u32, 4-byte aligned) and offs u64[n_rows + 1] in elements (offs[0] = 0
+ *   and ascending, as the select twins check).  It runs the device's rounds through the same header (csrc/dedup.h: the
+ *   hash in the kernel's tiles, the key of hash_bits bits, the run, compare and resolve rules); n_rounds is how many it
+ *   took.  hash_bits 0 makes every row collide: the rounds then number the distinct contents.  hash_bits > 64 or another
+ *   elem_bytes gives TGX_ERR_INVALID.  n_unique and n_rounds may be NULL; first may be NULL when n_rows = 0.
+ *
+ * tgx_dedup_last_times: device time of the calling thread's last first_equal call per stage, summed over its rounds, as
+ * tgx_select_last_times (the names are listed without a call): dedup_hash_kernel (the padded offsets' scan, the hash
+ * kernel, the keys), dedup_sort, dedup_compare_kernel (the runs, the compare offsets' scan, the compare), dedup_resolve
+ * (first, and the next list's compaction).  tgx_dedup_last_rounds: the rounds that call took. */
+#define TGX_DEDUP_SALT 0xA0761D6478BD642FULL
+tgx_status tgx_corpus_first_equal_device(tgx_corpus *c, uint32_t flags, void *stream, int64_t *d_first,
+                                         uint64_t *n_unique);
+tgx_status tgx_result_first_equal_device(const tgx_result *r, uint32_t flags, void *stream, int64_t *d_first,
+                                         uint64_t *n_unique);
+uint64_t tgx_row_hash(const uint8_t *bytes, uint64_t n, uint64_t seed);
+tgx_status tgx_corpus_row_hashes_device(tgx_corpus *c, uint64_t seed, void *stream, uint64_t *d_hashes);
+tgx_status tgx_result_row_hashes_device(const tgx_result *r, uint64_t seed, void *stream, uint64_t *d_hashes);
+tgx_status tgx_first_equal_host(const void *data, uint32_t elem_bytes, const uint64_t *offs, uint64_t n_rows,
+                                uint32_t hash_bits, int64_t *first, uint64_t *n_unique, uint32_t *n_rounds);
+int tgx_dedup_last_times(const char **names, float *ms, int cap);
+uint32_t tgx_dedup_last_rounds(void);
+
 /* ---- the front end on the device: a resident corpus split at special tokens, CRLF applied (csrc/front.hip) --------
  * What tgx_split_specials and tgx_pack_segments compute on host threads, for a corpus that is already in HBM (an upload,
  * or tgx_corpus_from_text of a decoded text), with the plan kept on the device for tgx_assemble_result_plan: a resident

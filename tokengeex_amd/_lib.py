@@ -174,6 +174,14 @@ SYMBOLS = {
     "tgx_shuffled_rows_host": (_i, [_u64, _u64, _vp]),
     "tgx_select_host": (_i, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp]),
     "tgx_select_text_host": (_i, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp]),
+    "tgx_corpus_first_equal_device": (_i, [_vp, _u32, _vp, _vp, C.POINTER(C.c_uint64)]),
+    "tgx_result_first_equal_device": (_i, [_vp, _u32, _vp, _vp, C.POINTER(C.c_uint64)]),
+    "tgx_row_hash": (_u64, [_vp, _u64, _u64]),
+    "tgx_corpus_row_hashes_device": (_i, [_vp, _u64, _vp, _vp]),
+    "tgx_result_row_hashes_device": (_i, [_vp, _u64, _vp, _vp]),
+    "tgx_first_equal_host": (_i, [_vp, _u32, _vp, _u64, _u32, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
+    "tgx_dedup_last_times": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_float), _i]),
+    "tgx_dedup_last_rounds": (_u32, []),
 }
 
 
@@ -554,6 +562,42 @@ def select_last_times() -> dict[str, float]:
     ms = (C.c_float * 8)()
     n = lib.tgx_select_last_times(names, ms, 8)
     return {names[i].decode(): float(ms[i]) for i in range(n)}
+
+
+def first_equal_host(data: np.ndarray, offs: np.ndarray, hash_bits: int = 64):
+    """Host twin of NativeCorpus.first_equal / NativeResult.first_equal (tgx_first_equal_host: the device's rounds through
+    the same header, no device) over data u8[N] or u32[T] and offsets u64[S+1] in elements -> (first int64[S], n_unique,
+    n_rounds).  hash_bits: bits of the row hash that make the sort key (0: every row collides)."""
+    data = np.ascontiguousarray(data)
+    if data.dtype not in (np.uint8, np.uint32):
+        raise TypeError(f"data must be uint8 or uint32 (got {data.dtype})")
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    n = max(offs.shape[0] - 1, 0)
+    first = np.empty(n, np.int64)
+    nu, nr = C.c_uint64(), C.c_uint32()
+    check(lib.tgx_first_equal_host(ptr(data) if data.size else None, data.dtype.itemsize, ptr(offs) if offs.size else None, n, int(hash_bits),
+                                   ptr(first) if n else None, C.byref(nu), C.byref(nr)))
+    return first, int(nu.value), int(nr.value)
+
+
+def row_hash(data: bytes, seed: int = 0) -> int:
+    """tgx_row_hash of a row's bytes under `seed`, a 64-bit integer (a row of ids: its little-endian u32 bytes)."""
+    data = bytes(data)
+    return lib.tgx_row_hash(data if data else None, len(data), int(seed) & (2**64 - 1))
+
+
+def dedup_last_times() -> dict[str, float]:
+    """Device time in ms of each stage of the calling thread's last first_equal, summed over its rounds
+    (tgx_dedup_last_times)."""
+    names = (C.c_char_p * 8)()
+    ms = (C.c_float * 8)()
+    n = lib.tgx_dedup_last_times(names, ms, 8)
+    return {names[i].decode(): float(ms[i]) for i in range(n)}
+
+
+def dedup_last_rounds() -> int:
+    """Rounds of the calling thread's last first_equal (tgx_dedup_last_rounds)."""
+    return int(lib.tgx_dedup_last_rounds())
 
 
 def front_host(flat: np.ndarray, offs: np.ndarray, specials: list[bytes], crlf: bool):
@@ -1105,6 +1149,19 @@ class NativeResult:
         pointer; tgx_result_lengths_device), queued on `stream` as in pad_device."""
         check(lib.tgx_result_lengths_device(self._h, stream or None, ptr_ or None))
 
+    # -- exact row deduplication (include/tgx.h: tgx_result_first_equal_device; csrc/dedup.hip) --
+    def first_equal(self, d_first: int, *, stream: int = 0) -> int:
+        """first[k] = the first row with row k's ids, as int64[S] into caller-owned device memory (a raw integer pointer;
+        tgx_result_first_equal_device), queued on `stream` as in pad_device -> the number of distinct rows."""
+        nu = C.c_uint64()
+        check(lib.tgx_result_first_equal_device(self._h, 0, stream or None, d_first or None, C.byref(nu)))
+        return int(nu.value)
+
+    def row_hashes(self, d_hashes: int, seed: int = 0, *, stream: int = 0) -> None:
+        """tgx_row_hash of every row's ids under `seed`, as u64[S] into caller-owned device memory
+        (tgx_result_row_hashes_device)."""
+        check(lib.tgx_result_row_hashes_device(self._h, int(seed) & (2**64 - 1), stream or None, d_hashes or None))
+
     def pad_host(self, row_len: int, pad_id: int, **kw) -> dict:
         """layout_pad_host over the ids and offsets copied to the host."""
         return layout_pad_host(self.ids(), self.offsets(), row_len, pad_id, **kw)
@@ -1284,6 +1341,19 @@ class NativeCorpus:
         c._h = hc
         c.device = self.device
         return c
+
+    def first_equal(self, d_first: int, *, stream: int = 0) -> int:
+        """first[k] = the first sample with sample k's bytes, as int64[S] into caller-owned device memory (a raw integer
+        pointer; tgx_corpus_first_equal_device), queued on `stream` -> the number of distinct samples.  With the same
+        indices, corpus and result stay aligned.  This corpus is only read."""
+        nu = C.c_uint64()
+        check(lib.tgx_corpus_first_equal_device(self._h, 0, stream or None, d_first or None, C.byref(nu)))
+        return int(nu.value)
+
+    def row_hashes(self, d_hashes: int, seed: int = 0, *, stream: int = 0) -> None:
+        """tgx_row_hash of every sample under `seed`, as u64[S] into caller-owned device memory
+        (tgx_corpus_row_hashes_device)."""
+        check(lib.tgx_corpus_row_hashes_device(self._h, int(seed) & (2**64 - 1), stream or None, d_hashes or None))
 
     def normalize(self, form: str) -> "NativeCorpus":
         """The corpus under a Unicode normalisation form ("nfd", "nfc", "nfkd", "nfkc") on the device (tgx_corpus_normalize,

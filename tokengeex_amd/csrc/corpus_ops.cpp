@@ -1,5 +1,5 @@
 // The C ABI's transforms of a resident corpus (include/tgx.h): its read-backs, a corpus from decoded text, the front end
-// (special-token split and CRLF), Unicode normalisation, row selection, and the split plan's handle.  They run on a stream of their own
+// (special-token split and CRLF), Unicode normalisation, row selection, row deduplication, and the split plan's handle.  They run on a stream of their own
 // under a StreamGuard and share device_internal.h with the passes (tgx_api.cpp, encode_pass.cpp, estep_pass.cpp, lattice_pass.cpp).
 #include <hip/hip_runtime.h>
 
@@ -13,6 +13,7 @@
 #include "../../include/tgx.h"
 #include "api_internal.h"
 #include "device_internal.h"
+#include "dedup.h"
 #include "front.h"
 #include "kernels.h"
 #include "norm.h"
@@ -437,6 +438,27 @@ tgx_status tgx_corpus_select(tgx_corpus* c, const int64_t* rows, uint64_t n_sele
     timer.read();
     *out = made_owner.release();
     return TGX_OK;
+}
+
+// ---- exact row deduplication: samples of a corpus (dedup.hip; dedup.h; result_ops.cpp has the rounds) ------------------
+
+tgx_status tgx_corpus_first_equal_device(tgx_corpus* c, uint32_t flags, void* stream, int64_t* d_first, uint64_t* n_unique) {
+    const char* who = "tgx_corpus_first_equal_device";
+    tgx_status st = require_device();
+    if (st != TGX_OK) return st;
+    if (!c) return fail(TGX_ERR_INVALID, "%s: corpus is NULL", who);
+    if ((st = layout_check_flags(who, flags, 0)) != TGX_OK) return st;
+    std::lock_guard<std::mutex> lkc(c->mu);
+    return dedup_first_equal(who, tgx::DedupRows{c->d_text, c->d_offs.get(), c->n_samples, c->n_bytes, 1}, c->device, stream, d_first, n_unique);
+}
+
+tgx_status tgx_corpus_row_hashes_device(tgx_corpus* c, uint64_t seed, void* stream, uint64_t* d_hashes) {
+    const char* who = "tgx_corpus_row_hashes_device";
+    const tgx_status st = require_device();
+    if (st != TGX_OK) return st;
+    if (!c) return fail(TGX_ERR_INVALID, "%s: corpus is NULL", who);
+    std::lock_guard<std::mutex> lkc(c->mu);
+    return dedup_row_hashes(who, tgx::DedupRows{c->d_text, c->d_offs.get(), c->n_samples, c->n_bytes, 1}, c->device, seed, stream, d_hashes);
 }
 
 // ---- the split plan (tgx_corpus_split_specials makes it, tgx_assemble_result_plan reads it) ------------------------

@@ -27,6 +27,10 @@
                         hipGetErrorString(_e), __FILE__, __LINE__, #expr);                \
     } while (0)
 
+namespace tgx {
+struct DedupRows;  // dedup.h
+}
+
 namespace tgx::dev {
 
 // ---- device buffer pool (tgx_api.cpp) --------------------------------------------
@@ -434,6 +438,13 @@ tgx_status select_rows_device(const char* who, const int64_t* rows, uint64_t n_s
 // The bad-index word of device rows: what select_check_kernel left (kSelectNoBad: every index in range) -> TGX_OK, or
 // TGX_ERR_INVALID naming k and rows[k], which is read from the device for the message.
 tgx_status select_bad_index(const char* who, uint64_t bad_k, const int64_t* d_rows, uint64_t n_src, hipStream_t hs);
+
+// ---- exact row deduplication (result_ops.cpp; the corpus's entry points in corpus_ops.cpp share it) ---------------------
+// The rounds of tgx_*_first_equal_device and the hashes of tgx_*_row_hashes_device over the rows of a result or of a
+// corpus (dedup.h: DedupRows), on the caller's stream under a StreamGuard of their own.  The handle, the flags and a
+// device have been checked; the destination is checked here, before anything is queued.
+tgx_status dedup_first_equal(const char* who, const tgx::DedupRows& rows, int device, void* stream, int64_t* d_first, uint64_t* n_unique);
+tgx_status dedup_row_hashes(const char* who, const tgx::DedupRows& rows, int device, uint64_t seed, void* stream, uint64_t* d_hashes);
 
 // ---- corpora (tgx_api.cpp) ----------------------------------------------------------
 // a copy on the device's copy stream of that direction, and the stream's end

@@ -1,8 +1,8 @@
 // The *_host twins of the result-side device entry points (include/tgx.h): tgx_layout_pad_host, tgx_layout_pack_host,
-// tgx_layout_windows_host, tgx_assemble_host, tgx_fim_host, tgx_select_host, tgx_select_text_host, tgx_shuffled_rows_host, tgx_decode_rows_host, tgx_spans_host, tgx_window_spans_host, tgx_front_host,
+// tgx_layout_windows_host, tgx_assemble_host, tgx_fim_host, tgx_select_host, tgx_select_text_host, tgx_shuffled_rows_host, tgx_first_equal_host, tgx_decode_rows_host, tgx_spans_host, tgx_window_spans_host, tgx_front_host,
 // tgx_normalize_host and tgx_lattice_stats_host, and the
 // argument checks they share with the device entry points of tgx_api.cpp.  A twin goes through the same index arithmetic as its kernels (layout.h, assemble.h,
-// fim.h, select.h, decode.h, spans.h, front.h, norm.h) on host memory.  Nothing in this file calls a HIP function, so it builds and runs without the
+// fim.h, select.h, dedup.h, decode.h, spans.h, front.h, norm.h) on host memory.  Nothing in this file calls a HIP function, so it builds and runs without the
 // handles, the pool or a device.
 #define TGX_HOST_ONLY  // tile_fill.h: the host loop, no kernel side
 #include <algorithm>
@@ -15,6 +15,7 @@
 #include "api_internal.h"
 #include "assemble.h"
 #include "decode.h"
+#include "dedup.h"
 #include "fim.h"
 #include "front.h"
 #include "layout.h"
@@ -585,6 +586,116 @@ tgx_status tgx_shuffled_rows_host(uint64_t n, uint64_t seed, int64_t* rows) {
         rows[g] = (int64_t)g;
     }
     std::stable_sort(rows, rows + n, [&keys](int64_t a, int64_t b) { return keys[a] < keys[b]; });
+    return TGX_OK;
+}
+
+// ---- exact row deduplication -----------------------------------------------------------
+
+uint64_t tgx_row_hash(const uint8_t* bytes, uint64_t n, uint64_t seed) { return tgx::dedup_row_hash_host(n ? bytes : nullptr, bytes ? n : 0, seed); }
+
+namespace {
+
+// the compare of one round: the candidates' concatenated elements in the kernel's tiles and slots, every slot walked
+// element by element (the kernel compares a slot inside one candidate 16 bytes at once, to the same flags)
+template <class T>
+void dedup_compare_host(const void* data, const uint64_t* offs, const uint32_t* rows, const uint32_t* head_row, const uint64_t* cmp_offs, uint64_t L,
+                        uint8_t* flag) {
+    constexpr bool kText = sizeof(T) == 1;
+    const uint64_t n_cmp = cmp_offs[L];
+    tgx::tiled_fill_host(
+        n_cmp, n_cmp, kText ? tgx::kDedupCmpByteTile : tgx::kDedupCmpTile, kText ? tgx::kDedupCmpByteGroup : tgx::kDedupCmpGroup, 0,
+        [&](uint64_t j) { return tgx::pack_find_row(cmp_offs, 0, 0, L - 1, j); },
+        [&](uint64_t lo, uint64_t hi, uint64_t e0, uint32_t n_in) {
+            tgx::DedupCursor cur;
+            tgx::dedup_compare_walk<T>(cur, static_cast<const T*>(data), offs, rows, head_row, cmp_offs, lo, hi, e0, n_in, flag);
+            return true;
+        });
+}
+
+}  // namespace
+
+tgx_status tgx_first_equal_host(const void* data, uint32_t elem_bytes, const uint64_t* offs, uint64_t n_rows, uint32_t hash_bits, int64_t* first,
+                                uint64_t* n_unique, uint32_t* n_rounds) {
+    const char* who = "tgx_first_equal_host";
+    if (n_unique) *n_unique = 0;
+    if (n_rounds) *n_rounds = 0;
+    if (elem_bytes != 1 && elem_bytes != 4) return fail(TGX_ERR_INVALID, "%s: elem_bytes %u is neither 1 nor 4", who, elem_bytes);
+    if (hash_bits > 64) return fail(TGX_ERR_INVALID, "%s: hash_bits %u is more than 64", who, hash_bits);
+    const tgx_status st = check_packed_list(who, "offs", "offsets", offs, n_rows, true);
+    if (st != TGX_OK) return st;
+    const uint64_t S = n_rows;
+    if (S >= 0xFFFFFFFFull) return fail(TGX_ERR_UNSUPPORTED, "%s: more than 2^32-1 rows", who);
+    if (offs[S] && !data) return fail(TGX_ERR_INVALID, "%s: data is NULL", who);
+    if (S && !first) return fail(TGX_ERR_INVALID, "%s: first is NULL", who);
+    const uint8_t* bytes = static_cast<const uint8_t*>(data);
+    std::vector<uint32_t> list, next, rows_a(S), rows_b(S), head_row(S), order(S);
+    std::vector<uint64_t> keys_a(S), keys_b(S), offs_tmp(S + 1);
+    std::vector<uint8_t> flag(S), mark(S);
+    const uint32_t* lp = nullptr;  // round 0: every row
+    uint64_t L = S, heads = 0;
+    uint32_t round = 0;
+    while (L) {
+        // the hash: the sums over the padded bytes in the kernel's tiles and slots, then the keys
+        const uint64_t s = tgx::dedup_seed(round);
+        offs_tmp[0] = 0;
+        for (uint64_t k = 0; k < L; k++) offs_tmp[k + 1] = offs_tmp[k] + tgx::dedup_pad_len(offs, elem_bytes, lp, L, k);
+        std::fill(keys_a.begin(), keys_a.begin() + L, 0);
+        const uint64_t n_pad = offs_tmp[L];
+        uint64_t owner_before = 0;  // the tiles' edges ascend: each owner is found from the one before, as the kernel's
+        tgx::tiled_fill_host(
+            n_pad, n_pad, tgx::kDedupTile, tgx::kDedupGroup, 0,
+            [&](uint64_t j) { return owner_before = tgx::dedup_find_from(offs_tmp.data(), owner_before, L - 1, j); },
+            [&](uint64_t lo, uint64_t hi, uint64_t e0, uint32_t n_in) {
+                tgx::DedupSlot sl;
+                tgx::dedup_slot(offs_tmp.data(), lo, hi, e0, n_in, sl);
+                for (uint32_t q = 0; q < sl.n; q++) {
+                    const uint64_t r = tgx::dedup_listed(lp, sl.k[q]);
+                    keys_a[sl.k[q]] += tgx::dedup_term(tgx::dedup_word_host(bytes + offs[r] * elem_bytes, (offs[r + 1] - offs[r]) * elem_bytes, sl.j[q]), sl.j[q], s);
+                }
+                return true;
+            });
+        for (uint64_t k = 0; k < L; k++) {
+            const uint64_t r = tgx::dedup_listed(lp, k);
+            keys_a[k] = tgx::dedup_key(tgx::dedup_finish(keys_a[k], (offs[r + 1] - offs[r]) * elem_bytes, s), hash_bits);
+            rows_a[k] = (uint32_t)r;
+            order[k] = (uint32_t)k;
+        }
+        // the stable sort by key: each run begins with its smallest row
+        std::stable_sort(order.begin(), order.begin() + L, [&keys_a](uint32_t x, uint32_t y) { return keys_a[x] < keys_a[y]; });
+        for (uint64_t i = 0; i < L; i++) {
+            keys_b[i] = keys_a[order[i]];
+            rows_b[i] = rows_a[order[i]];
+        }
+        // the runs, the compare of every candidate with its head, the resolve
+        for (uint64_t i = 0; i < L; i++) {
+            const uint64_t h = tgx::dedup_run_head(keys_b.data(), i);
+            head_row[i] = rows_b[h];
+            flag[i] = (h != i && tgx::dedup_len_differs(offs, rows_b[i], rows_b[h])) ? 1 : 0;
+        }
+        offs_tmp[0] = 0;
+        for (uint64_t i = 0; i < L; i++) offs_tmp[i + 1] = offs_tmp[i] + tgx::dedup_cmp_len(offs, rows_b.data(), head_row.data(), flag.data(), L, i);
+        if (elem_bytes == 1)
+            dedup_compare_host<uint8_t>(data, offs, rows_b.data(), head_row.data(), offs_tmp.data(), L, flag.data());
+        else
+            dedup_compare_host<uint32_t>(data, offs, rows_b.data(), head_row.data(), offs_tmp.data(), L, flag.data());
+        for (uint64_t i = 0; i < L; i++) {
+            const uint32_t r = rows_b[i];
+            mark[r] = flag[i];
+            if (!flag[i]) first[r] = (int64_t)head_row[i];
+            if (head_row[i] == r) heads++;
+        }
+        next.clear();
+        for (uint64_t k = 0; k < L; k++) {
+            const uint64_t r = tgx::dedup_listed(lp, k);
+            if (mark[r]) next.push_back((uint32_t)r);
+        }
+        list.swap(next);
+        lp = list.data();
+        L = list.size();
+        round++;
+    }
+    if (n_unique) *n_unique = heads;
+    if (n_rounds) *n_rounds = round;
     return TGX_OK;
 }
 

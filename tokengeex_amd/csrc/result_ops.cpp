@@ -14,9 +14,11 @@
 #include "device_internal.h"
 #include "assemble.h"
 #include "decode.h"
+#include "dedup.h"
 #include "fim.h"
 #include "kernels.h"
 #include "layout.h"
+#include "pass_internal.h"  // (the knobs: TGX_DEDUP_HASH_BITS)
 #include "select.h"
 #include "spans.h"
 
@@ -833,6 +835,154 @@ tgx_status tgx_shuffled_rows_device(int device, uint64_t n, uint64_t seed, void*
     HIP_TRY(hipStreamSynchronize(hs));
     guard.done();
     return TGX_OK;
+}
+
+// ---- exact row deduplication: the first row with the same content (dedup.hip; dedup.h has the hash and the rules) ----
+
+namespace {
+
+const char* const kDedupStageNames[tgx::kDedupStages] = {"dedup_hash_kernel", "dedup_sort", "dedup_compare_kernel", "dedup_resolve"};
+thread_local float g_dedup_ms[tgx::kDedupStages] = {0, 0, 0, 0};
+thread_local uint32_t g_dedup_rounds = 0;
+
+// bits of the hash that make the sort key: 64, or the test knob's (a small number makes rows collide)
+uint32_t dedup_hash_bits() {
+    int bits = 64;
+    knob_int("TGX_DEDUP_HASH_BITS", 0, 64, &bits);
+    return (uint32_t)bits;
+}
+
+// what the calls on rows share before anything is queued: the limit on S, the destination
+tgx_status dedup_check_dest(const char* who, const char* what, const tgx::DedupRows& rows, const void* dest, int device) {
+    if (rows.n_rows >= 0xFFFFFFFFull) return fail(TGX_ERR_UNSUPPORTED, "%s: more than 2^32-1 rows", who);
+    if (!dest) return fail(TGX_ERR_INVALID, "%s: %s is NULL", who, what);
+    return check_device_ptr(who, what, dest, device, "source");
+}
+
+}  // namespace
+
+namespace tgx::dev {
+
+// The rounds.  The scratch is the guard's, allocated once and used by every round; a round ends in the one host visit
+// that reads how many rows are left (and the heads so far), after which the stages' times of that round are added up.
+tgx_status dedup_first_equal(const char* who, const tgx::DedupRows& rows, int device, void* stream, int64_t* d_first, uint64_t* n_unique) {
+    const uint64_t S = rows.n_rows;
+    if (n_unique) *n_unique = 0;
+    if (S == 0) {
+        g_dedup_rounds = 0;
+        std::fill(g_dedup_ms, g_dedup_ms + tgx::kDedupStages, 0.f);
+        return TGX_OK;
+    }
+    DeviceScope scope;
+    HIP_TRY(hipSetDevice(device));
+    tgx_status st = dedup_check_dest(who, "d_first", rows, d_first, device);
+    if (st != TGX_OK) return st;
+    const uint32_t bits = dedup_hash_bits();
+    hipStream_t hs = stream_or_default(stream, device);
+    unsigned long long h_words[2] = {0, 0};  // rows left, heads so far (before the guard: a copy writes them)
+    float round_ms[tgx::kDedupStages] = {0, 0, 0, 0}, total_ms[tgx::kDedupStages] = {0, 0, 0, 0};
+    StageTimer<tgx::kDedupStages> timer(hs, round_ms);  // (before the guard: its events outlive the stream's work)
+    StreamGuard guard(device, hs);
+    tgx::DedupScratch s = {};
+    if (tgx::dedup_temp_bytes(S, &s.scan_bytes, &s.sort_bytes, &s.select_bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "%s: temp-size query failed", who);
+    const bool got = guard.alloc((size_t)S * 8, &s.keys_a) == hipSuccess && guard.alloc((size_t)S * 8, &s.keys_b) == hipSuccess &&
+                     guard.alloc((size_t)S * 4, &s.rows_a) == hipSuccess && guard.alloc((size_t)S * 4, &s.rows_b) == hipSuccess &&
+                     guard.alloc((size_t)(S + 1) * 8, &s.offs_tmp) == hipSuccess && guard.alloc((size_t)S * 4, &s.head_row) == hipSuccess &&
+                     guard.alloc((size_t)S, &s.flag) == hipSuccess && guard.alloc((size_t)S, &s.mark) == hipSuccess &&
+                     guard.alloc((size_t)S * 4, &s.list[0]) == hipSuccess && guard.alloc((size_t)S * 4, &s.list[1]) == hipSuccess &&
+                     guard.alloc(2 * sizeof(unsigned long long), &s.words) == hipSuccess &&
+                     guard.alloc(s.scan_bytes + 8, &s.scan_tmp) == hipSuccess &&  // (never NULL: that asks for the size)
+                     guard.alloc(s.sort_bytes + 8, &s.sort_tmp) == hipSuccess && guard.alloc(s.select_bytes + 8, &s.select_tmp) == hipSuccess;
+    if (!got) {
+        (void)hipGetLastError();
+        return fail(TGX_ERR_DEVICE, "out of device memory (dedup)");
+    }
+    HIP_TRY(hipMemsetAsync(s.words, 0, 2 * sizeof(unsigned long long), hs));
+    const uint32_t* list = nullptr;  // round 0: every row
+    uint64_t n_list = S;
+    uint32_t round = 0;
+    while (n_list) {
+        uint32_t* next = s.list[round & 1];
+        timer.begin(0);
+        if (tgx::launch_dedup_hash(rows, list, n_list, round, bits, s.offs_tmp, s.scan_tmp, s.scan_bytes, s.keys_a, s.keys_a, s.rows_a, hs) != hipSuccess)
+            return fail(TGX_ERR_DEVICE, "dedup_hash_kernel launch failed");
+        timer.end(0);
+        timer.begin(1);
+        if (tgx::launch_dedup_sort(s, n_list, bits, hs) != hipSuccess) return fail(TGX_ERR_DEVICE, "dedup sort launch failed");
+        timer.end(1);
+        timer.begin(2);
+        if (tgx::launch_dedup_compare(rows, s, n_list, hs) != hipSuccess) return fail(TGX_ERR_DEVICE, "dedup_compare_kernel launch failed");
+        timer.end(2);
+        timer.begin(3);
+        if (tgx::launch_dedup_resolve(s, list, n_list, next, d_first, hs) != hipSuccess) return fail(TGX_ERR_DEVICE, "dedup resolve launch failed");
+        timer.end(3);
+        if ((st = read_u64(hs, s.words, h_words, 2)) != TGX_OK) return st;  // the round's host visit
+        timer.read();
+        for (int k = 0; k < tgx::kDedupStages; k++) total_ms[k] += round_ms[k];
+        round++;
+        if (h_words[0] >= n_list) {  // (every round resolves its heads)
+            guard.done();
+            return fail(TGX_ERR_DEVICE, "%s: round %u resolved no row", who, round);
+        }
+        n_list = h_words[0];
+        list = next;
+    }
+    guard.done();  // (the stream has reached its end)
+    std::copy(total_ms, total_ms + tgx::kDedupStages, g_dedup_ms);
+    g_dedup_rounds = round;
+    if (n_unique) *n_unique = h_words[1];
+    return TGX_OK;
+}
+
+tgx_status dedup_row_hashes(const char* who, const tgx::DedupRows& rows, int device, uint64_t seed, void* stream, uint64_t* d_hashes) {
+    const uint64_t S = rows.n_rows;
+    if (S == 0) return TGX_OK;
+    DeviceScope scope;
+    HIP_TRY(hipSetDevice(device));
+    tgx_status st = dedup_check_dest(who, "d_hashes", rows, d_hashes, device);
+    if (st != TGX_OK) return st;
+    hipStream_t hs = stream_or_default(stream, device);
+    StreamGuard guard(device, hs);
+    size_t scan_bytes = 0, sort_bytes = 0, select_bytes = 0;
+    if (tgx::dedup_temp_bytes(S, &scan_bytes, &sort_bytes, &select_bytes) != hipSuccess) return fail(TGX_ERR_DEVICE, "%s: temp-size query failed", who);
+    uint64_t *pad_offs = nullptr, *sums = nullptr;
+    void* scan_tmp = nullptr;
+    if (guard.alloc((size_t)(S + 1) * 8, &pad_offs) != hipSuccess || guard.alloc((size_t)S * 8, &sums) != hipSuccess ||
+        guard.alloc(scan_bytes + 8, &scan_tmp) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(TGX_ERR_DEVICE, "out of device memory (dedup)");
+    }
+    if (tgx::launch_dedup_hash(rows, nullptr, S, seed, 64, pad_offs, scan_tmp, scan_bytes, sums, d_hashes, nullptr, hs) != hipSuccess)
+        return fail(TGX_ERR_DEVICE, "dedup_hash_kernel launch failed");
+    HIP_TRY(hipStreamSynchronize(hs));
+    guard.done();
+    return TGX_OK;
+}
+
+}  // namespace tgx::dev
+
+int tgx_dedup_last_times(const char** names, float* ms, int cap) { return stage_times(kDedupStageNames, g_dedup_ms, tgx::kDedupStages, names, ms, cap); }
+uint32_t tgx_dedup_last_rounds(void) { return g_dedup_rounds; }
+
+namespace {
+tgx::DedupRows dedup_rows_of(const tgx_result* r) { return tgx::DedupRows{r->d_ids.get(), r->d_offs.get(), r->n_samples, r->n_tokens, 4}; }
+}  // namespace
+
+tgx_status tgx_result_first_equal_device(const tgx_result* r, uint32_t flags, void* stream, int64_t* d_first, uint64_t* n_unique) {
+    const char* who = "tgx_result_first_equal_device";
+    tgx_status st = require_device();
+    if (st != TGX_OK) return st;
+    if (!r) return fail(TGX_ERR_INVALID, "%s: result is NULL", who);
+    if ((st = layout_check_flags(who, flags, 0)) != TGX_OK) return st;
+    return dedup_first_equal(who, dedup_rows_of(r), r->device, stream, d_first, n_unique);
+}
+
+tgx_status tgx_result_row_hashes_device(const tgx_result* r, uint64_t seed, void* stream, uint64_t* d_hashes) {
+    const char* who = "tgx_result_row_hashes_device";
+    const tgx_status st = require_device();
+    if (st != TGX_OK) return st;
+    if (!r) return fail(TGX_ERR_INVALID, "%s: result is NULL", who);
+    return dedup_row_hashes(who, dedup_rows_of(r), r->device, seed, stream, d_hashes);
 }
 
 // ---- spans: the part of its row's text that every token covers (spans.hip; spans.h has the index arithmetic) ------

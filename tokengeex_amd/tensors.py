@@ -180,6 +180,37 @@ def shuffled_rows(n: int, seed: int, device=0):
     return out
 
 
+# ---- exact row deduplication on the device (csrc/dedup.hip) --------------------------------------------------------------
+
+def first_equal(obj):
+    """-> [S] torch.int64 on obj's device (a NativeResult or NativeCorpus): first[k] = the first row with exactly row k's
+    content, so first[k] == k marks the rows to keep and torch.bincount(first) gives the group sizes.  Exact: a hash
+    finds the candidates, an element-by-element comparison decides."""
+    import torch
+    dev = _device_of(torch, obj)
+    out = torch.empty((obj.num_samples,), dtype=torch.int64, device=dev)
+    obj.first_equal(out.data_ptr() if out.numel() else 0, stream=torch.cuda.current_stream(dev).cuda_stream)
+    return out
+
+
+def unique_rows(obj):
+    """-> torch.int64 indices, ascending, of the rows of obj that no earlier row equals: what `select` takes to drop the
+    duplicates (of a corpus and, with the same indices, of its encoded result)."""
+    import torch
+    first = first_equal(obj)
+    return (first == torch.arange(first.shape[0], dtype=torch.int64, device=first.device)).nonzero().reshape(-1)
+
+
+def row_hashes(obj, seed: int = 0):
+    """-> [S] torch.int64 on obj's device holding the u64 bits of tgx_row_hash(row, seed) of every row: the same on every
+    machine, for a deduplication across ranks after an all-gather (probabilistic, unlike first_equal)."""
+    import torch
+    dev = _device_of(torch, obj)
+    out = torch.empty((obj.num_samples,), dtype=torch.int64, device=dev)
+    obj.row_hashes(out.data_ptr() if out.numel() else 0, seed, stream=torch.cuda.current_stream(dev).cuda_stream)
+    return out
+
+
 def _window_len(max_length, stride) -> tuple[int, int]:
     if max_length is None:
         raise TypeError("max_length is required for overflow windows")
