@@ -585,6 +585,80 @@ tgx_status tgx_first_equal_host(const void *data, uint32_t elem_bytes, const uin
 int tgx_dedup_last_times(const char **names, float *ms, int cap);
 uint32_t tgx_dedup_last_rounds(void);
 
+/* ---- near-duplicate rows on the device: MinHash signatures, LSH bands, clusters (csrc/minhash.hip) --------------------
+ * What the exact deduplication above leaves: rows that are almost each other's copies (a licence header with another
+ * year, a fork with one line changed).  Three calls: a signature per row, the band keys and bucket heads of the
+ * signatures, and the clusters.  Everything is integer work, pinned here, the same bits on every machine.  All
+ * arithmetic wraps at 2^64; R is the three rounds of tgx_row_hash, G = 0x9E3779B97F4A7C15.
+ *
+ * Signatures.  tgx_result_minhash_device(r, width, n_perm, seed, flags, stream, d_sig), tgx_corpus_minhash_device(c, ...):
+ *   row i has n_i elements of eb bytes (eb = 1: a corpus's text bytes; eb = 4: a result's u32 ids, an n-best result's
+ *   rows being rows).  With w = width (1 <= w, w·eb <= 64) and K = n_perm (1 <= K <= 1024), row i has
+ *   m_i = max(1, n_i - w + 1) shingles, shingle t the elements [t, t + min(w, n_i)): a row shorter than w, the empty row
+ *   included, has exactly one shingle, its whole content.  Every row has a signature; no value is special.
+ *     h(i,t)    = tgx_row_hash of the shingle's min(w, n_i)·eb little-endian bytes under the seed  seed ^ TGX_MINHASH_SALT
+ *                 (the length in its last step tells short rows with trailing zeros apart)
+ *     s         = R(seed ^ TGX_MINHASH_SALT)
+ *     a_k       = R(s ^ (2k+1)·G) | 1,     b_k = R(s ^ (2k+2)·G)
+ *     v_k(h)    = (uint32_t)((a_k·h + b_k) >> 32)                     (multiply-add-shift)
+ *     sig[i][k] = min over t < m_i of v_k(h(i,t))
+ *   d_sig is caller-owned device memory on the object's device, u32[S, K] row-major.  The destination check, the stream
+ *   rule, the locks, flags == 0 and the limit on S (S < 2^32 - 1, else TGX_ERR_UNSUPPORTED) are those of
+ *   tgx_corpus_first_equal_device.  w = 0, w·eb > 64, K = 0 or K > 1024: TGX_ERR_INVALID.  S = 0 writes nothing.  The
+ *   object is only read.  A minimum may be taken in any order and in any number of parts, so the kernel tiles the
+ *   concatenated shingle positions of all rows, 64 to a wave, and a row of any length gets the same bits.
+ * tgx_minhash_value(h, k, seed) is v_k(h), exported so that a caller on another machine can extend a signature.
+ *
+ * Bands.  tgx_minhash_bands_device(device, d_sig, S, K, bands, seed, stream, d_keys, d_heads): B = bands must divide K
+ *   (else TGX_ERR_INVALID), r = K / B.
+ *     key[i][b]  = tgx_row_hash of the 4r little-endian bytes of sig[i][b·r .. (b+1)·r) under the seed
+ *                  (seed ^ TGX_MINHASH_SALT) + b + 1                                 -> d_keys, u64[S, B]
+ *     head[i][b] = min { j : key[j][b] == key[i][b] }                                -> d_heads, int64[S, B]
+ *   Either output may be NULL, not both.  All pointers are device memory on `device`, checked before anything is queued;
+ *   stream rule as above.  Per band the heads are a stable radix sort of (key, row) and the run rule of the exact
+ *   deduplication, every band through one scratch set (8·S·B bytes of band-major keys, 16 bytes per row, the sort's
+ *   temporaries).  The keys alone are what a caller all-gathers for a pass across ranks.  Two rows of Jaccard similarity J
+ *   share at least one bucket with probability 1 - (1 - J^r)^B.
+ *
+ * Clusters.  tgx_minhash_near_first_device(device, d_sig, S, K, d_heads, B, min_agree, stream, d_first, &n_clusters):
+ *     agree(i,j) = #{ k : sig[i][k] == sig[j][k] }                              (agree / K estimates J)
+ *     first0[i]  = min( {i} + { head[i][b] : b < B, head[i][b] < i, agree(i, head[i][b]) >= min_agree } )
+ *     first[i]   = the root of i's chain under first0 (first0[i] <= i, so the chains end)   -> d_first, int64[S]
+ *     n_clusters = #{ i : first[i] == i }                                       (host memory, may be NULL)
+ *   1 <= min_agree <= K and 1 <= B <= K, else TGX_ERR_INVALID.  A head that is no row before i is never followed, so
+ *   heads from elsewhere cannot make the call read outside d_sig.  This is a STAR per bucket: a row is compared with
+ *   its bucket's head only, and transitivity comes from the chains alone; two rows of one bucket that both fail against
+ *   the head are not compared with each other.  The roots are found by pointer doubling between d_first and a scratch of
+ *   its size, one host visit per round.  first == arange(S) is the keep-mask, exactly as with first_equal.
+ *
+ * Host twins, no device, the same argument checks as tgx_first_equal_host: tgx_minhash_host(data, elem_bytes, offs,
+ *   n_rows, width, n_perm, seed, sig) walks the kernel's tiles, chunks and flush rule through csrc/minhash.h;
+ *   tgx_minhash_bands_host(sig, n_rows, n_perm, bands, seed, keys, heads); tgx_minhash_near_first_host(sig, n_rows, n_perm,
+ *   heads, bands, min_agree, first, &n_clusters).
+ *
+ * tgx_minhash_last_times: device time per stage of the calling thread's last calls, as tgx_dedup_last_times (the names
+ * are listed without a call).  Each of the three calls sets the stages it runs and leaves the others: minhash_sig_kernel
+ * (the positions' scan, the pre-set, the kernel); minhash_band_keys, minhash_sort, minhash_heads (summed over the bands);
+ * minhash_verify (first0), minhash_roots (the doubling rounds and the count). */
+#define TGX_MINHASH_SALT 0xD6E8FEB86659FD93ULL
+tgx_status tgx_result_minhash_device(const tgx_result *r, uint32_t width, uint32_t n_perm, uint64_t seed, uint32_t flags,
+                                     void *stream, uint32_t *d_sig);
+tgx_status tgx_corpus_minhash_device(tgx_corpus *c, uint32_t width, uint32_t n_perm, uint64_t seed, uint32_t flags,
+                                     void *stream, uint32_t *d_sig);
+uint32_t tgx_minhash_value(uint64_t h, uint32_t k, uint64_t seed);
+tgx_status tgx_minhash_bands_device(int device, const uint32_t *d_sig, uint64_t n_rows, uint32_t n_perm, uint32_t bands,
+                                    uint64_t seed, void *stream, uint64_t *d_keys, int64_t *d_heads);
+tgx_status tgx_minhash_near_first_device(int device, const uint32_t *d_sig, uint64_t n_rows, uint32_t n_perm,
+                                         const int64_t *d_heads, uint32_t bands, uint32_t min_agree, void *stream,
+                                         int64_t *d_first, uint64_t *n_clusters);
+tgx_status tgx_minhash_host(const void *data, uint32_t elem_bytes, const uint64_t *offs, uint64_t n_rows, uint32_t width,
+                            uint32_t n_perm, uint64_t seed, uint32_t *sig);
+tgx_status tgx_minhash_bands_host(const uint32_t *sig, uint64_t n_rows, uint32_t n_perm, uint32_t bands, uint64_t seed,
+                                  uint64_t *keys, int64_t *heads);
+tgx_status tgx_minhash_near_first_host(const uint32_t *sig, uint64_t n_rows, uint32_t n_perm, const int64_t *heads,
+                                       uint32_t bands, uint32_t min_agree, int64_t *first, uint64_t *n_clusters);
+int tgx_minhash_last_times(const char **names, float *ms, int cap);
+
 /* ---- the front end on the device: a resident corpus split at special tokens, CRLF applied (csrc/front.hip) --------
  * What tgx_split_specials and tgx_pack_segments compute on host threads, for a corpus that is already in HBM (an upload,
  * or tgx_corpus_from_text of a decoded text), with the plan kept on the device for tgx_assemble_result_plan: a resident

@@ -182,6 +182,15 @@ SYMBOLS = {
     "tgx_first_equal_host": (_i, [_vp, _u32, _vp, _u64, _u32, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     "tgx_dedup_last_times": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_float), _i]),
     "tgx_dedup_last_rounds": (_u32, []),
+    "tgx_result_minhash_device": (_i, [_vp, _u32, _u32, _u64, _u32, _vp, _vp]),
+    "tgx_corpus_minhash_device": (_i, [_vp, _u32, _u32, _u64, _u32, _vp, _vp]),
+    "tgx_minhash_value": (_u32, [_u64, _u32, _u64]),
+    "tgx_minhash_bands_device": (_i, [_i, _vp, _u64, _u32, _u32, _u64, _vp, _vp, _vp]),
+    "tgx_minhash_near_first_device": (_i, [_i, _vp, _u64, _u32, _vp, _u32, _u32, _vp, _vp, C.POINTER(C.c_uint64)]),
+    "tgx_minhash_host": (_i, [_vp, _u32, _vp, _u64, _u32, _u32, _u64, _vp]),
+    "tgx_minhash_bands_host": (_i, [_vp, _u64, _u32, _u32, _u64, _vp, _vp]),
+    "tgx_minhash_near_first_host": (_i, [_vp, _u64, _u32, _vp, _u32, _u32, _vp, C.POINTER(C.c_uint64)]),
+    "tgx_minhash_last_times": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_float), _i]),
 }
 
 
@@ -598,6 +607,76 @@ def dedup_last_times() -> dict[str, float]:
 def dedup_last_rounds() -> int:
     """Rounds of the calling thread's last first_equal (tgx_dedup_last_rounds)."""
     return int(lib.tgx_dedup_last_rounds())
+
+
+def minhash_host(data: np.ndarray, offs: np.ndarray, width: int = 5, n_perm: int = 128, seed: int = 0) -> np.ndarray:
+    """Host twin of NativeCorpus.minhash / NativeResult.minhash (tgx_minhash_host: the kernel's tiles, chunks and flush
+    rule through the same header, no device) over data u8[N] or u32[T] and offsets u64[S+1] in elements -> sig u32[S, K]."""
+    data = np.ascontiguousarray(data)
+    if data.dtype not in (np.uint8, np.uint32):
+        raise TypeError(f"data must be uint8 or uint32 (got {data.dtype})")
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    n = max(offs.shape[0] - 1, 0)
+    sig = np.empty((n, max(int(n_perm), 0)), np.uint32)
+    check(lib.tgx_minhash_host(ptr(data) if data.size else None, data.dtype.itemsize, ptr(offs) if offs.size else None, n, int(width), int(n_perm),
+                               int(seed) & (2**64 - 1), ptr(sig) if sig.size else None))
+    return sig
+
+
+def minhash_bands_host(sig: np.ndarray, bands: int, seed: int = 0):
+    """Host twin of minhash_bands (tgx_minhash_bands_host) over sig u32[S, K] -> (keys u64[S, B], heads int64[S, B])."""
+    sig = np.ascontiguousarray(sig, dtype=np.uint32)
+    S, K = sig.shape
+    keys = np.empty((S, max(int(bands), 0)), np.uint64)
+    heads = np.empty((S, max(int(bands), 0)), np.int64)
+    # (never NULL: both outputs are asked for, also when there is no row)
+    keep = np.zeros(1, np.uint64), np.zeros(1, np.int64)
+    check(lib.tgx_minhash_bands_host(ptr(sig) if sig.size else None, S, K, int(bands), int(seed) & (2**64 - 1), ptr(keys if keys.size else keep[0]),
+                                     ptr(heads if heads.size else keep[1])))
+    return keys, heads
+
+
+def minhash_near_first_host(sig: np.ndarray, heads: np.ndarray, min_agree: int):
+    """Host twin of the clustering (tgx_minhash_near_first_host) over sig u32[S, K] and heads int64[S, B] -> (first
+    int64[S], n_clusters)."""
+    sig = np.ascontiguousarray(sig, dtype=np.uint32)
+    heads = np.ascontiguousarray(heads, dtype=np.int64)
+    S, K = sig.shape
+    first = np.empty(S, np.int64)
+    nc = C.c_uint64()
+    check(lib.tgx_minhash_near_first_host(ptr(sig) if sig.size else None, S, K, ptr(heads) if heads.size else None, heads.shape[1], int(min_agree),
+                                          ptr(first) if S else None, C.byref(nc)))
+    return first, int(nc.value)
+
+
+def minhash_value(h: int, k: int, seed: int = 0) -> int:
+    """v_k(h) of the MinHash permutations under `seed` (tgx_minhash_value): with it a signature is extended elsewhere."""
+    return int(lib.tgx_minhash_value(int(h) & (2**64 - 1), int(k), int(seed) & (2**64 - 1)))
+
+
+def minhash_bands(device: int, d_sig: int, n_rows: int, n_perm: int, bands: int, seed: int = 0, d_keys: int = 0, d_heads: int = 0, *,
+                  stream: int = 0) -> None:
+    """Band keys u64[S, B] and bucket heads int64[S, B] of signatures u32[S, K], all raw integer pointers to device memory
+    on `device` (tgx_minhash_bands_device); either output may be 0."""
+    check(lib.tgx_minhash_bands_device(int(device), d_sig or None, int(n_rows), int(n_perm), int(bands), int(seed) & (2**64 - 1), stream or None,
+                                       d_keys or None, d_heads or None))
+
+
+def minhash_near_first(device: int, d_sig: int, n_rows: int, n_perm: int, d_heads: int, bands: int, min_agree: int, d_first: int, *,
+                       stream: int = 0) -> int:
+    """first int64[S] of the near-duplicate clusters into device memory (tgx_minhash_near_first_device) -> n_clusters."""
+    nc = C.c_uint64()
+    check(lib.tgx_minhash_near_first_device(int(device), d_sig or None, int(n_rows), int(n_perm), d_heads or None, int(bands), int(min_agree),
+                                            stream or None, d_first or None, C.byref(nc)))
+    return int(nc.value)
+
+
+def minhash_last_times() -> dict[str, float]:
+    """Device time in ms of each stage of the calling thread's last MinHash calls (tgx_minhash_last_times)."""
+    names = (C.c_char_p * 8)()
+    ms = (C.c_float * 8)()
+    n = lib.tgx_minhash_last_times(names, ms, 8)
+    return {names[i].decode(): float(ms[i]) for i in range(n)}
 
 
 def front_host(flat: np.ndarray, offs: np.ndarray, specials: list[bytes], crlf: bool):
@@ -1162,6 +1241,12 @@ class NativeResult:
         (tgx_result_row_hashes_device)."""
         check(lib.tgx_result_row_hashes_device(self._h, int(seed) & (2**64 - 1), stream or None, d_hashes or None))
 
+    # -- near-duplicate rows (include/tgx.h: tgx_result_minhash_device; csrc/minhash.hip) --
+    def minhash(self, d_sig: int, width: int = 5, n_perm: int = 128, seed: int = 0, *, stream: int = 0) -> None:
+        """The MinHash signature of every row's token n-grams of `width` ids, as u32[S, n_perm] into caller-owned device
+        memory (a raw integer pointer; tgx_result_minhash_device), queued on `stream` as in pad_device."""
+        check(lib.tgx_result_minhash_device(self._h, int(width), int(n_perm), int(seed) & (2**64 - 1), 0, stream or None, d_sig or None))
+
     def pad_host(self, row_len: int, pad_id: int, **kw) -> dict:
         """layout_pad_host over the ids and offsets copied to the host."""
         return layout_pad_host(self.ids(), self.offsets(), row_len, pad_id, **kw)
@@ -1354,6 +1439,11 @@ class NativeCorpus:
         """tgx_row_hash of every sample under `seed`, as u64[S] into caller-owned device memory
         (tgx_corpus_row_hashes_device)."""
         check(lib.tgx_corpus_row_hashes_device(self._h, int(seed) & (2**64 - 1), stream or None, d_hashes or None))
+
+    def minhash(self, d_sig: int, width: int = 5, n_perm: int = 128, seed: int = 0, *, stream: int = 0) -> None:
+        """The MinHash signature of every sample's byte shingles of `width` bytes, as u32[S, n_perm] into caller-owned
+        device memory (tgx_corpus_minhash_device).  This corpus is only read."""
+        check(lib.tgx_corpus_minhash_device(self._h, int(width), int(n_perm), int(seed) & (2**64 - 1), 0, stream or None, d_sig or None))
 
     def normalize(self, form: str) -> "NativeCorpus":
         """The corpus under a Unicode normalisation form ("nfd", "nfc", "nfkd", "nfkc") on the device (tgx_corpus_normalize,

@@ -1,8 +1,8 @@
 // The *_host twins of the result-side device entry points (include/tgx.h): tgx_layout_pad_host, tgx_layout_pack_host,
-// tgx_layout_windows_host, tgx_assemble_host, tgx_fim_host, tgx_select_host, tgx_select_text_host, tgx_shuffled_rows_host, tgx_first_equal_host, tgx_decode_rows_host, tgx_spans_host, tgx_window_spans_host, tgx_front_host,
+// tgx_layout_windows_host, tgx_assemble_host, tgx_fim_host, tgx_select_host, tgx_select_text_host, tgx_shuffled_rows_host, tgx_first_equal_host, tgx_minhash_host, tgx_minhash_bands_host, tgx_minhash_near_first_host, tgx_decode_rows_host, tgx_spans_host, tgx_window_spans_host, tgx_front_host,
 // tgx_normalize_host and tgx_lattice_stats_host, and the
 // argument checks they share with the device entry points of tgx_api.cpp.  A twin goes through the same index arithmetic as its kernels (layout.h, assemble.h,
-// fim.h, select.h, dedup.h, decode.h, spans.h, front.h, norm.h) on host memory.  Nothing in this file calls a HIP function, so it builds and runs without the
+// fim.h, select.h, dedup.h, minhash.h, decode.h, spans.h, front.h, norm.h) on host memory.  Nothing in this file calls a HIP function, so it builds and runs without the
 // handles, the pool or a device.
 #define TGX_HOST_ONLY  // tile_fill.h: the host loop, no kernel side
 #include <algorithm>
@@ -19,6 +19,7 @@
 #include "fim.h"
 #include "front.h"
 #include "layout.h"
+#include "minhash.h"
 #include "norm.h"
 #include "select.h"
 #include "spans.h"
@@ -696,6 +697,147 @@ tgx_status tgx_first_equal_host(const void* data, uint32_t elem_bytes, const uin
     }
     if (n_unique) *n_unique = heads;
     if (n_rounds) *n_rounds = round;
+    return TGX_OK;
+}
+
+// ---- near-duplicate rows ---------------------------------------------------------------
+
+uint32_t tgx_minhash_value(uint64_t h, uint32_t k, uint64_t seed) {
+    uint64_t a, b;
+    tgx::minhash_perm(tgx::minhash_perm_seed(seed), k, a, b);
+    return tgx::minhash_value(a, b, h);
+}
+
+namespace {
+
+tgx_status minhash_check_sig_host(const char* who, const uint32_t* sig, uint64_t n_rows, uint32_t n_perm) {
+    if (n_perm == 0 || n_perm > tgx::kMinhashMaxPerm) return fail(TGX_ERR_INVALID, "%s: n_perm %u is not in 1 .. %u", who, n_perm, tgx::kMinhashMaxPerm);
+    if (n_rows >= 0xFFFFFFFFull) return fail(TGX_ERR_UNSUPPORTED, "%s: more than 2^32-1 rows", who);
+    if (n_rows && !sig) return fail(TGX_ERR_INVALID, "%s: sig is NULL", who);
+    return TGX_OK;
+}
+
+}  // namespace
+
+// The kernel's walk: the positions in tiles of four chunks, the owners of a chunk's ends galloped from the chunk before,
+// every position's owner searched between them, the minima flushed when the owner changes and at the chunk's end, by
+// the kernel's rule (a plain store for a row inside the chunk, which would lose the other chunks' part if the rule were wrong).
+tgx_status tgx_minhash_host(const void* data, uint32_t elem_bytes, const uint64_t* offs, uint64_t n_rows, uint32_t width, uint32_t n_perm, uint64_t seed,
+                            uint32_t* sig) {
+    const char* who = "tgx_minhash_host";
+    if (elem_bytes != 1 && elem_bytes != 4) return fail(TGX_ERR_INVALID, "%s: elem_bytes %u is neither 1 nor 4", who, elem_bytes);
+    if (width == 0 || (uint64_t)width * elem_bytes > tgx::kMinhashMaxBytes)
+        return fail(TGX_ERR_INVALID, "%s: width %u of %u-byte elements is not in 1 .. %u", who, width, elem_bytes, tgx::kMinhashMaxBytes / elem_bytes);
+    if (n_perm == 0 || n_perm > tgx::kMinhashMaxPerm) return fail(TGX_ERR_INVALID, "%s: n_perm %u is not in 1 .. %u", who, n_perm, tgx::kMinhashMaxPerm);
+    const tgx_status st = check_packed_list(who, "offs", "offsets", offs, n_rows, true);
+    if (st != TGX_OK) return st;
+    const uint64_t S = n_rows, K = n_perm;
+    if (S >= 0xFFFFFFFFull) return fail(TGX_ERR_UNSUPPORTED, "%s: more than 2^32-1 rows", who);
+    if (offs[S] && !data) return fail(TGX_ERR_INVALID, "%s: data is NULL", who);
+    if (S && !sig) return fail(TGX_ERR_INVALID, "%s: sig is NULL", who);
+    if (S == 0) return TGX_OK;
+    const uint8_t* bytes = static_cast<const uint8_t*>(data);
+    std::vector<uint64_t> sh_offs(S + 1), a(K), b(K);
+    std::vector<uint32_t> mn(K, tgx::kMinhashNoSig);
+    sh_offs[0] = 0;
+    for (uint64_t k = 0; k < S; k++) sh_offs[k + 1] = sh_offs[k] + tgx::minhash_row_positions(offs, S, width, k);
+    const uint64_t M = sh_offs[S], hs = tgx::dedup_seed(tgx::minhash_hash_seed(seed)), ps = tgx::minhash_perm_seed(seed);
+    for (uint32_t k = 0; k < K; k++) tgx::minhash_perm(ps, k, a[k], b[k]);
+    std::fill(sig, sig + S * K, tgx::kMinhashNoSig);
+    uint64_t hi = 0;
+    for (uint64_t t0 = 0; t0 < M; t0 += tgx::kMinhashTile) {
+        for (uint64_t c0 = t0; c0 < M && c0 < t0 + tgx::kMinhashTile; c0 += tgx::kMinhashChunk) {
+            const uint64_t c_last = tgx::tile_last(c0, tgx::kMinhashChunk, M);
+            const uint64_t lo = tgx::dedup_find_from(sh_offs.data(), hi, S - 1, c0);
+            hi = tgx::dedup_find_from(sh_offs.data(), lo, S - 1, c_last);
+            uint64_t cur = lo;
+            auto flush = [&](uint64_t r) {
+                const bool inside = tgx::minhash_row_inside(sh_offs.data(), r, c0);
+                for (uint64_t k = 0; k < K; k++) {
+                    sig[r * K + k] = inside ? mn[k] : std::min(sig[r * K + k], mn[k]);
+                    mn[k] = tgx::kMinhashNoSig;
+                }
+            };
+            for (uint64_t pos = c0; pos <= c_last; pos++) {
+                const uint64_t i = tgx::pack_find_row(sh_offs.data(), 0, lo, hi, pos);
+                const uint64_t t = pos - sh_offs[i];
+                const uint32_t n_bytes = tgx::minhash_shingle_len(offs[i + 1] - offs[i], width) * elem_bytes;
+                uint64_t w[tgx::kMinhashMaxBytes / 8] = {};
+                for (uint32_t j = 0; 8 * j < n_bytes; j++) w[j] = tgx::dedup_word_host(bytes + (offs[i] + t) * elem_bytes, n_bytes, j);
+                const uint64_t h = tgx::minhash_hash_words(w, n_bytes, hs);
+                if (i != cur) {
+                    flush(cur);
+                    cur = i;
+                }
+                for (uint64_t k = 0; k < K; k++) mn[k] = std::min(mn[k], tgx::minhash_value(a[k], b[k], h));
+            }
+            flush(cur);
+        }
+    }
+    return TGX_OK;
+}
+
+tgx_status tgx_minhash_bands_host(const uint32_t* sig, uint64_t n_rows, uint32_t n_perm, uint32_t bands, uint64_t seed, uint64_t* keys, int64_t* heads) {
+    const char* who = "tgx_minhash_bands_host";
+    const tgx_status st = minhash_check_sig_host(who, sig, n_rows, n_perm);
+    if (st != TGX_OK) return st;
+    if (bands == 0 || n_perm % bands) return fail(TGX_ERR_INVALID, "%s: bands %u does not divide n_perm %u", who, bands, n_perm);
+    if (!keys && !heads) return fail(TGX_ERR_INVALID, "%s: keys and heads are both NULL", who);
+    const uint64_t S = n_rows, B = bands;
+    const uint32_t r = n_perm / bands;
+    std::vector<uint64_t> col(S), sorted(S);
+    std::vector<uint32_t> order(S);
+    for (uint32_t b = 0; b < bands; b++) {
+        for (uint64_t i = 0; i < S; i++) {
+            col[i] = tgx::minhash_band_key(sig + i * n_perm, r, b, seed);
+            if (keys) keys[i * B + b] = col[i];
+            order[i] = (uint32_t)i;
+        }
+        if (!heads) continue;
+        // the stable sort by key: each run begins with its smallest row
+        std::stable_sort(order.begin(), order.end(), [&col](uint32_t x, uint32_t y) { return col[x] < col[y]; });
+        for (uint64_t i = 0; i < S; i++) sorted[i] = col[order[i]];
+        for (uint64_t i = 0; i < S; i++) heads[(uint64_t)order[i] * B + b] = (int64_t)order[tgx::dedup_run_head(sorted.data(), i)];
+    }
+    return TGX_OK;
+}
+
+tgx_status tgx_minhash_near_first_host(const uint32_t* sig, uint64_t n_rows, uint32_t n_perm, const int64_t* heads, uint32_t bands, uint32_t min_agree,
+                                       int64_t* first, uint64_t* n_clusters) {
+    const char* who = "tgx_minhash_near_first_host";
+    if (n_clusters) *n_clusters = 0;
+    const tgx_status st = minhash_check_sig_host(who, sig, n_rows, n_perm);
+    if (st != TGX_OK) return st;
+    if (bands == 0 || bands > n_perm) return fail(TGX_ERR_INVALID, "%s: bands %u is not in 1 .. n_perm %u", who, bands, n_perm);
+    if (min_agree == 0 || min_agree > n_perm) return fail(TGX_ERR_INVALID, "%s: min_agree %u is not in 1 .. n_perm %u", who, min_agree, n_perm);
+    const uint64_t S = n_rows, K = n_perm, B = bands;
+    if (S == 0) return TGX_OK;
+    if (!heads) return fail(TGX_ERR_INVALID, "%s: heads is NULL", who);
+    if (!first) return fail(TGX_ERR_INVALID, "%s: first is NULL", who);
+    for (uint64_t i = 0; i < S; i++) {
+        uint64_t best = i;
+        for (uint64_t b = 0; b < B; b++) {
+            const int64_t head = heads[i * B + b];
+            if (!tgx::minhash_looks_at(head, best)) continue;
+            uint32_t agree = 0;
+            for (uint64_t k = 0; k < K; k++) agree += sig[i * K + k] == sig[(uint64_t)head * K + k];
+            if (tgx::minhash_takes(agree, min_agree)) best = (uint64_t)head;
+        }
+        first[i] = (int64_t)best;
+    }
+    // pointer doubling between two buffers, until a round moves nothing
+    std::vector<int64_t> other(S);
+    for (bool changed = true; changed;) {
+        changed = false;
+        for (uint64_t i = 0; i < S; i++) {
+            other[i] = tgx::minhash_hop(first, i);
+            changed = changed || other[i] != first[i];
+        }
+        std::copy(other.begin(), other.end(), first);
+    }
+    uint64_t n = 0;
+    for (uint64_t i = 0; i < S; i++) n += first[i] == (int64_t)i;
+    if (n_clusters) *n_clusters = n;
     return TGX_OK;
 }
 

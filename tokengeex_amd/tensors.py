@@ -211,6 +211,66 @@ def row_hashes(obj, seed: int = 0):
     return out
 
 
+# ---- near-duplicate rows on the device (csrc/minhash.hip) ----------------------------------------------------------------
+
+def minhash(obj, width: int = 5, n_perm: int = 128, seed: int = 0):
+    """-> [S, n_perm] torch.int32 on obj's device (a NativeResult: token n-grams of `width` ids; a NativeCorpus: shingles
+    of `width` bytes) holding the u32 bits of every row's MinHash signature, the same on every machine.  The share of
+    equal entries of two signatures estimates the Jaccard similarity of the two rows' shingle sets."""
+    import torch
+    dev = _device_of(torch, obj)
+    out = torch.empty((obj.num_samples, int(n_perm)), dtype=torch.int32, device=dev)
+    obj.minhash(out.data_ptr() if out.numel() else 0, width, n_perm, seed, stream=torch.cuda.current_stream(dev).cuda_stream)
+    return out
+
+
+def _check_sig(torch, sig):
+    if not isinstance(sig, torch.Tensor) or sig.dtype != torch.int32 or sig.dim() != 2 or not sig.is_cuda:
+        raise TypeError("sig must be a [S, K] torch.int32 tensor on a GPU, as minhash returns it")
+    return sig.contiguous()
+
+
+def minhash_bands(sig, bands: int, seed: int = 0):
+    """-> (keys, heads), both [S, bands] torch.int64 on sig's device: the u64 bits of every band's key (what ranks
+    all-gather for a pass across them) and head[i][b], the first row in row i's bucket of band b.  bands must divide K."""
+    import torch
+    sig = _check_sig(torch, sig)
+    S, K = sig.shape
+    keys = torch.empty((S, int(bands)), dtype=torch.int64, device=sig.device)
+    heads = torch.empty((S, int(bands)), dtype=torch.int64, device=sig.device)
+    spare = torch.empty(1, dtype=torch.int64, device=sig.device)  # (no row: the pointers still say that both are asked for)
+    _lib.minhash_bands(sig.device.index, sig.data_ptr() if S else 0, S, K, bands, seed, (keys if S else spare).data_ptr(),
+                       (heads if S else spare).data_ptr(), stream=torch.cuda.current_stream(sig.device).cuda_stream)
+    return keys, heads
+
+
+def near_first(sig, bands: int, threshold: float, seed: int = 0):
+    """-> [S] torch.int64 on sig's device: first[i] = the root of row i's near-duplicate cluster, so first[i] == i marks
+    the rows to keep.  Rows that share a bucket in one of `bands` bands are candidates; a row joins its bucket's head when
+    at least ceil(threshold·K) of their K signature values agree.  A star per bucket: a row is compared with the bucket's
+    head only, and clusters join through chains of heads."""
+    import math
+    import torch
+    sig = _check_sig(torch, sig)
+    S, K = sig.shape
+    if not 0.0 < float(threshold) <= 1.0:
+        raise ValueError(f"threshold must be in (0, 1] (got {threshold})")
+    min_agree = max(1, math.ceil(float(threshold) * K))
+    _, heads = minhash_bands(sig, bands, seed)
+    first = torch.empty((S,), dtype=torch.int64, device=sig.device)
+    _lib.minhash_near_first(sig.device.index, sig.data_ptr() if S else 0, S, K, heads.data_ptr() if S else 0, bands, min_agree,
+                            first.data_ptr() if S else 0, stream=torch.cuda.current_stream(sig.device).cuda_stream)
+    return first
+
+
+def near_unique_rows(sig, bands: int, threshold: float, seed: int = 0):
+    """-> torch.int64 indices, ascending, of the rows that are the root of their near-duplicate cluster: what `select`
+    takes to drop the near-copies (of a corpus and, with the same indices, of its encoded result)."""
+    import torch
+    first = near_first(sig, bands, threshold, seed)
+    return (first == torch.arange(first.shape[0], dtype=torch.int64, device=first.device)).nonzero().reshape(-1)
+
+
 def _window_len(max_length, stride) -> tuple[int, int]:
     if max_length is None:
         raise TypeError("max_length is required for overflow windows")
