@@ -16,6 +16,11 @@ M = len(SP)
 def truth(samples, specials, crlf):
     """-> (seg_offs, seg_special, segments' flat, segments' offsets) of the host route"""
     flat, offs = _lib.pack(samples)
+    return truth_flat(flat, offs, specials, crlf)
+
+
+def truth_flat(flat, offs, specials, crlf):
+    """truth() of a packed batch"""
     flat = np.ascontiguousarray(flat)
     seg_offs, sb, se, ss = _lib.split_specials_flat(flat, offs, specials)
     pflat, poffs = _lib.pack_segments(flat, sb, se, ss, crlf)
@@ -135,3 +140,38 @@ def random_batch(rng, max_bytes=64 << 10):
         samples.append(bytes(body))
         total += len(body)
     return samples, specials
+
+
+# ---- one corpus past the caps of csrc/front.hip's grids -----------------------------------------------------------------
+
+CAP = 4096            # csrc/front.hip: kFrontMaxBlocks, of the kernels over tiles and of those over candidates, samples and segments
+BLOCK = 256           # csrc/front.hip: kFrontBlock, items per block of the kernels with a thread per candidate, sample or segment
+PAST_SPECIALS = [SP, b"<s>", b"</s>", b"aa"]
+# the short rows, cycled: a row that is one special, empty rows, overlapping candidates ("aa" on a run), a prefix of a special
+# at a row's end, a special in text, "\r\n" inside a row and with a row's end between the two, specials back to back, and a
+# row of 102 bytes.  167 bytes, 13 rows, 14 accepted candidates and 11 segments to encode a round; 167 is odd, so over the rounds every row begins at every
+# byte of a 16-byte slot and of a tile: the specials straddle the slots' and tiles' edges at every split, and so do the "\r\n"
+PAST_POOL = (b"<s>", b"", b"aaaa", b"x<s", b"bc" + SP + b"d", b"e\r\nf\r", b"\n<s></s>", b"", SP, b"aaab", b"<s>aa<s", b"q<s>\r\n",
+             bytes(98 + (i * 7) % 20 for i in range(47)) + SP + bytes(98 + (i * 5) % 20 for i in range(44)))
+
+
+@functools.lru_cache(maxsize=None)
+def past_cap_corpus():
+    """-> (flat, offs, specials): the short rows of PAST_POOL over the first 4096·4096 bytes and a little more, so that the
+    kernels over tiles (front_mark, front_candidates, front_keep, front_pack) go round twice, with over 256·4096 rows and
+    over 256·4096 candidates, segments and segments to encode, so that the kernels with a thread per one of these do too.  Behind them, in
+    the second trip's tiles, two rows of three tiles each: one without a byte that begins a special (tiles without a
+    candidate: front_candidates_kernel's `continue`) and one of 4096 "<s>" (tiles of which nothing is kept:
+    front_pack_kernel's), then a round of the short rows."""
+    unit = np.frombuffer(b"".join(PAST_POOL), np.uint8)
+    unit_lens = np.asarray([len(r) for r in PAST_POOL], np.int64)
+    reps = CAP * T // unit.size + 8
+    plain = np.frombuffer(bytes(98 + (i * 7) % 20 for i in range(3 * T)), np.uint8)
+    only = np.frombuffer(b"<s>" * T, np.uint8)
+    flat = np.concatenate([np.tile(unit, reps), plain, only, unit])
+    lens = np.concatenate([np.tile(unit_lens, reps), [plain.size, only.size], unit_lens])
+    offs = np.zeros(lens.size + 1, np.uint64)
+    np.cumsum(lens, out=offs[1:])
+    for a in (flat, offs):
+        a.setflags(write=False)
+    return flat, offs, list(PAST_SPECIALS)

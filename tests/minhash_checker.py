@@ -5,7 +5,7 @@ step at a time.  It also gives the true Jaccard similarity of two rows' shingle 
 library."""
 import numpy as np
 
-from dedup_checker import M64, _mix, row_hash
+from dedup_checker import M64, _mix, row_hash, row_hash_equal_length
 
 SALT = 0xD6E8FEB86659FD93
 G = 0x9E3779B97F4A7C15
@@ -103,3 +103,50 @@ def near_first(sig, heads, min_agree):
             j = int(first0[j])
         first[i] = j
     return first, int((first == np.arange(S)).sum()), first0
+
+
+# ---- the same for many rows at once: numpy uint64 arithmetic, which wraps at 2^64 -------------------------------------
+
+def band_keys_np(sig, bands, seed=0):
+    """band_keys, a band of every row at a time -> uint64[S, B]"""
+    sig = np.ascontiguousarray(sig, dtype=np.uint32)
+    S, K = sig.shape
+    r = K // bands
+    keys = np.empty((S, bands), np.uint64)
+    for b in range(bands):
+        raw = np.ascontiguousarray(sig[:, b * r:(b + 1) * r].astype("<u4")).view(np.uint8).reshape(S, 4 * r)
+        keys[:, b] = row_hash_equal_length(raw, ((seed ^ SALT) + b + 1) & M64)
+    return keys
+
+
+def heads_of_np(keys):
+    """heads_of -> int64[S, B]: numpy's unique gives the first row of every key"""
+    S, B = keys.shape
+    heads = np.empty((S, B), np.int64)
+    for b in range(B):
+        _, first_row, inverse = np.unique(keys[:, b], return_index=True, return_inverse=True)
+        heads[:, b] = first_row[inverse.reshape(-1)]
+    return heads
+
+
+def near_first_memo(sig, heads, min_agree):
+    """near_first for many rows -> (first int64[S], n_clusters, first0): first0 a band of every row at a time, and the
+    roots in ascending order of the rows, each from the root of the earlier row it points to (first0[i] <= i).  A head
+    that is no row before i is not followed, whatever its value."""
+    sig = np.asarray(sig)
+    heads = np.asarray(heads, np.int64)
+    S, _ = sig.shape
+    me = np.arange(S, dtype=np.int64)
+    first0 = me.copy()
+    for b in range(heads.shape[1]):
+        h = heads[:, b]
+        before = (h >= 0) & (h < me)
+        j = np.where(before, h, 0)
+        takes = before & ((sig == sig[j]).sum(axis=1) >= min_agree)
+        first0 = np.minimum(first0, np.where(takes, h, me))
+    root = first0.tolist()
+    for i in range(S):
+        if root[i] != i:
+            root[i] = root[root[i]]
+    first = np.asarray(root, np.int64).reshape(S)
+    return first, int((first == me).sum()), first0

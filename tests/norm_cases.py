@@ -116,3 +116,34 @@ def mixed_rows() -> tuple[bytes, ...]:
     """48 KiB of the benchmark's mixed corpus: ASCII, CJK ideographs and fullwidth punctuation"""
     flat, offs = synth.make_corpus(48 << 10, "mixed", max_len=4096, seed_offset=3)
     return tuple(bytes(flat[int(offs[i]):int(offs[i + 1])]) for i in range(offs.size - 1))
+
+
+# ---- one corpus past the caps of csrc/norm.hip's grids ------------------------------------------------------------------
+
+CAP = 4096            # csrc/norm.hip: kNormMaxBlocks, of the kernels over tiles, over rows and over pieces
+BLOCK = 256           # threads of a block of the kernels with a thread per row
+PIECE_BLOCK = 64      # csrc/norm.hip: kPieceBlock, pieces per block of the kernels with a thread per piece
+
+
+@functools.lru_cache(maxsize=None)
+def past_cap_corpus():
+    """-> (flat, offs): rounds of edge_batch() and of the first 3 000 random_rows(), two empty rows behind each of those,
+    over the first 4096·4096 bytes and a little more: the kernels over tiles (norm_mark, norm_pieces, norm_places) go round
+    twice, there are over 256·4096 rows and over 64·4096 pieces.  A round is no multiple of a tile, so every round puts its
+    heads, marks and row ends at other places of the slots and tiles.  Behind them, in the second trip's tiles, a row of
+    three tiles of ASCII (tiles without a piece: norm_pieces_kernel's `continue`) and one more round."""
+    rows = list(edge_batch())
+    for r in random_rows()[:3000]:
+        rows += [r, b"", b""]
+    unit, unit_offs = _lib.pack(rows)
+    unit = np.ascontiguousarray(unit)
+    unit_lens = np.diff(unit_offs.astype(np.int64))
+    reps = CAP * TILE // unit.size + 1
+    plain = np.frombuffer(filler(3 * TILE, 3), np.uint8)
+    flat = np.concatenate([np.tile(unit, reps), plain, unit])
+    lens = np.concatenate([np.tile(unit_lens, reps), [plain.size], unit_lens])
+    offs = np.zeros(lens.size + 1, np.uint64)
+    np.cumsum(lens, out=offs[1:])
+    for a in (flat, offs):
+        a.setflags(write=False)
+    return flat, offs

@@ -105,6 +105,96 @@ def test_row_hash_matches_the_restatement():
     assert _lib.row_hash(b"") == dc.row_hash(b"") and _lib.row_hash(b"", 5) != _lib.row_hash(b"", 6)
 
 
+@pytest.mark.parametrize("kind", dedup_cases.KINDS)
+def test_vectorised_row_hash_matches_the_scalar_one(kind):
+    for name in dedup_cases.NAMES:
+        c = _case(name, kind)
+        rows = dc.row_bytes(c["data"], c["offs"])
+        for seed in (0, 0x9E3779B97F4A7C15):
+            want = np.asarray([dc.row_hash(r, seed) for r in rows], np.uint64)
+            assert np.array_equal(dc.row_hashes(c["data"], c["offs"], seed), want), (name, seed)
+    assert dc.row_hash_equal_length(np.zeros((3, 0), np.uint8), 5).tolist() == [dc.row_hash(b"", 5)] * 3
+
+
+@functools.lru_cache(maxsize=None)
+def _past_cap(kind):
+    c = dedup_cases.past_cap_case(kind)
+    c["want"] = dc.first_equal(c["data"], c["offs"])
+    for a in (c["data"], c["offs"], c["want"][0]):
+        a.setflags(write=False)
+    return c
+
+
+@pytest.mark.parametrize("kind", dedup_cases.KINDS)
+def test_past_cap_case_reaches_every_threshold(kind):
+    """the arithmetic of csrc/dedup.hip's launchers on the batch, from the mirrored constants"""
+    c = _past_cap(kind)
+    cap, tile_h, cmp_tile = 2048, 4096, dedup_cases.TILE[kind]   # kDedupMaxBlocks, kDedupTile, kDedupCmpByteTile / kDedupCmpTile
+    w = c["data"].dtype.itemsize
+    lens = np.diff(c["offs"].astype(np.int64))
+    S = lens.size
+    where = c["where"]
+    first, n_unique = c["want"]
+    pad_offs = np.concatenate([[0], np.cumsum(dedup_cases.pad_bytes(lens, w))])
+    n_pad = int(pad_offs[-1])
+    n_tiles = -(-n_pad // tile_h)
+    grid = min(cap, -(-(c["data"].size * w + 7 * S) // tile_h))
+    per_block = -(-n_tiles // grid)
+    print(f"{kind}: rows {S}, padded bytes {n_pad}, n_tiles {n_tiles}, grid {grid}, per_block {per_block}")
+    assert n_pad > cap * tile_h + tile_h and n_tiles >= 2050 and grid == cap and per_block == 2
+    working = -(-n_tiles // per_block)
+    assert n_tiles % 2 == 1 and working < grid, "the last working block has a run of one tile, and blocks behind it have none"
+    run = per_block * tile_h
+    k = where["carry"]      # inside one block's run, over both of its tiles
+    assert pad_offs[k] % run == tile_h // 2 and pad_offs[k] // run == (pad_offs[k + 1] - 1) // run
+    assert pad_offs[k] // tile_h + 1 == (pad_offs[k + 1] - 1) // tile_h and lens[k] == cmp_tile + 3
+    k = where["two_blocks"]  # from the second tile of one block's run into the first tile of the next block's
+    assert (pad_offs[k] // tile_h) % 2 == 1 and (pad_offs[k + 1] - 1) // tile_h == pad_offs[k] // tile_h + 1 and lens[k] == cmp_tile - 1
+    assert {int(n) - cmp_tile for n in lens[where["rows"]]} >= {-3, -2, -1, 1, 2, 3}
+    # the compare at 64 key bits: the candidates are the rows with an earlier equal
+    dup = first != np.arange(S)
+    cmp_total = int(lens[dup].sum())
+    print(f"{kind}: duplicates {int(dup.sum())}, compare total {cmp_total} elements, compare tiles {-(-cmp_total // cmp_tile)}")
+    assert cmp_total > cap * cmp_tile + cmp_tile
+    big = where["big"]
+    assert (lens[big] == 70_000).all() and (first[big] == big[0]).all()
+    data, offs = c["data"], c["offs"].astype(np.int64)
+    row = lambda k: data[offs[k]:offs[k + 1]]
+    a = row(big[0])
+    top = lambda r: dc.row_hash(dc.row_bytes(r, np.asarray([0, r.size]))[0]) >> (64 - c["low_bits"])
+    for name, at in (("mid", 35_000), ("first", 0), ("last", 69_999)):
+        k = where[name]
+        b = row(k)
+        assert b.size == a.size and np.flatnonzero(a != b).tolist() == [at] and first[k] == k
+        assert top(a) == top(b), "a candidate of the row it was made from under the knob"
+        # the candidates of 70 000 elements before it in that round: every earlier copy but the head
+        assert ((big < k).sum() - 1) * 70_000 >= cap * cmp_tile, "every element of the row is compared in the second trip"
+    assert big[-1] > where["last"]
+    # the kernels with a thread per row
+    assert S > 256 * cap and (lens[256 * cap - 2:256 * cap + 3] == 0).all()
+    assert (lens[:3] == 0).all() and (lens[-3:] == 0).all()
+    # a run of empty rows at the edge between the two tiles of a block's run
+    e = np.flatnonzero((lens[:-1] == 0) & (lens[1:] == 0) & (pad_offs[:-2] % run == tile_h))
+    assert e.size and (lens[e[0] + 1:] > 0).any()
+    # the collision run: a short content before the long part has the 70 000-element row's key, so round two lists every copy
+    pool_keys = {dc.row_hash(dc.row_bytes(p, np.asarray([0, p.size]))[0]) >> (64 - c["low_bits"]) for p in c["pool"]}
+    assert top(a) in pool_keys and where["rows"][0] >= dedup_cases.SHORT_A
+    assert big.size * int(dedup_cases.pad_bytes(70_000, w)) > cap * tile_h + tile_h
+    assert n_unique == len(c["pool"]) + c["n_long_contents"]
+    assert where["edge_rows"].size > 1000, "the rows on either side of the tile edges that short rows own"
+
+
+@pytest.mark.parametrize("kind", dedup_cases.KINDS)
+def test_twin_matches_the_checker_past_the_caps(kind):
+    c = _past_cap(kind)
+    want_first, want_unique = c["want"]
+    for bits in (64, c["low_bits"]):
+        first, n_unique, n_rounds = _lib.first_equal_host(c["data"], c["offs"], hash_bits=bits)
+        assert np.array_equal(first, want_first) and n_unique == want_unique, bits
+        print(f"{kind}: {bits} key bits, {n_rounds} rounds")
+        assert (n_rounds == 1) if bits == 64 else (2 <= n_rounds <= dedup_cases.MAX_DISTINCT)
+
+
 def test_twin_refuses_bad_arguments():
     lib = _lib.lib
     data = np.arange(8, dtype=np.uint8)

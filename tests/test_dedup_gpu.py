@@ -4,8 +4,10 @@ the default 64 key bits and, through the test knob TGX_DEDUP_HASH_BITS, at 4 and
 rounds go on; the unique rows of a corpus and of its encoded result stay aligned on real text.  Everything is compared
 exactly: this is integer work.
 
-The shapes are tests/dedup_cases.py's; the real text is test_assemble_gpu.py's corpus, 96 KiB of mixed text with a
-70 000-byte sample and empty samples, a third of its rows repeated through select, under the spec 32 000 vocabulary."""
+The shapes are tests/dedup_cases.py's, among them one batch per kind that takes every capped grid past its cap (over
+8 MiB of padded bytes, over 2048 tiles of candidates, over 2^19 rows); the real text is test_assemble_gpu.py's corpus,
+96 KiB of mixed text with a 70 000-byte sample and empty samples, a third of its rows repeated through select, under the
+spec 32 000 vocabulary."""
 import ctypes as C
 import functools
 import os
@@ -111,6 +113,66 @@ def test_row_hashes_are_tgx_row_hash_of_every_row(kind):
                 assert lib_hash == [int(x) for x in want[:8]]
         finally:
             src.free()
+
+
+# ---- past the caps of the grids: the second tile of a block's run, the second trip of the compare and of the row kernels --
+
+@functools.lru_cache(maxsize=None)
+def _past_cap(kind):
+    """dedup_cases.past_cap_case with the checker's and the twin's answers: computed once, never changed"""
+    c = dedup_cases.past_cap_case(kind)
+    c["want"] = dc.first_equal(c["data"], c["offs"])
+    c["twin"] = {bits: _lib.first_equal_host(c["data"], c["offs"], hash_bits=bits) for bits in (64, c["low_bits"])}
+    for a in (c["data"], c["offs"], c["want"][0]):
+        a.setflags(write=False)
+    return c
+
+
+@pytest.mark.parametrize("bits", [None, dedup_cases.PAST_CAP_BITS])
+@pytest.mark.parametrize("kind", dedup_cases.KINDS)
+def test_past_the_caps_first_equal(kind, bits):
+    """Over 2048·4096 + 4096 padded bytes (a block of dedup_hash_kernel takes two tiles, the last working block one, the
+    blocks behind it none), over 2048 tiles of candidates' elements (dedup_compare_kernel goes round twice) and over
+    256·2048 rows (so do dedup_finish / runs / resolve_kernel); tests/test_dedup_cpu.py holds the batch to these.  Under
+    the knob the later rounds hash over 8 MiB of padded bytes through a compacted list, and the copies of the
+    70 000-element row with one element changed are compared, in the compare's second trip, with the row they were made
+    from.  The rounds are the twin's, and at most MAX_DISTINCT."""
+    c = _past_cap(kind)
+    want_first, want_unique = c["want"]
+    twin_first, twin_unique, twin_rounds = c["twin"][64 if bits is None else bits]
+    assert (twin_rounds == 1) if bits is None else (2 <= twin_rounds <= dedup_cases.MAX_DISTINCT)
+    src = _source(c)
+    try:
+        with _bits(bits):
+            first, n_unique = _first_equal(src)
+        assert np.array_equal(first, want_first) and np.array_equal(first, twin_first)
+        assert n_unique == want_unique == twin_unique
+        assert _lib.dedup_last_rounds() == twin_rounds
+        got = _read(src, kind)
+        assert np.array_equal(got[0], c["data"]) and np.array_equal(got[1], c["offs"]), "the input is only read"
+    finally:
+        src.free()
+
+
+@pytest.mark.parametrize("kind", dedup_cases.KINDS)
+def test_past_the_caps_row_hashes(kind):
+    """every row's hash against the vectorised restatement, and against the scalar one on every long row, on the rows on
+    either side of every tile edge, and on a seeded sample of 2 000 short rows"""
+    c = _past_cap(kind)
+    where = c["where"]
+    rows = dc.row_bytes(c["data"], c["offs"])
+    S = len(rows)
+    rng = np.random.default_rng(8)
+    look = np.unique(np.concatenate([where["rows"], where["edge_rows"], rng.choice(S, 2000, replace=False), [0, S - 1]]))
+    scalar = functools.lru_cache(maxsize=None)(dc.row_hash)   # (most of these rows are copies of a few)
+    src = _source(c)
+    try:
+        for seed in (0, 0x9E3779B97F4A7C15):
+            got = tensors.row_hashes(src, seed).cpu().numpy().view(np.uint64)
+            assert np.array_equal(got, dc.row_hashes(c["data"], c["offs"], seed)), seed
+            assert [int(x) for x in got[look]] == [scalar(rows[k], seed) for k in look], seed
+    finally:
+        src.free()
 
 
 # ---- real text: the unique rows of a corpus and of its encoded result stay aligned --------------------------------

@@ -27,6 +27,40 @@ def test_fixed_cases(crlf):
         _check(samples, specials, crlf, name)
 
 
+def test_past_cap_corpus_reaches_every_threshold():
+    """the arithmetic of csrc/front.hip's launchers on the corpus, from the mirrored constants, and the twin on it"""
+    cap, tile, slot, block = 4096, 4096, 16, 256     # kFrontMaxBlocks, kFrontTile, kFrontGroup, kFrontBlock
+    flat, offs, specials = fc.past_cap_corpus()
+    n, S = flat.size, offs.size - 1
+    n_tiles = -(-n // tile)
+    lens = np.diff(offs.astype(np.int64))
+    begin = offs[:-1].astype(np.int64)
+    assert n > cap * tile + 2 * tile and n_tiles > cap and S > block * cap
+    for crlf in (False, True):
+        want = fc.truth_flat(flat, offs, specials, crlf)
+        got = _lib.front_host(flat, offs, specials, crlf)
+        for name, w, g in zip(("seg_offs", "seg_special", "segments' bytes", "segments' offsets"), want, got):
+            assert w.dtype == g.dtype and np.array_equal(w, g), (crlf, name)
+        seg_offs, ss, pflat, poffs = want
+        accepted, n_enc = int((ss >= 0).sum()), poffs.size - 1     # (every accepted special was a candidate)
+        print(f"crlf {crlf}: bytes {n}, tiles {n_tiles}, rows {S}, accepted candidates {accepted}, segments {ss.size}, to encode {n_enc}")
+        assert accepted > block * cap and ss.size > block * cap and n_enc + 1 > block * cap
+    # the two rows of three tiles lie in the second trip's tiles, each over at least two whole tiles
+    long = np.flatnonzero(lens == 3 * tile)
+    assert long.size == 2 and begin[long[0]] >= cap * tile and lens.max() == 3 * tile
+    plain, only = (flat[begin[k]:begin[k] + lens[k]].tobytes() for k in long)
+    assert not {sp[0] for sp in specials} & set(plain) and only == b"<s>" * tile
+    seg_offs, ss, _, _ = fc.truth_flat(flat, offs, specials, False)
+    assert seg_offs[long[0] + 1] - seg_offs[long[0]] == 1 and (ss[int(seg_offs[long[1]]):int(seg_offs[long[1] + 1])] == 1).all()
+    # over the rounds, the row that is one 11-byte special begins at every byte of a slot and at the last ten of a tile
+    starts = begin[np.flatnonzero(lens == fc.M)]
+    assert all(flat[b:b + fc.M].tobytes() == fc.SP for b in starts[:50])
+    assert set(starts % slot) == set(range(slot)) and set(range(tile - 10, tile)) <= set(starts % tile)
+    cr = np.flatnonzero((flat[:-1] == 13) & (flat[1:] == 10))
+    assert (cr % slot == slot - 1).any() and (cr % tile == tile - 1).any() and np.isin(cr + 1, begin).any()
+    assert (lens == 0).sum() > S // 8 and {len(r) for r in fc.PAST_POOL} >= {0, 3, fc.M}
+
+
 def test_the_cases_say_what_they_are_meant_to():
     """the ground truth itself, on the cases whose outcome the split rule states in words"""
     assert fc.segments([b"ababababa"], [b"aba"]) == [[(b"aba", 0), (b"b", -1), (b"aba", 0), (b"ba", -1)]]

@@ -2,7 +2,7 @@
 with the CRLF pass, against split_specials_flat + pack_segments on the host; the plan assembled where it is
 (tgx_assemble_result_plan) against tgx_assemble_result from the host arrays; and the Tokenizer's encode_corpus_* against
 its flat routes.  Everything is compared exactly: this is byte and integer movement.  The cases are those of
-tests/front_cases.py, each with the CRLF pass on and off."""
+tests/front_cases.py, each with the CRLF pass on and off, and its corpus of 16.8 MB that takes the grids past their caps."""
 import functools
 
 import numpy as np
@@ -33,25 +33,31 @@ def _same(res, want, key):
 
 
 def _check(samples, specials, crlf, key):
+    _check_flat(*tgx.pack(samples), specials, crlf, key)
+
+
+def _check_flat(flat, offs, specials, crlf, key, encode=True):
+    """a packed batch through the device front end against the host route; encode=False: without the encode of the
+    segments and the assembly of the plan"""
     nat = _native()
-    seg_offs, ss, pflat, poffs = fc.truth(samples, specials, crlf)
-    flat, offs = tgx.pack(samples)
+    seg_offs, ss, pflat, poffs = fc.truth_flat(flat, offs, specials, crlf)
     corpus = tgx.NativeCorpus(flat, offs)
     segs, plan = corpus.split_specials(specials, crlf)
     try:
         # the plan is the host's
-        assert (plan.num_samples, plan.num_segments, plan.num_encoded) == (len(samples), ss.size, poffs.size - 1), key
+        assert (plan.num_samples, plan.num_segments, plan.num_encoded) == (offs.size - 1, ss.size, poffs.size - 1), key
         assert plan.device == corpus.device == segs.device, key
         assert np.array_equal(plan.seg_offs(), seg_offs) and np.array_equal(plan.seg_special(), ss), key
         # the segments' corpus holds what the host packs, byte for byte, and encodes to the same ids
         assert segs.num_samples == poffs.size - 1 and segs.num_bytes == pflat.size, key
         assert np.array_equal(segs.offsets(), poffs) and np.array_equal(segs.bytes(), pflat), key
         got = want = None
-        if plan.num_encoded:
+        if encode and plan.num_encoded:
             got, want = nat.encode_corpus(segs), nat.encode_batch_flat(pflat, poffs)
             assert np.array_equal(got.offsets(), want.offsets()) and np.array_equal(got.ids(), want.ids()), key
         # the plan assembled from HBM against the host arrays uploaded
-        _same(nat.assemble_plan(got, plan, len(specials)), nat.assemble(want, seg_offs, ss, len(specials)), key)
+        if encode:
+            _same(nat.assemble_plan(got, plan, len(specials)), nat.assemble(want, seg_offs, ss, len(specials)), key)
         for r in (got, want):
             if r is not None:
                 r.free()
@@ -87,6 +93,24 @@ def test_random_batches():
     for it in range(12):
         samples, specials = fc.random_batch(rng)
         _check(samples, specials, bool(it & 1), ("random", it))
+
+
+@pytest.mark.parametrize("crlf", [False, True])
+def test_past_the_caps(crlf):
+    """fc.past_cap_corpus(): over 4096·4096 + 2·4096 bytes, so the kernels over tiles go round twice (two of them past tiles
+    they skip), and over 256·4096 samples, candidates, segments and segments to encode, so the kernels with a thread per one
+    of these do too (tests/test_front_cpu.py holds the corpus to this).  The plan, the segments' corpus and the source are
+    compared whole; the encode and the assembly are run on the first and the last 2 000 rows, taken with select."""
+    flat, offs, specials = fc.past_cap_corpus()
+    _check_flat(flat, offs, specials, crlf, "past the caps", encode=False)
+    S = offs.size - 1
+    corpus = tgx.NativeCorpus(flat, offs)
+    ends = corpus.select(np.concatenate([np.arange(2000), np.arange(S - 2000, S)]))
+    try:
+        _check_flat(ends.bytes(), ends.offsets(), specials, crlf, "past the caps, both ends")
+    finally:
+        ends.free()
+        corpus.free()
 
 
 def test_no_samples_and_no_bytes():

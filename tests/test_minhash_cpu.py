@@ -60,7 +60,7 @@ def test_cases_are_as_designed():
     assert (25 in minhash_cases.SHAPE["long_among_short"][2]) and minhash_cases.SHAPE["long_among_short"][1] == 250
 
 
-@pytest.mark.parametrize("name,kind", minhash_cases.all_cases())
+@pytest.mark.parametrize("name,kind", minhash_cases.all_cases() + minhash_cases.wide_cases())
 def test_twins_match_the_checker(name, kind):
     c = _case(name, kind)
     K = c["n_perm"]
@@ -80,6 +80,120 @@ def test_twins_match_the_checker(name, kind):
             want_first, want_clusters, _ = mc.near_first(c["sig"], want_heads, min_agree)
             assert np.array_equal(first, want_first), (bands, min_agree)
             assert n_clusters == want_clusters, (bands, min_agree)
+
+
+def test_wide_cases_take_the_wide_kernels():
+    """P = ceil(K / 64) of the wide cases: 5 and 8 (minhash_sig_kernel<*, 8>), 9 and 16 (<*, 16>), with and without a tail"""
+    K = [minhash_cases.WIDE[n][1] for n in minhash_cases.WIDE_NAMES]
+    assert K == [257, 512, 513, 1000, 1024] and [-(-k // 64) for k in K] == [5, 8, 9, 16, 16] and [k % 64 for k in K] == [1, 0, 1, 40, 0]
+    assert [minhash_cases.WIDE[n][2] for n in minhash_cases.WIDE_NAMES] == [(1, 257), (128,), (1, 27), (250, 8), (32,)]
+    for name in minhash_cases.WIDE_NAMES:
+        base = minhash_cases.WIDE[name][0]
+        a, b = _case(name, "ids"), _case(base, "ids")
+        assert [len(r) for r in a["rows"]] == [len(r) for r in b["rows"]] and a["width"] == b["width"] and a["rows"] != b["rows"]
+    assert not set(minhash_cases.WIDE_NAMES) & set(minhash_cases.NAMES)
+
+
+@pytest.mark.parametrize("name,kind", minhash_cases.all_cases() + minhash_cases.wide_cases())
+def test_vectorised_references_match_the_scalar_ones(name, kind):
+    c = _case(name, kind)
+    K = c["n_perm"]
+    for bands in c["bands"]:
+        for seed in SEEDS:
+            keys = mc.band_keys(c["sig"], bands, seed)
+            assert np.array_equal(mc.band_keys_np(c["sig"], bands, seed), keys), (bands, seed)
+            heads = mc.heads_of(keys)
+            assert np.array_equal(mc.heads_of_np(keys), heads), (bands, seed)
+        for min_agree in sorted({1, (K + 1) // 2, K}):
+            want, got = mc.near_first(c["sig"], heads, min_agree), mc.near_first_memo(c["sig"], heads, min_agree)
+            assert np.array_equal(got[0], want[0]) and got[1] == want[1] and np.array_equal(got[2], want[2]), (bands, min_agree)
+
+
+@pytest.mark.parametrize("kind", minhash_cases.KINDS)
+def test_past_cap_case_reaches_every_threshold(kind):
+    """the arithmetic of launch_minhash_sig and of minhash_sig_kernel on the batch, from the mirrored constants"""
+    cap, tile, chunk = 2048, 256, 64          # kMinhashMaxBlocks, kMinhashTile, kMinhashChunk
+    c = minhash_cases.past_cap_case(kind)
+    w, where = c["width"], c["where"]
+    lens = np.diff(c["offs"].astype(np.int64))
+    S = lens.size
+    sh_offs = np.concatenate([[0], np.cumsum(np.maximum(1, lens - w + 1))])
+    M = int(sh_offs[-1])
+    n_tiles = -(-M // tile)
+    grid = min(cap, -(-(c["data"].size + S) // tile))
+    per_block = -(-n_tiles // grid)
+    print(f"{kind}: rows {S}, positions {M}, n_tiles {n_tiles}, grid {grid}, per_block {per_block}")
+    assert M >= cap * tile + tile + 1 and grid == cap and per_block == 2 and 2000 < S < 5000
+    assert n_tiles % 2 == 1 and -(-n_tiles // 2) < grid and chunk < M % tile <= 2 * chunk
+    assert w == 2 and c["n_perm"] == 65 and np.unique(c["data"]).size <= 16
+    run = per_block * tile
+    assert {(e, d) for _, e, d in where["ends"]} == {(e, d) for e in (tile, tile + chunk, run) for d in range(-3, 4)}
+    for row, edge, d in where["ends"]:
+        assert (sh_offs[row + 1] - edge - d) % run == 0 and sh_offs[row + 1] - sh_offs[row] > chunk, (row, edge, d)
+    k = where["inside"]
+    assert sh_offs[k] % run == 30 and sh_offs[k + 1] - sh_offs[k] == 410 and sh_offs[k] // run == (sh_offs[k + 1] - 1) // run
+    k = where["straddle"]
+    assert sh_offs[k] % run == 300 and sh_offs[k + 1] - sh_offs[k] == 5 * tile + 37
+    assert (sh_offs[k + 1] - 1) // run - sh_offs[k] // run == 3
+    assert set(range(w + 3)) <= set(lens.tolist()) and (lens[:3] == 0).all() and (lens[-3:] == 0).all()
+    for seed in SEEDS:
+        assert np.array_equal(_lib.minhash_host(c["data"], c["offs"], w, 65, seed), mc.signatures(c["data"], c["offs"], w, 65, seed)), seed
+
+
+def test_twins_match_the_references_past_the_row_caps():
+    cap, block = 2048, 256                     # kMinhashMaxBlocks, kMinhashBlock
+    sig, alone = minhash_cases.band_rows_sig()
+    S = sig.shape[0]
+    assert S > block * cap and sig.shape[1] == 2
+    for bands in (1, 2):
+        keys = mc.band_keys_np(sig, bands, 3)
+        heads = mc.heads_of_np(keys)
+        twin_keys, twin_heads = _lib.minhash_bands_host(sig, bands, 3)
+        assert np.array_equal(twin_keys, keys) and np.array_equal(twin_heads, heads), bands
+        sizes = np.bincount(heads[:, 0], minlength=S)
+        assert (sizes[alone] == 1).all() and (sizes > 1000).sum() >= 12 and (sizes == 1).sum() == alone.size
+    sig = minhash_cases.verify_rows_sig()
+    S, K = sig.shape
+    assert S > 4 * 16384 and K == 65            # launch_minhash_verify: four rows per block, 8 * kMinhashMaxBlocks blocks
+    heads = mc.heads_of_np(mc.band_keys_np(sig, 13))
+    first, n_clusters, first0 = mc.near_first_memo(sig, heads, 40)
+    twin_first, twin_clusters = _lib.minhash_near_first_host(sig, heads, 40)
+    assert np.array_equal(twin_first, first) and twin_clusters == n_clusters
+    me = np.arange(S)
+    linked = first0 != me
+    agree = (sig == sig[first0]).sum(axis=1)
+    shares_a_band = (heads < me[:, None]).any(axis=1)
+    print(f"rows {S}, clusters {n_clusters}, linked {int(linked.sum())}, share a band with an earlier row but are not linked {int((shares_a_band & ~linked).sum())}")
+    assert linked.sum() > S // 4 and (shares_a_band & ~linked).sum() > 100 and (agree[linked] >= 40).all() and (agree[linked] < 65).any()
+
+
+def test_chains_and_heads_from_elsewhere():
+    for S in minhash_cases.CHAIN_SIZES:
+        sig, heads, want_first, want_clusters, min_agree = minhash_cases.chain_case(S)
+        first, n_clusters = _lib.minhash_near_first_host(sig, heads, min_agree)
+        assert np.array_equal(first, want_first) and n_clusters == want_clusters == 1, S
+    sig, heads, want_first, want_clusters, min_agree = minhash_cases.forest_case()
+    first, n_clusters = _lib.minhash_near_first_host(sig, heads, min_agree)
+    assert np.array_equal(first, want_first) and n_clusters == want_clusters == 16
+    assert np.bincount(want_first)[np.unique(want_first)].tolist()[:6] == [1, 2, 3, 5, 8, 13]
+    ref = mc.near_first_memo(sig, heads, min_agree)
+    assert np.array_equal(ref[0], want_first) and ref[1] == want_clusters
+    # heads that are no row before i are not followed
+    c = _case("contents", "ids")
+    S = len(c["rows"])
+    heads = mc.heads_of(mc.band_keys(c["sig"], 32))
+    wild, tame = minhash_cases.heads_from_elsewhere(heads)
+    me = np.arange(S)[:, None]
+    changed = wild != tame
+    assert changed.sum() > S * 32 // 4 and ((wild[changed] < 0) | (wild[changed] >= np.broadcast_to(me, wild.shape)[changed])).all()
+    assert {int(x) for x in wild[changed]} >= {S, 1 << 40, -1, -(1 << 63)}
+    for min_agree in (1, 64):
+        want = mc.near_first_memo(c["sig"], tame, min_agree)
+        assert np.array_equal(mc.near_first_memo(c["sig"], wild, min_agree)[0], want[0])
+        for h in (wild, tame):
+            first, n_clusters = _lib.minhash_near_first_host(c["sig"], h, min_agree)
+            assert np.array_equal(first, want[0]) and n_clusters == want[1], min_agree
+    assert mc.near_first_memo(c["sig"], tame, 1)[1] < S, "some heads are still followed"
 
 
 def test_value_matches_the_checker():

@@ -1,6 +1,7 @@
 """Near-duplicate rows on the GPU (tgx_corpus_minhash_device, tgx_result_minhash_device, tgx_minhash_bands_device,
 tgx_minhash_near_first_device; csrc/minhash.hip) against the independent checker (tests/minhash_checker.py) and the
-host twins, on the shapes of tests/minhash_cases.py for both kinds, and on real text: test_dedup_gpu.py's corpus under
+host twins, on the shapes of tests/minhash_cases.py for both kinds (K up to 1024, and one batch past the cap of the
+signature kernel's grid), on signatures, chains and heads made with numpy for the calls that take any, and on real text: test_dedup_gpu.py's corpus under
 the spec 32 000 vocabulary, a third of its rows repeated exactly and a further set repeated with one token replaced.
 Everything is compared exactly: this is integer work."""
 import ctypes as C
@@ -50,7 +51,7 @@ def _u64(t):
     return t.cpu().numpy().view(np.uint64)
 
 
-@pytest.mark.parametrize("name,kind", minhash_cases.all_cases())
+@pytest.mark.parametrize("name,kind", minhash_cases.all_cases() + minhash_cases.wide_cases())
 def test_device_matches_checker_and_twin(name, kind):
     import torch
     c = _case(name, kind)
@@ -88,6 +89,110 @@ def test_device_matches_checker_and_twin(name, kind):
         assert list(times) == STAGES and all(t >= 0 for t in times.values())
     finally:
         src.free()
+
+
+# ---- past the caps of the grids, deep chains, heads from elsewhere ---------------------------------------------------------
+
+def _dev(a):
+    """a numpy array (uint32 as its int32 bits) on the device"""
+    import torch
+    a = np.array(a, order="C")   # (a copy: the cases' arrays are read-only)
+    return torch.from_numpy(a.view(np.int32) if a.dtype == np.uint32 else a).cuda()
+
+
+def _near_first(sig, heads, min_agree):
+    """tgx_minhash_near_first_device over numpy sig and heads -> (first, n_clusters)"""
+    import torch
+    d_sig, d_heads = _dev(sig), _dev(heads)
+    S, K = sig.shape
+    first = torch.full((S,), -5, dtype=torch.int64, device="cuda")
+    n_clusters = _lib.minhash_near_first(0, d_sig.data_ptr(), S, K, d_heads.data_ptr(), heads.shape[1], min_agree, first.data_ptr())
+    assert np.array_equal(_u32(d_sig), sig) and np.array_equal(d_heads.cpu().numpy(), heads), "the inputs are only read"
+    return first.cpu().numpy(), n_clusters
+
+
+@pytest.mark.parametrize("kind", minhash_cases.KINDS)
+def test_past_the_caps_signatures(kind):
+    """2048·256 + 2·256 + 70 shingle positions: a block of minhash_sig_kernel takes two tiles, and in the second a wave
+    gallops from the `hi` of its chunk of the first; the last working block takes one tile, of which two waves have
+    nothing (tests/test_minhash_cpu.py holds the batch to this).  K = 65: two permutations per lane, the second a tail."""
+    c = minhash_cases.past_cap_case(kind)
+    src = _source(c)
+    try:
+        for seed in (0, SEED):
+            sig = tgx.minhash(src, c["width"], c["n_perm"], seed)
+            assert np.array_equal(_u32(sig), mc.signatures(c["data"], c["offs"], c["width"], c["n_perm"], seed)), seed
+            assert np.array_equal(_u32(sig), _lib.minhash_host(c["data"], c["offs"], c["width"], c["n_perm"], seed)), seed
+        got = _read(src, kind)
+        assert np.array_equal(got[0], c["data"]) and np.array_equal(got[1], c["offs"]), "the input is only read"
+    finally:
+        src.free()
+
+
+@pytest.mark.parametrize("bands", [1, 2])
+def test_past_the_row_caps_bands(bands):
+    """256·2048 + 300 rows: minhash_iota_kernel and minhash_heads_kernel go round twice, and with two bands so does
+    minhash_band_keys_kernel (a thread per key)"""
+    import torch
+    sig, _ = minhash_cases.band_rows_sig()
+    S, K = sig.shape
+    d_sig = _dev(sig)
+    want_keys = mc.band_keys_np(sig, bands, 3)
+    want_heads = mc.heads_of_np(want_keys)
+    twin_keys, twin_heads = _lib.minhash_bands_host(sig, bands, 3)
+    keys = torch.full((S, bands), -5, dtype=torch.int64, device="cuda")
+    heads = torch.full((S, bands), -5, dtype=torch.int64, device="cuda")
+    _lib.minhash_bands(0, d_sig.data_ptr(), S, K, bands, 3, keys.data_ptr(), heads.data_ptr())
+    assert np.array_equal(_u64(keys), want_keys) and np.array_equal(_u64(keys), twin_keys)
+    assert np.array_equal(heads.cpu().numpy(), want_heads) and np.array_equal(want_heads, twin_heads)
+    assert np.array_equal(_u32(d_sig), sig), "the signatures are only read"
+    t_keys, t_heads = tgx.minhash_bands(d_sig, bands, 3)
+    assert np.array_equal(_u64(t_keys), want_keys) and np.array_equal(t_heads.cpu().numpy(), want_heads)
+
+
+def test_past_the_verify_cap_near_first():
+    """4·16384 + 300 rows of K = 65: minhash_verify_kernel (a wave per row, four to a block, 16384 blocks) goes round twice;
+    13 bands, min_agree 40"""
+    sig = minhash_cases.verify_rows_sig()
+    heads = mc.heads_of_np(mc.band_keys_np(sig, 13))
+    want_first, want_clusters, _ = mc.near_first_memo(sig, heads, 40)
+    twin_first, twin_clusters = _lib.minhash_near_first_host(sig, heads, 40)
+    first, n_clusters = _near_first(sig, heads, 40)
+    assert np.array_equal(first, want_first) and np.array_equal(first, twin_first)
+    assert n_clusters == want_clusters == twin_clusters
+    keys, d_heads = tgx.minhash_bands(_dev(sig), 13)
+    assert np.array_equal(d_heads.cpu().numpy(), heads)
+
+
+@pytest.mark.parametrize("S", minhash_cases.CHAIN_SIZES)
+def test_one_chain_of_every_row(S):
+    """first0[i] = i - 1: a chain as deep as there are rows, so every round of the pointer doubling does work; the
+    expected answer is the construction's"""
+    sig, heads, want_first, want_clusters, min_agree = minhash_cases.chain_case(S)
+    first, n_clusters = _near_first(sig, heads, min_agree)
+    twin_first, twin_clusters = _lib.minhash_near_first_host(sig, heads, min_agree)
+    assert np.array_equal(first, want_first) and np.array_equal(twin_first, want_first)
+    assert n_clusters == want_clusters == twin_clusters == 1
+
+
+def test_a_forest_of_chains():
+    sig, heads, want_first, want_clusters, min_agree = minhash_cases.forest_case()
+    first, n_clusters = _near_first(sig, heads, min_agree)
+    twin_first, twin_clusters = _lib.minhash_near_first_host(sig, heads, min_agree)
+    assert np.array_equal(first, want_first) and np.array_equal(twin_first, want_first)
+    assert n_clusters == want_clusters == twin_clusters
+
+
+def test_heads_from_elsewhere_are_never_followed():
+    """entries of heads overwritten with i, i + 1, S, 2^40, -1 and INT64_MIN give what the same entries set to i give"""
+    c = _case("contents", "ids")
+    sig = np.asarray(c["sig"][0])
+    wild, tame = minhash_cases.heads_from_elsewhere(mc.heads_of(mc.band_keys(sig, 32)))
+    for min_agree in (1, 64, 128):
+        want_first, want_clusters, _ = mc.near_first_memo(sig, tame, min_agree)
+        for heads in (tame, wild):
+            first, n_clusters = _near_first(sig, heads, min_agree)
+            assert np.array_equal(first, want_first) and n_clusters == want_clusters, min_agree
 
 
 # ---- real text --------------------------------------------------------------------------------------------------------

@@ -75,6 +75,27 @@ def test_edges_of_slots_tiles_and_rows(form):
 
 
 @pytest.mark.parametrize("form", nc.FORMS)
+def test_past_cap_corpus_reaches_every_threshold(form):
+    """the arithmetic of csrc/norm.hip's launchers on the corpus, from the mirrored constants, and the twin on it"""
+    cap, tile, block, piece_block = 4096, 4096, 256, 64     # kNormMaxBlocks, kFrontTile, the row kernels' block, kPieceBlock
+    flat, offs = nc.past_cap_corpus()
+    n, S = flat.size, offs.size - 1
+    lens = np.diff(offs.astype(np.int64))
+    assert n > cap * tile + 2 * tile and S > block * cap
+    want_f, want_o = _lib.normalize_flat(form, flat, offs)
+    f, o, k = _lib.normalize_host_twin(form, flat, offs)
+    print(f"{form}: bytes {n}, tiles {-(-n // tile)}, rows {S}, pieces {k}")
+    assert np.array_equal(o, want_o) and np.array_equal(f, want_f)
+    assert k > piece_block * cap
+    # the ASCII of three tiles lies in the second trip's tiles, and there are pieces behind it
+    long = np.flatnonzero(lens == 3 * tile)
+    assert long.size == 1 and int(offs[long[0]]) >= cap * tile
+    run = flat[int(offs[long[0]]):int(offs[long[0] + 1])]
+    assert (run < 128).all() and not np.array_equal(f[int(o[long[0] + 1]):], flat[int(offs[long[0] + 1]):])
+    assert (lens[:-1] + lens[1:] == 0).sum() > 3000
+
+
+@pytest.mark.parametrize("form", nc.FORMS)
 def test_bytes_that_are_not_utf8_pass_through(form):
     _same(form, nc.INVALID, "invalid")
     _same(form, [b"".join(nc.INVALID)], "invalid, one row")

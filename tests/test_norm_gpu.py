@@ -1,7 +1,7 @@
 """Unicode normalisation on the device (tgx_corpus_normalize, csrc/norm.hip): a resident corpus against normalize_flat
 (csrc/unicode_norm.cpp) and the host twin, and the Tokenizer's encode_corpus_* with device_unicode against its flat
 routes.  Everything is compared exactly: this is byte and integer movement.  The inputs are those of tests/norm_cases.py
-(under 1 MB each)."""
+(under 1 MB each, and one of 17 MB that takes the grids past their caps)."""
 import numpy as np
 import pytest
 
@@ -15,13 +15,17 @@ import norm_cases as nc
 
 def _check(form, rows, key):
     """-> the number of pieces"""
-    flat, offs = tgx.pack(list(rows))
+    return _check_flat(form, *tgx.pack(list(rows)), key)
+
+
+def _check_flat(form, flat, offs, key):
+    """_check of a packed batch"""
     want_f, want_o = _lib.normalize_flat(form, flat, offs)
     twin_f, twin_o, twin_k = _lib.normalize_host_twin(form, flat, offs)
     corpus = tgx.NativeCorpus(flat, offs)
     out = corpus.normalize(form)
     try:
-        assert out.device == corpus.device and out.num_samples == len(rows) and out.num_bytes == want_f.size, (form, key)
+        assert out.device == corpus.device and out.num_samples == offs.size - 1 and out.num_bytes == want_f.size, (form, key)
         got_f, got_o = out.bytes(), out.offsets()
         assert np.array_equal(got_o, want_o) and np.array_equal(got_f, want_f), (form, key)
         assert np.array_equal(got_o, twin_o) and np.array_equal(got_f, twin_f) and out.n_pieces == twin_k, (form, key)
@@ -43,6 +47,15 @@ def test_edges_of_slots_tiles_and_rows(form):
 @pytest.mark.parametrize("form", nc.FORMS)
 def test_random_sequences_with_combining_marks(form):
     assert _check(form, nc.random_rows(), "random") > 10000
+
+
+@pytest.mark.parametrize("form", nc.FORMS)
+def test_past_the_caps(form):
+    """nc.past_cap_corpus(): over 4096·4096 + 2·4096 bytes, so norm_mark, norm_pieces (past tiles of ASCII that it skips) and
+    norm_places go round twice; over 256·4096 rows and over 64·4096 pieces, so the kernels with a thread per row or per
+    piece do too (tests/test_norm_cpu.py holds the corpus to this)"""
+    flat, offs = nc.past_cap_corpus()
+    assert _check_flat(form, flat, offs, "past the caps") > 262_144    # kPieceBlock · kNormMaxBlocks
 
 
 @pytest.mark.parametrize("form", nc.FORMS)
