@@ -659,6 +659,86 @@ tgx_status tgx_minhash_near_first_host(const uint32_t *sig, uint64_t n_rows, uin
                                        uint32_t bands, uint32_t min_agree, int64_t *first, uint64_t *n_clusters);
 int tgx_minhash_last_times(const char **names, float *ms, int cap);
 
+/* ---- shared n-grams on the device: gram sets and per-row contamination hits (csrc/gram.hip) ---------------------------
+ * Decontamination: which rows of a large source share an n-gram with a small held-out set (a benchmark, test files),
+ * and how many.  first_equal compares whole rows and MinHash whole-row similarity; a 2 KB problem pasted into a 200 KB
+ * file is seen by neither.  Two steps: a gram set of the held-out source, and a probe of the large one against it.
+ * Integer work, pinned here, the same bits on every machine.
+ *
+ * Definitions.  Row i of a source is the elements data[offs[i] .. offs[i+1]), of eb bytes (eb = 1: a corpus's text
+ *   bytes; eb = 4: a result's u32 ids).  With w = width (1 <= w, w·eb <= 64) the gram AT ELEMENT e of row i (e a global
+ *   element index) is the w elements from e on, and it is VALID iff e + w <= offs[i+1].  A row shorter than w owns no
+ *   gram: unlike MinHash, where every row owns one short shingle, an empty held-out row does not flag every empty row.
+ *     key(e) = tgx_row_hash of the gram's w·eb little-endian bytes under the seed  seed ^ TGX_MINHASH_SALT
+ *   which is MinHash's h(i,t) of a full shingle.  tgx_gram_key(bytes, n_bytes, seed) is that hash of any bytes, exported
+ *   so that another machine can build keys.
+ *   A GRAM SET is the ascending, distinct u64 keys of all valid grams of a source, in device memory, with a bucket
+ *   directory:  bits = n_keys <= 1 ? 0 : min(28, ceil_log2(n_keys));  dir is u32[2^bits + 1];  dir[b] = the lower bound of
+ *   the first key whose top `bits` bits are >= b;  dir[2^bits] = n_keys.  Key k is a member iff a binary search of
+ *   keys[dir[b] .. dir[b+1]), b = the top bits of k, finds it: a bucket holds about one key, and one that an adversary
+ *   filled costs its logarithm.  Membership is by 64-bit key, as with tgx_*_row_hashes_device: PROBABILISTIC in that two
+ *   different grams may share a key (about n_keys / 2^64 per probed gram); hits are not verified against the elements.
+ *
+ * Sets.  tgx_result_gramset_create(r, width, seed, flags, stream, &gs), tgx_corpus_gramset_create(c, ...): the rows' gram
+ *   counts max(0, n_i - w + 1) and their scan, a kernel that writes every valid gram's key to its slot, a radix sort, a
+ *   unique, a host visit for n_keys and the directory kernel (the scan's total, which sizes the sort, is a host visit
+ *   too).  flags must be 0; stream rule, locks and the limit on S as tgx_corpus_first_equal_device.  The source is only
+ *   read.  A source without a valid gram gives a valid set that contains nothing.
+ *   tgx_gramset_create_from_keys(device, host_keys, n, width, elem_bytes, seed, &gs): keys in any order, duplicates
+ *   allowed, sorted and made unique on the device (the library's stream of `device`): how the sets of several sources
+ *   are united, and how a test builds a hostile set.  width, elem_bytes and seed are what a probe hashes with.
+ *   w = 0, w·eb > 64, an elem_bytes other than 1 and 4: TGX_ERR_INVALID.  2^32 - 1 distinct keys or more:
+ *   TGX_ERR_UNSUPPORTED.  A set is read-only after creation, so concurrent hit calls may share it.
+ *   tgx_gramset_size: n_keys.  tgx_gramset_info(gs, &width, &elem_bytes, &seed, &device, &dir_bits): any may be NULL.
+ *   tgx_gramset_keys(gs, host_out): the n_keys keys, ascending, to host memory.  tgx_gramset_free.
+ *
+ * Hits.  tgx_result_gram_hits_device(r, gs, flags, stream, d_count, d_mask), tgx_corpus_gram_hits_device(c, ...), under
+ *   the set's width and seed:
+ *     count[i] = #{ valid grams of row i whose key is in the set }      -> d_count, i64[S]
+ *     mask[e]  = 1 where the gram at element e is valid and in the set, else 0   -> d_mask, u8[n_elems]
+ *   Every byte of both is written.  Either may be NULL, not both.  Both are caller-owned device memory on the source's
+ *   device, checked before anything is queued.  The source's element size or device differing from the set's, host
+ *   memory, nonzero flags: TGX_ERR_INVALID, with nothing queued or written.  S = 0 writes nothing.  The source is only
+ *   read.  Rows with count above a limit are dropped with tgx_*_select, of the corpus and of its result alike.
+ *   The kernel lays the elements of all rows end to end, 64 to a wave and a lane an element: the validity test, the
+ *   loads (an invalid position loads nothing), the hash, the two directory entries, the bucket.  A ballot of the hits is
+ *   cut per row: a row inside the wave's 64 elements gets a plain store, any other a 64-bit atomic add onto the count,
+ *   which was pre-set to 0 and which empty rows keep.
+ *
+ * Host twins, no device, the argument checks of tgx_first_equal_host: tgx_gram_keys_host(data, elem_bytes, offs, n_rows,
+ *   width, seed, keys_out, &n_keys) writes the ascending distinct keys (keys_out has room for n_elems = offs[n_rows]);
+ *   tgx_gram_hits_host(data, elem_bytes, offs, n_rows, width, seed, keys, n_keys, count, mask) takes keys in any order,
+ *   builds the directory and walks the kernel's chunks, tiles and store / add rule through csrc/gram.h;
+ *   tgx_gram_contains_host(keys, n_keys, probes, n_probes, out) is the membership test alone, out u8[n_probes].
+ *
+ * tgx_gram_last_times: device time per stage of the calling thread's last calls, as tgx_minhash_last_times: a create
+ * sets gram_keys_kernel (the counts' scan and the kernel; 0 from keys), gram_sort (sort and unique) and gram_dir; a hits
+ * call sets gram_hits_kernel (the pre-set and the kernel). */
+typedef struct tgx_gramset tgx_gramset;
+uint64_t tgx_gram_key(const uint8_t *bytes, uint64_t n_bytes, uint64_t seed);
+tgx_status tgx_result_gramset_create(const tgx_result *r, uint32_t width, uint64_t seed, uint32_t flags, void *stream,
+                                     tgx_gramset **out);
+tgx_status tgx_corpus_gramset_create(tgx_corpus *c, uint32_t width, uint64_t seed, uint32_t flags, void *stream,
+                                     tgx_gramset **out);
+tgx_status tgx_gramset_create_from_keys(int device, const uint64_t *keys, uint64_t n, uint32_t width, uint32_t elem_bytes,
+                                        uint64_t seed, tgx_gramset **out);
+uint64_t tgx_gramset_size(const tgx_gramset *gs);
+tgx_status tgx_gramset_info(const tgx_gramset *gs, uint32_t *width, uint32_t *elem_bytes, uint64_t *seed, int *device,
+                            uint32_t *dir_bits);
+tgx_status tgx_gramset_keys(const tgx_gramset *gs, uint64_t *keys_out);
+void tgx_gramset_free(tgx_gramset *gs);
+tgx_status tgx_result_gram_hits_device(const tgx_result *r, const tgx_gramset *gs, uint32_t flags, void *stream,
+                                       int64_t *d_count, uint8_t *d_mask);
+tgx_status tgx_corpus_gram_hits_device(tgx_corpus *c, const tgx_gramset *gs, uint32_t flags, void *stream,
+                                       int64_t *d_count, uint8_t *d_mask);
+tgx_status tgx_gram_keys_host(const void *data, uint32_t elem_bytes, const uint64_t *offs, uint64_t n_rows, uint32_t width,
+                              uint64_t seed, uint64_t *keys_out, uint64_t *n_keys);
+tgx_status tgx_gram_hits_host(const void *data, uint32_t elem_bytes, const uint64_t *offs, uint64_t n_rows, uint32_t width,
+                              uint64_t seed, const uint64_t *keys, uint64_t n_keys, int64_t *count, uint8_t *mask);
+tgx_status tgx_gram_contains_host(const uint64_t *keys, uint64_t n_keys, const uint64_t *probes, uint64_t n_probes,
+                                  uint8_t *out);
+int tgx_gram_last_times(const char **names, float *ms, int cap);
+
 /* ---- the front end on the device: a resident corpus split at special tokens, CRLF applied (csrc/front.hip) --------
  * What tgx_split_specials and tgx_pack_segments compute on host threads, for a corpus that is already in HBM (an upload,
  * or tgx_corpus_from_text of a decoded text), with the plan kept on the device for tgx_assemble_result_plan: a resident

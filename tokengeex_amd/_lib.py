@@ -191,6 +191,20 @@ SYMBOLS = {
     "tgx_minhash_bands_host": (_i, [_vp, _u64, _u32, _u32, _u64, _vp, _vp]),
     "tgx_minhash_near_first_host": (_i, [_vp, _u64, _u32, _vp, _u32, _u32, _vp, C.POINTER(C.c_uint64)]),
     "tgx_minhash_last_times": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_float), _i]),
+    "tgx_gram_key": (_u64, [_vp, _u64, _u64]),
+    "tgx_result_gramset_create": (_i, [_vp, _u32, _u64, _u32, _vp, _vp]),
+    "tgx_corpus_gramset_create": (_i, [_vp, _u32, _u64, _u32, _vp, _vp]),
+    "tgx_gramset_create_from_keys": (_i, [_i, _vp, _u64, _u32, _u32, _u64, _vp]),
+    "tgx_gramset_size": (_u64, [_vp]),
+    "tgx_gramset_info": (_i, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_uint32)]),
+    "tgx_gramset_keys": (_i, [_vp, _vp]),
+    "tgx_gramset_free": (None, [_vp]),
+    "tgx_result_gram_hits_device": (_i, [_vp, _vp, _u32, _vp, _vp, _vp]),
+    "tgx_corpus_gram_hits_device": (_i, [_vp, _vp, _u32, _vp, _vp, _vp]),
+    "tgx_gram_keys_host": (_i, [_vp, _u32, _vp, _u64, _u32, _u64, _vp, C.POINTER(C.c_uint64)]),
+    "tgx_gram_hits_host": (_i, [_vp, _u32, _vp, _u64, _u32, _u64, _vp, _u64, _vp, _vp]),
+    "tgx_gram_contains_host": (_i, [_vp, _u64, _vp, _u64, _vp]),
+    "tgx_gram_last_times": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_float), _i]),
 }
 
 
@@ -677,6 +691,129 @@ def minhash_last_times() -> dict[str, float]:
     ms = (C.c_float * 8)()
     n = lib.tgx_minhash_last_times(names, ms, 8)
     return {names[i].decode(): float(ms[i]) for i in range(n)}
+
+
+def _gram_source(data: np.ndarray, offs: np.ndarray):
+    data = np.ascontiguousarray(data)
+    if data.dtype not in (np.uint8, np.uint32):
+        raise TypeError(f"data must be uint8 or uint32 (got {data.dtype})")
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    return data, offs, max(offs.shape[0] - 1, 0)
+
+
+def gram_key(data: bytes, seed: int = 0) -> int:
+    """The key of a gram from its bytes under `seed` (tgx_gram_key; a gram of ids: their little-endian u32 bytes)."""
+    data = bytes(data)
+    return int(lib.tgx_gram_key(data if data else None, len(data), int(seed) & (2**64 - 1)))
+
+
+def gram_keys_host(data: np.ndarray, offs: np.ndarray, width: int, seed: int = 0) -> np.ndarray:
+    """Host twin of a gram set's creation (tgx_gram_keys_host: the kernel's walk through the same header, no device) over
+    data u8[N] or u32[T] and offsets u64[S+1] in elements -> the ascending distinct keys u64[n_keys]."""
+    data, offs, n = _gram_source(data, offs)
+    keys = np.empty(max(data.size, 1), np.uint64)
+    nk = C.c_uint64()
+    check(lib.tgx_gram_keys_host(ptr(data) if data.size else None, data.dtype.itemsize, ptr(offs) if offs.size else None, n, int(width),
+                                 int(seed) & (2**64 - 1), ptr(keys), C.byref(nk)))
+    return keys[:int(nk.value)].copy()
+
+
+def gram_hits_host(data: np.ndarray, offs: np.ndarray, width: int, seed: int, keys: np.ndarray):
+    """Host twin of gram_hits (tgx_gram_hits_host: the directory, the kernel's chunks and its store / add rule, no device)
+    against keys u64[n] in any order -> (count int64[S], mask uint8[n_elems])."""
+    data, offs, n = _gram_source(data, offs)
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    count = np.full(n, -7, np.int64)
+    mask = np.full(data.size, 7, np.uint8)
+    keep = np.zeros(1, np.int64), np.zeros(1, np.uint8)   # (never NULL: both outputs are asked for)
+    check(lib.tgx_gram_hits_host(ptr(data) if data.size else None, data.dtype.itemsize, ptr(offs) if offs.size else None, n, int(width),
+                                 int(seed) & (2**64 - 1), ptr(keys) if keys.size else None, keys.size, ptr(count if n else keep[0]),
+                                 ptr(mask if mask.size else keep[1])))
+    return count, mask
+
+
+def gram_contains_host(keys: np.ndarray, probes: np.ndarray) -> np.ndarray:
+    """Membership of every probe key in the set of `keys` (any order, duplicates allowed) through the directory and
+    bucket search that the kernel uses (tgx_gram_contains_host) -> bool[n_probes]."""
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    probes = np.ascontiguousarray(probes, dtype=np.uint64)
+    out = np.full(probes.size, 7, np.uint8)
+    check(lib.tgx_gram_contains_host(ptr(keys) if keys.size else None, keys.size, ptr(probes) if probes.size else None, probes.size,
+                                     ptr(out) if out.size else None))
+    return out.astype(bool)
+
+
+def gram_last_times() -> dict[str, float]:
+    """Device time in ms of each stage of the calling thread's last gram-set and gram-hits calls (tgx_gram_last_times)."""
+    names = (C.c_char_p * 8)()
+    ms = (C.c_float * 8)()
+    n = lib.tgx_gram_last_times(names, ms, 8)
+    return {names[i].decode(): float(ms[i]) for i in range(n)}
+
+
+class NativeGramSet:
+    """Owns a tgx_gramset: the distinct keys of a source's n-grams in HBM with their bucket directory (csrc/gram.hip).
+    Read-only after creation.  Made by NativeResult.gram_set, NativeCorpus.gram_set or from_keys."""
+
+    KINDS = {1: "bytes", 4: "ids"}
+
+    def __init__(self, handle):
+        self._h = handle
+
+    def __del__(self):
+        self.free()
+
+    def free(self):
+        if getattr(self, "_h", None):
+            lib.tgx_gramset_free(self._h)
+            self._h = None
+
+    @classmethod
+    def from_keys(cls, keys, width: int, kind: str, seed: int = 0, device: int = 0) -> "NativeGramSet":
+        """A set on `device` from host keys u64[n] in any order, duplicates allowed (tgx_gramset_create_from_keys): the
+        union of several sets' keys(), or keys made elsewhere with gram_key.  kind: "bytes" or "ids", with width and seed
+        what a probe hashes its grams with."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        eb = {v: k for k, v in cls.KINDS.items()}[kind]
+        h = C.c_void_p()
+        check(lib.tgx_gramset_create_from_keys(int(device), ptr(keys) if keys.size else None, keys.size, int(width), eb, int(seed) & (2**64 - 1),
+                                               C.byref(h)))
+        return cls(h)
+
+    def _info(self):
+        w, eb, seed, dev, bits = C.c_uint32(), C.c_uint32(), C.c_uint64(), C.c_int(), C.c_uint32()
+        check(lib.tgx_gramset_info(self._h, C.byref(w), C.byref(eb), C.byref(seed), C.byref(dev), C.byref(bits)))
+        return w.value, eb.value, seed.value, dev.value, bits.value
+
+    @property
+    def size(self) -> int:
+        return int(lib.tgx_gramset_size(self._h))
+
+    @property
+    def width(self) -> int:
+        return self._info()[0]
+
+    @property
+    def kind(self) -> str:
+        return self.KINDS[self._info()[1]]
+
+    @property
+    def seed(self) -> int:
+        return self._info()[2]
+
+    @property
+    def device(self) -> int:
+        return self._info()[3]
+
+    @property
+    def dir_bits(self) -> int:
+        return self._info()[4]
+
+    def keys(self) -> np.ndarray:
+        """The set's keys, ascending, copied to the host (tgx_gramset_keys)."""
+        out = np.empty(self.size, np.uint64)
+        check(lib.tgx_gramset_keys(self._h, ptr(out) if out.size else None))
+        return out
 
 
 def front_host(flat: np.ndarray, offs: np.ndarray, specials: list[bytes], crlf: bool):
@@ -1247,6 +1384,20 @@ class NativeResult:
         memory (a raw integer pointer; tgx_result_minhash_device), queued on `stream` as in pad_device."""
         check(lib.tgx_result_minhash_device(self._h, int(width), int(n_perm), int(seed) & (2**64 - 1), 0, stream or None, d_sig or None))
 
+    # -- shared n-grams (include/tgx.h: tgx_result_gramset_create, tgx_result_gram_hits_device; csrc/gram.hip) --
+    def gram_set(self, width: int, seed: int = 0, *, stream: int = 0) -> NativeGramSet:
+        """The set of the keys of every n-gram of `width` ids of the rows (tgx_result_gramset_create), queued on `stream`
+        as in pad_device.  This result is only read."""
+        h = C.c_void_p()
+        check(lib.tgx_result_gramset_create(self._h, int(width), int(seed) & (2**64 - 1), 0, stream or None, C.byref(h)))
+        return NativeGramSet(h)
+
+    def gram_hits(self, grams: NativeGramSet, d_count: int = 0, d_mask: int = 0, *, stream: int = 0) -> None:
+        """Per row the n-grams whose key is in `grams`, as int64[S], and per id whether the n-gram that begins there is
+        one, as u8[T], into caller-owned device memory (raw integer pointers, either may be 0;
+        tgx_result_gram_hits_device)."""
+        check(lib.tgx_result_gram_hits_device(self._h, grams._h, 0, stream or None, d_count or None, d_mask or None))
+
     def pad_host(self, row_len: int, pad_id: int, **kw) -> dict:
         """layout_pad_host over the ids and offsets copied to the host."""
         return layout_pad_host(self.ids(), self.offsets(), row_len, pad_id, **kw)
@@ -1444,6 +1595,19 @@ class NativeCorpus:
         """The MinHash signature of every sample's byte shingles of `width` bytes, as u32[S, n_perm] into caller-owned
         device memory (tgx_corpus_minhash_device).  This corpus is only read."""
         check(lib.tgx_corpus_minhash_device(self._h, int(width), int(n_perm), int(seed) & (2**64 - 1), 0, stream or None, d_sig or None))
+
+    def gram_set(self, width: int, seed: int = 0, *, stream: int = 0) -> NativeGramSet:
+        """The set of the keys of every n-gram of `width` bytes of the samples (tgx_corpus_gramset_create).  This corpus is
+        only read."""
+        h = C.c_void_p()
+        check(lib.tgx_corpus_gramset_create(self._h, int(width), int(seed) & (2**64 - 1), 0, stream or None, C.byref(h)))
+        return NativeGramSet(h)
+
+    def gram_hits(self, grams: NativeGramSet, d_count: int = 0, d_mask: int = 0, *, stream: int = 0) -> None:
+        """Per sample the n-grams whose key is in `grams`, as int64[S], and per byte whether the n-gram that begins there
+        is one, as u8[N], into caller-owned device memory (either may be 0; tgx_corpus_gram_hits_device).  This corpus is
+        only read."""
+        check(lib.tgx_corpus_gram_hits_device(self._h, grams._h, 0, stream or None, d_count or None, d_mask or None))
 
     def normalize(self, form: str) -> "NativeCorpus":
         """The corpus under a Unicode normalisation form ("nfd", "nfc", "nfkd", "nfkc") on the device (tgx_corpus_normalize,

@@ -1,8 +1,8 @@
 // The *_host twins of the result-side device entry points (include/tgx.h): tgx_layout_pad_host, tgx_layout_pack_host,
-// tgx_layout_windows_host, tgx_assemble_host, tgx_fim_host, tgx_select_host, tgx_select_text_host, tgx_shuffled_rows_host, tgx_first_equal_host, tgx_minhash_host, tgx_minhash_bands_host, tgx_minhash_near_first_host, tgx_decode_rows_host, tgx_spans_host, tgx_window_spans_host, tgx_front_host,
+// tgx_layout_windows_host, tgx_assemble_host, tgx_fim_host, tgx_select_host, tgx_select_text_host, tgx_shuffled_rows_host, tgx_first_equal_host, tgx_minhash_host, tgx_minhash_bands_host, tgx_minhash_near_first_host, tgx_gram_keys_host, tgx_gram_hits_host, tgx_gram_contains_host, tgx_decode_rows_host, tgx_spans_host, tgx_window_spans_host, tgx_front_host,
 // tgx_normalize_host and tgx_lattice_stats_host, and the
 // argument checks they share with the device entry points of tgx_api.cpp.  A twin goes through the same index arithmetic as its kernels (layout.h, assemble.h,
-// fim.h, select.h, dedup.h, minhash.h, decode.h, spans.h, front.h, norm.h) on host memory.  Nothing in this file calls a HIP function, so it builds and runs without the
+// fim.h, select.h, dedup.h, minhash.h, gram.h, decode.h, spans.h, front.h, norm.h) on host memory.  Nothing in this file calls a HIP function, so it builds and runs without the
 // handles, the pool or a device.
 #define TGX_HOST_ONLY  // tile_fill.h: the host loop, no kernel side
 #include <algorithm>
@@ -18,6 +18,7 @@
 #include "dedup.h"
 #include "fim.h"
 #include "front.h"
+#include "gram.h"
 #include "layout.h"
 #include "minhash.h"
 #include "norm.h"
@@ -838,6 +839,145 @@ tgx_status tgx_minhash_near_first_host(const uint32_t* sig, uint64_t n_rows, uin
     uint64_t n = 0;
     for (uint64_t i = 0; i < S; i++) n += first[i] == (int64_t)i;
     if (n_clusters) *n_clusters = n;
+    return TGX_OK;
+}
+
+// ---- shared n-grams --------------------------------------------------------------------
+
+uint64_t tgx_gram_key(const uint8_t* bytes, uint64_t n_bytes, uint64_t seed) { return tgx::dedup_row_hash_host(bytes, n_bytes, tgx::minhash_hash_seed(seed)); }
+
+namespace {
+
+tgx_status gram_check_source_host(const char* who, const void* data, uint32_t elem_bytes, const uint64_t* offs, uint64_t n_rows, uint32_t width) {
+    if (elem_bytes != 1 && elem_bytes != 4) return fail(TGX_ERR_INVALID, "%s: elem_bytes %u is neither 1 nor 4", who, elem_bytes);
+    if (width == 0 || (uint64_t)width * elem_bytes > tgx::kMinhashMaxBytes)
+        return fail(TGX_ERR_INVALID, "%s: width %u of %u-byte elements is not in 1 .. %u", who, width, elem_bytes, tgx::kMinhashMaxBytes / elem_bytes);
+    const tgx_status st = check_packed_list(who, "offs", "offsets", offs, n_rows, true);
+    if (st != TGX_OK) return st;
+    if (n_rows >= 0xFFFFFFFFull) return fail(TGX_ERR_UNSUPPORTED, "%s: more than 2^32-1 rows", who);
+    if (offs[n_rows] && !data) return fail(TGX_ERR_INVALID, "%s: data is NULL", who);
+    return TGX_OK;
+}
+
+// The kernels' walk over the elements of all rows laid end to end: tiles of four chunks, the owners of a chunk's ends
+// galloped from the chunk before, every element's owner searched between them.  at(c0, e, i, valid, key) sees every
+// element e, in order, with its row i and the validity and key of the gram that begins there.
+template <class At>
+void gram_walk_host(const uint8_t* bytes, uint32_t elem_bytes, const uint64_t* offs, uint64_t S, uint32_t width, uint64_t seed, At at) {
+    const uint64_t M = S ? offs[S] : 0, hs = tgx::dedup_seed(tgx::minhash_hash_seed(seed));
+    const uint32_t n_bytes = width * elem_bytes;
+    uint64_t hi = 0;
+    for (uint64_t t0 = 0; t0 < M; t0 += tgx::kGramTile) {
+        for (uint64_t c0 = t0; c0 < M && c0 < t0 + tgx::kGramTile; c0 += tgx::kGramChunk) {
+            const uint64_t c_last = tgx::tile_last(c0, tgx::kGramChunk, M);
+            const uint64_t lo = tgx::dedup_find_from(offs, hi, S - 1, c0);
+            hi = tgx::dedup_find_from(offs, lo, S - 1, c_last);
+            for (uint64_t e = c0; e <= c_last; e++) {
+                const uint64_t i = tgx::pack_find_row(offs, 0, lo, hi, e);
+                const bool valid = tgx::gram_valid(e, width, offs[i + 1]);
+                uint64_t key = 0;
+                if (valid) {  // (an invalid position reads nothing)
+                    uint64_t w[tgx::kMinhashMaxBytes / 8] = {};
+                    for (uint32_t j = 0; 8 * j < n_bytes; j++) w[j] = tgx::dedup_word_host(bytes + e * elem_bytes, n_bytes, j);
+                    key = tgx::minhash_hash_words(w, n_bytes, hs);
+                }
+                at(c0, e, i, valid, key);
+            }
+        }
+    }
+}
+
+// the directory of ascending keys
+std::vector<uint32_t> gram_dir_host(const std::vector<uint64_t>& keys, uint32_t bits) {
+    std::vector<uint32_t> dir(((size_t)1 << bits) + 1);
+    for (uint64_t b = 0; b < dir.size(); b++) dir[b] = tgx::gram_dir_entry(keys.data(), keys.size(), bits, b);
+    return dir;
+}
+
+// keys in any order, duplicates allowed -> ascending and distinct, with their directory
+tgx_status gram_set_host(const char* who, const uint64_t* keys, uint64_t n_keys, std::vector<uint64_t>* sorted, std::vector<uint32_t>* dir, uint32_t* bits) {
+    if (n_keys && !keys) return fail(TGX_ERR_INVALID, "%s: keys is NULL", who);
+    sorted->assign(keys, keys + n_keys);
+    std::sort(sorted->begin(), sorted->end());
+    sorted->erase(std::unique(sorted->begin(), sorted->end()), sorted->end());
+    if (sorted->size() > tgx::kGramMaxKeys) return fail(TGX_ERR_UNSUPPORTED, "%s: more than 2^32-2 keys", who);
+    *bits = tgx::gram_dir_bits(sorted->size());
+    *dir = gram_dir_host(*sorted, *bits);
+    return TGX_OK;
+}
+
+}  // namespace
+
+tgx_status tgx_gram_keys_host(const void* data, uint32_t elem_bytes, const uint64_t* offs, uint64_t n_rows, uint32_t width, uint64_t seed,
+                              uint64_t* keys_out, uint64_t* n_keys) {
+    const char* who = "tgx_gram_keys_host";
+    if (n_keys) *n_keys = 0;
+    const tgx_status st = gram_check_source_host(who, data, elem_bytes, offs, n_rows, width);
+    if (st != TGX_OK) return st;
+    if (!n_keys) return fail(TGX_ERR_INVALID, "%s: n_keys is NULL", who);
+    if (offs[n_rows] && !keys_out) return fail(TGX_ERR_INVALID, "%s: keys_out is NULL", who);
+    // every valid gram's key to its slot, as gram_keys_kernel; then the sort and the unique
+    std::vector<uint64_t> g_offs(n_rows + 1, 0);
+    for (uint64_t k = 0; k < n_rows; k++) g_offs[k + 1] = g_offs[k] + tgx::gram_row_count(offs, n_rows, width, k);
+    std::vector<uint64_t> raw(g_offs[n_rows]);
+    gram_walk_host(static_cast<const uint8_t*>(data), elem_bytes, offs, n_rows, width, seed, [&](uint64_t, uint64_t e, uint64_t i, bool valid, uint64_t key) {
+        if (valid) raw[g_offs[i] + (e - offs[i])] = key;
+    });
+    std::sort(raw.begin(), raw.end());
+    raw.erase(std::unique(raw.begin(), raw.end()), raw.end());
+    if (raw.size() > tgx::kGramMaxKeys) return fail(TGX_ERR_UNSUPPORTED, "%s: more than 2^32-2 keys", who);
+    std::copy(raw.begin(), raw.end(), keys_out);
+    *n_keys = raw.size();
+    return TGX_OK;
+}
+
+tgx_status tgx_gram_hits_host(const void* data, uint32_t elem_bytes, const uint64_t* offs, uint64_t n_rows, uint32_t width, uint64_t seed,
+                              const uint64_t* keys, uint64_t n_keys, int64_t* count, uint8_t* mask) {
+    const char* who = "tgx_gram_hits_host";
+    tgx_status st = gram_check_source_host(who, data, elem_bytes, offs, n_rows, width);
+    if (st != TGX_OK) return st;
+    if (!count && !mask) return fail(TGX_ERR_INVALID, "%s: count and mask are both NULL", who);
+    std::vector<uint64_t> sorted;
+    std::vector<uint32_t> dir;
+    uint32_t bits = 0;
+    if ((st = gram_set_host(who, keys, n_keys, &sorted, &dir, &bits)) != TGX_OK) return st;
+    if (n_rows == 0) return TGX_OK;
+    if (count) std::fill(count, count + n_rows, 0);  // the launcher's pre-set
+    // a stretch of one row inside a chunk ends when the owner or the chunk changes: then the kernel's store / add rule
+    uint64_t cur_c0 = 0, cur_row = 0, n_hits = 0;
+    bool open = false;
+    auto flush = [&]() {
+        if (!open || !count) return;
+        if (tgx::gram_row_inside(offs, cur_row, cur_c0))
+            count[cur_row] = (int64_t)n_hits;
+        else if (tgx::gram_adds(n_hits))
+            count[cur_row] += (int64_t)n_hits;
+    };
+    gram_walk_host(static_cast<const uint8_t*>(data), elem_bytes, offs, n_rows, width, seed, [&](uint64_t c0, uint64_t e, uint64_t i, bool valid, uint64_t key) {
+        if (!open || c0 != cur_c0 || i != cur_row) {
+            flush();
+            open = true;
+            cur_c0 = c0;
+            cur_row = i;
+            n_hits = 0;
+        }
+        const bool hit = valid && tgx::gram_contains(sorted.data(), dir.data(), bits, key);
+        if (mask) mask[e] = hit ? 1 : 0;
+        n_hits += hit;
+    });
+    flush();
+    return TGX_OK;
+}
+
+tgx_status tgx_gram_contains_host(const uint64_t* keys, uint64_t n_keys, const uint64_t* probes, uint64_t n_probes, uint8_t* out) {
+    const char* who = "tgx_gram_contains_host";
+    std::vector<uint64_t> sorted;
+    std::vector<uint32_t> dir;
+    uint32_t bits = 0;
+    const tgx_status st = gram_set_host(who, keys, n_keys, &sorted, &dir, &bits);
+    if (st != TGX_OK) return st;
+    if (n_probes && (!probes || !out)) return fail(TGX_ERR_INVALID, "%s: %s is NULL", who, probes ? "out" : "probes");
+    for (uint64_t p = 0; p < n_probes; p++) out[p] = tgx::gram_contains(sorted.data(), dir.data(), bits, probes[p]) ? 1 : 0;
     return TGX_OK;
 }
 

@@ -271,6 +271,38 @@ def near_unique_rows(sig, bands: int, threshold: float, seed: int = 0):
     return (first == torch.arange(first.shape[0], dtype=torch.int64, device=first.device)).nonzero().reshape(-1)
 
 
+# ---- shared n-grams on the device: decontamination (csrc/gram.hip) -------------------------------------------------------
+
+def gram_set(obj, width: int, seed: int = 0):
+    """-> a NativeGramSet on obj's device: the distinct 64-bit keys of every n-gram of `width` elements of obj's rows (a
+    NativeResult: ids; a NativeCorpus: bytes), queued on torch's current stream.  Made of a small held-out set and handed
+    to gram_hits.  A row shorter than `width` owns no n-gram."""
+    import torch
+    dev = _device_of(torch, obj)
+    return obj.gram_set(width, seed, stream=torch.cuda.current_stream(dev).cuda_stream)
+
+
+def gram_hits(obj, grams, return_mask: bool = False):
+    """-> [S] torch.int64 on obj's device: per row the n-grams (of grams.width elements) whose key is in `grams`; with
+    return_mask also [n_elems] torch.uint8, 1 where such an n-gram begins.  Membership is by 64-bit key, so
+    probabilistic in the sense of row_hashes; a hit is not verified against the elements."""
+    import torch
+    dev = _device_of(torch, obj)
+    count = torch.empty((obj.num_samples,), dtype=torch.int64, device=dev)
+    n_elems = obj.num_tokens if isinstance(obj, _lib.NativeResult) else obj.num_bytes
+    mask = torch.empty((n_elems,), dtype=torch.uint8, device=dev) if return_mask else None
+    spare = torch.empty(1, dtype=torch.int64, device=dev)  # (no row: the pointer still says that the counts are asked for)
+    obj.gram_hits(grams, (count if count.numel() else spare).data_ptr(), mask.data_ptr() if return_mask and n_elems else 0,
+                  stream=torch.cuda.current_stream(dev).cuda_stream)
+    return (count, mask) if return_mask else count
+
+
+def clean_rows(obj, grams, max_hits: int = 0):
+    """-> torch.int64 indices, ascending, of the rows of obj with at most max_hits n-grams in `grams`: what `select` takes
+    to drop the contaminated rows (of a corpus and, with the same indices, of its encoded result)."""
+    return (gram_hits(obj, grams) <= int(max_hits)).nonzero().reshape(-1)
+
+
 def _window_len(max_length, stride) -> tuple[int, int]:
     if max_length is None:
         raise TypeError("max_length is required for overflow windows")
