@@ -739,6 +739,72 @@ tgx_status tgx_gram_contains_host(const uint64_t *keys, uint64_t n_keys, const u
                                   uint8_t *out);
 int tgx_gram_last_times(const char **names, float *ms, int cap);
 
+/* ---- per-row text statistics and the line view of a resident corpus (csrc/textstat.hip) --------------------------------
+ * The heuristic quality filters of code corpora (a longest line over 1000 characters, a mean line length over 100, an
+ * alphanumeric share under 0.25, the share of duplicate lines) need per row a handful of counts and the lines
+ * themselves.  Two calls give both where the documents already lie.  Integer work, pinned here, the same on every machine.
+ *
+ * Definitions.  Row i is the bytes text[offs[i] .. offs[i+1]) of the corpus.
+ *   Terminator: only '\n' (0x0A) ends a line; '\r' is an ordinary byte.  A caller who wants CRLF folded runs the CRLF
+ *     front end first (tgx_corpus_split_specials with TGX_FRONT_CRLF).
+ *   Line end: position p of row i is a line end iff text[p] == '\n' or p == offs[i+1] - 1.
+ *   Line start: the line ending at p begins at max(offs[i], q + 1), q being the last '\n' before p at or after offs[i].
+ *   So no line continues from one row into the next, a trailing '\n' opens no empty last line, "\n" is one empty line,
+ *     and an empty row has no line.
+ *   Line length: without its '\n'; in bytes, or under TGX_TEXTSTAT_CHARS in characters.
+ *   Character: a byte b with (b & 0xC0) != 0x80, so everything is defined by bytes alone, on invalid UTF-8 too.
+ *
+ * tgx_corpus_text_stats_device(c, line_limit, flags, stream, d_stats, d_line_start) writes d_stats, int64
+ *   [TGX_TEXTSTAT_N, S], each statistic contiguous over the rows:
+ *      0 bytes       offs[i+1] - offs[i]
+ *      1 chars       characters
+ *      2 newlines    bytes equal to '\n'
+ *      3 lines       line ends
+ *      4 max_line    the longest line's length in the unit; 0 without a line
+ *      5 long_lines  lines whose length in the unit is greater than line_limit
+ *      6 alpha       A-Z, a-z
+ *      7 digit       0-9
+ *      8 space       0x20 and 0x09 .. 0x0D
+ *      9 non_ascii   bytes >= 0xC0: the characters that are not ASCII
+ *     10 control     bytes < 0x20 that are not space, and 0x7F
+ *   and d_line_start, u8[n_bytes]: 1 where a line begins (a nonempty row's first byte, or a byte after a '\n' within its
+ *   row), else 0.  Every byte of both is written.  Either may be NULL, not both.  Both are caller-owned device memory on
+ *   the corpus's device, checked before anything is queued; host memory or a flag other than TGX_TEXTSTAT_CHARS:
+ *   TGX_ERR_INVALID, with nothing queued or written.  Stream rule, the corpus's lock and the limit on S (S < 2^32 - 1) as
+ *   tgx_corpus_gram_hits_device.  S = 0 writes nothing.  The corpus is only read.
+ *   The kernels lay the bytes of all rows end to end, 64 to a wave and a lane a byte.  A first kernel writes one word per
+ *   64 bytes (has the chunk a line start; the units from its last line start on), a scan under the segmented sum turns
+ *   the words into the units of the line that is open at each chunk's first byte, and the second kernel cuts ballots of
+ *   the classes, the line ends and the long lines per row: a row inside the wave's 64 bytes gets plain stores, any other
+ *   64-bit atomic adds (max_line: an atomic maximum) onto the table, which was pre-set to 0 and which empty rows keep.  A
+ *   line's length never costs a walk back over the line: the time does not depend on the lines' lengths.
+ *
+ * tgx_corpus_lines(c, flags, stream, &out): a new corpus whose rows are the lines of c, in order, each with its '\n' if
+ *   it has one: the same bytes as c, its offsets the line starts plus n_bytes.  flags must be 0.  The line starts above
+ *   are compacted on the device; their number and then the offsets visit the host, as in tgx_corpus_select.  2^32 - 1
+ *   lines or more: TGX_ERR_UNSUPPORTED.  A corpus with no line gives an empty corpus.  The row a line came from needs no
+ *   call: it is repeat_interleave(arange(S), lines).
+ *
+ * Host twins, no device, the argument checks of the select twins (offs[0] = 0 and ascending): tgx_text_stats_host(text,
+ *   offs, n_rows, line_limit, flags, stats, line_start) writes stats i64[TGX_TEXTSTAT_N, n_rows] and line_start
+ *   u8[offs[n_rows]] (either may be NULL, not both); tgx_lines_host(text, offs, n_rows, out_offs, cap, &n_lines) writes
+ *   the n_lines + 1 offsets of the line view into out_offs u64[cap] (cap < n_lines + 1: TGX_ERR_INVALID, with n_lines
+ *   set).  Both walk the kernel's chunks, tiles, summaries, carry and store / add rule through csrc/textstat.h.
+ *
+ * tgx_textstat_last_times: device time per stage of the calling thread's last call, as tgx_gram_last_times (the names are
+ * listed without a call): textstat_summary_kernel, textstat_scan, textstat_kernel (the pre-set and the kernel), and
+ * textstat_lines (the count and the compaction of the line starts; 0 after a statistics call). */
+#define TGX_TEXTSTAT_N 11
+#define TGX_TEXTSTAT_CHARS 1u
+tgx_status tgx_corpus_text_stats_device(tgx_corpus *c, uint64_t line_limit, uint32_t flags, void *stream, int64_t *d_stats,
+                                        uint8_t *d_line_start);
+tgx_status tgx_corpus_lines(tgx_corpus *c, uint32_t flags, void *stream, tgx_corpus **out);
+tgx_status tgx_text_stats_host(const uint8_t *text, const uint64_t *offs, uint64_t n_rows, uint64_t line_limit, uint32_t flags,
+                               int64_t *stats, uint8_t *line_start);
+tgx_status tgx_lines_host(const uint8_t *text, const uint64_t *offs, uint64_t n_rows, uint64_t *out_offs, uint64_t cap,
+                          uint64_t *n_lines);
+int tgx_textstat_last_times(const char **names, float *ms, int cap);
+
 /* ---- the front end on the device: a resident corpus split at special tokens, CRLF applied (csrc/front.hip) --------
  * What tgx_split_specials and tgx_pack_segments compute on host threads, for a corpus that is already in HBM (an upload,
  * or tgx_corpus_from_text of a decoded text), with the plan kept on the device for tgx_assemble_result_plan: a resident

@@ -205,6 +205,11 @@ SYMBOLS = {
     "tgx_gram_hits_host": (_i, [_vp, _u32, _vp, _u64, _u32, _u64, _vp, _u64, _vp, _vp]),
     "tgx_gram_contains_host": (_i, [_vp, _u64, _vp, _u64, _vp]),
     "tgx_gram_last_times": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_float), _i]),
+    "tgx_corpus_text_stats_device": (_i, [_vp, _u64, _u32, _vp, _vp, _vp]),
+    "tgx_corpus_lines": (_i, [_vp, _u32, _vp, _vp]),
+    "tgx_text_stats_host": (_i, [_vp, _vp, _u64, _u64, _u32, _vp, _vp]),
+    "tgx_lines_host": (_i, [_vp, _vp, _u64, _vp, _u64, C.POINTER(C.c_uint64)]),
+    "tgx_textstat_last_times": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_float), _i]),
 }
 
 
@@ -748,6 +753,53 @@ def gram_last_times() -> dict[str, float]:
     names = (C.c_char_p * 8)()
     ms = (C.c_float * 8)()
     n = lib.tgx_gram_last_times(names, ms, 8)
+    return {names[i].decode(): float(ms[i]) for i in range(n)}
+
+
+# ---- per-row text statistics and the line view (include/tgx.h; csrc/textstat.hip, csrc/textstat.h) ----
+TEXTSTAT_N = 11
+TEXTSTAT_CHARS = 1
+TEXTSTAT_NAMES = ("bytes", "chars", "newlines", "lines", "max_line", "long_lines", "alpha", "digit", "space", "non_ascii", "control")
+
+
+def textstat_flags(unit: str) -> int:
+    """unit "char" or "byte" -> the flags of tgx_corpus_text_stats_device."""
+    if unit not in ("char", "byte"):
+        raise ValueError(f"unit must be 'char' or 'byte' (got {unit!r})")
+    return TEXTSTAT_CHARS if unit == "char" else 0
+
+
+def text_stats_host(text: np.ndarray, offs: np.ndarray, line_limit: int = 1000, unit: str = "char"):
+    """Host twin of NativeCorpus.text_stats (tgx_text_stats_host: the kernel's chunks, summaries, carry and store / add
+    rule through the same header, no device) over text u8[N] and offsets u64[S+1] -> (stats int64[11, S], line_start
+    uint8[N])."""
+    text = np.ascontiguousarray(text, dtype=np.uint8)
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    n = max(offs.shape[0] - 1, 0)
+    stats = np.full((TEXTSTAT_N, n), -7, np.int64)
+    marks = np.full(text.size, 7, np.uint8)
+    keep = np.zeros(1, np.int64), np.zeros(1, np.uint8)   # (never NULL: both outputs are asked for)
+    check(lib.tgx_text_stats_host(ptr(text) if text.size else None, ptr(offs) if offs.size else None, n, int(line_limit), textstat_flags(unit),
+                                  ptr(stats if n else keep[0]), ptr(marks if marks.size else keep[1])))
+    return stats, marks
+
+
+def lines_host(text: np.ndarray, offs: np.ndarray) -> np.ndarray:
+    """Host twin of NativeCorpus.lines (tgx_lines_host) -> the offsets u64[n_lines + 1] of the line view."""
+    text = np.ascontiguousarray(text, dtype=np.uint8)
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    n = max(offs.shape[0] - 1, 0)
+    out = np.full(text.size + 1, 7, np.uint64)
+    nl = C.c_uint64()
+    check(lib.tgx_lines_host(ptr(text) if text.size else None, ptr(offs) if offs.size else None, n, ptr(out), out.size, C.byref(nl)))
+    return out[:int(nl.value) + 1].copy()
+
+
+def textstat_last_times() -> dict[str, float]:
+    """Device time in ms of each stage of the calling thread's last text_stats or lines call (tgx_textstat_last_times)."""
+    names = (C.c_char_p * 8)()
+    ms = (C.c_float * 8)()
+    n = lib.tgx_textstat_last_times(names, ms, 8)
     return {names[i].decode(): float(ms[i]) for i in range(n)}
 
 
@@ -1608,6 +1660,22 @@ class NativeCorpus:
         is one, as u8[N], into caller-owned device memory (either may be 0; tgx_corpus_gram_hits_device).  This corpus is
         only read."""
         check(lib.tgx_corpus_gram_hits_device(self._h, grams._h, 0, stream or None, d_count or None, d_mask or None))
+
+    def text_stats(self, d_stats: int = 0, d_line_start: int = 0, line_limit: int = 1000, unit: str = "char", *, stream: int = 0) -> None:
+        """Per sample the eleven statistics of include/tgx.h as int64[11, S] (TEXTSTAT_NAMES; lengths in `unit`, "char" or
+        "byte"), and per byte whether a line begins there, as u8[N], into caller-owned device memory (either may be 0;
+        tgx_corpus_text_stats_device).  This corpus is only read."""
+        check(lib.tgx_corpus_text_stats_device(self._h, int(line_limit), textstat_flags(unit), stream or None, d_stats or None, d_line_start or None))
+
+    def lines(self, *, stream: int = 0) -> "NativeCorpus":
+        """A new resident corpus whose samples are the lines of this one, in order, each with its '\\n' if it has one
+        (tgx_corpus_lines).  This corpus is only read."""
+        hc = C.c_void_p()
+        check(lib.tgx_corpus_lines(self._h, 0, stream or None, C.byref(hc)))
+        c = NativeCorpus.__new__(NativeCorpus)
+        c._h = hc
+        c.device = self.device
+        return c
 
     def normalize(self, form: str) -> "NativeCorpus":
         """The corpus under a Unicode normalisation form ("nfd", "nfc", "nfkd", "nfkc") on the device (tgx_corpus_normalize,

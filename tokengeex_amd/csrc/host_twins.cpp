@@ -1,8 +1,8 @@
 // The *_host twins of the result-side device entry points (include/tgx.h): tgx_layout_pad_host, tgx_layout_pack_host,
-// tgx_layout_windows_host, tgx_assemble_host, tgx_fim_host, tgx_select_host, tgx_select_text_host, tgx_shuffled_rows_host, tgx_first_equal_host, tgx_minhash_host, tgx_minhash_bands_host, tgx_minhash_near_first_host, tgx_gram_keys_host, tgx_gram_hits_host, tgx_gram_contains_host, tgx_decode_rows_host, tgx_spans_host, tgx_window_spans_host, tgx_front_host,
+// tgx_layout_windows_host, tgx_assemble_host, tgx_fim_host, tgx_select_host, tgx_select_text_host, tgx_shuffled_rows_host, tgx_first_equal_host, tgx_minhash_host, tgx_minhash_bands_host, tgx_minhash_near_first_host, tgx_gram_keys_host, tgx_gram_hits_host, tgx_gram_contains_host, tgx_text_stats_host, tgx_lines_host, tgx_decode_rows_host, tgx_spans_host, tgx_window_spans_host, tgx_front_host,
 // tgx_normalize_host and tgx_lattice_stats_host, and the
 // argument checks they share with the device entry points of tgx_api.cpp.  A twin goes through the same index arithmetic as its kernels (layout.h, assemble.h,
-// fim.h, select.h, dedup.h, minhash.h, gram.h, decode.h, spans.h, front.h, norm.h) on host memory.  Nothing in this file calls a HIP function, so it builds and runs without the
+// fim.h, select.h, dedup.h, minhash.h, gram.h, textstat.h, decode.h, spans.h, front.h, norm.h) on host memory.  Nothing in this file calls a HIP function, so it builds and runs without the
 // handles, the pool or a device.
 #define TGX_HOST_ONLY  // tile_fill.h: the host loop, no kernel side
 #include <algorithm>
@@ -24,6 +24,7 @@
 #include "norm.h"
 #include "select.h"
 #include "spans.h"
+#include "textstat.h"
 #include "unicode_tables.h"
 
 using namespace tgx::host;
@@ -978,6 +979,153 @@ tgx_status tgx_gram_contains_host(const uint64_t* keys, uint64_t n_keys, const u
     if (st != TGX_OK) return st;
     if (n_probes && (!probes || !out)) return fail(TGX_ERR_INVALID, "%s: %s is NULL", who, probes ? "out" : "probes");
     for (uint64_t p = 0; p < n_probes; p++) out[p] = tgx::gram_contains(sorted.data(), dir.data(), bits, probes[p]) ? 1 : 0;
+    return TGX_OK;
+}
+
+// ---- text statistics and the line view ------------------------------------------------------
+
+namespace {
+
+tgx_status textstat_check_source_host(const char* who, const uint8_t* text, const uint64_t* offs, uint64_t n_rows) {
+    const tgx_status st = check_packed_list(who, "offs", "offsets", offs, n_rows, true);
+    if (st != TGX_OK) return st;
+    if (n_rows >= 0xFFFFFFFFull) return fail(TGX_ERR_UNSUPPORTED, "%s: more than 2^32-1 rows", who);
+    if (offs[n_rows] && !text) return fail(TGX_ERR_INVALID, "%s: text is NULL", who);
+    return TGX_OK;
+}
+
+// The kernels' walk over the bytes of all rows laid end to end: tiles of four chunks, the owners of a chunk's ends
+// galloped from the chunk before, every byte's owner searched between them.  body(c0, n_in, starts, row) sees every
+// chunk, in order, with the mask of its line starts and its lanes' owners.
+template <class Body>
+void textstat_walk_host(const uint8_t* text, const uint64_t* offs, uint64_t S, Body body) {
+    const uint64_t M = S ? offs[S] : 0;
+    uint64_t hi = 0;
+    for (uint64_t t0 = 0; t0 < M; t0 += tgx::kTextstatTile) {
+        for (uint64_t c0 = t0; c0 < M && c0 < t0 + tgx::kTextstatTile; c0 += tgx::kTextstatChunk) {
+            const uint64_t c_last = tgx::tile_last(c0, tgx::kTextstatChunk, M);
+            const uint64_t lo = tgx::dedup_find_from(offs, hi, S - 1, c0);
+            hi = tgx::dedup_find_from(offs, lo, S - 1, c_last);
+            const uint32_t n_in = (uint32_t)(c_last - c0) + 1;
+            uint64_t row[tgx::kTextstatChunk], nl = 0, starts = 0;
+            for (uint32_t l = 0; l < n_in; l++) {
+                row[l] = tgx::pack_find_row(offs, 0, lo, hi, c0 + l);
+                if (text[c0 + l] == '\n') nl |= 1ull << l;
+            }
+            const uint64_t after_nl = (nl << 1) | (c0 > 0 && text[c0 - 1] == '\n' ? 1ull : 0ull);
+            for (uint32_t l = 0; l < n_in; l++)
+                if (c0 + l == offs[row[l]] || ((after_nl >> l) & 1ull)) starts |= 1ull << l;
+            body(c0, n_in, starts, row);
+        }
+    }
+}
+
+// a class's mask over the n_in bytes from c0 on
+template <class Is>
+uint64_t textstat_mask_host(const uint8_t* text, uint64_t c0, uint32_t n_in, Is is) {
+    uint64_t m = 0;
+    for (uint32_t l = 0; l < n_in; l++)
+        if (is(text[c0 + l])) m |= 1ull << l;
+    return m;
+}
+
+// What the two twins share: the summaries, their scan, and the second kernel with its store / add rule.  The source has
+// been checked, n_rows > 0; stats and line_start may each be NULL.
+void textstat_host(const uint8_t* text, const uint64_t* offs, uint64_t S, uint64_t line_limit, uint32_t flags, int64_t* stats, uint8_t* line_start) {
+    const uint64_t N = offs[S], n_chunks = (N + tgx::kTextstatChunk - 1) / tgx::kTextstatChunk;
+    auto units_of = [&](uint64_t c0, uint32_t n_in) { return textstat_mask_host(text, c0, n_in, [&](uint8_t b) { return tgx::textstat_is_unit(b, flags); }); };
+    if (stats) std::fill(stats, stats + S * tgx::kTextstatN, 0);  // the launcher's pre-set
+    std::vector<uint64_t> summary(n_chunks), carry(n_chunks);
+    textstat_walk_host(text, offs, S, [&](uint64_t c0, uint32_t n_in, uint64_t starts, const uint64_t*) {
+        summary[c0 / tgx::kTextstatChunk] = tgx::textstat_summary(starts, units_of(c0, n_in));
+    });
+    uint64_t acc = 0;  // the exclusive scan under the segmented sum
+    for (uint64_t k = 0; k < n_chunks; k++) {
+        carry[k] = acc;
+        acc = tgx::TextstatCarryOp()(acc, summary[k]);
+    }
+    textstat_walk_host(text, offs, S, [&](uint64_t c0, uint32_t n_in, uint64_t starts, const uint64_t* row) {
+        if (line_start)
+            for (uint32_t l = 0; l < n_in; l++) line_start[c0 + l] = (uint8_t)((starts >> l) & 1ull);
+        if (!stats) return;
+        const uint64_t units = units_of(c0, n_in);
+        uint64_t ends = 0, longs = 0, len[tgx::kTextstatChunk] = {};
+        for (uint32_t l = 0; l < n_in; l++) {
+            const bool is_nl = text[c0 + l] == '\n';
+            if (!is_nl && c0 + l + 1 != offs[row[l] + 1]) continue;
+            ends |= 1ull << l;
+            len[l] = tgx::textstat_line_len(starts, units, l, is_nl, carry[c0 / tgx::kTextstatChunk]);
+            if (len[l] > line_limit) longs |= 1ull << l;
+        }
+        uint64_t ballots[tgx::kTextstatN] = {};
+        ballots[tgx::kTsChars] = textstat_mask_host(text, c0, n_in, tgx::textstat_is_char);
+        ballots[tgx::kTsNewlines] = textstat_mask_host(text, c0, n_in, [](uint8_t b) { return b == '\n'; });
+        ballots[tgx::kTsLines] = ends;
+        ballots[tgx::kTsLongLines] = longs;
+        ballots[tgx::kTsAlpha] = textstat_mask_host(text, c0, n_in, tgx::textstat_is_alpha);
+        ballots[tgx::kTsDigit] = textstat_mask_host(text, c0, n_in, tgx::textstat_is_digit);
+        ballots[tgx::kTsSpace] = textstat_mask_host(text, c0, n_in, tgx::textstat_is_space);
+        ballots[tgx::kTsNonAscii] = textstat_mask_host(text, c0, n_in, tgx::textstat_is_non_ascii);
+        ballots[tgx::kTsControl] = textstat_mask_host(text, c0, n_in, tgx::textstat_is_control);
+        for (uint32_t a = 0; a < n_in;) {  // the stretch [a, b] of one row
+            uint32_t b = a;
+            while (b + 1 < n_in && row[b + 1] == row[a]) b++;
+            const uint64_t i = row[a], stretch = tgx::textstat_span(a, b);
+            const bool inside = tgx::textstat_row_inside(offs, i, c0);
+            if (c0 + a == offs[i]) stats[tgx::kTsBytes * S + i] = (int64_t)(offs[i + 1] - offs[i]);
+            uint64_t longest = 0;
+            for (uint32_t l = a; l <= b; l++) longest = std::max(longest, len[l]);
+            int64_t& max_line = stats[tgx::kTsMaxLine * S + i];
+            if (inside)
+                max_line = (int64_t)longest;
+            else if (tgx::textstat_adds(longest))
+                max_line = std::max(max_line, (int64_t)longest);
+            for (uint32_t k = 0; k < tgx::kTextstatN; k++) {
+                if (k == tgx::kTsBytes || k == tgx::kTsMaxLine) continue;
+                const uint64_t v = tgx::textstat_popc(ballots[k] & stretch);
+                if (inside)
+                    stats[k * S + i] = (int64_t)v;
+                else if (tgx::textstat_adds(v))
+                    stats[k * S + i] += (int64_t)v;
+            }
+            a = b + 1;
+        }
+    });
+}
+
+}  // namespace
+
+tgx_status tgx_text_stats_host(const uint8_t* text, const uint64_t* offs, uint64_t n_rows, uint64_t line_limit, uint32_t flags, int64_t* stats,
+                               uint8_t* line_start) {
+    const char* who = "tgx_text_stats_host";
+    tgx_status st = textstat_check_source_host(who, text, offs, n_rows);
+    if (st != TGX_OK) return st;
+    if ((st = layout_check_flags(who, flags, tgx::kTextstatChars)) != TGX_OK) return st;
+    if (!stats && !line_start) return fail(TGX_ERR_INVALID, "%s: stats and line_start are both NULL", who);
+    if (n_rows == 0) return TGX_OK;
+    textstat_host(text, offs, n_rows, line_limit, flags, stats, line_start);
+    return TGX_OK;
+}
+
+tgx_status tgx_lines_host(const uint8_t* text, const uint64_t* offs, uint64_t n_rows, uint64_t* out_offs, uint64_t cap, uint64_t* n_lines) {
+    const char* who = "tgx_lines_host";
+    if (n_lines) *n_lines = 0;
+    const tgx_status st = textstat_check_source_host(who, text, offs, n_rows);
+    if (st != TGX_OK) return st;
+    if (!n_lines) return fail(TGX_ERR_INVALID, "%s: n_lines is NULL", who);
+    const uint64_t N = offs[n_rows];
+    std::vector<uint8_t> marks(N);
+    if (n_rows && N) textstat_host(text, offs, n_rows, 0, 0, nullptr, marks.data());
+    uint64_t n = 0;
+    for (uint64_t p = 0; p < N; p++) n += marks[p];
+    *n_lines = n;
+    if (n > tgx::kTextstatMaxLines) return fail(TGX_ERR_UNSUPPORTED, "%s: 2^32-1 lines or more", who);
+    if (cap < n + 1) return fail(TGX_ERR_INVALID, "%s: %llu offsets, room for %llu", who, (unsigned long long)(n + 1), (unsigned long long)cap);
+    if (!out_offs) return fail(TGX_ERR_INVALID, "%s: out_offs is NULL", who);
+    uint64_t k = 0;
+    for (uint64_t p = 0; p < N; p++)  // the compaction of the marked positions
+        if (marks[p]) out_offs[k++] = p;
+    out_offs[n] = N;
     return TGX_OK;
 }
 

@@ -303,6 +303,83 @@ def clean_rows(obj, grams, max_hits: int = 0):
     return (gram_hits(obj, grams) <= int(max_hits)).nonzero().reshape(-1)
 
 
+# ---- per-row text statistics and the line view: quality filters (csrc/textstat.hip) --------------------------------------
+
+class TextStats:
+    """What text_stats returns: `table`, [11, S] torch.int64 on the corpus's device, and a [S] view of it per statistic
+    (bytes, chars, newlines, lines, max_line, long_lines, alpha, digit, space, non_ascii, control: include/tgx.h);
+    `unit` ("char" or "byte") is what max_line and long_lines are counted in; `line_start` is the [N] uint8 mask of the
+    bytes at which a line begins, or None when it was not asked for."""
+
+    def __init__(self, table, unit: str, line_limit: int, line_start=None):
+        self.table, self.unit, self.line_limit, self.line_start = table, unit, int(line_limit), line_start
+        for k, name in enumerate(_lib.TEXTSTAT_NAMES):
+            setattr(self, name, table[k])
+
+    @property
+    def units(self):
+        """[S]: the rows' lengths in the unit (chars or bytes)."""
+        return self.chars if self.unit == "char" else self.bytes
+
+    @property
+    def mean_line(self):
+        """[S] float64: (units - newlines) / max(lines, 1), the mean length of a row's lines without their '\\n'."""
+        import torch
+        return (self.units - self.newlines).to(torch.float64) / self.lines.clamp(min=1).to(torch.float64)
+
+    @property
+    def alnum_frac(self):
+        """[S] float64: (alpha + digit) / max(chars, 1), the ASCII letters' and digits' share of the row's characters."""
+        import torch
+        return (self.alpha + self.digit).to(torch.float64) / self.chars.clamp(min=1).to(torch.float64)
+
+
+def text_stats(corpus: "_lib.NativeCorpus", unit: str = "char", line_limit: int = 1000, return_line_start: bool = False) -> TextStats:
+    """-> a TextStats of the corpus's rows, computed on its device and queued on torch's current stream: per row the
+    bytes, characters, '\\n's, lines, the longest line and the lines longer than line_limit (both in `unit`: "char", a
+    byte that is no UTF-8 continuation byte, or "byte"), and the ASCII letters, digits, white space, non-ASCII characters
+    and control bytes.  Only '\\n' ends a line, no line crosses a row's end, and a trailing '\\n' opens no empty last line.
+    With return_line_start also the [N] uint8 mask of the bytes at which a line begins."""
+    import torch
+    dev = _device_of(torch, corpus)
+    _lib.textstat_flags(unit)  # (raises on an unknown unit before anything is allocated)
+    S, N = corpus.num_samples, corpus.num_bytes
+    table = torch.empty((_lib.TEXTSTAT_N, S), dtype=torch.int64, device=dev)
+    marks = torch.empty((N,), dtype=torch.uint8, device=dev) if return_line_start else None
+    spare = torch.empty(1, dtype=torch.int64, device=dev)  # (no row: the pointer still says that the table is asked for)
+    corpus.text_stats((table if S else spare).data_ptr(), marks.data_ptr() if return_line_start and N else 0, line_limit, unit,
+                      stream=torch.cuda.current_stream(dev).cuda_stream)
+    return TextStats(table, unit, line_limit, marks)
+
+
+def quality_rows(corpus: "_lib.NativeCorpus", max_line: int = 1000, mean_line: float = 100.0, min_alnum: float = 0.25, unit: str = "char"):
+    """-> torch.int64 indices, ascending, of the rows that pass the line-length and alphanumeric filters of the Stack /
+    StarCoder recipe: what `select` takes to drop the others (of a corpus and, with the same indices, of its encoded
+    result).  A row is kept iff its longest line has at most max_line units, units - newlines <= mean_line · lines (its
+    mean line length is at most mean_line) and alpha + digit >= min_alnum · chars.  The comparisons are division-free
+    float64, so an empty row is kept.  Unlike the BigCode scripts, whose share is Python's Unicode str.isalnum over the
+    characters, the letters and digits counted here are ASCII only; text_stats gives `non_ascii` beside them for a caller
+    who wants to credit or discount the rest."""
+    import torch
+    s = text_stats(corpus, unit=unit, line_limit=max_line)
+    f64 = torch.float64
+    keep = s.max_line <= int(max_line)
+    keep &= (s.units - s.newlines).to(f64) <= float(mean_line) * s.lines.to(f64)
+    keep &= (s.alpha + s.digit).to(f64) >= float(min_alnum) * s.chars.to(f64)
+    return keep.nonzero().reshape(-1)
+
+
+def line_rows(corpus: "_lib.NativeCorpus"):
+    """-> (lines_corpus, line_row): a new resident corpus whose rows are the lines of `corpus`, in order, each with its
+    '\\n' if it has one, and [n_lines] torch.int64, the row of `corpus` that each line came from.  first_equal of the lines
+    plus torch gives the duplicate-line shares of the Gopher rules."""
+    import torch
+    dev = _device_of(torch, corpus)
+    lines = corpus.lines(stream=torch.cuda.current_stream(dev).cuda_stream)
+    counts = text_stats(corpus, unit="byte").lines
+    return lines, torch.repeat_interleave(torch.arange(corpus.num_samples, dtype=torch.int64, device=dev), counts)
+
+
 def _window_len(max_length, stride) -> tuple[int, int]:
     if max_length is None:
         raise TypeError("max_length is required for overflow windows")
