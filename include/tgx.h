@@ -805,6 +805,60 @@ tgx_status tgx_lines_host(const uint8_t *text, const uint64_t *offs, uint64_t n_
                           uint64_t *n_lines);
 int tgx_textstat_last_times(const char **names, float *ms, int cap);
 
+/* ---- repeated n-grams within a row: the Gopher repetition statistics (csrc/repeat.hip) ---------------------------------
+ * Which n-grams of row i occur earlier in row i: what the Gopher / MassiveText repetition rules (the share of a
+ * document taken by its most frequent 2- to 4-gram, the share covered by repeated 5- to 10-grams) need, for a result
+ * (token n-grams) or a corpus (byte n-grams) that stays in HBM.
+ *
+ * Definitions (csrc/repeat.h, used by the kernels and the host twin).  The source, the width w (1 <= w, w·eb <= 64), the
+ *   gram AT ELEMENT e, its validity (a row shorter than w owns no gram) and its key(e) are those of the shared n-grams
+ *   above.  The ROW KEY of a valid gram at element e of row i is
+ *     rkey(e) = mix(key(e) ^ ((i + 1) · 0x9E3779B97F4A7C15))        (mix: tgx_row_hash's 64-bit finaliser, a bijection)
+ *   so within a row two grams are EQUAL iff their keys are equal: probabilistic by the 64-bit key exactly as gram hits
+ *   are, and not verified against the elements; across rows equal grams get different row keys except by a 64-bit
+ *   collision.  An OCCURRENCE CLASS is the set of the valid grams of one row with one row key.  Its first member by
+ *   position is its FIRST occurrence, every other member is a REPEAT, and a class of two or more members is MULTI.
+ *
+ * tgx_result_repeat_stats_device(r, width, seed, flags, stream, d_stats, d_mask), tgx_corpus_repeat_stats_device(c, ...)
+ *   write d_stats, int64 [TGX_REPEAT_N, S], each statistic contiguous over the rows:
+ *     0 grams        valid grams of the row, max(0, n_i - w + 1)
+ *     1 repeated     valid grams that are repeats (grams - repeated = the distinct grams)
+ *     2 multi        valid grams that belong to a MULTI class (first occurrences included)
+ *     3 top          members of the row's largest class: 0 for a row without a gram, 1 when all its grams are distinct
+ *     4 covered      elements of the row that lie inside at least one REPEAT (each once, however many overlap it): what
+ *                    a pipeline that deletes repeats would delete
+ *     5 covered_all  elements that lie inside at least one member of a MULTI class (the Gopher paper's literal reading)
+ *   and d_mask, u8[n_elems]: bit 0 (TGX_REPEAT_MASK_REPEAT) where a repeat begins, bit 1 (TGX_REPEAT_MASK_MULTI) where a
+ *   member of a MULTI class begins, every other position 0, invalid positions included.  Every byte of both is written;
+ *   either may be NULL, not both.  Destinations are device memory of the source's device, checked before anything is
+ *   queued; host memory, a nonzero flag or a bad width: TGX_ERR_INVALID.  2^32-1 rows or more, or 2^32-1 elements or more
+ *   (positions are u32): TGX_ERR_UNSUPPORTED, before anything is queued.  Stream rule, corpus lock and pooled scratch as
+ *   tgx_corpus_gram_hits_device; S = 0 writes nothing.  The source is only read.
+ *   Pipeline: the rows' gram counts and their scan; a kernel that writes every valid gram's row key and position to its
+ *   slot; a stable radix sort of the pairs by key (so a class's first slot is its first occurrence); a kernel over the
+ *   sorted slots that writes the mask's byte of every valid position and maxes the length of every run onto `top`; a
+ *   kernel over the elements that turns the mask into the rows' sums and coverage.  One host visit reads the grams'
+ *   total, which sizes the sort.  Scratch: 24 bytes per gram, a byte per element without d_mask, 8 (S + 1) bytes and
+ *   rocPRIM's temporaries.
+ *
+ * Host twin, no device, the argument checks of tgx_gram_hits_host: tgx_repeat_stats_host(data, elem_bytes, offs, n_rows,
+ *   width, seed, stats, mask) goes through csrc/repeat.h: the same row keys, a stable sort, the run rule and the run's
+ *   end, and the kernel's chunks with the two-chunk coverage window and the store / add rule.
+ *
+ * tgx_repeat_last_times: device time per stage of the calling thread's last call, as tgx_gram_last_times (the names are
+ * listed without a call): repeat_keys_kernel (the counts' scan, the pre-sets and the kernel), repeat_sort,
+ * repeat_runs_kernel and repeat_cover_kernel (0 without d_stats). */
+#define TGX_REPEAT_N 6
+#define TGX_REPEAT_MASK_REPEAT 1u
+#define TGX_REPEAT_MASK_MULTI 2u
+tgx_status tgx_result_repeat_stats_device(const tgx_result *r, uint32_t width, uint64_t seed, uint32_t flags, void *stream,
+                                          int64_t *d_stats, uint8_t *d_mask);
+tgx_status tgx_corpus_repeat_stats_device(tgx_corpus *c, uint32_t width, uint64_t seed, uint32_t flags, void *stream,
+                                          int64_t *d_stats, uint8_t *d_mask);
+tgx_status tgx_repeat_stats_host(const void *data, uint32_t elem_bytes, const uint64_t *offs, uint64_t n_rows, uint32_t width,
+                                 uint64_t seed, int64_t *stats, uint8_t *mask);
+int tgx_repeat_last_times(const char **names, float *ms, int cap);
+
 /* ---- the front end on the device: a resident corpus split at special tokens, CRLF applied (csrc/front.hip) --------
  * What tgx_split_specials and tgx_pack_segments compute on host threads, for a corpus that is already in HBM (an upload,
  * or tgx_corpus_from_text of a decoded text), with the plan kept on the device for tgx_assemble_result_plan: a resident

@@ -210,6 +210,10 @@ SYMBOLS = {
     "tgx_text_stats_host": (_i, [_vp, _vp, _u64, _u64, _u32, _vp, _vp]),
     "tgx_lines_host": (_i, [_vp, _vp, _u64, _vp, _u64, C.POINTER(C.c_uint64)]),
     "tgx_textstat_last_times": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_float), _i]),
+    "tgx_result_repeat_stats_device": (_i, [_vp, _u32, _u64, _u32, _vp, _vp, _vp]),
+    "tgx_corpus_repeat_stats_device": (_i, [_vp, _u32, _u64, _u32, _vp, _vp, _vp]),
+    "tgx_repeat_stats_host": (_i, [_vp, _u32, _vp, _u64, _u32, _u64, _vp, _vp]),
+    "tgx_repeat_last_times": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_float), _i]),
 }
 
 
@@ -800,6 +804,43 @@ def textstat_last_times() -> dict[str, float]:
     names = (C.c_char_p * 8)()
     ms = (C.c_float * 8)()
     n = lib.tgx_textstat_last_times(names, ms, 8)
+    return {names[i].decode(): float(ms[i]) for i in range(n)}
+
+
+# ---- repeated n-grams within a row (include/tgx.h; csrc/repeat.hip, csrc/repeat.h) ----
+REPEAT_N = 6
+REPEAT_MASK_REPEAT = 1
+REPEAT_MASK_MULTI = 2
+REPEAT_NAMES = ("grams", "repeated", "multi", "top", "covered", "covered_all")
+GRAM_MAX_BYTES = 64
+
+
+def repeat_check_width(width: int, elem_bytes: int) -> int:
+    """width must be in 1 .. 64 / elem_bytes, as the device calls check it -> int(width)."""
+    width = int(width)
+    if width < 1 or width * elem_bytes > GRAM_MAX_BYTES:
+        raise ValueError(f"width {width} of {elem_bytes}-byte elements is not in 1 .. {GRAM_MAX_BYTES // elem_bytes}")
+    return width
+
+
+def repeat_stats_host(data: np.ndarray, offs: np.ndarray, width: int, seed: int = 0):
+    """Host twin of repeat_stats (tgx_repeat_stats_host: the row keys, a stable sort, the run rule and the kernel's chunks,
+    coverage window and store / add rule through the same header, no device) over data u8[N] or u32[T] and offsets
+    u64[S+1] in elements -> (stats int64[6, S], mask uint8[n_elems])."""
+    data, offs, n = _gram_source(data, offs)
+    stats = np.full((REPEAT_N, n), -7, np.int64)
+    mask = np.full(data.size, 7, np.uint8)
+    keep = np.zeros(1, np.int64), np.zeros(1, np.uint8)   # (never NULL: both outputs are asked for)
+    check(lib.tgx_repeat_stats_host(ptr(data) if data.size else None, data.dtype.itemsize, ptr(offs) if offs.size else None, n, int(width),
+                                    int(seed) & (2**64 - 1), ptr(stats if n else keep[0]), ptr(mask if mask.size else keep[1])))
+    return stats, mask
+
+
+def repeat_last_times() -> dict[str, float]:
+    """Device time in ms of each stage of the calling thread's last repeat_stats call (tgx_repeat_last_times)."""
+    names = (C.c_char_p * 8)()
+    ms = (C.c_float * 8)()
+    n = lib.tgx_repeat_last_times(names, ms, 8)
     return {names[i].decode(): float(ms[i]) for i in range(n)}
 
 
@@ -1444,6 +1485,12 @@ class NativeResult:
         check(lib.tgx_result_gramset_create(self._h, int(width), int(seed) & (2**64 - 1), 0, stream or None, C.byref(h)))
         return NativeGramSet(h)
 
+    def repeat_stats(self, width: int, seed: int = 0, d_stats: int = 0, d_mask: int = 0, *, stream: int = 0) -> None:
+        """Per row the repetition statistics of its n-grams of `width` ids, as int64[6, S], and per id whether a repeat
+        (bit 0) or a member of a class of two or more (bit 1) begins there, as u8[T], into caller-owned device memory
+        (either may be 0; tgx_result_repeat_stats_device)."""
+        check(lib.tgx_result_repeat_stats_device(self._h, int(width), int(seed) & (2**64 - 1), 0, stream or None, d_stats or None, d_mask or None))
+
     def gram_hits(self, grams: NativeGramSet, d_count: int = 0, d_mask: int = 0, *, stream: int = 0) -> None:
         """Per row the n-grams whose key is in `grams`, as int64[S], and per id whether the n-gram that begins there is
         one, as u8[T], into caller-owned device memory (raw integer pointers, either may be 0;
@@ -1660,6 +1707,12 @@ class NativeCorpus:
         is one, as u8[N], into caller-owned device memory (either may be 0; tgx_corpus_gram_hits_device).  This corpus is
         only read."""
         check(lib.tgx_corpus_gram_hits_device(self._h, grams._h, 0, stream or None, d_count or None, d_mask or None))
+
+    def repeat_stats(self, width: int, seed: int = 0, d_stats: int = 0, d_mask: int = 0, *, stream: int = 0) -> None:
+        """Per sample the repetition statistics of its n-grams of `width` bytes, as int64[6, S], and per byte whether a
+        repeat (bit 0) or a member of a class of two or more (bit 1) begins there, as u8[N], into caller-owned device
+        memory (either may be 0; tgx_corpus_repeat_stats_device).  This corpus is only read."""
+        check(lib.tgx_corpus_repeat_stats_device(self._h, int(width), int(seed) & (2**64 - 1), 0, stream or None, d_stats or None, d_mask or None))
 
     def text_stats(self, d_stats: int = 0, d_line_start: int = 0, line_limit: int = 1000, unit: str = "char", *, stream: int = 0) -> None:
         """Per sample the eleven statistics of include/tgx.h as int64[11, S] (TEXTSTAT_NAMES; lengths in `unit`, "char" or

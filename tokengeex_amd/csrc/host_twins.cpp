@@ -1,8 +1,8 @@
 // The *_host twins of the result-side device entry points (include/tgx.h): tgx_layout_pad_host, tgx_layout_pack_host,
-// tgx_layout_windows_host, tgx_assemble_host, tgx_fim_host, tgx_select_host, tgx_select_text_host, tgx_shuffled_rows_host, tgx_first_equal_host, tgx_minhash_host, tgx_minhash_bands_host, tgx_minhash_near_first_host, tgx_gram_keys_host, tgx_gram_hits_host, tgx_gram_contains_host, tgx_text_stats_host, tgx_lines_host, tgx_decode_rows_host, tgx_spans_host, tgx_window_spans_host, tgx_front_host,
+// tgx_layout_windows_host, tgx_assemble_host, tgx_fim_host, tgx_select_host, tgx_select_text_host, tgx_shuffled_rows_host, tgx_first_equal_host, tgx_minhash_host, tgx_minhash_bands_host, tgx_minhash_near_first_host, tgx_gram_keys_host, tgx_gram_hits_host, tgx_gram_contains_host, tgx_repeat_stats_host, tgx_text_stats_host, tgx_lines_host, tgx_decode_rows_host, tgx_spans_host, tgx_window_spans_host, tgx_front_host,
 // tgx_normalize_host and tgx_lattice_stats_host, and the
 // argument checks they share with the device entry points of tgx_api.cpp.  A twin goes through the same index arithmetic as its kernels (layout.h, assemble.h,
-// fim.h, select.h, dedup.h, minhash.h, gram.h, textstat.h, decode.h, spans.h, front.h, norm.h) on host memory.  Nothing in this file calls a HIP function, so it builds and runs without the
+// fim.h, select.h, dedup.h, minhash.h, gram.h, repeat.h, textstat.h, decode.h, spans.h, front.h, norm.h) on host memory.  Nothing in this file calls a HIP function, so it builds and runs without the
 // handles, the pool or a device.
 #define TGX_HOST_ONLY  // tile_fill.h: the host loop, no kernel side
 #include <algorithm>
@@ -22,6 +22,7 @@
 #include "layout.h"
 #include "minhash.h"
 #include "norm.h"
+#include "repeat.h"
 #include "select.h"
 #include "spans.h"
 #include "textstat.h"
@@ -979,6 +980,100 @@ tgx_status tgx_gram_contains_host(const uint64_t* keys, uint64_t n_keys, const u
     if (st != TGX_OK) return st;
     if (n_probes && (!probes || !out)) return fail(TGX_ERR_INVALID, "%s: %s is NULL", who, probes ? "out" : "probes");
     for (uint64_t p = 0; p < n_probes; p++) out[p] = tgx::gram_contains(sorted.data(), dir.data(), bits, probes[p]) ? 1 : 0;
+    return TGX_OK;
+}
+
+// ---- repeated n-grams within a row ------------------------------------------------------------
+
+tgx_status tgx_repeat_stats_host(const void* data, uint32_t elem_bytes, const uint64_t* offs, uint64_t n_rows, uint32_t width, uint64_t seed,
+                                 int64_t* stats, uint8_t* mask) {
+    const char* who = "tgx_repeat_stats_host";
+    const tgx_status st = gram_check_source_host(who, data, elem_bytes, offs, n_rows, width);
+    if (st != TGX_OK) return st;
+    if (!stats && !mask) return fail(TGX_ERR_INVALID, "%s: stats and mask are both NULL", who);
+    const uint64_t S = n_rows;
+    if (S == 0) return TGX_OK;
+    const uint64_t N = offs[S];
+    if (N > tgx::kRepeatMaxElems) return fail(TGX_ERR_UNSUPPORTED, "%s: 2^32-1 elements or more", who);
+    // the pre-sets
+    std::vector<uint8_t> own_flag(mask ? 0 : N);
+    uint8_t* flag = mask ? mask : own_flag.data();
+    std::fill(flag, flag + N, 0);
+    std::vector<uint64_t> g_offs(S + 1, 0);
+    for (uint64_t k = 0; k < S; k++) {
+        const uint64_t grams = tgx::gram_row_count(offs, S, width, k);
+        g_offs[k + 1] = g_offs[k] + grams;
+        if (!stats) continue;
+        for (uint32_t q = 0; q < tgx::kRepeatN; q++) stats[q * S + k] = 0;
+        stats[tgx::kRpGrams * S + k] = (int64_t)grams;
+        stats[tgx::kRpTop * S + k] = (int64_t)tgx::repeat_top_preset(grams);
+    }
+    // every valid gram's row key and position to its slot, as repeat_keys_kernel; then the stable sort by key
+    const uint64_t G = g_offs[S];
+    std::vector<uint64_t> keys_a(G), keys(G);
+    std::vector<uint32_t> pos_a(G), pos(G), order(G);
+    gram_walk_host(static_cast<const uint8_t*>(data), elem_bytes, offs, S, width, seed, [&](uint64_t, uint64_t e, uint64_t i, bool valid, uint64_t key) {
+        if (!valid) return;
+        const uint64_t slot = g_offs[i] + (e - offs[i]);
+        keys_a[slot] = tgx::repeat_row_key(key, i);
+        pos_a[slot] = (uint32_t)e;
+    });
+    for (uint64_t t = 0; t < G; t++) order[t] = (uint32_t)t;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return keys_a[a] < keys_a[b]; });
+    for (uint64_t t = 0; t < G; t++) {
+        keys[t] = keys_a[order[t]];
+        pos[t] = pos_a[order[t]];
+    }
+    // the runs, as repeat_runs_kernel
+    for (uint64_t t = 0; t < G; t++) {
+        const bool head = t == 0 || keys[t - 1] != keys[t], next_same = t + 1 < G && keys[t + 1] == keys[t];
+        flag[pos[t]] = tgx::repeat_flag(head, next_same);
+        if (stats && head && next_same) {
+            const int64_t len = (int64_t)(tgx::repeat_run_end(keys.data(), G, t) - t);
+            int64_t& top = stats[tgx::kRpTop * S + tgx::pack_find_row(offs, 0, 0, S - 1, pos[t])];
+            top = std::max(top, len);
+        }
+    }
+    if (!stats) return TGX_OK;
+    // the cover and the row sums, as repeat_cover_kernel: its chunks, the window of two chunks, the store / add rule
+    uint64_t hi = 0;
+    for (uint64_t c0 = 0; c0 < N; c0 += tgx::kGramChunk) {
+        const uint64_t c_last = tgx::tile_last(c0, tgx::kGramChunk, N);
+        const uint64_t lo = tgx::dedup_find_from(offs, hi, S - 1, c0);
+        hi = tgx::dedup_find_from(offs, lo, S - 1, c_last);
+        const uint32_t n_in = (uint32_t)(c_last - c0) + 1;
+        uint64_t row[tgx::kGramChunk], ballots[4] = {0, 0, 0, 0}, rep_b = 0, mul_b = 0;
+        for (uint32_t l = 0; l < tgx::kGramChunk; l++) {
+            if (l < n_in) {
+                row[l] = tgx::pack_find_row(offs, 0, lo, hi, c0 + l);
+                if (flag[c0 + l] & tgx::kRepeatBitRepeat) ballots[0] |= 1ull << l;
+                if (flag[c0 + l] & tgx::kRepeatBitMulti) ballots[1] |= 1ull << l;
+            }
+            if (c0) {  // (the chunk before is whole)
+                if (flag[c0 - tgx::kGramChunk + l] & tgx::kRepeatBitRepeat) rep_b |= 1ull << l;
+                if (flag[c0 - tgx::kGramChunk + l] & tgx::kRepeatBitMulti) mul_b |= 1ull << l;
+            }
+        }
+        for (uint32_t l = 0; l < n_in; l++) {
+            if (tgx::repeat_covered(rep_b, ballots[0], l, c0 + l, offs[row[l]], width)) ballots[2] |= 1ull << l;
+            if (tgx::repeat_covered(mul_b, ballots[1], l, c0 + l, offs[row[l]], width)) ballots[3] |= 1ull << l;
+        }
+        const uint32_t which[4] = {tgx::kRpRepeated, tgx::kRpMulti, tgx::kRpCovered, tgx::kRpCoveredAll};
+        for (uint32_t a = 0; a < n_in;) {  // the stretch [a, b] of one row
+            uint32_t b = a;
+            while (b + 1 < n_in && row[b + 1] == row[a]) b++;
+            const uint64_t i = row[a], stretch = ((b >= 63 ? 0ull : (1ull << (b + 1))) - 1) & ~((1ull << a) - 1);  // lanes [a, b]
+            const bool inside = tgx::gram_row_inside(offs, i, c0);
+            for (uint32_t q = 0; q < 4; q++) {
+                const uint64_t v = (uint64_t)__builtin_popcountll(ballots[q] & stretch);
+                if (inside)
+                    stats[which[q] * S + i] = (int64_t)v;
+                else if (tgx::gram_adds(v))
+                    stats[which[q] * S + i] += (int64_t)v;
+            }
+            a = b + 1;
+        }
+    }
     return TGX_OK;
 }
 

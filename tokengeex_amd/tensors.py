@@ -380,6 +380,159 @@ def line_rows(corpus: "_lib.NativeCorpus"):
     return lines, torch.repeat_interleave(torch.arange(corpus.num_samples, dtype=torch.int64, device=dev), counts)
 
 
+# ---- repeated n-grams within a row: the Gopher repetition filters (csrc/repeat.hip) ---------------------------------------
+
+GOPHER_TOP = ((2, .20), (3, .18), (4, .16))
+GOPHER_DUP = ((5, .15), (6, .14), (7, .13), (8, .12), (9, .11), (10, .10))
+
+
+class RepeatStats:
+    """What repeat_stats returns: `table`, [6, S] torch.int64 on the source's device, and a [S] view of it per statistic
+    (grams, repeated, multi, top, covered, covered_all: include/tgx.h); `elems`, [S] torch.int64, the rows' lengths in
+    elements (ids or bytes); `width`; `mask`, the [n_elems] uint8 tensor (bit 0: a repeat begins here, bit 1: a member
+    of a class of two or more begins here), or None when it was not asked for."""
+
+    def __init__(self, table, elems, width: int, mask=None):
+        self.table, self.elems, self.width, self.mask = table, elems, int(width), mask
+        for k, name in enumerate(_lib.REPEAT_NAMES):
+            setattr(self, name, table[k])
+
+    def _per_elem(self, count):
+        import torch
+        return count.to(torch.float64) / self.elems.clamp(min=1).to(torch.float64)
+
+    @property
+    def repeated_frac(self):
+        """[S] float64: repeated / max(grams, 1), the share of the row's n-grams that occurred earlier in the row."""
+        import torch
+        return self.repeated.to(torch.float64) / self.grams.clamp(min=1).to(torch.float64)
+
+    @property
+    def covered_frac(self):
+        """[S] float64: covered / max(elems, 1), the share of the row's elements inside a repeated n-gram."""
+        return self._per_elem(self.covered)
+
+    @property
+    def covered_all_frac(self):
+        """[S] float64: covered_all / max(elems, 1), first occurrences of the repeated n-grams included."""
+        return self._per_elem(self.covered_all)
+
+    @property
+    def top_frac(self):
+        """[S] float64: top · width / max(elems, 1) where top >= 2, else 0: the share of the row taken by the
+        occurrences of its most frequent n-gram (overlaps counted as often as they occur, as Gopher counts them)."""
+        import torch
+        frac = self._per_elem(self.top * self.width)
+        return torch.where(self.top >= 2, frac, torch.zeros_like(frac))
+
+
+def _elem_bytes(obj) -> int:
+    return 4 if isinstance(obj, _lib.NativeResult) else 1
+
+
+def _row_elems(obj):
+    return row_lengths(obj) if isinstance(obj, _lib.NativeResult) else text_stats(obj, unit="byte").bytes
+
+
+def repeat_stats(obj, width: int, seed: int = 0, return_mask: bool = False, *, elems=None) -> RepeatStats:
+    """-> a RepeatStats of obj's rows (a NativeResult: n-grams of `width` ids; a NativeCorpus: of `width` bytes),
+    computed on its device and queued on torch's current stream: per row the n-grams, those that occurred earlier in
+    the same row, those that occur twice or more, the occurrences of the most frequent one, and the elements covered
+    by repeats.  Equality is by 64-bit key, so probabilistic in the sense of gram_hits.  A row shorter than `width`
+    owns no n-gram.  elems: the rows' lengths if the caller has them (else they are computed)."""
+    import torch
+    dev = _device_of(torch, obj)
+    width = _lib.repeat_check_width(width, _elem_bytes(obj))  # (raises before anything is allocated)
+    S = obj.num_samples
+    n_elems = obj.num_tokens if isinstance(obj, _lib.NativeResult) else obj.num_bytes
+    table = torch.empty((_lib.REPEAT_N, S), dtype=torch.int64, device=dev)
+    mask = torch.empty((n_elems,), dtype=torch.uint8, device=dev) if return_mask else None
+    spare = torch.empty(1, dtype=torch.int64, device=dev)  # (no row: the pointer still says that the table is asked for)
+    obj.repeat_stats(width, seed, (table if S else spare).data_ptr(), mask.data_ptr() if return_mask and n_elems else 0,
+                     stream=torch.cuda.current_stream(dev).cuda_stream)
+    return RepeatStats(table, _row_elems(obj) if elems is None else elems, width, mask)
+
+
+def repetition_keep(stats, top=GOPHER_TOP, dup=GOPHER_DUP, literal: bool = False):
+    """The keep rule of repetition_rows alone, on tensors of any device: stats maps a width to its RepeatStats ->
+    [S] bool, False for a row with top_frac > limit for some (w, limit) of `top`, or with covered_frac (literal:
+    covered_all_frac) > limit for some (w, limit) of `dup`."""
+    keep = None
+    for w, limit in top:
+        ok = ~(stats[int(w)].top_frac > float(limit))
+        keep = ok if keep is None else keep & ok
+    for w, limit in dup:
+        s = stats[int(w)]
+        ok = ~((s.covered_all_frac if literal else s.covered_frac) > float(limit))
+        keep = ok if keep is None else keep & ok
+    return keep
+
+
+def repetition_rows(obj, top=GOPHER_TOP, dup=GOPHER_DUP, literal: bool = False, seed: int = 0):
+    """-> torch.int64 indices, ascending, of the rows that pass the n-gram repetition rules of Gopher / MassiveText: what
+    `select` takes to drop the others (of a result and, with the same indices, of its corpus).  A row is dropped iff
+    top_frac > limit for some (w, limit) of `top` (the share taken by its most frequent w-gram), or covered_frac > limit
+    for some (w, limit) of `dup` (the share covered by repeated w-grams; with literal=True covered_all_frac, which
+    counts the first occurrences too, the paper's literal reading, where the default is what a pipeline that deletes
+    the repeats would delete).  One repeat_stats call per distinct width.  The defaults are Gopher's numbers; Gopher
+    counts word n-grams and characters where this counts elements of the source (token ids or bytes), so the
+    thresholds are the caller's to tune.  A width that the source's element size cannot take raises before anything is
+    queued."""
+    import torch
+    top, dup = tuple(top), tuple(dup)
+    widths = sorted({int(w) for w, _ in top + dup})
+    for w in widths:
+        _lib.repeat_check_width(w, _elem_bytes(obj))
+    if not widths:
+        return torch.arange(obj.num_samples, dtype=torch.int64, device=_device_of(torch, obj))
+    elems = _row_elems(obj)
+    stats = {w: repeat_stats(obj, w, seed, elems=elems) for w in widths}
+    return repetition_keep(stats, top, dup, literal).nonzero().reshape(-1)
+
+
+def line_dup_counts(line_row, cls, line_bytes, n_rows: int):
+    """The duplicate-line rule alone, on tensors of any device: line_row [n_lines] int64 (ascending: the row of every
+    line), cls [n_lines] int64 (first_equal of the lines), line_bytes [n_lines] int64 -> (dup_lines, dup_bytes), both
+    [n_rows] int64.  A line is a duplicate iff it is not the first of its row with its content: the lines are sorted
+    stably by line_row · n_lines + cls, and a duplicate is one whose predecessor has the same key."""
+    import torch
+    n_lines = line_row.shape[0]
+    key = line_row * n_lines + cls
+    skey, order = torch.sort(key, stable=True)
+    is_dup = torch.zeros(n_lines, dtype=torch.int64, device=key.device)
+    if n_lines > 1:
+        is_dup[order[1:]] = (skey[1:] == skey[:-1]).to(torch.int64)
+    dup_lines = torch.zeros(int(n_rows), dtype=torch.int64, device=key.device).scatter_add_(0, line_row, is_dup)
+    dup_bytes = torch.zeros(int(n_rows), dtype=torch.int64, device=key.device).scatter_add_(0, line_row, is_dup * line_bytes)
+    return dup_lines, dup_bytes
+
+
+def line_dup_keep(dup_lines, dup_bytes, n_lines, n_bytes, max_dup_lines: float, max_dup_bytes: float):
+    """[S] bool: dup_lines <= max_dup_lines · lines and dup_bytes <= max_dup_bytes · bytes, division-free in float64."""
+    import torch
+    f64 = torch.float64
+    return (dup_lines.to(f64) <= float(max_dup_lines) * n_lines.to(f64)) & (dup_bytes.to(f64) <= float(max_dup_bytes) * n_bytes.to(f64))
+
+
+def line_repetition_rows(corpus: "_lib.NativeCorpus", max_dup_lines: float = 0.30, max_dup_bytes: float = 0.20, return_stats: bool = False):
+    """-> torch.int64 indices, ascending, of the rows that pass the duplicate-line rules of Gopher / MassiveText: what
+    `select` takes to drop the others.  A line (line_rows: '\\n' ends it and belongs to it, no line crosses a row's end)
+    is a duplicate iff an earlier line of the same row has exactly its bytes; a row is kept iff its duplicate lines are
+    at most max_dup_lines of its lines and their bytes at most max_dup_bytes of its bytes.  The comparisons are
+    division-free, so an empty row is kept.  A composition of line_rows, first_equal and torch, no kernel of its own.
+    The defaults are Gopher's numbers, where the byte share is a character share.  With return_stats also (dup_lines,
+    dup_bytes, lines, bytes), each [S] torch.int64."""
+    import torch
+    S = corpus.num_samples
+    lines, line_row = line_rows(corpus)
+    cls = first_equal(lines)
+    line_bytes = text_stats(lines, unit="byte").bytes
+    dup_lines, dup_bytes = line_dup_counts(line_row, cls, line_bytes, S)
+    s = text_stats(corpus, unit="byte")
+    rows = line_dup_keep(dup_lines, dup_bytes, s.lines, s.bytes, max_dup_lines, max_dup_bytes).nonzero().reshape(-1)
+    return (rows, (dup_lines, dup_bytes, s.lines, s.bytes)) if return_stats else rows
+
+
 def _window_len(max_length, stride) -> tuple[int, int]:
     if max_length is None:
         raise TypeError("max_length is required for overflow windows")
