@@ -1282,6 +1282,11 @@ uint32_t tgx_last_encode_lean_items(const tgx_model *m);
  * scratch and compact_kernel (dropout, tokens longer than 16 bytes, samples sent to encode6_kernel, a sample of 2^24
  * bytes or more, a build of encode5_kernel that does not count, TGX_IDS_IN_PLACE=0, or another encode path). */
 int tgx_last_encode_ids_in_place(const tgx_model *m);
+/* 1 when the last encode pass's encode5_kernel was a top-table build (a self-check: results do not depend on it): a
+ * walk's first two trie levels came from one table indexed by the first two text bytes, and the block's LDS held no copy
+ * of the root's records — room for more hot score values, or for one more wave.  0: the kernel kept its root copy
+ * (dropout, tokens longer than 16 bytes, TGX_E5_TOP=0), was not launched, or the pass took another encode path. */
+int tgx_last_encode_top_table(const tgx_model *m);
 
 /* ---- dropout ---------------------------------------------------------------
  * The reference draws rand::random::<f64>() from an unseeded thread RNG

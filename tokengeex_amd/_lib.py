@@ -101,6 +101,7 @@ SYMBOLS = {
     "tgx_last_encode_hot_values": (_u32, [_vp]),
     "tgx_last_encode_lean_items": (_u32, [_vp]),
     "tgx_last_encode_ids_in_place": (_i, [_vp]),
+    "tgx_last_encode_top_table": (_i, [_vp]),
     "tgx_last_encode_long_samples": (_u64, [_vp]),
     "tgx_last_estep_pieces": (_u64, [_vp]),
     "tgx_last_estep_redo": (_u64, [_vp]),
@@ -2076,6 +2077,12 @@ class NativeModel:
         """Whether the last encode pass wrote its ids in place: token counts from encode5_kernel's relaxation, no scratch
         of 4 bytes per text byte, no compact_kernel (a self-check: results do not depend on it)."""
         return bool(lib.tgx_last_encode_ids_in_place(self._h))
+
+    def last_encode_top_table(self) -> bool:
+        """Whether the last pass's encode5_kernel was a top-table build: a walk's first two trie levels from one table
+        indexed by the first two text bytes, no copy of the root's records in LDS (a self-check: results do not depend
+        on it)."""
+        return bool(lib.tgx_last_encode_top_table(self._h))
 
     def last_encode_long_samples(self) -> int:
         return lib.tgx_last_encode_long_samples(self._h)

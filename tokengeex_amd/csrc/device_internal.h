@@ -164,7 +164,9 @@ struct tgx_model {
     void* d_tokhash = nullptr;
     // encode5_kernel: 8-byte label-checked records + table of distinct score values (trie_build.h: Trie8)
     void* d_trie8 = nullptr;
-    double* d_values = nullptr;        // f64[n_values + 1]: -inf, then the distinct score values by rank (trie_build.h: Trie8)
+    void* d_top8 = nullptr;            // the top table over d_trie8 (top_table.h): written and re-ranked with it
+    bool last_encode_top = false;      // the last encode5 launch ran a TOP build (no root copy in LDS)
+    double* d_values = nullptr;       // f64[n_values + 1]: -inf, then the distinct score values by rank (trie_build.h: Trie8)
     std::vector<double> value_coverage;  // [k]: expected share of the matches whose value has rank <= k
     uint32_t n_values = 0, root_base8 = 0;
     uint32_t last_n_hot = 0;           // values in the LDS copy of the last encode5 launch

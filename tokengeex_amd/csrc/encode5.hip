@@ -28,6 +28,7 @@
 #include <type_traits>
 
 #include "device_common.h"
+#include "encode5_layout.h"
 #include "kernels.h"
 
 namespace tgx {
@@ -39,8 +40,7 @@ namespace tgx {
 // (lane constant) | ((l * 32 + d * 32) & 0x1E0): the alignment makes it one add and one and-or.  (A layout with
 // 32 columns and no wrap-around needs no address arithmetic at all but twice the LDS, and LDS is what limits the
 // waves per CU here.)
-constexpr uint32_t kE5RowStride = 512;
-constexpr uint32_t kE5GroupBytes = 4 * kE5RowStride;  // 2048
+// (kE5RowStride = 512, kE5GroupBytes = 2048: encode5_layout.h)
 
 template <int PPL>
 struct WalkCtx {
@@ -110,9 +110,13 @@ struct Res5 {
 // walks than that: the gathers are issued where they are and the trip goes on uncompacted.  PK (packed walks): wlane
 // holds the walk's own column bits (l * 32) as well, the entry of depth d is at bfi(0x1E0, wlane + 32 d, wlane).
 // DESIGN.md section R5.
-template <bool DROPOUT, bool LONG, bool RES, int PPL, int D, bool SKIP = false, int CK = 0, bool PK = false>
+// T0 (the TOP builds of encode5_kernel, at D == 1 only): rec[g] is the walk's top-table entry (top_table.h) — the record of
+// depth 1 with the rank of the 1-byte token in the upper half of its second word — and alive[g] says whether the walk
+// has a byte at all: the level first does what is left of depth 0 (that rank into column 0).
+template <bool DROPOUT, bool LONG, bool RES, int PPL, int D, bool SKIP = false, int CK = 0, bool PK = false, bool T0 = false>
 struct Walk5 {
     static_assert(CK == 0 || (!DROPOUT && !LONG && !RES && PPL >= 2 && D < CK && CK < 16), "compaction: hot and COLD builds of two to four walks per lane");
+    static_assert(!T0 || (D == 1 && !DROPOUT && !LONG && !RES && !PK), "top-table entries: the first level of the hot and COLD builds");
     // rec[g], c[g]: record and text byte of depth D of walk g (the load may still be in flight)
     static __device__ __forceinline__ void run(const WalkCtx<PPL>& W, Res5& R, const uint32_t (&bytes)[PPL][4], const uint32_t (&maxd)[PPL],
                                                const uint32_t (&pg)[PPL], const uint32_t (&wlane)[PPL], bool (&alive)[PPL],
@@ -125,6 +129,11 @@ struct Walk5 {
 #pragma unroll
         for (int g = 0; g < PPL; ++g) {
             asm("" : "+v"(rec[g].x), "+v"(rec[g].y));  // two 32-bit words (else the 64-bit load is picked apart with 64-bit ops)
+            if constexpr (T0) {
+                const uint32_t rank0 = rec[g].y >> 16;  // the 1-byte token: taken whatever the second byte is (the next sample's, padding)
+                if (alive[g] && rank0 != 0u) lds_st<uint16_t>(wlane[g] | W.l32, (uint16_t)rank0);
+                alive[g] = alive[g] && 1u < maxd[g];
+            }
             alive[g] = alive[g] && ((rec[g].x >> 24) == c[g]);
             const uint32_t rank = rec[g].y & 0xFFFFu;  // 0: no token ends here
             bool term = alive[g] && rank != 0u;
@@ -340,8 +349,7 @@ __device__ __forceinline__ double e5_score_one(uint32_t tab, __amdgpu_buffer_rsr
 // a long candidate is applied out of order and replaces an equal score iff its token is longer; `far` wins ties
 // against near candidates at a restart (everything in `far` starts earlier than any near start of that position).
 // A list that fills up puts the wave's samples on P.redo_list: the host redoes exactly those with encode2_kernel.
-constexpr uint32_t kE5LongCap = 62;                         // list entries per wave and iteration
-constexpr uint32_t kE5LongBytes = 8u + kE5LongCap * 4u;     // {count, pad} + entries {lane | group << 6 | depth << 8 | rank << 16}
+// (kE5LongCap = 62 list entries per wave and iteration, kE5LongBytes: encode5_layout.h)
 constexpr uint32_t kFarCode = 0x80u;                        // winner code of a long token: kFarCode | (length - 1)
 
 __device__ __forceinline__ uint32_t e5_winner_len_m1(uint32_t code, uint32_t l) {  // near winners: the step that pushed them
@@ -412,10 +420,13 @@ __device__ __forceinline__ void e5_long_tail(__amdgpu_buffer_rsrc_t trie, const 
 // LN: the lean relaxation (device_common.h: kLeanStep | kLeanBcast | kLeanFetch; 0: the kernel as it was)
 // CNT: the relaxation counts tokens (device_common.h: relax5_step) and the lane that writes a sample's
 // status writes its token count to P.counts beside it, so that the trace can write ids in place; false: the kernel as it was
-template <bool DROPOUT, bool COLD, int PPL, bool LONG, int CK = 0, int LN = 0, bool CNT = false>
+// TOP: levels 0 and 1 of a walk come from one gather of the top table (top_table.h: Q.top, indexed by the first two text
+// bytes) — the block keeps no copy of the root's records, and its LDS has no room for one (encode5_layout.h; DESIGN.md
+// section R9); false: the kernel as it was
+template <bool DROPOUT, bool COLD, int PPL, bool LONG, int CK = 0, int LN = 0, bool CNT = false, bool TOP = false>
 __global__ __launch_bounds__(1024, (PPL == 1 ? 8 : (PPL == 2 ? 6 : (PPL == 3 ? 4 : 1)))) void encode5_kernel(EncodeParams P, Encode5Params Q) {
     static_assert(!LONG || PPL == 4, "the long-token build runs four positions per lane");
-    static_assert((LN == 0 && !CNT) || (!LONG && !DROPOUT), "the long-token and dropout builds keep the kernel as it was");
+    static_assert((LN == 0 && !CNT && !TOP) || (!LONG && !DROPOUT), "the long-token and dropout builds keep the kernel as it was");
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr uint32_t LM = LONG ? 32 : 16;
     constexpr uint32_t SPAN = 16u * PPL;
@@ -424,8 +435,9 @@ __global__ __launch_bounds__(1024, (PPL == 1 ? 8 : (PPL == 2 ? 6 : (PPL == 3 ? 4
     const uint32_t wave = threadIdx.x >> 6;
     const uint2* __restrict__ trie = reinterpret_cast<const uint2*>(Q.trie8);
     const __amdgpu_buffer_rsrc_t trie_b = make_rsrc(Q.trie8, Q.trie_bytes);
+    const __amdgpu_buffer_rsrc_t top_b = make_rsrc(TOP ? Q.top : nullptr, TOP ? kE5TopBytes : 0u);  // (TOP builds only)
     const uint32_t lds0 = (uint32_t)reinterpret_cast<uintptr_t>(smem);  // LDS byte offset of the dynamic LDS (0 here)
-    // ---- LDS: [0, 8 (n_hot + 1)) score table (entry 0 = -inf: rank 0 = "no token") | root records | match indices
+    // ---- LDS: [0, 8 (n_hot + 1)) score table (entry 0 = -inf: rank 0 = "no token") | root records (not TOP) | match indices
     double* const score_tab = reinterpret_cast<double*>(smem);
     const uint32_t hot_bytes = 8u * (Q.n_hot + 1u);
     const __amdgpu_buffer_rsrc_t values = make_rsrc(reinterpret_cast<const unsigned char*>(Q.values) + hot_bytes, 8u * (Q.n_values - Q.n_hot));  // ranks beyond the LDS copy
@@ -433,8 +445,10 @@ __global__ __launch_bounds__(1024, (PPL == 1 ? 8 : (PPL == 2 ? 6 : (PPL == 3 ? 4
     unsigned char* wbase = smem + Q.idx_off + (size_t)wave * (PPL * kE5GroupBytes);
     {
         for (uint32_t i = threadIdx.x; i <= Q.n_hot; i += blockDim.x) score_tab[i] = Q.values[i];
-        uint2* rw = reinterpret_cast<uint2*>(smem + Q.root_off);
-        for (uint32_t i = threadIdx.x; i < 256u; i += blockDim.x) rw[i] = trie[(Q.root_base & ~255u) + i];
+        if constexpr (!TOP) {
+            uint2* rw = reinterpret_cast<uint2*>(smem + Q.root_off);
+            for (uint32_t i = threadIdx.x; i < 256u; i += blockDim.x) rw[i] = trie[(Q.root_base & ~255u) + i];
+        }
         if (Q.started && threadIdx.x == 0u) __hip_atomic_fetch_add(Q.started, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         __syncthreads();
     }
@@ -518,6 +532,14 @@ __global__ __launch_bounds__(1024, (PPL == 1 ? 8 : (PPL == 2 ? 6 : (PPL == 3 ? 4
         for (int g = 0; g < PPL; ++g)
 #pragma unroll
             for (int q = 0; q < 4; ++q) bytes[g][q] = __builtin_amdgcn_alignbyte(w[4 * g + q + 1], w[4 * g + q], sh);
+        // TOP: every walk's first record — the top table's entry of its first two text bytes.  The address needs the text
+        // alone, so the gathers are under way while the index buffers are reset.  (Every lane, whatever its walk has left:
+        // any two bytes index inside the table, the text is padded, and a walk without bytes ignores what comes back.)
+        uint2 top_rec[TOP ? PPL : 1];
+        if constexpr (TOP) {
+#pragma unroll
+            for (int g = 0; g < PPL; ++g) top_rec[g] = buf_ld8(top_b, word_times8<0>(bytes[g][0]));
+        }
 
         // every (start, len) starts as "no token": index 0 = the table's -inf entry
 #pragma unroll
@@ -543,8 +565,10 @@ __global__ __launch_bounds__(1024, (PPL == 1 ? 8 : (PPL == 2 ? 6 : (PPL == 3 ? 4
             maxd[g] = rem < LM ? rem : LM;
             alive[g] = maxd[g] > 0 && !(P.flags & 1u);
             wlane[g] = wr_off + g * kE5GroupBytes;
-            c[g] = bytes[g][0] & 0xFFu;
-            rec[g] = rootc[(Q.root_base ^ c[g]) & 255u];
+            if constexpr (!TOP) {
+                c[g] = bytes[g][0] & 0xFFu;
+                rec[g] = rootc[(Q.root_base ^ c[g]) & 255u];
+            }
         }
         {
             // (opaque per trip: as a loop invariant the sixteen column offsets of a lane get hoisted out of the
@@ -553,7 +577,21 @@ __global__ __launch_bounds__(1024, (PPL == 1 ? 8 : (PPL == 2 ? 6 : (PPL == 3 ? 4
             asm volatile("" : "+v"(l32));
             WalkCtx<PPL> W{trie_b, s, l32, P.dropout, P.seed};
             Res5 no_res{};
-            Walk5<DROPOUT, LONG, false, PPL, 0, COLD && PPL < 4, CK>::run(W, no_res, bytes, maxd, pg, wlane, alive, rec, c);  // (four positions per lane: the geometry of batches bound by their chains, where the stagger is worth more — 512 MiB 9.67 -> 10.11 ms with SKIP)
+            if constexpr (TOP) {
+                // level 0 is the 1-byte token's rank in the upper half of the entry's second word (a walk with a byte left
+                // takes it, whatever the second byte is: the next sample's first, or padding); the entry itself is the
+                // record of level 1, label and all, so the levels from 1 on are the ordinary ones
+                // (Walk5's T0: level 0 is done walk by walk at the head of level 1, so that the wait for one walk's entry
+                // leaves the younger gathers outstanding)
+#pragma unroll
+                for (int g = 0; g < PPL; ++g) {
+                    rec[g] = top_rec[g];
+                    c[g] = (bytes[g][0] >> 8) & 0xFFu;
+                }
+                Walk5<DROPOUT, LONG, false, PPL, 1, COLD && PPL < 4, CK, false, true>::run(W, no_res, bytes, maxd, pg, wlane, alive, rec, c);
+            } else {
+                Walk5<DROPOUT, LONG, false, PPL, 0, COLD && PPL < 4, CK>::run(W, no_res, bytes, maxd, pg, wlane, alive, rec, c);  // (four positions per lane: the geometry of batches bound by their chains, where the stagger is worth more — 512 MiB 9.67 -> 10.11 ms with SKIP)
+            }
         }
         if (LONG) {
 #pragma unroll
@@ -1404,9 +1442,12 @@ bool encode5_counts(bool dropout, bool cold, int ppl, bool long_tokens) {
     if (dropout || long_tokens) return false;
     return cold ? (ppl == 3 ? kE5CntCold3 : kE5CntCold) : (ppl == 2 ? kE5CntHot2 : kE5CntHot);
 }
+// the dropout and long-token builds have no TOP variant: they keep the root's records in LDS
+bool encode5_has_top(bool dropout, bool long_tokens) { return !dropout && !long_tokens; }
 // compact: the depth of Walk5's compaction (0, 4 .. 8); the DROPOUT, LONG and one-position-per-lane builds never compact
 // count: the counting build (the caller asks for it only where encode5_counts() says the build has one)
-static encode5_fn pick_encode5(bool dropout, bool cold, int ppl, bool long_tokens, int compact, bool lean, bool step_ok, bool count) {
+// top: the TOP build (the caller asks for it only where encode5_has_top() says the build has one)
+static encode5_fn pick_encode5(bool dropout, bool cold, int ppl, bool long_tokens, int compact, bool lean, bool step_ok, bool count, bool top) {
     if (long_tokens) {  // tokens of 17..32 bytes: four positions per lane only
         if (cold) return dropout ? encode5_kernel<true, true, 4, true> : encode5_kernel<false, true, 4, true>;
         return dropout ? encode5_kernel<true, false, 4, true> : encode5_kernel<false, false, 4, true>;
@@ -1423,60 +1464,51 @@ static encode5_fn pick_encode5(bool dropout, bool cold, int ppl, bool long_token
         if (ppl == 3) return encode5_kernel<true, false, 3, false>;
         return encode5_kernel<true, false, 4, false>;
     }
-#define TGX_E5K(C, PL, LN, CN) \
-    (compact == 4 ? encode5_kernel<false, C, PL, false, 4, LN, CN> : compact == 5 ? encode5_kernel<false, C, PL, false, 5, LN, CN> \
-     : compact == 6 ? encode5_kernel<false, C, PL, false, 6, LN, CN> : compact == 7 ? encode5_kernel<false, C, PL, false, 7, LN, CN> \
-     : compact == 8 ? encode5_kernel<false, C, PL, false, 8, LN, CN> : encode5_kernel<false, C, PL, false, 0, LN, CN>)
-#define TGX_E5L(LNH, LNC, LNC3, CN) \
+#define TGX_E5K(C, PL, LN, CN, T) \
+    (compact == 4 ? encode5_kernel<false, C, PL, false, 4, LN, CN, T> : compact == 5 ? encode5_kernel<false, C, PL, false, 5, LN, CN, T> \
+     : compact == 6 ? encode5_kernel<false, C, PL, false, 6, LN, CN, T> : compact == 7 ? encode5_kernel<false, C, PL, false, 7, LN, CN, T> \
+     : compact == 8 ? encode5_kernel<false, C, PL, false, 8, LN, CN, T> : encode5_kernel<false, C, PL, false, 0, LN, CN, T>)
+#define TGX_E5L(LNH, LNC, LNC3, CN, T) \
     if (cold) { \
-        if (ppl == 1) return encode5_kernel<false, true, 1, false, 0, LNC, CN && kE5CntCold>; \
-        if (ppl == 2) return TGX_E5K(true, 2, LNC, CN && kE5CntCold); \
-        if (ppl == 3) return TGX_E5K(true, 3, LNC3, CN && kE5CntCold3); \
-        return TGX_E5K(true, 4, LNC, CN && kE5CntCold); \
+        if (ppl == 1) return encode5_kernel<false, true, 1, false, 0, LNC, CN && kE5CntCold, T>; \
+        if (ppl == 2) return TGX_E5K(true, 2, LNC, CN && kE5CntCold, T); \
+        if (ppl == 3) return TGX_E5K(true, 3, LNC3, CN && kE5CntCold3, T); \
+        return TGX_E5K(true, 4, LNC, CN && kE5CntCold, T); \
     } \
-    if (ppl == 1) return encode5_kernel<false, false, 1, false, 0, LNH, CN && kE5CntHot>; \
-    if (ppl == 2) return TGX_E5K(false, 2, LNH, CN && kE5CntHot2); \
-    if (ppl == 3) return TGX_E5K(false, 3, LNH, CN && kE5CntHot); \
-    return TGX_E5K(false, 4, LNH, CN && kE5CntHot);
-#define TGX_E5C(CN) \
+    if (ppl == 1) return encode5_kernel<false, false, 1, false, 0, LNH, CN && kE5CntHot, T>; \
+    if (ppl == 2) return TGX_E5K(false, 2, LNH, CN && kE5CntHot2, T); \
+    if (ppl == 3) return TGX_E5K(false, 3, LNH, CN && kE5CntHot, T); \
+    return TGX_E5K(false, 4, LNH, CN && kE5CntHot, T);
+#define TGX_E5C(CN, T) \
     if (lean && step_ok) { \
-        TGX_E5L(kE5LeanHot, kE5LeanCold, kE5LeanCold3, CN) \
+        TGX_E5L(kE5LeanHot, kE5LeanCold, kE5LeanCold3, CN, T) \
     } \
     if (lean) {  /* a score beyond the lean step's gate: the same builds without the step (0: the kernel as it was) */ \
-        TGX_E5L(lean_without_step(kE5LeanHot), lean_without_step(kE5LeanCold), lean_without_step(kE5LeanCold3), CN) \
+        TGX_E5L(lean_without_step(kE5LeanHot), lean_without_step(kE5LeanCold), lean_without_step(kE5LeanCold3), CN, T) \
     } \
-    TGX_E5L(0, 0, 0, CN)
+    TGX_E5L(0, 0, 0, CN, T)
+#define TGX_E5T(CN) \
+    if (top) { \
+        TGX_E5C(CN, true) \
+    } \
+    TGX_E5C(CN, false)
     if (count) {  // (a build whose count is off by default has no counting instance: the flag then selects its plain one)
-        TGX_E5C(true)
+        TGX_E5T(true)
     }
-    TGX_E5C(false)
+    TGX_E5T(false)
+#undef TGX_E5T
 #undef TGX_E5C
 #undef TGX_E5L
 #undef TGX_E5K
 }
 
-// LDS of one block of `waves` waves: score table (-inf and n_hot values), the waves' lists of long matches (LONG
-// builds), root records, match indices
-uint32_t encode5_lds_layout(uint32_t n_hot, bool long_tokens, int waves, int ppl, uint32_t* list_off, uint32_t* root_off, uint32_t* idx_off) {
-    const uint32_t lo = (8u * (n_hot + 1u) + 15u) & ~15u;
-    const uint32_t score_bytes = lo + (long_tokens ? (uint32_t)waves * ((kE5LongBytes + 15u) & ~15u) : 0u);
-    if (list_off) *list_off = lo;
-    const uint32_t ro = (score_bytes + 15u) & ~15u;
-    const uint32_t io = (ro + 2048u + 511u) & ~511u;  // 512-byte aligned: see kE5RowStride
-    if (root_off) *root_off = ro;
-    if (idx_off) *idx_off = io;
-    return io + (uint32_t)waves * (uint32_t)ppl * kE5GroupBytes;
-}
-// the largest table that leaves a block of `waves` waves within `budget` bytes of LDS
-uint32_t encode5_max_hot(bool long_tokens, int waves, int ppl, uint32_t budget) {
-    const uint32_t fixed = encode5_lds_layout(0u, long_tokens, waves, ppl, nullptr, nullptr, nullptr) + 512u;  // alignment slack
-    return budget > fixed + 64u ? (budget - fixed) / 8u : 0u;
-}
+// (the LDS of a block — encode5_lds_layout, encode5_max_hot: encode5_layout.h)
 
-hipError_t encode5_waves_per_simd(bool dropout, bool cold, int ppl, bool long_tokens, int compact, bool lean, bool step_ok, bool count, int* out) {
+hipError_t encode5_waves_per_simd(bool dropout, bool cold, int ppl, bool long_tokens, int compact, bool lean, bool step_ok, bool count, bool top, int* out) {
     hipFuncAttributes attr;
     hipError_t e = hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(pick_encode5(dropout, cold, ppl, long_tokens, compact, lean && encode5_has_lean(dropout, long_tokens), step_ok,
-                                                                                             count && encode5_counts(dropout, cold, ppl, long_tokens))));
+                                                                                             count && encode5_counts(dropout, cold, ppl, long_tokens),
+                                                                                             top && encode5_has_top(dropout, long_tokens))));
     if (e != hipSuccess) return e;
     const int regs = (attr.numRegs + 7) & ~7;
     *out = regs > 0 ? (512 / regs > 8 ? 8 : 512 / regs) : 8;
@@ -1527,14 +1559,15 @@ hipError_t launch_encode6(const EncodeParams& p, Encode5Params q, bool cold, boo
 }
 
 hipError_t launch_encode5(const EncodeParams& p, Encode5Params q, bool cold, int ppl, bool long_tokens, int compact, bool lean, bool step_ok, bool count,
-                          int waves, uint32_t blocks, uint32_t min_lds, hipStream_t stream) {
-    uint32_t lds = encode5_lds_layout(q.n_hot, long_tokens, waves, ppl, &q.list_off, &q.root_off, &q.idx_off);
+                          bool top, int waves, uint32_t blocks, uint32_t min_lds, hipStream_t stream) {
+    if (top && (!encode5_has_top(p.dropout > 0.0, long_tokens) || !q.top)) return hipErrorInvalidValue;  // (the layout has no root copy)
+    uint32_t lds = encode5_lds_layout(q.n_hot, long_tokens, waves, ppl, &q.list_off, &q.root_off, &q.idx_off, top);
     if (lds > 160u * 1024u || q.n_hot > q.n_values || (!cold && q.n_hot != q.n_values) || (long_tokens && ppl != 4) ||
         (compact != 0 && (compact < 4 || compact > 8)))
         return hipErrorInvalidValue;
     lean = lean && encode5_has_lean(p.dropout > 0.0, long_tokens);
     if (count && !encode5_counts(p.dropout > 0.0, cold, ppl, long_tokens)) return hipErrorInvalidValue;  // the caller relies on the counts
-    encode5_fn fn = pick_encode5(p.dropout > 0.0, cold, ppl, long_tokens, compact, lean, step_ok, count);
+    encode5_fn fn = pick_encode5(p.dropout > 0.0, cold, ppl, long_tokens, compact, lean, step_ok, count, top);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return e;
     if (lean && (e = lean_lds_check(reinterpret_cast<const void*>(fn))) != hipSuccess) return e;

@@ -26,6 +26,7 @@
 #include "kernels.h"
 #include "encode_split.h"
 #include "ids_in_place.h"
+#include "top_table.h"
 #include "trie_build.h"
 
 using namespace tgx::host;
@@ -98,7 +99,8 @@ tgx_status ensure_value_ranks(tgx_model* m, const tgx_corpus* c) {
     }
     cov[nv] = 1.0;
     ok = hipMemcpyAsync(d_perm, perm.data(), ((size_t)nv + 1) * 4, hipMemcpyHostToDevice, m->stream) == hipSuccess &&
-         tgx::launch_rank_remap(m->d_trie8, (uint32_t)m->flat.table.size(), d_perm, m->stream) == hipSuccess &&
+         tgx::launch_rank_remap(m->d_trie8, (uint32_t)m->flat.table.size(), d_perm, tgx::kTrie8RankMask, m->stream) == hipSuccess &&
+         (!m->d_top8 || tgx::launch_rank_remap_top(m->d_top8, d_perm, m->stream) == hipSuccess) &&  // (ranks in both halves of its second words)
          hipMemcpyAsync(m->d_values, v2.data(), ((size_t)nv + 1) * 8, hipMemcpyHostToDevice, m->stream) == hipSuccess &&
          (w2.empty() || hipMemcpyAsync(m->d_wvalues, w2.data(), ((size_t)nv + 1) * 8, hipMemcpyHostToDevice, m->stream) == hipSuccess) &&
          hipStreamSynchronize(m->stream) == hipSuccess;
@@ -260,6 +262,8 @@ tgx::EncodeSplit split_long_samples(const tgx_model* m, const tgx_corpus* c, con
 //   * two positions per lane, every value in LDS: up to ~11 900 values — the generate-style vocabularies
 //     of SURVEY.md 8(d), 9 652 values at 32 000 entries, 10 569 at 65 536 —, 12.7 ms;
 //   * three positions per lane x 13 waves, every value in LDS: up to ~10 100 values, 12.5 ms;
+//   * the same with 14 waves in the TOP builds, whose LDS holds no copy of the root's records: up to 9 727 values — the
+//     32 000-entry vocabulary's 9 652 —, encode5_kernel 12.1 -> 11.5 ms (profiles/top_table);
 //   * three positions per lane with the ~7 800 hottest values in LDS and the others read from L2 by the
 //     relaxing lanes (COLD builds; every token its own score: after an M-step or merge), 14.0 ms.
 // Fewer waves when the batch has fewer samples than the chip has rows, so that they spread over the CUs.
@@ -273,7 +277,11 @@ struct Encode5Geometry {
     int compact;          // the build's switches: the depth at which live walks are compacted,
     bool lean, step_ok;   // the lean builds, and with the lean step
     bool in_place;        // the build counts tokens and the trace writes the ids in place (ids_in_place.h)
+    bool top;             // the TOP build: a walk's first two levels from the top table, no root copy in LDS
 };
+// Three positions per lane with every value in LDS runs 14 waves where the values fit beside them without the root copy
+// (9 727 at most: the 32 000-entry spec vocabulary has 9 652), else 13 as before: by measurement (profiles/top_table).
+constexpr bool kE5Top14Waves = true;
 // p: the pass's parameters so far (dropout, flags); n_long, corun_cus: the split; have_result: there is a result to write ids into
 tgx_status choose_encode5(const tgx_model* m, const tgx_corpus* c, const tgx::EncodeParams& p, bool long_tokens, uint64_t n_long,
                           uint32_t corun_cus, bool have_result, Encode5Geometry* out) {
@@ -293,6 +301,10 @@ tgx_status choose_encode5(const tgx_model* m, const tgx_corpus* c, const tgx::En
     bool lean = tgx::encode5_has_lean(dropout > 0.0, long_tokens);
     if (const char* e = knob("TGX_E5_LEAN")) lean = lean && atoi(e) != 0;
     const bool step_ok = m->lean_scores_ok;
+    // the TOP builds (encode5.hip) and their LDS layout without the root copy; TGX_E5_TOP=0: the kernels and the geometry as they were
+    bool top = tgx::encode5_has_top(dropout > 0.0, long_tokens) && m->d_top8 != nullptr;
+    if (const char* e = knob("TGX_E5_TOP")) top = top && atoi(e) != 0;
+    const uint32_t lds_cu = 160u * 1024u;
     // ids in place (ids_in_place.h): everything but the build's own term is known here, and the geometry below is
     // sized by the registers of the build that will run — the counting one where this holds and the build has one
     tgx::IdsInPlaceQuery iq{};
@@ -307,10 +319,10 @@ tgx_status choose_encode5(const tgx_model* m, const tgx_corpus* c, const tgx::En
     const bool want_count = have_result && tgx::ids_in_place(iq);
     {
         int ps4 = 0;
-        HIP_TRY(tgx::encode5_waves_per_simd(dropout > 0.0, false, 4, long_tokens, compact, lean, step_ok, want_count, &ps4));
+        HIP_TRY(tgx::encode5_waves_per_simd(dropout > 0.0, false, 4, long_tokens, compact, lean, step_ok, want_count, top, &ps4));
         hot_waves = std::min(16, ps4 * 4);
         const int least = long_tokens ? 12 : 13;  // (the long-token build has four positions per lane only)
-        while (hot_waves >= least && m->n_values > tgx::encode5_max_hot(long_tokens, hot_waves, 4, 160u * 1024u)) hot_waves--;
+        while (hot_waves >= least && m->n_values > tgx::encode5_max_hot(long_tokens, hot_waves, 4, lds_cu, top)) hot_waves--;
         if (hot_waves < least) {
             hot_waves = 0;  // not with four positions per lane
             if (!long_tokens) {
@@ -318,10 +330,14 @@ tgx_status choose_encode5(const tgx_model* m, const tgx_corpus* c, const tgx::En
                 // vocabulary, 12.5 ms against 12.8 with two positions per lane); two x 16 (up to ~11 900: the
                 // 65 536-entry one, 13.0 ms); else three x 16 with the ~7 800 hottest in LDS (every token its own
                 // score: 14.0 ms against 14.4 with four positions per lane and 3 712) — profiles/r03/n_e5_ppl3_sweep.txt
-                if (m->n_values <= tgx::encode5_max_hot(false, 13, 3, 160u * 1024u)) {
+                // (TOP: the root copy's 2 KiB are what a fourteenth wave lacked: encode5_kernel 12.00 -> 11.56 ms, profiles/top_table)
+                if (top && kE5Top14Waves && m->n_values <= tgx::encode5_max_hot(false, 14, 3, lds_cu, top)) {
+                    ppl = 3;
+                    hot_waves = 14;
+                } else if (m->n_values <= tgx::encode5_max_hot(false, 13, 3, lds_cu, top)) {
                     ppl = 3;
                     hot_waves = 13;
-                } else if (m->n_values <= tgx::encode5_max_hot(false, 16, 2, 160u * 1024u)) {
+                } else if (m->n_values <= tgx::encode5_max_hot(false, 16, 2, lds_cu, top)) {
                     ppl = 2;
                 } else {
                     ppl = 3;
@@ -355,19 +371,19 @@ tgx_status choose_encode5(const tgx_model* m, const tgx_corpus* c, const tgx::En
     const uint32_t budget = 160u * 1024u / (uint32_t)bpc;
     bool cold = false;
     int per_simd = 0;
-    HIP_TRY(tgx::encode5_waves_per_simd(dropout > 0.0, false, ppl, long_tokens, compact, lean, step_ok, want_count, &per_simd));
+    HIP_TRY(tgx::encode5_waves_per_simd(dropout > 0.0, false, ppl, long_tokens, compact, lean, step_ok, want_count, top, &per_simd));
     int waves = std::min(16, (per_simd / bpc) * 4);
     if ((ppl == 4 || ppl == 3) && bpc == 1 && hot_waves > 0) waves = std::min(waves, hot_waves);
-    if (m->n_values > tgx::encode5_max_hot(long_tokens, waves, ppl, budget)) {
+    if (m->n_values > tgx::encode5_max_hot(long_tokens, waves, ppl, budget, top)) {
         cold = true;
-        HIP_TRY(tgx::encode5_waves_per_simd(dropout > 0.0, true, ppl, long_tokens, compact, lean, step_ok, want_count, &per_simd));
+        HIP_TRY(tgx::encode5_waves_per_simd(dropout > 0.0, true, ppl, long_tokens, compact, lean, step_ok, want_count, top, &per_simd));
         waves = std::min(16, (per_simd / bpc) * 4);
     }
     if (balance_waves > 0 && ppl == 4 && bpc == 1) waves = std::min(waves, balance_waves);
     waves = waves_for_units(waves, rest_n, (uint64_t)cus5 * bpc);
     knob_int("TGX_WAVES", 1, 16, &waves);
-    while (waves > 1 && tgx::encode5_max_hot(long_tokens, waves, ppl, budget) < 16u) waves--;
-    uint32_t n_hot = std::min(m->n_values, tgx::encode5_max_hot(long_tokens, waves, ppl, budget));
+    while (waves > 1 && tgx::encode5_max_hot(long_tokens, waves, ppl, budget, top) < 16u) waves--;
+    uint32_t n_hot = std::min(m->n_values, tgx::encode5_max_hot(long_tokens, waves, ppl, budget, top));
     n_hot = knob_cap_hot("TGX_E5_HOT", n_hot);
     cold = n_hot < m->n_values;
     iq.build_counts = tgx::encode5_counts(dropout > 0.0, cold, ppl, long_tokens);
@@ -375,7 +391,7 @@ tgx_status choose_encode5(const tgx_model* m, const tgx_corpus* c, const tgx::En
     const uint64_t rows_per_block = 4 * (uint64_t)waves;
     const uint32_t blocks5 = (uint32_t)std::max<uint64_t>(
         1, std::min<uint64_t>((rest_n + rows_per_block - 1) / rows_per_block, (uint64_t)cus5 * bpc));
-    *out = Encode5Geometry{ppl, bpc, waves, per_simd, cold, n_hot, blocks5, compact, lean, step_ok, in_place};
+    *out = Encode5Geometry{ppl, bpc, waves, per_simd, cold, n_hot, blocks5, compact, lean, step_ok, in_place, top};
     return TGX_OK;
 }
 
@@ -420,6 +436,7 @@ tgx_status encode_rows5(tgx_model* m, tgx_corpus* c, tgx::EncodeParams& p, bool 
     Encode5Geometry g;
     if ((st = choose_encode5(m, c, p, long_tokens, n_long, corun_cus, r != nullptr, &g)) != TGX_OK) return st;
     m->last_n_hot = g.n_hot;
+    m->last_encode_top = g.top && c->n_samples - n_long != 0;  // (self-check: what tgx_last_encode_top_table reports)
     if (!g.in_place) {  // the trace writes through `tmp`
         if ((st = ensure_scratch(c, true)) != TGX_OK) return st;
         p.tmp = c->d_tmp;
@@ -435,6 +452,7 @@ tgx_status encode_rows5(tgx_model* m, tgx_corpus* c, tgx::EncodeParams& p, bool 
     q.trie_bytes = (uint32_t)(m->flat.table.size() * sizeof(tgx::Trie8Rec));
     q.values = m->d_values;
     q.root_base = m->root_base8;
+    q.top = m->d_top8;
     q.n_values = m->n_values;
     q.n_hot = g.n_hot;
     q.claim_chunk = claim_chunk_for(c->n_bytes, c->n_samples);
@@ -482,7 +500,7 @@ tgx_status encode_rows5(tgx_model* m, tgx_corpus* c, tgx::EncodeParams& p, bool 
             HIP_TRY(hipMemsetAsync(&m->d_ctrl->encode_redo, 0x00, 8, m->stream));
         }
         // (co-run: more than half of the CU's LDS, so that no block of the long-sample kernel shares the CU)
-        const hipError_t le = tgx::launch_encode5(p, q, g.cold, g.ppl, long_tokens, g.compact, g.lean, g.step_ok, g.in_place, g.waves, g.blocks5, corun_cus && n_long ? 84u * 1024u : 0u, m->stream);
+        const hipError_t le = tgx::launch_encode5(p, q, g.cold, g.ppl, long_tokens, g.compact, g.lean, g.step_ok, g.in_place, g.top, g.waves, g.blocks5, corun_cus && n_long ? 84u * 1024u : 0u, m->stream);
         if (le != hipSuccess) return fail(TGX_ERR_DEVICE, "encode5 launch failed: %s", hipGetErrorString(le));
     }
     bool joined = false, joined_slot = false;
@@ -672,6 +690,7 @@ tgx_status run_encode_kernel(tgx_model* m, tgx_corpus* c, double dropout, uint64
                 (unsigned long long)c->n_samples, (unsigned long long)c->n_bytes, p.lm, use4 ? (use5 ? "rows5" : "rows4") : (use2 ? "rows2" : "fused"),
                 m->flat.table.size(), p.root_base, m->n_values);
     m->last_lean_items = 0;
+    m->last_encode_top = false;
     if (use5) return encode_rows5(m, c, p, long_tokens, pass, r);
     if ((st = ensure_scratch(c, true)) != TGX_OK) return st;
     p.tmp = c->d_tmp;
@@ -765,6 +784,8 @@ tgx_status tgx::dev::ensure_encode_tables(tgx_model* m) {
         if (!m->d_values) HIP_TRY(hipMalloc((void**)&m->d_values, t8.values.size() * 8));
         HIP_TRY(hipMemcpy(m->d_trie8, t8.rec.data(), ns * sizeof(tgx::Trie8Rec), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(m->d_values, t8.values.data(), t8.values.size() * 8, hipMemcpyHostToDevice));
+        const tgx_status tst = upload_top_table(m, t8.rec.data(), ns, t8.root_base);
+        if (tst != TGX_OK) return tst;
         m->n_values = (uint32_t)t8.values.size() - 1u;
         m->value_coverage = std::move(t8.coverage);
         m->root_base8 = t8.root_base;
@@ -773,6 +794,14 @@ tgx_status tgx::dev::ensure_encode_tables(tgx_model* m) {
     HIP_TRY(hipStreamSynchronize(m->stream));
     hp.mark("uploads");
     m->encode_tables_ready = true;
+    return TGX_OK;
+}
+
+tgx_status tgx::dev::upload_top_table(tgx_model* m, const tgx::Trie8Rec* rec, size_t n_slots, uint32_t root_base) {
+    std::vector<tgx::Trie8Rec> top;
+    tgx::build_top_table(rec, n_slots, root_base, &top);
+    if (!m->d_top8) HIP_TRY(hipMalloc(&m->d_top8, top.size() * sizeof(tgx::Trie8Rec)));
+    HIP_TRY(hipMemcpy(m->d_top8, top.data(), top.size() * sizeof(tgx::Trie8Rec), hipMemcpyHostToDevice));
     return TGX_OK;
 }
 
@@ -1098,5 +1127,6 @@ uint64_t tgx_last_encode_long_samples(const tgx_model* m) { return m ? m->last_l
 uint32_t tgx_last_encode_corun_cus(const tgx_model* m) { return m ? m->last_corun_cus : 0; }
 uint32_t tgx_encode_corun_timeouts(const tgx_model* m) { return m ? m->corun_wait_timeouts : 0; }
 uint32_t tgx_last_encode_hot_values(const tgx_model* m) { return m ? m->last_n_hot : 0u; }
+int tgx_last_encode_top_table(const tgx_model* m) { return m && m->last_encode_top ? 1 : 0; }
 uint32_t tgx_last_encode_lean_items(const tgx_model* m) { return m ? m->last_lean_items : 0u; }
 int tgx_last_encode_ids_in_place(const tgx_model* m) { return (m && m->last_ids_in_place) ? 1 : 0; }

@@ -931,11 +931,18 @@ __global__ __launch_bounds__(256) void value_count_kernel(const uint8_t* __restr
     for (uint32_t i = threadIdx.x; i < kCountLds; i += blockDim.x)
         if (hist[i] && i <= n_values) atomicAdd(&counts[i], hist[i]);
 }
-__global__ __launch_bounds__(256) void rank_remap_kernel(uint2* __restrict__ trie, uint32_t n_slots, const uint32_t* __restrict__ perm) {
+__global__ __launch_bounds__(256) void rank_remap_kernel(uint2* __restrict__ trie, uint32_t n_slots, const uint32_t* __restrict__ perm, uint32_t rank_mask) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_slots) return;
-    const uint32_t r = trie[t].y;
+    const uint32_t r = trie[t].y & rank_mask;
     if (r) trie[t].y = perm[r];
+}
+// encode5_kernel's top table (top_table.h): 65 536 records, a 16-bit rank in either half of the second word (perm[0] == 0)
+__global__ __launch_bounds__(256) void rank_remap_top_kernel(uint2* __restrict__ top, const uint32_t* __restrict__ perm) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= 65536u) return;
+    const uint32_t r = top[t].y;
+    if (r) top[t].y = (perm[r & 0xFFFFu] & 0xFFFFu) | (perm[r >> 16] << 16);
 }
 hipError_t launch_match_count(const uint8_t* text, uint64_t n_bytes, uint32_t chunk, uint64_t stride, const void* trie8t, uint32_t n_slots,
                               uint32_t root_base, uint32_t n_tok, unsigned int* counts, uint32_t num_cus, hipStream_t stream) {
@@ -951,8 +958,12 @@ hipError_t launch_value_count(const uint8_t* text, uint64_t n_bytes, uint32_t ch
                        reinterpret_cast<const uint2*>(trie8), n_slots, root_base, n_values, max_len, counts);
     return hipGetLastError();
 }
-hipError_t launch_rank_remap(void* trie8t, uint32_t n_slots, const uint32_t* perm, hipStream_t stream) {
-    hipLaunchKernelGGL(rank_remap_kernel, dim3((n_slots + 255u) / 256u), dim3(256), 0, stream, reinterpret_cast<uint2*>(trie8t), n_slots, perm);
+hipError_t launch_rank_remap(void* trie8t, uint32_t n_slots, const uint32_t* perm, uint32_t rank_mask, hipStream_t stream) {
+    hipLaunchKernelGGL(rank_remap_kernel, dim3((n_slots + 255u) / 256u), dim3(256), 0, stream, reinterpret_cast<uint2*>(trie8t), n_slots, perm, rank_mask);
+    return hipGetLastError();
+}
+hipError_t launch_rank_remap_top(void* top, const uint32_t* perm, hipStream_t stream) {
+    hipLaunchKernelGGL(rank_remap_top_kernel, dim3(65536u / 256u), dim3(256), 0, stream, reinterpret_cast<uint2*>(top), perm);
     return hipGetLastError();
 }
 

@@ -107,6 +107,10 @@ static tgx_status ensure_estep_trie8(tgx_model* m) {
     HIP_TRY(hipMemcpy(m->d_trie8, t8.rec.data(), ns * sizeof(tgx::Trie8Rec), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(m->d_values, t8.values.data(), nv * 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(m->d_wvalues, w.data(), nv * 8, hipMemcpyHostToDevice));
+    {   // (the records are in build_trie8's order again: so is the top table an encode of this model reads)
+        const tgx_status tst = upload_top_table(m, t8.rec.data(), ns, t8.root_base);
+        if (tst != TGX_OK) return tst;
+    }
     m->n_values = (uint32_t)nv - 1u;
     m->root_base8 = t8.root_base;
     if (m->values_ranked || m->value_coverage.empty()) m->value_coverage = std::move(t8.coverage);
@@ -331,7 +335,7 @@ static tgx_status ensure_estep_trie8t(tgx_model* m, const tgx_corpus* c) {
         t8.w.swap(w2);
         t8.id_of_rank.swap(id2);
         if (hipMemcpyAsync(d_perm, perm.data(), nw * 4, hipMemcpyHostToDevice, m->stream) != hipSuccess ||
-            tgx::launch_rank_remap(m->d_trie8t, (uint32_t)ns, d_perm, m->stream) != hipSuccess || hipStreamSynchronize(m->stream) != hipSuccess)
+            tgx::launch_rank_remap(m->d_trie8t, (uint32_t)ns, d_perm, ~0u, m->stream) != hipSuccess || hipStreamSynchronize(m->stream) != hipSuccess)
             return fail(TGX_ERR_DEVICE, "rank remap failed: %s", hipGetErrorString(hipGetLastError()));
         pass.done();
         hp.mark("re-rank");

@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "decode.h"
+#include "encode5_layout.h"
 #include "fim.h"
 #include "spans.h"
 
@@ -60,6 +61,7 @@ struct Encode5Params {
     uint32_t pool;                            // encode6_kernel, COLD builds: pool entries per ring slot for values its walkers fetch (0: none)
     unsigned int* started;                    // encode5_kernel: when not null, every block adds 1 here once it is resident (host-visible memory:
                                               // the co-run launches the long-sample kernel only after all of them are)
+    const void* top;                          // encode5_kernel, TOP builds: the top table (top_table.h), Trie8Rec[65 536]
 };
 
 struct CompactParams {
@@ -254,7 +256,10 @@ hipError_t launch_match_count(const uint8_t* text, uint64_t n_bytes, uint32_t ch
 hipError_t launch_value_count(const uint8_t* text, uint64_t n_bytes, uint32_t chunk, uint64_t stride, const void* trie8, uint32_t n_slots,
                               uint32_t root_base, uint32_t n_values, uint32_t max_len, unsigned int* counts, uint32_t num_cus, hipStream_t stream);
 // rec[t].tok = perm[rec[t].tok] for every slot of the 8-byte E-step records (and encode5_kernel's: the second word is the rank there too)
-hipError_t launch_rank_remap(void* trie8t, uint32_t n_slots, const uint32_t* perm, hipStream_t stream);
+// rank_mask: the bits of the word that hold the rank (encode5_kernel's records: kTrie8RankMask); the others are dropped
+hipError_t launch_rank_remap(void* trie8t, uint32_t n_slots, const uint32_t* perm, uint32_t rank_mask, hipStream_t stream);
+// the same for encode5_kernel's top table (top_table.h), whose second words hold a rank in either half
+hipError_t launch_rank_remap_top(void* top, const uint32_t* perm, hipStream_t stream);
 hipError_t launch_snip_z_check(const double* zsnip, uint64_t n_snips, unsigned long long* err_snip, hipStream_t stream);
 hipError_t launch_piece_z_add(const double* zarr, const uint32_t* psnip, const uint32_t* order, uint64_t n_order, double* zsnip, hipStream_t stream);
 
@@ -291,8 +296,7 @@ hipError_t launch_trace_in_place(const EncodeParams& p, const TraceInPlace& o, u
 // err_sample code bits of the trace kernels (the plain value: the lowest sample whose end is not reached)
 constexpr unsigned long long kErrCorruptBp = 1ULL << 62;      // a back-pointer that names no vocabulary token (low bits: the text byte)
 constexpr unsigned long long kErrCountMismatch = 1ULL << 61;  // in place: the trace's token count differs from P.counts (low bits: the sample)
-uint32_t encode5_lds_layout(uint32_t n_hot, bool long_tokens, int waves, int ppl, uint32_t* list_off, uint32_t* root_off, uint32_t* idx_off);
-uint32_t encode5_max_hot(bool long_tokens, int waves, int ppl, uint32_t budget);
+// (encode5_lds_layout, encode5_max_hot: encode5_layout.h)
 // lean: the kernels with the lean relaxation step (TGX_E5_LEAN; device_common.h: relax5_lean_step) — the dropout and
 // long-token builds have none and run the step as it was (encode5_has_lean)
 bool encode5_has_lean(bool dropout, bool long_tokens);
@@ -303,8 +307,11 @@ int encode6_lean_items();
 // whether the build of encode5_kernel counts tokens in its relaxation and writes them to P.counts (DESIGN.md section R8;
 // decided per build in encode5.hip): the passes of such a build may write ids in place (ids_in_place.h)
 bool encode5_counts(bool dropout, bool cold, int ppl, bool long_tokens);
-// count: ask for the counting build where the geometry has one
-hipError_t encode5_waves_per_simd(bool dropout, bool cold, int ppl, bool long_tokens, int compact, bool lean, bool step_ok, bool count, int* out);
+// whether encode5_kernel has a TOP build for these (the first two levels of a walk from the top table,
+// no root copy in LDS): every hot and COLD build; the dropout and long-token builds keep their root copy
+bool encode5_has_top(bool dropout, bool long_tokens);
+// count: ask for the counting build where the geometry has one; top: the TOP build (where encode5_has_top())
+hipError_t encode5_waves_per_simd(bool dropout, bool cold, int ppl, bool long_tokens, int compact, bool lean, bool step_ok, bool count, bool top, int* out);
 uint32_t encode6_lds_layout(uint32_t n_hot, uint32_t pool, uint32_t* root_off, uint32_t* ctrl_off, uint32_t* ring_off);
 uint32_t encode6_max_hot(uint32_t budget, uint32_t pool);
 uint32_t encode6_pool_total(uint32_t pool);  // pool entries of a block (index space they take)
@@ -314,8 +321,9 @@ hipError_t launch_estep5_fwd(const struct Estep4Params& p, Encode5Params q, bool
 hipError_t launch_encode6(const EncodeParams& p, Encode5Params q, bool cold, bool lean, uint32_t blocks, hipStream_t stream);
 // compact: the depth at which the walks of a trip are compacted (0: never; 4 .. 8; encode5.hip: Walk5)
 // count: the counting build (an error where encode5_counts() says the build has none)
+// top: the TOP build and its LDS layout (an error where encode5_has_top() says the build has none, or without q.top)
 hipError_t launch_encode5(const EncodeParams& p, Encode5Params q, bool cold, int ppl, bool long_tokens, int compact, bool lean, bool step_ok, bool count,
-                          int waves, uint32_t blocks, uint32_t min_lds, hipStream_t stream);
+                          bool top, int waves, uint32_t blocks, uint32_t min_lds, hipStream_t stream);
 hipError_t launch_encode2(const EncodeParams& p, uint32_t num_cus, bool permuted, hipStream_t stream);   // encode2.hip
 hipError_t launch_trace32(const EncodeParams& p, uint32_t blocks, bool permuted, hipStream_t stream);
 hipError_t launch_encode4l(const EncodeParams& p, uint32_t num_cus, hipStream_t stream);  // encode4l.hip

@@ -52,6 +52,8 @@ tgx_status ensure_scratch(tgx_corpus* c, bool with_tmp = true);
 tgx::EncodeParams base_encode_params(const tgx_model* m, const tgx_corpus* c, uint64_t seed);
 // the token hash table and the 8-byte records, built at the first pass that reads them; caller holds m->mu
 tgx_status ensure_encode_tables(tgx_model* m);
+// encode5_kernel's top table (top_table.h) from the trie8 records just written to m->d_trie8: whoever writes those calls this
+tgx_status upload_top_table(tgx_model* m, const tgx::Trie8Rec* rec, size_t n_slots, uint32_t root_base);
 // m->h_ctrl->err as a status: TGX_ERR_NO_PATH with its error detail, or an internal error
 tgx_status check_no_path(tgx_model* m, const tgx_corpus* c);
 // counts in c->d_counts and ids right-aligned in c->d_tmp -> r's offsets and ids (the compaction is queued, not waited for)

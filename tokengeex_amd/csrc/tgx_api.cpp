@@ -552,6 +552,7 @@ void tgx_model_destroy(tgx_model* m) {
     if (m->d_trie_rev_w) (void)hipFree(m->d_trie_rev_w);
     if (m->d_tokhash) (void)hipFree(m->d_tokhash);
     if (m->d_trie8) (void)hipFree(m->d_trie8);
+    if (m->d_top8) (void)hipFree(m->d_top8);
     if (m->d_values) (void)hipFree(m->d_values);
     if (m->d_tokid) (void)hipFree(m->d_tokid);
     if (m->d_ctrl) (void)hipFree(m->d_ctrl);
