@@ -1207,6 +1207,10 @@ void tgx_free(void *p);
  * pooled buffer of `device` (all devices if negative) to the HIP runtime, e.g. before another library needs
  * the memory. */
 void tgx_pool_trim(int device);
+/* A test knob ("Hostile memory"): with TGX_KNOBS=1 and TGX_POOL_FILL=<0..255> every device buffer the
+ * library allocates for itself is set to that byte, over its whole pooled size, before its owner sees it.
+ * tgx_pool_filled_bytes: the bytes so filled since the process started; 0 forever without the knob. */
+uint64_t tgx_pool_filled_bytes(void);
 /* Page-locked host memory for the buffers a caller hands to tgx_encode_batch_host / tgx_corpus_upload and
  * receives ids in: copies from and to such memory are DMA transfers at the link's rate, copies from and to
  * ordinary (pageable) memory go through the driver's staging buffers at about half of it.  NULL (and

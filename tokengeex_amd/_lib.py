@@ -86,6 +86,7 @@ SYMBOLS = {
     "tgx_generate_u01": (_d, [_u64, _u64, _u64]),
     "tgx_free": (None, [_vp]),
     "tgx_pool_trim": (None, [_i]),
+    "tgx_pool_filled_bytes": (_u64, []),
     "tgx_host_alloc": (_vp, [_u64]),
     "tgx_host_free": (None, [_vp]),
     "tgx_digamma": (_d, [_d]),
@@ -315,6 +316,11 @@ def pinned_empty(shape, dtype) -> np.ndarray:
 def pool_trim(device: int = -1) -> None:
     """Returns the library's pooled device buffers to the HIP runtime (all devices if negative)."""
     lib.tgx_pool_trim(device)
+
+
+def pool_filled_bytes() -> int:
+    """Bytes of the library's own device buffers that TGX_POOL_FILL has filled in this process (0 without the knob)."""
+    return int(lib.tgx_pool_filled_bytes())
 
 
 def device_count() -> int:
@@ -1758,6 +1764,19 @@ class NativeModel:
                                       len(tokens), device, 1 if for_estep else 0, C.byref(h)))
         self._h = h
         self.device = device
+
+    @classmethod
+    def create_plain(cls, tokens: list[bytes], scores, device: int = 0) -> "NativeModel":
+        """The same model through tgx_model_create, the entry point without flags."""
+        flat, offs = pack(tokens)
+        m = cls.__new__(cls)
+        m._scores = np.ascontiguousarray(scores, dtype=np.float64)
+        if m._scores.shape[0] != len(tokens):
+            raise ValueError("scores and tokens differ in length")
+        h = C.c_void_p()
+        check(lib.tgx_model_create(ptr(flat) if flat.size else None, ptr(offs), ptr(m._scores), len(tokens), device, C.byref(h)))
+        m._h, m.device = h, device
+        return m
 
     def __del__(self):
         self.free()

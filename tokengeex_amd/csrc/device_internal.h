@@ -39,6 +39,9 @@ void pool_free(int device, void* ptr, size_t bytes);
 // hipFree of every pooled buffer of `device` (all devices if < 0); the caller's current device is kept
 void pool_trim(int device);
 size_t rounded(size_t bytes);
+// TGX_POOL_FILL (a knob): set the bytes the library is about to hand out, and wait for it; nothing without the knob.
+// pool_alloc calls it over the pooled size; an allocator that bypasses the pool (generate.hip) calls it itself.
+hipError_t pool_fill(int device, void* p, size_t bytes);
 
 // A pooled device buffer with one owner: (device, ptr, bytes), bytes being the rounded size it was asked with (what the
 // pool files it under).  It goes back to the pool exactly once: on reset(), on the next alloc() or with its owner.

@@ -32,6 +32,7 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "../../include/tgx.h"
+#include "device_internal.h"
 
 tgx_status tgx_set_error(tgx_status st, const char* msg);  // tgx_api.cpp
 
@@ -238,6 +239,8 @@ static tgx_status substring_df_impl(int device, const uint8_t* text, uint64_t n_
         void* p = nullptr;
         if (hipMalloc(&p, std::max<size_t>(bytes, 256)) != hipSuccess) return nullptr;
         owned.push_back(p);
+        // (these buffers bypass the pool; TGX_POOL_FILL covers them all the same)
+        if (tgx::dev::pool_fill(device, p, std::max<size_t>(bytes, 256)) != hipSuccess) return nullptr;
         return p;
     };
     // (TGX_DEBUG as tgx_api.cpp reads it: set, not empty, not "0")

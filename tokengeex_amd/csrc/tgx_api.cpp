@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdarg>
 #include <cstddef>
 #include <cstdio>
@@ -53,6 +54,7 @@ std::mutex g_pool_mu;
 std::vector<PoolEntry> g_pool;
 size_t g_pool_bytes = 0;
 constexpr size_t kPoolMaxBytes = 64ull << 30;
+std::atomic<uint64_t> g_pool_filled_bytes{0};  // tgx_pool_filled_bytes
 
 }  // namespace
 
@@ -83,11 +85,32 @@ void pool_trim(int device) {
     if (prev >= 0) (void)hipSetDevice(prev);
 }
 
+// TGX_POOL_FILL=<0..255> (a knob, read per allocation): the `bytes` at p, device memory of `device` that the library
+// is about to hand out, are set to that byte, and the device has finished doing so on return, so that nothing the
+// caller queues on any stream can overtake the fill.  Without the knob: nothing, and no HIP call.  The tests' way of
+// making the library's own memory hostile: a recycled buffer holds what its previous owner left anyway, this makes it
+// one known value over the whole pooled size (tests/test_pool_fill_gpu.py).
+hipError_t pool_fill(int device, void* p, size_t bytes) {
+    const char* e = knob("TGX_POOL_FILL");
+    if (!e || !*e) return hipSuccess;
+    char* end = nullptr;
+    const long v = strtol(e, &end, 10);
+    if (*end || v < 0 || v > 255 || !p || bytes == 0) return hipSuccess;
+    int prev = -1;
+    (void)hipGetDevice(&prev);
+    if (prev != device) (void)hipSetDevice(device);
+    hipError_t st = hipMemset(p, (int)v, bytes);
+    if (st == hipSuccess) st = hipDeviceSynchronize();
+    if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
+    if (st == hipSuccess) g_pool_filled_bytes.fetch_add(bytes, std::memory_order_relaxed);
+    return st;
+}
+
 hipError_t pool_alloc(int device, size_t bytes, void** out) {
     if (bytes == 0) bytes = 256;
     bytes = (bytes + 255) & ~size_t(255);
     {
-        std::lock_guard<std::mutex> lk(g_pool_mu);
+        std::unique_lock<std::mutex> lk(g_pool_mu);
         size_t best = g_pool.size();
         for (size_t i = 0; i < g_pool.size(); i++) {
             const PoolEntry& e = g_pool[i];
@@ -96,9 +119,16 @@ hipError_t pool_alloc(int device, size_t bytes, void** out) {
         }
         if (best != g_pool.size()) {
             *out = g_pool[best].ptr;
-            g_pool_bytes -= g_pool[best].bytes;
+            const size_t entry_bytes = g_pool[best].bytes;
+            g_pool_bytes -= entry_bytes;
             g_pool.erase(g_pool.begin() + (long)best);
-            return hipSuccess;
+            lk.unlock();
+            const hipError_t fe = pool_fill(device, *out, entry_bytes);
+            if (fe != hipSuccess) {  // (a caller takes any failure as "nothing allocated")
+                pool_free(device, *out, entry_bytes);
+                *out = nullptr;
+            }
+            return fe;
         }
     }
     hipError_t e = hipMalloc(out, bytes);
@@ -108,6 +138,12 @@ hipError_t pool_alloc(int device, size_t bytes, void** out) {
         (void)hipGetLastError();
         pool_trim(device);
         e = hipMalloc(out, bytes);
+    }
+    if (e != hipSuccess) return e;
+    e = pool_fill(device, *out, bytes);
+    if (e != hipSuccess) {
+        (void)hipFree(*out);
+        *out = nullptr;
     }
     return e;
 }
@@ -318,6 +354,7 @@ int tgx_abi_version(void) { return TGX_ABI_VERSION; }
 int tgx_device_count(void) { return usable_device_count(); }
 void tgx_free(void* p) { free(p); }
 void tgx_pool_trim(int device) { pool_trim(device); }
+uint64_t tgx_pool_filled_bytes(void) { return g_pool_filled_bytes.load(std::memory_order_relaxed); }
 void* tgx_host_alloc(uint64_t bytes) {
     if (require_device() != TGX_OK) return nullptr;
     void* p = nullptr;
