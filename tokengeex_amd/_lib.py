@@ -218,6 +218,14 @@ SYMBOLS = {
     "tgx_repeat_last_times": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_float), _i]),
 }
 
+# every exported symbol of include/tgx_words.h, which adds to the ABI in a header of its own: bound and checked at import
+# as the table above is
+WORD_SYMBOLS = {
+    "tgx_corpus_word_stats_device": (_i, [_vp, _u64, _vp, _vp, _u32, _u32, _vp, _vp, _vp]),
+    "tgx_word_stats_host": (_i, [_vp, _vp, _u64, _u64, _vp, _vp, _u32, _u32, _vp, _vp]),
+    "tgx_wordstat_last_times": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_float), _i]),
+}
+
 
 class TokenGeeXError(Exception):
     """tokengeex.TokenGeeXError — bindings/python/src/lib.rs:9,33-37; carries the
@@ -263,7 +271,7 @@ def _load() -> C.CDLL:
             "Build it with `python tokengeex_amd/build.py`.")
     _share_torch_hip_runtime()
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SYMBOLS.items():
+    for name, (res, args) in list(SYMBOLS.items()) + list(WORD_SYMBOLS.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args
@@ -811,6 +819,54 @@ def textstat_last_times() -> dict[str, float]:
     names = (C.c_char_p * 8)()
     ms = (C.c_float * 8)()
     n = lib.tgx_textstat_last_times(names, ms, 8)
+    return {names[i].decode(): float(ms[i]) for i in range(n)}
+
+
+# ---- per-row word statistics (include/tgx_words.h; csrc/wordstat.hip, csrc/wordstat.h) ----
+WORDSTAT_N = 14
+WORDSTAT_CHARS, WORDSTAT_FOLD = 1, 2
+WORDSTAT_NAMES = ("words", "word_units", "max_word", "long_words", "alpha_words", "alpha_wide_words", "hash", "ellipsis", "lines", "bullet_lines",
+                  "ellipsis_lines", "punct_lines", "stop_words", "stop_mask")
+WORD_MARK_START, WORD_MARK_END, WORD_MARK_STOP, WORD_MARK_BULLET = 1, 2, 4, 8
+GOPHER_STOP_WORDS = (b"the", b"be", b"to", b"of", b"and", b"that", b"have", b"with")
+
+
+def wordstat_flags(unit: str, fold_case: bool) -> int:
+    """unit "char" or "byte", and whether the text's A-Z are lowered for the stop words -> the flags of
+    tgx_corpus_word_stats_device."""
+    return (WORDSTAT_CHARS if textstat_flags(unit) else 0) | (WORDSTAT_FOLD if fold_case else 0)
+
+
+def _stop_table(stop_words):
+    """words as bytes or str (UTF-8) -> (flat u8, offs u64, n) of the ABI; the library checks them"""
+    words = [w.encode("utf-8") if isinstance(w, str) else bytes(w) for w in (stop_words or ())]
+    flat, offs = pack(words)
+    return flat, offs, len(words)
+
+
+def word_stats_host(text: np.ndarray, offs: np.ndarray, word_limit: int = 20, stop_words=GOPHER_STOP_WORDS, unit: str = "char",
+                    fold_case: bool = True):
+    """Host twin of NativeCorpus.word_stats (tgx_word_stats_host: the kernel's chunks, masks, summaries, carry and store /
+    add rule through the same header, no device) over text u8[N] and offsets u64[S+1] -> (stats int64[14, S], marks
+    uint8[N])."""
+    text = np.ascontiguousarray(text, dtype=np.uint8)
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    n = max(offs.shape[0] - 1, 0)
+    sflat, soffs, n_stop = _stop_table(stop_words)
+    stats = np.full((WORDSTAT_N, n), -7, np.int64)
+    marks = np.full(text.size, 7, np.uint8)
+    keep = np.zeros(1, np.int64), np.zeros(1, np.uint8)   # (never NULL: both outputs are asked for)
+    check(lib.tgx_word_stats_host(ptr(text) if text.size else None, ptr(offs) if offs.size else None, n, int(word_limit),
+                                  ptr(sflat) if sflat.size else None, ptr(soffs), n_stop, wordstat_flags(unit, fold_case),
+                                  ptr(stats if n else keep[0]), ptr(marks if marks.size else keep[1])))
+    return stats, marks
+
+
+def wordstat_last_times() -> dict[str, float]:
+    """Device time in ms of each stage of the calling thread's last word_stats call (tgx_wordstat_last_times)."""
+    names = (C.c_char_p * 8)()
+    ms = (C.c_float * 8)()
+    n = lib.tgx_wordstat_last_times(names, ms, 8)
     return {names[i].decode(): float(ms[i]) for i in range(n)}
 
 
@@ -1726,6 +1782,15 @@ class NativeCorpus:
         "byte"), and per byte whether a line begins there, as u8[N], into caller-owned device memory (either may be 0;
         tgx_corpus_text_stats_device).  This corpus is only read."""
         check(lib.tgx_corpus_text_stats_device(self._h, int(line_limit), textstat_flags(unit), stream or None, d_stats or None, d_line_start or None))
+
+    def word_stats(self, d_stats: int = 0, d_marks: int = 0, word_limit: int = 20, stop_words=GOPHER_STOP_WORDS, unit: str = "char",
+                   fold_case: bool = True, *, stream: int = 0) -> None:
+        """Per sample the fourteen word statistics of include/tgx_words.h as int64[14, S] (WORDSTAT_NAMES; word lengths in
+        `unit`, "char" or "byte"), and per byte its marks (WORD_MARK_*), as u8[N], into caller-owned device memory (either
+        may be 0; tgx_corpus_word_stats_device).  stop_words: at most 63 words of 1 to 8 bytes.  This corpus is only read."""
+        sflat, soffs, n_stop = _stop_table(stop_words)
+        check(lib.tgx_corpus_word_stats_device(self._h, int(word_limit), ptr(sflat) if sflat.size else None, ptr(soffs), n_stop,
+                                               wordstat_flags(unit, fold_case), stream or None, d_stats or None, d_marks or None))
 
     def lines(self, *, stream: int = 0) -> "NativeCorpus":
         """A new resident corpus whose samples are the lines of this one, in order, each with its '\\n' if it has one

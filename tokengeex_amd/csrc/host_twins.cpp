@@ -1,8 +1,8 @@
 // The *_host twins of the result-side device entry points (include/tgx.h): tgx_layout_pad_host, tgx_layout_pack_host,
-// tgx_layout_windows_host, tgx_assemble_host, tgx_fim_host, tgx_select_host, tgx_select_text_host, tgx_shuffled_rows_host, tgx_first_equal_host, tgx_minhash_host, tgx_minhash_bands_host, tgx_minhash_near_first_host, tgx_gram_keys_host, tgx_gram_hits_host, tgx_gram_contains_host, tgx_repeat_stats_host, tgx_text_stats_host, tgx_lines_host, tgx_decode_rows_host, tgx_spans_host, tgx_window_spans_host, tgx_front_host,
+// tgx_layout_windows_host, tgx_assemble_host, tgx_fim_host, tgx_select_host, tgx_select_text_host, tgx_shuffled_rows_host, tgx_first_equal_host, tgx_minhash_host, tgx_minhash_bands_host, tgx_minhash_near_first_host, tgx_gram_keys_host, tgx_gram_hits_host, tgx_gram_contains_host, tgx_repeat_stats_host, tgx_text_stats_host, tgx_lines_host, tgx_word_stats_host (include/tgx_words.h), tgx_decode_rows_host, tgx_spans_host, tgx_window_spans_host, tgx_front_host,
 // tgx_normalize_host and tgx_lattice_stats_host, and the
 // argument checks they share with the device entry points of tgx_api.cpp.  A twin goes through the same index arithmetic as its kernels (layout.h, assemble.h,
-// fim.h, select.h, dedup.h, minhash.h, gram.h, repeat.h, textstat.h, decode.h, spans.h, front.h, norm.h) on host memory.  Nothing in this file calls a HIP function, so it builds and runs without the
+// fim.h, select.h, dedup.h, minhash.h, gram.h, repeat.h, textstat.h, wordstat.h, decode.h, spans.h, front.h, norm.h) on host memory.  Nothing in this file calls a HIP function, so it builds and runs without the
 // handles, the pool or a device.
 #define TGX_HOST_ONLY  // tile_fill.h: the host loop, no kernel side
 #include <algorithm>
@@ -27,6 +27,8 @@
 #include "spans.h"
 #include "textstat.h"
 #include "unicode_tables.h"
+#include "wordstat.h"
+#include "../../include/tgx_words.h"
 
 using namespace tgx::host;
 
@@ -1221,6 +1223,129 @@ tgx_status tgx_lines_host(const uint8_t* text, const uint64_t* offs, uint64_t n_
     for (uint64_t p = 0; p < N; p++)  // the compaction of the marked positions
         if (marks[p]) out_offs[k++] = p;
     out_offs[n] = N;
+    return TGX_OK;
+}
+
+// ---- word statistics (include/tgx_words.h) -----------------------------------------------------
+
+namespace {
+
+// The twin of wordstat.hip's two kernels and the scan between them: the chunks of textstat_walk_host, the masks as words,
+// the summaries, the scan as a fold, and the second kernel lane by lane with its store / add rule.  The source and the
+// table (u64[2 * n_stop], wordstat.h) have been checked, S > 0; stats and marks may each be NULL.
+void wordstat_host(const uint8_t* text, const uint64_t* offs, uint64_t S, uint64_t word_limit, uint32_t flags, const uint64_t* table, uint32_t n_stop,
+                   int64_t* stats, uint8_t* marks) {
+    const uint64_t N = offs[S], n_chunks = (N + tgx::kTextstatChunk - 1) / tgx::kTextstatChunk;
+    const bool fold = (flags & tgx::kWordstatFold) != 0;
+    auto masks_of = [&](uint64_t c0, uint32_t n_in, uint64_t starts, const uint64_t* row) {
+        tgx::WordMasks m = {};
+        for (uint32_t l = 0; l < n_in; l++) {
+            const uint8_t b = text[c0 + l];
+            const uint64_t bit = 1ull << l;
+            const bool space = tgx::textstat_is_space(b);
+            if (space || c0 + l == offs[row[l]]) m.resets |= bit;
+            if (!space && tgx::textstat_is_unit(b, (flags & tgx::kWordstatChars) ? tgx::kTextstatChars : 0u)) m.units |= bit;
+            if (tgx::textstat_is_alpha(b)) m.alpha |= bit;
+            if (tgx::wordstat_is_wide(b)) m.wide |= bit;
+            if (!space) m.nonspace |= bit;
+        }
+        m.starts = starts;
+        return m;
+    };
+    if (stats) std::fill(stats, stats + S * tgx::kWordstatN, 0);  // the launcher's pre-set
+    std::vector<uint64_t> summary(n_chunks), carry(n_chunks);
+    textstat_walk_host(text, offs, S, [&](uint64_t c0, uint32_t n_in, uint64_t starts, const uint64_t* row) {
+        summary[c0 / tgx::kTextstatChunk] = tgx::wordstat_summary(masks_of(c0, n_in, starts, row));
+    });
+    uint64_t acc = 0;  // the exclusive scan under WordstatCarryOp
+    for (uint64_t k = 0; k < n_chunks; k++) {
+        carry[k] = acc;
+        acc = tgx::WordstatCarryOp()(acc, summary[k]);
+    }
+    textstat_walk_host(text, offs, S, [&](uint64_t c0, uint32_t n_in, uint64_t starts, const uint64_t* row) {
+        const tgx::WordMasks m = masks_of(c0, n_in, starts, row);
+        const uint64_t cy = carry[c0 / tgx::kTextstatChunk];
+        uint64_t ballots[tgx::kWordstatN] = {}, hits[tgx::kWordstatMaxStop] = {}, len[tgx::kTextstatChunk] = {};
+        uint8_t mark[tgx::kTextstatChunk] = {};
+        ballots[tgx::kWsWordUnits] = m.units;
+        for (uint32_t l = 0; l < n_in; l++) {
+            const uint64_t p = c0 + l, bit = 1ull << l, row_begin = offs[row[l]], row_end = offs[row[l] + 1];
+            uint8_t prev = 0;
+            const uint64_t tail = tgx::wordstat_tail_of(text, p, row_begin, fold, &prev);
+            const bool nonspace = (m.nonspace >> l) & 1ull;
+            const bool is_wend = nonspace && (p + 1 == row_end || tgx::textstat_is_space(text[p + 1]));
+            const uint32_t nsb = tgx::wordstat_nsb(m, l, cy);
+            const bool is_nl = text[p] == '\n', is_lend = is_nl || p + 1 == row_end;
+            if (is_wend) {
+                const tgx::WordSoFar w = tgx::wordstat_word(m, l, cy);
+                len[l] = w.units;
+                ballots[tgx::kWsWords] |= bit;
+                if (w.units > word_limit) ballots[tgx::kWsLongWords] |= bit;
+                if (w.alpha) ballots[tgx::kWsAlphaWords] |= bit;
+                if (w.alpha || w.wide) ballots[tgx::kWsAlphaWideWords] |= bit;
+                for (uint32_t k = 0; k < n_stop; k++)
+                    if (tgx::wordstat_matches(tail, prev, table[tgx::kWordstatStopWords * k], table[tgx::kWordstatStopWords * k + 1])) {
+                        hits[k] |= bit;
+                        ballots[tgx::kWsStopWords] |= bit;
+                    }
+            }
+            if (text[p] == '#') ballots[tgx::kWsHash] |= bit;
+            if (tgx::wordstat_is_ellipsis(tail)) ballots[tgx::kWsEllipsis] |= bit;
+            if (tgx::wordstat_is_bullet(tail, nsb)) ballots[tgx::kWsBulletLines] |= bit;
+            if (is_lend) {
+                ballots[tgx::kWsLines] |= bit;
+                if (tgx::wordstat_ellipsis_line(tail, is_nl)) ballots[tgx::kWsEllipsisLines] |= bit;
+                if (tgx::wordstat_punct_line(tail, is_nl)) ballots[tgx::kWsPunctLines] |= bit;
+            }
+            mark[l] = (uint8_t)((tgx::wordstat_is_word_start(tail) ? tgx::kWordMarkStart : 0u) | (is_wend ? tgx::kWordMarkEnd : 0u) |
+                                ((ballots[tgx::kWsStopWords] & bit) ? tgx::kWordMarkStop : 0u) | ((ballots[tgx::kWsBulletLines] & bit) ? tgx::kWordMarkBullet : 0u));
+        }
+        if (marks) std::copy(mark, mark + n_in, marks + c0);
+        if (!stats) return;
+        for (uint32_t a = 0; a < n_in;) {  // the stretch [a, b] of one row
+            uint32_t b = a;
+            while (b + 1 < n_in && row[b + 1] == row[a]) b++;
+            const uint64_t i = row[a], stretch = tgx::textstat_span(a, b);
+            const bool inside = tgx::textstat_row_inside(offs, i, c0);
+            uint64_t longest = 0, stop_mask = 0;
+            for (uint32_t l = a; l <= b; l++) longest = std::max(longest, len[l]);
+            for (uint32_t k = 0; k < n_stop; k++)
+                if (hits[k] & stretch) stop_mask |= 1ull << k;
+            int64_t& max_word = stats[tgx::kWsMaxWord * S + i];
+            if (inside)
+                max_word = (int64_t)longest;
+            else if (tgx::textstat_adds(longest))
+                max_word = std::max(max_word, (int64_t)longest);
+            for (uint32_t k = 0; k < tgx::kWordstatN; k++) {
+                if (k == tgx::kWsMaxWord || k == tgx::kWsStopMask) continue;
+                const uint64_t v = tgx::textstat_popc(ballots[k] & stretch);
+                if (inside)
+                    stats[k * S + i] = (int64_t)v;
+                else if (tgx::textstat_adds(v))
+                    stats[k * S + i] += (int64_t)v;
+            }
+            if (inside)
+                stats[tgx::kWsStopMask * S + i] = (int64_t)stop_mask;
+            else if (tgx::textstat_adds(stop_mask))
+                stats[tgx::kWsStopMask * S + i] |= (int64_t)stop_mask;
+            a = b + 1;
+        }
+    });
+}
+
+}  // namespace
+
+tgx_status tgx_word_stats_host(const uint8_t* text, const uint64_t* offs, uint64_t n_rows, uint64_t word_limit, const uint8_t* stop_bytes,
+                               const uint64_t* stop_offs, uint32_t n_stop, uint32_t flags, int64_t* stats, uint8_t* marks) {
+    const char* who = "tgx_word_stats_host";
+    tgx_status st = textstat_check_source_host(who, text, offs, n_rows);
+    if (st != TGX_OK) return st;
+    if ((st = layout_check_flags(who, flags, tgx::kWordstatChars | tgx::kWordstatFold)) != TGX_OK) return st;
+    std::vector<uint64_t> table(tgx::kWordstatStopWords * std::max<uint32_t>(std::min(n_stop, tgx::kWordstatMaxStop), 1u));
+    if (const char* why = tgx::wordstat_pack_table(stop_bytes, stop_offs, n_stop, flags, table.data())) return fail(TGX_ERR_INVALID, "%s: %s", who, why);
+    if (!stats && !marks) return fail(TGX_ERR_INVALID, "%s: stats and marks are both NULL", who);
+    if (n_rows == 0) return TGX_OK;
+    wordstat_host(text, offs, n_rows, word_limit, flags, table.data(), n_stop, stats, marks);
     return TGX_OK;
 }
 

@@ -380,6 +380,148 @@ def line_rows(corpus: "_lib.NativeCorpus"):
     return lines, torch.repeat_interleave(torch.arange(corpus.num_samples, dtype=torch.int64, device=dev), counts)
 
 
+# ---- per-row word statistics: the Gopher quality filters (csrc/wordstat.hip) ------------------------------------------------
+
+GOPHER_STOP_WORDS = _lib.GOPHER_STOP_WORDS
+
+
+class WordStats:
+    """What word_stats returns: `table`, [14, S] torch.int64 on the corpus's device, and a [S] view of it per statistic
+    (words, word_units, max_word, long_words, alpha_words, alpha_wide_words, hash, ellipsis, lines, bullet_lines,
+    ellipsis_lines, punct_lines, stop_words, stop_mask: include/tgx_words.h); `unit` ("char" or "byte") is what a word's
+    length is counted in; `stop_words`, the table's entries, bit k of stop_mask being entry k; `mask` is the [N] uint8
+    tensor of the bytes' marks (bit 0 a word start, bit 1 a word end, bit 2 the end of a stop word, bit 3 the last byte
+    of a line-leading bullet), or None when it was not asked for.  The shares are float64 with a denominator of at
+    least 1, so a row without a word or a line has 0."""
+
+    def __init__(self, table, unit: str, word_limit: int, stop_words=(), mask=None):
+        self.table, self.unit, self.word_limit, self.stop_words, self.mask = table, unit, int(word_limit), tuple(stop_words), mask
+        for k, name in enumerate(_lib.WORDSTAT_NAMES):
+            setattr(self, name, table[k])
+
+    def _share(self, count, of):
+        import torch
+        return count.to(torch.float64) / of.clamp(min=1).to(torch.float64)
+
+    @property
+    def mean_word(self):
+        """[S] float64: word_units / max(words, 1), the mean length of a row's words."""
+        return self._share(self.word_units, self.words)
+
+    @property
+    def alpha_frac(self):
+        """[S] float64: alpha_words / max(words, 1), the share of the words that hold an ASCII letter."""
+        return self._share(self.alpha_words, self.words)
+
+    @property
+    def alpha_wide_frac(self):
+        """[S] float64: alpha_wide_words / max(words, 1): an ASCII letter or any non-ASCII byte."""
+        return self._share(self.alpha_wide_words, self.words)
+
+    @property
+    def hash_ratio(self):
+        """[S] float64: hash / max(words, 1)."""
+        return self._share(self.hash, self.words)
+
+    @property
+    def ellipsis_ratio(self):
+        """[S] float64: ellipsis / max(words, 1)."""
+        return self._share(self.ellipsis, self.words)
+
+    @property
+    def bullet_frac(self):
+        """[S] float64: bullet_lines / max(lines, 1)."""
+        return self._share(self.bullet_lines, self.lines)
+
+    @property
+    def ellipsis_line_frac(self):
+        """[S] float64: ellipsis_lines / max(lines, 1)."""
+        return self._share(self.ellipsis_lines, self.lines)
+
+    @property
+    def punct_line_frac(self):
+        """[S] float64: punct_lines / max(lines, 1), the share of the lines that end in . ! ? or a double quote (C4,
+        FineWeb)."""
+        return self._share(self.punct_lines, self.lines)
+
+    @property
+    def stop_distinct(self):
+        """[S] int64: the popcount of stop_mask, how many different stop words the row holds."""
+        return _popcount63(self.stop_mask)
+
+
+def _popcount63(mask):
+    """the set bits among bits 0 .. 62 of every entry of an int64 tensor (a stop table has at most 63 entries)"""
+    import torch
+    bits = torch.arange(63, dtype=torch.int64, device=mask.device).reshape(-1, *([1] * mask.dim()))
+    return ((mask.unsqueeze(0) >> bits) & 1).sum(0)
+
+
+def word_stats(corpus: "_lib.NativeCorpus", word_limit: int = 20, stop_words=GOPHER_STOP_WORDS, unit: str = "char", fold_case: bool = True,
+               return_mask: bool = False) -> WordStats:
+    """-> a WordStats of the corpus's rows, computed on its device and queued on torch's current stream: per row the
+    words, the sum of their lengths, the longest and those longer than word_limit (lengths in `unit`: "char", a byte that
+    is no UTF-8 continuation byte, or "byte"), the words that hold a letter, the '#'s and ellipses, the lines and those
+    that begin with a bullet, end with an ellipsis or end with terminal punctuation, and the occurrences and the set of
+    the stop words (at most 63 words of 1 to 8 bytes, bytes or str; with fold_case the text's A-Z match a-z, and an entry
+    must then hold no A-Z).  With return_mask also the [N] uint8 marks of the bytes.
+
+    A word is a maximal run of bytes that are no white space (0x20, 0x09 .. 0x0D: what bytes.split() splits on; non-ASCII
+    spaces are ordinary bytes) within a row.  Gopher's words come from a word tokenizer, these from white space: "end."
+    is one word here and punctuation counts into its length.  The letter test is ASCII (alpha_words) or ASCII plus any
+    non-ASCII byte (alpha_wide_words), not Unicode's classes.  Trailing spaces at a line's end are not trimmed before the
+    ellipsis and punctuation tests."""
+    import torch
+    dev = _device_of(torch, corpus)
+    _lib.wordstat_flags(unit, fold_case)  # (raises on an unknown unit before anything is allocated)
+    stop_words = tuple(stop_words or ())
+    S, N = corpus.num_samples, corpus.num_bytes
+    table = torch.empty((_lib.WORDSTAT_N, S), dtype=torch.int64, device=dev)
+    marks = torch.empty((N,), dtype=torch.uint8, device=dev) if return_mask else None
+    spare = torch.empty(1, dtype=torch.int64, device=dev)  # (no row: the pointer still says that the table is asked for)
+    corpus.word_stats((table if S else spare).data_ptr(), marks.data_ptr() if return_mask and N else 0, word_limit, stop_words, unit, fold_case,
+                      stream=torch.cuda.current_stream(dev).cuda_stream)
+    return WordStats(table, unit, word_limit, stop_words, marks)
+
+
+def gopher_quality_keep(table, min_words: int = 50, max_words: int = 100_000, mean_word=(3, 10), max_symbol_ratio: float = 0.1,
+                        max_bullet_lines: float = 0.9, max_ellipsis_lines: float = 0.3, min_alpha_words: float = 0.8, min_stop_words: int = 2,
+                        wide_is_alpha: bool = True):
+    """-> [S] torch.bool, the rows that pass Gopher's quality rules, from a [14, S] int64 table of word_stats on any
+    device.  A row is kept iff min_words <= words <= max_words, mean_word[0] · words <= word_units <= mean_word[1] · words,
+    hash <= max_symbol_ratio · words and ellipsis <= max_symbol_ratio · words, bullet_lines <= max_bullet_lines · lines,
+    ellipsis_lines <= max_ellipsis_lines · lines, the words with a letter >= min_alpha_words · words (alpha_wide_words
+    with wide_is_alpha, which credits every non-ASCII byte as a letter, else alpha_words), and at least min_stop_words
+    different stop words occur.  The comparisons are division-free float64: a row exactly on a threshold is kept, and an
+    empty row fails min_words >= 1.  The defaults are Gopher's figures over white-space words, which are not Gopher's
+    tokenizer's words: the thresholds are the caller's to tune."""
+    import torch
+    f64 = torch.float64
+    d = dict(zip(_lib.WORDSTAT_NAMES, table))
+    words, lines = d["words"].to(f64), d["lines"].to(f64)
+    keep = (d["words"] >= int(min_words)) & (d["words"] <= int(max_words))
+    keep &= (d["word_units"].to(f64) >= float(mean_word[0]) * words) & (d["word_units"].to(f64) <= float(mean_word[1]) * words)
+    keep &= (d["hash"].to(f64) <= float(max_symbol_ratio) * words) & (d["ellipsis"].to(f64) <= float(max_symbol_ratio) * words)
+    keep &= d["bullet_lines"].to(f64) <= float(max_bullet_lines) * lines
+    keep &= d["ellipsis_lines"].to(f64) <= float(max_ellipsis_lines) * lines
+    keep &= d["alpha_wide_words" if wide_is_alpha else "alpha_words"].to(f64) >= float(min_alpha_words) * words
+    keep &= _popcount63(d["stop_mask"]) >= int(min_stop_words)
+    return keep
+
+
+def gopher_quality_rows(corpus: "_lib.NativeCorpus", min_words: int = 50, max_words: int = 100_000, mean_word=(3, 10), max_symbol_ratio: float = 0.1,
+                        max_bullet_lines: float = 0.9, max_ellipsis_lines: float = 0.3, min_alpha_words: float = 0.8, min_stop_words: int = 2,
+                        wide_is_alpha: bool = True, stop_words=GOPHER_STOP_WORDS, unit: str = "char", fold_case: bool = True):
+    """-> torch.int64 indices, ascending, of the rows that pass gopher_quality_keep over word_stats of the corpus: what
+    `select` takes to drop the others (of a corpus and, with the same indices, of its encoded result).  The words come
+    from white space, not from Gopher's word tokenizer, the letter test is ASCII plus (with wide_is_alpha) any non-ASCII
+    byte, and the thresholds are the caller's to tune."""
+    s = word_stats(corpus, stop_words=stop_words, unit=unit, fold_case=fold_case)
+    keep = gopher_quality_keep(s.table, min_words, max_words, mean_word, max_symbol_ratio, max_bullet_lines, max_ellipsis_lines, min_alpha_words,
+                               min_stop_words, wide_is_alpha)
+    return keep.nonzero().reshape(-1)
+
+
 # ---- repeated n-grams within a row: the Gopher repetition filters (csrc/repeat.hip) ---------------------------------------
 
 GOPHER_TOP = ((2, .20), (3, .18), (4, .16))
