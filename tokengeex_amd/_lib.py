@@ -226,6 +226,18 @@ WORD_SYMBOLS = {
     "tgx_wordstat_last_times": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_float), _i]),
 }
 
+# every exported symbol of include/tgx_phrases.h, a header of its own in the same way: bound and checked at import too
+PHRASE_SYMBOLS = {
+    "tgx_phraseset_create": (_i, [_i, _vp, _vp, _u32, _u32, _u32, _vp]),
+    "tgx_phraseset_info": (_i, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
+    "tgx_phraseset_free": (None, [_vp]),
+    "tgx_corpus_phrase_hits_device": (_i, [_vp, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "tgx_result_phrase_hits_device": (_i, [_vp, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "tgx_phrase_hits_host": (_i, [_vp, _u32, _vp, _u64, _vp, _vp, _u32, _u32, _vp, _vp, _vp]),
+    "tgx_phrase_last_times": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_float), _i]),
+}
+
 
 class TokenGeeXError(Exception):
     """tokengeex.TokenGeeXError — bindings/python/src/lib.rs:9,33-37; carries the
@@ -271,7 +283,7 @@ def _load() -> C.CDLL:
             "Build it with `python tokengeex_amd/build.py`.")
     _share_torch_hip_runtime()
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(WORD_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(WORD_SYMBOLS.items()) + list(PHRASE_SYMBOLS.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args
@@ -972,6 +984,97 @@ class NativeGramSet:
         return out
 
 
+# ---- literal phrase matching (include/tgx_phrases.h; csrc/phrase.hip, csrc/phrase.h) ----
+PHRASE_FOLD_CASE, PHRASE_WHOLE_WORD = 1, 2
+PHRASE_MAX_LEN, PHRASE_MAX_BYTES = 255, 256
+PHRASE_KINDS = {1: "bytes", 4: "ids"}
+
+
+def phrase_flags(fold_case: bool, whole_word: bool) -> int:
+    """-> the flags of tgx_phraseset_create."""
+    return (PHRASE_FOLD_CASE if fold_case else 0) | (PHRASE_WHOLE_WORD if whole_word else 0)
+
+
+def _phrase_table(phrases, kind: str):
+    """phrases as list[bytes | str] (a str as UTF-8) for kind "bytes", list[list[int]] for kind "ids" -> (flat u8 or u32,
+    offs u64 in elements, n, elem_bytes) of the ABI; the library checks the lengths"""
+    if kind not in ("bytes", "ids"):
+        raise ValueError(f"kind must be 'bytes' or 'ids' (got {kind!r})")
+    if kind == "bytes":
+        items = [w.encode("utf-8") if isinstance(w, str) else bytes(w) for w in phrases]
+        flat, offs = pack(items)
+        return np.ascontiguousarray(flat), offs, len(items), 1
+    items = [np.asarray(w, dtype=np.int64).reshape(-1) for w in phrases]
+    for w in items:
+        if w.size and (int(w.min()) < 0 or int(w.max()) > 0xFFFFFFFF):
+            raise ValueError("an id of a phrase is not in 0 .. 2^32-1")
+    offs = np.zeros(len(items) + 1, dtype=np.uint64)
+    if items:
+        np.cumsum(np.fromiter((w.size for w in items), dtype=np.uint64, count=len(items)), out=offs[1:])
+    flat = np.concatenate(items).astype(np.uint32) if items else np.zeros(0, np.uint32)
+    return np.ascontiguousarray(flat), offs, len(items), 4
+
+
+def phrase_hits_host(data: np.ndarray, offs: np.ndarray, phrases, fold_case: bool = False, whole_word: bool = False):
+    """Host twin of phrase_hits (tgx_phrase_hits_host: the same table, the kernel's chunks, filter, walk and store / add
+    rule through the same header, no device) over data u8[N] or u32[T] and offsets u64[S+1] in elements ->
+    (count int64[S], longest uint8[n_elems], per_phrase int64[P])."""
+    data, offs, n = _gram_source(data, offs)
+    pflat, poffs, n_phr, eb = _phrase_table(phrases, PHRASE_KINDS[data.dtype.itemsize])
+    count = np.full(n, -7, np.int64)
+    longest = np.full(data.size, 7, np.uint8)
+    per = np.full(n_phr, -7, np.int64)
+    keep = np.zeros(1, np.int64), np.zeros(1, np.uint8), np.zeros(1, np.int64)   # (never NULL: all outputs are asked for)
+    check(lib.tgx_phrase_hits_host(ptr(data) if data.size else None, eb, ptr(offs) if offs.size else None, n, ptr(pflat) if pflat.size else None,
+                                   ptr(poffs), n_phr, phrase_flags(fold_case, whole_word), ptr(count if n else keep[0]),
+                                   ptr(longest if longest.size else keep[1]), ptr(per if n_phr else keep[2])))
+    return count, longest, per
+
+
+def phrase_last_times() -> dict[str, float]:
+    """Device time in ms of each stage of the calling thread's last phrase_hits call (tgx_phrase_last_times)."""
+    names = (C.c_char_p * 8)()
+    ms = (C.c_float * 8)()
+    n = lib.tgx_phrase_last_times(names, ms, 8)
+    return {names[i].decode(): float(ms[i]) for i in range(n)}
+
+
+class NativePhraseSet:
+    """Owns a tgx_phraseset: the trie of a list of literal phrases in HBM with its first-level filter (csrc/phrase.hip).
+    Read-only after creation: calls and threads share it."""
+
+    def __init__(self, phrases, kind: str = "bytes", fold_case: bool = False, whole_word: bool = False, device: int = 0):
+        pflat, poffs, n_phr, eb = _phrase_table(phrases, kind)
+        h = C.c_void_p()
+        check(lib.tgx_phraseset_create(int(device), ptr(pflat) if pflat.size else None, ptr(poffs), n_phr, eb, phrase_flags(fold_case, whole_word),
+                                       C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        self.free()
+
+    def free(self):
+        if getattr(self, "_h", None):
+            lib.tgx_phraseset_free(self._h)
+            self._h = None
+
+    def info(self) -> dict:
+        """The fields of tgx_phraseset_info."""
+        n, d, eb, fl, ml, dev, tb = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_int(), C.c_uint64()
+        check(lib.tgx_phraseset_info(self._h, C.byref(n), C.byref(d), C.byref(eb), C.byref(fl), C.byref(ml), C.byref(dev), C.byref(tb)))
+        return {"size": n.value, "distinct": d.value, "elem_bytes": eb.value, "flags": fl.value, "max_len": ml.value, "device": dev.value,
+                "table_bytes": tb.value}
+
+    size = property(lambda self: self.info()["size"])
+    distinct = property(lambda self: self.info()["distinct"])
+    kind = property(lambda self: PHRASE_KINDS[self.info()["elem_bytes"]])
+    fold_case = property(lambda self: bool(self.info()["flags"] & PHRASE_FOLD_CASE))
+    whole_word = property(lambda self: bool(self.info()["flags"] & PHRASE_WHOLE_WORD))
+    max_len = property(lambda self: self.info()["max_len"])
+    device = property(lambda self: self.info()["device"])
+    table_bytes = property(lambda self: self.info()["table_bytes"])
+
+
 def front_host(flat: np.ndarray, offs: np.ndarray, specials: list[bytes], crlf: bool):
     """Host twin of NativeCorpus.split_specials (tgx_front_host: the kernels' index arithmetic, no device) over a packed
     batch (offs from 0) -> (seg_offs u64[S+1], seg_special i32[K], segments' flat, segments' offsets u64[E+1]): the plan of
@@ -1560,6 +1663,12 @@ class NativeResult:
         tgx_result_gram_hits_device)."""
         check(lib.tgx_result_gram_hits_device(self._h, grams._h, 0, stream or None, d_count or None, d_mask or None))
 
+    def phrase_hits(self, phrases: "NativePhraseSet", d_count: int = 0, d_longest: int = 0, d_per_phrase: int = 0, *, stream: int = 0) -> None:
+        """Per row the occurrences of the phrases of `phrases`, as int64[S], per id the longest occurrence that begins
+        there, as u8[T], and per phrase its occurrences, as int64[P], into caller-owned device memory (raw integer
+        pointers, any may be 0, not all; tgx_result_phrase_hits_device)."""
+        check(lib.tgx_result_phrase_hits_device(self._h, phrases._h, 0, stream or None, d_count or None, d_longest or None, d_per_phrase or None))
+
     def pad_host(self, row_len: int, pad_id: int, **kw) -> dict:
         """layout_pad_host over the ids and offsets copied to the host."""
         return layout_pad_host(self.ids(), self.offsets(), row_len, pad_id, **kw)
@@ -1770,6 +1879,12 @@ class NativeCorpus:
         is one, as u8[N], into caller-owned device memory (either may be 0; tgx_corpus_gram_hits_device).  This corpus is
         only read."""
         check(lib.tgx_corpus_gram_hits_device(self._h, grams._h, 0, stream or None, d_count or None, d_mask or None))
+
+    def phrase_hits(self, phrases: "NativePhraseSet", d_count: int = 0, d_longest: int = 0, d_per_phrase: int = 0, *, stream: int = 0) -> None:
+        """Per sample the occurrences of the phrases of `phrases`, as int64[S], per byte the longest occurrence that
+        begins there, as u8[N], and per phrase its occurrences, as int64[P], into caller-owned device memory (any may be
+        0, not all; tgx_corpus_phrase_hits_device).  This corpus is only read."""
+        check(lib.tgx_corpus_phrase_hits_device(self._h, phrases._h, 0, stream or None, d_count or None, d_longest or None, d_per_phrase or None))
 
     def repeat_stats(self, width: int, seed: int = 0, d_stats: int = 0, d_mask: int = 0, *, stream: int = 0) -> None:
         """Per sample the repetition statistics of its n-grams of `width` bytes, as int64[6, S], and per byte whether a

@@ -15,8 +15,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libtgx.so")
-SOURCES = ["kernels.hip", "estep.hip", "encode2.hip", "encode4l.hip", "encode5.hip", "estep4.hip", "estep4l.hip", "estep7.hip", "cuts.hip", "pairs.hip", "generate.hip", "sample.hip", "stats.hip", "nbest.hip", "layout.hip", "assemble.hip", "fim.hip", "select.hip", "dedup.hip", "minhash.hip", "gram.hip", "repeat.hip", "textstat.hip", "wordstat.hip", "decode.hip", "spans.hip", "front.hip", "norm.hip", "tgx_api.cpp", "encode_pass.cpp", "estep_pass.cpp", "lattice_pass.cpp", "result_ops.cpp", "corpus_ops.cpp", "minhash_ops.cpp", "gram_ops.cpp", "repeat_ops.cpp", "textstat_ops.cpp", "wordstat_ops.cpp", "host_twins.cpp", "trie_build.cpp", "prune_host.cpp", "frontback.cpp", "unicode_norm.cpp"]
-HEADERS = ["api_internal.h", "device_internal.h", "pass_internal.h", "kernels.h", "sample.h", "stats.h", "nbest.h", "layout.h", "assemble.h", "fim.h", "select.h", "dedup.h", "minhash.h", "gram.h", "gram_walk.h", "repeat.h", "shingle_load.h", "textstat.h", "textstat_walk.h", "wordstat.h", "decode.h", "spans.h", "front.h", "norm.h", "device_common.h", "lattice_walk.h", "tile_fill.h", "scan_helpers.h", "lean_gate.h", "ids_in_place.h", "encode_split.h", "encode5_layout.h", "top_table.h", "trace_body.h", "trie_build.h", "unicode_tables.h", os.path.join("..", "..", "include", "tgx.h"), os.path.join("..", "..", "include", "tgx_words.h")]
+SOURCES = ["kernels.hip", "estep.hip", "encode2.hip", "encode4l.hip", "encode5.hip", "estep4.hip", "estep4l.hip", "estep7.hip", "cuts.hip", "pairs.hip", "generate.hip", "sample.hip", "stats.hip", "nbest.hip", "layout.hip", "assemble.hip", "fim.hip", "select.hip", "dedup.hip", "minhash.hip", "gram.hip", "repeat.hip", "textstat.hip", "wordstat.hip", "phrase.hip", "decode.hip", "spans.hip", "front.hip", "norm.hip", "tgx_api.cpp", "encode_pass.cpp", "estep_pass.cpp", "lattice_pass.cpp", "result_ops.cpp", "corpus_ops.cpp", "minhash_ops.cpp", "gram_ops.cpp", "repeat_ops.cpp", "textstat_ops.cpp", "wordstat_ops.cpp", "phrase_ops.cpp", "host_twins.cpp", "trie_build.cpp", "prune_host.cpp", "frontback.cpp", "unicode_norm.cpp"]
+HEADERS = ["api_internal.h", "device_internal.h", "pass_internal.h", "kernels.h", "sample.h", "stats.h", "nbest.h", "layout.h", "assemble.h", "fim.h", "select.h", "dedup.h", "minhash.h", "gram.h", "gram_walk.h", "repeat.h", "shingle_load.h", "textstat.h", "textstat_walk.h", "wordstat.h", "phrase.h", "decode.h", "spans.h", "front.h", "norm.h", "device_common.h", "lattice_walk.h", "tile_fill.h", "scan_helpers.h", "lean_gate.h", "ids_in_place.h", "encode_split.h", "encode5_layout.h", "top_table.h", "trace_body.h", "trie_build.h", "unicode_tables.h", os.path.join("..", "..", "include", "tgx.h"), os.path.join("..", "..", "include", "tgx_words.h"), os.path.join("..", "..", "include", "tgx_phrases.h")]
 ARCH = "gfx950"
 
 

@@ -1,5 +1,5 @@
 // The *_host twins of the result-side device entry points (include/tgx.h): tgx_layout_pad_host, tgx_layout_pack_host,
-// tgx_layout_windows_host, tgx_assemble_host, tgx_fim_host, tgx_select_host, tgx_select_text_host, tgx_shuffled_rows_host, tgx_first_equal_host, tgx_minhash_host, tgx_minhash_bands_host, tgx_minhash_near_first_host, tgx_gram_keys_host, tgx_gram_hits_host, tgx_gram_contains_host, tgx_repeat_stats_host, tgx_text_stats_host, tgx_lines_host, tgx_word_stats_host (include/tgx_words.h), tgx_decode_rows_host, tgx_spans_host, tgx_window_spans_host, tgx_front_host,
+// tgx_layout_windows_host, tgx_assemble_host, tgx_fim_host, tgx_select_host, tgx_select_text_host, tgx_shuffled_rows_host, tgx_first_equal_host, tgx_minhash_host, tgx_minhash_bands_host, tgx_minhash_near_first_host, tgx_gram_keys_host, tgx_gram_hits_host, tgx_gram_contains_host, tgx_repeat_stats_host, tgx_text_stats_host, tgx_lines_host, tgx_word_stats_host (include/tgx_words.h), tgx_phrase_hits_host (include/tgx_phrases.h), tgx_decode_rows_host, tgx_spans_host, tgx_window_spans_host, tgx_front_host,
 // tgx_normalize_host and tgx_lattice_stats_host, and the
 // argument checks they share with the device entry points of tgx_api.cpp.  A twin goes through the same index arithmetic as its kernels (layout.h, assemble.h,
 // fim.h, select.h, dedup.h, minhash.h, gram.h, repeat.h, textstat.h, wordstat.h, decode.h, spans.h, front.h, norm.h) on host memory.  Nothing in this file calls a HIP function, so it builds and runs without the
@@ -22,12 +22,14 @@
 #include "layout.h"
 #include "minhash.h"
 #include "norm.h"
+#include "phrase.h"
 #include "repeat.h"
 #include "select.h"
 #include "spans.h"
 #include "textstat.h"
 #include "unicode_tables.h"
 #include "wordstat.h"
+#include "../../include/tgx_phrases.h"
 #include "../../include/tgx_words.h"
 
 using namespace tgx::host;
@@ -982,6 +984,72 @@ tgx_status tgx_gram_contains_host(const uint64_t* keys, uint64_t n_keys, const u
     if (st != TGX_OK) return st;
     if (n_probes && (!probes || !out)) return fail(TGX_ERR_INVALID, "%s: %s is NULL", who, probes ? "out" : "probes");
     for (uint64_t p = 0; p < n_probes; p++) out[p] = tgx::gram_contains(sorted.data(), dir.data(), bits, probes[p]) ? 1 : 0;
+    return TGX_OK;
+}
+
+// ---- literal phrase matching (include/tgx_phrases.h) --------------------------------------------
+
+tgx_status tgx_phrase_hits_host(const void* data_, uint32_t elem_bytes, const uint64_t* offs, uint64_t n_rows, const void* phrases,
+                                const uint64_t* phrase_offs, uint32_t n_phrases, uint32_t flags, int64_t* count, uint8_t* longest,
+                                int64_t* per_phrase) {
+    const char* who = "tgx_phrase_hits_host";
+    tgx::PhraseTable table;
+    const char* why = nullptr;
+    const tgx::PhraseBuild built = tgx::phrase_build_table(phrases, phrase_offs, n_phrases, elem_bytes, flags, &table, &why);
+    if (built != tgx::kPhraseOk) return fail(built == tgx::kPhraseInvalid ? TGX_ERR_INVALID : TGX_ERR_UNSUPPORTED, "%s: %s", who, why);
+    const tgx_status st = check_packed_list(who, "offs", "offsets", offs, n_rows, true);
+    if (st != TGX_OK) return st;
+    if (n_rows >= 0xFFFFFFFFull) return fail(TGX_ERR_UNSUPPORTED, "%s: more than 2^32-1 rows", who);
+    if (offs[n_rows] && !data_) return fail(TGX_ERR_INVALID, "%s: data is NULL", who);
+    if (!count && !longest && !per_phrase) return fail(TGX_ERR_INVALID, "%s: count, longest and per_phrase are all NULL", who);
+    const uint8_t* data = static_cast<const uint8_t*>(data_);
+    const uint64_t S = n_rows, M = offs[S];
+    const uint32_t eb = elem_bytes, max_bytes = table.max_len * eb;
+    const bool fold = flags & tgx::kPhraseFoldCase, whole = flags & tgx::kPhraseWholeWord;
+    if (count) std::fill(count, count + S, 0);  // the launcher's pre-sets
+    if (per_phrase) std::fill(per_phrase, per_phrase + n_phrases, 0);
+    // a stretch of one row inside a chunk ends when the owner or the chunk changes: then the kernel's store / add rule
+    uint64_t hi = 0;
+    for (uint64_t t0 = 0; t0 < M; t0 += tgx::kGramTile) {
+        for (uint64_t c0 = t0; c0 < M && c0 < t0 + tgx::kGramTile; c0 += tgx::kGramChunk) {
+            const uint64_t c_last = tgx::tile_last(c0, tgx::kGramChunk, M);
+            const uint64_t lo = tgx::dedup_find_from(offs, hi, S - 1, c0);
+            hi = tgx::dedup_find_from(offs, lo, S - 1, c_last);
+            uint64_t cur_row = 0, n_hits = 0;
+            bool open = false;
+            auto flush = [&]() {
+                if (!open || !count) return;
+                if (tgx::gram_row_inside(offs, cur_row, c0))
+                    count[cur_row] = (int64_t)n_hits;
+                else if (tgx::gram_adds(n_hits))
+                    count[cur_row] += (int64_t)n_hits;
+            };
+            for (uint64_t pos = c0; pos <= c_last; pos++) {
+                const uint64_t row = tgx::pack_find_row(offs, 0, lo, hi, pos);
+                if (!open || row != cur_row) {
+                    flush();
+                    open = true;
+                    cur_row = row;
+                    n_hits = 0;
+                }
+                const uint64_t left = (offs[row + 1] - pos) * eb;
+                const uint32_t avail = left > max_bytes ? max_bytes + 1 : (uint32_t)left;
+                const uint8_t* s = data + pos * eb;
+                auto get = [&](uint32_t k) { return tgx::phrase_fold(s[k], fold); };
+                const uint32_t b0 = get(0), b1 = avail >= 2 ? get(1) : 0u;
+                bool go = tgx::phrase_filter_pass(table.filter.data(), b0, b1);
+                if (whole && go) go = pos == offs[row] || !tgx::phrase_word_byte(tgx::phrase_fold(s[-1], fold));
+                tgx::PhraseHit h = {0, 0};
+                if (go)
+                    h = tgx::phrase_walk(table.rec.data(), table.root_base, eb, avail, max_bytes, whole, get, [&](uint32_t p) {
+                        if (per_phrase) per_phrase[p]++;
+                    });
+                if (longest) longest[pos] = (uint8_t)h.longest;
+                n_hits += h.count;
+            }
+            flush();
+        }
+    }
     return TGX_OK;
 }
 

@@ -524,6 +524,90 @@ def gopher_quality_rows(corpus: "_lib.NativeCorpus", min_words: int = 50, max_wo
 
 # ---- repeated n-grams within a row: the Gopher repetition filters (csrc/repeat.hip) ---------------------------------------
 
+# ---- literal phrase matching: blocklists and keyword filters (csrc/phrase.hip) ---------------------------------------------
+
+AUTOGENERATED = ("auto-generated", "autogenerated", "automatically generated", "generated automatically", "this file is generated")
+
+
+def phrase_set(phrases, *, kind: str = "bytes", fold_case: bool = False, whole_word: bool = False, device: int = 0):
+    """-> a NativePhraseSet on `device`: a trie in device memory over a list of literal phrases, handed to phrase_hits.
+    kind "bytes": list[bytes | str] (a str as UTF-8), each of 1 to 255 bytes, for a NativeCorpus; kind "ids":
+    list[list[int]], each of 1 to 64 ids, for a NativeResult.  fold_case lowers A-Z in the phrases and in the text (ASCII
+    only); whole_word asks that the bytes on either side of an occurrence, inside its row, are no word bytes
+    ([A-Za-z0-9_] and every byte >= 0x80); both need kind "bytes".  Phrases equal after folding are one phrase under
+    the lowest index.  It carries .size, .distinct, .kind, .max_len, .device and .free()."""
+    return _lib.NativePhraseSet(phrases, kind, fold_case, whole_word, int(device))
+
+
+def phrase_hits(obj, phrases, return_longest: bool = False, return_per_phrase: bool = False):
+    """-> [S] torch.int64 on obj's device: per row the occurrences (start, phrase) of the phrases of `phrases` (a
+    NativePhraseSet of obj's kind), queued on torch's current stream.  Occurrences may overlap and none crosses a row's
+    end.  With return_longest also [n_elems] torch.uint8, the length of the longest occurrence that begins at each
+    element (0: none); with return_per_phrase also [P] torch.int64, the occurrences of each phrase over all rows.  The
+    extras follow the counts in that order.  Matching is exact, unlike gram_hits' keys."""
+    import torch
+    dev = _device_of(torch, obj)
+    n_elems = obj.num_tokens if isinstance(obj, _lib.NativeResult) else obj.num_bytes
+    count = torch.empty((obj.num_samples,), dtype=torch.int64, device=dev)
+    longest = torch.empty((n_elems,), dtype=torch.uint8, device=dev) if return_longest else None
+    per = torch.empty((phrases.size,), dtype=torch.int64, device=dev) if return_per_phrase else None
+    spare = torch.empty(1, dtype=torch.int64, device=dev)  # (no row: the pointer still says that the counts are asked for)
+    obj.phrase_hits(phrases, (count if count.numel() else spare).data_ptr(), longest.data_ptr() if return_longest and n_elems else 0,
+                    per.data_ptr() if return_per_phrase and per.numel() else 0, stream=torch.cuda.current_stream(dev).cuda_stream)
+    out = (count,) + ((longest,) if return_longest else ()) + ((per,) if return_per_phrase else ())
+    return out if len(out) > 1 else count
+
+
+def phrase_rows(obj, phrases, max_hits: int = 0):
+    """-> torch.int64 indices, ascending, of the rows of obj with at most max_hits occurrences of the phrases: what `select`
+    takes to drop the others (of a corpus and, with the same indices, of its encoded result)."""
+    return (phrase_hits(obj, phrases) <= int(max_hits)).nonzero().reshape(-1)
+
+
+def phrase_cover(longest):
+    """Plain torch, on any device: `longest` [N] uint8 of phrase_hits -> [N] bool, True for the elements inside some
+    occurrence: cummax(e + longest[e]) > e over the flat array, which is right across rows because no occurrence crosses
+    a row's end.  For redaction, or the share of a row's bytes in blocked phrases."""
+    import torch
+    n = longest.shape[0]
+    at = torch.arange(n, dtype=torch.int64, device=longest.device)
+    if n == 0:
+        return at.to(torch.bool)
+    return torch.cummax(at + longest.to(torch.int64), 0).values > at
+
+
+def head_lines_keep(line_row, line_hits, n_rows: int, head_lines: int = 5):
+    """The rule of autogenerated_rows alone, on tensors of any device: line_row [n_lines] int64 (ascending: the row of
+    every line), line_hits [n_lines] int64 (the occurrences in every line) -> [n_rows] bool, False for a row with an
+    occurrence in one of its first head_lines lines."""
+    import torch
+    n_lines, n_rows = line_row.shape[0], int(n_rows)
+    lines_of = torch.zeros(n_rows, dtype=torch.int64, device=line_row.device).scatter_add_(0, line_row, torch.ones_like(line_row))
+    first = torch.cumsum(lines_of, 0) - lines_of
+    in_row = torch.arange(n_lines, dtype=torch.int64, device=line_row.device) - first[line_row]
+    bad = ((in_row < int(head_lines)) & (line_hits > 0)).to(torch.int64)
+    return torch.zeros(n_rows, dtype=torch.int64, device=line_row.device).scatter_add_(0, line_row, bad) == 0
+
+
+def autogenerated_rows(corpus: "_lib.NativeCorpus", head_lines: int = 5, phrases=AUTOGENERATED):
+    """-> torch.int64 indices, ascending, of the rows with none of `phrases` in their first head_lines lines, matched with
+    A-Z lowered: what `select` takes to drop the files that say they were generated, as the BigCode (Stack / StarCoder)
+    filter does.  The default list is that filter's: "auto-generated", "autogenerated", "automatically generated",
+    "generated automatically", "this file is generated".  A composition of line_rows, phrase_hits of the lines and torch,
+    no kernel of its own.  Where it differs from the script: a line here ends at '\\n' only (line_rows), where Python's
+    splitlines also ends one at '\\r', form feed and the Unicode line separators, and the fold is ASCII, where str.lower
+    also lowers other scripts (the keywords are ASCII, so only text such as a Kelvin sign for 'k' could differ)."""
+    lines, line_row = line_rows(corpus)
+    ps = phrases if isinstance(phrases, _lib.NativePhraseSet) else phrase_set(list(phrases), fold_case=True, device=corpus.device)
+    try:
+        hits = phrase_hits(lines, ps)
+        return head_lines_keep(line_row, hits, corpus.num_samples, head_lines).nonzero().reshape(-1)
+    finally:
+        lines.free()
+        if ps is not phrases:
+            ps.free()
+
+
 GOPHER_TOP = ((2, .20), (3, .18), (4, .16))
 GOPHER_DUP = ((5, .15), (6, .14), (7, .13), (8, .12), (9, .11), (10, .10))
 
