@@ -226,6 +226,14 @@ WORD_SYMBOLS = {
     "tgx_wordstat_last_times": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_float), _i]),
 }
 
+# every exported symbol of include/tgx_word_ids.h, a header of its own beside tgx_words.h: bound and checked at import too
+WORDS_SYMBOLS = {
+    "tgx_corpus_words": (_i, [_vp, _u32, _u64, _vp, _vp]),
+    "tgx_word_key": (_u64, [_vp, _u64, _u32, _u64]),
+    "tgx_words_host": (_i, [_vp, _vp, _u64, _u32, _u64, _vp, _u64, _vp, C.POINTER(C.c_uint64)]),
+    "tgx_words_last_times": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_float), _i]),
+}
+
 # every exported symbol of include/tgx_phrases.h, a header of its own in the same way: bound and checked at import too
 PHRASE_SYMBOLS = {
     "tgx_phraseset_create": (_i, [_i, _vp, _vp, _u32, _u32, _u32, _vp]),
@@ -283,7 +291,7 @@ def _load() -> C.CDLL:
             "Build it with `python tokengeex_amd/build.py`.")
     _share_torch_hip_runtime()
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(WORD_SYMBOLS.items()) + list(PHRASE_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(WORD_SYMBOLS.items()) + list(WORDS_SYMBOLS.items()) + list(PHRASE_SYMBOLS.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args
@@ -879,6 +887,49 @@ def wordstat_last_times() -> dict[str, float]:
     names = (C.c_char_p * 8)()
     ms = (C.c_float * 8)()
     n = lib.tgx_wordstat_last_times(names, ms, 8)
+    return {names[i].decode(): float(ms[i]) for i in range(n)}
+
+
+# ---- word ids: a corpus's words as rows of a result (include/tgx_word_ids.h; csrc/words.hip, csrc/words.h) ----
+WORDS_FOLD = 1
+
+
+def words_flags(fold_case: bool) -> int:
+    """whether A-Z are lowered before a word is hashed -> the flags of tgx_corpus_words"""
+    return WORDS_FOLD if fold_case else 0
+
+
+def word_key(word, fold_case: bool = True, seed: int = 0) -> int:
+    """The 64-bit key of `word` (bytes, or str as UTF-8) taken as one word (tgx_word_key: on the host, no device); its id
+    is the key >> 33."""
+    b = np.frombuffer(word.encode("utf-8") if isinstance(word, str) else bytes(word), dtype=np.uint8)
+    return int(lib.tgx_word_key(ptr(b) if b.size else None, b.size, words_flags(fold_case), int(seed) & (2**64 - 1)))
+
+
+def words_host(text: np.ndarray, offs: np.ndarray, fold_case: bool = True, seed: int = 0):
+    """Host twin of NativeCorpus.words (tgx_words_host: the kernels' chunks, doubling steps, records, carry, emit rule and
+    offsets through the same header, no device) over text u8[N] and offsets u64[S+1] -> (ids u32[n_words], offsets
+    u64[S+1]).  Two calls: the first asks for the number of words."""
+    text = np.ascontiguousarray(text, dtype=np.uint8)
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    n = max(offs.shape[0] - 1, 0)
+    flags, seed = words_flags(fold_case), int(seed) & (2**64 - 1)
+    out_offs = np.zeros(n + 1, np.uint64)
+    nw = C.c_uint64()
+    args = (ptr(text) if text.size else None, ptr(offs) if offs.size else None, n, flags, seed)
+    st = lib.tgx_words_host(*args, None, 0, ptr(out_offs), C.byref(nw))
+    if st != OK and nw.value == 0:
+        check(st)
+    ids = np.empty(int(nw.value), np.uint32)
+    check(lib.tgx_words_host(*args, ptr(ids) if ids.size else None, ids.size, ptr(out_offs), C.byref(nw)))
+    return ids, out_offs
+
+
+def words_last_times() -> dict[str, float]:
+    """Device time in ms of each stage of the calling thread's last NativeCorpus.words (tgx_words_last_times)."""
+    names = (C.c_char_p * 8)()
+    ms = (C.c_float * 8)()
+    n = lib.tgx_words_last_times(names, ms, 8)
     return {names[i].decode(): float(ms[i]) for i in range(n)}
 
 
@@ -1906,6 +1957,14 @@ class NativeCorpus:
         sflat, soffs, n_stop = _stop_table(stop_words)
         check(lib.tgx_corpus_word_stats_device(self._h, int(word_limit), ptr(sflat) if sflat.size else None, ptr(soffs), n_stop,
                                                wordstat_flags(unit, fold_case), stream or None, d_stats or None, d_marks or None))
+
+    def words(self, flags: int = 0, seed: int = 0, stream: int = 0) -> "NativeResult":
+        """A new result on the corpus's device whose row i holds one id below 2^31 per white-space word of row i, in order
+        (tgx_corpus_words; include/tgx_word_ids.h has the id).  flags: 0 or WORDS_FOLD (A-Z lowered first).  This corpus is
+        only read."""
+        h = C.c_void_p()
+        check(lib.tgx_corpus_words(self._h, _u32_arg(flags, "flags"), int(seed) & (2**64 - 1), stream or None, C.byref(h)))
+        return NativeResult(h)
 
     def lines(self, *, stream: int = 0) -> "NativeCorpus":
         """A new resident corpus whose samples are the lines of this one, in order, each with its '\\n' if it has one

@@ -1,8 +1,8 @@
 // The *_host twins of the result-side device entry points (include/tgx.h): tgx_layout_pad_host, tgx_layout_pack_host,
-// tgx_layout_windows_host, tgx_assemble_host, tgx_fim_host, tgx_select_host, tgx_select_text_host, tgx_shuffled_rows_host, tgx_first_equal_host, tgx_minhash_host, tgx_minhash_bands_host, tgx_minhash_near_first_host, tgx_gram_keys_host, tgx_gram_hits_host, tgx_gram_contains_host, tgx_repeat_stats_host, tgx_text_stats_host, tgx_lines_host, tgx_word_stats_host (include/tgx_words.h), tgx_phrase_hits_host (include/tgx_phrases.h), tgx_decode_rows_host, tgx_spans_host, tgx_window_spans_host, tgx_front_host,
+// tgx_layout_windows_host, tgx_assemble_host, tgx_fim_host, tgx_select_host, tgx_select_text_host, tgx_shuffled_rows_host, tgx_first_equal_host, tgx_minhash_host, tgx_minhash_bands_host, tgx_minhash_near_first_host, tgx_gram_keys_host, tgx_gram_hits_host, tgx_gram_contains_host, tgx_repeat_stats_host, tgx_text_stats_host, tgx_lines_host, tgx_word_stats_host (include/tgx_words.h), tgx_words_host and tgx_word_key (include/tgx_word_ids.h), tgx_phrase_hits_host (include/tgx_phrases.h), tgx_decode_rows_host, tgx_spans_host, tgx_window_spans_host, tgx_front_host,
 // tgx_normalize_host and tgx_lattice_stats_host, and the
 // argument checks they share with the device entry points of tgx_api.cpp.  A twin goes through the same index arithmetic as its kernels (layout.h, assemble.h,
-// fim.h, select.h, dedup.h, minhash.h, gram.h, repeat.h, textstat.h, wordstat.h, decode.h, spans.h, front.h, norm.h) on host memory.  Nothing in this file calls a HIP function, so it builds and runs without the
+// fim.h, select.h, dedup.h, minhash.h, gram.h, repeat.h, textstat.h, wordstat.h, words.h, decode.h, spans.h, front.h, norm.h) on host memory.  Nothing in this file calls a HIP function, so it builds and runs without the
 // handles, the pool or a device.
 #define TGX_HOST_ONLY  // tile_fill.h: the host loop, no kernel side
 #include <algorithm>
@@ -28,8 +28,10 @@
 #include "spans.h"
 #include "textstat.h"
 #include "unicode_tables.h"
+#include "words.h"
 #include "wordstat.h"
 #include "../../include/tgx_phrases.h"
+#include "../../include/tgx_word_ids.h"
 #include "../../include/tgx_words.h"
 
 using namespace tgx::host;
@@ -1414,6 +1416,86 @@ tgx_status tgx_word_stats_host(const uint8_t* text, const uint64_t* offs, uint64
     if (!stats && !marks) return fail(TGX_ERR_INVALID, "%s: stats and marks are both NULL", who);
     if (n_rows == 0) return TGX_OK;
     wordstat_host(text, offs, n_rows, word_limit, flags, table.data(), n_stop, stats, marks);
+    return TGX_OK;
+}
+
+// ---- word ids (include/tgx_word_ids.h) -----------------------------------------------------------
+
+namespace {
+
+// What words.hip's two walking kernels compute of a chunk (words_chunk there): the masks and every lane's scanned h, the
+// six doubling steps taken lane by lane.  (Descending lanes: a step reads the lane below as it was before the step.)
+struct WordsChunkHost {
+    uint64_t resets = 0, nonspace = 0, ends = 0;
+    uint64_t h[tgx::kTextstatChunk] = {};
+};
+template <uint32_t D>
+void words_step_host(WordsChunkHost& c, const uint32_t* reach, uint32_t n_in) {
+    for (uint32_t l = n_in; l-- > D;) c.h[l] = tgx::words_step<D>(c.h[l], c.h[l - D], reach[l]);
+}
+WordsChunkHost words_chunk_host(const uint8_t* text, const uint64_t* offs, uint64_t c0, uint32_t n_in, const uint64_t* row, bool fold) {
+    WordsChunkHost c;
+    for (uint32_t l = 0; l < n_in; l++) {
+        const uint64_t p = c0 + l, bit = 1ull << l;
+        const bool space = tgx::textstat_is_space(text[p]);
+        if (space || p == offs[row[l]]) c.resets |= bit;
+        if (space) continue;
+        c.nonspace |= bit;
+        c.h[l] = tgx::words_digit(text[p], fold);
+        if (p + 1 == offs[row[l] + 1] || tgx::textstat_is_space(text[p + 1])) c.ends |= bit;
+    }
+    uint32_t reach[tgx::kTextstatChunk];
+    for (uint32_t l = 0; l < n_in; l++) reach[l] = tgx::words_reach(c.resets, l);
+    words_step_host<1>(c, reach, n_in);
+    words_step_host<2>(c, reach, n_in);
+    words_step_host<4>(c, reach, n_in);
+    words_step_host<8>(c, reach, n_in);
+    words_step_host<16>(c, reach, n_in);
+    words_step_host<32>(c, reach, n_in);
+    return c;
+}
+
+}  // namespace
+
+uint64_t tgx_word_key(const uint8_t* bytes, uint64_t n, uint32_t flags, uint64_t seed) {
+    return tgx::words_key_of(bytes, bytes ? n : 0, (flags & tgx::kWordsFold) != 0, seed);
+}
+
+tgx_status tgx_words_host(const uint8_t* text, const uint64_t* offs, uint64_t n_rows, uint32_t flags, uint64_t seed, uint32_t* out_ids, uint64_t ids_cap,
+                          uint64_t* out_offs, uint64_t* n_words) {
+    const char* who = "tgx_words_host";
+    if (n_words) *n_words = 0;
+    tgx_status st = textstat_check_source_host(who, text, offs, n_rows);
+    if (st != TGX_OK) return st;
+    if ((st = layout_check_flags(who, flags, tgx::kWordsFold)) != TGX_OK) return st;
+    if (!n_words || !out_offs) return fail(TGX_ERR_INVALID, "%s: %s is NULL", who, n_words ? "out_offs" : "n_words");
+    const uint64_t S = n_rows, N = offs[S], n_chunks = (N + tgx::kTextstatChunk - 1) / tgx::kTextstatChunk;
+    const bool fold = (flags & tgx::kWordsFold) != 0;
+    // the first kernel's records, the identity behind them, and their exclusive scan as a fold
+    std::vector<tgx::WordsRec> rec(n_chunks + 1, tgx::words_identity()), carry(n_chunks + 1);
+    textstat_walk_host(text, offs, S, [&](uint64_t c0, uint32_t n_in, uint64_t, const uint64_t* row) {
+        const WordsChunkHost c = words_chunk_host(text, offs, c0, n_in, row, fold);
+        rec[c0 / tgx::kTextstatChunk] = tgx::words_record(c.resets, c.nonspace, c.ends, c.h[n_in - 1], tgx::words_pow(tgx::words_open_lanes(c.resets, n_in)));
+    });
+    tgx::WordsRec acc = tgx::words_identity();
+    for (uint64_t k = 0; k <= n_chunks; k++) {
+        carry[k] = acc;
+        acc = tgx::WordsCarryOp()(acc, rec[k]);
+    }
+    const uint64_t total = carry[n_chunks].ends;
+    *n_words = total;
+    if (total > tgx::kWordsMaxWords) return fail(TGX_ERR_UNSUPPORTED, "%s: 2^32-1 words or more", who);
+    if (ids_cap < total) return fail(TGX_ERR_INVALID, "%s: %llu words, room for %llu", who, (unsigned long long)total, (unsigned long long)ids_cap);
+    if (total && !out_ids) return fail(TGX_ERR_INVALID, "%s: out_ids is NULL", who);
+    const uint64_t t = tgx::words_seed(seed);
+    textstat_walk_host(text, offs, S, [&](uint64_t c0, uint32_t n_in, uint64_t, const uint64_t* row) {
+        const WordsChunkHost c = words_chunk_host(text, offs, c0, n_in, row, fold);
+        const tgx::WordsRec& cy = carry[c0 / tgx::kTextstatChunk];
+        for (uint32_t l = 0; l < n_in; l++)
+            if ((c.ends >> l) & 1ull)
+                out_ids[tgx::words_end_place(c.ends, l, cy)] = tgx::words_id(tgx::words_end_key(c.resets, c.nonspace, l, c.h[l], tgx::words_pow(l + 1), cy, t));
+    });
+    for (uint64_t k = 0; k <= S; k++) out_offs[k] = tgx::words_row_offset(text, offs, k, N, carry.data());
     return TGX_OK;
 }
 

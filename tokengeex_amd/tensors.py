@@ -522,6 +522,32 @@ def gopher_quality_rows(corpus: "_lib.NativeCorpus", min_words: int = 50, max_wo
     return keep.nonzero().reshape(-1)
 
 
+# ---- word ids: a corpus's words as rows of a result (csrc/words.hip) ---------------------------------------------------------
+
+def word_rows(corpus: "_lib.NativeCorpus", fold_case: bool = True, seed: int = 0) -> "_lib.NativeResult":
+    """-> a NativeResult on the corpus's device whose row i holds one id per white-space word of row i, in order, computed
+    on the device and queued on torch's current stream.  Every pass over a result then works on words:
+    repetition_rows(word_rows(corpus)) is Gopher's repetition rule over words, minhash(word_rows(corpus), 5) the word
+    5-gram shingles of MinHash dedup, gram_set(word_rows(eval_corpus), 13) 13-word decontamination, and
+    phrase_set([[word_id(w) for w in p.split()] for p in phrases], kind="ids") whole-word phrases; select, first_equal,
+    row_lengths (the rows' word counts) and to_padded take it too.
+
+    A word is what word_stats counts: a maximal run of bytes that are no white space (0x20, 0x09 .. 0x0D) within a row.
+    Its id, below 2^31 (the result's vocab_size), is the top 31 bits of a 64-bit hash of its bytes, seeded by `seed`; with
+    fold_case A-Z are lowered first, and nothing else is.  Equal words have equal ids; different words differ with the
+    probability of the hash, which is not robust against input made to collide.  Where each word starts and ends in the
+    text is word_stats(corpus, return_mask=True).mask (bit 0 a word start, bit 1 a word end), in the same order."""
+    import torch
+    dev = _device_of(torch, corpus)
+    return corpus.words(_lib.words_flags(fold_case), seed, stream=torch.cuda.current_stream(dev).cuda_stream)
+
+
+def word_id(word, fold_case: bool = True, seed: int = 0) -> int:
+    """-> the id that word_rows gives `word` (bytes, or str as UTF-8; taken as one word) under the same fold_case and seed:
+    computed on the host."""
+    return _lib.word_key(word, fold_case, seed) >> 33
+
+
 # ---- repeated n-grams within a row: the Gopher repetition filters (csrc/repeat.hip) ---------------------------------------
 
 # ---- literal phrase matching: blocklists and keyword filters (csrc/phrase.hip) ---------------------------------------------
@@ -701,8 +727,8 @@ def repetition_rows(obj, top=GOPHER_TOP, dup=GOPHER_DUP, literal: bool = False, 
     for some (w, limit) of `dup` (the share covered by repeated w-grams; with literal=True covered_all_frac, which
     counts the first occurrences too, the paper's literal reading, where the default is what a pipeline that deletes
     the repeats would delete).  One repeat_stats call per distinct width.  The defaults are Gopher's numbers; Gopher
-    counts word n-grams and characters where this counts elements of the source (token ids or bytes), so the
-    thresholds are the caller's to tune.  A width that the source's element size cannot take raises before anything is
+    counts word n-grams, and this counts elements of the source: repetition_rows(word_rows(corpus)) is the rule over
+    white-space words, while over token ids or bytes the thresholds are the caller's to tune.  A width that the source's element size cannot take raises before anything is
     queued."""
     import torch
     top, dup = tuple(top), tuple(dup)
