@@ -246,6 +246,13 @@ PHRASE_SYMBOLS = {
     "tgx_phrase_last_times": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_float), _i]),
 }
 
+# every exported symbol of include/tgx_patterns.h, a header of its own in the same way: bound and checked at import too
+PATTERN_SYMBOLS = {
+    "tgx_corpus_dfa_hits_device": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "tgx_dfa_hits_host": (_i, [_vp, _vp, _u64, _vp, _vp, _vp]),
+    "tgx_dfa_last_times": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_float), _i]),
+}
+
 
 class TokenGeeXError(Exception):
     """tokengeex.TokenGeeXError — bindings/python/src/lib.rs:9,33-37; carries the
@@ -291,7 +298,7 @@ def _load() -> C.CDLL:
             "Build it with `python tokengeex_amd/build.py`.")
     _share_torch_hip_runtime()
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(WORD_SYMBOLS.items()) + list(WORDS_SYMBOLS.items()) + list(PHRASE_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(WORD_SYMBOLS.items()) + list(WORDS_SYMBOLS.items()) + list(PHRASE_SYMBOLS.items()) + list(PATTERN_SYMBOLS.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args
@@ -1126,6 +1133,51 @@ class NativePhraseSet:
     table_bytes = property(lambda self: self.info()["table_bytes"])
 
 
+# ---- byte patterns as a DFA over every row (include/tgx_patterns.h; csrc/dfa.hip, csrc/dfa.h) ----
+DFA_MAX_STATES = 16
+
+
+class TgxDfa(C.Structure):
+    """tgx_dfa of include/tgx_patterns.h"""
+    _fields_ = [("n_states", C.c_uint32), ("start", C.c_uint32), ("next", (C.c_uint8 * DFA_MAX_STATES) * 256), ("tag", C.c_uint8 * DFA_MAX_STATES)]
+
+
+def dfa_struct(pat) -> TgxDfa:
+    """An automaton with .n_states, .start, .next (uint8 [256, 16]) and .tag (uint8 [16]), such as a
+    patterns.BytePattern, as the struct of the ABI.  The library checks it."""
+    d = TgxDfa()
+    d.n_states, d.start = int(pat.n_states), int(pat.start)
+    nxt, tag = np.ascontiguousarray(pat.next, dtype=np.uint8), np.ascontiguousarray(pat.tag, dtype=np.uint8)
+    if nxt.shape != (256, DFA_MAX_STATES) or tag.shape != (DFA_MAX_STATES,):
+        raise ValueError("an automaton's next is uint8 [256, 16] and its tag uint8 [16]")
+    C.memmove(d.next, nxt.ctypes.data, nxt.nbytes)
+    C.memmove(d.tag, tag.ctypes.data, tag.nbytes)
+    return d
+
+
+def dfa_hits_host(text: np.ndarray, offs: np.ndarray, pat):
+    """Host twin of NativeCorpus.dfa_hits (tgx_dfa_hits_host: the same maps, the kernels' chunks, doubling steps, records,
+    carry and store / add rule through the same header, no device) over text u8[N] and offsets u64[S+1] ->
+    (count int64[S], ends uint8[N])."""
+    text = np.ascontiguousarray(text, dtype=np.uint8)
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    n = max(offs.shape[0] - 1, 0)
+    count = np.full(n, -7, np.int64)
+    ends = np.full(text.size, 7, np.uint8)
+    keep = np.zeros(1, np.int64), np.zeros(1, np.uint8)   # (never NULL: both outputs are asked for)
+    check(lib.tgx_dfa_hits_host(ptr(text) if text.size else None, ptr(offs) if offs.size else None, n, C.byref(dfa_struct(pat)),
+                                ptr(count if n else keep[0]), ptr(ends if ends.size else keep[1])))
+    return count, ends
+
+
+def dfa_last_times() -> dict[str, float]:
+    """Device time in ms of each stage of the calling thread's last dfa_hits call (tgx_dfa_last_times)."""
+    names = (C.c_char_p * 8)()
+    ms = (C.c_float * 8)()
+    n = lib.tgx_dfa_last_times(names, ms, 8)
+    return {names[i].decode(): float(ms[i]) for i in range(n)}
+
+
 def front_host(flat: np.ndarray, offs: np.ndarray, specials: list[bytes], crlf: bool):
     """Host twin of NativeCorpus.split_specials (tgx_front_host: the kernels' index arithmetic, no device) over a packed
     batch (offs from 0) -> (seg_offs u64[S+1], seg_special i32[K], segments' flat, segments' offsets u64[E+1]): the plan of
@@ -1936,6 +1988,12 @@ class NativeCorpus:
         begins there, as u8[N], and per phrase its occurrences, as int64[P], into caller-owned device memory (any may be
         0, not all; tgx_corpus_phrase_hits_device).  This corpus is only read."""
         check(lib.tgx_corpus_phrase_hits_device(self._h, phrases._h, 0, stream or None, d_count or None, d_longest or None, d_per_phrase or None))
+
+    def dfa_hits(self, pat, d_count: int = 0, d_ends: int = 0, *, stream: int = 0) -> None:
+        """Per sample the bytes after which the automaton `pat` (a patterns.BytePattern, or anything dfa_struct takes) is in
+        a tagged state, every row beginning in its start state, as int64[S], and per byte that state's tag, as u8[N], into
+        caller-owned device memory (either may be 0, not both; tgx_corpus_dfa_hits_device).  This corpus is only read."""
+        check(lib.tgx_corpus_dfa_hits_device(self._h, C.byref(dfa_struct(pat)), d_count or None, d_ends or None, stream or None))
 
     def repeat_stats(self, width: int, seed: int = 0, d_stats: int = 0, d_mask: int = 0, *, stream: int = 0) -> None:
         """Per sample the repetition statistics of its n-grams of `width` bytes, as int64[6, S], and per byte whether a

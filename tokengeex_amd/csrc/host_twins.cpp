@@ -1,8 +1,8 @@
 // The *_host twins of the result-side device entry points (include/tgx.h): tgx_layout_pad_host, tgx_layout_pack_host,
-// tgx_layout_windows_host, tgx_assemble_host, tgx_fim_host, tgx_select_host, tgx_select_text_host, tgx_shuffled_rows_host, tgx_first_equal_host, tgx_minhash_host, tgx_minhash_bands_host, tgx_minhash_near_first_host, tgx_gram_keys_host, tgx_gram_hits_host, tgx_gram_contains_host, tgx_repeat_stats_host, tgx_text_stats_host, tgx_lines_host, tgx_word_stats_host (include/tgx_words.h), tgx_words_host and tgx_word_key (include/tgx_word_ids.h), tgx_phrase_hits_host (include/tgx_phrases.h), tgx_decode_rows_host, tgx_spans_host, tgx_window_spans_host, tgx_front_host,
+// tgx_layout_windows_host, tgx_assemble_host, tgx_fim_host, tgx_select_host, tgx_select_text_host, tgx_shuffled_rows_host, tgx_first_equal_host, tgx_minhash_host, tgx_minhash_bands_host, tgx_minhash_near_first_host, tgx_gram_keys_host, tgx_gram_hits_host, tgx_gram_contains_host, tgx_repeat_stats_host, tgx_text_stats_host, tgx_lines_host, tgx_word_stats_host (include/tgx_words.h), tgx_words_host and tgx_word_key (include/tgx_word_ids.h), tgx_phrase_hits_host (include/tgx_phrases.h), tgx_dfa_hits_host (include/tgx_patterns.h), tgx_decode_rows_host, tgx_spans_host, tgx_window_spans_host, tgx_front_host,
 // tgx_normalize_host and tgx_lattice_stats_host, and the
 // argument checks they share with the device entry points of tgx_api.cpp.  A twin goes through the same index arithmetic as its kernels (layout.h, assemble.h,
-// fim.h, select.h, dedup.h, minhash.h, gram.h, repeat.h, textstat.h, wordstat.h, words.h, decode.h, spans.h, front.h, norm.h) on host memory.  Nothing in this file calls a HIP function, so it builds and runs without the
+// fim.h, select.h, dedup.h, minhash.h, gram.h, repeat.h, textstat.h, wordstat.h, words.h, dfa.h, decode.h, spans.h, front.h, norm.h) on host memory.  Nothing in this file calls a HIP function, so it builds and runs without the
 // handles, the pool or a device.
 #define TGX_HOST_ONLY  // tile_fill.h: the host loop, no kernel side
 #include <algorithm>
@@ -16,6 +16,7 @@
 #include "assemble.h"
 #include "decode.h"
 #include "dedup.h"
+#include "dfa.h"
 #include "fim.h"
 #include "front.h"
 #include "gram.h"
@@ -30,6 +31,7 @@
 #include "unicode_tables.h"
 #include "words.h"
 #include "wordstat.h"
+#include "../../include/tgx_patterns.h"
 #include "../../include/tgx_phrases.h"
 #include "../../include/tgx_word_ids.h"
 #include "../../include/tgx_words.h"
@@ -1496,6 +1498,80 @@ tgx_status tgx_words_host(const uint8_t* text, const uint64_t* offs, uint64_t n_
                 out_ids[tgx::words_end_place(c.ends, l, cy)] = tgx::words_id(tgx::words_end_key(c.resets, c.nonspace, l, c.h[l], tgx::words_pow(l + 1), cy, t));
     });
     for (uint64_t k = 0; k <= S; k++) out_offs[k] = tgx::words_row_offset(text, offs, k, N, carry.data());
+    return TGX_OK;
+}
+
+// ---- a DFA over the bytes of every row (include/tgx_patterns.h) ----------------------------------
+
+namespace {
+
+// The twin of dfa.hip's two kernels and the scan between them: the chunks of textstat_walk_host, every lane's map and the
+// six doubling steps taken lane by lane (descending lanes: a step reads the lane below as it was before the step), the
+// records, the scan as a fold, and the second kernel with its store / add rule.  The source and the automaton have been
+// checked, S > 0; count and ends may each be NULL.
+template <uint32_t NS>
+void dfa_host(const uint8_t* text, const uint64_t* offs, uint64_t S, const tgx_dfa* dfa, int64_t* count, uint8_t* ends) {
+    using Map = tgx::DfaMap<NS>;
+    const uint64_t N = offs[S], n_chunks = (N + tgx::kTextstatChunk - 1) / tgx::kTextstatChunk;
+    const uint32_t start = dfa->start;
+    std::vector<uint64_t> table(tgx::kDfaTableWords<NS>);
+    tgx::dfa_build_table<NS>(dfa->n_states, dfa->next, dfa->tag, table.data());
+    const Map* maps = reinterpret_cast<const Map*>(table.data());
+    const uint8_t* tags = reinterpret_cast<const uint8_t*>(table.data() + tgx::kDfaMapWords<NS>);
+    auto chunk_of = [&](uint64_t c0, uint32_t n_in, const uint64_t* row, Map* m) {
+        for (uint32_t l = 0; l < n_in; l++) m[l] = tgx::dfa_lane_map<NS>(maps[text[c0 + l]], c0 + l == offs[row[l]], start);
+        for (uint32_t d = 1; d < tgx::kTextstatChunk; d <<= 1)
+            for (uint32_t l = n_in; l-- > d;) m[l] = tgx::dfa_compose<NS>(m[l - d], m[l]);
+    };
+    if (count) std::fill(count, count + S, 0);  // the launcher's pre-set
+    std::vector<Map> rec(n_chunks + 1, tgx::dfa_identity<NS>()), carry(n_chunks + 1);
+    textstat_walk_host(text, offs, S, [&](uint64_t c0, uint32_t n_in, uint64_t, const uint64_t* row) {
+        Map m[tgx::kTextstatChunk];
+        chunk_of(c0, n_in, row, m);
+        rec[c0 / tgx::kTextstatChunk] = m[n_in - 1];
+    });
+    Map acc = tgx::dfa_identity<NS>();  // the exclusive scan under DfaCarryOp
+    for (uint64_t k = 0; k <= n_chunks; k++) {
+        carry[k] = acc;
+        acc = tgx::DfaCarryOp<NS>()(acc, rec[k]);
+    }
+    textstat_walk_host(text, offs, S, [&](uint64_t c0, uint32_t n_in, uint64_t, const uint64_t* row) {
+        Map m[tgx::kTextstatChunk];
+        chunk_of(c0, n_in, row, m);
+        uint64_t tagged = 0;
+        for (uint32_t l = 0; l < n_in; l++) {
+            const uint8_t tag = tags[tgx::dfa_state<NS>(m[l], carry[c0 / tgx::kTextstatChunk], start)];
+            if (ends) ends[c0 + l] = tag;
+            if (tag) tagged |= 1ull << l;
+        }
+        if (!count) return;
+        for (uint32_t a = 0; a < n_in;) {  // the stretch [a, b] of one row
+            uint32_t b = a;
+            while (b + 1 < n_in && row[b + 1] == row[a]) b++;
+            const uint64_t i = row[a], v = tgx::textstat_popc(tagged & tgx::textstat_span(a, b));
+            if (tgx::textstat_row_inside(offs, i, c0))
+                count[i] = (int64_t)v;
+            else if (tgx::textstat_adds(v))
+                count[i] += (int64_t)v;
+            a = b + 1;
+        }
+    });
+}
+
+}  // namespace
+
+tgx_status tgx_dfa_hits_host(const uint8_t* text, const uint64_t* offs, uint64_t n_rows, const tgx_dfa* dfa, int64_t* count, uint8_t* ends) {
+    const char* who = "tgx_dfa_hits_host";
+    const tgx_status st = textstat_check_source_host(who, text, offs, n_rows);
+    if (st != TGX_OK) return st;
+    if (!dfa) return fail(TGX_ERR_INVALID, "%s: dfa is NULL", who);
+    if (const char* why = tgx::dfa_check(dfa->n_states, dfa->start, dfa->next, dfa->tag)) return fail(TGX_ERR_INVALID, "%s: %s", who, why);
+    if (!count && !ends) return fail(TGX_ERR_INVALID, "%s: count and ends are both NULL", who);
+    if (n_rows == 0) return TGX_OK;
+    if (tgx::dfa_width(dfa->n_states) == 8)
+        dfa_host<8>(text, offs, n_rows, dfa, count, ends);
+    else
+        dfa_host<16>(text, offs, n_rows, dfa, count, ends);
     return TGX_OK;
 }
 

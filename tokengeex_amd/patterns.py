@@ -1,0 +1,350 @@
+"""Byte patterns over character classes, compiled to the automaton that pattern_hits runs on the device
+(include/tgx_patterns.h: tgx_dfa; csrc/dfa.hip).
+
+    pat = compile_pattern(r"[a-zA-Z0-9._%+-]+@[a-zA-Z0-9.-]+\\.[a-zA-Z]{2,}")     # 7 states
+    pat = compile_pattern([r"\\d{3}-\\d{2}-\\d{4}", r"\\d{5,}"])                    # pattern k tags its matches with bit k
+
+Pure Python over bytes: a parser, Thompson's NFA, the subset construction (with search=True the start is re-entered at
+every byte, which is the automaton of .*R: it marks where a match of R ENDS) and Moore's minimisation.  The device
+serves automata of at most 16 states; a pattern that needs more raises ValueError with the count.
+
+Syntax: literal bytes; the escapes \\\\ \\. (a backslash before any ASCII punctuation is that byte) \\n \\t \\r \\f \\v \\d \\w
+\\s \\xHH; `.`, any byte but '\\n'; [...] with ranges and a leading ^; ( ), |, * + ?, {m}, {m,}, {m,n}.  A str pattern is
+its UTF-8 bytes, a non-ASCII byte inside [...] is refused, \\d \\w \\s are ASCII ([0-9], [A-Za-z0-9_], space and 0x09 ..
+0x0D).  Anchors, backreferences, look-around, lazy and possessive quantifiers and Unicode classes are refused by name."""
+from __future__ import annotations
+
+import numpy as np
+
+MAX_STATES = 16      # TGX_DFA_MAX_STATES
+MAX_PATTERNS = 8     # one tag bit each
+MAX_SUBSETS = 4096   # the subset construction gives up beyond this many states
+MAX_REPEAT = 256     # of one {m,n}
+
+_ALL = (1 << 256) - 1
+_DIGIT = sum(1 << b for b in range(0x30, 0x3A))
+_WORD = _DIGIT | sum(1 << b for b in range(0x41, 0x5B)) | sum(1 << b for b in range(0x61, 0x7B)) | (1 << 0x5F)
+_SPACE = (1 << 0x20) | sum(1 << b for b in range(9, 14))
+_CLASSES = {ord("d"): _DIGIT, ord("w"): _WORD, ord("s"): _SPACE}
+_CONTROLS = {ord("n"): 10, ord("t"): 9, ord("r"): 13, ord("f"): 12, ord("v"): 11}
+_PUNCT = frozenset(b"!\"#$%&'()*+,-./:;<=>?@[\\]^_`{|}~ ")
+
+
+def _fold(mask: int) -> int:
+    """the other ASCII case of every letter of the set"""
+    for lo in range(0x61, 0x7B):
+        if mask >> lo & 1 or mask >> (lo - 32) & 1:
+            mask |= (1 << lo) | (1 << (lo - 32))
+    return mask
+
+
+class _Parser:
+    """pattern bytes -> a tree of ("set", mask), ("cat", [..]), ("alt", [..]), ("rep", node, m, n | None)"""
+
+    def __init__(self, src: bytes, fold_case: bool):
+        self.s, self.i, self.fold = src, 0, fold_case
+
+    def fail(self, what: str):
+        raise ValueError(f"pattern {self.s!r}: {what} at byte {self.i}")
+
+    def peek(self):
+        return self.s[self.i] if self.i < len(self.s) else None
+
+    def set(self, mask: int):
+        return ("set", _fold(mask) if self.fold else mask)
+
+    def parse(self):
+        node = self.alt()
+        if self.i < len(self.s):
+            self.fail("an unmatched )")
+        return node
+
+    def alt(self):
+        arms = [self.cat()]
+        while self.peek() == ord("|"):
+            self.i += 1
+            arms.append(self.cat())
+        return arms[0] if len(arms) == 1 else ("alt", arms)
+
+    def cat(self):
+        items = []
+        while self.peek() is not None and self.peek() not in b"|)":
+            items.append(self.repeat())
+        return ("cat", items)
+
+    def repeat(self):
+        node = self.atom()
+        while True:
+            c = self.peek()
+            if c == ord("*"):
+                m, n = 0, None
+            elif c == ord("+"):
+                m, n = 1, None
+            elif c == ord("?"):
+                m, n = 0, 1
+            elif c == ord("{"):
+                m, n = self.bounds()
+            else:
+                return node
+            self.i += 1
+            if self.peek() == ord("?"):
+                self.fail("a lazy quantifier (not supported)")
+            if self.peek() == ord("+"):
+                self.fail("a possessive quantifier (not supported)")
+            node = ("rep", node, m, n)
+
+    def bounds(self):
+        """at '{': -> (m, n), leaving the index on the '}'"""
+        close = self.s.find(b"}", self.i)
+        body = self.s[self.i + 1:close] if close > 0 else b""
+        lo, comma, hi = body.partition(b",")
+        if not lo.isdigit() or (hi and not hi.isdigit()):
+            self.fail("a malformed {m,n}")
+        m = int(lo)
+        n = m if not comma else (int(hi) if hi else None)
+        if (n is not None and n < m) or max(m, n or 0) > MAX_REPEAT:
+            self.fail(f"a {{m,n}} with n < m or a bound above {MAX_REPEAT}")
+        self.i = close
+        return m, n
+
+    def atom(self):
+        c = self.peek()
+        self.i += 1
+        if c == ord("("):
+            if self.peek() == ord("?"):
+                nxt = self.s[self.i + 1:self.i + 3]
+                self.fail("look-around (not supported)" if nxt[:1] in (b"=", b"!") or nxt[:2] in (b"<=", b"<!") else
+                          "a backreference (not supported)" if nxt[:2] == b"P=" else "a (?...) group (not supported)")
+            node = self.alt()
+            if self.peek() != ord(")"):
+                self.fail("a missing )")
+            self.i += 1
+            return node
+        if c == ord("["):
+            return self.char_class()
+        if c == ord("."):
+            return ("set", _ALL & ~(1 << 10))
+        if c in b"^$":
+            self.i -= 1
+            self.fail("an anchor (not supported)")
+        if c in b"*+?{":
+            self.i -= 1
+            self.fail("a quantifier with nothing to repeat")
+        if c == ord("\\"):
+            return self.set(self.escape(False))
+        return self.set(1 << c)
+
+    def escape(self, in_class: bool) -> int:
+        """after a backslash: -> the set it stands for"""
+        c = self.peek()
+        if c is None:
+            self.fail("a trailing backslash")
+        self.i += 1
+        if c in _CLASSES:
+            return _CLASSES[c]
+        if c in _CONTROLS:
+            return 1 << _CONTROLS[c]
+        if c == ord("x"):
+            hexes = self.s[self.i:self.i + 2]
+            try:
+                b = int(hexes, 16) if len(hexes) == 2 else -1
+            except ValueError:
+                b = -1
+            if b < 0:
+                self.fail("a malformed \\xHH")
+            self.i += 2
+            return 1 << b
+        if c in _PUNCT:
+            return 1 << c
+        self.i -= 1
+        if c in b"0123456789":
+            self.fail("a backreference (not supported)")
+        if c in b"bBAZz":
+            self.fail("an anchor (not supported)")
+        if c in b"pPNX":
+            self.fail("a Unicode class (not supported)")
+        self.fail(f"the escape \\{chr(c)} (not supported)")
+
+    def class_item(self):
+        """one member of a [...]: -> (set, the single byte it is or None)"""
+        c = self.peek()
+        if c is None:
+            self.fail("an unterminated [")
+        self.i += 1
+        if c == ord("\\"):
+            mask = self.escape(True)
+            return mask, (mask.bit_length() - 1 if mask & (mask - 1) == 0 else None)
+        if c >= 0x80:
+            self.i -= 1
+            self.fail("a non-ASCII byte inside [...] (a class is a set of bytes; write \\xHH for a byte)")
+        return 1 << c, c
+
+    def char_class(self):
+        negate = self.peek() == ord("^")
+        self.i += negate
+        mask, first = 0, True
+        while first or self.peek() != ord("]"):
+            first = False
+            part, lo = self.class_item()
+            if self.peek() == ord("-") and self.s[self.i + 1:self.i + 2] not in (b"]", b""):
+                self.i += 1
+                _, hi = self.class_item()
+                if lo is None or hi is None or hi < lo:
+                    self.fail("a bad range in [...]")
+                part = sum(1 << b for b in range(lo, hi + 1))
+            mask |= part
+        self.i += 1
+        if self.fold:
+            mask = _fold(mask)
+        return ("set", _ALL & ~mask if negate else mask)
+
+
+class _Nfa:
+    """Thompson's construction: eps[s] the states reached for free, edge[s] = (mask, target) or None"""
+
+    def __init__(self):
+        self.eps, self.edge = [], []
+
+    def state(self):
+        self.eps.append([])
+        self.edge.append(None)
+        return len(self.eps) - 1
+
+    def build(self, node, a: int) -> int:
+        """the fragment of `node` from state a -> its end state"""
+        kind = node[0]
+        if kind == "set":
+            z = self.state()  # (every fragment begins at a fresh state, so `a` has no edge yet)
+            self.edge[a] = (node[1], z)
+            return z
+        if kind == "cat":
+            for item in node[1]:
+                nxt = self.state()
+                self.eps[a].append(nxt)
+                a = self.build(item, nxt)
+            return a
+        if kind == "alt":
+            z = self.state()
+            for arm in node[1]:
+                s = self.state()
+                self.eps[a].append(s)
+                self.eps[self.build(arm, s)].append(z)
+            return z
+        _, sub, m, n = node
+        for _ in range(m):
+            s = self.state()
+            self.eps[a].append(s)
+            a = self.build(sub, s)
+        if n is None:  # a star
+            s, z = self.state(), self.state()
+            self.eps[a] += [s, z]
+            self.eps[self.build(sub, s)] += [s, z]
+            return z
+        z = self.state()
+        self.eps[a].append(z)
+        for _ in range(n - m):  # optional copies, each skipping to the end
+            s = self.state()
+            self.eps[a].append(s)
+            a = self.build(sub, s)
+            self.eps[a].append(z)
+        return z
+
+    def closure(self, states):
+        seen, todo = set(states), list(states)
+        while todo:
+            for t in self.eps[todo.pop()]:
+                if t not in seen:
+                    seen.add(t)
+                    todo.append(t)
+        return frozenset(seen)
+
+
+def _byte_classes(masks):
+    """the bytes grouped by the sets they belong to: -> (class of each byte, a representative byte per class)"""
+    sig = {}
+    cls = np.zeros(256, np.int64)
+    reps = []
+    for b in range(256):
+        key = tuple(m >> b & 1 for m in masks)
+        if key not in sig:
+            sig[key] = len(reps)
+            reps.append(b)
+        cls[b] = sig[key]
+    return cls, reps
+
+
+class BytePattern:
+    """A compiled automaton: .n_states, .start, .next (uint8 [256, 16]: next[b][s]), .tag (uint8 [16]: bit k set in an
+    accepting state of pattern k) as numpy, the fields of tgx_dfa, and .patterns, the sources as bytes."""
+
+    def __init__(self, n_states, start, nxt, tag, patterns=()):
+        self.n_states, self.start, self.patterns = int(n_states), int(start), tuple(patterns)
+        self.next = np.ascontiguousarray(nxt, dtype=np.uint8)
+        self.tag = np.ascontiguousarray(tag, dtype=np.uint8)
+        assert self.next.shape == (256, MAX_STATES) and self.tag.shape == (MAX_STATES,)
+
+    def __repr__(self):
+        return f"BytePattern({list(self.patterns)!r}, n_states={self.n_states})"
+
+
+def compile_pattern(patterns, fold_case: bool = False, search: bool = True) -> BytePattern:
+    """-> a BytePattern of one pattern (bytes or str) or of a list of up to 8, pattern k tagging its matches with bit k.
+    search=True: the automaton of .*R, whose tag at a byte says that a match ends there (what pattern_hits counts);
+    search=False: the automaton of R itself from a row's first byte, with a dead state.  fold_case adds the other ASCII
+    case to every literal and class.  ValueError: a syntax error, an unsupported construct (named), a pattern that
+    matches the empty string, or more than 16 states after minimisation (the message carries the count)."""
+    if isinstance(patterns, (str, bytes, bytearray)):
+        patterns = [patterns]
+    sources = [p.encode("utf-8") if isinstance(p, str) else bytes(p) for p in patterns]
+    if not 1 <= len(sources) <= MAX_PATTERNS:
+        raise ValueError(f"{len(sources)} patterns: 1 to {MAX_PATTERNS} go into one automaton")
+    nfa = _Nfa()
+    root = nfa.state()
+    accept = {}
+    for k, src in enumerate(sources):
+        s = nfa.state()
+        nfa.eps[root].append(s)
+        accept[nfa.build(_Parser(src, fold_case).parse(), s)] = 1 << k
+    first = nfa.closure([root])
+    if any(s in accept for s in first):
+        raise ValueError("a pattern matches the empty string")
+    cls, reps = _byte_classes(sorted({e[0] for e in nfa.edge if e}))
+    # the subset construction over the byte classes
+    index, subsets, trans = {first: 0}, [first], []
+    while len(trans) < len(subsets):
+        cur, row = subsets[len(trans)], []
+        for b in reps:
+            moved = nfa.closure([nfa.edge[s][1] for s in cur if nfa.edge[s] and nfa.edge[s][0] >> b & 1])
+            if search:
+                moved |= first
+            if moved not in index:
+                if len(subsets) >= MAX_SUBSETS:
+                    raise ValueError(f"more than {MAX_SUBSETS} states before minimisation: the limit after it is {MAX_STATES}")
+                index[moved] = len(subsets)
+                subsets.append(moved)
+            row.append(index[moved])
+        trans.append(row)
+    tags = [0] * len(subsets)
+    for i, sub in enumerate(subsets):
+        for s in sub:
+            tags[i] |= accept.get(s, 0)
+    # Moore: split by tag, then by the blocks of the successors, until nothing splits
+    block = tags
+    while True:
+        keys = {}
+        refined = [keys.setdefault((block[i], tuple(block[t] for t in trans[i])), len(keys)) for i in range(len(subsets))]
+        if len(keys) == len(set(block)):
+            break
+        block = refined
+    names = {}
+    for i in range(len(subsets)):  # blocks numbered by their first member: the start is state 0
+        names.setdefault(block[i], len(names))
+    n = len(names)
+    if n > MAX_STATES:
+        raise ValueError(f"the automaton has {n} states after minimisation: the limit is {MAX_STATES}")
+    nxt, tag = np.zeros((256, MAX_STATES), np.uint8), np.zeros(MAX_STATES, np.uint8)
+    for i in range(len(subsets)):
+        s = names[block[i]]
+        tag[s] = tags[i]
+        nxt[:, s] = np.array([names[block[t]] for t in trans[i]], np.uint8)[cls]
+    return BytePattern(n, 0, nxt, tag, sources)

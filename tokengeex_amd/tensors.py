@@ -634,6 +634,34 @@ def autogenerated_rows(corpus: "_lib.NativeCorpus", head_lines: int = 5, phrases
             ps.free()
 
 
+# ---- byte patterns over character classes: a DFA scanned over every row (csrc/dfa.hip) ---------------------------------------
+
+def pattern_hits(corpus: "_lib.NativeCorpus", pat, return_ends: bool = False):
+    """-> [S] torch.int64 on the corpus's device: per row the bytes at which a match of `pat` ends, queued on torch's
+    current stream.  pat: a patterns.BytePattern (patterns.compile_pattern: regex-class syntax, up to 8 patterns and 16
+    states), or a pattern or list of patterns, which is compiled here.  With return_ends also [N] torch.uint8, at every
+    byte the patterns that end there (bit k: pattern k; 0: none).  Every row is matched on its own: no match crosses a
+    row's end.  Matches are counted by their ends, so "aaa" holds two ends of `aa`, and one end of `a+b` however many
+    starts it has."""
+    import torch
+    from . import patterns
+    dev = _device_of(torch, corpus)
+    if not isinstance(pat, patterns.BytePattern):
+        pat = patterns.compile_pattern(pat)
+    S, N = corpus.num_samples, corpus.num_bytes
+    count = torch.empty((S,), dtype=torch.int64, device=dev)
+    ends = torch.empty((N,), dtype=torch.uint8, device=dev) if return_ends else None
+    spare = torch.empty(1, dtype=torch.int64, device=dev)  # (no row: the pointer still says that the counts are asked for)
+    corpus.dfa_hits(pat, (count if S else spare).data_ptr(), ends.data_ptr() if return_ends and N else 0, stream=torch.cuda.current_stream(dev).cuda_stream)
+    return (count, ends) if return_ends else count
+
+
+def pattern_rows(corpus: "_lib.NativeCorpus", pat, max_hits: int = 0):
+    """-> torch.int64 indices, ascending, of the rows of the corpus with at most max_hits match ends of `pat`: what
+    `select` takes to drop the others (of a corpus and, with the same indices, of its encoded result)."""
+    return (pattern_hits(corpus, pat) <= int(max_hits)).nonzero().reshape(-1)
+
+
 GOPHER_TOP = ((2, .20), (3, .18), (4, .16))
 GOPHER_DUP = ((5, .15), (6, .14), (7, .13), (8, .12), (9, .11), (10, .10))
 
