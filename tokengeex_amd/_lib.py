@@ -253,6 +253,15 @@ PATTERN_SYMBOLS = {
     "tgx_dfa_last_times": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_float), _i]),
 }
 
+# every exported symbol of include/tgx_redact.h, a header of its own in the same way: bound and checked at import too
+REDACT_SYMBOLS = {
+    "tgx_corpus_dfa_cover_device": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "tgx_dfa_cover_host": (_i, [_vp, _vp, _u64, _vp, _vp, _vp]),
+    "tgx_corpus_redact": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp]),
+    "tgx_redact_host": (_i, [_vp, _vp, _u64, _vp, _vp, _vp, _u32, _vp, _u64, _vp, C.POINTER(C.c_uint64)]),
+    "tgx_redact_last_times": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_float), _i]),
+}
+
 
 class TokenGeeXError(Exception):
     """tokengeex.TokenGeeXError — bindings/python/src/lib.rs:9,33-37; carries the
@@ -298,7 +307,7 @@ def _load() -> C.CDLL:
             "Build it with `python tokengeex_amd/build.py`.")
     _share_torch_hip_runtime()
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(WORD_SYMBOLS.items()) + list(WORDS_SYMBOLS.items()) + list(PHRASE_SYMBOLS.items()) + list(PATTERN_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(WORD_SYMBOLS.items()) + list(WORDS_SYMBOLS.items()) + list(PHRASE_SYMBOLS.items()) + list(PATTERN_SYMBOLS.items()) + list(REDACT_SYMBOLS.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args
@@ -1178,6 +1187,79 @@ def dfa_last_times() -> dict[str, float]:
     return {names[i].decode(): float(ms[i]) for i in range(n)}
 
 
+# ---- cover and redaction (include/tgx_redact.h; csrc/cover.hip, csrc/redact.hip) ----
+REDACT_MAX_CLASSES = 8
+REDACT_MAX_REPL = 64
+
+
+class TgxDfaCover(C.Structure):
+    """tgx_dfa_cover of include/tgx_redact.h"""
+    _fields_ = [("fwd", TgxDfa), ("bwd", TgxDfa), ("cover", (C.c_uint8 * DFA_MAX_STATES) * DFA_MAX_STATES)]
+
+
+def dfa_cover_struct(pat) -> TgxDfaCover:
+    """A cover pattern (patterns.compile_pattern(cover=True): the forward automaton's fields, .back and .cover, uint8
+    [16, 16]) as the struct of the ABI.  The library checks it."""
+    d = TgxDfaCover()
+    d.fwd, d.bwd = dfa_struct(pat), dfa_struct(pat.back)
+    cover = np.ascontiguousarray(pat.cover, dtype=np.uint8)
+    if cover.shape != (DFA_MAX_STATES, DFA_MAX_STATES):
+        raise ValueError("a cover pattern's pair table is uint8 [16, 16]")
+    C.memmove(d.cover, cover.ctypes.data, cover.nbytes)
+    return d
+
+
+def dfa_cover_host(text: np.ndarray, offs: np.ndarray, pat):
+    """Host twin of NativeCorpus.dfa_cover (tgx_dfa_cover_host: the kernels' chunks, doubling steps in both directions,
+    mirrored records, carries and store / add rule through the same headers, no device) over text u8[N] and offsets
+    u64[S+1] -> (covered int64[S], mask uint8[N])."""
+    text = np.ascontiguousarray(text, dtype=np.uint8)
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    n = max(offs.shape[0] - 1, 0)
+    covered = np.full(n, -7, np.int64)
+    mask = np.full(text.size, 7, np.uint8)
+    keep = np.zeros(1, np.int64), np.zeros(1, np.uint8)   # (never NULL: both outputs are asked for)
+    check(lib.tgx_dfa_cover_host(ptr(text) if text.size else None, ptr(offs) if offs.size else None, n, C.byref(dfa_cover_struct(pat)),
+                                 ptr(covered if n else keep[0]), ptr(mask if mask.size else keep[1])))
+    return covered, mask
+
+
+def _replacements(replacements):
+    """list[bytes | str] -> (flat u8, offs u64[n + 1], n), packed as the ABI takes them; the library checks the limits"""
+    flat, offs = pack([r.encode("utf-8") if isinstance(r, str) else bytes(r) for r in replacements])
+    return flat, offs, len(offs) - 1
+
+
+def redact_host(text: np.ndarray, offs: np.ndarray, mask: np.ndarray, replacements):
+    """Host twin of NativeCorpus.redact (tgx_redact_host: the kernels' lengths, sums and offsets through csrc/redact.h, no
+    device) over text u8[N], offsets u64[S+1] and mask u8[N] -> (the new text u8, the new offsets u64[S+1])."""
+    text = np.ascontiguousarray(text, dtype=np.uint8)
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    mask = np.ascontiguousarray(mask, dtype=np.uint8)
+    if mask.shape != text.shape:
+        raise ValueError("the mask has a byte per byte of the text")
+    rflat, roffs, n_repl = _replacements(replacements)
+    n = max(offs.shape[0] - 1, 0)
+    new_offs, length = np.zeros(n + 1, np.uint64), C.c_uint64()
+    args = (ptr(text) if text.size else None, ptr(offs) if offs.size else None, n, ptr(mask) if mask.size else None, ptr(rflat) if rflat.size else None,
+            ptr(roffs), n_repl)
+    st = lib.tgx_redact_host(*args, None, 0, ptr(new_offs), C.byref(length))   # the length first
+    if st != OK and not (st == ERR_INVALID and length.value):
+        check(st)
+    out = np.zeros(length.value, np.uint8)
+    if length.value:
+        check(lib.tgx_redact_host(*args, ptr(out), length.value, ptr(new_offs), C.byref(length)))
+    return out, new_offs
+
+
+def redact_last_times() -> dict[str, float]:
+    """Device time in ms of each stage of the calling thread's last dfa_cover and redact calls (tgx_redact_last_times)."""
+    names = (C.c_char_p * 8)()
+    ms = (C.c_float * 8)()
+    n = lib.tgx_redact_last_times(names, ms, 8)
+    return {names[i].decode(): float(ms[i]) for i in range(n)}
+
+
 def front_host(flat: np.ndarray, offs: np.ndarray, specials: list[bytes], crlf: bool):
     """Host twin of NativeCorpus.split_specials (tgx_front_host: the kernels' index arithmetic, no device) over a packed
     batch (offs from 0) -> (seg_offs u64[S+1], seg_special i32[K], segments' flat, segments' offsets u64[E+1]): the plan of
@@ -1994,6 +2076,25 @@ class NativeCorpus:
         a tagged state, every row beginning in its start state, as int64[S], and per byte that state's tag, as u8[N], into
         caller-owned device memory (either may be 0, not both; tgx_corpus_dfa_hits_device).  This corpus is only read."""
         check(lib.tgx_corpus_dfa_hits_device(self._h, C.byref(dfa_struct(pat)), d_count or None, d_ends or None, stream or None))
+
+    def dfa_cover(self, pat, d_covered: int = 0, d_mask: int = 0, *, stream: int = 0) -> None:
+        """Per sample the bytes that lie inside a match of the cover pattern `pat` (patterns.compile_pattern(cover=True), or
+        anything dfa_cover_struct takes), as int64[S], and per byte the patterns it lies inside, as u8[N] (bit k: pattern
+        k), into caller-owned device memory (either may be 0, not both; tgx_corpus_dfa_cover_device).  This corpus is only
+        read."""
+        check(lib.tgx_corpus_dfa_cover_device(self._h, C.byref(dfa_cover_struct(pat)), d_covered or None, d_mask or None, stream or None))
+
+    def redact(self, d_mask: int, replacements, *, stream: int = 0) -> "NativeCorpus":
+        """A new resident corpus of the same rows in which every run of bytes of one class of the device mask u8[N] (the
+        index of a byte's lowest set bit, below len(replacements)) is replaced by replacements[class], 0 to 64 bytes each
+        and at most 8 of them (tgx_corpus_redact).  This corpus is only read."""
+        rflat, roffs, n_repl = _replacements(replacements)
+        hc = C.c_void_p()
+        check(lib.tgx_corpus_redact(self._h, d_mask or None, ptr(rflat) if rflat.size else None, ptr(roffs), n_repl, 0, stream or None, C.byref(hc)))
+        c = NativeCorpus.__new__(NativeCorpus)
+        c._h = hc
+        c.device = self.device
+        return c
 
     def repeat_stats(self, width: int, seed: int = 0, d_stats: int = 0, d_mask: int = 0, *, stream: int = 0) -> None:
         """Per sample the repetition statistics of its n-grams of `width` bytes, as int64[6, S], and per byte whether a

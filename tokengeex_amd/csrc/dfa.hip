@@ -10,52 +10,21 @@
 // The table, the 256 maps and the 16 tags, is copied into LDS once by every block in front of its run of tiles: 2 KiB +
 // 16 bytes at NS = 16, half the maps at NS = 8.  A lane's map is one LDS read indexed by its byte.  The cross-lane move of
 // a step is __shfl_up, ds_bpermute_b32 (two for a 64-bit map), as in words.hip and for the same reason: DPP's row shifts
-// stop at a row of 16 lanes.  No LDS beyond the table, no scratch.
+// stop at a row of 16 lanes.  No LDS beyond the table, no scratch.  The table's copy and the in-wave scan are in
+// dfa_wave.h, which cover.hip shares.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <rocprim/device/device_scan.hpp>
 
 #include "dfa.h"
+#include "dfa_wave.h"
 #include "scan_helpers.h"
 #include "textstat_walk.h"
 
 namespace tgx {
 
 namespace {
-
-// The block's copy of the table: thread t takes map t, the first sixteen threads a tag each.
-template <uint32_t NS>
-struct DfaLds {
-    DfaMap<NS> map[256];
-    uint8_t tag[kDfaMaxStates];
-};
-template <uint32_t NS>
-__device__ inline void dfa_load_table(const uint64_t* __restrict__ table, DfaLds<NS>& lds) {
-    static_assert(kTextstatBlock == 256, "a thread a map");
-    lds.map[threadIdx.x] = reinterpret_cast<const DfaMap<NS>*>(table)[threadIdx.x];
-    if (threadIdx.x < kDfaMaxStates) lds.tag[threadIdx.x] = reinterpret_cast<const uint8_t*>(table + kDfaMapWords<NS>)[threadIdx.x];
-    __syncthreads();
-}
-
-template <uint32_t NS, uint32_t D>
-__device__ inline DfaMap<NS> dfa_step(DfaMap<NS> mine, uint32_t lane) {
-    const DfaMap<NS> below = __shfl_up(mine, D, 64);
-    return lane >= D ? dfa_compose<NS>(below, mine) : mine;
-}
-// every lane's scanned map: that of the chunk's bytes up to and including its own (the identity in a lane without a byte)
-template <uint32_t NS>
-__device__ inline DfaMap<NS> dfa_chunk(const DfaLds<NS>& lds, const TextLane& t, uint32_t lane, uint32_t start) {
-    DfaMap<NS> m = dfa_identity<NS>();
-    if (t.in) m = dfa_lane_map<NS>(lds.map[t.b], t.pos == t.row_begin, start);
-    m = dfa_step<NS, 1>(m, lane);
-    m = dfa_step<NS, 2>(m, lane);
-    m = dfa_step<NS, 4>(m, lane);
-    m = dfa_step<NS, 8>(m, lane);
-    m = dfa_step<NS, 16>(m, lane);
-    m = dfa_step<NS, 32>(m, lane);
-    return m;
-}
 
 // rec[c] of every chunk c, and the identity behind the last
 template <uint32_t NS>

@@ -1,8 +1,8 @@
 // The *_host twins of the result-side device entry points (include/tgx.h): tgx_layout_pad_host, tgx_layout_pack_host,
-// tgx_layout_windows_host, tgx_assemble_host, tgx_fim_host, tgx_select_host, tgx_select_text_host, tgx_shuffled_rows_host, tgx_first_equal_host, tgx_minhash_host, tgx_minhash_bands_host, tgx_minhash_near_first_host, tgx_gram_keys_host, tgx_gram_hits_host, tgx_gram_contains_host, tgx_repeat_stats_host, tgx_text_stats_host, tgx_lines_host, tgx_word_stats_host (include/tgx_words.h), tgx_words_host and tgx_word_key (include/tgx_word_ids.h), tgx_phrase_hits_host (include/tgx_phrases.h), tgx_dfa_hits_host (include/tgx_patterns.h), tgx_decode_rows_host, tgx_spans_host, tgx_window_spans_host, tgx_front_host,
+// tgx_layout_windows_host, tgx_assemble_host, tgx_fim_host, tgx_select_host, tgx_select_text_host, tgx_shuffled_rows_host, tgx_first_equal_host, tgx_minhash_host, tgx_minhash_bands_host, tgx_minhash_near_first_host, tgx_gram_keys_host, tgx_gram_hits_host, tgx_gram_contains_host, tgx_repeat_stats_host, tgx_text_stats_host, tgx_lines_host, tgx_word_stats_host (include/tgx_words.h), tgx_words_host and tgx_word_key (include/tgx_word_ids.h), tgx_phrase_hits_host (include/tgx_phrases.h), tgx_dfa_hits_host (include/tgx_patterns.h), tgx_dfa_cover_host and tgx_redact_host (include/tgx_redact.h), tgx_decode_rows_host, tgx_spans_host, tgx_window_spans_host, tgx_front_host,
 // tgx_normalize_host and tgx_lattice_stats_host, and the
 // argument checks they share with the device entry points of tgx_api.cpp.  A twin goes through the same index arithmetic as its kernels (layout.h, assemble.h,
-// fim.h, select.h, dedup.h, minhash.h, gram.h, repeat.h, textstat.h, wordstat.h, words.h, dfa.h, decode.h, spans.h, front.h, norm.h) on host memory.  Nothing in this file calls a HIP function, so it builds and runs without the
+// fim.h, select.h, dedup.h, minhash.h, gram.h, repeat.h, textstat.h, wordstat.h, words.h, dfa.h, cover.h, redact.h, decode.h, spans.h, front.h, norm.h) on host memory.  Nothing in this file calls a HIP function, so it builds and runs without the
 // handles, the pool or a device.
 #define TGX_HOST_ONLY  // tile_fill.h: the host loop, no kernel side
 #include <algorithm>
@@ -14,6 +14,7 @@
 
 #include "api_internal.h"
 #include "assemble.h"
+#include "cover.h"
 #include "decode.h"
 #include "dedup.h"
 #include "dfa.h"
@@ -24,6 +25,7 @@
 #include "minhash.h"
 #include "norm.h"
 #include "phrase.h"
+#include "redact.h"
 #include "repeat.h"
 #include "select.h"
 #include "spans.h"
@@ -33,6 +35,7 @@
 #include "wordstat.h"
 #include "../../include/tgx_patterns.h"
 #include "../../include/tgx_phrases.h"
+#include "../../include/tgx_redact.h"
 #include "../../include/tgx_word_ids.h"
 #include "../../include/tgx_words.h"
 
@@ -1572,6 +1575,147 @@ tgx_status tgx_dfa_hits_host(const uint8_t* text, const uint64_t* offs, uint64_t
         dfa_host<8>(text, offs, n_rows, dfa, count, ends);
     else
         dfa_host<16>(text, offs, n_rows, dfa, count, ends);
+    return TGX_OK;
+}
+
+// ---- cover and redaction (include/tgx_redact.h) ---------------------------------------------------
+
+namespace {
+
+// The twin of cover.hip's two kernels and the two scans between them: the chunks of textstat_walk_host, the forward
+// doubling steps as in dfa_host and the backward ones lane by lane (ascending lanes: a step reads the lane above as it
+// was before the step; a lane without a byte holds the identity, which composing leaves out), both records, the backward
+// one mirrored, the scans as folds, and the second kernel with its store / add rule.  The source and the automata have
+// been checked, S > 0; covered and mask may each be NULL.
+template <uint32_t NSF, uint32_t NSB>
+void cover_host(const uint8_t* text, const uint64_t* offs, uint64_t S, const tgx_dfa_cover* cov, int64_t* covered, uint8_t* mask) {
+    using MapF = tgx::DfaMap<NSF>;
+    using MapB = tgx::DfaMap<NSB>;
+    const uint64_t N = offs[S], n_chunks = (N + tgx::kTextstatChunk - 1) / tgx::kTextstatChunk;
+    const uint32_t f_start = cov->fwd.start, b_start = cov->bwd.start;
+    std::vector<uint64_t> table(tgx::kCoverTableWords<NSF, NSB>);
+    tgx::cover_build_table<NSF, NSB>(cov->fwd.n_states, cov->fwd.next, cov->fwd.tag, cov->bwd.n_states, cov->bwd.next, cov->cover, table.data());
+    const MapF* maps_f = reinterpret_cast<const MapF*>(table.data());
+    const MapB* maps_b = reinterpret_cast<const MapB*>(table.data() + tgx::kDfaTableWords<NSF>);
+    const uint8_t* pair = reinterpret_cast<const uint8_t*>(table.data() + tgx::kDfaTableWords<NSF> + tgx::kDfaTableWords<NSB>);
+    auto chunk_of = [&](uint64_t c0, uint32_t n_in, const uint64_t* row, MapF* mf, MapB* mb) {
+        for (uint32_t l = 0; l < n_in; l++) {
+            mf[l] = tgx::dfa_lane_map<NSF>(maps_f[text[c0 + l]], c0 + l == offs[row[l]], f_start);
+            mb[l] = tgx::dfa_lane_map<NSB>(maps_b[text[c0 + l]], c0 + l + 1 == offs[row[l] + 1], b_start);
+        }
+        for (uint32_t d = 1; d < tgx::kTextstatChunk; d <<= 1) {
+            for (uint32_t l = n_in; l-- > d;) mf[l] = tgx::dfa_compose<NSF>(mf[l - d], mf[l]);
+            for (uint32_t l = 0; l + d < n_in; l++) mb[l] = tgx::dfa_compose<NSB>(mb[l + d], mb[l]);
+        }
+    };
+    if (covered) std::fill(covered, covered + S, 0);  // the launcher's pre-set
+    std::vector<MapF> rec_f(n_chunks + 1, tgx::dfa_identity<NSF>()), carry_f(n_chunks + 1);
+    std::vector<MapB> rec_b(n_chunks + 1, tgx::dfa_identity<NSB>()), carry_b(n_chunks + 1);
+    textstat_walk_host(text, offs, S, [&](uint64_t c0, uint32_t n_in, uint64_t, const uint64_t* row) {
+        MapF mf[tgx::kTextstatChunk];
+        MapB mb[tgx::kTextstatChunk];
+        chunk_of(c0, n_in, row, mf, mb);
+        rec_f[c0 / tgx::kTextstatChunk] = mf[n_in - 1];
+        rec_b[tgx::cover_mirror(c0 / tgx::kTextstatChunk, n_chunks)] = mb[0];
+    });
+    MapF acc_f = tgx::dfa_identity<NSF>();  // the exclusive scans under DfaCarryOp
+    MapB acc_b = tgx::dfa_identity<NSB>();
+    for (uint64_t k = 0; k <= n_chunks; k++) {
+        carry_f[k] = acc_f;
+        carry_b[k] = acc_b;
+        acc_f = tgx::DfaCarryOp<NSF>()(acc_f, rec_f[k]);
+        acc_b = tgx::DfaCarryOp<NSB>()(acc_b, rec_b[k]);
+    }
+    textstat_walk_host(text, offs, S, [&](uint64_t c0, uint32_t n_in, uint64_t, const uint64_t* row) {
+        MapF mf[tgx::kTextstatChunk];
+        MapB mb[tgx::kTextstatChunk];
+        chunk_of(c0, n_in, row, mf, mb);
+        const uint64_t k = c0 / tgx::kTextstatChunk;
+        uint64_t marked = 0;
+        for (uint32_t l = 0; l < n_in; l++) {
+            const uint32_t f = tgx::dfa_state<NSF>(mf[l], carry_f[k], f_start);
+            const uint32_t g = tgx::cover_back_state<NSB>(l + 1 < n_in ? mb[l + 1] : tgx::dfa_identity<NSB>(), l == n_in - 1, c0 + l + 1 == offs[row[l] + 1],
+                                                          carry_b[tgx::cover_mirror(k, n_chunks)], b_start);
+            const uint8_t m = pair[tgx::kDfaMaxStates * f + g];
+            if (mask) mask[c0 + l] = m;
+            if (m) marked |= 1ull << l;
+        }
+        if (!covered) return;
+        for (uint32_t a = 0; a < n_in;) {  // the stretch [a, b] of one row
+            uint32_t b = a;
+            while (b + 1 < n_in && row[b + 1] == row[a]) b++;
+            const uint64_t i = row[a], v = tgx::textstat_popc(marked & tgx::textstat_span(a, b));
+            if (tgx::textstat_row_inside(offs, i, c0))
+                covered[i] = (int64_t)v;
+            else if (tgx::textstat_adds(v))
+                covered[i] += (int64_t)v;
+            a = b + 1;
+        }
+    });
+}
+
+}  // namespace
+
+tgx_status tgx_dfa_cover_host(const uint8_t* text, const uint64_t* offs, uint64_t n_rows, const tgx_dfa_cover* cov, int64_t* covered, uint8_t* mask) {
+    const char* who = "tgx_dfa_cover_host";
+    const tgx_status st = textstat_check_source_host(who, text, offs, n_rows);
+    if (st != TGX_OK) return st;
+    if (!cov) return fail(TGX_ERR_INVALID, "%s: cov is NULL", who);
+    if (const char* why = tgx::cover_check(cov->fwd.n_states, cov->fwd.start, cov->fwd.next, cov->fwd.tag, cov->bwd.n_states, cov->bwd.start, cov->bwd.next))
+        return fail(TGX_ERR_INVALID, "%s: %s", who, why);
+    if (!covered && !mask) return fail(TGX_ERR_INVALID, "%s: covered and mask are both NULL", who);
+    if (n_rows == 0) return TGX_OK;
+    if (tgx::dfa_width(cov->fwd.n_states) == 8)
+        tgx::dfa_width(cov->bwd.n_states) == 8 ? cover_host<8, 8>(text, offs, n_rows, cov, covered, mask) : cover_host<8, 16>(text, offs, n_rows, cov, covered, mask);
+    else
+        tgx::dfa_width(cov->bwd.n_states) == 8 ? cover_host<16, 8>(text, offs, n_rows, cov, covered, mask) : cover_host<16, 16>(text, offs, n_rows, cov, covered, mask);
+    return TGX_OK;
+}
+
+// The twin of redact.hip: the lengths chunk by chunk, their exclusive sum as a fold, the row boundaries through
+// redact_row_offset and the fill with the exclusive sum inside a chunk.
+tgx_status tgx_redact_host(const uint8_t* text, const uint64_t* offs, uint64_t n_rows, const uint8_t* mask, const uint8_t* repl_bytes,
+                           const uint64_t* repl_offs, uint32_t n_repl, uint8_t* out_text, uint64_t out_cap, uint64_t* out_offs, uint64_t* out_len) {
+    const char* who = "tgx_redact_host";
+    if (out_len) *out_len = 0;
+    const tgx_status st = textstat_check_source_host(who, text, offs, n_rows);
+    if (st != TGX_OK) return st;
+    std::vector<uint64_t> words(tgx::kRedactTableWords);
+    if (const char* why = tgx::redact_pack_table(repl_bytes, repl_offs, n_repl, words.data())) return fail(TGX_ERR_INVALID, "%s: %s", who, why);
+    if (!out_offs || !out_len) return fail(TGX_ERR_INVALID, "%s: %s is NULL", who, out_offs ? "out_len" : "out_offs");
+    const uint64_t S = n_rows, N = offs[S], n_chunks = (N + tgx::kTextstatChunk - 1) / tgx::kTextstatChunk;
+    if (N && !mask) return fail(TGX_ERR_INVALID, "%s: mask is NULL", who);
+    const tgx::RedactTable* table = reinterpret_cast<const tgx::RedactTable*>(words.data());
+    auto lengths_of = [&](uint64_t c0, uint32_t n_in, const uint64_t* row, uint32_t* cls, uint32_t* len) {
+        for (uint32_t l = 0; l < n_in; l++) {
+            const uint64_t p = c0 + l, begin = offs[row[l]];
+            cls[l] = tgx::redact_class(mask[p], n_repl);
+            len[l] = tgx::redact_len(cls[l], p > begin ? tgx::redact_class(mask[p - 1], n_repl) : tgx::kRedactNone, p == begin, table->len);
+        }
+    };
+    std::vector<uint64_t> carry(n_chunks + 1, 0);
+    textstat_walk_host(text, offs, S, [&](uint64_t c0, uint32_t n_in, uint64_t, const uint64_t* row) {
+        uint32_t cls[tgx::kTextstatChunk], len[tgx::kTextstatChunk];
+        lengths_of(c0, n_in, row, cls, len);
+        for (uint32_t l = 0; l < n_in; l++) carry[c0 / tgx::kTextstatChunk + 1] += len[l];  // (the record, summed below)
+    });
+    for (uint64_t k = 0; k < n_chunks; k++) carry[k + 1] += carry[k];  // the exclusive sum: entry k is what lies in front of chunk k
+    for (uint64_t r = 0; r <= S; r++) out_offs[r] = tgx::redact_row_offset(mask, offs, r, n_repl, table->len, carry.data());
+    *out_len = carry[n_chunks];
+    if (out_cap < *out_len)
+        return fail(TGX_ERR_INVALID, "%s: %llu bytes, room for %llu", who, (unsigned long long)*out_len, (unsigned long long)out_cap);
+    if (*out_len && !out_text) return fail(TGX_ERR_INVALID, "%s: out_text is NULL", who);
+    textstat_walk_host(text, offs, S, [&](uint64_t c0, uint32_t n_in, uint64_t, const uint64_t* row) {
+        uint32_t cls[tgx::kTextstatChunk], len[tgx::kTextstatChunk];
+        lengths_of(c0, n_in, row, cls, len);
+        uint64_t at = carry[c0 / tgx::kTextstatChunk];
+        for (uint32_t l = 0; l < n_in; at += len[l], l++) {
+            if (cls[l] == tgx::kRedactNone)
+                out_text[at] = text[c0 + l];
+            else
+                std::copy(table->bytes[cls[l]], table->bytes[cls[l]] + len[l], out_text + at);
+        }
+    });
     return TGX_OK;
 }
 

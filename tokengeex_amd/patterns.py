@@ -8,6 +8,11 @@ Pure Python over bytes: a parser, Thompson's NFA, the subset construction (with 
 every byte, which is the automaton of .*R: it marks where a match of R ENDS) and Moore's minimisation.  The device
 serves automata of at most 16 states; a pattern that needs more raises ValueError with the count.
 
+    pat = compile_pattern(r"\\d{3}-\\d{2}-\\d{4}", cover=True)                     # 12 forward and 11 backward states
+
+With cover=True the pattern also carries a backward automaton and a table over the pairs of states, which together say
+which bytes lie INSIDE a match (include/tgx_redact.h: tgx_dfa_cover; csrc/cover.hip).
+
 Syntax: literal bytes; the escapes \\\\ \\. (a backslash before any ASCII punctuation is that byte) \\n \\t \\r \\f \\v \\d \\w
 \\s \\xHH; `.`, any byte but '\\n'; [...] with ranges and a leading ^; ( ), |, * + ?, {m}, {m,}, {m,n}.  A str pattern is
 its UTF-8 bytes, a non-ASCII byte inside [...] is refused, \\d \\w \\s are ASCII ([0-9], [A-Za-z0-9_], space and 0x09 ..
@@ -287,12 +292,110 @@ class BytePattern:
         return f"BytePattern({list(self.patterns)!r}, n_states={self.n_states})"
 
 
-def compile_pattern(patterns, fold_case: bool = False, search: bool = True) -> BytePattern:
+class BackPattern:
+    """The backward half of a cover pattern: .n_states, .start, .next (uint8 [256, 16]) and an all-zero .tag, the fields of
+    tgx_dfa_cover's bwd, which is run from a row's last byte to its first."""
+
+    def __init__(self, n_states, start, nxt):
+        self.n_states, self.start = int(n_states), int(start)
+        self.next = np.ascontiguousarray(nxt, dtype=np.uint8)
+        self.tag = np.zeros(MAX_STATES, np.uint8)
+
+
+def _explore(start, reps, move):
+    """the subsets reachable from `start` under move(subset, representative byte): -> (subsets, trans[i][class])"""
+    index, subsets, trans = {start: 0}, [start], []
+    while len(trans) < len(subsets):
+        row = []
+        for b in reps:
+            moved = move(subsets[len(trans)], b)
+            if moved not in index:
+                if len(subsets) >= MAX_SUBSETS:
+                    raise ValueError(f"more than {MAX_SUBSETS} states before minimisation: the limit after it is {MAX_STATES}")
+                index[moved] = len(subsets)
+                subsets.append(moved)
+            row.append(index[moved])
+        trans.append(row)
+    return subsets, trans
+
+
+def _moore(block, trans):
+    """Moore's refinement of the initial blocks (any hashable per state) -> (the class of each state, numbered by first
+    member, so the start is class 0; the number of classes)"""
+    while True:
+        keys = {}
+        refined = [keys.setdefault((block[i], tuple(block[t] for t in trans[i])), len(keys)) for i in range(len(trans))]
+        if len(keys) == len(set(block)):
+            break
+        block = refined
+    names = {}
+    for b in block:
+        names.setdefault(b, len(names))
+    return [names[b] for b in block], len(names)
+
+
+def _table(state_of, trans, cls):
+    nxt = np.zeros((256, MAX_STATES), np.uint8)
+    for i, s in enumerate(state_of):
+        nxt[:, s] = np.array([state_of[t] for t in trans[i]], np.uint8)[cls]
+    return nxt
+
+
+def _compile_cover(nfa, first, accept, owner, cls, reps, sources) -> BytePattern:
+    """The two-sided automaton of include/tgx_redact.h.  Forward: the NFA states reached after AT LEAST one byte of an
+    attempt begun at or before the byte (the attempts' first states stay out of the set: a match that begins at j + 1
+    must not cover j).  Backward: the NFA states from which the bytes to the right, or none, reach an accept.  A byte is
+    inside a match of pattern k iff the two sets share a state of pattern k's fragment."""
+    edge = nfa.edge
+    into = [[] for _ in nfa.eps]  # the eps edges reversed
+    for s, targets in enumerate(nfa.eps):
+        for t in targets:
+            into[t].append(s)
+
+    def back_closure(states):
+        seen, todo = set(states), list(states)
+        while todo:
+            for t in into[todo.pop()]:
+                if t not in seen:
+                    seen.add(t)
+                    todo.append(t)
+        return frozenset(seen)
+
+    ends = back_closure(accept)
+    fsub, ftrans = _explore(frozenset(), reps, lambda cur, b: nfa.closure([edge[s][1] for s in cur | first if edge[s] and edge[s][0] >> b & 1]))
+    bsub, btrans = _explore(ends, reps, lambda cur, b: back_closure([s for s, e in enumerate(edge) if e and e[0] >> b & 1 and e[1] in cur]) | ends)
+    ftag = [sum({accept[s] for s in sub if s in accept}) for sub in fsub]
+    pair = [[0] * len(bsub) for _ in fsub]
+    for i, x in enumerate(fsub):
+        for j, y in enumerate(bsub):
+            for s in x & y:
+                pair[i][j] |= owner[s]
+    fstate, nf = _moore([(ftag[i], tuple(pair[i])) for i in range(len(fsub))], ftrans)
+    bstate, nb = _moore([tuple(pair[i][j] for i in range(len(fsub))) for j in range(len(bsub))], btrans)
+    for side, n in (("forward", nf), ("backward", nb)):
+        if n > MAX_STATES:
+            raise ValueError(f"the {side} automaton of the cover has {n} states after minimisation: the limit is {MAX_STATES}")
+    tag, cover = np.zeros(MAX_STATES, np.uint8), np.zeros((MAX_STATES, MAX_STATES), np.uint8)
+    for i, f in enumerate(fstate):
+        tag[f] = ftag[i]
+        for j, g in enumerate(bstate):
+            cover[f][g] = pair[i][j]
+    pat = BytePattern(nf, 0, _table(fstate, ftrans, cls), tag, sources)
+    pat.back, pat.cover = BackPattern(nb, 0, _table(bstate, btrans, cls)), cover
+    return pat
+
+
+def compile_pattern(patterns, fold_case: bool = False, search: bool = True, cover: bool = False) -> BytePattern:
     """-> a BytePattern of one pattern (bytes or str) or of a list of up to 8, pattern k tagging its matches with bit k.
     search=True: the automaton of .*R, whose tag at a byte says that a match ends there (what pattern_hits counts);
     search=False: the automaton of R itself from a row's first byte, with a dead state.  fold_case adds the other ASCII
     case to every literal and class.  ValueError: a syntax error, an unsupported construct (named), a pattern that
-    matches the empty string, or more than 16 states after minimisation (the message carries the count)."""
+    matches the empty string, or more than 16 states after minimisation (the message carries the count).
+    cover=True (pattern_cover, redact_patterns): the pattern also carries .back, a BackPattern run from a row's last byte
+    to its first, and .cover, uint8 [16, 16]: cover[f][g] has bit k set iff a byte after which the forward automaton is
+    in f, and before which the backward one is in g, lies inside a match of pattern k.  The forward automaton still
+    tags match ends, but is a larger one than without cover; more than 16 states on either side is a ValueError that
+    names the side."""
     if isinstance(patterns, (str, bytes, bytearray)):
         patterns = [patterns]
     sources = [p.encode("utf-8") if isinstance(p, str) else bytes(p) for p in patterns]
@@ -300,15 +403,20 @@ def compile_pattern(patterns, fold_case: bool = False, search: bool = True) -> B
         raise ValueError(f"{len(sources)} patterns: 1 to {MAX_PATTERNS} go into one automaton")
     nfa = _Nfa()
     root = nfa.state()
-    accept = {}
+    accept, owner = {}, [0]
     for k, src in enumerate(sources):
         s = nfa.state()
         nfa.eps[root].append(s)
         accept[nfa.build(_Parser(src, fold_case).parse(), s)] = 1 << k
+        owner += [1 << k] * (len(nfa.eps) - len(owner))  # every state of the fragment belongs to pattern k
     first = nfa.closure([root])
     if any(s in accept for s in first):
         raise ValueError("a pattern matches the empty string")
     cls, reps = _byte_classes(sorted({e[0] for e in nfa.edge if e}))
+    if cover:
+        if not search:
+            raise ValueError("cover=True needs search=True: a cover is of the matches anywhere in a row")
+        return _compile_cover(nfa, first, accept, owner, cls, reps, sources)
     # the subset construction over the byte classes
     index, subsets, trans = {first: 0}, [first], []
     while len(trans) < len(subsets):

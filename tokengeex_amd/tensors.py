@@ -662,6 +662,75 @@ def pattern_rows(corpus: "_lib.NativeCorpus", pat, max_hits: int = 0):
     return (pattern_hits(corpus, pat) <= int(max_hits)).nonzero().reshape(-1)
 
 
+# ---- cover and redaction: the bytes inside a match, and runs of a mask replaced (csrc/cover.hip, csrc/redact.hip) ------------
+
+def pattern_cover(corpus: "_lib.NativeCorpus", pat, return_mask: bool = False):
+    """-> [S] torch.int64 on the corpus's device: per row the bytes that lie inside some match of `pat`, queued on torch's
+    current stream.  pat: a patterns.BytePattern from compile_pattern(..., cover=True), or a pattern or list of patterns,
+    which is compiled here.  With return_mask also [N] torch.uint8, at every byte the patterns it lies inside (bit k:
+    pattern k; 0: none), what `redact` takes.  Every match counts, overlapping ones too: under `a+b`, all of "aaab" is
+    covered.  Every row is matched on its own."""
+    import torch
+    from . import patterns
+    dev = _device_of(torch, corpus)
+    if not isinstance(pat, patterns.BytePattern):
+        pat = patterns.compile_pattern(pat, cover=True)
+    if not hasattr(pat, "cover"):
+        raise ValueError("pattern_cover needs a pattern compiled with cover=True")
+    S, N = corpus.num_samples, corpus.num_bytes
+    covered = torch.empty((S,), dtype=torch.int64, device=dev)
+    mask = torch.empty((N,), dtype=torch.uint8, device=dev) if return_mask else None
+    spare = torch.empty(1, dtype=torch.int64, device=dev)  # (no row: the pointer still says that the counts are asked for)
+    corpus.dfa_cover(pat, (covered if S else spare).data_ptr(), mask.data_ptr() if return_mask and N else 0, stream=torch.cuda.current_stream(dev).cuda_stream)
+    return (covered, mask) if return_mask else covered
+
+
+def redact(corpus: "_lib.NativeCorpus", mask, replacements) -> "_lib.NativeCorpus":
+    """-> a new resident corpus of the same rows in which every run of masked bytes is replaced, queued on torch's current
+    stream.  mask: [N] torch.uint8 (or bool) on the corpus's device, from pattern_cover, phrase_cover or the caller's
+    own; a byte's class is the index of its lowest set bit, and a maximal stretch of bytes of one row with the same
+    class is replaced by replacements[class] (bytes or str, 0 to 64 bytes, at most 8 of them).  A byte whose mask is 0, or
+    whose class has no replacement, is copied.  The corpus is only read."""
+    import torch
+    dev = _device_of(torch, corpus)
+    if mask.dtype == torch.bool:
+        mask = mask.to(torch.uint8)
+    ptr = _check_dest(torch, "mask", mask, dev, torch.uint8, corpus.num_bytes)
+    return corpus.redact(ptr if corpus.num_bytes else 0, list(replacements), stream=torch.cuda.current_stream(dev).cuda_stream)
+
+
+def redact_patterns(corpus: "_lib.NativeCorpus", patterns, replacements, fold_case: bool = False) -> "_lib.NativeCorpus":
+    """-> a new resident corpus in which every stretch of bytes inside matches of patterns[k] is replaced by
+    replacements[k]: compile_pattern(..., fold_case, cover=True), pattern_cover and redact.  Where matches of two
+    patterns overlap, the bytes they share go to the pattern with the lower index.  Patterns that fit one automaton of
+    16 states a side share a cover pass; the list is cut, in order, into the fewest such groups from the left (e-mail
+    and IPv4 together need 33 forward states, so they take a pass each), and the groups' masks are OR-ed.
+        redact_patterns(corpus, [email, ipv4], ["<EMAIL>", "<IP_ADDRESS>"])"""
+    import torch
+    from . import patterns as _patterns
+    if isinstance(patterns, (str, bytes, bytearray)):
+        patterns, replacements = [patterns], [replacements] if isinstance(replacements, (str, bytes, bytearray)) else replacements
+    patterns = list(patterns)
+    if len(patterns) != len(replacements) or not 1 <= len(patterns) <= _lib.REDACT_MAX_CLASSES:
+        raise ValueError(f"{len(patterns)} patterns and {len(replacements)} replacements: 1 to {_lib.REDACT_MAX_CLASSES} of each, one for one")
+    mask, k = None, 0
+    while k < len(patterns):
+        n = len(patterns) - k
+        while True:  # the longest group from k on that compiles; a pattern that does not compile alone raises
+            try:
+                pat = _patterns.compile_pattern(patterns[k:k + n], fold_case=fold_case, cover=True)
+                break
+            except ValueError:
+                if n == 1:
+                    raise
+                n -= 1
+        _, part = pattern_cover(corpus, pat, return_mask=True)
+        part = torch.bitwise_left_shift(part, k) if k else part
+        mask = part if mask is None else mask | part
+        k += n
+    return redact(corpus, mask, replacements)
+
+
 GOPHER_TOP = ((2, .20), (3, .18), (4, .16))
 GOPHER_DUP = ((5, .15), (6, .14), (7, .13), (8, .12), (9, .11), (10, .10))
 
