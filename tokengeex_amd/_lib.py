@@ -262,6 +262,15 @@ REDACT_SYMBOLS = {
     "tgx_redact_last_times": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_float), _i]),
 }
 
+# every exported symbol of include/tgx_shapes.h, a header of its own in the same way: bound and checked at import too
+SHAPE_SYMBOLS = {
+    "tgx_corpus_shape_hits_device": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "tgx_corpus_shape_cover_device": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "tgx_shape_hits_host": (_i, [_vp, _vp, _u64, _vp, _vp, _vp]),
+    "tgx_shape_cover_host": (_i, [_vp, _vp, _u64, _vp, _vp, _vp]),
+    "tgx_shapes_last_times": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_float), _i]),
+}
+
 
 class TokenGeeXError(Exception):
     """tokengeex.TokenGeeXError — bindings/python/src/lib.rs:9,33-37; carries the
@@ -307,7 +316,7 @@ def _load() -> C.CDLL:
             "Build it with `python tokengeex_amd/build.py`.")
     _share_torch_hip_runtime()
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(WORD_SYMBOLS.items()) + list(WORDS_SYMBOLS.items()) + list(PHRASE_SYMBOLS.items()) + list(PATTERN_SYMBOLS.items()) + list(REDACT_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(WORD_SYMBOLS.items()) + list(WORDS_SYMBOLS.items()) + list(PHRASE_SYMBOLS.items()) + list(PATTERN_SYMBOLS.items()) + list(REDACT_SYMBOLS.items()) + list(SHAPE_SYMBOLS.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args
@@ -1260,6 +1269,65 @@ def redact_last_times() -> dict[str, float]:
     return {names[i].decode(): float(ms[i]) for i in range(n)}
 
 
+# ---- shapes: fixed-length class sequences as a windowed bit scan (include/tgx_shapes.h; csrc/shape.hip, csrc/shape.h) ----
+SHAPES_MAX_PATTERNS = 8
+SHAPE_MAX_LEN = 64
+SHAPES_MAX_BITS = 128
+
+
+class TgxShapes(C.Structure):
+    """tgx_shapes of include/tgx_shapes.h"""
+    _fields_ = [("n_patterns", C.c_uint32), ("len", C.c_uint32 * SHAPES_MAX_PATTERNS), ("cls", (C.c_uint8 * 32) * SHAPES_MAX_BITS),
+                ("not_before", (C.c_uint8 * 32) * SHAPES_MAX_PATTERNS), ("not_after", (C.c_uint8 * 32) * SHAPES_MAX_PATTERNS)]
+
+
+def shapes_struct(shp) -> TgxShapes:
+    """Shapes with .n_patterns, .len (uint32 [8]), .cls (uint8 [128, 32]), .not_before and .not_after (uint8 [8, 32]), such
+    as a patterns.ShapePattern, as the struct of the ABI.  The library checks it."""
+    d = TgxShapes()
+    d.n_patterns = int(shp.n_patterns)
+    for field, dtype, shape in (("len", np.uint32, (SHAPES_MAX_PATTERNS,)), ("cls", np.uint8, (SHAPES_MAX_BITS, 32)),
+                                ("not_before", np.uint8, (SHAPES_MAX_PATTERNS, 32)), ("not_after", np.uint8, (SHAPES_MAX_PATTERNS, 32))):
+        a = np.ascontiguousarray(getattr(shp, field), dtype=dtype)
+        if a.shape != shape:
+            raise ValueError(f"the shapes' {field} is {np.dtype(dtype).name} {list(shape)}")
+        C.memmove(getattr(d, field), a.ctypes.data, a.nbytes)
+    return d
+
+
+def _shape_host(fn, text: np.ndarray, offs: np.ndarray, shp):
+    text = np.ascontiguousarray(text, dtype=np.uint8)
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    n = max(offs.shape[0] - 1, 0)
+    per_row = np.full(n, -7, np.int64)
+    per_byte = np.full(text.size, 7, np.uint8)
+    keep = np.zeros(1, np.int64), np.zeros(1, np.uint8)   # (never NULL: both outputs are asked for)
+    check(fn(ptr(text) if text.size else None, ptr(offs) if offs.size else None, n, C.byref(shapes_struct(shp)),
+             ptr(per_row if n else keep[0]), ptr(per_byte if per_byte.size else keep[1])))
+    return per_row, per_byte
+
+
+def shape_hits_host(text: np.ndarray, offs: np.ndarray, shp):
+    """Host twin of NativeCorpus.shape_hits (tgx_shape_hits_host: the same tables, the kernel's chunks, halo, doubling
+    steps, guards and store / add rule through csrc/shape.h, no device) over text u8[N] and offsets u64[S+1] ->
+    (count int64[S], ends uint8[N])."""
+    return _shape_host(lib.tgx_shape_hits_host, text, offs, shp)
+
+
+def shape_cover_host(text: np.ndarray, offs: np.ndarray, shp):
+    """Host twin of NativeCorpus.shape_cover (tgx_shape_cover_host: the ends as above, then the cover kernel's pairs of
+    ballots and windows) -> (covered int64[S], mask uint8[N])."""
+    return _shape_host(lib.tgx_shape_cover_host, text, offs, shp)
+
+
+def shapes_last_times() -> dict[str, float]:
+    """Device time in ms of each stage of the calling thread's last shape_hits and shape_cover calls (tgx_shapes_last_times)."""
+    names = (C.c_char_p * 8)()
+    ms = (C.c_float * 8)()
+    n = lib.tgx_shapes_last_times(names, ms, 8)
+    return {names[i].decode(): float(ms[i]) for i in range(n)}
+
+
 def front_host(flat: np.ndarray, offs: np.ndarray, specials: list[bytes], crlf: bool):
     """Host twin of NativeCorpus.split_specials (tgx_front_host: the kernels' index arithmetic, no device) over a packed
     batch (offs from 0) -> (seg_offs u64[S+1], seg_special i32[K], segments' flat, segments' offsets u64[E+1]): the plan of
@@ -2083,6 +2151,18 @@ class NativeCorpus:
         k), into caller-owned device memory (either may be 0, not both; tgx_corpus_dfa_cover_device).  This corpus is only
         read."""
         check(lib.tgx_corpus_dfa_cover_device(self._h, C.byref(dfa_cover_struct(pat)), d_covered or None, d_mask or None, stream or None))
+
+    def shape_hits(self, shp, d_count: int = 0, d_ends: int = 0, *, stream: int = 0) -> None:
+        """Per sample the bytes at which a match of the shapes `shp` (a patterns.ShapePattern, or anything shapes_struct
+        takes) ends, as int64[S], and per byte the patterns that end there, as u8[N] (bit k: pattern k), into caller-owned
+        device memory (either may be 0, not both; tgx_corpus_shape_hits_device).  This corpus is only read."""
+        check(lib.tgx_corpus_shape_hits_device(self._h, C.byref(shapes_struct(shp)), d_count or None, d_ends or None, stream or None))
+
+    def shape_cover(self, shp, d_covered: int = 0, d_mask: int = 0, *, stream: int = 0) -> None:
+        """Per sample the bytes that lie inside a match of the shapes `shp`, as int64[S], and per byte the patterns it lies
+        inside, as u8[N] (bit k: pattern k), into caller-owned device memory (either may be 0, not both;
+        tgx_corpus_shape_cover_device).  This corpus is only read."""
+        check(lib.tgx_corpus_shape_cover_device(self._h, C.byref(shapes_struct(shp)), d_covered or None, d_mask or None, stream or None))
 
     def redact(self, d_mask: int, replacements, *, stream: int = 0) -> "NativeCorpus":
         """A new resident corpus of the same rows in which every run of bytes of one class of the device mask u8[N] (the

@@ -1,8 +1,8 @@
 // The *_host twins of the result-side device entry points (include/tgx.h): tgx_layout_pad_host, tgx_layout_pack_host,
-// tgx_layout_windows_host, tgx_assemble_host, tgx_fim_host, tgx_select_host, tgx_select_text_host, tgx_shuffled_rows_host, tgx_first_equal_host, tgx_minhash_host, tgx_minhash_bands_host, tgx_minhash_near_first_host, tgx_gram_keys_host, tgx_gram_hits_host, tgx_gram_contains_host, tgx_repeat_stats_host, tgx_text_stats_host, tgx_lines_host, tgx_word_stats_host (include/tgx_words.h), tgx_words_host and tgx_word_key (include/tgx_word_ids.h), tgx_phrase_hits_host (include/tgx_phrases.h), tgx_dfa_hits_host (include/tgx_patterns.h), tgx_dfa_cover_host and tgx_redact_host (include/tgx_redact.h), tgx_decode_rows_host, tgx_spans_host, tgx_window_spans_host, tgx_front_host,
+// tgx_layout_windows_host, tgx_assemble_host, tgx_fim_host, tgx_select_host, tgx_select_text_host, tgx_shuffled_rows_host, tgx_first_equal_host, tgx_minhash_host, tgx_minhash_bands_host, tgx_minhash_near_first_host, tgx_gram_keys_host, tgx_gram_hits_host, tgx_gram_contains_host, tgx_repeat_stats_host, tgx_text_stats_host, tgx_lines_host, tgx_word_stats_host (include/tgx_words.h), tgx_words_host and tgx_word_key (include/tgx_word_ids.h), tgx_phrase_hits_host (include/tgx_phrases.h), tgx_dfa_hits_host (include/tgx_patterns.h), tgx_dfa_cover_host and tgx_redact_host (include/tgx_redact.h), tgx_shape_hits_host and tgx_shape_cover_host (include/tgx_shapes.h), tgx_decode_rows_host, tgx_spans_host, tgx_window_spans_host, tgx_front_host,
 // tgx_normalize_host and tgx_lattice_stats_host, and the
 // argument checks they share with the device entry points of tgx_api.cpp.  A twin goes through the same index arithmetic as its kernels (layout.h, assemble.h,
-// fim.h, select.h, dedup.h, minhash.h, gram.h, repeat.h, textstat.h, wordstat.h, words.h, dfa.h, cover.h, redact.h, decode.h, spans.h, front.h, norm.h) on host memory.  Nothing in this file calls a HIP function, so it builds and runs without the
+// fim.h, select.h, dedup.h, minhash.h, gram.h, repeat.h, textstat.h, wordstat.h, words.h, dfa.h, cover.h, redact.h, shape.h, decode.h, spans.h, front.h, norm.h) on host memory.  Nothing in this file calls a HIP function, so it builds and runs without the
 // handles, the pool or a device.
 #define TGX_HOST_ONLY  // tile_fill.h: the host loop, no kernel side
 #include <algorithm>
@@ -28,6 +28,7 @@
 #include "redact.h"
 #include "repeat.h"
 #include "select.h"
+#include "shape.h"
 #include "spans.h"
 #include "textstat.h"
 #include "unicode_tables.h"
@@ -36,6 +37,7 @@
 #include "../../include/tgx_patterns.h"
 #include "../../include/tgx_phrases.h"
 #include "../../include/tgx_redact.h"
+#include "../../include/tgx_shapes.h"
 #include "../../include/tgx_word_ids.h"
 #include "../../include/tgx_words.h"
 
@@ -1716,6 +1718,131 @@ tgx_status tgx_redact_host(const uint8_t* text, const uint64_t* offs, uint64_t n
                 std::copy(table->bytes[cls[l]], table->bytes[cls[l]] + len[l], out_text + at);
         }
     });
+    return TGX_OK;
+}
+
+// ---- shapes: fixed-length class sequences (include/tgx_shapes.h) -----------------------------------
+
+namespace {
+
+// The rows' sums of a chunk's marked lanes by the kernels' store / add rule, stretch by stretch.
+void shape_row_sums_host(const uint64_t* offs, uint64_t c0, uint32_t n_in, const uint64_t* row, uint64_t marked, int64_t* sums) {
+    for (uint32_t a = 0; a < n_in;) {  // the stretch [a, b] of one row
+        uint32_t b = a;
+        while (b + 1 < n_in && row[b + 1] == row[a]) b++;
+        const uint64_t i = row[a], v = tgx::textstat_popc(marked & tgx::textstat_span(a, b));
+        if (tgx::textstat_row_inside(offs, i, c0))
+            sums[i] = (int64_t)v;
+        else if (tgx::textstat_adds(v))
+            sums[i] += (int64_t)v;
+        a = b + 1;
+    }
+}
+
+// The twin of shape_ends_kernel: the chunks of textstat_walk_host, both registers of words, the six doubling steps lane
+// by lane with the kernel's rotate of the halo (its lanes below d go stale here too), ROWOK, the last positions, both
+// guards and the store / add rule.  The source and the shapes have been checked, S > 0; count and ends may each be NULL.
+template <uint32_t NW>
+void shape_ends_host(const uint8_t* text, const uint64_t* offs, uint64_t S, const tgx_shapes* shp, int64_t* count, uint8_t* ends) {
+    using Word = tgx::ShapeWord<NW>;
+    constexpr uint32_t L = tgx::kTextstatChunk;
+    std::vector<uint64_t> words(tgx::kShapeTableWords<NW>);
+    tgx::shape_build_table<NW>(shp->n_patterns, shp->len, shp->cls, shp->not_before, shp->not_after, words.data());
+    const tgx::ShapeTable<NW>& tab = *reinterpret_cast<const tgx::ShapeTable<NW>*>(words.data());
+    if (count) std::fill(count, count + S, 0);  // the launcher's pre-set
+    textstat_walk_host(text, offs, S, [&](uint64_t c0, uint32_t n_in, uint64_t, const uint64_t* row) {
+        const bool has_halo = c0 >= L;
+        Word own[L], halo[L], rot[L], below[L];
+        for (uint32_t l = 0; l < L; l++) {
+            own[l] = l < n_in ? tab.b[text[c0 + l]] : tgx::shape_zero<NW>();
+            halo[l] = has_halo ? tab.b[text[c0 - L + l]] : tgx::shape_zero<NW>();
+        }
+        for (uint32_t s = 0, d = 1; s < tgx::kShapeSteps; s++, d <<= 1) {
+            for (uint32_t l = 0; l < L; l++) {  // the shuffles read every lane as it was before the step
+                rot[l] = halo[(l - d) & 63u];
+                below[l] = own[l >= d ? l - d : l];
+            }
+            for (uint32_t l = 0; l < L; l++) {
+                if (l >= d) halo[l] = tgx::shape_step<NW>(halo[l], rot[l], d, tab.z[s]);
+                own[l] = tgx::shape_step<NW>(own[l], l >= d ? below[l] : rot[l], d, tab.z[s]);
+            }
+        }
+        uint64_t tagged = 0;
+        for (uint32_t l = 0; l < n_in; l++) {
+            const uint64_t pos = c0 + l, in_row = pos - offs[row[l]], row_end = offs[row[l] + 1];
+            uint32_t e = tgx::shape_last_bits<NW>(tgx::shape_and<NW>(own[l], tab.rowok[in_row < tgx::kShapeMaxLen - 1 ? in_row : tgx::kShapeMaxLen - 1]), tab.last,
+                                                  tab.n_patterns);
+            for (uint32_t used = tab.nb_used; used; used &= used - 1) {
+                const uint32_t k = (uint32_t)__builtin_ctz(used), len = tab.len[k];
+                // the kernel's shuffle: lane (l - len) & 63 of the own chunk when l >= len, of the halo otherwise
+                if (tgx::shape_guarded_before(in_row, len) && ((tab.nb[l >= len ? text[c0 + l - len] : text[c0 - L + ((l - len) & 63u)]] >> k) & 1u)) e &= ~(1u << k);
+            }
+            if (pos + 1 < row_end) e &= ~(uint32_t)tab.na[text[pos + 1]];
+            if (ends) ends[pos] = (uint8_t)e;
+            if (e) tagged |= 1ull << l;
+        }
+        if (count) shape_row_sums_host(offs, c0, n_in, row, tagged, count);
+    });
+}
+
+// The twin of shape_cover_kernel: a chunk's ends and the next chunk's as a pair of ballots per pattern, and every lane's
+// window through shape_covered.
+void shape_cover_host(const uint8_t* text, const uint64_t* offs, uint64_t S, const tgx_shapes* shp, const uint8_t* ends, int64_t* covered, uint8_t* mask) {
+    const uint64_t N = offs[S];
+    if (covered) std::fill(covered, covered + S, 0);  // the launcher's pre-set
+    textstat_walk_host(text, offs, S, [&](uint64_t c0, uint32_t n_in, uint64_t, const uint64_t* row) {
+        uint8_t m[tgx::kTextstatChunk] = {};
+        for (uint32_t k = 0; k < shp->n_patterns; k++) {
+            uint64_t own = 0, next = 0;
+            for (uint32_t l = 0; l < tgx::kTextstatChunk; l++) {
+                if (l < n_in && ((ends[c0 + l] >> k) & 1u)) own |= 1ull << l;
+                if (c0 + tgx::kTextstatChunk + l < N && ((ends[c0 + tgx::kTextstatChunk + l] >> k) & 1u)) next |= 1ull << l;
+            }
+            for (uint32_t l = 0; l < n_in; l++)
+                if (tgx::shape_covered(own, next, l, shp->len[k])) m[l] |= (uint8_t)(1u << k);
+        }
+        uint64_t marked = 0;
+        for (uint32_t l = 0; l < n_in; l++) {
+            if (mask) mask[c0 + l] = m[l];
+            if (m[l]) marked |= 1ull << l;
+        }
+        if (covered) shape_row_sums_host(offs, c0, n_in, row, marked, covered);
+    });
+}
+
+// what the two twins' entries share: the checks, in the device calls' order
+tgx_status shape_check_host(const char* who, const uint8_t* text, const uint64_t* offs, uint64_t n_rows, const tgx_shapes* shp, const void* out_rows,
+                            const void* out_bytes, const char* rows_name, const char* bytes_name) {
+    const tgx_status st = textstat_check_source_host(who, text, offs, n_rows);
+    if (st != TGX_OK) return st;
+    if (!shp) return fail(TGX_ERR_INVALID, "%s: shapes is NULL", who);
+    if (const char* why = tgx::shape_check(shp->n_patterns, shp->len, shp->cls)) return fail(TGX_ERR_INVALID, "%s: %s", who, why);
+    if (!out_rows && !out_bytes) return fail(TGX_ERR_INVALID, "%s: %s and %s are both NULL", who, rows_name, bytes_name);
+    return TGX_OK;
+}
+
+void shape_ends_host_any(const uint8_t* text, const uint64_t* offs, uint64_t S, const tgx_shapes* shp, int64_t* count, uint8_t* ends) {
+    if (tgx::shape_nw(tgx::shape_total(shp->n_patterns, shp->len)) == 1)
+        shape_ends_host<1>(text, offs, S, shp, count, ends);
+    else
+        shape_ends_host<2>(text, offs, S, shp, count, ends);
+}
+
+}  // namespace
+
+tgx_status tgx_shape_hits_host(const uint8_t* text, const uint64_t* offs, uint64_t n_rows, const tgx_shapes* shapes, int64_t* count, uint8_t* ends) {
+    const tgx_status st = shape_check_host("tgx_shape_hits_host", text, offs, n_rows, shapes, count, ends, "count", "ends");
+    if (st != TGX_OK || n_rows == 0) return st;
+    shape_ends_host_any(text, offs, n_rows, shapes, count, ends);
+    return TGX_OK;
+}
+
+tgx_status tgx_shape_cover_host(const uint8_t* text, const uint64_t* offs, uint64_t n_rows, const tgx_shapes* shapes, int64_t* covered, uint8_t* mask) {
+    const tgx_status st = shape_check_host("tgx_shape_cover_host", text, offs, n_rows, shapes, covered, mask, "covered", "mask");
+    if (st != TGX_OK || n_rows == 0) return st;
+    std::vector<uint8_t> ends(offs[n_rows]);  // the device call's scratch
+    shape_ends_host_any(text, offs, n_rows, shapes, nullptr, ends.data());
+    shape_cover_host(text, offs, n_rows, shapes, ends.data(), covered, mask);
     return TGX_OK;
 }
 

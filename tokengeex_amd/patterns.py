@@ -456,3 +456,101 @@ def compile_pattern(patterns, fold_case: bool = False, search: bool = True, cove
         tag[s] = tags[i]
         nxt[:, s] = np.array([names[block[t]] for t in trans[i]], np.uint8)[cls]
     return BytePattern(n, 0, nxt, tag, sources)
+
+
+# ---- shapes: fixed-length sequences of byte classes (include/tgx_shapes.h; csrc/shape.hip) ----------------
+SHAPE_MAX_LEN = 64        # TGX_SHAPE_MAX_LEN
+SHAPES_MAX_BITS = 128     # TGX_SHAPES_MAX_BITS
+SHAPES_MAX_PATTERNS = 8   # TGX_SHAPES_MAX_PATTERNS
+
+
+class ShapePattern:
+    """Compiled shapes: .n_patterns, .len (uint32 [8]), .cls (uint8 [128, 32]: position q of the patterns laid end to
+    end, byte b at bit b & 7 of cls[q][b >> 3]), .not_before and .not_after (uint8 [8, 32]) as numpy, the fields of
+    tgx_shapes, and .patterns, the sources as bytes."""
+
+    def __init__(self, lens, cls, not_before, not_after, patterns=()):
+        self.n_patterns, self.patterns = len(lens), tuple(patterns)
+        self.len = np.zeros(SHAPES_MAX_PATTERNS, np.uint32)
+        self.len[:len(lens)] = lens
+        self.cls = np.ascontiguousarray(cls, dtype=np.uint8)
+        self.not_before = np.ascontiguousarray(not_before, dtype=np.uint8)
+        self.not_after = np.ascontiguousarray(not_after, dtype=np.uint8)
+        assert self.cls.shape == (SHAPES_MAX_BITS, 32) and self.not_before.shape == self.not_after.shape == (SHAPES_MAX_PATTERNS, 32)
+
+    def __repr__(self):
+        return f"ShapePattern({list(self.patterns)!r}, len={self.len[:self.n_patterns].tolist()})"
+
+
+_NO_SHAPE = "a shape is a fixed-length sequence of byte classes"
+
+
+def _shape_atoms(src: bytes, node, top: bool = True):
+    """a pattern's tree -> the sets of its positions, or ValueError naming the construct that is no shape"""
+    kind = node[0]
+    if kind == "set":
+        return [node[1]]
+    if kind == "alt":
+        raise ValueError(f"pattern {src!r}: an alternation (|): {_NO_SHAPE}")
+    if kind == "cat":
+        atoms = [a for item in node[1] for a in _shape_atoms(src, item, False)]
+        if not top and len(node[1]) != 1:
+            raise ValueError(f"pattern {src!r}: a group around {len(node[1])} atoms: {_NO_SHAPE}")
+        return atoms
+    _, sub, m, n = node
+    if m != n:
+        what = {(0, None): "*", (1, None): "+", (0, 1): "?"}.get((m, n), f"{{{m},{'' if n is None else n}}}")
+        raise ValueError(f"pattern {src!r}: the quantifier {what}: {_NO_SHAPE} (an atom may have {{m}} and nothing else)")
+    atoms = _shape_atoms(src, sub, False)
+    if len(atoms) != 1 or sub[0] == "rep":
+        raise ValueError(f"pattern {src!r}: a {{m}} of more than one atom: {_NO_SHAPE}")
+    return atoms * m
+
+
+def _set_bytes(mask: int) -> np.ndarray:
+    return np.frombuffer(mask.to_bytes(32, "little"), np.uint8)
+
+
+def compile_shapes(patterns, fold_case: bool = False) -> ShapePattern:
+    """-> a ShapePattern of one pattern or of a list of up to 8, pattern k marking its matches with bit k (shape_hits,
+    shape_cover, redact_patterns(shapes=True)).  A pattern is bytes or str, or a tuple (pattern, not_before,
+    not_after) whose guards are a [...] class or "": the byte in front of a match must not be in not_before, the byte
+    behind it not in not_after (a row's ends pass every guard).  The pattern is a sequence of single-byte atoms, literals,
+    escapes, `.` and [...], each with an optional {m}: `AKIA[0-9A-Z]{16}`, `ghp_[0-9a-zA-Z]{36}`, ("[0-9a-f]{32}",
+    "[0-9a-f]", "[0-9a-f]").  ValueError: a syntax error, any other construct (named: |, * + ?, {m,n}, a group around more
+    than one atom), a length of 0 or over 64, a total over 128 positions, more than 8 patterns (the message carries the
+    number).  fold_case adds the other ASCII case to every literal and class, the guards' too."""
+    if isinstance(patterns, (str, bytes, bytearray)) or (isinstance(patterns, tuple) and len(patterns) == 3 and not isinstance(patterns[0], tuple)):
+        patterns = [patterns]
+    patterns = list(patterns)
+    if not 1 <= len(patterns) <= SHAPES_MAX_PATTERNS:
+        raise ValueError(f"{len(patterns)} patterns: 1 to {SHAPES_MAX_PATTERNS} go into one set of shapes")
+
+    def source(p):
+        return p.encode("utf-8") if isinstance(p, str) else bytes(p)
+
+    lens, sets, sources = [], [], []
+    guards = np.zeros((2, SHAPES_MAX_PATTERNS, 32), np.uint8)
+    for k, p in enumerate(patterns):
+        src, before, after = (source(x) for x in (p if isinstance(p, tuple) else (p, b"", b"")))
+        atoms = _shape_atoms(src, _Parser(src, fold_case).parse())
+        if not 1 <= len(atoms) <= SHAPE_MAX_LEN:
+            raise ValueError(f"pattern {src!r}: a length of {len(atoms)}: a shape has 1 to {SHAPE_MAX_LEN} positions" +
+                             (" (it matches the empty string)" if not atoms else ""))
+        if any(a == 0 for a in atoms):
+            raise ValueError(f"pattern {src!r}: an empty class matches nothing")
+        for side, g in enumerate((before, after)):
+            if g:
+                one = _shape_atoms(g, _Parser(g, fold_case).parse())
+                if len(one) != 1:
+                    raise ValueError(f"guard {g!r}: a guard is one class of bytes, [...], or \"\"")
+                guards[side, k] = _set_bytes(one[0])
+        lens.append(len(atoms))
+        sets += atoms
+        sources.append(src)
+    if len(sets) > SHAPES_MAX_BITS:
+        raise ValueError(f"{len(sets)} positions in all: one set of shapes has at most {SHAPES_MAX_BITS}")
+    cls = np.zeros((SHAPES_MAX_BITS, 32), np.uint8)
+    for q, mask in enumerate(sets):
+        cls[q] = _set_bytes(mask)
+    return ShapePattern(lens, cls, guards[0], guards[1], sources)

@@ -699,13 +699,18 @@ def redact(corpus: "_lib.NativeCorpus", mask, replacements) -> "_lib.NativeCorpu
     return corpus.redact(ptr if corpus.num_bytes else 0, list(replacements), stream=torch.cuda.current_stream(dev).cuda_stream)
 
 
-def redact_patterns(corpus: "_lib.NativeCorpus", patterns, replacements, fold_case: bool = False) -> "_lib.NativeCorpus":
+def redact_patterns(corpus: "_lib.NativeCorpus", patterns, replacements, fold_case: bool = False, shapes: bool = False) -> "_lib.NativeCorpus":
     """-> a new resident corpus in which every stretch of bytes inside matches of patterns[k] is replaced by
     replacements[k]: compile_pattern(..., fold_case, cover=True), pattern_cover and redact.  Where matches of two
     patterns overlap, the bytes they share go to the pattern with the lower index.  Patterns that fit one automaton of
     16 states a side share a cover pass; the list is cut, in order, into the fewest such groups from the left (e-mail
     and IPv4 together need 33 forward states, so they take a pass each), and the groups' masks are OR-ed.
-        redact_patterns(corpus, [email, ipv4], ["<EMAIL>", "<IP_ADDRESS>"])"""
+        redact_patterns(corpus, [email, ipv4], ["<EMAIL>", "<IP_ADDRESS>"])
+    shapes=True also serves the fixed-length class sequences that no automaton of 16 states holds (compile_shapes,
+    shape_cover): a tuple (pattern, not_before, not_after) is always a shape, and so is a plain pattern that does not
+    compile alone as a cover automaton.  The shapes are cut from the left into the fewest groups of at most 8 patterns
+    and 128 positions, a cover pass each, and every mask lands on its pattern's index.
+        redact_patterns(corpus, [email, ("[0-9a-f]{32}", "[0-9a-f]", "[0-9a-f]"), "AKIA[0-9A-Z]{16}"], ["<EMAIL>", "<KEY>", "<KEY>"], shapes=True)"""
     import torch
     from . import patterns as _patterns
     if isinstance(patterns, (str, bytes, bytearray)):
@@ -713,22 +718,89 @@ def redact_patterns(corpus: "_lib.NativeCorpus", patterns, replacements, fold_ca
     patterns = list(patterns)
     if len(patterns) != len(replacements) or not 1 <= len(patterns) <= _lib.REDACT_MAX_CLASSES:
         raise ValueError(f"{len(patterns)} patterns and {len(replacements)} replacements: 1 to {_lib.REDACT_MAX_CLASSES} of each, one for one")
-    mask, k = None, 0
-    while k < len(patterns):
-        n = len(patterns) - k
-        while True:  # the longest group from k on that compiles; a pattern that does not compile alone raises
+    as_shape = []  # the indices that take the shapes' pass
+    for k, p in enumerate(patterns if shapes else ()):
+        if not isinstance(p, tuple):
             try:
-                pat = _patterns.compile_pattern(patterns[k:k + n], fold_case=fold_case, cover=True)
+                _patterns.compile_pattern(p, fold_case=fold_case, cover=True)
+                continue
+            except ValueError:
+                pass
+        _patterns.compile_shapes(p, fold_case=fold_case)  # (neither an automaton nor a shape: this one's ValueError)
+        as_shape.append(k)
+    parts = []  # (mask, the index of each of its bits)
+    dfa = [k for k in range(len(patterns)) if k not in as_shape]
+    while dfa:
+        n = len(dfa)
+        while True:  # the longest group from the left that compiles; a pattern that does not compile alone raises
+            try:
+                pat = _patterns.compile_pattern([patterns[k] for k in dfa[:n]], fold_case=fold_case, cover=True)
                 break
             except ValueError:
                 if n == 1:
                     raise
                 n -= 1
-        _, part = pattern_cover(corpus, pat, return_mask=True)
-        part = torch.bitwise_left_shift(part, k) if k else part
+        parts.append((pattern_cover(corpus, pat, return_mask=True)[1], dfa[:n]))
+        dfa = dfa[n:]
+    while as_shape:
+        n = len(as_shape)
+        while True:  # the longest group from the left within 8 patterns and 128 positions
+            try:
+                shp = _patterns.compile_shapes([patterns[k] for k in as_shape[:n]], fold_case=fold_case)
+                break
+            except ValueError:
+                if n == 1:
+                    raise
+                n -= 1
+        parts.append((shape_cover(corpus, shp, return_mask=True)[1], as_shape[:n]))
+        as_shape = as_shape[n:]
+    mask = None
+    for part, where in parts:
+        if where == list(range(where[0], where[0] + len(where))):  # a run of indices: one shift
+            part = torch.bitwise_left_shift(part, where[0]) if where[0] else part
+        else:
+            part = sum(torch.bitwise_left_shift(torch.bitwise_and(torch.bitwise_right_shift(part, b), 1), k) for b, k in enumerate(where))
         mask = part if mask is None else mask | part
-        k += n
     return redact(corpus, mask, replacements)
+
+
+# ---- shapes: fixed-length class sequences as a windowed bit scan (csrc/shape.hip) -------------------------------------------
+
+def _shape_call(corpus: "_lib.NativeCorpus", shp, call, per_byte: bool):
+    import torch
+    from . import patterns
+    dev = _device_of(torch, corpus)
+    if not isinstance(shp, patterns.ShapePattern):
+        shp = patterns.compile_shapes(shp)
+    S, N = corpus.num_samples, corpus.num_bytes
+    rows = torch.empty((S,), dtype=torch.int64, device=dev)
+    byts = torch.empty((N,), dtype=torch.uint8, device=dev) if per_byte else None
+    spare = torch.empty(1, dtype=torch.int64, device=dev)  # (no row: the pointer still says that the counts are asked for)
+    call(corpus, shp, (rows if S else spare).data_ptr(), byts.data_ptr() if per_byte and N else 0, stream=torch.cuda.current_stream(dev).cuda_stream)
+    return (rows, byts) if per_byte else rows
+
+
+def shape_hits(corpus: "_lib.NativeCorpus", shp, return_ends: bool = False):
+    """-> [S] torch.int64 on the corpus's device: per row the bytes at which a match of the shapes `shp` ends, queued on
+    torch's current stream.  shp: a patterns.ShapePattern (patterns.compile_shapes: fixed-length sequences of byte
+    classes, up to 8 patterns of up to 64 positions, 128 in all, each with optional guards), or what compile_shapes
+    takes, which is compiled here.  With return_ends also [N] torch.uint8, at every byte the patterns that end there
+    (bit k: pattern k).  Every row is matched on its own, and a guard never looks outside its row.  What the automata of
+    pattern_hits cannot hold: API keys and tokens such as `AKIA[0-9A-Z]{16}`."""
+    return _shape_call(corpus, shp, _lib.NativeCorpus.shape_hits, return_ends)
+
+
+def shape_rows(corpus: "_lib.NativeCorpus", shp, max_hits: int = 0):
+    """-> torch.int64 indices, ascending, of the rows of the corpus with at most max_hits match ends of `shp`: what
+    `select` takes to drop the others, as pattern_rows."""
+    return (shape_hits(corpus, shp) <= int(max_hits)).nonzero().reshape(-1)
+
+
+def shape_cover(corpus: "_lib.NativeCorpus", shp, return_mask: bool = False):
+    """-> [S] torch.int64 on the corpus's device: per row the bytes that lie inside some match of the shapes `shp`.  With
+    return_mask also [N] torch.uint8, at every byte the patterns it lies inside (bit k: pattern k), what `redact`
+    takes.  Overlapping matches merge: under `a{4}`, all of "aaaaaa" is covered."""
+    return _shape_call(corpus, shp, _lib.NativeCorpus.shape_cover, return_mask)
 
 
 GOPHER_TOP = ((2, .20), (3, .18), (4, .16))
