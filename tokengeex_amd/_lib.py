@@ -253,6 +253,13 @@ PATTERN_SYMBOLS = {
     "tgx_dfa_last_times": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_float), _i]),
 }
 
+# every exported symbol of include/tgx_patterns64.h, a header of its own in the same way: bound and checked at import too
+PATTERN64_SYMBOLS = {
+    "tgx_corpus_dfa64_hits_device": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "tgx_dfa64_hits_host": (_i, [_vp, _vp, _u64, _vp, _vp, _vp]),
+    "tgx_dfa64_last_times": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_float), _i]),
+}
+
 # every exported symbol of include/tgx_redact.h, a header of its own in the same way: bound and checked at import too
 REDACT_SYMBOLS = {
     "tgx_corpus_dfa_cover_device": (_i, [_vp, _vp, _vp, _vp, _vp]),
@@ -316,7 +323,7 @@ def _load() -> C.CDLL:
             "Build it with `python tokengeex_amd/build.py`.")
     _share_torch_hip_runtime()
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(WORD_SYMBOLS.items()) + list(WORDS_SYMBOLS.items()) + list(PHRASE_SYMBOLS.items()) + list(PATTERN_SYMBOLS.items()) + list(REDACT_SYMBOLS.items()) + list(SHAPE_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(WORD_SYMBOLS.items()) + list(WORDS_SYMBOLS.items()) + list(PHRASE_SYMBOLS.items()) + list(PATTERN_SYMBOLS.items()) + list(PATTERN64_SYMBOLS.items()) + list(REDACT_SYMBOLS.items()) + list(SHAPE_SYMBOLS.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args
@@ -1193,6 +1200,53 @@ def dfa_last_times() -> dict[str, float]:
     names = (C.c_char_p * 8)()
     ms = (C.c_float * 8)()
     n = lib.tgx_dfa_last_times(names, ms, 8)
+    return {names[i].decode(): float(ms[i]) for i in range(n)}
+
+
+# ---- byte patterns of up to 64 states (include/tgx_patterns64.h; csrc/dfa64.hip, csrc/dfa64.h) ----
+DFA64_MAX_STATES = 64
+
+
+class TgxDfa64(C.Structure):
+    """tgx_dfa64 of include/tgx_patterns64.h"""
+    _fields_ = [("n_states", C.c_uint32), ("start", C.c_uint32), ("next", (C.c_uint8 * DFA64_MAX_STATES) * 256), ("tag", C.c_uint8 * DFA64_MAX_STATES)]
+
+
+def dfa64_struct(pat) -> TgxDfa64:
+    """An automaton with .n_states, .start, .next (uint8 [256, 64] or [256, 16]) and .tag (uint8 [64] or [16]), such as a
+    patterns.BytePattern of either width, as the 64-state struct of the ABI.  The library checks it."""
+    d = TgxDfa64()
+    d.n_states, d.start = int(pat.n_states), int(pat.start)
+    nxt, tag = np.asarray(pat.next, dtype=np.uint8), np.asarray(pat.tag, dtype=np.uint8)
+    if nxt.ndim != 2 or nxt.shape[0] != 256 or nxt.shape[1] not in (DFA_MAX_STATES, DFA64_MAX_STATES) or tag.shape != (nxt.shape[1],):
+        raise ValueError("an automaton's next is uint8 [256, 64] or [256, 16] and its tag uint8 [64] or [16]")
+    wide, tags = np.zeros((256, DFA64_MAX_STATES), np.uint8), np.zeros(DFA64_MAX_STATES, np.uint8)
+    wide[:, :nxt.shape[1]], tags[:tag.shape[0]] = nxt, tag
+    C.memmove(d.next, wide.ctypes.data, wide.nbytes)
+    C.memmove(d.tag, tags.ctypes.data, tags.nbytes)
+    return d
+
+
+def dfa64_hits_host(text: np.ndarray, offs: np.ndarray, pat):
+    """Host twin of NativeCorpus.dfa64_hits (tgx_dfa64_hits_host: the kernels' chunks, segments, row-start masks, fold,
+    scan, chain and store / add rule through the same header, no device) over text u8[N] and offsets u64[S+1] ->
+    (count int64[S], ends uint8[N])."""
+    text = np.ascontiguousarray(text, dtype=np.uint8)
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    n = max(offs.shape[0] - 1, 0)
+    count = np.full(n, -7, np.int64)
+    ends = np.full(text.size, 7, np.uint8)
+    keep = np.zeros(1, np.int64), np.zeros(1, np.uint8)   # (never NULL: both outputs are asked for)
+    check(lib.tgx_dfa64_hits_host(ptr(text) if text.size else None, ptr(offs) if offs.size else None, n, C.byref(dfa64_struct(pat)),
+                                  ptr(count if n else keep[0]), ptr(ends if ends.size else keep[1])))
+    return count, ends
+
+
+def dfa64_last_times() -> dict[str, float]:
+    """Device time in ms of each stage of the calling thread's last dfa64_hits call (tgx_dfa64_last_times)."""
+    names = (C.c_char_p * 8)()
+    ms = (C.c_float * 8)()
+    n = lib.tgx_dfa64_last_times(names, ms, 8)
     return {names[i].decode(): float(ms[i]) for i in range(n)}
 
 
@@ -2144,6 +2198,13 @@ class NativeCorpus:
         a tagged state, every row beginning in its start state, as int64[S], and per byte that state's tag, as u8[N], into
         caller-owned device memory (either may be 0, not both; tgx_corpus_dfa_hits_device).  This corpus is only read."""
         check(lib.tgx_corpus_dfa_hits_device(self._h, C.byref(dfa_struct(pat)), d_count or None, d_ends or None, stream or None))
+
+    def dfa64_hits(self, pat, d_count: int = 0, d_ends: int = 0, *, stream: int = 0) -> None:
+        """dfa_hits for an automaton of up to 64 states (a patterns.BytePattern of either width, or anything dfa64_struct
+        takes): per sample the bytes after which it is in a tagged state, as int64[S], and every byte's tag, as u8[N],
+        into caller-owned device memory (either may be 0, not both; tgx_corpus_dfa64_hits_device).  This corpus is only
+        read."""
+        check(lib.tgx_corpus_dfa64_hits_device(self._h, C.byref(dfa64_struct(pat)), d_count or None, d_ends or None, stream or None))
 
     def dfa_cover(self, pat, d_covered: int = 0, d_mask: int = 0, *, stream: int = 0) -> None:
         """Per sample the bytes that lie inside a match of the cover pattern `pat` (patterns.compile_pattern(cover=True), or

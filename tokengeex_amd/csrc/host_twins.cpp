@@ -1,8 +1,8 @@
 // The *_host twins of the result-side device entry points (include/tgx.h): tgx_layout_pad_host, tgx_layout_pack_host,
-// tgx_layout_windows_host, tgx_assemble_host, tgx_fim_host, tgx_select_host, tgx_select_text_host, tgx_shuffled_rows_host, tgx_first_equal_host, tgx_minhash_host, tgx_minhash_bands_host, tgx_minhash_near_first_host, tgx_gram_keys_host, tgx_gram_hits_host, tgx_gram_contains_host, tgx_repeat_stats_host, tgx_text_stats_host, tgx_lines_host, tgx_word_stats_host (include/tgx_words.h), tgx_words_host and tgx_word_key (include/tgx_word_ids.h), tgx_phrase_hits_host (include/tgx_phrases.h), tgx_dfa_hits_host (include/tgx_patterns.h), tgx_dfa_cover_host and tgx_redact_host (include/tgx_redact.h), tgx_shape_hits_host and tgx_shape_cover_host (include/tgx_shapes.h), tgx_decode_rows_host, tgx_spans_host, tgx_window_spans_host, tgx_front_host,
+// tgx_layout_windows_host, tgx_assemble_host, tgx_fim_host, tgx_select_host, tgx_select_text_host, tgx_shuffled_rows_host, tgx_first_equal_host, tgx_minhash_host, tgx_minhash_bands_host, tgx_minhash_near_first_host, tgx_gram_keys_host, tgx_gram_hits_host, tgx_gram_contains_host, tgx_repeat_stats_host, tgx_text_stats_host, tgx_lines_host, tgx_word_stats_host (include/tgx_words.h), tgx_words_host and tgx_word_key (include/tgx_word_ids.h), tgx_phrase_hits_host (include/tgx_phrases.h), tgx_dfa_hits_host (include/tgx_patterns.h), tgx_dfa64_hits_host (include/tgx_patterns64.h), tgx_dfa_cover_host and tgx_redact_host (include/tgx_redact.h), tgx_shape_hits_host and tgx_shape_cover_host (include/tgx_shapes.h), tgx_decode_rows_host, tgx_spans_host, tgx_window_spans_host, tgx_front_host,
 // tgx_normalize_host and tgx_lattice_stats_host, and the
 // argument checks they share with the device entry points of tgx_api.cpp.  A twin goes through the same index arithmetic as its kernels (layout.h, assemble.h,
-// fim.h, select.h, dedup.h, minhash.h, gram.h, repeat.h, textstat.h, wordstat.h, words.h, dfa.h, cover.h, redact.h, shape.h, decode.h, spans.h, front.h, norm.h) on host memory.  Nothing in this file calls a HIP function, so it builds and runs without the
+// fim.h, select.h, dedup.h, minhash.h, gram.h, repeat.h, textstat.h, wordstat.h, words.h, dfa.h, dfa64.h, cover.h, redact.h, shape.h, decode.h, spans.h, front.h, norm.h) on host memory.  Nothing in this file calls a HIP function, so it builds and runs without the
 // handles, the pool or a device.
 #define TGX_HOST_ONLY  // tile_fill.h: the host loop, no kernel side
 #include <algorithm>
@@ -18,6 +18,7 @@
 #include "decode.h"
 #include "dedup.h"
 #include "dfa.h"
+#include "dfa64.h"
 #include "fim.h"
 #include "front.h"
 #include "gram.h"
@@ -35,6 +36,7 @@
 #include "words.h"
 #include "wordstat.h"
 #include "../../include/tgx_patterns.h"
+#include "../../include/tgx_patterns64.h"
 #include "../../include/tgx_phrases.h"
 #include "../../include/tgx_redact.h"
 #include "../../include/tgx_shapes.h"
@@ -1843,6 +1845,79 @@ tgx_status tgx_shape_cover_host(const uint8_t* text, const uint64_t* offs, uint6
     std::vector<uint8_t> ends(offs[n_rows]);  // the device call's scratch
     shape_ends_host_any(text, offs, n_rows, shapes, nullptr, ends.data());
     shape_cover_host(text, offs, n_rows, shapes, ends.data(), covered, mask);
+    return TGX_OK;
+}
+
+// ---- a DFA of up to 64 states over the bytes of every row (include/tgx_patterns64.h) ----------------
+
+// The twin of dfa64.hip's stages: every chunk's map, a state a run, and its row-start mask on the chunks of
+// textstat_walk_host (the identity and 0 past the corpus's end); the chunks folded into their segment's record; the
+// records folded into their group's, the groups chained from `start` and every group's segments from its entry; every
+// segment's chunks chained from its entry and walked from there; and the counts by the store / add rule.
+tgx_status tgx_dfa64_hits_host(const uint8_t* text, const uint64_t* offs, uint64_t n_rows, const tgx_dfa64* dfa, int64_t* count, uint8_t* ends) {
+    const char* who = "tgx_dfa64_hits_host";
+    const tgx_status st = textstat_check_source_host(who, text, offs, n_rows);
+    if (st != TGX_OK) return st;
+    if (!dfa) return fail(TGX_ERR_INVALID, "%s: dfa is NULL", who);
+    if (const char* why = tgx::dfa64_check(dfa->n_states, dfa->start, dfa->next, dfa->tag)) return fail(TGX_ERR_INVALID, "%s: %s", who, why);
+    if (!count && !ends) return fail(TGX_ERR_INVALID, "%s: count and ends are both NULL", who);
+    if (n_rows == 0) return TGX_OK;
+    const uint64_t S = n_rows, N = offs[S], n_segs = tgx::dfa64_segs(N), n_groups = tgx::dfa64_groups(n_segs);
+    const uint32_t start = dfa->start;
+    std::vector<uint8_t> table(tgx::kDfa64TableBytes);
+    tgx::dfa64_build_table(dfa->n_states, dfa->next, dfa->tag, table.data());
+    const uint8_t *next = table.data(), *tag = next + 256 * tgx::kDfa64MaxStates;
+    // dfa64_map_kernel
+    std::vector<uint8_t> cmap(n_segs * tgx::kDfa64Seg), srec(n_segs * tgx::kDfa64Map), grec(n_groups * tgx::kDfa64Map), gentry(n_groups), sentry(n_segs);
+    std::vector<uint64_t> cmask(n_segs * tgx::kDfa64SegChunks, 0);
+    for (uint64_t k = 0; k < n_segs * tgx::kDfa64SegChunks; k++) tgx::dfa64_identity(&cmap[k * tgx::kDfa64Map]);
+    textstat_walk_host(text, offs, S, [&](uint64_t c0, uint32_t n_in, uint64_t, const uint64_t* row) {
+        const uint64_t chunk = c0 / tgx::kDfa64Chunk;
+        for (uint32_t l = 0; l < n_in; l++)
+            if (c0 + l == offs[row[l]]) cmask[chunk] |= 1ull << l;
+        for (uint32_t s = 0; s < tgx::kDfa64Map; s++) {
+            uint32_t q = s;
+            for (uint32_t l = 0; l < n_in; l++) q = tgx::dfa64_step(next, q, text[c0 + l], (cmask[chunk] >> l) & 1ull, start);
+            cmap[chunk * tgx::kDfa64Map + s] = (uint8_t)q;
+        }
+    });
+    for (uint64_t seg = 0; seg < n_segs; seg++) {
+        uint8_t* rec = &srec[seg * tgx::kDfa64Map];
+        tgx::dfa64_identity(rec);
+        for (uint32_t k = 0; k < tgx::kDfa64SegChunks; k++) tgx::dfa64_fold(rec, &cmap[(seg * tgx::kDfa64SegChunks + k) * tgx::kDfa64Map]);
+    }
+    // dfa64_scan
+    for (uint64_t g = 0; g < n_groups; g++) {
+        uint8_t* rec = &grec[g * tgx::kDfa64Map];
+        tgx::dfa64_identity(rec);
+        for (uint64_t seg = g * tgx::kDfa64Group; seg < n_segs && seg < (g + 1) * tgx::kDfa64Group; seg++) tgx::dfa64_fold(rec, &srec[seg * tgx::kDfa64Map]);
+    }
+    tgx::dfa64_chain_host(grec.data(), n_groups, start, gentry.data());
+    for (uint64_t g = 0; g < n_groups; g++) {
+        const uint64_t first = g * tgx::kDfa64Group, n = n_segs - first < tgx::kDfa64Group ? n_segs - first : tgx::kDfa64Group;
+        tgx::dfa64_chain_host(&srec[first * tgx::kDfa64Map], n, gentry[g], &sentry[first]);
+    }
+    // dfa64_replay_kernel
+    std::vector<uint8_t> own_tags(ends ? 0 : N);
+    uint8_t* tags = ends ? ends : own_tags.data();
+    for (uint64_t seg = 0; seg < n_segs; seg++) {
+        uint8_t entry[tgx::kDfa64SegChunks];
+        tgx::dfa64_chain_host(&cmap[seg * tgx::kDfa64Seg], tgx::kDfa64SegChunks, sentry[seg], entry);
+        for (uint32_t k = 0; k < tgx::kDfa64SegChunks; k++) {
+            const uint64_t chunk = seg * tgx::kDfa64SegChunks + k, c0 = chunk * tgx::kDfa64Chunk;
+            uint32_t q = entry[k];
+            for (uint32_t l = 0, n = tgx::dfa64_chunk_bytes(c0, N); l < n; l++) {
+                q = tgx::dfa64_step(next, q, text[c0 + l], (cmask[chunk] >> l) & 1ull, start);
+                tags[c0 + l] = tag[q];
+            }
+        }
+    }
+    // dfa64_count_kernel
+    if (!count) return TGX_OK;
+    std::fill(count, count + S, 0);  // the launcher's pre-set
+    textstat_walk_host(text, offs, S, [&](uint64_t c0, uint32_t n_in, uint64_t, const uint64_t* row) {
+        shape_row_sums_host(offs, c0, n_in, row, textstat_mask_host(tags, c0, n_in, [](uint8_t t) { return t != 0; }), count);
+    });
     return TGX_OK;
 }
 

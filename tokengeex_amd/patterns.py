@@ -8,6 +8,11 @@ Pure Python over bytes: a parser, Thompson's NFA, the subset construction (with 
 every byte, which is the automaton of .*R: it marks where a match of R ENDS) and Moore's minimisation.  The device
 serves automata of at most 16 states; a pattern that needs more raises ValueError with the count.
 
+    pat = compile_pattern(r"\\(?\\d{3}\\)?[ .-]?\\d{3}[ .-]?\\d{4}", max_states=64)   # a phone shape: 17 states
+
+With max_states=64 the automaton may have up to 64 states; one of more than 16 is run by the kernels of csrc/dfa64.hip (a
+lane per state, then a lane per chunk: include/tgx_patterns64.h: tgx_dfa64).
+
     pat = compile_pattern(r"\\d{3}-\\d{2}-\\d{4}", cover=True)                     # 12 forward and 11 backward states
 
 With cover=True the pattern also carries a backward automaton and a table over the pairs of states, which together say
@@ -22,6 +27,7 @@ from __future__ import annotations
 import numpy as np
 
 MAX_STATES = 16      # TGX_DFA_MAX_STATES
+MAX_STATES64 = 64    # TGX_DFA64_MAX_STATES
 MAX_PATTERNS = 8     # one tag bit each
 MAX_SUBSETS = 4096   # the subset construction gives up beyond this many states
 MAX_REPEAT = 256     # of one {m,n}
@@ -280,13 +286,15 @@ def _byte_classes(masks):
 
 class BytePattern:
     """A compiled automaton: .n_states, .start, .next (uint8 [256, 16]: next[b][s]), .tag (uint8 [16]: bit k set in an
-    accepting state of pattern k) as numpy, the fields of tgx_dfa, and .patterns, the sources as bytes."""
+    accepting state of pattern k) as numpy, the fields of tgx_dfa, and .patterns, the sources as bytes.  One of more
+    than 16 states (compile_pattern(..., max_states=64)) has the fields of tgx_dfa64: .next [256, 64] and .tag [64]."""
 
     def __init__(self, n_states, start, nxt, tag, patterns=()):
         self.n_states, self.start, self.patterns = int(n_states), int(start), tuple(patterns)
         self.next = np.ascontiguousarray(nxt, dtype=np.uint8)
         self.tag = np.ascontiguousarray(tag, dtype=np.uint8)
-        assert self.next.shape == (256, MAX_STATES) and self.tag.shape == (MAX_STATES,)
+        width = MAX_STATES if self.n_states <= MAX_STATES else MAX_STATES64
+        assert self.next.shape == (256, width) and self.tag.shape == (width,)
 
     def __repr__(self):
         return f"BytePattern({list(self.patterns)!r}, n_states={self.n_states})"
@@ -385,7 +393,7 @@ def _compile_cover(nfa, first, accept, owner, cls, reps, sources) -> BytePattern
     return pat
 
 
-def compile_pattern(patterns, fold_case: bool = False, search: bool = True, cover: bool = False) -> BytePattern:
+def compile_pattern(patterns, fold_case: bool = False, search: bool = True, cover: bool = False, max_states: int = MAX_STATES) -> BytePattern:
     """-> a BytePattern of one pattern (bytes or str) or of a list of up to 8, pattern k tagging its matches with bit k.
     search=True: the automaton of .*R, whose tag at a byte says that a match ends there (what pattern_hits counts);
     search=False: the automaton of R itself from a row's first byte, with a dead state.  fold_case adds the other ASCII
@@ -395,7 +403,14 @@ def compile_pattern(patterns, fold_case: bool = False, search: bool = True, cove
     to its first, and .cover, uint8 [16, 16]: cover[f][g] has bit k set iff a byte after which the forward automaton is
     in f, and before which the backward one is in g, lies inside a match of pattern k.  The forward automaton still
     tags match ends, but is a larger one than without cover; more than 16 states on either side is a ValueError that
-    names the side."""
+    names the side.
+    max_states=64 (pattern_hits, pattern_rows): up to 64 states after minimisation, and a ValueError with the count above
+    that; an automaton of more than 16 has .next [256, 64] and .tag [64].  Any value but 16 and 64 is a ValueError, and so
+    is 64 with cover=True: cover and redaction keep their 16 states."""
+    if max_states not in (MAX_STATES, MAX_STATES64):
+        raise ValueError(f"max_states={max_states!r}: an automaton has at most {MAX_STATES} states, or {MAX_STATES64} with max_states={MAX_STATES64}")
+    if cover and max_states != MAX_STATES:
+        raise ValueError(f"cover=True keeps the limit of {MAX_STATES} states on either side")
     if isinstance(patterns, (str, bytes, bytearray)):
         patterns = [patterns]
     sources = [p.encode("utf-8") if isinstance(p, str) else bytes(p) for p in patterns]
@@ -427,7 +442,7 @@ def compile_pattern(patterns, fold_case: bool = False, search: bool = True, cove
                 moved |= first
             if moved not in index:
                 if len(subsets) >= MAX_SUBSETS:
-                    raise ValueError(f"more than {MAX_SUBSETS} states before minimisation: the limit after it is {MAX_STATES}")
+                    raise ValueError(f"more than {MAX_SUBSETS} states before minimisation: the limit after it is {max_states}")
                 index[moved] = len(subsets)
                 subsets.append(moved)
             row.append(index[moved])
@@ -448,9 +463,10 @@ def compile_pattern(patterns, fold_case: bool = False, search: bool = True, cove
     for i in range(len(subsets)):  # blocks numbered by their first member: the start is state 0
         names.setdefault(block[i], len(names))
     n = len(names)
-    if n > MAX_STATES:
-        raise ValueError(f"the automaton has {n} states after minimisation: the limit is {MAX_STATES}")
-    nxt, tag = np.zeros((256, MAX_STATES), np.uint8), np.zeros(MAX_STATES, np.uint8)
+    if n > max_states:
+        raise ValueError(f"the automaton has {n} states after minimisation: the limit is {max_states}")
+    width = MAX_STATES if n <= MAX_STATES else MAX_STATES64
+    nxt, tag = np.zeros((256, width), np.uint8), np.zeros(width, np.uint8)
     for i in range(len(subsets)):
         s = names[block[i]]
         tag[s] = tags[i]

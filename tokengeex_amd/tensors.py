@@ -639,7 +639,8 @@ def autogenerated_rows(corpus: "_lib.NativeCorpus", head_lines: int = 5, phrases
 def pattern_hits(corpus: "_lib.NativeCorpus", pat, return_ends: bool = False):
     """-> [S] torch.int64 on the corpus's device: per row the bytes at which a match of `pat` ends, queued on torch's
     current stream.  pat: a patterns.BytePattern (patterns.compile_pattern: regex-class syntax, up to 8 patterns and 16
-    states), or a pattern or list of patterns, which is compiled here.  With return_ends also [N] torch.uint8, at every
+    states, or 64 with max_states=64: one of more than 16 states runs on the kernels of csrc/dfa64.hip), or a pattern or
+    list of patterns, which is compiled here for 16 states.  With return_ends also [N] torch.uint8, at every
     byte the patterns that end there (bit k: pattern k; 0: none).  Every row is matched on its own: no match crosses a
     row's end.  Matches are counted by their ends, so "aaa" holds two ends of `aa`, and one end of `a+b` however many
     starts it has."""
@@ -652,7 +653,8 @@ def pattern_hits(corpus: "_lib.NativeCorpus", pat, return_ends: bool = False):
     count = torch.empty((S,), dtype=torch.int64, device=dev)
     ends = torch.empty((N,), dtype=torch.uint8, device=dev) if return_ends else None
     spare = torch.empty(1, dtype=torch.int64, device=dev)  # (no row: the pointer still says that the counts are asked for)
-    corpus.dfa_hits(pat, (count if S else spare).data_ptr(), ends.data_ptr() if return_ends and N else 0, stream=torch.cuda.current_stream(dev).cuda_stream)
+    hits = corpus.dfa_hits if pat.n_states <= patterns.MAX_STATES else corpus.dfa64_hits
+    hits(pat, (count if S else spare).data_ptr(), ends.data_ptr() if return_ends and N else 0, stream=torch.cuda.current_stream(dev).cuda_stream)
     return (count, ends) if return_ends else count
 
 
