@@ -278,6 +278,19 @@ SHAPE_SYMBOLS = {
     "tgx_shapes_last_times": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_float), _i]),
 }
 
+# every exported symbol of include/tgx_hashed.h, a header of its own in the same way: bound and checked at import too
+HASHED_SYMBOLS = {
+    "tgx_result_hashed_counts_device": (_i, [_vp, _vp, _u32, _u64, _u64, _u32, _vp, _vp]),
+    "tgx_corpus_hashed_counts_device": (_i, [_vp, _vp, _u32, _u64, _u64, _u32, _vp, _vp]),
+    "tgx_result_hashed_scores_device": (_i, [_vp, _vp, _u32, _u64, _u32, _u64, _vp, _u32, _vp, _vp]),
+    "tgx_corpus_hashed_scores_device": (_i, [_vp, _vp, _u32, _u64, _u32, _u64, _vp, _u32, _vp, _vp]),
+    "tgx_hashed_bucket": (_u64, [_u64, _u64]),
+    "tgx_hashed_info": (_i, [_u32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "tgx_hashed_counts_host": (_i, [_vp, _u32, _vp, _u64, _vp, _u32, _u64, _u64, _vp]),
+    "tgx_hashed_scores_host": (_i, [_vp, _u32, _vp, _u64, _vp, _u32, _u64, _u32, _u64, _vp, _vp]),
+    "tgx_hashed_last_times": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_float), _i]),
+}
+
 
 class TokenGeeXError(Exception):
     """tokengeex.TokenGeeXError — bindings/python/src/lib.rs:9,33-37; carries the
@@ -323,7 +336,7 @@ def _load() -> C.CDLL:
             "Build it with `python tokengeex_amd/build.py`.")
     _share_torch_hip_runtime()
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(WORD_SYMBOLS.items()) + list(WORDS_SYMBOLS.items()) + list(PHRASE_SYMBOLS.items()) + list(PATTERN_SYMBOLS.items()) + list(PATTERN64_SYMBOLS.items()) + list(REDACT_SYMBOLS.items()) + list(SHAPE_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(WORD_SYMBOLS.items()) + list(WORDS_SYMBOLS.items()) + list(PHRASE_SYMBOLS.items()) + list(PATTERN_SYMBOLS.items()) + list(PATTERN64_SYMBOLS.items()) + list(REDACT_SYMBOLS.items()) + list(SHAPE_SYMBOLS.items()) + list(HASHED_SYMBOLS.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args
@@ -825,6 +838,85 @@ def gram_last_times() -> dict[str, float]:
     ms = (C.c_float * 8)()
     n = lib.tgx_gram_last_times(names, ms, 8)
     return {names[i].decode(): float(ms[i]) for i in range(n)}
+
+
+# ---- hashed n-gram features (include/tgx_hashed.h; csrc/hashed.hip, csrc/hashed.h) ----
+HASHED_FRAC_BITS = 24     # a weight w is the i32 rint(w * 2^24), |w| < 128
+
+
+def _hashed_widths(widths):
+    w = np.ascontiguousarray(list(widths), dtype=np.uint32)
+    return w, (ptr(w) if w.size else None), int(w.size)
+
+
+def hashed_bucket(key: int, buckets: int) -> int:
+    """The bucket of a gram's key among `buckets`: floor(key * buckets / 2^64) (tgx_hashed_bucket)."""
+    return int(lib.tgx_hashed_bucket(int(key) & (2**64 - 1), int(buckets)))
+
+
+def hashed_info(n_vectors: int = 1) -> dict[str, int]:
+    """The LDS table's 32-bit entries and the largest number of buckets that the LDS kernels serve for n_vectors weight
+    vectors (1: the counts too); beyond it the kernels work on memory (tgx_hashed_info)."""
+    e, b = C.c_uint64(), C.c_uint64()
+    check(lib.tgx_hashed_info(int(n_vectors), C.byref(e), C.byref(b)))
+    return {"lds_max_entries": int(e.value), "lds_max_buckets": int(b.value)}
+
+
+def hashed_counts_host(data: np.ndarray, offs: np.ndarray, widths, buckets: int, seed: int = 0) -> np.ndarray:
+    """Host twin of hashed_counts (tgx_hashed_counts_host: the kernel's chunks and keys through the same header, no
+    device) over data u8[N] or u32[T] and offsets u64[S+1] in elements -> int64[buckets] (untouched, -7, when S = 0)."""
+    data, offs, n = _gram_source(data, offs)
+    w, wp, nw = _hashed_widths(widths)
+    counts = np.full(max(int(buckets), 0), -7, np.int64)
+    check(lib.tgx_hashed_counts_host(ptr(data) if data.size else None, data.dtype.itemsize, ptr(offs) if offs.size else None, n, wp, nw, int(buckets),
+                                     int(seed) & (2**64 - 1), ptr(counts) if counts.size else None))
+    return counts
+
+
+def hashed_scores_host(data: np.ndarray, offs: np.ndarray, widths, q: np.ndarray, seed: int = 0) -> np.ndarray:
+    """Host twin of hashed_scores (tgx_hashed_scores_host: the kernel's chunks and its store / add rule, no device) under
+    the fixed-point weights q int32[K, B] -> int64[S, K]."""
+    data, offs, n = _gram_source(data, offs)
+    w, wp, nw = _hashed_widths(widths)
+    q = np.ascontiguousarray(q, dtype=np.int32)
+    K, B = q.shape
+    scores = np.full((n, K), -7, np.int64)
+    check(lib.tgx_hashed_scores_host(ptr(data) if data.size else None, data.dtype.itemsize, ptr(offs) if offs.size else None, n, wp, nw, B, K,
+                                     int(seed) & (2**64 - 1), ptr(q) if q.size else None, ptr(scores) if scores.size else None))
+    return scores
+
+
+def hashed_last_times() -> dict[str, float]:
+    """Device time in ms of the calling thread's last hashed-counts and hashed-scores calls (tgx_hashed_last_times)."""
+    names = (C.c_char_p * 8)()
+    ms = (C.c_float * 8)()
+    n = lib.tgx_hashed_last_times(names, ms, 8)
+    return {names[i].decode(): float(ms[i]) for i in range(n)}
+
+
+def _hashed_device(obj, counts: bool):
+    if isinstance(obj, NativeResult):
+        return lib.tgx_result_hashed_counts_device if counts else lib.tgx_result_hashed_scores_device
+    if isinstance(obj, NativeCorpus):
+        return lib.tgx_corpus_hashed_counts_device if counts else lib.tgx_corpus_hashed_scores_device
+    raise TypeError("obj must be a NativeResult or a NativeCorpus")
+
+
+def hashed_counts_device(obj, widths, buckets: int, seed: int, d_counts: int, *, stream: int = 0) -> None:
+    """How many n-grams of the given widths of obj's rows (a NativeResult: ids; a NativeCorpus: bytes) fall into each of
+    `buckets` hash buckets, as int64[buckets] into caller-owned device memory (a raw integer pointer;
+    tgx_*_hashed_counts_device), queued on `stream` as in pad_device."""
+    w, wp, nw = _hashed_widths(widths)
+    check(_hashed_device(obj, True)(obj._h, wp, nw, int(buckets), int(seed) & (2**64 - 1), 0, stream or None, d_counts or None))
+
+
+def hashed_scores_device(obj, widths, buckets: int, n_vectors: int, seed: int, d_q: int, d_scores: int, *, stream: int = 0) -> None:
+    """Per row of obj the sum over its n-grams of the weight of the gram's bucket under each of n_vectors fixed-point
+    weight vectors d_q (int32[n_vectors, buckets] in device memory), as int64[S, n_vectors] into caller-owned device
+    memory (raw integer pointers; tgx_*_hashed_scores_device)."""
+    w, wp, nw = _hashed_widths(widths)
+    check(_hashed_device(obj, False)(obj._h, wp, nw, int(buckets), int(n_vectors), int(seed) & (2**64 - 1), d_q or None, 0, stream or None,
+                                     d_scores or None))
 
 
 # ---- per-row text statistics and the line view (include/tgx.h; csrc/textstat.hip, csrc/textstat.h) ----

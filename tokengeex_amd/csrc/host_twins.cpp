@@ -1,8 +1,8 @@
 // The *_host twins of the result-side device entry points (include/tgx.h): tgx_layout_pad_host, tgx_layout_pack_host,
-// tgx_layout_windows_host, tgx_assemble_host, tgx_fim_host, tgx_select_host, tgx_select_text_host, tgx_shuffled_rows_host, tgx_first_equal_host, tgx_minhash_host, tgx_minhash_bands_host, tgx_minhash_near_first_host, tgx_gram_keys_host, tgx_gram_hits_host, tgx_gram_contains_host, tgx_repeat_stats_host, tgx_text_stats_host, tgx_lines_host, tgx_word_stats_host (include/tgx_words.h), tgx_words_host and tgx_word_key (include/tgx_word_ids.h), tgx_phrase_hits_host (include/tgx_phrases.h), tgx_dfa_hits_host (include/tgx_patterns.h), tgx_dfa64_hits_host (include/tgx_patterns64.h), tgx_dfa_cover_host and tgx_redact_host (include/tgx_redact.h), tgx_shape_hits_host and tgx_shape_cover_host (include/tgx_shapes.h), tgx_decode_rows_host, tgx_spans_host, tgx_window_spans_host, tgx_front_host,
+// tgx_layout_windows_host, tgx_assemble_host, tgx_fim_host, tgx_select_host, tgx_select_text_host, tgx_shuffled_rows_host, tgx_first_equal_host, tgx_minhash_host, tgx_minhash_bands_host, tgx_minhash_near_first_host, tgx_gram_keys_host, tgx_gram_hits_host, tgx_gram_contains_host, tgx_repeat_stats_host, tgx_text_stats_host, tgx_lines_host, tgx_word_stats_host (include/tgx_words.h), tgx_words_host and tgx_word_key (include/tgx_word_ids.h), tgx_phrase_hits_host (include/tgx_phrases.h), tgx_dfa_hits_host (include/tgx_patterns.h), tgx_dfa64_hits_host (include/tgx_patterns64.h), tgx_dfa_cover_host and tgx_redact_host (include/tgx_redact.h), tgx_shape_hits_host and tgx_shape_cover_host (include/tgx_shapes.h), tgx_hashed_counts_host and tgx_hashed_scores_host (include/tgx_hashed.h), tgx_decode_rows_host, tgx_spans_host, tgx_window_spans_host, tgx_front_host,
 // tgx_normalize_host and tgx_lattice_stats_host, and the
 // argument checks they share with the device entry points of tgx_api.cpp.  A twin goes through the same index arithmetic as its kernels (layout.h, assemble.h,
-// fim.h, select.h, dedup.h, minhash.h, gram.h, repeat.h, textstat.h, wordstat.h, words.h, dfa.h, dfa64.h, cover.h, redact.h, shape.h, decode.h, spans.h, front.h, norm.h) on host memory.  Nothing in this file calls a HIP function, so it builds and runs without the
+// fim.h, select.h, dedup.h, minhash.h, gram.h, hashed.h, repeat.h, textstat.h, wordstat.h, words.h, dfa.h, dfa64.h, cover.h, redact.h, shape.h, decode.h, spans.h, front.h, norm.h) on host memory.  Nothing in this file calls a HIP function, so it builds and runs without the
 // handles, the pool or a device.
 #define TGX_HOST_ONLY  // tile_fill.h: the host loop, no kernel side
 #include <algorithm>
@@ -22,6 +22,7 @@
 #include "fim.h"
 #include "front.h"
 #include "gram.h"
+#include "hashed.h"
 #include "layout.h"
 #include "minhash.h"
 #include "norm.h"
@@ -35,6 +36,7 @@
 #include "unicode_tables.h"
 #include "words.h"
 #include "wordstat.h"
+#include "../../include/tgx_hashed.h"
 #include "../../include/tgx_patterns.h"
 #include "../../include/tgx_patterns64.h"
 #include "../../include/tgx_phrases.h"
@@ -995,6 +997,111 @@ tgx_status tgx_gram_contains_host(const uint64_t* keys, uint64_t n_keys, const u
     if (st != TGX_OK) return st;
     if (n_probes && (!probes || !out)) return fail(TGX_ERR_INVALID, "%s: %s is NULL", who, probes ? "out" : "probes");
     for (uint64_t p = 0; p < n_probes; p++) out[p] = tgx::gram_contains(sorted.data(), dir.data(), bits, probes[p]) ? 1 : 0;
+    return TGX_OK;
+}
+
+// ---- hashed n-gram features (include/tgx_hashed.h) ------------------------------------------------
+
+uint64_t tgx_hashed_bucket(uint64_t key, uint64_t buckets) { return tgx::hashed_bucket(key, buckets); }
+
+tgx_status tgx_hashed_info(uint32_t n_vectors, uint64_t* lds_max_entries, uint64_t* lds_max_buckets) {
+    if (n_vectors < 1 || n_vectors > tgx::kHashedMaxVectors)
+        return fail(TGX_ERR_INVALID, "tgx_hashed_info: n_vectors %u is not in 1 .. %u", n_vectors, tgx::kHashedMaxVectors);
+    if (lds_max_entries) *lds_max_entries = tgx::kHashedLdsEntries;
+    if (lds_max_buckets) *lds_max_buckets = tgx::hashed_lds_buckets(n_vectors);
+    return TGX_OK;
+}
+
+namespace {
+
+// The kernels' walk: chunks of 64 elements of all rows laid end to end, the owners of a chunk's ends galloped from the
+// chunk before, every element's owner searched between them, the keys of all valid widths from the words of the longest
+// valid window.  at(c0, i, n_valid, keys) sees every element, in order, with its chunk and its row.
+template <class At>
+tgx_status hashed_walk_host(const char* who, const void* data, uint32_t elem_bytes, const uint64_t* offs, uint64_t S, const uint32_t* widths,
+                            uint32_t n_widths, uint64_t buckets, uint32_t n_vectors, uint64_t seed, const void* out, const char* out_name, At at) {
+    tgx::HashedWidths ws;
+    tgx_status st = tgx::hashed_check(who, widths, n_widths, elem_bytes, buckets, n_vectors, &ws);
+    if (st != TGX_OK) return st;
+    if ((st = check_packed_list(who, "offs", "offsets", offs, S, true)) != TGX_OK) return st;
+    if (S >= 0xFFFFFFFFull) return fail(TGX_ERR_UNSUPPORTED, "%s: more than 2^32-1 rows", who);
+    if (offs[S] && !data) return fail(TGX_ERR_INVALID, "%s: data is NULL", who);
+    if (S && !out) return fail(TGX_ERR_INVALID, "%s: %s is NULL", who, out_name);
+    const uint8_t* bytes = static_cast<const uint8_t*>(data);
+    const uint64_t M = S ? offs[S] : 0, hs = tgx::dedup_seed(tgx::minhash_hash_seed(seed));
+    uint64_t hi = 0;
+    for (uint64_t c0 = 0; c0 < M; c0 += tgx::kGramChunk) {
+        const uint64_t c_last = tgx::tile_last(c0, tgx::kGramChunk, M);
+        const uint64_t lo = tgx::dedup_find_from(offs, hi, S - 1, c0);
+        hi = tgx::dedup_find_from(offs, lo, S - 1, c_last);
+        for (uint64_t e = c0; e <= c_last; e++) {
+            const uint64_t i = tgx::pack_find_row(offs, 0, lo, hi, e);
+            const uint32_t n_valid = tgx::hashed_valid_widths(ws, e, offs[i + 1]);
+            uint64_t keys[tgx::kHashedMaxWidths] = {};
+            if (n_valid) {  // (a position without a valid gram reads nothing)
+                const uint32_t n_bytes = tgx::hashed_window(ws, n_valid) * elem_bytes;
+                uint64_t w[8] = {};
+                for (uint32_t q = 0; 8 * q < n_bytes; q++) w[q] = tgx::dedup_word_host(bytes + e * elem_bytes, n_bytes, q);
+                tgx::hashed_keys(w, ws, elem_bytes, n_valid, hs, keys);
+            }
+            at(c0, i, n_valid, keys);
+        }
+    }
+    return TGX_OK;
+}
+
+}  // namespace
+
+tgx_status tgx_hashed_counts_host(const void* data, uint32_t elem_bytes, const uint64_t* offs, uint64_t n_rows, const uint32_t* widths, uint32_t n_widths,
+                                  uint64_t buckets, uint64_t seed, int64_t* counts) {
+    bool first = true;
+    const tgx_status st = hashed_walk_host("tgx_hashed_counts_host", data, elem_bytes, offs, n_rows, widths, n_widths, buckets, 1, seed, counts, "counts",
+                                           [&](uint64_t, uint64_t, uint32_t n_valid, const uint64_t* keys) {
+                                               if (first) std::fill(counts, counts + buckets, 0);  // the launcher's pre-set
+                                               first = false;
+                                               for (uint32_t j = 0; j < n_valid; j++) counts[tgx::hashed_bucket(keys[j], buckets)]++;
+                                           });
+    if (st == TGX_OK && n_rows && first) std::fill(counts, counts + buckets, 0);  // rows without an element
+    return st;
+}
+
+tgx_status tgx_hashed_scores_host(const void* data, uint32_t elem_bytes, const uint64_t* offs, uint64_t n_rows, const uint32_t* widths, uint32_t n_widths,
+                                  uint64_t buckets, uint32_t n_vectors, uint64_t seed, const int32_t* q, int64_t* scores) {
+    const char* who = "tgx_hashed_scores_host";
+    if (!q) return fail(TGX_ERR_INVALID, "%s: q is NULL", who);
+    // a stretch of one row inside a chunk ends when the owner or the chunk changes: then the kernel's store / add rule
+    uint64_t cur_c0 = 0, cur_row = 0;
+    int64_t sums[tgx::kHashedMaxVectors] = {};
+    bool open = false, first = true;
+    auto flush = [&]() {
+        if (!open) return;
+        const bool inside = tgx::gram_row_inside(offs, cur_row, cur_c0);
+        for (uint32_t k = 0; k < n_vectors; k++) {
+            if (inside)
+                scores[cur_row * n_vectors + k] = sums[k];
+            else if (tgx::gram_adds((uint64_t)sums[k]))
+                scores[cur_row * n_vectors + k] += sums[k];
+        }
+    };
+    const tgx_status st = hashed_walk_host(who, data, elem_bytes, offs, n_rows, widths, n_widths, buckets, n_vectors, seed, scores, "scores",
+                                           [&](uint64_t c0, uint64_t i, uint32_t n_valid, const uint64_t* keys) {
+                                               if (first) std::fill(scores, scores + n_rows * n_vectors, 0);  // the launcher's pre-set
+                                               first = false;
+                                               if (!open || c0 != cur_c0 || i != cur_row) {
+                                                   flush();
+                                                   open = true;
+                                                   cur_c0 = c0;
+                                                   cur_row = i;
+                                                   std::fill(sums, sums + n_vectors, 0);
+                                               }
+                                               for (uint32_t j = 0; j < n_valid; j++) {
+                                                   const uint64_t b = tgx::hashed_bucket(keys[j], buckets);
+                                                   for (uint32_t k = 0; k < n_vectors; k++) sums[k] += q[(uint64_t)k * buckets + b];
+                                               }
+                                           });
+    if (st != TGX_OK) return st;
+    flush();
+    if (n_rows && first) std::fill(scores, scores + n_rows * n_vectors, 0);  // rows without an element
     return TGX_OK;
 }
 

@@ -303,6 +303,80 @@ def clean_rows(obj, grams, max_hits: int = 0):
     return (gram_hits(obj, grams) <= int(max_hits)).nonzero().reshape(-1)
 
 
+# ---- hashed n-gram features on the device: bucket counts and linear scores (csrc/hashed.hip) -----------------------------
+
+def hashed_counts(obj, buckets: int = 10000, widths=(1, 2), seed: int = 0):
+    """-> [buckets] torch.int64 on obj's device (a NativeResult: ids, word_rows' among them; a NativeCorpus: bytes): how
+    many n-grams of the given widths (1 to 4, ascending) of obj's rows fall into each hash bucket.  The bucket of a gram is
+    floor(key * buckets / 2^64) of gram_set's 64-bit key.  Exact integers: the same on every machine."""
+    import torch
+    dev = _device_of(torch, obj)
+    out = torch.zeros((int(buckets),), dtype=torch.int64, device=dev)  # (a source without rows writes nothing)
+    _lib.hashed_counts_device(obj, widths, buckets, seed, out.data_ptr() if out.numel() else 0, stream=torch.cuda.current_stream(dev).cuda_stream)
+    return out
+
+
+def quantize_weights(w):
+    """-> torch.int32 of w's shape: rint(w * 2^24), the fixed-point weights hashed_scores sums exactly.  A weight that is
+    not finite or not below 128 in magnitude raises ValueError."""
+    import torch
+    w = torch.as_tensor(w, dtype=torch.float64)
+    if w.numel() and (not bool(torch.isfinite(w).all()) or float(w.abs().max()) >= 128.0):
+        raise ValueError("weights must be finite and below 128 in magnitude")
+    return torch.round(w * float(1 << _lib.HASHED_FRAC_BITS)).clamp_(-(2.0**31 - 1), 2.0**31 - 1).to(torch.int32)  # (128 - 2^-26 rounds up)
+
+
+def hashed_scores(obj, weights, widths=(1, 2), seed: int = 0, raw: bool = False):
+    """-> [S, K] on obj's device: per row the sum over its n-grams (of all widths) of the weight of the gram's bucket, for
+    each of the K weight vectors.  weights: [B] or [K, B]; a float tensor is quantised with quantize_weights, an int32
+    tensor is taken as the fixed-point Q itself.  raw: the exact torch.int64 sums of Q; else torch.float64, the sums
+    times 2^-24.  The sums are integers, so the result does not depend on the order of the additions."""
+    import torch
+    dev = _device_of(torch, obj)
+    q = torch.as_tensor(weights)
+    q = q if q.dtype == torch.int32 else quantize_weights(q)
+    if q.dim() == 1:
+        q = q.reshape(1, -1)
+    if q.dim() != 2:
+        raise ValueError(f"weights must be [B] or [K, B] (got {tuple(q.shape)})")
+    q = q.to(dev).contiguous()
+    K, B = q.shape
+    out = torch.empty((obj.num_samples, K), dtype=torch.int64, device=dev)
+    spare = torch.empty(1, dtype=torch.int64, device=dev)  # (no row: the pointer still says that the scores are asked for)
+    _lib.hashed_scores_device(obj, widths, B, K, seed, q.data_ptr() if q.numel() else 0, (out if out.numel() else spare).data_ptr(),
+                              stream=torch.cuda.current_stream(dev).cuda_stream)
+    return out if raw else out.to(torch.float64) * (2.0 ** -_lib.HASHED_FRAC_BITS)
+
+
+def nb_weights(counts, alpha: float = 1.0):
+    """-> torch.float64 of counts' shape ([B] or [K, B]): log((c + alpha) / (sum c + alpha * B)) per row, the log
+    probabilities of a multinomial naive-Bayes class (or of DSIR's bag-of-buckets model) under additive smoothing."""
+    import torch
+    c = torch.as_tensor(counts).to(torch.float64)
+    return torch.log((c + alpha) / (c.sum(dim=-1, keepdim=True) + alpha * c.shape[-1]))
+
+
+def dsir_weights(target_counts, raw_counts, alpha: float = 1.0):
+    """-> torch.float64 [B]: the log importance weight of every bucket, nb_weights(target) - nb_weights(raw) (DSIR, Xie
+    et al. 2023): hashed_scores under it is a row's log importance weight."""
+    return nb_weights(target_counts, alpha) - nb_weights(raw_counts, alpha)
+
+
+def dsir_rows(obj, target_counts, raw_counts, n: int, seed: int = 0, widths=(1, 2), hash_seed: int = 0, alpha: float = 1.0):
+    """-> torch.int64 indices, ascending, of n rows of obj drawn without replacement in proportion to their importance
+    weights (Gumbel top-k over the log weights, from a device generator seeded with `seed`): what `select` takes to keep
+    corpus and result aligned.  target_counts, raw_counts: hashed_counts of the target and of the raw source under the
+    same buckets, widths and hash_seed."""
+    import torch
+    scores = hashed_scores(obj, dsir_weights(target_counts, raw_counts, alpha), widths, hash_seed)[:, 0]
+    if not 0 <= int(n) <= scores.shape[0]:
+        raise ValueError(f"n must be in 0 .. {scores.shape[0]} (got {n})")
+    gen = torch.Generator(device=scores.device)
+    gen.manual_seed(int(seed))
+    u = torch.rand(scores.shape, dtype=torch.float64, device=scores.device, generator=gen).clamp_(min=2.0 ** -53)
+    return torch.topk(scores - torch.log(-torch.log(u)), int(n)).indices.sort().values
+
+
 # ---- per-row text statistics and the line view: quality filters (csrc/textstat.hip) --------------------------------------
 
 class TextStats:
