@@ -291,6 +291,15 @@ HASHED_SYMBOLS = {
     "tgx_hashed_last_times": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_float), _i]),
 }
 
+# every exported symbol of include/tgx_find.h, a header of its own in the same way: bound and checked at import too
+FIND_SYMBOLS = {
+    "tgx_corpus_find_device": (_i, [_vp, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "tgx_corpus_mine_device": (_i, [_vp, _vp, _u32, _u64, _u64, _vp, _vp, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _vp]),
+    "tgx_find_host": (_i, [_vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp]),
+    "tgx_mine_host": (_i, [_vp, _vp, _u64, _vp, _u32, _u64, _u64, _vp, _vp, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "tgx_find_last_times": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_float), _i]),
+}
+
 
 class TokenGeeXError(Exception):
     """tokengeex.TokenGeeXError — bindings/python/src/lib.rs:9,33-37; carries the
@@ -336,7 +345,7 @@ def _load() -> C.CDLL:
             "Build it with `python tokengeex_amd/build.py`.")
     _share_torch_hip_runtime()
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(WORD_SYMBOLS.items()) + list(WORDS_SYMBOLS.items()) + list(PHRASE_SYMBOLS.items()) + list(PATTERN_SYMBOLS.items()) + list(PATTERN64_SYMBOLS.items()) + list(REDACT_SYMBOLS.items()) + list(SHAPE_SYMBOLS.items()) + list(HASHED_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(WORD_SYMBOLS.items()) + list(WORDS_SYMBOLS.items()) + list(PHRASE_SYMBOLS.items()) + list(PATTERN_SYMBOLS.items()) + list(PATTERN64_SYMBOLS.items()) + list(REDACT_SYMBOLS.items()) + list(SHAPE_SYMBOLS.items()) + list(HASHED_SYMBOLS.items()) + list(FIND_SYMBOLS.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args
@@ -1342,6 +1351,54 @@ def dfa64_last_times() -> dict[str, float]:
     return {names[i].decode(): float(ms[i]) for i in range(n)}
 
 
+# ---- leftmost-first matches and idiom mining (include/tgx_find.h; csrc/find.hip, csrc/find.h) ----
+FIND_MAX_LEN = 64
+MINE_SEED = 0x1D10
+
+
+def find_host(text: np.ndarray, offs: np.ndarray, pat, max_len: int = FIND_MAX_LEN):
+    """Host twin of NativeCorpus.find (tgx_find_host: the kernels' walks, doubling rounds, maps, fold, scan and store /
+    add rule through the same header, no device) over text u8[N] and offsets u64[S+1] -> (count int64[S], lens
+    uint8[N], truncated int64[S]).  pat: an automaton from patterns.compile_pattern(..., find=True)."""
+    text = np.ascontiguousarray(text, dtype=np.uint8)
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    n = max(offs.shape[0] - 1, 0)
+    count, truncated = np.full(n, -7, np.int64), np.full(n, -7, np.int64)
+    lens = np.full(text.size, 7, np.uint8)
+    keep = np.zeros(1, np.int64), np.zeros(1, np.uint8), np.zeros(1, np.int64)   # (never NULL: every output is asked for)
+    check(lib.tgx_find_host(ptr(text) if text.size else None, ptr(offs) if offs.size else None, n, C.byref(dfa64_struct(pat)), int(max_len),
+                            ptr(count if n else keep[0]), ptr(lens if lens.size else keep[1]), ptr(truncated if n else keep[2])))
+    return count, lens, truncated
+
+
+def _mine_call(fn, head, pat, max_len: int, top: int, seed: int, tail=()):
+    """the shared ends of tgx_corpus_mine_device and tgx_mine_host -> (pos uint64[n], len uint32[n], count uint64[n],
+    n_distinct, n_matches)"""
+    cap = max(int(top), 1)
+    pos, length, count = np.zeros(cap, np.uint64), np.zeros(cap, np.uint32), np.zeros(cap, np.uint64)
+    n_out, n_distinct, n_matches = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    check(fn(*head, C.byref(dfa64_struct(pat)), int(max_len), int(top), int(seed), ptr(pos), ptr(length), ptr(count), C.byref(n_out), C.byref(n_distinct),
+             C.byref(n_matches), *tail))
+    k = n_out.value
+    return pos[:k], length[:k], count[:k], n_distinct.value, n_matches.value
+
+
+def mine_host(text: np.ndarray, offs: np.ndarray, pat, top: int, max_len: int = FIND_MAX_LEN, seed: int = MINE_SEED):
+    """Host twin of NativeCorpus.mine (tgx_mine_host) -> (pos, len, count, n_distinct, n_matches): the `top` most frequent
+    distinct matches by count descending, then first occurrence ascending."""
+    text = np.ascontiguousarray(text, dtype=np.uint8)
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    return _mine_call(lib.tgx_mine_host, (ptr(text) if text.size else None, ptr(offs) if offs.size else None, max(offs.shape[0] - 1, 0)), pat, max_len, top, seed)
+
+
+def find_last_times() -> dict[str, float]:
+    """Device time in ms of each stage of the calling thread's last find or mine call (tgx_find_last_times)."""
+    names = (C.c_char_p * 8)()
+    ms = (C.c_float * 8)()
+    n = lib.tgx_find_last_times(names, ms, 8)
+    return {names[i].decode(): float(ms[i]) for i in range(n)}
+
+
 # ---- cover and redaction (include/tgx_redact.h; csrc/cover.hip, csrc/redact.hip) ----
 REDACT_MAX_CLASSES = 8
 REDACT_MAX_REPL = 64
@@ -2297,6 +2354,19 @@ class NativeCorpus:
         into caller-owned device memory (either may be 0, not both; tgx_corpus_dfa64_hits_device).  This corpus is only
         read."""
         check(lib.tgx_corpus_dfa64_hits_device(self._h, C.byref(dfa64_struct(pat)), d_count or None, d_ends or None, stream or None))
+
+    def find(self, pat, d_count: int = 0, d_lens: int = 0, d_truncated: int = 0, *, max_len: int = FIND_MAX_LEN, stream: int = 0) -> None:
+        """The leftmost-first, non-overlapping matches of an automaton from patterns.compile_pattern(..., find=True) in
+        every row, what re.finditer gives: the matches per row (int64[S]), the match length at every emitted start
+        (uint8[N], 0 elsewhere) and per row the visited positions whose walk ran into max_len (int64[S]) into caller-owned
+        device memory (any may be 0, not all; tgx_corpus_find_device).  This corpus is only read."""
+        check(lib.tgx_corpus_find_device(self._h, C.byref(dfa64_struct(pat)), int(max_len), d_count or None, d_lens or None, d_truncated or None, stream or None))
+
+    def mine(self, pat, top: int, *, max_len: int = FIND_MAX_LEN, seed: int = MINE_SEED, stream: int = 0):
+        """-> (pos uint64[n], len uint32[n], count uint64[n], n_distinct, n_matches) as numpy: the `top` most frequent
+        distinct matches by count descending, then first occurrence ascending, equal by 64-bit key
+        (tgx_corpus_mine_device; synchronous).  pos is the first occurrence's offset in the corpus's text."""
+        return _mine_call(lib.tgx_corpus_mine_device, (self._h,), pat, max_len, top, seed, (stream or None,))
 
     def dfa_cover(self, pat, d_covered: int = 0, d_mask: int = 0, *, stream: int = 0) -> None:
         """Per sample the bytes that lie inside a match of the cover pattern `pat` (patterns.compile_pattern(cover=True), or

@@ -2,7 +2,7 @@
 // tgx_layout_windows_host, tgx_assemble_host, tgx_fim_host, tgx_select_host, tgx_select_text_host, tgx_shuffled_rows_host, tgx_first_equal_host, tgx_minhash_host, tgx_minhash_bands_host, tgx_minhash_near_first_host, tgx_gram_keys_host, tgx_gram_hits_host, tgx_gram_contains_host, tgx_repeat_stats_host, tgx_text_stats_host, tgx_lines_host, tgx_word_stats_host (include/tgx_words.h), tgx_words_host and tgx_word_key (include/tgx_word_ids.h), tgx_phrase_hits_host (include/tgx_phrases.h), tgx_dfa_hits_host (include/tgx_patterns.h), tgx_dfa64_hits_host (include/tgx_patterns64.h), tgx_dfa_cover_host and tgx_redact_host (include/tgx_redact.h), tgx_shape_hits_host and tgx_shape_cover_host (include/tgx_shapes.h), tgx_hashed_counts_host and tgx_hashed_scores_host (include/tgx_hashed.h), tgx_decode_rows_host, tgx_spans_host, tgx_window_spans_host, tgx_front_host,
 // tgx_normalize_host and tgx_lattice_stats_host, and the
 // argument checks they share with the device entry points of tgx_api.cpp.  A twin goes through the same index arithmetic as its kernels (layout.h, assemble.h,
-// fim.h, select.h, dedup.h, minhash.h, gram.h, hashed.h, repeat.h, textstat.h, wordstat.h, words.h, dfa.h, dfa64.h, cover.h, redact.h, shape.h, decode.h, spans.h, front.h, norm.h) on host memory.  Nothing in this file calls a HIP function, so it builds and runs without the
+// fim.h, select.h, dedup.h, minhash.h, gram.h, hashed.h, repeat.h, textstat.h, wordstat.h, words.h, dfa.h, dfa64.h, find.h, cover.h, redact.h, shape.h, decode.h, spans.h, front.h, norm.h) on host memory.  Nothing in this file calls a HIP function, so it builds and runs without the
 // handles, the pool or a device.
 #define TGX_HOST_ONLY  // tile_fill.h: the host loop, no kernel side
 #include <algorithm>
@@ -20,6 +20,7 @@
 #include "dfa.h"
 #include "dfa64.h"
 #include "fim.h"
+#include "find.h"
 #include "front.h"
 #include "gram.h"
 #include "hashed.h"
@@ -36,6 +37,7 @@
 #include "unicode_tables.h"
 #include "words.h"
 #include "wordstat.h"
+#include "../../include/tgx_find.h"
 #include "../../include/tgx_hashed.h"
 #include "../../include/tgx_patterns.h"
 #include "../../include/tgx_patterns64.h"
@@ -2025,6 +2027,136 @@ tgx_status tgx_dfa64_hits_host(const uint8_t* text, const uint64_t* offs, uint64
     textstat_walk_host(text, offs, S, [&](uint64_t c0, uint32_t n_in, uint64_t, const uint64_t* row) {
         shape_row_sums_host(offs, c0, n_in, row, textstat_mask_host(tags, c0, n_in, [](uint8_t t) { return t != 0; }), count);
     });
+    return TGX_OK;
+}
+
+// ---- leftmost-first matches and the mine (include/tgx_find.h) --------------------------------------------------
+
+namespace {
+
+tgx_status find_check_host(const char* who, const uint8_t* text, const uint64_t* offs, uint64_t n_rows, const tgx_dfa64* dfa, uint32_t max_len) {
+    const tgx_status st = textstat_check_source_host(who, text, offs, n_rows);
+    if (st != TGX_OK) return st;
+    if (!dfa) return fail(TGX_ERR_INVALID, "%s: dfa is NULL", who);
+    if (const char* why = tgx::dfa64_check(dfa->n_states, dfa->start, dfa->next, dfa->tag)) return fail(TGX_ERR_INVALID, "%s: %s", who, why);
+    if (const char* why = tgx::find_check_max_len(max_len)) return fail(TGX_ERR_INVALID, "%s: %s", who, why);
+    return TGX_OK;
+}
+
+// The twin of find.hip's three stages: every position's walk byte on the chunks of textstat_walk_host; every chunk's map
+// by the doubling rounds, folded into its segment's record; dfa64's scan of the records from skip 0; and the replay, the
+// skip carried from chunk to chunk, with the visited sets and the row sums by the store / add rule.  S > 0; lens u8[N]
+// is written; count and truncated may each be NULL.
+void find_host(const uint8_t* text, const uint64_t* offs, uint64_t S, const tgx_dfa64* dfa, uint32_t max_len, uint8_t* lens, int64_t* count, int64_t* truncated) {
+    const uint64_t N = offs[S], n_segs = tgx::dfa64_segs(N), n_groups = tgx::dfa64_groups(n_segs);
+    std::vector<uint8_t> table(tgx::kFindTableBytes);
+    tgx::find_build_table(dfa->n_states, dfa->next, dfa->tag, table.data());
+    // find_walk_kernel
+    uint8_t* walk = lens;
+    textstat_walk_host(text, offs, S, [&](uint64_t c0, uint32_t n_in, uint64_t, const uint64_t* row) {
+        for (uint32_t l = 0; l < n_in; l++) walk[c0 + l] = (uint8_t)tgx::find_walk_host(table.data(), dfa->start, text, c0 + l, offs[row[l] + 1], max_len);
+    });
+    std::vector<uint8_t> srec(n_segs * tgx::kDfa64Map), grec(n_groups * tgx::kDfa64Map), gentry(n_groups), sentry(n_segs);
+    uint8_t map[tgx::kDfa64Map];
+    for (uint64_t seg = 0; seg < n_segs; seg++) {
+        uint8_t* rec = &srec[seg * tgx::kDfa64Map];
+        tgx::dfa64_identity(rec);
+        for (uint32_t k = 0; k < tgx::kDfa64SegChunks; k++) {
+            const uint64_t c0 = (seg * tgx::kDfa64SegChunks + k) * tgx::kDfa64Chunk;
+            const uint32_t n_in = tgx::dfa64_chunk_bytes(c0, N);
+            if (!n_in) break;
+            tgx::find_chunk_host(walk + c0, n_in, 0, map, nullptr);
+            tgx::dfa64_fold(rec, map);
+        }
+    }
+    // dfa64_scan, from skip 0
+    for (uint64_t g = 0; g < n_groups; g++) {
+        uint8_t* rec = &grec[g * tgx::kDfa64Map];
+        tgx::dfa64_identity(rec);
+        for (uint64_t seg = g * tgx::kDfa64Group; seg < n_segs && seg < (g + 1) * tgx::kDfa64Group; seg++) tgx::dfa64_fold(rec, &srec[seg * tgx::kDfa64Map]);
+    }
+    tgx::dfa64_chain_host(grec.data(), n_groups, 0, gentry.data());
+    for (uint64_t g = 0; g < n_groups; g++) {
+        const uint64_t first = g * tgx::kDfa64Group, n = n_segs - first < tgx::kDfa64Group ? n_segs - first : tgx::kDfa64Group;
+        tgx::dfa64_chain_host(&srec[first * tgx::kDfa64Map], n, gentry[g], &sentry[first]);
+    }
+    // find_replay_kernel
+    if (count) std::fill(count, count + S, 0);  // the launcher's pre-sets
+    if (truncated) std::fill(truncated, truncated + S, 0);
+    uint32_t e = 0;
+    textstat_walk_host(text, offs, S, [&](uint64_t c0, uint32_t n_in, uint64_t, const uint64_t* row) {
+        if (c0 % tgx::kDfa64Seg == 0) e = sentry[c0 / tgx::kDfa64Seg];
+        uint64_t visited = 0, emitted = 0, cut = 0;
+        tgx::find_chunk_host(walk + c0, n_in, e, map, &visited);
+        e = map[e];
+        for (uint32_t l = 0; l < n_in; l++) {
+            const bool seen = (visited >> l) & 1ull;
+            const uint32_t wb = walk[c0 + l], len = seen ? tgx::find_len(wb) : 0;
+            if (len) emitted |= 1ull << l;
+            if (seen && (wb & tgx::kFindTrunc)) cut |= 1ull << l;
+            lens[c0 + l] = (uint8_t)len;
+        }
+        if (count) shape_row_sums_host(offs, c0, n_in, row, emitted, count);
+        if (truncated) shape_row_sums_host(offs, c0, n_in, row, cut, truncated);
+    });
+}
+
+}  // namespace
+
+tgx_status tgx_find_host(const uint8_t* text, const uint64_t* offs, uint64_t n_rows, const tgx_dfa64* dfa, uint32_t max_len, int64_t* count, uint8_t* lens,
+                         int64_t* truncated) {
+    const char* who = "tgx_find_host";
+    const tgx_status st = find_check_host(who, text, offs, n_rows, dfa, max_len);
+    if (st != TGX_OK) return st;
+    if (!count && !lens && !truncated) return fail(TGX_ERR_INVALID, "%s: count, lens and truncated are all NULL", who);
+    if (n_rows == 0) return TGX_OK;
+    std::vector<uint8_t> own(lens ? 0 : offs[n_rows]);  // the device call's scratch
+    find_host(text, offs, n_rows, dfa, max_len, lens ? lens : own.data(), count, truncated);
+    return TGX_OK;
+}
+
+// The twin of the mine's stages: the matches' positions ascending, their keys, the stable sort by key, the runs' first
+// positions and counts, and find_before's order.
+tgx_status tgx_mine_host(const uint8_t* text, const uint64_t* offs, uint64_t n_rows, const tgx_dfa64* dfa, uint32_t max_len, uint64_t top, uint64_t seed,
+                         uint64_t* out_pos, uint32_t* out_len, uint64_t* out_count, uint64_t* n_out, uint64_t* n_distinct, uint64_t* n_matches) {
+    const char* who = "tgx_mine_host";
+    if (n_out) *n_out = 0;
+    if (n_distinct) *n_distinct = 0;
+    if (n_matches) *n_matches = 0;
+    const tgx_status st = find_check_host(who, text, offs, n_rows, dfa, max_len);
+    if (st != TGX_OK) return st;
+    if (top == 0) return fail(TGX_ERR_INVALID, "%s: top is 0", who);
+    if (!out_pos || !out_len || !out_count || !n_out) return fail(TGX_ERR_INVALID, "%s: an output is NULL", who);
+    if (n_rows == 0 || offs[n_rows] == 0) return TGX_OK;
+    const uint64_t N = offs[n_rows];
+    std::vector<uint8_t> lens(N);
+    find_host(text, offs, n_rows, dfa, max_len, lens.data(), nullptr, nullptr);
+    struct Match {
+        uint64_t key, pos;
+    };
+    std::vector<Match> m;
+    for (uint64_t p = 0; p < N; p++)
+        if (lens[p]) m.push_back({tgx_gram_key(text + p, lens[p], seed), p});
+    std::stable_sort(m.begin(), m.end(), [](const Match& a, const Match& b) { return a.key < b.key; });
+    struct Run {
+        uint64_t pos, count;
+    };
+    std::vector<Run> runs;
+    for (uint64_t i = 0; i < m.size(); i++) {
+        if (i == 0 || m[i].key != m[i - 1].key) runs.push_back({m[i].pos, 0});
+        runs.back().count++;
+    }
+    // (first positions are distinct, so find_before is a total order: what the device's two stable sorts give)
+    std::sort(runs.begin(), runs.end(), [](const Run& a, const Run& b) { return tgx::find_before(a.count, a.pos, b.count, b.pos); });
+    const uint64_t n_top = std::min<uint64_t>(top, runs.size());
+    for (uint64_t i = 0; i < n_top; i++) {
+        out_pos[i] = runs[i].pos;
+        out_len[i] = lens[runs[i].pos];
+        out_count[i] = runs[i].count;
+    }
+    *n_out = n_top;
+    if (n_distinct) *n_distinct = runs.size();
+    if (n_matches) *n_matches = m.size();
     return TGX_OK;
 }
 

@@ -18,8 +18,13 @@ lane per state, then a lane per chunk: include/tgx_patterns64.h: tgx_dfa64; DESI
 With cover=True the pattern also carries a backward automaton and a table over the pairs of states, which together say
 which bytes lie INSIDE a match (include/tgx_redact.h: tgx_dfa_cover; csrc/cover.hip).
 
+    pat = compile_pattern(r"std::\\w+", find=True)                                # what re.finditer finds: 8 states
+
+With find=True the automaton is the anchored, leftmost-first one that find_matches and mine_idioms walk from every
+start byte (include/tgx_find.h; csrc/find.hip).
+
 Syntax: literal bytes; the escapes \\\\ \\. (a backslash before any ASCII punctuation is that byte) \\n \\t \\r \\f \\v \\d \\w
-\\s \\xHH; `.`, any byte but '\\n'; [...] with ranges and a leading ^; ( ), |, * + ?, {m}, {m,}, {m,n}.  A str pattern is
+\\s \\xHH; `.`, any byte but '\\n'; [...] with ranges and a leading ^; ( ) and (?: ), |, * + ?, {m}, {m,}, {m,n}.  A str pattern is
 its UTF-8 bytes, a non-ASCII byte inside [...] is refused, \\d \\w \\s are ASCII ([0-9], [A-Za-z0-9_], space and 0x09 ..
 0x0D).  Anchors, backreferences, look-around, lazy and possessive quantifiers and Unicode classes are refused by name."""
 from __future__ import annotations
@@ -122,7 +127,9 @@ class _Parser:
         c = self.peek()
         self.i += 1
         if c == ord("("):
-            if self.peek() == ord("?"):
+            if self.s[self.i:self.i + 2] == b"?:":  # a group that captures nothing: every group here is one
+                self.i += 2
+            elif self.peek() == ord("?"):
                 nxt = self.s[self.i + 1:self.i + 3]
                 self.fail("look-around (not supported)" if nxt[:1] in (b"=", b"!") or nxt[:2] in (b"<=", b"<!") else
                           "a backreference (not supported)" if nxt[:2] == b"P=" else "a (?...) group (not supported)")
@@ -252,13 +259,30 @@ class _Nfa:
             self.eps[self.build(sub, s)] += [s, z]
             return z
         z = self.state()
-        self.eps[a].append(z)
-        for _ in range(n - m):  # optional copies, each skipping to the end
+        for _ in range(n - m):  # optional copies, each skipping to the end; the copy goes first: a repeat is greedy
             s = self.state()
-            self.eps[a].append(s)
+            self.eps[a] += [s, z]
             a = self.build(sub, s)
-            self.eps[a].append(z)
+        self.eps[a].append(z)
         return z
+
+    def ordered_closure(self, states, accept):
+        """the states reached for free from `states`, in priority order (eps edges in their order, depth first, a state
+        at its first visit), of which only those with an edge or in `accept` are kept -> a tuple that ends at its first
+        accepting state: what has a lower priority than a match can no longer win"""
+        seen, out = set(), []
+        todo = list(reversed(states))
+        while todo:
+            s = todo.pop()
+            if s in seen:
+                continue
+            seen.add(s)
+            if s in accept:
+                return tuple(out + [s])
+            if self.edge[s]:
+                out.append(s)
+            todo += reversed(self.eps[s])
+        return tuple(out)
 
     def closure(self, states):
         seen, todo = set(states), list(states)
@@ -393,7 +417,30 @@ def _compile_cover(nfa, first, accept, owner, cls, reps, sources) -> BytePattern
     return pat
 
 
-def compile_pattern(patterns, fold_case: bool = False, search: bool = True, cover: bool = False, max_states: int = MAX_STATES) -> BytePattern:
+def _compile_find(nfa, root, accept, cls, reps, sources) -> BytePattern:
+    """The automaton of find_matches (include/tgx_find.h): the subset construction over ORDERED lists of NFA states, so
+    that from a start byte the last tagged state before the dead state is the leftmost-first match."""
+    final = set(accept)
+
+    def move(cur, b):
+        return nfa.ordered_closure([nfa.edge[s][1] for s in cur if s not in final and nfa.edge[s][0] >> b & 1], final)
+
+    subsets, trans = _explore(nfa.ordered_closure([root], final), reps, move)
+    state_of, n = _moore([int(bool(sub) and sub[-1] in final) for sub in subsets], trans)
+    if n > MAX_STATES64:
+        raise ValueError(f"the automaton has {n} states after minimisation: the limit is {MAX_STATES64}")
+    width = MAX_STATES if n <= MAX_STATES else MAX_STATES64
+    nxt, tag = np.zeros((256, width), np.uint8), np.zeros(width, np.uint8)
+    for i, s in enumerate(state_of):
+        tag[s] = int(bool(subsets[i]) and subsets[i][-1] in final)
+        nxt[:, s] = np.array([state_of[t] for t in trans[i]], np.uint8)[cls]
+    pat = BytePattern(n, 0, nxt, tag, sources)
+    pat.find = True
+    return pat
+
+
+def compile_pattern(patterns, fold_case: bool = False, search: bool | None = None, cover: bool = False, max_states: int = MAX_STATES,
+                    find: bool = False) -> BytePattern:
     """-> a BytePattern of one pattern (bytes or str) or of a list of up to 8, pattern k tagging its matches with bit k.
     search=True: the automaton of .*R, whose tag at a byte says that a match ends there (what pattern_hits counts);
     search=False: the automaton of R itself from a row's first byte, with a dead state.  fold_case adds the other ASCII
@@ -406,7 +453,15 @@ def compile_pattern(patterns, fold_case: bool = False, search: bool = True, cove
     names the side.
     max_states=64 (pattern_hits, pattern_rows): up to 64 states after minimisation, and a ValueError with the count above
     that; an automaton of more than 16 has .next [256, 64] and .tag [64].  Any value but 16 and 64 is a ValueError, and so
-    is 64 with cover=True: cover and redaction keep their 16 states."""
+    is 64 with cover=True: cover and redaction keep their 16 states.
+    find=True (find_matches, mine_idioms): the anchored automaton of the patterns' alternation in list order, with a dead
+    state and the tag 1, of up to 64 states whatever max_states says, built over ordered state lists so that the last
+    tagged state before the dead state is the match a regex engine's leftmost-first search finds at that start
+    (alternatives in source order, greedy repeats); .find is True.  With cover=True or an explicit search= it is a
+    ValueError."""
+    if find and (cover or search is not None):
+        raise ValueError("find=True is an automaton of its own: it takes neither cover=True nor search=")
+    search = True if search is None else search
     if max_states not in (MAX_STATES, MAX_STATES64):
         raise ValueError(f"max_states={max_states!r}: an automaton has at most {MAX_STATES} states, or {MAX_STATES64} with max_states={MAX_STATES64}")
     if cover and max_states != MAX_STATES:
@@ -428,6 +483,8 @@ def compile_pattern(patterns, fold_case: bool = False, search: bool = True, cove
     if any(s in accept for s in first):
         raise ValueError("a pattern matches the empty string")
     cls, reps = _byte_classes(sorted({e[0] for e in nfa.edge if e}))
+    if find:
+        return _compile_find(nfa, root, accept, cls, reps, sources)
     if cover:
         if not search:
             raise ValueError("cover=True needs search=True: a cover is of the matches anywhere in a row")

@@ -738,6 +738,51 @@ def pattern_rows(corpus: "_lib.NativeCorpus", pat, max_hits: int = 0):
     return (pattern_hits(corpus, pat) <= int(max_hits)).nonzero().reshape(-1)
 
 
+# ---- leftmost-first matches and idiom mining: re.finditer on the device (csrc/find.hip) -----------------------------------------
+
+def _find_pattern(pat):
+    from . import patterns
+    if not isinstance(pat, patterns.BytePattern):
+        pat = patterns.compile_pattern(pat, find=True)
+    if not getattr(pat, "find", False):
+        raise ValueError("find_matches and mine_idioms need a pattern compiled with find=True")
+    return pat
+
+
+def find_matches(corpus: "_lib.NativeCorpus", pat, max_len: int = 64, return_lens: bool = False, return_truncated: bool = False):
+    """-> [S] torch.int64 on the corpus's device: per row the matches that re.finditer(pat, row) gives, the non-overlapping
+    matches found left to right with the engine's leftmost-first choice (alternatives in source order, greedy repeats),
+    queued on torch's current stream.  pat: a patterns.BytePattern from compile_pattern(..., find=True), or a pattern or
+    list of patterns (their alternation in list order), which is compiled here.  With return_lens also [N] torch.uint8,
+    the match length at the byte where a match starts and 0 elsewhere; with return_truncated also [S] torch.int64, the
+    searches of the row that ran into max_len (1 .. 64) bytes while the pattern could still go on: where it is 0 the
+    row's matches are exactly re.finditer's, elsewhere a longer match was cut at max_len.  No match crosses a row's end."""
+    import torch
+    dev = _device_of(torch, corpus)
+    pat = _find_pattern(pat)
+    S, N = corpus.num_samples, corpus.num_bytes
+    count = torch.empty((S,), dtype=torch.int64, device=dev)
+    lens = torch.empty((N,), dtype=torch.uint8, device=dev) if return_lens else None
+    truncated = torch.empty((S,), dtype=torch.int64, device=dev) if return_truncated else None
+    spare = torch.empty(1, dtype=torch.int64, device=dev)  # (no row: the pointer still says that the counts are asked for)
+    corpus.find(pat, (count if S else spare).data_ptr(), lens.data_ptr() if return_lens and N else 0, truncated.data_ptr() if return_truncated and S else 0,
+                max_len=max_len, stream=torch.cuda.current_stream(dev).cuda_stream)
+    out = (count,) + ((lens,) if return_lens else ()) + ((truncated,) if return_truncated else ())
+    return out if len(out) > 1 else count
+
+
+def mine_idioms(corpus: "_lib.NativeCorpus", pat, top: int, max_len: int = 64) -> "list[tuple[bytes, int]]":
+    """-> [(bytes, count)], the `top` most frequent distinct matches of find_matches over the whole corpus, by count
+    descending and then by first occurrence: the reference's IdiomMiner (src/mine.rs) with a fixed rule for ties.  Matches
+    are counted by a 64-bit key of their bytes.  Synchronous on torch's current stream; the matches' bytes are read from
+    the corpus."""
+    import torch
+    dev = _device_of(torch, corpus)
+    pos, length, count, _, _ = corpus.mine(_find_pattern(pat), top, max_len=max_len, stream=torch.cuda.current_stream(dev).cuda_stream)
+    text = corpus.bytes() if len(pos) else None
+    return [(text[int(p):int(p) + int(n)].tobytes(), int(k)) for p, n, k in zip(pos, length, count)]
+
+
 # ---- cover and redaction: the bytes inside a match, and runs of a mask replaced (csrc/cover.hip, csrc/redact.hip) ------------
 
 def pattern_cover(corpus: "_lib.NativeCorpus", pat, return_mask: bool = False):
