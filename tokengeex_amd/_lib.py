@@ -300,6 +300,14 @@ FIND_SYMBOLS = {
     "tgx_find_last_times": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_float), _i]),
 }
 
+# every exported symbol of include/tgx_allow.h, a header of its own in the same way: bound and checked at import too
+ALLOW_SYMBOLS = {
+    "tgx_substring_df_allow": (_i, [_i, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _u32, _d, _u64, _vp, _u64, _pvp, _pvp, _pvp, _pu64, _pu64, _pu64, _pu64,
+                                    C.POINTER(C.c_uint32)]),
+    "tgx_allow_masks_host": (_i, [_vp, _u64, _vp, _vp, _vp, _vp, _u64, _u32, _d, _u64, _vp, _vp, _pu64]),
+    "tgx_allow_last_times": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_float), _i]),
+}
+
 
 class TokenGeeXError(Exception):
     """tokengeex.TokenGeeXError — bindings/python/src/lib.rs:9,33-37; carries the
@@ -345,7 +353,7 @@ def _load() -> C.CDLL:
             "Build it with `python tokengeex_amd/build.py`.")
     _share_torch_hip_runtime()
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(WORD_SYMBOLS.items()) + list(WORDS_SYMBOLS.items()) + list(PHRASE_SYMBOLS.items()) + list(PATTERN_SYMBOLS.items()) + list(PATTERN64_SYMBOLS.items()) + list(REDACT_SYMBOLS.items()) + list(SHAPE_SYMBOLS.items()) + list(HASHED_SYMBOLS.items()) + list(FIND_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(WORD_SYMBOLS.items()) + list(WORDS_SYMBOLS.items()) + list(PHRASE_SYMBOLS.items()) + list(PATTERN_SYMBOLS.items()) + list(PATTERN64_SYMBOLS.items()) + list(REDACT_SYMBOLS.items()) + list(SHAPE_SYMBOLS.items()) + list(HASHED_SYMBOLS.items()) + list(FIND_SYMBOLS.items()) + list(ALLOW_SYMBOLS.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args
@@ -1731,6 +1739,53 @@ def substring_df_top(flat: np.ndarray, part_begin: np.ndarray, part_end: np.ndar
     k = n.value
     return (_take(pos, k, C.c_uint64, np.uint64), _take(ln, k, C.c_uint32, np.uint32), _take(df, k, C.c_uint32, np.uint32),
             nw.value, nd.value, cut.value)
+
+
+# ---- the allow pattern inside the pass (include/tgx_allow.h; csrc/allow.hip, csrc/allow.h) ----
+def substring_df_allow(flat: np.ndarray, part_begin: np.ndarray, part_end: np.ndarray, part_sample: np.ndarray,
+                       max_token_length: int, top_k: int, allow, insert_probability: float = 1.0, seed: int = 0, device: int = 0, part_origin=None,
+                       with_collisions: bool = False):
+    """substring_df_top over the windows that `allow` accepts only (tgx_substring_df_allow): an anchored automaton such as
+    patterns.compile_pattern(..., search=False, max_states=64), walked from every start byte on the device before anything
+    is hashed or counted -> (pos, len, df, n_windows, n_distinct, cutoff_df [, entries that met a foreign run in a discarded
+    attempt]), all over allowed substrings only."""
+    flat = np.ascontiguousarray(flat, np.uint8)
+    pb, pe = np.ascontiguousarray(part_begin, np.uint64), np.ascontiguousarray(part_end, np.uint64)
+    ps = np.ascontiguousarray(part_sample, np.uint32)
+    po = None if part_origin is None else np.ascontiguousarray(part_origin, np.uint64)
+    pos, ln, df, n, nw, nc = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+    nd, cut = C.c_uint64(), C.c_uint32()
+    check(lib.tgx_substring_df_allow(device, ptr(flat) if flat.size else None, flat.size, ptr(pb), ptr(pe), ptr(ps), None if po is None else ptr(po), pb.shape[0],
+                                     max_token_length, float(insert_probability), seed & (2**64 - 1), C.byref(dfa64_struct(allow)), int(top_k), C.byref(pos),
+                                     C.byref(ln), C.byref(df), C.byref(n), C.byref(nw), C.byref(nc), C.byref(nd), C.byref(cut)))
+    k = n.value
+    out = (_take(pos, k, C.c_uint64, np.uint64), _take(ln, k, C.c_uint32, np.uint32), _take(df, k, C.c_uint32, np.uint32),
+           nw.value, nd.value, cut.value)
+    return out + (nc.value,) if with_collisions else out
+
+
+def allow_masks_host(flat: np.ndarray, part_begin: np.ndarray, part_end: np.ndarray, part_sample: np.ndarray, max_token_length: int, allow,
+                     insert_probability: float = 1.0, seed: int = 0, part_origin=None):
+    """Host twin of substring_df_allow's first kernel (tgx_allow_masks_host: the walk's trips, the limit, the settling rule
+    and the draw through the kernels' header, no device) -> (mask uint32[N], n_windows): bit l - 1 of mask[p] is set iff the
+    window of l bytes at p is kept."""
+    flat = np.ascontiguousarray(flat, np.uint8)
+    pb, pe = np.ascontiguousarray(part_begin, np.uint64), np.ascontiguousarray(part_end, np.uint64)
+    ps = np.ascontiguousarray(part_sample, np.uint32)
+    po = None if part_origin is None else np.ascontiguousarray(part_origin, np.uint64)
+    mask, nw = np.full(flat.size, 0xFFFFFFFF, np.uint32), C.c_uint64()
+    check(lib.tgx_allow_masks_host(ptr(flat) if flat.size else None, flat.size, ptr(pb), ptr(pe), ptr(ps), None if po is None else ptr(po), pb.shape[0],
+                                   max_token_length, float(insert_probability), seed & (2**64 - 1), C.byref(dfa64_struct(allow)),
+                                   ptr(mask) if mask.size else None, C.byref(nw)))
+    return mask, nw.value
+
+
+def allow_last_times() -> dict[str, float]:
+    """Device time in ms of each stage of the calling thread's last substring_df_allow call (tgx_allow_last_times)."""
+    names = (C.c_char_p * 8)()
+    ms = (C.c_float * 8)()
+    n = lib.tgx_allow_last_times(names, ms, 8)
+    return {names[i].decode(): float(ms[i]) for i in range(n)}
 
 
 def generate_u01(seed: int, sample: int, window_hash: int) -> float:

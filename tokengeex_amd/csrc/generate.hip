@@ -19,6 +19,10 @@
 // What stays on the host, as in the reference: the split regex (parts arrive as byte ranges), the allow regex
 // (a pure function of the candidate: applied to the distinct substrings that come back instead of to every
 // window) and the added / suggested tokens.  HBM-bound byte and integer work; no MFMA.
+//
+// The allow regex as an automaton is served by window kernels of their own (allow.hip, include/tgx_allow.h): the
+// checks, the uploads, the scan and everything from the sort on are the functions of generate.h, defined below, which
+// both paths call.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -33,23 +37,11 @@
 
 #include "../../include/tgx.h"
 #include "device_internal.h"
+#include "generate.h"
 
 tgx_status tgx_set_error(tgx_status st, const char* msg);  // tgx_api.cpp
 
 namespace tgx {
-
-constexpr uint64_t kFnvOffset = 0xCBF29CE484222325ULL, kFnvPrime = 0x100000001B3ULL;
-
-// same function as tgx_generate_u01 below and tokengeex_amd/generate.py::_u01
-__host__ __device__ inline double generate_u01(uint64_t seed, uint64_t sample, uint64_t h) {
-    uint64_t x = seed ^ (sample * 0x9E3779B97F4A7C15ULL) ^ (h * 0xC2B2AE3D27D4EB4FULL);
-    x ^= x >> 30;
-    x *= 0xBF58476D1CE4E5B9ULL;
-    x ^= x >> 27;
-    x *= 0x94D049BB133111EBULL;
-    x ^= x >> 31;
-    return (double)(x >> 11) * (1.0 / 9007199254740992.0);
-}
 
 struct WindowParams {
     const uint8_t* text;          // padded: reads up to 32 bytes past a position are safe
@@ -95,12 +87,9 @@ __global__ __launch_bounds__(256) void window_kernel(WindowParams P) {
         uint64_t h = kFnvOffset, g = kFnvOffset ^ P.salt;
         for (uint32_t len = 1; len <= P.max_len && p + len <= end; ++len) {
             const uint64_t c = (uint64_t)P.text[p + len - 1];
-            h = (h ^ c) * kFnvPrime;
-            if (P.salt) g = ((g ^ c) * 0x9E3779B97F4A7C15ULL) ^ (g >> 29);  // an unrelated mixing chain: keys that met under h part here
+            generate_hash_byte(c, P.salt, h, g);
             const bool boundary = (p + len == end) || (P.text[p + len] & 0xC0u) != 0x80u;
-            // one draw per OCCURRENCE (src/generate.rs:84-89, 108-113: `rng.gen_range(0.0..1.0) < insert_probability` inside the loops
-            // over positions and lengths): the stand-in for the thread RNG hashes (seed, sample, offset in the sample, length)
-            if (boundary && (P.prob >= 1.0 || generate_u01(P.seed, sample, ((p - origin) << 8) | len) < P.prob)) {
+            if (boundary && generate_keep(P.prob, P.seed, sample, p - origin, len)) {
                 emit(kept, (P.salt ? g : h) & P.key_mask, len);
                 kept++;
             }
@@ -125,7 +114,7 @@ __global__ __launch_bounds__(256) void window_kernel(WindowParams P) {
     const uint64_t at = P.blk_offs[blockIdx.x] + before + (incl - kept);
     windows([&](uint32_t i, uint64_t h, uint32_t len) {
         P.keys[at + i] = h;
-        P.vals[at + i] = ((uint64_t)sample << 37) | (p << 5) | (uint64_t)(len - 1u);
+        P.vals[at + i] = generate_value(sample, p, len);
     });
 }
 
@@ -182,137 +171,143 @@ __global__ __launch_bounds__(256) void run_check_kernel(const uint8_t* __restric
     if (!same) atomicAdd(collisions, 1ull);
 }
 
-}  // namespace tgx
+// ---- what every path of the pass shares (generate.h) ----------------------------------------------------------------------
 
-extern "C" {
+void* GenerateScratch::alloc(size_t bytes) {
+    void* p = nullptr;
+    if (hipMalloc(&p, std::max<size_t>(bytes, 256)) != hipSuccess) return nullptr;
+    owned.push_back(p);
+    // (these buffers bypass the pool; TGX_POOL_FILL covers them all the same)
+    if (tgx::dev::pool_fill(device, p, std::max<size_t>(bytes, 256)) != hipSuccess) return nullptr;
+    return p;
+}
 
-double tgx_generate_u01(uint64_t seed, uint64_t sample, uint64_t window_hash) { return tgx::generate_u01(seed, sample, window_hash); }
+void GenerateScratch::release() {
+    for (void* p : owned) (void)hipFree(p);
+    owned.clear();
+}
 
-// Document frequencies of the char-aligned substrings of at most max_token_length (<= 32) bytes of the parts
-// text[part_begin[k], part_end[k]) (sorted, disjoint; part_sample[k] non-decreasing), every OCCURRENCE kept with probability
-// insert_probability (src/generate.rs:84-89, 108-113: a substring with k occurrences in a sample is counted for it with
-// probability 1 - (1 - p)^k); part_origin[k]: where the part's sample begins in `text` (NULL: the part is its own sample) —
-// the draw of an occurrence is tgx_generate_u01(seed, sample, offset in the sample << 8 | length).  Out: one entry per distinct substring — the position and length
-// of one occurrence and the number of samples it occurs in — malloc'd (tgx_free), in ascending order of the
-// substrings' sort keys (their FNV-1a hashes).  Two different substrings with one 64-bit key are DETECTED (every entry of
-// a run is compared with the run's first, byte by byte) and resolved: the pass is sorted again under a second, salted hash
-// of the windows' bytes, up to three times; *n_collisions reports how many entries met a foreign run in the attempts that
-// were discarded.  text must be < 4 GiB.
-static tgx_status substring_df_impl(int device, const uint8_t* text, uint64_t n_bytes, const uint64_t* part_begin,
-                                    const uint64_t* part_end, const uint32_t* part_sample, const uint64_t* part_origin, uint64_t n_parts,
-                                    uint32_t max_token_length, double insert_probability, uint64_t seed, uint64_t top_k,
-                                    uint64_t** out_pos, uint32_t** out_len, uint32_t** out_df, uint64_t* n_out,
-                                    uint64_t* n_windows, uint64_t* n_collisions, uint64_t* n_distinct, uint32_t* cutoff_df) {
-    using namespace tgx;
-    if (n_distinct) *n_distinct = 0;
-    if (cutoff_df) *cutoff_df = 0;
-    if (!out_pos || !out_len || !out_df || !n_out) return tgx_set_error(TGX_ERR_INVALID, "tgx_substring_df: NULL argument");
-    *out_pos = nullptr;
-    *out_len = nullptr;
-    *out_df = nullptr;
-    *n_out = 0;
-    if (n_windows) *n_windows = 0;
-    if (n_collisions) *n_collisions = 0;
-    if (n_parts && (!text || !part_begin || !part_end || !part_sample)) return tgx_set_error(TGX_ERR_INVALID, "tgx_substring_df: NULL argument");
-    // (windows of up to 32 bytes: the reference's CLI default is 24, src/cli.rs:675; a value carries length - 1 in 5 bits)
-    if (max_token_length < 1 || max_token_length > 32) return tgx_set_error(TGX_ERR_UNSUPPORTED, "tgx_substring_df: max_token_length must be 1..32");
-    if (n_bytes >= (1ull << 32)) return tgx_set_error(TGX_ERR_UNSUPPORTED, "tgx_substring_df: feed at most 4 GiB per call");
-    if (n_parts == 0 || n_bytes == 0) return TGX_OK;
-    for (uint64_t k = 0; k < n_parts; k++) {
-        if (part_origin && part_origin[k] > part_begin[k]) return tgx_set_error(TGX_ERR_INVALID, "tgx_substring_df: a part begins before its sample");
-        if (part_end[k] < part_begin[k] || part_end[k] > n_bytes || (k && part_begin[k] < part_end[k - 1]) ||
-            (k && part_sample[k] < part_sample[k - 1]) || part_sample[k] >= (1u << 27))
-            return tgx_set_error(TGX_ERR_INVALID, "tgx_substring_df: parts must be sorted, disjoint, inside the text, with ascending sample ids below 2^27");
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-        (void)hipGetLastError();
-        return tgx_set_error(TGX_ERR_DEVICE, "no usable HIP device (gfx950 required)");
-    }
-    std::vector<void*> owned;
-    auto fail = [&](tgx_status st, const char* msg) {
-        (void)hipDeviceSynchronize();
-        for (void* p : owned) (void)hipFree(p);
-        return tgx_set_error(st, msg);
-    };
-    auto dalloc = [&](size_t bytes) -> void* {
-        void* p = nullptr;
-        if (hipMalloc(&p, std::max<size_t>(bytes, 256)) != hipSuccess) return nullptr;
-        owned.push_back(p);
-        // (these buffers bypass the pool; TGX_POOL_FILL covers them all the same)
-        if (tgx::dev::pool_fill(device, p, std::max<size_t>(bytes, 256)) != hipSuccess) return nullptr;
-        return p;
-    };
-    // (TGX_DEBUG as tgx_api.cpp reads it: set, not empty, not "0")
+namespace {
+
+tgx_status generate_fail(GenerateScratch& scratch, tgx_status st, const char* msg) {
+    (void)hipDeviceSynchronize();
+    scratch.release();
+    return tgx_set_error(st, msg);
+}
+
+// (TGX_DEBUG as tgx_api.cpp reads it: set, not empty, not "0")
+bool generate_debug() {
     const char* dbg_env = getenv("TGX_DEBUG");
-    const bool dbg = dbg_env && *dbg_env && *dbg_env != '0';
+    return dbg_env && *dbg_env && *dbg_env != '0';
+}
+
+// (expands where `scratch` and `dbg` are visible)
 #define G_TRY(expr)                                                       \
     do {                                                                  \
         if (dbg) { fprintf(stderr, "[tgx] generate: %s\n", #expr); fflush(stderr); } \
-        if ((expr) != hipSuccess) return fail(TGX_ERR_DEVICE, "HIP error in tgx_substring_df: " #expr); \
-        if (dbg && hipDeviceSynchronize() != hipSuccess) return fail(TGX_ERR_DEVICE, "HIP error after " #expr); \
+        if ((expr) != hipSuccess) return generate_fail(scratch, TGX_ERR_DEVICE, "HIP error in tgx_substring_df: " #expr); \
+        if (dbg && hipDeviceSynchronize() != hipSuccess) return generate_fail(scratch, TGX_ERR_DEVICE, "HIP error after " #expr); \
     } while (0)
-    G_TRY(hipSetDevice(device));
-    const uint64_t n_blocks = (n_bytes + 255) / 256;
+
+}  // namespace
+
+tgx_status substring_df_check(const GenerateArgs& a, bool* empty) {
+    *empty = false;
+    if (a.n_distinct) *a.n_distinct = 0;
+    if (a.cutoff_df) *a.cutoff_df = 0;
+    if (!a.out_pos || !a.out_len || !a.out_df || !a.n_out) return tgx_set_error(TGX_ERR_INVALID, "tgx_substring_df: NULL argument");
+    *a.out_pos = nullptr;
+    *a.out_len = nullptr;
+    *a.out_df = nullptr;
+    *a.n_out = 0;
+    if (a.n_windows) *a.n_windows = 0;
+    if (a.n_collisions) *a.n_collisions = 0;
+    if (a.n_parts && (!a.text || !a.part_begin || !a.part_end || !a.part_sample)) return tgx_set_error(TGX_ERR_INVALID, "tgx_substring_df: NULL argument");
+    if (const char* why = generate_check_sizes(a.n_bytes, a.max_token_length)) return tgx_set_error(TGX_ERR_UNSUPPORTED, why);
+    if (a.n_parts == 0 || a.n_bytes == 0) {
+        *empty = true;
+        return TGX_OK;
+    }
+    if (const char* why = generate_check_parts(a.n_bytes, a.part_begin, a.part_end, a.part_sample, a.part_origin, a.n_parts)) return tgx_set_error(TGX_ERR_INVALID, why);
+    return TGX_OK;
+}
+
+tgx_status substring_df_upload(const GenerateArgs& a, GenerateScratch& scratch, GenerateInput* in) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || a.device < 0 || a.device >= ndev) {
+        (void)hipGetLastError();
+        return tgx_set_error(TGX_ERR_DEVICE, "no usable HIP device (gfx950 required)");
+    }
+    scratch.device = a.device;
+    const bool dbg = generate_debug();
+    G_TRY(hipSetDevice(a.device));
+    const uint64_t n_bytes = a.n_bytes, n_parts = a.n_parts, n_blocks = (n_bytes + kGenerateBlock - 1) / kGenerateBlock;
     // first part whose end lies beyond each block's start
     std::vector<uint32_t> blk_part(n_blocks);
     {
         uint64_t k = 0;
         for (uint64_t b = 0; b < n_blocks; b++) {
-            while (k < n_parts && part_end[k] <= b * 256) k++;
+            while (k < n_parts && a.part_end[k] <= b * kGenerateBlock) k++;
             blk_part[b] = (uint32_t)std::min<uint64_t>(k, 0xFFFFFFFFull);
         }
     }
-    uint8_t* d_text = (uint8_t*)dalloc(n_bytes + 64);
-    uint64_t* d_pb = (uint64_t*)dalloc(n_parts * 8);
-    uint64_t* d_pe = (uint64_t*)dalloc(n_parts * 8);
-    uint32_t* d_ps = (uint32_t*)dalloc(n_parts * 4);
-    uint32_t* d_bp = (uint32_t*)dalloc(n_blocks * 4);
-    uint32_t* d_bc = (uint32_t*)dalloc(n_blocks * 4);
-    uint64_t* d_bo = (uint64_t*)dalloc((n_blocks + 1) * 8);
-    unsigned long long* d_ctr = (unsigned long long*)dalloc(64);
-    if (!d_text || !d_pb || !d_pe || !d_ps || !d_bp || !d_bc || !d_bo || !d_ctr) return fail(TGX_ERR_DEVICE, "out of device memory (generate)");
+    uint8_t* d_text = (uint8_t*)scratch.alloc(n_bytes + 64);
+    uint64_t* d_pb = (uint64_t*)scratch.alloc(n_parts * 8);
+    uint64_t* d_pe = (uint64_t*)scratch.alloc(n_parts * 8);
+    uint32_t* d_ps = (uint32_t*)scratch.alloc(n_parts * 4);
+    uint32_t* d_bp = (uint32_t*)scratch.alloc(n_blocks * 4);
+    unsigned long long* d_ctr = (unsigned long long*)scratch.alloc(64);
+    if (!d_text || !d_pb || !d_pe || !d_ps || !d_bp || !d_ctr) return generate_fail(scratch, TGX_ERR_DEVICE, "out of device memory (generate)");
     G_TRY(hipMemset(d_text + n_bytes, 0, 64));
-    G_TRY(hipMemcpy(d_text, text, n_bytes, hipMemcpyHostToDevice));
-    G_TRY(hipMemcpy(d_pb, part_begin, n_parts * 8, hipMemcpyHostToDevice));
-    G_TRY(hipMemcpy(d_pe, part_end, n_parts * 8, hipMemcpyHostToDevice));
-    G_TRY(hipMemcpy(d_ps, part_sample, n_parts * 4, hipMemcpyHostToDevice));
-    uint64_t* d_po = (uint64_t*)dalloc(n_parts * 8);
-    if (!d_po) return fail(TGX_ERR_DEVICE, "out of device memory (generate)");
-    G_TRY(hipMemcpy(d_po, part_origin ? part_origin : part_begin, n_parts * 8, hipMemcpyHostToDevice));
+    G_TRY(hipMemcpy(d_text, a.text, n_bytes, hipMemcpyHostToDevice));
+    G_TRY(hipMemcpy(d_pb, a.part_begin, n_parts * 8, hipMemcpyHostToDevice));
+    G_TRY(hipMemcpy(d_pe, a.part_end, n_parts * 8, hipMemcpyHostToDevice));
+    G_TRY(hipMemcpy(d_ps, a.part_sample, n_parts * 4, hipMemcpyHostToDevice));
+    uint64_t* d_po = (uint64_t*)scratch.alloc(n_parts * 8);
+    if (!d_po) return generate_fail(scratch, TGX_ERR_DEVICE, "out of device memory (generate)");
+    G_TRY(hipMemcpy(d_po, a.part_origin ? a.part_origin : a.part_begin, n_parts * 8, hipMemcpyHostToDevice));
     G_TRY(hipMemcpy(d_bp, blk_part.data(), n_blocks * 4, hipMemcpyHostToDevice));
     G_TRY(hipMemset(d_ctr, 0, 64));
-    WindowParams P{};
-    P.text = d_text;
-    P.n_bytes = n_bytes;
-    P.part_begin = d_pb;
-    P.part_end = d_pe;
-    P.part_sample = d_ps;
-    P.part_origin = d_po;
-    P.n_parts = n_parts;
-    P.blk_part = d_bp;
-    P.max_len = max_token_length;
-    P.prob = insert_probability;
-    P.seed = seed;
-    P.blk_count = d_bc;
-    hipLaunchKernelGGL(window_kernel<false>, dim3((uint32_t)n_blocks), dim3(256), 0, 0, P);
-    G_TRY(hipGetLastError());
-    // exclusive scan of the block counts (u32 -> u64)
+    *in = GenerateInput{d_text, d_pb, d_pe, d_po, d_ps, d_bp, n_blocks, d_ctr};
+    return TGX_OK;
+}
+
+// exclusive scan of the counts (u32 -> u64)
+tgx_status substring_df_offsets(GenerateScratch& scratch, const uint32_t* d_count, uint64_t* d_offs, uint64_t n, uint64_t* total) {
+    const bool dbg = generate_debug();
+    uint32_t* d_bc = const_cast<uint32_t*>(d_count);
+    uint64_t* d_bo = d_offs;
     {
         size_t tb = 0;
-        G_TRY((rocprim::exclusive_scan(nullptr, tb, d_bc, d_bo, (uint64_t)0, (size_t)n_blocks, rocprim::plus<uint64_t>())));
-        void* tmp = dalloc(tb);
-        if (!tmp) return fail(TGX_ERR_DEVICE, "out of device memory (generate)");
-        G_TRY((rocprim::exclusive_scan(tmp, tb, d_bc, d_bo, (uint64_t)0, (size_t)n_blocks, rocprim::plus<uint64_t>())));
+        G_TRY((rocprim::exclusive_scan(nullptr, tb, d_bc, d_bo, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>())));
+        void* tmp = scratch.alloc(tb);
+        if (!tmp) return generate_fail(scratch, TGX_ERR_DEVICE, "out of device memory (generate)");
+        G_TRY((rocprim::exclusive_scan(tmp, tb, d_bc, d_bo, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>())));
     }
     uint64_t last_off = 0;
     uint32_t last_cnt = 0;
-    G_TRY(hipMemcpy(&last_off, d_bo + (n_blocks - 1), 8, hipMemcpyDeviceToHost));
-    G_TRY(hipMemcpy(&last_cnt, d_bc + (n_blocks - 1), 4, hipMemcpyDeviceToHost));
-    const uint64_t M = last_off + last_cnt;
-    if (n_windows) *n_windows = M;
+    G_TRY(hipMemcpy(&last_off, d_bo + (n - 1), 8, hipMemcpyDeviceToHost));
+    G_TRY(hipMemcpy(&last_cnt, d_bc + (n - 1), 4, hipMemcpyDeviceToHost));
+    *total = last_off + last_cnt;
+    return TGX_OK;
+}
+
+tgx_status substring_df_tail(const GenerateArgs& a, GenerateScratch& scratch, const GenerateInput& in, uint64_t M, const GenerateEmit& emit, GenerateTimer* timer) {
+    const bool dbg = generate_debug();
+    const uint8_t* d_text = in.text;
+    unsigned long long* d_ctr = in.ctr;
+    const uint64_t top_k = a.top_k;
+    auto fail = [&](tgx_status st, const char* msg) { return generate_fail(scratch, st, msg); };
+    auto dalloc = [&](size_t bytes) { return scratch.alloc(bytes); };
+    auto stage_begin = [&](int stage) {
+        if (timer) timer->begin(stage);
+    };
+    auto stage_end = [&](int stage) {
+        if (timer) timer->end(stage);
+    };
+    if (a.n_windows) *a.n_windows = M;
     if (M == 0) {
-        for (void* p : owned) (void)hipFree(p);
+        scratch.release();
         return TGX_OK;
     }
     if (M >= (1ull << 32)) return fail(TGX_ERR_UNSUPPORTED, "tgx_substring_df: more than 2^32 windows in one call: feed smaller batches");
@@ -321,9 +316,6 @@ static tgx_status substring_df_impl(int device, const uint8_t* text, uint64_t n_
     uint64_t* d_keys2 = (uint64_t*)dalloc(M * 8);
     uint64_t* d_vals2 = (uint64_t*)dalloc(M * 8);
     if (!d_keys || !d_vals || !d_keys2 || !d_vals2) return fail(TGX_ERR_DEVICE, "out of device memory (generate: windows)");
-    P.blk_offs = d_bo;
-    P.keys = d_keys;
-    P.vals = d_vals;
     // forced-collision test (TGX_KNOBS=1 TGX_GENERATE_COLLIDE=bits): the first attempt keeps that many key bits only
     uint64_t first_mask = ~0ull;
     {
@@ -338,12 +330,14 @@ static tgx_status substring_df_impl(int device, const uint8_t* text, uint64_t n_
     uint32_t* d_df = nullptr;
     uint32_t n_runs = 0;
     unsigned long long coll_total = 0, coll = 0;
-    for (int attempt = 0; attempt < 4; attempt++) {
-        P.salt = attempt ? 0xD6E8FEB86659FD93ULL * (uint64_t)attempt : 0ull;
-        P.key_mask = attempt ? ~0ull : first_mask;
+    for (int attempt = 0; attempt < 4; attempt++) {  // (a timed call reports the stages of its last attempt)
+        const uint64_t salt = attempt ? 0xD6E8FEB86659FD93ULL * (uint64_t)attempt : 0ull;
+        const uint64_t key_mask = attempt ? ~0ull : first_mask;
         G_TRY(hipMemset(d_ctr, 0, 64));
-        hipLaunchKernelGGL(window_kernel<true>, dim3((uint32_t)n_blocks), dim3(256), 0, 0, P);
-        G_TRY(hipGetLastError());
+        stage_begin(kGenStageEmit);
+        G_TRY(emit(salt, key_mask, d_keys, d_vals));
+        stage_end(kGenStageEmit);
+        stage_begin(kGenStageSort);
         {
             size_t tb = 0;
             G_TRY(rocprim::radix_sort_pairs(nullptr, tb, d_keys, d_keys2, d_vals, d_vals2, (size_t)M));
@@ -351,6 +345,8 @@ static tgx_status substring_df_impl(int device, const uint8_t* text, uint64_t n_
             if (!tmp) return fail(TGX_ERR_DEVICE, "out of device memory (generate: sort)");
             G_TRY(rocprim::radix_sort_pairs(tmp, tb, d_keys, d_keys2, d_vals, d_vals2, (size_t)M));
         }
+        stage_end(kGenStageSort);
+        stage_begin(kGenStageRuns);
         // run ids: inclusive scan of the run heads
         hipLaunchKernelGGL(run_heads_kernel, dim3(mblocks), dim3(256), 0, 0, d_keys2, M, d_head);
         G_TRY(hipGetLastError());
@@ -371,6 +367,7 @@ static tgx_status substring_df_impl(int device, const uint8_t* text, uint64_t n_
         G_TRY(hipGetLastError());
         hipLaunchKernelGGL(run_check_kernel, dim3(mblocks), dim3(256), 0, 0, d_text, d_vals2, d_run, M, n_runs, d_rep, d_ctr, d_ctr + 1);
         G_TRY(hipGetLastError());
+        stage_end(kGenStageRuns);
         unsigned long long ctr[2] = {0, 0};  // [0] entries that met a foreign run (a key collision), [1] entries whose run id was out of range
         G_TRY(hipMemcpy(ctr, d_ctr, 16, hipMemcpyDeviceToHost));
         if (ctr[1]) return fail(TGX_ERR_DEVICE, "tgx_substring_df: entries with a run id outside [1, n_runs] (run ids corrupt)");
@@ -378,9 +375,9 @@ static tgx_status substring_df_impl(int device, const uint8_t* text, uint64_t n_
         coll_total += coll;
         if (!coll) break;  // every run is one substring: the counts are exact
     }
-    if (n_collisions) *n_collisions = coll_total;
+    if (a.n_collisions) *a.n_collisions = coll_total;
     if (coll) return fail(TGX_ERR_UNSUPPORTED, "tgx_substring_df: different substrings shared a 64-bit key under four independent hashes");
-    if (n_distinct) *n_distinct = n_runs;
+    if (a.n_distinct) *a.n_distinct = n_runs;
     // top_k: only the top_k most frequent substrings leave the device (VocabularyGenerator::generate keeps the most
     // frequent ones, src/generate.rs:150-152, 199-213): a stable descending radix sort of (df, representative) —
     // equal frequencies stay in ascending hash order —, and the frequency of the first substring that is cut off
@@ -389,20 +386,20 @@ static tgx_status substring_df_impl(int device, const uint8_t* text, uint64_t n_
         uint32_t* d_df2 = (uint32_t*)dalloc((size_t)n_runs * 4);
         uint64_t* d_rep2 = (uint64_t*)dalloc((size_t)n_runs * 8);
         if (!d_df2 || !d_rep2) return fail(TGX_ERR_DEVICE, "out of device memory (generate: top-k)");
+        stage_begin(kGenStageTop);
         size_t tb = 0;
         G_TRY(rocprim::radix_sort_pairs_desc(nullptr, tb, d_df, d_df2, d_rep, d_rep2, (size_t)n_runs));
         void* tmp = dalloc(tb);
         if (!tmp) return fail(TGX_ERR_DEVICE, "out of device memory (generate: top-k sort)");
         G_TRY(rocprim::radix_sort_pairs_desc(tmp, tb, d_df, d_df2, d_rep, d_rep2, (size_t)n_runs));
+        stage_end(kGenStageTop);
         uint32_t cut = 0;
         G_TRY(hipMemcpy(&cut, d_df2 + top_k, 4, hipMemcpyDeviceToHost));
-        if (cutoff_df) *cutoff_df = cut;
+        if (a.cutoff_df) *a.cutoff_df = cut;
         d_df = d_df2;
         d_rep = d_rep2;
         n_ret = top_k;
     }
-    const uint32_t n_runs_all = n_runs;
-    (void)n_runs_all;
     n_runs = (uint32_t)n_ret;
     std::vector<uint64_t> rep(n_runs);
     uint64_t* pos = (uint64_t*)malloc(sizeof(uint64_t) * std::max<uint32_t>(n_runs, 1));
@@ -425,22 +422,82 @@ static tgx_status substring_df_impl(int device, const uint8_t* text, uint64_t n_
         pos[r] = (rep[r] >> 5) & 0xFFFFFFFFull;
         len[r] = (uint32_t)(rep[r] & 31u) + 1u;
     }
-    for (void* p : owned) (void)hipFree(p);
-#undef G_TRY
-    *out_pos = pos;
-    *out_len = len;
-    *out_df = df;
-    *n_out = n_runs;
+    scratch.release();
+    *a.out_pos = pos;
+    *a.out_len = len;
+    *a.out_df = df;
+    *a.n_out = n_runs;
     return TGX_OK;
 }
+
+namespace {
+
+// Document frequencies of the char-aligned substrings of at most max_token_length (<= 32) bytes of the parts
+// text[part_begin[k], part_end[k]) (sorted, disjoint; part_sample[k] non-decreasing), every OCCURRENCE kept with probability
+// insert_probability (src/generate.rs:84-89, 108-113: a substring with k occurrences in a sample is counted for it with
+// probability 1 - (1 - p)^k); part_origin[k]: where the part's sample begins in `text` (NULL: the part is its own sample) —
+// the draw of an occurrence is tgx_generate_u01(seed, sample, offset in the sample << 8 | length).  Out: one entry per distinct substring — the position and length
+// of one occurrence and the number of samples it occurs in — malloc'd (tgx_free), in ascending order of the
+// substrings' sort keys (their FNV-1a hashes).  Two different substrings with one 64-bit key are DETECTED (every entry of
+// a run is compared with the run's first, byte by byte) and resolved: the pass is sorted again under a second, salted hash
+// of the windows' bytes, up to three times; *n_collisions reports how many entries met a foreign run in the attempts that
+// were discarded.  text must be < 4 GiB.
+tgx_status substring_df_impl(const GenerateArgs& a) {
+    bool empty = false;
+    tgx_status st = substring_df_check(a, &empty);
+    if (st != TGX_OK || empty) return st;
+    GenerateScratch scratch;
+    GenerateInput in{};
+    if ((st = substring_df_upload(a, scratch, &in)) != TGX_OK) return st;
+    const bool dbg = generate_debug();
+    uint32_t* d_bc = (uint32_t*)scratch.alloc(in.n_blocks * 4);
+    uint64_t* d_bo = (uint64_t*)scratch.alloc((in.n_blocks + 1) * 8);
+    if (!d_bc || !d_bo) return generate_fail(scratch, TGX_ERR_DEVICE, "out of device memory (generate)");
+    WindowParams P{};
+    P.text = in.text;
+    P.n_bytes = a.n_bytes;
+    P.part_begin = in.part_begin;
+    P.part_end = in.part_end;
+    P.part_sample = in.part_sample;
+    P.part_origin = in.part_origin;
+    P.n_parts = a.n_parts;
+    P.blk_part = in.blk_part;
+    P.max_len = a.max_token_length;
+    P.prob = a.insert_probability;
+    P.seed = a.seed;
+    P.blk_count = d_bc;
+    hipLaunchKernelGGL(window_kernel<false>, dim3((uint32_t)in.n_blocks), dim3(256), 0, 0, P);
+    G_TRY(hipGetLastError());
+    uint64_t M = 0;
+    if ((st = substring_df_offsets(scratch, d_bc, d_bo, in.n_blocks, &M)) != TGX_OK) return st;
+    P.blk_offs = d_bo;
+    return substring_df_tail(a, scratch, in, M, [&](uint64_t salt, uint64_t key_mask, uint64_t* keys, uint64_t* vals) {
+        P.salt = salt;
+        P.key_mask = key_mask;
+        P.keys = keys;
+        P.vals = vals;
+        hipLaunchKernelGGL(window_kernel<true>, dim3((uint32_t)in.n_blocks), dim3(256), 0, 0, P);
+        return hipGetLastError();
+    }, nullptr);
+}
+
+#undef G_TRY
+
+}  // namespace
+
+}  // namespace tgx
+
+extern "C" {
+
+double tgx_generate_u01(uint64_t seed, uint64_t sample, uint64_t window_hash) { return tgx::generate_u01(seed, sample, window_hash); }
 
 tgx_status tgx_substring_df(int device, const uint8_t* text, uint64_t n_bytes, const uint64_t* part_begin,
                             const uint64_t* part_end, const uint32_t* part_sample, const uint64_t* part_origin, uint64_t n_parts,
                             uint32_t max_token_length, double insert_probability, uint64_t seed, uint64_t** out_pos,
                             uint32_t** out_len, uint32_t** out_df, uint64_t* n_out, uint64_t* n_windows,
                             uint64_t* n_collisions) {
-    return substring_df_impl(device, text, n_bytes, part_begin, part_end, part_sample, part_origin, n_parts, max_token_length,
-                             insert_probability, seed, 0, out_pos, out_len, out_df, n_out, n_windows, n_collisions, nullptr, nullptr);
+    return tgx::substring_df_impl({device, text, n_bytes, part_begin, part_end, part_sample, part_origin, n_parts, max_token_length, insert_probability, seed, 0,
+                                   out_pos, out_len, out_df, n_out, n_windows, n_collisions, nullptr, nullptr});
 }
 
 // The same with only the top_k most frequent substrings returned (descending frequency; 0 = all): *n_distinct = the
@@ -452,8 +509,8 @@ tgx_status tgx_substring_df_top(int device, const uint8_t* text, uint64_t n_byte
                                 uint32_t max_token_length, double insert_probability, uint64_t seed, uint64_t top_k,
                                 uint64_t** out_pos, uint32_t** out_len, uint32_t** out_df, uint64_t* n_out,
                                 uint64_t* n_windows, uint64_t* n_collisions, uint64_t* n_distinct, uint32_t* cutoff_df) {
-    return substring_df_impl(device, text, n_bytes, part_begin, part_end, part_sample, part_origin, n_parts, max_token_length,
-                             insert_probability, seed, top_k, out_pos, out_len, out_df, n_out, n_windows, n_collisions, n_distinct, cutoff_df);
+    return tgx::substring_df_impl({device, text, n_bytes, part_begin, part_end, part_sample, part_origin, n_parts, max_token_length, insert_probability, seed,
+                                   top_k, out_pos, out_len, out_df, n_out, n_windows, n_collisions, n_distinct, cutoff_df});
 }
 
 }  // extern "C"

@@ -12,6 +12,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "allow.h"
 #include "api_internal.h"
 #include "assemble.h"
 #include "cover.h"
@@ -37,6 +38,7 @@
 #include "unicode_tables.h"
 #include "words.h"
 #include "wordstat.h"
+#include "../../include/tgx_allow.h"
 #include "../../include/tgx_find.h"
 #include "../../include/tgx_hashed.h"
 #include "../../include/tgx_patterns.h"
@@ -2157,6 +2159,44 @@ tgx_status tgx_mine_host(const uint8_t* text, const uint64_t* offs, uint64_t n_r
     *n_out = n_top;
     if (n_distinct) *n_distinct = runs.size();
     if (n_matches) *n_matches = m.size();
+    return TGX_OK;
+}
+
+// ---- the allow filter of the document-frequency pass (include/tgx_allow.h) ----------------------------------------
+
+// The twin of allow_mask_kernel: the chunks of 64 positions, a position's part found from its block's first part as the
+// kernel finds it, and the walk's trips through allow.h; the chunks' counts add up to *n_windows.
+tgx_status tgx_allow_masks_host(const uint8_t* text, uint64_t n_bytes, const uint64_t* part_begin, const uint64_t* part_end, const uint32_t* part_sample,
+                                const uint64_t* part_origin, uint64_t n_parts, uint32_t max_token_length, double insert_probability, uint64_t seed,
+                                const tgx_dfa64* allow, uint32_t* mask, uint64_t* n_windows) {
+    const char* who = "tgx_allow_masks_host";
+    if (n_windows) *n_windows = 0;
+    if ((n_bytes && (!text || !mask)) || (n_parts && (!part_begin || !part_end || !part_sample))) return fail(TGX_ERR_INVALID, "%s: NULL argument", who);
+    if (const char* why = tgx::generate_check_sizes(n_bytes, max_token_length)) return fail(TGX_ERR_UNSUPPORTED, "%s", why);
+    if (!allow) return fail(TGX_ERR_INVALID, "%s: allow is NULL", who);
+    if (const char* why = tgx::dfa64_check(allow->n_states, allow->start, allow->next, allow->tag)) return fail(TGX_ERR_INVALID, "%s: %s", who, why);
+    if (const char* why = tgx::generate_check_parts(n_bytes, part_begin, part_end, part_sample, part_origin, n_parts)) return fail(TGX_ERR_INVALID, "%s", why);
+    std::vector<uint8_t> table(tgx::kFindTableBytes);
+    tgx::find_build_table(allow->n_states, allow->next, allow->tag, table.data());
+    uint64_t total = 0, blk_first = 0;  // blk_first: the first part whose end lies beyond the block's start (blk_part)
+    for (uint64_t chunk = 0; chunk < tgx::allow_chunks(n_bytes); chunk++) {
+        const uint64_t c0 = chunk * tgx::kAllowChunk;
+        if (chunk % tgx::kAllowBlockChunks == 0)
+            while (blk_first < n_parts && part_end[blk_first] <= c0) blk_first++;
+        uint32_t chunk_count = 0;
+        for (uint64_t p = c0; p < c0 + tgx::kAllowChunk && p < n_bytes; p++) {
+            mask[p] = 0;
+            if ((text[p] & 0xC0u) == 0x80u) continue;
+            uint64_t k = blk_first;
+            while (k < n_parts && part_end[k] <= p) k++;
+            if (k == n_parts || part_begin[k] > p) continue;
+            const tgx::AllowDraw d = {insert_probability, seed, part_sample[k], p - (part_origin ? part_origin[k] : part_begin[k])};
+            mask[p] = tgx::allow_mask_host(table.data(), allow->start, text, n_bytes, p, part_end[k], max_token_length, d);
+            chunk_count += (uint32_t)__builtin_popcount(mask[p]);
+        }
+        total += chunk_count;
+    }
+    if (n_windows) *n_windows = total;
     return TGX_OK;
 }
 

@@ -6,6 +6,9 @@ initial vocabulary `prune` starts from.
 hashes its windows, a radix sort groups equal substrings, a run pass counts distinct samples; the split regex
 reaches the device as byte ranges, the allow regex — a pure function of the candidate — is applied on the host to
 the substrings that come back, and the added / suggested tokens are searched on the host as in the reference.
+An allow pattern given as a patterns.BytePattern (the anchored automaton of compile_pattern(..., search=False,
+max_states=64)) is applied on the device instead, BEFORE the count (`tgx_substring_df_allow`, csrc/allow.hip): top_k and
+the cut-off bound are then spent on allowed substrings only.
 There is no host fallback: without a GPU (or for max_token_length > 32) the calls fail.  The checker of this path
 is the CPU oracle's restatement of the generator (test infrastructure, never imported here).
 
@@ -34,6 +37,7 @@ import numpy as np
 
 from . import _lib
 from .merge import compile_rust_regex
+from .patterns import BytePattern
 
 _M64 = (1 << 64) - 1
 
@@ -64,6 +68,13 @@ class VocabularyGenerator:
 
     def __init__(self, max_token_length: int, insert_probability: float, split=None, allow=None,
                  added_tokens=(), suggested_tokens=(), seed: int = 0, device: int = 0, top_k: int | None = None):
+        # A BytePattern as `allow` filters on the device, inside the count (tgx_substring_df_allow).  It must be ANCHORED
+        # (compile_pattern(..., search=False, max_states=64)): a window is allowed iff the plain walk over exactly its bytes
+        # ends in a tagged state.  That cannot be checked on the automaton (a search=True one is only seen to re-enter its
+        # start), so it is the caller's to get right; the two kinds that carry a mark are refused.
+        self._on_device = isinstance(allow, BytePattern)
+        if self._on_device and (getattr(allow, "find", False) or hasattr(allow, "cover")):
+            raise ValueError("VocabularyGenerator: allow takes the anchored automaton of compile_pattern(..., search=False), not a find=True or cover=True pattern")
         if device is None:
             raise _lib.TokenGeeXError("VocabularyGenerator counts on a GPU: there is no host path")
         if int(max_token_length) > 32:  # (the reference has no limit, src/generate.rs:78-83; its CLI's default is 24, src/cli.rs:675)
@@ -93,13 +104,20 @@ class VocabularyGenerator:
     def _keep(self, sample_index: int, offset: int, length: int, added: bool = False) -> bool:
         return self.insert_probability >= 1.0 or _u01(self.seed, sample_index, offset, length, added) < self.insert_probability
 
+    def _allows(self, cand: str) -> bool:
+        if self.allow is None:
+            return True
+        if self._on_device:
+            return self.allow.fullmatch(cand.encode("utf-8", "surrogatepass"))
+        return bool(self.allow.search(cand))
+
     def _extra_kept(self, sample_index: int, sample: str, b: bytes, parts, t: str, tb: bytes) -> bool:
         """Does sample's set hold the added / suggested token t (src/generate.rs:72-127)?  Either a window that spells it was
         kept (every char-aligned occurrence inside a part is a candidate with a draw of its own, if the token is short enough
         and allowed) or one of its successive non-overlapping matches was (str::match_indices, a draw per match)."""
         if self.insert_probability >= 1.0:
             return t in sample
-        if len(tb) <= self.max_token_length and (self.allow is None or self.allow.search(t)):
+        if len(tb) <= self.max_token_length and self._allows(t):
             for a, z in parts:
                 o = b.find(tb, a, z)
                 while o >= 0:
@@ -180,9 +198,13 @@ class VocabularyGenerator:
         extra_set = set(extra)
         if pb.size:
             # the keep rule sees the global sample index (the device packs it into 27 bits)
-            pos, ln, df, _, _, cut = _lib.substring_df_top(flat, pb, pe, (ps.astype(np.uint64) + first).astype(np.uint32),
-                                                           self.max_token_length, self.top_k, self.insert_probability, self.seed, self.device,
-                                                           part_origin=po)
+            ids = (ps.astype(np.uint64) + first).astype(np.uint32)
+            if self._on_device:  # filtered before the count: top_k and the cut-off bound are spent on allowed substrings only
+                pos, ln, df, _, _, cut = _lib.substring_df_allow(flat, pb, pe, ids, self.max_token_length, self.top_k, self.allow, self.insert_probability,
+                                                                 self.seed, self.device, part_origin=po)
+            else:
+                pos, ln, df, _, _, cut = _lib.substring_df_top(flat, pb, pe, ids, self.max_token_length, self.top_k, self.insert_probability, self.seed,
+                                                               self.device, part_origin=po)
             self.passes += 1  # (counted once the device has answered: a refused batch is retried in halves)
             self._bound_total += cut
             raw = flat.tobytes()
@@ -190,7 +212,7 @@ class VocabularyGenerator:
                 cand = raw[p_:p_ + l_].decode("utf-8", "surrogatepass")
                 if cand in extra_set:
                     continue  # counted below: a sample's set holds the token once, whichever rule put it there
-                if self.allow is None or self.allow.search(cand):
+                if self._on_device or self.allow is None or self.allow.search(cand):
                     self._freq[cand] = self._freq.get(cand, 0) + d_
                     if cut:
                         self._bound_seen[cand] = self._bound_seen.get(cand, 0) + cut

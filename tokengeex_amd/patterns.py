@@ -323,6 +323,14 @@ class BytePattern:
     def __repr__(self):
         return f"BytePattern({list(self.patterns)!r}, n_states={self.n_states})"
 
+    def fullmatch(self, data: bytes) -> bool:
+        """The plain walk from .start over all of data: does it end in a tagged state?  For an anchored automaton
+        (search=False) that is "the pattern matches exactly data", what the device's allow filter asks of a window."""
+        q = self.start
+        for b in data:
+            q = int(self.next[b][q])
+        return bool(self.tag[q])
+
 
 class BackPattern:
     """The backward half of a cover pattern: .n_states, .start, .next (uint8 [256, 16]) and an all-zero .tag, the fields of
