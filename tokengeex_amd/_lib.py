@@ -308,6 +308,14 @@ ALLOW_SYMBOLS = {
     "tgx_allow_last_times": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_float), _i]),
 }
 
+# every exported symbol of include/tgx_dupspans.h, a header of its own in the same way: bound and checked at import too
+DUPSPAN_SYMBOLS = {
+    "tgx_corpus_dup_spans_device": (_i, [_vp, _u32, _u32, _u64, _u32, _vp, _vp, _vp]),
+    "tgx_result_dup_spans_device": (_i, [_vp, _u32, _u32, _u64, _u32, _vp, _vp, _vp]),
+    "tgx_dup_spans_host": (_i, [_vp, _u32, _vp, _u64, _u32, _u32, _u64, _vp, _vp]),
+    "tgx_dupspan_last_times": (_i, [C.POINTER(C.c_char_p), C.POINTER(C.c_float), _i]),
+}
+
 
 class TokenGeeXError(Exception):
     """tokengeex.TokenGeeXError — bindings/python/src/lib.rs:9,33-37; carries the
@@ -353,7 +361,7 @@ def _load() -> C.CDLL:
             "Build it with `python tokengeex_amd/build.py`.")
     _share_torch_hip_runtime()
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SYMBOLS.items()) + list(WORD_SYMBOLS.items()) + list(WORDS_SYMBOLS.items()) + list(PHRASE_SYMBOLS.items()) + list(PATTERN_SYMBOLS.items()) + list(PATTERN64_SYMBOLS.items()) + list(REDACT_SYMBOLS.items()) + list(SHAPE_SYMBOLS.items()) + list(HASHED_SYMBOLS.items()) + list(FIND_SYMBOLS.items()) + list(ALLOW_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(WORD_SYMBOLS.items()) + list(WORDS_SYMBOLS.items()) + list(PHRASE_SYMBOLS.items()) + list(PATTERN_SYMBOLS.items()) + list(PATTERN64_SYMBOLS.items()) + list(REDACT_SYMBOLS.items()) + list(SHAPE_SYMBOLS.items()) + list(HASHED_SYMBOLS.items()) + list(FIND_SYMBOLS.items()) + list(ALLOW_SYMBOLS.items()) + list(DUPSPAN_SYMBOLS.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args
@@ -1108,6 +1116,43 @@ def repeat_last_times() -> dict[str, float]:
     names = (C.c_char_p * 8)()
     ms = (C.c_float * 8)()
     n = lib.tgx_repeat_last_times(names, ms, 8)
+    return {names[i].decode(): float(ms[i]) for i in range(n)}
+
+
+# ---- duplicate spans across rows (include/tgx_dupspans.h; csrc/dupspan.hip, csrc/dupspan.h) ----
+DUPSPAN_N = 3
+DUPSPAN_MASK_DUP = 1
+DUPSPAN_MASK_COVERED = 2
+DUPSPAN_NAMES = ("grams", "dup", "covered")
+DUPSPAN_KEY_BITS = 40   # the Python default: the fastest of 64, 48, 40 and 32 where it was measured (profiles/dupspans/); the result is the same for all
+
+
+def dupspan_check_key_bits(key_bits: int) -> int:
+    """key_bits must be in 1 .. 64, as the device calls check it -> int(key_bits)."""
+    key_bits = int(key_bits)
+    if not 1 <= key_bits <= 64:
+        raise ValueError(f"key_bits {key_bits} is not in 1 .. 64")
+    return key_bits
+
+
+def dup_spans_host(data: np.ndarray, offs: np.ndarray, width: int, key_bits: int = DUPSPAN_KEY_BITS, seed: int = 0):
+    """Host twin of dup_spans (tgx_dup_spans_host: the keys, a stable sort on the masked key, the walk-back rule and the
+    kernel's chunks, coverage window and store / add rule through the same header, no device) over data u8[N] or u32[T]
+    and offsets u64[S+1] in elements -> (table int64[3, S], mask uint8[n_elems])."""
+    data, offs, n = _gram_source(data, offs)
+    table = np.full((DUPSPAN_N, n), -7, np.int64)
+    mask = np.full(data.size, 7, np.uint8)
+    keep = np.zeros(1, np.int64), np.zeros(1, np.uint8)   # (never NULL: both outputs are asked for)
+    check(lib.tgx_dup_spans_host(ptr(data) if data.size else None, data.dtype.itemsize, ptr(offs) if offs.size else None, n, int(width),
+                                 int(key_bits), int(seed) & (2**64 - 1), ptr(table if n else keep[0]), ptr(mask if mask.size else keep[1])))
+    return table, mask
+
+
+def dupspan_last_times() -> dict[str, float]:
+    """Device time in ms of each stage of the calling thread's last dup_spans call (tgx_dupspan_last_times)."""
+    names = (C.c_char_p * 8)()
+    ms = (C.c_float * 8)()
+    n = lib.tgx_dupspan_last_times(names, ms, 8)
     return {names[i].decode(): float(ms[i]) for i in range(n)}
 
 
@@ -2168,6 +2213,14 @@ class NativeResult:
         (either may be 0; tgx_result_repeat_stats_device)."""
         check(lib.tgx_result_repeat_stats_device(self._h, int(width), int(seed) & (2**64 - 1), 0, stream or None, d_stats or None, d_mask or None))
 
+    def dup_spans(self, width: int, key_bits: int = DUPSPAN_KEY_BITS, seed: int = 0, d_table: int = 0, d_mask: int = 0, *, stream: int = 0) -> None:
+        """Per row its n-grams of `width` ids, those whose ids occurred earlier in the result (in any row: verified
+        against the ids, not by key) and the ids inside one, as int64[3, S], and per id whether such a duplicate begins
+        there (bit 0) or covers it (bit 1), as u8[T], into caller-owned device memory (either may be 0;
+        tgx_result_dup_spans_device)."""
+        check(lib.tgx_result_dup_spans_device(self._h, int(width), int(key_bits), int(seed) & (2**64 - 1), 0, stream or None, d_table or None,
+                                              d_mask or None))
+
     def gram_hits(self, grams: NativeGramSet, d_count: int = 0, d_mask: int = 0, *, stream: int = 0) -> None:
         """Per row the n-grams whose key is in `grams`, as int64[S], and per id whether the n-gram that begins there is
         one, as u8[T], into caller-owned device memory (raw integer pointers, either may be 0;
@@ -2459,6 +2512,14 @@ class NativeCorpus:
         repeat (bit 0) or a member of a class of two or more (bit 1) begins there, as u8[N], into caller-owned device
         memory (either may be 0; tgx_corpus_repeat_stats_device).  This corpus is only read."""
         check(lib.tgx_corpus_repeat_stats_device(self._h, int(width), int(seed) & (2**64 - 1), 0, stream or None, d_stats or None, d_mask or None))
+
+    def dup_spans(self, width: int, key_bits: int = DUPSPAN_KEY_BITS, seed: int = 0, d_table: int = 0, d_mask: int = 0, *, stream: int = 0) -> None:
+        """Per row its n-grams of `width` bytes, those whose bytes occurred earlier in the corpus (in any row: verified
+        against the bytes, not by key) and the bytes inside one, as int64[3, S], and per byte whether such a duplicate
+        begins there (bit 0) or covers it (bit 1), as u8[N], into caller-owned device memory (either may be 0;
+        tgx_corpus_dup_spans_device).  This corpus is only read."""
+        check(lib.tgx_corpus_dup_spans_device(self._h, int(width), int(key_bits), int(seed) & (2**64 - 1), 0, stream or None, d_table or None,
+                                              d_mask or None))
 
     def text_stats(self, d_stats: int = 0, d_line_start: int = 0, line_limit: int = 1000, unit: str = "char", *, stream: int = 0) -> None:
         """Per sample the eleven statistics of include/tgx.h as int64[11, S] (TEXTSTAT_NAMES; lengths in `unit`, "char" or

@@ -1,8 +1,8 @@
 // The *_host twins of the result-side device entry points (include/tgx.h): tgx_layout_pad_host, tgx_layout_pack_host,
-// tgx_layout_windows_host, tgx_assemble_host, tgx_fim_host, tgx_select_host, tgx_select_text_host, tgx_shuffled_rows_host, tgx_first_equal_host, tgx_minhash_host, tgx_minhash_bands_host, tgx_minhash_near_first_host, tgx_gram_keys_host, tgx_gram_hits_host, tgx_gram_contains_host, tgx_repeat_stats_host, tgx_text_stats_host, tgx_lines_host, tgx_word_stats_host (include/tgx_words.h), tgx_words_host and tgx_word_key (include/tgx_word_ids.h), tgx_phrase_hits_host (include/tgx_phrases.h), tgx_dfa_hits_host (include/tgx_patterns.h), tgx_dfa64_hits_host (include/tgx_patterns64.h), tgx_dfa_cover_host and tgx_redact_host (include/tgx_redact.h), tgx_shape_hits_host and tgx_shape_cover_host (include/tgx_shapes.h), tgx_hashed_counts_host and tgx_hashed_scores_host (include/tgx_hashed.h), tgx_decode_rows_host, tgx_spans_host, tgx_window_spans_host, tgx_front_host,
+// tgx_layout_windows_host, tgx_assemble_host, tgx_fim_host, tgx_select_host, tgx_select_text_host, tgx_shuffled_rows_host, tgx_first_equal_host, tgx_minhash_host, tgx_minhash_bands_host, tgx_minhash_near_first_host, tgx_gram_keys_host, tgx_gram_hits_host, tgx_gram_contains_host, tgx_repeat_stats_host, tgx_dup_spans_host (include/tgx_dupspans.h), tgx_text_stats_host, tgx_lines_host, tgx_word_stats_host (include/tgx_words.h), tgx_words_host and tgx_word_key (include/tgx_word_ids.h), tgx_phrase_hits_host (include/tgx_phrases.h), tgx_dfa_hits_host (include/tgx_patterns.h), tgx_dfa64_hits_host (include/tgx_patterns64.h), tgx_dfa_cover_host and tgx_redact_host (include/tgx_redact.h), tgx_shape_hits_host and tgx_shape_cover_host (include/tgx_shapes.h), tgx_hashed_counts_host and tgx_hashed_scores_host (include/tgx_hashed.h), tgx_decode_rows_host, tgx_spans_host, tgx_window_spans_host, tgx_front_host,
 // tgx_normalize_host and tgx_lattice_stats_host, and the
 // argument checks they share with the device entry points of tgx_api.cpp.  A twin goes through the same index arithmetic as its kernels (layout.h, assemble.h,
-// fim.h, select.h, dedup.h, minhash.h, gram.h, hashed.h, repeat.h, textstat.h, wordstat.h, words.h, dfa.h, dfa64.h, find.h, cover.h, redact.h, shape.h, decode.h, spans.h, front.h, norm.h) on host memory.  Nothing in this file calls a HIP function, so it builds and runs without the
+// fim.h, select.h, dedup.h, minhash.h, gram.h, hashed.h, repeat.h, dupspan.h, textstat.h, wordstat.h, words.h, dfa.h, dfa64.h, find.h, cover.h, redact.h, shape.h, decode.h, spans.h, front.h, norm.h) on host memory.  Nothing in this file calls a HIP function, so it builds and runs without the
 // handles, the pool or a device.
 #define TGX_HOST_ONLY  // tile_fill.h: the host loop, no kernel side
 #include <algorithm>
@@ -20,6 +20,7 @@
 #include "dedup.h"
 #include "dfa.h"
 #include "dfa64.h"
+#include "dupspan.h"
 #include "fim.h"
 #include "find.h"
 #include "front.h"
@@ -39,6 +40,7 @@
 #include "words.h"
 #include "wordstat.h"
 #include "../../include/tgx_allow.h"
+#include "../../include/tgx_dupspans.h"
 #include "../../include/tgx_find.h"
 #include "../../include/tgx_hashed.h"
 #include "../../include/tgx_patterns.h"
@@ -1262,6 +1264,98 @@ tgx_status tgx_repeat_stats_host(const void* data, uint32_t elem_bytes, const ui
                     stats[which[q] * S + i] = (int64_t)v;
                 else if (tgx::gram_adds(v))
                     stats[which[q] * S + i] += (int64_t)v;
+            }
+            a = b + 1;
+        }
+    }
+    return TGX_OK;
+}
+
+// ---- duplicate spans across rows ----------------------------------------------------------------
+
+tgx_status tgx_dup_spans_host(const void* data, uint32_t elem_bytes, const uint64_t* offs, uint64_t n_rows, uint32_t width, uint32_t key_bits,
+                              uint64_t seed, int64_t* table, uint8_t* mask) {
+    const char* who = "tgx_dup_spans_host";
+    const tgx_status st = gram_check_source_host(who, data, elem_bytes, offs, n_rows, width);
+    if (st != TGX_OK) return st;
+    if (key_bits < 1 || key_bits > 64) return fail(TGX_ERR_INVALID, "%s: key_bits %u is not in 1 .. 64", who, key_bits);
+    if (!table && !mask) return fail(TGX_ERR_INVALID, "%s: table and mask are both NULL", who);
+    const uint64_t S = n_rows;
+    if (S == 0) return TGX_OK;
+    const uint64_t N = offs[S];
+    if (N > tgx::kDupspanMaxElems) return fail(TGX_ERR_UNSUPPORTED, "%s: 2^32-1 elements or more", who);
+    // the pre-sets
+    std::vector<uint8_t> own_flag(mask ? 0 : N);
+    uint8_t* flag = mask ? mask : own_flag.data();
+    std::fill(flag, flag + N, 0);
+    std::vector<uint64_t> g_offs(S + 1, 0);
+    for (uint64_t k = 0; k < S; k++) {
+        const uint64_t grams = tgx::gram_row_count(offs, S, width, k);
+        g_offs[k + 1] = g_offs[k] + grams;
+        if (!table) continue;
+        table[tgx::kDsGrams * S + k] = (int64_t)grams;
+        table[tgx::kDsDup * S + k] = table[tgx::kDsCovered * S + k] = 0;
+    }
+    // every valid gram's key and position to its slot, as dupspan_keys_kernel; then the stable sort on the masked key
+    const uint64_t G = g_offs[S], key_mask = tgx::dupspan_key_mask(key_bits);
+    const uint8_t* bytes = static_cast<const uint8_t*>(data);
+    std::vector<uint64_t> keys_a(G), keys(G);
+    std::vector<uint32_t> pos_a(G), pos(G), order(G);
+    gram_walk_host(bytes, elem_bytes, offs, S, width, seed, [&](uint64_t, uint64_t e, uint64_t i, bool valid, uint64_t key) {
+        if (!valid) return;
+        const uint64_t slot = g_offs[i] + (e - offs[i]);
+        keys_a[slot] = key;
+        pos_a[slot] = (uint32_t)e;
+    });
+    for (uint64_t t = 0; t < G; t++) order[t] = (uint32_t)t;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return (keys_a[a] & key_mask) < (keys_a[b] & key_mask); });
+    for (uint64_t t = 0; t < G; t++) {
+        keys[t] = keys_a[order[t]];
+        pos[t] = pos_a[order[t]];
+    }
+    // the match, as dupspan_match_kernel: the elements compared, the walk back through the run
+    const size_t gram_bytes = (size_t)width * elem_bytes;
+    for (uint64_t t = 0; t < G; t++) {
+        const uint8_t* mine = bytes + (size_t)pos[t] * elem_bytes;
+        if (!tgx::dupspan_candidate(t, keys[t], t ? keys[t - 1] : 0, key_mask)) continue;
+        const bool dup = tgx::dupspan_walk_back(keys.data(), pos.data(), t, keys[t], key_mask, pos[t - 1],
+                                                [&](uint32_t q) { return std::memcmp(mine, bytes + (size_t)q * elem_bytes, gram_bytes) == 0; });
+        if (dup) flag[pos[t]] = tgx::kDupspanBitDup;
+    }
+    // the cover and the row sums, as dupspan_cover_kernel: its chunks, the window of two chunks, the store / add rule.
+    // The window reads bit 0 alone, so finishing the mask in place as the walk goes changes nothing it reads.
+    uint64_t hi = 0;
+    for (uint64_t c0 = 0; c0 < N; c0 += tgx::kGramChunk) {
+        const uint64_t c_last = tgx::tile_last(c0, tgx::kGramChunk, N);
+        const uint64_t lo = tgx::dedup_find_from(offs, hi, S - 1, c0);
+        hi = tgx::dedup_find_from(offs, lo, S - 1, c_last);
+        const uint32_t n_in = (uint32_t)(c_last - c0) + 1;
+        uint64_t row[tgx::kGramChunk], ballots[2] = {0, 0}, dup_b = 0;
+        for (uint32_t l = 0; l < tgx::kGramChunk; l++) {
+            if (l < n_in) {
+                row[l] = tgx::pack_find_row(offs, 0, lo, hi, c0 + l);
+                if (flag[c0 + l] & tgx::kDupspanBitDup) ballots[0] |= 1ull << l;
+            }
+            if (c0 && (flag[c0 - tgx::kGramChunk + l] & tgx::kDupspanBitDup)) dup_b |= 1ull << l;  // (the chunk before is whole)
+        }
+        for (uint32_t l = 0; l < n_in; l++) {
+            if (!tgx::repeat_covered(dup_b, ballots[0], l, c0 + l, offs[row[l]], width)) continue;
+            ballots[1] |= 1ull << l;
+            if (mask) mask[c0 + l] |= tgx::kDupspanBitCovered;
+        }
+        if (!table) continue;
+        const uint32_t which[2] = {tgx::kDsDup, tgx::kDsCovered};
+        for (uint32_t a = 0; a < n_in;) {  // the stretch [a, b] of one row
+            uint32_t b = a;
+            while (b + 1 < n_in && row[b + 1] == row[a]) b++;
+            const uint64_t i = row[a], stretch = ((b >= 63 ? 0ull : (1ull << (b + 1))) - 1) & ~((1ull << a) - 1);  // lanes [a, b]
+            const bool inside = tgx::gram_row_inside(offs, i, c0);
+            for (uint32_t q = 0; q < 2; q++) {
+                const uint64_t v = (uint64_t)__builtin_popcountll(ballots[q] & stretch);
+                if (inside)
+                    table[which[q] * S + i] = (int64_t)v;
+                else if (tgx::gram_adds(v))
+                    table[which[q] * S + i] += (int64_t)v;
             }
             a = b + 1;
         }

@@ -1032,6 +1032,74 @@ def repetition_rows(obj, top=GOPHER_TOP, dup=GOPHER_DUP, literal: bool = False, 
     return repetition_keep(stats, top, dup, literal).nonzero().reshape(-1)
 
 
+# ---- duplicate spans across rows, verified against the elements (csrc/dupspan.hip) -------------------------------------------
+
+class DupSpans:
+    """What dup_spans returns: `table`, [3, S] torch.int64 on the source's device, and a [S] view of it per statistic
+    (grams, dup, covered: include/tgx_dupspans.h); `elems`, [S] torch.int64, the rows' lengths in elements (ids or
+    bytes); `width`; `mask`, the [n_elems] uint8 tensor (bit 0: a duplicate n-gram begins here, bit 1: the element lies
+    inside one), or None when it was not asked for."""
+
+    def __init__(self, table, elems, width: int, mask=None):
+        self.table, self.elems, self.width, self.mask = table, elems, int(width), mask
+        for k, name in enumerate(_lib.DUPSPAN_NAMES):
+            setattr(self, name, table[k])
+
+    @property
+    def covered_frac(self):
+        """[S] float64: covered / max(elems, 1), the share of the row's elements inside an n-gram seen earlier."""
+        import torch
+        return self.covered.to(torch.float64) / self.elems.clamp(min=1).to(torch.float64)
+
+
+def dup_spans(obj, width: int, *, key_bits: int = _lib.DUPSPAN_KEY_BITS, seed: int = 0, return_mask: bool = False, elems=None) -> DupSpans:
+    """-> a DupSpans of obj's rows (a NativeResult, so word_rows too: n-grams of `width` ids; a NativeCorpus: of `width`
+    bytes), computed on its device and queued on torch's current stream: per row the n-grams, those whose elements
+    occurred EARLIER IN THE SOURCE, in any row (the ExactSubstr question of Lee et al. 2021), and the elements inside
+    one.  Equality is exact: the 64-bit key only brings candidates together and every match is verified against the
+    elements.  The first occurrence in row order is never a duplicate, so `select` decides which copy survives.
+    key_bits (1 .. 64) is a speed knob, the bits of the key that are sorted on; the result is the same for every value,
+    and the default, 40, was the fastest of 64, 48, 40 and 32 on 256 MiB of text and on its encode (profiles/dupspans/).
+    Values far below log2 of the number of n-grams are for tests of small sources only: different n-grams then share runs,
+    a slot of such a run costs up to the run's length, and the match kernel runs for a very long time.
+    A row shorter than `width` owns no n-gram.  elems: the rows' lengths if the caller has them."""
+    import torch
+    dev = _device_of(torch, obj)
+    width = _lib.repeat_check_width(width, _elem_bytes(obj))  # (raises before anything is allocated)
+    key_bits = _lib.dupspan_check_key_bits(key_bits)
+    S = obj.num_samples
+    n_elems = obj.num_tokens if isinstance(obj, _lib.NativeResult) else obj.num_bytes
+    table = torch.empty((_lib.DUPSPAN_N, S), dtype=torch.int64, device=dev)
+    mask = torch.empty((n_elems,), dtype=torch.uint8, device=dev) if return_mask else None
+    spare = torch.empty(1, dtype=torch.int64, device=dev)  # (no row: the pointer still says that the table is asked for)
+    obj.dup_spans(width, key_bits, seed, (table if S else spare).data_ptr(), mask.data_ptr() if return_mask and n_elems else 0,
+                  stream=torch.cuda.current_stream(dev).cuda_stream)
+    return DupSpans(table, _row_elems(obj) if elems is None else elems, width, mask)
+
+
+def span_keep(covered, elems, max_frac: float):
+    """The keep rule of span_rows alone, on tensors of any device -> [S] bool: covered <= max_frac · elems, compared
+    without a division, so an empty row is kept."""
+    import torch
+    return covered.to(torch.float64) <= float(max_frac) * elems.to(torch.float64)
+
+
+def span_rows(obj, width: int, max_frac: float, *, key_bits: int = _lib.DUPSPAN_KEY_BITS, seed: int = 0):
+    """-> torch.int64 indices, ascending, of the rows of which at most the share max_frac lies inside n-grams of `width`
+    elements seen earlier in the source: what `select` takes to drop the others (of a result and, with the same
+    indices, of its corpus).  An empty row is kept."""
+    s = dup_spans(obj, width, key_bits=key_bits, seed=seed)
+    return span_keep(s.covered, s.elems, max_frac).nonzero().reshape(-1)
+
+
+def dedup_spans(corpus: "_lib.NativeCorpus", width: int = 50, **kw) -> "_lib.NativeCorpus":
+    """-> a new resident corpus of the same rows with every byte deleted that lies inside an n-gram of `width` bytes seen
+    earlier in the corpus: dup_spans' mask and `redact` with an empty replacement.  The first copy of a span stays.  The
+    corpus is only read; re-encode the new one rather than deleting ids of a result."""
+    mask = dup_spans(corpus, width, return_mask=True, **kw).mask
+    return redact(corpus, (mask >> 1) & 1, [b""])
+
+
 def line_dup_counts(line_row, cls, line_bytes, n_rows: int):
     """The duplicate-line rule alone, on tensors of any device: line_row [n_lines] int64 (ascending: the row of every
     line), cls [n_lines] int64 (first_equal of the lines), line_bytes [n_lines] int64 -> (dup_lines, dup_bytes), both
