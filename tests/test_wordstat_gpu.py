@@ -15,6 +15,7 @@ from tokengeex_amd import _lib, synth
 
 import dedup_checker as dc
 import dirty_runs
+import side_runs
 import wordstat_cases
 import wordstat_checker as ck
 from wordstat_cases import COMBOS, table_for
@@ -26,10 +27,8 @@ ALL = wordstat_cases.NAMES + ("past_cap",)
 @functools.lru_cache(maxsize=None)
 def _case(name):
     """a case with the checker's answers: computed once, never changed"""
-    c = wordstat_cases.past_cap_case() if name == "past_cap" else wordstat_cases.case(name)
-    c["want"] = {combo: ck.stats_of(c["text"], c["offs"], combo[0], table_for(combo[2], combo[3]), combo[1], combo[2]) for combo in COMBOS}
-    for a in (c["text"], c["offs"]) + tuple(x for pair in c["want"].values() for x in pair):
-        a.setflags(write=False)
+    c = dict(side_runs.wordstat_case(name))
+    c["want"] = {combo: side_runs.wordstat_want(name, combo) for combo in COMBOS}
     return c
 
 
@@ -140,42 +139,12 @@ def test_bad_arguments_are_refused_before_anything_is_queued():
 
 # ---- filled pool memory ---------------------------------------------------------------------------------------------------
 
-FILL_CASES = ("short_rows", "edges_chunk", "edges_tile", "edges_two_tiles", "stop_words", "bullets", "ellipses", "past_cap")
-FILL_COMBO = (5, "char", True, True)
-
-
-def _fill_entry(with_marks):
-    """a dirty_runs.Entry of the word statistics, built here and not registered: the registry holds include/tgx.h's
-    functions, and this call is declared in include/tgx_words.h"""
-
-    def run(ctx):
-        out = {}
-        for name in FILL_CASES:
-            c = _case(name)
-            corpus = tgx.NativeCorpus(c["text"], c["offs"])
-            S, N = len(c["offs"]) - 1, c["text"].size
-            table, marks = ctx.full((ck.N, S), "int64", -7), ctx.full((max(N, 1),), "uint8", 7)
-            corpus.word_stats(table.data_ptr(), marks.data_ptr() if with_marks and N else 0, FILL_COMBO[0], table_for(True, True), FILL_COMBO[1], FILL_COMBO[2],
-                              stream=ctx.stream)
-            out[f"{name}/table"], out[f"{name}/marks"] = _np(table), _np(marks)[:N]
-            corpus.free()
-        return out
-
-    def check(out):
-        for name in FILL_CASES:
-            want, want_marks = _case(name)["want"][FILL_COMBO]
-            assert np.array_equal(out[f"{name}/table"], want), (name, "table")
-            assert np.array_equal(out[f"{name}/marks"], want_marks) if with_marks else (out[f"{name}/marks"] == 7).all(), (name, "marks")
-
-    return dirty_runs.Entry(f"word_stats_{'with' if with_marks else 'without'}_marks", ("tgx_corpus_word_stats_device",), run, check, {}, True)
-
-
 @pytest.mark.parametrize("with_marks", [True, False])
 def test_on_filled_pool_memory(monkeypatch, with_marks):
     """test_pool_fill_gpu.py's three fills: every pooled buffer of the call (the summaries, the carries, the scan's room,
     the stop table) holds 0, 255 or 1 before its owner sees it, and the outputs are the same bits under all three"""
     import test_pool_fill_gpu as pf
-    e = _fill_entry(with_marks)
+    e = side_runs.ENTRIES[f"word_stats_{'with' if with_marks else 'without'}_marks"]
     ctx = dirty_runs.Ctx()
     tgx.pool_trim()
     runs = {}
